@@ -44,6 +44,10 @@ the per-kernel probe (150 untimed + K eager steps with HIP events around every k
 leg + SpMM batch sweep, the other workloads, the data-parallel shard profile, and LAST the headline: W untimed warmup
 steps, then exactly K timed steps between barrier + synchronize pairs.  A fresh process needs ~30 steps to reach the
 clocks the chip sustains; with the headline last its timed steps are sustained-clock steps at any K / W.
+
+--dump-outputs DIR: after the timed steps, rank 0 writes what the last of them computed as DIR/<name>.npy (float32, the
+loss float64; see `step_outputs`).  Inputs and initial weights are seeded and the kernels sum in a fixed order, so runs
+with the same arguments give the same arrays: two builds can be compared output for output.
 """
 from __future__ import annotations
 
@@ -66,6 +70,7 @@ import torch.distributed as dist
 EPOCH_GRAPHS = 160  # BASELINE.json configs[3]
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: 8 TB/s HBM3E
 LDS_PEAK_GBS = 256 * 256 * 2.4  # MI355X_MICROARCH.md, LDS: 256 B/clk/CU x 256 CUs x 2.4 GHz max clock = 157,286 GB/s
+DUMP_LIMIT_BYTES = 64 << 20  # --dump-outputs: at most this much in all
 
 
 def parse():
@@ -90,7 +95,13 @@ def parse():
     ap.add_argument("--no-other-workloads", action="store_true", help="skip the d=8 / d=12 / G(n,p) steps")
     ap.add_argument("--no-dp-profile", action="store_true", help="skip the single-rank data-parallel shard profile")
     ap.add_argument("--no-spmm-sweep", action="store_true", help="skip the SpMM batch-size sweep")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last of them computed (loss, per-graph losses, "
+                         "probabilities, partition, parameters and gradient) as DIR/<name>.npy (rank 0)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def regular_graph(n, d, seed):
@@ -456,6 +467,10 @@ def main():
     # host memory); forward/backward and Adam around the eager all-reduce on N GPUs
     elapsed, last_loss = timed(trainer, dataset, args.warmup, args.steps)
     note("headline timed region done")
+    # read back before anything else steps the model (the strong-scaling region below trains it further)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, step_outputs(trainer, last_loss))
+        note(f"outputs of the last timed step written to {args.dump_outputs}")
 
     # N > 1, weak run: the same job on the strong split (160 graphs in total, 160 / N per rank)
     strong = None
@@ -553,6 +568,47 @@ def main():
     print(json.dumps(out), flush=True)
     if dp:
         dist.destroy_process_group()
+
+
+def step_outputs(trainer, loss):
+    """What the last timed step computed, as host arrays: the loss `epoch()` returned, every graph's loss of that
+    epoch, the probabilities and partition of its last optimizer step's batch, and the parameters and gradient that
+    step left in the model (logical shapes)."""
+    eng, last = trainer.eng, trainer._batches[-1]
+    if trainer.dp or trainer._dropout() > 0.0:   # these steps keep the per-graph losses in the device slots
+        slots = trainer._loss_slots.cpu().numpy()
+    else:                                        # single-GPU steps land them in the pinned host buffer
+        slots = trainer._loss_host_np
+    out = {
+        "loss": np.array([loss], np.float64),
+        "graph_losses": np.concatenate([slots[i, :b.B] for i, b in enumerate(trainer._batches)]).astype(np.float32),
+        "probabilities": trainer._out[0][:last.R].cpu().numpy(),
+        "partition": trainer._out[1][:last.R].cpu().numpy().astype(np.float32),
+    }
+    for prefix, buf in (("param", eng.flat), ("grad", eng.grad)):
+        for k, v in eng.views(buf).items():
+            out[f"{prefix}.{k}"] = v.contiguous().cpu().numpy()
+    return out
+
+
+def dump_outputs(path, arrays):
+    """Write every array as `path/<name>.npy`.  While all of them fit DUMP_LIMIT_BYTES they are written whole; past
+    that, an array larger than an equal share of the limit is replaced by a fixed, seeded sample of its rows, whose
+    indices go to `<name>.rows.npy`."""
+    os.makedirs(path, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(v) for k, v in arrays.items()}
+    for v in arrays.values():
+        assert v.dtype in (np.float32, np.float64), v.dtype
+    share = (DUMP_LIMIT_BYTES - 4096 * len(arrays)) // len(arrays)   # (npy headers)
+    fits = sum(v.nbytes for v in arrays.values()) <= DUMP_LIMIT_BYTES - 256 * len(arrays)
+    for name, v in arrays.items():
+        if not fits and v.nbytes > share:
+            row_bytes = v.nbytes // v.shape[0]
+            k = max(1, share // (row_bytes + 8))
+            rows = np.sort(np.random.default_rng(0).choice(v.shape[0], size=k, replace=False))
+            np.save(os.path.join(path, f"{name}.rows.npy"), rows.astype(np.float64))
+            v = v[rows]
+        np.save(os.path.join(path, f"{name}.npy"), v)
 
 
 def lib_groups(pkg, batch, F):

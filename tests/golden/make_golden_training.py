@@ -139,6 +139,22 @@ def loss_cases():
     return out
 
 
+# dL/dP is the autograd of the S S^T GEMM: its last bit follows the accumulation order of the code path MKL picks for
+# the CPU at start-up (AVX-512 on recent Intel parts, SSE4.2 on AMD parts, AVX2 between).  Each path is recorded from
+# a child process that MKL_ENABLE_INSTRUCTIONS caps at it (run on an AVX-512 machine so that every path is reachable).
+MKL_PATHS = ("AVX512", "AVX2", "SSE4_2")
+
+
+def loss_grads_by_mkl_path():
+    import subprocess
+    per_path = {}
+    for isa in MKL_PATHS:
+        res = subprocess.run([sys.executable, os.path.abspath(__file__), "--loss-grads"], capture_output=True, text=True,
+                             check=True, env=dict(os.environ, MKL_ENABLE_INSTRUCTIONS=isa))
+        per_path[isa] = json.loads(res.stdout.splitlines()[-1])
+    return per_path
+
+
 def extend_cases():
     m = torch.arange(12, dtype=torch.float32).reshape(3, 4)[:, :3] + 1
     a = RT.extend_matrix_torch(m, 7)
@@ -382,10 +398,18 @@ def main():
             }
         finally:
             os.chdir(cwd)
+    per_path = loss_grads_by_mkl_path()
+    for i, case in enumerate(data["loss"]):
+        case["dL_dP_by_mkl_path"] = {isa: grads[i] for isa, grads in per_path.items()}
     path = os.path.join(HERE, "training.json")
     json.dump(data, open(path, "w"))
     print("wrote", path, os.path.getsize(path), "bytes")
 
 
 if __name__ == "__main__":
-    main()
+    if sys.argv[1:] == ["--loss-grads"]:   # (child of loss_grads_by_mkl_path)
+        with tempfile.TemporaryDirectory() as tmp:
+            os.chdir(tmp)
+            print(json.dumps([c["dL_dP"] for c in loss_cases()]))
+    else:
+        main()

@@ -1068,6 +1068,42 @@ def test_bench_single_rank_over_rccl(pkg):
     assert d["last_loss"] == s["last_loss"]          # same six graphs, same six steps, integer-valued loss
 
 
+def test_bench_dump_outputs_of_the_last_timed_step(pkg, tmp_path):
+    """`bench.py --dump-outputs DIR` writes what the last timed step computed.  With every other region off, W untimed
+    + K timed steps are all the model sees: `--warmup 1 --steps 3` and `--warmup 2 --steps 2` start from the same
+    seeded graphs and weights and take four steps each, so their arrays are equal bit for bit (which also pins that
+    the step counts are exact and the run is reproducible)."""
+    import json, subprocess, sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
+    dumps, lines = {}, {}
+    for w, k in ((1, 3), (2, 2)):
+        d = tmp_path / f"w{w}k{k}"
+        out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", str(k),
+                              "--warmup", str(w), "--graphs-per-gpu", "6", "--no-cpu-baseline", "--no-sequential",
+                              "--no-probe", "--dump-outputs", str(d)], capture_output=True, text=True, timeout=400, env=env)
+        assert out.returncode == 0, out.stderr[-3000:]
+        (line,) = [l for l in out.stdout.strip().splitlines() if l.startswith("{")]
+        lines[k] = json.loads(line)
+        assert lines[k]["steps"] == k and lines[k]["warmup"] == w
+        dumps[k] = {f[:-4]: np.load(d / f) for f in sorted(os.listdir(d))}
+        assert sum(os.path.getsize(d / f) for f in os.listdir(d)) <= 64 << 20
+    a, b = dumps[3], dumps[2]
+    names = {"loss", "graph_losses", "probabilities", "partition"} | {
+        f"{p}.{k}" for p in ("param", "grad") for k in pkg.engine.PARAM_ORDER}
+    assert set(a) == names
+    for k, v in a.items():
+        assert v.dtype == (np.float64 if k == "loss" else np.float32), k
+        assert np.array_equal(v, b[k]), k
+    assert a["loss"][0] == lines[3]["last_loss"] == float(a["graph_losses"].sum(dtype=np.float32))
+    assert a["graph_losses"].shape == (6,) and np.all(a["graph_losses"] < 0)
+    P, S = a["probabilities"], a["partition"]
+    assert P.shape == (6000, 3) and S.shape == (6000,) and np.abs(P.sum(1) - 1).max() < 1e-5
+    assert set(np.unique(S)) <= {0.0, 1.0, 2.0}
+    assert a["param.conv1.weight"].shape == a["grad.conv1.weight"].shape == (1000, 500)
+    assert a["param.conv2.weight"].shape == (500, 3) and a["param.conv2.bias"].shape == (3,)
+
+
 def _slab_of(W1: np.ndarray) -> np.ndarray:
     """gmc_model.W1_slab: [ceil(F/16)][N][16], pad columns zero."""
     N, F = W1.shape

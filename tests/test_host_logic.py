@@ -291,6 +291,40 @@ def test_bench_helpers_fingerprint_and_graph_generation(monkeypatch, tmp_path):
     assert [sorted(g.edges()) for g in serial] == [sorted(g.edges()) for g in forked]
 
 
+def test_bench_dump_outputs_writes_whole_arrays_or_a_seeded_sample_within_the_limit(monkeypatch, tmp_path):
+    """`bench.dump_outputs` (--dump-outputs DIR): float arrays as DIR/<name>.npy, whole while all fit the limit; past
+    it, the arrays over an equal share of it become a fixed seeded sample of their rows (indices in <name>.rows.npy)
+    and the directory stays within the limit.  `--steps 0` is refused before anything runs."""
+    import importlib, subprocess, sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    sys.path.insert(0, root)
+    bench = importlib.import_module("bench")
+    rng = np.random.RandomState(0)
+    arrays = {"loss": np.array([-3.5]), "big": rng.rand(4000, 3).astype(np.float32),
+              "w": rng.rand(50, 20).astype(np.float32)}
+    bench.dump_outputs(str(tmp_path / "whole"), arrays)
+    assert sorted(os.listdir(tmp_path / "whole")) == ["big.npy", "loss.npy", "w.npy"]
+    for k, v in arrays.items():
+        got = np.load(tmp_path / "whole" / f"{k}.npy")
+        assert got.dtype == v.dtype and np.array_equal(got, v)
+    limit = 40000
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", limit)
+    for run in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / run), arrays)
+        assert sum(os.path.getsize(tmp_path / run / f) for f in os.listdir(tmp_path / run)) <= limit
+    assert sorted(os.listdir(tmp_path / "a")) == ["big.npy", "big.rows.npy", "loss.npy", "w.npy"]
+    rows = np.load(tmp_path / "a" / "big.rows.npy")
+    assert rows.dtype == np.float64 and 0 < rows.size < 4000 and np.all(np.diff(rows) > 0)
+    assert np.array_equal(np.load(tmp_path / "a" / "big.npy"), arrays["big"][rows.astype(np.int64)])
+    for f in os.listdir(tmp_path / "a"):
+        assert np.array_equal(np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f))   # the sample is fixed
+    with pytest.raises(AssertionError):
+        bench.dump_outputs(str(tmp_path / "ints"), {"s": np.arange(3)})
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "0"],
+                         capture_output=True, text=True, timeout=300)
+    assert out.returncode == 2 and "--steps must be at least 1" in out.stderr and out.stdout.strip() == ""
+
+
 def test_sampler_semantics_are_numpy_version_independent(built, monkeypatch):
     """assign_partitions (TestingNeuralNetwork.py:18-46): host form and oracle use the pinned NumPy 1.x
     arithmetic (float64 running sum and compare) whatever NumPy is installed; on draws one ulp either side of
