@@ -35,6 +35,10 @@ size_t gmc_dw1_scratch_floats(const gmc_batch *b, int N, int F, bool lds);
 int gmc_dw1_launch(const gmc_batch *, const float *, long, float *, float *, int, int, bool, hipStream_t);
 bool gmc_lds_fits(const gmc_batch *b);
 int gmc_lds_groups(const gmc_batch *b, int F);
+int gmc_fwd1_flavour(const gmc_batch *b, int F);
+int gmc_bwd1_flavour(const gmc_batch *b, int F, bool head);
+int gmc_spmm_lds_flavour(const gmc_batch *b, int F, int shared_src, int use_vals, bool epi);
+int gmc_dw1_lds_flavour(const gmc_batch *b, int F);
 int gmc_spmm_lds_launch(const gmc_batch *, const float *, long, int, int, int, const float *, const float *, int,
                         float *, long, int, int, const float *, float *, int, hipStream_t);
 int gmc_dropout_launch(float *, long, int, int, long, float, unsigned long long, hipStream_t);
@@ -223,7 +227,7 @@ int backward_body(const gmc_batch *b, const gmc_model *m, const Workspace &w, fl
 // ---- timing probe -------------------------------------------------------------------
 #include <vector>
 namespace {
-struct ProbeRec { int tag; hipEvent_t a, b; };
+struct ProbeRec { int tag; int flv; hipEvent_t a, b; };
 struct ProbeState {
     bool on = false;
     std::vector<ProbeRec> pool;
@@ -237,6 +241,7 @@ void gmc_probe_mark(int tag, bool begin, hipStream_t st) {
         if (g_probe.used >= g_probe.pool.size()) return;  // capacity exhausted: stop recording
         ProbeRec &r = g_probe.pool[g_probe.used];
         r.tag = tag;
+        r.flv = 0;
         (void)hipEventRecord(r.a, st);
     } else {
         if (g_probe.used >= g_probe.pool.size()) return;
@@ -247,10 +252,14 @@ void gmc_probe_mark(int tag, bool begin, hipStream_t st) {
     }
 }
 
+void gmc_probe_flavour(int word) {
+    if (g_probe.on && g_probe.used < g_probe.pool.size()) g_probe.pool[g_probe.used].flv = word;   // (the open record)
+}
+
 extern "C" int gmc_probe_begin(int32_t capacity) {
     if (capacity < 0) return GMC_ERR_SHAPE;
     while ((int)g_probe.pool.size() < capacity) {
-        ProbeRec r{-1, nullptr, nullptr};
+        ProbeRec r{-1, 0, nullptr, nullptr};
         hipError_t e = hipEventCreate(&r.a);
         if (e == hipSuccess) e = hipEventCreate(&r.b);
         if (e != hipSuccess) return (int)e;
@@ -274,6 +283,38 @@ extern "C" int gmc_probe_end(int32_t *tags, float *ms, int32_t max) {
         if (tags) tags[i] = g_probe.pool[i].tag;
         if (ms) ms[i] = t;
     }
+    return n;
+}
+
+extern "C" int gmc_probe_flavours(int32_t *words, int32_t max) {
+    if (g_probe.on) return GMC_ERR_UNSUPPORTED;   // (after gmc_probe_end)
+    const int n = (int)g_probe.used;
+    for (int i = 0; i < n && i < max; ++i)
+        if (words) words[i] = g_probe.pool[i].flv;
+    return n;
+}
+
+// the flavour words of a training step's LDS-tiled launches, as forward_body / backward_body / gmc_train_step_f32
+// choose them (the unfused sequence without dropout: with it the aggregation of the forward drops its W2 epilogue,
+// i.e. takes the backward aggregation's word)
+extern "C" int gmc_lds_flavours(const gmc_batch *batch, int32_t F, int32_t one_graph_step, int32_t *words, int32_t max) {
+    if (!batch) return GMC_ERR_NULL;
+    if (batch->abi != GMC_VERSION) return GMC_ERR_ABI;
+    if (F <= 0 || F % 4 || F > 1024 || max < 0 || batch->B < 0) return GMC_ERR_SHAPE;
+    int out[6], n = 0;
+    if (gmc_lds_fits(batch)) {
+        const bool head = one_graph_step && gmc_bwd1_takes_head(batch) && gmc_dw1_chunks(batch->B, true, gmc_lds_slices(batch, F)) == 1;
+        out[n++] = gmc_fwd1_flavour(batch, F);
+        out[n++] = gmc_bwd1_flavour(batch, F, head);
+        if (!gmc_has_overflow(batch)) {   // (overflow lists: the unfused sequence takes the row kernels, see use_lds)
+            out[n++] = gmc_spmm_lds_flavour(batch, F, 1, 1, false);   // W1 gather
+            out[n++] = gmc_spmm_lds_flavour(batch, F, 0, 0, true);    // aggregation + relu + W2 epilogue
+            out[n++] = gmc_spmm_lds_flavour(batch, F, 0, 0, false);   // backward aggregation
+            out[n++] = gmc_dw1_lds_flavour(batch, F);
+        }
+    }
+    for (int i = 0; i < n && i < max; ++i)
+        if (words) words[i] = out[i];
     return n;
 }
 

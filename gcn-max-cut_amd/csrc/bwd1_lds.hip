@@ -697,33 +697,42 @@ __global__ GMC_LDS_BOUNDS void bwd1_lds_kernel(Bwd1Args a) {
     col_epilogue<Q>(cs, red, a.colpart, chunk, s, FS, a.F);
 }
 
-template <int FS, int W>
-int launch_bwd1(const Bwd1Args &a, size_t lds, hipStream_t st) {
-    constexpr int rows_per_pass = kThreads / (FS / 4);
-    const int acc = (a.b.n_max + rows_per_pass - 1) / rows_per_pass;
-    if (acc > 8) return GMC_ERR_UNSUPPORTED;
-    const int grid = a.slices * a.chunks;
-    const bool hv = a.b.ell_vals != nullptr;
-    const int ns = ns_class(W, a.b.ell_slots, !hv);   // live slots: no row of the batch has more neighbours
-    const bool ov = gmc_has_overflow(&a.b);   // hub rows: every slot live, overflow lists walked
+// 8 rows per thread at FS = 16 would need n_max > 1024, which no 16-column tile fits (pick_fs): never instantiated
+template <int FS, int W, bool HV, int NS, bool OV>
+int launch_bwd1_acc(int flv, const Bwd1Args &a, int grid, size_t lds, hipStream_t st) {
     if constexpr (W == 8) {
-        if (a.hZ0) {   // one graph, unit weights, no lists, n <= 1024 (gmc_bwd1_takes_head): the head rides in this launch
-            return ns == 7 ? launch(bwd1_reg_kernel<FS, 4, false, 7, false, true>, grid, lds, st, a)
-                           : launch(bwd1_reg_kernel<FS, 4, false, 8, false, true>, grid, lds, st, a);
-        }
-#define GMC_BWD1(HV, NSK, OV) (acc <= 4 ? launch(bwd1_reg_kernel<FS, 4, HV, NSK, OV>, grid, lds, st, a) \
-                                        : launch(bwd1_reg_kernel<FS, 8, HV, NSK, OV>, grid, lds, st, a))
-        if (ov) return hv ? GMC_ERR_UNSUPPORTED : GMC_BWD1(false, 8, true);   // (weights + overflow: row kernels, see gmc_lds_fits)
-        return hv ? GMC_BWD1(true, 8, false) : ns == 7 ? GMC_BWD1(false, 7, false) : GMC_BWD1(false, 8, false);
+#define GMC_BWD1(AC) launch_flv(flv, flavour_word(GMC_FLV_BWD1_REG, FS, 8, AC, HV, NS, OV), bwd1_reg_kernel<FS, AC, HV, NS, OV>, grid, lds, st, a)
+        if (GMC_FLV_ACC(flv) == 4) return GMC_BWD1(4);
+        if constexpr (FS > 16) return GMC_BWD1(8);
 #undef GMC_BWD1
     } else {
-#define GMC_BWD1(HV, NSK, OV) (acc <= 4 ? launch(bwd1_lds_kernel<FS, W, 4, HV, NSK, OV>, grid, lds, st, a) \
-                                        : launch(bwd1_lds_kernel<FS, W, 8, HV, NSK, OV>, grid, lds, st, a))
-        if (ov) return hv ? GMC_ERR_UNSUPPORTED : GMC_BWD1(false, 16, true);
-        return hv ? GMC_BWD1(true, 16, false) : ns == 10 ? GMC_BWD1(false, 10, false) : ns == 12 ? GMC_BWD1(false, 12, false)
-                  : ns == 14 ? GMC_BWD1(false, 14, false) : GMC_BWD1(false, 16, false);
+#define GMC_BWD1(AC) launch_flv(flv, flavour_word(GMC_FLV_BWD1, FS, W, AC, HV, NS, OV), bwd1_lds_kernel<FS, W, AC, HV, NS, OV>, grid, lds, st, a)
+        if (GMC_FLV_ACC(flv) == 4) return GMC_BWD1(4);
+        if constexpr (FS > 16) return GMC_BWD1(8);
 #undef GMC_BWD1
     }
+    return GMC_ERR_UNSUPPORTED;
+}
+
+template <int FS, int W>
+int launch_bwd1(int flv, const Bwd1Args &a, size_t lds, hipStream_t st) {
+    const int grid = a.slices * a.chunks;
+    const int ns = GMC_FLV_NS(flv);
+    if constexpr (W == 8) {
+        if (GMC_FLV_HEAD(flv)) {   // one graph, unit weights, no lists, n <= 1024 (gmc_bwd1_takes_head): the head rides in this launch
+#define GMC_HEAD(NSK) launch_flv(flv, flavour_word(GMC_FLV_BWD1_REG, FS, 8, 4, false, NSK, false, true), bwd1_reg_kernel<FS, 4, false, NSK, false, true>, grid, lds, st, a)
+            return ns == 7 ? GMC_HEAD(7) : GMC_HEAD(8);
+#undef GMC_HEAD
+        }
+    }
+    if (GMC_FLV_OVF(flv)) return launch_bwd1_acc<FS, W, false, W, true>(flv, a, grid, lds, st);
+    if (GMC_FLV_HAS_VAL(flv)) return launch_bwd1_acc<FS, W, true, W, false>(flv, a, grid, lds, st);
+    if constexpr (W == 8) return ns == 7 ? launch_bwd1_acc<FS, 8, false, 7, false>(flv, a, grid, lds, st)
+                                         : launch_bwd1_acc<FS, 8, false, 8, false>(flv, a, grid, lds, st);
+    else return ns == 10 ? launch_bwd1_acc<FS, 16, false, 10, false>(flv, a, grid, lds, st)
+              : ns == 12 ? launch_bwd1_acc<FS, 16, false, 12, false>(flv, a, grid, lds, st)
+              : ns == 14 ? launch_bwd1_acc<FS, 16, false, 14, false>(flv, a, grid, lds, st)
+                         : launch_bwd1_acc<FS, 16, false, 16, false>(flv, a, grid, lds, st);
 }
 
 }  // namespace
@@ -745,12 +754,30 @@ bool gmc_bwd1_takes_head(const gmc_batch *b) {
 struct gmc_bwd1_head {
     const float *Z0; int zparts; const float *b2; float C; float *P; int *S; float *loss; float *db2part; int *tick;
 };
+// Flavour word of the fused backward for this batch (host only: reads struct fields, never the device arrays);
+// head: the launch computes the one-graph head as well.  0 = gmc_bwd1_lds_launch refuses the batch.
+int gmc_bwd1_flavour(const gmc_batch *b, int F, bool head) {
+    if (!gmc_lds_fits(b) || F <= 0) return 0;
+    if (head && !gmc_bwd1_takes_head(b)) return 0;
+    const int fs = pick_fs(b->n_max, b->ell_width), W = b->ell_width;
+    const int rows_per_pass = kThreads / (fs / 4);
+    if ((b->n_max + rows_per_pass - 1) / rows_per_pass > 8) return 0;
+    const int acc = acc_rows(b->n_max, fs);
+    if (fs == 16 && acc != 4) return 0;
+    const bool ovf = gmc_has_overflow(b), hv = b->ell_vals != nullptr;
+    if (ovf && hv) return 0;   // (weights + overflow: row kernels, see gmc_lds_fits)
+    // live slots: no row of the batch has more neighbours; hub rows: every slot live, overflow lists walked
+    const int ns = ovf ? W : ns_class(W, b->ell_slots, !hv);
+    return flavour_word(W == 8 ? GMC_FLV_BWD1_REG : GMC_FLV_BWD1, fs, W, acc, hv, ns, ovf, head);
+}
+
 int gmc_bwd1_lds_launch(const gmc_batch *b, const float *H, const float *GY2, const float *W2,
                         float *dw1part, float *colpart, int F, int chunks, int graphs_per_chunk,
                         hipStream_t st, const gmc_bwd1_head *head) {
-    if (!gmc_lds_fits(b)) return GMC_ERR_UNSUPPORTED;
-    if (head && (!gmc_bwd1_takes_head(b) || chunks != 1 || !head->Z0 || !head->b2 || !head->P || !head->db2part)) return GMC_ERR_UNSUPPORTED;
-    const int fs = pick_fs(b->n_max, b->ell_width);
+    const int flv = gmc_bwd1_flavour(b, F, head != nullptr);
+    if (!flv) return GMC_ERR_UNSUPPORTED;
+    if (head && (chunks != 1 || !head->Z0 || !head->b2 || !head->P || !head->db2part)) return GMC_ERR_UNSUPPORTED;
+    const int fs = GMC_FLV_FS(flv);
     Bwd1Args a{*b, H, GY2, W2, dw1part, colpart, F, (F + fs - 1) / fs, chunks, graphs_per_chunk, 0, 0,
                head ? head->Z0 : nullptr, head ? head->zparts : 0, head ? head->C : 0.f, head ? head->b2 : nullptr,
                head ? head->P : nullptr, head ? head->S : nullptr, head ? head->loss : nullptr,
@@ -764,16 +791,16 @@ int gmc_bwd1_lds_launch(const gmc_batch *b, const float *H, const float *GY2, co
         lds = kOvfLdsBytes;
     }
     GmcProbeScope probe(GMC_K_BWD1_FUSED, st);
-    if (b->ell_width == 8) {
+    if (GMC_FLV_W(flv) == 8) {
         switch (fs) {
-            case 64: return launch_bwd1<64, 8>(a, lds, st);
-            case 32: return launch_bwd1<32, 8>(a, lds, st);
-            default: return launch_bwd1<16, 8>(a, lds, st);
+            case 64: return launch_bwd1<64, 8>(flv, a, lds, st);
+            case 32: return launch_bwd1<32, 8>(flv, a, lds, st);
+            default: return launch_bwd1<16, 8>(flv, a, lds, st);
         }
     }
     switch (fs) {
-        case 64: return launch_bwd1<64, 16>(a, lds, st);
-        case 32: return launch_bwd1<32, 16>(a, lds, st);
-        default: return launch_bwd1<16, 16>(a, lds, st);
+        case 64: return launch_bwd1<64, 16>(flv, a, lds, st);
+        case 32: return launch_bwd1<32, 16>(flv, a, lds, st);
+        default: return launch_bwd1<16, 16>(flv, a, lds, st);
     }
 }

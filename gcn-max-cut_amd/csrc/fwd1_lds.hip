@@ -328,42 +328,62 @@ __global__ GMC_LDS_BOUNDS void fwd1_lds_kernel(TileArgs a) {
     MARK(3);
 }
 
-template <int FS, int W>
-int launch_fwd1(const TileArgs &a, size_t lds, int grid, hipStream_t st) {
-    constexpr int rows_per_pass = kThreads / (FS / 4);
-    const int acc = (a.b.n_max + rows_per_pass - 1) / rows_per_pass;
-    if (acc > 8) return GMC_ERR_UNSUPPORTED;
-    // live slots (no row of the batch has more neighbours): unit-weight kernels skip the others
-    const int ns = ns_class(W, a.b.ell_slots, !a.use_vals);
-#define GMC_FWD1(AC, HV, NSK, OV) launch(fwd1_lds_kernel<FS, W, AC, HV, NSK, OV>, grid, lds, st, a)
-#define GMC_FWD1_ACC(HV, NSK, OV) (acc <= 4 ? GMC_FWD1(4, HV, NSK, OV) : GMC_FWD1(8, HV, NSK, OV))
-    if (gmc_has_overflow(&a.b)) {   // hub rows: every slot live (weights + overflow: row kernels, see gmc_lds_fits)
-        if (a.use_vals) return GMC_ERR_UNSUPPORTED;
-        return GMC_FWD1_ACC(false, W, true);
-    }
-    if (a.use_vals) return GMC_FWD1_ACC(true, W, false);
-    if constexpr (W == 8) return ns == 7 ? GMC_FWD1_ACC(false, 7, false) : GMC_FWD1_ACC(false, 8, false);
-    else return ns == 10 ? GMC_FWD1_ACC(false, 10, false) : ns == 12 ? GMC_FWD1_ACC(false, 12, false)
-              : ns == 14 ? GMC_FWD1_ACC(false, 14, false) : GMC_FWD1_ACC(false, 16, false);
-#undef GMC_FWD1_ACC
+// 8 rows per thread at FS = 16 would need n_max > 1024, which no 16-column tile fits (pick_fs): never instantiated
+template <int FS, int W, bool HV, int NS, bool OV>
+int launch_fwd1_acc(int flv, const TileArgs &a, size_t lds, int grid, hipStream_t st) {
+#define GMC_FWD1(AC) launch_flv(flv, flavour_word(GMC_FLV_FWD1, FS, W, AC, HV, NS, OV), fwd1_lds_kernel<FS, W, AC, HV, NS, OV>, grid, lds, st, a)
+    if (GMC_FLV_ACC(flv) == 4) return GMC_FWD1(4);
+    if constexpr (FS > 16) return GMC_FWD1(8);
+    return GMC_ERR_UNSUPPORTED;
 #undef GMC_FWD1
 }
 
+template <int FS, int W>
+int launch_fwd1(int flv, const TileArgs &a, size_t lds, int grid, hipStream_t st) {
+    const int ns = GMC_FLV_NS(flv);
+    if (GMC_FLV_OVF(flv)) return launch_fwd1_acc<FS, W, false, W, true>(flv, a, lds, grid, st);
+    if (GMC_FLV_HAS_VAL(flv)) return launch_fwd1_acc<FS, W, true, W, false>(flv, a, lds, grid, st);
+    if constexpr (W == 8) return ns == 7 ? launch_fwd1_acc<FS, 8, false, 7, false>(flv, a, lds, grid, st)
+                                         : launch_fwd1_acc<FS, 8, false, 8, false>(flv, a, lds, grid, st);
+    else return ns == 10 ? launch_fwd1_acc<FS, 16, false, 10, false>(flv, a, lds, grid, st)
+              : ns == 12 ? launch_fwd1_acc<FS, 16, false, 12, false>(flv, a, lds, grid, st)
+              : ns == 14 ? launch_fwd1_acc<FS, 16, false, 14, false>(flv, a, lds, grid, st)
+                         : launch_fwd1_acc<FS, 16, false, 16, false>(flv, a, lds, grid, st);
+}
+
 }  // namespace
+
+// Flavour word of the fused forward for this batch (host only: reads struct fields, never the device arrays);
+// 0 = gmc_fwd1_lds_launch refuses the batch.  Every choice of template arguments is made here.
+int gmc_fwd1_flavour(const gmc_batch *b, int F) {
+    if (!gmc_lds_fits(b) || F <= 0) return 0;
+    const int fs = pick_fs(b->n_max, b->ell_width), W = b->ell_width;
+    const int slices = (F + fs - 1) / fs;
+    // 8-slot tables: the column constants of every slice sit in LDS, 16 B per (padded) column (16-slot tables load
+    // them slice by slice)
+    if (W == 8 && ((size_t)slices * fs > (size_t)kThreads || (size_t)16 * slices * fs > lds_consts(b->n_max, fs, 8)))
+        return 0;
+    const int rows_per_pass = kThreads / (fs / 4);
+    if ((b->n_max + rows_per_pass - 1) / rows_per_pass > 8) return 0;
+    const int acc = acc_rows(b->n_max, fs);
+    if (fs == 16 && acc != 4) return 0;
+    const bool ovf = gmc_has_overflow(b), hv = b->ell_vals != nullptr;
+    if (ovf && hv) return 0;   // hub rows: every slot live (weights + overflow: row kernels, see gmc_lds_fits)
+    // live slots (no row of the batch has more neighbours): unit-weight kernels skip the others
+    const int ns = ovf ? W : ns_class(W, b->ell_slots, !hv);
+    return flavour_word(GMC_FLV_FWD1, fs, W, acc, hv, ns, ovf) | flavour_per(gmc_lds_slices_per_group(b, F));
+}
 
 // fused layer-1 forward: H (slab layout) = relu(dinv o (A @ (dinv o (A_val @ W1[:n]))) + b1) and
 // Zpart[group][r][:] = dinv[r] * (H[r, group's columns] @ W2[group's rows])
 // W1_slab (optional): the [ceil(F/16)][N][16] copy of W1 (gmc_w1_slab_f32); N = rows of W1
 int gmc_fwd1_lds_launch(const gmc_batch *b, const float *W1, const float *b1, const float *W2, float *H,
                         float *Zpart, int F, hipStream_t st, const float *W1_slab, int N) {
-    if (!gmc_lds_fits(b)) return GMC_ERR_UNSUPPORTED;
+    const int flv = gmc_fwd1_flavour(b, F);
+    if (!flv) return GMC_ERR_UNSUPPORTED;
     if (b->B == 0) return GMC_OK;
-    const int fs = pick_fs(b->n_max, b->ell_width);
+    const int fs = GMC_FLV_FS(flv);
     const int slices = (F + fs - 1) / fs, groups = gmc_lds_groups(b, F);
-    // 8-slot tables: the column constants of every slice sit in LDS, 16 B per (padded) column (16-slot tables load
-    // them slice by slice)
-    if (b->ell_width == 8 && ((size_t)slices * fs > (size_t)kThreads || (size_t)16 * slices * fs > lds_consts(b->n_max, fs, 8)))
-        return GMC_ERR_UNSUPPORTED;
     // contiguous ranges of (graph, group) items, one persistent workgroup per CU when there are enough
     const int total = b->B * groups, cus = device_cus();
     const int ipw = (total + cus - 1) / cus, grid = (total + ipw - 1) / ipw;
@@ -371,7 +391,7 @@ int gmc_fwd1_lds_launch(const gmc_batch *b, const float *W1, const float *b1, co
                F, slices, groups, W2, Zpart, ipw, 0, 0, 0, 0};
     if (W1_slab) { a.X = W1_slab; a.x_rs = 16; a.x_slab16 = 1; a.x_rows = N; }
     size_t lds = lds_bytes(b->n_max, b->ell_width, fs);
-    if (gmc_has_overflow(b)) {   // hub rows: all of the CU's LDS, the spare holds the graph's first overflow blocks
+    if (GMC_FLV_OVF(flv)) {   // hub rows: all of the CU's LDS, the spare holds the graph's first overflow blocks
         const size_t own = ovf_own_bytes(0, b->n_max, b->ell_width, fs);
         if (own + ovf_desc_bytes(b->n_max) > kOvfLdsBytes) return GMC_ERR_UNSUPPORTED;   // (gmc_lds_fits says so beforehand)
         a.own_lds = (int)own;
@@ -379,16 +399,16 @@ int gmc_fwd1_lds_launch(const gmc_batch *b, const float *W1, const float *b1, co
         lds = kOvfLdsBytes;
     }
     GmcProbeScope probe(GMC_K_FWD1_FUSED, st);
-    if (b->ell_width == 8) {
+    if (GMC_FLV_W(flv) == 8) {
         switch (fs) {
-            case 64: return launch_fwd1<64, 8>(a, lds, grid, st);
-            case 32: return launch_fwd1<32, 8>(a, lds, grid, st);
-            default: return launch_fwd1<16, 8>(a, lds, grid, st);
+            case 64: return launch_fwd1<64, 8>(flv, a, lds, grid, st);
+            case 32: return launch_fwd1<32, 8>(flv, a, lds, grid, st);
+            default: return launch_fwd1<16, 8>(flv, a, lds, grid, st);
         }
     }
     switch (fs) {
-        case 64: return launch_fwd1<64, 16>(a, lds, grid, st);
-        case 32: return launch_fwd1<32, 16>(a, lds, grid, st);
-        default: return launch_fwd1<16, 16>(a, lds, grid, st);
+        case 64: return launch_fwd1<64, 16>(flv, a, lds, grid, st);
+        case 32: return launch_fwd1<32, 16>(flv, a, lds, grid, st);
+        default: return launch_fwd1<16, 16>(flv, a, lds, grid, st);
     }
 }

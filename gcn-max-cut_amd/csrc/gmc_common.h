@@ -16,6 +16,8 @@
 // Optional per-kernel timing (bench.py): hipEvents recorded around each launch of the fused
 // step on the caller's stream.  Off by default (no events, capture-safe).
 void gmc_probe_mark(int tag, bool begin, hipStream_t st);
+// the flavour word (gcnmaxcut.h, GMC_FLV_*) of the launch the open GmcProbeScope brackets (records without one: 0)
+void gmc_probe_flavour(int word);
 struct GmcProbeScope {
     int tag; hipStream_t st;
     GmcProbeScope(int t, hipStream_t s) : tag(t), st(s) { gmc_probe_mark(tag, true, st); }

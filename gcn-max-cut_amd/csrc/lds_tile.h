@@ -604,6 +604,22 @@ int pick_fs(int n_max, int W) {
     return 0;
 }
 
+// The flavour word (gcnmaxcut.h, GMC_FLV_*) of one instantiation.  Each launcher's host-only `*_flavour` function
+// makes every choice of template arguments from the gmc_batch fields and F; the launcher then dispatches on the
+// word's fields and launches through launch_flv, which refuses a kernel whose own word differs - the query
+// (gmc_lds_flavours) and the launch cannot drift apart.
+constexpr int flavour_word(int kernel, int FS, int W, int ACC, bool has_val, int NS, bool ovf, bool head = false,
+                           bool epi = false, bool shared = false) {
+    return kernel | FS << 3 | W << 10 | ACC << 15 | NS << 19 | (int)has_val << 24 | (int)ovf << 25 | (int)head << 26 |
+           (int)epi << 27 | (int)shared << 28;
+}
+inline int flavour_per(int per) { return (per >= 8 ? 3 : per >= 4 ? 2 : per >= 2 ? 1 : 0) << 29; }
+// rows per thread of a slice width for graphs of n_max nodes
+inline int acc_rows(int n_max, int FS) {
+    const int rows_per_pass = kThreads / (FS / 4);
+    return (n_max + rows_per_pass - 1) / rows_per_pass <= 4 ? 4 : 8;
+}
+
 template <typename K, typename A>
 int launch(K k, int grid, size_t lds, hipStream_t st, const A &args) {
     if (lds > 64 * 1024) {
@@ -623,6 +639,14 @@ int launch(K k, int grid, size_t lds, hipStream_t st, const A &args) {
     GMC_LAUNCH_CHECK();
     return GMC_OK;
 }
+// launch kernel k, whose template arguments encode to `have`, for the predicted word `want` (GMC_FLV_PER is not a
+// template argument)
+template <typename K, typename A>
+int launch_flv(int want, int have, K k, int grid, size_t lds, hipStream_t st, const A &args) {
+    if ((want & ~GMC_FLV_PER_MASK) != have) return GMC_ERR_UNSUPPORTED;
+    gmc_probe_flavour(want);
+    return launch(k, grid, lds, st, args);
+}
 
 }  // namespace
 
@@ -631,4 +655,5 @@ int gmc_lds_slice_width(const gmc_batch *b);
 bool gmc_lds_fits(const gmc_batch *b);
 int gmc_lds_slices(const gmc_batch *b, int F);
 int gmc_lds_groups(const gmc_batch *b, int F);
+int gmc_lds_slices_per_group(const gmc_batch *b, int F);
 int device_cus(bool allow_override = true);

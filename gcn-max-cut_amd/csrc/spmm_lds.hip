@@ -268,72 +268,52 @@ __global__ GMC_LDS_BOUNDS void dw1_lds_kernel(Dw1TileArgs a) {
     }
 }
 
-template <int FS, int W>
-int launch_spmm(const TileArgs &a, size_t lds, hipStream_t st) {
-    constexpr int rows_per_pass = kThreads / (FS / 4);
-    const int acc = (a.b.n_max + rows_per_pass - 1) / rows_per_pass;
-    const int grid = a.b.B * a.groups;
-    const bool epi = a.Zpart != nullptr;
-#define GMC_PICK(AC)                                                                                          \
-    do {                                                                                                      \
-        if (a.shared_src)  /* W1 gather: weights apply, never fused with W2 */                               \
-            return a.use_vals ? launch(spmm_lds_kernel<FS, W, AC, false, true, true>, grid, lds, st, a)       \
-                              : launch(spmm_lds_kernel<FS, W, AC, false, false, true>, grid, lds, st, a);     \
-        if (a.use_vals) return epi ? launch(spmm_lds_kernel<FS, W, AC, true, true, false>, grid, lds, st, a)  \
-                                   : launch(spmm_lds_kernel<FS, W, AC, false, true, false>, grid, lds, st, a);\
-        return epi ? launch(spmm_lds_kernel<FS, W, AC, true, false, false>, grid, lds, st, a)                 \
-                   : launch(spmm_lds_kernel<FS, W, AC, false, false, false>, grid, lds, st, a);               \
-    } while (0)
-    // live slots (no row of the batch has more neighbours): the unit-weight aggregation skips the others
-    const int ns = ns_class(W, a.b.ell_slots, !a.use_vals && !a.shared_src);
-#define GMC_NS(NSK)                                                                                                    \
-    do {                                                                                                               \
-        if (acc <= 4) return epi ? launch(spmm_lds_kernel<FS, W, 4, true, false, false, NSK>, grid, lds, st, a)        \
-                                 : launch(spmm_lds_kernel<FS, W, 4, false, false, false, NSK>, grid, lds, st, a);      \
-        if (acc <= 8) return epi ? launch(spmm_lds_kernel<FS, W, 8, true, false, false, NSK>, grid, lds, st, a)        \
-                                 : launch(spmm_lds_kernel<FS, W, 8, false, false, false, NSK>, grid, lds, st, a);      \
-        return GMC_ERR_UNSUPPORTED;                                                                                    \
-    } while (0)
-    if constexpr (W == 8) {
-        if (ns == 7) GMC_NS(7);
-    } else {
-        if (ns == 10) GMC_NS(10);
-        if (ns == 12) GMC_NS(12);
-        if (ns == 14) GMC_NS(14);
-    }
-#undef GMC_NS
-    if (acc <= 4) GMC_PICK(4);
-    if (acc <= 8) GMC_PICK(8);
-#undef GMC_PICK
+// 8 rows per thread at FS = 16 would need n_max > 1024, which no 16-column tile fits (pick_fs): never instantiated
+template <int FS, int W, bool EPI, bool HV, bool SHARED, int NS>
+int launch_spmm_acc(int flv, const TileArgs &a, int grid, size_t lds, hipStream_t st) {
+#define GMC_SPMM(AC) launch_flv(flv, flavour_word(GMC_FLV_SPMM, FS, W, AC, HV, NS, false, false, EPI, SHARED), \
+                                spmm_lds_kernel<FS, W, AC, EPI, HV, SHARED, NS>, grid, lds, st, a)
+    if (GMC_FLV_ACC(flv) == 4) return GMC_SPMM(4);
+    if constexpr (FS > 16) return GMC_SPMM(8);
     return GMC_ERR_UNSUPPORTED;
+#undef GMC_SPMM
 }
 
 template <int FS, int W>
-int launch_dw1(const Dw1TileArgs &a, size_t lds, hipStream_t st) {
-    constexpr int rows_per_pass = kThreads / (FS / 4);
-    const int acc = (a.b.n_max + rows_per_pass - 1) / rows_per_pass;
-    const int grid = a.slices * a.chunks;
-    const bool hv = a.b.ell_vals != nullptr;
-    const int ns = ns_class(W, a.b.ell_slots, !hv);
-#define GMC_NS(NSK)                                                                        \
-    do {                                                                                   \
-        if (acc <= 4) return launch(dw1_lds_kernel<FS, W, 4, false, NSK>, grid, lds, st, a); \
-        if (acc <= 8) return launch(dw1_lds_kernel<FS, W, 8, false, NSK>, grid, lds, st, a); \
-        return GMC_ERR_UNSUPPORTED;                                                        \
-    } while (0)
-    if constexpr (W == 8) {
-        if (ns == 7) GMC_NS(7);
-    } else {
-        if (ns == 10) GMC_NS(10);
-        if (ns == 12) GMC_NS(12);
-        if (ns == 14) GMC_NS(14);
-    }
+int launch_spmm(int flv, const TileArgs &a, size_t lds, hipStream_t st) {
+    const int grid = a.b.B * a.groups;
+    if (GMC_FLV_SHARED(flv))  // W1 gather: weights apply, never fused with W2
+        return GMC_FLV_HAS_VAL(flv) ? launch_spmm_acc<FS, W, false, true, true, W>(flv, a, grid, lds, st)
+                                    : launch_spmm_acc<FS, W, false, false, true, W>(flv, a, grid, lds, st);
+    // aggregations (unit weights: the ELL weights are the W1 gather's, see gmc_spmm_lds_flavour)
+#define GMC_NS(NSK) (GMC_FLV_EPI(flv) ? launch_spmm_acc<FS, W, true, false, false, NSK>(flv, a, grid, lds, st) \
+                                      : launch_spmm_acc<FS, W, false, false, false, NSK>(flv, a, grid, lds, st))
+    const int ns = GMC_FLV_NS(flv);
+    if constexpr (W == 8) return ns == 7 ? GMC_NS(7) : GMC_NS(8);
+    else return ns == 10 ? GMC_NS(10) : ns == 12 ? GMC_NS(12) : ns == 14 ? GMC_NS(14) : GMC_NS(16);
 #undef GMC_NS
-    if (acc <= 4) return hv ? launch(dw1_lds_kernel<FS, W, 4, true>, grid, lds, st, a)
-                            : launch(dw1_lds_kernel<FS, W, 4, false>, grid, lds, st, a);
-    if (acc <= 8) return hv ? launch(dw1_lds_kernel<FS, W, 8, true>, grid, lds, st, a)
-                            : launch(dw1_lds_kernel<FS, W, 8, false>, grid, lds, st, a);
+}
+
+template <int FS, int W, bool HV, int NS>
+int launch_dw1_acc(int flv, const Dw1TileArgs &a, int grid, size_t lds, hipStream_t st) {
+#define GMC_DW1(AC) launch_flv(flv, flavour_word(GMC_FLV_DW1, FS, W, AC, HV, NS, false), dw1_lds_kernel<FS, W, AC, HV, NS>, grid, lds, st, a)
+    if (GMC_FLV_ACC(flv) == 4) return GMC_DW1(4);
+    if constexpr (FS > 16) return GMC_DW1(8);
     return GMC_ERR_UNSUPPORTED;
+#undef GMC_DW1
+}
+
+template <int FS, int W>
+int launch_dw1(int flv, const Dw1TileArgs &a, size_t lds, hipStream_t st) {
+    const int grid = a.slices * a.chunks;
+    if (GMC_FLV_HAS_VAL(flv)) return launch_dw1_acc<FS, W, true, W>(flv, a, grid, lds, st);
+    const int ns = GMC_FLV_NS(flv);
+    if constexpr (W == 8) return ns == 7 ? launch_dw1_acc<FS, 8, false, 7>(flv, a, grid, lds, st)
+                                         : launch_dw1_acc<FS, 8, false, 8>(flv, a, grid, lds, st);
+    else return ns == 10 ? launch_dw1_acc<FS, 16, false, 10>(flv, a, grid, lds, st)
+              : ns == 12 ? launch_dw1_acc<FS, 16, false, 12>(flv, a, grid, lds, st)
+              : ns == 14 ? launch_dw1_acc<FS, 16, false, 14>(flv, a, grid, lds, st)
+                         : launch_dw1_acc<FS, 16, false, 16>(flv, a, grid, lds, st);
 }
 
 }  // namespace
@@ -371,6 +351,11 @@ int gmc_lds_slices(const gmc_batch *b, int F) {
 // between classes the W2 partials are folded in a different association (last-ulp differences).
 // GMC_LDS_SLICES_PER_WG overrides (tuning runs only).
 int gmc_lds_groups(const gmc_batch *b, int F) {
+    const int per = gmc_lds_slices_per_group(b, F);
+    return per ? (gmc_lds_slices(b, F) + per - 1) / per : 0;
+}
+// the slices of one group (1, 2, 4; 0: graphs do not fit)
+int gmc_lds_slices_per_group(const gmc_batch *b, int F) {
     const int fs = pick_fs(b->n_max, b->ell_width);
     if (!fs) return 0;
     const int slices = (F + fs - 1) / fs;
@@ -387,7 +372,36 @@ int gmc_lds_groups(const gmc_batch *b, int F) {
         while (per > 1 && (long)b->B * ((slices + per - 1) / per) < want) per >>= 1;
     }
     if (per > kMaxSlicesPerWg) per = kMaxSlicesPerWg;
-    return (slices + per - 1) / per;
+    return per;
+}
+
+// Flavour words of the one-kernel-per-operation launches (host only: struct fields, never the device arrays); 0 = the
+// launcher refuses the batch.  Every choice of template arguments is made here.
+static int lds_rows_flavour(const gmc_batch *b, int F, int &fs, int &acc) {
+    if (!gmc_lds_fits(b) || gmc_has_overflow(b) || F <= 0) return 0;   // (overflow lists: the fused kernels walk them)
+    fs = pick_fs(b->n_max, b->ell_width);
+    const int rows_per_pass = kThreads / (fs / 4);
+    if ((b->n_max + rows_per_pass - 1) / rows_per_pass > 8) return 0;
+    acc = acc_rows(b->n_max, fs);
+    return fs == 16 && acc != 4 ? 0 : 1;
+}
+// shared_src: the W1 row gather (the ELL weights apply); otherwise an aggregation, unit weights: no caller aggregates
+// with the ELL weights (the layer's structure carries none), so spmm_lds_kernel<.., HAS_VAL, !SHARED> is not built
+int gmc_spmm_lds_flavour(const gmc_batch *b, int F, int shared_src, int use_vals, bool epi) {
+    int fs = 0, acc = 0;
+    if (!lds_rows_flavour(b, F, fs, acc)) return 0;
+    const int W = b->ell_width, per = flavour_per(gmc_lds_slices_per_group(b, F));
+    const bool hv = use_vals && b->ell_vals != nullptr;
+    if (shared_src) return flavour_word(GMC_FLV_SPMM, fs, W, acc, hv, W, false, false, false, true) | per;
+    if (hv) return 0;
+    // live slots (no row of the batch has more neighbours): the unit-weight aggregation skips the others
+    return flavour_word(GMC_FLV_SPMM, fs, W, acc, false, ns_class(W, b->ell_slots, true), false, false, epi) | per;
+}
+int gmc_dw1_lds_flavour(const gmc_batch *b, int F) {
+    int fs = 0, acc = 0;
+    if (!lds_rows_flavour(b, F, fs, acc)) return 0;
+    const bool hv = b->ell_vals != nullptr;
+    return flavour_word(GMC_FLV_DW1, fs, b->ell_width, acc, hv, ns_class(b->ell_width, b->ell_slots, !hv), false);
 }
 
 // Y = act(scale * A_g @ X + bias) for every graph of the batch, LDS-staged; optional fused
@@ -400,26 +414,27 @@ int gmc_spmm_lds_launch(const gmc_batch *b, const float *X, long ldx, int x_slab
     if (!b || !X || !Y) return GMC_ERR_NULL;
     if (F % 4 || ldx % 4 || ldy % 4 || !gmc_aligned16(X) || !gmc_aligned16(Y))
         return GMC_ERR_ALIGN;
-    if (!gmc_lds_fits(b) || gmc_has_overflow(b)) return GMC_ERR_UNSUPPORTED;   // (overflow lists: the fused kernels walk them)
+    const int flv = gmc_spmm_lds_flavour(b, F, shared_src, use_vals, Zpart != nullptr);
+    if (!flv) return GMC_ERR_UNSUPPORTED;
     if (b->B == 0) return GMC_OK;
-    const int fs = pick_fs(b->n_max, b->ell_width);
+    const int fs = GMC_FLV_FS(flv);
     const long slab_ss = (long)b->R * fs;
     TileArgs a{*b, X, x_slab ? fs : ldx, x_slab ? slab_ss : fs, shared_src, use_vals && b->ell_vals != nullptr,
                scale, bias, relu, Y, y_slab ? fs : ldy, y_slab ? slab_ss : fs, F,
                (F + fs - 1) / fs, gmc_lds_groups(b, F), W2, Zpart, 0};
     const size_t lds = lds_bytes(b->n_max, b->ell_width, fs);
     GmcProbeScope probe(tag, st);
-    if (b->ell_width == 8) {
+    if (GMC_FLV_W(flv) == 8) {
         switch (fs) {
-            case 64: return launch_spmm<64, 8>(a, lds, st);
-            case 32: return launch_spmm<32, 8>(a, lds, st);
-            default: return launch_spmm<16, 8>(a, lds, st);
+            case 64: return launch_spmm<64, 8>(flv, a, lds, st);
+            case 32: return launch_spmm<32, 8>(flv, a, lds, st);
+            default: return launch_spmm<16, 8>(flv, a, lds, st);
         }
     }
     switch (fs) {
-        case 64: return launch_spmm<64, 16>(a, lds, st);
-        case 32: return launch_spmm<32, 16>(a, lds, st);
-        default: return launch_spmm<16, 16>(a, lds, st);
+        case 64: return launch_spmm<64, 16>(flv, a, lds, st);
+        case 32: return launch_spmm<32, 16>(flv, a, lds, st);
+        default: return launch_spmm<16, 16>(flv, a, lds, st);
     }
 }
 
@@ -444,22 +459,23 @@ int device_cus(bool allow_override) {
 // dW1 partials: out[chunk][v][:] = sum_{g in chunk} sum_e vals[e] * U[g][nbr(e), :], v < n_max
 int gmc_dw1_lds_launch(const gmc_batch *b, const float *U, long ldu, int u_slab, float *out, int F, int chunks,
                        int graphs_per_chunk, hipStream_t st) {
-    if (!gmc_lds_fits(b) || gmc_has_overflow(b)) return GMC_ERR_UNSUPPORTED;
-    const int fs = pick_fs(b->n_max, b->ell_width);
+    const int flv = gmc_dw1_lds_flavour(b, F);
+    if (!flv) return GMC_ERR_UNSUPPORTED;
+    const int fs = GMC_FLV_FS(flv);
     Dw1TileArgs a{*b, U, u_slab ? fs : ldu, u_slab ? (long)b->R * fs : fs, out, F, (F + fs - 1) / fs, chunks,
                   graphs_per_chunk};
     const size_t lds = lds_bytes(b->n_max, b->ell_width, fs);
     GmcProbeScope probe(GMC_K_DW1, st);
-    if (b->ell_width == 8) {
+    if (GMC_FLV_W(flv) == 8) {
         switch (fs) {
-            case 64: return launch_dw1<64, 8>(a, lds, st);
-            case 32: return launch_dw1<32, 8>(a, lds, st);
-            default: return launch_dw1<16, 8>(a, lds, st);
+            case 64: return launch_dw1<64, 8>(flv, a, lds, st);
+            case 32: return launch_dw1<32, 8>(flv, a, lds, st);
+            default: return launch_dw1<16, 8>(flv, a, lds, st);
         }
     }
     switch (fs) {
-        case 64: return launch_dw1<64, 16>(a, lds, st);
-        case 32: return launch_dw1<32, 16>(a, lds, st);
-        default: return launch_dw1<16, 16>(a, lds, st);
+        case 64: return launch_dw1<64, 16>(flv, a, lds, st);
+        case 32: return launch_dw1<32, 16>(flv, a, lds, st);
+        default: return launch_dw1<16, 16>(flv, a, lds, st);
     }
 }

@@ -21,7 +21,7 @@ SYMBOLS = (
     "gmc_adam_f32", "gmc_workspace_bytes", "gmc_forward", "gmc_train_fwd_bwd",
     "gmc_backward_from_gp", "gmc_probe_begin", "gmc_probe_end", "gmc_set_fuse", "gmc_decode_sample_f32", "gmc_adam_devstep_f32", "gmc_ell_arrange_host", "gmc_ell_slots_for", "gmc_train_step_f32",
     "gmc_adam_devstep_model_f32", "gmc_w1_slab_floats", "gmc_w1_slab_f32", "gmc_host_device_pointer", "gmc_publish_f32",
-    "gmc_publish_adam_devstep_model_f32",
+    "gmc_publish_adam_devstep_model_f32", "gmc_probe_flavours", "gmc_lds_flavours",
 )
 
 MAX_GRAPH_NODES = 4096
@@ -93,6 +93,8 @@ def _declare(lib: C.CDLL) -> None:
     lib.gmc_decode_sample_f32.argtypes = [C.POINTER(GmcBatch), vp, vp, vp, i32, vp, vp, vp, vp, vp, vp]
     lib.gmc_probe_begin.argtypes = [i32]
     lib.gmc_probe_end.argtypes = [vp, vp, i32]
+    lib.gmc_probe_flavours.argtypes = [vp, i32]
+    lib.gmc_lds_flavours.argtypes = [C.POINTER(GmcBatch), i32, i32, vp, i32]
     lib.gmc_host_device_pointer.argtypes = [vp, C.POINTER(vp)]
     lib.gmc_publish_f32.argtypes = [vp, i32, vp, vp]
     lib.gmc_publish_adam_devstep_model_f32.argtypes = [vp, i32, vp, vp, vp, vp, vp, i32, i32, vp, C.c_double, C.c_double,
@@ -175,12 +177,33 @@ KERNEL_TAGS = ("gather_w1", "agg_fwd", "head", "hidden_bwd", "colsum", "agg_bwd"
                "adam", "spmm_user", "dense_mfma", "bwd1_fused", "fwd1_fused", "decode", "finish")
 
 
+FLAVOUR_KERNELS = {1: "fwd1_lds", 2: "bwd1_lds", 3: "bwd1_reg", 4: "spmm_lds", 5: "dw1_lds"}   # GMC_FLV_KERNEL
+
+
+def flavour_fields(word: int) -> dict:
+    """The bit fields of a flavour word (include/gcnmaxcut.h, GMC_FLV_*)."""
+    return dict(kernel=FLAVOUR_KERNELS.get(word & 7, "?"), FS=word >> 3 & 0x7f, W=word >> 10 & 0x1f,
+                ACC=word >> 15 & 0xf, NS=word >> 19 & 0x1f, HAS_VAL=word >> 24 & 1, OVF=word >> 25 & 1,
+                HEAD=word >> 26 & 1, EPI=word >> 27 & 1, SHARED=word >> 28 & 1, PER=1 << (word >> 29 & 3))
+
+
+def lds_flavours(batch_struct: GmcBatch, F: int, one_graph_step: bool = False) -> list:
+    """Flavour words of the LDS-tiled launches of a training step (gmc_lds_flavours; host only, no GPU):
+    the fused sequence (fwd1, bwd1), then - batches without overflow lists - the gmc_set_fuse(0) sequence."""
+    words = (C.c_int32 * 8)()
+    n = load().gmc_lds_flavours(C.byref(batch_struct), int(F), int(bool(one_graph_step)), words, 8)
+    if n < 0:
+        check(n, "gmc_lds_flavours")
+    return [int(words[i]) for i in range(n)]
+
+
 class Probe:
     """``with Probe(capacity) as p: ...`` then ``p.records`` = [(kernel_tag, ms), ...]:
-    per-launch HIP-event timings recorded by the library on the launch stream."""
+    per-launch HIP-event timings recorded by the library on the launch stream, and ``p.flavours`` = the
+    flavour word of each of those launches (0 for kernels outside the LDS-tiled families)."""
 
     def __init__(self, capacity: int):
-        self.capacity, self.records = capacity, []
+        self.capacity, self.records, self.flavours = capacity, [], []
 
     def __enter__(self):
         check(load().gmc_probe_begin(self.capacity), "gmc_probe_begin")
@@ -193,4 +216,9 @@ class Probe:
         if n < 0:
             raise RuntimeError(f"gmc_probe_end failed ({n})")
         self.records = [(KERNEL_TAGS[tags[i]], float(ms[i])) for i in range(min(n, self.capacity))]
+        words = (C.c_int32 * self.capacity)()
+        m = load().gmc_probe_flavours(words, self.capacity)
+        if m != n:
+            raise RuntimeError(f"gmc_probe_flavours returned {m}, gmc_probe_end {n}")
+        self.flavours = [int(words[i]) for i in range(min(n, self.capacity))]
         return False

@@ -175,6 +175,38 @@ int gmc_set_fuse(int on);
 
 int gmc_probe_begin(int32_t capacity);
 int gmc_probe_end(int32_t *tags, float *ms, int32_t max);
+/* Valid after gmc_probe_end: the flavour word (below) of each recorded launch, 0 for a kernel that is not one of the
+ * LDS-tiled families.  Writes up to `max` words (host pointer), returns the number of launches recorded. */
+int gmc_probe_flavours(int32_t *words, int32_t max);
+
+/* Flavour words: WHICH instantiation of an LDS-tiled kernel family a launch runs (the host picks one per batch
+ * from n_max, the table width, the live slots, edge weights and overflow lists).  Bit fields of a non-negative int32: */
+#define GMC_FLV_KERNEL(w) ((w) & 0x7)          /* family: GMC_FLV_FWD1 .. GMC_FLV_DW1 */
+#define GMC_FLV_FS(w) (((w) >> 3) & 0x7f)      /* columns per slice: 16, 32, 64 */
+#define GMC_FLV_W(w) (((w) >> 10) & 0x1f)      /* neighbour slots per row of the table: 8, 16 */
+#define GMC_FLV_ACC(w) (((w) >> 15) & 0xf)     /* rows per thread: 4, 8 */
+#define GMC_FLV_NS(w) (((w) >> 19) & 0x1f)     /* live slots the gathers read: 7, 8, 10, 12, 14, 16 */
+#define GMC_FLV_HAS_VAL(w) (((w) >> 24) & 1)   /* edge weights */
+#define GMC_FLV_OVF(w) (((w) >> 25) & 1)       /* overflow lists (hub rows) */
+#define GMC_FLV_HEAD(w) (((w) >> 26) & 1)      /* bwd1_reg: the one-graph head runs inside the backward */
+#define GMC_FLV_EPI(w) (((w) >> 27) & 1)       /* spmm_lds: fused (Y o scale) @ W2 epilogue */
+#define GMC_FLV_SHARED(w) (((w) >> 28) & 1)    /* spmm_lds: one shared source table (the W1 row gather) */
+#define GMC_FLV_PER(w) (1 << (((w) >> 29) & 3)) /* fwd1 / spmm_lds: column slices per workgroup item (1, 2, 4, 8) */
+#define GMC_FLV_PER_MASK (3 << 29)             /* (not a template argument: it changes how the W2 partials fold) */
+enum {
+    GMC_FLV_FWD1 = 1,      /* fwd1_lds_kernel<FS, W, ACC, HAS_VAL, NS, OVF>: the fused layer-1 forward */
+    GMC_FLV_BWD1 = 2,      /* bwd1_lds_kernel<FS, W, ACC, HAS_VAL, NS, OVF>: the fused backward, 16-slot tables */
+    GMC_FLV_BWD1_REG = 3,  /* bwd1_reg_kernel<FS, ACC, HAS_VAL, NS, OVF, HEAD>: the fused backward, 8-slot tables */
+    GMC_FLV_SPMM = 4,      /* spmm_lds_kernel<FS, W, ACC, EPI, HAS_VAL, SHARED, NS>: one-kernel-per-operation SpMM */
+    GMC_FLV_DW1 = 5        /* dw1_lds_kernel<FS, W, ACC, HAS_VAL, NS>: one-kernel-per-operation dW1 gather */
+};
+/* HOST query (no HIP call; the batch's pointers are only tested against NULL): the flavour words of the LDS-tiled
+ * launches a training step of this batch with hidden width F makes, in launch order - first the fused sequence
+ * (fwd1, then bwd1; one_graph_step != 0: as gmc_train_step_f32 runs it, which computes a one-graph batch's head
+ * inside the backward), then the one-kernel-per-operation sequence of gmc_set_fuse(0) (W1 gather, aggregation with
+ * the W2 epilogue, backward aggregation, dW1), the latter only for batches without overflow lists.  Returns the
+ * number of words (writes up to `max`), 0 when the batch takes the row kernels, <0 on bad arguments. */
+int gmc_lds_flavours(const gmc_batch *batch, int32_t F, int32_t one_graph_step, int32_t *words, int32_t max);
 
 /* ---- building blocks (each is also used by the fused entry points below) ---------- */
 

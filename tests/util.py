@@ -113,3 +113,84 @@ def check_step_against_oracle(pkg, net, ds, params, C=1.0):
         assert np.abs(Pn[off:off + n] - CO.forward(rp, cl, vl, *Wl)["P"]).max() < 1e-4
         off += n
     return eng, tags
+
+
+# ---- float64 restatement of one training step (forward, loss, backward) on a graph's CSR, for the flavour matrix.
+# Written from the algorithm the oracle documents (oracle/gcn_oracle.c: GraphConv norm='both' twice, softmax, terminal
+# override + argmax, cut loss, straight-through dLoss/dP = C * A_val @ onehot(S)), on dense n x n operators.
+def f64_forward(rp, cl, vl, W1, b1, W2, b2):
+    n = len(rp) - 1
+    rows = np.repeat(np.arange(n), np.diff(rp))
+    A = np.zeros((n, n))
+    A[rows, cl] = 1.0                                   # structure: the aggregations carry no edge weight
+    X = np.zeros((n, n))
+    X[rows, cl] = 1.0 if vl is None else vl.astype(np.float64)   # features = the weighted adjacency
+    dinv = 1.0 / np.sqrt(np.maximum(np.diff(rp), 1).astype(np.float64))
+    W1, b1, W2, b2 = (np.asarray(w, np.float64) for w in (W1, b1, W2, b2))
+    T0 = dinv[:, None] * (X @ W1[:n])
+    H = np.maximum(dinv[:, None] * (A @ T0) + b1, 0.0)
+    Z = dinv[:, None] * (A @ (dinv[:, None] * H @ W2)) + b2
+    E = np.exp(Z - Z.max(1, keepdims=True))
+    return dict(A=A, X=X, dinv=dinv, H=H, P=E / E.sum(1, keepdims=True))
+
+
+def f64_partition(P):
+    S = P.argmax(1)
+    S[:3] = [0, 1, 2]
+    return S
+
+
+def f64_loss_and_gp(f, S, C=1.0):
+    """loss = -C * cut(S), GP = C * A_val @ onehot(S)."""
+    X = f["X"]
+    cut = 0.5 * float((X * (S[:, None] != S[None, :])).sum())
+    return -C * cut, C * X @ np.eye(3)[S]
+
+
+def f64_backward(f, GP, W2, N):
+    A, X, dinv, H, P = f["A"], f["X"], f["dinv"], f["H"], f["P"]
+    W2 = np.asarray(W2, np.float64)
+    gz = P * (GP - (GP * P).sum(1, keepdims=True))     # softmax backward
+    gy2 = A @ (dinv[:, None] * gz)
+    dW2 = (dinv[:, None] * H).T @ gy2
+    g = np.where(H > 0, dinv[:, None] * (gy2 @ W2.T), 0.0)
+    gy1 = A @ (dinv[:, None] * g)
+    dW1 = np.zeros((N, H.shape[1]))
+    dW1[:len(dinv)] = X @ (dinv[:, None] * gy1)
+    return dict(W1=dW1, b1=g.sum(0), W2=dW2, b2=gz.sum(0))
+
+
+def f64_step(csrs, params, S_got, C=1.0, tie=1e-6):
+    """Per graph: float64 P, the partition (the kernels' own where the float64 top-2 margin is below `tie`: the
+    summation orders differ, a near-tie may decode either way - anywhere else the partitions must agree), the loss
+    of that partition, and the summed float64 gradient of the batch."""
+    W = [params[k] for k in ("conv1.weight", "conv1.bias", "conv2.weight", "conv2.bias")]
+    grad = None
+    Ps, losses, off = [], [], 0
+    for rp, cl, vl in csrs:
+        n = len(rp) - 1
+        f = f64_forward(rp, cl, vl, *W)
+        S = f64_partition(f["P"])
+        s_got = np.asarray(S_got[off:off + n])
+        diff = np.nonzero(s_got != S)[0]
+        if diff.size:
+            srt = np.sort(f["P"][diff], axis=1)
+            assert (srt[:, 2] - srt[:, 1]).max() < tie, (diff, srt)
+            S = s_got.astype(np.int64)
+        loss, GP = f64_loss_and_gp(f, S, C)
+        g = f64_backward(f, GP, W[2], W[0].shape[0])
+        grad = g if grad is None else {k: grad[k] + g[k] for k in grad}
+        Ps.append(f["P"])
+        losses.append(loss)
+        off += n
+    return np.concatenate(Ps), np.asarray(losses), grad
+
+
+def row_error_ratio(got, ref, floor):
+    """max over rows of |got - ref| / max(max |ref row|, floor * max |ref|): each parameter row (dW1 row j, a b1 entry,
+    a dW2 row, a b2 entry) judged against its own magnitude; `floor` keeps rows that are exactly zero in the reference
+    (rows past every graph's n) at a bar relative to the tensor."""
+    got = np.asarray(got, np.float64).reshape(ref.shape[0], -1)
+    ref = np.asarray(ref, np.float64).reshape(ref.shape[0], -1)
+    scale = np.maximum(np.abs(ref).max(1), floor * max(np.abs(ref).max(), 1e-30))
+    return float((np.abs(got - ref).max(1) / scale).max())
