@@ -117,8 +117,8 @@ Workspace carve(const gmc_batch *b, const gmc_model *m, int training, void *base
     w.Z0 = take((size_t)w.zparts * R * 3);
     if (training) {
         w.GY2 = take(R * 4);  // (GY2[r,0..2], dinv[r]) per row: one aligned 16 B load downstream
-        size_t tiles = w.fs ? gmc_hidden_slab_tiles(b->R) : gmc_hidden_tiles(b->R);
-        if (w.fs && (size_t)gmc_dw1_chunks(b->B, true, gmc_lds_slices(b, F)) > tiles) tiles = gmc_dw1_chunks(b->B, true, gmc_lds_slices(b, F));
+        size_t tiles = (size_t)(w.fs ? gmc_hidden_slab_tiles(b->R) : gmc_hidden_tiles(b->R));
+        if (w.fs && (size_t)gmc_dw1_chunks(b->B, true, gmc_lds_slices(b, m->F)) > tiles) tiles = (size_t)gmc_dw1_chunks(b->B, true, gmc_lds_slices(b, m->F));
         w.part = take(tiles * F * 4);
         w.db2part = take((size_t)b->B * 3);
         w.dw1part = take(gmc_dw1_scratch_floats(b, m->N, m->F, w.fs != 0));
@@ -135,7 +135,7 @@ int check(const gmc_batch *b, const gmc_model *m) {
     if (!m->W1 || !m->b1 || !m->W2 || !m->b2) return GMC_ERR_NULL;
     if (m->K != 3) return GMC_ERR_CLASSES;
     if (b->B < 0 || b->R < 0 || b->nnz < 0 || m->N <= 0 || m->F <= 0) return GMC_ERR_SHAPE;
-    if (m->F % 4 || m->F > 1024) return GMC_ERR_UNSUPPORTED;  // float4 rows, <= 4 passes per lane
+    if (m->F % 4 || m->F > GMC_MAX_HIDDEN) return GMC_ERR_UNSUPPORTED;  // float4 rows
     if (!(m->dropout_p >= 0.f && m->dropout_p < 1.f)) return GMC_ERR_SHAPE;
     if (m->W1_slab && !gmc_aligned16(m->W1_slab)) return GMC_ERR_ALIGN;
     if (b->B > 0 && (b->n_max < 3 || b->n_max > GMC_MAX_GRAPH_NODES)) return GMC_ERR_GRAPH_SIZE;
@@ -300,7 +300,7 @@ extern "C" int gmc_probe_flavours(int32_t *words, int32_t max) {
 extern "C" int gmc_lds_flavours(const gmc_batch *batch, int32_t F, int32_t one_graph_step, int32_t *words, int32_t max) {
     if (!batch) return GMC_ERR_NULL;
     if (batch->abi != GMC_VERSION) return GMC_ERR_ABI;
-    if (F <= 0 || F % 4 || F > 1024 || max < 0 || batch->B < 0) return GMC_ERR_SHAPE;
+    if (F <= 0 || F % 4 || F > GMC_MAX_HIDDEN || max < 0 || batch->B < 0) return GMC_ERR_SHAPE;
     int out[6], n = 0;
     if (gmc_lds_fits(batch)) {
         const bool head = one_graph_step && gmc_bwd1_takes_head(batch) && gmc_dw1_chunks(batch->B, true, gmc_lds_slices(batch, F)) == 1;
@@ -335,7 +335,7 @@ extern "C" const char *gmc_error_string(int code) {
         case GMC_ERR_ALIGN: return "pointer or leading dimension not 16-byte aligned";
         case GMC_ERR_WORKSPACE: return "workspace too small";
         case GMC_ERR_GRAPH_SIZE: return "graph has fewer than 3 or more than GMC_MAX_GRAPH_NODES nodes";
-        case GMC_ERR_UNSUPPORTED: return "unsupported shape (the leading dimension F must be a multiple of 4 and <= 1024)";
+        case GMC_ERR_UNSUPPORTED: return "unsupported shape (the hidden width F must be a multiple of 4 and <= 4096 = GMC_MAX_HIDDEN)";
         case GMC_ERR_ABI: return "gmc_batch.abi / gmc_model.abi differs from the library's GMC_VERSION: rebuild the caller against this include/gcnmaxcut.h";
         default: return code > 0 ? hipGetErrorString((hipError_t)code) : "unknown gmc error";
     }

@@ -3,7 +3,7 @@
 // padded adjacency, dW1[v,:] = sum_g sum_{u in nbr_g(v)} X[u,v] * U[g,u,:] with
 // U = dinv o GY1, and rows v >= n_g receive nothing (exactly 0).
 //
-// gather_reduce: one wave per (node id v, graph chunk); CSR-order gather of U rows with
+// gather_reduce: one wave per (node id v, graph chunk, 1024-column block); CSR-order gather of U rows with
 // 8 rows in flight, graphs ascending; writes either dW1 directly (one chunk) or a
 // per-chunk partial that fold_chunks sums in chunk order.  No atomics: reproducible.
 #include "gmc_common.h"
@@ -31,7 +31,8 @@ __global__ __launch_bounds__(256) void dw1_gather_kernel(Dw1Args a) {
     const int chunk = blockIdx.y;
     const int g0 = chunk * a.graphs_per_chunk;
     const int g1 = min(a.b.B, g0 + a.graphs_per_chunk);
-    const int F4 = a.F >> 2;
+    const int c4b = (int)blockIdx.z * 256;       // first float4 column of my block (F > 1024: several blocks)
+    const int F4 = min((a.F >> 2) - c4b, 256);
     bool on[NP];
     int cc[NP];
     float4 acc[NP];
@@ -65,7 +66,7 @@ __global__ __launch_bounds__(256) void dw1_gather_kernel(Dw1Args a) {
                 for (int u = 0; u < kUnroll; ++u) {
                     const long c = __builtin_amdgcn_readlane(myc, j + u);
                     w[u] = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, myv), j + u));
-                    src[u] = a.U + c * a.ldu;
+                    src[u] = a.U + c * a.ldu + 4 * c4b;
                 }
 #pragma unroll
                 for (int u = 0; u < kUnroll; ++u)
@@ -82,7 +83,7 @@ __global__ __launch_bounds__(256) void dw1_gather_kernel(Dw1Args a) {
             }
         }
     }
-    float4 *dst = reinterpret_cast<float4 *>(a.out + ((long)chunk * a.N + v) * a.F);
+    float4 *dst = reinterpret_cast<float4 *>(a.out + ((long)chunk * a.N + v) * a.F) + c4b;
 #pragma unroll
     for (int p = 0; p < NP; ++p)
         if (on[p]) dst[lane + 64 * p] = acc[p];
@@ -151,7 +152,8 @@ size_t gmc_dw1_scratch_floats(const gmc_batch *b, int N, int F, bool lds) {
 
 int gmc_dw1_launch(const gmc_batch *b, const float *U, long ldu, float *dW1, float *scratch,
                    int N, int F, bool lds, hipStream_t st) {
-    if (F % 4 || ldu % 4 || F > 1024) return GMC_ERR_ALIGN;
+    if (F % 4 || ldu % 4) return GMC_ERR_ALIGN;
+    if (F > GMC_MAX_HIDDEN) return GMC_ERR_UNSUPPORTED;
     const int chunks = gmc_dw1_chunks(b->B, lds, lds ? gmc_lds_slices(b, F) : 0);
     const int per = (b->B + chunks - 1) / chunks;
     int rows = N;
@@ -161,7 +163,7 @@ int gmc_dw1_launch(const gmc_batch *b, const float *U, long ldu, float *dW1, flo
         rows = b->n_max;
     } else {
         Dw1Args a{*b, U, ldu, chunks > 1 ? scratch : dW1, N, F, per};
-        dim3 grid((N + 3) / 4, chunks);
+        dim3 grid((N + 3) / 4, chunks, (F + 1023) / 1024);   // (F > 1024: 1024-column blocks of the 4-pass kernel)
         gmc_probe_mark(GMC_K_DW1, true, st);
         if (F <= 256) hipLaunchKernelGGL(dw1_gather_kernel<1>, grid, dim3(256), 0, st, a);
         else if (F <= 512) hipLaunchKernelGGL(dw1_gather_kernel<2>, grid, dim3(256), 0, st, a);

@@ -57,15 +57,25 @@ __global__ GMC_LDS_BOUNDS void fwd1_lds_kernel(TileArgs a) {
         return c;
     };
 
-    if (!CSL) {   // (slices * FS <= 1024 = kThreads: one column per thread; pad columns hold zeros)
-        const int cc = threadIdx.x;
+    // 8-slot tables: a window of kThreads columns (kSlicesPerWin slices), one column per thread; pad columns hold
+    // zeros.  F <= kThreads is one window, loaded here once.  Wider F: the window of the first slice here, the next
+    // one inside the slice loop when the items cross into it (behind barrier 1, published by barrier 2)
+    constexpr int kSlicesPerWin = kThreads / FS;
+    auto load_window = [&](int win) {
+        const int cc = win * kThreads + (int)threadIdx.x;
         const bool c_on = cc < a.slices * FS;
         float4 c = gmc::f4_zero();
         if (c_on && cc < a.F) {
             if (a.W2) { c.x = a.W2[(long)cc * 3]; c.y = a.W2[(long)cc * 3 + 1]; c.z = a.W2[(long)cc * 3 + 2]; }
             if (a.bias) c.w = a.bias[cc];
         }
-        if (c_on) cst[cc] = c;
+        if (c_on) cst[threadIdx.x] = c;
+    };
+    int win = 0;   // window of column constants in LDS (wave-uniform)
+    if (!CSL) {
+        const int g_first = it0 / a.groups;
+        win = (it0 - g_first * a.groups) * per / kSlicesPerWin;
+        load_window(win);
     }
 
     MARK(1);
@@ -194,6 +204,12 @@ __global__ GMC_LDS_BOUNDS void fwd1_lds_kernel(TileArgs a) {
             STAMP(1);  // DMA wait
             loop_barrier();  // ... for every wave; readers of the previous T0 tile are done
             STAMP(2);  // barrier 1
+            // (8-slot tables, F > kThreads only) slice s lies outside the constants' window: every reader of the window
+            // (gather #2 of slice s-1) is behind barrier 1, gather #1 does not read it, barrier 2 publishes the next
+            if (!CSL && s / kSlicesPerWin != win) {
+                win = s / kSlicesPerWin;
+                load_window(win);
+            }
             // gather #1: T0 tile
             if constexpr (W == 8) {
                 uint4 ids = reinterpret_cast<const uint4 *>(nb)[min(lrow, n - 1)];
@@ -258,8 +274,8 @@ __global__ GMC_LDS_BOUNDS void fwd1_lds_kernel(TileArgs a) {
             STAMP(5);  // DMA issue
             // gather #2: H rows + fused W2; every thread issues exactly ACC stores (rows past n repeat
             // row n-1: same value to the same address) so that the vm_wait above counts exactly
-            // my 4 columns' constants (indexed by absolute column): W2 rows as (w0,w1) pairs + w2, bias pairs
-            const int cb = (CSL ? (s & 1) : s) * FS + 4 * q;
+            // my 4 columns' constants (indexed by column within the window / CSL buffer): W2 rows as (w0,w1) pairs + w2, bias pairs
+            const int cb = (CSL ? (s & 1) : s - win * kSlicesPerWin) * FS + 4 * q;
             const float4 c0 = cst[cb], c1 = cst[cb + 1], c2 = cst[cb + 2], c3 = cst[cb + 3];
             const gmc::v2f w01[4] = {{c0.x, c0.y}, {c1.x, c1.y}, {c2.x, c2.y}, {c3.x, c3.y}};
             const float w2c[4] = {c0.z, c1.z, c2.z, c3.z};
@@ -359,10 +375,10 @@ int gmc_fwd1_flavour(const gmc_batch *b, int F) {
     if (!gmc_lds_fits(b) || F <= 0) return 0;
     const int fs = pick_fs(b->n_max, b->ell_width), W = b->ell_width;
     const int slices = (F + fs - 1) / fs;
-    // 8-slot tables: the column constants of every slice sit in LDS, 16 B per (padded) column (16-slot tables load
-    // them slice by slice)
-    if (W == 8 && ((size_t)slices * fs > (size_t)kThreads || (size_t)16 * slices * fs > lds_consts(b->n_max, fs, 8)))
-        return 0;
+    // 8-slot tables: the column constants of a window of up to kThreads columns sit in LDS, 16 B per column (16-slot
+    // tables load them slice by slice)
+    if (W == 8 && (size_t)16 * kThreads > lds_consts(b->n_max, fs, 8)) return 0;
+    if (slices * fs > GMC_MAX_HIDDEN) return 0;
     const int rows_per_pass = kThreads / (fs / 4);
     if ((b->n_max + rows_per_pass - 1) / rows_per_pass > 8) return 0;
     const int acc = acc_rows(b->n_max, fs);

@@ -143,8 +143,8 @@ __host__ __device__ inline size_t tile_floats(int n_max, int FS) { return (size_
 constexpr int kMaxSlicesPerWg = 8;
 // third LDS region (after the two tiles and the table):
 //   8-slot tables - the larger of
-//   - the column constants (bias, W2 rows): 16 B per column - every slice of up to 1024 columns for
-//     the persistent fused forward, kMaxSlicesPerWg slices for the SpMM (8 * FS * 16 B <= that);
+//   - the column constants (bias, W2 rows): 16 B per column - a window of 1024 columns (all of them for F <= 1024)
+//     for the persistent fused forward, kMaxSlicesPerWg slices for the SpMM (8 * FS * 16 B <= that);
 //   - the per-row constants (GY2[r,:], dinv[r]) of the graph in flight in bwd1_reg: 16 B per row (its second
 //     copy of them sits in the table region: that kernel keeps the neighbour ids in registers);
 //   16-slot tables (the table is twice as large: 32 B per row) - only the column constants of the slices in

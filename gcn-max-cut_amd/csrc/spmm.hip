@@ -197,6 +197,94 @@ __global__ __launch_bounds__(256) void spmm_rows_v4(SpmmArgs a) {
     }
 }
 
+// F > 1024 (hidden widths up to GMC_MAX_HIDDEN): spmm_rows_v4's four passes per lane over one 1024-column block of
+// the row at a time.  Each block re-walks the row's neighbour list (ids stay in registers); the fused W2 epilogue
+// accumulates over all blocks before the wave's fold.
+template <int RPW, int kUnroll, bool HAS_VAL, bool EPI, int VARIANT>
+__global__ __launch_bounds__(256) void spmm_rows_wide(SpmmArgs a) {
+    constexpr int NP = 4;
+    const int lane = gmc::lane_id();
+    const int wave = gmc::uniform((int)(threadIdx.x >> 6));
+    const int wg = xcd_remap((int)blockIdx.x, (int)gridDim.x, a.group_wgs);
+    const int F4 = a.F >> 2;
+    const int r0 = gmc::uniform((wg * kWavesPerWg + wave) * RPW);
+    if (r0 >= a.n_rows) return;
+    const int nr = min(RPW, a.n_rows - r0);
+    const int rp = a.rowptr[r0 + min(lane, nr)];
+    float myscale = 1.f;
+    if (a.scale) myscale = a.scale[r0 + min(lane, nr - 1)];
+    int myc[RPW];
+    float myv[RPW];
+#pragma unroll
+    for (int i = 0; i < RPW; ++i) {
+        const int beg = __builtin_amdgcn_readlane(rp, i), end = __builtin_amdgcn_readlane(rp, i + 1);
+        const bool have = i < nr && lane < end - beg;
+        myc[i] = have ? a.col[beg + lane] : 0;
+        myv[i] = 1.f;
+        if (HAS_VAL) myv[i] = have ? a.vals[beg + lane] : 0.f;
+    }
+#pragma unroll
+    for (int i = 0; i < RPW; ++i) {
+        if (i >= nr) break;
+        const long r = r0 + i;
+        const int beg = __builtin_amdgcn_readlane(rp, i), end = __builtin_amdgcn_readlane(rp, i + 1);
+        const float s = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, myscale), i));
+        float z0 = 0.f, z1 = 0.f, z2 = 0.f;
+#pragma unroll 1
+        for (int cb = 0; cb < F4; cb += 64 * NP) {   // (wave-uniform) 1024-column blocks
+            bool on[NP];
+            int cc[NP];
+            float4 acc[NP];
+#pragma unroll
+            for (int p = 0; p < NP; ++p) {
+                const int c = cb + lane + 64 * p;
+                on[p] = c < F4;
+                cc[p] = on[p] ? c : F4 - 1;
+                acc[p] = gmc::f4_zero();
+            }
+            const int cnt0 = min(64, end - beg);
+#pragma unroll 1
+            for (int j = 0; j < cnt0; j += kUnroll) gather_rows<NP, kUnroll, HAS_VAL>(a, myc[i], myv[i], j, cnt0, cc, acc);
+#pragma unroll 1
+            for (int e0 = beg + 64; e0 < end; e0 += 64) {  // rows with more than 64 neighbours
+                const int cnt = min(64, end - e0);
+                const int c2 = lane < cnt ? a.col[e0 + lane] : 0;
+                float v2 = 1.f;
+                if (HAS_VAL) v2 = lane < cnt ? a.vals[e0 + lane] : 0.f;
+#pragma unroll 1
+                for (int j = 0; j < cnt; j += kUnroll) gather_rows<NP, kUnroll, HAS_VAL>(a, c2, v2, j, cnt, cc, acc);
+            }
+#pragma unroll
+            for (int p = 0; p < NP; ++p) {
+                const float4 bias = a.bias ? reinterpret_cast<const float4 *>(a.bias)[cc[p]] : gmc::f4_zero();
+                float4 y;
+                y.x = fmaf(acc[p].x, s, bias.x);
+                y.y = fmaf(acc[p].y, s, bias.y);
+                y.z = fmaf(acc[p].z, s, bias.z);
+                y.w = fmaf(acc[p].w, s, bias.w);
+                if (a.relu) {
+                    y.x = y.x > 0.f ? y.x : 0.f; y.y = y.y > 0.f ? y.y : 0.f;
+                    y.z = y.z > 0.f ? y.z : 0.f; y.w = y.w > 0.f ? y.w : 0.f;
+                }
+                if (on[p]) reinterpret_cast<float4 *>(a.Y + r * a.ldy)[cb + lane + 64 * p] = y;
+                if (EPI && on[p]) {
+                    const float *w2 = a.W2 + (long)(cb + lane + 64 * p) * 12;
+                    z0 += y.x * w2[0] + y.y * w2[3] + y.z * w2[6] + y.w * w2[9];
+                    z1 += y.x * w2[1] + y.y * w2[4] + y.z * w2[7] + y.w * w2[10];
+                    z2 += y.x * w2[2] + y.y * w2[5] + y.z * w2[8] + y.w * w2[11];
+                }
+            }
+        }
+        if (EPI) {
+            z0 = gmc::wave_sum(z0); z1 = gmc::wave_sum(z1); z2 = gmc::wave_sum(z2);
+            if (lane == 0) {
+                float *z = a.Z0 + r * 3;
+                z[0] = z0 * s; z[1] = z1 * s; z[2] = z2 * s;
+            }
+        }
+    }
+}
+
 // Any F / any alignment: lane owns single columns; used for odd hidden sizes only.
 template <bool HAS_VAL>
 __global__ __launch_bounds__(256) void spmm_rows_scalar(SpmmArgs a) {
@@ -250,7 +338,25 @@ const Tune &tune() {
 }
 
 template <int VARIANT>
+int launch_wide(SpmmArgs a, int group_rows, hipStream_t st) {
+    constexpr int rows_per_wg = kRowsPerWave * kWavesPerWg;
+    const int grid = (a.n_rows + rows_per_wg - 1) / rows_per_wg;
+    a.group_wgs = group_rows > 0 ? (group_rows + rows_per_wg - 1) / rows_per_wg : 0;
+    const bool hv = a.vals != nullptr, epi = a.Z0 != nullptr;
+    if (hv) {
+        if (epi) hipLaunchKernelGGL((spmm_rows_wide<kRowsPerWave, kUnroll, true, true, VARIANT>), dim3(grid), dim3(256), 0, st, a);
+        else hipLaunchKernelGGL((spmm_rows_wide<kRowsPerWave, kUnroll, true, false, VARIANT>), dim3(grid), dim3(256), 0, st, a);
+    } else {
+        if (epi) hipLaunchKernelGGL((spmm_rows_wide<kRowsPerWave, kUnroll, false, true, VARIANT>), dim3(grid), dim3(256), 0, st, a);
+        else hipLaunchKernelGGL((spmm_rows_wide<kRowsPerWave, kUnroll, false, false, VARIANT>), dim3(grid), dim3(256), 0, st, a);
+    }
+    GMC_LAUNCH_CHECK();
+    return GMC_OK;
+}
+
+template <int VARIANT>
 int launch_np(const SpmmArgs &a, int group_rows, hipStream_t st) {
+    if (a.F > 1024) return launch_wide<VARIANT>(a, group_rows, st);
     if (a.F <= 256) return launch_cfg<1, kRowsPerWave, kUnroll, false, VARIANT>(a, group_rows, st);
     if (a.F <= 512) {
         if (VARIANT == 0 && tune().rpw) {
@@ -280,7 +386,7 @@ int gmc_spmm_launch(const int32_t *rowptr, const int32_t *col, const float *vals
     SpmmArgs a{rowptr, col, vals, scale, X, (long)ldx, bias, relu, Y, (long)ldy,
                n_rows, F, 0, W2, Z0};
     const bool vec = (F % 4 == 0) && (ldx % 4 == 0) && (ldy % 4 == 0) && gmc_aligned16(X) &&
-                     gmc_aligned16(Y) && (!bias || gmc_aligned16(bias)) && F <= 1024;
+                     gmc_aligned16(Y) && (!bias || gmc_aligned16(bias)) && F <= GMC_MAX_HIDDEN;
     GmcProbeScope probe(tag, st);
     if (!vec) {
         if (Z0) return GMC_ERR_UNSUPPORTED;  // callers use gmc_dense_hw2_f32 instead

@@ -28,6 +28,10 @@ def flat_layout(N: int, F: int, K: int) -> Tuple[List[int], int]:
     return offs, offs[-1]
 
 
+# widest hidden layer the kernels take (GMC_MAX_HIDDEN of include/gcnmaxcut.h; hidden_dim is padded to a multiple of 4)
+MAX_HIDDEN = 4096
+
+
 class FusedEngine:
     """One per model.  ``adopt`` re-homes a module's parameters into the flat buffer."""
 
@@ -37,8 +41,8 @@ class FusedEngine:
         if K != 3:
             raise ValueError("number_classes must be 3: the terminal override is 3-wide "
                              "(TrainingNeural.py:91-93)")
-        if F < 1 or F > 1024:
-            raise ValueError("hidden_dim must be in 1..1024 on this path")
+        if F < 1 or F > MAX_HIDDEN:
+            raise ValueError(f"hidden_dim must be in 1..{MAX_HIDDEN} on this path (include/gcnmaxcut.h: GMC_MAX_HIDDEN)")
         self.N, self.F, self.K = N, F, K
         # Any hidden_dim (TrainingNeural.py:42,66-67 accept any int; n_nodes=50 gives 25): the kernels work on 16-byte
         # column groups, so the flat buffer carries the hidden dimension padded to a multiple of 4 (Fp).  Pad columns of

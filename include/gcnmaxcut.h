@@ -49,6 +49,9 @@ enum {
 };
 
 #define GMC_MAX_GRAPH_NODES 4096 /* per-graph head kernel keeps [n,3] tiles in LDS */
+/* Largest hidden width F (gmc_model.F, the F of every entry point below that takes one): F must be a multiple of 4
+ * in 1..GMC_MAX_HIDDEN; wider models return GMC_ERR_UNSUPPORTED. */
+#define GMC_MAX_HIDDEN 4096
 
 /* A block-diagonal batch of B graphs resident in HBM.  This is the CSR form of what
  * graphExtender.process_graphs_from_folder emits per graph (graphExtender.py:102-114:
@@ -98,7 +101,8 @@ typedef struct gmc_batch {
 } gmc_batch;
 
 /* GCNSoftmax parameters in DGL GraphConv layout (TrainingNeural.py:72-77):
- * conv1.weight [N,F], conv1.bias [F], conv2.weight [F,K], conv2.bias [K]. */
+ * conv1.weight [N,F], conv1.bias [F], conv2.weight [F,K], conv2.bias [K].  F: a multiple of 4, at most
+ * GMC_MAX_HIDDEN (callers pad a hidden width that is not: gcn-max-cut_amd/engine.py). */
 typedef struct gmc_model {
     int32_t abi;   /* GMC_VERSION of the header the caller was compiled against (checked) */
     int32_t N, F, K;
@@ -205,7 +209,9 @@ enum {
  * (fwd1, then bwd1; one_graph_step != 0: as gmc_train_step_f32 runs it, which computes a one-graph batch's head
  * inside the backward), then the one-kernel-per-operation sequence of gmc_set_fuse(0) (W1 gather, aggregation with
  * the W2 epilogue, backward aggregation, dW1), the latter only for batches without overflow lists.  Returns the
- * number of words (writes up to `max`), 0 when the batch takes the row kernels, <0 on bad arguments. */
+ * number of words (writes up to `max`), 0 when the batch takes the row kernels, <0 on bad arguments (F not a
+ * multiple of 4 in 1..GMC_MAX_HIDDEN: GMC_ERR_SHAPE).  Wider F is a runtime slice count of the same kernels: every
+ * word for F > 1024 is, with GMC_FLV_PER cleared, one that F = 1024 gives for the same batch. */
 int gmc_lds_flavours(const gmc_batch *batch, int32_t F, int32_t one_graph_step, int32_t *words, int32_t max);
 
 /* ---- building blocks (each is also used by the fused entry points below) ---------- */
@@ -217,7 +223,9 @@ int gmc_lds_flavours(const gmc_batch *batch, int32_t F, int32_t one_graph_step, 
  * group_rows > 0 asks for XCD-grouped scheduling: consecutive runs of that many rows
  * (one graph) are processed by workgroups of one XCD so neighbour rows are L2 hits.
  * If W2/Z0 are non-NULL (K must be 3) the layer-2 feature transform is fused into the
- * epilogue: Z0[r,:] = scale[r] * (Y[r,:] @ W2)   ((H*outdeg^-1/2)@W2, :83). */
+ * epilogue: Z0[r,:] = scale[r] * (Y[r,:] @ W2)   ((H*outdeg^-1/2)@W2, :83).
+ * Any F >= 1; the 16-byte vector kernels serve F % 4 == 0 up to GMC_MAX_HIDDEN (wider or unaligned F without W2:
+ * one column per lane; with W2: GMC_ERR_UNSUPPORTED). */
 int gmc_spmm_f32(const int32_t *rowptr, const int32_t *col, const float *vals,
                  const float *scale, const float *X, int64_t ldx, const float *bias, int relu,
                  float *Y, int64_t ldy, int32_t n_rows, int32_t F, int32_t group_rows,
@@ -286,7 +294,8 @@ int gmc_publish_adam_devstep_model_f32(const float *publish_src, int32_t publish
                                        double lr, double beta1, double beta2, double eps, int32_t *step_counter,
                                        gmc_stream_t stream);
 
-/* bytes of scratch gmc_forward / gmc_train_fwd_bwd need for this batch and model */
+/* bytes of scratch gmc_forward / gmc_train_fwd_bwd need for this batch and model (64-bit sizes: R * F may exceed
+ * 2^31 elements) */
 size_t gmc_workspace_bytes(const gmc_batch *batch, const gmc_model *model, int training);
 
 /* GCNSoftmax.forward for every graph of the batch (TrainingNeural.py:79-85):
