@@ -17,6 +17,7 @@ RCCL all-reduce of the flat gradient per step.
 """
 from __future__ import annotations
 
+import enum
 import os
 import warnings
 import random  # noqa: F401  (reference namespace)
@@ -317,8 +318,44 @@ def _graphs_per_step(explicit: Optional[int]) -> int:
 
 
 _NOT_LANDED = np.uint32(0x7FC0DEAD)   # quiet-NaN payload no arithmetic produces: "this loss slot has not been written"
-_SPIN_BEFORE_YIELD = 2048             # ~0.5 ms of looks before the polling loops start yielding the core
+_SPIN_BEFORE_YIELD = 2048             # ~0.5 ms of looks before the polling loop starts yielding the core
 _POLL_DEADLINE_S = 5.0
+
+
+def _arm(bits: np.ndarray) -> None:
+    """Mark every slot of a pinned loss buffer "not landed" before the launches that fill it.  The mark is a BIT
+    PATTERN no kernel produces (`_NOT_LANDED`), so a loss that genuinely IS NaN (diverged weights) counts as landed
+    and comes back as NaN at once - as `loss.item()` would (TrainingNeural.py:387-388)."""
+    bits.fill(_NOT_LANDED)
+
+
+class Launch(enum.Enum):
+    """How :meth:`FusedTrainer.epoch` launches an epoch (chosen by :func:`launch_path`)."""
+    DROPOUT = "dropout"       # eager one-kernel-per-operation sequence, a fresh dropout mask per step
+    GRAPH = "graph"           # the whole epoch replayed from one hipGraph
+    DIRECT = "direct"         # eager train_step launches storing the losses straight into the pinned host slots
+    COPY = "copy"             # eager train_step launches, then a copy of the losses and a stream synchronisation
+    DP = "dp"                 # data-parallel sequence (shard step -> all-reduce -> Adam), eager
+    DP_GRAPHS = "dp_graphs"   # the same with hipGraphs on either side of the eager all-reduce
+
+
+def launch_path(*, dp: bool, dropout: float, allow_graph: bool, fused_step: bool, steps: int, mapped: bool,
+                poll: bool, dp_graphs: bool) -> Launch:
+    """The launch path of one epoch, from its facts.  Dropout: a fresh mask per step (a replayed graph would repeat
+    one).  Data-parallel: eager - as fast as graphs (0.246 against 0.249 ms per step on one rank over RCCL) and no
+    stream capture beside RCCL's threads - unless GCN_MAXCUT_DP_GRAPHS=1 (``dp_graphs``).  An engine without the
+    fused ``train_step`` runs the same sequence, whose all-reduce is then a no-op.  Otherwise the fused
+    ``train_step``: several steps are captured once into a hipGraph (no per-launch host cost); ONE step runs eager
+    when its losses can be stored into pinned slots (``mapped``) that the host watches (``poll``), so the host
+    queues the next step behind this step's backward (0.2259 against 0.2288 ms for a graph replay per step)."""
+    if dropout > 0.0:
+        return Launch.DROPOUT
+    if dp or not fused_step:
+        return Launch.DP_GRAPHS if dp and allow_graph and dp_graphs else Launch.DP
+    direct = mapped and poll
+    if allow_graph and (steps > 1 or steps == 1 and not direct):
+        return Launch.GRAPH
+    return Launch.DIRECT if direct else Launch.COPY
 
 
 class FusedTrainer:
@@ -339,18 +376,20 @@ class FusedTrainer:
         # dp: steps run the data-parallel sequence (shard step -> all-reduce -> Adam).  More than one rank, or a
         # single rank asked to (GCN_MAXCUT_DP_SINGLE_RANK=1: RCCL and the graphs around it on a one-GPU box)
         self.dp = dp_active()
-        if self.dp and hasattr(self.eng, "sync_replicas"):
+        if self.dp:
             self.eng.sync_replicas(0)   # one model: rank 0's parameters / moments on every replica
-        # the fused forward of this trainer's steps reads the engine's slab copy of conv1.weight (FusedEngine.ensure_slab)
-        self._slab = {"slab": True} if hasattr(self.eng, "ensure_slab") else {}
+        # what the engine offers: the fused step; scratch, slab copy of W1, device-stepped Adam (not host stand-ins)
+        self._fused_step = hasattr(self.eng, "train_step")
+        self._hip = hasattr(self.eng, "adam_step_dev")
+        self._dp_graphs_env = os.environ.get("GCN_MAXCUT_DP_GRAPHS", "0") == "1"
         self._plan_key = None
         self._ws: Optional[torch.Tensor] = None   # scratch of this trainer's steps (captured graphs point into it)
         self._graph_key = None
-        self._graph_env = None
-        self._poll = os.environ.get("GCN_MAXCUT_POLL_LOSS", "1") != "0"   # watch the pinned loss slots instead of a stream sync
+        self._poll = True           # watch the pinned loss slots instead of a stream sync (off after a deadline hit)
         self._dp_graph = None       # (per-step forward/backward hipGraphs, Adam hipGraph) of a data-parallel rank
         self._dp_graph_key = None
-        self.allow_graph = True     # set False to force eager launches (per-kernel probing)
+        # False: eager launches only (per-kernel probing; an engine off the GPU has no hipGraphs)
+        self.allow_graph = self.eng.device.type == "cuda"
         self._graph = None          # hipGraph of one whole epoch (single GPU)
         self._graph_steps = 0
         self._batches: List[GraphBatch] = []
@@ -359,7 +398,7 @@ class FusedTrainer:
         self._step_host: Optional[torch.Tensor] = None
         self._out = None
         self.last_enqueue_s = 0.0
-        self.deadline_hits = 0      # epochs whose losses did not land within the polling deadline (see _wait_for_losses)
+        self.deadline_hits = 0      # epochs whose losses did not land within the polling deadline (see _landed)
 
     def invalidate(self) -> None:
         """Forget the planned batches (and the captured hipGraphs with them): the next epoch walks the dataset
@@ -411,27 +450,23 @@ class FusedTrainer:
                            if dev.type == "cuda" else None)
         self._loss_host_np = self._loss_host.numpy() if self._loss_host is not None else None   # (shares the pinned memory)
         self._loss_host_bits = self._loss_host_np.view(np.uint32) if self._loss_host_np is not None else None
-        # device-side address of that pinned buffer: the captured steps store their per-graph losses straight
-        # into it (one system-scope store each, as soon as the value is final), so the host has a step's loss
-        # while its backward is still running and no copy node trails the graph (GCN_MAXCUT_LOSS_ZEROCOPY=0: copy)
-        self._loss_host_dev = None
-        if (self._loss_host is not None and hasattr(self.eng, "lib") and self._poll
-                and os.environ.get("GCN_MAXCUT_LOSS_ZEROCOPY", "1") != "0"):
-            self._loss_host_dev = hip.mapped_ptr(self._loss_host)
+        self._loss_rows = ([(self._loss_host_bits[i, :b.B], self._loss_host_np[i, :b.B])   # (bits, values) of each step
+                            for i, b in enumerate(self._batches) if b.B] if self._loss_host is not None else [])
+        # device-side address of that pinned buffer (None when the runtime cannot map it, or polling is off): the
+        # steps store their per-graph losses straight into it (one system-scope store each, as soon as the value is
+        # final), so the host has a step's loss while its backward is still running and no copy node trails the graph
+        self._loss_host_dev = hip.mapped_ptr(self._loss_host) if self._loss_host is not None and self._poll else None
         self._step_host = (torch.empty_like(self._step_loss, device="cpu").pin_memory()
                            if dev.type == "cuda" else None)
         self._step_host_np = self._step_host.numpy() if self._step_host is not None else None
         self._step_host_bits = self._step_host_np.view(np.uint32) if self._step_host_np is not None else None
         # data-parallel steps: the all-reduced loss of a step (the gradient's tail slot) is published to this pinned
         # buffer by a one-wave launch BEFORE the step's Adam launches, so the host has it while Adam still runs
-        self._step_host_dev = None
-        if (self._step_host is not None and hasattr(self.eng, "publish") and self._poll
-                and os.environ.get("GCN_MAXCUT_LOSS_ZEROCOPY", "1") != "0"):
-            self._step_host_dev = hip.mapped_ptr(self._step_host)
+        self._step_host_dev = hip.mapped_ptr(self._step_host) if self._step_host is not None and self._poll else None
         # private scratch, sized for the largest step: the engine's own scratch is re-allocated whenever a
         # later call (evaluate_model on a bigger batch, another trainer) needs more, which would leave a
         # captured hipGraph replaying into freed memory
-        if hasattr(self.eng, "workspace_bytes") and self._batches:
+        if self._hip and self._batches:
             drop = float(getattr(self.net, "dropout_frac", 0.0) or 0.0)
             if drop > 0.0:   # the dropout sequence needs a little more scratch: size for it
                 self.eng.set_dropout(drop, 0)
@@ -461,205 +496,136 @@ class FusedTrainer:
         """One pass over the dataset; returns the cumulative loss (one host sync)."""
         t_entry = perf_counter()
         self.prepare(dataset)
-        eng, cfg = self.eng, self.config
         drop = self._dropout()
-        if drop > 0.0:
-            # dropout: eager launches of the one-kernel-per-operation sequence, a fresh mask per step (the
-            # captured graphs would replay one mask; every reference configuration trains with p = 0)
-            lr, betas, eps = self._hyper()
-            tail = eng.grad[eng.count:eng.count + 1]
-            for i, batch in enumerate(self._batches):
-                eng.set_dropout(drop)
-                if batch.B == 0:
-                    eng.grad[:eng.count + 1].zero_()
-                else:
-                    eng.train_fwd_bwd(batch, cfg.C, out=(self._out[0], self._out[1], self._loss_slots[i]), ws=self._ws)
-                if self.dp:
-                    eng.allreduce_grad()
-                self._step_loss[i:i + 1].copy_(tail)
-                eng.adam_step(lr, betas, eps)
-            eng.set_dropout(0.0)
-            return float(self._step_loss.cpu().numpy().sum(dtype=np.float64))
-        use_graph = self._use_graph()
-        publish = None
-        # eager launches with the losses stored straight into the pinned buffer: the host is back as soon as the
-        # loss kernels have run and queues the next step's launches behind this step's backward
-        eager_direct = (not use_graph and not self.dp and hasattr(eng, "train_step") and self._poll
-                        and getattr(self, "_loss_host_dev", None) is not None)
-        poll = (use_graph or eager_direct) and self._poll and self._loss_host_np is not None
-        if poll:
-            self._loss_host_bits.fill(_NOT_LANDED)   # sentinel bit pattern: no kernel produces it, a NaN LOSS is not it
-        if use_graph:
-            self._replay_epoch()
-        elif not self.dp and hasattr(eng, "train_step"):
-            eng.sync_step_dev()
-            self._enqueue_epoch(with_readback=eager_direct)
+        path = launch_path(dp=self.dp, dropout=drop, allow_graph=self.allow_graph, fused_step=self._fused_step,
+                           steps=len(self._batches), mapped=self._loss_host_dev is not None, poll=self._poll,
+                           dp_graphs=self._dp_graphs_env)
+        if path is Launch.DROPOUT:
+            self._run_dropout(drop)
+        elif path is Launch.DP or path is Launch.DP_GRAPHS:
+            self._run_dp(graphs=path is Launch.DP_GRAPHS)
+        elif path is Launch.GRAPH:
+            self._run_graph()
         else:
-            # the step's loss rides in the gradient all-reduce: train_fwd_bwd leaves the shard's loss sum
-            # in the slot after the gradient (GMC_MODEL_GRAD_TAIL), the all-reduce makes it the batch's
-            tail = eng.grad[eng.count:eng.count + 1]
-            last = len(self._batches) - 1
-            lr, betas, eps = self._hyper()
-            graphs = self._dp_graphs() if self._use_dp_graph() else None
-            if graphs is not None:
-                eng.sync_step_dev()
-                if self._slab:
-                    eng.ensure_slab()   # (a launch only when torch wrote the parameters since the last step)
-            publish = self._step_host_dev if self.dp else None
-            if publish:
-                self._step_host_bits.fill(_NOT_LANDED)   # sentinel bit pattern (a NaN loss is a landed value)
-            for i, batch in enumerate(self._batches):
-                if batch.B == 0:
-                    # this rank's shard of the step is empty (last group smaller than the world): it
-                    # contributes a zero gradient and a ZERO loss - the tail slot still holds the previous
-                    # step's all-reduced loss and would otherwise be added once more per empty rank
-                    eng.grad[:eng.count + 1].zero_()
-                elif graphs is not None:
-                    graphs[0][i].replay()              # forward + loss + backward + gradient fold of my shard
-                else:
-                    eng.train_fwd_bwd(batch, cfg.C, out=(self._out[0], self._out[1], self._loss_slots[i]),
-                                      **({"ws": self._ws} if self._ws is not None else {}), **self._slab)
-                fused_publish = None
-                if self.dp:
-                    eng.allreduce_grad()               # ONE RCCL all-reduce of [gradient | loss] per step, eager
-                    if publish and graphs is None and self._slab and hasattr(eng, "adam_step_dev"):
-                        fused_publish = (tail, publish + 4 * i)   # rides in front of the Adam launch below
-                    elif publish:                      # the step's loss -> pinned host slot i, ahead of Adam
-                        eng.publish(tail, publish + 4 * i)
-                    elif i != last:                    # the last step's slot is read in place below
-                        self._step_loss[i:i + 1].copy_(tail)
-                if graphs is not None:
-                    graphs[1].replay()                 # Adam, step number read from / advanced in device memory
-                    eng.step_count += 1
-                    eng._dev_step += 1
-                elif self._slab and hasattr(eng, "adam_step_dev"):
-                    eng.sync_step_dev()                # (a launch only after host-stepped updates)
-                    # keeps the slab copy of W1 current; with `publish`: loss store + counter tick + Adam in two launches
-                    eng.adam_step_dev(lr, betas, eps, **self._slab, **({"publish": fused_publish} if fused_publish else {}))
-                else:
-                    eng.adam_step(lr, betas, eps)
+            self._run_eager(direct=path is Launch.DIRECT)
         self.last_enqueue_s = perf_counter() - t_entry   # host time to queue the epoch's launches (bench.py reports it)
-        if self.dp:   # one host sync per epoch
-            if not self._batches:
-                return 0.0
-            if self._step_host is not None:
-                host, bits = self._step_host_np, self._step_host_bits
-                if self._poll and not publish:
-                    bits.fill(_NOT_LANDED)   # sentinel bit pattern (a NaN loss is a landed value)
-                if publish:
-                    pass            # every step has already sent its loss
-                elif last == 0:   # one step per epoch: its loss goes from the gradient's tail slot to the host
-                    self._step_host.copy_(tail, non_blocking=True)
-                else:
-                    self._step_loss[last:last + 1].copy_(tail)
-                    self._step_host.copy_(self._step_loss, non_blocking=True)
-                if self._poll:   # watch the pinned slots instead of sleeping in the stream sync (see _wait_for_losses)
-                    spins, deadline = 0, None
-                    while True:
-                        if bits[last] != _NOT_LANDED and not (bits == _NOT_LANDED).any():
-                            return float(host.sum(dtype=np.float64))
-                        spins += 1
-                        if spins > _SPIN_BEFORE_YIELD and spins & 63 == 0:
-                            sleep(0)   # give the core away: RCCL's proxy threads and the other ranks' hosts share it
-                            now = time()
-                            deadline = deadline or now + _POLL_DEADLINE_S
-                            if now > deadline:
-                                self._deadline_hit()
-                                break
-                torch.cuda.current_stream().synchronize()
-                return float(host.sum(dtype=np.float64))
-            self._step_loss[last:last + 1].copy_(tail)
-            return float(sum(self._step_loss.cpu().tolist()))
-        # one device->host copy per epoch; the reference adds one float per optimizer step
-        # (loss.item(), :388), each the sum of that step's per-graph losses
-        if self._loss_host is not None:
-            if not use_graph and not eager_direct:   # (the replayed graph ends with this copy / stores directly)
-                self._loss_host.copy_(self._loss_slots, non_blocking=True)
-            host = self._loss_host_np
-            if poll:
-                return self._wait_for_losses(host)
-            torch.cuda.current_stream().synchronize()
-        else:
-            host = self._loss_slots.cpu().numpy()
-        if len(self._batches) == 1:
-            return float(host[0, :self._batches[0].B].sum(dtype=np.float32))
-        total = 0.0
-        for i, batch in enumerate(self._batches):
-            total += float(host[i, :batch.B].sum(dtype=np.float32))
-        return total
+        if path is Launch.DROPOUT:
+            return float(self._step_loss.cpu().numpy().sum(dtype=np.float64))
+        if path is Launch.DP or path is Launch.DP_GRAPHS:
+            return self._step_losses()
+        return self._slot_losses(copy=path is Launch.COPY)
 
-    def _wait_for_losses(self, host: np.ndarray) -> float:
-        """The loss kernels store every graph's loss straight into pinned host memory (or the replayed graph ends
-        with that copy): the host watches that memory instead of sleeping in hipStreamSynchronize (whose wake-up
-        costs ~10 us per step of a 0.25 ms step).  "Not landed yet" is a BIT PATTERN (`_NOT_LANDED`, a NaN payload
-        no kernel produces) the slots are filled with before the launch, so a loss that genuinely IS NaN (diverged
-        weights) counts as landed and comes back as NaN at once - as `loss.item()` would (TrainingNeural.py:387-388).
-        After ~0.5 ms of spinning the loop yields the core between looks; slots that have not landed within
-        `_POLL_DEADLINE_S` hand over to the stream synchronisation - which reports whatever went wrong on the device -
-        and polling is switched off for the rest of the run with ONE warning (e.g. pinned memory that is not
-        host-coherent: every epoch would otherwise pay the deadline).  Returns the epoch's cumulative loss."""
-        bits = self._loss_host_bits
-        total, deadline = 0.0, None
+    # ---- launch paths (launch_path says which one an epoch takes)
+    def _run_dropout(self, drop: float) -> None:
+        """The one-kernel-per-operation sequence with a fresh dropout mask per step."""
+        eng, cfg = self.eng, self.config
+        lr, betas, eps = self._hyper()
+        tail = eng.grad[eng.count:eng.count + 1]
         for i, batch in enumerate(self._batches):
-            nb = batch.B
-            if nb == 0:
-                continue
-            row, brow, spins = host[i], bits[i], 0
-            while True:
-                if brow[nb - 1] != _NOT_LANDED and brow[0] != _NOT_LANDED and not (brow[:nb] == _NOT_LANDED).any():
-                    total += float(row[:nb].sum(dtype=np.float32))
-                    break
-                spins += 1
-                if spins > _SPIN_BEFORE_YIELD and spins & 63 == 0:
-                    sleep(0)
-                    now = time()
-                    deadline = deadline or now + _POLL_DEADLINE_S
-                    if now > deadline:   # the stream is done after this: whatever the slots hold IS the result
-                        torch.cuda.current_stream().synchronize()   # (raises if the device faulted)
-                        self._deadline_hit()
-                        total += float(row[:nb].sum(dtype=np.float32))
-                        break
-        return total
+            eng.set_dropout(drop)
+            if batch.B == 0:
+                eng.grad[:eng.count + 1].zero_()
+            else:
+                eng.train_fwd_bwd(batch, cfg.C, out=(self._out[0], self._out[1], self._loss_slots[i]), ws=self._ws)
+            if self.dp:
+                eng.allreduce_grad()
+            self._step_loss[i:i + 1].copy_(tail)
+            eng.adam_step(lr, betas, eps)
+        eng.set_dropout(0.0)
 
-    def _deadline_hit(self) -> None:
-        self.deadline_hits += 1
+    def _run_eager(self, direct: bool) -> None:
+        """Eager train_step launches; ``direct``: the losses are stored straight into the pinned host slots, so the
+        host is back as soon as the loss kernels have run and queues the next step behind this step's backward."""
+        if direct:
+            _arm(self._loss_host_bits)
+        self.eng.sync_step_dev()
+        self._train_steps(self._loss_host_dev if direct else None)
+
+    def _run_graph(self) -> None:
+        """Replay the epoch's hipGraph (captured on the first epoch, which itself runs eager)."""
+        eng = self.eng
         if self._poll:
-            self._poll = False
-            warnings.warn("GCN max-cut: the step's losses did not reach the pinned host buffer within "
-                          f"{_POLL_DEADLINE_S:.0f} s of polling; falling back to stream synchronisation for the rest "
-                          "of this run (is the pinned memory host-coherent? HIP_HOST_COHERENT=0 breaks zero-copy stores)")
+            _arm(self._loss_host_bits)
+        eng.sync_step_dev()   # (no launch while this trainer's replays are the only thing stepping the optimizer)
+        # the captured launches carry lr / betas / eps / C and the scratch pointer as kernel arguments
+        key = (self._hyper(), float(self.config.C), self._ws.data_ptr() if self._ws is not None else 0)
+        if self._graph is not None and key != self._graph_key:
+            self._graph = None
+        self._graph_key = key
+        if self._graph is None:
+            self._train_steps(None)               # eager epoch: sizes the workspace, warms the kernels
+            graph = torch.cuda.CUDAGraph()
+            before = eng.step_count
+            with torch.cuda.graph(graph):
+                self._train_steps(self._loss_host_dev)
+                if self._loss_host_dev is None:   # the graph ends with the copy of the losses
+                    self._loss_host.copy_(self._loss_slots, non_blocking=True)
+            eng.step_count = eng._dev_step = before   # capture enqueued nothing
+            self._graph, self._graph_steps = graph, len(self._batches)
+            self._loss_host.copy_(self._loss_slots, non_blocking=True)   # this (eager) epoch's losses
+            return
+        eng.ensure_slab()   # (a launch only when torch wrote the parameters since the last replay)
+        self._graph.replay()
+        eng.step_count += self._graph_steps
+        eng._dev_step += self._graph_steps
 
-    def _use_graph(self) -> bool:
-        """On one GPU an epoch's launches (the reference's one Adam step per graph: hundreds of
-        ~10 us kernels; or one batched step: six) are captured once into a hipGraph and replayed per
-        epoch, which removes the per-launch host cost."""
-        if self._graph_env is None:   # process-wide facts, looked up once
-            self._graph_env = torch.cuda.is_available() and os.environ.get("GCN_MAXCUT_HIPGRAPH", "1") != "0"
-        if not (self.allow_graph and not self.dp and self._graph_env and len(self._batches) >= 1
-                and hasattr(self.eng, "train_step")):
-            return False
-        # ONE step per epoch (the batched schedule): four eager launches, queued behind the previous step's
-        # backward as soon as its losses have reached the pinned buffer, run back to back; a graph replay per step
-        # pays the ~10 us between two graph executions instead (measured: 0.2259 vs 0.2288 ms per step)
-        if (len(self._batches) == 1 and self._poll and getattr(self, "_loss_host_dev", None) is not None
-                and os.environ.get("GCN_MAXCUT_EAGER_SINGLE_STEP", "1") != "0"):
-            return False
-        return True
+    def _train_steps(self, loss_dev: Optional[int]) -> None:
+        """One fused train_step launch per step; ``loss_dev``: device address of the pinned slots that get the losses."""
+        eng, cfg = self.eng, self.config
+        lr, betas, eps = self._hyper()
+        row_bytes = self._loss_slots.shape[1] * 4
+        for i, batch in enumerate(self._batches):
+            eng.train_step(batch, lr, cfg.C, out=(self._out[0], self._out[1], self._loss_slots[i]), betas=betas, eps=eps,
+                           ws=self._ws, slab=True, loss_ptr=loss_dev + i * row_bytes if loss_dev else None)
 
-    def _use_dp_graph(self) -> bool:
-        """Data-parallel ranks launch eagerly by default: the host has a step's loss before its Adam launches run
-        (publish) and queues the next step's launches behind them, which is as fast as replaying graphs (0.246 against
-        0.249 ms per step on one rank over RCCL) and keeps stream capture away from RCCL's threads.
-        GCN_MAXCUT_DP_GRAPHS=1: the launches on either side of the all-reduce are replayed from hipGraphs - one
-        per step for forward/loss/backward, one for Adam."""
-        return (self.allow_graph and self.dp and hasattr(self.eng, "adam_step_dev") and self._ws is not None
-                and torch.cuda.is_available() and os.environ.get("GCN_MAXCUT_HIPGRAPH", "1") != "0"
-                and os.environ.get("GCN_MAXCUT_DP_GRAPHS", "0") == "1")
+    def _run_dp(self, graphs: bool) -> None:
+        """Shard step, ONE RCCL all-reduce of [gradient | loss], Adam.  The step's loss rides in the all-reduce (the
+        slot after the gradient, GMC_MODEL_GRAD_TAIL) and reaches pinned slot i ahead of the step's Adam: fused into
+        the Adam launch (eager), a publish launch (``graphs``), or a device copy when the slots are not mapped."""
+        eng, cfg = self.eng, self.config
+        tail = eng.grad[eng.count:eng.count + 1]
+        last = len(self._batches) - 1
+        lr, betas, eps = self._hyper()
+        publish = self._step_host_dev
+        if self._poll and self._step_host is not None:
+            _arm(self._step_host_bits)
+        if graphs:
+            fwd_bwd, adam = self._dp_graphs()
+            eng.sync_step_dev()
+            eng.ensure_slab()   # (a launch only when torch wrote the parameters since the last step)
+        for i, batch in enumerate(self._batches):
+            if batch.B == 0:
+                # this rank's shard of the step is empty (last group smaller than the world): it
+                # contributes a zero gradient and a ZERO loss - the tail slot still holds the previous
+                # step's all-reduced loss and would otherwise be added once more per empty rank
+                eng.grad[:eng.count + 1].zero_()
+            elif graphs:
+                fwd_bwd[i].replay()                   # forward + loss + backward + gradient fold of my shard
+            elif self._hip:
+                eng.train_fwd_bwd(batch, cfg.C, out=(self._out[0], self._out[1], self._loss_slots[i]), ws=self._ws,
+                                  slab=True)
+            else:
+                eng.train_fwd_bwd(batch, cfg.C, out=(self._out[0], self._out[1], self._loss_slots[i]))
+            eng.allreduce_grad()                      # ONE RCCL all-reduce of [gradient | loss] per step, eager
+            if not publish and i != last:             # (the last step's slot is read in place: _step_losses)
+                self._step_loss[i:i + 1].copy_(tail)
+            if graphs:
+                if publish:
+                    eng.publish(tail, publish + 4 * i)
+                adam.replay()                         # Adam, step number read from / advanced in device memory
+                eng.step_count += 1
+                eng._dev_step += 1
+            elif self._hip:
+                eng.sync_step_dev()                   # (a launch only after host-stepped updates)
+                # keeps the slab copy of W1 current; with `publish`: loss store + counter tick + Adam in two launches
+                eng.adam_step_dev(lr, betas, eps, slab=True, publish=(tail, publish + 4 * i) if publish else None)
+            else:
+                eng.adam_step(lr, betas, eps)
 
     def _dp_graphs(self):
         eng, cfg = self.eng, self.config
         hyper = self._hyper()
-        key = (hyper, float(cfg.C), self._ws.data_ptr())
+        key = (hyper, float(cfg.C), self._ws.data_ptr() if self._ws is not None else 0)
         if self._dp_graph is not None and self._dp_graph_key == key:
             return self._dp_graph
         lr, betas, eps = hyper
@@ -669,59 +635,93 @@ class FusedTrainer:
                 fb.append(None)
                 continue
             out = (self._out[0], self._out[1], self._loss_slots[i])
-            eng.train_fwd_bwd(batch, cfg.C, out=out, ws=self._ws, **self._slab)     # eager once: warms the kernels
+            eng.train_fwd_bwd(batch, cfg.C, out=out, ws=self._ws, slab=True)     # eager once: warms the kernels
             g = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g):
-                eng.train_fwd_bwd(batch, cfg.C, out=out, ws=self._ws, **self._slab)
+                eng.train_fwd_bwd(batch, cfg.C, out=out, ws=self._ws, slab=True)
             fb.append(g)
         before, flat, m, v = eng.step_count, eng.flat.clone(), eng.m.clone(), eng.v.clone()
         eng.sync_step_dev()
-        eng.adam_step_dev(lr, betas, eps, **self._slab)                # eager once (state restored below)
+        eng.adam_step_dev(lr, betas, eps, slab=True)                # eager once (state restored below)
         ga = torch.cuda.CUDAGraph()
         with torch.cuda.graph(ga):
-            eng.adam_step_dev(lr, betas, eps, **self._slab)
+            eng.adam_step_dev(lr, betas, eps, slab=True)
         eng.flat.copy_(flat); eng.m.copy_(m); eng.v.copy_(v)
         eng.step_count = before
-        eng._dev_step = -1                                             # (the capture pass counted on the host only)
+        eng._dev_step = -1                                          # (the capture pass counted on the host only)
         eng.sync_step_dev()
         self._dp_graph, self._dp_graph_key = (fb, ga), key
         return self._dp_graph
 
-    def _enqueue_epoch(self, with_readback: bool = False) -> None:
-        eng, cfg = self.eng, self.config
-        lr, betas, eps = self._hyper()
-        direct = self._loss_host_dev if with_readback else None
-        row_bytes = self._loss_slots.shape[1] * 4 if self._loss_slots is not None else 0
-        for i, batch in enumerate(self._batches):
-            extra = {"loss_ptr": direct + i * row_bytes} if direct else {}
-            eng.train_step(batch, lr, cfg.C, out=(self._out[0], self._out[1], self._loss_slots[i]), betas=betas, eps=eps,
-                           ws=self._ws, **self._slab, **extra)
-        if with_readback and self._loss_host is not None and not direct:
-            self._loss_host.copy_(self._loss_slots, non_blocking=True)
+    # ---- the epoch's loss (one host sync)
+    def _slot_losses(self, copy: bool) -> float:
+        """Cumulative loss of a single-GPU epoch: the reference adds one float per optimizer step (loss.item(),
+        :388), each the sum of that step's per-graph losses.  ``copy``: the losses are still in the device slots."""
+        if self._loss_host is None:
+            host = self._loss_slots.cpu().numpy()
+            rows = [host[i, :b.B] for i, b in enumerate(self._batches)]
+        elif not copy and self._poll:
+            rows = self._landed(self._loss_rows)   # (each step's sum is taken while the later steps still run)
+        else:
+            if copy:
+                self._loss_host.copy_(self._loss_slots, non_blocking=True)
+            torch.cuda.current_stream().synchronize()
+            rows = [values for _bits, values in self._loss_rows]
+        total = 0.0
+        for values in rows:
+            total += float(values.sum(dtype=np.float32))
+        return total
 
-    def _replay_epoch(self) -> None:
-        eng = self.eng
-        eng.sync_step_dev()   # (no launch while this trainer's replays are the only thing stepping the optimizer)
-        # the captured launches carry lr / betas / eps / C and the scratch pointer as kernel arguments
-        key = (self._hyper(), float(self.config.C), self._ws.data_ptr() if self._ws is not None else 0)
-        if self._graph is not None and key != self._graph_key:
-            self._graph = None
-        self._graph_key = key
-        if self._graph is None:
-            self._enqueue_epoch()                 # eager epoch: sizes the workspace, warms the kernels
-            graph = torch.cuda.CUDAGraph()
-            before = eng.step_count
-            with torch.cuda.graph(graph):
-                self._enqueue_epoch(with_readback=True)
-            eng.step_count = eng._dev_step = before   # capture enqueued nothing
-            self._graph, self._graph_steps = graph, len(self._batches)
-            self._loss_host.copy_(self._loss_slots, non_blocking=True)   # this (eager) epoch's losses
-            return
-        if self._slab:
-            eng.ensure_slab()   # (a launch only when torch wrote the parameters since the last replay)
-        self._graph.replay()
-        eng.step_count += self._graph_steps
-        eng._dev_step += self._graph_steps
+    def _step_losses(self) -> float:
+        """Cumulative loss of a data-parallel epoch: the sum of the steps' all-reduced losses."""
+        if not self._batches:
+            return 0.0
+        eng, last = self.eng, len(self._batches) - 1
+        tail = eng.grad[eng.count:eng.count + 1]
+        if self._step_host is None:
+            self._step_loss[last:last + 1].copy_(tail)
+            return float(sum(self._step_loss.cpu().tolist()))
+        if not self._step_host_dev:
+            if last == 0:   # one step per epoch: its loss goes from the gradient's tail slot to the host
+                self._step_host.copy_(tail, non_blocking=True)
+            else:
+                self._step_loss[last:last + 1].copy_(tail)
+                self._step_host.copy_(self._step_loss, non_blocking=True)
+        if self._poll:
+            host, = self._landed([(self._step_host_bits, self._step_host_np)])
+        else:
+            torch.cuda.current_stream().synchronize()
+            host = self._step_host_np
+        return float(host.sum(dtype=np.float64))
+
+    def _landed(self, rows):
+        """Yield the values of each (bits, values) row of pinned host slots (``bits`` armed with :func:`_arm`) as soon
+        as every slot of it holds a loss.  The losses are stored there by the loss kernels or by a copy behind the
+        epoch's launches: the host watches that memory instead of sleeping in hipStreamSynchronize (whose wake-up
+        costs ~10 us per step of a 0.25 ms step).  After ~0.5 ms of spinning the loop yields the core between looks
+        (RCCL's proxy threads and the other ranks' hosts share it).  Slots that have not landed within
+        `_POLL_DEADLINE_S` hand over to the stream synchronisation - which reports whatever went wrong on the device,
+        and after which the slots hold the result - and polling is switched off for the rest of the run with ONE
+        warning (e.g. pinned memory that is not host-coherent: every epoch would otherwise pay the deadline)."""
+        deadline, synced = None, False
+        for bits, values in rows:
+            spins = 0
+            while not synced and (bits[-1] == _NOT_LANDED or bits[0] == _NOT_LANDED or (bits == _NOT_LANDED).any()):
+                spins += 1
+                if spins > _SPIN_BEFORE_YIELD and spins & 63 == 0:
+                    sleep(0)
+                    now = time()
+                    deadline = deadline or now + _POLL_DEADLINE_S
+                    if now > deadline:
+                        torch.cuda.current_stream().synchronize()   # (raises if the device faulted)
+                        self.deadline_hits += 1
+                        self._poll = False
+                        warnings.warn("GCN max-cut: the step's losses did not reach the pinned host buffer within "
+                                      f"{_POLL_DEADLINE_S:.0f} s of polling; falling back to stream synchronisation for "
+                                      "the rest of this run (is the pinned memory host-coherent? HIP_HOST_COHERENT=0 "
+                                      "breaks zero-copy stores)")
+                        synced = True
+            yield values
 
     def sync_optimizer_state(self) -> None:
         """Expose step / exp_avg / exp_avg_sq of the fused Adam through ``optimizer.state``."""

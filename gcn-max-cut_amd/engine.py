@@ -66,7 +66,7 @@ class FusedEngine:
         self.w1_slab: Optional[torch.Tensor] = None
         self._slab_sig = None
         self._adopted: List = []
-        self.slab_enabled = hip.HAS_SLAB and os.environ.get("GCN_MAXCUT_W1_SLAB", "1") != "0"
+        self.slab_enabled = True   # False: no slab copy, the fused forward reads conv1.weight itself
 
     # ---- parameters
     def views(self, buf: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
@@ -99,7 +99,7 @@ class FusedEngine:
     def ensure_slab(self) -> int:
         """Device pointer of the slab copy of conv1.weight (gmc_model.W1_slab), re-built first when a torch
         operation wrote the parameters since it was last known to be current (optimizer.step(), load_state_dict,
-        a broadcast, ...).  0 when the copy is switched off (GCN_MAXCUT_W1_SLAB=0 / an older library).  A write
+        a broadcast, ...).  0 when the copy is switched off (``slab_enabled`` = False).  A write
         torch cannot see (``param.data`` arithmetic, foreign kernels) is picked up one step late: the Adam
         kernels refresh the copy from the row-major weights on every step."""
         if not self.slab_enabled:

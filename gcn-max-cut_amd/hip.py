@@ -62,7 +62,6 @@ class GmcModel(C.Structure):
 
 
 _lib: Optional[C.CDLL] = None
-HAS_SLAB = True   # (every 0.2.x library has the W1 slab entry points; kept for callers that still ask)
 
 
 def _declare(lib: C.CDLL) -> None:

@@ -1220,22 +1220,23 @@ def test_slab_and_host_memory_entry_points_directly(pkg):
     assert hip.mapped_ptr(torch.zeros(4)) is None      # pageable memory: refused, the trainer then copies instead
 
 
-def test_one_step_epochs_same_result_on_every_launch_path(pkg, monkeypatch):
+def test_one_step_epochs_same_result_on_every_launch_trigger(pkg, monkeypatch):
     """One batched step per epoch - the bench workload's shape - through the three launch paths: eager launches
-    with the losses stored straight into pinned host memory (default), a graph replay per step, and plain eager
-    launches with a device loss buffer, a copy and a stream synchronisation.  Same losses, bit-identical models."""
+    with the losses stored straight into pinned host memory (default), a graph replay per step (the pinned buffer
+    cannot be mapped into the device), and plain eager launches with a device loss buffer, a copy and a stream
+    synchronisation (no graphs, polling switched off).  Same losses, bit-identical models."""
     specs = [(1000, 7, 91), (640, 7, 92), (1000, 7, 93)]
     ds = util.product_dataset(specs)
     runs = {}
-    for path, env in (("direct", {}), ("graph", {"GCN_MAXCUT_EAGER_SINGLE_STEP": "0"}),
-                      ("copy", {"GCN_MAXCUT_LOSS_ZEROCOPY": "0", "GCN_MAXCUT_POLL_LOSS": "0", "GCN_MAXCUT_HIPGRAPH": "0"})):
-        for k in ("GCN_MAXCUT_EAGER_SINGLE_STEP", "GCN_MAXCUT_LOSS_ZEROCOPY", "GCN_MAXCUT_POLL_LOSS", "GCN_MAXCUT_HIPGRAPH"):
-            monkeypatch.delenv(k, raising=False)
-        for k, v in env.items():
-            monkeypatch.setenv(k, v)
+    for path in ("direct", "graph", "copy"):
         T, cfg, net, embed, opt, params = model_and_params(pkg, 128, seed=17)
         tr = T.FusedTrainer(net, opt, cfg, graphs_per_step=len(specs))
-        losses = [tr.epoch(ds) for _ in range(6)]
+        with monkeypatch.context() as m:
+            if path == "graph":
+                m.setattr(pkg.hip, "mapped_ptr", lambda t: None)
+            if path == "copy":
+                tr.allow_graph, tr._poll = False, False
+            losses = [tr.epoch(ds) for _ in range(6)]
         torch.cuda.synchronize()
         if path == "direct":
             assert tr._graph is None and tr._loss_host_dev is not None

@@ -250,6 +250,31 @@ def test_sharding_helpers(built):
         assert best == dp[(w, len(ws))]
 
 
+def test_launch_path_table(T):
+    """FusedTrainer.epoch's choice of launch path, every path and every fall-back trigger."""
+    L = T.Launch
+    single = dict(dp=False, dropout=0.0, allow_graph=True, fused_step=True, steps=1, mapped=True, poll=True,
+                  dp_graphs=False)
+
+    def path(**facts):
+        return T.launch_path(**{**single, **facts})
+
+    assert path() is L.DIRECT                                   # one step, losses stored into watched pinned slots
+    assert path(mapped=False) is L.GRAPH                        # ... the pinned slots are not mapped into the device
+    assert path(poll=False) is L.GRAPH                          # ... polling switched off (deadline hit)
+    assert path(steps=2) is path(steps=160, mapped=False) is path(steps=160, poll=False) is L.GRAPH
+    assert path(steps=0) is L.DIRECT and path(steps=0, mapped=False) is L.COPY
+    assert path(allow_graph=False) is path(allow_graph=False, steps=160) is L.DIRECT
+    assert path(allow_graph=False, mapped=False) is path(allow_graph=False, poll=False, steps=160) is L.COPY
+    for facts in ({}, dict(dp=True), dict(dp=True, dp_graphs=True), dict(fused_step=False, allow_graph=False)):
+        assert path(dropout=0.5, **facts) is L.DROPOUT           # a fresh mask per step, never a replayed graph
+    assert path(dp=True) is path(dp=True, dp_graphs=True, allow_graph=False) is L.DP
+    assert path(dp=True, fused_step=False, mapped=False, poll=False, steps=3) is L.DP
+    assert path(dp=True, dp_graphs=True) is path(dp=True, dp_graphs=True, fused_step=False, steps=5) is L.DP_GRAPHS
+    # an engine without the fused train_step runs the sequence on one process too (its all-reduce is a no-op)
+    assert path(fused_step=False) is path(fused_step=False, dp_graphs=True, steps=3, mapped=False) is L.DP
+
+
 def test_bench_launcher_refuses_cleanly_without_gpus():
     """`bench.py --gpus N` (N > 1) spawns its own ranks; with fewer visible devices than ranks it must say so
     and exit non-zero BEFORE starting anything (here: no GPU at all)."""
