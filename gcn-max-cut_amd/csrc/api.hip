@@ -1,71 +1,9 @@
 // C-ABI orchestration: the fused forward / training entry points of gcnmaxcut.h.
 // Everything is enqueued on the caller's stream; nothing allocates or synchronises.
-#include "gmc_common.h"
+#include "launchers.h"
 #include <stdlib.h>
 
-// launchers defined in the kernel files
-int gmc_head_bwd_launch(const gmc_batch *, const float *, const float *, float *, float *, hipStream_t);
-int gmc_hidden_tiles(int R);
-int gmc_hidden_slab_tiles(int R);
-int gmc_hidden_bwd_slab_launch(const float *, const float *, const float *, const float *, float *, float *, int,
-                               int, int, hipStream_t);
-int gmc_lds_slice_width(const gmc_batch *b);
-int gmc_dw1_chunks(int B, bool lds, int slices);
-int gmc_lds_slices(const gmc_batch *b, int F);
-int gmc_fold_chunks_launch(const float *, float *, int, int, int, int, hipStream_t);
-bool gmc_bwd1_fits(const gmc_batch *b);
-int gmc_head_launch(const gmc_batch *, const float *, int32_t, const float *, float, float *, int32_t *, float *,
-                    float *, float *, int *, hipStream_t);
-int gmc_finish_launch(const float *, const float *, const float *, int, int, int, int, int, float *, float *, float *,
-                      float *, double, double, double, double, int *, const float *, hipStream_t, float *);
-int gmc_loss_tail_launch(const float *, int, float *, hipStream_t);
-int gmc_fwd1_lds_launch(const gmc_batch *, const float *, const float *, const float *, float *, float *, int,
-                        hipStream_t, const float *, int);
-struct gmc_bwd1_head {   // (bwd1_lds.hip) the head's arguments for a backward launch that computes it as well
-    const float *Z0; int zparts; const float *b2; float C; float *P; int *S; float *loss; float *db2part; int *tick;
-};
-bool gmc_bwd1_takes_head(const gmc_batch *b);
-int gmc_bwd1_lds_launch(const gmc_batch *, const float *, const float *, const float *, float *, float *, int, int,
-                        int, hipStream_t, const gmc_bwd1_head *);
-int gmc_hidden_bwd_launch(const float *, long, const float *, const float *, const float *, float *,
-                          long, float *, int, int, hipStream_t);
-int gmc_colsum_reduce_launch(const float *, int, int, float *, float *, const float *, int, float *,
-                             hipStream_t);
-size_t gmc_dw1_scratch_floats(const gmc_batch *b, int N, int F, bool lds);
-int gmc_dw1_launch(const gmc_batch *, const float *, long, float *, float *, int, int, bool, hipStream_t);
-bool gmc_lds_fits(const gmc_batch *b);
-int gmc_lds_groups(const gmc_batch *b, int F);
-int gmc_fwd1_flavour(const gmc_batch *b, int F);
-int gmc_bwd1_flavour(const gmc_batch *b, int F, bool head);
-int gmc_spmm_lds_flavour(const gmc_batch *b, int F, int shared_src, int use_vals, bool epi);
-int gmc_dw1_lds_flavour(const gmc_batch *b, int F);
-int gmc_spmm_lds_launch(const gmc_batch *, const float *, long, int, int, int, const float *, const float *, int,
-                        float *, long, int, int, const float *, float *, int, hipStream_t);
-int gmc_dropout_launch(float *, long, int, int, long, float, unsigned long long, hipStream_t);
-int gmc_hw2_rows_launch(const float *, const float *, const float *, float *, long, int, int, long, hipStream_t);
-int gmc_scale_copy_launch(const float *, float *, int, float, hipStream_t);
-
 namespace {
-
-struct Workspace {
-    long ld;         // row kernels: leading dimension of the [R,F] buffers (F rounded up to 32 floats)
-    int fs;          // LDS kernels: slice width of the slab layout [slice][R][fs] (0 = row-major)
-    int zparts;      // partials in Z0 (LDS path: one per slice group)
-    float *T0;       // [R,ld]  (X o dinv)@W1, later Gs = dinv o Gpre
-    float *H;        // [R,ld]  relu(conv1), later U = dinv o (A @ Gs)
-    float *Z0;       // [zparts,R,3]
-    float *GY2;      // [R,4] = (GY2[r,0..2], dinv[r])
-    float *part;     // [tiles,F,4]
-    float *db2part;  // [B,3]
-    float *dw1part;  // [chunks,N,F]
-    float *W2s;      // [F,3] = W2 / (1-p), dropout only (last, so that forward-only carving shares the prefix)
-    size_t bytes;
-};
-
-bool dropout_on(const gmc_model *m) { return m->dropout_p > 0.f; }
-bool fuse_enabled();
-bool use_lds(const gmc_batch *b, const gmc_model *m);
-unsigned long long dropout_seed(const gmc_model *m) { return ((unsigned long long)m->dropout_seed_hi << 32) | m->dropout_seed_lo; }
 
 // Fused layer kernels (default) vs the one-kernel-per-op sequence: gmc_set_fuse(0) selects the latter
 // (bench.py times the stand-alone SpMM kernel that way).  The shipped library reads no environment variables;
@@ -82,24 +20,65 @@ bool fuse_enabled() {
     return g_fuse != 0;
 }
 
-// LDS-staged tiles whenever the largest graph fits a CU's LDS.  A batch with overflow lists (rows of more than
-// ell_width neighbours) is served by the FUSED LDS kernels only: with the one-kernel-per-operation sequence
-// selected, or with dropout (which runs that sequence), it takes the row kernels.
-bool use_lds(const gmc_batch *b, const gmc_model *m) {
+// The kernel sequence of a call, decided once.  Three sequences:
+//   row kernels (fs == 0) - the largest graph does not fit a CU's LDS;
+//   fused LDS kernels (fused) - fused forward, head, fused backward + finish (train_step: + Adam);
+//   one-kernel-per-operation LDS sequence - gmc_set_fuse(0), or dropout (which needs H before the W2 product).
+// A batch with overflow lists (rows of more than ell_width neighbours) is served by the fused LDS kernels only: in the
+// one-kernel-per-operation sequence it takes the row kernels.
+struct Plan {
+    int fs;             // slice width of the LDS kernels and the slab layout [slice][R][fs]; 0 = row kernels
+    bool fused;         // fused forward and fused backward
+    bool head_in_bwd;   // train_step: the one-graph head runs inside the fused backward
+    int zparts;         // partials in Z0 (fused W2 epilogue: one per slice group)
+    int slices;         // column slices (LDS sequences)
+    int chunks;         // dW1 chunks of the LDS sequences
+};
+
+// train_step: the call is gmc_train_step_f32 (fused Adam; a one-graph batch may take the head into the backward)
+Plan plan(const gmc_batch *b, int F, float dropout_p, bool fuse, bool train_step) {
+    Plan p{};
+    const bool dropout = dropout_p > 0.f;
+    const GmcLdsGeom g = gmc_lds_geometry(b, F);
+    bool lds = g.fits && !(g.ovf && (!fuse || dropout));
 #ifdef GMC_TUNING
-    static const int forced = [] {
+    static const bool forced_rows = [] {
         const char *e = getenv("GMC_SPMM_ALGO");
-        return !e ? 0 : (e[0] == 'r' ? 1 : 2);
+        return e && e[0] == 'r';
     }();
-    if (forced == 1) return false;
+    if (forced_rows) lds = false;
 #endif
-    if (gmc_has_overflow(b) && (!fuse_enabled() || (m && m->dropout_p > 0.f))) return false;
-    return gmc_lds_fits(b);
+    p.zparts = 1;
+    if (!lds) return p;
+    p.fs = g.fs;
+    p.slices = g.slices;
+    p.chunks = gmc_dw1_chunks(b->B, true, g.slices);
+    p.fused = fuse && !dropout;
+    if (!dropout) p.zparts = gmc_lds_groups(b, F);   // (dropout: Z0 comes from its own kernel)
+    p.head_in_bwd = train_step && p.fused && p.chunks == 1 && gmc_bwd1_takes_head(b);
+    return p;
 }
+
+struct Workspace {
+    Plan plan;
+    long ld;         // row kernels: leading dimension of the [R,F] buffers (F rounded up to 32 floats)
+    float *T0;       // [R,ld]  (X o dinv)@W1, later Gs = dinv o Gpre
+    float *H;        // [R,ld]  relu(conv1), later U = dinv o (A @ Gs)
+    float *Z0;       // [plan.zparts,R,3]
+    float *GY2;      // [R,4] = (GY2[r,0..2], dinv[r])
+    float *part;     // [tiles,F,4]
+    float *db2part;  // [B,3]
+    float *dw1part;  // [chunks,N,F]
+    float *W2s;      // [F,3] = W2 / (1-p), dropout only (last, so that forward-only carving shares the prefix)
+    size_t bytes;
+};
+
+bool dropout_on(const gmc_model *m) { return m->dropout_p > 0.f; }
+unsigned long long dropout_seed(const gmc_model *m) { return ((unsigned long long)m->dropout_seed_hi << 32) | m->dropout_seed_lo; }
 
 size_t align_up(size_t x) { return (x + 255) & ~(size_t)255; }
 
-Workspace carve(const gmc_batch *b, const gmc_model *m, int training, void *base) {
+Workspace carve(const gmc_batch *b, const gmc_model *m, int training, void *base, bool train_step = false) {
     Workspace w{};
     size_t off = 0;
     auto take = [&](size_t floats) {
@@ -108,20 +87,20 @@ Workspace carve(const gmc_batch *b, const gmc_model *m, int training, void *base
         return p;
     };
     const size_t R = (size_t)b->R, F = (size_t)m->F;
+    w.plan = plan(b, m->F, m->dropout_p, fuse_enabled(), train_step);
+    const int fs = w.plan.fs;
     w.ld = (long)((F + 31) / 32 * 32);
-    w.fs = use_lds(b, m) ? gmc_lds_slice_width(b) : 0;
-    w.zparts = (w.fs && !dropout_on(m)) ? gmc_lds_groups(b, m->F) : 1;   // (dropout: Z0 comes from its own kernel)
-    const size_t cols = w.fs ? (F + w.fs - 1) / w.fs * w.fs : (size_t)w.ld;
+    const size_t cols = fs ? (F + fs - 1) / fs * fs : (size_t)w.ld;
     w.T0 = take(R * cols);
     w.H = take(R * cols);
-    w.Z0 = take((size_t)w.zparts * R * 3);
+    w.Z0 = take((size_t)w.plan.zparts * R * 3);
     if (training) {
         w.GY2 = take(R * 4);  // (GY2[r,0..2], dinv[r]) per row: one aligned 16 B load downstream
-        size_t tiles = (size_t)(w.fs ? gmc_hidden_slab_tiles(b->R) : gmc_hidden_tiles(b->R));
-        if (w.fs && (size_t)gmc_dw1_chunks(b->B, true, gmc_lds_slices(b, m->F)) > tiles) tiles = (size_t)gmc_dw1_chunks(b->B, true, gmc_lds_slices(b, m->F));
+        size_t tiles = (size_t)(fs ? gmc_hidden_slab_tiles(b->R) : gmc_hidden_tiles(b->R));
+        if (fs && (size_t)w.plan.chunks > tiles) tiles = (size_t)w.plan.chunks;
         w.part = take(tiles * F * 4);
         w.db2part = take((size_t)b->B * 3);
-        w.dw1part = take(gmc_dw1_scratch_floats(b, m->N, m->F, w.fs != 0));
+        w.dw1part = take(gmc_dw1_scratch_floats(b, m->N, m->F, fs != 0));
         if (dropout_on(m)) w.W2s = take(F * 3);
     }
     w.bytes = off;
@@ -150,7 +129,7 @@ int group_rows(const gmc_batch *b) { return b->uniform_n > 0 ? b->uniform_n : b-
 // the fused layer-2 feature transform (zparts partials on the LDS path).
 int aggregate(const gmc_batch *b, const Workspace &w, const float *X, float *Y, int F, const float *bias, int relu,
               const float *W2, float *Z0, int tag, hipStream_t st) {
-    if (w.fs)
+    if (w.plan.fs)
         return gmc_spmm_lds_launch(b, X, w.ld, 1, 0, 0, b->dinv, bias, relu, Y, w.ld, 1, F, W2, Z0, tag, st);
     return gmc_spmm_launch(b->rowptr, b->gcol, nullptr, b->dinv, X, w.ld, bias, relu, Y, w.ld, b->R, F,
                            group_rows(b), W2, Z0, tag, st);
@@ -158,10 +137,11 @@ int aggregate(const gmc_batch *b, const Workspace &w, const float *X, float *Y, 
 
 int forward_body(const gmc_batch *b, const gmc_model *m, const Workspace &w, hipStream_t st) {
     const int F = m->F;
-    if (w.fs && fuse_enabled() && !dropout_on(m))  // T0 lives only in LDS
+    if (w.plan.fused)  // T0 lives only in LDS
         return gmc_fwd1_lds_launch(b, m->W1, m->b1, m->W2, w.H, w.Z0, F, st, m->W1_slab, m->N);
     // layer 1 feature transform as a row gather of W1:  T0 = dinv o (A_val @ W1[:n])
-    int rc = w.fs ? gmc_spmm_lds_launch(b, m->W1, F, 0, 1, 1, b->dinv, nullptr, 0, w.T0, w.ld, 1, F, nullptr,
+    const int fs = w.plan.fs;
+    int rc = fs ? gmc_spmm_lds_launch(b, m->W1, F, 0, 1, 1, b->dinv, nullptr, 0, w.T0, w.ld, 1, F, nullptr,
                                         nullptr, GMC_K_GATHER_W1, st)
                   : gmc_spmm_launch(b->rowptr, b->lcol, b->vals, b->dinv, m->W1, F, nullptr, 0, w.T0, w.ld,
                                     b->R, F, group_rows(b), nullptr, nullptr, GMC_K_GATHER_W1, st);
@@ -169,9 +149,9 @@ int forward_body(const gmc_batch *b, const gmc_model *m, const Workspace &w, hip
     if (dropout_on(m)) {  // relu -> dropout -> layer-2 feature transform of the DROPPED activations (:81-83)
         rc = aggregate(b, w, w.T0, w.H, F, m->b1, 1, nullptr, nullptr, GMC_K_AGG_FWD, st);
         if (rc) return rc;
-        rc = gmc_dropout_launch(w.H, b->R, F, w.fs, w.ld, m->dropout_p, dropout_seed(m), st);
+        rc = gmc_dropout_launch(w.H, b->R, F, fs, w.ld, m->dropout_p, dropout_seed(m), st);
         if (rc) return rc;
-        return gmc_hw2_rows_launch(w.H, b->dinv, m->W2, w.Z0, b->R, F, w.fs, w.ld, st);
+        return gmc_hw2_rows_launch(w.H, b->dinv, m->W2, w.Z0, b->R, F, fs, w.ld, st);
     }
     // layer 1 aggregation + bias + relu with the layer 2 feature transform fused in
     return aggregate(b, w, w.T0, w.H, F, m->b1, 1, m->W2, w.Z0, GMC_K_AGG_FWD, st);
@@ -198,8 +178,8 @@ int backward_body(const gmc_batch *b, const gmc_model *m, const Workspace &w, fl
         if (rc) return rc;
         W2b = w.W2s;
     }
-    if (w.fs && fuse_enabled() && gmc_bwd1_fits(b) && !dropout_on(m)) {  // one pass over H: Gs and U live only in LDS
-        const int chunks = gmc_dw1_chunks(b->B, true, gmc_lds_slices(b, m->F)), per = (b->B + chunks - 1) / chunks;
+    if (w.plan.fused) {  // one pass over H: Gs and U live only in LDS
+        const int chunks = w.plan.chunks, per = (b->B + chunks - 1) / chunks;
         int rc = gmc_bwd1_lds_launch(b, w.H, w.GY2, m->W2, w.dw1part, w.part, m->F, chunks, per, st, head);
         if (rc) return rc;
         return gmc_finish_launch(w.dw1part, w.part, w.db2part, chunks, b->n_max, m->N, m->F, b->B, grad,
@@ -208,16 +188,17 @@ int backward_body(const gmc_batch *b, const gmc_model *m, const Workspace &w, fl
                                  af ? af->step_counter : nullptr, loss_tail, st, af ? af->w1_slab : nullptr);
     }
     if (af) return GMC_ERR_UNSUPPORTED;  // the fused Adam rides on the fused backward
-    int rc = w.fs ? gmc_hidden_bwd_slab_launch(w.H, w.GY2, W2b, b->dinv, Gs, w.part, b->R, m->F, w.fs, st)
+    const int fs = w.plan.fs;
+    int rc = fs ? gmc_hidden_bwd_slab_launch(w.H, w.GY2, W2b, b->dinv, Gs, w.part, b->R, m->F, fs, st)
                   : gmc_hidden_bwd_launch(w.H, w.ld, w.GY2, W2b, b->dinv, Gs, w.ld, w.part, b->R, m->F, st);
     if (rc) return rc;
-    rc = gmc_colsum_reduce_launch(w.part, w.fs ? gmc_hidden_slab_tiles(b->R) : gmc_hidden_tiles(b->R), m->F,
+    rc = gmc_colsum_reduce_launch(w.part, fs ? gmc_hidden_slab_tiles(b->R) : gmc_hidden_tiles(b->R), m->F,
                                   dW2, db1, w.db2part, b->B, db2, st);
     if (rc) return rc;
     // conv1 backward aggregation:  U = dinv o (A @ Gs)
     rc = aggregate(b, w, Gs, U, m->F, nullptr, 0, nullptr, nullptr, GMC_K_AGG_BWD, st);
     if (rc) return rc;
-    rc = gmc_dw1_launch(b, U, w.ld, dW1, w.dw1part, m->N, m->F, w.fs != 0, st);
+    rc = gmc_dw1_launch(b, U, w.ld, dW1, w.dw1part, m->N, m->F, fs != 0, st);
     if (rc || !loss_tail) return rc;
     return gmc_loss_tail_launch(loss_tail, b->B, db2 + 3, st);
 }
@@ -294,24 +275,24 @@ extern "C" int gmc_probe_flavours(int32_t *words, int32_t max) {
     return n;
 }
 
-// the flavour words of a training step's LDS-tiled launches, as forward_body / backward_body / gmc_train_step_f32
-// choose them (the unfused sequence without dropout: with it the aggregation of the forward drops its W2 epilogue,
-// i.e. takes the backward aggregation's word)
+// the flavour words of a training step's LDS-tiled launches: the fused sequence's, then those of the
+// one-kernel-per-operation sequence (gmc_set_fuse(0)) without dropout - with it the aggregation of the forward drops its
+// W2 epilogue, i.e. takes the backward aggregation's word
 extern "C" int gmc_lds_flavours(const gmc_batch *batch, int32_t F, int32_t one_graph_step, int32_t *words, int32_t max) {
     if (!batch) return GMC_ERR_NULL;
     if (batch->abi != GMC_VERSION) return GMC_ERR_ABI;
     if (F <= 0 || F % 4 || F > GMC_MAX_HIDDEN || max < 0 || batch->B < 0) return GMC_ERR_SHAPE;
     int out[6], n = 0;
-    if (gmc_lds_fits(batch)) {
-        const bool head = one_graph_step && gmc_bwd1_takes_head(batch) && gmc_dw1_chunks(batch->B, true, gmc_lds_slices(batch, F)) == 1;
+    const Plan fused = plan(batch, F, 0.f, true, one_graph_step != 0), unfused = plan(batch, F, 0.f, false, false);
+    if (fused.fused) {
         out[n++] = gmc_fwd1_flavour(batch, F);
-        out[n++] = gmc_bwd1_flavour(batch, F, head);
-        if (!gmc_has_overflow(batch)) {   // (overflow lists: the unfused sequence takes the row kernels, see use_lds)
-            out[n++] = gmc_spmm_lds_flavour(batch, F, 1, 1, false);   // W1 gather
-            out[n++] = gmc_spmm_lds_flavour(batch, F, 0, 0, true);    // aggregation + relu + W2 epilogue
-            out[n++] = gmc_spmm_lds_flavour(batch, F, 0, 0, false);   // backward aggregation
-            out[n++] = gmc_dw1_lds_flavour(batch, F);
-        }
+        out[n++] = gmc_bwd1_flavour(batch, F, fused.head_in_bwd);
+    }
+    if (unfused.fs) {
+        out[n++] = gmc_spmm_lds_flavour(batch, F, 1, 1, false);   // W1 gather
+        out[n++] = gmc_spmm_lds_flavour(batch, F, 0, 0, true);    // aggregation + relu + W2 epilogue
+        out[n++] = gmc_spmm_lds_flavour(batch, F, 0, 0, false);   // backward aggregation
+        out[n++] = gmc_dw1_lds_flavour(batch, F);
     }
     for (int i = 0; i < n && i < max; ++i)
         if (words) words[i] = out[i];
@@ -365,7 +346,7 @@ extern "C" int gmc_forward(const gmc_batch *batch, const gmc_model *model, float
     hipStream_t st = static_cast<hipStream_t>(stream);
     rc = forward_body(batch, model, w, st);
     if (rc) return rc;
-    return gmc_head_f32(batch, w.Z0, w.zparts, model->b2, C, P, S, loss, nullptr, nullptr, stream);
+    return gmc_head_f32(batch, w.Z0, w.plan.zparts, model->b2, C, P, S, loss, nullptr, nullptr, stream);
 }
 
 extern "C" int gmc_train_fwd_bwd(const gmc_batch *batch, const gmc_model *model, float C,
@@ -386,13 +367,10 @@ extern "C" int gmc_train_fwd_bwd(const gmc_batch *batch, const gmc_model *model,
     }
     rc = forward_body(batch, model, w, st);
     if (rc) return rc;
-    rc = gmc_head_f32(batch, w.Z0, w.zparts, model->b2, C, P, S, loss, w.GY2, w.db2part, stream);
+    rc = gmc_head_f32(batch, w.Z0, w.plan.zparts, model->b2, C, P, S, loss, w.GY2, w.db2part, stream);
     if (rc) return rc;
     return backward_body(batch, model, w, grad, st, nullptr, tail ? loss : nullptr);
 }
-
-extern "C" int gmc_adam_devstep_model_f32(float *, const float *, float *, float *, int32_t, int32_t, float *, double,
-                                          double, double, double, int32_t *, gmc_stream_t);
 
 extern "C" int gmc_train_step_f32(const gmc_batch *batch, int32_t N, int32_t F, float *param, float C,
                                   void *workspace, size_t workspace_bytes, float *P, int32_t *S, float *loss,
@@ -406,11 +384,10 @@ extern "C" int gmc_train_step_f32(const gmc_batch *batch, int32_t N, int32_t F, 
     if (rc) return rc;
     if (!P || !workspace) return GMC_ERR_NULL;
     if (!gmc_aligned16(grad)) return GMC_ERR_ALIGN;
-    Workspace w = carve(batch, &model, 1, workspace);
+    Workspace w = carve(batch, &model, 1, workspace, true);
     if (w.bytes > workspace_bytes) return GMC_ERR_WORKSPACE;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    const bool fused = batch->R > 0 && w.fs && fuse_enabled() && gmc_bwd1_fits(batch);
-    if (!fused) {  // general shapes: gradient, then the stand-alone Adam
+    if (batch->R == 0 || !w.plan.fused) {  // general shapes: gradient, then the stand-alone Adam
         rc = gmc_train_fwd_bwd(batch, &model, C, workspace, workspace_bytes, P, S, loss, grad, stream);
         if (rc) return rc;
         return gmc_adam_devstep_model_f32(param, grad, mom, var, N, F, w1_slab, lr, beta1, beta2, eps, step_counter, stream);
@@ -418,18 +395,18 @@ extern "C" int gmc_train_step_f32(const gmc_batch *batch, int32_t N, int32_t F, 
     rc = forward_body(batch, &model, w, st);
     if (rc) return rc;
     // One graph per step (the reference's own schedule): the backward launch computes the head as well - every one of
-    // its workgroups for itself, the rows (GY2, dinv) never leave the CU - three launches per graph-step instead of four
-    const bool head_in_bwd = gmc_bwd1_takes_head(batch) && gmc_dw1_chunks(batch->B, true, gmc_lds_slices(batch, F)) == 1;
-    // the head (launch) advances the step counter for the fused Adam of the finish kernel
+    // its workgroups for itself, the rows (GY2, dinv) never leave the CU - three launches per graph-step instead of four.
+    // The head (launch) advances the step counter for the fused Adam of the finish kernel.
+    const bool head_in_bwd = w.plan.head_in_bwd;
     if (!head_in_bwd) {
-        rc = gmc_head_launch(batch, w.Z0, w.zparts, model.b2, C, P, S, loss, w.GY2, w.db2part, step_counter, st);
+        rc = gmc_head_launch(batch, w.Z0, w.plan.zparts, model.b2, C, P, S, loss, w.GY2, w.db2part, step_counter, st);
         if (rc) return rc;
     }
     AdamFuse af;
     af.param = param; af.m = mom; af.v = var; af.lr = lr; af.beta1 = beta1; af.beta2 = beta2; af.eps = eps;
     af.step_counter = step_counter;
     af.w1_slab = w1_slab;
-    const gmc_bwd1_head hd{w.Z0, w.zparts, model.b2, C, P, S, loss, w.db2part, step_counter};
+    const gmc_bwd1_head hd{w.Z0, w.plan.zparts, model.b2, C, P, S, loss, w.db2part, step_counter};
     return backward_body(batch, &model, w, grad, st, &af, nullptr, head_in_bwd ? &hd : nullptr);
 }
 

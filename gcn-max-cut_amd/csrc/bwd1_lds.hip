@@ -151,10 +151,8 @@ __device__ __forceinline__ void dma_row_consts(const float *GY2, int r0, int n, 
 // Two barriers per graph; the transform of graph g+1 follows gather #2 of graph g in the same barrier interval:
 //     -> A ->  gather #1(g) (bufA -> bufB)  -> B ->  DMA(g+1) -> bufA || gather #2(g), then transform(g+1)
 // (the 16-slot flavour below needs more: its table lives in the LDS the second constants buffer uses)
-// * a thread transforms exactly the cells its own DMA instructions fetched, so the H tile of graph g+1
-//   needs no rendezvous between "landed" (the issuing wave's vmcnt) and the transform.  The loop can also
-//   interleave the transform of piece k (counted vmcnt: pieces retire in issue order) with the rows of gather #2
-//   (tuning builds, GMC_BWD1_LEAD) - measured, no gain, see the note at kLead.
+// * a thread transforms exactly the cells its own loads fetched, so the H tile of graph g+1 needs no rendezvous
+//   between "landed" (the issuing wave's vmcnt) and the transform.
 // * the row constants are double-buffered (the second buffer is the LDS the 16-slot flavour keeps its
 //   table in) and fetched a graph ahead, between A and B, so barrier B publishes them before transform(g+1);
 //   (Tried and dropped, measured same-box: pulling the H tile of graph g+2 into L2 with 4-byte LDS-DMA
@@ -190,31 +188,19 @@ __global__ GMC_LDS_BOUNDS void bwd1_reg_kernel(Bwd1Args a) {
     const int g0 = chunk * a.graphs_per_chunk, g1 = min(a.b.B, g0 + a.graphs_per_chunk);
     if (g0 >= g1) return;
     constexpr bool ovf = OVF;   // some row of the batch has more than 8 neighbours: overflow lists (gmc_batch.ovf_*)
-    // first row of my wave in pass 0 (wave-uniform): pass k of the tile DMA is issued by this wave iff that row + k *
-    // rows-per-pass is a row of the graph - what the counted waits below have to know
-    const int wrow0 = __builtin_amdgcn_readfirstlane((int)(threadIdx.x & ~63u) / Q);
 
-    // KREG of my ACC cells of the next graph's H tile do not come by LDS-DMA after barrier B but by ordinary loads
-    // into registers issued a phase EARLIER (behind barrier A, while bufA is still being gathered from): their
-    // shadow is gather #1 + gather #2, and the DMA that is left moves (ACC - KREG) / ACC of the tile in gather #2's
-    // shadow.  Every wave issues exactly KREG such loads per graph (rows past n re-read row n-1): the wait for the
-    // row constants' DMA in front of barrier B counts on it.
-    // Measured (round 3, same box, R = 160,000, us per launch): KREG 0: 112.4-114.7 | 1: 113.8-114.0 | 2: 111.7-112.6 |
-    // 3: 110.9-111.6.  Worth 1-2 %: the tile's arrival is not what the loop waits for most.
-#ifndef GMC_BWD1_KREG
-#define GMC_BWD1_KREG 3
-#endif
-    constexpr int KREG = (!HAS_VAL && !OVF) ? (GMC_BWD1_KREG < ACC ? GMC_BWD1_KREG : ACC) : 0;
-    float4 hreg[KREG > 0 ? KREG : 1];
-    // RECYCLE (default with KREG > 0): NO LDS-DMA for the tile at all - the cells beyond the first KREG are loaded into
-    // the staging registers of cells already transformed: cell j >= KREG into slot j % KREG, behind transform(j - KREG),
-    // which rides between the rows of gather #2 (the data of the early cells IS there by then, unlike in the
-    // interleaving experiment above).  Every wait for H data is then the compiler's own counted vmcnt on loads it
-    // knows; the transform takes its cell from registers (no ds_read), the tile never lands raw in LDS.
-#ifndef GMC_BWD1_RECYCLE
-#define GMC_BWD1_RECYCLE 1
-#endif
-    constexpr bool kRecycle = GMC_BWD1_RECYCLE && KREG > 0;
+    // Unit weights, no lists (kRecycle): the H tile never lands raw in LDS.  KREG = 3 of my ACC cells of the next
+    // graph's tile come by ordinary loads into registers issued a phase EARLY (behind barrier A, while bufA is still
+    // being gathered from: their shadow is gather #1 + gather #2); every later cell j is loaded into the registers of
+    // cell j - KREG once that one is transformed, between the rows of gather #2.  Every wait for H data is then the
+    // compiler's own counted vmcnt on loads it knows, and the transform takes its cell from registers.  Every wave
+    // issues exactly KREG early loads per graph (rows past n re-read row n-1): the wait for the row constants' DMA in
+    // front of barrier B counts on it.  The other flavours take the tile by LDS-DMA after barrier B.  (Measurements of
+    // KREG 0..3, of the LDS-DMA tile with counted per-piece waits and of the row constants read ahead:
+    // profiles/r03_ablation.json.)
+    constexpr bool kRecycle = !HAS_VAL && !OVF;
+    constexpr int KREG = kRecycle ? 3 : 0;
+    float4 hreg[kRecycle ? KREG : 1];
     auto load_cell = [&](int slot, int k, int r0n, int nn) {
         const int l = min(lrow + k * kRowsPerPass, nn - 1);
         const gmc::v4f v = __builtin_nontemporal_load(reinterpret_cast<const gmc::v4f *>(Hs + (long)(r0n + l) * FS + 4 * q));
@@ -253,14 +239,14 @@ __global__ GMC_LDS_BOUNDS void bwd1_reg_kernel(Bwd1Args a) {
     auto zero_pads = [&](float *buf, int n) {  // the zero rows n..n+3 the padding entries point at
         if (threadIdx.x < kPadRows * FS) buf[n * FS + threadIdx.x] = 0.f;
     };
-    auto fetch_tile = [&](int r0, int n, int k0) {  // H tile of the graph at rows [r0, r0+n) -> bufA, my passes k0..ACC-1
+    auto fetch_tile = [&](int r0, int n) {  // H tile of the graph at rows [r0, r0+n) -> bufA
         constexpr int kRows = kThreads / (FS / 4);
         const unsigned base = (unsigned)(size_t)(__attribute__((address_space(3))) float *)bufA;
         const unsigned wave_dst = (unsigned)__builtin_amdgcn_readfirstlane((int)(base + 16u * (threadIdx.x & ~63u)));
 #pragma unroll
         for (int k = 0; k < ACC; ++k) {
             const int l = lrow + k * kRows;
-            if (k >= k0 && l < n) glds16<true>(Hs + (long)(r0 + l) * FS + 4 * q, wave_dst + 16u * (unsigned)(k * kThreads));   // H: read once
+            if (l < n) glds16<true>(Hs + (long)(r0 + l) * FS + 4 * q, wave_dst + 16u * (unsigned)(k * kThreads));   // H: read once
         }
     };
     // H -> Gs for my cell of pass k of a graph of n rows (row constants from `gyl`).  Rows past n: constants 0 make
@@ -273,34 +259,15 @@ __global__ GMC_LDS_BOUNDS void bwd1_reg_kernel(Bwd1Args a) {
         if (ABL(7)) return;
         const int l = lrow + k * kRowsPerPass;
         if (l >= n) rck = gmc::f4_zero();
-        const bool from_reg = kRecycle || k < KREG;
-        transform_row(cs, reinterpret_cast<float4 *>(bufA) + min(l, n) * Q + q, rck, from_reg ? &hreg[KREG > 0 ? k % KREG : 0] : nullptr);
+        transform_row(cs, reinterpret_cast<float4 *>(bufA) + min(l, n) * Q + q, rck, kRecycle ? &hreg[k % KREG] : nullptr);
     };
     auto transform = [&](int k, int n, const float *gyl) { transform_with(k, n, row_consts(k, n, gyl)); };
-    // wait until piece k of the tile DMA this wave issued `pieces` pieces of has landed (they retire in issue order;
-    // younger loads of the gather only make the wait longer than needed, never shorter)
-    auto wait_piece = [&](int k, int pieces) {
-        const int younger = pieces - 1 - k;   // wave-uniform
-#if defined(GMC_BWD1_FULLWAIT) || !defined(GMC_BWD1_LEAD)   // default: the whole tile before the first transform
-        // (the ACC id loads of graph g+1 issued behind gather #2 are younger than the tile and stay in flight)
-        if (k == 0) vm_wait<ACC>();
-        return;
-#endif
-        if (younger <= 0) dma_wait();
-        else if (younger == 1) vm_wait<1>();
-        else if (younger == 2) vm_wait<2>();
-        else if (younger == 3) vm_wait<3>();
-        else if (younger == 4) vm_wait<4>();
-        else if (younger == 5) vm_wait<5>();
-        else if (younger == 6) vm_wait<6>();
-        else vm_wait<7>();
-    };
 
     // graph offsets are scalar loads: each is requested one graph ahead of its first use
     int r0 = a.b.goff[g0], n = a.b.goff[g0 + 1] - r0;
     int nn = g0 + 1 < g1 ? a.b.goff[g0 + 2] - (r0 + n) : 0;   // size of graph g+1 (0: none)
     if constexpr (!HEAD) dma_row_consts(a.GY2, r0, n, gy0);
-    if (!kRecycle) fetch_tile(r0, n, KREG);
+    if (!kRecycle) fetch_tile(r0, n);
     load_hreg(r0, n);
     float4 hlast = gmc::f4_zero();
     if constexpr (kRecycle && ACC == KREG + 1) {
@@ -361,7 +328,7 @@ __global__ GMC_LDS_BOUNDS void bwd1_reg_kernel(Bwd1Args a) {
         // (the transforms of graph g are done with hreg.  Unconditional - the last graph re-reads rows of its own -
         // so that every path issues the same number of loads: a branch here makes the compiler wait for vmcnt(0)
         // at the join, i.e. for these very loads, before the first gather read)
-        if (KREG > 0) load_hreg(nn > 0 ? r0n : r0, nn > 0 ? nn : n);
+        if (kRecycle) load_hreg(nn > 0 ? r0n : r0, nn > 0 ? nn : n);
         // OVF: my rows' overflow descriptors, read ONCE per graph - barrier A has published them - and ahead of gather
         // #1: the two fix-up loops find a wave's hub rows by ballot (no LDS round trip in front of a branch), and a
         // wave without hub rows skips them on a scalar branch
@@ -387,7 +354,7 @@ __global__ GMC_LDS_BOUNDS void bwd1_reg_kernel(Bwd1Args a) {
         for (int k = 0; k < ACC; ++k) {
             const int l = min(lrow + k * kRowsPerPass, n);  // rows past n: 0 into the zero row
             float4 u;
-            if constexpr (GMC_OVF_HALVES_BWD && ovf) u = gather_ids8_halves<FS>(bufA, idr[k], q);   // (see lds_tile.h)
+            if constexpr (ovf) u = gather_ids8_halves<FS>(bufA, idr[k], q);   // (see lds_tile.h)
             else u = ABL(5) ? make_float4(dv[k], dv[k], dv[k], dv[k]) : gather_ids8<FS, false, NS>(bufA, idr[k], nullptr, q);
             u.x *= dv[k]; u.y *= dv[k]; u.z *= dv[k]; u.w *= dv[k];
             reinterpret_cast<float4 *>(bufB)[l * Q + q] = u;
@@ -407,19 +374,16 @@ __global__ GMC_LDS_BOUNDS void bwd1_reg_kernel(Bwd1Args a) {
         }
         STAMP(3);  // gather 1
         // my share of graph g+1's row constants (the KREG register loads behind it may stay in flight)
-        if (KREG > 0) vm_wait<KREG>();
+        if (kRecycle) vm_wait<KREG>();
         else dma_wait();
         loop_barrier();
         STAMP(4);  // barrier B: U tile complete, bufA free, next row constants visible
         // (3) next graph's H tile streams into bufA while (4) gathers from bufB and (1') turns the landed pieces into Gs
-        int pieces = 0;   // tile DMA instructions this wave issues for graph g+1 (wave-uniform)
         if (kRecycle) {
             if (nn > 0) zero_pads(bufA, nn);
         } else if (nn > 0 && !ABL(1)) {
-            fetch_tile(r0n, nn, KREG);
+            fetch_tile(r0n, nn);
             zero_pads(bufA, nn);
-#pragma unroll
-            for (int k = KREG; k < ACC; ++k) pieces += wrow0 + k * kRowsPerPass < nn ? 1 : 0;
             // OVF: the next graph's block offsets travel with its tile; its blocks are requested behind the transforms
             // (the first point where the offsets are known to have landed) and fly through the fix-up loop and the
             // barrier in front of the commit: no memory round trip of the overflow lists is left in the open
@@ -427,58 +391,33 @@ __global__ GMC_LDS_BOUNDS void bwd1_reg_kernel(Bwd1Args a) {
         }
         STAMP(5);  // fetch issue
         const float *wbase = HAS_VAL ? a.b.ell_vals + (long)r0 * W : nullptr;
-        // order inside a wave: the first half of gather #2 goes ahead of the first transform (the DMA needs about
-        // that long), then they alternate; across waves nothing is in step any more - one wave's packed-FMA
-        // transform runs beside the others' LDS reads
-        // Measured (round 3, same box, us per launch at R = 160,000): transform after the whole gather and a full wait
-        // 112.2-113.1 | lead ACC with counted waits 113.1-114.4 | lead 3: 113.0-115.2 | lead 2: 114.4-115.5 | lead 1:
-        // 117.0.  The interleaving buys nothing: a piece lands ~2.6 us after its issue whatever the wave does
-        // meanwhile (every CU streams its tile at the same moment), so the transforms still start when the tile is
-        // there and run with all waves in the same VALU phase.  The default is the plain order.
-#ifndef GMC_BWD1_LEAD
-        constexpr int kLead = ACC;
-#else
-        constexpr int kLead = GMC_BWD1_LEAD < ACC ? GMC_BWD1_LEAD : ACC;   // tuning builds
-#endif
-        // GMC_BWD1_RCK_AHEAD (tuning): the row constants of transform k+1 are read from LDS together with the reads of
-        // gather row k instead of in a round trip of their own in front of the transform
-#ifndef GMC_BWD1_RCK_AHEAD
-#define GMC_BWD1_RCK_AHEAD 0
-#endif
-        constexpr bool kRckAhead = GMC_BWD1_RCK_AHEAD && kRecycle;
-        float4 rck_cur = gmc::f4_zero();
-        if (kRckAhead && nn > 0) rck_cur = row_consts(0, nn, gyn);
+        // Order: recycle flavours turn cell k of graph g+1 into Gs ahead of row k of gather #2 (k < ACC); the LDS-DMA
+        // flavours run the whole gather, then the transforms behind one wait for the whole tile (k >= ACC).
+        // Interleaving those transforms with the gather rows behind counted per-piece waits bought nothing: a piece
+        // lands ~2.6 us after its issue whatever the wave does meanwhile, because every CU streams its tile at the
+        // same moment (profiles/r03_ablation.json).  (One loop of 2 ACC steps: split in two, the compiler schedules
+        // the unrolled body differently.)
 #pragma unroll
-        for (int k = 0; k < ACC + kLead; ++k) {
+        for (int k = 0; k < 2 * ACC; ++k) {
             if (k < ACC) {
-                float4 rck_next = gmc::f4_zero();
-                if (kRecycle && nn > 0) {   // cell k is in registers: turn it into Gs AHEAD of row k of the gather, then
-                    if (kRckAhead) {        // send for the cell that recycles its registers (longest possible shadow)
-                        transform_with(k, nn, rck_cur);
-                        if (k + 1 < ACC) rck_next = row_consts(k + 1, nn, gyn);
-                    } else {
-                        transform(k, nn, gyn);
-                    }
+                if (kRecycle && nn > 0) {   // cell k is in registers: turn it into Gs, then send for the cell that
+                    transform(k, nn, gyn);  // recycles its registers (longest possible shadow)
                     if (k + KREG < ACC) load_cell(k % KREG, k + KREG, r0n, nn);
                 }
                 const int l = min(lrow + k * kRowsPerPass, n - 1);  // (weights of a real row; the ids are pads past n)
                 if constexpr (HAS_VAL) acc[k] += gmc::f4v(gather_ids8<FS, true, NS>(bufB, idr[k], wbase + (long)l * W, q));
-                else if constexpr (GMC_OVF_HALVES_BWD && ovf) acc[k] += gmc::f4v(gather_ids8_halves<FS>(bufB, idr[k], q));
+                else if constexpr (ovf) acc[k] += gmc::f4v(gather_ids8_halves<FS>(bufB, idr[k], q));
                 else acc[k] += ABL(4) ? (gmc::v4f)(__uint_as_float(idr[k].x)) : gather_ids8_pk<FS, NS>(bufB, idr[k], q);
                 // the sum is needed HERE (its only user is the store after the graph loop: left alone the
                 // optimiser sinks the adds and keeps four rows of reads, 128 VGPRs, alive)
                 asm volatile("" : "+v"(acc[k]));
-                if (kRckAhead) {
-                    asm volatile("" : "+v"(rck_next.x), "+v"(rck_next.y), "+v"(rck_next.z), "+v"(rck_next.w));
-                    rck_cur = rck_next;
-                }
-                // plain order (kLead == ACC): gather #2 is done with the ids - request graph g+1's now, so that they
-                // travel under the wait for the tile and the transforms instead of in front of barrier A
-                if (k == ACC - 1 && kLead == ACC && nn > 0) load_ids(r0n, nn);
+                // gather #2 is done with the ids - request graph g+1's now, so that they travel under the wait for the
+                // tile and the transforms instead of in front of barrier A
+                if (k == ACC - 1 && nn > 0) load_ids(r0n, nn);
             }
-            if (!kRecycle && k >= kLead && nn > 0) {
-                const int j = k - kLead;
-                wait_piece(j, pieces);
+            if (!kRecycle && k >= ACC && nn > 0) {
+                const int j = k - ACC;
+                if (j == 0) vm_wait<ACC>();   // the whole tile (the ACC id loads just issued are younger: they stay in flight)
                 __builtin_amdgcn_sched_barrier(0);   // the transform's LDS read must not move above the wait
                 transform(j, nn, gyn);
             }
@@ -494,11 +433,8 @@ __global__ GMC_LDS_BOUNDS void bwd1_reg_kernel(Bwd1Args a) {
             }
         }
         STAMP(6);  // gather 2 + transform of the next graph
-        // (default order: the wait in front of the first transform covered the tile; the id loads of graph g+1 - and an
-        // OVF kernel's block loads - stay in flight through the barrier below)
-        if (!kRecycle && kLead != ACC) dma_wait();
+        // (the id loads of graph g+1 - and an OVF kernel's block loads - stay in flight through the barrier below)
         STAMP(7);
-        if (kLead != ACC && nn > 0) load_ids(r0n, nn);   // (interleaved tuning builds: the ids are in use until here)
         if constexpr (ovf) {
             if (nn > 0) {   // every wave is done with this graph's descriptors / blocks before they are rewritten
                 loop_barrier();
@@ -697,48 +633,18 @@ __global__ GMC_LDS_BOUNDS void bwd1_lds_kernel(Bwd1Args a) {
     col_epilogue<Q>(cs, red, a.colpart, chunk, s, FS, a.F);
 }
 
-// 8 rows per thread at FS = 16 would need n_max > 1024, which no 16-column tile fits (pick_fs): never instantiated
-template <int FS, int W, bool HV, int NS, bool OV>
-int launch_bwd1_acc(int flv, const Bwd1Args &a, int grid, size_t lds, hipStream_t st) {
-    if constexpr (W == 8) {
-#define GMC_BWD1(AC) launch_flv(flv, flavour_word(GMC_FLV_BWD1_REG, FS, 8, AC, HV, NS, OV), bwd1_reg_kernel<FS, AC, HV, NS, OV>, grid, lds, st, a)
-        if (GMC_FLV_ACC(flv) == 4) return GMC_BWD1(4);
-        if constexpr (FS > 16) return GMC_BWD1(8);
-#undef GMC_BWD1
-    } else {
-#define GMC_BWD1(AC) launch_flv(flv, flavour_word(GMC_FLV_BWD1, FS, W, AC, HV, NS, OV), bwd1_lds_kernel<FS, W, AC, HV, NS, OV>, grid, lds, st, a)
-        if (GMC_FLV_ACC(flv) == 4) return GMC_BWD1(4);
-        if constexpr (FS > 16) return GMC_BWD1(8);
-#undef GMC_BWD1
+// the flavours built: unit weights with every NS class, edge weights, overflow lists (unit weights, every slot live);
+// 8-slot tables (bwd1_reg_kernel) also the one-graph head at ACC = 4 with unit weights (gmc_bwd1_takes_head)
+struct Bwd1Built {
+    template <typename L> static constexpr bool has(L) {
+        if (L::EPI || L::SHARED || (L::HAS_VAL && L::OVF)) return false;
+        if (L::HEAD) return L::W == 8 && L::ACC == 4 && !L::HAS_VAL && !L::OVF;
+        return L::HAS_VAL || L::OVF ? L::NS == L::W : true;
     }
-    return GMC_ERR_UNSUPPORTED;
-}
-
-template <int FS, int W>
-int launch_bwd1(int flv, const Bwd1Args &a, size_t lds, hipStream_t st) {
-    const int grid = a.slices * a.chunks;
-    const int ns = GMC_FLV_NS(flv);
-    if constexpr (W == 8) {
-        if (GMC_FLV_HEAD(flv)) {   // one graph, unit weights, no lists, n <= 1024 (gmc_bwd1_takes_head): the head rides in this launch
-#define GMC_HEAD(NSK) launch_flv(flv, flavour_word(GMC_FLV_BWD1_REG, FS, 8, 4, false, NSK, false, true), bwd1_reg_kernel<FS, 4, false, NSK, false, true>, grid, lds, st, a)
-            return ns == 7 ? GMC_HEAD(7) : GMC_HEAD(8);
-#undef GMC_HEAD
-        }
-    }
-    if (GMC_FLV_OVF(flv)) return launch_bwd1_acc<FS, W, false, W, true>(flv, a, grid, lds, st);
-    if (GMC_FLV_HAS_VAL(flv)) return launch_bwd1_acc<FS, W, true, W, false>(flv, a, grid, lds, st);
-    if constexpr (W == 8) return ns == 7 ? launch_bwd1_acc<FS, 8, false, 7, false>(flv, a, grid, lds, st)
-                                         : launch_bwd1_acc<FS, 8, false, 8, false>(flv, a, grid, lds, st);
-    else return ns == 10 ? launch_bwd1_acc<FS, 16, false, 10, false>(flv, a, grid, lds, st)
-              : ns == 12 ? launch_bwd1_acc<FS, 16, false, 12, false>(flv, a, grid, lds, st)
-              : ns == 14 ? launch_bwd1_acc<FS, 16, false, 14, false>(flv, a, grid, lds, st)
-                         : launch_bwd1_acc<FS, 16, false, 16, false>(flv, a, grid, lds, st);
-}
+};
 
 }  // namespace
 
-// fused layer-1 backward over the slab-layout H: dW1 partials [chunks][n_max][F] and column
-// partials [chunks][F][4] (dW2, db1)
 // Can the fused backward of this batch compute the head as well (gmc_bwd1_head)?  One graph (every launch of the
 // reference's one-step-per-graph schedule), 8-slot table, unit weights, no overflow lists, at most 1024 rows (one row
 // per thread in the head, four passes in the backward), and the head's LDS arrays fit the U tile's buffer.
@@ -750,25 +656,13 @@ bool gmc_bwd1_takes_head(const gmc_batch *b) {
     return (size_t)(7 * (b->n_max + 4) + 64) <= tile_floats(b->n_max, fs);
 }
 
-// head != nullptr (only if gmc_bwd1_takes_head): the launch computes the graph's head too and GY2 is not read
-struct gmc_bwd1_head {
-    const float *Z0; int zparts; const float *b2; float C; float *P; int *S; float *loss; float *db2part; int *tick;
-};
 // Flavour word of the fused backward for this batch (host only: reads struct fields, never the device arrays);
 // head: the launch computes the one-graph head as well.  0 = gmc_bwd1_lds_launch refuses the batch.
 int gmc_bwd1_flavour(const gmc_batch *b, int F, bool head) {
-    if (!gmc_lds_fits(b) || F <= 0) return 0;
+    const GmcLdsGeom g = gmc_lds_geometry(b, F);
+    if (!g.fits || F <= 0) return 0;
     if (head && !gmc_bwd1_takes_head(b)) return 0;
-    const int fs = pick_fs(b->n_max, b->ell_width), W = b->ell_width;
-    const int rows_per_pass = kThreads / (fs / 4);
-    if ((b->n_max + rows_per_pass - 1) / rows_per_pass > 8) return 0;
-    const int acc = acc_rows(b->n_max, fs);
-    if (fs == 16 && acc != 4) return 0;
-    const bool ovf = gmc_has_overflow(b), hv = b->ell_vals != nullptr;
-    if (ovf && hv) return 0;   // (weights + overflow: row kernels, see gmc_lds_fits)
-    // live slots: no row of the batch has more neighbours; hub rows: every slot live, overflow lists walked
-    const int ns = ovf ? W : ns_class(W, b->ell_slots, !hv);
-    return flavour_word(W == 8 ? GMC_FLV_BWD1_REG : GMC_FLV_BWD1, fs, W, acc, hv, ns, ovf, head);
+    return flavour_word(g.W == 8 ? GMC_FLV_BWD1_REG : GMC_FLV_BWD1, g.fs, g.W, g.acc, g.hv, g.ns, g.ovf, head);
 }
 
 int gmc_bwd1_lds_launch(const gmc_batch *b, const float *H, const float *GY2, const float *W2,
@@ -791,16 +685,14 @@ int gmc_bwd1_lds_launch(const gmc_batch *b, const float *H, const float *GY2, co
         lds = kOvfLdsBytes;
     }
     GmcProbeScope probe(GMC_K_BWD1_FUSED, st);
-    if (GMC_FLV_W(flv) == 8) {
-        switch (fs) {
-            case 64: return launch_bwd1<64, 8>(flv, a, lds, st);
-            case 32: return launch_bwd1<32, 8>(flv, a, lds, st);
-            default: return launch_bwd1<16, 8>(flv, a, lds, st);
-        }
-    }
-    switch (fs) {
-        case 64: return launch_bwd1<64, 16>(flv, a, lds, st);
-        case 32: return launch_bwd1<32, 16>(flv, a, lds, st);
-        default: return launch_bwd1<16, 16>(flv, a, lds, st);
-    }
+    return decode_flavour<Bwd1Built>(flv, [&](auto L) {
+        using K = decltype(L);
+        const int grid = a.slices * a.chunks;
+        if constexpr (K::W == 8)
+            return launch_flv(flv, K::word(GMC_FLV_BWD1_REG), bwd1_reg_kernel<K::FS, K::ACC, K::HAS_VAL, K::NS, K::OVF, K::HEAD>,
+                              grid, lds, st, a);
+        else
+            return launch_flv(flv, K::word(GMC_FLV_BWD1), bwd1_lds_kernel<K::FS, K::W, K::ACC, K::HAS_VAL, K::NS, K::OVF>,
+                              grid, lds, st, a);
+    });
 }

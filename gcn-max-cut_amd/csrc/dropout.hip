@@ -12,7 +12,7 @@
 // slab), of the launch shape and of the batch a graph sits in, reproducible from the seed.  It is NOT
 // torch's Philox stream: bit parity with F.dropout's random numbers is unobtainable ("parity unpinned" for
 // the mask; the arithmetic around it is property-tested, tests/test_gpu_parity.py).
-#include "gmc_common.h"
+#include "launchers.h"
 
 namespace {
 

@@ -6,7 +6,7 @@
 // gather_reduce: one wave per (node id v, graph chunk, 1024-column block); CSR-order gather of U rows with
 // 8 rows in flight, graphs ascending; writes either dW1 directly (one chunk) or a
 // per-chunk partial that fold_chunks sums in chunk order.  No atomics: reproducible.
-#include "gmc_common.h"
+#include "launchers.h"
 #include <cstdlib>
 
 namespace {
@@ -105,11 +105,8 @@ __global__ __launch_bounds__(256) void fold_chunks_kernel(const float4 *part, fl
 
 }  // namespace
 
-bool gmc_lds_fits(const gmc_batch *b);
-int gmc_lds_slices(const gmc_batch *b, int F);
-int gmc_dw1_lds_launch(const gmc_batch *, const float *, long, int, float *, int, int, int, hipStream_t);
-
-int gmc_fold_chunks_launch(const float *scratch, float *dW1, int N, int rows, int F, int chunks, hipStream_t st) {
+// dW1[v][:] = the sum of the chunks' partials for v < rows, 0 for the other rows of the N
+static int fold_chunks_launch(const float *scratch, float *dW1, int N, int rows, int F, int chunks, hipStream_t st) {
     GmcProbeScope probe(GMC_K_DW1_FOLD, st);
     const long n4 = (long)N * F / 4;
     const int blocks = (int)((n4 + 255) / 256 < 2048 ? (n4 + 255) / 256 : 2048);
@@ -145,7 +142,7 @@ int gmc_dw1_chunks(int B, bool lds, int slices) {
 
 // floats of scratch gmc_dw1_launch needs
 size_t gmc_dw1_scratch_floats(const gmc_batch *b, int N, int F, bool lds) {
-    const int chunks = gmc_dw1_chunks(b->B, lds, lds ? gmc_lds_slices(b, F) : 0);
+    const int chunks = gmc_dw1_chunks(b->B, lds, lds ? gmc_lds_geometry(b, F).slices : 0);
     if (lds) return (size_t)chunks * b->n_max * F;
     return chunks > 1 ? (size_t)chunks * N * F : 0;
 }
@@ -154,7 +151,7 @@ int gmc_dw1_launch(const gmc_batch *b, const float *U, long ldu, float *dW1, flo
                    int N, int F, bool lds, hipStream_t st) {
     if (F % 4 || ldu % 4) return GMC_ERR_ALIGN;
     if (F > GMC_MAX_HIDDEN) return GMC_ERR_UNSUPPORTED;
-    const int chunks = gmc_dw1_chunks(b->B, lds, lds ? gmc_lds_slices(b, F) : 0);
+    const int chunks = gmc_dw1_chunks(b->B, lds, lds ? gmc_lds_geometry(b, F).slices : 0);
     const int per = (b->B + chunks - 1) / chunks;
     int rows = N;
     if (lds) {
@@ -172,12 +169,5 @@ int gmc_dw1_launch(const gmc_batch *b, const float *U, long ldu, float *dW1, flo
         GMC_LAUNCH_CHECK();
         if (chunks == 1) return GMC_OK;
     }
-    GmcProbeScope probe(GMC_K_DW1_FOLD, st);
-    const long n4 = (long)N * F / 4;
-    const int blocks = (int)((n4 + 255) / 256 < 2048 ? (n4 + 255) / 256 : 2048);
-    hipLaunchKernelGGL(fold_chunks_kernel, dim3(blocks), dim3(256), 0, st,
-                       reinterpret_cast<const float4 *>(scratch), reinterpret_cast<float4 *>(dW1), N, rows,
-                       F / 4, chunks);
-    GMC_LAUNCH_CHECK();
-    return GMC_OK;
+    return fold_chunks_launch(scratch, dW1, N, rows, F, chunks, st);
 }

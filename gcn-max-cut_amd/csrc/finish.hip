@@ -7,7 +7,7 @@
 // all in a fixed order (bitwise reproducible), then - when the optimizer pointers are given -
 // torch.optim.Adam.step (TrainingNeural.py:386) on the same element while it is in registers.
 // Replaces three tiny latency-bound launches (colsum, fold, adam) of the fused path by one.
-#include "gmc_common.h"
+#include "launchers.h"
 #include <math.h>
 
 // Diagnostic build only (-DGMC_STAMP): wall-clock entry / exit marks of every block (see head.hip)

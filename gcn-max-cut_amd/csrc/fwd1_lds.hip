@@ -220,10 +220,8 @@ __global__ GMC_LDS_BOUNDS void fwd1_lds_kernel(TileArgs a) {
                     if (k + 1 < ACC) ids = reinterpret_cast<const uint4 *>(nb)[min(l + kRowsPerPass, n - 1)];
                     // rows past n redo row n-1 (same value to the same address): no exec-mask juggling
                     const int lc = min(l, n - 1);
-                    float4 t;
-                    if constexpr (GMC_OVF_HALVES_FWD && ovf && !HAS_VAL) t = gather_ids8_halves<FS>(bufA, cur, q);   // (see lds_tile.h)
-                    else t = ABL(5) ? make_float4(sc[k], sc[k], sc[k], sc[k])
-                                    : gather_ids8<FS, HAS_VAL, NS>(bufA, cur, HAS_VAL ? wbase + (long)lc * W : nullptr, q);
+                    float4 t = ABL(5) ? make_float4(sc[k], sc[k], sc[k], sc[k])
+                                      : gather_ids8<FS, HAS_VAL, NS>(bufA, cur, HAS_VAL ? wbase + (long)lc * W : nullptr, q);
                     t.x *= sc[k]; t.y *= sc[k]; t.z *= sc[k]; t.w *= sc[k];
                     // (OVF: a clamped duplicate must not write - its table-only sum could land on row n-1 AFTER the
                     // owner's fix-up below has added that row's overflow blocks)
@@ -316,9 +314,7 @@ __global__ GMC_LDS_BOUNDS void fwd1_lds_kernel(TileArgs a) {
                 if constexpr (W == 8) {
                     const uint4 cur = ids2;
                     if (k + 1 < ACC) ids2 = reinterpret_cast<const uint4 *>(nb)[min(l + kRowsPerPass, n - 1)];
-                    gmc::v4f h;
-                    if constexpr (GMC_OVF_HALVES_FWD && ovf) h = gmc::f4v(gather_ids8_halves<FS>(bufB, cur, q));
-                    else h = ABL(4) ? (gmc::v4f)(__uint_as_float(cur.x)) : gather_ids8_pk<FS, NS>(bufB, cur, q);
+                    const gmc::v4f h = ABL(4) ? (gmc::v4f)(__uint_as_float(cur.x)) : gather_ids8_pk<FS, NS>(bufB, cur, q);
                     if (!later) emit(k, h);
                 } else {
                     const gmc::v4f h = gmc::f4v(gather_row<FS, W, false, NS>(bufB, nb, nullptr, l, q));
@@ -344,55 +340,28 @@ __global__ GMC_LDS_BOUNDS void fwd1_lds_kernel(TileArgs a) {
     MARK(3);
 }
 
-// 8 rows per thread at FS = 16 would need n_max > 1024, which no 16-column tile fits (pick_fs): never instantiated
-template <int FS, int W, bool HV, int NS, bool OV>
-int launch_fwd1_acc(int flv, const TileArgs &a, size_t lds, int grid, hipStream_t st) {
-#define GMC_FWD1(AC) launch_flv(flv, flavour_word(GMC_FLV_FWD1, FS, W, AC, HV, NS, OV), fwd1_lds_kernel<FS, W, AC, HV, NS, OV>, grid, lds, st, a)
-    if (GMC_FLV_ACC(flv) == 4) return GMC_FWD1(4);
-    if constexpr (FS > 16) return GMC_FWD1(8);
-    return GMC_ERR_UNSUPPORTED;
-#undef GMC_FWD1
-}
-
-template <int FS, int W>
-int launch_fwd1(int flv, const TileArgs &a, size_t lds, int grid, hipStream_t st) {
-    const int ns = GMC_FLV_NS(flv);
-    if (GMC_FLV_OVF(flv)) return launch_fwd1_acc<FS, W, false, W, true>(flv, a, lds, grid, st);
-    if (GMC_FLV_HAS_VAL(flv)) return launch_fwd1_acc<FS, W, true, W, false>(flv, a, lds, grid, st);
-    if constexpr (W == 8) return ns == 7 ? launch_fwd1_acc<FS, 8, false, 7, false>(flv, a, lds, grid, st)
-                                         : launch_fwd1_acc<FS, 8, false, 8, false>(flv, a, lds, grid, st);
-    else return ns == 10 ? launch_fwd1_acc<FS, 16, false, 10, false>(flv, a, lds, grid, st)
-              : ns == 12 ? launch_fwd1_acc<FS, 16, false, 12, false>(flv, a, lds, grid, st)
-              : ns == 14 ? launch_fwd1_acc<FS, 16, false, 14, false>(flv, a, lds, grid, st)
-                         : launch_fwd1_acc<FS, 16, false, 16, false>(flv, a, lds, grid, st);
-}
+// the flavours built: unit weights with every NS class, edge weights, overflow lists (unit weights, every slot live)
+struct Fwd1Built {
+    template <typename L> static constexpr bool has(L) {
+        if (L::HEAD || L::EPI || L::SHARED || (L::HAS_VAL && L::OVF)) return false;
+        return L::HAS_VAL || L::OVF ? L::NS == L::W : true;
+    }
+};
 
 }  // namespace
 
-// Flavour word of the fused forward for this batch (host only: reads struct fields, never the device arrays);
-// 0 = gmc_fwd1_lds_launch refuses the batch.  Every choice of template arguments is made here.
+// Flavour word of the fused forward for this batch (host only); 0 = gmc_fwd1_lds_launch refuses the batch
 int gmc_fwd1_flavour(const gmc_batch *b, int F) {
-    if (!gmc_lds_fits(b) || F <= 0) return 0;
-    const int fs = pick_fs(b->n_max, b->ell_width), W = b->ell_width;
-    const int slices = (F + fs - 1) / fs;
+    const GmcLdsGeom g = gmc_lds_geometry(b, F);
+    if (!g.fits || F <= 0) return 0;
     // 8-slot tables: the column constants of a window of up to kThreads columns sit in LDS, 16 B per column (16-slot
     // tables load them slice by slice)
-    if (W == 8 && (size_t)16 * kThreads > lds_consts(b->n_max, fs, 8)) return 0;
-    if (slices * fs > GMC_MAX_HIDDEN) return 0;
-    const int rows_per_pass = kThreads / (fs / 4);
-    if ((b->n_max + rows_per_pass - 1) / rows_per_pass > 8) return 0;
-    const int acc = acc_rows(b->n_max, fs);
-    if (fs == 16 && acc != 4) return 0;
-    const bool ovf = gmc_has_overflow(b), hv = b->ell_vals != nullptr;
-    if (ovf && hv) return 0;   // hub rows: every slot live (weights + overflow: row kernels, see gmc_lds_fits)
-    // live slots (no row of the batch has more neighbours): unit-weight kernels skip the others
-    const int ns = ovf ? W : ns_class(W, b->ell_slots, !hv);
-    return flavour_word(GMC_FLV_FWD1, fs, W, acc, hv, ns, ovf) | flavour_per(gmc_lds_slices_per_group(b, F));
+    if (g.W == 8 && (size_t)16 * kThreads > lds_consts(b->n_max, g.fs, 8)) return 0;
+    if (g.slices * g.fs > GMC_MAX_HIDDEN) return 0;
+    return flavour_word(GMC_FLV_FWD1, g.fs, g.W, g.acc, g.hv, g.ns, g.ovf) | flavour_per(gmc_lds_slices_per_group(b, F));
 }
 
-// fused layer-1 forward: H (slab layout) = relu(dinv o (A @ (dinv o (A_val @ W1[:n]))) + b1) and
-// Zpart[group][r][:] = dinv[r] * (H[r, group's columns] @ W2[group's rows])
-// W1_slab (optional): the [ceil(F/16)][N][16] copy of W1 (gmc_w1_slab_f32); N = rows of W1
+// fused layer-1 forward (launchers.h)
 int gmc_fwd1_lds_launch(const gmc_batch *b, const float *W1, const float *b1, const float *W2, float *H,
                         float *Zpart, int F, hipStream_t st, const float *W1_slab, int N) {
     const int flv = gmc_fwd1_flavour(b, F);
@@ -415,16 +384,9 @@ int gmc_fwd1_lds_launch(const gmc_batch *b, const float *W1, const float *b1, co
         lds = kOvfLdsBytes;
     }
     GmcProbeScope probe(GMC_K_FWD1_FUSED, st);
-    if (GMC_FLV_W(flv) == 8) {
-        switch (fs) {
-            case 64: return launch_fwd1<64, 8>(flv, a, lds, grid, st);
-            case 32: return launch_fwd1<32, 8>(flv, a, lds, grid, st);
-            default: return launch_fwd1<16, 8>(flv, a, lds, grid, st);
-        }
-    }
-    switch (fs) {
-        case 64: return launch_fwd1<64, 16>(flv, a, lds, grid, st);
-        case 32: return launch_fwd1<32, 16>(flv, a, lds, grid, st);
-        default: return launch_fwd1<16, 16>(flv, a, lds, grid, st);
-    }
+    return decode_flavour<Fwd1Built>(flv, [&](auto L) {
+        using K = decltype(L);
+        return launch_flv(flv, K::word(GMC_FLV_FWD1), fwd1_lds_kernel<K::FS, K::W, K::ACC, K::HAS_VAL, K::NS, K::OVF>,
+                          grid, lds, st, a);
+    });
 }

@@ -24,12 +24,6 @@ struct GmcProbeScope {
     ~GmcProbeScope() { gmc_probe_mark(tag, false, st); }
 };
 
-// internal form of gmc_spmm_f32 with a probe tag (variant 1 = shared-source W1 gather)
-int gmc_spmm_launch(const int32_t *rowptr, const int32_t *col, const float *vals, const float *scale,
-                    const float *X, int64_t ldx, const float *bias, int relu, float *Y, int64_t ldy,
-                    int32_t n_rows, int32_t F, int32_t group_rows, const float *W2, float *Z0,
-                    int tag, hipStream_t st);
-
 static inline bool gmc_aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 // does the batch carry overflow lists the LDS-tiled kernels have to walk?  (ovf_ptr without a single block - the host
 // says so through ovf_max_blocks, the pointers are device memory - is a batch without lists: the OVF kernels read

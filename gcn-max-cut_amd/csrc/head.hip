@@ -12,6 +12,7 @@
 //      GY2 = A @ (dinv o GZ)
 // Sums run in CSR / fixed tree order: bitwise reproducible.
 #include "head_body.h"
+#include "launchers.h"
 
 #ifdef GMC_STAMP
 extern "C" int gmc_debug_read_stamps_head(unsigned long long *out, int n) {
@@ -81,11 +82,6 @@ int check_batch(const gmc_batch *b) {
 
 }  // namespace
 
-// Internal launcher.  tick != nullptr: the launch also advances the device-side Adam step counter
-// (gmc_train_step_f32; saves a one-thread launch per step).
-int gmc_head_launch(const gmc_batch *batch, const float *Z0, int32_t z_parts, const float *b2, float C, float *P,
-                    int32_t *S, float *loss, float *GY2, float *db2part, int *tick, hipStream_t stream);
-
 extern "C" int gmc_head_f32(const gmc_batch *batch, const float *Z0, int32_t z_parts, const float *b2,
                             float C, float *P, int32_t *S, float *loss, float *GY2, float *db2part,
                             gmc_stream_t stream) {
@@ -93,6 +89,8 @@ extern "C" int gmc_head_f32(const gmc_batch *batch, const float *Z0, int32_t z_p
                            static_cast<hipStream_t>(stream));
 }
 
+// Internal launcher.  tick != nullptr: the launch also advances the device-side Adam step counter
+// (gmc_train_step_f32; saves a one-thread launch per step).
 int gmc_head_launch(const gmc_batch *batch, const float *Z0, int32_t z_parts, const float *b2, float C, float *P,
                     int32_t *S, float *loss, float *GY2, float *db2part, int *tick, hipStream_t stream) {
     int rc = check_batch(batch);

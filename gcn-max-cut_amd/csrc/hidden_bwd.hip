@@ -8,7 +8,7 @@
 // One streaming pass over H: each thread owns 4 columns (float4, 2 KiB-coalesced rows) and
 // walks a tile of rows keeping its dW2/db1 partials in registers; tile partials go to a
 // small scratch and are folded in fixed order by colsum_reduce (no float atomics).
-#include "gmc_common.h"
+#include "launchers.h"
 
 namespace {
 

@@ -1,0 +1,90 @@
+// The library's internal cross-file interface: every launcher and host query one translation unit defines and another
+// calls.  (The C ABI is include/gcnmaxcut.h.)  All launchers enqueue on `st` and return a GMC_* code or a HIP error.
+#pragma once
+#include "gmc_common.h"
+
+// ---- LDS-tiled kernels: the batch's geometry (spmm_lds.hip) ---------------------------------------------------------
+// Everything the LDS-tiled kernels' template arguments share, worked out once from the gmc_batch fields (host only:
+// never the device arrays).  fits == false: the graphs do not fit a CU's LDS and the row kernels serve the batch.
+struct GmcLdsGeom {
+    bool fits;
+    int fs;       // columns per slice (16, 32, 64)
+    int W;        // neighbour slots per table row (8, 16)
+    int acc;      // rows per thread (4, 8)
+    int ns;       // live slots the gathers read (ns_class; every slot with overflow lists)
+    bool hv;      // edge weights (gmc_batch.ell_vals)
+    bool ovf;     // overflow lists (gmc_has_overflow)
+    int slices;   // ceil(F / fs)
+};
+GmcLdsGeom gmc_lds_geometry(const gmc_batch *b, int F);
+bool gmc_lds_fits(const gmc_batch *b);
+int gmc_lds_slices_per_group(const gmc_batch *b, int F);   // slices of one workgroup item: 1, 2, 4
+int gmc_lds_groups(const gmc_batch *b, int F);             // slice groups per graph (Zpart partials of the W2 epilogue)
+int device_cus(bool allow_override = true);                // compute units (gmc_debug_set_device_cus may override)
+
+// ---- flavour words (GMC_FLV_*, gcnmaxcut.h) of the LDS-tiled launches; 0 = the launcher refuses the batch ----------
+int gmc_fwd1_flavour(const gmc_batch *b, int F);
+int gmc_bwd1_flavour(const gmc_batch *b, int F, bool head);
+int gmc_spmm_lds_flavour(const gmc_batch *b, int F, int shared_src, int use_vals, bool epi);
+int gmc_dw1_lds_flavour(const gmc_batch *b, int F);
+// can the fused backward of this batch compute the one-graph head as well (gmc_bwd1_head)?
+bool gmc_bwd1_takes_head(const gmc_batch *b);
+
+// ---- the fused layer-1 kernels -------------------------------------------------------------------------------------
+// H (slab layout) = relu(dinv o (A @ (dinv o (A_val @ W1[:n]))) + b1), Zpart[group][r][:] = dinv[r] * (H @ W2) over the
+// group's columns.  W1_slab (optional): the [ceil(F/16)][N][16] copy of W1.
+int gmc_fwd1_lds_launch(const gmc_batch *b, const float *W1, const float *b1, const float *W2, float *H, float *Zpart,
+                        int F, hipStream_t st, const float *W1_slab, int N);
+// the head's arguments for a fused backward launch that computes the one-graph head as well
+struct gmc_bwd1_head {
+    const float *Z0; int zparts; const float *b2; float C; float *P; int *S; float *loss; float *db2part; int *tick;
+};
+// dW1 partials [chunks][n_max][F] and column partials [chunks][F][4] = (dW2, db1) from the slab-layout H;
+// head != nullptr (gmc_bwd1_takes_head only): the launch computes the head too and GY2 is not read
+int gmc_bwd1_lds_launch(const gmc_batch *b, const float *H, const float *GY2, const float *W2, float *dw1part,
+                        float *colpart, int F, int chunks, int graphs_per_chunk, hipStream_t st,
+                        const gmc_bwd1_head *head);
+// folds the fused backward's partials into grad; param != nullptr: Adam on param / m / v as well (device step counter)
+int gmc_finish_launch(const float *dw1part, const float *colpart, const float *db2part, int chunks, int n_max, int N,
+                      int F, int B, float *grad, float *param, float *m, float *v, double lr, double beta1,
+                      double beta2, double eps, int *step_counter, const float *loss_for_tail, hipStream_t st,
+                      float *w1_slab);
+int gmc_loss_tail_launch(const float *loss, int B, float *slot, hipStream_t st);
+
+// ---- SpMM (spmm.hip: row kernels, spmm_lds.hip: LDS-tiled) ---------------------------------------------------------
+// internal form of gmc_spmm_f32 with a probe tag
+int gmc_spmm_launch(const int32_t *rowptr, const int32_t *col, const float *vals, const float *scale, const float *X,
+                    int64_t ldx, const float *bias, int relu, float *Y, int64_t ldy, int32_t n_rows, int32_t F,
+                    int32_t group_rows, const float *W2, float *Z0, int tag, hipStream_t st);
+// Y = act(scale * A_g @ X + bias) per graph, LDS-staged; optional fused Zpart (W2 epilogue).  x_slab / y_slab: the
+// operand uses the slab layout [slice][R][FS] instead of row-major with leading dimension ldx / ldy
+int gmc_spmm_lds_launch(const gmc_batch *b, const float *X, long ldx, int x_slab, int shared_src, int use_vals,
+                        const float *scale, const float *bias, int relu, float *Y, long ldy, int y_slab, int F,
+                        const float *W2, float *Zpart, int tag, hipStream_t st);
+
+// ---- dW1 (dw1.hip, spmm_lds.hip) ------------------------------------------------------------------------------------
+int gmc_dw1_chunks(int B, bool lds, int slices);
+size_t gmc_dw1_scratch_floats(const gmc_batch *b, int N, int F, bool lds);
+int gmc_dw1_launch(const gmc_batch *b, const float *U, long ldu, float *dW1, float *scratch, int N, int F, bool lds,
+                   hipStream_t st);
+int gmc_dw1_lds_launch(const gmc_batch *b, const float *U, long ldu, int u_slab, float *out, int F, int chunks,
+                       int graphs_per_chunk, hipStream_t st);
+
+// ---- head (head.hip), hidden backward (hidden_bwd.hip), dropout (dropout.hip) --------------------------------------
+// tick != nullptr: the launch also advances the device-side Adam step counter
+int gmc_head_launch(const gmc_batch *batch, const float *Z0, int32_t z_parts, const float *b2, float C, float *P,
+                    int32_t *S, float *loss, float *GY2, float *db2part, int *tick, hipStream_t st);
+int gmc_head_bwd_launch(const gmc_batch *batch, const float *P, const float *GP, float *GY2, float *db2part,
+                        hipStream_t st);
+int gmc_hidden_tiles(int R);
+int gmc_hidden_slab_tiles(int R);
+int gmc_hidden_bwd_launch(const float *H, long ldh, const float *GY2, const float *W2, const float *dinv, float *Gs,
+                          long ldg, float *part, int R, int F, hipStream_t st);
+int gmc_hidden_bwd_slab_launch(const float *H, const float *GY2, const float *W2, const float *dinv, float *Gs,
+                               float *part, int R, int F, int fs, hipStream_t st);
+int gmc_colsum_reduce_launch(const float *part, int tiles, int F, float *dW2, float *db1, const float *db2part, int B,
+                             float *db2, hipStream_t st);
+int gmc_dropout_launch(float *H, long R, int F, int fs, long ld, float p, unsigned long long seed, hipStream_t st);
+int gmc_hw2_rows_launch(const float *H, const float *dinv, const float *W2, float *Z0, long R, int F, int fs, long ld,
+                        hipStream_t st);
+int gmc_scale_copy_launch(const float *src, float *dst, int n, float s, hipStream_t st);

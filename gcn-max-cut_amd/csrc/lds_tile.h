@@ -3,7 +3,9 @@
 // anonymous namespace: each translation unit gets its own copy.
 #pragma once
 #include "gmc_common.h"
+#include "launchers.h"
 #include <stdlib.h>
+#include <type_traits>
 
 
 // Diagnostic build only (-DGMC_STAMP, `make stamp`): EVERY wave of the first 256 workgroups accumulates the
@@ -58,16 +60,6 @@ static __device__ unsigned long long g_stamps[4096 * 16];  // one copy per trans
 #define GMC_ABLATE 0
 #endif
 #define ABL(n) (GMC_ABLATE == (n))
-
-// OVF flavours of the 8-slot kernels: 1 = read a row's slots four at a time (gather_ids8_halves: fewer registers in
-// flight), 0 = the plain kernels' gathers (eight reads in flight per row).  The backward needs the former to stay
-// free of scratch; the forward does not any more (its hub rows are a register bit now, not LDS descriptors).
-#ifndef GMC_OVF_HALVES_FWD
-#define GMC_OVF_HALVES_FWD 0
-#endif
-#ifndef GMC_OVF_HALVES_BWD
-#define GMC_OVF_HALVES_BWD 1
-#endif
 
 namespace {
 
@@ -574,8 +566,9 @@ __device__ __forceinline__ gmc::v4f gather_ids8_pk(const float *tile, const uint
 }
 
 // gather_ids8 for unit weights with the row's eight slots read four at a time (two half blocks kept apart): what the
-// OVF flavours of the 8-slot kernels use - they carry a few more live values than the plain kernels, and with eight
-// rows of reads in flight that was enough to push values into scratch inside the gathers.
+// OVF flavours of the 8-slot backward use - they carry a few more live values than the plain kernels, and with eight
+// rows of reads in flight that was enough to push values into scratch inside the gathers.  (The OVF forward gathers
+// like the plain kernels: its hub rows are a register bit, not LDS descriptors.)
 template <int FS>
 __device__ __forceinline__ float4 gather_ids8_halves(const float *tile, const uint4 ids, int q) {
     float4 x[4];
@@ -605,15 +598,57 @@ int pick_fs(int n_max, int W) {
 }
 
 // The flavour word (gcnmaxcut.h, GMC_FLV_*) of one instantiation.  Each launcher's host-only `*_flavour` function
-// makes every choice of template arguments from the gmc_batch fields and F; the launcher then dispatches on the
-// word's fields and launches through launch_flv, which refuses a kernel whose own word differs - the query
-// (gmc_lds_flavours) and the launch cannot drift apart.
+// makes every choice of template arguments from the batch's geometry (gmc_lds_geometry) and F; the launcher turns the
+// word back into template arguments with decode_flavour and launches through launch_flv, which refuses a kernel whose
+// own word differs - the query (gmc_lds_flavours) and the launch cannot drift apart.
 constexpr int flavour_word(int kernel, int FS, int W, int ACC, bool has_val, int NS, bool ovf, bool head = false,
                            bool epi = false, bool shared = false) {
     return kernel | FS << 3 | W << 10 | ACC << 15 | NS << 19 | (int)has_val << 24 | (int)ovf << 25 | (int)head << 26 |
            (int)epi << 27 | (int)shared << 28;
 }
 inline int flavour_per(int per) { return (per >= 8 ? 3 : per >= 4 ? 2 : per >= 2 ? 1 : 0) << 29; }
+
+// the template fields of a flavour word as compile-time constants
+template <int FS_, int W_, int ACC_, int NS_, int BITS>   // BITS = word bits 24..28: HAS_VAL, OVF, HEAD, EPI, SHARED
+struct Flv {
+    static constexpr int FS = FS_, W = W_, ACC = ACC_, NS = NS_;
+    static constexpr bool HAS_VAL = BITS & 1, OVF = BITS >> 1 & 1, HEAD = BITS >> 2 & 1, EPI = BITS >> 3 & 1,
+                          SHARED = BITS >> 4 & 1;
+    static constexpr int word(int kernel) { return flavour_word(kernel, FS, W, ACC, HAS_VAL, NS, OVF, HEAD, EPI, SHARED); }
+};
+// f(std::integral_constant<int, V>{}) for the V of Vs that equals v; GMC_ERR_UNSUPPORTED if none does
+template <int... Vs, typename Fn>
+int with_value(int v, Fn &&f) {
+    int rc = GMC_ERR_UNSUPPORTED;
+    (void)((v == Vs && ((rc = f(std::integral_constant<int, Vs>{})), true)) || ...);
+    return rc;
+}
+// Turn a flavour word into its Flv and return launch(Flv{}) if the kernel builds that flavour (Built::has(Flv{}): each
+// launcher states its set next to it); any other word returns GMC_ERR_UNSUPPORTED.  Only geometries the query can
+// produce are decoded: NS one of the table's classes (ns_class), ACC = 8 at FS >= 32 (a 16-column tile never holds
+// more than 1020 rows, see pick_fs).
+template <typename Built, typename Launch>
+int decode_flavour(int flv, Launch &&launch) {
+    return with_value<8, 16>(GMC_FLV_W(flv), [&](auto W) {
+        return with_value<16, 32, 64>(GMC_FLV_FS(flv), [&](auto FS) {
+            return with_value<4, 8>(GMC_FLV_ACC(flv), [&](auto ACC) {
+                return with_value<7, 8, 10, 12, 14, 16>(GMC_FLV_NS(flv), [&](auto NS) {
+                    constexpr bool ns_ok = W == 8 ? NS == 7 || NS == 8 : NS >= 10;
+                    if constexpr (!ns_ok || (ACC == 8 && FS == 16)) {
+                        return (int)GMC_ERR_UNSUPPORTED;
+                    } else {
+                        return with_value<0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16, 17, 18, 19, 20, 21, 22, 23,
+                                          24, 25, 26, 27, 28, 29, 30, 31>((flv >> 24) & 31, [&](auto bits) {
+                            using L = Flv<FS, W, ACC, NS, bits>;
+                            if constexpr (Built::has(L{})) return launch(L{});
+                            else return (int)GMC_ERR_UNSUPPORTED;
+                        });
+                    }
+                });
+            });
+        });
+    });
+}
 // rows per thread of a slice width for graphs of n_max nodes
 inline int acc_rows(int n_max, int FS) {
     const int rows_per_pass = kThreads / (FS / 4);
@@ -649,11 +684,3 @@ int launch_flv(int want, int have, K k, int grid, size_t lds, hipStream_t st, co
 }
 
 }  // namespace
-
-// host-side queries shared by the three translation units (defined in spmm_lds.hip)
-int gmc_lds_slice_width(const gmc_batch *b);
-bool gmc_lds_fits(const gmc_batch *b);
-int gmc_lds_slices(const gmc_batch *b, int F);
-int gmc_lds_groups(const gmc_batch *b, int F);
-int gmc_lds_slices_per_group(const gmc_batch *b, int F);
-int device_cus(bool allow_override = true);

@@ -17,7 +17,7 @@
 //   * workgroups are dealt round-robin over the 8 XCDs; `group_wgs` consecutive
 //     workgroup-chunks (= one graph of the block-diagonal batch) are given to ONE XCD
 //     so the 7x neighbour re-reads of a graph hit that XCD's 4 MiB L2.
-#include "gmc_common.h"
+#include "launchers.h"
 #include <stdio.h>
 #include <stdlib.h>
 

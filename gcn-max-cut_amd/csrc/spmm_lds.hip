@@ -268,80 +268,45 @@ __global__ GMC_LDS_BOUNDS void dw1_lds_kernel(Dw1TileArgs a) {
     }
 }
 
-// 8 rows per thread at FS = 16 would need n_max > 1024, which no 16-column tile fits (pick_fs): never instantiated
-template <int FS, int W, bool EPI, bool HV, bool SHARED, int NS>
-int launch_spmm_acc(int flv, const TileArgs &a, int grid, size_t lds, hipStream_t st) {
-#define GMC_SPMM(AC) launch_flv(flv, flavour_word(GMC_FLV_SPMM, FS, W, AC, HV, NS, false, false, EPI, SHARED), \
-                                spmm_lds_kernel<FS, W, AC, EPI, HV, SHARED, NS>, grid, lds, st, a)
-    if (GMC_FLV_ACC(flv) == 4) return GMC_SPMM(4);
-    if constexpr (FS > 16) return GMC_SPMM(8);
-    return GMC_ERR_UNSUPPORTED;
-#undef GMC_SPMM
-}
-
-template <int FS, int W>
-int launch_spmm(int flv, const TileArgs &a, size_t lds, hipStream_t st) {
-    const int grid = a.b.B * a.groups;
-    if (GMC_FLV_SHARED(flv))  // W1 gather: weights apply, never fused with W2
-        return GMC_FLV_HAS_VAL(flv) ? launch_spmm_acc<FS, W, false, true, true, W>(flv, a, grid, lds, st)
-                                    : launch_spmm_acc<FS, W, false, false, true, W>(flv, a, grid, lds, st);
-    // aggregations (unit weights: the ELL weights are the W1 gather's, see gmc_spmm_lds_flavour)
-#define GMC_NS(NSK) (GMC_FLV_EPI(flv) ? launch_spmm_acc<FS, W, true, false, false, NSK>(flv, a, grid, lds, st) \
-                                      : launch_spmm_acc<FS, W, false, false, false, NSK>(flv, a, grid, lds, st))
-    const int ns = GMC_FLV_NS(flv);
-    if constexpr (W == 8) return ns == 7 ? GMC_NS(7) : GMC_NS(8);
-    else return ns == 10 ? GMC_NS(10) : ns == 12 ? GMC_NS(12) : ns == 14 ? GMC_NS(14) : GMC_NS(16);
-#undef GMC_NS
-}
-
-template <int FS, int W, bool HV, int NS>
-int launch_dw1_acc(int flv, const Dw1TileArgs &a, int grid, size_t lds, hipStream_t st) {
-#define GMC_DW1(AC) launch_flv(flv, flavour_word(GMC_FLV_DW1, FS, W, AC, HV, NS, false), dw1_lds_kernel<FS, W, AC, HV, NS>, grid, lds, st, a)
-    if (GMC_FLV_ACC(flv) == 4) return GMC_DW1(4);
-    if constexpr (FS > 16) return GMC_DW1(8);
-    return GMC_ERR_UNSUPPORTED;
-#undef GMC_DW1
-}
-
-template <int FS, int W>
-int launch_dw1(int flv, const Dw1TileArgs &a, size_t lds, hipStream_t st) {
-    const int grid = a.slices * a.chunks;
-    if (GMC_FLV_HAS_VAL(flv)) return launch_dw1_acc<FS, W, true, W>(flv, a, grid, lds, st);
-    const int ns = GMC_FLV_NS(flv);
-    if constexpr (W == 8) return ns == 7 ? launch_dw1_acc<FS, 8, false, 7>(flv, a, grid, lds, st)
-                                         : launch_dw1_acc<FS, 8, false, 8>(flv, a, grid, lds, st);
-    else return ns == 10 ? launch_dw1_acc<FS, 16, false, 10>(flv, a, grid, lds, st)
-              : ns == 12 ? launch_dw1_acc<FS, 16, false, 12>(flv, a, grid, lds, st)
-              : ns == 14 ? launch_dw1_acc<FS, 16, false, 14>(flv, a, grid, lds, st)
-                         : launch_dw1_acc<FS, 16, false, 16>(flv, a, grid, lds, st);
-}
+// the flavours built: the W1 gather (shared source: weights apply, never fused with W2, every slot), and the
+// aggregations (unit weights: no caller aggregates with the ELL weights, see gmc_spmm_lds_flavour)
+struct SpmmBuilt {
+    template <typename L> static constexpr bool has(L) {
+        if (L::OVF || L::HEAD) return false;
+        return L::SHARED ? !L::EPI && L::NS == L::W : !L::HAS_VAL;
+    }
+};
+struct Dw1Built {
+    template <typename L> static constexpr bool has(L) {
+        return !L::OVF && !L::HEAD && !L::EPI && !L::SHARED && (!L::HAS_VAL || L::NS == L::W);
+    }
+};
 
 }  // namespace
 
 
-// slice width the LDS kernels (and the slab layout) use for this batch; 0 = row kernels
-int gmc_lds_slice_width(const gmc_batch *b) { return b->ell ? pick_fs(b->n_max, b->ell_width) : 0; }
-
-bool gmc_lds_fits(const gmc_batch *b) {
-    if (!b->ell) return false;
-    const int fs = pick_fs(b->n_max, b->ell_width);
-    if (!fs) return false;
-    const int rows_per_pass = kThreads / (fs / 4);
-    if ((b->n_max + rows_per_pass - 1) / rows_per_pass > 8) return false;
-    // overflow lists: their per-row descriptors have to fit behind the fused kernels' own LDS (n <= ~1004 with 8-slot
-    // tables at 16-column tiles; larger graphs with hub rows take the row kernels)
-    // (and no edge weights: the overflow blocks' weights would have to be read from global memory inside a gather)
-    return !gmc_has_overflow(b) || (!b->ell_vals && ovf_fits(b->n_max, b->ell_width, fs, b->ovf_max_blocks));
+// Slice width for the batch (pick_fs), rows per thread, live slots: what every LDS-tiled kernel's template
+// arguments share.  Fits: the widest slice whose two tile buffers + table fit the CU's LDS holds every row in at most
+// 8 passes; overflow lists need their per-row descriptors and blocks to fit behind the fused kernels' own LDS (n <=
+// ~1004 with 8-slot tables at 16-column tiles; larger graphs with hub rows take the row kernels) and no edge weights
+// (the overflow blocks' weights would have to be read from global memory inside a gather).
+GmcLdsGeom gmc_lds_geometry(const gmc_batch *b, int F) {
+    GmcLdsGeom g{};
+    g.W = b->ell_width;
+    g.fs = b->ell ? pick_fs(b->n_max, g.W) : 0;
+    if (!g.fs) return g;
+    const int rows_per_pass = kThreads / (g.fs / 4);
+    g.hv = b->ell_vals != nullptr;
+    g.ovf = gmc_has_overflow(b);
+    g.acc = acc_rows(b->n_max, g.fs);
+    g.ns = g.ovf ? g.W : ns_class(g.W, b->ell_slots, !g.hv);   // hub rows: every slot live, overflow lists walked
+    g.slices = (F + g.fs - 1) / g.fs;
+    g.fits = (b->n_max + rows_per_pass - 1) / rows_per_pass <= 8 &&
+             (!g.ovf || (!g.hv && ovf_fits(b->n_max, g.W, g.fs, b->ovf_max_blocks)));
+    return g;
 }
 
-bool gmc_bwd1_fits(const gmc_batch *b) { return gmc_lds_fits(b); }
-
-
-// column slices of the LDS-tiled kernels for F columns (0: graphs do not fit)
-int gmc_lds_slices(const gmc_batch *b, int F) {
-    const int fs = pick_fs(b->n_max, b->ell_width);
-    return fs ? (F + fs - 1) / fs : 0;
-}
+bool gmc_lds_fits(const gmc_batch *b) { return gmc_lds_geometry(b, 0).fits; }
 
 // Slice groups per graph == Zpart partials of the fused W2 epilogue (one workgroup, or one item of a
 // persistent workgroup, per group).  4 slices per group when that yields at least half a workgroup
@@ -352,13 +317,13 @@ int gmc_lds_slices(const gmc_batch *b, int F) {
 // GMC_LDS_SLICES_PER_WG overrides (tuning runs only).
 int gmc_lds_groups(const gmc_batch *b, int F) {
     const int per = gmc_lds_slices_per_group(b, F);
-    return per ? (gmc_lds_slices(b, F) + per - 1) / per : 0;
+    return per ? (gmc_lds_geometry(b, F).slices + per - 1) / per : 0;
 }
 // the slices of one group (1, 2, 4; 0: graphs do not fit)
 int gmc_lds_slices_per_group(const gmc_batch *b, int F) {
-    const int fs = pick_fs(b->n_max, b->ell_width);
-    if (!fs) return 0;
-    const int slices = (F + fs - 1) / fs;
+    const GmcLdsGeom g = gmc_lds_geometry(b, F);
+    if (!g.fs) return 0;
+    const int slices = g.slices;
 #ifdef GMC_TUNING   // tuning builds only: the shipped library reads no environment
     static const int per_env = getenv("GMC_LDS_SLICES_PER_WG") ? atoi(getenv("GMC_LDS_SLICES_PER_WG")) : 0;
 #else
@@ -375,33 +340,24 @@ int gmc_lds_slices_per_group(const gmc_batch *b, int F) {
     return per;
 }
 
-// Flavour words of the one-kernel-per-operation launches (host only: struct fields, never the device arrays); 0 = the
-// launcher refuses the batch.  Every choice of template arguments is made here.
-static int lds_rows_flavour(const gmc_batch *b, int F, int &fs, int &acc) {
-    if (!gmc_lds_fits(b) || gmc_has_overflow(b) || F <= 0) return 0;   // (overflow lists: the fused kernels walk them)
-    fs = pick_fs(b->n_max, b->ell_width);
-    const int rows_per_pass = kThreads / (fs / 4);
-    if ((b->n_max + rows_per_pass - 1) / rows_per_pass > 8) return 0;
-    acc = acc_rows(b->n_max, fs);
-    return fs == 16 && acc != 4 ? 0 : 1;
-}
+// Flavour words of the one-kernel-per-operation launches (0: the launcher refuses the batch).  Overflow lists are
+// walked by the fused kernels only.
 // shared_src: the W1 row gather (the ELL weights apply); otherwise an aggregation, unit weights: no caller aggregates
 // with the ELL weights (the layer's structure carries none), so spmm_lds_kernel<.., HAS_VAL, !SHARED> is not built
 int gmc_spmm_lds_flavour(const gmc_batch *b, int F, int shared_src, int use_vals, bool epi) {
-    int fs = 0, acc = 0;
-    if (!lds_rows_flavour(b, F, fs, acc)) return 0;
-    const int W = b->ell_width, per = flavour_per(gmc_lds_slices_per_group(b, F));
-    const bool hv = use_vals && b->ell_vals != nullptr;
-    if (shared_src) return flavour_word(GMC_FLV_SPMM, fs, W, acc, hv, W, false, false, false, true) | per;
+    const GmcLdsGeom g = gmc_lds_geometry(b, F);
+    if (!g.fits || g.ovf || F <= 0) return 0;
+    const int per = flavour_per(gmc_lds_slices_per_group(b, F));
+    const bool hv = use_vals && g.hv;
+    if (shared_src) return flavour_word(GMC_FLV_SPMM, g.fs, g.W, g.acc, hv, g.W, false, false, false, true) | per;
     if (hv) return 0;
     // live slots (no row of the batch has more neighbours): the unit-weight aggregation skips the others
-    return flavour_word(GMC_FLV_SPMM, fs, W, acc, false, ns_class(W, b->ell_slots, true), false, false, epi) | per;
+    return flavour_word(GMC_FLV_SPMM, g.fs, g.W, g.acc, false, ns_class(g.W, b->ell_slots, true), false, false, epi) | per;
 }
 int gmc_dw1_lds_flavour(const gmc_batch *b, int F) {
-    int fs = 0, acc = 0;
-    if (!lds_rows_flavour(b, F, fs, acc)) return 0;
-    const bool hv = b->ell_vals != nullptr;
-    return flavour_word(GMC_FLV_DW1, fs, b->ell_width, acc, hv, ns_class(b->ell_width, b->ell_slots, !hv), false);
+    const GmcLdsGeom g = gmc_lds_geometry(b, F);
+    if (!g.fits || g.ovf || F <= 0) return 0;
+    return flavour_word(GMC_FLV_DW1, g.fs, g.W, g.acc, g.hv, g.ns, false);
 }
 
 // Y = act(scale * A_g @ X + bias) for every graph of the batch, LDS-staged; optional fused
@@ -424,18 +380,12 @@ int gmc_spmm_lds_launch(const gmc_batch *b, const float *X, long ldx, int x_slab
                (F + fs - 1) / fs, gmc_lds_groups(b, F), W2, Zpart, 0};
     const size_t lds = lds_bytes(b->n_max, b->ell_width, fs);
     GmcProbeScope probe(tag, st);
-    if (GMC_FLV_W(flv) == 8) {
-        switch (fs) {
-            case 64: return launch_spmm<64, 8>(flv, a, lds, st);
-            case 32: return launch_spmm<32, 8>(flv, a, lds, st);
-            default: return launch_spmm<16, 8>(flv, a, lds, st);
-        }
-    }
-    switch (fs) {
-        case 64: return launch_spmm<64, 16>(flv, a, lds, st);
-        case 32: return launch_spmm<32, 16>(flv, a, lds, st);
-        default: return launch_spmm<16, 16>(flv, a, lds, st);
-    }
+    return decode_flavour<SpmmBuilt>(flv, [&](auto L) {
+        using K = decltype(L);
+        return launch_flv(flv, K::word(GMC_FLV_SPMM),
+                          spmm_lds_kernel<K::FS, K::W, K::ACC, K::EPI, K::HAS_VAL, K::SHARED, K::NS>, b->B * a.groups,
+                          lds, st, a);
+    });
 }
 
 // compute units of the current device (persistent kernels launch one workgroup per CU)
@@ -466,16 +416,9 @@ int gmc_dw1_lds_launch(const gmc_batch *b, const float *U, long ldu, int u_slab,
                   graphs_per_chunk};
     const size_t lds = lds_bytes(b->n_max, b->ell_width, fs);
     GmcProbeScope probe(GMC_K_DW1, st);
-    if (GMC_FLV_W(flv) == 8) {
-        switch (fs) {
-            case 64: return launch_dw1<64, 8>(flv, a, lds, st);
-            case 32: return launch_dw1<32, 8>(flv, a, lds, st);
-            default: return launch_dw1<16, 8>(flv, a, lds, st);
-        }
-    }
-    switch (fs) {
-        case 64: return launch_dw1<64, 16>(flv, a, lds, st);
-        case 32: return launch_dw1<32, 16>(flv, a, lds, st);
-        default: return launch_dw1<16, 16>(flv, a, lds, st);
-    }
+    return decode_flavour<Dw1Built>(flv, [&](auto L) {
+        using K = decltype(L);
+        return launch_flv(flv, K::word(GMC_FLV_DW1), dw1_lds_kernel<K::FS, K::W, K::ACC, K::HAS_VAL, K::NS>,
+                          a.slices * a.chunks, lds, st, a);
+    });
 }
