@@ -8,8 +8,9 @@
 // there and the existing backward kernels see relu'(H_dropped) = relu'(H) o mask without knowing about the
 // mask; only the 1/(1-p) factor has to be carried (through the scaled copy of W2).
 //
-// The mask is a counter-based hash of (seed, row, column): independent of the memory layout (row-major or
-// slab), of the launch shape and of the batch a graph sits in, reproducible from the seed.  It is NOT
+// The mask is a counter-based hash of (seed, batch row, column): independent of the memory layout (row-major or
+// slab) and of the launch shape, reproducible from the seed.  The row is the row of the batch, so a graph's mask
+// depends on its offset in the batch (tests/test_row_kernels.py pins this).  It is NOT
 // torch's Philox stream: bit parity with F.dropout's random numbers is unobtainable ("parity unpinned" for
 // the mask; the arithmetic around it is property-tested, tests/test_gpu_parity.py).
 #include "launchers.h"

@@ -306,35 +306,52 @@ __global__ __launch_bounds__(256) void spmm_rows_scalar(SpmmArgs a) {
     }
 }
 
+// The W1 gather (VARIANT 1) never carries the W2 epilogue: only the aggregations are instantiated with EPI.
+template <int NP, int RPW, int UNR, bool HAS_VAL, bool NT, int VARIANT>
+void launch_v4(const SpmmArgs &a, int grid, hipStream_t st) {
+    if constexpr (VARIANT == 0) {
+        if (a.Z0) {
+            hipLaunchKernelGGL((spmm_rows_v4<NP, RPW, UNR, HAS_VAL, true, NT, 0>), dim3(grid), dim3(256), 0, st, a);
+            return;
+        }
+    }
+    hipLaunchKernelGGL((spmm_rows_v4<NP, RPW, UNR, HAS_VAL, false, NT, VARIANT>), dim3(grid), dim3(256), 0, st, a);
+}
+
 template <int NP, int RPW, int UNR, bool NT, int VARIANT>
 int launch_cfg(SpmmArgs a, int group_rows, hipStream_t st) {
     constexpr int rows_per_wg = RPW * kWavesPerWg;
     const int grid = (a.n_rows + rows_per_wg - 1) / rows_per_wg;
     a.group_wgs = group_rows > 0 ? (group_rows + rows_per_wg - 1) / rows_per_wg : 0;
-    const bool hv = a.vals != nullptr, epi = a.Z0 != nullptr;
-    if (hv) {
-        if (epi) hipLaunchKernelGGL((spmm_rows_v4<NP, RPW, UNR, true, true, NT, VARIANT>), dim3(grid), dim3(256), 0, st, a);
-        else hipLaunchKernelGGL((spmm_rows_v4<NP, RPW, UNR, true, false, NT, VARIANT>), dim3(grid), dim3(256), 0, st, a);
-    } else {
-        if (epi) hipLaunchKernelGGL((spmm_rows_v4<NP, RPW, UNR, false, true, NT, VARIANT>), dim3(grid), dim3(256), 0, st, a);
-        else hipLaunchKernelGGL((spmm_rows_v4<NP, RPW, UNR, false, false, NT, VARIANT>), dim3(grid), dim3(256), 0, st, a);
-    }
+    if (a.vals) launch_v4<NP, RPW, UNR, true, NT, VARIANT>(a, grid, st);
+    else launch_v4<NP, RPW, UNR, false, NT, VARIANT>(a, grid, st);
     GMC_LAUNCH_CHECK();
     return GMC_OK;
 }
 
+#ifdef GMC_TUNING   // tuning builds only (`make variant DEFS=-DGMC_TUNING`): the shipped library reads no environment
 // GMC_SPMM_TUNE="rpw,unroll,nt" selects a tuning variant (F in (256,512], aggregation use);
 // read once.  Only for the sweeps recorded under profiles/: production uses the default.
 struct Tune { int rpw = 0, unr = 0, nt = 0; };
 const Tune &tune() {
     static Tune t = [] {
         Tune v;
-#ifdef GMC_TUNING   // tuning builds only (`make variant DEFS=-DGMC_TUNING`): the shipped library reads no environment
         if (const char *e = getenv("GMC_SPMM_TUNE")) sscanf(e, "%d,%d,%d", &v.rpw, &v.unr, &v.nt);
-#endif
         return v;
     }();
     return t;
+}
+#endif
+
+template <bool HAS_VAL, int VARIANT>
+void launch_wide_v(const SpmmArgs &a, int grid, hipStream_t st) {
+    if constexpr (VARIANT == 0) {
+        if (a.Z0) {
+            hipLaunchKernelGGL((spmm_rows_wide<kRowsPerWave, kUnroll, HAS_VAL, true, 0>), dim3(grid), dim3(256), 0, st, a);
+            return;
+        }
+    }
+    hipLaunchKernelGGL((spmm_rows_wide<kRowsPerWave, kUnroll, HAS_VAL, false, VARIANT>), dim3(grid), dim3(256), 0, st, a);
 }
 
 template <int VARIANT>
@@ -342,14 +359,8 @@ int launch_wide(SpmmArgs a, int group_rows, hipStream_t st) {
     constexpr int rows_per_wg = kRowsPerWave * kWavesPerWg;
     const int grid = (a.n_rows + rows_per_wg - 1) / rows_per_wg;
     a.group_wgs = group_rows > 0 ? (group_rows + rows_per_wg - 1) / rows_per_wg : 0;
-    const bool hv = a.vals != nullptr, epi = a.Z0 != nullptr;
-    if (hv) {
-        if (epi) hipLaunchKernelGGL((spmm_rows_wide<kRowsPerWave, kUnroll, true, true, VARIANT>), dim3(grid), dim3(256), 0, st, a);
-        else hipLaunchKernelGGL((spmm_rows_wide<kRowsPerWave, kUnroll, true, false, VARIANT>), dim3(grid), dim3(256), 0, st, a);
-    } else {
-        if (epi) hipLaunchKernelGGL((spmm_rows_wide<kRowsPerWave, kUnroll, false, true, VARIANT>), dim3(grid), dim3(256), 0, st, a);
-        else hipLaunchKernelGGL((spmm_rows_wide<kRowsPerWave, kUnroll, false, false, VARIANT>), dim3(grid), dim3(256), 0, st, a);
-    }
+    if (a.vals) launch_wide_v<true, VARIANT>(a, grid, st);
+    else launch_wide_v<false, VARIANT>(a, grid, st);
     GMC_LAUNCH_CHECK();
     return GMC_OK;
 }
@@ -359,6 +370,7 @@ int launch_np(const SpmmArgs &a, int group_rows, hipStream_t st) {
     if (a.F > 1024) return launch_wide<VARIANT>(a, group_rows, st);
     if (a.F <= 256) return launch_cfg<1, kRowsPerWave, kUnroll, false, VARIANT>(a, group_rows, st);
     if (a.F <= 512) {
+#ifdef GMC_TUNING
         if (VARIANT == 0 && tune().rpw) {
             const Tune &t = tune();
 #define GMC_TUNE_CASE(R, U, N) \
@@ -368,6 +380,7 @@ int launch_np(const SpmmArgs &a, int group_rows, hipStream_t st) {
             GMC_TUNE_CASE(2, 4, 1) GMC_TUNE_CASE(2, 8, 1) GMC_TUNE_CASE(4, 4, 1) GMC_TUNE_CASE(4, 8, 1)
 #undef GMC_TUNE_CASE
         }
+#endif
         return launch_cfg<2, kRowsPerWave, kUnroll, false, VARIANT>(a, group_rows, st);
     }
     return launch_cfg<4, kRowsPerWave, kUnroll, false, VARIANT>(a, group_rows, st);
@@ -382,6 +395,7 @@ int gmc_spmm_launch(const int32_t *rowptr, const int32_t *col, const float *vals
     if (!rowptr || !col || !X || !Y) return GMC_ERR_NULL;
     if (n_rows < 0 || F <= 0 || ldx < F || ldy < F) return GMC_ERR_SHAPE;
     if ((W2 == nullptr) != (Z0 == nullptr)) return GMC_ERR_NULL;
+    if (tag == GMC_K_GATHER_W1 && Z0) return GMC_ERR_UNSUPPORTED;   // the W1 gather has no W2 epilogue
     if (n_rows == 0) return GMC_OK;
     SpmmArgs a{rowptr, col, vals, scale, X, (long)ldx, bias, relu, Y, (long)ldy,
                n_rows, F, 0, W2, Z0};

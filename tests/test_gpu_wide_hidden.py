@@ -56,18 +56,6 @@ def dataset(case):
     return util.product_dataset([(530, 7, 4031), (500, 8, 4032)])
 
 
-def kink_columns(ds, params, noise=1e-7):
-    """Columns f of layer 1 with a float64 pre-activation within fp32 accumulation noise of 0 (relu kinks: the kernels
-    and the oracle may take different sides, and then that column of dW1 and entry of db1 differ by design)."""
-    W = [params[k].astype(np.float64) for k in ("conv1.weight", "conv1.bias", "conv2.weight", "conv2.bias")]
-    kink = np.zeros(W[1].shape[0], bool)
-    for rp, cl, vl in util.csrs_of(ds):
-        f = util.f64_forward(rp, cl, vl, *W)
-        pre = f["dinv"][:, None] * (f["A"] @ (f["dinv"][:, None] * (f["X"] @ W[0][:len(f["dinv"])]))) + W[1]
-        kink |= (np.abs(pre) < noise).any(0)
-    return kink
-
-
 def check_step(pkg, net, ds, params):
     """util.check_step_against_oracle; where it finds a dW1 / db1 entry off the bar, the relu-kink rule of
     test_gpu_parity.test_relu_kink_is_the_only_gradient_mismatch instead: every column off the bar holds a
@@ -90,7 +78,7 @@ def check_step(pkg, net, ds, params):
     got = {k: g.cpu().numpy() for k, g in eng.views(eng.grad).items()}
     for k in ("conv2.weight", "conv2.bias"):
         assert np.abs(got[k].ravel() - ref[k]).max() <= 1e-4 * max(1.0, np.abs(ref[k]).max()), k
-    kink = np.nonzero(kink_columns(ds, params))[0]
+    kink = np.nonzero(util.kink_columns(util.csrs_of(ds), params))[0]
     F = got["conv1.bias"].shape[0]
     d1 = np.abs(got["conv1.weight"] - ref["conv1.weight"].reshape(-1, F)).max(0)
     bad = np.nonzero(d1 > 1e-4 * max(1.0, np.abs(ref["conv1.weight"]).max()))[0]

@@ -16,12 +16,11 @@ one-graph gmc_train_step_f32 - whether the head runs inside the backward.  This 
 """
 import ctypes as C
 import re
-import struct
-import subprocess
 
 import pytest
 
-ROCM_LLVM = "/opt/rocm/llvm/bin"
+from tests import util
+
 PER_MASK = 3 << 29
 KERNEL_IDS = {"fwd1_lds": 1, "bwd1_lds": 2, "bwd1_reg": 3, "spmm_lds": 4, "dw1_lds": 5}
 
@@ -141,33 +140,9 @@ def kind_struct(hip, kind, n, B=None):
 
 def instantiated_flavours(lib_path):
     """Template arguments of every LDS-tiled kernel in the library's gfx950 code objects, as flavour words (GMC_FLV_PER
-    clear).  The offload bundles of the .so are read directly (the __CLANG_OFFLOAD_BUNDLE__ header), the code objects'
-    symbols with llvm-readelf, demangled with c++filt."""
-    data = open(lib_path, "rb").read()
-    magic = b"__CLANG_OFFLOAD_BUNDLE__"
-    syms = set()
-    for m in re.finditer(re.escape(magic), data):
-        p = m.start()
-        (n,) = struct.unpack_from("<Q", data, p + len(magic))
-        q = p + len(magic) + 8
-        for _ in range(n):
-            off, size, tl = struct.unpack_from("<QQQ", data, q)
-            triple = data[q + 24:q + 24 + tl].decode()
-            q += 24 + tl
-            if not triple.endswith("gfx950"):
-                continue
-            co = data[p + off:p + off + size]
-            assert co[:4] == b"\x7fELF", triple
-            out = subprocess.run([f"{ROCM_LLVM}/llvm-readelf", "-s", "--wide", "-"], input=co, capture_output=True,
-                                 check=True).stdout.decode()
-            for line in out.splitlines():
-                f = line.split()
-                if len(f) >= 8 and f[3] == "FUNC" and f[7].startswith("_Z"):
-                    syms.add(f[7])
-    assert syms, "no gfx950 code object found in the library"
-    dem = subprocess.run(["c++filt"], input="\n".join(sorted(syms)), capture_output=True, text=True, check=True).stdout
+    clear)."""
     words = set()
-    for line in dem.splitlines():
+    for line in sorted(util.kernel_symbols(lib_path)):
         m = re.search(r"\b(fwd1_lds|bwd1_lds|bwd1_reg|spmm_lds|dw1_lds)_kernel<([^>]*)>", line)
         if not m:
             continue

@@ -1,6 +1,9 @@
 """Shared builders for the parity tests: the same seeded graphs go through the product's
 GraphExtender (-> GraphHandle + padded adjacency) and through the oracle's."""
 import copy
+import re
+import struct
+import subprocess
 
 import numpy as np
 import torch
@@ -160,16 +163,18 @@ def f64_backward(f, GP, W2, N):
     return dict(W1=dW1, b1=g.sum(0), W2=dW2, b2=gz.sum(0))
 
 
-def f64_step(csrs, params, S_got, C=1.0, tie=1e-6):
+def f64_step(csrs, params, S_got, C=1.0, tie=1e-6, sparse=False):
     """Per graph: float64 P, the partition (the kernels' own where the float64 top-2 margin is below `tie`: the
     summation orders differ, a near-tie may decode either way - anywhere else the partitions must agree), the loss
-    of that partition, and the summed float64 gradient of the batch."""
+    of that partition, and the summed float64 gradient of the batch.  `sparse`: the CSR restatement (same values)."""
+    fwd, lgp, bwd = ((f64_forward_sparse, f64_loss_and_gp_sparse, f64_backward_sparse) if sparse else
+                     (f64_forward, f64_loss_and_gp, f64_backward))
     W = [params[k] for k in ("conv1.weight", "conv1.bias", "conv2.weight", "conv2.bias")]
     grad = None
     Ps, losses, off = [], [], 0
     for rp, cl, vl in csrs:
         n = len(rp) - 1
-        f = f64_forward(rp, cl, vl, *W)
+        f = fwd(rp, cl, vl, *W)
         S = f64_partition(f["P"])
         s_got = np.asarray(S_got[off:off + n])
         diff = np.nonzero(s_got != S)[0]
@@ -177,8 +182,8 @@ def f64_step(csrs, params, S_got, C=1.0, tie=1e-6):
             srt = np.sort(f["P"][diff], axis=1)
             assert (srt[:, 2] - srt[:, 1]).max() < tie, (diff, srt)
             S = s_got.astype(np.int64)
-        loss, GP = f64_loss_and_gp(f, S, C)
-        g = f64_backward(f, GP, W[2], W[0].shape[0])
+        loss, GP = lgp(f, S, C)
+        g = bwd(f, GP, W[2], W[0].shape[0])
         grad = g if grad is None else {k: grad[k] + g[k] for k in grad}
         Ps.append(f["P"])
         losses.append(loss)
@@ -194,3 +199,137 @@ def row_error_ratio(got, ref, floor):
     ref = np.asarray(ref, np.float64).reshape(ref.shape[0], -1)
     scale = np.maximum(np.abs(ref).max(1), floor * max(np.abs(ref).max(), 1e-30))
     return float((np.abs(got - ref).max(1) / scale).max())
+
+
+
+def kink_columns(csrs, params, noise=1e-7, sparse=False):
+    """Columns f of layer 1 with a float64 pre-activation within fp32 accumulation noise of 0 (relu kinks: the kernels
+    and the oracle may take different sides, and then that column of dW1 and entry of db1 differ by design)."""
+    W = [params[k].astype(np.float64) for k in ("conv1.weight", "conv1.bias", "conv2.weight", "conv2.bias")]
+    kink = np.zeros(W[1].shape[0], bool)
+    for rp, cl, vl in csrs:
+        if sparse:
+            pre = f64_forward_sparse(rp, cl, vl, *W)["pre"]
+        else:
+            f = f64_forward(rp, cl, vl, *W)
+            pre = f["dinv"][:, None] * (f["A"] @ (f["dinv"][:, None] * (f["X"] @ W[0][:len(f["dinv"])]))) + W[1]
+        kink |= (np.abs(pre) < noise).any(0)
+    return kink
+
+
+# ---- the same float64 step on CSR segment sums: no n x n operator, for graphs of thousands of nodes and wide layers
+def csr_mm(rp, cl, w, M, block=512):
+    """CSR matrix (edge weights w; None = unit) times the dense float64 M, as per-row segment sums of M's rows."""
+    n = len(rp) - 1
+    out = np.zeros((n, M.shape[1]))
+    live = np.nonzero(np.diff(rp))[0]
+    if live.size == 0:
+        return out
+    starts = np.asarray(rp[:-1])[live]
+    for c0 in range(0, M.shape[1], block):
+        G = M[cl, c0:c0 + block]
+        if w is not None:
+            G = G * w[:, None]
+        out[live, c0:c0 + block] = np.add.reduceat(G, starts, axis=0)
+    return out
+
+
+def f64_forward_sparse(rp, cl, vl, W1, b1, W2, b2):
+    """f64_forward on the CSR: the aggregations carry no edge weight, the features (the weighted adjacency) do."""
+    n = len(rp) - 1
+    vw = None if vl is None else np.asarray(vl, np.float64)
+    dinv = 1.0 / np.sqrt(np.maximum(np.diff(rp), 1).astype(np.float64))
+    W1, b1, W2, b2 = (np.asarray(w, np.float64) for w in (W1, b1, W2, b2))
+    T0 = dinv[:, None] * csr_mm(rp, cl, vw, W1[:n])
+    pre = dinv[:, None] * csr_mm(rp, cl, None, T0) + b1
+    H = np.maximum(pre, 0.0)
+    Z = dinv[:, None] * csr_mm(rp, cl, None, dinv[:, None] * H @ W2) + b2
+    E = np.exp(Z - Z.max(1, keepdims=True))
+    return dict(rp=rp, cl=cl, w=vw, dinv=dinv, pre=pre, H=H, P=E / E.sum(1, keepdims=True))
+
+
+def f64_loss_and_gp_sparse(f, S, C=1.0):
+    rp, cl, w = f["rp"], f["cl"], f["w"]
+    rows = np.repeat(np.arange(len(rp) - 1), np.diff(rp))
+    cut_w = (S[rows] != S[cl]).astype(np.float64)
+    cut = 0.5 * float((cut_w if w is None else cut_w * w).sum())
+    return -C * cut, C * csr_mm(rp, cl, w, np.eye(3)[S])
+
+
+def f64_backward_sparse(f, GP, W2, N):
+    rp, cl, w, dinv, H, P = f["rp"], f["cl"], f["w"], f["dinv"], f["H"], f["P"]
+    W2 = np.asarray(W2, np.float64)
+    gz = P * (GP - (GP * P).sum(1, keepdims=True))
+    gy2 = csr_mm(rp, cl, None, dinv[:, None] * gz)
+    dW2 = (dinv[:, None] * H).T @ gy2
+    g = np.where(H > 0, dinv[:, None] * (gy2 @ W2.T), 0.0)
+    gy1 = csr_mm(rp, cl, None, dinv[:, None] * g)
+    dW1 = np.zeros((N, H.shape[1]))
+    dW1[:len(dinv)] = csr_mm(rp, cl, w, dinv[:, None] * gy1)
+    return dict(W1=dW1, b1=g.sum(0), W2=dW2, b2=gz.sum(0))
+
+
+# ---- the dropout mask of csrc/dropout.hip restated: splitmix64 of (seed, batch row, column), 24-bit uniform in float32
+_U64 = np.uint64
+
+
+def mix64(z):
+    z = np.asarray(z, np.uint64)
+    with np.errstate(over="ignore"):
+        z = (z ^ (z >> _U64(30))) * _U64(0xBF58476D1CE4E5B9)
+        z = (z ^ (z >> _U64(27))) * _U64(0x94D049BB133111EB)
+    return z ^ (z >> _U64(31))
+
+
+def dropout_uniform(seed, rows, cols):
+    """uniform_of(seed, row, col) for every (row, col) of the two index vectors: [len(rows), len(cols)] float32."""
+    idx = np.asarray(rows, np.uint64)[:, None] * _U64(4096) + np.asarray(cols, np.uint64)[None, :] + _U64(1)
+    with np.errstate(over="ignore"):
+        h = mix64(_U64(seed) + _U64(0x9E3779B97F4A7C15) * idx)
+    return (h >> _U64(40)).astype(np.float32) * np.float32(1.0 / 16777216.0)
+
+
+def dropout_keep(seed, rows, cols, p):
+    """The kept units of the batch rows x columns (the kernel keeps iff u >= p, both in float32)."""
+    return dropout_uniform(seed, rows, cols) >= np.float32(p)
+
+
+# ---- the gfx950 code objects of the built library (census tests; CPU only)
+ROCM_LLVM = "/opt/rocm/llvm/bin"
+
+
+def gfx950_code_objects(lib_path):
+    """The gfx950 ELF code objects inside the library's offload bundles (the __CLANG_OFFLOAD_BUNDLE__ header)."""
+    data = open(lib_path, "rb").read()
+    magic = b"__CLANG_OFFLOAD_BUNDLE__"
+    out = []
+    for m in re.finditer(re.escape(magic), data):
+        p = m.start()
+        (n,) = struct.unpack_from("<Q", data, p + len(magic))
+        q = p + len(magic) + 8
+        for _ in range(n):
+            off, size, tl = struct.unpack_from("<QQQ", data, q)
+            triple = data[q + 24:q + 24 + tl].decode()
+            q += 24 + tl
+            if not triple.endswith("gfx950"):
+                continue
+            co = data[p + off:p + off + size]
+            assert co[:4] == b"\x7fELF", triple
+            out.append(co)
+    assert out, "no gfx950 code object found in the library"
+    return out
+
+
+def kernel_symbols(lib_path):
+    """Demangled names of every function in the library's gfx950 code objects (symbols read with llvm-readelf,
+    demangled with c++filt)."""
+    syms = set()
+    for co in gfx950_code_objects(lib_path):
+        out = subprocess.run([f"{ROCM_LLVM}/llvm-readelf", "-s", "--wide", "-"], input=co, capture_output=True,
+                             check=True).stdout.decode()
+        for line in out.splitlines():
+            f = line.split()
+            if len(f) >= 8 and f[3] == "FUNC" and f[7].startswith("_Z"):
+                syms.add(f[7])
+    dem = subprocess.run(["c++filt"], input="\n".join(sorted(syms)), capture_output=True, text=True, check=True).stdout
+    return set(dem.splitlines())
