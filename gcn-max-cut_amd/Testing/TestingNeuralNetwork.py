@@ -79,7 +79,24 @@ def _sample_on_gpu(batch: GraphBatch, P: torch.Tensor, iterations: int):
     rc = hip.load().gmc_decode_sample_f32(batch.ref(), p(P.contiguous()), p(u), p(uo), iterations, p(assign_all),
                                           p(cut_all), p(best_assign), p(best_cut), p(best_iter), hip.stream())
     hip.check(rc, "gmc_decode_sample_f32")
-    return best_assign, best_cut, cut_all
+    return best_assign, best_cut, cut_all, assign_all
+
+
+def _refine_on_gpu(batch: GraphBatch, assign: torch.Tensor, max_sweeps: int):
+    """Local search (gmc_refine_local_f32) over the candidates assign [cands, R] int8, refined in place; returns the
+    best refined assignment [R], its cut and candidate index per graph."""
+    dev = batch.device
+    cands = int(assign.shape[0])
+    order, cgoff, cptr = batch.refine_order()
+    cut_all = torch.empty((batch.B, cands), dtype=torch.float32, device=dev)
+    best_assign = torch.empty(batch.R, dtype=torch.int32, device=dev)
+    best_cut = torch.empty(batch.B, dtype=torch.float32, device=dev)
+    best_idx = torch.empty(batch.B, dtype=torch.int32, device=dev)
+    p = hip.ptr
+    rc = hip.load().gmc_refine_local_f32(batch.ref(), p(order), p(cgoff), p(cptr), cands, p(assign), int(max_sweeps),
+                                         p(cut_all), p(best_assign), p(best_cut), p(best_idx), None, hip.stream())
+    hip.check(rc, "gmc_refine_local_f32")
+    return best_assign, best_cut, best_idx
 
 
 def _as_number(x: float):
@@ -94,7 +111,27 @@ def post_processing_optimization(node_probabilities, graph, iterations: int = 20
     if iterations <= 0:
         return None, -float('inf')
     batch = GraphBatch([from_networkx(graph)], None, dev)
-    best_assign, best_cut, _ = _sample_on_gpu(batch, probs, iterations)
+    best_assign, best_cut, _, _ = _sample_on_gpu(batch, probs, iterations)
+    return best_assign.cpu().tolist(), _as_number(best_cut.item())
+
+
+def local_search_optimization(partition_assignment, graph, max_sweeps: int = 100) -> Tuple[List[int], Any]:
+    """Refine one assignment of ``graph`` (e.g. ``simple_partition_assignment``'s) by single-node moves on the GPU
+    (extension, include/gcnmaxcut.h ``gmc_refine_local_f32``): nodes 0, 1, 2 keep their classes, every other node
+    moves to the class that cuts the most of its edge weight, sweep after sweep, until a sweep moves nothing or
+    ``max_sweeps`` have run.  Returns the refined assignment and its cut value."""
+    dev = hip.require_gpu()
+    part = np.asarray(list(partition_assignment), dtype=np.int64)
+    n = graph.number_of_nodes()
+    if part.shape != (n,):
+        raise ValueError(f"partition_assignment has {part.size} entries, the graph {n} nodes")
+    if part.size and (int(part.min()) < 0 or int(part.max()) > 2):
+        raise ValueError("partition_assignment holds a class outside 0..2")
+    if max_sweeps < 0:
+        raise ValueError(f"max_sweeps must be >= 0, got {max_sweeps}")
+    batch = GraphBatch([from_networkx(graph)], None, dev)
+    assign = torch.from_numpy(part.astype(np.int8)).to(dev).reshape(1, n)
+    best_assign, best_cut, _ = _refine_on_gpu(batch, assign, max_sweeps)
     return best_assign.cpu().tolist(), _as_number(best_cut.item())
 
 
@@ -187,10 +224,14 @@ def test_multiple_graphs(model, processed_graphs: Dict, graph_sizes: List[int],
 test_multiple_graphs.__test__ = False
 
 
-def decode_dataset(model, processed_graphs: Dict, post_processing_iterations: int = 200) -> List[Dict[str, Any]]:
+def decode_dataset(model, processed_graphs: Dict, post_processing_iterations: int = 200,
+                   local_search_sweeps: int = 0) -> List[Dict[str, Any]]:
     """Throughput form of the same evaluation (extension): ONE batched forward and ONE sampler
     launch for the whole dataset.  Results equal ``test_multiple_graphs``'s per-graph numbers when
-    the RNG state is the same (uniforms are drawn graph by graph in dataset order)."""
+    the RNG state is the same (uniforms are drawn graph by graph in dataset order).
+    ``local_search_sweeps > 0`` also refines the argmax decode (candidate 0) and every sample (candidates
+    1..iterations, in draw order) by local search (``local_search_optimization``) in one more launch; each result
+    then carries ``refined_cut``, ``refined_assignment`` and ``refined_from`` (the winning candidate)."""
     items = list(processed_graphs.values())
     eng = model.engine()
     model.eval()
@@ -198,7 +239,11 @@ def decode_dataset(model, processed_graphs: Dict, post_processing_iterations: in
     vals = [h.edge_values(it[1]) for h, it in zip(handles, items)]
     batch = GraphBatch(handles, vals, eng.device)
     P, S, loss = eng.forward(batch, 1.0, want_loss=True)
-    best_assign, best_cut, _ = _sample_on_gpu(batch, P, post_processing_iterations)
+    best_assign, best_cut, _, assign_all = _sample_on_gpu(batch, P, post_processing_iterations)
+    refined = None
+    if local_search_sweeps > 0:
+        cands = torch.cat([S.to(torch.int8).reshape(1, -1), assign_all])
+        refined = [t.cpu().numpy() for t in _refine_on_gpu(batch, cands, local_search_sweeps)]
     S_host, best_host = S.cpu().numpy(), best_assign.cpu().numpy()
     simple, post = (-loss).cpu().tolist(), best_cut.cpu().tolist()
     out = []
@@ -207,4 +252,8 @@ def decode_dataset(model, processed_graphs: Dict, post_processing_iterations: in
         out.append({'nodes': hi - lo, 'simple_cut': _as_number(simple[g]), 'simple_assignment': S_host[lo:hi].tolist(),
                     'post_cut': _as_number(post[g]), 'post_assignment': best_host[lo:hi].tolist(),
                     'improvement': _as_number(post[g] - simple[g])})
+        if refined is not None:
+            ref_assign, ref_cut, ref_idx = refined
+            out[-1].update({'refined_cut': _as_number(ref_cut[g]), 'refined_assignment': ref_assign[lo:hi].tolist(),
+                            'refined_from': int(ref_idx[g])})
     return out

@@ -1,0 +1,60 @@
+// Cut count and best-candidate pick shared by the post-processing sampler (decode.hip) and the local search
+// (refine.hip): both score their candidates with the same code, so a candidate the search does not move gets, bit
+// for bit, the cut the sampler reports for it.
+#pragma once
+#include "gmc_common.h"
+
+namespace gmc {
+
+// Cut of the assignment `sa` (local node id -> class byte, in LDS) of the graph on batch rows r0 .. r0+n-1: the
+// edge-parallel count over the CSR (each undirected edge seen twice -> / 2), one thread per row, a butterfly per
+// wave, the four wave sums in a fixed order.  Every thread of the 256-thread workgroup must call it (one barrier);
+// thread 0 gets the cut.  red: 4 floats of LDS.
+__device__ __forceinline__ float block_cut(const gmc_batch &b, const unsigned char *sa, int r0, int n, float *red) {
+    float cut = 0.f;
+    for (int l = threadIdx.x; l < n; l += blockDim.x) {
+        const int r = r0 + l;
+        const int me = sa[l];
+        for (int e = b.rowptr[r]; e < b.rowptr[r + 1]; ++e) {
+            const float w = b.vals ? b.vals[e] : 1.0f;
+            cut += sa[b.lcol[e]] != me ? w : 0.f;
+        }
+    }
+    cut = wave_sum(cut);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = cut;
+    __syncthreads();
+    return (((red[0] + red[1]) + red[2]) + red[3]) * 0.5f;
+}
+
+struct PickArgs {
+    gmc_batch b;
+    int iters;                     // candidates per graph
+    const signed char *assign_all; // [iters][R]
+    const float *cut_all;          // [B][iters]
+    int *best_assign;  // [R]
+    float *best_cut;   // [B]
+    int *best_iter;    // [B]
+};
+
+// One workgroup (256 threads) per graph: the strictly best candidate, the first one on ties, and its assignment.
+__device__ __forceinline__ void pick_best(const PickArgs &a) {
+    __shared__ int sbest;
+    const int g = blockIdx.x;
+    if (threadIdx.x == 0) {  // strict '>' keeps the first best (TestingNeuralNetwork.py:94)
+        int bi = 0;
+        float bc = a.cut_all[(long)g * a.iters];
+        for (int i = 1; i < a.iters; ++i) {
+            const float c = a.cut_all[(long)g * a.iters + i];
+            if (c > bc) { bc = c; bi = i; }
+        }
+        sbest = bi;
+        a.best_cut[g] = bc;
+        a.best_iter[g] = bi;
+    }
+    __syncthreads();
+    const int r0 = a.b.goff[g], n = a.b.goff[g + 1] - r0;
+    for (int l = threadIdx.x; l < n; l += blockDim.x)
+        a.best_assign[r0 + l] = a.assign_all[(long)sbest * a.b.R + r0 + l];
+}
+
+}  // namespace gmc

@@ -19,6 +19,7 @@
 // One workgroup per (iteration, graph): the sampled assignment lives in LDS, the cut is an
 // edge-parallel count over the CSR (each undirected edge seen twice -> / 2).
 #include "gmc_common.h"
+#include "cut_body.h"
 
 namespace {
 
@@ -51,50 +52,11 @@ __global__ __launch_bounds__(256) void decode_sample_kernel(DecodeArgs a) {
         a.assign_all[(long)it * a.b.R + r0 + l] = (signed char)c;
     }
     __syncthreads();
-    float cut = 0.f;
-    for (int l = threadIdx.x; l < n; l += blockDim.x) {
-        const int r = r0 + l;
-        const int me = sa[l];
-        for (int e = a.b.rowptr[r]; e < a.b.rowptr[r + 1]; ++e) {
-            const float w = a.b.vals ? a.b.vals[e] : 1.0f;
-            cut += sa[a.b.lcol[e]] != me ? w : 0.f;
-        }
-    }
-    cut = gmc::wave_sum(cut);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = cut;
-    __syncthreads();
-    if (threadIdx.x == 0) a.cut_all[(long)g * a.iters + it] = (((red[0] + red[1]) + red[2]) + red[3]) * 0.5f;
+    const float cut = gmc::block_cut(a.b, sa, r0, n, red);
+    if (threadIdx.x == 0) a.cut_all[(long)g * a.iters + it] = cut;
 }
 
-struct PickArgs {
-    gmc_batch b;
-    int iters;
-    const signed char *assign_all;
-    const float *cut_all;
-    int *best_assign;  // [R]
-    float *best_cut;   // [B]
-    int *best_iter;    // [B]
-};
-
-__global__ __launch_bounds__(256) void decode_pick_kernel(PickArgs a) {
-    __shared__ int sbest;
-    const int g = blockIdx.x;
-    if (threadIdx.x == 0) {  // strict '>' keeps the first best (TestingNeuralNetwork.py:94)
-        int bi = 0;
-        float bc = a.cut_all[(long)g * a.iters];
-        for (int i = 1; i < a.iters; ++i) {
-            const float c = a.cut_all[(long)g * a.iters + i];
-            if (c > bc) { bc = c; bi = i; }
-        }
-        sbest = bi;
-        a.best_cut[g] = bc;
-        a.best_iter[g] = bi;
-    }
-    __syncthreads();
-    const int r0 = a.b.goff[g], n = a.b.goff[g + 1] - r0;
-    for (int l = threadIdx.x; l < n; l += blockDim.x)
-        a.best_assign[r0 + l] = a.assign_all[(long)sbest * a.b.R + r0 + l];
-}
+__global__ __launch_bounds__(256) void decode_pick_kernel(gmc::PickArgs a) { gmc::pick_best(a); }
 
 }  // namespace
 
@@ -117,7 +79,7 @@ extern "C" int gmc_decode_sample_f32(const gmc_batch *batch, const float *P, con
         hipLaunchKernelGGL(decode_sample_kernel, dim3(iters, batch->B), dim3(256), (size_t)batch->n_max, st, a);
         GMC_LAUNCH_CHECK();
     }
-    PickArgs p{*batch, iters, reinterpret_cast<const signed char *>(assign_all), cut_all, best_assign, best_cut, best_iter};
+    gmc::PickArgs p{*batch, iters, reinterpret_cast<const signed char *>(assign_all), cut_all, best_assign, best_cut, best_iter};
     hipLaunchKernelGGL(decode_pick_kernel, dim3(batch->B), dim3(256), 0, st, p);
     GMC_LAUNCH_CHECK();
     return GMC_OK;

@@ -1,0 +1,163 @@
+// Single-node-move local search over decoded partitions (an extension: the reference stops at the best of its random
+// samples, TestingNeuralNetwork.py:66-98).
+//
+// Per graph of the batch (local ids 0..n-1): nodes 0, 1, 2 never move (override_fixed_nodes, TrainingNeural.py:87-94).
+// The movable nodes 3..n-1 are coloured first-fit in increasing id against their movable neighbours of smaller id
+// (gmc_refine_order_host, on the host), so every colour class is an independent set among movable nodes.  A sweep
+// visits the classes in increasing colour; each node v of a class sums, in fp32 and in the CSR order of its row, the
+// weights of its edges to classes 0, 1 and 2 (self-loops skipped) into W0, W1, W2, and moves to the class k of the
+// smallest W (lowest index on ties) iff W[k] < W[class(v)].  No two nodes of a class are adjacent, so the nodes of a
+// class move in parallel and the result is that of a sequential sweep in (colour, id) order.  Sweeps stop after one
+// that moves nothing, or after max_sweeps.  The refined candidates are then scored and picked by the sampler's own
+// code (cut_body.h).
+//
+// One workgroup per (candidate, graph): the candidate's classes live in LDS as bytes (n_max <= 4096 -> 4 KB), one
+// thread per node of the current class, a barrier between classes, a workgroup-wide OR closing every sweep.
+#include "gmc_common.h"
+#include "cut_body.h"
+
+#include <vector>
+
+namespace {
+
+struct RefineArgs {
+    gmc_batch b;
+    const int *order;        // movable rows of each graph, sorted by (colour, id)
+    const int *cgoff;        // [B+1] first class pointer of each graph
+    const int *cptr;         // class k of graph g: order[cptr[cgoff[g]+k] .. cptr[cgoff[g]+k+1])
+    int cands;
+    int max_sweeps;
+    signed char *assign;     // [cands][R], in/out
+    float *cut_all;          // [B][cands]
+    int *sweeps;             // [B][cands] or NULL
+};
+
+__global__ __launch_bounds__(256) void refine_local_kernel(RefineArgs a) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char sa[];
+    __shared__ float red[4];
+    const int cand = blockIdx.x, g = blockIdx.y;
+    const int r0 = a.b.goff[g];
+    const int n = a.b.goff[g + 1] - r0;
+    signed char *as = a.assign + (long)cand * a.b.R + r0;
+    for (int l = threadIdx.x; l < n; l += blockDim.x) sa[l] = (unsigned char)as[l];
+    __syncthreads();
+    const int k0 = a.cgoff[g];
+    const int classes = a.cgoff[g + 1] - k0 - 1;
+    int s = 0;
+    while (s < a.max_sweeps) {
+        ++s;
+        int moved = 0;
+        for (int k = 0; k < classes; ++k) {
+            const int hi = a.cptr[k0 + k + 1];
+            for (int i = a.cptr[k0 + k] + threadIdx.x; i < hi; i += blockDim.x) {
+                const int l = a.order[i] - r0;
+                if ((unsigned)l >= (unsigned)n) continue;   // not a row of this graph: never touch LDS for it
+                // three sums chosen by compares (an indexed private array would live in scratch); a class byte
+                // outside 0..2 adds to none of them
+                float w0 = 0.f, w1 = 0.f, w2 = 0.f;
+                const int e1 = a.b.rowptr[r0 + l + 1];
+                for (int e = a.b.rowptr[r0 + l]; e < e1; ++e) {
+                    const int u = a.b.lcol[e];
+                    if (u == l) continue;
+                    const float w = a.b.vals ? a.b.vals[e] : 1.0f;
+                    const int cu = sa[u];
+                    w0 += cu == 0 ? w : 0.f;
+                    w1 += cu == 1 ? w : 0.f;
+                    w2 += cu == 2 ? w : 0.f;
+                }
+                const int c = sa[l];
+                const float wc = c == 0 ? w0 : c == 1 ? w1 : c == 2 ? w2 : __builtin_inff();
+                int kk = 0;
+                float wk = w0;
+                if (w1 < wk) { kk = 1; wk = w1; }
+                if (w2 < wk) { kk = 2; wk = w2; }
+                if (wk < wc) {
+                    sa[l] = (unsigned char)kk;
+                    moved = 1;
+                }
+            }
+            if (k + 1 < classes) __syncthreads();
+        }
+        if (!__syncthreads_or(moved)) break;
+    }
+    for (int l = threadIdx.x; l < n; l += blockDim.x) as[l] = (signed char)sa[l];
+    const float cut = gmc::block_cut(a.b, sa, r0, n, red);
+    if (threadIdx.x == 0) {
+        a.cut_all[(long)g * a.cands + cand] = cut;
+        if (a.sweeps) a.sweeps[(long)g * a.cands + cand] = s;
+    }
+}
+
+__global__ __launch_bounds__(256) void refine_pick_kernel(gmc::PickArgs a) { gmc::pick_best(a); }
+
+}  // namespace
+
+// HOST routine (all pointers are host pointers): first-fit colouring of every graph's movable nodes and the
+// (colour, id) order the kernel walks.  cptr_cap < R + B is refused before anything is written.
+extern "C" int gmc_refine_order_host(int32_t B, const int32_t *goff, const int32_t *rowptr, const int32_t *lcol,
+                                     int32_t *order, int32_t *cgoff, int32_t *cptr, int32_t cptr_cap) {
+    if (!goff || !rowptr || !lcol || !order || !cgoff || !cptr) return GMC_ERR_NULL;
+    if (B < 0) return GMC_ERR_SHAPE;
+    for (int g = 0; g < B; ++g) {
+        const int n = goff[g + 1] - goff[g];
+        if (n < 3 || n > GMC_MAX_GRAPH_NODES) return GMC_ERR_GRAPH_SIZE;
+    }
+    if ((long long)cptr_cap < (long long)goff[B] + B) return GMC_ERR_SHAPE;
+    std::vector<int> colour(GMC_MAX_GRAPH_NODES), mark, count;
+    int pos = 0, kp = 0;
+    for (int g = 0; g < B; ++g) {
+        const int r0 = goff[g], n = goff[g + 1] - r0;
+        int ncol = 0;
+        mark.clear();   // mark[c] == v: colour c is taken at node v; stamps of the previous graph must not survive
+        for (int v = 3; v < n; ++v) {
+            for (int e = rowptr[r0 + v]; e < rowptr[r0 + v + 1]; ++e) {
+                const int u = lcol[e];
+                if (u >= 3 && u < v) mark[colour[u]] = v;   // colours taken by movable neighbours of smaller id
+            }
+            int c = 0;
+            while (c < ncol && mark[c] == v) ++c;
+            if (c == ncol) {
+                ++ncol;
+                mark.push_back(-1);
+            }
+            colour[v] = c;
+        }
+        count.assign(ncol, 0);
+        for (int v = 3; v < n; ++v) ++count[colour[v]];
+        cgoff[g] = kp;
+        cptr[kp++] = pos;
+        for (int c = 0; c < ncol; ++c) {   // count[c] becomes the next free place of class c
+            const int m = count[c];
+            count[c] = pos;
+            pos += m;
+            cptr[kp++] = pos;
+        }
+        for (int v = 3; v < n; ++v) order[count[colour[v]]++] = r0 + v;   // increasing id inside each class
+    }
+    cgoff[B] = kp;
+    return GMC_OK;
+}
+
+extern "C" int gmc_refine_local_f32(const gmc_batch *batch, const int32_t *order, const int32_t *cgoff,
+                                    const int32_t *cptr, int32_t cands, int8_t *assign, int32_t max_sweeps,
+                                    float *cut_all, int32_t *best_assign, float *best_cut, int32_t *best_idx,
+                                    int32_t *sweeps, gmc_stream_t stream) {
+    if (!batch || !order || !cgoff || !cptr || !assign || !cut_all || !best_assign || !best_cut || !best_idx)
+        return GMC_ERR_NULL;
+    if (batch->abi != GMC_VERSION) return GMC_ERR_ABI;
+    if (!batch->goff || !batch->rowptr || !batch->lcol) return GMC_ERR_NULL;
+    if (cands < 1 || max_sweeps < 0 || batch->B < 0) return GMC_ERR_SHAPE;
+    if (batch->B > 0 && (batch->n_max < 3 || batch->n_max > GMC_MAX_GRAPH_NODES)) return GMC_ERR_GRAPH_SIZE;
+    if (batch->B == 0) return GMC_OK;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    RefineArgs a{*batch, order, cgoff, cptr, cands, max_sweeps, reinterpret_cast<signed char *>(assign), cut_all, sweeps};
+    {
+        GmcProbeScope probe(GMC_K_REFINE, st);
+        hipLaunchKernelGGL(refine_local_kernel, dim3(cands, batch->B), dim3(256), (size_t)batch->n_max, st, a);
+        GMC_LAUNCH_CHECK();
+    }
+    gmc::PickArgs p{*batch, cands, reinterpret_cast<const signed char *>(assign), cut_all, best_assign, best_cut, best_idx};
+    hipLaunchKernelGGL(refine_pick_kernel, dim3(batch->B), dim3(256), 0, st, p);
+    GMC_LAUNCH_CHECK();
+    return GMC_OK;
+}

@@ -21,7 +21,8 @@ SYMBOLS = (
     "gmc_adam_f32", "gmc_workspace_bytes", "gmc_forward", "gmc_train_fwd_bwd",
     "gmc_backward_from_gp", "gmc_probe_begin", "gmc_probe_end", "gmc_set_fuse", "gmc_decode_sample_f32", "gmc_adam_devstep_f32", "gmc_ell_arrange_host", "gmc_ell_slots_for", "gmc_train_step_f32",
     "gmc_adam_devstep_model_f32", "gmc_w1_slab_floats", "gmc_w1_slab_f32", "gmc_host_device_pointer", "gmc_publish_f32",
-    "gmc_publish_adam_devstep_model_f32", "gmc_probe_flavours", "gmc_lds_flavours",
+    "gmc_publish_adam_devstep_model_f32", "gmc_probe_flavours", "gmc_lds_flavours", "gmc_refine_order_host",
+    "gmc_refine_local_f32",
 )
 
 MAX_GRAPH_NODES = 4096
@@ -90,6 +91,8 @@ def _declare(lib: C.CDLL) -> None:
     lib.gmc_w1_slab_f32.argtypes = [vp, i32, i32, vp, vp]
     lib.gmc_set_fuse.argtypes = [C.c_int]
     lib.gmc_decode_sample_f32.argtypes = [C.POINTER(GmcBatch), vp, vp, vp, i32, vp, vp, vp, vp, vp, vp]
+    lib.gmc_refine_order_host.argtypes = [i32, vp, vp, vp, vp, vp, vp, i32]
+    lib.gmc_refine_local_f32.argtypes = [C.POINTER(GmcBatch), vp, vp, vp, i32, vp, i32, vp, vp, vp, vp, vp, vp]
     lib.gmc_probe_begin.argtypes = [i32]
     lib.gmc_probe_end.argtypes = [vp, vp, i32]
     lib.gmc_probe_flavours.argtypes = [vp, i32]
@@ -173,7 +176,8 @@ def stream() -> int:
 
 
 KERNEL_TAGS = ("gather_w1", "agg_fwd", "head", "hidden_bwd", "colsum", "agg_bwd", "dw1", "dw1_fold",
-               "adam", "spmm_user", "dense_mfma", "bwd1_fused", "fwd1_fused", "decode", "finish")
+               "adam", "spmm_user", "dense_mfma", "bwd1_fused", "fwd1_fused", "decode", "finish",
+               "refine")
 
 
 FLAVOUR_KERNELS = {1: "fwd1_lds", 2: "bwd1_lds", 3: "bwd1_reg", 4: "spmm_lds", 5: "dw1_lds"}   # GMC_FLV_KERNEL

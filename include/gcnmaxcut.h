@@ -165,7 +165,8 @@ enum {
     GMC_K_FWD1_FUSED = 12, /* W1 gather + layer-1 aggregation (+ fused H@W2), one kernel */
     GMC_K_DECODE = 13,     /* post-processing sampler + cut count */
     GMC_K_FINISH = 14,     /* fold of the gradient partials (+ fused Adam) over the flat buffer */
-    GMC_K_COUNT = 15
+    GMC_K_REFINE = 15,     /* local search over decoded candidates + cut count (gmc_refine_local_f32) */
+    GMC_K_COUNT = 16
 };
 
 /* Timing probe for bench.py: between gmc_probe_begin and gmc_probe_end every kernel launch
@@ -346,6 +347,43 @@ int gmc_decode_sample_f32(const gmc_batch *batch, const float *P, const double *
                           const int64_t *uoff, int32_t iters, int8_t *assign_all, float *cut_all,
                           int32_t *best_assign, float *best_cut, int32_t *best_iter,
                           gmc_stream_t stream);
+
+/* ---- local search over decoded partitions (extension: no counterpart in the reference) ---------------------------
+ *
+ * Single-node-move refinement of candidate partitions, per graph of the batch (local ids 0..n-1, CSR rows of an
+ * undirected graph, weight 1 where vals is NULL):
+ *  - nodes 0, 1, 2 never move, whatever class they hold (override_fixed_nodes, TrainingNeural.py:87-94); the
+ *    movable nodes are 3..n-1;
+ *  - colouring: first-fit over the movable nodes in increasing id, a node taking the smallest colour no movable
+ *    neighbour of smaller id holds (self-loops and neighbours 0..2 ignored), so each colour class is an independent
+ *    set among movable nodes;
+ *  - one sweep visits the classes in increasing colour; every node v of a class sums in fp32, in the CSR order of its
+ *    row, the weights of its edges to neighbours of class 0, 1 and 2 as the classes stand at the start of that colour
+ *    step (self-loops skipped) into W0, W1, W2; with c = class(v) and k the class of the smallest W (lowest index on
+ *    ties), v moves to k iff W[k] < W[c] (a class byte outside 0..2 counts for no W, and such a movable node takes k).
+ *    The result equals a sequential sweep in (colour, id) order;
+ *  - sweeps run until one moves nothing, or max_sweeps have run (max_sweeps = 0: no move). */
+
+/* HOST routine (all pointers are host pointers): the colouring above for a batch of B graphs (goff [B+1], rowptr,
+ * lcol as in gmc_batch).  Writes order: per graph, the batch row ids of its movable nodes sorted by (colour, id)
+ * (R - 3B entries; room for R suffices); cgoff [B+1] and cptr: class k of graph g is
+ * order[cptr[cgoff[g]+k] .. cptr[cgoff[g]+k+1]), graph g has cgoff[g+1] - cgoff[g] - 1 classes (none for n = 3).
+ * cptr needs at most R + B entries: cptr_cap < R + B returns GMC_ERR_SHAPE before anything is written; a graph
+ * with < 3 or > GMC_MAX_GRAPH_NODES nodes GMC_ERR_GRAPH_SIZE. */
+int gmc_refine_order_host(int32_t B, const int32_t *goff, const int32_t *rowptr, const int32_t *lcol,
+                          int32_t *order, int32_t *cgoff, int32_t *cptr, int32_t cptr_cap);
+
+/* The local search above on `cands` candidates of every graph: assign [cands][R] int8 (device, in/out) holds them
+ * and receives the refined assignments; order / cgoff / cptr are gmc_refine_order_host's output in device memory.
+ * Each refined candidate is then scored and picked exactly as gmc_decode_sample_f32 scores and picks its samples:
+ * cut_all [B][cands], best_assign [R] int32 (the strictly best candidate, first wins), best_cut [B], best_idx [B].
+ * sweeps [B][cands] (NULL: not written): the sweeps run, the last of them the one that moved nothing when the
+ * candidate converged within max_sweeps.  Errors: a NULL pointer (sweeps aside) GMC_ERR_NULL, batch->abi
+ * GMC_ERR_ABI, cands < 1 or max_sweeps < 0 GMC_ERR_SHAPE, n_max outside 3..GMC_MAX_GRAPH_NODES GMC_ERR_GRAPH_SIZE;
+ * B == 0 launches nothing. */
+int gmc_refine_local_f32(const gmc_batch *batch, const int32_t *order, const int32_t *cgoff, const int32_t *cptr,
+                         int32_t cands, int8_t *assign, int32_t max_sweeps, float *cut_all, int32_t *best_assign,
+                         float *best_cut, int32_t *best_idx, int32_t *sweeps, gmc_stream_t stream);
 
 #ifdef __cplusplus
 }
