@@ -2,8 +2,11 @@
 """Headline benchmark: GCN max-cut training epochs/sec + SpMM achieved HBM GB/s on
 n=1000 d=7 regular graphs (BASELINE.json), one process per GPU.
 
-    python bench.py --gpus N --steps K --warmup W            (N > 1: spawns the N ranks itself)
+    python bench.py --gpus N --steps K --warmup W [--full]   (N > 1: spawns the N ranks itself)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K steps, writes --dump-outputs and prints the headline line.  --full adds
+every region below that is not the headline; the headline's timed steps compute and time the same in both.
 
 A *step* is one pass of the hot path (forward, cut loss, backward, RCCL gradient all-reduce
 when N > 1, fused Adam) over this rank's batch of graphs; inputs are resident in HBM before
@@ -11,10 +14,11 @@ the timed region.  Workload at N=1: config[3] of BASELINE.json on one GPU - 160 
 n=1000 d=7 graphs (R = 160,000 rows, 646 MB algorithmic bytes per F=500 SpMM, beyond the
 256 MiB Infinity Cache).  `value` counts epochs of 160 graphs per second.  --scaling weak
 (default): every rank holds its own 160 graphs (N*160 graphs per step); --scaling strong: the 160
-graphs are split over the ranks (160/N each - BASELINE config[3] literally at N=8).  With N > 1 the
-line of a weak run also carries `strong_scaling`, the same job re-timed on the strong split.
+graphs are split over the ranks (160/N each - BASELINE config[3] literally at N=8).  With --full and N > 1 the
+line of a weak run also carries `strong_scaling`, the same job re-timed on the strong split, and
+`allreduce_ms_per_step`.
 
-The JSON line also carries
+With --full the JSON line also carries
   roofline      - the DOMINANT KERNEL OF THE TIMED STEP (the fused backward or forward of layer 1): the bytes it must
                   move per launch (compulsory = algorithmic: H once + tables + partials) / its mean launch duration,
                   HIP events recorded by the library on the launch stream over K eager steps; `traffic` = PMC bytes
@@ -39,11 +43,15 @@ The JSON line also carries
                   variant B = oracle/gcn_oracle.c (scalar C: CSR SpMM, fused
                   argmax / loss), 1 thread.  Both GPU/CPU ratios are printed (neither is a quality claim).
 
-Order of the regions inside one run: graph generation (worker processes, before the GPU is touched), `sequential`,
+Order of the regions inside a --full run: graph generation (worker processes, before the GPU is touched), `sequential`,
 the per-kernel probe (150 untimed + K eager steps with HIP events around every kernel), the one-kernel-per-operation
-leg + SpMM batch sweep, the other workloads, the data-parallel shard profile, and LAST the headline: W untimed warmup
-steps, then exactly K timed steps between barrier + synchronize pairs.  A fresh process needs ~30 steps to reach the
-clocks the chip sustains; with the headline last its timed steps are sustained-clock steps at any K / W.
+leg (10 untimed + K probed steps) + SpMM batch sweep, the other workloads, the data-parallel shard profile, and LAST
+the headline: W untimed warmup steps, then exactly K timed steps between barrier + synchronize pairs.  A plain run
+generates the headline's graphs only and takes the probe's and the one-kernel-per-operation leg's steps without HIP
+events: they train the model the timed steps start from.  In place of the profile it pauses as long as a --full run
+idles before its timed steps (PAUSE_BEFORE_HEADLINE_S): after such a pause the chip runs ~100 steps slower than
+sustained, so a short run's figure depends on it.  After the timed steps, --full adds the strong split, the
+all-reduce time, the CPU baselines and the parity gate.
 
 --dump-outputs DIR: after the timed steps, rank 0 writes what the last of them computed as DIR/<name>.npy (float32, the
 loss float64; see `step_outputs`).  Inputs and initial weights are seeded and the kernels sum in a fixed order, so runs
@@ -71,6 +79,7 @@ EPOCH_GRAPHS = 160  # BASELINE.json configs[3]
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: 8 TB/s HBM3E
 LDS_PEAK_GBS = 256 * 256 * 2.4  # MI355X_MICROARCH.md, LDS: 256 B/clk/CU x 256 CUs x 2.4 GHz max clock = 157,286 GB/s
 DUMP_LIMIT_BYTES = 64 << 20  # --dump-outputs: at most this much in all
+PAUSE_BEFORE_HEADLINE_S = 0.2  # plain run: the idle time a --full run has before its timed steps
 
 
 def parse():
@@ -88,13 +97,18 @@ def parse():
     ap.add_argument("--mode", choices=["batched", "sequential"], default="batched",
                     help="batched: one Adam step per rank-batch (DP schedule); sequential: the "
                          "reference's one Adam step per graph (N=1 only)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every region beyond the headline: reference schedule, per-kernel HIP events and "
+                         "rooflines, SpMM batch sweep, other workloads, data-parallel profile, strong scaling, "
+                         "all-reduce time, CPU baselines and parity gate")
     ap.add_argument("--cpu-seconds", type=float, default=10.0, help="budget of EACH CPU baseline sample (three are timed)")
-    ap.add_argument("--no-sequential", action="store_true", help="skip the reference-schedule region")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-probe", action="store_true", help="do not record per-kernel HIP events")
-    ap.add_argument("--no-other-workloads", action="store_true", help="skip the d=8 / d=12 / G(n,p) steps")
-    ap.add_argument("--no-dp-profile", action="store_true", help="skip the single-rank data-parallel shard profile")
-    ap.add_argument("--no-spmm-sweep", action="store_true", help="skip the SpMM batch-size sweep")
+    ap.add_argument("--no-sequential", action="store_true", help="skip the reference-schedule region (--full)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="skip the CPU baselines (--full)")
+    ap.add_argument("--no-probe", action="store_true",
+                    help="skip the probe and one-kernel-per-operation regions, their steps included")
+    ap.add_argument("--no-other-workloads", action="store_true", help="skip the d=8 / d=12 / G(n,p) steps (--full)")
+    ap.add_argument("--no-dp-profile", action="store_true", help="skip the single-rank data-parallel shard profile (--full)")
+    ap.add_argument("--no-spmm-sweep", action="store_true", help="skip the SpMM batch-size sweep (--full)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last of them computed (loss, per-graph losses, "
                          "probabilities, partition, parameters and gradient) as DIR/<name>.npy (rank 0)")
@@ -237,7 +251,7 @@ def main():
     gpg, n, d = args.graphs_per_gpu, args.nodes, args.degree
 
     # ---- synthetic inputs, generated on worker processes BEFORE this process touches the GPU
-    extras_on = (not dp and args.mode == "batched" and not args.no_other_workloads and not args.no_probe)
+    extras_on = (args.full and not dp and args.mode == "batched" and not args.no_other_workloads and not args.no_probe)
     seeds = [3000 + rank * gpg + i for i in range(gpg)]
     specs = [("reg", n, d, sd) for sd in seeds]
     extra_defs = []
@@ -331,14 +345,21 @@ def main():
             dist.all_reduce(dt, op=dist.ReduceOp.MAX)
         return float(dt.item()), loss
 
-    def probed(tr, data, untimed, steps):
+    def probed(tr, data, untimed, steps, record=True):
         """Per-kernel mean milliseconds over `steps` eager steps (HIP events recorded by the library on the launch
-        stream around every kernel; a graph replay cannot carry them), after `untimed` eager steps."""
+        stream around every kernel; a graph replay cannot carry them), after `untimed` eager steps.  `record=False`
+        takes the same steps without the events and returns nothing."""
         was = tr.allow_graph
         tr.allow_graph = False
         for _ in range(untimed):
             tr.epoch(data)
         sync()
+        if not record:
+            for _ in range(steps):
+                tr.epoch(data)
+            sync()
+            tr.allow_graph = was
+            return None
         te = time.perf_counter()
         with pkg.hip.Probe(16 * max(1, len(tr._batches)) * steps) as probe:
             for _ in range(steps):
@@ -357,7 +378,7 @@ def main():
     # the reference's own schedule on the same graphs: one Adam step per graph (TrainingNeural.py:371-386),
     # one hipGraph per epoch - what `cpu_baseline` (same schedule, host cores) is to be compared with
     sequential = None
-    if not dp and args.mode == "batched" and not args.no_sequential:
+    if args.full and not dp and args.mode == "batched" and not args.no_sequential:
         net_s, embed_s, opt_s = fresh_model()
         tr_q = T.FusedTrainer(net_s, opt_s, cfg, graphs_per_step=1, local_shard=True)
         k_seq = max(3, args.steps // 10)
@@ -370,10 +391,15 @@ def main():
         note("reference-schedule region done")
 
     # per-kernel means of the default (fused) step: 150 untimed eager steps (kernel set-up; ~40 ms of full load bring
-    # the chip to its sustained clocks after the light reference-schedule region), then K probed ones -> `roofline`
+    # the chip to its sustained clocks after the light reference-schedule region), then K probed ones -> `roofline`.
+    # These steps and those of the next region train the model the timed steps start from: a run without --full takes
+    # them too, without the HIP events, so that its timed steps compute what those of a --full run compute.
     kmean, eager_ms = {}, None
     if not args.no_probe:
-        kmean, _by, eager_ms = probed(trainer, dataset, 150, args.steps)
+        if args.full:
+            kmean, _by, eager_ms = probed(trainer, dataset, 150, args.steps)
+        else:
+            probed(trainer, dataset, 150, args.steps, record=False)
 
     # third region (EVERY rank runs it: each step holds a collective when N > 1): the same step as
     # one kernel per operation -> timings of the stand-alone SpMM kernel
@@ -381,7 +407,10 @@ def main():
     lib = pkg.hip.load()
     if args.mode == "batched" and not args.no_probe:
         prev = lib.gmc_set_fuse(0)
-        _m, k2, _w = probed(trainer, dataset, 10, args.steps)
+        if args.full:
+            _m, k2, _w = probed(trainer, dataset, 10, args.steps)
+        else:
+            probed(trainer, dataset, 10, args.steps, record=False)
         lib.gmc_set_fuse(prev)
         spmm = [ms for tag in ("agg_fwd", "agg_bwd") for ms in k2.get(tag, [])]
         note("probe + one-kernel-per-operation regions done")
@@ -389,7 +418,7 @@ def main():
     # SpMM at several batch sizes ("config 3 must be reported at several batch sizes"):
     # B = 1024 is the 160 graphs repeated (R = 1,024,000 rows, 4.1 GB per [R, F] operand: nothing can be cache-served)
     by_batch = None
-    if not dp and args.mode == "batched" and not args.no_probe and not args.no_spmm_sweep and gpg >= 20:
+    if args.full and not dp and args.mode == "batched" and not args.no_probe and not args.no_spmm_sweep and gpg >= 20:
         by_batch = {}
         keys = list(dataset)
         prev = lib.gmc_set_fuse(0)
@@ -452,7 +481,8 @@ def main():
 
     # data-parallel step sequence at the strong split's shard sizes, ONE rank over RCCL (N = 1 runs only)
     dp_profile = None
-    if not dp and args.mode == "batched" and not args.no_dp_profile and not args.no_probe:
+    profile_on = not dp and args.mode == "batched" and not args.no_dp_profile and not args.no_probe
+    if profile_on and args.full:
         try:   # (an extra: whatever goes wrong in it must not cost the run its headline)
             dp_profile = dp_shard_profile(args, pkg, T, cfg, dataset, fresh_model, timed, probed)
         except Exception as e:   # noqa: BLE001
@@ -460,6 +490,12 @@ def main():
             if dist.is_initialized():
                 dist.destroy_process_group()
         note("data-parallel shard profile done")
+    elif profile_on:
+        # A --full run's timed steps start ~0.2 s after the profile's last launch (its RCCL group is torn down in
+        # between), and after such a pause the chip runs the next ~100 steps slower than sustained (DESIGN.md section
+        # 6).  A plain run pauses as long in its place: --steps and --warmup time the steps they always have.
+        sync()
+        time.sleep(PAUSE_BEFORE_HEADLINE_S)
 
     trainer.allow_graph = True
 
@@ -474,7 +510,7 @@ def main():
 
     # N > 1, weak run: the same job on the strong split (160 graphs in total, 160 / N per rank)
     strong = None
-    if dp and args.scaling == "weak" and args.mode == "batched":
+    if args.full and dp and args.scaling == "weak" and args.mode == "batched":
         per = min(len(dataset), max(1, EPOCH_GRAPHS // world))
         sub = {k: dataset[k] for k in list(dataset)[:per]}
         tr_s = T.FusedTrainer(net, opt, cfg, graphs_per_step=per, local_shard=True)
@@ -484,7 +520,7 @@ def main():
 
     # per-step collective time (events on the launch stream around the eager all-reduce), N > 1
     allreduce_ms = None
-    if dp:
+    if args.full and dp:
         allreduce_ms = allreduce_time_ms(eng, sync)
 
     if rank != 0:
@@ -522,10 +558,11 @@ def main():
         "host_enqueue_us_per_step": 1e6 * trainer.last_enqueue_s,
         "kernels_ms": {k: round(v, 5) for k, v in sorted(kmean.items())},
         "graph_generation_s": round(t_gen, 2),
-        "steady_state_note": "the first ~30 steps of a fresh process run ~9 % slower (clock ramp); the timed steps are the "
-                             "LAST region of this run (after the reference-schedule, probe, sweep and profile regions), "
-                             "so they are sustained-clock steps at any --steps/--warmup; DESIGN.md quotes the defaults "
-                             "--steps 200 --warmup 30",
+        "steady_state_note": "the first ~30 steps of a fresh process run ~9 % slower (clock ramp), and ~100 steps after "
+                             "an idle pause up to ~45 % slower; the timed steps follow the probe and "
+                             "one-kernel-per-operation steps and a 0.2 s pause (--full: the reference-schedule, sweep, "
+                             "other-workload and profile regions, whose RCCL teardown is the pause), so short runs "
+                             "time clocks below the sustained ones; DESIGN.md quotes the defaults --steps 200 --warmup 30",
     }
     if allreduce_ms is not None:
         out["allreduce_ms_per_step"] = allreduce_ms
@@ -555,7 +592,7 @@ def main():
     if dp_profile is not None:
         out["dp_shard_profile"] = dp_profile
 
-    if not dp and not args.no_cpu_baseline:
+    if args.full and not dp and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(args, graphs, terms, net)
         if sequential is not None:   # same schedule on both sides: GPU reference-schedule rate / CPU rate (both variants)
             cb = out["cpu_baseline"]

@@ -966,11 +966,13 @@ def test_dropout_training_path(pkg):
 
 
 def test_bench_line_contract(pkg):
-    """bench.py prints ONE JSON line with the keys the driver reads (small run: 8 graphs per GPU)."""
+    """bench.py --full prints ONE JSON line with the keys the driver reads and every region beyond the headline
+    (small run: 8 graphs per GPU)."""
     import json, subprocess, sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
-                          "--graphs-per-gpu", "8", "--cpu-seconds", "1"], capture_output=True, text=True, timeout=600)
+                          "--graphs-per-gpu", "8", "--cpu-seconds", "1", "--full"], capture_output=True, text=True,
+                         timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.strip().splitlines() if l.startswith("{")]
     assert len(lines) == 1
@@ -1021,16 +1023,47 @@ def test_bench_line_contract(pkg):
     assert rec["faster"] in ("eager", "graphs") and rec["eager"]["host_enqueue_us"] > 0
 
 
+def test_bench_plain_run_is_the_headline_of_a_full_run(pkg, tmp_path):
+    """bench.py without --full runs only what its headline needs: the line has the headline's keys and none of the
+    regions --full adds.  Its timed steps start from the model the probe and one-kernel-per-operation steps leave, as
+    those of a --full run do, so the last timed step of either computes the same arrays bit for bit."""
+    import json, subprocess, sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
+    lines, dumps = {}, {}
+    for tag, extra in (("plain", []), ("full", ["--full", "--cpu-seconds", "0.2"])):
+        d = tmp_path / tag
+        out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup",
+                              "1", "--graphs-per-gpu", "8", "--dump-outputs", str(d)] + extra,
+                             capture_output=True, text=True, timeout=600, env=env)
+        assert out.returncode == 0, out.stderr[-3000:]
+        (line,) = [l for l in out.stdout.strip().splitlines() if l.startswith("{")]
+        lines[tag] = json.loads(line)
+        dumps[tag] = {f[:-4]: np.load(d / f) for f in sorted(os.listdir(d))}
+    p, f = lines["plain"], lines["full"]
+    for k in ("metric", "unit", "n_gpus", "steps", "warmup", "higher_is_better", "scaling", "vs_baseline", "dtype", "data",
+              "config", "launch", "last_loss"):
+        assert p[k] == f[k], k
+    assert p["value"] > 0 and abs(p["ms_per_step"] * p["value"] * 160 / (1e3 * 8) - 1) < 1e-6
+    for k in ("sequential", "cpu_baseline", "parity", "other_workloads", "dp_shard_profile", "kernels_ms_unfused"):
+        assert k not in p and k in f, k
+    assert p["roofline"] is None and p["roofline_spmm"] is None and p["kernels_ms"] == {}
+    assert p["ms_per_step_eager_probed"] is None
+    assert set(dumps["plain"]) == set(dumps["full"]) and "param.conv1.weight" in dumps["plain"]
+    for k, v in dumps["plain"].items():
+        assert np.array_equal(v, dumps["full"][k]), k
+
+
 def test_bench_two_rank_rehearsal_on_one_gpu(pkg):
     """`bench.py --gpus 2` launches its own two ranks (children, before any GPU call); on a one-GPU box
     GCN_MAXCUT_BENCH_REHEARSE=1 puts both on device 0 over gloo: the N > 1 control flow end to end -
-    sharded datasets, replica sync, hipGraphs around the eager all-reduce, both scalings in one line."""
+    sharded datasets, replica sync, hipGraphs around the eager all-reduce, both scalings in one line (--full)."""
     import json, subprocess, sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, GCN_MAXCUT_BENCH_REHEARSE="1")
     env.pop("WORLD_SIZE", None)
     out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-                          "--graphs-per-gpu", "6"], capture_output=True, text=True, timeout=900, env=env)
+                          "--graphs-per-gpu", "6", "--full"], capture_output=True, text=True, timeout=900, env=env)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.strip().splitlines() if l.startswith("{")]
     assert len(lines) == 1
@@ -1047,14 +1080,15 @@ def test_bench_single_rank_over_rccl(pkg):
     """RCCL itself on the one GPU a test box has: GCN_MAXCUT_DP_SINGLE_RANK=1 makes a world of ONE rank run the
     data-parallel step sequence over backend "nccl" - communicator set-up, replica broadcast, the [gradient | loss]
     all-reduce on the launch stream between eager launches (the default; GCN_MAXCUT_DP_GRAPHS=1 replays hipGraphs there).
-    The loss must be the one the single-GPU fused step reaches after the same number of steps."""
+    The loss must be the one the single-GPU fused step reaches after the same number of steps (--full: the line
+    carries the all-reduce time)."""
     import json, subprocess, sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     base = dict(os.environ)
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT"):
         base.pop(k, None)
     args = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "2",
-            "--graphs-per-gpu", "6", "--no-cpu-baseline", "--no-sequential", "--no-probe"]
+            "--graphs-per-gpu", "6", "--no-cpu-baseline", "--no-sequential", "--no-probe", "--full"]
     lines = {}
     for tag, env in (("rccl", dict(base, GCN_MAXCUT_DP_SINGLE_RANK="1")), ("single", base)):
         out = subprocess.run(args, capture_output=True, text=True, timeout=400, env=env)
