@@ -6,7 +6,7 @@ import pytest
 import torch
 
 from oracle import c_oracle as CO
-from tests import util
+from tests import stepcheck, util
 
 pytestmark = pytest.mark.gpu
 
@@ -17,21 +17,13 @@ def pkg(built):
     return built
 
 
-def model(hidden, n_nodes=1000):
-    from gcn_max_cut_amd.Training import TrainingNeural as T
-    cfg = T.TrainingConfig(n_nodes=n_nodes, hidden_dim=hidden)
-    torch.manual_seed(0)
-    net, embed, opt = T.setup_model_and_optimizer(cfg)
-    return T, cfg, net, embed, opt, util.np_params(net.state_dict())
-
-
 @pytest.mark.parametrize("hidden", [250, 25, 7, 1, 498])
 def test_step_at_hidden_dims_that_are_not_multiples_of_four(pkg, hidden):
-    T, cfg, net, embed, opt, params = model(hidden)
+    T, cfg, net, embed, opt, params = util.model(hidden)
     assert params["conv1.weight"].shape == (1000, hidden) and params["conv2.weight"].shape == (hidden, 3)
     specs = [(1000, 7, 401), (300, 8, 402), (120, 12, 403)] if hidden >= 25 else [(200, 7, 404), (90, 6, 405)]
     ds = util.product_dataset(specs)
-    eng, tags = util.check_step_against_oracle(pkg, net, ds, params)
+    eng, _got, _ = stepcheck.check_step_against_oracle(pkg, net, ds, params)
     assert eng.F == hidden and eng.Fp % 4 == 0 and 0 <= eng.Fp - hidden < 4
     sd = net.state_dict()
     assert tuple(sd["conv1.weight"].shape) == (1000, hidden) and tuple(sd["conv1.bias"].shape) == (hidden,)

@@ -10,11 +10,11 @@ import torch
 
 from oracle import c_oracle as CO
 from oracle import ref_dense as R
-from tests import util
+from tests import stepcheck, util
 
 pytestmark = pytest.mark.gpu
 
-PROB_TOL = 1e-4
+PROB_TOL = stepcheck.PROB_TOL
 
 
 @pytest.fixture(scope="module")
@@ -111,14 +111,6 @@ def test_mfma_dense_integer_exact(pkg):
     assert np.array_equal(Z.cpu().numpy(), 2 * (H @ W2))
 
 
-def model_and_params(pkg, hidden, seed=0):
-    from gcn_max_cut_amd.Training import TrainingNeural as T
-    cfg = T.TrainingConfig(n_nodes=1000, hidden_dim=hidden)
-    torch.manual_seed(seed)
-    net, embed, opt = T.setup_model_and_optimizer(cfg)
-    return T, cfg, net, embed, opt, util.np_params(net.state_dict())
-
-
 SPECS_SMALL = [(100, 7, 1000), (50, 6, 1001), (64, 8, 1002), (30, 5, 1003)]
 
 
@@ -127,7 +119,7 @@ SPECS_SMALL = [(100, 7, 1000), (50, 6, 1001), (64, 8, 1002), (30, 5, 1003)]
                                           # degrees 9..16: the 16-slot neighbour table; 20: no table (row kernels)
                                           (64, [(120, 12, 11), (90, 10, 12), (60, 9, 13)]), (32, [(80, 20, 14)])])
 def test_forward_probabilities_and_partitions(pkg, hidden, specs):
-    T, cfg, net, *_rest, params = model_and_params(pkg, hidden)
+    T, cfg, net, *_rest, params = util.model(hidden)
     ds = util.product_dataset(specs)
     net.eval()
     for (g, a_pad, nx_g, _t) in ds.values():
@@ -158,16 +150,16 @@ def test_batched_forward_is_bitwise_the_per_graph_forward(pkg):
     (bitwise), and are the single-graph forward exactly when the launch shape class is the same
     (same LDS slice width and slices per group); across classes the fused H@W2 partials are folded in
     a different association: equal to rounding."""
-    T, cfg, net, *_ = model_and_params(pkg, 500)
+    T, cfg, net, *_ = util.model(500)
     eng = net.engine()
     big = [(1000, 7, 3000 + i) for i in range(9)]
     items = list(util.product_dataset(big).values())
-    batch = pkg.GraphBatch([it[0] for it in items], None, eng.device)
+    batch = util.batch_of(pkg, eng, items, weighted=False)
     P, S, loss = [t.clone() for t in eng.forward(batch, 1.0, want_loss=True)]
     # same graphs, reversed order, two of them swapped for others: per-graph results unchanged
     other = list(util.product_dataset([(1000, 7, 77), (1000, 7, 78)]).values())
     perm = items[::-1][:7] + other
-    batch2 = pkg.GraphBatch([it[0] for it in perm], None, eng.device)
+    batch2 = util.batch_of(pkg, eng, perm, weighted=False)
     P2, S2, loss2 = eng.forward(batch2, 1.0, want_loss=True)
     for j in range(7):
         g = len(items) - 1 - j
@@ -181,15 +173,15 @@ def test_batched_forward_is_bitwise_the_per_graph_forward(pkg):
         assert float((batch.split(P)[g] - Pg).abs().max()) < 1e-6
     # same class (4 slices per group from 16 graphs of this size on): batch of 40 == batch of 20
     many = list(util.product_dataset([(1000, 7, 5000 + i) for i in range(40)]).values())
-    b40 = pkg.GraphBatch([it[0] for it in many], None, eng.device)
-    b20 = pkg.GraphBatch([it[0] for it in many[10:30]], None, eng.device)
+    b40 = util.batch_of(pkg, eng, many, weighted=False)
+    b20 = util.batch_of(pkg, eng, many[10:30], weighted=False)
     P40 = eng.forward(b40, 1.0)[0].clone()
     P20 = eng.forward(b20, 1.0)[0]
     for j in range(20):
         assert torch.equal(b40.split(P40)[10 + j], b20.split(P20)[j])
     mixed = [(1000, 7, 3000), (500, 6, 1), (300, 8, 2), (64, 5, 3)]
     items = list(util.product_dataset(mixed).values())
-    batch = pkg.GraphBatch([it[0] for it in items], None, eng.device)
+    batch = util.batch_of(pkg, eng, items, weighted=False)
     P, S, loss = eng.forward(batch, 1.0, want_loss=True)
     for g, it in enumerate(items):
         single = pkg.GraphBatch([it[0]], None, eng.device)
@@ -209,12 +201,12 @@ def test_graphs_larger_than_the_lds_tiles_use_the_row_kernels(pkg):
     ds = util.product_dataset(specs, max_nodes=1600)
     eng = net.engine()
     items = list(ds.values())
-    batch = pkg.GraphBatch([it[0] for it in items], None, eng.device)
+    batch = util.batch_of(pkg, eng, items, weighted=False)
     P, S, loss = eng.train_fwd_bwd(batch, 1.0)
     ct = CO.CTrainer(params)
     ref_loss = ct.step(util.csrs_of(ds))
     assert np.array_equal(loss.cpu().numpy(), ref_loss)
-    ref = flat_ref_grads(ct)
+    ref = stepcheck.flat_ref_grads(ct)
     for k, g in eng.views(eng.grad).items():
         g, r = g.cpu().numpy().ravel(), ref[k]
         assert np.abs(g - r).max() <= 1e-4 * max(1.0, np.abs(r).max()), k
@@ -230,11 +222,11 @@ def test_persistent_forward_ranges_cross_graphs(pkg, monkeypatch):
     """The fused forward hands every workgroup a contiguous range of (graph, slice group) items.
     With 4 'CUs' a range spans several graphs of different sizes: the result must be bitwise the
     one-item-per-workgroup result (and within tolerance of the oracle, checked elsewhere)."""
-    T, cfg, net, *_ = model_and_params(pkg, 500)
+    T, cfg, net, *_ = util.model(500)
     eng = net.engine()
     specs = [(300, 7, 41), (120, 6, 42), (1000, 7, 43), (64, 5, 44), (500, 8, 45), (250, 7, 46), (90, 6, 47)]
     items = list(util.product_dataset(specs).values())
-    batch = pkg.GraphBatch([it[0] for it in items], None, eng.device)
+    batch = util.batch_of(pkg, eng, items, weighted=False)
     lib = pkg.hip.load()
     try:
         lib.gmc_debug_set_device_cus(100000)   # one item per workgroup
@@ -253,11 +245,11 @@ def test_persistent_forward_ranges_cross_graphs(pkg, monkeypatch):
 
 
 def test_loss_equals_minus_cut_of_argmax_partition(pkg):
-    T, cfg, net, *_ = model_and_params(pkg, 64)
+    T, cfg, net, *_ = util.model(64)
     ds = util.product_dataset(SPECS_SMALL + [(500, 7, 5)])
     eng = net.engine()
     items = list(ds.values())
-    batch = pkg.GraphBatch([it[0] for it in items], None, eng.device)
+    batch = util.batch_of(pkg, eng, items, weighted=False)
     P, S, loss = eng.forward(batch, 1.0, want_loss=True)
     for g, it in enumerate(items):
         part = batch.split(S)[g].cpu().numpy()
@@ -274,11 +266,11 @@ def test_full_size_batch_properties(pkg):
     need no oracle run: rows of P sum to 1, terminals keep their classes, loss == -cut(argmax) exactly
     (integers), node relabelling permutes P (to rounding), rows of dW1 beyond n stay zero, and the
     step is bitwise reproducible."""
-    T, cfg, net, *_ = model_and_params(pkg, 500)
+    T, cfg, net, *_ = util.model(500)
     eng = net.engine()
     B = 160
     items = list(util.product_dataset([(1000, 7, 7000 + i) for i in range(B - 1)] + [(600, 7, 7999)]).values())
-    batch = pkg.GraphBatch([it[0] for it in items], None, eng.device)
+    batch = util.batch_of(pkg, eng, items, weighted=False)
     P, S, loss = [t.clone() for t in eng.train_fwd_bwd(batch, 1.0)]
     g1 = eng.grad.clone()
     assert float((P.sum(1) - 1).abs().max()) < 1e-6
@@ -292,7 +284,7 @@ def test_full_size_batch_properties(pkg):
             assert float(lh[g]) == -float(R.cut_value(part.tolist(), it[2]))
         off += n
     assert float(lh.sum()) == float(sum(lh.tolist())) and np.all(lh == np.round(lh))
-    eng._ws.fill_(255)
+    util.poison(eng, batch, grad=False)
     P2, S2, loss2 = eng.train_fwd_bwd(batch, 1.0)
     assert torch.equal(P, P2) and torch.equal(S, S2) and torch.equal(loss, loss2) and torch.equal(g1, eng.grad)
     # relabel the non-terminal nodes of one graph: probabilities follow the permutation
@@ -319,11 +311,6 @@ def test_full_size_batch_properties(pkg):
     assert float((Pb[inv] - Pa).abs().max()) > 1e-5   # (and without it the outputs genuinely differ)
 
 
-def flat_ref_grads(ct):
-    o = np.cumsum([0, ct.N * ct.F, ct.F, ct.F * ct.K, ct.K])
-    return {k: ct.grad[o[i]:o[i + 1]] for i, k in enumerate(("conv1.weight", "conv1.bias", "conv2.weight", "conv2.bias"))}
-
-
 @pytest.mark.parametrize("hidden,specs", [(16, SPECS_SMALL), (500, [(500, 7, 1000), (500, 6, 1001)]),
                                           (500, [(1000, 7, 2000 + i) for i in range(9)]),
                                           # the reference's default dataset name is ..._d8_12_...: degrees up to 12
@@ -333,21 +320,19 @@ def flat_ref_grads(ct):
                                           # 8 rows per thread (see test_one_kernel_per_operation_sequence_matches_oracle)
                                           (128, [(530, 7, 31), (520, 6, 32)]), (256, [(270, 7, 33), (262, 8, 34)])])
 def test_step_gradients_match_oracle(pkg, hidden, specs):
-    T, cfg, net, embed, opt, params = model_and_params(pkg, hidden)
+    T, cfg, net, embed, opt, params = util.model(hidden)
     ds = util.product_dataset(specs)
-    eng, _tags = util.check_step_against_oracle(pkg, net, ds, params)
+    eng, _got, _ = stepcheck.check_step_against_oracle(pkg, net, ds, params)
     # rows of dW1 that no graph reaches are exactly zero
     nmax = max(s[0] for s in specs)
     assert float(eng.views(eng.grad)["conv1.weight"][nmax:].abs().max() if nmax < 1000 else 0.0) == 0.0
 
 
 def test_step_gradients_match_torch_autograd_oracle(pkg):
-    T, cfg, net, embed, opt, params = model_and_params(pkg, 16)
+    T, cfg, net, embed, opt, params = util.model(16)
     ds = util.product_dataset(SPECS_SMALL)
     eng = net.engine()
-    items = list(ds.values())
-    batch = pkg.GraphBatch([it[0] for it in items], None, eng.device)
-    eng.train_fwd_bwd(batch, 1.0)
+    eng.train_fwd_bwd(util.batch_of(pkg, eng, ds, weighted=False), 1.0)
     ods = util.oracle_dataset(SPECS_SMALL)
     tp = {k: torch.from_numpy(v) for k, v in params.items()}
     _, grads, _ = R.loss_and_grads(tp, list(ods.values()))
@@ -361,25 +346,18 @@ def test_step_gradients_match_torch_autograd_oracle(pkg):
 def test_weighted_edges_and_loss_scale(pkg, fuse, specs):
     """Non-unit edge weights (the `vals` / `ell_vals` variants of every kernel), C != 1, in the fused
     default and in the one-kernel-per-operation sequence."""
-    T, cfg, net, embed, opt, params = model_and_params(pkg, 32)
+    T, cfg, net, embed, opt, params = util.model(32)
     from gcn_max_cut_amd.DataGenerator import graphExtender as GE
     graphs, terms = util.weighted_copy(specs)
     ds = GE.process_graphs_from_folder(graphs, terms, 1000)
     eng = net.engine()
-    items = list(ds.values())
-    vals = [it[0].edge_values(it[1]) for it in items]
-    assert all(v is not None for v in vals)
-    batch = pkg.GraphBatch([it[0] for it in items], vals, eng.device)
-    lib = pkg.hip.load()
-    prev = lib.gmc_set_fuse(fuse)
-    try:
-        P, S, loss = eng.train_fwd_bwd(batch, 2.5)
-    finally:
-        lib.gmc_set_fuse(prev)
+    assert all(it[0].edge_values(it[1]) is not None for it in ds.values())
+    with util.fused(pkg, fuse):
+        P, S, loss = eng.train_fwd_bwd(util.batch_of(pkg, eng, ds), 2.5)
     ct = CO.CTrainer(params, Cc=2.5)
     ref_loss = ct.step(util.csrs_of(ds))
     np.testing.assert_allclose(loss.cpu().numpy(), ref_loss, rtol=1e-6)
-    ref = flat_ref_grads(ct)
+    ref = stepcheck.flat_ref_grads(ct)
     for k, g in eng.views(eng.grad).items():
         r = ref[k]
         assert np.abs(g.cpu().numpy().ravel() - r).max() <= 1e-4 * max(1.0, np.abs(r).max()), k
@@ -412,7 +390,7 @@ def test_sequential_training_follows_oracle(pkg, specs):
     """Three epochs of the reference schedule (one Adam step per graph), replayed as a hipGraph;
     the second dataset mixes a degree-20 graph (row kernels, stand-alone Adam inside the captured
     step) with 8- and 16-slot ones."""
-    T, cfg, net, embed, opt, params = model_and_params(pkg, 16)
+    T, cfg, net, embed, opt, params = util.model(16)
     ds = util.product_dataset(specs)
     ct = CO.CTrainer(params, lr=cfg.learning_rate)
     csrs = util.csrs_of(ds)
@@ -444,7 +422,7 @@ def test_data_parallel_step_sequence_equals_the_fused_step(pkg):
     ds = util.product_dataset(specs)
     runs = []
     for variant in ("fused", "dp-sequence"):
-        T, cfg, net, embed, opt, params = model_and_params(pkg, 64, seed=5)
+        T, cfg, net, embed, opt, params = util.model(64, seed=5)
         eng = net.engine()
         tr = T.FusedTrainer(net, opt, cfg, graphs_per_step=2,
                             engine=eng if variant == "fused" else WithoutFusedStep(eng))
@@ -459,7 +437,7 @@ def test_data_parallel_step_sequence_equals_the_fused_step(pkg):
 
 def test_autograd_path_matches_fused_step(pkg):
     """net(g, A) -> reference-style helper chain -> .backward() uses the HIP backward."""
-    T, cfg, net, embed, opt, params = model_and_params(pkg, 32)
+    T, cfg, net, embed, opt, params = util.model(32)
     ds = util.product_dataset([(100, 7, 31)])
     (g, a_pad, nx_g, _t), = ds.values()
     net.train()
@@ -505,48 +483,12 @@ def test_one_kernel_per_operation_sequence_matches_oracle(pkg, hidden, specs):
     """gmc_set_fuse(0): the stand-alone LDS SpMM / hidden-backward / dW1 kernels (the sequence whose
     SpMM bench.py's `roofline` times) against the C oracle, same bar as the fused default.
     (The relu-kink case (900, 7, 6) has its own test below.)"""
-    T, cfg, net, embed, opt, params = model_and_params(pkg, hidden)
+    T, cfg, net, embed, opt, params = util.model(hidden)
     ds = util.product_dataset(specs)
-    eng = net.engine()
-    items = list(ds.values())
-    batch = pkg.GraphBatch([it[0] for it in items], None, eng.device)
-    lib = pkg.hip.load()
-    prev = lib.gmc_set_fuse(0)
-    try:
-        eng.train_fwd_bwd(batch, 1.0)
-        eng._ws.fill_(255)
-        eng.grad.fill_(float("nan"))
-        P, S, loss = eng.train_fwd_bwd(batch, 1.0)
-    finally:
-        lib.gmc_set_fuse(prev)
-    off = 0
-    for (rp, cl, vl) in util.csrs_of(ds):
-        f = CO.forward(rp, cl, vl, params["conv1.weight"], params["conv1.bias"], params["conv2.weight"], params["conv2.bias"])
-        n = len(rp) - 1
-        assert np.abs(P[off:off + n].cpu().numpy() - f["P"]).max() < PROB_TOL
-        off += n
-    ct = CO.CTrainer(params)
-    ref_loss = ct.step(util.csrs_of(ds))
-    # a row may decode differently from the oracle only on a float64 near-tie (then, and only then, the
-    # gradients differ by design); everything else must hold
-    Sk, Pk, off, near_ties = S.cpu().numpy(), P.cpu().numpy(), 0, 0
-    for (rp, cl, vl), (_g, _a, nx_g, _t) in zip(util.csrs_of(ds), ds.values()):
-        n = len(rp) - 1
-        P64 = R.forward_dense_f64({k: torch.from_numpy(v) for k, v in params.items()}, nx_g)
-        ref_s = P64.argmax(1)
-        ref_s[:3] = [0, 1, 2]
-        differ = np.nonzero(Sk[off:off + n] != ref_s)[0]
-        srt = np.sort(P64[differ], axis=1)
-        assert ((srt[:, 2] - srt[:, 1]) < 1e-6).all(), (differ, srt)
-        near_ties += differ.size
-        off += n
-    if near_ties == 0:
-        assert np.array_equal(loss.cpu().numpy(), ref_loss)
-        ref = flat_ref_grads(ct)
-        for k, g in eng.views(eng.grad).items():
-            g, r = g.cpu().numpy().ravel(), ref[k]
-            assert np.abs(g - r).max() <= 1e-4 * max(1.0, np.abs(r).max()), k
-    assert float(eng.grad[eng.count]) == float(loss.sum())
+    # a row may decode differently from the oracle only on a near-tie (margin < 1e-6); loss and gradient are then the
+    # oracle's for the partition the kernels chose; everything else must hold
+    _eng, got, _ = stepcheck.check_step_against_oracle(pkg, net, ds, params, fuse=0, weighted=False)
+    stepcheck.f64_step(util.csrs_of(ds), params, got.S)      # ... and only on a near-tie of the float64 formula
 
 
 @pytest.mark.parametrize("fuse", [1, 0])
@@ -557,48 +499,14 @@ def test_relu_kink_is_the_only_gradient_mismatch(pkg, fuse):
     bar holds a pre-activation within fp32 noise of zero in the float64 formula; all other columns, dW2
     and db2 meet the bar."""
     specs = [(1000, 7, 5), (900, 7, 6), (500, 6, 8)]
-    T, cfg, net, embed, opt, params = model_and_params(pkg, 500)
+    T, cfg, net, embed, opt, params = util.model(500)
     ds = util.product_dataset(specs)
-    eng = net.engine()
-    items = list(ds.values())
-    batch = pkg.GraphBatch([it[0] for it in items], None, eng.device)
-    lib = pkg.hip.load()
-    prev = lib.gmc_set_fuse(fuse)
-    try:
-        eng.train_fwd_bwd(batch, 1.0)
-        eng._ws.fill_(255)
-        eng.grad.fill_(float("nan"))
-        P, S, loss = eng.train_fwd_bwd(batch, 1.0)
-    finally:
-        lib.gmc_set_fuse(prev)
-    ct = CO.CTrainer(params)
-    ref_loss = ct.step(util.csrs_of(ds))
-    assert np.array_equal(loss.cpu().numpy(), ref_loss)
-    # float64 pre-activations of layer 1: |y| < noise marks a kink column
-    kink = np.zeros(500, bool)
-    W1, b1 = params["conv1.weight"].astype(np.float64), params["conv1.bias"].astype(np.float64)
-    for (_g, _a, nx_g, _t) in items:
-        n = nx_g.number_of_nodes()
-        a = np.zeros((n, n))
-        for u, v in nx_g.edges():
-            a[u, v] = a[v, u] = 1.0
-        dis = 1.0 / np.sqrt(a.sum(1))
-        t0 = dis[:, None] * (a @ W1[:n])                 # dinv o (A @ W1[:n])  (the X @ W1 row gather)
-        pre = dis[:, None] * (a @ t0) + b1               # layer-1 pre-activation
-        kink |= (np.abs(pre) < 1e-7).any(0)           # ~50 terms of ~3e-3: fp32 accumulation noise is ~1e-8
-    ref = flat_ref_grads(ct)
-    got = {k: g.cpu().numpy() for k, g in eng.views(eng.grad).items()}
-    for k in ("conv2.weight", "conv2.bias"):   # (row f of dW2 = H[:, f]^T (...): H ~ 0 at the kink either way)
-        r = ref[k]
-        assert np.abs(got[k].ravel() - r).max() <= 1e-4 * max(1.0, np.abs(r).max()), k
-    tol1 = 1e-4 * max(1.0, np.abs(ref["conv1.weight"]).max())
-    d1 = np.abs(got["conv1.weight"] - ref["conv1.weight"].reshape(1000, 500)).max(0)       # per column
-    bad = np.nonzero(d1 > tol1)[0]
-    assert set(bad) <= set(np.nonzero(kink)[0]), (bad, np.nonzero(kink)[0])
-    tolb = 1e-4 * max(1.0, np.abs(ref["conv1.bias"]).max())
-    badb = np.nonzero(np.abs(got["conv1.bias"] - ref["conv1.bias"]) > tolb)[0]
-    assert set(badb) <= set(np.nonzero(kink)[0])
-    assert kink.sum() <= 25 and len(bad) <= 2          # (a few of 500 columns qualify; at most the known one differs)
+    # float64 pre-activations of layer 1: |y| < noise marks a kink column (~50 terms of ~3e-3: fp32 accumulation noise
+    # is ~1e-8).  (Row f of dW2 = H[:, f]^T (...): H ~ 0 at the kink either way, so dW2 / db2 get no exception.)
+    _eng, _got, res = stepcheck.check_step_against_oracle(pkg, net, ds, params, fuse=fuse, weighted=False, kinks=(1e-7, 2))
+    assert res["near_ties"] == 0                       # the losses are the oracle's own
+    kink = stepcheck.kink_columns(util.csrs_of(ds), params, noise=1e-7)
+    assert kink.sum() <= 25                            # (a few of 500 columns qualify; at most the known one differs)
 
 
 def test_adam_parity_step_by_step_on_the_reference_schedule(pkg):
@@ -607,7 +515,7 @@ def test_adam_parity_step_by_step_on_the_reference_schedule(pkg):
     correction or moment update on a LATE step cannot hide behind accumulated trajectory noise.  Checked per
     step t: loss; m and v; and the parameter update on every entry whose gradient is at least 1 % of the
     largest (relative error of the update below 2 %: at t = 12 the bias correction is a factor 6.6)."""
-    T, cfg, net, embed, opt, params = model_and_params(pkg, 16)
+    T, cfg, net, embed, opt, params = util.model(16)
     specs = SPECS_SMALL * 3
     ds = util.product_dataset(specs)
     eng = net.engine()
@@ -643,7 +551,7 @@ def test_replayed_epoch_survives_a_larger_forward_and_follows_hyper_parameters(p
     sequence with eager launches.  The replay must also follow a changed learning rate / C."""
     results = []
     for allow_graph in (True, False):
-        T, cfg, net, embed, opt, params = model_and_params(pkg, 32)
+        T, cfg, net, embed, opt, params = util.model(32)
         ds = util.product_dataset(SPECS_SMALL)
         big = util.product_dataset([(200, 7, 100 + i) for i in range(24)])
         tr = T._trainer_for(net, opt, cfg)
@@ -670,10 +578,10 @@ def test_replayed_epoch_survives_a_larger_forward_and_follows_hyper_parameters(p
 def test_empty_batch_clears_gradient_and_loss_tail(pkg):
     """A data-parallel rank whose shard of a step is empty: zero gradient AND zero loss in the tail slot
     (which still holds the previous step's batch loss)."""
-    T, cfg, net, embed, opt, params = model_and_params(pkg, 16)
+    T, cfg, net, embed, opt, params = util.model(16)
     ds = util.product_dataset(SPECS_SMALL[:2])
     eng = net.engine()
-    batch = pkg.GraphBatch([it[0] for it in ds.values()], None, eng.device)
+    batch = util.batch_of(pkg, eng, ds.values(), weighted=False)
     eng.train_fwd_bwd(batch, 1.0)
     assert float(eng.grad[eng.count]) < 0
     empty = pkg.GraphBatch([], None, eng.device)
@@ -686,7 +594,7 @@ def test_smallest_graphs_and_empty_inputs(pkg):
     dataset (the reference returns 0 / average 0, TrainingNeural.py:371,566), a batch of zero graphs."""
     import networkx as nx
     from gcn_max_cut_amd.Training import TrainingNeural as T
-    T_, cfg, net, embed, opt, params = model_and_params(pkg, 16)
+    T_, cfg, net, embed, opt, params = util.model(16)
     from gcn_max_cut_amd.DataGenerator import graphExtender as GE
     from gcn_max_cut_amd import commons
     # the reference's terminal normalisation skips graphs with two or more of {0,1,2} among their
@@ -707,13 +615,13 @@ def test_smallest_graphs_and_empty_inputs(pkg):
         ds[len(ds)] = it
     eng = net.engine()
     items = list(ds.values())
-    batch = pkg.GraphBatch([it[0] for it in items], None, eng.device)
+    batch = util.batch_of(pkg, eng, items, weighted=False)
     P, S, loss = eng.train_fwd_bwd(batch, 1.0)
     ct = CO.CTrainer(params)
     ref_loss = ct.step(util.csrs_of(ds))
     assert np.array_equal(loss.cpu().numpy(), ref_loss)
     assert float(loss[0]) == -3.0   # triangle, three different terminals: every edge is cut
-    ref = flat_ref_grads(ct)
+    ref = stepcheck.flat_ref_grads(ct)
     for k, g in eng.views(eng.grad).items():
         assert np.abs(g.cpu().numpy().ravel() - ref[k]).max() <= 1e-4 * max(1.0, np.abs(ref[k]).max()), k
     assert T.evaluate_model(net, {}, cfg) == {'average_loss': 0, 'total_loss': 0.0, 'num_samples': 0}
@@ -826,7 +734,7 @@ def test_sampler_boundary_draws_follow_the_pinned_numpy_semantics(pkg, monkeypat
 def test_inference_harness_matches_oracle_post_processing(pkg):
     """test_multiple_graphs (config 5 shape: mixed sizes) == oracle decode with the same RNG."""
     from gcn_max_cut_amd.Testing import TestingNeuralNetwork as TN
-    T, cfg, net, *_rest, params = model_and_params(pkg, 64)
+    T, cfg, net, *_rest, params = util.model(64)
     specs = [(50, 6, 50001), (100, 7, 100001), (200, 8, 200001), (300, 6, 300001), (500, 7, 500001)]
     ds = util.product_dataset(specs)
     np.random.seed(0)
@@ -851,7 +759,7 @@ def test_inference_harness_matches_oracle_post_processing(pkg):
 
 def test_forward_with_arbitrary_dense_features(pkg):
     """net(g, X) with X that is not the adjacency: dense layer-1 GEMM + HIP kernels (inference)."""
-    T, cfg, net, *_rest, params = model_and_params(pkg, 32)
+    T, cfg, net, *_rest, params = util.model(32)
     ds = util.product_dataset([(60, 5, 77)])
     (g, a_pad, nx_g, _t), = ds.values()
     torch.manual_seed(1)
@@ -1168,7 +1076,7 @@ def test_w1_slab_copy_layout_and_bitwise_identical_training(pkg, hidden, gps, mo
     for dp_sequence in (False, True):
         runs = []
         for slab in (True, False):
-            T, cfg, net, embed, opt, params = model_and_params(pkg, hidden, seed=9)
+            T, cfg, net, embed, opt, params = util.model(hidden, seed=9)
             eng = net.engine()
             eng.slab_enabled = slab and eng.slab_enabled
             tr = T.FusedTrainer(net, opt, cfg, graphs_per_step=gps, engine=WithoutFusedStep(eng) if dp_sequence else eng)
@@ -1192,7 +1100,7 @@ def test_w1_slab_copy_follows_torch_writes(pkg):
     ds = util.product_dataset([(1000, 7, 71), (640, 7, 72)])
     runs = []
     for slab in (True, False):
-        T, cfg, net, embed, opt, params = model_and_params(pkg, 64, seed=3)
+        T, cfg, net, embed, opt, params = util.model(64, seed=3)
         eng = net.engine()
         eng.slab_enabled = slab and eng.slab_enabled
         tr = T.FusedTrainer(net, opt, cfg, graphs_per_step=2)
@@ -1263,7 +1171,7 @@ def test_one_step_epochs_same_result_on_every_launch_trigger(pkg, monkeypatch):
     ds = util.product_dataset(specs)
     runs = {}
     for path in ("direct", "graph", "copy"):
-        T, cfg, net, embed, opt, params = model_and_params(pkg, 128, seed=17)
+        T, cfg, net, embed, opt, params = util.model(128, seed=17)
         tr = T.FusedTrainer(net, opt, cfg, graphs_per_step=len(specs))
         with monkeypatch.context() as m:
             if path == "graph":
@@ -1291,7 +1199,7 @@ def test_polled_losses_nan_is_a_value_and_first_epoch_is_fast(pkg):
     import math, time as _time
     ds = util.product_dataset([(300, 7, 91), (200, 6, 92), (260, 8, 93)])
     for gps in (3, 1):       # batched step (eager, zero-copy stores) and the reference schedule (hipGraph per epoch)
-        T, cfg, net, embed, opt, _ = model_and_params(pkg, 64)   # (a NaN step ruins the weights: fresh model each time)
+        T, cfg, net, embed, opt, _ = util.model(64)   # (a NaN step ruins the weights: fresh model each time)
         tr = T.FusedTrainer(net, opt, cfg, graphs_per_step=gps)
         t0 = _time.perf_counter()
         first = tr.epoch(ds)
@@ -1305,7 +1213,7 @@ def test_polled_losses_nan_is_a_value_and_first_epoch_is_fast(pkg):
         assert _time.perf_counter() - t0 < 1.0 and tr.deadline_hits == 0 and tr._poll
         tr.config = cfg
     # a middle item replaced in a large dict is invisible to prepare()'s probes: invalidate() re-plans
-    T, cfg, net, embed, opt, _ = model_and_params(pkg, 64)
+    T, cfg, net, embed, opt, _ = util.model(64)
     big = util.product_dataset([(60, 5, 200 + i) for i in range(40)])
     tr = T.FusedTrainer(net, opt, cfg, graphs_per_step=40)
     tr.epoch(big)

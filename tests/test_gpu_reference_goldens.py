@@ -9,9 +9,8 @@ import numpy as np
 import pytest
 import torch
 
-from oracle import c_oracle as CO
 from oracle import ref_dense as R
-from tests import util
+from tests import stepcheck, util
 
 pytestmark = pytest.mark.gpu
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -159,84 +158,21 @@ def test_reference_evaluate_model_fixture_on_the_gpu_head(pkg, G):
 
 
 # --------------------------------------------------------------------------- BASELINE configs, literally
-def model(pkg, hidden, seed=0):
-    from gcn_max_cut_amd.Training import TrainingNeural as T
-    cfg = T.TrainingConfig(n_nodes=1000, hidden_dim=hidden)
-    torch.manual_seed(seed)
-    net, embed, opt = T.setup_model_and_optimizer(cfg)
-    return T, cfg, net, embed, opt, util.np_params(net.state_dict())
-
-
-def flat_ref_grads(ct):
-    o = np.cumsum([0, ct.N * ct.F, ct.F, ct.F * ct.K, ct.K])
-    return {"conv1.weight": ct.grad[o[0]:o[1]], "conv1.bias": ct.grad[o[1]:o[2]],
-            "conv2.weight": ct.grad[o[2]:o[3]], "conv2.bias": ct.grad[o[3]:o[4]]}
-
-
 def check_step_against_c_oracle(pkg, specs, hidden=500):
     """One batched training step (forward, loss, backward) of the default fused sequence vs the scalar C
-    oracle: probabilities 1e-4, argmax exact where the float64-free margin is clear, per-graph losses, and the
-    batch gradient 1e-4 of its largest entry (where a graph decodes differently on a sub-1e-6 margin the
-    gradient differs by design: then the differing rows must all be near-ties)."""
-    T, cfg, net, embed, opt, params = model(pkg, hidden)
+    oracle: probabilities 1e-4, argmax exact where the float64-free margin is clear (a row may decode differently only
+    on a sub-1e-6 margin; loss and gradient are then the oracle's for the partition the kernels chose), per-graph
+    losses, and the batch gradient 1e-4 of its largest entry.
+
+    Relu kinks: among the batch's millions of layer-1 pre-activations a few land within fp32 rounding of 0 (sums of
+    ~50 terms of ~3e-3: fp32 accumulation noise ~1e-8), kernels and oracle may take different sides, and then that
+    hidden column's dW1 column and db1 entry differ by one row's contribution.  Such columns are identified in float64
+    and are the ONLY place where the 1e-4 bar may be missed.  Returns the number of rows decoded on a near-tie."""
+    T, cfg, net, embed, opt, params = util.model(hidden)
     ds = util.product_dataset(specs)
-    eng = net.engine()
-    items = list(ds.values())
-    batch = pkg.GraphBatch([it[0] for it in items], None, eng.device)
-    eng.train_fwd_bwd(batch, 1.0)
-    eng._ws.fill_(255)
-    eng.grad.fill_(float("nan"))
-    P, S, loss = eng.train_fwd_bwd(batch, 1.0)
-    P, S, loss = P.cpu().numpy(), S.cpu().numpy(), loss.cpu().numpy()
-    csrs = util.csrs_of(ds)
-    ct = CO.CTrainer(params)
-    ref_loss = ct.step(csrs)
-    off, undecided = 0, 0
-    for i, (rp, cl, vl) in enumerate(csrs):
-        n = len(rp) - 1
-        f = CO.forward(rp, cl, vl, params["conv1.weight"], params["conv1.bias"], params["conv2.weight"], params["conv2.bias"])
-        assert np.abs(P[off:off + n] - f["P"]).max() < 1e-4
-        ref_s = f["P"].argmax(1)
-        ref_s[:3] = [0, 1, 2]
-        diff = np.nonzero(S[off:off + n] != ref_s)[0]
-        if diff.size:   # only rows whose top-2 margin is inside fp32 noise may decode differently
-            srt = np.sort(f["P"][diff].astype(np.float64), axis=1)
-            assert (srt[:, 2] - srt[:, 1]).max() < 1e-6, (i, diff, srt)
-            undecided += diff.size
-        else:
-            assert loss[i] == ref_loss[i], i
-        off += n
-    assert float(eng.grad[eng.count]) == float(loss.sum())
-    if undecided == 0:
-        # relu kinks: among the batch's millions of layer-1 pre-activations a few land within fp32 rounding
-        # of 0, kernels and oracle may take different sides, and then that hidden column's dW1 column and db1
-        # entry differ by one row's contribution.  Such columns are identified in float64 and are the ONLY
-        # place where the 1e-4 bar may be missed.
-        kink = np.zeros(hidden, bool)
-        W1, b1 = params["conv1.weight"].astype(np.float64), params["conv1.bias"].astype(np.float64)
-        for (_g, _a, nx_g, _t) in items:
-            n = nx_g.number_of_nodes()
-            a = np.zeros((n, n))
-            for u, v in nx_g.edges():
-                a[u, v] = a[v, u] = 1.0
-            dis = 1.0 / np.sqrt(a.sum(1))
-            pre = dis[:, None] * (a @ (dis[:, None] * (a @ W1[:n]))) + b1
-            kink |= (np.abs(pre) < 3e-8).any(0)     # (sums of ~50 terms of ~3e-3: fp32 accumulation noise ~1e-8)
-        ref = flat_ref_grads(ct)
-        bad_cols = set()
-        for k, gr in eng.views(eng.grad).items():
-            gr, r = gr.cpu().numpy(), ref[k].reshape(tuple(gr.shape))
-            tol = 1e-4 * max(1.0, np.abs(r).max())
-            d = np.abs(gr - r)
-            if k == "conv1.weight":
-                bad_cols |= set(np.nonzero(d.max(0) > tol)[0])
-            elif k == "conv1.bias":
-                bad_cols |= set(np.nonzero(d > tol)[0])
-            else:
-                assert d.max() <= tol, k
-        assert bad_cols <= set(np.nonzero(kink)[0]), (sorted(bad_cols), np.nonzero(kink)[0])
-        assert len(bad_cols) <= max(2, len(items) // 10)
-    return undecided
+    _eng, _got, res = stepcheck.check_step_against_oracle(pkg, net, ds, params, weighted=False,
+                                                          kinks=(3e-8, max(2, len(ds) // 10)))
+    return res["near_ties"]
 
 
 def test_config3_full_size_step_against_the_c_oracle(pkg):
@@ -262,7 +198,7 @@ def test_config4_mixed_sizes_inference_with_200_iteration_post_processing(pkg):
     reference's draw order against the oracle restatement (itself pinned against the reference's own
     post_processing_optimization by tests/golden/decode.json), bit for bit: same best assignment, same cut."""
     from gcn_max_cut_amd.Testing import TestingNeuralNetwork as TN
-    T, cfg, net, *_ = model(pkg, 500)
+    T, cfg, net, *_ = util.model(500)
     specs = [(n, 6 + (i % 3), n * 1000 + i) for n in (50, 100, 200, 300, 500) for i in range(2)]
     ds = util.product_dataset(specs)
     net.eval()
@@ -283,7 +219,7 @@ def test_evaluate_optimal_partitioning_on_the_gpu_model(pkg):
     """GetOptimalNetValue / evaluate_optimal_partitioning (TrainingNeural.py:253-289) on the real HIP
     model, against the oracle restatement of the same lines fed with the oracle's probabilities: six
     forwards (the permutations never reach the model), terminal override, 0.5 threshold, legacy cut."""
-    T, cfg, net, embed, opt, params = model(pkg, 64)
+    T, cfg, net, embed, opt, params = util.model(64)
     ds = util.product_dataset([(40, 5, 41), (64, 6, 43)])
     tp = {k: torch.from_numpy(v) for k, v in params.items()}
     for (g, a_pad, nx_g, _t) in ds.values():

@@ -1,10 +1,10 @@
 """GPU matrix of the row-kernel sequence (tests/test_row_kernels.py: ROW_MATRIX and the census that pins it) against
-a float64 restatement of the training step on CSR segment sums (tests/util.py, f64_*_sparse).
+a float64 restatement of the training step on CSR segment sums (tests/stepcheck.py, f64_*_sparse).
 
 Each case builds its batch (the n graph, then B - 1 graphs of 12 nodes), checks that it has the table / overflow
 lists of its route and that the query gives it no LDS word, poisons workspace and gradient, and runs one
 gmc_train_fwd_bwd under the probe: the tags are exactly the row sequence, every flavour word is 0.  P, the partition
-(near-tie rule of util.f64_step), the loss (-C cut of the kernels' own partition), the gradient per parameter row
+(near-tie rule of stepcheck.f64_step), the loss (-C cut of the kernels' own partition), the gradient per parameter row
 (never looser than the oracle bar) and the zero dW1 rows past n_max are compared with float64; gmc_forward's P, S and
 loss are bitwise those of the training step.  Further: gmc_spmm_f32 per launch class, gmc_backward_from_gp with a dense
 random dL/dP, three Adam steps of the largest advertised problem (N = 4096, hidden 2048, one 4096-node graph), and
@@ -23,17 +23,12 @@ import numpy as np
 import pytest
 import torch
 
-from tests import util
+from tests import stepcheck, util
+from tests.stepcheck import KEYS, ORACLE_BAR, P_TOL, ROW_FLOOR, ROW_TOL, SHORT
 from tests.test_row_kernels import (DROPOUT_CASES, GP_CASES, ROW_MATRIX, USER_SPMM, dw1_chunks, launch_np, row_tags)
 
 pytestmark = pytest.mark.gpu
 
-P_TOL = 5e-7            # absolute, probabilities
-ROW_TOL = 2e-4          # per parameter row, relative to the row's own magnitude
-ROW_FLOOR = 1e-3        # ... or this fraction of the tensor's largest entry, for rows that are (near) zero
-ORACLE_BAR = 1e-4       # the oracle tests' bar (x max(1, max|grad|)): the per-row bar is never looser
-KEYS = ("conv1.weight", "conv1.bias", "conv2.weight", "conv2.bias")
-SHORT = dict(zip(("W1", "b1", "W2", "b2"), KEYS))
 MEASURED = {}
 
 
@@ -44,36 +39,14 @@ def pkg(built):
 
 
 # ---- graphs
-def near_regular(n, d, seed):
-    d = min(d, n - 1)
-    m = n if n * d % 2 == 0 else n + 1
-    g = nx.random_regular_graph(d, m, seed=seed)
-    if m > n:
-        g.remove_node(n)
-    out = nx.Graph()
-    out.add_nodes_from(range(n))
-    out.add_edges_from(g.edges)
-    return out
-
-
-def add_hub(g, hub_degree, seed, hub=5):
-    rng = np.random.RandomState(seed)
-    for v in rng.permutation(g.number_of_nodes()):
-        if g.degree(hub) >= hub_degree:
-            break
-        if int(v) != hub and not g.has_edge(hub, int(v)):
-            g.add_edge(hub, int(v))
-    assert g.degree(hub) == hub_degree
-
-
 def big_graph(kind, n, seed):
     if kind == "gnp":
         g = nx.gnp_random_graph(n, 30.0 / n, seed=seed)
         assert min(d for _v, d in g.degree()) > 0
         return g
-    g = near_regular(n, {"reg7": 7, "ovf8": 7, "hub": 7, "reg12": 12, "ovf16": 12}[kind], seed)
+    g = util.near_regular(n, {"reg7": 7, "ovf8": 7, "hub": 7, "reg12": 12, "ovf16": 12}[kind], seed, attrs=False)
     if kind in ("ovf8", "ovf16", "hub"):
-        add_hub(g, {"ovf8": 12, "ovf16": 20, "hub": 150}[kind], seed)
+        util.add_hub(g, {"ovf8": 12, "ovf16": 20, "hub": 150}[kind], seed, attrs=False)
     return g
 
 
@@ -82,7 +55,7 @@ def build(pkg, kind, n, F, weights, B, N=None, seed=None):
     from gcn_max_cut_amd import graph as G
     from gcn_max_cut_amd.Training import TrainingNeural as T
     seed = 7 * n + F + B if seed is None else seed
-    graphs = [big_graph(kind, n, seed)] + [near_regular(12, 3, seed + i) for i in range(1, B)]
+    graphs = [big_graph(kind, n, seed)] + [util.near_regular(12, 3, seed + i, attrs=False) for i in range(1, B)]
     rng = np.random.RandomState(seed)
     for g in graphs:
         for u, v in g.edges():
@@ -99,40 +72,23 @@ def build(pkg, kind, n, F, weights, B, N=None, seed=None):
 
 # ---- comparisons
 def check_grad(grads, g64, csrs, params, what, kinks_ok=True):
-    """Every parameter row within ROW_TOL of the float64 gradient and within the oracle bar.  A layer-1 column whose
-    float64 pre-activation lies within fp32 noise of 0 (a relu kink) may differ (test_gpu_wide_hidden's rule: at most
-    three such columns)."""
-    worst, kink = 0.0, None
-    for k, key in SHORT.items():
-        g, r = np.asarray(grads[key], np.float64).reshape(g64[k].shape), g64[k]
-        assert np.isfinite(g).all(), (what, key)
-        ratio = util.row_error_ratio(g, r, ROW_FLOOR)
-        bar = ORACLE_BAR * max(1.0, float(np.abs(r).max()))
-        if (ratio > ROW_TOL or np.abs(g - r).max() > bar) and k in ("W1", "b1") and kinks_ok:
-            if kink is None:
-                kink = np.nonzero(util.kink_columns(csrs, params, sparse=True))[0]
-            off = np.nonzero((np.abs(g - r) > 0.5 * ROW_TOL * np.abs(r).max()).reshape(-1, r.shape[-1]).any(0))[0]
-            assert len(kink) <= 3 and set(off) <= set(kink), (what, key, off, kink)
-            keep = np.ones(r.shape[-1], bool)
-            keep[kink] = False
-            g, r = g[..., keep], r[..., keep]
-            ratio = util.row_error_ratio(g, r, ROW_FLOOR)
-        assert np.abs(g - r).max() <= bar, (what, key, float(np.abs(g - r).max()), bar)
-        assert ratio <= ROW_TOL, (what, key, ratio)
-        worst = max(worst, ratio)
-    return worst
+    """Every parameter row within ROW_TOL of the float64 gradient (keyed W1 / b1 / W2 / b2) and within the oracle bar.
+    A layer-1 column whose float64 pre-activation lies within fp32 noise of 0 (a relu kink) may differ
+    (test_gpu_wide_hidden's rule: at most three such columns).  Returns the worst row ratio."""
+    res = stepcheck.compare_grads(grads, stepcheck.named(g64), what=what, **rules(csrs, params, kinks_ok))
+    assert res["kink_cols"] is None or res["kink_cols"] <= 3, (what, res)
+    return res["rows"]
+
+
+def rules(csrs, params, kinks_ok=True):
+    return dict(grad_bar=ORACLE_BAR, row_tol=ROW_TOL, row_floor=ROW_FLOOR, kinks=(1e-7, 3) if kinks_ok else None,
+                csrs=csrs, params=params, sparse=True)
 
 
 def record(family, p_err, ratio):
     a, b = MEASURED.get(family, (0.0, 0.0))
     MEASURED[family] = (max(a, p_err), max(b, ratio))
     print(f"row case {family}: P {p_err:.2e} rows {ratio:.2e}")
-
-
-def poison(eng, batch):
-    eng._workspace(batch, True)
-    eng._ws.fill_(255)                 # all-ones bytes = NaN
-    eng.grad.fill_(float("nan"))
 
 
 # ---- the matrix
@@ -145,29 +101,19 @@ def test_row_matrix(pkg, case):
     assert (h.n_max, h.ell_width, h.ovf_max_blocks, h.vals is not None) == (n, W, blocks, weights), cid
     if W:
         assert h.ell_slots == slots, cid
-    lib = pkg.hip.load()
     words = pkg.hip.lds_flavours(batch.c, eng.Fp)
     assert words == [] if fuse else len(words) == 2, cid
-    prev = lib.gmc_set_fuse(fuse)
-    try:
-        poison(eng, batch)
-        with pkg.hip.Probe(64) as probe:
-            P, S, loss = eng.train_fwd_bwd(batch)
-        grads = {k: v.cpu().numpy() for k, v in eng.views(eng.grad).items()}
-        Pf, Sf, lossf = eng.forward(batch, want_loss=True)
-    finally:
-        lib.gmc_set_fuse(prev)
-    assert [t for t, _ms in probe.records] == row_tags(B), (cid, probe.records)
-    assert not any(probe.flavours), probe.flavours
-    assert torch.equal(P, Pf) and torch.equal(S, Sf) and torch.equal(loss, lossf), cid
-    P, S, loss = P.cpu().numpy(), S.cpu().numpy(), loss.cpu().numpy()
-    P64, loss64, g64 = util.f64_step(csrs, params, S, sparse=True)
-    p_err = float(np.abs(P - P64).max())
-    assert p_err <= P_TOL, (cid, p_err)
-    assert np.array_equal(loss, loss64.astype(np.float32)), (cid, loss, loss64)
-    assert float(eng.grad[eng.count]) == float(loss.sum())
-    assert not grads["conv1.weight"][n:].any(), cid          # rows past every graph's n: exactly 0
-    ratio = check_grad(grads, g64, csrs, params, cid)
+    with util.fused(pkg, fuse):
+        got = stepcheck.run_step(pkg, eng, batch)
+        Pf, Sf, lossf = (t.cpu().numpy() for t in eng.forward(batch, want_loss=True))
+    assert got.tags == row_tags(B), (cid, got.tags)
+    assert not any(got.flavours), got.flavours
+    assert np.array_equal(got.P, Pf) and np.array_equal(got.S, Sf) and np.array_equal(got.loss, lossf), cid
+    ref = stepcheck.f64_step(csrs, params, got.S, sparse=True)
+    assert not got.grads["conv1.weight"][n:].any(), cid          # rows past every graph's n: exactly 0
+    res = stepcheck.compare_step(got, ref, p_tol=P_TOL, what=cid, **rules(csrs, params))
+    assert res["kink_cols"] is None or res["kink_cols"] <= 3, (cid, res)
+    p_err, ratio = res["p_err"], res["rows"]
     record(f"matrix F{launch_np(F)} B{'1' if B == 1 else 'fold' if dw1_chunks(B) > 1 else 'chunk1'}", p_err, ratio)
     record("matrix " + cid, p_err, ratio)
 
@@ -178,8 +124,8 @@ def test_row_matrix(pkg, case):
 def test_user_spmm(pkg, F, weights, epi):
     lib = pkg.hip.load()
     rng = np.random.RandomState(F + 2 * weights + epi)
-    g = near_regular(300, 9, F)
-    add_hub(g, 80, F)                                        # one row of more than 64 neighbours
+    g = util.near_regular(300, 9, F, attrs=False)
+    util.add_hub(g, 80, F, attrs=False)                           # one row of more than 64 neighbours
     from gcn_max_cut_amd import graph as G
     hd = G.from_networkx(g)
     rp, cl = hd.rowptr, hd.col
@@ -199,14 +145,14 @@ def test_user_spmm(pkg, F, weights, epi):
                           n, F, 0, p(t["W2"]) if epi else None, p(Z0), pkg.hip.stream())
     pkg.hip.check(rc, "gmc_spmm_f32")
     Y64 = np.maximum(scale[:, None].astype(np.float64) *
-                     util.csr_mm(rp, cl, None if vl is None else vl.astype(np.float64), X[:, :F].astype(np.float64))
+                     stepcheck.csr_mm(rp, cl, None if vl is None else vl.astype(np.float64), X[:, :F].astype(np.float64))
                      + bias, 0.0)
     Yg = Y.cpu().numpy()[:, :F].astype(np.float64)
-    ratio = util.row_error_ratio(Yg, Y64, ROW_FLOOR)
+    ratio = stepcheck.row_error_ratio(Yg, Y64, ROW_FLOOR)
     assert ratio <= ROW_TOL, ratio
     if epi:
         Z64 = scale[:, None] * (Y64 @ W2.astype(np.float64))
-        zr = util.row_error_ratio(Z0.cpu().numpy(), Z64, ROW_FLOOR)
+        zr = stepcheck.row_error_ratio(Z0.cpu().numpy(), Z64, ROW_FLOOR)
         assert zr <= ROW_TOL, zr
         ratio = max(ratio, zr)
     record(f"spmm_f32 F{launch_np(F) if F % 4 == 0 else 'scalar'}", 0.0, ratio)
@@ -233,10 +179,10 @@ def test_backward_from_gp_with_a_dense_gp(pkg, cid):
     Pn = P.cpu().numpy().astype(np.float64)
     for rp, cl, vl in csrs:
         m = len(rp) - 1
-        f = util.f64_forward_sparse(rp, cl, vl, *W)
+        f = stepcheck.f64_forward_sparse(rp, cl, vl, *W)
         assert np.abs(f["P"] - Pn[off:off + m]).max() <= P_TOL
         f["P"] = Pn[off:off + m]                              # the backward differentiates at the kernels' P
-        g = util.f64_backward_sparse(f, GP[off:off + m].astype(np.float64), W[2], W[0].shape[0])
+        g = stepcheck.f64_backward_sparse(f, GP[off:off + m].astype(np.float64), W[2], W[0].shape[0])
         g64 = g if g64 is None else {k: g64[k] + g[k] for k in g64}
         off += m
     ratio = check_grad(grads, g64, csrs, params, cid)
@@ -260,10 +206,11 @@ def test_largest_problem_three_adam_steps(pkg):
             P, S, loss = eng.train_step(batch, lr, betas=(b1, b2), eps=eps)
         assert [tg for tg, _ms in probe.records] == row_tags(1) + ["adam"], probe.records
         state = {k: v.astype(np.float32) for k, v in before.items()}
-        P64, loss64, g64 = util.f64_step(csrs, state, S.cpu().numpy(), sparse=True)
-        p_err = float(np.abs(P.cpu().numpy() - P64).max())
+        ref = stepcheck.f64_step(csrs, state, S.cpu().numpy(), sparse=True)
+        g64 = {k: ref.grads[key] for k, key in SHORT.items()}
+        p_err = float(np.abs(P.cpu().numpy() - ref.P).max())
         assert p_err <= P_TOL, (t, p_err)
-        assert np.array_equal(loss.cpu().numpy(), loss64.astype(np.float32)), t
+        assert np.array_equal(loss.cpu().numpy(), ref.loss), t
         grads = {k: v.cpu().numpy() for k, v in eng.views(eng.grad).items()}
         ratio = check_grad(grads, g64, csrs, state, f"adam step {t}")
         record("largest problem (grad)", p_err, ratio)
@@ -290,13 +237,13 @@ def f64_dropout_step(csrs, params, S_got, goffs, seed, p, C_=1.0):
     for (rp, cl, vl), g0 in zip(csrs, goffs):
         n = len(rp) - 1
         keep = util.dropout_keep(seed, g0 + np.arange(n), np.arange(Fh), p)
-        f = util.f64_forward_sparse(rp, cl, vl, W1, b1, W2, b2)
+        f = stepcheck.f64_forward_sparse(rp, cl, vl, W1, b1, W2, b2)
         dinv = f["dinv"]
         Hd = f["H"] * keep / (1.0 - p)
-        Z = dinv[:, None] * util.csr_mm(rp, cl, None, dinv[:, None] * Hd @ W2) + b2
+        Z = dinv[:, None] * stepcheck.csr_mm(rp, cl, None, dinv[:, None] * Hd @ W2) + b2
         E = np.exp(Z - Z.max(1, keepdims=True))
         P = E / E.sum(1, keepdims=True)
-        S = util.f64_partition(P)
+        S = stepcheck.f64_partition(P)
         s_got = np.asarray(S_got[g0:g0 + n])
         diff = np.nonzero(s_got != S)[0]
         if diff.size:
@@ -304,14 +251,14 @@ def f64_dropout_step(csrs, params, S_got, goffs, seed, p, C_=1.0):
             assert (srt[:, 2] - srt[:, 1]).max() < 1e-6, (diff, srt)
             S = s_got.astype(np.int64)
         f.update(P=P, H=Hd)
-        loss, GP = util.f64_loss_and_gp_sparse(f, S, C_)
+        loss, GP = stepcheck.f64_loss_and_gp_sparse(f, S, C_)
         gz = P * (GP - (GP * P).sum(1, keepdims=True))
-        gy2 = util.csr_mm(rp, cl, None, dinv[:, None] * gz)
+        gy2 = stepcheck.csr_mm(rp, cl, None, dinv[:, None] * gz)
         dW2 = (dinv[:, None] * Hd).T @ gy2
         gg = np.where(Hd > 0, dinv[:, None] * (gy2 @ W2.T) / (1.0 - p), 0.0)
-        gy1 = util.csr_mm(rp, cl, None, dinv[:, None] * gg)
+        gy1 = stepcheck.csr_mm(rp, cl, None, dinv[:, None] * gg)
         dW1 = np.zeros_like(W1)
-        dW1[:n] = util.csr_mm(rp, cl, f["w"], dinv[:, None] * gy1)
+        dW1[:n] = stepcheck.csr_mm(rp, cl, f["w"], dinv[:, None] * gy1)
         g = dict(W1=dW1, b1=gg.sum(0), W2=dW2, b2=gz.sum(0))
         grad = g if grad is None else {k: grad[k] + g[k] for k in grad}
         Ps.append(P); losses.append(loss); Hs.append((keep, f["pre"], Hd))
@@ -344,7 +291,7 @@ def test_dropout_against_float64_with_the_restated_mask(pkg):
         eng.set_dropout(p, seed)
         try:
             # route 1: the training entry
-            poison(eng, batch)
+            util.poison(eng, batch)
             with pkg.hip.Probe(64) as probe:
                 P, S, loss = eng.train_fwd_bwd(batch)
             grads = {k: v.cpu().numpy().copy() for k, v in eng.views(eng.grad).items()}

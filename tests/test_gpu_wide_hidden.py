@@ -9,7 +9,7 @@ import torch
 
 from oracle import c_oracle as CO
 from oracle import ref_dense as R
-from tests import util
+from tests import stepcheck, util
 
 pytestmark = pytest.mark.gpu
 
@@ -24,84 +24,18 @@ def pkg(built):
     return built
 
 
-def model(hidden, seed=0):
-    from gcn_max_cut_amd.Training import TrainingNeural as T
-    cfg = T.TrainingConfig(n_nodes=1000, hidden_dim=hidden)
-    torch.manual_seed(seed)
-    net, embed, opt = T.setup_model_and_optimizer(cfg)
-    return T, cfg, net, embed, opt, util.np_params(net.state_dict())
-
-
-def with_hub(n, d, seed, hub_degree, hub=5):
-    g = R.regular_graph(n, d, seed)
-    rng = np.random.RandomState(seed)
-    others = [v for v in rng.permutation(n) if v != hub and not g.has_edge(hub, int(v))]
-    for v in others[:hub_degree - d]:
-        g.add_edge(hub, int(v), weight=1, capacity=1)
-    assert g.degree(hub) == hub_degree
-    return g
-
-
 def dataset(case):
     if case == "mix":
         return util.product_dataset(MIX)
     if case == "weighted":
         return util.dataset_of(*util.weighted_copy(MIX, seed=7))
     if case == "hub":   # one degree-40 row: overflow lists (fused LDS kernels; the unfused sequence: row kernels)
-        graphs = {0: with_hub(1000, 7, 4011, 40), 1: R.regular_graph(300, 7, 4012)}
+        graphs = {0: util.with_hub(1000, 7, 4011, 40), 1: R.regular_graph(300, 7, 4012)}
         return util.dataset_of(graphs, {i: R.seeded_terminals(g.number_of_nodes(), 4013 + i) for i, g in graphs.items()})
     if case == "n270":  # 8 rows per thread at 64-column tiles
         return util.product_dataset([(270, 7, 4021), (200, 6, 4022)])
     assert case == "n530"  # 8 rows per thread at 32-column tiles
     return util.product_dataset([(530, 7, 4031), (500, 8, 4032)])
-
-
-def check_step(pkg, net, ds, params):
-    """util.check_step_against_oracle; where it finds a dW1 / db1 entry off the bar, the relu-kink rule of
-    test_gpu_parity.test_relu_kink_is_the_only_gradient_mismatch instead: every column off the bar holds a
-    pre-activation within fp32 noise of 0 in the float64 formula, dW2 / db2 / P / the losses meet the bar."""
-    try:
-        return util.check_step_against_oracle(pkg, net, ds, params)
-    except AssertionError as e:
-        if e.args[:1] not in (("conv1.weight",), ("conv1.bias",)):
-            raise
-    eng = net.engine()
-    batch = batch_of(pkg, eng, ds)
-    with pkg.hip.Probe(64) as probe:
-        P, S, loss = eng.train_fwd_bwd(batch, 1.0)
-    tags = [t for t, _ms in probe.records]
-    ct = CO.CTrainer(params)
-    csrs = util.csrs_of(ds)
-    assert np.array_equal(loss.cpu().numpy(), ct.step(csrs))
-    o = np.cumsum([0, ct.N * ct.F, ct.F, ct.F * ct.K, ct.K])
-    ref = {k: ct.grad[o[i]:o[i + 1]] for i, k in enumerate(("conv1.weight", "conv1.bias", "conv2.weight", "conv2.bias"))}
-    got = {k: g.cpu().numpy() for k, g in eng.views(eng.grad).items()}
-    for k in ("conv2.weight", "conv2.bias"):
-        assert np.abs(got[k].ravel() - ref[k]).max() <= 1e-4 * max(1.0, np.abs(ref[k]).max()), k
-    kink = np.nonzero(util.kink_columns(util.csrs_of(ds), params))[0]
-    F = got["conv1.bias"].shape[0]
-    d1 = np.abs(got["conv1.weight"] - ref["conv1.weight"].reshape(-1, F)).max(0)
-    bad = np.nonzero(d1 > 1e-4 * max(1.0, np.abs(ref["conv1.weight"]).max()))[0]
-    badb = np.nonzero(np.abs(got["conv1.bias"] - ref["conv1.bias"]) > 1e-4 * max(1.0, np.abs(ref["conv1.bias"]).max()))[0]
-    assert set(bad) | set(badb) <= set(kink) and len(bad) <= 3, (bad, badb, kink)
-    Wl = [params[k] for k in ("conv1.weight", "conv1.bias", "conv2.weight", "conv2.bias")]
-    Pn, off = P.cpu().numpy(), 0
-    for rp, cl, vl in csrs:
-        n = len(rp) - 1
-        assert np.abs(Pn[off:off + n] - CO.forward(rp, cl, vl, *Wl)["P"]).max() < 1e-4
-        off += n
-    return eng, tags
-
-
-def batch_of(pkg, eng, ds):
-    items = list(ds.values())
-    return pkg.GraphBatch([it[0] for it in items], [it[0].edge_values(it[1]) for it in items], eng.device)
-
-
-def probed_words(pkg, eng, batch):
-    with pkg.hip.Probe(64) as pr:
-        eng.train_fwd_bwd(batch, 1.0)
-    return {w & ~PER_MASK for w in pr.flavours if w}
 
 
 @pytest.mark.parametrize("case", ["mix", "weighted", "hub", "n270", "n530"])
@@ -110,22 +44,20 @@ def probed_words(pkg, eng, batch):
 def test_step_against_oracle(pkg, hidden, fuse, case):
     """One batched step: per-graph loss (or a documented near-tie), gradient <= 1e-4 of its largest entry, P within 1e-4
     of the C oracle and of the float64 restatement; the launches are the LDS flavours F = 1024 takes for this batch."""
-    T, cfg, net, embed, opt, params = model(hidden)
+    T, cfg, net, embed, opt, params = util.model(hidden)
     ds = dataset(case)
-    lib = pkg.hip.load()
-    prev = lib.gmc_set_fuse(fuse)
-    try:
-        eng, tags = check_step(pkg, net, ds, params)
-        batch = batch_of(pkg, eng, ds)
+    with util.fused(pkg, fuse):
+        # relu kinks (test_gpu_parity.test_relu_kink_is_the_only_gradient_mismatch): a dW1 column / db1 entry may be off
+        # the bar only where the float64 pre-activation lies within fp32 noise of 0, at most three columns
+        eng, got, _ = stepcheck.check_step_against_oracle(pkg, net, ds, params, kinks=(1e-7, 3))
+        batch = util.batch_of(pkg, eng, ds)
         at1024 = pkg.hip.lds_flavours(batch.c, 1024)
         want = {w & ~PER_MASK for w in (at1024[:2] if fuse else at1024[2:])}
-        assert probed_words(pkg, eng, batch) == want, (tags, want)
-        assert ("fwd1_fused" in tags) == bool(fuse and at1024) and ("bwd1_fused" in tags) == bool(fuse and at1024)
+        assert {w & ~PER_MASK for w in got.flavours if w} == want, (got.tags, want)
+        assert ("fwd1_fused" in got.tags) == bool(fuse and at1024) and ("bwd1_fused" in got.tags) == bool(fuse and at1024)
         P, S, _loss = eng.forward(batch, 1.0, want_loss=True)
-    finally:
-        lib.gmc_set_fuse(prev)
     assert eng.F == hidden and eng.Fp % 4 == 0
-    P64, _l, _g = util.f64_step(util.csrs_of(ds), params, S.cpu().numpy())
+    P64 = stepcheck.f64_step(util.csrs_of(ds), params, S.cpu().numpy()).P
     assert np.abs(P.cpu().numpy() - P64).max() < 1e-4
 
 
@@ -134,7 +66,7 @@ def test_adam_parity_on_the_reference_schedule_at_2048(pkg):
     parameters and moments and given the C oracle's gradient of that step, against the device's update (every entry
     whose gradient is >= 1 % of the largest: update within 2 %; moments 1e-4 / 2e-4 of their largest).  The one-graph
     backward computes the head (no head launch; the bwd1_reg flavour carries GMC_FLV_HEAD)."""
-    T, cfg, net, embed, opt, params = model(2048)
+    T, cfg, net, embed, opt, params = util.model(2048)
     ds = util.product_dataset([(100, 7, 4041), (50, 6, 4042), (300, 8, 4043), (64, 8, 4044), (1000, 7, 4045)])
     eng = net.engine()
     csrs = util.csrs_of(ds)
@@ -192,7 +124,7 @@ def test_batched_and_data_parallel_trainer_at_2048(pkg):
     ds = util.product_dataset([(1000, 7, 4051), (640, 6, 4052), (300, 8, 4053), (90, 11, 4054)])
     runs = []
     for variant in ("fused", "dp-sequence"):
-        T, cfg, net, embed, opt, params = model(2048, seed=5)
+        T, cfg, net, embed, opt, params = util.model(2048, seed=5)
         eng = net.engine()
         tr = T.FusedTrainer(net, opt, cfg, graphs_per_step=2,
                             engine=eng if variant == "fused" else WithoutFusedStep(eng))
@@ -213,7 +145,7 @@ def test_batched_and_data_parallel_trainer_at_2048(pkg):
 def test_autograd_chain_and_dense_features_at_2048(pkg):
     """net(g, A) -> override_fixed_nodes -> apply_max_to_one_hot -> compute_loss -> backward equals the fused gradient;
     net(g, X) with random dense X under no_grad (the wide row SpMM with the fused W2 epilogue) equals ref_dense."""
-    T, cfg, net, embed, opt, params = model(2048)
+    T, cfg, net, embed, opt, params = util.model(2048)
     ds = util.product_dataset([(300, 7, 4061)])
     (g, a_pad, nx_g, _t), = ds.values()
     net.train()
@@ -308,7 +240,7 @@ def test_dropout_at_2048(pkg):
 def test_forward_offsets_past_2_31(pkg):
     """1100 graphs of n = 1000 (d = 7) at hidden 2048: H is 2.25e9 elements.  P of the first and the last graphs (two
     different graphs, alternating through the batch) against the C oracle."""
-    T, cfg, net, embed, opt, params = model(2048)
+    T, cfg, net, embed, opt, params = util.model(2048)
     ds = util.product_dataset([(1000, 7, 4081), (1000, 7, 4082)])
     items = list(ds.values())
     eng = net.engine()
@@ -329,7 +261,7 @@ def test_checkpoint_round_trip_at_2048(pkg, tmp_path, monkeypatch):
     """save_neural_model / load_neural_model keep the reference's logical shapes; the loaded model's next step equals
     the original's."""
     monkeypatch.chdir(tmp_path)
-    T, cfg, net, embed, opt, params = model(2048)
+    T, cfg, net, embed, opt, params = util.model(2048)
     ds = util.product_dataset([(300, 7, 4091), (120, 6, 4092)])
     T.train_single_epoch(ds, net, opt, embed, cfg)
     T.save_neural_model(net, opt, embed, 1, [0.0], cfg, "m.pth")
@@ -343,7 +275,7 @@ def test_checkpoint_round_trip_at_2048(pkg, tmp_path, monkeypatch):
     out = []
     for n_ in (net, net2):
         e = n_.engine()
-        _P, _S, loss = e.train_fwd_bwd(pkg.GraphBatch([it[0] for it in items], None, e.device), cfg.C)
+        _P, _S, loss = e.train_fwd_bwd(util.batch_of(pkg, e, items, weighted=False), cfg.C)
         out.append((loss.cpu().clone(), e.grad[:e.count].cpu().clone()))
     assert torch.equal(out[0][0], out[1][0]) and torch.equal(out[0][1], out[1][1])
 

@@ -11,7 +11,7 @@ overflow windows, with edge weights, under gmc_set_fuse(0) or dropout).  This mo
 - reachable <= instantiated, instantiated - reachable == DEAD (each with its reason);
 - ROW_MATRIX (run by tests/test_gpu_row_kernels.py) covers every reachable instantiation and every route into the row
   sequence, and the query gives no LDS word for any of its batches;
-- the sparse float64 step equals the dense one of tests/util.py; the numpy dropout mask is the kernel's hash.
+- the sparse float64 step equals the dense one of tests/stepcheck.py; the numpy dropout mask is the kernel's hash.
 """
 import ctypes as C
 import math
@@ -20,7 +20,7 @@ import re
 import numpy as np
 import pytest
 
-from tests import util
+from tests import stepcheck, util
 from tests.test_lds_flavours import batch_struct
 
 FAMILIES = ("spmm_rows_v4", "spmm_rows_wide", "spmm_rows_scalar", "dw1_gather_kernel", "fold_chunks_kernel",
@@ -263,19 +263,19 @@ def test_sparse_float64_step_equals_the_dense_one(weighted):
                             np.float32)
         csrs.append((rp, cl, vl))
         W = [params[k] for k in ("conv1.weight", "conv1.bias", "conv2.weight", "conv2.bias")]
-        fd, fs = util.f64_forward(rp, cl, vl, *W), util.f64_forward_sparse(rp, cl, vl, *W)
+        fd, fs = stepcheck.f64_forward(rp, cl, vl, *W), stepcheck.f64_forward_sparse(rp, cl, vl, *W)
         for k in ("dinv", "H", "P"):
             assert np.abs(fd[k] - fs[k]).max() <= 1e-12 * max(1.0, np.abs(fd[k]).max()), k
-        S = util.f64_partition(fd["P"])
-        (ld, gd), (ls, gs) = util.f64_loss_and_gp(fd, S), util.f64_loss_and_gp_sparse(fs, S)
+        S = stepcheck.f64_partition(fd["P"])
+        (ld, gd), (ls, gs) = stepcheck.f64_loss_and_gp(fd, S), stepcheck.f64_loss_and_gp_sparse(fs, S)
         assert ld == ls and np.array_equal(gd, gs)
-    S_all = np.concatenate([util.f64_partition(util.f64_forward_sparse(rp, cl, vl, *W)["P"]) for rp, cl, vl in csrs])
-    Pd, lossd, gd = util.f64_step(csrs, params, S_all)
-    Ps, losss, gs = util.f64_step(csrs, params, S_all, sparse=True)
+    S_all = np.concatenate([stepcheck.f64_partition(stepcheck.f64_forward_sparse(rp, cl, vl, *W)["P"]) for rp, cl, vl in csrs])
+    Pd, lossd, gd, _ties = stepcheck.f64_step(csrs, params, S_all)
+    Ps, losss, gs, _ties = stepcheck.f64_step(csrs, params, S_all, sparse=True)
     assert np.abs(Pd - Ps).max() <= 1e-12 and np.array_equal(lossd, losss)
     for k in gd:
         assert np.abs(gd[k] - gs[k]).max() <= 1e-12 * max(1.0, np.abs(gd[k]).max()), k
-    assert np.array_equal(util.kink_columns(csrs, params, noise=1e-2), util.kink_columns(csrs, params, noise=1e-2,
+    assert np.array_equal(stepcheck.kink_columns(csrs, params, noise=1e-2), stepcheck.kink_columns(csrs, params, noise=1e-2,
                                                                                           sparse=True))
 
 

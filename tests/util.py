@@ -1,10 +1,11 @@
 """Shared builders for the parity tests: the same seeded graphs go through the product's
 GraphExtender (-> GraphHandle + padded adjacency) and through the oracle's."""
-import copy
+import contextlib
 import re
 import struct
 import subprocess
 
+import networkx as nx
 import numpy as np
 import torch
 
@@ -53,220 +54,75 @@ def dataset_of(graphs, terms, max_nodes=1000):
     return GE.process_graphs_from_folder(graphs, terms, max_nodes)
 
 
-def check_step_against_oracle(pkg, net, ds, params, C=1.0):
-    """One batched forward + loss + backward of the dataset through the C ABI against the C oracle: per-graph loss
-    (== -cut of the partition the kernels chose), every gradient entry <= 1e-4 of the largest.  The workspace and
-    the gradient buffer are poisoned first: nothing may be read before it is written in the same step.  Returns
-    (engine, kernel tags of the step) so that callers can assert which kernel sequence ran."""
-    eng = net.engine()
-    items = list(ds.values())
-    batch = pkg.GraphBatch([it[0] for it in items], [it[0].edge_values(it[1]) for it in items], eng.device)
-    eng.train_fwd_bwd(batch, C)        # sizes the workspace ...
-    eng._ws.fill_(255)                 # ... which is then poisoned (all-ones bytes = NaN)
-    eng.grad.fill_(float("nan"))
-    with pkg.hip.Probe(64) as probe:
-        P, S, loss = eng.train_fwd_bwd(batch, C)
-    tags = [t for t, _ms in probe.records]
-    ct = CO.CTrainer(params, Cc=C)
-    csrs = csrs_of(ds)
-    ref_loss = ct.step(csrs)
-    loss_np, S_np = loss.cpu().numpy(), S.cpu().numpy()
-    if not np.array_equal(loss_np, ref_loss):
-        # A graph whose loss differs decoded some row differently.  That is legitimate only on a near-tie (the
-        # summation order of the kernels is not the oracle's: top-2 margin inside fp32 noise); the gradient of
-        # such a graph is then the oracle's backward for the partition the KERNELS chose, which is what is built
-        # here: same forward, GP from the kernels' S, same backward.
-        W = [params[k] for k in ("conv1.weight", "conv1.bias", "conv2.weight", "conv2.bias")]
-        acc = [np.zeros_like(w) for w in W]
-        off = 0
-        for i, (rp, cl, vl) in enumerate(csrs):
-            n = len(rp) - 1
-            f = CO.forward(rp, cl, vl, *W)
-            ref_s = f["P"].argmax(1); ref_s[:3] = [0, 1, 2]
-            s_i = S_np[off:off + n]
-            diff = np.nonzero(s_i != ref_s)[0]
-            if diff.size == 0:
-                assert loss_np[i] == ref_loss[i], i
-            else:
-                srt = np.sort(f["P"][diff].astype(np.float64), axis=1)
-                assert (srt[:, 2] - srt[:, 1]).max() < 1e-6, (i, diff, srt)
-            wv = np.ones(len(cl), np.float32) if vl is None else vl
-            rows = np.repeat(np.arange(n), np.diff(rp))
-            GP = np.zeros((n, 3), np.float32)
-            np.add.at(GP, (rows, s_i[cl]), C * wv)                  # GP = C * A_val @ onehot(S)
-            cut = 0.5 * float(wv[s_i[rows] != s_i[cl]].sum())
-            assert loss_np[i] == np.float32(-C * cut), i            # loss == -C cut of the partition the kernels chose
-            for a_, d_ in zip(acc, CO.backward(rp, cl, vl, W[0].shape[0], W[2], f["H"], f["P"], GP)):
-                a_ += d_
-            off += n
-        ref = dict(zip(("conv1.weight", "conv1.bias", "conv2.weight", "conv2.bias"), [a_.ravel() for a_ in acc]))
-    else:
-        o = np.cumsum([0, ct.N * ct.F, ct.F, ct.F * ct.K, ct.K])
-        ref = {k: ct.grad[o[i]:o[i + 1]] for i, k in enumerate(("conv1.weight", "conv1.bias", "conv2.weight", "conv2.bias"))}
-    assert float(eng.grad[eng.count]) == float(loss_np.sum())   # GMC_MODEL_GRAD_TAIL: the loss rides behind the gradient
-    for k, g in eng.views(eng.grad).items():
-        g, r = g.cpu().numpy().ravel(), ref[k]
-        assert np.abs(g - r).max() <= 1e-4 * max(1.0, np.abs(r).max()), k
-    # probabilities of every graph against the oracle forward
-    off = 0
-    Pn = P.cpu().numpy()
-    Wl = [params[k] for k in ("conv1.weight", "conv1.bias", "conv2.weight", "conv2.bias")]
-    for (rp, cl, vl) in csrs:
-        n = len(rp) - 1
-        assert np.abs(Pn[off:off + n] - CO.forward(rp, cl, vl, *Wl)["P"]).max() < 1e-4
-        off += n
-    return eng, tags
-
-
-# ---- float64 restatement of one training step (forward, loss, backward) on a graph's CSR, for the flavour matrix.
-# Written from the algorithm the oracle documents (oracle/gcn_oracle.c: GraphConv norm='both' twice, softmax, terminal
-# override + argmax, cut loss, straight-through dLoss/dP = C * A_val @ onehot(S)), on dense n x n operators.
-def f64_forward(rp, cl, vl, W1, b1, W2, b2):
-    n = len(rp) - 1
-    rows = np.repeat(np.arange(n), np.diff(rp))
-    A = np.zeros((n, n))
-    A[rows, cl] = 1.0                                   # structure: the aggregations carry no edge weight
-    X = np.zeros((n, n))
-    X[rows, cl] = 1.0 if vl is None else vl.astype(np.float64)   # features = the weighted adjacency
-    dinv = 1.0 / np.sqrt(np.maximum(np.diff(rp), 1).astype(np.float64))
-    W1, b1, W2, b2 = (np.asarray(w, np.float64) for w in (W1, b1, W2, b2))
-    T0 = dinv[:, None] * (X @ W1[:n])
-    H = np.maximum(dinv[:, None] * (A @ T0) + b1, 0.0)
-    Z = dinv[:, None] * (A @ (dinv[:, None] * H @ W2)) + b2
-    E = np.exp(Z - Z.max(1, keepdims=True))
-    return dict(A=A, X=X, dinv=dinv, H=H, P=E / E.sum(1, keepdims=True))
-
-
-def f64_partition(P):
-    S = P.argmax(1)
-    S[:3] = [0, 1, 2]
-    return S
-
-
-def f64_loss_and_gp(f, S, C=1.0):
-    """loss = -C * cut(S), GP = C * A_val @ onehot(S)."""
-    X = f["X"]
-    cut = 0.5 * float((X * (S[:, None] != S[None, :])).sum())
-    return -C * cut, C * X @ np.eye(3)[S]
-
-
-def f64_backward(f, GP, W2, N):
-    A, X, dinv, H, P = f["A"], f["X"], f["dinv"], f["H"], f["P"]
-    W2 = np.asarray(W2, np.float64)
-    gz = P * (GP - (GP * P).sum(1, keepdims=True))     # softmax backward
-    gy2 = A @ (dinv[:, None] * gz)
-    dW2 = (dinv[:, None] * H).T @ gy2
-    g = np.where(H > 0, dinv[:, None] * (gy2 @ W2.T), 0.0)
-    gy1 = A @ (dinv[:, None] * g)
-    dW1 = np.zeros((N, H.shape[1]))
-    dW1[:len(dinv)] = X @ (dinv[:, None] * gy1)
-    return dict(W1=dW1, b1=g.sum(0), W2=dW2, b2=gz.sum(0))
-
-
-def f64_step(csrs, params, S_got, C=1.0, tie=1e-6, sparse=False):
-    """Per graph: float64 P, the partition (the kernels' own where the float64 top-2 margin is below `tie`: the
-    summation orders differ, a near-tie may decode either way - anywhere else the partitions must agree), the loss
-    of that partition, and the summed float64 gradient of the batch.  `sparse`: the CSR restatement (same values)."""
-    fwd, lgp, bwd = ((f64_forward_sparse, f64_loss_and_gp_sparse, f64_backward_sparse) if sparse else
-                     (f64_forward, f64_loss_and_gp, f64_backward))
-    W = [params[k] for k in ("conv1.weight", "conv1.bias", "conv2.weight", "conv2.bias")]
-    grad = None
-    Ps, losses, off = [], [], 0
-    for rp, cl, vl in csrs:
-        n = len(rp) - 1
-        f = fwd(rp, cl, vl, *W)
-        S = f64_partition(f["P"])
-        s_got = np.asarray(S_got[off:off + n])
-        diff = np.nonzero(s_got != S)[0]
-        if diff.size:
-            srt = np.sort(f["P"][diff], axis=1)
-            assert (srt[:, 2] - srt[:, 1]).max() < tie, (diff, srt)
-            S = s_got.astype(np.int64)
-        loss, GP = lgp(f, S, C)
-        g = bwd(f, GP, W[2], W[0].shape[0])
-        grad = g if grad is None else {k: grad[k] + g[k] for k in grad}
-        Ps.append(f["P"])
-        losses.append(loss)
-        off += n
-    return np.concatenate(Ps), np.asarray(losses), grad
-
-
-def row_error_ratio(got, ref, floor):
-    """max over rows of |got - ref| / max(max |ref row|, floor * max |ref|): each parameter row (dW1 row j, a b1 entry,
-    a dW2 row, a b2 entry) judged against its own magnitude; `floor` keeps rows that are exactly zero in the reference
-    (rows past every graph's n) at a bar relative to the tensor."""
-    got = np.asarray(got, np.float64).reshape(ref.shape[0], -1)
-    ref = np.asarray(ref, np.float64).reshape(ref.shape[0], -1)
-    scale = np.maximum(np.abs(ref).max(1), floor * max(np.abs(ref).max(), 1e-30))
-    return float((np.abs(got - ref).max(1) / scale).max())
-
-
-
-def kink_columns(csrs, params, noise=1e-7, sparse=False):
-    """Columns f of layer 1 with a float64 pre-activation within fp32 accumulation noise of 0 (relu kinks: the kernels
-    and the oracle may take different sides, and then that column of dW1 and entry of db1 differ by design)."""
-    W = [params[k].astype(np.float64) for k in ("conv1.weight", "conv1.bias", "conv2.weight", "conv2.bias")]
-    kink = np.zeros(W[1].shape[0], bool)
-    for rp, cl, vl in csrs:
-        if sparse:
-            pre = f64_forward_sparse(rp, cl, vl, *W)["pre"]
-        else:
-            f = f64_forward(rp, cl, vl, *W)
-            pre = f["dinv"][:, None] * (f["A"] @ (f["dinv"][:, None] * (f["X"] @ W[0][:len(f["dinv"])]))) + W[1]
-        kink |= (np.abs(pre) < noise).any(0)
-    return kink
-
-
-# ---- the same float64 step on CSR segment sums: no n x n operator, for graphs of thousands of nodes and wide layers
-def csr_mm(rp, cl, w, M, block=512):
-    """CSR matrix (edge weights w; None = unit) times the dense float64 M, as per-row segment sums of M's rows."""
-    n = len(rp) - 1
-    out = np.zeros((n, M.shape[1]))
-    live = np.nonzero(np.diff(rp))[0]
-    if live.size == 0:
-        return out
-    starts = np.asarray(rp[:-1])[live]
-    for c0 in range(0, M.shape[1], block):
-        G = M[cl, c0:c0 + block]
-        if w is not None:
-            G = G * w[:, None]
-        out[live, c0:c0 + block] = np.add.reduceat(G, starts, axis=0)
+def near_regular(n, d, seed, attrs=True):
+    """d-regular on n nodes; when n * d is odd, a d-regular graph on n + 1 nodes without its last node.
+    `attrs`: unit weight / capacity on every edge, as the reference's generator sets them."""
+    d = min(d, n - 1)
+    m = n if n * d % 2 == 0 else n + 1
+    g = nx.random_regular_graph(d, m, seed=seed)
+    if m > n:
+        g.remove_node(n)
+    out = nx.Graph()
+    out.add_nodes_from(range(n))
+    out.add_edges_from(g.edges)
+    if attrs:
+        nx.set_edge_attributes(out, 1, "weight")
+        nx.set_edge_attributes(out, 1, "capacity")
     return out
 
 
-def f64_forward_sparse(rp, cl, vl, W1, b1, W2, b2):
-    """f64_forward on the CSR: the aggregations carry no edge weight, the features (the weighted adjacency) do."""
-    n = len(rp) - 1
-    vw = None if vl is None else np.asarray(vl, np.float64)
-    dinv = 1.0 / np.sqrt(np.maximum(np.diff(rp), 1).astype(np.float64))
-    W1, b1, W2, b2 = (np.asarray(w, np.float64) for w in (W1, b1, W2, b2))
-    T0 = dinv[:, None] * csr_mm(rp, cl, vw, W1[:n])
-    pre = dinv[:, None] * csr_mm(rp, cl, None, T0) + b1
-    H = np.maximum(pre, 0.0)
-    Z = dinv[:, None] * csr_mm(rp, cl, None, dinv[:, None] * H @ W2) + b2
-    E = np.exp(Z - Z.max(1, keepdims=True))
-    return dict(rp=rp, cl=cl, w=vw, dinv=dinv, pre=pre, H=H, P=E / E.sum(1, keepdims=True))
+def add_hub(g, hub_degree, seed, hub=5, attrs=True):
+    """Raises node `hub` to hub_degree: new neighbours in the order of a seeded permutation of the nodes."""
+    rng = np.random.RandomState(seed)
+    for v in rng.permutation(g.number_of_nodes()):
+        if g.degree(hub) >= hub_degree:
+            break
+        if int(v) != hub and not g.has_edge(hub, int(v)):
+            g.add_edge(hub, int(v), **(dict(weight=1, capacity=1) if attrs else {}))
+    assert g.degree(hub) == hub_degree
+    return g
 
 
-def f64_loss_and_gp_sparse(f, S, C=1.0):
-    rp, cl, w = f["rp"], f["cl"], f["w"]
-    rows = np.repeat(np.arange(len(rp) - 1), np.diff(rp))
-    cut_w = (S[rows] != S[cl]).astype(np.float64)
-    cut = 0.5 * float((cut_w if w is None else cut_w * w).sum())
-    return -C * cut, C * csr_mm(rp, cl, w, np.eye(3)[S])
+def with_hub(n, d, seed, hub_degree, hub=5):
+    return add_hub(R.regular_graph(n, d, seed), hub_degree, seed, hub)
 
 
-def f64_backward_sparse(f, GP, W2, N):
-    rp, cl, w, dinv, H, P = f["rp"], f["cl"], f["w"], f["dinv"], f["H"], f["P"]
-    W2 = np.asarray(W2, np.float64)
-    gz = P * (GP - (GP * P).sum(1, keepdims=True))
-    gy2 = csr_mm(rp, cl, None, dinv[:, None] * gz)
-    dW2 = (dinv[:, None] * H).T @ gy2
-    g = np.where(H > 0, dinv[:, None] * (gy2 @ W2.T), 0.0)
-    gy1 = csr_mm(rp, cl, None, dinv[:, None] * g)
-    dW1 = np.zeros((N, H.shape[1]))
-    dW1[:len(dinv)] = csr_mm(rp, cl, w, dinv[:, None] * gy1)
-    return dict(W1=dW1, b1=g.sum(0), W2=dW2, b2=gz.sum(0))
+def model(hidden, n_nodes=1000, seed=0):
+    from gcn_max_cut_amd.Training import TrainingNeural as T
+    cfg = T.TrainingConfig(n_nodes=n_nodes, hidden_dim=hidden)
+    torch.manual_seed(seed)
+    net, embed, opt = T.setup_model_and_optimizer(cfg)
+    return T, cfg, net, embed, opt, np_params(net.state_dict())
+
+
+def batch_of(pkg, eng, ds, weighted=True):
+    """The GraphBatch of a dataset (or a list of its items) on the engine's device; `weighted`: with each graph's
+    edge_values (None for a graph of unit weights), else no values at all."""
+    items = list(ds.values()) if isinstance(ds, dict) else list(ds)
+    vals = [it[0].edge_values(it[1]) for it in items] if weighted else None
+    return pkg.GraphBatch([it[0] for it in items], vals, eng.device)
+
+
+@contextlib.contextmanager
+def fused(pkg, on):
+    """gmc_set_fuse(on) for the block (None: as it is), restored after it."""
+    if on is None:
+        yield
+        return
+    lib = pkg.hip.load()
+    prev = lib.gmc_set_fuse(on)
+    try:
+        yield
+    finally:
+        lib.gmc_set_fuse(prev)
+
+
+def poison(eng, batch, grad=True):
+    """Sizes the engine's training workspace for the batch, then fills it and (`grad`) the gradient with NaN."""
+    eng._workspace(batch, True)
+    eng._ws.fill_(255)                 # all-ones bytes = NaN
+    if grad:
+        eng.grad.fill_(float("nan"))
 
 
 # ---- the dropout mask of csrc/dropout.hip restated: splitmix64 of (seed, batch row, column), 24-bit uniform in float32
