@@ -99,6 +99,52 @@ def _refine_on_gpu(batch: GraphBatch, assign: torch.Tensor, max_sweeps: int):
     return best_assign, best_cut, best_idx
 
 
+def anneal_levels() -> np.ndarray:
+    """The level table ``gmc_refine_anneal_f32`` compares ``delta / T`` against: ``-log((i + 0.5) / 1024)`` for
+    i = 0..1023, quantiles of an exponential variate (float64, rounded to float32 once).  With it the kernel's move
+    rule is a Metropolis test at 10-bit resolution, and the device evaluates neither exp nor log."""
+    i = np.arange(hip.ANNEAL_LEVELS, dtype=np.float64)
+    return (-np.log((i + 0.5) / hip.ANNEAL_LEVELS)).astype(np.float32)
+
+
+def anneal_schedule(sweeps: int, t_start: float = 1.5, t_end: float = 0.15, scale: float = 1.0) -> np.ndarray:
+    """float32 ``1 / T_s`` of a geometric cooling ``T_s = scale * t_start * (t_end / t_start) ** (s / max(sweeps-1, 1))``
+    (float64, rounded once).  ``scale``: the mean edge weight of the batch (1 for unit weights)."""
+    if sweeps < 0:
+        raise ValueError(f"sweeps must be >= 0, got {sweeps}")
+    if not (t_start > 0 and t_end > 0 and scale > 0):
+        raise ValueError("t_start, t_end and scale must be > 0")
+    s = np.arange(int(sweeps), dtype=np.float64)
+    temps = float(scale) * float(t_start) * (float(t_end) / float(t_start)) ** (s / max(int(sweeps) - 1, 1))
+    return (1.0 / temps).astype(np.float32)
+
+
+def _anneal_on_gpu(batch: GraphBatch, assign: torch.Tensor, inv_temp: np.ndarray, seed: int, max_descent_sweeps: int):
+    """Annealing + descent (gmc_refine_anneal_f32) over the candidates assign [cands, R] int8, in place; returns the
+    best annealed assignment [R], its cut and candidate index per graph."""
+    dev = batch.device
+    cands = int(assign.shape[0])
+    order, cgoff, cptr = batch.refine_order()
+    sweeps = int(len(inv_temp))
+    inv_t = torch.from_numpy(np.ascontiguousarray(inv_temp, np.float32)).to(dev) if sweeps else None
+    levels = torch.from_numpy(anneal_levels()).to(dev) if sweeps else None
+    cut_all = torch.empty((batch.B, cands), dtype=torch.float32, device=dev)
+    best_assign = torch.empty(batch.R, dtype=torch.int32, device=dev)
+    best_cut = torch.empty(batch.B, dtype=torch.float32, device=dev)
+    best_idx = torch.empty(batch.B, dtype=torch.int32, device=dev)
+    p = hip.ptr
+    rc = hip.load().gmc_refine_anneal_f32(batch.ref(), p(order), p(cgoff), p(cptr), cands, p(assign), p(inv_t), sweeps,
+                                          p(levels), int(seed) & (2 ** 64 - 1), int(max_descent_sweeps), p(cut_all),
+                                          p(best_assign), p(best_cut), p(best_idx), None, None, hip.stream())
+    hip.check(rc, "gmc_refine_anneal_f32")
+    return best_assign, best_cut, best_idx
+
+
+def _mean_edge_weight(batch: GraphBatch) -> float:
+    vals = batch.host.vals
+    return 1.0 if vals is None else float(np.mean(vals, dtype=np.float64))
+
+
 def _as_number(x: float):
     return int(x) if float(x).is_integer() else float(x)
 
@@ -132,6 +178,29 @@ def local_search_optimization(partition_assignment, graph, max_sweeps: int = 100
     batch = GraphBatch([from_networkx(graph)], None, dev)
     assign = torch.from_numpy(part.astype(np.int8)).to(dev).reshape(1, n)
     best_assign, best_cut, _ = _refine_on_gpu(batch, assign, max_sweeps)
+    return best_assign.cpu().tolist(), _as_number(best_cut.item())
+
+
+def annealing_optimization(partition_assignment, graph, sweeps: int = 100, t_start: float = 1.5, t_end: float = 0.15,
+                           seed: int = 0, max_descent_sweeps: int = 100) -> Tuple[List[int], Any]:
+    """Anneal one assignment of ``graph`` on the GPU past the single-move local optima ``local_search_optimization``
+    stops at (extension, include/gcnmaxcut.h ``gmc_refine_anneal_f32``): ``sweeps`` Metropolis sweeps cooling from
+    ``t_start`` to ``t_end`` (in units of the graph's mean edge weight), the best state passed through kept, then the
+    local search from it.  Nodes 0, 1, 2 keep their classes; the result is never worse than the input and is
+    reproducible from ``seed``.  Returns the assignment and its cut value."""
+    dev = hip.require_gpu()
+    part = np.asarray(list(partition_assignment), dtype=np.int64)
+    n = graph.number_of_nodes()
+    if part.shape != (n,):
+        raise ValueError(f"partition_assignment has {part.size} entries, the graph {n} nodes")
+    if part.size and (int(part.min()) < 0 or int(part.max()) > 2):
+        raise ValueError("partition_assignment holds a class outside 0..2")
+    if sweeps < 0 or max_descent_sweeps < 0:
+        raise ValueError(f"sweeps and max_descent_sweeps must be >= 0, got {sweeps} and {max_descent_sweeps}")
+    batch = GraphBatch([from_networkx(graph)], None, dev)
+    assign = torch.from_numpy(part.astype(np.int8)).to(dev).reshape(1, n)
+    inv_temp = anneal_schedule(sweeps, t_start, t_end, _mean_edge_weight(batch))
+    best_assign, best_cut, _ = _anneal_on_gpu(batch, assign, inv_temp, seed, max_descent_sweeps)
     return best_assign.cpu().tolist(), _as_number(best_cut.item())
 
 
@@ -225,13 +294,18 @@ test_multiple_graphs.__test__ = False
 
 
 def decode_dataset(model, processed_graphs: Dict, post_processing_iterations: int = 200,
-                   local_search_sweeps: int = 0) -> List[Dict[str, Any]]:
+                   local_search_sweeps: int = 0, anneal_sweeps: int = 0, anneal_candidates: Optional[int] = None,
+                   anneal_seed: int = 0) -> List[Dict[str, Any]]:
     """Throughput form of the same evaluation (extension): ONE batched forward and ONE sampler
     launch for the whole dataset.  Results equal ``test_multiple_graphs``'s per-graph numbers when
     the RNG state is the same (uniforms are drawn graph by graph in dataset order).
     ``local_search_sweeps > 0`` also refines the argmax decode (candidate 0) and every sample (candidates
     1..iterations, in draw order) by local search (``local_search_optimization``) in one more launch; each result
-    then carries ``refined_cut``, ``refined_assignment`` and ``refined_from`` (the winning candidate)."""
+    then carries ``refined_cut``, ``refined_assignment`` and ``refined_from`` (the winning candidate).
+    ``anneal_sweeps > 0`` anneals a copy of the first ``anneal_candidates`` of the same 1 + iterations candidates
+    (``None``: all of them) with ``annealing_optimization``'s defaults in one more launch; each result then carries
+    ``annealed_cut``, ``annealed_assignment`` and ``annealed_from``.  Neither option changes the other keys or the
+    uniforms drawn."""
     items = list(processed_graphs.values())
     eng = model.engine()
     model.eval()
@@ -244,6 +318,14 @@ def decode_dataset(model, processed_graphs: Dict, post_processing_iterations: in
     if local_search_sweeps > 0:
         cands = torch.cat([S.to(torch.int8).reshape(1, -1), assign_all])
         refined = [t.cpu().numpy() for t in _refine_on_gpu(batch, cands, local_search_sweeps)]
+    annealed = None
+    if anneal_sweeps > 0:
+        take = 1 + post_processing_iterations if anneal_candidates is None else int(anneal_candidates)
+        if not 1 <= take <= 1 + post_processing_iterations:
+            raise ValueError(f"anneal_candidates must be in 1..{1 + post_processing_iterations}, got {anneal_candidates}")
+        cands = torch.cat([S.to(torch.int8).reshape(1, -1), assign_all[:take - 1]]).contiguous()
+        inv_temp = anneal_schedule(anneal_sweeps, scale=_mean_edge_weight(batch))
+        annealed = [t.cpu().numpy() for t in _anneal_on_gpu(batch, cands, inv_temp, anneal_seed, 100)]
     S_host, best_host = S.cpu().numpy(), best_assign.cpu().numpy()
     simple, post = (-loss).cpu().tolist(), best_cut.cpu().tolist()
     out = []
@@ -256,4 +338,8 @@ def decode_dataset(model, processed_graphs: Dict, post_processing_iterations: in
             ref_assign, ref_cut, ref_idx = refined
             out[-1].update({'refined_cut': _as_number(ref_cut[g]), 'refined_assignment': ref_assign[lo:hi].tolist(),
                             'refined_from': int(ref_idx[g])})
+        if annealed is not None:
+            ann_assign, ann_cut, ann_idx = annealed
+            out[-1].update({'annealed_cut': _as_number(ann_cut[g]), 'annealed_assignment': ann_assign[lo:hi].tolist(),
+                            'annealed_from': int(ann_idx[g])})
     return out

@@ -1,6 +1,6 @@
-// Cut count and best-candidate pick shared by the post-processing sampler (decode.hip) and the local search
-// (refine.hip): both score their candidates with the same code, so a candidate the search does not move gets, bit
-// for bit, the cut the sampler reports for it.
+// Cut count and best-candidate pick shared by the post-processing sampler (decode.hip), the local search
+// (refine.hip) and the annealing (anneal.hip): all score their candidates with the same code, so a candidate a search
+// does not move gets, bit for bit, the cut the sampler reports for it.
 #pragma once
 #include "gmc_common.h"
 
@@ -10,20 +10,30 @@ namespace gmc {
 // edge-parallel count over the CSR (each undirected edge seen twice -> / 2), one thread per row, a butterfly per
 // wave, the four wave sums in a fixed order.  Every thread of the 256-thread workgroup must call it (one barrier);
 // thread 0 gets the cut.  red: 4 floats of LDS.
-__device__ __forceinline__ float block_cut(const gmc_batch &b, const unsigned char *sa, int r0, int n, float *red) {
+//
+// block_cut_csr is the count itself over any copy of the graph's CSR: rp[l] .. rp[l + 1] are the edges of local row l
+// in col (local neighbour ids) and vals (NULL: all ones).  block_cut reads the batch's arrays in global memory; the
+// annealing kernel (anneal.hip) also calls block_cut_csr on the copy it keeps in LDS - one piece of code, one
+// summation order, the same bits.
+template <class RP, class COL>
+__device__ __forceinline__ float block_cut_csr(const RP *rp, const COL *col, const float *vals, const unsigned char *sa,
+                                               int n, float *red) {
     float cut = 0.f;
     for (int l = threadIdx.x; l < n; l += blockDim.x) {
-        const int r = r0 + l;
         const int me = sa[l];
-        for (int e = b.rowptr[r]; e < b.rowptr[r + 1]; ++e) {
-            const float w = b.vals ? b.vals[e] : 1.0f;
-            cut += sa[b.lcol[e]] != me ? w : 0.f;
+        for (int e = rp[l]; e < (int)rp[l + 1]; ++e) {
+            const float w = vals ? vals[e] : 1.0f;
+            cut += sa[col[e]] != me ? w : 0.f;
         }
     }
     cut = wave_sum(cut);
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = cut;
     __syncthreads();
     return (((red[0] + red[1]) + red[2]) + red[3]) * 0.5f;
+}
+
+__device__ __forceinline__ float block_cut(const gmc_batch &b, const unsigned char *sa, int r0, int n, float *red) {
+    return block_cut_csr(b.rowptr + r0, b.lcol, b.vals, sa, n, red);
 }
 
 struct PickArgs {

@@ -15,6 +15,7 @@
 // thread per node of the current class, a barrier between classes, a workgroup-wide OR closing every sweep.
 #include "gmc_common.h"
 #include "cut_body.h"
+#include "move_body.h"
 
 #include <vector>
 
@@ -52,26 +53,10 @@ __global__ __launch_bounds__(256) void refine_local_kernel(RefineArgs a) {
             for (int i = a.cptr[k0 + k] + threadIdx.x; i < hi; i += blockDim.x) {
                 const int l = a.order[i] - r0;
                 if ((unsigned)l >= (unsigned)n) continue;   // not a row of this graph: never touch LDS for it
-                // three sums chosen by compares (an indexed private array would live in scratch); a class byte
-                // outside 0..2 adds to none of them
-                float w0 = 0.f, w1 = 0.f, w2 = 0.f;
-                const int e1 = a.b.rowptr[r0 + l + 1];
-                for (int e = a.b.rowptr[r0 + l]; e < e1; ++e) {
-                    const int u = a.b.lcol[e];
-                    if (u == l) continue;
-                    const float w = a.b.vals ? a.b.vals[e] : 1.0f;
-                    const int cu = sa[u];
-                    w0 += cu == 0 ? w : 0.f;
-                    w1 += cu == 1 ? w : 0.f;
-                    w2 += cu == 2 ? w : 0.f;
-                }
-                const int c = sa[l];
-                const float wc = c == 0 ? w0 : c == 1 ? w1 : c == 2 ? w2 : __builtin_inff();
-                int kk = 0;
-                float wk = w0;
-                if (w1 < wk) { kk = 1; wk = w1; }
-                if (w2 < wk) { kk = 2; wk = w2; }
-                if (wk < wc) {
+                float w0, w1, w2;
+                gmc::class_sums(a.b.rowptr + r0, a.b.lcol, a.b.vals, sa, l, w0, w1, w2);
+                int kk;
+                if (gmc::local_move(w0, w1, w2, sa[l], kk)) {
                     sa[l] = (unsigned char)kk;
                     moved = 1;
                 }

@@ -22,10 +22,11 @@ SYMBOLS = (
     "gmc_backward_from_gp", "gmc_probe_begin", "gmc_probe_end", "gmc_set_fuse", "gmc_decode_sample_f32", "gmc_adam_devstep_f32", "gmc_ell_arrange_host", "gmc_ell_slots_for", "gmc_train_step_f32",
     "gmc_adam_devstep_model_f32", "gmc_w1_slab_floats", "gmc_w1_slab_f32", "gmc_host_device_pointer", "gmc_publish_f32",
     "gmc_publish_adam_devstep_model_f32", "gmc_probe_flavours", "gmc_lds_flavours", "gmc_refine_order_host",
-    "gmc_refine_local_f32",
+    "gmc_refine_local_f32", "gmc_refine_anneal_f32", "gmc_refine_anneal_staged",
 )
 
 MAX_GRAPH_NODES = 4096
+ANNEAL_LEVELS = 1024  # GMC_ANNEAL_LEVELS: entries of the level table gmc_refine_anneal_f32 reads
 MODEL_GRAD_TAIL = 1   # gmc_model.flags: grad has a tail slot that receives the batch's loss sum
 ABI_VERSION = 200     # GMC_VERSION of include/gcnmaxcut.h these struct layouts follow (checked at load and per call)
 
@@ -93,6 +94,9 @@ def _declare(lib: C.CDLL) -> None:
     lib.gmc_decode_sample_f32.argtypes = [C.POINTER(GmcBatch), vp, vp, vp, i32, vp, vp, vp, vp, vp, vp]
     lib.gmc_refine_order_host.argtypes = [i32, vp, vp, vp, vp, vp, vp, i32]
     lib.gmc_refine_local_f32.argtypes = [C.POINTER(GmcBatch), vp, vp, vp, i32, vp, i32, vp, vp, vp, vp, vp, vp]
+    lib.gmc_refine_anneal_f32.argtypes = [C.POINTER(GmcBatch), vp, vp, vp, i32, vp, vp, i32, vp, C.c_uint64, i32,
+                                          vp, vp, vp, vp, vp, vp, vp]
+    lib.gmc_refine_anneal_staged.argtypes = [C.POINTER(GmcBatch)]
     lib.gmc_probe_begin.argtypes = [i32]
     lib.gmc_probe_end.argtypes = [vp, vp, i32]
     lib.gmc_probe_flavours.argtypes = [vp, i32]
@@ -177,7 +181,7 @@ def stream() -> int:
 
 KERNEL_TAGS = ("gather_w1", "agg_fwd", "head", "hidden_bwd", "colsum", "agg_bwd", "dw1", "dw1_fold",
                "adam", "spmm_user", "dense_mfma", "bwd1_fused", "fwd1_fused", "decode", "finish",
-               "refine")
+               "refine", "anneal")
 
 
 FLAVOUR_KERNELS = {1: "fwd1_lds", 2: "bwd1_lds", 3: "bwd1_reg", 4: "spmm_lds", 5: "dw1_lds"}   # GMC_FLV_KERNEL

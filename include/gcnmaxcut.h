@@ -166,7 +166,8 @@ enum {
     GMC_K_DECODE = 13,     /* post-processing sampler + cut count */
     GMC_K_FINISH = 14,     /* fold of the gradient partials (+ fused Adam) over the flat buffer */
     GMC_K_REFINE = 15,     /* local search over decoded candidates + cut count (gmc_refine_local_f32) */
-    GMC_K_COUNT = 16
+    GMC_K_ANNEAL = 16,     /* annealing + descent over decoded candidates + cut count (gmc_refine_anneal_f32) */
+    GMC_K_COUNT = 17
 };
 
 /* Timing probe for bench.py: between gmc_probe_begin and gmc_probe_end every kernel launch
@@ -362,7 +363,10 @@ int gmc_decode_sample_f32(const gmc_batch *batch, const float *P, const double *
  *    step (self-loops skipped) into W0, W1, W2; with c = class(v) and k the class of the smallest W (lowest index on
  *    ties), v moves to k iff W[k] < W[c] (a class byte outside 0..2 counts for no W, and such a movable node takes k).
  *    The result equals a sequential sweep in (colour, id) order;
- *  - sweeps run until one moves nothing, or max_sweeps have run (max_sweeps = 0: no move). */
+ *  - sweeps run until one moves nothing, or max_sweeps have run (max_sweeps = 0: no move).
+ * Every move of a node with a class byte 0..2 raises the cut as gmc_decode_sample_f32 counts it.  That count takes
+ * every edge of a byte outside 0..2 as cut, so giving such a node its class may lower it: "the refined cut is never
+ * below the input cut" holds for candidates whose class bytes are all 0..2. */
 
 /* HOST routine (all pointers are host pointers): the colouring above for a batch of B graphs (goff [B+1], rowptr,
  * lcol as in gmc_batch).  Writes order: per graph, the batch row ids of its movable nodes sorted by (colour, id)
@@ -384,6 +388,58 @@ int gmc_refine_order_host(int32_t B, const int32_t *goff, const int32_t *rowptr,
 int gmc_refine_local_f32(const gmc_batch *batch, const int32_t *order, const int32_t *cgoff, const int32_t *cptr,
                          int32_t cands, int8_t *assign, int32_t max_sweeps, float *cut_all, int32_t *best_assign,
                          float *best_cut, int32_t *best_idx, int32_t *sweeps, gmc_stream_t stream);
+
+/* ---- annealing over decoded partitions (extension: no counterpart in the reference) ------------------------------
+ *
+ * The local search above stops at the first single-move local optimum.  This search first runs annealing sweeps that
+ * also accept moves that lose cut, keeps the best state it passes through, and then descends from it with the local
+ * search.  Per (candidate `cand`, graph), with the colouring and order / cgoff / cptr of gmc_refine_order_host; nodes
+ * 0, 1, 2 never move:
+ *  1. state = the input candidate, best = state, best_cut = cut(state): the cut as gmc_decode_sample_f32 and
+ *     gmc_refine_local_f32 count it (fp32, the same code, the same summation order).
+ *  2. annealing sweeps s = 0 .. anneal_sweeps-1, each with inv_temp[s] = 1/T_s (finite, > 0).  A sweep visits the
+ *     colour classes in increasing colour.  Every node v of a class (local id v) computes W0, W1, W2 exactly as the
+ *     local search does: fp32 sums in the CSR order of its row, self-loops skipped, a class byte outside 0..2 counting
+ *     for none.  With c = class(v), the target k is the class of the smaller W among the two classes other than c
+ *     (the lower index on a tie) and delta = W[k] - W[c] in fp32;
+ *         v moves to k  iff  delta < 0  or  delta * inv_temp[s] <= levels[h >> 54]      (one fp32 multiply)
+ *         h = mix64(seed + 0x9E3779B97F4A7C15 * (ctr + 1)),   ctr = (uint64)cand << 32 | (uint64)s << 12 | v
+ *     in uint64 arithmetic, mix64 the splitmix64 finaliser: z = (z ^ z >> 30) * 0xBF58476D1CE4E5B9;
+ *     z = (z ^ z >> 27) * 0x94D049BB133111EB; z ^ z >> 31.  A movable node whose class byte is outside 0..2 takes the
+ *     local search's k (the smallest of all three W, lowest index on ties) unconditionally.  `levels` is a table of
+ *     GMC_ANNEAL_LEVELS floats the caller supplies, so the device evaluates neither exp nor log; with
+ *     levels[i] = (float)(-log((i + 0.5) / GMC_ANNEAL_LEVELS)), quantiles of an exponential variate, the rule is a
+ *     Metropolis test (accept with probability exp(-delta / T)) at 10-bit resolution.
+ *     After each sweep c_s = cut(state); if c_s > best_cut: best = state, best_cut = c_s (the snapshot).
+ *  3. descent: state = best, then the sweeps of gmc_refine_local_f32, with exactly its rule, until one moves nothing or
+ *     max_descent_sweeps have run.
+ *  4. state is written back, scored and picked exactly as gmc_refine_local_f32 scores and picks.
+ * By construction: a class is an independent set and the level depends only on (cand, s, v), so the parallel colour
+ * step equals a sequential visit in (colour, id) order; anneal_sweeps = 0 is gmc_refine_local_f32 with
+ * max_sweeps = max_descent_sweeps, bit for bit; the output cut of a candidate whose class bytes are all 0..2 is never
+ * below its input cut (the cut count takes every edge of a byte outside 0..2 as cut, and the first visit of such a
+ * node gives it a class, so its candidate's cut may fall); and a candidate's result depends on its graph, its index,
+ * the seed and the schedule alone - not on the graph's place in the batch nor on the rest of the batch. */
+#define GMC_ANNEAL_LEVELS 1024
+
+/* The annealing above on `cands` candidates of every graph: assign [cands][R] int8 (device, in/out); order / cgoff /
+ * cptr as for gmc_refine_local_f32; inv_temp [anneal_sweeps] and levels [GMC_ANNEAL_LEVELS] device floats (either may
+ * be NULL when anneal_sweeps == 0).  Outputs as gmc_refine_local_f32's: cut_all [B][cands], best_assign [R] int32,
+ * best_cut [B], best_idx [B]; optional (NULL: not written) snap_sweep [B][cands]: 0 = the descent started from the
+ * input, s + 1 = from the snapshot taken after sweep s; sweeps [B][cands]: the descent sweeps run, counted as the
+ * local search counts them.  Errors, all found before any HIP call: a NULL required pointer GMC_ERR_NULL, batch->abi
+ * GMC_ERR_ABI, cands < 1, a negative sweep count or anneal_sweeps >= 2^20 (the counter layout) GMC_ERR_SHAPE, n_max
+ * outside 3..GMC_MAX_GRAPH_NODES GMC_ERR_GRAPH_SIZE; B == 0 launches nothing.  Two launches on the caller's stream. */
+int gmc_refine_anneal_f32(const gmc_batch *batch, const int32_t *order, const int32_t *cgoff, const int32_t *cptr,
+                          int32_t cands, int8_t *assign, const float *inv_temp, int32_t anneal_sweeps,
+                          const float *levels, uint64_t seed, int32_t max_descent_sweeps, float *cut_all,
+                          int32_t *best_assign, float *best_cut, int32_t *best_idx, int32_t *snap_sweep,
+                          int32_t *sweeps, gmc_stream_t stream);
+/* DIAGNOSTIC host query (no HIP call; reads n_max, nnz_max and whether vals is NULL) for tests and timing scripts;
+ * results never depend on its answer: 1 when gmc_refine_anneal_f32 keeps a copy of each graph's CSR in LDS for this
+ * batch, 0 when the graphs are too large for that and it reads the batch's arrays in global memory (same results, bit
+ * for bit); < 0 on a bad argument. */
+int gmc_refine_anneal_staged(const gmc_batch *batch);
 
 #ifdef __cplusplus
 }
