@@ -115,6 +115,39 @@ class _GCNForward(torch.autograd.Function):
             eng.set_dropout(*now)
 
 
+class _GCNForwardFeatures(torch.autograd.Function):
+    """softmax(conv2(relu(conv1(X)))) for node features X that are not the padded adjacency (learned embeddings:
+    ``net(g, embed.weight)``), with a HIP backward that returns dX and the four parameter gradients.  The three
+    dense products of layer 1 (X @ W1, X^T @ U, U @ W1^T) run in the library's fp32 MFMA GEMM."""
+
+    @staticmethod
+    def forward(ctx, net, batch, X, *params):
+        eng = net.engine()
+        ctx.dropout = eng.dropout_state()    # (p, seed) this forward runs with: the backward needs the same
+        ws = torch.empty(eng.workspace_bytes_features(batch, True), dtype=torch.uint8, device=eng.device)
+        Xd = eng.pad_features(batch, X)      # (padded once when N % 4 != 0: the backward reads the same tensor)
+        P, _, _ = eng.forward_features(batch, Xd, ws=ws)
+        ctx.net, ctx.batch, ctx.ws, ctx.like = net, batch, ws, (X.device, X.dtype)
+        ctx.save_for_backward(P, Xd)
+        return P
+
+    @staticmethod
+    def backward(ctx, gp):
+        P, X = ctx.saved_tensors
+        eng = ctx.net.engine()
+        now = eng.dropout_state()
+        eng.set_dropout(*ctx.dropout)
+        try:
+            # needs_input_grad: (net, batch, X, W1, b1, W2, b2).  GCNSoftmax.forward enters this Function only for
+            # features that require grad, so through net(g, X) the dX GEMM always runs; want_dx = False is reached by
+            # callers of the Function or of the engine whose features are constant
+            g, dX = eng.backward_features_from_gp(ctx.batch, X, P, gp, ws=ctx.ws, want_dx=ctx.needs_input_grad[2])
+            grads = tuple(g[k].clone() if need else None for k, need in zip(PARAM_ORDER, ctx.needs_input_grad[3:]))
+            return (None, None, None if dX is None else dX.to(*ctx.like)) + grads
+        finally:
+            eng.set_dropout(*now)
+
+
 class GCNSoftmax(nn.Module):
     """Graph Convolutional Network with softmax output (TrainingNeural.py:69-85)."""
 
@@ -153,36 +186,45 @@ class GCNSoftmax(nn.Module):
             eng.set_dropout(0.0)
 
     def _forward_dense_features(self, g, inputs):
-        if self.training and self.dropout_frac > 0.0:
-            raise NotImplementedError("dropout > 0 with features that are not the padded adjacency")
-        if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
+        """``net(g, X)`` for features with non-zeros off the graph's edges: inference when no gradient is asked
+        for, the differentiable path when ``X`` requires grad (``embed.weight``); F.dropout applies in train mode."""
+        eng = self.engine()
+        params = [dict(self.named_parameters())[k] for k in PARAM_ORDER]
+        differentiable = torch.is_grad_enabled() and inputs.requires_grad
+        if torch.is_grad_enabled() and not inputs.requires_grad and any(p.requires_grad for p in params):
             raise NotImplementedError(
-                "gradients are implemented for the reference's usage net(g, padded_adjacency) "
-                "(TrainingNeural.py:373); call under torch.no_grad() for arbitrary features")
-        return _dense_forward(self, g, inputs)
+                "gradients with CONSTANT features are implemented for the reference's usage net(g, padded_adjacency) "
+                "(TrainingNeural.py:373) only: call under torch.no_grad() for arbitrary constant features; features "
+                "that require grad (learned embeddings, e.g. embed.weight) take the differentiable dense path")
+        eng.set_dropout(self.dropout_frac if self.training else 0.0)
+        try:
+            if differentiable:
+                return _GCNForwardFeatures.apply(self, _dense_batch_of(g, eng.device), inputs, *params)
+            return _dense_forward(self, g, inputs)
+        finally:
+            eng.set_dropout(0.0)
+
+
+def _dense_batch_of(g: GraphHandle, device) -> GraphBatch:
+    """Single-graph device batch for features that are not the padded adjacency: the structure alone (layer 1 ignores
+    edge values with such features, and the probabilities never read them)."""
+    if not isinstance(g, GraphHandle):
+        raise TypeError(f"expected a GraphHandle (made by process_graphs_from_folder), got {type(g)}")
+    key = ("dense_batch", str(device))
+    b = g._cache.get(key)
+    if b is None:
+        b = GraphBatch([g], [None], device)
+        g._cache[key] = b
+    return b
 
 
 def _dense_forward(net: "GCNSoftmax", g: GraphHandle, inputs: torch.Tensor) -> torch.Tensor:
-    """``net(g, X)`` for features that are NOT the padded adjacency (non-zeros off the edges):
-    the layer-1 feature transform is then a genuine dense GEMM (rocBLAS through torch.matmul,
-    the "plain library GEMM" case), everything after it runs in the HIP kernels.  Inference
-    only - no gradient is defined on this path."""
+    """``net(g, X)`` for features that are NOT the padded adjacency (non-zeros off the edges), without a gradient:
+    ``gmc_forward_features`` - the layer-1 feature transform is a genuine dense GEMM on the library's own fp32 MFMA
+    kernel, everything after it the one-kernel-per-operation sequence.  The same entry point is the forward of the
+    differentiable path (:class:`_GCNForwardFeatures`); the engine's dropout setting applies."""
     eng = net.engine()
-    lib, p = hip.load(), hip.ptr
-    batch = GraphBatch([g], [None], eng.device)
-    v = eng.padded_views()   # (hidden dimension padded to a multiple of 4: pad columns are zeros)
-    X = inputs.detach().to(eng.device, torch.float32)
-    if X.shape != (g.n, eng.N):
-        raise ValueError(f"features must be [{g.n}, {eng.N}], got {tuple(X.shape)}")
-    T0 = ((X * batch.dinv[:, None]) @ v["conv1.weight"]).contiguous()
-    F_ = eng.Fp
-    H = torch.empty((g.n, F_), dtype=torch.float32, device=eng.device)
-    Z0 = torch.empty((g.n, 3), dtype=torch.float32, device=eng.device)
-    P = torch.empty((g.n, 3), dtype=torch.float32, device=eng.device)
-    hip.check(lib.gmc_spmm_f32(p(batch.rowptr), p(batch.gcol), None, p(batch.dinv), p(T0), F_, p(v["conv1.bias"]), 1,
-                               p(H), F_, g.n, F_, 0, p(v["conv2.weight"]), p(Z0), hip.stream()), "gmc_spmm_f32")
-    hip.check(lib.gmc_head_f32(batch.ref(), p(Z0), 1, p(v["conv2.bias"]), 1.0, p(P), None, None, None, None,
-                               hip.stream()), "gmc_head_f32")
+    P, _, _ = eng.forward_features(_dense_batch_of(g, eng.device), inputs)
     return P
 
 

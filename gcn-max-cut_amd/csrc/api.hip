@@ -26,6 +26,8 @@ bool fuse_enabled() {
 //   one-kernel-per-operation LDS sequence - gmc_set_fuse(0), or dropout (which needs H before the W2 product).
 // A batch with overflow lists (rows of more than ell_width neighbours) is served by the fused LDS kernels only: in the
 // one-kernel-per-operation sequence it takes the row kernels.
+// Dense features (gmc_forward_features: X is not the padded adjacency) always take the row kernels: the layer-1 GEMMs
+// then address plain row-major [R, ld] buffers.
 struct Plan {
     int fs;             // slice width of the LDS kernels and the slab layout [slice][R][fs]; 0 = row kernels
     bool fused;         // fused forward and fused backward
@@ -36,8 +38,10 @@ struct Plan {
 };
 
 // train_step: the call is gmc_train_step_f32 (fused Adam; a one-graph batch may take the head into the backward)
-Plan plan(const gmc_batch *b, int F, float dropout_p, bool fuse, bool train_step) {
+Plan plan(const gmc_batch *b, int F, float dropout_p, bool fuse, bool train_step, bool dense = false) {
     Plan p{};
+    p.zparts = 1;
+    if (dense) return p;
     const bool dropout = dropout_p > 0.f;
     const GmcLdsGeom g = gmc_lds_geometry(b, F);
     bool lds = g.fits && !(g.ovf && (!fuse || dropout));
@@ -48,7 +52,6 @@ Plan plan(const gmc_batch *b, int F, float dropout_p, bool fuse, bool train_step
     }();
     if (forced_rows) lds = false;
 #endif
-    p.zparts = 1;
     if (!lds) return p;
     p.fs = g.fs;
     p.slices = g.slices;
@@ -78,7 +81,9 @@ unsigned long long dropout_seed(const gmc_model *m) { return ((unsigned long lon
 
 size_t align_up(size_t x) { return (x + 255) & ~(size_t)255; }
 
-Workspace carve(const gmc_batch *b, const gmc_model *m, int training, void *base, bool train_step = false) {
+// dense: the call is one of the *_features entry points (dW1 comes from a GEMM: no dW1 scratch)
+Workspace carve(const gmc_batch *b, const gmc_model *m, int training, void *base, bool train_step = false,
+                bool dense = false) {
     Workspace w{};
     size_t off = 0;
     auto take = [&](size_t floats) {
@@ -87,7 +92,7 @@ Workspace carve(const gmc_batch *b, const gmc_model *m, int training, void *base
         return p;
     };
     const size_t R = (size_t)b->R, F = (size_t)m->F;
-    w.plan = plan(b, m->F, m->dropout_p, fuse_enabled(), train_step);
+    w.plan = plan(b, m->F, m->dropout_p, fuse_enabled(), train_step, dense);
     const int fs = w.plan.fs;
     w.ld = (long)((F + 31) / 32 * 32);
     const size_t cols = fs ? (F + fs - 1) / fs * fs : (size_t)w.ld;
@@ -100,14 +105,15 @@ Workspace carve(const gmc_batch *b, const gmc_model *m, int training, void *base
         if (fs && (size_t)w.plan.chunks > tiles) tiles = (size_t)w.plan.chunks;
         w.part = take(tiles * F * 4);
         w.db2part = take((size_t)b->B * 3);
-        w.dw1part = take(gmc_dw1_scratch_floats(b, m->N, m->F, fs != 0));
+        w.dw1part = take(dense ? 0 : gmc_dw1_scratch_floats(b, m->N, m->F, fs != 0));
         if (dropout_on(m)) w.W2s = take(F * 3);
     }
     w.bytes = off;
     return w;
 }
 
-int check(const gmc_batch *b, const gmc_model *m) {
+// dense: features with their own N columns - a graph may then have more nodes than conv1.weight has rows
+int check(const gmc_batch *b, const gmc_model *m, bool dense = false) {
     if (!b || !m) return GMC_ERR_NULL;
     if (b->abi != GMC_VERSION || m->abi != GMC_VERSION) return GMC_ERR_ABI;   // built against another header
     if (!b->goff || !b->rowptr || !b->gcol || !b->lcol || !b->dinv) return GMC_ERR_NULL;
@@ -118,7 +124,7 @@ int check(const gmc_batch *b, const gmc_model *m) {
     if (!(m->dropout_p >= 0.f && m->dropout_p < 1.f)) return GMC_ERR_SHAPE;
     if (m->W1_slab && !gmc_aligned16(m->W1_slab)) return GMC_ERR_ALIGN;
     if (b->B > 0 && (b->n_max < 3 || b->n_max > GMC_MAX_GRAPH_NODES)) return GMC_ERR_GRAPH_SIZE;
-    if (b->n_max > m->N) return GMC_ERR_SHAPE;  // more nodes than rows of conv1.weight
+    if (!dense && b->n_max > m->N) return GMC_ERR_SHAPE;  // more nodes than rows of conv1.weight
     return GMC_OK;
 }
 
@@ -135,13 +141,17 @@ int aggregate(const gmc_batch *b, const Workspace &w, const float *X, float *Y, 
                            group_rows(b), W2, Z0, tag, st);
 }
 
-int forward_body(const gmc_batch *b, const gmc_model *m, const Workspace &w, hipStream_t st) {
+// X (optional, row kernel plan only): dense features [R, N] - layer 1's feature transform is a GEMM
+int forward_body(const gmc_batch *b, const gmc_model *m, const Workspace &w, hipStream_t st, const float *X = nullptr,
+                 long ldx = 0) {
     const int F = m->F;
     if (w.plan.fused)  // T0 lives only in LDS
         return gmc_fwd1_lds_launch(b, m->W1, m->b1, m->W2, w.H, w.Z0, F, st, m->W1_slab, m->N);
-    // layer 1 feature transform as a row gather of W1:  T0 = dinv o (A_val @ W1[:n])
+    // layer 1 feature transform:  T0 = dinv o (X @ W1), for X = the padded adjacency a row gather of W1:
+    // T0 = dinv o (A_val @ W1[:n])
     const int fs = w.plan.fs;
-    int rc = fs ? gmc_spmm_lds_launch(b, m->W1, F, 0, 1, 1, b->dinv, nullptr, 0, w.T0, w.ld, 1, F, nullptr,
+    int rc = X ? gmc_gemm_launch(0, 0, b->R, F, m->N, X, ldx, m->W1, F, b->dinv, w.T0, w.ld, st)
+             : fs ? gmc_spmm_lds_launch(b, m->W1, F, 0, 1, 1, b->dinv, nullptr, 0, w.T0, w.ld, 1, F, nullptr,
                                         nullptr, GMC_K_GATHER_W1, st)
                   : gmc_spmm_launch(b->rowptr, b->lcol, b->vals, b->dinv, m->W1, F, nullptr, 0, w.T0, w.ld,
                                     b->R, F, group_rows(b), nullptr, nullptr, GMC_K_GATHER_W1, st);
@@ -165,9 +175,11 @@ struct AdamFuse {  // optional Adam fused into the gradient fold (single GPU)
 };
 
 // loss_tail: per-graph losses whose sum goes to the slot after the gradient (GMC_MODEL_GRAD_TAIL), or nullptr
+// X (optional, row kernel plan only): the dense features of the forward - dW1 = X^T @ U, and dX = U @ W1^T when asked for
 int backward_body(const gmc_batch *b, const gmc_model *m, const Workspace &w, float *grad,
                   hipStream_t st, const AdamFuse *af = nullptr, const float *loss_tail = nullptr,
-                  const gmc_bwd1_head *head = nullptr) {
+                  const gmc_bwd1_head *head = nullptr, const float *X = nullptr, long ldx = 0, float *dX = nullptr,
+                  long lddx = 0) {
     const long F = m->F;
     float *dW1 = grad, *db1 = grad + (long)m->N * F, *dW2 = db1 + F, *db2 = dW2 + F * 3;
     float *Gs = w.T0, *U = w.H;
@@ -198,7 +210,12 @@ int backward_body(const gmc_batch *b, const gmc_model *m, const Workspace &w, fl
     // conv1 backward aggregation:  U = dinv o (A @ Gs)
     rc = aggregate(b, w, Gs, U, m->F, nullptr, 0, nullptr, nullptr, GMC_K_AGG_BWD, st);
     if (rc) return rc;
-    rc = gmc_dw1_launch(b, U, w.ld, dW1, w.dw1part, m->N, m->F, fs != 0, st);
+    if (X) {
+        rc = gmc_gemm_launch(1, 0, m->N, m->F, b->R, X, ldx, U, w.ld, nullptr, dW1, F, st);
+        if (!rc && dX) rc = gmc_gemm_launch(0, 1, b->R, m->N, m->F, U, w.ld, m->W1, F, nullptr, dX, lddx, st);
+    } else {
+        rc = gmc_dw1_launch(b, U, w.ld, dW1, w.dw1part, m->N, m->F, fs != 0, st);
+    }
     if (rc || !loss_tail) return rc;
     return gmc_loss_tail_launch(loss_tail, b->B, db2 + 3, st);
 }
@@ -427,4 +444,56 @@ extern "C" int gmc_backward_from_gp(const gmc_batch *batch, const gmc_model *mod
     rc = gmc_head_bwd_launch(batch, P, GP, w.GY2, w.db2part, st);
     if (rc) return rc;
     return backward_body(batch, model, w, grad, st);
+}
+
+// ---- features that are not the padded adjacency ------------------------------------------------------------------------
+namespace {
+int check_features(const gmc_batch *b, const gmc_model *m, const float *X, int64_t ldx) {
+    int rc = check(b, m, true);
+    if (rc) return rc;
+    if (ldx < m->N) return GMC_ERR_SHAPE;
+    if (!gmc_aligned16(X) || ldx % 4 || !gmc_aligned16(m->W1)) return GMC_ERR_ALIGN;   // (the GEMMs' operands)
+    return GMC_OK;
+}
+}  // namespace
+
+extern "C" size_t gmc_workspace_bytes_features(const gmc_batch *batch, const gmc_model *model, int training) {
+    if (!batch || !model) return 0;
+    return carve(batch, model, training, nullptr, false, true).bytes;
+}
+
+extern "C" int gmc_forward_features(const gmc_batch *batch, const gmc_model *model, const float *X, int64_t ldx,
+                                    float C, void *workspace, size_t workspace_bytes, float *P, int32_t *S,
+                                    float *loss, gmc_stream_t stream) {
+    if (!batch || !model || !X || !P || !workspace) return GMC_ERR_NULL;
+    int rc = check_features(batch, model, X, ldx);
+    if (rc) return rc;
+    Workspace w = carve(batch, model, 0, workspace, false, true);
+    if (w.bytes > workspace_bytes) return GMC_ERR_WORKSPACE;
+    if (batch->R == 0) return GMC_OK;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    rc = forward_body(batch, model, w, st, X, (long)ldx);
+    if (rc) return rc;
+    return gmc_head_f32(batch, w.Z0, w.plan.zparts, model->b2, C, P, S, loss, nullptr, nullptr, stream);
+}
+
+extern "C" int gmc_backward_features_from_gp(const gmc_batch *batch, const gmc_model *model, const float *X,
+                                             int64_t ldx, void *workspace, size_t workspace_bytes, const float *P,
+                                             const float *GP, float *grad, float *dX, int64_t lddx,
+                                             gmc_stream_t stream) {
+    if (!batch || !model || !X || !P || !GP || !workspace || !grad) return GMC_ERR_NULL;
+    int rc = check_features(batch, model, X, ldx);
+    if (rc) return rc;
+    if (dX && lddx < model->N) return GMC_ERR_SHAPE;
+    if (!gmc_aligned16(grad) || (dX && (!gmc_aligned16(dX) || lddx % 4))) return GMC_ERR_ALIGN;
+    Workspace w = carve(batch, model, 1, workspace, false, true);
+    if (w.bytes > workspace_bytes) return GMC_ERR_WORKSPACE;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (batch->R == 0) {
+        const size_t n = (size_t)model->N * model->F + model->F + (size_t)model->F * 3 + 3;
+        return (int)hipMemsetAsync(grad, 0, n * sizeof(float), st);
+    }
+    rc = gmc_head_bwd_launch(batch, P, GP, w.GY2, w.db2part, st);
+    if (rc) return rc;
+    return backward_body(batch, model, w, grad, st, nullptr, nullptr, nullptr, X, (long)ldx, dX, (long)lddx);
 }

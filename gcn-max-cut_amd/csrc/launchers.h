@@ -88,3 +88,8 @@ int gmc_dropout_launch(float *H, long R, int F, int fs, long ld, float p, unsign
 int gmc_hw2_rows_launch(const float *H, const float *dinv, const float *W2, float *Z0, long R, int F, int fs, long ld,
                         hipStream_t st);
 int gmc_scale_copy_launch(const float *src, float *dst, int n, float s, hipStream_t st);
+
+// ---- dense fp32 GEMM on the matrix cores (gemm_mfma.hip) ------------------------------------------------------------
+// C[M,Nc] = scale o (op(A) @ op(B)), ta / tb: the operand is stored transposed; internal form of gmc_gemm_f32
+int gmc_gemm_launch(int ta, int tb, int M, int Nc, int K, const float *A, long lda, const float *B, long ldb,
+                    const float *scale, float *C, long ldc, hipStream_t st);

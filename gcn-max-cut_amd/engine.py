@@ -245,6 +245,58 @@ class FusedEngine:
         hip.check(rc, "gmc_backward_from_gp")
         return self.views(self.grad)
 
+    # ---- features that are not the padded adjacency (layer 1 is a dense GEMM: gmc_forward_features)
+    def workspace_bytes_features(self, batch: GraphBatch, training: bool) -> int:
+        return max(256, int(self.lib.gmc_workspace_bytes_features(batch.ref(), C.byref(self._model), int(training))))
+
+    def pad_features(self, batch: GraphBatch, X: torch.Tensor) -> torch.Tensor:
+        """``X`` [R, N] as the library takes it: fp32 on the device, 16-byte aligned rows - the columns padded with
+        zeros to a multiple of 4 when N is not one.  A tensor this method returned passes through unchanged, so a
+        caller that runs forward and backward on the same features pads them once."""
+        ld = (self.N + 3) // 4 * 4
+        if X.dim() != 2 or X.shape[0] != batch.R or X.shape[1] not in (self.N, ld):
+            raise ValueError(f"features must be [{batch.R}, {self.N}], got {tuple(X.shape)}")
+        X = X.detach().to(self.device, torch.float32)
+        if X.shape[1] != ld:
+            Xp = torch.zeros((batch.R, ld), dtype=torch.float32, device=self.device)
+            Xp[:, :self.N] = X
+            return Xp
+        X = X.contiguous()
+        return X.clone() if X.data_ptr() % 16 else X
+
+    def forward_features(self, batch: GraphBatch, X: torch.Tensor, C_: float = 1.0, want_loss: bool = False,
+                         ws: Optional[torch.Tensor] = None):
+        """:meth:`forward` for node features ``X`` [R, N] that are not the padded adjacency (the rows of the batch's
+        graphs stacked): the layer-1 feature transform is the library's fp32 MFMA GEMM.  ``ws``: caller-owned scratch
+        of :meth:`workspace_bytes_features` bytes (kept alive for :meth:`backward_features_from_gp`)."""
+        P = torch.empty((batch.R, 3), dtype=torch.float32, device=self.device)
+        S = torch.empty(batch.R, dtype=torch.int32, device=self.device) if want_loss else None
+        loss = torch.empty(batch.B, dtype=torch.float32, device=self.device) if want_loss else None
+        Xd = self.pad_features(batch, X)
+        if batch.B == 0:
+            return P, S, loss
+        if ws is None:
+            ws = torch.empty(self.workspace_bytes_features(batch, False), dtype=torch.uint8, device=self.device)
+        rc = self.lib.gmc_forward_features(batch.ref(), C.byref(self._model), hip.ptr(Xd), Xd.shape[1], C_, hip.ptr(ws),
+                                           ws.numel(), hip.ptr(P), hip.ptr(S), hip.ptr(loss), hip.stream())
+        hip.check(rc, "gmc_forward_features")
+        return P, S, loss
+
+    def backward_features_from_gp(self, batch: GraphBatch, X: torch.Tensor, P: torch.Tensor, GP: torch.Tensor,
+                                  ws: torch.Tensor, want_dx: bool = True):
+        """(parameter gradients, dX or None) for a caller-supplied dLoss/dP; ``ws``: the training-sized scratch of the
+        :meth:`forward_features` call that produced ``P`` from the same ``X``.  ``want_dx`` = False skips the dX GEMM."""
+        Xd = self.pad_features(batch, X)
+        dX = torch.empty_like(Xd) if want_dx else None
+        if batch.B == 0:
+            self.grad[:self.count].zero_()
+            return self.views(self.grad), (dX[:, :self.N] if want_dx else None)
+        rc = self.lib.gmc_backward_features_from_gp(
+            batch.ref(), C.byref(self._model), hip.ptr(Xd), Xd.shape[1], hip.ptr(ws), ws.numel(), hip.ptr(P),
+            hip.ptr(GP.to(torch.float32).contiguous()), hip.ptr(self.grad), hip.ptr(dX), Xd.shape[1], hip.stream())
+        hip.check(rc, "gmc_backward_features_from_gp")
+        return self.views(self.grad), (dX[:, :self.N] if want_dx else None)
+
     def adam_step(self, lr: float, betas=(0.9, 0.999), eps: float = 1e-8) -> None:
         """torch.optim.Adam.step over the flat buffer (TrainingNeural.py:386)."""
         self.step_count += 1

@@ -23,6 +23,7 @@ SYMBOLS = (
     "gmc_adam_devstep_model_f32", "gmc_w1_slab_floats", "gmc_w1_slab_f32", "gmc_host_device_pointer", "gmc_publish_f32",
     "gmc_publish_adam_devstep_model_f32", "gmc_probe_flavours", "gmc_lds_flavours", "gmc_refine_order_host",
     "gmc_refine_local_f32", "gmc_refine_anneal_f32", "gmc_refine_anneal_staged",
+    "gmc_gemm_f32", "gmc_workspace_bytes_features", "gmc_forward_features", "gmc_backward_features_from_gp",
 )
 
 MAX_GRAPH_NODES = 4096
@@ -97,6 +98,12 @@ def _declare(lib: C.CDLL) -> None:
     lib.gmc_refine_anneal_f32.argtypes = [C.POINTER(GmcBatch), vp, vp, vp, i32, vp, vp, i32, vp, C.c_uint64, i32,
                                           vp, vp, vp, vp, vp, vp, vp]
     lib.gmc_refine_anneal_staged.argtypes = [C.POINTER(GmcBatch)]
+    lib.gmc_gemm_f32.argtypes = [i32, i32, i32, i32, i32, vp, i64, vp, i64, vp, vp, i64, vp]
+    lib.gmc_workspace_bytes_features.restype = sz
+    lib.gmc_workspace_bytes_features.argtypes = [C.POINTER(GmcBatch), C.POINTER(GmcModel), C.c_int]
+    lib.gmc_forward_features.argtypes = [C.POINTER(GmcBatch), C.POINTER(GmcModel), vp, i64, f32, vp, sz, vp, vp, vp, vp]
+    lib.gmc_backward_features_from_gp.argtypes = [C.POINTER(GmcBatch), C.POINTER(GmcModel), vp, i64, vp, sz, vp, vp,
+                                                  vp, vp, i64, vp]
     lib.gmc_probe_begin.argtypes = [i32]
     lib.gmc_probe_end.argtypes = [vp, vp, i32]
     lib.gmc_probe_flavours.argtypes = [vp, i32]
@@ -109,7 +116,8 @@ def _declare(lib: C.CDLL) -> None:
     lib.gmc_debug_set_device_cus.restype = C.c_int
     for name in SYMBOLS:
         fn = getattr(lib, name)
-        if name not in ("gmc_version", "gmc_error_string", "gmc_workspace_bytes", "gmc_w1_slab_floats"):
+        if name not in ("gmc_version", "gmc_error_string", "gmc_workspace_bytes", "gmc_w1_slab_floats",
+                        "gmc_workspace_bytes_features"):
             fn.restype = C.c_int
 
 
@@ -182,6 +190,8 @@ def stream() -> int:
 KERNEL_TAGS = ("gather_w1", "agg_fwd", "head", "hidden_bwd", "colsum", "agg_bwd", "dw1", "dw1_fold",
                "adam", "spmm_user", "dense_mfma", "bwd1_fused", "fwd1_fused", "decode", "finish",
                "refine", "anneal")
+# the tags after those (GMC_K_GEMM = 17 on): what Probe names a record by
+PROBE_TAGS = KERNEL_TAGS + ("gemm",)
 
 
 FLAVOUR_KERNELS = {1: "fwd1_lds", 2: "bwd1_lds", 3: "bwd1_reg", 4: "spmm_lds", 5: "dw1_lds"}   # GMC_FLV_KERNEL
@@ -222,7 +232,7 @@ class Probe:
         n = load().gmc_probe_end(tags, ms, self.capacity)
         if n < 0:
             raise RuntimeError(f"gmc_probe_end failed ({n})")
-        self.records = [(KERNEL_TAGS[tags[i]], float(ms[i])) for i in range(min(n, self.capacity))]
+        self.records = [(PROBE_TAGS[tags[i]], float(ms[i])) for i in range(min(n, self.capacity))]
         words = (C.c_int32 * self.capacity)()
         m = load().gmc_probe_flavours(words, self.capacity)
         if m != n:

@@ -167,7 +167,8 @@ enum {
     GMC_K_FINISH = 14,     /* fold of the gradient partials (+ fused Adam) over the flat buffer */
     GMC_K_REFINE = 15,     /* local search over decoded candidates + cut count (gmc_refine_local_f32) */
     GMC_K_ANNEAL = 16,     /* annealing + descent over decoded candidates + cut count (gmc_refine_anneal_f32) */
-    GMC_K_COUNT = 17
+    GMC_K_GEMM = 17,       /* dense fp32 GEMM on the matrix cores (gmc_gemm_f32; the dense-feature path) */
+    GMC_K_COUNT = 18
 };
 
 /* Timing probe for bench.py: between gmc_probe_begin and gmc_probe_end every kernel launch
@@ -237,6 +238,16 @@ int gmc_spmm_f32(const int32_t *rowptr, const int32_t *col, const float *vals,
  * Stand-alone form of the only dense contraction on the path (TrainingNeural.py:83). */
 int gmc_dense_hw2_f32(const float *H, int64_t ldh, const float *dinv, const float *W2,
                       float *Z0, int32_t n_rows, int32_t F, gmc_stream_t stream);
+
+/* C[M,Nc] = scale o (op(A) @ op(B)) in exact fp32 on the matrix cores (v_mfma_f32_16x16x4_f32); ta / tb: 0 = the
+ * operand as stored (A [M,K], B [K,Nc]), 1 = stored transposed (A [K,M], B [Nc,K]); all row-major with leading
+ * dimensions; scale [M] or NULL.  The forms NN, TN and NT exist (ta = tb = 1: GMC_ERR_UNSUPPORTED) - the three dense
+ * products of GraphConv layer 1 with features that are not the padded adjacency (TrainingNeural.py:80 and its
+ * backward): T0 = dinv o (X @ W1), dW1 = X^T @ U, dX = U @ W1^T.  Any M, Nc, K >= 0 (M or Nc == 0 launches nothing);
+ * A, B, C 16-byte aligned and lda, ldb, ldc multiples of 4, else GMC_ERR_ALIGN.  k is summed in ascending order by one
+ * workgroup per 64 x 64 output tile: no atomics, bitwise reproducible. */
+int gmc_gemm_f32(int32_t ta, int32_t tb, int32_t M, int32_t Nc, int32_t K, const float *A, int64_t lda,
+                 const float *B, int64_t ldb, const float *scale, float *C, int64_t ldc, gmc_stream_t stream);
 
 /* Per-graph head: Z = dinv * (A @ Z0) + b2, P = softmax(Z) (TrainingNeural.py:83-84);
  * rows 0,1,2 forced to e0,e1,e2 and S = row-argmax, first max wins (:87-106);
@@ -333,6 +344,31 @@ int gmc_train_step_f32(const gmc_batch *batch, int32_t N, int32_t F, float *para
 int gmc_backward_from_gp(const gmc_batch *batch, const gmc_model *model, void *workspace,
                          size_t workspace_bytes, const float *P, const float *GP, float *grad,
                          gmc_stream_t stream);
+
+/* ---- features that are not the padded adjacency (learned node embeddings: net(g, embed.weight)) --------------------
+ *
+ * X [R, N] (leading dimension ldx >= N, a multiple of 4; 16-byte aligned): the feature rows of the batch's graphs
+ * stacked in batch row order, N = model->N.  Layer 1's feature transform is then a dense GEMM (gmc_gemm_f32) instead of
+ * the row gather of W1, and layer 1 ignores batch->vals (DGL's aggregation is structure-only; only the head's cut reads
+ * edge weights).  Everything else is the one-kernel-per-operation sequence on row-major [R, F] buffers, dropout
+ * (model->dropout_p) included.  A graph may have more nodes than N here.  Workspace: gmc_workspace_bytes_features
+ * (NOT gmc_workspace_bytes: the two plans differ). */
+size_t gmc_workspace_bytes_features(const gmc_batch *batch, const gmc_model *model, int training);
+
+/* GCNSoftmax.forward(g, X) for every graph of the batch (TrainingNeural.py:79-85); S / loss as for gmc_forward.
+ * Errors, all found before any HIP call: a NULL required pointer GMC_ERR_NULL, the structs' abi GMC_ERR_ABI, sizes
+ * (ldx < N included) GMC_ERR_SHAPE, X or ldx GMC_ERR_ALIGN, GMC_ERR_WORKSPACE.  R == 0 launches nothing. */
+int gmc_forward_features(const gmc_batch *batch, const gmc_model *model, const float *X, int64_t ldx, float C,
+                         void *workspace, size_t workspace_bytes, float *P, int32_t *S, float *loss,
+                         gmc_stream_t stream);
+
+/* Backward of gmc_forward_features for a caller-supplied dLoss/dP: grad as for gmc_backward_from_gp (dW1 = X^T @ U is
+ * written straight into it), dX [R, N] (leading dimension lddx, as ldx; NULL: not computed) = U @ W1^T.  Requires the
+ * (training-sized) workspace, the X and the dropout (p, seed) of the gmc_forward_features call that produced P.
+ * R == 0 launches nothing but the zeroing of grad. */
+int gmc_backward_features_from_gp(const gmc_batch *batch, const gmc_model *model, const float *X, int64_t ldx,
+                                  void *workspace, size_t workspace_bytes, const float *P, const float *GP,
+                                  float *grad, float *dX, int64_t lddx, gmc_stream_t stream);
 
 /* ---- decode / post-processing (the caller of the path in BASELINE configs[4]) -------- */
 
