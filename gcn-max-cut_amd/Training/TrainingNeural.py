@@ -13,7 +13,9 @@ the loss pads to a hard-coded 1000 (Q2), the "best" state aliases the live param
 names (Q9).  Extension (keyword-only / environment, default off): ``graphs_per_step`` > 1
 switches to batched steps (one Adam step per batch of graphs, summed loss), and when
 ``torch.distributed`` is initialised each rank trains on its shard of every batch with one
-RCCL all-reduce of the flat gradient per step.
+RCCL all-reduce of the flat gradient per step.  ``loss="expected_cut"`` (or GCN_MAXCUT_LOSS=expected_cut) trains on
+the relaxed loss - ``compute_loss`` of ``override_fixed_nodes(P)`` without the one-hot step, the expected cut of
+independent rounding - instead of the reference's hard one; :func:`cut_loss` is either loss as a differentiable op.
 """
 from __future__ import annotations
 
@@ -34,7 +36,7 @@ import torch.nn.functional as F  # noqa: F401
 
 from .. import hip
 from ..commons import open_file, save_object  # noqa: F401
-from ..engine import PARAM_ORDER, FusedEngine, dp_active, shard_by_weight, shard_for_rank  # noqa: F401
+from ..engine import PARAM_ORDER, FusedEngine, device_cut_loss, dp_active, shard_by_weight, shard_for_rank  # noqa: F401
 from ..graph import GraphBatch, GraphHandle
 
 TORCH_DEVICE = torch.device('cuda' if torch.cuda.is_available() else 'cpu')
@@ -241,6 +243,38 @@ def graph_batch_of(g: GraphHandle, inputs, device) -> GraphBatch:
     return b
 
 
+# --------------------------------------------------------------------------- the loss on the device
+class _CutLoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, P, batch, C, loss):
+        losses, GP = device_cut_loss(batch, P, C, loss)
+        ctx.save_for_backward(GP)
+        ctx.like = (P.device, P.dtype)
+        return losses.sum().to(*ctx.like)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        (GP,) = ctx.saved_tensors
+        return (grad_out.to(GP.device, GP.dtype) * GP).to(*ctx.like), None, None, None
+
+
+def cut_loss(g, P, C: float = 1.0, relaxed: bool = False):
+    """The scalar loss of probabilities ``P`` [n,3] on graph ``g`` (a GraphHandle with its own edge weights, or a
+    GraphBatch with ``P`` [R,3]: then the sum over its graphs), computed and differentiated on the device in O(edges)
+    (``gmc_cut_loss_f32``).  With ``A_pad`` the graph's padded adjacency it equals, in value and in ``dLoss/dP``,
+
+    * ``relaxed=False``: ``compute_loss(apply_max_to_one_hot(override_fixed_nodes(P)), A_pad, C=C)`` - the reference's
+      hard loss, ``-C * cut`` of the argmax decode with the straight-through gradient ``C * A_val @ onehot(S)``;
+    * ``relaxed=True``: ``compute_loss(override_fixed_nodes(P), A_pad, C=C)`` - the expected cut under independent
+      rounding, ``-C/2 * sum_uv w_uv (1 - Pt_u . Pt_v)`` with gradient ``C * A_val @ Pt``.
+
+    Forward keeps ``GP = dLoss/dP``; backward returns ``grad_out * GP``.  So
+    ``cut_loss(g, net(g, embed.weight), relaxed=True).backward()`` trains through the HIP forward and backward."""
+    dev = hip.require_gpu()
+    batch = g if isinstance(g, GraphBatch) else graph_batch_of(g, None, dev)
+    return _CutLoss.apply(P, batch, float(C), "expected_cut" if relaxed else "cut")
+
+
 # --------------------------------------------------------------------------- loss helpers (torch ops)
 def override_fixed_nodes(h):
     """Rows 0,1,2 <- e0,e1,e2 with straight-through gradient (TrainingNeural.py:87-94)."""
@@ -406,8 +440,12 @@ class FusedTrainer:
     (so ``optimizer.state_dict()`` has the reference's layout)."""
 
     def __init__(self, net: GCNSoftmax, optimizer, config: TrainingConfig, graphs_per_step: int = 1,
-                 local_shard: bool = False, engine=None):
+                 local_shard: bool = False, engine=None, loss: Optional[str] = None):
         self.net, self.optimizer, self.config = net, optimizer, config
+        # "cut" (the reference's hard loss) or "expected_cut" (the relaxed one); None: GCN_MAXCUT_LOSS.  Every launch
+        # path takes it; an engine is handed the keyword only when it is not the default (stand-ins without it work)
+        self.loss = hip.loss_name(loss)
+        self._loss_kw = {} if self.loss == "cut" else {"loss": self.loss}
         self.eng = engine if engine is not None else net.engine()
         self.graphs_per_step = graphs_per_step
         # local_shard: `dataset` already is this rank's shard (graphs_per_step of ITS graphs per
@@ -568,7 +606,8 @@ class FusedTrainer:
             if batch.B == 0:
                 eng.grad[:eng.count + 1].zero_()
             else:
-                eng.train_fwd_bwd(batch, cfg.C, out=(self._out[0], self._out[1], self._loss_slots[i]), ws=self._ws)
+                eng.train_fwd_bwd(batch, cfg.C, out=(self._out[0], self._out[1], self._loss_slots[i]), ws=self._ws,
+                                  **self._loss_kw)
             if self.dp:
                 eng.allreduce_grad()
             self._step_loss[i:i + 1].copy_(tail)
@@ -618,7 +657,8 @@ class FusedTrainer:
         row_bytes = self._loss_slots.shape[1] * 4
         for i, batch in enumerate(self._batches):
             eng.train_step(batch, lr, cfg.C, out=(self._out[0], self._out[1], self._loss_slots[i]), betas=betas, eps=eps,
-                           ws=self._ws, slab=True, loss_ptr=loss_dev + i * row_bytes if loss_dev else None)
+                           ws=self._ws, slab=True, loss_ptr=loss_dev + i * row_bytes if loss_dev else None,
+                           **self._loss_kw)
 
     def _run_dp(self, graphs: bool) -> None:
         """Shard step, ONE RCCL all-reduce of [gradient | loss], Adam.  The step's loss rides in the all-reduce (the
@@ -645,9 +685,9 @@ class FusedTrainer:
                 fwd_bwd[i].replay()                   # forward + loss + backward + gradient fold of my shard
             elif self._hip:
                 eng.train_fwd_bwd(batch, cfg.C, out=(self._out[0], self._out[1], self._loss_slots[i]), ws=self._ws,
-                                  slab=True)
+                                  slab=True, **self._loss_kw)
             else:
-                eng.train_fwd_bwd(batch, cfg.C, out=(self._out[0], self._out[1], self._loss_slots[i]))
+                eng.train_fwd_bwd(batch, cfg.C, out=(self._out[0], self._out[1], self._loss_slots[i]), **self._loss_kw)
             eng.allreduce_grad()                      # ONE RCCL all-reduce of [gradient | loss] per step, eager
             if not publish and i != last:             # (the last step's slot is read in place: _step_losses)
                 self._step_loss[i:i + 1].copy_(tail)
@@ -677,10 +717,10 @@ class FusedTrainer:
                 fb.append(None)
                 continue
             out = (self._out[0], self._out[1], self._loss_slots[i])
-            eng.train_fwd_bwd(batch, cfg.C, out=out, ws=self._ws, slab=True)     # eager once: warms the kernels
+            eng.train_fwd_bwd(batch, cfg.C, out=out, ws=self._ws, slab=True, **self._loss_kw)   # eager once: warms the kernels
             g = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g):
-                eng.train_fwd_bwd(batch, cfg.C, out=out, ws=self._ws, slab=True)
+                eng.train_fwd_bwd(batch, cfg.C, out=out, ws=self._ws, slab=True, **self._loss_kw)
             fb.append(g)
         before, flat, m, v = eng.step_count, eng.flat.clone(), eng.m.clone(), eng.v.clone()
         eng.sync_step_dev()
@@ -777,11 +817,13 @@ class FusedTrainer:
                 'exp_avg': mv[k], 'exp_avg_sq': vv[k]}
 
 
-def _trainer_for(net, optimizer, config, graphs_per_step: Optional[int] = None) -> FusedTrainer:
+def _trainer_for(net, optimizer, config, graphs_per_step: Optional[int] = None,
+                 loss: Optional[str] = None) -> FusedTrainer:
     gps = _graphs_per_step(graphs_per_step)
+    loss = hip.loss_name(loss)   # (None: GCN_MAXCUT_LOSS, default "cut"; a bad name raises ValueError)
     tr = getattr(net, "_fused_trainer", None)
-    if tr is None or tr.optimizer is not optimizer or tr.graphs_per_step != gps:
-        tr = FusedTrainer(net, optimizer, config, gps)
+    if tr is None or tr.optimizer is not optimizer or tr.graphs_per_step != gps or tr.loss != loss:
+        tr = FusedTrainer(net, optimizer, config, gps, loss=loss)
         net._fused_trainer = tr
     tr.config = config
     return tr
@@ -789,12 +831,13 @@ def _trainer_for(net, optimizer, config, graphs_per_step: Optional[int] = None) 
 
 def train_single_epoch(dataset: Dict, net, optimizer, embed, config: TrainingConfig,
                        dataset_files: Optional[List[str]] = None, *,
-                       graphs_per_step: Optional[int] = None) -> float:
+                       graphs_per_step: Optional[int] = None, loss: Optional[str] = None) -> float:
     """One epoch, cumulative loss (TrainingNeural.py:341-390).  The device batches planned for ``dataset`` are
     kept from epoch to epoch while it looks unchanged (:meth:`FusedTrainer.prepare` says how that is decided);
-    after editing a large dataset dict in place call ``net._fused_trainer.invalidate()``."""
+    after editing a large dataset dict in place call ``net._fused_trainer.invalidate()``.  ``loss``: ``"cut"`` (the
+    reference's), ``"expected_cut"`` (the relaxed loss) or None = the environment's GCN_MAXCUT_LOSS (default cut)."""
     net.train()
-    trainer = _trainer_for(net, optimizer, config, graphs_per_step)
+    trainer = _trainer_for(net, optimizer, config, graphs_per_step, loss)
     if dataset_files is None:
         dataset_files = ['./nx_test_generated_graph_n200_300_d8_12_t500.pkl']
     cumulative_loss = 0.0
@@ -819,9 +862,11 @@ def _checkpoint(net, optimizer, embed, epoch, loss_history, config) -> Dict:
 
 
 def train_model(dataset: Dict, config: TrainingConfig, dataset_files: Optional[List[str]] = None, *,
-                graphs_per_step: Optional[int] = None) -> Tuple:
+                graphs_per_step: Optional[int] = None, loss: Optional[str] = None) -> Tuple:
     """Main training function (TrainingNeural.py:392-484):
-    returns ``(model, best_loss, final_epoch, embedding_weights, loss_history)``."""
+    returns ``(model, best_loss, final_epoch, embedding_weights, loss_history)``.  ``loss``: as for
+    :func:`train_single_epoch`."""
+    loss = hip.loss_name(loss)
     say = print if _rank0() else (lambda *a, **k: None)
     say(f"Starting training with {config.number_epochs} epochs")
     say(f"Model: {config.n_nodes} nodes, {config.number_classes} classes")
@@ -836,7 +881,7 @@ def train_model(dataset: Dict, config: TrainingConfig, dataset_files: Optional[L
 
     for epoch in range(config.number_epochs):
         cumulative_loss = train_single_epoch(dataset, net, optimizer, embed, config, dataset_files,
-                                             graphs_per_step=graphs_per_step)
+                                             graphs_per_step=graphs_per_step, loss=loss)
         loss_history.append(cumulative_loss)
 
         stalled = cumulative_loss > prev_loss or abs(prev_loss - cumulative_loss) <= config.tolerance
@@ -876,10 +921,11 @@ def train_model(dataset: Dict, config: TrainingConfig, dataset_files: Optional[L
 def train_from_pickle(dataset_filename: str, model_name: str, n_nodes: int = 1000, **kwargs) -> Tuple:
     """Train from a dataset pickle (TrainingNeural.py:486-513)."""
     graphs_per_step = kwargs.pop('graphs_per_step', None)
+    loss = kwargs.pop('loss', None)
     config = TrainingConfig(**{'n_nodes': n_nodes, 'save_directory': f'{model_name}.pth', **kwargs})
     print(f"Loading dataset from {dataset_filename}")
     dataset = open_file(dataset_filename)
-    return train_model(dataset, config, graphs_per_step=graphs_per_step)
+    return train_model(dataset, config, graphs_per_step=graphs_per_step, loss=loss)
 
 
 def train_multi_class(dataset_filename: str, model_name: str, num_classes: int = 3, **kwargs) -> Tuple:
@@ -888,9 +934,11 @@ def train_multi_class(dataset_filename: str, model_name: str, num_classes: int =
     return train_from_pickle(dataset_filename, model_name, **params)
 
 
-def evaluate_model(model, dataset: Dict, config: TrainingConfig) -> Dict:
+def evaluate_model(model, dataset: Dict, config: TrainingConfig, *, loss: Optional[str] = None) -> Dict:
     """Average / total loss over a dataset (TrainingNeural.py:537-570): forward, terminal
-    override, argmax decode and cut loss for all graphs in one fused launch sequence."""
+    override, argmax decode and cut loss for all graphs in one fused launch sequence.  ``loss``: as for
+    :func:`train_single_epoch` (``"expected_cut"``: the relaxed loss of the same probabilities)."""
+    loss_kw = {} if hip.loss_name(loss) == "cut" else {"loss": hip.loss_name(loss)}
     model.eval()
     items = list(dataset.values())
     if not items:
@@ -899,9 +947,9 @@ def evaluate_model(model, dataset: Dict, config: TrainingConfig) -> Dict:
     handles = [it[0] for it in items]
     vals = [h.edge_values(it[1]) for h, it in zip(handles, items)]
     batch = GraphBatch(handles, vals, eng.device)
-    _, _, loss = eng.forward(batch, config.C, want_loss=True)
+    _, _, losses = eng.forward(batch, config.C, want_loss=True, **loss_kw)
     total = 0.0
-    for value in loss.cpu().tolist():
+    for value in losses.cpu().tolist():
         total += value
     return {'average_loss': total / len(items), 'total_loss': total, 'num_samples': len(items)}
 

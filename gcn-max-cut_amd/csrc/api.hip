@@ -38,7 +38,9 @@ struct Plan {
 };
 
 // train_step: the call is gmc_train_step_f32 (fused Adam; a one-graph batch may take the head into the backward)
-Plan plan(const gmc_batch *b, int F, float dropout_p, bool fuse, bool train_step, bool dense = false) {
+// hard_loss: GMC_LOSS_CUT - the only loss the head inside the backward launch computes
+Plan plan(const gmc_batch *b, int F, float dropout_p, bool fuse, bool train_step, bool dense = false,
+          bool hard_loss = true) {
     Plan p{};
     p.zparts = 1;
     if (dense) return p;
@@ -58,7 +60,7 @@ Plan plan(const gmc_batch *b, int F, float dropout_p, bool fuse, bool train_step
     p.chunks = gmc_dw1_chunks(b->B, true, g.slices);
     p.fused = fuse && !dropout;
     if (!dropout) p.zparts = gmc_lds_groups(b, F);   // (dropout: Z0 comes from its own kernel)
-    p.head_in_bwd = train_step && p.fused && p.chunks == 1 && gmc_bwd1_takes_head(b);
+    p.head_in_bwd = train_step && hard_loss && p.fused && p.chunks == 1 && gmc_bwd1_takes_head(b);
     return p;
 }
 
@@ -77,6 +79,7 @@ struct Workspace {
 };
 
 bool dropout_on(const gmc_model *m) { return m->dropout_p > 0.f; }
+int loss_kind_of(const gmc_model *m) { return (m->flags & GMC_MODEL_LOSS_EXPECTED) ? GMC_LOSS_EXPECTED_CUT : GMC_LOSS_CUT; }
 unsigned long long dropout_seed(const gmc_model *m) { return ((unsigned long long)m->dropout_seed_hi << 32) | m->dropout_seed_lo; }
 
 size_t align_up(size_t x) { return (x + 255) & ~(size_t)255; }
@@ -92,7 +95,7 @@ Workspace carve(const gmc_batch *b, const gmc_model *m, int training, void *base
         return p;
     };
     const size_t R = (size_t)b->R, F = (size_t)m->F;
-    w.plan = plan(b, m->F, m->dropout_p, fuse_enabled(), train_step, dense);
+    w.plan = plan(b, m->F, m->dropout_p, fuse_enabled(), train_step, dense, loss_kind_of(m) == GMC_LOSS_CUT);
     const int fs = w.plan.fs;
     w.ld = (long)((F + 31) / 32 * 32);
     const size_t cols = fs ? (F + fs - 1) / fs * fs : (size_t)w.ld;
@@ -334,6 +337,7 @@ extern "C" const char *gmc_error_string(int code) {
         case GMC_ERR_WORKSPACE: return "workspace too small";
         case GMC_ERR_GRAPH_SIZE: return "graph has fewer than 3 or more than GMC_MAX_GRAPH_NODES nodes";
         case GMC_ERR_UNSUPPORTED: return "unsupported shape (the hidden width F must be a multiple of 4 and <= 4096 = GMC_MAX_HIDDEN)";
+        case GMC_ERR_LOSS: return "unknown loss kind (GMC_LOSS_CUT = 0, GMC_LOSS_EXPECTED_CUT = 1)";
         case GMC_ERR_ABI: return "gmc_batch.abi / gmc_model.abi differs from the library's GMC_VERSION: rebuild the caller against this include/gcnmaxcut.h";
         default: return code > 0 ? hipGetErrorString((hipError_t)code) : "unknown gmc error";
     }
@@ -363,7 +367,8 @@ extern "C" int gmc_forward(const gmc_batch *batch, const gmc_model *model, float
     hipStream_t st = static_cast<hipStream_t>(stream);
     rc = forward_body(batch, model, w, st);
     if (rc) return rc;
-    return gmc_head_f32(batch, w.Z0, w.plan.zparts, model->b2, C, P, S, loss, nullptr, nullptr, stream);
+    return gmc_head_launch(batch, w.Z0, w.plan.zparts, model->b2, C, P, S, loss, nullptr, nullptr, nullptr, st,
+                           loss_kind_of(model));
 }
 
 extern "C" int gmc_train_fwd_bwd(const gmc_batch *batch, const gmc_model *model, float C,
@@ -384,7 +389,8 @@ extern "C" int gmc_train_fwd_bwd(const gmc_batch *batch, const gmc_model *model,
     }
     rc = forward_body(batch, model, w, st);
     if (rc) return rc;
-    rc = gmc_head_f32(batch, w.Z0, w.plan.zparts, model->b2, C, P, S, loss, w.GY2, w.db2part, stream);
+    rc = gmc_head_launch(batch, w.Z0, w.plan.zparts, model->b2, C, P, S, loss, w.GY2, w.db2part, nullptr, st,
+                         loss_kind_of(model));
     if (rc) return rc;
     return backward_body(batch, model, w, grad, st, nullptr, tail ? loss : nullptr);
 }
@@ -393,10 +399,21 @@ extern "C" int gmc_train_step_f32(const gmc_batch *batch, int32_t N, int32_t F, 
                                   void *workspace, size_t workspace_bytes, float *P, int32_t *S, float *loss,
                                   float *grad, float *mom, float *var, double lr, double beta1, double beta2,
                                   double eps, int32_t *step_counter, float *w1_slab, gmc_stream_t stream) {
+    return gmc_train_step_loss_f32(batch, N, F, param, C, GMC_LOSS_CUT, workspace, workspace_bytes, P, S, loss, grad,
+                                   mom, var, lr, beta1, beta2, eps, step_counter, w1_slab, stream);
+}
+
+extern "C" int gmc_train_step_loss_f32(const gmc_batch *batch, int32_t N, int32_t F, float *param, float C,
+                                       int32_t loss_kind, void *workspace, size_t workspace_bytes, float *P,
+                                       int32_t *S, float *loss, float *grad, float *mom, float *var, double lr,
+                                       double beta1, double beta2, double eps, int32_t *step_counter,
+                                       float *w1_slab, gmc_stream_t stream) {
+    if (!gmc_loss_kind_ok(loss_kind)) return GMC_ERR_LOSS;
     if (!param || !grad || !mom || !var || !step_counter) return GMC_ERR_NULL;
     if (!gmc_aligned16(param) || !gmc_aligned16(mom) || !gmc_aligned16(var)) return GMC_ERR_ALIGN;
     const long nW1 = (long)N * F;
-    gmc_model model{GMC_VERSION, N, F, 3, 0, param, param + nW1, param + nW1 + F, param + nW1 + F + (long)F * 3, 0.f, 0u, 0u, w1_slab};
+    const int flags = loss_kind == GMC_LOSS_EXPECTED_CUT ? GMC_MODEL_LOSS_EXPECTED : 0;
+    gmc_model model{GMC_VERSION, N, F, 3, flags, param, param + nW1, param + nW1 + F, param + nW1 + F + (long)F * 3, 0.f, 0u, 0u, w1_slab};
     int rc = check(batch, &model);
     if (rc) return rc;
     if (!P || !workspace) return GMC_ERR_NULL;
@@ -416,7 +433,8 @@ extern "C" int gmc_train_step_f32(const gmc_batch *batch, int32_t N, int32_t F, 
     // The head (launch) advances the step counter for the fused Adam of the finish kernel.
     const bool head_in_bwd = w.plan.head_in_bwd;
     if (!head_in_bwd) {
-        rc = gmc_head_launch(batch, w.Z0, w.plan.zparts, model.b2, C, P, S, loss, w.GY2, w.db2part, step_counter, st);
+        rc = gmc_head_launch(batch, w.Z0, w.plan.zparts, model.b2, C, P, S, loss, w.GY2, w.db2part, step_counter, st,
+                             loss_kind);
         if (rc) return rc;
     }
     AdamFuse af;
@@ -474,7 +492,8 @@ extern "C" int gmc_forward_features(const gmc_batch *batch, const gmc_model *mod
     hipStream_t st = static_cast<hipStream_t>(stream);
     rc = forward_body(batch, model, w, st, X, (long)ldx);
     if (rc) return rc;
-    return gmc_head_f32(batch, w.Z0, w.plan.zparts, model->b2, C, P, S, loss, nullptr, nullptr, stream);
+    return gmc_head_launch(batch, w.Z0, w.plan.zparts, model->b2, C, P, S, loss, nullptr, nullptr, nullptr, st,
+                           loss_kind_of(model));
 }
 
 extern "C" int gmc_backward_features_from_gp(const gmc_batch *batch, const gmc_model *model, const float *X,

@@ -10,6 +10,8 @@
 //   loss.backward() (:385) down to the input of conv2's aggregation:
 //      GP = C * A_val @ onehot(S);  GZ = P o (GP - rowsum(GP o P));  db2 = colsum(GZ);
 //      GY2 = A @ (dinv o GZ)
+// GMC_LOSS_EXPECTED_CUT (head_soft_kernel): the same chain without the one-hot step of :96-106 - the expected cut of
+// independent rounding, loss = -C/2 sum_uv w_uv (1 - Pt_u . Pt_v), GP = C * A_val @ Pt, Pt = override_fixed_nodes(P).
 // Sums run in CSR / fixed tree order: bitwise reproducible.
 #include "head_body.h"
 #include "launchers.h"
@@ -26,6 +28,13 @@ template <int W>
 __global__ __launch_bounds__(kHeadThreads) void head_kernel(HeadArgs a) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     head_body<W>(a, (int)blockIdx.x, lds, true, nullptr);
+}
+
+// the relaxed loss: its own kernel name, head_kernel<W> stays the three instantiations it was
+template <int W>
+__global__ __launch_bounds__(kHeadThreads) void head_soft_kernel(HeadArgs a) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    head_body<W, true>(a, (int)blockIdx.x, lds, true, nullptr);
 }
 
 // GY2 for a caller-supplied dLoss/dP (autograd path): same phases 2b/3 as above.
@@ -86,13 +95,21 @@ extern "C" int gmc_head_f32(const gmc_batch *batch, const float *Z0, int32_t z_p
                             float C, float *P, int32_t *S, float *loss, float *GY2, float *db2part,
                             gmc_stream_t stream) {
     return gmc_head_launch(batch, Z0, z_parts, b2, C, P, S, loss, GY2, db2part, nullptr,
-                           static_cast<hipStream_t>(stream));
+                           static_cast<hipStream_t>(stream), GMC_LOSS_CUT);
+}
+
+extern "C" int gmc_head_loss_f32(const gmc_batch *batch, const float *Z0, int32_t z_parts, const float *b2,
+                                 float C, int32_t loss_kind, float *P, int32_t *S, float *loss, float *GY2,
+                                 float *db2part, gmc_stream_t stream) {
+    if (!gmc_loss_kind_ok(loss_kind)) return GMC_ERR_LOSS;
+    return gmc_head_launch(batch, Z0, z_parts, b2, C, P, S, loss, GY2, db2part, nullptr,
+                           static_cast<hipStream_t>(stream), loss_kind);
 }
 
 // Internal launcher.  tick != nullptr: the launch also advances the device-side Adam step counter
-// (gmc_train_step_f32; saves a one-thread launch per step).
+// (gmc_train_step_f32; saves a one-thread launch per step).  loss_kind: GMC_LOSS_* (checked by the caller).
 int gmc_head_launch(const gmc_batch *batch, const float *Z0, int32_t z_parts, const float *b2, float C, float *P,
-                    int32_t *S, float *loss, float *GY2, float *db2part, int *tick, hipStream_t stream) {
+                    int32_t *S, float *loss, float *GY2, float *db2part, int *tick, hipStream_t stream, int loss_kind) {
     int rc = check_batch(batch);
     if (rc) return rc;
     if (!Z0 || !b2 || !P) return GMC_ERR_NULL;
@@ -100,16 +117,24 @@ int gmc_head_launch(const gmc_batch *batch, const float *Z0, int32_t z_parts, co
     if (GY2 && !db2part) return GMC_ERR_NULL;
     if (batch->B == 0) return GMC_OK;
     HeadArgs a{*batch, Z0, z_parts, b2, C, P, S, loss, GY2, db2part, tick};
-    const size_t lds = sizeof(float) * (7 * ((size_t)batch->n_max + 4) + 64);
+    const bool soft = loss_kind == GMC_LOSS_EXPECTED_CUT;
+    const size_t lds = sizeof(float) * (7 * ((size_t)batch->n_max + 4) + 64 + (soft ? 12 : 0));
     const int w = (batch->ell != nullptr && (batch->ell_width == 8 || batch->ell_width == 16)) ? batch->ell_width : 0;
-    const void *fn = w == 8 ? reinterpret_cast<const void *>(head_kernel<8>)
+    const void *fn = soft ? (w == 8 ? reinterpret_cast<const void *>(head_soft_kernel<8>)
+                             : w == 16 ? reinterpret_cast<const void *>(head_soft_kernel<16>)
+                                       : reinterpret_cast<const void *>(head_soft_kernel<0>))
+                   : w == 8 ? reinterpret_cast<const void *>(head_kernel<8>)
                    : w == 16 ? reinterpret_cast<const void *>(head_kernel<16>) : reinterpret_cast<const void *>(head_kernel<0>);
     if (lds > 64 * 1024) {
         hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return (int)e;
     }
     GmcProbeScope probe(GMC_K_HEAD, stream);
-    if (w == 8) hipLaunchKernelGGL(head_kernel<8>, dim3(batch->B), dim3(kHeadThreads), lds, stream, a);
+    if (soft) {
+        if (w == 8) hipLaunchKernelGGL(head_soft_kernel<8>, dim3(batch->B), dim3(kHeadThreads), lds, stream, a);
+        else if (w == 16) hipLaunchKernelGGL(head_soft_kernel<16>, dim3(batch->B), dim3(kHeadThreads), lds, stream, a);
+        else hipLaunchKernelGGL(head_soft_kernel<0>, dim3(batch->B), dim3(kHeadThreads), lds, stream, a);
+    } else if (w == 8) hipLaunchKernelGGL(head_kernel<8>, dim3(batch->B), dim3(kHeadThreads), lds, stream, a);
     else if (w == 16) hipLaunchKernelGGL(head_kernel<16>, dim3(batch->B), dim3(kHeadThreads), lds, stream, a);
     else hipLaunchKernelGGL(head_kernel<0>, dim3(batch->B), dim3(kHeadThreads), lds, stream, a);
     GMC_LAUNCH_CHECK();

@@ -99,11 +99,16 @@ __device__ __forceinline__ void for_neighbours(const gmc_batch &b, int r0, int l
     (void)n;
 }
 
-// The head of graph g on the calling workgroup (kHeadThreads threads, all of them; `lds`: 7 * (n_max + 4) + 64 floats).
+// The head of graph g on the calling workgroup (kHeadThreads threads, all of them; `lds`: 7 * (n_max + 4) + 64 floats,
+// SOFT: 12 more).
+//   SOFT     the relaxed loss (GMC_LOSS_EXPECTED_CUT): the expected cut under independent rounding,
+//            loss = -C/2 sum_u sum_{v in N(u)} w_uv (1 - Pt_u . Pt_v),  GP_u = C sum_{v in N(u)} w_uv Pt_v,  Pt = P with
+//            rows 0..2 replaced by e0, e1, e2 (TrainingNeural.py:291-309,:154-176 on override_fixed_nodes(P), :87-94,
+//            without the one-hot step of :96-106).  S stays the argmax decode.  false: the code below is what it was.
 //   outputs  store P / S / loss / db2part and advance the step counter (one caller per graph does)
 //   gy_lds   != nullptr: the rows (GY2[r,:], dinv[r]) go to this LDS array [n] instead of a.GY2 - a caller that consumes
 //            them itself (the one-graph backward: bwd1_lds.hip)
-template <int W>
+template <int W, bool SOFT = false>
 __device__ __forceinline__ void head_body(const HeadArgs &a, const int g, float *lds, const bool outputs, float4 *gy_lds) {
     constexpr bool ELL = W > 0;
     HMARK(0);
@@ -114,6 +119,7 @@ __device__ __forceinline__ void head_body(const HeadArgs &a, const int g, float 
     float *sP = lds + 3 * NP;                 // [NP*3]  softmax output
     int *sS = reinterpret_cast<int *>(lds + 6 * NP);  // [NP] argmax class
     float *red = lds + 7 * NP;                // [64]
+    float *sT = red + 64;                     // [9]  SOFT: the softmax rows 0..2 (sP holds e0, e1, e2 there)
     const bool train = a.GY2 != nullptr || gy_lds != nullptr;
     // nobody reads the counter during this kernel.  A no-return atomic: `*tick += 1` is a load the wave has to wait for
     // before its store - a memory round trip at the top of block 0's critical path (a one-graph launch IS block 0)
@@ -167,6 +173,9 @@ __device__ __forceinline__ void head_body(const HeadArgs &a, const int g, float 
     }
     if (threadIdx.x < 12) sA[3 * n + threadIdx.x] = 0.f;
     if (threadIdx.x < 4) sS[n + threadIdx.x] = 3;  // a class no node has
+    if constexpr (SOFT) {
+        if (threadIdx.x < 12) sP[3 * n + threadIdx.x] = 0.f;
+    }
     HMARK(1);
     __syncthreads();
     HMARK(2);
@@ -183,7 +192,12 @@ __device__ __forceinline__ void head_body(const HeadArgs &a, const int g, float 
         const float inv = 1.0f / (e0 + e1 + e2);
         const float p0 = e0 * inv, p1 = e1 * inv, p2 = e2 * inv;
         if (outputs) { a.P[(long)r * 3] = p0; a.P[(long)r * 3 + 1] = p1; a.P[(long)r * 3 + 2] = p2; }
-        sP[3 * l] = p0; sP[3 * l + 1] = p1; sP[3 * l + 2] = p2;
+        if (SOFT && l < 3) {  // Pt: the terminal rows are e_l; the softmax backward below still needs the row itself
+            sT[3 * l] = p0; sT[3 * l + 1] = p1; sT[3 * l + 2] = p2;
+            sP[3 * l] = l == 0 ? 1.f : 0.f; sP[3 * l + 1] = l == 1 ? 1.f : 0.f; sP[3 * l + 2] = l == 2 ? 1.f : 0.f;
+        } else {
+            sP[3 * l] = p0; sP[3 * l + 1] = p1; sP[3 * l + 2] = p2;
+        }
         int s;
         if (l < 3) {
             s = l;  // (e_l + p) - p: 1 at l, exactly 0 elsewhere -> argmax is l
@@ -206,15 +220,29 @@ __device__ __forceinline__ void head_body(const HeadArgs &a, const int g, float 
         const int r = r0 + l;
         const int me = sS[l];
         float g0 = 0.f, g1 = 0.f, g2 = 0.f, cut = 0.f;
-        for_neighbours<W>(a.b, r0, l, n, l == l0, cid0, cid1, [&](int c, float w) {
-            const int sc = sS[c];  // padding slots carry class 3: no contribution
-            g0 += sc == 0 ? w : 0.f; g1 += sc == 1 ? w : 0.f; g2 += sc == 2 ? w : 0.f;
-            cut += (sc != me && sc != 3) ? w : 0.f;
-        });
+        if constexpr (SOFT) {
+            // Padding ids (n..n+3 of the table, n of the overflow blocks) come with weight 1 in a batch without weights:
+            // their Pt rows are zero, which keeps them out of g but would count w (1 - 0) as a cut edge - the id decides
+            const float u0 = sP[3 * l], u1 = sP[3 * l + 1], u2 = sP[3 * l + 2];
+            for_neighbours<W>(a.b, r0, l, n, l == l0, cid0, cid1, [&](int c, float w) {
+                const float q0 = sP[3 * c], q1 = sP[3 * c + 1], q2 = sP[3 * c + 2];
+                const float wv = c < n ? w : 0.f;
+                g0 += wv * q0; g1 += wv * q1; g2 += wv * q2;
+                cut += wv * (1.0f - (u0 * q0 + u1 * q1 + u2 * q2));
+            });
+        } else {
+            for_neighbours<W>(a.b, r0, l, n, l == l0, cid0, cid1, [&](int c, float w) {
+                const int sc = sS[c];  // padding slots carry class 3: no contribution
+                g0 += sc == 0 ? w : 0.f; g1 += sc == 1 ? w : 0.f; g2 += sc == 2 ? w : 0.f;
+                cut += (sc != me && sc != 3) ? w : 0.f;
+            });
+        }
         acc[0] += cut;
         if (train) {
             g0 *= a.C; g1 *= a.C; g2 *= a.C;
-            const float p0 = sP[3 * l], p1 = sP[3 * l + 1], p2 = sP[3 * l + 2];
+            const bool own = SOFT && l < 3;
+            const float p0 = own ? sT[3 * l] : sP[3 * l], p1 = own ? sT[3 * l + 1] : sP[3 * l + 1],
+                        p2 = own ? sT[3 * l + 2] : sP[3 * l + 2];
             const float dot = g0 * p0 + g1 * p1 + g2 * p2;
             const float z0 = p0 * (g0 - dot), z1 = p1 * (g1 - dot), z2 = p2 * (g2 - dot);
             acc[1] += z0; acc[2] += z1; acc[3] += z2;

@@ -71,9 +71,10 @@ int gmc_dw1_lds_launch(const gmc_batch *b, const float *U, long ldu, int u_slab,
                        int graphs_per_chunk, hipStream_t st);
 
 // ---- head (head.hip), hidden backward (hidden_bwd.hip), dropout (dropout.hip) --------------------------------------
-// tick != nullptr: the launch also advances the device-side Adam step counter
+// tick != nullptr: the launch also advances the device-side Adam step counter; loss_kind: GMC_LOSS_*
+inline bool gmc_loss_kind_ok(int kind) { return kind == GMC_LOSS_CUT || kind == GMC_LOSS_EXPECTED_CUT; }
 int gmc_head_launch(const gmc_batch *batch, const float *Z0, int32_t z_parts, const float *b2, float C, float *P,
-                    int32_t *S, float *loss, float *GY2, float *db2part, int *tick, hipStream_t st);
+                    int32_t *S, float *loss, float *GY2, float *db2part, int *tick, hipStream_t st, int loss_kind);
 int gmc_head_bwd_launch(const gmc_batch *batch, const float *P, const float *GP, float *GY2, float *db2part,
                         hipStream_t st);
 int gmc_hidden_tiles(int R);

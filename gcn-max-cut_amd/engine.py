@@ -115,10 +115,18 @@ class FusedEngine:
             self._slab_sig = sig
         return hip.ptr(self.w1_slab)
 
-    def _model_ref(self, slab: bool):
-        """byref(gmc_model) for a call; ``slab``: with the (current) slab copy of W1."""
+    def _model_ref(self, slab: bool, loss: str = "cut"):
+        """byref(gmc_model) for a call; ``slab``: with the (current) slab copy of W1; ``loss``: the loss the call
+        computes (GMC_MODEL_LOSS_EXPECTED in the flags for ``expected_cut``; a bad name raises ValueError)."""
+        flags = hip.MODEL_GRAD_TAIL | (hip.MODEL_LOSS_EXPECTED if hip.loss_kind(loss) else 0)
         self._model.W1_slab = self.ensure_slab() if slab else None
+        self._model.flags = flags
         return C.byref(self._model)
+
+    def _model_done(self) -> None:
+        """After a call that went through :meth:`_model_ref`: the struct is the default one again."""
+        self._model.W1_slab = None
+        self._model.flags = hip.MODEL_GRAD_TAIL
 
     def set_dropout(self, p: float, seed: Optional[int] = None) -> None:
         """F.dropout between the layers (TrainingNeural.py:82) for the next forward / training calls:
@@ -170,69 +178,75 @@ class FusedEngine:
         return max(256, int(self.lib.gmc_workspace_bytes(batch.ref(), C.byref(self._model), int(training))))
 
     def forward(self, batch: GraphBatch, C_: float = 1.0, want_loss: bool = False,
-                ws: Optional[torch.Tensor] = None):
+                ws: Optional[torch.Tensor] = None, loss: str = "cut"):
         """P [R,3] (and S [R], loss [B] when ``want_loss``) - TrainingNeural.py:79-85.
-        ``ws``: caller-owned scratch (kept alive for a later :meth:`backward_from_gp`)."""
+        ``ws``: caller-owned scratch (kept alive for a later :meth:`backward_from_gp`).  ``loss``: ``"cut"`` (the
+        reference's -C * cut of the argmax decode) or ``"expected_cut"`` (the relaxed loss: ``hip.LOSS_KINDS``)."""
+        hip.loss_kind(loss)
         P = torch.empty((batch.R, 3), dtype=torch.float32, device=self.device)
         S = torch.empty(batch.R, dtype=torch.int32, device=self.device) if want_loss else None
-        loss = torch.empty(batch.B, dtype=torch.float32, device=self.device) if want_loss else None
+        losses = torch.empty(batch.B, dtype=torch.float32, device=self.device) if want_loss else None
         if batch.B == 0:   # nothing to launch (empty tensors have no device pointer to hand over)
-            return P, S, loss
+            return P, S, losses
         ws, nbytes = (ws, ws.numel()) if ws is not None else self._workspace(batch, False)
-        rc = self.lib.gmc_forward(batch.ref(), C.byref(self._model), C_, hip.ptr(ws), nbytes,
-                                  hip.ptr(P), hip.ptr(S), hip.ptr(loss), hip.stream())
+        rc = self.lib.gmc_forward(batch.ref(), self._model_ref(False, loss), C_, hip.ptr(ws), nbytes,
+                                  hip.ptr(P), hip.ptr(S), hip.ptr(losses), hip.stream())
+        self._model_done()
         hip.check(rc, "gmc_forward")
-        return P, S, loss
+        return P, S, losses
 
     def train_fwd_bwd(self, batch: GraphBatch, C_: float = 1.0, out=None, ws: Optional[torch.Tensor] = None,
-                      slab: bool = False):
+                      slab: bool = False, loss: str = "cut"):
         """forward + loss + backward for the batch's summed loss; gradient lands in
         ``self.grad[:count]`` - TrainingNeural.py:373-385.  ``ws``: caller-owned scratch (a trainer
         whose launches are captured into a hipGraph must own it: the engine's own scratch moves
-        whenever a later call needs more)."""
+        whenever a later call needs more).  ``loss``: as for :meth:`forward`."""
+        hip.loss_kind(loss)
         if out is None:
             P = torch.empty((batch.R, 3), dtype=torch.float32, device=self.device)
             S = torch.empty(batch.R, dtype=torch.int32, device=self.device)
-            loss = torch.empty(batch.B, dtype=torch.float32, device=self.device)
+            losses = torch.empty(batch.B, dtype=torch.float32, device=self.device)
         else:
-            P, S, loss = out
+            P, S, losses = out
         if batch.B == 0:   # no graphs: zero gradient AND zero loss in the tail slot, nothing to launch
             self.grad[:self.count + 1].zero_()
-            return P, S, loss
+            return P, S, losses
         ws, nbytes = (ws, ws.numel()) if ws is not None else self._workspace(batch, True)
-        rc = self.lib.gmc_train_fwd_bwd(batch.ref(), self._model_ref(slab), C_, hip.ptr(ws), nbytes,
-                                        hip.ptr(P), hip.ptr(S), hip.ptr(loss), hip.ptr(self.grad),
+        rc = self.lib.gmc_train_fwd_bwd(batch.ref(), self._model_ref(slab, loss), C_, hip.ptr(ws), nbytes,
+                                        hip.ptr(P), hip.ptr(S), hip.ptr(losses), hip.ptr(self.grad),
                                         hip.stream())
-        self._model.W1_slab = None
+        self._model_done()
         hip.check(rc, "gmc_train_fwd_bwd")
-        return P, S, loss
+        return P, S, losses
 
     def train_step(self, batch: GraphBatch, lr: float, C_: float = 1.0, out=None, betas=(0.9, 0.999),
                    eps: float = 1e-8, ws: Optional[torch.Tensor] = None, slab: bool = False,
-                   loss_ptr: Optional[int] = None):
+                   loss_ptr: Optional[int] = None, loss: str = "cut"):
         """One whole optimizer step (forward, loss, backward, fused gradient fold + Adam) - the
         single-GPU form of the loop body of train_single_epoch (TrainingNeural.py:373-386).
         Replay-invariant: the step number is read from / advanced in device memory.  ``loss_ptr``: device-side
         address of pinned host memory (``hip.mapped_ptr``) that receives the per-graph losses instead of
-        ``out[2]`` - each is stored as soon as it is final, before the backward kernels run."""
+        ``out[2]`` - each is stored as soon as it is final, before the backward kernels run.  ``loss``: as for
+        :meth:`forward` (gmc_train_step_loss_f32; a one-graph ``expected_cut`` step launches the head on its own)."""
+        kind = hip.loss_kind(loss)
         ws, nbytes = (ws, ws.numel()) if ws is not None else self._workspace(batch, True)
         if out is None:
             P = torch.empty((batch.R, 3), dtype=torch.float32, device=self.device)
             S = torch.empty(batch.R, dtype=torch.int32, device=self.device)
-            loss = torch.empty(batch.B, dtype=torch.float32, device=self.device)
+            losses = torch.empty(batch.B, dtype=torch.float32, device=self.device)
         else:
-            P, S, loss = out
+            P, S, losses = out
         tail = (self.ensure_slab() if slab else None, hip.stream())
-        rc = self.lib.gmc_train_step_f32(batch.ref(), self.N, self.Fp, hip.ptr(self.flat), C_, hip.ptr(ws), nbytes,
-                                         hip.ptr(P), hip.ptr(S), loss_ptr or hip.ptr(loss), hip.ptr(self.grad),
-                                         hip.ptr(self.m), hip.ptr(self.v), lr, betas[0], betas[1], eps,
-                                         hip.ptr(self.step_dev), *tail)
+        rc = self.lib.gmc_train_step_loss_f32(batch.ref(), self.N, self.Fp, hip.ptr(self.flat), C_, kind, hip.ptr(ws),
+                                              nbytes, hip.ptr(P), hip.ptr(S), loss_ptr or hip.ptr(losses),
+                                              hip.ptr(self.grad), hip.ptr(self.m), hip.ptr(self.v), lr, betas[0],
+                                              betas[1], eps, hip.ptr(self.step_dev), *tail)
         if not slab:
             self._slab_sig = None   # W1 moved, the copy did not
-        hip.check(rc, "gmc_train_step_f32")
+        hip.check(rc, "gmc_train_step_loss_f32")
         self.step_count += 1
         self._dev_step += 1
-        return P, S, loss
+        return P, S, losses
 
     def backward_from_gp(self, batch: GraphBatch, P: torch.Tensor, GP: torch.Tensor,
                          ws: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
@@ -265,22 +279,26 @@ class FusedEngine:
         return X.clone() if X.data_ptr() % 16 else X
 
     def forward_features(self, batch: GraphBatch, X: torch.Tensor, C_: float = 1.0, want_loss: bool = False,
-                         ws: Optional[torch.Tensor] = None):
+                         ws: Optional[torch.Tensor] = None, loss: str = "cut"):
         """:meth:`forward` for node features ``X`` [R, N] that are not the padded adjacency (the rows of the batch's
         graphs stacked): the layer-1 feature transform is the library's fp32 MFMA GEMM.  ``ws``: caller-owned scratch
-        of :meth:`workspace_bytes_features` bytes (kept alive for :meth:`backward_features_from_gp`)."""
+        of :meth:`workspace_bytes_features` bytes (kept alive for :meth:`backward_features_from_gp`).  ``loss``: as for
+        :meth:`forward`."""
+        hip.loss_kind(loss)
         P = torch.empty((batch.R, 3), dtype=torch.float32, device=self.device)
         S = torch.empty(batch.R, dtype=torch.int32, device=self.device) if want_loss else None
-        loss = torch.empty(batch.B, dtype=torch.float32, device=self.device) if want_loss else None
+        losses = torch.empty(batch.B, dtype=torch.float32, device=self.device) if want_loss else None
         Xd = self.pad_features(batch, X)
         if batch.B == 0:
-            return P, S, loss
+            return P, S, losses
         if ws is None:
             ws = torch.empty(self.workspace_bytes_features(batch, False), dtype=torch.uint8, device=self.device)
-        rc = self.lib.gmc_forward_features(batch.ref(), C.byref(self._model), hip.ptr(Xd), Xd.shape[1], C_, hip.ptr(ws),
-                                           ws.numel(), hip.ptr(P), hip.ptr(S), hip.ptr(loss), hip.stream())
+        rc = self.lib.gmc_forward_features(batch.ref(), self._model_ref(False, loss), hip.ptr(Xd), Xd.shape[1], C_,
+                                           hip.ptr(ws), ws.numel(), hip.ptr(P), hip.ptr(S), hip.ptr(losses),
+                                           hip.stream())
+        self._model_done()
         hip.check(rc, "gmc_forward_features")
-        return P, S, loss
+        return P, S, losses
 
     def backward_features_from_gp(self, batch: GraphBatch, X: torch.Tensor, P: torch.Tensor, GP: torch.Tensor,
                                   ws: torch.Tensor, want_dx: bool = True):
@@ -370,6 +388,25 @@ class FusedEngine:
         if dp_active():
             dist.all_reduce(self.grad, op=dist.ReduceOp.SUM)
         return self.grad[self.count] if local_loss_sum is not None else None
+
+
+def device_cut_loss(batch: GraphBatch, P: torch.Tensor, C_: float = 1.0, loss: str = "cut", want_gp: bool = True,
+                    device: Optional[torch.device] = None):
+    """(loss [B], GP [R,3] or None) of given probabilities ``P`` [R,3] (gmc_cut_loss_f32): per-graph loss and
+    dLoss/dP, O(edges) on the device - ``GP`` is what :meth:`FusedEngine.backward_from_gp` takes.  The loss has no
+    parameters, so it needs no engine."""
+    kind = hip.loss_kind(loss)
+    device = device or hip.require_gpu()
+    if P.dim() != 2 or tuple(P.shape) != (batch.R, 3):
+        raise ValueError(f"P must be [{batch.R}, 3], got {tuple(P.shape)}")
+    Pd = P.detach().to(device, torch.float32).contiguous()
+    losses = torch.empty(batch.B, dtype=torch.float32, device=device)
+    GP = torch.empty((batch.R, 3), dtype=torch.float32, device=device) if want_gp else None
+    if batch.B == 0:
+        return losses, GP
+    rc = hip.load().gmc_cut_loss_f32(batch.ref(), hip.ptr(Pd), C_, kind, hip.ptr(losses), hip.ptr(GP), hip.stream())
+    hip.check(rc, "gmc_cut_loss_f32")
+    return losses, GP
 
 
 def dp_active() -> bool:

@@ -24,11 +24,17 @@ SYMBOLS = (
     "gmc_publish_adam_devstep_model_f32", "gmc_probe_flavours", "gmc_lds_flavours", "gmc_refine_order_host",
     "gmc_refine_local_f32", "gmc_refine_anneal_f32", "gmc_refine_anneal_staged",
     "gmc_gemm_f32", "gmc_workspace_bytes_features", "gmc_forward_features", "gmc_backward_features_from_gp",
+    "gmc_head_loss_f32", "gmc_train_step_loss_f32", "gmc_cut_loss_f32",
 )
 
 MAX_GRAPH_NODES = 4096
 ANNEAL_LEVELS = 1024  # GMC_ANNEAL_LEVELS: entries of the level table gmc_refine_anneal_f32 reads
 MODEL_GRAD_TAIL = 1   # gmc_model.flags: grad has a tail slot that receives the batch's loss sum
+MODEL_LOSS_EXPECTED = 2   # gmc_model.flags: loss and gradient are GMC_LOSS_EXPECTED_CUT
+# GMC_LOSS_*: the reference's hard loss (-C * cut of the argmax decode) and the relaxed one (the expected cut of
+# independent rounding: compute_loss on override_fixed_nodes(P) without the one-hot step)
+LOSS_KINDS = {"cut": 0, "expected_cut": 1}
+LOSS_ENV = "GCN_MAXCUT_LOSS"
 ABI_VERSION = 200     # GMC_VERSION of include/gcnmaxcut.h these struct layouts follow (checked at load and per call)
 
 
@@ -64,6 +70,23 @@ class GmcModel(C.Structure):
         super().__init__(**kw)
 
 
+def loss_kind(name: Optional[str]) -> int:
+    """GMC_LOSS_* of a loss name; ``None`` reads the environment switch GCN_MAXCUT_LOSS (default ``cut``).  The
+    library itself reads no environment."""
+    if name is None:
+        name = os.environ.get(LOSS_ENV) or "cut"
+    try:
+        return LOSS_KINDS[name]
+    except (KeyError, TypeError):
+        raise ValueError(f"unknown loss {name!r}: expected one of {sorted(LOSS_KINDS)}") from None
+
+
+def loss_name(name: Optional[str]) -> str:
+    """The canonical name of a loss (``None``: the environment's)."""
+    kind = loss_kind(name)
+    return next(k for k, v in LOSS_KINDS.items() if v == kind)
+
+
 _lib: Optional[C.CDLL] = None
 
 
@@ -75,6 +98,10 @@ def _declare(lib: C.CDLL) -> None:
     lib.gmc_spmm_f32.argtypes = [vp, vp, vp, vp, vp, i64, vp, C.c_int, vp, i64, i32, i32, i32, vp, vp, vp]
     lib.gmc_dense_hw2_f32.argtypes = [vp, i64, vp, vp, vp, i32, i32, vp]
     lib.gmc_head_f32.argtypes = [C.POINTER(GmcBatch), vp, i32, vp, f32, vp, vp, vp, vp, vp, vp]
+    lib.gmc_head_loss_f32.argtypes = [C.POINTER(GmcBatch), vp, i32, vp, f32, i32, vp, vp, vp, vp, vp, vp]
+    lib.gmc_cut_loss_f32.argtypes = [C.POINTER(GmcBatch), vp, f32, i32, vp, vp, vp]
+    lib.gmc_train_step_loss_f32.argtypes = [C.POINTER(GmcBatch), i32, i32, vp, f32, i32, vp, sz, vp, vp, vp, vp, vp, vp,
+                                            C.c_double, C.c_double, C.c_double, C.c_double, vp, vp, vp]
     lib.gmc_adam_f32.argtypes = [vp, vp, vp, vp, i64, C.c_double, C.c_double, C.c_double, C.c_double, i32, vp]
     lib.gmc_workspace_bytes.restype = sz
     lib.gmc_workspace_bytes.argtypes = [C.POINTER(GmcBatch), C.POINTER(GmcModel), C.c_int]

@@ -45,8 +45,21 @@ enum {
     GMC_ERR_WORKSPACE = -5,   /* workspace too small */
     GMC_ERR_GRAPH_SIZE = -6,  /* a graph has < 3 or > GMC_MAX_GRAPH_NODES nodes */
     GMC_ERR_UNSUPPORTED = -7,
-    GMC_ERR_ABI = -8          /* gmc_batch.abi / gmc_model.abi != GMC_VERSION: caller built against another header */
+    GMC_ERR_ABI = -8,         /* gmc_batch.abi / gmc_model.abi != GMC_VERSION: caller built against another header */
+    GMC_ERR_LOSS = -9         /* loss_kind is not one of GMC_LOSS_* */
 };
+
+/* The loss of a graph, for its probabilities P [n,3] and Pt = override_fixed_nodes(P) (rows 0,1,2 <- e0,e1,e2 with a
+ * straight-through gradient, TrainingNeural.py:87-94):
+ *  GMC_LOSS_CUT           the reference's: compute_loss (:291-309,:154-176) of apply_max_to_one_hot(Pt) (:96-106),
+ *                         loss = -C * cut(S), S = row-argmax of Pt;  dLoss/dP = C * A_val @ onehot(S) (straight-through).
+ *  GMC_LOSS_EXPECTED_CUT  the same compute_loss (:291-309,:154-176) of Pt itself, without the one-hot step of :96-106 -
+ *                         the expected cut when every node draws its class independently from its row:
+ *                         loss = -C/2 * sum_u sum_{v in N(u)} w_uv (1 - Pt_u . Pt_v);  dLoss/dP_u = C * sum_{v in N(u)}
+ *                         w_uv Pt_v for every row u, rows 0..2 included.  (A self-loop would count as in the dense
+ *                         formula; the reference's graphs have none.)  S stays the argmax decode.
+ * Both are summed in a fixed order (bitwise reproducible) and stored with one system-scope store per graph. */
+enum { GMC_LOSS_CUT = 0, GMC_LOSS_EXPECTED_CUT = 1 };
 
 #define GMC_MAX_GRAPH_NODES 4096 /* per-graph head kernel keeps [n,3] tiles in LDS */
 /* Largest hidden width F (gmc_model.F, the F of every entry point below that takes one): F must be a multiple of 4
@@ -129,6 +142,10 @@ typedef struct gmc_model {
  * data-parallel caller carry the step's loss (TrainingNeural.py:387-388) through the gradient
  * all-reduce instead of a second collective. */
 #define GMC_MODEL_GRAD_TAIL 1
+/* gmc_forward, gmc_train_fwd_bwd and gmc_forward_features: the loss (and, training, its gradient) is
+ * GMC_LOSS_EXPECTED_CUT instead of GMC_LOSS_CUT (compute_loss on override_fixed_nodes(P), TrainingNeural.py:291-309
+ * on :87-94, without :96-106). */
+#define GMC_MODEL_LOSS_EXPECTED 2
 
 int gmc_version(void);
 const char *gmc_error_string(int code);
@@ -260,6 +277,25 @@ int gmc_gemm_f32(int32_t ta, int32_t tb, int32_t M, int32_t Nc, int32_t K, const
 int gmc_head_f32(const gmc_batch *batch, const float *Z0, int32_t z_parts, const float *b2, float C,
                  float *P, int32_t *S, float *loss, float *GY2, float *db2part, gmc_stream_t stream);
 
+/* gmc_head_f32 with the loss chosen by loss_kind (GMC_LOSS_*; gmc_head_f32 is this call with GMC_LOSS_CUT).  With
+ * GMC_LOSS_EXPECTED_CUT loss[g] and the GP behind GY2 / db2part are those of compute_loss(override_fixed_nodes(P))
+ * (TrainingNeural.py:291-309,:154-176 on :87-94); P and S are what gmc_head_f32 gives, bit for bit.  An unknown
+ * loss_kind returns GMC_ERR_LOSS before anything else is looked at. */
+int gmc_head_loss_f32(const gmc_batch *batch, const float *Z0, int32_t z_parts, const float *b2, float C,
+                      int32_t loss_kind, float *P, int32_t *S, float *loss, float *GY2, float *db2part,
+                      gmc_stream_t stream);
+
+/* The loss alone, for given probabilities P [R,3] (the output of gmc_forward / gmc_forward_features, or any caller's):
+ * loss[g] (device or pinned host memory, [B]) and, when GP != NULL, GP [R,3] = dLoss/dP as defined at GMC_LOSS_*
+ * (for GMC_LOSS_CUT the straight-through C * A_val @ onehot(S) of TrainingNeural.py:96-106 + :291-309; for
+ * GMC_LOSS_EXPECTED_CUT the exact gradient up to the straight-through override of :87-94).  O(edges): one workgroup
+ * per graph walks the neighbour table, overflow lists or CSR rows as the head does, the rows held in LDS - what a
+ * caller of gmc_backward_from_gp / gmc_backward_features_from_gp needs instead of the dense [n,1000] products of
+ * :154-176.  Errors, all found before any HIP call: loss_kind GMC_ERR_LOSS, a NULL batch / P / loss GMC_ERR_NULL,
+ * batch->abi GMC_ERR_ABI, sizes GMC_ERR_SHAPE, n_max GMC_ERR_GRAPH_SIZE.  B == 0 launches nothing. */
+int gmc_cut_loss_f32(const gmc_batch *batch, const float *P, float C, int32_t loss_kind, float *loss, float *GP,
+                     gmc_stream_t stream);
+
 /* torch.optim.Adam.step (TrainingNeural.py:337,:386) over one flat buffer, fused:
  * m,v update + bias correction + parameter update in a single sweep. step >= 1.  The
  * hyper-parameters are doubles because torch derives 1-beta, lr/bias_correction1 and
@@ -336,6 +372,16 @@ int gmc_train_step_f32(const gmc_batch *batch, int32_t N, int32_t F, float *para
                        size_t workspace_bytes, float *P, int32_t *S, float *loss, float *grad, float *m,
                        float *v, double lr, double beta1, double beta2, double eps, int32_t *step_counter,
                        float *w1_slab, gmc_stream_t stream);
+
+/* gmc_train_step_f32 with the loss chosen by loss_kind (GMC_LOSS_*; gmc_train_step_f32 is this call with
+ * GMC_LOSS_CUT), as replay-invariant.  With GMC_LOSS_EXPECTED_CUT the step descends compute_loss on
+ * override_fixed_nodes(P) (TrainingNeural.py:291-309 on :87-94, without :96-106); a one-graph batch then runs the
+ * stand-alone head launch (the head inside the backward launch is GMC_LOSS_CUT only).  An unknown loss_kind returns
+ * GMC_ERR_LOSS before anything else is looked at. */
+int gmc_train_step_loss_f32(const gmc_batch *batch, int32_t N, int32_t F, float *param, float C, int32_t loss_kind,
+                            void *workspace, size_t workspace_bytes, float *P, int32_t *S, float *loss, float *grad,
+                            float *m, float *v, double lr, double beta1, double beta2, double eps,
+                            int32_t *step_counter, float *w1_slab, gmc_stream_t stream);
 
 /* Backward for a caller-supplied dLoss/dP (autograd.Function path: callers that build
  * their own loss from GCNSoftmax.forward's output, e.g. the reference's
