@@ -177,13 +177,13 @@ int gmc_loss_tail_launch(const float *loss, int B, float *slot, hipStream_t st) 
     return GMC_OK;
 }
 
-// param == nullptr -> gradients only.  *step_counter (device) must already hold this step's number.
+// adam == nullptr -> gradients only.  *step_counter (device) must already hold this step's number.
 int gmc_finish_launch(const float *dw1part, const float *colpart, const float *db2part, int chunks, int n_max,
-                      int N, int F, int B, float *grad, float *param, float *m, float *v, double lr, double beta1,
-                      double beta2, double eps, int *step_counter, const float *loss_for_tail, hipStream_t st,
-                      float *w1_slab) {
-    FinishArgs a{dw1part, colpart, db2part, chunks, n_max, N, F, B, grad, param, m, v, lr, beta1, beta2, (float)eps,
-                 step_counter, loss_for_tail, param ? w1_slab : nullptr};
+                      int N, int F, int B, float *grad, const AdamFuse *adam, const float *loss_for_tail,
+                      hipStream_t st) {
+    const AdamFuse af = adam ? *adam : AdamFuse{};
+    FinishArgs a{dw1part, colpart, db2part, chunks, n_max, N, F, B, grad, af.param, af.m, af.v, af.lr, af.beta1,
+                 af.beta2, (float)af.eps, af.step_counter, loss_for_tail, af.param ? af.w1_slab : nullptr};
     const long n4 = (long)N * F / 4;
     long blocks = (n4 + 255) / 256;
     if (blocks > 2048) blocks = 2048;

@@ -44,11 +44,16 @@ struct gmc_bwd1_head {
 int gmc_bwd1_lds_launch(const gmc_batch *b, const float *H, const float *GY2, const float *W2, float *dw1part,
                         float *colpart, int F, int chunks, int graphs_per_chunk, hipStream_t st,
                         const gmc_bwd1_head *head);
-// folds the fused backward's partials into grad; param != nullptr: Adam on param / m / v as well (device step counter)
+// optional Adam fused into the gradient fold (single GPU); *step_counter (device) already holds this step's number
+struct AdamFuse {
+    float *param = nullptr, *m = nullptr, *v = nullptr;
+    double lr = 0, beta1 = 0, beta2 = 0, eps = 0;
+    int *step_counter = nullptr;
+    float *w1_slab = nullptr;  // slab copy of W1 to refresh with the update (gmc_model.W1_slab)
+};
+// folds the fused backward's partials into grad; adam == nullptr: fold only
 int gmc_finish_launch(const float *dw1part, const float *colpart, const float *db2part, int chunks, int n_max, int N,
-                      int F, int B, float *grad, float *param, float *m, float *v, double lr, double beta1,
-                      double beta2, double eps, int *step_counter, const float *loss_for_tail, hipStream_t st,
-                      float *w1_slab);
+                      int F, int B, float *grad, const AdamFuse *adam, const float *loss_for_tail, hipStream_t st);
 int gmc_loss_tail_launch(const float *loss, int B, float *slot, hipStream_t st);
 
 // ---- SpMM (spmm.hip: row kernels, spmm_lds.hip: LDS-tiled) ---------------------------------------------------------

@@ -7,6 +7,7 @@ All kernels are enqueued on torch's current HIP stream through ``gcnmaxcut.h``.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import os
 from typing import Dict, List, Optional, Sequence, Tuple
@@ -59,7 +60,6 @@ class FusedEngine:
         self.step_dev = torch.zeros(1, dtype=torch.int32, device=self.device)  # device mirror of step_count
         self._dev_step = 0   # what step_dev holds (host shadow): replayed / device-stepped launches advance both
         self._ws: Optional[torch.Tensor] = None
-        self._model = hip.GmcModel()
         self._refresh_model()
         # slab copy of conv1.weight for the fused forward (gmc_model.W1_slab): used by the calls that ask for it
         # (FusedTrainer's steps), kept current by the fused Adam kernels, re-built when torch wrote the parameters
@@ -115,18 +115,16 @@ class FusedEngine:
             self._slab_sig = sig
         return hip.ptr(self.w1_slab)
 
-    def _model_ref(self, slab: bool, loss: str = "cut"):
-        """byref(gmc_model) for a call; ``slab``: with the (current) slab copy of W1; ``loss``: the loss the call
-        computes (GMC_MODEL_LOSS_EXPECTED in the flags for ``expected_cut``; a bad name raises ValueError)."""
-        flags = hip.MODEL_GRAD_TAIL | (hip.MODEL_LOSS_EXPECTED if hip.loss_kind(loss) else 0)
-        self._model.W1_slab = self.ensure_slab() if slab else None
-        self._model.flags = flags
-        return C.byref(self._model)
-
-    def _model_done(self) -> None:
-        """After a call that went through :meth:`_model_ref`: the struct is the default one again."""
-        self._model.W1_slab = None
-        self._model.flags = hip.MODEL_GRAD_TAIL
+    def _call_model(self, slab: bool = False, loss: str = "cut") -> hip.GmcModel:
+        """A call's own gmc_model: a copy of the resident one (weights, dropout); ``slab``: with the (current) slab copy
+        of W1; ``loss``: the loss the call computes (GMC_MODEL_LOSS_EXPECTED in the flags for ``expected_cut``).  The
+        resident struct is never written for a call, so there is nothing to restore after one."""
+        model = hip.GmcModel.from_buffer_copy(self._model)
+        if slab:
+            model.W1_slab = self.ensure_slab()
+        if hip.loss_kind(loss):
+            model.flags |= hip.MODEL_LOSS_EXPECTED
+        return model
 
     def set_dropout(self, p: float, seed: Optional[int] = None) -> None:
         """F.dropout between the layers (TrainingNeural.py:82) for the next forward / training calls:
@@ -144,6 +142,16 @@ class FusedEngine:
 
     def dropout_state(self) -> Tuple[float, int]:
         return float(self._model.dropout_p), (int(self._model.dropout_seed_hi) << 32) | int(self._model.dropout_seed_lo)
+
+    @contextlib.contextmanager
+    def dropout(self, p: float, seed: Optional[int] = None):
+        """``with eng.dropout(p, seed):`` - :meth:`set_dropout` for the calls inside, the previous (p, seed) after them."""
+        before = self.dropout_state()
+        self.set_dropout(p, seed)
+        try:
+            yield
+        finally:
+            self.set_dropout(*before)
 
     def adopt(self, module: torch.nn.Module) -> None:
         """Make ``module.conv{1,2}.{weight,bias}`` views of the flat buffer (values kept)."""
@@ -166,12 +174,21 @@ class FusedEngine:
     def make_batch(self, handles, values=None) -> GraphBatch:
         return GraphBatch(handles, values, self.device)
 
-    # ---- scratch
+    # ---- scratch and outputs
     def _workspace(self, batch: GraphBatch, training: bool) -> Tuple[torch.Tensor, int]:
         need = int(self.lib.gmc_workspace_bytes(batch.ref(), C.byref(self._model), int(training)))
         if self._ws is None or self._ws.numel() < need:
             self._ws = torch.empty(max(need, 256), dtype=torch.uint8, device=self.device)
         return self._ws, self._ws.numel()
+
+    def _outputs(self, batch: GraphBatch, out=None, want_loss: bool = True):
+        """(P [R,3], S [R], losses [B]) of a call: the caller's ``out``, else fresh (S, losses only when ``want_loss``)."""
+        if out is not None:
+            return out
+        P = torch.empty((batch.R, 3), dtype=torch.float32, device=self.device)
+        S = torch.empty(batch.R, dtype=torch.int32, device=self.device) if want_loss else None
+        losses = torch.empty(batch.B, dtype=torch.float32, device=self.device) if want_loss else None
+        return P, S, losses
 
     # ---- compute
     def workspace_bytes(self, batch: GraphBatch, training: bool) -> int:
@@ -182,17 +199,24 @@ class FusedEngine:
         """P [R,3] (and S [R], loss [B] when ``want_loss``) - TrainingNeural.py:79-85.
         ``ws``: caller-owned scratch (kept alive for a later :meth:`backward_from_gp`).  ``loss``: ``"cut"`` (the
         reference's -C * cut of the argmax decode) or ``"expected_cut"`` (the relaxed loss: ``hip.LOSS_KINDS``)."""
+        return self._forward(batch, None, C_, want_loss, ws, loss)
+
+    def _forward(self, batch: GraphBatch, X: Optional[torch.Tensor], C_: float, want_loss: bool,
+                 ws: Optional[torch.Tensor], loss: str):
+        """:meth:`forward` (``X`` None: gmc_forward) and :meth:`forward_features` (gmc_forward_features)."""
         hip.loss_kind(loss)
-        P = torch.empty((batch.R, 3), dtype=torch.float32, device=self.device)
-        S = torch.empty(batch.R, dtype=torch.int32, device=self.device) if want_loss else None
-        losses = torch.empty(batch.B, dtype=torch.float32, device=self.device) if want_loss else None
+        P, S, losses = self._outputs(batch, None, want_loss)
+        Xd = None if X is None else self.pad_features(batch, X)
         if batch.B == 0:   # nothing to launch (empty tensors have no device pointer to hand over)
             return P, S, losses
-        ws, nbytes = (ws, ws.numel()) if ws is not None else self._workspace(batch, False)
-        rc = self.lib.gmc_forward(batch.ref(), self._model_ref(False, loss), C_, hip.ptr(ws), nbytes,
-                                  hip.ptr(P), hip.ptr(S), hip.ptr(losses), hip.stream())
-        self._model_done()
-        hip.check(rc, "gmc_forward")
+        if ws is None:   # the engine's own scratch; the dense plan gets one of its own
+            ws = (self._workspace(batch, False)[0] if X is None else
+                  torch.empty(self.workspace_bytes_features(batch, False), dtype=torch.uint8, device=self.device))
+        name, feat = ("gmc_forward", ()) if X is None else ("gmc_forward_features", (hip.ptr(Xd), Xd.shape[1]))
+        model = self._call_model(loss=loss)
+        rc = getattr(self.lib, name)(batch.ref(), C.byref(model), *feat, C_, hip.ptr(ws), ws.numel(), hip.ptr(P),
+                                     hip.ptr(S), hip.ptr(losses), hip.stream())
+        hip.check(rc, name)
         return P, S, losses
 
     def train_fwd_bwd(self, batch: GraphBatch, C_: float = 1.0, out=None, ws: Optional[torch.Tensor] = None,
@@ -202,20 +226,14 @@ class FusedEngine:
         whose launches are captured into a hipGraph must own it: the engine's own scratch moves
         whenever a later call needs more).  ``loss``: as for :meth:`forward`."""
         hip.loss_kind(loss)
-        if out is None:
-            P = torch.empty((batch.R, 3), dtype=torch.float32, device=self.device)
-            S = torch.empty(batch.R, dtype=torch.int32, device=self.device)
-            losses = torch.empty(batch.B, dtype=torch.float32, device=self.device)
-        else:
-            P, S, losses = out
+        P, S, losses = self._outputs(batch, out)
         if batch.B == 0:   # no graphs: zero gradient AND zero loss in the tail slot, nothing to launch
             self.grad[:self.count + 1].zero_()
             return P, S, losses
         ws, nbytes = (ws, ws.numel()) if ws is not None else self._workspace(batch, True)
-        rc = self.lib.gmc_train_fwd_bwd(batch.ref(), self._model_ref(slab, loss), C_, hip.ptr(ws), nbytes,
-                                        hip.ptr(P), hip.ptr(S), hip.ptr(losses), hip.ptr(self.grad),
-                                        hip.stream())
-        self._model_done()
+        model = self._call_model(slab, loss)
+        rc = self.lib.gmc_train_fwd_bwd(batch.ref(), C.byref(model), C_, hip.ptr(ws), nbytes, hip.ptr(P), hip.ptr(S),
+                                        hip.ptr(losses), hip.ptr(self.grad), hip.stream())
         hip.check(rc, "gmc_train_fwd_bwd")
         return P, S, losses
 
@@ -230,12 +248,7 @@ class FusedEngine:
         :meth:`forward` (gmc_train_step_loss_f32; a one-graph ``expected_cut`` step launches the head on its own)."""
         kind = hip.loss_kind(loss)
         ws, nbytes = (ws, ws.numel()) if ws is not None else self._workspace(batch, True)
-        if out is None:
-            P = torch.empty((batch.R, 3), dtype=torch.float32, device=self.device)
-            S = torch.empty(batch.R, dtype=torch.int32, device=self.device)
-            losses = torch.empty(batch.B, dtype=torch.float32, device=self.device)
-        else:
-            P, S, losses = out
+        P, S, losses = out if out is not None else self._outputs(batch)
         tail = (self.ensure_slab() if slab else None, hip.stream())
         rc = self.lib.gmc_train_step_loss_f32(batch.ref(), self.N, self.Fp, hip.ptr(self.flat), C_, kind, hip.ptr(ws),
                                               nbytes, hip.ptr(P), hip.ptr(S), loss_ptr or hip.ptr(losses),
@@ -252,12 +265,25 @@ class FusedEngine:
                          ws: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
         """Gradients for a caller-supplied dLoss/dP (autograd path); ``ws`` must be the
         (training-sized) workspace of the forward that produced ``P``."""
-        ws, nbytes = (ws, ws.numel()) if ws is not None else self._workspace(batch, True)
-        rc = self.lib.gmc_backward_from_gp(batch.ref(), C.byref(self._model), hip.ptr(ws), nbytes,
-                                           hip.ptr(P), hip.ptr(GP.contiguous()), hip.ptr(self.grad),
-                                           hip.stream())
-        hip.check(rc, "gmc_backward_from_gp")
-        return self.views(self.grad)
+        return self._backward(batch, None, P, GP, ws, False)[0]
+
+    def _backward(self, batch: GraphBatch, X: Optional[torch.Tensor], P: torch.Tensor, GP: torch.Tensor,
+                  ws: Optional[torch.Tensor], want_dx: bool):
+        """:meth:`backward_from_gp` (``X`` None: gmc_backward_from_gp) and :meth:`backward_features_from_gp`
+        (gmc_backward_features_from_gp): (parameter gradients, dX or None)."""
+        Xd = None if X is None else self.pad_features(batch, X)
+        dX = torch.empty_like(Xd) if want_dx else None
+        if batch.B == 0:
+            self.grad[:self.count].zero_()
+        else:
+            if ws is None:
+                ws = self._workspace(batch, True)[0]
+            name, feat, dx = (("gmc_backward_from_gp", (), ()) if X is None else
+                              ("gmc_backward_features_from_gp", (hip.ptr(Xd), Xd.shape[1]), (hip.ptr(dX), Xd.shape[1])))
+            rc = getattr(self.lib, name)(batch.ref(), C.byref(self._model), *feat, hip.ptr(ws), ws.numel(), hip.ptr(P),
+                                         hip.ptr(GP.to(torch.float32).contiguous()), hip.ptr(self.grad), *dx, hip.stream())
+            hip.check(rc, name)
+        return self.views(self.grad), (dX[:, :self.N] if want_dx else None)
 
     # ---- features that are not the padded adjacency (layer 1 is a dense GEMM: gmc_forward_features)
     def workspace_bytes_features(self, batch: GraphBatch, training: bool) -> int:
@@ -284,36 +310,13 @@ class FusedEngine:
         graphs stacked): the layer-1 feature transform is the library's fp32 MFMA GEMM.  ``ws``: caller-owned scratch
         of :meth:`workspace_bytes_features` bytes (kept alive for :meth:`backward_features_from_gp`).  ``loss``: as for
         :meth:`forward`."""
-        hip.loss_kind(loss)
-        P = torch.empty((batch.R, 3), dtype=torch.float32, device=self.device)
-        S = torch.empty(batch.R, dtype=torch.int32, device=self.device) if want_loss else None
-        losses = torch.empty(batch.B, dtype=torch.float32, device=self.device) if want_loss else None
-        Xd = self.pad_features(batch, X)
-        if batch.B == 0:
-            return P, S, losses
-        if ws is None:
-            ws = torch.empty(self.workspace_bytes_features(batch, False), dtype=torch.uint8, device=self.device)
-        rc = self.lib.gmc_forward_features(batch.ref(), self._model_ref(False, loss), hip.ptr(Xd), Xd.shape[1], C_,
-                                           hip.ptr(ws), ws.numel(), hip.ptr(P), hip.ptr(S), hip.ptr(losses),
-                                           hip.stream())
-        self._model_done()
-        hip.check(rc, "gmc_forward_features")
-        return P, S, losses
+        return self._forward(batch, X, C_, want_loss, ws, loss)
 
     def backward_features_from_gp(self, batch: GraphBatch, X: torch.Tensor, P: torch.Tensor, GP: torch.Tensor,
                                   ws: torch.Tensor, want_dx: bool = True):
         """(parameter gradients, dX or None) for a caller-supplied dLoss/dP; ``ws``: the training-sized scratch of the
         :meth:`forward_features` call that produced ``P`` from the same ``X``.  ``want_dx`` = False skips the dX GEMM."""
-        Xd = self.pad_features(batch, X)
-        dX = torch.empty_like(Xd) if want_dx else None
-        if batch.B == 0:
-            self.grad[:self.count].zero_()
-            return self.views(self.grad), (dX[:, :self.N] if want_dx else None)
-        rc = self.lib.gmc_backward_features_from_gp(
-            batch.ref(), C.byref(self._model), hip.ptr(Xd), Xd.shape[1], hip.ptr(ws), ws.numel(), hip.ptr(P),
-            hip.ptr(GP.to(torch.float32).contiguous()), hip.ptr(self.grad), hip.ptr(dX), Xd.shape[1], hip.stream())
-        hip.check(rc, "gmc_backward_features_from_gp")
-        return self.views(self.grad), (dX[:, :self.N] if want_dx else None)
+        return self._backward(batch, X, P, GP, ws, want_dx)
 
     def adam_step(self, lr: float, betas=(0.9, 0.999), eps: float = 1e-8) -> None:
         """torch.optim.Adam.step over the flat buffer (TrainingNeural.py:386)."""
@@ -332,24 +335,19 @@ class FusedEngine:
         copy as well (which must be current: :meth:`ensure_slab`).  ``publish`` = (device floats, device-side
         address of pinned host memory): the values are stored there by the one-wave launch that also advances the
         step counter, in front of the Adam sweep (two launches for publish + Adam + tick instead of three)."""
+        keep_slab = slab and self.slab_enabled
+        bufs = (hip.ptr(self.flat), hip.ptr(self.grad), hip.ptr(self.m), hip.ptr(self.v))
         if publish is not None:
-            src, dst = publish
-            rc = self.lib.gmc_publish_adam_devstep_model_f32(
-                hip.ptr(src), src.numel(), dst, hip.ptr(self.flat), hip.ptr(self.grad), hip.ptr(self.m), hip.ptr(self.v),
-                self.N, self.Fp, self.ensure_slab() if (slab and self.slab_enabled) else None, lr, betas[0], betas[1], eps,
-                hip.ptr(self.step_dev), hip.stream())
-            if not (slab and self.slab_enabled):
-                self._slab_sig = None
-        elif slab and self.slab_enabled:
-            rc = self.lib.gmc_adam_devstep_model_f32(hip.ptr(self.flat), hip.ptr(self.grad), hip.ptr(self.m),
-                                                     hip.ptr(self.v), self.N, self.Fp, self.ensure_slab(), lr, betas[0],
-                                                     betas[1], eps, hip.ptr(self.step_dev), hip.stream())
+            name, (src, dst) = "gmc_publish_adam_devstep_model_f32", publish
+            args = (hip.ptr(src), src.numel(), dst, *bufs, self.N, self.Fp, self.ensure_slab() if keep_slab else None)
+        elif keep_slab:
+            name, args = "gmc_adam_devstep_model_f32", (*bufs, self.N, self.Fp, self.ensure_slab())
         else:
-            rc = self.lib.gmc_adam_devstep_f32(hip.ptr(self.flat), hip.ptr(self.grad), hip.ptr(self.m),
-                                               hip.ptr(self.v), self.count, lr, betas[0], betas[1], eps,
-                                               hip.ptr(self.step_dev), hip.stream())
-            self._slab_sig = None
-        hip.check(rc, "gmc_adam_devstep_f32")
+            name, args = "gmc_adam_devstep_f32", (*bufs, self.count)
+        rc = getattr(self.lib, name)(*args, lr, betas[0], betas[1], eps, hip.ptr(self.step_dev), hip.stream())
+        if not keep_slab:
+            self._slab_sig = None   # W1 moved, the slab copy did not
+        hip.check(rc, name)
         self.step_count += 1
         self._dev_step += 1
 

@@ -15,18 +15,6 @@ import torch
 _PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("GCN_MAXCUT_LIB") or os.path.join(_PKG, "lib", "libgcnmaxcut_hip.so")
 
-# every symbol include/gcnmaxcut.h declares (tests check the .so exports all of them)
-SYMBOLS = (
-    "gmc_version", "gmc_error_string", "gmc_spmm_f32", "gmc_dense_hw2_f32", "gmc_head_f32",
-    "gmc_adam_f32", "gmc_workspace_bytes", "gmc_forward", "gmc_train_fwd_bwd",
-    "gmc_backward_from_gp", "gmc_probe_begin", "gmc_probe_end", "gmc_set_fuse", "gmc_decode_sample_f32", "gmc_adam_devstep_f32", "gmc_ell_arrange_host", "gmc_ell_slots_for", "gmc_train_step_f32",
-    "gmc_adam_devstep_model_f32", "gmc_w1_slab_floats", "gmc_w1_slab_f32", "gmc_host_device_pointer", "gmc_publish_f32",
-    "gmc_publish_adam_devstep_model_f32", "gmc_probe_flavours", "gmc_lds_flavours", "gmc_refine_order_host",
-    "gmc_refine_local_f32", "gmc_refine_anneal_f32", "gmc_refine_anneal_staged",
-    "gmc_gemm_f32", "gmc_workspace_bytes_features", "gmc_forward_features", "gmc_backward_features_from_gp",
-    "gmc_head_loss_f32", "gmc_train_step_loss_f32", "gmc_cut_loss_f32",
-)
-
 MAX_GRAPH_NODES = 4096
 ANNEAL_LEVELS = 1024  # GMC_ANNEAL_LEVELS: entries of the level table gmc_refine_anneal_f32 reads
 MODEL_GRAD_TAIL = 1   # gmc_model.flags: grad has a tail slot that receives the batch's loss sum
@@ -87,65 +75,65 @@ def loss_name(name: Optional[str]) -> str:
     return next(k for k, v in LOSS_KINDS.items() if v == kind)
 
 
+def _api() -> dict:
+    """name -> (restype, argtypes) of every symbol include/gcnmaxcut.h declares: the one place an entry point is
+    added to (tests check the .so exports all of them)."""
+    vp, i32, i64, f32, f64, sz, i = C.c_void_p, C.c_int32, C.c_int64, C.c_float, C.c_double, C.c_size_t, C.c_int
+    B, M = C.POINTER(GmcBatch), C.POINTER(GmcModel)
+    adam = [f64, f64, f64, f64]   # lr, beta1, beta2, eps
+    return {
+        "gmc_version": (i, []),
+        "gmc_error_string": (C.c_char_p, [i]),
+        "gmc_spmm_f32": (i, [vp, vp, vp, vp, vp, i64, vp, i, vp, i64, i32, i32, i32, vp, vp, vp]),
+        "gmc_dense_hw2_f32": (i, [vp, i64, vp, vp, vp, i32, i32, vp]),
+        "gmc_head_f32": (i, [B, vp, i32, vp, f32, vp, vp, vp, vp, vp, vp]),
+        "gmc_head_loss_f32": (i, [B, vp, i32, vp, f32, i32, vp, vp, vp, vp, vp, vp]),
+        "gmc_cut_loss_f32": (i, [B, vp, f32, i32, vp, vp, vp]),
+        "gmc_adam_f32": (i, [vp, vp, vp, vp, i64, *adam, i32, vp]),
+        "gmc_adam_devstep_f32": (i, [vp, vp, vp, vp, i64, *adam, vp, vp]),
+        "gmc_adam_devstep_model_f32": (i, [vp, vp, vp, vp, i32, i32, vp, *adam, vp, vp]),
+        "gmc_publish_f32": (i, [vp, i32, vp, vp]),
+        "gmc_publish_adam_devstep_model_f32": (i, [vp, i32, vp, vp, vp, vp, vp, i32, i32, vp, *adam, vp, vp]),
+        "gmc_host_device_pointer": (i, [vp, C.POINTER(vp)]),
+        "gmc_w1_slab_floats": (sz, [i32, i32]),
+        "gmc_w1_slab_f32": (i, [vp, i32, i32, vp, vp]),
+        "gmc_workspace_bytes": (sz, [B, M, i]),
+        "gmc_forward": (i, [B, M, f32, vp, sz, vp, vp, vp, vp]),
+        "gmc_train_fwd_bwd": (i, [B, M, f32, vp, sz, vp, vp, vp, vp, vp]),
+        "gmc_train_step_f32": (i, [B, i32, i32, vp, f32, vp, sz, vp, vp, vp, vp, vp, vp, *adam, vp, vp, vp]),
+        "gmc_train_step_loss_f32": (i, [B, i32, i32, vp, f32, i32, vp, sz, vp, vp, vp, vp, vp, vp, *adam, vp, vp, vp]),
+        "gmc_backward_from_gp": (i, [B, M, vp, sz, vp, vp, vp, vp]),
+        "gmc_workspace_bytes_features": (sz, [B, M, i]),
+        "gmc_forward_features": (i, [B, M, vp, i64, f32, vp, sz, vp, vp, vp, vp]),
+        "gmc_backward_features_from_gp": (i, [B, M, vp, i64, vp, sz, vp, vp, vp, vp, i64, vp]),
+        "gmc_gemm_f32": (i, [i32, i32, i32, i32, i32, vp, i64, vp, i64, vp, vp, i64, vp]),
+        "gmc_set_fuse": (i, [i]),
+        "gmc_probe_begin": (i, [i32]),
+        "gmc_probe_end": (i, [vp, vp, i32]),
+        "gmc_probe_flavours": (i, [vp, i32]),
+        "gmc_lds_flavours": (i, [B, i32, i32, vp, i32]),
+        "gmc_ell_arrange_host": (i, [i32, vp, vp, vp, vp, i32, vp, vp]),
+        "gmc_ell_slots_for": (i, [i32, vp, i32]),
+        "gmc_decode_sample_f32": (i, [B, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp]),
+        "gmc_refine_order_host": (i, [i32, vp, vp, vp, vp, vp, vp, i32]),
+        "gmc_refine_local_f32": (i, [B, vp, vp, vp, i32, vp, i32, vp, vp, vp, vp, vp, vp]),
+        "gmc_refine_anneal_f32": (i, [B, vp, vp, vp, i32, vp, vp, i32, vp, C.c_uint64, i32, vp, vp, vp, vp, vp, vp, vp]),
+        "gmc_refine_anneal_staged": (i, [B]),
+    }
+
+
+_API = _api()
+SYMBOLS = tuple(_API)
+
 _lib: Optional[C.CDLL] = None
 
 
 def _declare(lib: C.CDLL) -> None:
-    vp, i32, i64, f32, sz = C.c_void_p, C.c_int32, C.c_int64, C.c_float, C.c_size_t
-    lib.gmc_version.restype = C.c_int
-    lib.gmc_error_string.restype = C.c_char_p
-    lib.gmc_error_string.argtypes = [C.c_int]
-    lib.gmc_spmm_f32.argtypes = [vp, vp, vp, vp, vp, i64, vp, C.c_int, vp, i64, i32, i32, i32, vp, vp, vp]
-    lib.gmc_dense_hw2_f32.argtypes = [vp, i64, vp, vp, vp, i32, i32, vp]
-    lib.gmc_head_f32.argtypes = [C.POINTER(GmcBatch), vp, i32, vp, f32, vp, vp, vp, vp, vp, vp]
-    lib.gmc_head_loss_f32.argtypes = [C.POINTER(GmcBatch), vp, i32, vp, f32, i32, vp, vp, vp, vp, vp, vp]
-    lib.gmc_cut_loss_f32.argtypes = [C.POINTER(GmcBatch), vp, f32, i32, vp, vp, vp]
-    lib.gmc_train_step_loss_f32.argtypes = [C.POINTER(GmcBatch), i32, i32, vp, f32, i32, vp, sz, vp, vp, vp, vp, vp, vp,
-                                            C.c_double, C.c_double, C.c_double, C.c_double, vp, vp, vp]
-    lib.gmc_adam_f32.argtypes = [vp, vp, vp, vp, i64, C.c_double, C.c_double, C.c_double, C.c_double, i32, vp]
-    lib.gmc_workspace_bytes.restype = sz
-    lib.gmc_workspace_bytes.argtypes = [C.POINTER(GmcBatch), C.POINTER(GmcModel), C.c_int]
-    lib.gmc_forward.argtypes = [C.POINTER(GmcBatch), C.POINTER(GmcModel), f32, vp, sz, vp, vp, vp, vp]
-    lib.gmc_train_fwd_bwd.argtypes = [C.POINTER(GmcBatch), C.POINTER(GmcModel), f32, vp, sz, vp, vp, vp, vp, vp]
-    lib.gmc_backward_from_gp.argtypes = [C.POINTER(GmcBatch), C.POINTER(GmcModel), vp, sz, vp, vp, vp, vp]
-    lib.gmc_adam_devstep_f32.argtypes = [vp, vp, vp, vp, i64, C.c_double, C.c_double, C.c_double, C.c_double, vp, vp]
-    lib.gmc_ell_arrange_host.argtypes = [i32, vp, vp, vp, vp, i32, vp, vp]
-    lib.gmc_ell_slots_for.argtypes = [i32, vp, i32]
-    lib.gmc_train_step_f32.argtypes = [C.POINTER(GmcBatch), i32, i32, vp, f32, vp, sz, vp, vp, vp, vp, vp, vp,
-                                       C.c_double, C.c_double, C.c_double, C.c_double, vp, vp, vp]
-    lib.gmc_adam_devstep_model_f32.argtypes = [vp, vp, vp, vp, i32, i32, vp, C.c_double, C.c_double, C.c_double,
-                                               C.c_double, vp, vp]
-    lib.gmc_w1_slab_floats.argtypes = [i32, i32]
-    lib.gmc_w1_slab_floats.restype = sz
-    lib.gmc_w1_slab_f32.argtypes = [vp, i32, i32, vp, vp]
-    lib.gmc_set_fuse.argtypes = [C.c_int]
-    lib.gmc_decode_sample_f32.argtypes = [C.POINTER(GmcBatch), vp, vp, vp, i32, vp, vp, vp, vp, vp, vp]
-    lib.gmc_refine_order_host.argtypes = [i32, vp, vp, vp, vp, vp, vp, i32]
-    lib.gmc_refine_local_f32.argtypes = [C.POINTER(GmcBatch), vp, vp, vp, i32, vp, i32, vp, vp, vp, vp, vp, vp]
-    lib.gmc_refine_anneal_f32.argtypes = [C.POINTER(GmcBatch), vp, vp, vp, i32, vp, vp, i32, vp, C.c_uint64, i32,
-                                          vp, vp, vp, vp, vp, vp, vp]
-    lib.gmc_refine_anneal_staged.argtypes = [C.POINTER(GmcBatch)]
-    lib.gmc_gemm_f32.argtypes = [i32, i32, i32, i32, i32, vp, i64, vp, i64, vp, vp, i64, vp]
-    lib.gmc_workspace_bytes_features.restype = sz
-    lib.gmc_workspace_bytes_features.argtypes = [C.POINTER(GmcBatch), C.POINTER(GmcModel), C.c_int]
-    lib.gmc_forward_features.argtypes = [C.POINTER(GmcBatch), C.POINTER(GmcModel), vp, i64, f32, vp, sz, vp, vp, vp, vp]
-    lib.gmc_backward_features_from_gp.argtypes = [C.POINTER(GmcBatch), C.POINTER(GmcModel), vp, i64, vp, sz, vp, vp,
-                                                  vp, vp, i64, vp]
-    lib.gmc_probe_begin.argtypes = [i32]
-    lib.gmc_probe_end.argtypes = [vp, vp, i32]
-    lib.gmc_probe_flavours.argtypes = [vp, i32]
-    lib.gmc_lds_flavours.argtypes = [C.POINTER(GmcBatch), i32, i32, vp, i32]
-    lib.gmc_host_device_pointer.argtypes = [vp, C.POINTER(vp)]
-    lib.gmc_publish_f32.argtypes = [vp, i32, vp, vp]
-    lib.gmc_publish_adam_devstep_model_f32.argtypes = [vp, i32, vp, vp, vp, vp, vp, i32, i32, vp, C.c_double, C.c_double,
-                                                       C.c_double, C.c_double, vp, vp]
+    for name, (restype, argtypes) in _API.items():
+        fn = getattr(lib, name)
+        fn.restype, fn.argtypes = restype, argtypes
     lib.gmc_debug_set_device_cus.argtypes = [C.c_int]   # test hook (not part of gcnmaxcut.h)
     lib.gmc_debug_set_device_cus.restype = C.c_int
-    for name in SYMBOLS:
-        fn = getattr(lib, name)
-        if name not in ("gmc_version", "gmc_error_string", "gmc_workspace_bytes", "gmc_w1_slab_floats",
-                        "gmc_workspace_bytes_features"):
-            fn.restype = C.c_int
 
 
 def load() -> C.CDLL:

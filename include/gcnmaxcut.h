@@ -324,6 +324,19 @@ int gmc_w1_slab_f32(const float *W1, int32_t N, int32_t F, float *slab, gmc_stre
 
 /* ---- fused entry points ------------------------------------------------------------ */
 
+/* Argument checks of gmc_forward, gmc_train_fwd_bwd, gmc_train_step_loss_f32, gmc_backward_from_gp, gmc_forward_features
+ * and gmc_backward_features_from_gp: all before any HIP call, in this order - the first thing wrong decides the code.
+ *  1. the struct pointers, and X of the *_features calls                                   GMC_ERR_NULL
+ *  2. the structs: abi (GMC_ERR_ABI, before any other field is read), required pointer fields (NULL), K (CLASSES),
+ *     sizes (SHAPE), F (UNSUPPORTED), dropout_p (SHAPE), W1_slab (ALIGN), n_max (GRAPH_SIZE; > N without X: SHAPE)
+ *  3. the features: ldx < N (SHAPE), then X, ldx % 4, W1                                   GMC_ERR_ALIGN
+ *  4. workspace and the output pointers P, GP, grad                                        GMC_ERR_NULL
+ *  5. lddx < N (SHAPE), then grad, dX, lddx % 4                                            GMC_ERR_ALIGN
+ *  6. the workspace size                                                                   GMC_ERR_WORKSPACE
+ * gmc_train_step_loss_f32 looks at loss_kind (GMC_ERR_LOSS), then at param, grad, m, v, step_counter (NULL, ALIGN)
+ * before all of that: the model of step 2 is made of them.  gmc_train_fwd_bwd with GMC_MODEL_GRAD_TAIL checks last that
+ * loss is there (NULL).  The two size queries return 0 for a NULL struct or one whose abi word differs. */
+
 /* `loss` of the entry points below may be device memory or PINNED HOST memory mapped into the device: each
  * graph's value is written with one system-scope store as soon as it is final (by the loss kernel, before the
  * backward kernels of the same call run), so a host thread watching that memory has the step's loss while the

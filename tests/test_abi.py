@@ -93,6 +93,16 @@ def test_structs_carry_the_abi_word_and_it_is_checked(built):
     old_b, old_m = hip.GmcBatch(abi=100), hip.GmcModel(abi=100)
     some = C.c_void_p(4096)
     assert lib.gmc_workspace_bytes(C.byref(hip.GmcBatch()), C.byref(hip.GmcModel()), 1) >= 0
+    # the size queries read nothing else of a struct of another version either: they answer 0
+    sized = hip.GmcBatch(B=2, R=120, nnz=600, n_max=60, goff=4096, rowptr=4096, gcol=4096, lcol=4096, dinv=4096)
+    model = hip.GmcModel(N=1000, F=32, K=3, W1=4096, b1=4096, W2=4096, b2=4096)
+    for query in (lib.gmc_workspace_bytes, lib.gmc_workspace_bytes_features):
+        assert query(C.byref(sized), C.byref(model), 1) > 0
+        sized.abi = 100
+        assert query(C.byref(sized), C.byref(model), 1) == 0
+        sized.abi, model.abi = hip.ABI_VERSION, 100
+        assert query(C.byref(sized), C.byref(model), 1) == 0
+        model.abi = hip.ABI_VERSION
     assert lib.gmc_forward(C.byref(old_b), C.byref(hip.GmcModel()), 1.0, some, 1 << 20, some, None, None, None) == -8
     assert lib.gmc_forward(C.byref(hip.GmcBatch()), C.byref(old_m), 1.0, some, 1 << 20, some, None, None, None) == -8
     assert lib.gmc_head_f32(C.byref(old_b), some, 1, some, 1.0, some, None, None, None, None, None) == -8
