@@ -59,11 +59,39 @@ def _terminal_swap(terminals: List[int]) -> Optional[Dict[int, int]]:
     return {terminals[1]: a, terminals[2]: b, a: terminals[1], b: terminals[2]}
 
 
+def terminal_relabelling(terminals: List[int], number_classes: int) -> Optional[Dict[int, int]]:
+    """The label permutation {old: new} that moves ``number_classes`` given terminals onto the labels 0..K-1
+    (``terminals[i]`` becomes node i, the terminal of class i), or None when the list does not hold exactly K distinct
+    nodes.  The labels of 0..K-1 that are displaced take the terminals' old labels in ascending order; every other
+    node keeps its label."""
+    K = int(number_classes)
+    if len(terminals) != K or len(set(terminals)) != K:
+        return None
+    perm = {int(t): i for i, t in enumerate(terminals)}
+    displaced = sorted(set(range(K)) - set(perm))
+    freed = sorted(set(perm) - set(range(K)))
+    perm.update(zip(displaced, freed))
+    return perm
+
+
+def move_terminals_to_front(graph, terminals: List[int], number_classes: int) -> bool:
+    """Relabel ``graph`` in place (through :func:`swap_graph_nodes`) so that its ``number_classes`` terminals are the
+    nodes 0..K-1; False (graph untouched) when :func:`terminal_relabelling` refuses the list."""
+    perm = terminal_relabelling(terminals, number_classes)
+    if perm is None or not all(graph.has_node(t) for t in terminals):
+        return False
+    # swap_graph_nodes renames node `label` to the KEY whose value is `label`: hand it the inverse permutation
+    swap_graph_nodes(graph, {new: old for old, new in perm.items()})
+    return True
+
+
 def process_graphs_from_folder(all_graphs: Dict, all_terminals: Dict, max_nodes: int,
                                save_batch_size: Optional[int] = None,
-                               output_filename_prefix: str = "processed_graphs") -> Dict:
+                               output_filename_prefix: str = "processed_graphs", number_classes: int = 3) -> Dict:
     """Normalise terminals to node ids 0,1,2 and emit the training dataset
-    (graphExtender.py:50-132)."""
+    (graphExtender.py:50-132).  ``number_classes`` other than 3 (extension): the K terminals of every graph move onto
+    the labels 0..K-1 (:func:`move_terminals_to_front`), graphs whose terminal list does not hold K distinct nodes are
+    skipped, and the items carry ``list(range(K))``; 3 is the reference's path."""
     datasetItem = {}
     i = 0
     skipped = 0
@@ -71,18 +99,23 @@ def process_graphs_from_folder(all_graphs: Dict, all_terminals: Dict, max_nodes:
     try:
         for filename, graph in all_graphs.items():
             terminals = all_terminals[filename]
-            mapping = _terminal_swap(terminals)
-            if mapping is None:
-                skipped += 1
-                continue
-            swap_graph_nodes(graph, mapping)
+            if number_classes != 3:
+                if not move_terminals_to_front(graph, terminals, number_classes):
+                    skipped += 1
+                    continue
+            else:
+                mapping = _terminal_swap(terminals)
+                if mapping is None:
+                    skipped += 1
+                    continue
+                swap_graph_nodes(graph, mapping)
             print(f"Terminal swapped {i}")
 
             handle = from_networkx(graph).to(TORCH_DEVICE)
             q_torch = adjacency_tensor(graph, torch_dtype=TORCH_DTYPE, torch_device=TORCH_DEVICE)
             full_matrix = extend_matrix_torch_2(q_torch, max_nodes, torch_dtype=TORCH_DTYPE,
                                                 torch_device=TORCH_DEVICE)
-            datasetItem[i] = [handle, full_matrix, graph, [0, 1, 2]]
+            datasetItem[i] = [handle, full_matrix, graph, list(range(number_classes))]
             i += 1
 
             if save_batch_size and (i % save_batch_size == 0):

@@ -54,15 +54,29 @@ def calculate_cut_value(partition_assignment: List[int], graph) -> int:
 
 
 def simple_partition_assignment(node_probabilities: torch.Tensor) -> List[int]:
-    """argmax decode with the terminals forced to 0,1,2 (TestingNeuralNetwork.py:100-122)."""
+    """argmax decode with the terminals forced to 0,1,2 (TestingNeuralNetwork.py:100-122); for probabilities of K != 3
+    columns the first min(K, n) nodes are the terminals of classes 0..K-1."""
     part = torch.argmax(node_probabilities, dim=1).cpu().numpy().tolist()
-    if len(part) >= 3:
-        part[0], part[1], part[2] = 0, 1, 2
+    K = int(node_probabilities.shape[1])
+    if K == 3:   # the reference's lines: they differ from the loop below only for n < 3, where they fix nothing
+        if len(part) >= 3:
+            part[0], part[1], part[2] = 0, 1, 2
+        return part
+    for i in range(min(K, len(part))):
+        part[i] = i
     return part
+
+
+def _three_classes_only(what: str, classes: int) -> None:
+    """The sampler and the refinement kernels (decode.hip, refine.hip, anneal.hip) are 3-class."""
+    if int(classes) != 3:
+        raise ValueError(f"{what} is implemented for number_classes = 3 only, got {int(classes)} classes: use the "
+                         "argmax decode (simple_partition_assignment) for a model with another number_classes")
 
 
 def _sample_on_gpu(batch: GraphBatch, P: torch.Tensor, iterations: int):
     """Draw the uniforms in the reference's order and run the fused sampler + cut count."""
+    _three_classes_only("the sampling post-processing", P.shape[1])
     sizes = [int(n) - 3 for n in batch.sizes]
     draws = [np.random.rand(iterations, m) for m in sizes]          # graph -> iteration -> node
     uoff = np.zeros(batch.B + 1, np.int64)
@@ -161,18 +175,23 @@ def post_processing_optimization(node_probabilities, graph, iterations: int = 20
     return best_assign.cpu().tolist(), _as_number(best_cut.item())
 
 
-def local_search_optimization(partition_assignment, graph, max_sweeps: int = 100) -> Tuple[List[int], Any]:
+def local_search_optimization(partition_assignment, graph, max_sweeps: int = 100,
+                              number_classes: int = 3) -> Tuple[List[int], Any]:
     """Refine one assignment of ``graph`` (e.g. ``simple_partition_assignment``'s) by single-node moves on the GPU
     (extension, include/gcnmaxcut.h ``gmc_refine_local_f32``): nodes 0, 1, 2 keep their classes, every other node
     moves to the class that cuts the most of its edge weight, sweep after sweep, until a sweep moves nothing or
-    ``max_sweeps`` have run.  Returns the refined assignment and its cut value."""
+    ``max_sweeps`` have run.  Returns the refined assignment and its cut value.  The kernel is 3-class - it would treat
+    nodes 0, 1, 2 of a 2-class partition as terminals and move nodes into class 2 - so ``number_classes`` other than 3
+    (say which model the partition comes from) raises ``ValueError``."""
+    _three_classes_only("local_search_optimization", number_classes)
     dev = hip.require_gpu()
     part = np.asarray(list(partition_assignment), dtype=np.int64)
     n = graph.number_of_nodes()
     if part.shape != (n,):
         raise ValueError(f"partition_assignment has {part.size} entries, the graph {n} nodes")
     if part.size and (int(part.min()) < 0 or int(part.max()) > 2):
-        raise ValueError("partition_assignment holds a class outside 0..2")
+        raise ValueError("partition_assignment holds a class outside 0..2 (the refinement kernels are written for "
+                         "number_classes = 3)")
     if max_sweeps < 0:
         raise ValueError(f"max_sweeps must be >= 0, got {max_sweeps}")
     batch = GraphBatch([from_networkx(graph)], None, dev)
@@ -182,19 +201,22 @@ def local_search_optimization(partition_assignment, graph, max_sweeps: int = 100
 
 
 def annealing_optimization(partition_assignment, graph, sweeps: int = 100, t_start: float = 1.5, t_end: float = 0.15,
-                           seed: int = 0, max_descent_sweeps: int = 100) -> Tuple[List[int], Any]:
+                           seed: int = 0, max_descent_sweeps: int = 100, number_classes: int = 3) -> Tuple[List[int], Any]:
     """Anneal one assignment of ``graph`` on the GPU past the single-move local optima ``local_search_optimization``
     stops at (extension, include/gcnmaxcut.h ``gmc_refine_anneal_f32``): ``sweeps`` Metropolis sweeps cooling from
     ``t_start`` to ``t_end`` (in units of the graph's mean edge weight), the best state passed through kept, then the
     local search from it.  Nodes 0, 1, 2 keep their classes; the result is never worse than the input and is
-    reproducible from ``seed``.  Returns the assignment and its cut value."""
+    reproducible from ``seed``.  Returns the assignment and its cut value.  3-class like
+    :func:`local_search_optimization`: ``number_classes`` other than 3 raises ``ValueError``."""
+    _three_classes_only("annealing_optimization", number_classes)
     dev = hip.require_gpu()
     part = np.asarray(list(partition_assignment), dtype=np.int64)
     n = graph.number_of_nodes()
     if part.shape != (n,):
         raise ValueError(f"partition_assignment has {part.size} entries, the graph {n} nodes")
     if part.size and (int(part.min()) < 0 or int(part.max()) > 2):
-        raise ValueError("partition_assignment holds a class outside 0..2")
+        raise ValueError("partition_assignment holds a class outside 0..2 (the refinement kernels are written for "
+                         "number_classes = 3)")
     if sweeps < 0 or max_descent_sweeps < 0:
         raise ValueError(f"sweeps and max_descent_sweeps must be >= 0, got {sweeps} and {max_descent_sweeps}")
     batch = GraphBatch([from_networkx(graph)], None, dev)
@@ -215,7 +237,12 @@ def test_single_graph(model, dgl_graph, adjacency_matrix, nx_graph, terminals: L
         simple_cut = calculate_cut_value(simple_assignment, nx_graph)
         simple_time = time() - t0
         t0 = time()
-        post_assignment, post_cut = post_processing_optimization(node_probabilities, nx_graph, post_processing_iterations)
+        if post_processing_iterations <= 0 and node_probabilities.shape[1] != 3:
+            # argmax-only evaluation of a model with number_classes != 3 (the sampler is 3-class): no post-processing
+            post_assignment, post_cut = list(simple_assignment), simple_cut
+        else:
+            post_assignment, post_cut = post_processing_optimization(node_probabilities, nx_graph,
+                                                                     post_processing_iterations)
         post_time = time() - t0
         improvement = post_cut - simple_cut
         return {
@@ -308,6 +335,7 @@ def decode_dataset(model, processed_graphs: Dict, post_processing_iterations: in
     uniforms drawn."""
     items = list(processed_graphs.values())
     eng = model.engine()
+    _three_classes_only("decode_dataset", eng.K)
     model.eval()
     handles = [it[0] for it in items]
     vals = [h.edge_values(it[1]) for h, it in zip(handles, items)]

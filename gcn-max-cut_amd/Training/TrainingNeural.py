@@ -143,7 +143,7 @@ class GCNSoftmax(nn.Module):
         """The fused engine owning this model's parameters (created on first use)."""
         if self._engine is None:
             w1, w2 = self.conv1.weight, self.conv2.weight
-            self._engine = FusedEngine(w1.shape[0], w1.shape[1], w2.shape[1], hip.require_gpu())
+            self._engine = FusedEngine(w1.shape[0], w1.shape[1], w2.shape[1], hip.require_gpu(), kway=w2.shape[1] != 3)
         if not self._engine.owns(self):
             self._engine.adopt(self)
         return self._engine
@@ -155,6 +155,11 @@ class GCNSoftmax(nn.Module):
         except NotImplementedError:
             return self._forward_dense_features(g, inputs)
         params = [dict(self.named_parameters())[k] for k in PARAM_ORDER]
+        if eng.kway and torch.is_grad_enabled() and any(p.requires_grad for p in params):
+            raise NotImplementedError(
+                f"autograd through net(g, X) is implemented for number_classes = 3 only (this model has number_classes = "
+                f"{eng.K}): train it with train_model / train_single_epoch, and call the model under torch.no_grad() "
+                "for its probabilities")
         # F.dropout(h, p=self.dropout_frac, training=self.training) (:82): a fresh mask per call in train mode;
         # the engine's dropout is 0 outside of such a call (evaluate_model, decode, the trainer's own steps)
         with eng.dropout(self.dropout_frac if self.training else 0.0):
@@ -241,6 +246,9 @@ def cut_loss(g, P, C: float = 1.0, relaxed: bool = False):
 
     Forward keeps ``GP = dLoss/dP``; backward returns ``grad_out * GP``.  So
     ``cut_loss(g, net(g, embed.weight), relaxed=True).backward()`` trains through the HIP forward and backward."""
+    if P.dim() != 2 or P.shape[1] != 3:
+        raise ValueError(f"cut_loss takes probabilities of number_classes = 3 columns, got {tuple(P.shape)}: a model with "
+                         "another number_classes computes its loss inside train_model / evaluate_model")
     dev = hip.require_gpu()
     batch = g if isinstance(g, GraphBatch) else graph_batch_of(g, None, dev)
     return _CutLoss.apply(P, batch, float(C), "expected_cut" if relaxed else "cut")
@@ -248,10 +256,12 @@ def cut_loss(g, P, C: float = 1.0, relaxed: bool = False):
 
 # --------------------------------------------------------------------------- loss helpers (torch ops)
 def override_fixed_nodes(h):
-    """Rows 0,1,2 <- e0,e1,e2 with straight-through gradient (TrainingNeural.py:87-94)."""
-    eye = torch.eye(3, dtype=h.dtype, device=h.device)
-    head = eye + h[:3] - h[:3].detach()
-    return torch.cat([head, h[3:].clone()], dim=0)
+    """Rows 0..K-1 <- e_0..e_{K-1} with straight-through gradient, K = the number of columns (TrainingNeural.py:87-94,
+    where K is 3: rows 0,1,2 <- e0,e1,e2)."""
+    k = min(h.shape[1], h.shape[0])
+    eye = torch.eye(h.shape[1], dtype=h.dtype, device=h.device)[:k]
+    head = eye + h[:k] - h[:k].detach()
+    return torch.cat([head, h[k:].clone()], dim=0)
 
 
 def max_to_one_hot(tensor):

@@ -443,3 +443,144 @@ extern "C" int gmc_backward_features_from_gp(const gmc_batch *batch, const gmc_m
     if (!X) return GMC_ERR_NULL;   // (what tells the plain call from this one)
     return backward_call(batch, model, X, ldx, workspace, workspace_bytes, P, GP, grad, dX, lddx, stream);
 }
+
+// ---- number_classes K in 2..GMC_KWAY_MAX_CLASSES: the row-kernel sequence with the K-wide kernels of kway.hip -------------
+namespace {
+
+struct KwayWorkspace {
+    long ld;         // leading dimension of the [R,F] buffers (F rounded up to 32 floats)
+    float *T0;       // [R,ld]  dinv o (A_val @ W1[:n]), later Gs = dinv o Gpre
+    float *H;        // [R,ld]  relu(conv1), later U = dinv o (A @ Gs)
+    float *Z0;       // [R,K]
+    float *GY2;      // [R,K]
+    float *part;     // [tiles,F,K+1]
+    float *db2part;  // [B,K]
+    float *dw1part;  // [chunks,N,F]
+    size_t bytes;
+};
+
+// base == nullptr: sizes only
+KwayWorkspace kway_carve(const gmc_batch *b, const gmc_model *m, bool training, void *base) {
+    KwayWorkspace w{};
+    size_t off = 0;
+    auto take = [&](size_t floats) {
+        float *p = base ? reinterpret_cast<float *>(static_cast<char *>(base) + off) : nullptr;
+        off += align_up(floats * sizeof(float));
+        return p;
+    };
+    const size_t R = (size_t)b->R, F = (size_t)m->F, K = (size_t)m->K;
+    w.ld = (long)((F + 31) / 32 * 32);
+    w.T0 = take(R * w.ld);
+    w.H = take(R * w.ld);
+    w.Z0 = take(R * K);
+    if (training) {
+        w.GY2 = take(R * K);
+        w.part = take((size_t)gmc_hidden_tiles(b->R) * F * (K + 1));
+        w.db2part = take((size_t)b->B * K);
+        w.dw1part = take(gmc_dw1_scratch_floats(b, m->N, m->F, false));
+    }
+    w.bytes = off;
+    return w;
+}
+
+bool kway_classes_ok(int K) { return K >= 2 && K <= GMC_KWAY_MAX_CLASSES; }
+
+// steps 1 and 2 of the documented order
+int kway_check(const gmc_batch *b, const gmc_model *m) {
+    if (int rc = check_abi(b, m)) return rc;
+    if (!b->goff || !b->rowptr || !b->gcol || !b->lcol || !b->dinv) return GMC_ERR_NULL;
+    if (!m->W1 || !m->b1 || !m->W2 || !m->b2) return GMC_ERR_NULL;
+    if (!kway_classes_ok(m->K)) return GMC_ERR_CLASSES;
+    if (b->B < 0 || b->R < 0 || b->nnz < 0 || m->N <= 0 || m->F <= 0) return GMC_ERR_SHAPE;
+    if (m->F % 4 || m->F > GMC_MAX_HIDDEN) return GMC_ERR_UNSUPPORTED;  // float4 rows
+    if (!(m->dropout_p >= 0.f && m->dropout_p < 1.f)) return GMC_ERR_SHAPE;
+    if (m->dropout_p > 0.f) return GMC_ERR_UNSUPPORTED;                 // the K-class sequence has no dropout
+    if (m->W1_slab && !gmc_aligned16(m->W1_slab)) return GMC_ERR_ALIGN;
+    if (b->B > 0 && (b->n_max < m->K || b->n_max > GMC_MAX_GRAPH_NODES ||
+                     gmc_kway_head_lds_bytes(b->n_max, m->K, loss_of(m)) > GMC_KWAY_LDS_BYTES))
+        return GMC_ERR_GRAPH_SIZE;
+    if (b->n_max > m->N) return GMC_ERR_SHAPE;  // more nodes than rows of conv1.weight
+    return GMC_OK;
+}
+
+struct KwayCall {
+    const gmc_batch *b; const gmc_model *m;
+    KwayWorkspace w{}; hipStream_t st = nullptr;
+};
+
+int kway_open(KwayCall &c, bool training, void *workspace, size_t workspace_bytes, gmc_stream_t stream, const float *P,
+              const float *grad) {
+    if (int rc = kway_check(c.b, c.m)) return rc;                                    // 1. 2.
+    if (!workspace || !P || (training && !grad)) return GMC_ERR_NULL;                // 4. workspace and outputs
+    if (!gmc_aligned16(grad) || !gmc_aligned16(P) || !gmc_aligned16(c.m->W2)) return GMC_ERR_ALIGN;   // 5.
+    c.w = kway_carve(c.b, c.m, training, workspace);                                 // 6. workspace size
+    if (c.w.bytes > workspace_bytes) return GMC_ERR_WORKSPACE;
+    c.st = static_cast<hipStream_t>(stream);
+    return GMC_OK;
+}
+
+// forward and head; GY2 / db2part of the workspace are filled when it was carved for training
+int kway_forward_body(const KwayCall &c, float C, float *P, int32_t *S, float *loss) {
+    const gmc_batch *b = c.b; const gmc_model *m = c.m; const KwayWorkspace &w = c.w;
+    const int F = m->F;
+    // T0 = dinv o (A_val @ W1[:n]): a row gather of W1
+    int rc = gmc_spmm_launch(b->rowptr, b->lcol, b->vals, b->dinv, m->W1, F, nullptr, 0, w.T0, w.ld, b->R, F,
+                             group_rows(b), nullptr, nullptr, GMC_K_GATHER_W1, c.st);
+    if (rc) return rc;
+    // H = relu(dinv o (A @ T0) + b1)
+    rc = gmc_spmm_launch(b->rowptr, b->gcol, nullptr, b->dinv, w.T0, w.ld, m->b1, 1, w.H, w.ld, b->R, F, group_rows(b),
+                         nullptr, nullptr, GMC_K_AGG_FWD, c.st);
+    if (rc) return rc;
+    rc = gmc_kway_hw2_launch(w.H, w.ld, b->dinv, m->W2, w.Z0, b->R, F, m->K, c.st);
+    if (rc) return rc;
+    return gmc_kway_head_launch(b, w.Z0, m->b2, C, m->K, loss_of(m), P, S, loss, w.GY2, w.db2part, c.st);
+}
+
+int kway_backward_body(const KwayCall &c, float *grad, const float *loss_tail) {
+    const gmc_batch *b = c.b; const gmc_model *m = c.m; const KwayWorkspace &w = c.w;
+    const long F = m->F, K = m->K;
+    float *dW1 = grad, *db1 = grad + (long)m->N * F, *dW2 = db1 + F, *db2 = dW2 + F * K;
+    float *Gs = w.T0, *U = w.H;
+    int rc = gmc_kway_hidden_bwd_launch(w.H, w.ld, w.GY2, m->W2, b->dinv, Gs, w.ld, w.part, b->R, m->F, m->K, c.st);
+    if (rc) return rc;
+    rc = gmc_kway_reduce_launch(w.part, gmc_hidden_tiles(b->R), m->F, m->K, dW2, db1, w.db2part, b->B, db2, c.st);
+    if (rc) return rc;
+    // conv1 backward aggregation:  U = dinv o (A @ Gs)
+    rc = gmc_spmm_launch(b->rowptr, b->gcol, nullptr, b->dinv, Gs, w.ld, nullptr, 0, U, w.ld, b->R, m->F, group_rows(b),
+                         nullptr, nullptr, GMC_K_AGG_BWD, c.st);
+    if (rc) return rc;
+    rc = gmc_dw1_launch(b, U, w.ld, dW1, w.dw1part, m->N, m->F, false, c.st);
+    if (rc || !loss_tail) return rc;
+    return gmc_loss_tail_launch(loss_tail, b->B, db2 + K, c.st);
+}
+
+}  // namespace
+
+extern "C" size_t gmc_kway_workspace_bytes(const gmc_batch *batch, const gmc_model *model, int training) {
+    if (check_abi(batch, model) || !kway_classes_ok(model->K)) return 0;
+    return kway_carve(batch, model, training != 0, nullptr).bytes;
+}
+
+extern "C" int gmc_kway_forward(const gmc_batch *batch, const gmc_model *model, float C, void *workspace,
+                                size_t workspace_bytes, float *P, int32_t *S, float *loss, gmc_stream_t stream) {
+    KwayCall c{batch, model};
+    int rc = kway_open(c, false, workspace, workspace_bytes, stream, P, nullptr);
+    if (rc || batch->R == 0) return rc;
+    return kway_forward_body(c, C, P, S, loss);
+}
+
+extern "C" int gmc_kway_train_fwd_bwd(const gmc_batch *batch, const gmc_model *model, float C, void *workspace,
+                                      size_t workspace_bytes, float *P, int32_t *S, float *loss, float *grad,
+                                      gmc_stream_t stream) {
+    KwayCall c{batch, model};
+    int rc = kway_open(c, true, workspace, workspace_bytes, stream, P, grad);
+    if (rc) return rc;
+    const bool tail = (model->flags & GMC_MODEL_GRAD_TAIL) != 0;
+    if (tail && !loss) return GMC_ERR_NULL;
+    if (batch->R == 0) {
+        const size_t n = (size_t)model->N * model->F + model->F + (size_t)model->F * model->K + model->K + (tail ? 1 : 0);
+        return (int)hipMemsetAsync(grad, 0, n * sizeof(float), c.st);
+    }
+    rc = kway_forward_body(c, C, P, S, loss);
+    return rc ? rc : kway_backward_body(c, grad, tail ? loss : nullptr);
+}

@@ -99,3 +99,18 @@ int gmc_scale_copy_launch(const float *src, float *dst, int n, float s, hipStrea
 // C[M,Nc] = scale o (op(A) @ op(B)), ta / tb: the operand is stored transposed; internal form of gmc_gemm_f32
 int gmc_gemm_launch(int ta, int tb, int M, int Nc, int K, const float *A, long lda, const float *B, long ldb,
                     const float *scale, float *C, long ldc, hipStream_t st);
+
+// ---- the K-class step (kway.hip): the K-wide forms of hw2_rows, the head, the hidden backward and the partials' fold ----
+// K: 2..GMC_KWAY_MAX_CLASSES, else GMC_ERR_CLASSES.  Row-major operands: Z0, P, GY2 [R,K], W2 [F,K] (W2 and P 16-byte
+// aligned), part [gmc_hidden_tiles(R)][F][K+1], db2part [B,K].
+constexpr size_t GMC_KWAY_LDS_BYTES = 160 * 1024;   // a CU's LDS: what one graph's [n,K] tiles of the head may take
+size_t gmc_kway_head_lds_bytes(int n_max, int K, int loss_kind);
+int gmc_kway_hw2_launch(const float *H, long ld, const float *dinv, const float *W2, float *Z0, long R, int F, int K,
+                        hipStream_t st);
+// GY2 == nullptr: forward only (P, S, loss); GMC_ERR_GRAPH_SIZE when gmc_kway_head_lds_bytes exceeds GMC_KWAY_LDS_BYTES
+int gmc_kway_head_launch(const gmc_batch *b, const float *Z0, const float *b2, float C, int K, int loss_kind, float *P,
+                         int32_t *S, float *loss, float *GY2, float *db2part, hipStream_t st);
+int gmc_kway_hidden_bwd_launch(const float *H, long ldh, const float *GY2, const float *W2, const float *dinv, float *Gs,
+                               long ldg, float *part, int R, int F, int K, hipStream_t st);
+int gmc_kway_reduce_launch(const float *part, int tiles, int F, int K, float *dW2, float *db1, const float *db2part,
+                           int B, float *db2, hipStream_t st);

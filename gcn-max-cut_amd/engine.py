@@ -36,15 +36,26 @@ MAX_HIDDEN = 4096
 class FusedEngine:
     """One per model.  ``adopt`` re-homes a module's parameters into the flat buffer."""
 
-    def __init__(self, N: int, F: int, K: int, device: Optional[torch.device] = None):
+    def __init__(self, N: int, F: int, K: int, device: Optional[torch.device] = None, *, kway: bool = False):
+        """``kway`` = True asks for the K-class engine (number_classes K in 2..8 through gmc_kway_*: the row-kernel sequence,
+        ``[R,K]`` outputs, no fused step / slab / dropout / dense features).  It is required for K != 3 - a caller written
+        for the 3-class engine's surface is told so instead of meeting NotImplementedError later - and allowed for K = 3,
+        which then runs the same sequence.  ``GCNSoftmax.engine()`` passes it for models with number_classes != 3."""
         self.device = device or hip.require_gpu()
         self.lib = hip.load()
-        if K != 3:
-            raise ValueError("number_classes must be 3: the terminal override is 3-wide "
-                             "(TrainingNeural.py:91-93)")
+        if not 2 <= K <= hip.KWAY_MAX_CLASSES:
+            raise ValueError(f"number_classes must be in 2..{hip.KWAY_MAX_CLASSES}, got {K} (nodes 0..K-1 of every graph "
+                             "are the terminals of classes 0..K-1)")
+        if K != 3 and not kway:
+            raise ValueError(f"number_classes = {K}: the fused engine is 3-class (the terminal override of "
+                             "TrainingNeural.py:91-93 is 3-wide); FusedEngine(N, F, K, kway=True) is the K-class engine")
         if F < 1 or F > MAX_HIDDEN:
             raise ValueError(f"hidden_dim must be in 1..{MAX_HIDDEN} on this path (include/gcnmaxcut.h: GMC_MAX_HIDDEN)")
         self.N, self.F, self.K = N, F, K
+        # number_classes != 3: the K-class entry points (gmc_kway_*) - the one-kernel-per-operation row-kernel sequence
+        # with [R,K] outputs.  The fused 3-way kernels, the slab copy of W1, dropout, dense features and the
+        # caller-supplied dLoss/dP are 3-class only and raise NotImplementedError there.
+        self.kway = bool(kway)
         # Any hidden_dim (TrainingNeural.py:42,66-67 accept any int; n_nodes=50 gives 25): the kernels work on 16-byte
         # column groups, so the flat buffer carries the hidden dimension padded to a multiple of 4 (Fp).  Pad columns of
         # W1 / entries of b1 / rows of W2 are 0 and stay 0 (their activations are relu(0), every gradient entry is an
@@ -104,6 +115,7 @@ class FusedEngine:
         kernels refresh the copy from the row-major weights on every step."""
         if not self.slab_enabled:
             return 0
+        self._three_way_only("the slab copy of conv1.weight")
         sig = self._param_signature()
         if self.w1_slab is None:
             self.w1_slab = torch.empty(int(self.lib.gmc_w1_slab_floats(self.N, self.Fp)), dtype=torch.float32,
@@ -114,6 +126,21 @@ class FusedEngine:
             hip.check(rc, "gmc_w1_slab_f32")
             self._slab_sig = sig
         return hip.ptr(self.w1_slab)
+
+    def _three_way_only(self, what: str) -> None:
+        if self.kway:
+            raise NotImplementedError(f"{what} is implemented for the fused 3-class engine only (this is the K-class engine, "
+                                      f"number_classes = {self.K}: forward, train_fwd_bwd and the Adam steps are what it "
+                                      "offers)")
+
+    def _entry(self, name: str) -> str:
+        """The library entry point of a call: gmc_<name>, or gmc_kway_<name> for number_classes != 3."""
+        return f"gmc_kway_{name}" if self.kway else f"gmc_{name}"
+
+    def _check_terminals(self, batch: GraphBatch) -> None:
+        if self.kway and batch.B and int(batch.sizes.min()) < self.K:
+            raise ValueError(f"number_classes = {self.K}: every graph needs at least {self.K} nodes (nodes 0..{self.K - 1} "
+                             f"are its terminals), got one with {int(batch.sizes.min())}")
 
     def _call_model(self, slab: bool = False, loss: str = "cut") -> hip.GmcModel:
         """A call's own gmc_model: a copy of the resident one (weights, dropout); ``slab``: with the (current) slab copy
@@ -134,6 +161,8 @@ class FusedEngine:
         p = float(p)
         if not 0.0 <= p < 1.0:
             raise ValueError(f"dropout probability has to be in [0, 1), got {p}")
+        if p > 0.0:
+            self._three_way_only("dropout")
         if p > 0.0 and seed is None:
             seed = int(torch.randint(0, 2 ** 62, (1,)).item())
         self._model.dropout_p = p
@@ -176,27 +205,28 @@ class FusedEngine:
 
     # ---- scratch and outputs
     def _workspace(self, batch: GraphBatch, training: bool) -> Tuple[torch.Tensor, int]:
-        need = int(self.lib.gmc_workspace_bytes(batch.ref(), C.byref(self._model), int(training)))
+        need = int(getattr(self.lib, self._entry("workspace_bytes"))(batch.ref(), C.byref(self._model), int(training)))
         if self._ws is None or self._ws.numel() < need:
             self._ws = torch.empty(max(need, 256), dtype=torch.uint8, device=self.device)
         return self._ws, self._ws.numel()
 
     def _outputs(self, batch: GraphBatch, out=None, want_loss: bool = True):
-        """(P [R,3], S [R], losses [B]) of a call: the caller's ``out``, else fresh (S, losses only when ``want_loss``)."""
+        """(P [R,K], S [R], losses [B]) of a call: the caller's ``out``, else fresh (S, losses only when ``want_loss``)."""
         if out is not None:
             return out
-        P = torch.empty((batch.R, 3), dtype=torch.float32, device=self.device)
+        P = torch.empty((batch.R, self.K), dtype=torch.float32, device=self.device)
         S = torch.empty(batch.R, dtype=torch.int32, device=self.device) if want_loss else None
         losses = torch.empty(batch.B, dtype=torch.float32, device=self.device) if want_loss else None
         return P, S, losses
 
     # ---- compute
     def workspace_bytes(self, batch: GraphBatch, training: bool) -> int:
-        return max(256, int(self.lib.gmc_workspace_bytes(batch.ref(), C.byref(self._model), int(training))))
+        return max(256, int(getattr(self.lib, self._entry("workspace_bytes"))(batch.ref(), C.byref(self._model),
+                                                                             int(training))))
 
     def forward(self, batch: GraphBatch, C_: float = 1.0, want_loss: bool = False,
                 ws: Optional[torch.Tensor] = None, loss: str = "cut"):
-        """P [R,3] (and S [R], loss [B] when ``want_loss``) - TrainingNeural.py:79-85.
+        """P [R,K] (and S [R], loss [B] when ``want_loss``) - TrainingNeural.py:79-85.
         ``ws``: caller-owned scratch (kept alive for a later :meth:`backward_from_gp`).  ``loss``: ``"cut"`` (the
         reference's -C * cut of the argmax decode) or ``"expected_cut"`` (the relaxed loss: ``hip.LOSS_KINDS``)."""
         return self._forward(batch, None, C_, want_loss, ws, loss)
@@ -205,6 +235,9 @@ class FusedEngine:
                  ws: Optional[torch.Tensor], loss: str):
         """:meth:`forward` (``X`` None: gmc_forward) and :meth:`forward_features` (gmc_forward_features)."""
         hip.loss_kind(loss)
+        if X is not None:
+            self._three_way_only("a forward through dense node features")
+        self._check_terminals(batch)
         P, S, losses = self._outputs(batch, None, want_loss)
         Xd = None if X is None else self.pad_features(batch, X)
         if batch.B == 0:   # nothing to launch (empty tensors have no device pointer to hand over)
@@ -212,7 +245,7 @@ class FusedEngine:
         if ws is None:   # the engine's own scratch; the dense plan gets one of its own
             ws = (self._workspace(batch, False)[0] if X is None else
                   torch.empty(self.workspace_bytes_features(batch, False), dtype=torch.uint8, device=self.device))
-        name, feat = ("gmc_forward", ()) if X is None else ("gmc_forward_features", (hip.ptr(Xd), Xd.shape[1]))
+        name, feat = (self._entry("forward"), ()) if X is None else ("gmc_forward_features", (hip.ptr(Xd), Xd.shape[1]))
         model = self._call_model(loss=loss)
         rc = getattr(self.lib, name)(batch.ref(), C.byref(model), *feat, C_, hip.ptr(ws), ws.numel(), hip.ptr(P),
                                      hip.ptr(S), hip.ptr(losses), hip.stream())
@@ -226,15 +259,17 @@ class FusedEngine:
         whose launches are captured into a hipGraph must own it: the engine's own scratch moves
         whenever a later call needs more).  ``loss``: as for :meth:`forward`."""
         hip.loss_kind(loss)
+        self._check_terminals(batch)
         P, S, losses = self._outputs(batch, out)
         if batch.B == 0:   # no graphs: zero gradient AND zero loss in the tail slot, nothing to launch
             self.grad[:self.count + 1].zero_()
             return P, S, losses
         ws, nbytes = (ws, ws.numel()) if ws is not None else self._workspace(batch, True)
         model = self._call_model(slab, loss)
-        rc = self.lib.gmc_train_fwd_bwd(batch.ref(), C.byref(model), C_, hip.ptr(ws), nbytes, hip.ptr(P), hip.ptr(S),
-                                        hip.ptr(losses), hip.ptr(self.grad), hip.stream())
-        hip.check(rc, "gmc_train_fwd_bwd")
+        name = self._entry("train_fwd_bwd")
+        rc = getattr(self.lib, name)(batch.ref(), C.byref(model), C_, hip.ptr(ws), nbytes, hip.ptr(P), hip.ptr(S),
+                                     hip.ptr(losses), hip.ptr(self.grad), hip.stream())
+        hip.check(rc, name)
         return P, S, losses
 
     def train_step(self, batch: GraphBatch, lr: float, C_: float = 1.0, out=None, betas=(0.9, 0.999),
@@ -247,6 +282,7 @@ class FusedEngine:
         ``out[2]`` - each is stored as soon as it is final, before the backward kernels run.  ``loss``: as for
         :meth:`forward` (gmc_train_step_loss_f32; a one-graph ``expected_cut`` step launches the head on its own)."""
         kind = hip.loss_kind(loss)
+        self._three_way_only("the fused train_step")
         ws, nbytes = (ws, ws.numel()) if ws is not None else self._workspace(batch, True)
         P, S, losses = out if out is not None else self._outputs(batch)
         tail = (self.ensure_slab() if slab else None, hip.stream())
@@ -271,6 +307,7 @@ class FusedEngine:
                   ws: Optional[torch.Tensor], want_dx: bool):
         """:meth:`backward_from_gp` (``X`` None: gmc_backward_from_gp) and :meth:`backward_features_from_gp`
         (gmc_backward_features_from_gp): (parameter gradients, dX or None)."""
+        self._three_way_only("the backward from a caller's dLoss/dP")
         Xd = None if X is None else self.pad_features(batch, X)
         dX = torch.empty_like(Xd) if want_dx else None
         if batch.B == 0:
@@ -287,6 +324,7 @@ class FusedEngine:
 
     # ---- features that are not the padded adjacency (layer 1 is a dense GEMM: gmc_forward_features)
     def workspace_bytes_features(self, batch: GraphBatch, training: bool) -> int:
+        self._three_way_only("a forward through dense node features")
         return max(256, int(self.lib.gmc_workspace_bytes_features(batch.ref(), C.byref(self._model), int(training))))
 
     def pad_features(self, batch: GraphBatch, X: torch.Tensor) -> torch.Tensor:
@@ -336,6 +374,11 @@ class FusedEngine:
         address of pinned host memory): the values are stored there by the one-wave launch that also advances the
         step counter, in front of the Adam sweep (two launches for publish + Adam + tick instead of three)."""
         keep_slab = slab and self.slab_enabled
+        if keep_slab:
+            self._three_way_only("the slab copy of conv1.weight")
+        if self.kway and publish is not None:   # (the fused publish + Adam launch knows the N x F x 3 layout only)
+            self.publish(*publish)
+            publish = None
         bufs = (hip.ptr(self.flat), hip.ptr(self.grad), hip.ptr(self.m), hip.ptr(self.v))
         if publish is not None:
             name, (src, dst) = "gmc_publish_adam_devstep_model_f32", publish

@@ -23,6 +23,7 @@ MODEL_LOSS_EXPECTED = 2   # gmc_model.flags: loss and gradient are GMC_LOSS_EXPE
 # independent rounding: compute_loss on override_fixed_nodes(P) without the one-hot step)
 LOSS_KINDS = {"cut": 0, "expected_cut": 1}
 LOSS_ENV = "GCN_MAXCUT_LOSS"
+KWAY_MAX_CLASSES = 8  # GMC_KWAY_MAX_CLASSES: number_classes the gmc_kway_* entry points take (2..8; 3 also has the fused path)
 ABI_VERSION = 200     # GMC_VERSION of include/gcnmaxcut.h these struct layouts follow (checked at load and per call)
 
 
@@ -106,6 +107,9 @@ def _api() -> dict:
         "gmc_workspace_bytes_features": (sz, [B, M, i]),
         "gmc_forward_features": (i, [B, M, vp, i64, f32, vp, sz, vp, vp, vp, vp]),
         "gmc_backward_features_from_gp": (i, [B, M, vp, i64, vp, sz, vp, vp, vp, vp, i64, vp]),
+        "gmc_kway_workspace_bytes": (sz, [B, M, i]),
+        "gmc_kway_forward": (i, [B, M, f32, vp, sz, vp, vp, vp, vp]),
+        "gmc_kway_train_fwd_bwd": (i, [B, M, f32, vp, sz, vp, vp, vp, vp, vp]),
         "gmc_gemm_f32": (i, [i32, i32, i32, i32, i32, vp, i64, vp, i64, vp, vp, i64, vp]),
         "gmc_set_fuse": (i, [i]),
         "gmc_probe_begin": (i, [i32]),

@@ -95,7 +95,10 @@ class FusedTrainer:
         if self.dp:
             self.eng.sync_replicas(0)   # one model: rank 0's parameters / moments on every replica
         # what the engine offers: the fused step; scratch, slab copy of W1, device-stepped Adam (not host stand-ins)
-        self._fused_step = hasattr(self.eng, "train_step")
+        # (a number_classes != 3 engine has neither the fused step nor the slab copy: train_fwd_bwd -> Adam, eager)
+        self._kway = bool(getattr(self.eng, "kway", False))
+        self._fused_step = hasattr(self.eng, "train_step") and not self._kway
+        self._slab = not self._kway
         self._hip = hasattr(self.eng, "adam_step_dev")
         self._dp_graphs_env = os.environ.get("GCN_MAXCUT_DP_GRAPHS", "0") == "1"
         self._plan_key = None
@@ -156,7 +159,7 @@ class FusedTrainer:
             self._batches.append(self.eng.make_batch(handles, vals))
         rmax = max((b.R for b in self._batches), default=0)
         bmax = max((b.B for b in self._batches), default=0)
-        self._out = (torch.empty((rmax, 3), dtype=torch.float32, device=dev),
+        self._out = (torch.empty((rmax, int(getattr(self.eng, "K", 3))), dtype=torch.float32, device=dev),
                      torch.empty(rmax, dtype=torch.int32, device=dev))
         self._loss_slots = torch.zeros((len(self._batches), max(bmax, 1)), dtype=torch.float32, device=dev)
         self._step_loss = torch.zeros(len(self._batches), dtype=torch.float32, device=dev)
@@ -183,7 +186,7 @@ class FusedTrainer:
         # later call (evaluate_model on a bigger batch, another trainer) needs more, which would leave a
         # captured hipGraph replaying into freed memory
         if self._hip and self._batches:
-            drop = float(getattr(self.net, "dropout_frac", 0.0) or 0.0)
+            drop = 0.0 if self._kway else float(getattr(self.net, "dropout_frac", 0.0) or 0.0)   # (K-class: no dropout)
             with self.eng.dropout(drop, 0):   # the dropout sequence needs a little more scratch: size for it
                 need = max((self.eng.workspace_bytes(b, True) for b in self._batches if b.B), default=0)
             if need and (self._ws is None or self._ws.numel() < need):
@@ -208,11 +211,14 @@ class FusedTrainer:
     def epoch(self, dataset: Dict) -> float:
         """One pass over the dataset; returns the cumulative loss (one host sync)."""
         t_entry = perf_counter()
+        if self._kway and self._dropout() > 0.0:
+            raise NotImplementedError(f"dropout is implemented for number_classes = 3 only (this model has number_classes "
+                                      f"= {self.eng.K}): train it with dropout = 0")
         self.prepare(dataset)
         drop = self._dropout()
         path = launch_path(dp=self.dp, dropout=drop, allow_graph=self.allow_graph, fused_step=self._fused_step,
                            steps=len(self._batches), mapped=self._loss_host_dev is not None, poll=self._poll,
-                           dp_graphs=self._dp_graphs_env)
+                           dp_graphs=self._dp_graphs_env and not self._kway)
         if path is Launch.DROPOUT:
             self._run_dropout(drop)
         elif path is Launch.DP or path is Launch.DP_GRAPHS:
@@ -318,7 +324,7 @@ class FusedTrainer:
                 fwd_bwd[i].replay()                   # forward + loss + backward + gradient fold of my shard
             elif self._hip:
                 eng.train_fwd_bwd(batch, cfg.C, out=(self._out[0], self._out[1], self._loss_slots[i]), ws=self._ws,
-                                  slab=True, **self._loss_kw)
+                                  slab=self._slab, **self._loss_kw)
             else:
                 eng.train_fwd_bwd(batch, cfg.C, out=(self._out[0], self._out[1], self._loss_slots[i]), **self._loss_kw)
             eng.allreduce_grad()                      # ONE RCCL all-reduce of [gradient | loss] per step, eager
@@ -333,7 +339,8 @@ class FusedTrainer:
             elif self._hip:
                 eng.sync_step_dev()                   # (a launch only after host-stepped updates)
                 # keeps the slab copy of W1 current; with `publish`: loss store + counter tick + Adam in two launches
-                eng.adam_step_dev(lr, betas, eps, slab=True, publish=(tail, publish + 4 * i) if publish else None)
+                eng.adam_step_dev(lr, betas, eps, slab=self._slab,
+                                  publish=(tail, publish + 4 * i) if publish else None)
             else:
                 eng.adam_step(lr, betas, eps)
 

@@ -176,7 +176,7 @@ enum {
     GMC_K_DW1_FOLD = 7,   /* fold of the dW1 chunk partials */
     GMC_K_ADAM = 8,       /* fused Adam                                      :386 */
     GMC_K_SPMM_USER = 9,  /* gmc_spmm_f32 called directly */
-    GMC_K_DENSE_MFMA = 10,
+    GMC_K_DENSE_MFMA = 10, /* the stand-alone H @ W2 product: gmc_dense_hw2_f32, and hw2_k of the K-class sequence */
     GMC_K_BWD1_FUSED = 11, /* hidden backward + conv1 backward aggregation + dW1, one pass over H (a one-graph
                             * gmc_train_step_f32 computes the head in this launch as well: no GMC_K_HEAD record) */
     GMC_K_FWD1_FUSED = 12, /* W1 gather + layer-1 aggregation (+ fused H@W2), one kernel */
@@ -428,6 +428,38 @@ int gmc_forward_features(const gmc_batch *batch, const gmc_model *model, const f
 int gmc_backward_features_from_gp(const gmc_batch *batch, const gmc_model *model, const float *X, int64_t ldx,
                                   void *workspace, size_t workspace_bytes, const float *P, const float *GP,
                                   float *grad, float *dX, int64_t lddx, gmc_stream_t stream);
+
+/* ---- number_classes K other than 3 (2 <= K <= GMC_KWAY_MAX_CLASSES) ---------------------------------------------------
+ *
+ * The entry points above are the reference's 3-class model and answer GMC_ERR_CLASSES for any other model->K.  These
+ * three run the same 2-layer GraphConv with conv2.weight [F,K], conv2.bias [K] and a softmax over K columns
+ * (TrainingNeural.py:72-85 with number_classes = K, :515-535 train_multi_class), K = model->K:
+ *  - terminals: nodes 0..K-1 of every graph are fixed to classes 0..K-1 - override_fixed_nodes (:87-94) with eye(K) on the
+ *    first K rows, same straight-through form; every graph needs at least K nodes (n_max < K: GMC_ERR_GRAPH_SIZE; a
+ *    smaller graph inside a batch is the caller's to refuse: goff is device memory);
+ *  - GMC_LOSS_CUT: loss = -C * cut(S), S = row-argmax (first maximum wins) with rows 0..K-1 forced to their own class,
+ *    dLoss/dP = C * A_val @ onehot_K(S) on every row; GMC_LOSS_EXPECTED_CUT (GMC_MODEL_LOSS_EXPECTED in model->flags):
+ *    as defined at GMC_LOSS_*, Pt = P with rows 0..K-1 replaced by e_0..e_{K-1}.  At K = 3 both are the definitions above.
+ * Kernel sequence: one kernel per operation on row-major [R, ld] buffers (the plan of the *_features calls), the
+ * class-count-free kernels shared with it, the K-wide ones from csrc/kway.hip; gmc_set_fuse does not matter.  The head
+ * keeps a graph's [n,K] tiles in LDS: about (2K+1)(n_max+4) floats, GMC_ERR_GRAPH_SIZE beyond a CU's 160 KiB (K = 8: n_max
+ * near 2400; K = 2: GMC_MAX_GRAPH_NODES).  No dropout (dropout_p > 0: GMC_ERR_UNSUPPORTED), W1_slab is not read.
+ * P [R,K] and model->W2 must be 16-byte aligned (GMC_ERR_ALIGN, with grad).  Argument checks: the order documented
+ * above for the fused entry points, with K outside 2..GMC_KWAY_MAX_CLASSES as step 2's GMC_ERR_CLASSES and dropout_p > 0
+ * (UNSUPPORTED) behind the dropout_p range check.  Results are bitwise reproducible; K = 3 is allowed and agrees with
+ * the entry points above to rounding (another kernel sequence). */
+#define GMC_KWAY_MAX_CLASSES 8
+/* bytes of scratch gmc_kway_forward / gmc_kway_train_fwd_bwd need (0 for a NULL struct, another abi word, or K outside
+ * 2..GMC_KWAY_MAX_CLASSES) */
+size_t gmc_kway_workspace_bytes(const gmc_batch *batch, const gmc_model *model, int training);
+/* gmc_forward for K classes: P [R,K]; S [R] / loss [B] optional.  An empty batch returns GMC_OK without a launch. */
+int gmc_kway_forward(const gmc_batch *batch, const gmc_model *model, float C, void *workspace, size_t workspace_bytes,
+                     float *P, int32_t *S, float *loss, gmc_stream_t stream);
+/* gmc_train_fwd_bwd for K classes: grad is the flat [W1 | b1 | W2 | b2] buffer of N*F + F + F*K + K floats, plus the
+ * tail slot with GMC_MODEL_GRAD_TAIL (loss must then be non-NULL).  An empty batch zeroes grad (and the tail slot)
+ * without any other launch. */
+int gmc_kway_train_fwd_bwd(const gmc_batch *batch, const gmc_model *model, float C, void *workspace,
+                           size_t workspace_bytes, float *P, int32_t *S, float *loss, float *grad, gmc_stream_t stream);
 
 /* ---- decode / post-processing (the caller of the path in BASELINE configs[4]) -------- */
 
