@@ -8,12 +8,16 @@ Same names, arguments and result dictionaries as the reference for ``assign_part
 sampling iterations and their cut counts run in one launch of ``gmc_decode_sample_f32``; the
 uniform draws still come from numpy's global RNG in the reference's order, so with the same
 ``np.random.seed`` the sampled assignments and cut values are the reference's, exactly.
+With a ``seed`` (argument, or the switch ``GCN_MAXCUT_SAMPLE_SEED``) the uniforms are instead drawn on the GPU by
+``gmc_decode_sample_seeded_f32`` from a counter-based hash (extension): numpy's RNG is not touched, nothing is
+generated on the host, and a graph's samples depend on the seed and its index in the dataset alone.
 The reporting / plotting half of the reference module (``analyze_results`` .. ``generate_summary_report``,
 :297-638) is presentation code outside the path and is not reproduced.
 """
 from __future__ import annotations
 
 import ctypes as C
+import os
 from time import time
 from typing import Any, Dict, List, Optional, Tuple
 
@@ -40,6 +44,61 @@ def assign_partitions(node_probs: np.ndarray) -> List[int]:
                 break
         else:
             out.append(len(probs) - 1)
+    return out
+
+
+SAMPLE_SEED_ENV = "GCN_MAXCUT_SAMPLE_SEED"
+_M64 = (1 << 64) - 1
+_GOLD = 0x9E3779B97F4A7C15
+
+
+def _mix64(z: int) -> int:
+    """splitmix64's finaliser on a Python integer (csrc/mix64.h)."""
+    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & _M64
+    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & _M64
+    return z ^ (z >> 31)
+
+
+def _sample_seed(seed: Optional[int]) -> Optional[int]:
+    """The sampler's seed as a uint64, or None for the numpy stream: the argument, else the environment switch
+    GCN_MAXCUT_SAMPLE_SEED (read here, at call time; the library itself reads no environment)."""
+    if seed is None:
+        text = os.environ.get(SAMPLE_SEED_ENV)
+        if text is None or not text.strip():
+            return None
+        try:
+            seed = int(text.strip(), 0)
+        except ValueError:
+            raise ValueError(f"{SAMPLE_SEED_ENV} must be an integer, got {text!r}") from None
+    return int(seed) & _M64
+
+
+def _graph_key(seed: int, index: int) -> int:
+    if int(index) < 0:
+        raise ValueError(f"a graph's index must be >= 0, got {index}")
+    return _mix64((int(seed) + _GOLD * (int(index) + 1)) & _M64)
+
+
+def sample_keys(seed: int, indices) -> np.ndarray:
+    """The keys of the seeded sampler (include/gcnmaxcut.h, gmc_decode_sample_seeded_f32) for the graphs at positions
+    ``indices`` of a dataset: ``mix64(seed + GOLD * (index + 1))`` in uint64 arithmetic."""
+    return np.array([_graph_key(seed, i) for i in indices], dtype=np.uint64)
+
+
+def assign_partitions_seeded(node_probs: np.ndarray, seed: int, graph_index: int = 0, iteration: int = 0) -> List[int]:
+    """One sample of the seeded post-processing (host form of sample_seeded.hip, the counterpart of
+    :func:`assign_partitions`): iteration ``iteration`` of the graph at position ``graph_index``, the uniform of local
+    node l hashed from the graph's key, the iteration and l.  Python integers masked to 64 bits and Python floats."""
+    if int(iteration) < 0 or int(iteration) >= 1 << 31:
+        raise ValueError(f"iteration must be in 0..2^31-1, got {iteration}")
+    key = _graph_key(seed, graph_index)
+    out = [0, 1, 2]
+    for l, probs in enumerate(node_probs[3:], 3):
+        h = _mix64((key + _GOLD * (((int(iteration) << 32) | l) + 1)) & _M64)
+        r = float(h >> 11) * 2.0 ** -53          # < 2^53: exact
+        c0 = float(probs[0])
+        c1 = c0 + float(probs[1])
+        out.append(0 if r < c0 else (1 if r < c1 else 2))
     return out
 
 
@@ -74,9 +133,15 @@ def _three_classes_only(what: str, classes: int) -> None:
                          "argmax decode (simple_partition_assignment) for a model with another number_classes")
 
 
-def _sample_on_gpu(batch: GraphBatch, P: torch.Tensor, iterations: int):
-    """Draw the uniforms in the reference's order and run the fused sampler + cut count."""
+def _sample_on_gpu(batch: GraphBatch, P: torch.Tensor, iterations: int, seed: Optional[int] = None, indices=None,
+                   keep_samples: bool = True):
+    """Draw the uniforms in the reference's order and run the fused sampler + cut count.  With ``seed`` (a uint64; the
+    callers resolve argument and environment with ``_sample_seed``) the seeded sampler runs instead: the graphs'
+    dataset positions ``indices`` (default 0..B-1) make their keys, no uniform exists on the host, and the
+    [iterations, R] samples are allocated only if ``keep_samples`` (else ``assign_all`` is returned as None)."""
     _three_classes_only("the sampling post-processing", P.shape[1])
+    if seed is not None:
+        return _sample_seeded_on_gpu(batch, P, iterations, seed, indices, keep_samples)
     sizes = [int(n) - 3 for n in batch.sizes]
     draws = [np.random.rand(iterations, m) for m in sizes]          # graph -> iteration -> node
     uoff = np.zeros(batch.B + 1, np.int64)
@@ -93,6 +158,24 @@ def _sample_on_gpu(batch: GraphBatch, P: torch.Tensor, iterations: int):
     rc = hip.load().gmc_decode_sample_f32(batch.ref(), p(P.contiguous()), p(u), p(uo), iterations, p(assign_all),
                                           p(cut_all), p(best_assign), p(best_cut), p(best_iter), hip.stream())
     hip.check(rc, "gmc_decode_sample_f32")
+    return best_assign, best_cut, cut_all, assign_all
+
+
+def _sample_seeded_on_gpu(batch: GraphBatch, P: torch.Tensor, iterations: int, seed: int, indices, keep_samples: bool):
+    keys = sample_keys(seed, range(batch.B) if indices is None else indices)
+    if keys.size != batch.B:
+        raise ValueError(f"{keys.size} graph indices for a batch of {batch.B} graphs")
+    dev = batch.device
+    gkey = torch.from_numpy(keys.view(np.int64)).to(dev) if batch.B else torch.zeros(1, dtype=torch.int64, device=dev)
+    assign_all = torch.empty((iterations, batch.R), dtype=torch.int8, device=dev) if keep_samples else None
+    cut_all = torch.empty((batch.B, iterations), dtype=torch.float32, device=dev)
+    best_assign = torch.empty(batch.R, dtype=torch.int32, device=dev)
+    best_cut = torch.empty(batch.B, dtype=torch.float32, device=dev)
+    best_iter = torch.empty(batch.B, dtype=torch.int32, device=dev)
+    p = hip.ptr
+    rc = hip.load().gmc_decode_sample_seeded_f32(batch.ref(), p(P.contiguous()), p(gkey), iterations, p(assign_all),
+                                                 p(cut_all), p(best_assign), p(best_cut), p(best_iter), hip.stream())
+    hip.check(rc, "gmc_decode_sample_seeded_f32")
     return best_assign, best_cut, cut_all, assign_all
 
 
@@ -163,15 +246,19 @@ def _as_number(x: float):
     return int(x) if float(x).is_integer() else float(x)
 
 
-def post_processing_optimization(node_probabilities, graph, iterations: int = 200) -> Tuple[List[int], int]:
-    """Best of ``iterations`` random samples (TestingNeuralNetwork.py:66-98), on the GPU."""
+def post_processing_optimization(node_probabilities, graph, iterations: int = 200, *, seed: Optional[int] = None,
+                                 graph_index: int = 0) -> Tuple[List[int], int]:
+    """Best of ``iterations`` random samples (TestingNeuralNetwork.py:66-98), on the GPU.  ``seed`` (extension; None
+    reads GCN_MAXCUT_SAMPLE_SEED, and without either the numpy stream of the reference is drawn): the samples of the
+    seeded sampler for the graph at position ``graph_index`` of its dataset; numpy's RNG is then left alone."""
     dev = hip.require_gpu()
+    seed = _sample_seed(seed)
     probs = node_probabilities if isinstance(node_probabilities, torch.Tensor) else torch.from_numpy(np.asarray(node_probabilities))
     probs = probs.detach().to(dev, torch.float32)
     if iterations <= 0:
         return None, -float('inf')
     batch = GraphBatch([from_networkx(graph)], None, dev)
-    best_assign, best_cut, _, _ = _sample_on_gpu(batch, probs, iterations)
+    best_assign, best_cut, _, _ = _sample_on_gpu(batch, probs, iterations, seed, [graph_index], keep_samples=False)
     return best_assign.cpu().tolist(), _as_number(best_cut.item())
 
 
@@ -227,8 +314,10 @@ def annealing_optimization(partition_assignment, graph, sweeps: int = 100, t_sta
 
 
 def test_single_graph(model, dgl_graph, adjacency_matrix, nx_graph, terminals: List[int],
-                      post_processing_iterations: int = 200) -> Dict[str, Any]:
-    """Argmax decode and post-processed decode of one graph (TestingNeuralNetwork.py:124-186)."""
+                      post_processing_iterations: int = 200, *, seed: Optional[int] = None,
+                      graph_index: int = 0) -> Dict[str, Any]:
+    """Argmax decode and post-processed decode of one graph (TestingNeuralNetwork.py:124-186).  ``seed`` /
+    ``graph_index``: as for :func:`post_processing_optimization`."""
     try:
         with torch.no_grad():
             node_probabilities = model(dgl_graph, adjacency_matrix)
@@ -242,7 +331,8 @@ def test_single_graph(model, dgl_graph, adjacency_matrix, nx_graph, terminals: L
             post_assignment, post_cut = list(simple_assignment), simple_cut
         else:
             post_assignment, post_cut = post_processing_optimization(node_probabilities, nx_graph,
-                                                                     post_processing_iterations)
+                                                                     post_processing_iterations, seed=seed,
+                                                                     graph_index=graph_index)
         post_time = time() - t0
         improvement = post_cut - simple_cut
         return {
@@ -262,8 +352,11 @@ test_single_graph.__test__ = False  # harness function, not a pytest test
 
 
 def test_multiple_graphs(model, processed_graphs: Dict, graph_sizes: List[int],
-                         post_processing_iterations: int = 200, verbose: bool = True) -> Tuple[List[Dict], Dict]:
-    """Evaluate a dataset and bucket the results by graph size (TestingNeuralNetwork.py:188-295)."""
+                         post_processing_iterations: int = 200, verbose: bool = True, *,
+                         seed: Optional[int] = None) -> Tuple[List[Dict], Dict]:
+    """Evaluate a dataset and bucket the results by graph size (TestingNeuralNetwork.py:188-295).  ``seed``
+    (extension): the seeded sampler, a graph's index being its position in ``processed_graphs`` (skipped graphs
+    still count), so the per-graph results equal ``decode_dataset(..., sample_seed=seed)``'s."""
     if verbose:
         print("Testing neural network performance...")
         print("=" * 60)
@@ -293,7 +386,8 @@ def test_multiple_graphs(model, processed_graphs: Dict, graph_sizes: List[int],
             if verbose:
                 print(f"  Skipping: graph size {size} not in test configuration")
             continue
-        result = test_single_graph(model, g, adjacency_matrix, nx_graph, terminals, post_processing_iterations)
+        result = test_single_graph(model, g, adjacency_matrix, nx_graph, terminals, post_processing_iterations,
+                                   seed=seed, graph_index=count - 1)
         if result['success']:
             result.update({'graph_name': name, 'graph_size': size})
             test_results.append(result)
@@ -322,7 +416,7 @@ test_multiple_graphs.__test__ = False
 
 def decode_dataset(model, processed_graphs: Dict, post_processing_iterations: int = 200,
                    local_search_sweeps: int = 0, anneal_sweeps: int = 0, anneal_candidates: Optional[int] = None,
-                   anneal_seed: int = 0) -> List[Dict[str, Any]]:
+                   anneal_seed: int = 0, *, sample_seed: Optional[int] = None) -> List[Dict[str, Any]]:
     """Throughput form of the same evaluation (extension): ONE batched forward and ONE sampler
     launch for the whole dataset.  Results equal ``test_multiple_graphs``'s per-graph numbers when
     the RNG state is the same (uniforms are drawn graph by graph in dataset order).
@@ -332,7 +426,11 @@ def decode_dataset(model, processed_graphs: Dict, post_processing_iterations: in
     ``anneal_sweeps > 0`` anneals a copy of the first ``anneal_candidates`` of the same 1 + iterations candidates
     (``None``: all of them) with ``annealing_optimization``'s defaults in one more launch; each result then carries
     ``annealed_cut``, ``annealed_assignment`` and ``annealed_from``.  Neither option changes the other keys or the
-    uniforms drawn."""
+    uniforms drawn.
+    ``sample_seed`` (None reads GCN_MAXCUT_SAMPLE_SEED; without either, the numpy stream above): the samples come
+    from the seeded sampler, a graph's index being its position in ``processed_graphs.values()`` - the per-graph
+    numbers of ``test_multiple_graphs(..., seed=sample_seed)``.  No uniform is drawn or copied by the host, numpy's
+    RNG is left alone, and the [iterations, R] samples exist only when one of the two searches wants them."""
     items = list(processed_graphs.values())
     eng = model.engine()
     _three_classes_only("decode_dataset", eng.K)
@@ -341,7 +439,9 @@ def decode_dataset(model, processed_graphs: Dict, post_processing_iterations: in
     vals = [h.edge_values(it[1]) for h, it in zip(handles, items)]
     batch = GraphBatch(handles, vals, eng.device)
     P, S, loss = eng.forward(batch, 1.0, want_loss=True)
-    best_assign, best_cut, _, assign_all = _sample_on_gpu(batch, P, post_processing_iterations)
+    best_assign, best_cut, _, assign_all = _sample_on_gpu(batch, P, post_processing_iterations,
+                                                          _sample_seed(sample_seed), range(len(items)),
+                                                          keep_samples=local_search_sweeps > 0 or anneal_sweeps > 0)
     refined = None
     if local_search_sweeps > 0:
         cands = torch.cat([S.to(torch.int8).reshape(1, -1), assign_all])

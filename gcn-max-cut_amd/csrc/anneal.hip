@@ -22,6 +22,7 @@
 // template over the accessor, so their arithmetic cannot differ.
 #include "gmc_common.h"
 #include "cut_body.h"
+#include "mix64.h"
 #include "move_body.h"
 
 #define GMC_ANNEAL_LDS_BUDGET (40 * 1024)
@@ -29,7 +30,8 @@
 
 namespace {
 
-typedef unsigned long long u64;
+using gmc::mix64;
+using gmc::u64;
 
 struct AnnealArgs {
     gmc_batch b;
@@ -45,12 +47,6 @@ struct AnnealArgs {
     int staged;              // the launch has room for the staged copy
     int n_pad, off_starts, off_vals, off_order, off_ids;   // LDS layout (bytes from the dynamic base)
 };
-
-__device__ __forceinline__ u64 mix64(u64 z) {  // splitmix64 finaliser (dropout.hip)
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ULL;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBULL;
-    return z ^ (z >> 31);
-}
 
 // the graph as the batch holds it in global memory
 struct GlobalCsr {

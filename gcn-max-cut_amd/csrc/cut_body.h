@@ -1,6 +1,6 @@
-// Cut count and best-candidate pick shared by the post-processing sampler (decode.hip), the local search
-// (refine.hip) and the annealing (anneal.hip): all score their candidates with the same code, so a candidate a search
-// does not move gets, bit for bit, the cut the sampler reports for it.
+// Cut count and best-candidate pick shared by the post-processing samplers (decode.hip, sample_seeded.hip), the local
+// search (refine.hip) and the annealing (anneal.hip): all score their candidates with the same code, so a candidate a
+// search does not move gets, bit for bit, the cut the sampler reports for it.
 #pragma once
 #include "gmc_common.h"
 
@@ -46,25 +46,32 @@ struct PickArgs {
     int *best_iter;    // [B]
 };
 
-// One workgroup (256 threads) per graph: the strictly best candidate, the first one on ties, and its assignment.
-__device__ __forceinline__ void pick_best(const PickArgs &a) {
+// One workgroup (256 threads) per graph: the index of the strictly best of its `iters` candidate cuts, the first one on
+// ties; thread 0 writes best_cut[g] and best_iter[g], every thread gets the index (one barrier).
+__device__ __forceinline__ int pick_best_index(const float *cut_all, int iters, int g, float *best_cut, int *best_iter) {
     __shared__ int sbest;
-    const int g = blockIdx.x;
     if (threadIdx.x == 0) {  // strict '>' keeps the first best (TestingNeuralNetwork.py:94)
         int bi = 0;
-        float bc = a.cut_all[(long)g * a.iters];
-        for (int i = 1; i < a.iters; ++i) {
-            const float c = a.cut_all[(long)g * a.iters + i];
+        float bc = cut_all[(long)g * iters];
+        for (int i = 1; i < iters; ++i) {
+            const float c = cut_all[(long)g * iters + i];
             if (c > bc) { bc = c; bi = i; }
         }
         sbest = bi;
-        a.best_cut[g] = bc;
-        a.best_iter[g] = bi;
+        best_cut[g] = bc;
+        best_iter[g] = bi;
     }
     __syncthreads();
+    return sbest;
+}
+
+// One workgroup (256 threads) per graph: the strictly best candidate, the first one on ties, and its assignment.
+__device__ __forceinline__ void pick_best(const PickArgs &a) {
+    const int g = blockIdx.x;
+    const int best = pick_best_index(a.cut_all, a.iters, g, a.best_cut, a.best_iter);
     const int r0 = a.b.goff[g], n = a.b.goff[g + 1] - r0;
     for (int l = threadIdx.x; l < n; l += blockDim.x)
-        a.best_assign[r0 + l] = a.assign_all[(long)sbest * a.b.R + r0 + l];
+        a.best_assign[r0 + l] = a.assign_all[(long)best * a.b.R + r0 + l];
 }
 
 }  // namespace gmc

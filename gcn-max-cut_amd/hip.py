@@ -119,6 +119,7 @@ def _api() -> dict:
         "gmc_ell_arrange_host": (i, [i32, vp, vp, vp, vp, i32, vp, vp]),
         "gmc_ell_slots_for": (i, [i32, vp, i32]),
         "gmc_decode_sample_f32": (i, [B, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp]),
+        "gmc_decode_sample_seeded_f32": (i, [B, vp, vp, i32, vp, vp, vp, vp, vp, vp]),
         "gmc_refine_order_host": (i, [i32, vp, vp, vp, vp, vp, vp, i32]),
         "gmc_refine_local_f32": (i, [B, vp, vp, vp, i32, vp, i32, vp, vp, vp, vp, vp, vp]),
         "gmc_refine_anneal_f32": (i, [B, vp, vp, vp, i32, vp, vp, i32, vp, C.c_uint64, i32, vp, vp, vp, vp, vp, vp, vp]),
@@ -210,7 +211,7 @@ KERNEL_TAGS = ("gather_w1", "agg_fwd", "head", "hidden_bwd", "colsum", "agg_bwd"
                "adam", "spmm_user", "dense_mfma", "bwd1_fused", "fwd1_fused", "decode", "finish",
                "refine", "anneal")
 # the tags after those (GMC_K_GEMM = 17 on): what Probe names a record by
-PROBE_TAGS = KERNEL_TAGS + ("gemm",)
+PROBE_TAGS = KERNEL_TAGS + ("gemm", "sample")
 
 
 FLAVOUR_KERNELS = {1: "fwd1_lds", 2: "bwd1_lds", 3: "bwd1_reg", 4: "spmm_lds", 5: "dw1_lds"}   # GMC_FLV_KERNEL

@@ -185,7 +185,8 @@ enum {
     GMC_K_REFINE = 15,     /* local search over decoded candidates + cut count (gmc_refine_local_f32) */
     GMC_K_ANNEAL = 16,     /* annealing + descent over decoded candidates + cut count (gmc_refine_anneal_f32) */
     GMC_K_GEMM = 17,       /* dense fp32 GEMM on the matrix cores (gmc_gemm_f32; the dense-feature path) */
-    GMC_K_COUNT = 18
+    GMC_K_SAMPLE = 18,     /* seeded post-processing sampler + cut count (gmc_decode_sample_seeded_f32) */
+    GMC_K_COUNT = 19
 };
 
 /* Timing probe for bench.py: between gmc_probe_begin and gmc_probe_end every kernel launch
@@ -475,6 +476,43 @@ int gmc_decode_sample_f32(const gmc_batch *batch, const float *P, const double *
                           const int64_t *uoff, int32_t iters, int8_t *assign_all, float *cut_all,
                           int32_t *best_assign, float *best_cut, int32_t *best_iter,
                           gmc_stream_t stream);
+
+/* ---- the same sampler with its uniforms drawn on the GPU from a seed (extension) ----------------------------------
+ *
+ * gmc_decode_sample_f32 reads uniforms the caller drew on the host in numpy's order, which is what reproduces the
+ * reference's numbers.  This entry point draws them itself from a counter-based hash: no uniform is generated on the
+ * host or copied, results are reproducible from the seed and independent of how graphs are batched.
+ *
+ * The draw rule.  All arithmetic is modulo 2^64.
+ *  - GOLD = 0x9E3779B97F4A7C15.
+ *  - mix64 is the splitmix64 finaliser, exactly as in anneal.hip (stated at gmc_refine_anneal_f32 below).
+ *  - A graph's key is key = mix64(seed + GOLD * (index + 1)).  index is the graph's position in its dataset, a
+ *    non-negative integer.
+ *  - The uniform for iteration it (0-based) and local node l of that graph is
+ *    h = mix64(key + GOLD * (((u64)it << 32 | l) + 1)), then u = (double)(h >> 11) * 2^-53.  This lies in [0, 1) and
+ *    is exact.
+ *  - Nodes 0, 1, 2 are the terminals of classes 0, 1, 2.
+ *  - Node l >= 3 takes its class exactly as decode_sample_kernel does today:
+ *      c0 = (double)p[0];
+ *      c1 = c0 + (double)p[1];
+ *      class 0 if u < c0;
+ *      else class 1 if u < c1;
+ *      else class 2.
+ * A graph's samples depend on its key alone.  They do not depend on the batch it sits in, on its position in the
+ * batch, or on iters: iteration 5 of a 10-iteration call is iteration 5 of a 200-iteration call.
+ *
+ * gkey: device uint64 [B], the keys (the caller computes them: the library never sees the seed or the indices).
+ * Outputs (device) as gmc_decode_sample_f32's: cut_all [B][iters], best_assign [R] int32 (the strictly best sample,
+ * the first on ties), best_cut [B], best_iter [B]; a sample's cut has the bits gmc_decode_sample_f32 and
+ * gmc_refine_local_f32(max_sweeps = 0) report for the same assignment.  assign_all [iters][R] int8 may be NULL: then
+ * nothing of size iters x R is written (best_assign is regenerated from the hash either way) and every other output
+ * equals the non-NULL call's.  Argument checks, before any HIP call, in the order of the other decoders: a NULL
+ * pointer (assign_all aside) GMC_ERR_NULL, batch->abi GMC_ERR_ABI, a NULL goff / rowptr / lcol GMC_ERR_NULL,
+ * iters < 1 or B < 0 GMC_ERR_SHAPE, n_max < 3 or n_max > 65535 GMC_ERR_GRAPH_SIZE; B == 0 returns GMC_OK without a
+ * launch.  The call allocates nothing and does not synchronise: two launches on the caller's stream. */
+int gmc_decode_sample_seeded_f32(const gmc_batch *batch, const float *P, const uint64_t *gkey, int32_t iters,
+                                 int8_t *assign_all, float *cut_all, int32_t *best_assign, float *best_cut,
+                                 int32_t *best_iter, gmc_stream_t stream);
 
 /* ---- local search over decoded partitions (extension: no counterpart in the reference) ---------------------------
  *
