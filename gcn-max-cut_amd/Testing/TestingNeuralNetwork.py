@@ -11,6 +11,9 @@ uniform draws still come from numpy's global RNG in the reference's order, so wi
 With a ``seed`` (argument, or the switch ``GCN_MAXCUT_SAMPLE_SEED``) the uniforms are instead drawn on the GPU by
 ``gmc_decode_sample_seeded_f32`` from a counter-based hash (extension): numpy's RNG is not touched, nothing is
 generated on the host, and a graph's samples depend on the seed and its index in the dataset alone.
+``conditional_rounding`` / ``round_dataset`` (extension) round the probabilities by conditional expectations
+(``gmc_round_conditional_f32``): one deterministic partition per graph whose cut is not below the expected cut, for
+any ``number_classes`` in 2..8.
 The reporting / plotting half of the reference module (``analyze_results`` .. ``generate_summary_report``,
 :297-638) is presentation code outside the path and is not reproduced.
 """
@@ -313,6 +316,67 @@ def annealing_optimization(partition_assignment, graph, sweeps: int = 100, t_sta
     return best_assign.cpu().tolist(), _as_number(best_cut.item())
 
 
+def _rounding_classes(classes: int) -> int:
+    """The class count of the rounding (round.hip is written for 2..8 classes)."""
+    K = int(classes)
+    if not 2 <= K <= hip.KWAY_MAX_CLASSES:
+        raise ValueError(f"conditional rounding takes number_classes in 2..{hip.KWAY_MAX_CLASSES}, got {K} classes")
+    return K
+
+
+def _round_on_gpu(batch: GraphBatch, P: torch.Tensor, descent_sweeps: int):
+    """Rounding by conditional expectations + descent (gmc_round_conditional_f32) of P [R, K] for every graph of the
+    batch, one launch; returns the assignment [R] int8, and per graph its cut, the expected cut and the descent sweeps
+    run."""
+    K = _rounding_classes(P.shape[1])
+    if descent_sweeps < 0:
+        raise ValueError(f"descent_sweeps must be >= 0, got {descent_sweeps}")
+    if batch.B and int(batch.sizes.min()) < K:
+        raise ValueError(f"number_classes = {K}: every graph needs at least {K} nodes (nodes 0..{K - 1} are the "
+                         f"terminals), got one with {int(batch.sizes.min())}")
+    dev = batch.device
+    assign = torch.empty(batch.R, dtype=torch.int8, device=dev)
+    cut = torch.empty(batch.B, dtype=torch.float32, device=dev)
+    expected = torch.empty(batch.B, dtype=torch.float32, device=dev)
+    sweeps = torch.empty(batch.B, dtype=torch.int32, device=dev)
+    if batch.B == 0:   # nothing to launch (empty tensors have no device pointer to hand over)
+        return assign, cut, expected, sweeps
+    order, cgoff, cptr = batch.refine_order(K)
+    p = hip.ptr
+    rc = hip.load().gmc_round_conditional_f32(batch.ref(), p(P.contiguous()), K, p(order), p(cgoff), p(cptr),
+                                              int(descent_sweeps), p(assign), p(cut), p(expected), p(sweeps),
+                                              hip.stream())
+    hip.check(rc, "gmc_round_conditional_f32")
+    return assign, cut, expected, sweeps
+
+
+def conditional_rounding(node_probabilities, graph, descent_sweeps: int = 0) -> Tuple[List[int], Any]:
+    """Round the node probabilities of ``graph`` ([n, K], K = number_classes in 2..8, nodes 0..K-1 the terminals) into
+    one partition by conditional expectations on the GPU (extension, include/gcnmaxcut.h
+    ``gmc_round_conditional_f32``): every node in turn takes the class that keeps the expected cut of the still
+    unrounded rest from falling, so the cut returned is at least the expected cut of rounding every node independently
+    from its row - what ``loss="expected_cut"`` trains on - deterministic, one visit per node.  ``descent_sweeps > 0``
+    then runs that many sweeps of the local search's rule at K classes (until one moves nothing).  Returns the
+    assignment and its cut value."""
+    probs = node_probabilities if isinstance(node_probabilities, torch.Tensor) else torch.from_numpy(np.asarray(node_probabilities))
+    if probs.dim() != 2:
+        raise ValueError(f"node_probabilities must be [n, number_classes], got {tuple(probs.shape)}")
+    K = _rounding_classes(probs.shape[1])
+    n = graph.number_of_nodes()
+    if n < K:
+        raise ValueError(f"number_classes = {K}: the graph needs at least {K} nodes (nodes 0..{K - 1} are the "
+                         f"terminals), got {n}")
+    if probs.shape[0] != n:
+        raise ValueError(f"node_probabilities has {probs.shape[0]} rows, the graph {n} nodes")
+    if descent_sweeps < 0:
+        raise ValueError(f"descent_sweeps must be >= 0, got {descent_sweeps}")
+    dev = hip.require_gpu()
+    probs = probs.detach().to(dev, torch.float32)
+    batch = GraphBatch([from_networkx(graph)], None, dev)
+    assign, cut, _, _ = _round_on_gpu(batch, probs, descent_sweeps)
+    return assign.cpu().tolist(), _as_number(cut.item())
+
+
 def test_single_graph(model, dgl_graph, adjacency_matrix, nx_graph, terminals: List[int],
                       post_processing_iterations: int = 200, *, seed: Optional[int] = None,
                       graph_index: int = 0) -> Dict[str, Any]:
@@ -416,7 +480,8 @@ test_multiple_graphs.__test__ = False
 
 def decode_dataset(model, processed_graphs: Dict, post_processing_iterations: int = 200,
                    local_search_sweeps: int = 0, anneal_sweeps: int = 0, anneal_candidates: Optional[int] = None,
-                   anneal_seed: int = 0, *, sample_seed: Optional[int] = None) -> List[Dict[str, Any]]:
+                   anneal_seed: int = 0, *, sample_seed: Optional[int] = None,
+                   rounding_descent_sweeps: Optional[int] = None) -> List[Dict[str, Any]]:
     """Throughput form of the same evaluation (extension): ONE batched forward and ONE sampler
     launch for the whole dataset.  Results equal ``test_multiple_graphs``'s per-graph numbers when
     the RNG state is the same (uniforms are drawn graph by graph in dataset order).
@@ -430,7 +495,13 @@ def decode_dataset(model, processed_graphs: Dict, post_processing_iterations: in
     ``sample_seed`` (None reads GCN_MAXCUT_SAMPLE_SEED; without either, the numpy stream above): the samples come
     from the seeded sampler, a graph's index being its position in ``processed_graphs.values()`` - the per-graph
     numbers of ``test_multiple_graphs(..., seed=sample_seed)``.  No uniform is drawn or copied by the host, numpy's
-    RNG is left alone, and the [iterations, R] samples exist only when one of the two searches wants them."""
+    RNG is left alone, and the [iterations, R] samples exist only when one of the two searches wants them.
+    ``rounding_descent_sweeps`` (not None): one more launch rounds the same probabilities by conditional expectations
+    (``conditional_rounding``) and descends that many sweeps from the result; each result then carries
+    ``expected_cut``, ``rounded_cut`` and ``rounded_assignment``.  The other keys and the uniforms drawn stay what they
+    are without it, and the rounded assignment is not among the candidates of the two searches."""
+    if rounding_descent_sweeps is not None and rounding_descent_sweeps < 0:
+        raise ValueError(f"rounding_descent_sweeps must be >= 0, got {rounding_descent_sweeps}")
     items = list(processed_graphs.values())
     eng = model.engine()
     _three_classes_only("decode_dataset", eng.K)
@@ -454,6 +525,9 @@ def decode_dataset(model, processed_graphs: Dict, post_processing_iterations: in
         cands = torch.cat([S.to(torch.int8).reshape(1, -1), assign_all[:take - 1]]).contiguous()
         inv_temp = anneal_schedule(anneal_sweeps, scale=_mean_edge_weight(batch))
         annealed = [t.cpu().numpy() for t in _anneal_on_gpu(batch, cands, inv_temp, anneal_seed, 100)]
+    rounded = None
+    if rounding_descent_sweeps is not None:
+        rounded = [t.cpu().numpy() for t in _round_on_gpu(batch, P, rounding_descent_sweeps)]
     S_host, best_host = S.cpu().numpy(), best_assign.cpu().numpy()
     simple, post = (-loss).cpu().tolist(), best_cut.cpu().tolist()
     out = []
@@ -470,4 +544,37 @@ def decode_dataset(model, processed_graphs: Dict, post_processing_iterations: in
             ann_assign, ann_cut, ann_idx = annealed
             out[-1].update({'annealed_cut': _as_number(ann_cut[g]), 'annealed_assignment': ann_assign[lo:hi].tolist(),
                             'annealed_from': int(ann_idx[g])})
+        if rounded is not None:
+            rnd_assign, rnd_cut, rnd_expected, _ = rounded
+            out[-1].update({'expected_cut': float(rnd_expected[g]), 'rounded_cut': _as_number(rnd_cut[g]),
+                            'rounded_assignment': rnd_assign[lo:hi].tolist()})
+    return out
+
+
+def round_dataset(model, processed_graphs: Dict, descent_sweeps: int = 0) -> List[Dict[str, Any]]:
+    """Argmax decode and conditional rounding of a whole dataset (extension): ONE batched forward and ONE rounding
+    launch (``gmc_round_conditional_f32``), for a model of any ``number_classes`` in 2..8 - the decoder, and with
+    ``descent_sweeps > 0`` the local search, of the models the 3-class sampler and searches refuse.  Per graph:
+    ``nodes``, ``simple_cut`` / ``simple_assignment`` (the argmax decode, as ``decode_dataset`` reports it),
+    ``expected_cut`` (of rounding every node independently from its row, terminals fixed), ``rounded_cut`` /
+    ``rounded_assignment`` (never below ``expected_cut`` but for fp32 rounding) and ``descent_sweeps`` (the sweeps
+    run, the last of them the one that moved nothing when the descent converged)."""
+    if descent_sweeps < 0:
+        raise ValueError(f"descent_sweeps must be >= 0, got {descent_sweeps}")
+    items = list(processed_graphs.values())
+    eng = model.engine()
+    _rounding_classes(eng.K)
+    model.eval()
+    handles = [it[0] for it in items]
+    vals = [h.edge_values(it[1]) for h, it in zip(handles, items)]
+    batch = GraphBatch(handles, vals, eng.device)
+    P, S, loss = eng.forward(batch, 1.0, want_loss=True)
+    assign, cut, expected, sweeps = [t.cpu().numpy() for t in _round_on_gpu(batch, P, descent_sweeps)]
+    S_host, simple = S.cpu().numpy(), (-loss).cpu().tolist()
+    out = []
+    for g in range(len(items)):
+        lo, hi = int(batch.goff_host[g]), int(batch.goff_host[g + 1])
+        out.append({'nodes': hi - lo, 'simple_cut': _as_number(simple[g]), 'simple_assignment': S_host[lo:hi].tolist(),
+                    'expected_cut': float(expected[g]), 'rounded_cut': _as_number(cut[g]),
+                    'rounded_assignment': assign[lo:hi].tolist(), 'descent_sweeps': int(sweeps[g])})
     return out

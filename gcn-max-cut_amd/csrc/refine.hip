@@ -77,15 +77,16 @@ __global__ __launch_bounds__(256) void refine_pick_kernel(gmc::PickArgs a) { gmc
 
 }  // namespace
 
-// HOST routine (all pointers are host pointers): first-fit colouring of every graph's movable nodes and the
-// (colour, id) order the kernel walks.  cptr_cap < R + B is refused before anything is written.
-extern "C" int gmc_refine_order_host(int32_t B, const int32_t *goff, const int32_t *rowptr, const int32_t *lcol,
-                                     int32_t *order, int32_t *cgoff, int32_t *cptr, int32_t cptr_cap) {
+// HOST routine (all pointers are host pointers): first-fit colouring of every graph's movable nodes first..n-1 and the
+// (colour, id) order the kernels walk.  cptr_cap < R + B is refused before anything is written.  One body for
+// gmc_refine_order_host (first = 3) and gmc_round_order_host (first = K).
+static int order_host(int32_t B, const int32_t *goff, const int32_t *rowptr, const int32_t *lcol, int first,
+                      int32_t *order, int32_t *cgoff, int32_t *cptr, int32_t cptr_cap) {
     if (!goff || !rowptr || !lcol || !order || !cgoff || !cptr) return GMC_ERR_NULL;
     if (B < 0) return GMC_ERR_SHAPE;
     for (int g = 0; g < B; ++g) {
         const int n = goff[g + 1] - goff[g];
-        if (n < 3 || n > GMC_MAX_GRAPH_NODES) return GMC_ERR_GRAPH_SIZE;
+        if (n < first || n > GMC_MAX_GRAPH_NODES) return GMC_ERR_GRAPH_SIZE;
     }
     if ((long long)cptr_cap < (long long)goff[B] + B) return GMC_ERR_SHAPE;
     std::vector<int> colour(GMC_MAX_GRAPH_NODES), mark, count;
@@ -94,10 +95,10 @@ extern "C" int gmc_refine_order_host(int32_t B, const int32_t *goff, const int32
         const int r0 = goff[g], n = goff[g + 1] - r0;
         int ncol = 0;
         mark.clear();   // mark[c] == v: colour c is taken at node v; stamps of the previous graph must not survive
-        for (int v = 3; v < n; ++v) {
+        for (int v = first; v < n; ++v) {
             for (int e = rowptr[r0 + v]; e < rowptr[r0 + v + 1]; ++e) {
                 const int u = lcol[e];
-                if (u >= 3 && u < v) mark[colour[u]] = v;   // colours taken by movable neighbours of smaller id
+                if (u >= first && u < v) mark[colour[u]] = v;   // colours taken by movable neighbours of smaller id
             }
             int c = 0;
             while (c < ncol && mark[c] == v) ++c;
@@ -108,7 +109,7 @@ extern "C" int gmc_refine_order_host(int32_t B, const int32_t *goff, const int32
             colour[v] = c;
         }
         count.assign(ncol, 0);
-        for (int v = 3; v < n; ++v) ++count[colour[v]];
+        for (int v = first; v < n; ++v) ++count[colour[v]];
         cgoff[g] = kp;
         cptr[kp++] = pos;
         for (int c = 0; c < ncol; ++c) {   // count[c] becomes the next free place of class c
@@ -117,10 +118,23 @@ extern "C" int gmc_refine_order_host(int32_t B, const int32_t *goff, const int32
             pos += m;
             cptr[kp++] = pos;
         }
-        for (int v = 3; v < n; ++v) order[count[colour[v]]++] = r0 + v;   // increasing id inside each class
+        for (int v = first; v < n; ++v) order[count[colour[v]]++] = r0 + v;   // increasing id inside each class
     }
     cgoff[B] = kp;
     return GMC_OK;
+}
+
+extern "C" int gmc_refine_order_host(int32_t B, const int32_t *goff, const int32_t *rowptr, const int32_t *lcol,
+                                     int32_t *order, int32_t *cgoff, int32_t *cptr, int32_t cptr_cap) {
+    return order_host(B, goff, rowptr, lcol, 3, order, cgoff, cptr, cptr_cap);
+}
+
+// the same colouring with the movable nodes starting at K: the order gmc_round_conditional_f32 (round.hip) walks
+extern "C" int gmc_round_order_host(int32_t B, const int32_t *goff, const int32_t *rowptr, const int32_t *lcol,
+                                    int32_t K, int32_t *order, int32_t *cgoff, int32_t *cptr, int32_t cptr_cap) {
+    if (!goff || !rowptr || !lcol || !order || !cgoff || !cptr) return GMC_ERR_NULL;
+    if (K < 2 || K > GMC_KWAY_MAX_CLASSES) return GMC_ERR_CLASSES;
+    return order_host(B, goff, rowptr, lcol, K, order, cgoff, cptr, cptr_cap);
 }
 
 extern "C" int gmc_refine_local_f32(const gmc_batch *batch, const int32_t *order, const int32_t *cgoff,

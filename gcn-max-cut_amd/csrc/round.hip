@@ -1,0 +1,238 @@
+// Rounding of node probabilities by conditional expectations, followed by the local search's descent (an extension:
+// the reference decodes by argmax or by random samples, TestingNeuralNetwork.py:66-122).  The algorithm is stated in
+// include/gcnmaxcut.h (gmc_round_conditional_f32); the colouring and the (colour, id) order are those of refine.hip
+// with the movable nodes starting at K (gmc_round_order_host), the descent is refine.hip's sweep at K classes, the
+// score is cut_body.h's.
+//
+// One 256-thread workgroup per graph, K a template argument.  The workgroup's LDS, sized by n_max:
+//
+//   q      [n_max][K] float   the state: a node's row of P until it is rounded, e_class afterwards (terminals: from
+//                             the start).  A node's K values are contiguous, so a neighbour costs one read of K floats.
+//   cls    [n_max] byte       the class bytes: what the descent reads (the state is one-hot by then, so the sums over
+//                             q are sums of the weights whose neighbour holds the class: one byte per neighbour instead
+//                             of K floats, and at K = 3 literally move_body.h's sums), what block_cut scores, the output.
+//
+// (4K + 1) * n_max bytes: 33 * n_max at K = 8, beyond 64 KiB from n_max = 1986 (the launch raises the kernel's
+// dynamic-LDS limit then), 132 KiB at n_max = GMC_MAX_GRAPH_NODES.
+#include "gmc_common.h"
+#include "cut_body.h"
+
+namespace {
+
+struct RoundArgs {
+    gmc_batch b;
+    const float *P;          // [R][K]
+    const int *order;        // movable rows of each graph, sorted by (colour, id)   (gmc_round_order_host)
+    const int *cgoff;        // [B+1] first class pointer of each graph
+    const int *cptr;         // class k of graph g: order[cptr[cgoff[g]+k] .. cptr[cgoff[g]+k+1])
+    int max_descent_sweeps;
+    signed char *assign;     // [R]
+    float *cut;              // [B]
+    float *expected;         // [B] or NULL
+    int *sweeps;             // [B] or NULL
+};
+
+// K floats in registers: every index below is a constant once the loops are unrolled (an index that is not would put
+// the array into scratch)
+template <int K>
+struct Sums {
+    float m[K];
+};
+
+// M_k = sum over the edges of local row l, CSR order, self-loops skipped, of w_e * q_u[k], from +0.  Product and sum
+// are rounded separately: hipcc contracts a * b + c into one fused multiply-add unless told not to.
+template <int K>
+__device__ __forceinline__ Sums<K> state_sums(const int *rp, const int *col, const float *vals, const float *q, int l) {
+#pragma clang fp contract(off)
+    Sums<K> s;
+#pragma unroll
+    for (int k = 0; k < K; ++k) s.m[k] = 0.f;
+    const int e1 = rp[l + 1];
+    for (int e = rp[l]; e < e1; ++e) {
+        const int u = col[e];
+        if (u == l) continue;
+        const float w = vals ? vals[e] : 1.0f;
+        const float *qu = q + u * K;
+#pragma unroll
+        for (int k = 0; k < K; ++k) {
+            const float t = w * qu[k];
+            s.m[k] = s.m[k] + t;
+        }
+    }
+    return s;
+}
+
+// the same sums over a one-hot state, read from the class bytes: W_k = sum of the weights of the edges to neighbours of
+// class k (K = 3: move_body.h's class_sums, the same operations in the same order)
+template <int K>
+__device__ __forceinline__ Sums<K> class_sums_k(const int *rp, const int *col, const float *vals,
+                                                const unsigned char *cls, int l) {
+    Sums<K> s;
+#pragma unroll
+    for (int k = 0; k < K; ++k) s.m[k] = 0.f;
+    const int e1 = rp[l + 1];
+    for (int e = rp[l]; e < e1; ++e) {
+        const int u = col[e];
+        if (u == l) continue;
+        const float w = vals ? vals[e] : 1.0f;
+        const int cu = cls[u];
+#pragma unroll
+        for (int k = 0; k < K; ++k) s.m[k] += cu == k ? w : 0.f;
+    }
+    return s;
+}
+
+// the class of the smallest sum, the lowest index on ties; wk = that sum
+template <int K>
+__device__ __forceinline__ int smallest(const Sums<K> &s, float &wk) {
+    int kk = 0;
+    wk = s.m[0];
+#pragma unroll
+    for (int k = 1; k < K; ++k)
+        if (s.m[k] < wk) { kk = k; wk = s.m[k]; }
+    return kk;
+}
+
+// the node's share of the expected cut: sum over its edges (self-loops skipped) of w_e * (1 - q_u . q_l)
+template <int K>
+__device__ __forceinline__ float expected_row(const int *rp, const int *col, const float *vals, const float *q, int l) {
+#pragma clang fp contract(off)
+    float ql[K];
+#pragma unroll
+    for (int k = 0; k < K; ++k) ql[k] = q[l * K + k];
+    float acc = 0.f;
+    const int e1 = rp[l + 1];
+    for (int e = rp[l]; e < e1; ++e) {
+        const int u = col[e];
+        if (u == l) continue;
+        const float w = vals ? vals[e] : 1.0f;
+        float dot = 0.f;
+#pragma unroll
+        for (int k = 0; k < K; ++k) dot += q[u * K + k] * ql[k];
+        acc += w * (1.0f - dot);
+    }
+    return acc;
+}
+
+template <int K>
+__global__ __launch_bounds__(256) void round_conditional_kernel(RoundArgs a) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
+    __shared__ float red[4];
+    const int g = blockIdx.x;
+    const int r0 = a.b.goff[g];
+    const int n = a.b.goff[g + 1] - r0;
+    if (n > a.b.n_max || n < K) return;   // (a batch that contradicts its own n_max: the LDS is sized by it)
+    float *q = reinterpret_cast<float *>(lds);
+    unsigned char *cls = lds + (size_t)a.b.n_max * K * sizeof(float);
+    const int *rp = a.b.rowptr + r0;
+    const int *col = a.b.lcol;
+    const float *vals = a.b.vals;
+    // state: terminals e_l (their rows of P are not read), every other node its row of P
+    const float *Pg = a.P + (long)r0 * K;
+    for (int i = threadIdx.x; i < n * K; i += blockDim.x) {
+        const int l = i / K, k = i - l * K;
+        q[i] = l < K ? (l == k ? 1.0f : 0.0f) : Pg[i];
+    }
+    for (int l = threadIdx.x; l < n; l += blockDim.x) cls[l] = (unsigned char)(l < K ? l : 0);
+    __syncthreads();
+    if (a.expected) {   // workgroup-uniform
+        float acc = 0.f;
+        for (int l = threadIdx.x; l < n; l += blockDim.x) acc += expected_row<K>(rp, col, vals, q, l);
+        acc = gmc::wave_sum(acc);
+        if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
+        __syncthreads();
+        if (threadIdx.x == 0) a.expected[g] = (((red[0] + red[1]) + red[2]) + red[3]) * 0.5f;
+        __syncthreads();   // every row has read the unrounded state, thread 0 has read red
+    }
+    const int k0 = a.cgoff[g];
+    const int classes = a.cgoff[g + 1] - k0 - 1;
+    // rounding: one visit of every movable node, class by class
+    for (int k = 0; k < classes; ++k) {
+        const int hi = a.cptr[k0 + k + 1];
+        for (int i = a.cptr[k0 + k] + threadIdx.x; i < hi; i += blockDim.x) {
+            const int l = a.order[i] - r0;
+            if (l < K || l >= n) continue;   // not a movable row of this graph: never touch LDS for it
+            const Sums<K> s = state_sums<K>(rp, col, vals, q, l);
+            float wk;
+            const int kk = smallest<K>(s, wk);
+#pragma unroll
+            for (int c = 0; c < K; ++c) q[l * K + c] = c == kk ? 1.0f : 0.0f;
+            cls[l] = (unsigned char)kk;
+        }
+        __syncthreads();   // the next class, the descent or the cut count reads what this one wrote
+    }
+    // descent: refine.hip's sweeps at K classes over the class bytes
+    int sw = 0;
+    while (sw < a.max_descent_sweeps) {
+        ++sw;
+        int moved = 0;
+        for (int k = 0; k < classes; ++k) {
+            const int hi = a.cptr[k0 + k + 1];
+            for (int i = a.cptr[k0 + k] + threadIdx.x; i < hi; i += blockDim.x) {
+                const int l = a.order[i] - r0;
+                if (l < K || l >= n) continue;
+                const Sums<K> s = class_sums_k<K>(rp, col, vals, cls, l);
+                const int c = cls[l];
+                float wc = s.m[0];
+#pragma unroll
+                for (int j = 1; j < K; ++j) wc = c == j ? s.m[j] : wc;
+                float wk;
+                const int kk = smallest<K>(s, wk);
+                if (wk < wc) {
+                    cls[l] = (unsigned char)kk;
+                    moved = 1;
+                }
+            }
+            if (k + 1 < classes) __syncthreads();
+        }
+        if (!__syncthreads_or(moved)) break;
+    }
+    signed char *as = a.assign + r0;
+    for (int l = threadIdx.x; l < n; l += blockDim.x) as[l] = (signed char)cls[l];
+    const float cut = gmc::block_cut(a.b, cls, r0, n, red);   // scored as gmc_refine_local_f32 scores
+    if (threadIdx.x == 0) {
+        a.cut[g] = cut;
+        if (a.sweeps) a.sweeps[g] = sw;
+    }
+}
+
+template <int K>
+int round_launch(const RoundArgs &a, hipStream_t st) {
+    const size_t lds = (size_t)a.b.n_max * (K * sizeof(float) + 1);
+    if (lds > 64 * 1024) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(round_conditional_kernel<K>),
+                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) return (int)e;
+    }
+    GmcProbeScope probe(GMC_K_REFINE, st);
+    hipLaunchKernelGGL((round_conditional_kernel<K>), dim3(a.b.B), dim3(256), lds, st, a);
+    GMC_LAUNCH_CHECK();
+    return GMC_OK;
+}
+
+}  // namespace
+
+extern "C" int gmc_round_conditional_f32(const gmc_batch *batch, const float *P, int32_t K, const int32_t *order,
+                                         const int32_t *cgoff, const int32_t *cptr, int32_t max_descent_sweeps,
+                                         int8_t *assign, float *cut, float *expected, int32_t *sweeps,
+                                         gmc_stream_t stream) {
+    if (!batch || !P || !order || !cgoff || !cptr || !assign || !cut) return GMC_ERR_NULL;
+    if (batch->abi != GMC_VERSION) return GMC_ERR_ABI;
+    if (!batch->goff || !batch->rowptr || !batch->lcol) return GMC_ERR_NULL;
+    if (K < 2 || K > GMC_KWAY_MAX_CLASSES) return GMC_ERR_CLASSES;
+    if (max_descent_sweeps < 0 || batch->B < 0) return GMC_ERR_SHAPE;
+    if (batch->B > 0 && (batch->n_max < K || batch->n_max > GMC_MAX_GRAPH_NODES)) return GMC_ERR_GRAPH_SIZE;
+    if (batch->B == 0) return GMC_OK;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const RoundArgs a{*batch, P, order, cgoff, cptr, max_descent_sweeps, reinterpret_cast<signed char *>(assign), cut,
+                      expected, sweeps};
+    switch (K) {
+        case 2: return round_launch<2>(a, st);
+        case 3: return round_launch<3>(a, st);
+        case 4: return round_launch<4>(a, st);
+        case 5: return round_launch<5>(a, st);
+        case 6: return round_launch<6>(a, st);
+        case 7: return round_launch<7>(a, st);
+        default: return round_launch<8>(a, st);
+    }
+}

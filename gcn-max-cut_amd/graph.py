@@ -291,22 +291,31 @@ class GraphBatch:
     def ref(self):
         return C.byref(self.c)
 
-    def refine_order(self):
-        """(order, cgoff, cptr) on the device: the colour classes gmc_refine_local_f32 walks (gmc_refine_order_host).
-        Computed on first use and kept with the batch; batches that are never refined never pay for it."""
-        if getattr(self, "_refine", None) is None:
+    def refine_order(self, K: int = 3):
+        """(order, cgoff, cptr) on the device: the colour classes gmc_refine_local_f32 walks (gmc_refine_order_host),
+        or, for ``K`` other than 3, the ones gmc_round_conditional_f32 walks when nodes 0..K-1 are the terminals
+        (gmc_round_order_host).  Computed on first use and kept with the batch, per ``K``; batches that are never
+        refined never pay for it."""
+        K = int(K)
+        cache = self.__dict__.setdefault("_refine", {})
+        if K not in cache:
             h = self.host
             order = np.zeros(max(h.R, 1), np.int32)
             cgoff = np.zeros(h.B + 1, np.int32)
             cptr = np.zeros(h.R + h.B, np.int32)
             ptr = lambda a: a.ctypes.data_as(C.c_void_p)
             go32 = h.goff.astype(np.int32)
-            rc = hip.load().gmc_refine_order_host(h.B, ptr(go32), ptr(h.rowptr), ptr(h.lcol), ptr(order), ptr(cgoff),
-                                                  ptr(cptr), cptr.size)
-            hip.check(rc, "gmc_refine_order_host")
+            if K == 3:
+                rc = hip.load().gmc_refine_order_host(h.B, ptr(go32), ptr(h.rowptr), ptr(h.lcol), ptr(order),
+                                                      ptr(cgoff), ptr(cptr), cptr.size)
+                hip.check(rc, "gmc_refine_order_host")
+            else:
+                rc = hip.load().gmc_round_order_host(h.B, ptr(go32), ptr(h.rowptr), ptr(h.lcol), K, ptr(order),
+                                                     ptr(cgoff), ptr(cptr), cptr.size)
+                hip.check(rc, "gmc_round_order_host")
             dev = lambda a: torch.from_numpy(a).to(self.device)
-            self._refine = (dev(order), dev(cgoff), dev(cptr[:max(int(cgoff[-1]), 1)].copy()))
-        return self._refine
+            cache[K] = (dev(order), dev(cgoff), dev(cptr[:max(int(cgoff[-1]), 1)].copy()))
+        return cache[K]
 
     def split(self, t: torch.Tensor) -> List[torch.Tensor]:
         """Per-graph views of a [R, ...] tensor."""

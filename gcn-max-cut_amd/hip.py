@@ -124,6 +124,8 @@ def _api() -> dict:
         "gmc_refine_local_f32": (i, [B, vp, vp, vp, i32, vp, i32, vp, vp, vp, vp, vp, vp]),
         "gmc_refine_anneal_f32": (i, [B, vp, vp, vp, i32, vp, vp, i32, vp, C.c_uint64, i32, vp, vp, vp, vp, vp, vp, vp]),
         "gmc_refine_anneal_staged": (i, [B]),
+        "gmc_round_order_host": (i, [i32, vp, vp, vp, i32, vp, vp, vp, i32]),
+        "gmc_round_conditional_f32": (i, [B, vp, i32, vp, vp, vp, i32, vp, vp, vp, vp, vp]),
     }
 
 

@@ -182,7 +182,8 @@ enum {
     GMC_K_FWD1_FUSED = 12, /* W1 gather + layer-1 aggregation (+ fused H@W2), one kernel */
     GMC_K_DECODE = 13,     /* post-processing sampler + cut count */
     GMC_K_FINISH = 14,     /* fold of the gradient partials (+ fused Adam) over the flat buffer */
-    GMC_K_REFINE = 15,     /* local search over decoded candidates + cut count (gmc_refine_local_f32) */
+    GMC_K_REFINE = 15,     /* local search over decoded candidates + cut count (gmc_refine_local_f32); also the
+                            * rounding by conditional expectations + descent (gmc_round_conditional_f32) */
     GMC_K_ANNEAL = 16,     /* annealing + descent over decoded candidates + cut count (gmc_refine_anneal_f32) */
     GMC_K_GEMM = 17,       /* dense fp32 GEMM on the matrix cores (gmc_gemm_f32; the dense-feature path) */
     GMC_K_SAMPLE = 18,     /* seeded post-processing sampler + cut count (gmc_decode_sample_seeded_f32) */
@@ -605,6 +606,59 @@ int gmc_refine_anneal_f32(const gmc_batch *batch, const int32_t *order, const in
  * batch, 0 when the graphs are too large for that and it reads the batch's arrays in global memory (same results, bit
  * for bit); < 0 on a bad argument. */
 int gmc_refine_anneal_staged(const gmc_batch *batch);
+
+/* ---- rounding by conditional expectations (extension: no counterpart in the reference) ---------------------------
+ *
+ * GMC_LOSS_EXPECTED_CUT trains on the expected cut of rounding every node independently from its row of P.  This
+ * decoder turns such a P into ONE partition whose cut is not below that expectation (the method of conditional
+ * expectations), deterministically and with one visit per node, then optionally descends from it with the local
+ * search.  It takes K = 2 .. GMC_KWAY_MAX_CLASSES classes.  Per graph of the batch (local ids 0..n-1, n >= K, CSR rows
+ * of an undirected graph, weight w_e = 1 where vals is NULL); nodes 0..K-1 are the terminals of classes 0..K-1:
+ *  1. state: q[u][0..K-1], fp32.  A terminal u has q_u = e_u; its row of P is never read into the result, whatever it
+ *     holds (NaN included).  Every other node has q_u = its row of P as given (not renormalised).
+ *  2. expected cut (optional output): 1/2 * sum_v sum_{e in row v, u != v} w_e * (1 - q_u . q_v) over that state,
+ *     summed in fp32 - one partial per row, the rows of a thread added in ascending order, a butterfly per wave, the
+ *     four wave sums ascending (the block sum of the cut count).  Reproducible run to run; the bits are not pinned.
+ *  3. rounding: the movable nodes K..n-1 are coloured first-fit as for the local search above, with K in the place of
+ *     3 (gmc_round_order_host).  The colour classes are visited in increasing colour.  Node v of a class computes, for
+ *     every class k, M_k = sum_{e in row v, CSR order, u != v} w_e * q_u[k] starting from +0, the product and the sum
+ *     each rounded to fp32 (no fused multiply-add), over the state as it stands at the start of that colour step.  v
+ *     takes the class kk of the smallest M (the lowest index on ties): q_v becomes e_kk, its class byte kk.  No two
+ *     nodes of a class are adjacent, so the result equals a sequential visit in (colour, id) order.
+ *     M_k is the cut v loses in expectation by taking class k, so the smallest M keeps the conditional expectation of
+ *     the cut from falling: in exact arithmetic the rounded cut is >= the expected cut of step 2.  In fp32 a decision
+ *     can lose at most 2 (deg + 1) 2^-24 of the node's absolute weighted degree.
+ *  4. descent: up to max_descent_sweeps sweeps of the local search's rule at K classes over the same state, which is
+ *     one-hot by now, so the same M_k are the sums of the weights of v's edges to neighbours of class k: v moves to
+ *     the class kk of the smallest M (lowest index on ties) iff M_kk < M_own; sweeps stop after one that moves
+ *     nothing.  At K = 3 this is gmc_refine_local_f32 on the rounded assignment, byte for byte and sweep for sweep.
+ *  5. score: the cut of the class bytes as gmc_decode_sample_f32 and gmc_refine_local_f32 count it (the same code,
+ *     the same bits).
+ * Nothing is claimed about denormal probabilities or products (a tie may then hinge on how they are flushed). */
+
+/* HOST routine (all pointers are host pointers): gmc_refine_order_host's colouring and (colour, id) order with the
+ * movable nodes starting at K instead of 3 (order: R - K*B entries; cptr_cap >= R + B as there).  K = 3 writes what
+ * gmc_refine_order_host writes, array for array.  K outside 2..GMC_KWAY_MAX_CLASSES GMC_ERR_CLASSES; a graph with
+ * < K or > GMC_MAX_GRAPH_NODES nodes GMC_ERR_GRAPH_SIZE. */
+int gmc_round_order_host(int32_t B, const int32_t *goff, const int32_t *rowptr, const int32_t *lcol, int32_t K,
+                         int32_t *order, int32_t *cgoff, int32_t *cptr, int32_t cptr_cap);
+
+/* The rounding above for every graph of the batch: P [R,K] device floats, order / cgoff / cptr gmc_round_order_host's
+ * output for the same K in device memory.  Outputs (device): assign [R] int8 (a row of candidates for
+ * gmc_refine_local_f32 / gmc_refine_anneal_f32 when K = 3), cut [B]; optional (NULL: not computed) expected [B], the
+ * expected cut of step 2, and sweeps [B], the descent sweeps run, counted as gmc_refine_local_f32 counts them (0 for
+ * max_descent_sweeps = 0).  Argument checks, before any HIP call, in the order of the other decoders: a NULL pointer
+ * (expected and sweeps aside) GMC_ERR_NULL, batch->abi GMC_ERR_ABI, a NULL goff / rowptr / lcol GMC_ERR_NULL, K outside
+ * 2..GMC_KWAY_MAX_CLASSES GMC_ERR_CLASSES, max_descent_sweeps < 0 or B < 0 GMC_ERR_SHAPE, n_max < K or n_max >
+ * GMC_MAX_GRAPH_NODES GMC_ERR_GRAPH_SIZE; B == 0 returns GMC_OK without a launch.  A graph with fewer than K or more
+ * than n_max nodes inside a batch is skipped (nothing of it is written; the caller refuses such batches: goff is
+ * device memory).  One 256-thread workgroup per graph keeps q [n_max][K] and the class bytes in LDS, (4K + 1) * n_max
+ * bytes - 132 KiB for K = 8 at GMC_MAX_GRAPH_NODES, which fits, so that constant is the only size limit.  The call
+ * allocates nothing and does not synchronise: one launch on the caller's stream, no atomics, bitwise reproducible. */
+int gmc_round_conditional_f32(const gmc_batch *batch, const float *P /*[R,K]*/, int32_t K,
+                              const int32_t *order, const int32_t *cgoff, const int32_t *cptr,
+                              int32_t max_descent_sweeps, int8_t *assign /*[R]*/, float *cut /*[B]*/,
+                              float *expected /*[B] or NULL*/, int32_t *sweeps /*[B] or NULL*/, gmc_stream_t stream);
 
 #ifdef __cplusplus
 }
