@@ -14,6 +14,10 @@ generated on the host, and a graph's samples depend on the seed and its index in
 ``conditional_rounding`` / ``round_dataset`` (extension) round the probabilities by conditional expectations
 (``gmc_round_conditional_f32``): one deterministic partition per graph whose cut is not below the expected cut, for
 any ``number_classes`` in 2..8.
+``sampling_optimization``, ``kway_local_search``, ``kway_annealing`` and ``search_dataset`` (extension) are the seeded
+sampler, the local search and the annealing for ``number_classes`` in 2..8 (``gmc_kway_decode_sample_seeded_f32``,
+``gmc_kway_refine_anneal_f32``); at three classes they return what the 3-class functions return.  Those, and
+``decode_dataset``, keep refusing any other class count.
 The reporting / plotting half of the reference module (``analyze_results`` .. ``generate_summary_report``,
 :297-638) is presentation code outside the path and is not reproduced.
 """
@@ -377,6 +381,168 @@ def conditional_rounding(node_probabilities, graph, descent_sweeps: int = 0) -> 
     return assign.cpu().tolist(), _as_number(cut.item())
 
 
+# ---- the seeded sampler, the local search and the annealing for number_classes K in 2..8 (extension) -----------------
+def _search_classes(what: str, classes: int) -> int:
+    """The class count of the K-class decoders (kway_search.hip is written for 2..8 classes)."""
+    K = int(classes)
+    if not 2 <= K <= hip.KWAY_MAX_CLASSES:
+        raise ValueError(f"{what} takes number_classes in 2..{hip.KWAY_MAX_CLASSES}, got {K} classes")
+    return K
+
+
+def assign_partitions_seeded_kway(node_probs: np.ndarray, seed: int, graph_index: int = 0, iteration: int = 0) -> List[int]:
+    """:func:`assign_partitions_seeded` for probabilities of K = 2..8 columns (host form of kway_search.hip's sampler):
+    nodes 0..K-1 are the terminals, node l >= K takes the first class j in 0..K-2 whose running double sum exceeds the
+    hashed uniform, else class K-1 (no compare against the last sum).  At K = 3 it is :func:`assign_partitions_seeded`."""
+    probs_all = np.asarray(node_probs)
+    if probs_all.ndim != 2:
+        raise ValueError(f"node_probs must be [n, number_classes], got {tuple(probs_all.shape)}")
+    K = _search_classes("assign_partitions_seeded_kway", probs_all.shape[1])
+    if int(iteration) < 0 or int(iteration) >= 1 << 31:
+        raise ValueError(f"iteration must be in 0..2^31-1, got {iteration}")
+    key = _graph_key(int(seed) & _M64, graph_index)
+    out = list(range(min(K, len(probs_all))))
+    for l, probs in enumerate(probs_all[K:], K):
+        h = _mix64((key + _GOLD * (((int(iteration) << 32) | l) + 1)) & _M64)
+        r = float(h >> 11) * 2.0 ** -53          # < 2^53: exact
+        running = float(probs[0])
+        for j in range(K - 1):
+            if j:
+                running = running + float(probs[j])
+            if r < running:
+                out.append(j)
+                break
+        else:
+            out.append(K - 1)
+    return out
+
+
+def _needs_terminals(batch: GraphBatch, K: int) -> None:
+    if batch.B and int(batch.sizes.min()) < K:
+        raise ValueError(f"number_classes = {K}: every graph needs at least {K} nodes (nodes 0..{K - 1} are the "
+                         f"terminals), got one with {int(batch.sizes.min())}")
+
+
+def _kway_sample_on_gpu(batch: GraphBatch, P: torch.Tensor, iterations: int, seed: int, indices, keep_samples: bool):
+    """The seeded sampler at K = P.shape[1] classes (gmc_kway_decode_sample_seeded_f32), as ``_sample_seeded_on_gpu``."""
+    K = _search_classes("the K-class sampler", P.shape[1])
+    _needs_terminals(batch, K)
+    keys = sample_keys(seed, range(batch.B) if indices is None else indices)
+    if keys.size != batch.B:
+        raise ValueError(f"{keys.size} graph indices for a batch of {batch.B} graphs")
+    dev = batch.device
+    gkey = torch.from_numpy(keys.view(np.int64)).to(dev) if batch.B else torch.zeros(1, dtype=torch.int64, device=dev)
+    assign_all = torch.empty((iterations, batch.R), dtype=torch.int8, device=dev) if keep_samples else None
+    cut_all = torch.empty((batch.B, iterations), dtype=torch.float32, device=dev)
+    best_assign = torch.empty(batch.R, dtype=torch.int32, device=dev)
+    best_cut = torch.empty(batch.B, dtype=torch.float32, device=dev)
+    best_iter = torch.empty(batch.B, dtype=torch.int32, device=dev)
+    p = hip.ptr
+    rc = hip.load().gmc_kway_decode_sample_seeded_f32(batch.ref(), p(P.contiguous()), K, p(gkey), iterations,
+                                                      p(assign_all), p(cut_all), p(best_assign), p(best_cut),
+                                                      p(best_iter), hip.stream())
+    hip.check(rc, "gmc_kway_decode_sample_seeded_f32")
+    return best_assign, best_cut, cut_all, assign_all
+
+
+def sampling_optimization(node_probabilities, graph, iterations: int = 200, *, seed: int = 0,
+                          graph_index: int = 0) -> Tuple[List[int], Any]:
+    """Best of ``iterations`` seeded samples of the node probabilities [n, K], K = number_classes in 2..8 (extension,
+    include/gcnmaxcut.h ``gmc_kway_decode_sample_seeded_f32``): what ``post_processing_optimization(..., seed=seed)``
+    does for a 3-class model - and, at K = 3, returns.  Nodes 0..K-1 are the terminals; ``graph_index`` is the graph's
+    position in its dataset.  Returns the assignment and its cut value."""
+    probs = node_probabilities if isinstance(node_probabilities, torch.Tensor) else torch.from_numpy(np.asarray(node_probabilities))
+    if probs.dim() != 2:
+        raise ValueError(f"node_probabilities must be [n, number_classes], got {tuple(probs.shape)}")
+    K = _search_classes("sampling_optimization", probs.shape[1])
+    n = graph.number_of_nodes()
+    if n < K:
+        raise ValueError(f"number_classes = {K}: the graph needs at least {K} nodes (nodes 0..{K - 1} are the "
+                         f"terminals), got {n}")
+    if probs.shape[0] != n:
+        raise ValueError(f"node_probabilities has {probs.shape[0]} rows, the graph {n} nodes")
+    dev = hip.require_gpu()
+    probs = probs.detach().to(dev, torch.float32)
+    if iterations <= 0:
+        return None, -float('inf')
+    batch = GraphBatch([from_networkx(graph)], None, dev)
+    best_assign, best_cut, _, _ = _kway_sample_on_gpu(batch, probs, iterations, int(seed) & _M64, [graph_index],
+                                                      keep_samples=False)
+    return best_assign.cpu().tolist(), _as_number(best_cut.item())
+
+
+def _kway_anneal_on_gpu(batch: GraphBatch, K: int, assign: torch.Tensor, inv_temp: np.ndarray, seed: int,
+                        max_descent_sweeps: int):
+    """Annealing + descent at K classes (gmc_kway_refine_anneal_f32) over the candidates assign [cands, R] int8, in
+    place; returns the best assignment [R], its cut and candidate index per graph.  No annealing sweeps: the K-class
+    local search."""
+    _needs_terminals(batch, K)
+    dev = batch.device
+    cands = int(assign.shape[0])
+    order, cgoff, cptr = batch.refine_order(K)
+    sweeps = int(len(inv_temp))
+    inv_t = torch.from_numpy(np.ascontiguousarray(inv_temp, np.float32)).to(dev) if sweeps else None
+    levels = torch.from_numpy(anneal_levels()).to(dev) if sweeps else None
+    cut_all = torch.empty((batch.B, cands), dtype=torch.float32, device=dev)
+    best_assign = torch.empty(batch.R, dtype=torch.int32, device=dev)
+    best_cut = torch.empty(batch.B, dtype=torch.float32, device=dev)
+    best_idx = torch.empty(batch.B, dtype=torch.int32, device=dev)
+    p = hip.ptr
+    rc = hip.load().gmc_kway_refine_anneal_f32(batch.ref(), K, p(order), p(cgoff), p(cptr), cands, p(assign), p(inv_t),
+                                               sweeps, p(levels), int(seed) & _M64, int(max_descent_sweeps), p(cut_all),
+                                               p(best_assign), p(best_cut), p(best_idx), None, None, hip.stream())
+    hip.check(rc, "gmc_kway_refine_anneal_f32")
+    return best_assign, best_cut, best_idx
+
+
+def _kway_partition(what: str, partition_assignment, graph, number_classes: int) -> Tuple[int, np.ndarray]:
+    """The checks the K-class searches share: the class count, the length, the class values, the terminals' room."""
+    K = _search_classes(what, number_classes)
+    part = np.asarray(list(partition_assignment), dtype=np.int64)
+    n = graph.number_of_nodes()
+    if part.shape != (n,):
+        raise ValueError(f"partition_assignment has {part.size} entries, the graph {n} nodes")
+    if n < K:
+        raise ValueError(f"number_classes = {K}: the graph needs at least {K} nodes (nodes 0..{K - 1} are the "
+                         f"terminals), got {n}")
+    if int(part.min()) < 0 or int(part.max()) > K - 1:
+        raise ValueError(f"partition_assignment holds a class outside 0..{K - 1} (number_classes = {K})")
+    return K, part
+
+
+def kway_local_search(partition_assignment, graph, number_classes: int, max_sweeps: int = 100) -> Tuple[List[int], Any]:
+    """:func:`local_search_optimization` for a partition into ``number_classes`` = 2..8 classes (extension,
+    include/gcnmaxcut.h ``gmc_kway_refine_anneal_f32`` without annealing sweeps): nodes 0..K-1 keep their classes,
+    every other node moves to the class that cuts the most of its edge weight, sweep after sweep, until a sweep moves
+    nothing or ``max_sweeps`` have run.  Returns the refined assignment and its cut value."""
+    K, part = _kway_partition("kway_local_search", partition_assignment, graph, number_classes)
+    if max_sweeps < 0:
+        raise ValueError(f"max_sweeps must be >= 0, got {max_sweeps}")
+    dev = hip.require_gpu()
+    batch = GraphBatch([from_networkx(graph)], None, dev)
+    assign = torch.from_numpy(part.astype(np.int8)).to(dev).reshape(1, -1)
+    best_assign, best_cut, _ = _kway_anneal_on_gpu(batch, K, assign, np.zeros(0, np.float32), 0, max_sweeps)
+    return best_assign.cpu().tolist(), _as_number(best_cut.item())
+
+
+def kway_annealing(partition_assignment, graph, number_classes: int, sweeps: int = 100, t_start: float = 1.5,
+                   t_end: float = 0.15, seed: int = 0, max_descent_sweeps: int = 100) -> Tuple[List[int], Any]:
+    """:func:`annealing_optimization` for a partition into ``number_classes`` = 2..8 classes (extension,
+    include/gcnmaxcut.h ``gmc_kway_refine_anneal_f32``): ``sweeps`` Metropolis sweeps cooling from ``t_start`` to
+    ``t_end`` (in units of the graph's mean edge weight), each node proposing the best of the K-1 other classes, the
+    best state passed through kept, then the K-class local search from it.  Nodes 0..K-1 keep their classes; the result
+    is never worse than the input and is reproducible from ``seed``.  Returns the assignment and its cut value."""
+    K, part = _kway_partition("kway_annealing", partition_assignment, graph, number_classes)
+    if sweeps < 0 or max_descent_sweeps < 0:
+        raise ValueError(f"sweeps and max_descent_sweeps must be >= 0, got {sweeps} and {max_descent_sweeps}")
+    dev = hip.require_gpu()
+    batch = GraphBatch([from_networkx(graph)], None, dev)
+    assign = torch.from_numpy(part.astype(np.int8)).to(dev).reshape(1, -1)
+    inv_temp = anneal_schedule(sweeps, t_start, t_end, _mean_edge_weight(batch))
+    best_assign, best_cut, _ = _kway_anneal_on_gpu(batch, K, assign, inv_temp, seed, max_descent_sweeps)
+    return best_assign.cpu().tolist(), _as_number(best_cut.item())
+
+
 def test_single_graph(model, dgl_graph, adjacency_matrix, nx_graph, terminals: List[int],
                       post_processing_iterations: int = 200, *, seed: Optional[int] = None,
                       graph_index: int = 0) -> Dict[str, Any]:
@@ -577,4 +743,61 @@ def round_dataset(model, processed_graphs: Dict, descent_sweeps: int = 0) -> Lis
         out.append({'nodes': hi - lo, 'simple_cut': _as_number(simple[g]), 'simple_assignment': S_host[lo:hi].tolist(),
                     'expected_cut': float(expected[g]), 'rounded_cut': _as_number(cut[g]),
                     'rounded_assignment': assign[lo:hi].tolist(), 'descent_sweeps': int(sweeps[g])})
+    return out
+
+
+def search_dataset(model, processed_graphs: Dict, samples: int = 200, *, sample_seed: int = 0, anneal_sweeps: int = 100,
+                   anneal_seed: int = 0, max_descent_sweeps: int = 100,
+                   candidates: Optional[int] = None) -> List[Dict[str, Any]]:
+    """Decode a whole dataset of a model of any ``number_classes`` in 2..8 with everything the 3-class path has
+    (extension): ONE batched forward, ONE rounding launch (``round_dataset(..., 0)``), ONE launch of the seeded sampler
+    (``gmc_kway_decode_sample_seeded_f32``, a graph's index its position in ``processed_graphs.values()``) and ONE
+    search launch (``gmc_kway_refine_anneal_f32``) over the candidates of every graph: candidate 0 the argmax decode,
+    candidate 1 the rounded partition, candidates 2.. the ``samples`` samples in iteration order.  ``candidates`` in
+    1..2 + samples takes a prefix of them (``None``: all); ``anneal_sweeps = 0`` is the local search alone.
+    ``samples = 0`` is allowed: the candidates are then the argmax and the rounded one.  Per graph: ``nodes``,
+    ``simple_cut`` / ``simple_assignment``, ``expected_cut``, ``rounded_cut`` / ``rounded_assignment`` (as
+    ``round_dataset(..., 0)`` reports them), ``post_cut`` / ``post_assignment`` (the best sample, with ``samples > 0``)
+    and ``searched_cut``, ``searched_assignment``, ``searched_from`` (the winning candidate)."""
+    if samples < 0:
+        raise ValueError(f"samples must be >= 0, got {samples}")
+    if anneal_sweeps < 0 or max_descent_sweeps < 0:
+        raise ValueError(f"anneal_sweeps and max_descent_sweeps must be >= 0, got {anneal_sweeps} and {max_descent_sweeps}")
+    take = 2 + samples if candidates is None else int(candidates)
+    if not 1 <= take <= 2 + samples:
+        raise ValueError(f"candidates must be in 1..{2 + samples}, got {candidates}")
+    items = list(processed_graphs.values())
+    eng = model.engine()
+    K = _search_classes("search_dataset", eng.K)
+    model.eval()
+    handles = [it[0] for it in items]
+    vals = [h.edge_values(it[1]) for h, it in zip(handles, items)]
+    batch = GraphBatch(handles, vals, eng.device)
+    _needs_terminals(batch, K)
+    P, S, loss = eng.forward(batch, 1.0, want_loss=True)
+    rnd_assign, rnd_cut, rnd_expected, _ = _round_on_gpu(batch, P, 0)
+    rows = [S.to(torch.int8).reshape(1, -1), rnd_assign.reshape(1, -1)]
+    sampled = None
+    if samples > 0:
+        best_assign, best_cut, _, assign_all = _kway_sample_on_gpu(batch, P, samples, int(sample_seed) & _M64,
+                                                                   range(len(items)), keep_samples=take > 2)
+        sampled = (best_assign.cpu().numpy(), best_cut.cpu().tolist())
+        if assign_all is not None:
+            rows.append(assign_all)
+    cands = torch.cat(rows)[:take].contiguous()
+    inv_temp = anneal_schedule(anneal_sweeps, scale=_mean_edge_weight(batch))
+    found_assign, found_cut, found_idx = [t.cpu().numpy() for t in
+                                          _kway_anneal_on_gpu(batch, K, cands, inv_temp, anneal_seed, max_descent_sweeps)]
+    S_host, simple = S.cpu().numpy(), (-loss).cpu().tolist()
+    rnd_assign, rnd_cut, rnd_expected = rnd_assign.cpu().numpy(), rnd_cut.cpu().numpy(), rnd_expected.cpu().numpy()
+    out = []
+    for g in range(len(items)):
+        lo, hi = int(batch.goff_host[g]), int(batch.goff_host[g + 1])
+        out.append({'nodes': hi - lo, 'simple_cut': _as_number(simple[g]), 'simple_assignment': S_host[lo:hi].tolist(),
+                    'expected_cut': float(rnd_expected[g]), 'rounded_cut': _as_number(rnd_cut[g]),
+                    'rounded_assignment': rnd_assign[lo:hi].tolist()})
+        if sampled is not None:
+            out[-1].update({'post_cut': _as_number(sampled[1][g]), 'post_assignment': sampled[0][lo:hi].tolist()})
+        out[-1].update({'searched_cut': _as_number(found_cut[g]), 'searched_assignment': found_assign[lo:hi].tolist(),
+                        'searched_from': int(found_idx[g])})
     return out

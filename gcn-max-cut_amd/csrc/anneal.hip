@@ -24,48 +24,17 @@
 #include "cut_body.h"
 #include "mix64.h"
 #include "move_body.h"
-
-#define GMC_ANNEAL_LDS_BUDGET (40 * 1024)
-#define GMC_ANNEAL_LDS_STATIC 512   // allowance for red, flag and the barrier's word (288 B as built)
+#include "anneal_layout.h"
 
 namespace {
 
 using gmc::mix64;
 using gmc::u64;
-
-struct AnnealArgs {
-    gmc_batch b;
-    const int *order, *cgoff, *cptr;   // gmc_refine_order_host's output
-    int cands, anneal_sweeps, max_descent_sweeps;
-    const float *inv_temp;   // [anneal_sweeps]
-    const float *levels;     // [GMC_ANNEAL_LEVELS]
-    u64 seed;
-    signed char *assign;     // [cands][R], in/out
-    float *cut_all;          // [B][cands]
-    int *snap_sweep;         // [B][cands] or NULL
-    int *sweeps;             // [B][cands] or NULL
-    int staged;              // the launch has room for the staged copy
-    int n_pad, off_starts, off_vals, off_order, off_ids;   // LDS layout (bytes from the dynamic base)
-};
-
-// the graph as the batch holds it in global memory
-struct GlobalCsr {
-    const int *rp;      // rowptr + r0: absolute edge positions of local row l
-    const int *col;
-    const float *vals;
-    const int *order;
-    int r0;
-    __device__ __forceinline__ int node(int i) const { return order[i] - r0; }
-};
-// the workgroup's copy in LDS (edge positions relative to the graph's first edge, order relative to its first entry)
-struct LdsCsr {
-    const int *rp;
-    const unsigned short *col;
-    const float *vals;
-    const unsigned short *order;
-    int i0;
-    __device__ __forceinline__ int node(int i) const { return order[i - i0]; }
-};
+using gmc::AnnealArgs;
+using gmc::GlobalCsr;
+using gmc::LdsCsr;
+using gmc::AnnealLayout;
+using gmc::anneal_layout;
 
 template <class G>
 __device__ __forceinline__ void anneal_body(const AnnealArgs &a, const G &g, unsigned char *sa, unsigned char *sb,
@@ -203,25 +172,6 @@ __global__ __launch_bounds__(256) void anneal_kernel(AnnealArgs a) {
 }
 
 __global__ __launch_bounds__(256) void anneal_pick_kernel(gmc::PickArgs a) { gmc::pick_best(a); }
-
-// LDS bytes of a launch for this batch and whether they include the staged copy
-struct AnnealLayout {
-    int staged, n_pad, off_starts, off_vals, off_order, off_ids, bytes;
-};
-AnnealLayout anneal_layout(const gmc_batch *b) {
-    AnnealLayout L{};
-    L.n_pad = (b->n_max + 15) & ~15;
-    const int base = 4 * GMC_ANNEAL_LEVELS + 2 * L.n_pad;
-    const long nnz = b->nnz_max > 0 ? b->nnz_max : 0;
-    L.off_starts = base;
-    L.off_vals = L.off_starts + (((b->n_max + 1) * 4 + 15) & ~15);
-    L.off_order = L.off_vals + (b->vals ? (int)((nnz * 4 + 15) & ~15L) : 0);
-    L.off_ids = L.off_order + 2 * L.n_pad;
-    const long total = L.off_ids + ((nnz * 2 + 15) & ~15L);
-    L.staged = nnz > 0 && total + GMC_ANNEAL_LDS_STATIC <= GMC_ANNEAL_LDS_BUDGET;
-    L.bytes = L.staged ? (int)total : base;
-    return L;
-}
 
 }  // namespace
 

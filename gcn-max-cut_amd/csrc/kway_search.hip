@@ -1,0 +1,332 @@
+// The seeded sampler and the annealing (with the local search as its descent) at K = 2..8 classes: the decoders of the
+// models gmc_kway_forward serves (an extension: the reference samples and stops, TestingNeuralNetwork.py:66-98, and is
+// 3-class).  Both algorithms are stated in include/gcnmaxcut.h (gmc_kway_decode_sample_seeded_f32,
+// gmc_kway_refine_anneal_f32); at K = 3 they are sample_seeded.hip's and anneal.hip's, output for output.
+//
+// K is a template argument, one 256-thread workgroup per (candidate, graph) as in those files.
+//
+// Sampler: the class bytes of a sample in n_max bytes of LDS, the cut by gmc::block_cut, the pick kernel regenerates
+// the winner from the hash.  The running sum of a row's probabilities lives in one register: the loop over the
+// constant K is unrolled and stops comparing after the first class that takes the draw.
+//
+// Annealing: the LDS layout of anneal.hip (anneal_layout.h: level table, state and best bytes, and the staged copy of
+// the graph's CSR when it fits GMC_ANNEAL_LDS_BUDGET) - it does not depend on K.  The K sums of a node are
+// compare-selected accumulators (move_body.h), "own sum" and "smallest among the others" unrolled compare chains; both
+// accessor paths run one templated body.
+#include "gmc_common.h"
+#include "cut_body.h"
+#include "mix64.h"
+#include "move_body.h"
+#include "anneal_layout.h"
+
+namespace {
+
+using gmc::mix64;
+using gmc::u64;
+using gmc::AnnealArgs;
+using gmc::AnnealLayout;
+using gmc::GlobalCsr;
+using gmc::LdsCsr;
+using gmc::Sums;
+
+// ---- the sampler --------------------------------------------------------------------------------------------------
+
+struct KSeededArgs {
+    gmc_batch b;
+    const float *P;          // [R,K]
+    const u64 *gkey;         // [B]
+    int iters;
+    signed char *assign_all; // [iters][R] or NULL
+    float *cut_all;          // [B][iters]
+    int *best_assign;        // [R]        (the pick kernel)
+    float *best_cut;         // [B]
+    int *best_iter;          // [B]
+};
+
+// key + GOLD * (((u64)it << 32 | l) + 1) without the node: l < 2^32 only adds GOLD * l
+__device__ __forceinline__ u64 iteration_base(u64 key, int it) {
+    return key + GMC_GOLD * (((u64)(unsigned)it << 32) + 1ULL);
+}
+
+// class of local node l >= K with probabilities p[0..K-1]: the first class j in 0..K-2 whose running double sum
+// exceeds the hashed uniform, class K-1 otherwise (no compare against the last sum: a NaN row gives K-1)
+template <int K>
+__device__ __forceinline__ int seeded_class_k(u64 base, int l, const float *p) {
+    const u64 h = mix64(base + GMC_GOLD * (u64)(unsigned)l);
+    const double r = (double)(h >> 11) * 0x1.0p-53;   // [0, 1), exact
+    double c = (double)p[0];
+    int cls = K - 1;
+    bool open = true;   // no class has taken the draw yet
+#pragma unroll
+    for (int j = 0; j < K - 1; ++j) {
+        if (j > 0) c = c + (double)p[j];
+        const bool take = open && r < c;
+        cls = take ? j : cls;
+        open = open && !take;
+    }
+    return cls;
+}
+
+template <int K>
+__global__ __launch_bounds__(256) void sample_seeded_k_kernel(KSeededArgs a) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char sa[];
+    __shared__ float red[4];
+    const int it = blockIdx.x, g = blockIdx.y;
+    const int r0 = a.b.goff[g];
+    const int n = a.b.goff[g + 1] - r0;
+    if (n > a.b.n_max || n < K) return;   // (the LDS is sized by n_max; a graph without its K terminals is skipped)
+    const u64 base = iteration_base(a.gkey[g], it);
+    for (int l = threadIdx.x; l < n; l += blockDim.x) {
+        const int c = l < K ? l : seeded_class_k<K>(base, l, a.P + (long)(r0 + l) * K);
+        sa[l] = (unsigned char)c;
+        if (a.assign_all) a.assign_all[(long)it * a.b.R + r0 + l] = (signed char)c;
+    }
+    __syncthreads();
+    const float cut = gmc::block_cut(a.b, sa, r0, n, red);
+    if (threadIdx.x == 0) a.cut_all[(long)g * a.iters + it] = cut;
+}
+
+// One workgroup per graph: the winning iteration, then its assignment again from the hash (never read from assign_all)
+template <int K>
+__global__ __launch_bounds__(256) void sample_seeded_k_pick_kernel(KSeededArgs a) {
+    const int g = blockIdx.x;
+    const int r0 = a.b.goff[g], n = a.b.goff[g + 1] - r0;
+    if (n > a.b.n_max || n < K) return;   // workgroup-uniform: the graphs the sampler skipped
+    const int best = gmc::pick_best_index(a.cut_all, a.iters, g, a.best_cut, a.best_iter);
+    const u64 base = iteration_base(a.gkey[g], best);
+    for (int l = threadIdx.x; l < n; l += blockDim.x)
+        a.best_assign[r0 + l] = l < K ? l : seeded_class_k<K>(base, l, a.P + (long)(r0 + l) * K);
+}
+
+template <int K>
+int sample_launch(const KSeededArgs &a, hipStream_t st) {
+    {
+        GmcProbeScope probe(GMC_K_SAMPLE, st);
+        hipLaunchKernelGGL((sample_seeded_k_kernel<K>), dim3(a.iters, a.b.B), dim3(256), (size_t)a.b.n_max, st, a);
+        GMC_LAUNCH_CHECK();
+    }
+    hipLaunchKernelGGL((sample_seeded_k_pick_kernel<K>), dim3(a.b.B), dim3(256), 0, st, a);
+    GMC_LAUNCH_CHECK();
+    return GMC_OK;
+}
+
+// ---- annealing + descent ------------------------------------------------------------------------------------------
+
+// one descent visit of local node l: the local search's rule at K classes (round.hip's descent; K = 3: local_move)
+template <int K, class G>
+__device__ __forceinline__ bool descent_visit(const G &g, unsigned char *sa, int l) {
+    const Sums<K> s = gmc::class_sums_k<K>(g.rp, g.col, g.vals, sa, l);
+    const int c = sa[l];
+    const float wc = gmc::own_sum_or_inf<K>(s, c);
+    float wk;
+    const int kk = gmc::smallest<K>(s, wk);
+    if (wk < wc) {
+        sa[l] = (unsigned char)kk;
+        return true;
+    }
+    return false;
+}
+
+template <int K, class G>
+__device__ __forceinline__ void anneal_body_k(const AnnealArgs &a, const G &g, unsigned char *sa, unsigned char *sb,
+                                              const float *lv, int n, int k0, int classes, float *red, int *flag) {
+    const int cand = blockIdx.x, gi = blockIdx.y;
+    int snap = 0;
+    if (a.anneal_sweeps > 0) {
+        float best_cut = gmc::block_cut_csr(g.rp, g.col, g.vals, sa, n, red);   // thread 0
+        __syncthreads();   // (thread 0 has read red before a graph without classes recounts)
+        for (int s = 0; s < a.anneal_sweeps; ++s) {
+            const float inv_t = a.inv_temp[s];
+            // seed + GOLD * (ctr + 1), ctr = cand << 32 | s << 12 | v: the part without v (v < 2^12 only adds)
+            const u64 base = a.seed + GMC_GOLD * ((((u64)(unsigned)cand << 32) | ((u64)(unsigned)s << 12)) + 1ULL);
+            for (int k = 0; k < classes; ++k) {
+                const int hi = a.cptr[k0 + k + 1];
+                for (int i = a.cptr[k0 + k] + threadIdx.x; i < hi; i += blockDim.x) {
+                    const int l = g.node(i);
+                    if (l < K || l >= n) continue;   // not a movable row of this graph: never touch LDS for it
+                    const Sums<K> w = gmc::class_sums_k<K>(g.rp, g.col, g.vals, sa, l);
+                    const int c = sa[l];
+                    // a byte of no class equals no k: own sum +inf, the smallest of all K sums as the target, taken
+                    // unconditionally (delta = 0 - inf); no branch, so the sums stay in registers
+                    const bool has_class = (unsigned)c < (unsigned)K;
+                    const float wc = gmc::own_sum_or_inf<K>(w, c);
+                    float wk;
+                    const int kk = gmc::smallest_other<K>(w, c, wk);
+                    wk = has_class ? wk : 0.f;
+                    const float delta = wk - wc;
+                    const u64 h = mix64(base + GMC_GOLD * (u64)(unsigned)l);
+                    if (delta < 0.f || delta * inv_t <= lv[h >> 54]) sa[l] = (unsigned char)kk;
+                }
+                __syncthreads();   // the next class, or the recount, reads what this one wrote
+            }
+            const float cut = gmc::block_cut_csr(g.rp, g.col, g.vals, sa, n, red);
+            if (threadIdx.x == 0) {
+                const int better = cut > best_cut;
+                if (better) best_cut = cut;
+                *flag = better;
+            }
+            __syncthreads();   // (also: thread 0 has read red before the next recount writes it)
+            if (*flag) {       // workgroup-uniform
+                snap = s + 1;
+                for (int l = threadIdx.x; l < n; l += blockDim.x) sb[l] = sa[l];
+                __syncthreads();   // the next sweep moves nodes other threads are copying
+            }
+        }
+        for (int l = threadIdx.x; l < n; l += blockDim.x) sa[l] = sb[l];
+        __syncthreads();
+    }
+    int s = 0;
+    while (s < a.max_descent_sweeps) {
+        ++s;
+        int moved = 0;
+        for (int k = 0; k < classes; ++k) {
+            const int hi = a.cptr[k0 + k + 1];
+            for (int i = a.cptr[k0 + k] + threadIdx.x; i < hi; i += blockDim.x) {
+                const int l = g.node(i);
+                if (l < K || l >= n) continue;
+                if (descent_visit<K>(g, sa, l)) moved = 1;
+            }
+            if (k + 1 < classes) __syncthreads();
+        }
+        if (!__syncthreads_or(moved)) break;
+    }
+    if (threadIdx.x == 0) {
+        if (a.snap_sweep) a.snap_sweep[(long)gi * a.cands + cand] = snap;
+        if (a.sweeps) a.sweeps[(long)gi * a.cands + cand] = s;
+    }
+}
+
+template <int K>
+__global__ __launch_bounds__(256) void anneal_k_kernel(AnnealArgs a) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
+    __shared__ float red[4];
+    __shared__ int flag;
+    const int cand = blockIdx.x, gi = blockIdx.y;
+    const int r0 = a.b.goff[gi];
+    const int n = a.b.goff[gi + 1] - r0;
+    if (n > a.b.n_max || n < K) return;   // (the LDS is sized by n_max; a graph without its K terminals is skipped)
+    float *lv = reinterpret_cast<float *>(lds);
+    unsigned char *sa = lds + 4 * GMC_ANNEAL_LEVELS;
+    unsigned char *sb = sa + a.n_pad;
+    signed char *as = a.assign + (long)cand * a.b.R + r0;
+    for (int l = threadIdx.x; l < n; l += blockDim.x) sa[l] = sb[l] = (unsigned char)as[l];
+    if (a.anneal_sweeps > 0)
+        for (int i = threadIdx.x; i < GMC_ANNEAL_LEVELS; i += blockDim.x) lv[i] = a.levels[i];
+    const int k0 = a.cgoff[gi];
+    const int classes = a.cgoff[gi + 1] - k0 - 1;
+    const int e0 = a.b.rowptr[r0];
+    const int nnz = a.b.rowptr[r0 + n] - e0;
+    const int i0 = a.cptr[k0];
+    const int movable = a.cptr[k0 + classes] - i0;
+    // the copy is sized by n_max and nnz_max: a graph that contradicts them takes the global path
+    if (a.staged && nnz >= 0 && nnz <= a.b.nnz_max && movable >= 0 && movable <= a.n_pad) {
+        int *starts = reinterpret_cast<int *>(lds + a.off_starts);
+        float *vals = a.b.vals ? reinterpret_cast<float *>(lds + a.off_vals) : nullptr;
+        unsigned short *ord = reinterpret_cast<unsigned short *>(lds + a.off_order);
+        unsigned short *ids = reinterpret_cast<unsigned short *>(lds + a.off_ids);
+        for (int l = threadIdx.x; l <= n; l += blockDim.x) starts[l] = a.b.rowptr[r0 + l] - e0;
+        for (int e = threadIdx.x; e < nnz; e += blockDim.x) {
+            ids[e] = (unsigned short)a.b.lcol[e0 + e];
+            if (vals) vals[e] = a.b.vals[e0 + e];
+        }
+        for (int i = threadIdx.x; i < movable; i += blockDim.x) {
+            const int l = a.order[i0 + i] - r0;
+            ord[i] = (unsigned)l < (unsigned)n ? (unsigned short)l : (unsigned short)0xffff;
+        }
+        __syncthreads();
+        const LdsCsr g{starts, ids, vals, ord, i0};
+        anneal_body_k<K>(a, g, sa, sb, lv, n, k0, classes, red, &flag);
+    } else {
+        __syncthreads();
+        const GlobalCsr g{a.b.rowptr + r0, a.b.lcol, a.b.vals, a.order, r0};
+        anneal_body_k<K>(a, g, sa, sb, lv, n, k0, classes, red, &flag);
+    }
+    for (int l = threadIdx.x; l < n; l += blockDim.x) as[l] = (signed char)sa[l];
+    const float cut = gmc::block_cut(a.b, sa, r0, n, red);   // scored as gmc_refine_local_f32 scores
+    if (threadIdx.x == 0) a.cut_all[(long)gi * a.cands + cand] = cut;
+}
+
+struct KPickArgs {
+    gmc::PickArgs p;
+    int K;
+};
+__global__ __launch_bounds__(256) void anneal_k_pick_kernel(KPickArgs a) {
+    const int g = blockIdx.x;
+    const int n = a.p.b.goff[g + 1] - a.p.b.goff[g];
+    if (n > a.p.b.n_max || n < a.K) return;   // workgroup-uniform: the graphs the search skipped
+    gmc::pick_best(a.p);
+}
+
+template <int K>
+int anneal_launch(const AnnealArgs &a, int lds_bytes, hipStream_t st) {
+    GmcProbeScope probe(GMC_K_ANNEAL, st);
+    hipLaunchKernelGGL((anneal_k_kernel<K>), dim3(a.cands, a.b.B), dim3(256), (size_t)lds_bytes, st, a);
+    GMC_LAUNCH_CHECK();
+    return GMC_OK;
+}
+
+}  // namespace
+
+extern "C" int gmc_kway_decode_sample_seeded_f32(const gmc_batch *batch, const float *P, int32_t K,
+                                                 const uint64_t *gkey, int32_t iters, int8_t *assign_all,
+                                                 float *cut_all, int32_t *best_assign, float *best_cut,
+                                                 int32_t *best_iter, gmc_stream_t stream) {
+    if (!batch || !P || !gkey || !cut_all || !best_assign || !best_cut || !best_iter) return GMC_ERR_NULL;
+    if (batch->abi != GMC_VERSION) return GMC_ERR_ABI;
+    if (!batch->goff || !batch->rowptr || !batch->lcol) return GMC_ERR_NULL;
+    if (K < 2 || K > GMC_KWAY_MAX_CLASSES) return GMC_ERR_CLASSES;
+    if (iters < 1 || batch->B < 0) return GMC_ERR_SHAPE;
+    if (batch->B > 0 && (batch->n_max < K || batch->n_max > 65535)) return GMC_ERR_GRAPH_SIZE;
+    if (batch->B == 0) return GMC_OK;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const KSeededArgs a{*batch, P, reinterpret_cast<const u64 *>(gkey), iters,
+                        reinterpret_cast<signed char *>(assign_all), cut_all, best_assign, best_cut, best_iter};
+    switch (K) {
+        case 2: return sample_launch<2>(a, st);
+        case 3: return sample_launch<3>(a, st);
+        case 4: return sample_launch<4>(a, st);
+        case 5: return sample_launch<5>(a, st);
+        case 6: return sample_launch<6>(a, st);
+        case 7: return sample_launch<7>(a, st);
+        default: return sample_launch<8>(a, st);
+    }
+}
+
+extern "C" int gmc_kway_refine_anneal_f32(const gmc_batch *batch, int32_t K, const int32_t *order,
+                                          const int32_t *cgoff, const int32_t *cptr, int32_t cands, int8_t *assign,
+                                          const float *inv_temp, int32_t anneal_sweeps, const float *levels,
+                                          uint64_t seed, int32_t max_descent_sweeps, float *cut_all,
+                                          int32_t *best_assign, float *best_cut, int32_t *best_idx,
+                                          int32_t *snap_sweep, int32_t *sweeps, gmc_stream_t stream) {
+    if (!batch || !order || !cgoff || !cptr || !assign || !cut_all || !best_assign || !best_cut || !best_idx)
+        return GMC_ERR_NULL;
+    if (batch->abi != GMC_VERSION) return GMC_ERR_ABI;
+    if (!batch->goff || !batch->rowptr || !batch->lcol) return GMC_ERR_NULL;
+    if (K < 2 || K > GMC_KWAY_MAX_CLASSES) return GMC_ERR_CLASSES;
+    if (cands < 1 || anneal_sweeps < 0 || anneal_sweeps >= (1 << 20) || max_descent_sweeps < 0 || batch->B < 0)
+        return GMC_ERR_SHAPE;
+    if (anneal_sweeps > 0 && (!inv_temp || !levels)) return GMC_ERR_NULL;
+    if (batch->B > 0 && (batch->n_max < K || batch->n_max > GMC_MAX_GRAPH_NODES)) return GMC_ERR_GRAPH_SIZE;
+    if (batch->B == 0) return GMC_OK;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const AnnealLayout L = gmc::anneal_layout(batch);
+    const AnnealArgs a{*batch, order, cgoff, cptr, cands, anneal_sweeps, max_descent_sweeps, inv_temp, levels, seed,
+                       reinterpret_cast<signed char *>(assign), cut_all, snap_sweep, sweeps,
+                       L.staged, L.n_pad, L.off_starts, L.off_vals, L.off_order, L.off_ids};
+    int rc;
+    switch (K) {
+        case 2: rc = anneal_launch<2>(a, L.bytes, st); break;
+        case 3: rc = anneal_launch<3>(a, L.bytes, st); break;
+        case 4: rc = anneal_launch<4>(a, L.bytes, st); break;
+        case 5: rc = anneal_launch<5>(a, L.bytes, st); break;
+        case 6: rc = anneal_launch<6>(a, L.bytes, st); break;
+        case 7: rc = anneal_launch<7>(a, L.bytes, st); break;
+        default: rc = anneal_launch<8>(a, L.bytes, st); break;
+    }
+    if (rc != GMC_OK) return rc;
+    const KPickArgs p{{*batch, cands, reinterpret_cast<const signed char *>(assign), cut_all, best_assign, best_cut,
+                       best_idx}, K};
+    hipLaunchKernelGGL(anneal_k_pick_kernel, dim3(batch->B), dim3(256), 0, st, p);
+    GMC_LAUNCH_CHECK();
+    return GMC_OK;
+}

@@ -1,5 +1,6 @@
-// The node visit shared by the local search (refine.hip) and the annealing (anneal.hip): the class sums of a node and
-// the local search's move rule, one definition so that the two kernels cannot drift apart.
+// The node visit shared by the local search (refine.hip), the annealing (anneal.hip), the rounding's descent (round.hip)
+// and the K-class search (kway_search.hip): the class sums of a node and the local search's move rule, one definition so
+// that the kernels cannot drift apart.
 #pragma once
 #include "gmc_common.h"
 
@@ -33,6 +34,66 @@ __device__ __forceinline__ bool local_move(float w0, float w1, float w2, int c, 
     if (w1 < wk) { kk = 1; wk = w1; }
     if (w2 < wk) { kk = 2; wk = w2; }
     return wk < wc;
+}
+
+// K floats in registers: every index below is a constant once the loops are unrolled (an index that is not would put
+// the array into scratch)
+template <int K>
+struct Sums {
+    float m[K];
+};
+
+// class_sums at K classes: W_k = sum of the weights of the edges of local row l to neighbours of class k, fp32, in the
+// CSR order of the row, self-loops skipped, a class byte outside 0..K-1 adding to none (K = 3: class_sums, the same
+// operations in the same order)
+template <int K, class RP, class COL>
+__device__ __forceinline__ Sums<K> class_sums_k(const RP *rp, const COL *col, const float *vals,
+                                                const unsigned char *cls, int l) {
+    Sums<K> s;
+#pragma unroll
+    for (int k = 0; k < K; ++k) s.m[k] = 0.f;
+    const int e1 = rp[l + 1];
+    for (int e = rp[l]; e < e1; ++e) {
+        const int u = col[e];
+        if (u == l) continue;
+        const float w = vals ? vals[e] : 1.0f;
+        const int cu = cls[u];
+#pragma unroll
+        for (int k = 0; k < K; ++k) s.m[k] += cu == k ? w : 0.f;
+    }
+    return s;
+}
+
+// the class of the smallest sum, the lowest index on ties; wk = that sum
+template <int K>
+__device__ __forceinline__ int smallest(const Sums<K> &s, float &wk) {
+    int kk = 0;
+    wk = s.m[0];
+#pragma unroll
+    for (int k = 1; k < K; ++k)
+        if (s.m[k] < wk) { kk = k; wk = s.m[k]; }
+    return kk;
+}
+
+// the sum of class byte c, +inf for a byte outside 0..K-1
+template <int K>
+__device__ __forceinline__ float own_sum_or_inf(const Sums<K> &s, int c) {
+    float wc = __builtin_inff();
+#pragma unroll
+    for (int j = 0; j < K; ++j) wc = c == j ? s.m[j] : wc;
+    return wc;
+}
+
+// the class of the smallest sum among the classes other than c, the lowest index on ties; wk = that sum (a byte c
+// outside 0..K-1 excludes none: smallest)
+template <int K>
+__device__ __forceinline__ int smallest_other(const Sums<K> &s, int c, float &wk) {
+    int kk = c == 0 ? 1 : 0;
+    wk = c == 0 ? s.m[1] : s.m[0];
+#pragma unroll
+    for (int k = 1; k < K; ++k)
+        if (k != c && s.m[k] < wk) { kk = k; wk = s.m[k]; }
+    return kk;
 }
 
 }  // namespace gmc

@@ -16,8 +16,13 @@
 // dynamic-LDS limit then), 132 KiB at n_max = GMC_MAX_GRAPH_NODES.
 #include "gmc_common.h"
 #include "cut_body.h"
+#include "move_body.h"
 
 namespace {
+
+using gmc::Sums;
+using gmc::class_sums_k;   // the sums over the class bytes and the pick of the smallest: move_body.h
+using gmc::smallest;
 
 struct RoundArgs {
     gmc_batch b;
@@ -30,13 +35,6 @@ struct RoundArgs {
     float *cut;              // [B]
     float *expected;         // [B] or NULL
     int *sweeps;             // [B] or NULL
-};
-
-// K floats in registers: every index below is a constant once the loops are unrolled (an index that is not would put
-// the array into scratch)
-template <int K>
-struct Sums {
-    float m[K];
 };
 
 // M_k = sum over the edges of local row l, CSR order, self-loops skipped, of w_e * q_u[k], from +0.  Product and sum
@@ -60,37 +58,6 @@ __device__ __forceinline__ Sums<K> state_sums(const int *rp, const int *col, con
         }
     }
     return s;
-}
-
-// the same sums over a one-hot state, read from the class bytes: W_k = sum of the weights of the edges to neighbours of
-// class k (K = 3: move_body.h's class_sums, the same operations in the same order)
-template <int K>
-__device__ __forceinline__ Sums<K> class_sums_k(const int *rp, const int *col, const float *vals,
-                                                const unsigned char *cls, int l) {
-    Sums<K> s;
-#pragma unroll
-    for (int k = 0; k < K; ++k) s.m[k] = 0.f;
-    const int e1 = rp[l + 1];
-    for (int e = rp[l]; e < e1; ++e) {
-        const int u = col[e];
-        if (u == l) continue;
-        const float w = vals ? vals[e] : 1.0f;
-        const int cu = cls[u];
-#pragma unroll
-        for (int k = 0; k < K; ++k) s.m[k] += cu == k ? w : 0.f;
-    }
-    return s;
-}
-
-// the class of the smallest sum, the lowest index on ties; wk = that sum
-template <int K>
-__device__ __forceinline__ int smallest(const Sums<K> &s, float &wk) {
-    int kk = 0;
-    wk = s.m[0];
-#pragma unroll
-    for (int k = 1; k < K; ++k)
-        if (s.m[k] < wk) { kk = k; wk = s.m[k]; }
-    return kk;
 }
 
 // the node's share of the expected cut: sum over its edges (self-loops skipped) of w_e * (1 - q_u . q_l)

@@ -184,9 +184,11 @@ enum {
     GMC_K_FINISH = 14,     /* fold of the gradient partials (+ fused Adam) over the flat buffer */
     GMC_K_REFINE = 15,     /* local search over decoded candidates + cut count (gmc_refine_local_f32); also the
                             * rounding by conditional expectations + descent (gmc_round_conditional_f32) */
-    GMC_K_ANNEAL = 16,     /* annealing + descent over decoded candidates + cut count (gmc_refine_anneal_f32) */
+    GMC_K_ANNEAL = 16,     /* annealing + descent over decoded candidates + cut count (gmc_refine_anneal_f32,
+                            * gmc_kway_refine_anneal_f32) */
     GMC_K_GEMM = 17,       /* dense fp32 GEMM on the matrix cores (gmc_gemm_f32; the dense-feature path) */
-    GMC_K_SAMPLE = 18,     /* seeded post-processing sampler + cut count (gmc_decode_sample_seeded_f32) */
+    GMC_K_SAMPLE = 18,     /* seeded post-processing sampler + cut count (gmc_decode_sample_seeded_f32,
+                            * gmc_kway_decode_sample_seeded_f32) */
     GMC_K_COUNT = 19
 };
 
@@ -604,7 +606,8 @@ int gmc_refine_anneal_f32(const gmc_batch *batch, const int32_t *order, const in
 /* DIAGNOSTIC host query (no HIP call; reads n_max, nnz_max and whether vals is NULL) for tests and timing scripts;
  * results never depend on its answer: 1 when gmc_refine_anneal_f32 keeps a copy of each graph's CSR in LDS for this
  * batch, 0 when the graphs are too large for that and it reads the batch's arrays in global memory (same results, bit
- * for bit); < 0 on a bad argument. */
+ * for bit); < 0 on a bad argument.  The layout does not depend on the class count, so the answer holds for
+ * gmc_kway_refine_anneal_f32 on the same batch as well. */
 int gmc_refine_anneal_staged(const gmc_batch *batch);
 
 /* ---- rounding by conditional expectations (extension: no counterpart in the reference) ---------------------------
@@ -659,6 +662,74 @@ int gmc_round_conditional_f32(const gmc_batch *batch, const float *P /*[R,K]*/, 
                               const int32_t *order, const int32_t *cgoff, const int32_t *cptr,
                               int32_t max_descent_sweeps, int8_t *assign /*[R]*/, float *cut /*[B]*/,
                               float *expected /*[B] or NULL*/, int32_t *sweeps /*[B] or NULL*/, gmc_stream_t stream);
+
+/* ---- the seeded sampler and the annealing at K classes (extension; K = 2 .. GMC_KWAY_MAX_CLASSES) ------------------
+ *
+ * gmc_decode_sample_seeded_f32, gmc_refine_local_f32 and gmc_refine_anneal_f32 are 3-class.  The two entry points below
+ * are the same decoders for the models of gmc_kway_forward: nodes 0..K-1 of every graph are the terminals of classes
+ * 0..K-1, P has K columns, class bytes are 0..K-1.  At K = 3 every output of either equals, byte for byte, the output
+ * of its 3-class counterpart.
+ *
+ * The K-class draw rule.  All arithmetic is modulo 2^64; GOLD, mix64 and a graph's key are those of
+ * gmc_decode_sample_seeded_f32.
+ *  - The uniform for iteration it (0-based) and local node l is h = mix64(key + GOLD * (((u64)it << 32 | l) + 1)), then
+ *    u = (double)(h >> 11) * 2^-53, in [0, 1) and exact.
+ *  - Nodes 0..K-1 are the terminals of classes 0..K-1, whatever their rows of P hold.
+ *  - Node l >= K, with p its row of P: c_0 = (double)p[0], c_j = c_{j-1} + (double)p[j] (a running sum in double).
+ *    The node takes the first class j in 0..K-2 with u < c_j, else class K-1.  Class K-1 is the fallback: no compare
+ *    against c_{K-1} is made, so an all-zero row and a NaN row give K-1.
+ * As at three classes a graph's samples depend on its key alone - not on the batch, its place in it, or iters. */
+
+/* The K-class sampler for every graph of the batch: P [R,K] device floats, gkey [B] device uint64.  Outputs (device) as
+ * gmc_decode_sample_seeded_f32's: cut_all [B][iters], best_assign [R] int32 (the strictly best sample, the first on
+ * ties, regenerated from the hash), best_cut [B], best_iter [B]; assign_all [iters][R] int8 may be NULL, and every other
+ * output is then equal.  A sample's cut has the bits gmc_refine_local_f32 / gmc_kway_refine_anneal_f32 report for the
+ * same assignment (the same code).  Argument checks, before any HIP call, in the order of the other decoders: a NULL
+ * pointer (assign_all aside) GMC_ERR_NULL, batch->abi GMC_ERR_ABI, a NULL goff / rowptr / lcol GMC_ERR_NULL, K outside
+ * 2..GMC_KWAY_MAX_CLASSES GMC_ERR_CLASSES, iters < 1 or B < 0 GMC_ERR_SHAPE, n_max < K or n_max > 65535
+ * GMC_ERR_GRAPH_SIZE; B == 0 returns GMC_OK without a launch.  A graph with fewer than K or more than n_max nodes
+ * inside a batch is skipped (nothing of it is written), as gmc_round_conditional_f32 skips it.  The call allocates
+ * nothing and does not synchronise: two launches on the caller's stream, no atomics, bitwise reproducible. */
+int gmc_kway_decode_sample_seeded_f32(const gmc_batch *batch, const float *P /*[R,K]*/, int32_t K,
+                                      const uint64_t *gkey, int32_t iters, int8_t *assign_all /*or NULL*/,
+                                      float *cut_all, int32_t *best_assign, float *best_cut, int32_t *best_iter,
+                                      gmc_stream_t stream);
+
+/* The K-class annealing: steps 1-4 of gmc_refine_anneal_f32 per (candidate `cand`, graph), with the colouring and
+ * order / cgoff / cptr of gmc_round_order_host for the same K, and these generalisations:
+ *  - nodes 0..K-1 never move, whatever class they hold; the movable nodes are K..n-1;
+ *  - a node v computes W_0..W_{K-1}: fp32 sums in the CSR order of its row of the weights of its edges to neighbours
+ *    of class 0..K-1, self-loops skipped, a class byte outside 0..K-1 counting for none;
+ *  - annealing sweep: with c = class(v), the target k is the class of the smallest W among the K-1 classes other than c
+ *    (the lowest index on ties), delta = W[k] - W[c] in fp32, and
+ *        v moves to k  iff  delta < 0  or  delta * inv_temp[s] <= levels[h >> 54]
+ *    with h, ctr = (uint64)cand << 32 | (uint64)s << 12 | v, the level table and the snapshot rule exactly those of
+ *    gmc_refine_anneal_f32.  A movable node whose byte is outside 0..K-1 takes the class of the smallest of all K sums
+ *    (lowest index on ties) unconditionally;
+ *  - descent: the local search's rule at K classes, the one gmc_round_conditional_f32 runs in its step 4: v moves to
+ *    the class kk of the smallest of all K sums (lowest index on ties) iff W[kk] < W[c] (a byte outside 0..K-1: always);
+ *    sweeps until one moves nothing or max_descent_sweeps have run;
+ *  - score and pick: as gmc_refine_local_f32 scores and picks (fp32, the same code).
+ * anneal_sweeps = 0 is the K-class local search over `cands` candidates with max_sweeps = max_descent_sweeps; on the
+ * one candidate gmc_round_conditional_f32(max_descent_sweeps = 0) writes it gives what that call gives with the
+ * descent, assignment and sweep count.  At K = 3 every output equals gmc_refine_anneal_f32's, and with
+ * anneal_sweeps = 0 gmc_refine_local_f32's.  What gmc_refine_anneal_f32 states "by construction" holds with 0..K-1 in
+ * the place of 0..2.
+ * Arguments and outputs as gmc_refine_anneal_f32's: assign [cands][R] int8 (in/out), inv_temp [anneal_sweeps] and
+ * levels [GMC_ANNEAL_LEVELS] (either may be NULL when anneal_sweeps == 0), cut_all [B][cands], best_assign [R] int32,
+ * best_cut [B], best_idx [B], optional snap_sweep / sweeps [B][cands].  Argument checks, before any HIP call: a NULL
+ * required pointer GMC_ERR_NULL, batch->abi GMC_ERR_ABI, a NULL goff / rowptr / lcol GMC_ERR_NULL, K outside
+ * 2..GMC_KWAY_MAX_CLASSES GMC_ERR_CLASSES, cands < 1, a negative sweep count, anneal_sweeps >= 2^20 or B < 0
+ * GMC_ERR_SHAPE, anneal_sweeps > 0 with a NULL inv_temp or levels GMC_ERR_NULL, n_max outside K..GMC_MAX_GRAPH_NODES
+ * GMC_ERR_GRAPH_SIZE; B == 0 returns GMC_OK without a launch.  A graph with fewer than K or more than n_max nodes
+ * inside a batch is skipped.  The LDS of a launch is gmc_refine_anneal_f32's, which does not depend on K
+ * (gmc_refine_anneal_staged answers for this call too).  The call allocates nothing and does not synchronise: two
+ * launches on the caller's stream, no atomics, bitwise reproducible. */
+int gmc_kway_refine_anneal_f32(const gmc_batch *batch, int32_t K, const int32_t *order, const int32_t *cgoff,
+                               const int32_t *cptr, int32_t cands, int8_t *assign, const float *inv_temp,
+                               int32_t anneal_sweeps, const float *levels, uint64_t seed, int32_t max_descent_sweeps,
+                               float *cut_all, int32_t *best_assign, float *best_cut, int32_t *best_idx,
+                               int32_t *snap_sweep, int32_t *sweeps, gmc_stream_t stream);
 
 #ifdef __cplusplus
 }
