@@ -17,6 +17,8 @@ switches to batched steps (one Adam step per batch of graphs, summed loss), and 
 RCCL all-reduce of the flat gradient per step.  ``loss="expected_cut"`` (or GCN_MAXCUT_LOSS=expected_cut) trains on
 the relaxed loss - ``compute_loss`` of ``override_fixed_nodes(P)`` without the one-hot step, the expected cut of
 independent rounding - instead of the reference's hard one; :func:`cut_loss` is either loss as a differentiable op.
+``layer1="attention"`` (or GCN_MAXCUT_LAYER1=attention) builds a :class:`GATSoftmax`: the first layer is single-head graph
+attention on the hand-written kernels of ``csrc/attention.hip`` instead of ``GraphConv(norm='both')``.
 """
 from __future__ import annotations
 
@@ -183,6 +185,72 @@ class GCNSoftmax(nn.Module):
             if differentiable:
                 return _GCNForward.apply(self, _dense_batch_of(g, eng.device), inputs, *params)
             return _dense_forward(self, g, inputs)
+
+
+class GATConv(nn.Module):
+    """Parameter container of the attention first layer: ``weight`` [in,out] and ``bias`` as :class:`GraphConv`, plus the
+    two attention vectors ``attn_src`` / ``attn_dst`` [out], each initialised xavier-uniform as an [out, 1] matrix from
+    torch's generator.  The arithmetic lives in the HIP library (include/gcnmaxcut.h, gmc_att_*)."""
+
+    def __init__(self, in_feats: int, out_feats: int):
+        super().__init__()
+        self._in_feats, self._out_feats = in_feats, out_feats
+        self.weight = nn.Parameter(torch.empty(in_feats, out_feats))
+        self.bias = nn.Parameter(torch.empty(out_feats))
+        self.attn_src = nn.Parameter(torch.empty(out_feats))
+        self.attn_dst = nn.Parameter(torch.empty(out_feats))
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        nn.init.xavier_uniform_(self.weight)
+        nn.init.zeros_(self.bias)
+        for a in (self.attn_src, self.attn_dst):
+            nn.init.xavier_uniform_(a.data.view(-1, 1))
+
+    def extra_repr(self):
+        return f"in={self._in_feats}, out={self._out_feats}, heads=1, self_loops=True, negative_slope={hip.ATTENTION_SLOPE}"
+
+
+class GATSoftmax(GCNSoftmax):
+    """:class:`GCNSoftmax` whose first layer is single-head graph attention on the graph with self-loops added, followed
+    by relu (``layer1="attention"``; include/gcnmaxcut.h states the model).  Same constructor; three classes.  It trains
+    through train_model / train_single_epoch (both losses) and answers ``net(g, a_pad)`` under ``torch.no_grad()``;
+    dropout, dense features and autograd through ``net(g, X)`` are implemented for ``layer1="graphconv"`` only."""
+
+    def __init__(self, in_feats: int, hidden_size: int, num_classes: int, dropout: float, device):
+        super().__init__(in_feats, hidden_size, num_classes, dropout, device)
+        self.conv1 = GATConv(in_feats, hidden_size).to(device)
+
+    def engine(self) -> FusedEngine:
+        if self._engine is None:
+            w1, w2 = self.conv1.weight, self.conv2.weight
+            self._engine = FusedEngine(w1.shape[0], w1.shape[1], w2.shape[1], hip.require_gpu(), attention=True)
+        if not self._engine.owns(self):
+            self._engine.adopt(self)
+        return self._engine
+
+    def forward(self, g, inputs):
+        eng = self.engine()
+        try:
+            batch = graph_batch_of(g, inputs, eng.device)
+        except NotImplementedError:
+            raise NotImplementedError("dense node features are implemented for layer1 = 'graphconv' only (this model has "
+                                      "layer1 = 'attention': its features are the padded adjacency)") from None
+        if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
+            raise NotImplementedError(
+                "autograd through net(g, X) is implemented for layer1 = 'graphconv' only (this model has layer1 = "
+                "'attention'): train it with train_model / train_single_epoch, and call the model under torch.no_grad() "
+                "for its probabilities")
+        if self.training and self.dropout_frac > 0.0:
+            raise NotImplementedError("dropout is implemented for layer1 = 'graphconv' only (this model has layer1 = "
+                                      "'attention'): use dropout = 0")
+        P, _, _ = eng.forward(batch)
+        return P
+
+
+def layer1_of(net) -> str:
+    """``"attention"`` for a :class:`GATSoftmax`, else ``"graphconv"``."""
+    return "attention" if isinstance(net, GATSoftmax) else "graphconv"
 
 
 def _cached_batch(g: GraphHandle, key: tuple, vals, device) -> GraphBatch:
@@ -356,16 +424,31 @@ def evaluate_optimal_partitioning(net, dgl_graph, inputs, adjacency_matrix, term
 
 
 # --------------------------------------------------------------------------- training
-def setup_model_and_optimizer(config: TrainingConfig):
+def setup_model_and_optimizer(config: TrainingConfig, *, layer1: Optional[str] = None):
     """(model, embedding, optimizer) - TrainingNeural.py:311-339.  The embedding is never
     used by the forward (Q1) but is part of the optimizer, the checkpoint and the return
-    value, as in the reference."""
-    net = GCNSoftmax(config.dim_embedding, config.hidden_dim, config.number_classes,
-                     config.dropout, TORCH_DEVICE)
+    value, as in the reference.  ``layer1``: ``"graphconv"`` (the reference's model), ``"attention"`` (a
+    :class:`GATSoftmax`) or None = the environment's GCN_MAXCUT_LAYER1 (default graphconv)."""
+    model_class = GATSoftmax if hip.layer1_name(layer1) == "attention" else GCNSoftmax
+    if model_class is GATSoftmax and config.number_classes != 3:
+        raise ValueError(f"number_classes = {config.number_classes}: layer1 = 'attention' is implemented for the 3-class "
+                         "model only")
+    net = model_class(config.dim_embedding, config.hidden_dim, config.number_classes,
+                      config.dropout, TORCH_DEVICE)
     net = net.type(TORCH_DTYPE).to(TORCH_DEVICE)
     embed = nn.Embedding(config.n_nodes, config.dim_embedding).type(TORCH_DTYPE).to(TORCH_DEVICE)
     optimizer = torch.optim.Adam(chain(net.parameters(), embed.parameters()), lr=config.learning_rate)
     return net, embed, optimizer
+
+
+def _setup(config: TrainingConfig, layer1: str):
+    """:func:`setup_model_and_optimizer` for a RESOLVED ``layer1`` (a name, never None).  The keyword is left out only when
+    it says what the function would choose by itself - the environment's value included - so that stand-ins of the function
+    without the keyword keep working and an explicit ``"graphconv"``, or a checkpoint's own keys, beat
+    GCN_MAXCUT_LAYER1=attention."""
+    if layer1 == hip.layer1_name(None):
+        return setup_model_and_optimizer(config)
+    return setup_model_and_optimizer(config, layer1=layer1)
 
 
 def _trainer_for(net, optimizer, config, graphs_per_step: Optional[int] = None,
@@ -382,11 +465,17 @@ def _trainer_for(net, optimizer, config, graphs_per_step: Optional[int] = None,
 
 def train_single_epoch(dataset: Dict, net, optimizer, embed, config: TrainingConfig,
                        dataset_files: Optional[List[str]] = None, *,
-                       graphs_per_step: Optional[int] = None, loss: Optional[str] = None) -> float:
+                       graphs_per_step: Optional[int] = None, loss: Optional[str] = None,
+                       layer1: Optional[str] = None) -> float:
     """One epoch, cumulative loss (TrainingNeural.py:341-390).  The device batches planned for ``dataset`` are
     kept from epoch to epoch while it looks unchanged (:meth:`FusedTrainer.prepare` says how that is decided);
     after editing a large dataset dict in place call ``net._fused_trainer.invalidate()``.  ``loss``: ``"cut"`` (the
-    reference's), ``"expected_cut"`` (the relaxed loss) or None = the environment's GCN_MAXCUT_LOSS (default cut)."""
+    reference's), ``"expected_cut"`` (the relaxed loss) or None = the environment's GCN_MAXCUT_LOSS (default cut).
+    ``layer1``: when given, the first layer ``net`` must have (the model itself was built by
+    :func:`setup_model_and_optimizer`): another one is a ValueError."""
+    if layer1 is not None and hip.layer1_name(layer1) != layer1_of(net):
+        raise ValueError(f"layer1 = {layer1!r}, but the model was built with layer1 = {layer1_of(net)!r} "
+                         "(setup_model_and_optimizer(config, layer1=...))")
     net.train()
     trainer = _trainer_for(net, optimizer, config, graphs_per_step, loss)
     if dataset_files is None:
@@ -413,17 +502,18 @@ def _checkpoint(net, optimizer, embed, epoch, loss_history, config) -> Dict:
 
 
 def train_model(dataset: Dict, config: TrainingConfig, dataset_files: Optional[List[str]] = None, *,
-                graphs_per_step: Optional[int] = None, loss: Optional[str] = None) -> Tuple:
+                graphs_per_step: Optional[int] = None, loss: Optional[str] = None, layer1: Optional[str] = None) -> Tuple:
     """Main training function (TrainingNeural.py:392-484):
     returns ``(model, best_loss, final_epoch, embedding_weights, loss_history)``.  ``loss``: as for
-    :func:`train_single_epoch`."""
+    :func:`train_single_epoch`; ``layer1``: as for :func:`setup_model_and_optimizer`."""
     loss = hip.loss_name(loss)
+    layer1 = hip.layer1_name(layer1)
     say = print if _rank0() else (lambda *a, **k: None)
     say(f"Starting training with {config.number_epochs} epochs")
     say(f"Model: {config.n_nodes} nodes, {config.number_classes} classes")
     say(f"Device: {TORCH_DEVICE}")
 
-    net, embed, optimizer = setup_model_and_optimizer(config)
+    net, embed, optimizer = _setup(config, layer1)
     best_loss, best_model_state = float('inf'), None
     loss_history: List[float] = []
     patience_counter, prev_loss = 0, float('inf')
@@ -473,10 +563,11 @@ def train_from_pickle(dataset_filename: str, model_name: str, n_nodes: int = 100
     """Train from a dataset pickle (TrainingNeural.py:486-513)."""
     graphs_per_step = kwargs.pop('graphs_per_step', None)
     loss = kwargs.pop('loss', None)
+    layer1 = kwargs.pop('layer1', None)
     config = TrainingConfig(**{'n_nodes': n_nodes, 'save_directory': f'{model_name}.pth', **kwargs})
     print(f"Loading dataset from {dataset_filename}")
     dataset = open_file(dataset_filename)
-    return train_model(dataset, config, graphs_per_step=graphs_per_step, loss=loss)
+    return train_model(dataset, config, graphs_per_step=graphs_per_step, loss=loss, layer1=layer1)
 
 
 def train_multi_class(dataset_filename: str, model_name: str, num_classes: int = 3, **kwargs) -> Tuple:
@@ -505,8 +596,10 @@ def evaluate_model(model, dataset: Dict, config: TrainingConfig, *, loss: Option
     return {'average_loss': total / len(items), 'total_loss': total, 'num_samples': len(items)}
 
 
-def load_neural_model(model_path: str, config: TrainingConfig):
-    """(model, inputs, loaded_config) from a checkpoint (TrainingNeural.py:572-609)."""
+def load_neural_model(model_path: str, config: TrainingConfig, *, layer1: Optional[str] = None):
+    """(model, inputs, loaded_config) from a checkpoint (TrainingNeural.py:572-609).  A checkpoint with ``conv1.attn_src``
+    among its keys loads as a :class:`GATSoftmax` without being told, any other as a :class:`GCNSoftmax`; ``layer1``
+    (``"graphconv"`` / ``"attention"``) insists on one."""
     import torch.serialization
     try:
         torch.serialization.add_safe_globals([TrainingConfig])
@@ -517,7 +610,10 @@ def load_neural_model(model_path: str, config: TrainingConfig):
         except Exception:
             with torch.serialization.safe_globals([TrainingConfig]):
                 checkpoint = torch.load(model_path, map_location=TORCH_DEVICE)
-    net, embed, _ = setup_model_and_optimizer(config)
+    if layer1 is None:   # the checkpoint's own keys decide (not the environment: the weights are what they are)
+        layer1 = "attention" if "conv1.attn_src" in checkpoint['model'] else "graphconv"
+    layer1 = hip.layer1_name(layer1)
+    net, embed, _ = _setup(config, layer1)
     net.load_state_dict(checkpoint['model'])
     return net, checkpoint.get('inputs', embed.weight), checkpoint.get('config', config)
 

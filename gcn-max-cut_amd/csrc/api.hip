@@ -584,3 +584,157 @@ extern "C" int gmc_kway_train_fwd_bwd(const gmc_batch *batch, const gmc_model *m
     rc = kway_forward_body(c, C, P, S, loss);
     return rc ? rc : kway_backward_body(c, grad, tail ? loss : nullptr);
 }
+
+// ---- graph-attention first layer: the row-kernel sequence with the kernels of attention.hip -------------------------------
+namespace {
+
+struct AttWorkspace {
+    long ld;           // leading dimension of the [R,F] buffers (F rounded up to 32 floats)
+    float *T;          // [R,ld]  X @ W1 (kept for the backward)
+    float *H;          // [R,ld]  relu(attention aggregation + b1), later dT
+    float *Z0;         // [R,3]
+    float *s_src, *s_dst, *alpha_s;   // [R]
+    float *alpha_e;    // [nnz]
+    float *G;          // [R,ld]  gradient at layer 1's pre-activation
+    float *GY2;        // [R,4]
+    float *part;       // [tiles,F,4]
+    float *db2part;    // [B,3]
+    float *dw1part;    // [chunks,N,F]
+    float *ones, *dz_s, *ds_src, *ds_dst;   // [R]
+    float *dz_e;       // [nnz]
+    float *apart;      // [tiles,2,F]
+    size_t bytes;
+};
+
+// base == nullptr: sizes only
+AttWorkspace att_carve(const gmc_batch *b, const gmc_model *m, bool training, void *base) {
+    AttWorkspace w{};
+    size_t off = 0;
+    auto take = [&](size_t floats) {
+        float *p = base ? reinterpret_cast<float *>(static_cast<char *>(base) + off) : nullptr;
+        off += align_up(floats * sizeof(float));
+        return p;
+    };
+    const size_t R = (size_t)b->R, F = (size_t)m->F, nnz = (size_t)b->nnz;
+    w.ld = (long)((F + 31) / 32 * 32);
+    w.T = take(R * w.ld);
+    w.H = take(R * w.ld);
+    w.Z0 = take(R * 3);
+    w.s_src = take(R);
+    w.s_dst = take(R);
+    w.alpha_s = take(R);
+    w.alpha_e = take(nnz);
+    if (training) {
+        w.G = take(R * w.ld);
+        w.GY2 = take(R * 4);
+        w.part = take((size_t)gmc_hidden_tiles(b->R) * F * 4);
+        w.db2part = take((size_t)b->B * 3);
+        w.dw1part = take(gmc_dw1_scratch_floats(b, m->N, m->F, false));
+        w.ones = take(R);
+        w.dz_s = take(R);
+        w.ds_src = take(R);
+        w.ds_dst = take(R);
+        w.dz_e = take(nnz);
+        w.apart = take(gmc_att_avec_part_floats(b->R, m->F));
+    }
+    w.bytes = off;
+    return w;
+}
+
+struct AttCall {
+    const gmc_batch *b; const gmc_model *m;
+    const float *a_src, *a_dst; float slope;
+    AttWorkspace w{}; hipStream_t st = nullptr;
+};
+
+int att_open(AttCall &c, bool training, void *workspace, size_t workspace_bytes, gmc_stream_t stream, const float *P,
+             const float *grad) {
+    if (!c.b || !c.m || !c.a_src || !c.a_dst) return GMC_ERR_NULL;               // 1. (the vectors: as X of *_features)
+    if (int rc = check(c.b, c.m, false)) return rc;                              // 2. (K must be 3)
+    if (c.m->dropout_p > 0.f) return GMC_ERR_UNSUPPORTED;                        //    the attention sequence has no dropout
+    if (!(c.slope >= 0.f && c.slope <= 1.f)) return GMC_ERR_SHAPE;               // 3. the slope of the leaky relu
+    if (!workspace || !P || (training && !grad)) return GMC_ERR_NULL;            // 4. workspace and outputs
+    if (!gmc_aligned16(grad) || !gmc_aligned16(c.m->W1) || !gmc_aligned16(c.m->b1)) return GMC_ERR_ALIGN;   // 5.
+    c.w = att_carve(c.b, c.m, training, workspace);                              // 6. workspace size
+    if (c.w.bytes > workspace_bytes) return GMC_ERR_WORKSPACE;
+    c.st = static_cast<hipStream_t>(stream);
+    return GMC_OK;
+}
+
+// forward and head; GY2 / db2part of the workspace are filled when it was carved for training
+int att_forward_body(const AttCall &c, float C, float *P, int32_t *S, float *loss) {
+    const gmc_batch *b = c.b; const gmc_model *m = c.m; const AttWorkspace &w = c.w;
+    const int F = m->F;
+    // T = A_val @ W1[:n]: the row gather of W1 without a row scale
+    int rc = gmc_spmm_launch(b->rowptr, b->lcol, b->vals, nullptr, m->W1, F, nullptr, 0, w.T, w.ld, b->R, F, group_rows(b),
+                             nullptr, nullptr, GMC_K_GATHER_W1, c.st);
+    if (rc) return rc;
+    rc = gmc_att_scores_launch(w.T, w.ld, c.a_src, c.a_dst, w.s_src, w.s_dst, b->R, F, c.st);
+    if (rc) return rc;
+    rc = gmc_att_fwd_launch(b, w.T, w.ld, w.s_src, w.s_dst, c.slope, m->b1, w.alpha_e, w.alpha_s, w.H, F, c.st);
+    if (rc) return rc;
+    {
+        GmcProbeScope probe(GMC_K_DENSE_MFMA, c.st);
+        rc = gmc_hw2_rows_launch(w.H, b->dinv, m->W2, w.Z0, b->R, F, 0, w.ld, c.st);
+    }
+    if (rc) return rc;
+    return gmc_head_launch(b, w.Z0, 1, m->b2, C, P, S, loss, w.GY2, w.GY2 ? w.db2part : nullptr, nullptr, c.st, loss_of(m));
+}
+
+int att_backward_body(const AttCall &c, float *grad, const float *loss_tail) {
+    const gmc_batch *b = c.b; const gmc_model *m = c.m; const AttWorkspace &w = c.w;
+    const long F = m->F;
+    float *dW1 = grad, *db1 = grad + (long)m->N * F, *dW2 = db1 + F, *db2 = dW2 + F * 3;
+    float *da_src = db2 + 3, *da_dst = da_src + F;
+    float *dT = w.H;
+    // layer 2's dinv travels in GY2; the hidden backward, given ones for layer 1's dinv, leaves G
+    int rc = gmc_att_gy2_scale_launch(w.GY2, b->dinv, w.ones, b->R, c.st);
+    if (rc) return rc;
+    rc = gmc_hidden_bwd_launch(w.H, w.ld, w.GY2, m->W2, w.ones, w.G, w.ld, w.part, b->R, m->F, c.st);
+    if (rc) return rc;
+    rc = gmc_colsum_reduce_launch(w.part, gmc_hidden_tiles(b->R), m->F, dW2, db1, w.db2part, b->B, db2, c.st);
+    if (rc) return rc;
+    rc = gmc_att_edge_bwd_launch(b, w.T, w.G, w.ld, w.s_src, w.s_dst, c.slope, w.alpha_e, w.alpha_s, w.dz_e, w.dz_s,
+                                 w.ds_dst, m->F, c.st);
+    if (rc) return rc;
+    rc = gmc_att_bwd_t_launch(b, w.G, w.ld, w.alpha_e, w.alpha_s, w.dz_e, w.dz_s, w.ds_dst, w.ds_src, c.a_src, c.a_dst,
+                              dT, m->F, c.st);
+    if (rc) return rc;
+    rc = gmc_att_avec_launch(w.T, w.ld, w.ds_src, w.ds_dst, w.apart, da_src, da_dst, b->R, m->F, c.st);
+    if (rc) return rc;
+    rc = gmc_dw1_launch(b, dT, w.ld, dW1, w.dw1part, m->N, m->F, false, c.st);
+    if (rc || !loss_tail) return rc;
+    return gmc_loss_tail_launch(loss_tail, b->B, da_dst + F, c.st);
+}
+
+}  // namespace
+
+extern "C" size_t gmc_att_workspace_bytes(const gmc_batch *batch, const gmc_model *model, int training) {
+    if (check_abi(batch, model) || model->K != 3) return 0;
+    return att_carve(batch, model, training != 0, nullptr).bytes;
+}
+
+extern "C" int gmc_att_forward(const gmc_batch *batch, const gmc_model *model, const float *a_src, const float *a_dst,
+                               float slope, float C, void *workspace, size_t workspace_bytes, float *P, int32_t *S,
+                               float *loss, gmc_stream_t stream) {
+    AttCall c{batch, model, a_src, a_dst, slope};
+    int rc = att_open(c, false, workspace, workspace_bytes, stream, P, nullptr);
+    if (rc || batch->R == 0) return rc;
+    return att_forward_body(c, C, P, S, loss);
+}
+
+extern "C" int gmc_att_train_fwd_bwd(const gmc_batch *batch, const gmc_model *model, const float *a_src,
+                                     const float *a_dst, float slope, float C, void *workspace, size_t workspace_bytes,
+                                     float *P, int32_t *S, float *loss, float *grad, gmc_stream_t stream) {
+    AttCall c{batch, model, a_src, a_dst, slope};
+    int rc = att_open(c, true, workspace, workspace_bytes, stream, P, grad);
+    if (rc) return rc;
+    const bool tail = (model->flags & GMC_MODEL_GRAD_TAIL) != 0;
+    if (tail && !loss) return GMC_ERR_NULL;
+    if (batch->R == 0) {
+        const size_t n = (size_t)model->N * model->F + model->F + (size_t)model->F * 3 + 3 + 2 * (size_t)model->F + (tail ? 1 : 0);
+        return (int)hipMemsetAsync(grad, 0, n * sizeof(float), c.st);
+    }
+    rc = att_forward_body(c, C, P, S, loss);
+    return rc ? rc : att_backward_body(c, grad, tail ? loss : nullptr);
+}

@@ -114,3 +114,23 @@ int gmc_kway_hidden_bwd_launch(const float *H, long ldh, const float *GY2, const
                                long ldg, float *part, int R, int F, int K, hipStream_t st);
 int gmc_kway_reduce_launch(const float *part, int tiles, int F, int K, float *dW2, float *db1, const float *db2part,
                            int B, float *db2, hipStream_t st);
+
+// ---- the graph-attention first layer (attention.hip): the row kernels of the gmc_att_* entry points -----------------
+// Row-major [R, ld] operands T (= X @ W1), H, G (gradient at layer 1's pre-activation), dT; per-row scalars s_src, s_dst,
+// alpha_s, dz_s, ds_src, ds_dst [R]; per-CSR-entry scalars alpha_e, dz_e [nnz].  a_src / a_dst [F] need no alignment.
+size_t gmc_att_avec_part_floats(int R, int F);
+int gmc_att_scores_launch(const float *T, long ld, const float *a_src, const float *a_dst, float *s_src, float *s_dst,
+                          int R, int F, hipStream_t st);
+int gmc_att_fwd_launch(const gmc_batch *b, const float *T, long ld, const float *s_src, const float *s_dst, float slope,
+                       const float *bias, float *alpha_e, float *alpha_s, float *H, int F, hipStream_t st);
+// GY2 [R,4] rows scaled by dinv in place, ones[r] = 1
+int gmc_att_gy2_scale_launch(float *GY2, const float *dinv, float *ones, int R, hipStream_t st);
+int gmc_att_edge_bwd_launch(const gmc_batch *b, const float *T, const float *G, long ld, const float *s_src,
+                            const float *s_dst, float slope, const float *alpha_e, const float *alpha_s, float *dz_e,
+                            float *dz_s, float *ds_dst, int F, hipStream_t st);
+int gmc_att_bwd_t_launch(const gmc_batch *b, const float *G, long ld, const float *alpha_e, const float *alpha_s,
+                         const float *dz_e, const float *dz_s, const float *ds_dst, float *ds_src, const float *a_src,
+                         const float *a_dst, float *dT, int F, hipStream_t st);
+// da_src = sum_r ds_src[r] * T[r,:], da_dst = sum_r ds_dst[r] * T[r,:]; part: gmc_att_avec_part_floats(R, F) floats
+int gmc_att_avec_launch(const float *T, long ld, const float *ds_src, const float *ds_dst, float *part, float *da_src,
+                        float *da_dst, int R, int F, hipStream_t st);

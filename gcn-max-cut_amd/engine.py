@@ -19,10 +19,12 @@ from . import hip
 from .graph import GraphBatch
 
 PARAM_ORDER = ("conv1.weight", "conv1.bias", "conv2.weight", "conv2.bias")
+# the attention engine's flat buffer carries the two attention vectors of layer 1 behind the four GraphConv tensors
+ATT_PARAM_ORDER = PARAM_ORDER + ("conv1.attn_src", "conv1.attn_dst")
 
 
-def flat_layout(N: int, F: int, K: int) -> Tuple[List[int], int]:
-    sizes = [N * F, F, F * K, K]
+def flat_layout(N: int, F: int, K: int, attention: bool = False) -> Tuple[List[int], int]:
+    sizes = [N * F, F, F * K, K] + ([F, F] if attention else [])
     offs = [0]
     for s in sizes:
         offs.append(offs[-1] + s)
@@ -36,16 +38,25 @@ MAX_HIDDEN = 4096
 class FusedEngine:
     """One per model.  ``adopt`` re-homes a module's parameters into the flat buffer."""
 
-    def __init__(self, N: int, F: int, K: int, device: Optional[torch.device] = None, *, kway: bool = False):
+    def __init__(self, N: int, F: int, K: int, device: Optional[torch.device] = None, *, kway: bool = False,
+                 attention: bool = False):
         """``kway`` = True asks for the K-class engine (number_classes K in 2..8 through gmc_kway_*: the row-kernel sequence,
         ``[R,K]`` outputs, no fused step / slab / dropout / dense features).  It is required for K != 3 - a caller written
         for the 3-class engine's surface is told so instead of meeting NotImplementedError later - and allowed for K = 3,
-        which then runs the same sequence.  ``GCNSoftmax.engine()`` passes it for models with number_classes != 3."""
+        which then runs the same sequence.  ``GCNSoftmax.engine()`` passes it for models with number_classes != 3.
+
+        ``attention`` = True asks for the attention engine: layer 1 is single-head graph attention (gmc_att_*: the
+        row-kernel sequence of csrc/attention.hip), three classes, the flat buffer ``[W1 | b1 | W2 | b2 | a_src | a_dst]``.
+        It offers forward, train_fwd_bwd and the Adam steps; the fused step, the slab copy, dropout, dense features and the
+        caller-supplied dLoss/dP raise NotImplementedError naming ``layer1``.  ``GATSoftmax.engine()`` passes it."""
         self.device = device or hip.require_gpu()
         self.lib = hip.load()
         if not 2 <= K <= hip.KWAY_MAX_CLASSES:
             raise ValueError(f"number_classes must be in 2..{hip.KWAY_MAX_CLASSES}, got {K} (nodes 0..K-1 of every graph "
                              "are the terminals of classes 0..K-1)")
+        if attention and (K != 3 or kway):
+            raise ValueError(f"number_classes = {K}: layer1 = 'attention' is implemented for the 3-class model only "
+                             "(FusedEngine(N, F, 3, attention=True))")
         if K != 3 and not kway:
             raise ValueError(f"number_classes = {K}: the fused engine is 3-class (the terminal override of "
                              "TrainingNeural.py:91-93 is 3-wide); FusedEngine(N, F, K, kway=True) is the K-class engine")
@@ -56,12 +67,15 @@ class FusedEngine:
         # with [R,K] outputs.  The fused 3-way kernels, the slab copy of W1, dropout, dense features and the
         # caller-supplied dLoss/dP are 3-class only and raise NotImplementedError there.
         self.kway = bool(kway)
+        # layer1 = "attention": the gmc_att_* entry points; six tensors in the flat buffer
+        self.attention = bool(attention)
+        self.param_order = ATT_PARAM_ORDER if self.attention else PARAM_ORDER
         # Any hidden_dim (TrainingNeural.py:42,66-67 accept any int; n_nodes=50 gives 25): the kernels work on 16-byte
         # column groups, so the flat buffer carries the hidden dimension padded to a multiple of 4 (Fp).  Pad columns of
         # W1 / entries of b1 / rows of W2 are 0 and stay 0 (their activations are relu(0), every gradient entry is an
         # exact 0, Adam of 0 is 0); the module's parameters and state_dict keep the logical shapes as views [:, :F].
         self.Fp = (F + 3) // 4 * 4
-        self.offs, self.count = flat_layout(N, self.Fp, K)
+        self.offs, self.count = flat_layout(N, self.Fp, K, self.attention)
         # + 4 floats of tail: slot `count` carries the summed loss through the all-reduce
         self.flat = torch.zeros(self.count + 4, dtype=torch.float32, device=self.device)
         self.grad = torch.zeros_like(self.flat)
@@ -82,17 +96,24 @@ class FusedEngine:
     # ---- parameters
     def views(self, buf: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
         """The four tensors in the reference's (logical) shapes: views of ``buf`` (for hidden_dim % 4 != 0
-        ``conv1.weight`` is a strided view of the padded rows)."""
+        ``conv1.weight`` is a strided view of the padded rows).  The attention engine: six, with ``conv1.attn_src`` and
+        ``conv1.attn_dst`` [F]."""
         p, F = self.padded_views(buf), self.F
-        return {"conv1.weight": p["conv1.weight"][:, :F], "conv1.bias": p["conv1.bias"][:F],
-                "conv2.weight": p["conv2.weight"][:F], "conv2.bias": p["conv2.bias"]}
+        out = {"conv1.weight": p["conv1.weight"][:, :F], "conv1.bias": p["conv1.bias"][:F],
+               "conv2.weight": p["conv2.weight"][:F], "conv2.bias": p["conv2.bias"]}
+        if self.attention:
+            out.update({k: p[k][:F] for k in ATT_PARAM_ORDER[4:]})
+        return out
 
     def padded_views(self, buf: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
         """The same four tensors as the kernels see them: hidden dimension padded to Fp, contiguous."""
         buf = self.flat if buf is None else buf
         o, N, F, K = self.offs, self.N, self.Fp, self.K
-        return {"conv1.weight": buf[o[0]:o[1]].view(N, F), "conv1.bias": buf[o[1]:o[2]],
-                "conv2.weight": buf[o[2]:o[3]].view(F, K), "conv2.bias": buf[o[3]:o[4]]}
+        out = {"conv1.weight": buf[o[0]:o[1]].view(N, F), "conv1.bias": buf[o[1]:o[2]],
+               "conv2.weight": buf[o[2]:o[3]].view(F, K), "conv2.bias": buf[o[3]:o[4]]}
+        if self.attention:
+            out.update({"conv1.attn_src": buf[o[4]:o[5]], "conv1.attn_dst": buf[o[5]:o[6]]})
+        return out
 
     def _refresh_model(self) -> None:
         v = self.padded_views()
@@ -128,14 +149,25 @@ class FusedEngine:
         return hip.ptr(self.w1_slab)
 
     def _three_way_only(self, what: str) -> None:
+        if self.attention:
+            raise NotImplementedError(f"{what} is implemented for layer1 = 'graphconv' only (this is the attention engine, "
+                                      "layer1 = 'attention': forward, train_fwd_bwd and the Adam steps are what it offers)")
         if self.kway:
             raise NotImplementedError(f"{what} is implemented for the fused 3-class engine only (this is the K-class engine, "
                                       f"number_classes = {self.K}: forward, train_fwd_bwd and the Adam steps are what it "
                                       "offers)")
 
     def _entry(self, name: str) -> str:
-        """The library entry point of a call: gmc_<name>, or gmc_kway_<name> for number_classes != 3."""
-        return f"gmc_kway_{name}" if self.kway else f"gmc_{name}"
+        """The library entry point of a call: gmc_<name>, gmc_kway_<name> for number_classes != 3, gmc_att_<name> for the
+        attention engine."""
+        return f"gmc_att_{name}" if self.attention else f"gmc_kway_{name}" if self.kway else f"gmc_{name}"
+
+    def _layer1_args(self) -> tuple:
+        """What the gmc_att_* calls take behind the model struct: the two attention vectors and the slope."""
+        if not self.attention:
+            return ()
+        v = self.padded_views()
+        return hip.ptr(v["conv1.attn_src"]), hip.ptr(v["conv1.attn_dst"]), hip.ATTENTION_SLOPE
 
     def _check_terminals(self, batch: GraphBatch) -> None:
         if self.kway and batch.B and int(batch.sizes.min()) < self.K:
@@ -183,22 +215,22 @@ class FusedEngine:
             self.set_dropout(*before)
 
     def adopt(self, module: torch.nn.Module) -> None:
-        """Make ``module.conv{1,2}.{weight,bias}`` views of the flat buffer (values kept)."""
+        """Make ``module.conv{1,2}.{weight,bias}`` (and the attention vectors) views of the flat buffer (values kept)."""
         named = dict(module.named_parameters())
         views = self.views()
-        for k in PARAM_ORDER:
+        for k in self.param_order:
             p = named[k]
             if p.data_ptr() != views[k].data_ptr() or p.device != self.device or p.stride() != views[k].stride():
                 views[k].copy_(p.detach().to(self.device, torch.float32))
                 p.data = views[k]
-        self._adopted = [named[k] for k in PARAM_ORDER]
+        self._adopted = [named[k] for k in self.param_order]
         self._slab_sig = None
 
     def owns(self, module: torch.nn.Module) -> bool:
         named = dict(module.named_parameters())
         views = self.views()
         return all(named[k].data_ptr() == views[k].data_ptr() and named[k].stride() == views[k].stride()
-                   for k in PARAM_ORDER)
+                   for k in self.param_order)
 
     def make_batch(self, handles, values=None) -> GraphBatch:
         return GraphBatch(handles, values, self.device)
@@ -245,7 +277,8 @@ class FusedEngine:
         if ws is None:   # the engine's own scratch; the dense plan gets one of its own
             ws = (self._workspace(batch, False)[0] if X is None else
                   torch.empty(self.workspace_bytes_features(batch, False), dtype=torch.uint8, device=self.device))
-        name, feat = (self._entry("forward"), ()) if X is None else ("gmc_forward_features", (hip.ptr(Xd), Xd.shape[1]))
+        name, feat = ((self._entry("forward"), self._layer1_args()) if X is None else
+                      ("gmc_forward_features", (hip.ptr(Xd), Xd.shape[1])))
         model = self._call_model(loss=loss)
         rc = getattr(self.lib, name)(batch.ref(), C.byref(model), *feat, C_, hip.ptr(ws), ws.numel(), hip.ptr(P),
                                      hip.ptr(S), hip.ptr(losses), hip.stream())
@@ -267,8 +300,8 @@ class FusedEngine:
         ws, nbytes = (ws, ws.numel()) if ws is not None else self._workspace(batch, True)
         model = self._call_model(slab, loss)
         name = self._entry("train_fwd_bwd")
-        rc = getattr(self.lib, name)(batch.ref(), C.byref(model), C_, hip.ptr(ws), nbytes, hip.ptr(P), hip.ptr(S),
-                                     hip.ptr(losses), hip.ptr(self.grad), hip.stream())
+        rc = getattr(self.lib, name)(batch.ref(), C.byref(model), *self._layer1_args(), C_, hip.ptr(ws), nbytes, hip.ptr(P),
+                                     hip.ptr(S), hip.ptr(losses), hip.ptr(self.grad), hip.stream())
         hip.check(rc, name)
         return P, S, losses
 
@@ -376,7 +409,7 @@ class FusedEngine:
         keep_slab = slab and self.slab_enabled
         if keep_slab:
             self._three_way_only("the slab copy of conv1.weight")
-        if self.kway and publish is not None:   # (the fused publish + Adam launch knows the N x F x 3 layout only)
+        if (self.kway or self.attention) and publish is not None:   # (the fused publish + Adam launch knows the N x F x 3 layout only)
             self.publish(*publish)
             publish = None
         bufs = (hip.ptr(self.flat), hip.ptr(self.grad), hip.ptr(self.m), hip.ptr(self.v))

@@ -147,13 +147,19 @@ class BatchArrays:
     """Host-side (numpy) form of a block-diagonal batch: everything ``struct gmc_batch``
     points to, built without touching a GPU (so the layout is testable on CPU)."""
 
-    def __init__(self, handles: Sequence[GraphHandle], values: Optional[Sequence[Optional[np.ndarray]]] = None):
+    def __init__(self, handles: Sequence[GraphHandle], values: Optional[Sequence[Optional[np.ndarray]]] = None,
+                 allow_zero_degree: bool = False):
+        """``allow_zero_degree``: nodes without neighbours are no error.  GraphConv refuses them as DGL does, and so does
+        every function of the Python API that builds its batches itself (the trainer, ``net(g, X)``, ``evaluate_model``, the
+        decoders), whatever the model's first layer; the attention layer gives every row a self term, so a caller of the
+        engine (``FusedEngine(..., attention=True)``: forward, train_fwd_bwd) may hand it a batch built with this flag."""
         B = len(handles)
         ns = np.asarray([h.n for h in handles], np.int64)
         for h in handles:
             if h.n < 3 or h.n > hip.MAX_GRAPH_NODES:
                 raise ValueError(f"graph with {h.n} nodes: need 3 <= n <= {hip.MAX_GRAPH_NODES}")
-            h.check_degrees()
+            if not allow_zero_degree:
+                h.check_degrees()
         goff = np.zeros(B + 1, np.int64)
         np.cumsum(ns, out=goff[1:])
         nnzs = np.asarray([h.col.size for h in handles], np.int64)
@@ -264,10 +270,10 @@ class GraphBatch:
     """Block-diagonal batch resident on one GPU; mirrors ``struct gmc_batch``."""
 
     def __init__(self, handles: Sequence[GraphHandle], values: Optional[Sequence[Optional[np.ndarray]]] = None,
-                 device: Optional[torch.device] = None):
+                 device: Optional[torch.device] = None, allow_zero_degree: bool = False):
         device = device or hip.require_gpu()
         self.device = device
-        h = BatchArrays(handles, values)
+        h = BatchArrays(handles, values, allow_zero_degree)
         self.host = h
         self.B, self.R, self.nnz, self.n_max, self.uniform_n = h.B, h.R, h.nnz, h.n_max, h.uniform_n
         self.sizes, self.goff_host = h.sizes, h.goff

@@ -23,6 +23,10 @@ MODEL_LOSS_EXPECTED = 2   # gmc_model.flags: loss and gradient are GMC_LOSS_EXPE
 # independent rounding: compute_loss on override_fixed_nodes(P) without the one-hot step)
 LOSS_KINDS = {"cut": 0, "expected_cut": 1}
 LOSS_ENV = "GCN_MAXCUT_LOSS"
+# layer 1 of the model: the reference's GraphConv(norm='both'), or single-head graph attention (gmc_att_*: GATSoftmax)
+LAYER1_KINDS = ("graphconv", "attention")
+LAYER1_ENV = "GCN_MAXCUT_LAYER1"
+ATTENTION_SLOPE = 0.2  # negative slope of the attention scores' leaky relu (the GAT paper's)
 KWAY_MAX_CLASSES = 8  # GMC_KWAY_MAX_CLASSES: number_classes the gmc_kway_* entry points take (2..8; 3 also has the fused path)
 ABI_VERSION = 200     # GMC_VERSION of include/gcnmaxcut.h these struct layouts follow (checked at load and per call)
 
@@ -76,6 +80,16 @@ def loss_name(name: Optional[str]) -> str:
     return next(k for k, v in LOSS_KINDS.items() if v == kind)
 
 
+def layer1_name(name: Optional[str]) -> str:
+    """The canonical name of a first layer; ``None`` reads the environment switch GCN_MAXCUT_LAYER1 (default
+    ``graphconv``) at call time.  The library itself reads no environment."""
+    if name is None:
+        name = os.environ.get(LAYER1_ENV) or "graphconv"
+    if name not in LAYER1_KINDS:
+        raise ValueError(f"unknown layer1 {name!r}: expected one of {sorted(LAYER1_KINDS)}")
+    return name
+
+
 def _api() -> dict:
     """name -> (restype, argtypes) of every symbol include/gcnmaxcut.h declares: the one place an entry point is
     added to (tests check the .so exports all of them)."""
@@ -110,6 +124,9 @@ def _api() -> dict:
         "gmc_kway_workspace_bytes": (sz, [B, M, i]),
         "gmc_kway_forward": (i, [B, M, f32, vp, sz, vp, vp, vp, vp]),
         "gmc_kway_train_fwd_bwd": (i, [B, M, f32, vp, sz, vp, vp, vp, vp, vp]),
+        "gmc_att_workspace_bytes": (sz, [B, M, i]),
+        "gmc_att_forward": (i, [B, M, vp, vp, f32, f32, vp, sz, vp, vp, vp, vp]),
+        "gmc_att_train_fwd_bwd": (i, [B, M, vp, vp, f32, f32, vp, sz, vp, vp, vp, vp, vp]),
         "gmc_gemm_f32": (i, [i32, i32, i32, i32, i32, vp, i64, vp, i64, vp, vp, i64, vp]),
         "gmc_set_fuse": (i, [i]),
         "gmc_probe_begin": (i, [i32]),

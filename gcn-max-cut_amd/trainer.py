@@ -96,7 +96,9 @@ class FusedTrainer:
             self.eng.sync_replicas(0)   # one model: rank 0's parameters / moments on every replica
         # what the engine offers: the fused step; scratch, slab copy of W1, device-stepped Adam (not host stand-ins)
         # (a number_classes != 3 engine has neither the fused step nor the slab copy: train_fwd_bwd -> Adam, eager)
-        self._kway = bool(getattr(self.eng, "kway", False))
+        # (the attention engine - layer1 = "attention" - likewise: gmc_att_train_fwd_bwd -> Adam, eager, six tensors)
+        self._attention = bool(getattr(self.eng, "attention", False))
+        self._kway = bool(getattr(self.eng, "kway", False)) or self._attention
         self._fused_step = hasattr(self.eng, "train_step") and not self._kway
         self._slab = not self._kway
         self._hip = hasattr(self.eng, "adam_step_dev")
@@ -211,6 +213,9 @@ class FusedTrainer:
     def epoch(self, dataset: Dict) -> float:
         """One pass over the dataset; returns the cumulative loss (one host sync)."""
         t_entry = perf_counter()
+        if self._attention and self._dropout() > 0.0:
+            raise NotImplementedError("dropout is implemented for layer1 = 'graphconv' only (this model has layer1 = "
+                                      "'attention'): train it with dropout = 0")
         if self._kway and self._dropout() > 0.0:
             raise NotImplementedError(f"dropout is implemented for number_classes = 3 only (this model has number_classes "
                                       f"= {self.eng.K}): train it with dropout = 0")
@@ -451,7 +456,7 @@ class FusedTrainer:
             return
         named = dict(self.net.named_parameters())
         mv, vv = self.eng.views(self.eng.m), self.eng.views(self.eng.v)
-        for k in PARAM_ORDER:
+        for k in getattr(self.eng, "param_order", PARAM_ORDER):
             self.optimizer.state[named[k]] = {
                 'step': torch.tensor(float(self.eng.step_count)),
                 'exp_avg': mv[k], 'exp_avg_sq': vv[k]}

@@ -167,16 +167,20 @@ int gmc_ell_slots_for(int32_t R, const int32_t *rowptr, int32_t W);
 /* Kernel tags reported by the timing probe (one per launch of the fused step). */
 enum {
     GMC_K_GATHER_W1 = 0,  /* (X o dinv) @ W1 as a row gather of W1          TrainingNeural.py:80 */
-    GMC_K_AGG_FWD = 1,    /* layer-1 aggregation + b1 + relu (+ fused H@W2)  :80-83 */
+    GMC_K_AGG_FWD = 1,    /* layer-1 aggregation + b1 + relu (+ fused H@W2)  :80-83; gmc_att_*: the attention aggregation */
     GMC_K_HEAD = 2,       /* per-graph [n,3] head: softmax, decode, loss, GY2 :83-106,:154-176 */
-    GMC_K_HIDDEN_BWD = 3, /* dW2/db1 partials + Gs                           backward of :81-83 */
-    GMC_K_COLSUM = 4,     /* fold of the partials, db2 */
-    GMC_K_AGG_BWD = 5,    /* conv1 backward aggregation                      backward of :80 */
+    GMC_K_HIDDEN_BWD = 3, /* dW2/db1 partials + Gs                           backward of :81-83 (gmc_att_*: two records, the
+                           * row scaling of GY2 in front of it) */
+    GMC_K_COLSUM = 4,     /* fold of the partials, db2 (gmc_att_*: three records, the partials of da_src / da_dst and their
+                           * fold behind it) */
+    GMC_K_AGG_BWD = 5,    /* conv1 backward aggregation                      backward of :80 (gmc_att_*: two records, the
+                           * edge backward, then the transposed aggregation) */
     GMC_K_DW1 = 6,        /* dW1 gather-reduce over graphs */
     GMC_K_DW1_FOLD = 7,   /* fold of the dW1 chunk partials */
     GMC_K_ADAM = 8,       /* fused Adam                                      :386 */
     GMC_K_SPMM_USER = 9,  /* gmc_spmm_f32 called directly */
-    GMC_K_DENSE_MFMA = 10, /* the stand-alone H @ W2 product: gmc_dense_hw2_f32, and hw2_k of the K-class sequence */
+    GMC_K_DENSE_MFMA = 10, /* the stand-alone H @ W2 product: gmc_dense_hw2_f32, and hw2_k of the K-class sequence; gmc_att_*:
+                            * two records, the attention scores (row dot products) and H @ W2 */
     GMC_K_BWD1_FUSED = 11, /* hidden backward + conv1 backward aggregation + dW1, one pass over H (a one-graph
                             * gmc_train_step_f32 computes the head in this launch as well: no GMC_K_HEAD record) */
     GMC_K_FWD1_FUSED = 12, /* W1 gather + layer-1 aggregation (+ fused H@W2), one kernel */
@@ -464,6 +468,57 @@ int gmc_kway_forward(const gmc_batch *batch, const gmc_model *model, float C, vo
  * without any other launch. */
 int gmc_kway_train_fwd_bwd(const gmc_batch *batch, const gmc_model *model, float C, void *workspace,
                            size_t workspace_bytes, float *P, int32_t *S, float *loss, float *grad, gmc_stream_t stream);
+
+/* ---- a graph-attention first layer (extension: the first of the "future improvements" of the reference's README) ------
+ *
+ * The entry points above have GraphConv(norm='both') as layer 1 (TrainingNeural.py:80).  These three replace that layer's
+ * aggregation by single-head graph attention (GAT) on the graph with self-loops added, followed by relu; three classes;
+ * layer 2, the head, both losses, the terminal override and the decoders are those of gmc_forward (TrainingNeural.py:83-106).
+ * Per graph, on local nodes; the terms of row i are its CSR entries (rowptr / gcol / lcol) plus ONE self term - a self-loop
+ * edge of the graph counts as one more ordinary term:
+ *
+ *   T[i,:]   = sum_e vals[e] * W1[lcol[e],:]                  (X @ W1 for X = the padded adjacency; no row scale)
+ *   s_src[j] = T[j,:] . a_src        s_dst[i] = T[i,:] . a_dst
+ *   z_ij     = s_dst[i] + s_src[j]   e_ij = z_ij > 0 ? z_ij : slope * z_ij          for j in terms(i)
+ *   alpha_ij = exp(e_ij - m_i) / sum_j exp(e_ij - m_i),  m_i = max_j e_ij
+ *   H[i,:]   = relu(sum_j alpha_ij * T[j,:] + b1)
+ *   Z0 = dinv o (H @ W2), then the head of gmc_forward (GraphConv norm='both' for layer 2)
+ *
+ * No attention dropout and no feature dropout; edge weights enter through the features only (as in this library's GraphConv
+ * aggregation); a node without neighbours has alpha_ii = 1.  a_src, a_dst: [F] device floats (any alignment), slope: the
+ * negative slope of the leaky relu, in [0, 1] (0.2 in the GAT paper).
+ *
+ * Backward, with G = relu'(H) o (dinv o (GY2 @ W2^T)) the gradient at the pre-activation:
+ *
+ *   da_ij   = G[i,:] . T[j,:]
+ *   de_ij   = alpha_ij * (da_ij - sum_k alpha_ik * da_ik)
+ *   dz_ij   = de_ij * (z_ij > 0 ? 1 : slope)
+ *   ds_dst[i] = sum_j dz_ij                       (row i's own terms)
+ *   ds_src[j] = sum_{i: j in terms(i)} dz_ij      (the reverse edges)
+ *   dT[j,:] = sum_{i: j in terms(i)} alpha_ij * G[i,:] + ds_src[j] * a_src + ds_dst[j] * a_dst
+ *   da_src  = sum_j ds_src[j] * T[j,:]            da_dst = sum_i ds_dst[i] * T[i,:]
+ *   dW1     = X^T @ dT;  db1 = colsum(G);  dW2, db2: as gmc_train_fwd_bwd
+ *
+ * The flat gradient is [dW1 | db1 | dW2 | db2 | da_src | da_dst]: N*F + F + F*3 + 3 + 2F floats, plus the tail slot with
+ * GMC_MODEL_GRAD_TAIL.  The batch's CSR must be symmetric with each row's columns in ascending order (what
+ * gcn-max-cut_amd/graph.py builds): the backward finds the reverse of an entry by a binary search.
+ * Kernel sequence: one kernel per operation on row-major [R, ld] buffers (the plan of the *_features and gmc_kway_* calls),
+ * the layer-1 kernels from csrc/attention.hip; gmc_set_fuse does not matter, the ELL table is read by the head only,
+ * W1_slab is not read.  model->K must be 3 (GMC_ERR_CLASSES); dropout_p > 0: GMC_ERR_UNSUPPORTED.  Argument checks: the
+ * order documented above for the fused entry points, with a_src / a_dst among step 1's pointers (NULL), dropout_p > 0
+ * (UNSUPPORTED) at the end of step 2, the slope as step 3 (outside [0, 1] or NaN: SHAPE), and W1 / b1 with grad in step 5
+ * (ALIGN; P and W2 need no alignment here, unlike gmc_kway_*: the 3-wide kernels read them with 4-byte accesses).  Results are bitwise reproducible (no float atomics: every sum runs in a fixed order). */
+/* bytes of scratch gmc_att_forward / gmc_att_train_fwd_bwd need (0 for a NULL struct, another abi word, or K != 3) */
+size_t gmc_att_workspace_bytes(const gmc_batch *batch, const gmc_model *model, int training);
+/* gmc_forward with the attention layer: P [R,3]; S [R] / loss [B] optional.  An empty batch returns GMC_OK without a launch. */
+int gmc_att_forward(const gmc_batch *batch, const gmc_model *model, const float *a_src, const float *a_dst, float slope,
+                    float C, void *workspace, size_t workspace_bytes, float *P, int32_t *S, float *loss,
+                    gmc_stream_t stream);
+/* gmc_train_fwd_bwd with the attention layer: grad as laid out above (with GMC_MODEL_GRAD_TAIL loss must be non-NULL).  An
+ * empty batch zeroes grad (and the tail slot) without any other launch. */
+int gmc_att_train_fwd_bwd(const gmc_batch *batch, const gmc_model *model, const float *a_src, const float *a_dst,
+                          float slope, float C, void *workspace, size_t workspace_bytes, float *P, int32_t *S, float *loss,
+                          float *grad, gmc_stream_t stream);
 
 /* ---- decode / post-processing (the caller of the path in BASELINE configs[4]) -------- */
 
