@@ -87,11 +87,17 @@ def move_terminals_to_front(graph, terminals: List[int], number_classes: int) ->
 
 def process_graphs_from_folder(all_graphs: Dict, all_terminals: Dict, max_nodes: int,
                                save_batch_size: Optional[int] = None,
-                               output_filename_prefix: str = "processed_graphs", number_classes: int = 3) -> Dict:
+                               output_filename_prefix: str = "processed_graphs", number_classes: int = 3,
+                               adjacency: str = "dense") -> Dict:
     """Normalise terminals to node ids 0,1,2 and emit the training dataset
     (graphExtender.py:50-132).  ``number_classes`` other than 3 (extension): the K terminals of every graph move onto
     the labels 0..K-1 (:func:`move_terminals_to_front`), graphs whose terminal list does not hold K distinct nodes are
-    skipped, and the items carry ``list(range(K))``; 3 is the reference's path."""
+    skipped, and the items carry ``list(range(K))``; 3 is the reference's path.  ``adjacency`` (extension): ``"dense"``
+    is the reference's item; ``"none"`` puts ``None`` where the dense ``[n, max_nodes]`` tensor would be (1.6 GB per graph
+    at n = 20,000) - the trainer, ``evaluate_model`` and ``net(g, None)`` then read the handle's own edge weights, which
+    is what they take from the tensor."""
+    if adjacency not in ("dense", "none"):
+        raise ValueError(f"unknown adjacency {adjacency!r}: expected 'dense' or 'none'")
     datasetItem = {}
     i = 0
     skipped = 0
@@ -112,9 +118,14 @@ def process_graphs_from_folder(all_graphs: Dict, all_terminals: Dict, max_nodes:
             print(f"Terminal swapped {i}")
 
             handle = from_networkx(graph).to(TORCH_DEVICE)
-            q_torch = adjacency_tensor(graph, torch_dtype=TORCH_DTYPE, torch_device=TORCH_DEVICE)
-            full_matrix = extend_matrix_torch_2(q_torch, max_nodes, torch_dtype=TORCH_DTYPE,
-                                                torch_device=TORCH_DEVICE)
+            if adjacency == "none":
+                if graph.number_of_nodes() > max_nodes:
+                    raise ValueError("N should be greater than or equal to the original matrix size.")
+                full_matrix = None
+            else:
+                q_torch = adjacency_tensor(graph, torch_dtype=TORCH_DTYPE, torch_device=TORCH_DEVICE)
+                full_matrix = extend_matrix_torch_2(q_torch, max_nodes, torch_dtype=TORCH_DTYPE,
+                                                    torch_device=TORCH_DEVICE)
             datasetItem[i] = [handle, full_matrix, graph, list(range(number_classes))]
             i += 1
 
@@ -134,8 +145,9 @@ def process_graphs_from_folder(all_graphs: Dict, all_terminals: Dict, max_nodes:
 
 
 def load_and_process_graphs(graphs_filename: str, terminals_filename: str, max_nodes: int,
-                            output_filename: str, save_batch_size: Optional[int] = None) -> None:
-    """graphExtender.py:134-161."""
+                            output_filename: str, save_batch_size: Optional[int] = None,
+                            adjacency: str = "dense") -> None:
+    """graphExtender.py:134-161.  ``adjacency``: as for :func:`process_graphs_from_folder`."""
     print(f"Loading graphs from {graphs_filename}")
     all_graphs = open_file(graphs_filename)
     print(f"Loading terminals from {terminals_filename}")
@@ -143,7 +155,8 @@ def load_and_process_graphs(graphs_filename: str, terminals_filename: str, max_n
     print(f"Processing {len(all_graphs)} graphs with max_nodes={max_nodes}")
     processed = process_graphs_from_folder(all_graphs, all_terminals, max_nodes,
                                            save_batch_size=save_batch_size,
-                                           output_filename_prefix=output_filename.replace('.pkl', ''))
+                                           output_filename_prefix=output_filename.replace('.pkl', ''),
+                                           adjacency=adjacency)
     if processed:
         print(f"Saving final dataset to {output_filename}")
         save_object(processed, output_filename)

@@ -140,6 +140,15 @@ def _three_classes_only(what: str, classes: int) -> None:
                          "argmax decode (simple_partition_assignment) for a model with another number_classes")
 
 
+def _decoder_graph_size(what: str, nodes: int) -> None:
+    """The sampler, the rounding and the searches keep a graph's state in one workgroup's LDS (include/gcnmaxcut.h:
+    GMC_MAX_GRAPH_NODES)."""
+    if int(nodes) > hip.MAX_GRAPH_NODES:
+        raise ValueError(f"{what} is implemented for graphs of up to {hip.MAX_GRAPH_NODES} nodes, got one with {int(nodes)}: "
+                         "a larger graph gets the argmax partition (evaluate_model for its loss, "
+                         "simple_partition_assignment on net(g, None) under torch.no_grad() for the assignment)")
+
+
 def _sample_on_gpu(batch: GraphBatch, P: torch.Tensor, iterations: int, seed: Optional[int] = None, indices=None,
                    keep_samples: bool = True):
     """Draw the uniforms in the reference's order and run the fused sampler + cut count.  With ``seed`` (a uint64; the
@@ -548,6 +557,7 @@ def test_single_graph(model, dgl_graph, adjacency_matrix, nx_graph, terminals: L
                       graph_index: int = 0) -> Dict[str, Any]:
     """Argmax decode and post-processed decode of one graph (TestingNeuralNetwork.py:124-186).  ``seed`` /
     ``graph_index``: as for :func:`post_processing_optimization`."""
+    _decoder_graph_size("test_single_graph", len(nx_graph.nodes()) if nx_graph is not None else 0)
     try:
         with torch.no_grad():
             node_probabilities = model(dgl_graph, adjacency_matrix)
@@ -673,6 +683,7 @@ def decode_dataset(model, processed_graphs: Dict, post_processing_iterations: in
     _three_classes_only("decode_dataset", eng.K)
     model.eval()
     handles = [it[0] for it in items]
+    _decoder_graph_size("decode_dataset", max((h.n for h in handles), default=0))
     vals = [h.edge_values(it[1]) for h, it in zip(handles, items)]
     batch = GraphBatch(handles, vals, eng.device)
     P, S, loss = eng.forward(batch, 1.0, want_loss=True)
@@ -732,6 +743,7 @@ def round_dataset(model, processed_graphs: Dict, descent_sweeps: int = 0) -> Lis
     _rounding_classes(eng.K)
     model.eval()
     handles = [it[0] for it in items]
+    _decoder_graph_size("round_dataset", max((h.n for h in handles), default=0))
     vals = [h.edge_values(it[1]) for h, it in zip(handles, items)]
     batch = GraphBatch(handles, vals, eng.device)
     P, S, loss = eng.forward(batch, 1.0, want_loss=True)
@@ -771,6 +783,7 @@ def search_dataset(model, processed_graphs: Dict, samples: int = 200, *, sample_
     K = _search_classes("search_dataset", eng.K)
     model.eval()
     handles = [it[0] for it in items]
+    _decoder_graph_size("search_dataset", max((h.n for h in handles), default=0))
     vals = [h.edge_values(it[1]) for h, it in zip(handles, items)]
     batch = GraphBatch(handles, vals, eng.device)
     _needs_terminals(batch, K)

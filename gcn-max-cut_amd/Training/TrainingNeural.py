@@ -162,6 +162,8 @@ class GCNSoftmax(nn.Module):
                 f"autograd through net(g, X) is implemented for number_classes = 3 only (this model has number_classes = "
                 f"{eng.K}): train it with train_model / train_single_epoch, and call the model under torch.no_grad() "
                 "for its probabilities")
+        if torch.is_grad_enabled() and any(p.requires_grad for p in params):
+            eng._small_only(batch, "autograd through net(g, X)")
         # F.dropout(h, p=self.dropout_frac, training=self.training) (:82): a fresh mask per call in train mode;
         # the engine's dropout is 0 outside of such a call (evaluate_model, decode, the trainer's own steps)
         with eng.dropout(self.dropout_frac if self.training else 0.0):
@@ -319,6 +321,10 @@ def cut_loss(g, P, C: float = 1.0, relaxed: bool = False):
                          "another number_classes computes its loss inside train_model / evaluate_model")
     dev = hip.require_gpu()
     batch = g if isinstance(g, GraphBatch) else graph_batch_of(g, None, dev)
+    if batch.B and batch.n_max > hip.MAX_GRAPH_NODES:
+        raise ValueError(f"cut_loss is implemented for graphs of up to {hip.MAX_GRAPH_NODES} nodes, got one with "
+                         f"{batch.n_max}: a larger graph trains through train_model and gets its loss and its argmax "
+                         "partition from evaluate_model / simple_partition_assignment on net(g, None)")
     return _CutLoss.apply(P, batch, float(C), "expected_cut" if relaxed else "cut")
 
 

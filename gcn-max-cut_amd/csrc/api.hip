@@ -456,6 +456,9 @@ struct KwayWorkspace {
     float *part;     // [tiles,F,K+1]
     float *db2part;  // [B,K]
     float *dw1part;  // [chunks,N,F]
+    int32_t *S;      // [R]            gmc_large_* only (large_carve): the decode, for the loss launch
+    float *headpart; // [slots,K+1]    ... the head's tile partials (gmc_large_headpart_floats)
+    float *GZd;      // [R,K]          ... dinv o GZ (training)
     size_t bytes;
 };
 
@@ -485,8 +488,13 @@ KwayWorkspace kway_carve(const gmc_batch *b, const gmc_model *m, bool training, 
 
 bool kway_classes_ok(int K) { return K >= 2 && K <= GMC_KWAY_MAX_CLASSES; }
 
-// steps 1 and 2 of the documented order
-int kway_check(const gmc_batch *b, const gmc_model *m) {
+// would gmc_kway_* refuse the batch for its size (the head keeps a graph's [n,K] tiles in a CU's LDS)?
+bool kway_too_large(const gmc_batch *b, const gmc_model *m) {
+    return b->n_max > GMC_MAX_GRAPH_NODES || gmc_kway_head_lds_bytes(b->n_max, m->K, loss_of(m)) > GMC_KWAY_LDS_BYTES;
+}
+
+// steps 1 and 2 of the documented order; large: the gmc_large_* entry points (several workgroups per graph: no LDS bound)
+int kway_check(const gmc_batch *b, const gmc_model *m, bool large = false) {
     if (int rc = check_abi(b, m)) return rc;
     if (!b->goff || !b->rowptr || !b->gcol || !b->lcol || !b->dinv) return GMC_ERR_NULL;
     if (!m->W1 || !m->b1 || !m->W2 || !m->b2) return GMC_ERR_NULL;
@@ -496,24 +504,40 @@ int kway_check(const gmc_batch *b, const gmc_model *m) {
     if (!(m->dropout_p >= 0.f && m->dropout_p < 1.f)) return GMC_ERR_SHAPE;
     if (m->dropout_p > 0.f) return GMC_ERR_UNSUPPORTED;                 // the K-class sequence has no dropout
     if (m->W1_slab && !gmc_aligned16(m->W1_slab)) return GMC_ERR_ALIGN;
-    if (b->B > 0 && (b->n_max < m->K || b->n_max > GMC_MAX_GRAPH_NODES ||
-                     gmc_kway_head_lds_bytes(b->n_max, m->K, loss_of(m)) > GMC_KWAY_LDS_BYTES))
+    if (b->B > 0 && (b->n_max < m->K || (large ? b->n_max > GMC_LARGE_MAX_GRAPH_NODES : kway_too_large(b, m))))
         return GMC_ERR_GRAPH_SIZE;
     if (b->n_max > m->N) return GMC_ERR_SHAPE;  // more nodes than rows of conv1.weight
     return GMC_OK;
 }
 
+// gmc_large_*: the same buffers, then what the row-parallel head of large.hip keeps between its launches
+KwayWorkspace large_carve(const gmc_batch *b, const gmc_model *m, bool training, void *base) {
+    KwayWorkspace w = kway_carve(b, m, training, base);
+    size_t off = w.bytes;
+    auto take = [&](size_t floats) {
+        float *p = base ? reinterpret_cast<float *>(static_cast<char *>(base) + off) : nullptr;
+        off += align_up(floats * sizeof(float));
+        return p;
+    };
+    w.S = reinterpret_cast<int32_t *>(take((size_t)b->R));
+    w.headpart = take(gmc_large_headpart_floats(b, m->K));
+    if (training) w.GZd = take((size_t)b->R * m->K);
+    w.bytes = off;
+    return w;
+}
+
 struct KwayCall {
     const gmc_batch *b; const gmc_model *m;
+    bool large = false;   // gmc_large_*: the head of large.hip, graphs up to GMC_LARGE_MAX_GRAPH_NODES nodes
     KwayWorkspace w{}; hipStream_t st = nullptr;
 };
 
 int kway_open(KwayCall &c, bool training, void *workspace, size_t workspace_bytes, gmc_stream_t stream, const float *P,
               const float *grad) {
-    if (int rc = kway_check(c.b, c.m)) return rc;                                    // 1. 2.
+    if (int rc = kway_check(c.b, c.m, c.large)) return rc;                           // 1. 2.
     if (!workspace || !P || (training && !grad)) return GMC_ERR_NULL;                // 4. workspace and outputs
     if (!gmc_aligned16(grad) || !gmc_aligned16(P) || !gmc_aligned16(c.m->W2)) return GMC_ERR_ALIGN;   // 5.
-    c.w = kway_carve(c.b, c.m, training, workspace);                                 // 6. workspace size
+    c.w = c.large ? large_carve(c.b, c.m, training, workspace) : kway_carve(c.b, c.m, training, workspace);   // 6. size
     if (c.w.bytes > workspace_bytes) return GMC_ERR_WORKSPACE;
     c.st = static_cast<hipStream_t>(stream);
     return GMC_OK;
@@ -526,13 +550,22 @@ int kway_forward_body(const KwayCall &c, float C, float *P, int32_t *S, float *l
     // T0 = dinv o (A_val @ W1[:n]): a row gather of W1
     int rc = gmc_spmm_launch(b->rowptr, b->lcol, b->vals, b->dinv, m->W1, F, nullptr, 0, w.T0, w.ld, b->R, F,
                              group_rows(b), nullptr, nullptr, GMC_K_GATHER_W1, c.st);
+    if (!rc && c.large)   // (gmc_large_*: rows of more than 64 entries once more, summed in chunks - launchers.h)
+        rc = gmc_large_hub_rows_launch(b->rowptr, b->lcol, b->vals, b->dinv, m->W1, F, nullptr, 0, w.T0, w.ld, b->R, F,
+                                       GMC_K_GATHER_W1, c.st);
     if (rc) return rc;
     // H = relu(dinv o (A @ T0) + b1)
     rc = gmc_spmm_launch(b->rowptr, b->gcol, nullptr, b->dinv, w.T0, w.ld, m->b1, 1, w.H, w.ld, b->R, F, group_rows(b),
                          nullptr, nullptr, GMC_K_AGG_FWD, c.st);
+    if (!rc && c.large)
+        rc = gmc_large_hub_rows_launch(b->rowptr, b->gcol, nullptr, b->dinv, w.T0, w.ld, m->b1, 1, w.H, w.ld, b->R, F,
+                                       GMC_K_AGG_FWD, c.st);
     if (rc) return rc;
     rc = gmc_kway_hw2_launch(w.H, w.ld, b->dinv, m->W2, w.Z0, b->R, F, m->K, c.st);
     if (rc) return rc;
+    if (c.large)
+        return gmc_large_head_launch(b, w.Z0, m->b2, C, m->K, loss_of(m), P, S, loss, w.S, w.GZd, w.headpart, w.GY2,
+                                     w.db2part, c.st);
     return gmc_kway_head_launch(b, w.Z0, m->b2, C, m->K, loss_of(m), P, S, loss, w.GY2, w.db2part, c.st);
 }
 
@@ -548,6 +581,9 @@ int kway_backward_body(const KwayCall &c, float *grad, const float *loss_tail) {
     // conv1 backward aggregation:  U = dinv o (A @ Gs)
     rc = gmc_spmm_launch(b->rowptr, b->gcol, nullptr, b->dinv, Gs, w.ld, nullptr, 0, U, w.ld, b->R, m->F, group_rows(b),
                          nullptr, nullptr, GMC_K_AGG_BWD, c.st);
+    if (!rc && c.large)
+        rc = gmc_large_hub_rows_launch(b->rowptr, b->gcol, nullptr, b->dinv, Gs, w.ld, nullptr, 0, U, w.ld, b->R, m->F,
+                                       GMC_K_AGG_BWD, c.st);
     if (rc) return rc;
     rc = gmc_dw1_launch(b, U, w.ld, dW1, w.dw1part, m->N, m->F, false, c.st);
     if (rc || !loss_tail) return rc;
@@ -561,28 +597,70 @@ extern "C" size_t gmc_kway_workspace_bytes(const gmc_batch *batch, const gmc_mod
     return kway_carve(batch, model, training != 0, nullptr).bytes;
 }
 
-extern "C" int gmc_kway_forward(const gmc_batch *batch, const gmc_model *model, float C, void *workspace,
-                                size_t workspace_bytes, float *P, int32_t *S, float *loss, gmc_stream_t stream) {
-    KwayCall c{batch, model};
+namespace {
+
+int kway_forward_call(KwayCall c, float C, void *workspace, size_t workspace_bytes, float *P, int32_t *S, float *loss,
+                      gmc_stream_t stream) {
     int rc = kway_open(c, false, workspace, workspace_bytes, stream, P, nullptr);
-    if (rc || batch->R == 0) return rc;
+    if (rc || c.b->R == 0) return rc;
     return kway_forward_body(c, C, P, S, loss);
 }
 
-extern "C" int gmc_kway_train_fwd_bwd(const gmc_batch *batch, const gmc_model *model, float C, void *workspace,
-                                      size_t workspace_bytes, float *P, int32_t *S, float *loss, float *grad,
-                                      gmc_stream_t stream) {
-    KwayCall c{batch, model};
+int kway_train_call(KwayCall c, float C, void *workspace, size_t workspace_bytes, float *P, int32_t *S, float *loss,
+                    float *grad, gmc_stream_t stream) {
     int rc = kway_open(c, true, workspace, workspace_bytes, stream, P, grad);
     if (rc) return rc;
+    const gmc_model *model = c.m;
     const bool tail = (model->flags & GMC_MODEL_GRAD_TAIL) != 0;
     if (tail && !loss) return GMC_ERR_NULL;
-    if (batch->R == 0) {
+    if (c.b->R == 0) {
         const size_t n = (size_t)model->N * model->F + model->F + (size_t)model->F * model->K + model->K + (tail ? 1 : 0);
         return (int)hipMemsetAsync(grad, 0, n * sizeof(float), c.st);
     }
     rc = kway_forward_body(c, C, P, S, loss);
     return rc ? rc : kway_backward_body(c, grad, tail ? loss : nullptr);
+}
+
+}  // namespace
+
+extern "C" int gmc_kway_forward(const gmc_batch *batch, const gmc_model *model, float C, void *workspace,
+                                size_t workspace_bytes, float *P, int32_t *S, float *loss, gmc_stream_t stream) {
+    return kway_forward_call(KwayCall{batch, model}, C, workspace, workspace_bytes, P, S, loss, stream);
+}
+
+extern "C" int gmc_kway_train_fwd_bwd(const gmc_batch *batch, const gmc_model *model, float C, void *workspace,
+                                      size_t workspace_bytes, float *P, int32_t *S, float *loss, float *grad,
+                                      gmc_stream_t stream) {
+    return kway_train_call(KwayCall{batch, model}, C, workspace, workspace_bytes, P, S, loss, grad, stream);
+}
+
+// ---- graphs beyond GMC_MAX_GRAPH_NODES: the same sequence with the head of large.hip ---------------------------------------
+// The shared launchers were read for anything sized by n_max or N and for 32-bit products before they were relied on at
+// these sizes: gmc_spmm_launch (element offsets long; xcd_remap is the identity once a group exceeds the grid),
+// gmc_kway_hw2_launch, gmc_kway_hidden_bwd_launch / gmc_hidden_tiles, gmc_kway_reduce_launch, gmc_dw1_launch /
+// gmc_dw1_scratch_floats ((N+3)/4 workgroups, long offsets) and gmc_loss_tail_launch needed no change.
+extern "C" size_t gmc_large_workspace_bytes(const gmc_batch *batch, const gmc_model *model, int training) {
+    if (check_abi(batch, model) || !kway_classes_ok(model->K)) return 0;
+    return large_carve(batch, model, training != 0, nullptr).bytes;
+}
+
+extern "C" int gmc_large_forward(const gmc_batch *batch, const gmc_model *model, float C, void *workspace,
+                                 size_t workspace_bytes, float *P, int32_t *S, float *loss, gmc_stream_t stream) {
+    return kway_forward_call(KwayCall{batch, model, true}, C, workspace, workspace_bytes, P, S, loss, stream);
+}
+
+extern "C" int gmc_large_train_fwd_bwd(const gmc_batch *batch, const gmc_model *model, float C, void *workspace,
+                                       size_t workspace_bytes, float *P, int32_t *S, float *loss, float *grad,
+                                       gmc_stream_t stream) {
+    return kway_train_call(KwayCall{batch, model, true}, C, workspace, workspace_bytes, P, S, loss, grad, stream);
+}
+
+extern "C" int gmc_large_required(const gmc_batch *batch, const gmc_model *model) {
+    if (int rc = check_abi(batch, model)) return rc;
+    if (!kway_classes_ok(model->K)) return GMC_ERR_CLASSES;
+    if (batch->B <= 0) return 0;
+    if (model->K == 3) return batch->n_max > GMC_MAX_GRAPH_NODES ? 1 : 0;   // gmc_*: check()
+    return kway_too_large(batch, model) ? 1 : 0;                            // gmc_kway_*: kway_check()
 }
 
 // ---- graph-attention first layer: the row-kernel sequence with the kernels of attention.hip -------------------------------

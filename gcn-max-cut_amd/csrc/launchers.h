@@ -115,6 +115,22 @@ int gmc_kway_hidden_bwd_launch(const float *H, long ldh, const float *GY2, const
 int gmc_kway_reduce_launch(const float *part, int tiles, int F, int K, float *dW2, float *db1, const float *db2part,
                            int B, float *db2, hipStream_t st);
 
+// ---- the head for graphs beyond a CU's LDS (large.hip): head_k_kernel as row-parallel launches, several workgroups per
+// graph (tiles of 256 rows).  Sw [R] ints, GZd [R,K] (dinv o GZ) and headpart [gmc_large_headpart_floats] are scratch.
+size_t gmc_large_headpart_floats(const gmc_batch *b, int K);
+// GZd == nullptr: forward only (P, S, loss); else GY2 [R,K] and db2part [B,K] are written too
+int gmc_large_head_launch(const gmc_batch *b, const float *Z0, const float *b2, float C, int K, int loss_kind, float *P,
+                          int32_t *S, float *loss, int32_t *Sw, float *GZd, float *headpart, float *GY2, float *db2part,
+                          hipStream_t st);
+// Rows of more than 64 entries of Y = act(scale * A @ X + bias), written again after gmc_spmm_launch (same operands; F and
+// the leading dimensions multiples of 4, 16-byte aligned): the row kernels of spmm.hip add a row's entries one after the
+// other in CSR order, whose float32 error grows with the degree (5.6e-5 of the sum for 4200 equal addends); here the
+// row's sum is that of its first 64 entries plus, one after the other, the sum of each further 64 (each in CSR order), so
+// the error grows with 64 + deg / 64.  Rows of up to 64 entries are left as spmm.hip wrote them.
+int gmc_large_hub_rows_launch(const int32_t *rowptr, const int32_t *col, const float *vals, const float *scale,
+                              const float *X, long ldx, const float *bias, int relu, float *Y, long ldy, int32_t n_rows,
+                              int32_t F, int tag, hipStream_t st);
+
 // ---- the graph-attention first layer (attention.hip): the row kernels of the gmc_att_* entry points -----------------
 // Row-major [R, ld] operands T (= X @ W1), H, G (gradient at layer 1's pre-activation), dT; per-row scalars s_src, s_dst,
 // alpha_s, dz_s, ds_src, ds_dst [R]; per-CSR-entry scalars alpha_e, dz_e [nnz].  a_src / a_dst [F] need no alignment.

@@ -61,7 +61,9 @@ class FusedEngine:
             raise ValueError(f"number_classes = {K}: the fused engine is 3-class (the terminal override of "
                              "TrainingNeural.py:91-93 is 3-wide); FusedEngine(N, F, K, kway=True) is the K-class engine")
         if F < 1 or F > MAX_HIDDEN:
-            raise ValueError(f"hidden_dim must be in 1..{MAX_HIDDEN} on this path (include/gcnmaxcut.h: GMC_MAX_HIDDEN)")
+            raise ValueError(f"hidden_dim must be in 1..{MAX_HIDDEN} on this path (include/gcnmaxcut.h: GMC_MAX_HIDDEN), got {F}: "
+                             f"TrainingConfig derives hidden_dim = n_nodes // 2 when none is given, so a model of n_nodes > "
+                             f"{2 * MAX_HIDDEN + 1} needs an explicit hidden_dim")
         self.N, self.F, self.K = N, F, K
         # number_classes != 3: the K-class entry points (gmc_kway_*) - the one-kernel-per-operation row-kernel sequence
         # with [R,K] outputs.  The fused 3-way kernels, the slab copy of W1, dropout, dense features and the
@@ -157,10 +159,36 @@ class FusedEngine:
                                       f"number_classes = {self.K}: forward, train_fwd_bwd and the Adam steps are what it "
                                       "offers)")
 
-    def _entry(self, name: str) -> str:
+    def _entry(self, name: str, large: bool = False) -> str:
         """The library entry point of a call: gmc_<name>, gmc_kway_<name> for number_classes != 3, gmc_att_<name> for the
-        attention engine."""
+        attention engine; ``large``: gmc_large_<name>, for a batch that :meth:`needs_large`."""
+        if large:
+            return f"gmc_large_{name}"
         return f"gmc_att_{name}" if self.attention else f"gmc_kway_{name}" if self.kway else f"gmc_{name}"
+
+    def needs_large(self, batch: GraphBatch, loss: str = "cut") -> bool:
+        """Does this batch hold a graph too large for the engine's ordinary sequence (one workgroup per graph's head: more
+        than ``hip.MAX_GRAPH_NODES`` nodes, fewer for the K-class engine at number_classes > 3)?  The library decides
+        (gmc_large_required); the answer is kept with the batch.  Such a batch runs forward / train_fwd_bwd through
+        gmc_large_* - several workgroups per graph, up to ``hip.LARGE_MAX_GRAPH_NODES`` nodes - and nothing else."""
+        key = (self.K, hip.loss_kind(loss))
+        cache = batch.__dict__.setdefault("_needs_large", {})
+        if key not in cache:
+            model = hip.GmcModel(K=self.K, flags=hip.MODEL_LOSS_EXPECTED if key[1] else 0)
+            rc = int(self.lib.gmc_large_required(batch.ref(), C.byref(model)))
+            if rc < 0:
+                hip.check(rc, "gmc_large_required")
+            cache[key] = bool(rc)
+        return cache[key]
+
+    def _small_only(self, batch: GraphBatch, what: str) -> None:
+        """NotImplementedError for what a batch that :meth:`needs_large` does not offer (either loss: the stricter one)."""
+        if self.needs_large(batch, "expected_cut"):
+            raise NotImplementedError(
+                f"{what} is implemented for graphs of up to {hip.MAX_GRAPH_NODES} nodes only (fewer for number_classes > 3, "
+                f"where the head's [n,K] tiles have to fit a CU's LDS): this batch has a graph of {batch.n_max} nodes, "
+                f"number_classes = {self.K}.  Larger graphs (up to {hip.LARGE_MAX_GRAPH_NODES} nodes) offer forward and "
+                "train_fwd_bwd with layer1 = 'graphconv', without dropout and with the padded adjacency as features")
 
     def _layer1_args(self) -> tuple:
         """What the gmc_att_* calls take behind the model struct: the two attention vectors and the slope."""
@@ -237,7 +265,7 @@ class FusedEngine:
 
     # ---- scratch and outputs
     def _workspace(self, batch: GraphBatch, training: bool) -> Tuple[torch.Tensor, int]:
-        need = int(getattr(self.lib, self._entry("workspace_bytes"))(batch.ref(), C.byref(self._model), int(training)))
+        need = self.workspace_bytes(batch, training)
         if self._ws is None or self._ws.numel() < need:
             self._ws = torch.empty(max(need, 256), dtype=torch.uint8, device=self.device)
         return self._ws, self._ws.numel()
@@ -253,8 +281,17 @@ class FusedEngine:
 
     # ---- compute
     def workspace_bytes(self, batch: GraphBatch, training: bool) -> int:
-        return max(256, int(getattr(self.lib, self._entry("workspace_bytes"))(batch.ref(), C.byref(self._model),
-                                                                             int(training))))
+        large = self.needs_large(batch, "expected_cut")   # (either loss: gmc_large_*'s scratch covers gmc_kway_*'s)
+        if large:
+            self._large_only_what_it_offers(batch)
+        return max(256, int(getattr(self.lib, self._entry("workspace_bytes", large))(batch.ref(), C.byref(self._model),
+                                                                                    int(training))))
+
+    def _large_only_what_it_offers(self, batch: GraphBatch) -> None:
+        if self.attention:
+            self._small_only(batch, "layer1 = 'attention'")
+        if self._model.dropout_p > 0.0:
+            self._small_only(batch, "dropout")
 
     def forward(self, batch: GraphBatch, C_: float = 1.0, want_loss: bool = False,
                 ws: Optional[torch.Tensor] = None, loss: str = "cut"):
@@ -269,7 +306,11 @@ class FusedEngine:
         hip.loss_kind(loss)
         if X is not None:
             self._three_way_only("a forward through dense node features")
+            self._small_only(batch, "a forward through dense node features")
         self._check_terminals(batch)
+        large = X is None and self.needs_large(batch, loss)
+        if large:
+            self._large_only_what_it_offers(batch)
         P, S, losses = self._outputs(batch, None, want_loss)
         Xd = None if X is None else self.pad_features(batch, X)
         if batch.B == 0:   # nothing to launch (empty tensors have no device pointer to hand over)
@@ -277,7 +318,7 @@ class FusedEngine:
         if ws is None:   # the engine's own scratch; the dense plan gets one of its own
             ws = (self._workspace(batch, False)[0] if X is None else
                   torch.empty(self.workspace_bytes_features(batch, False), dtype=torch.uint8, device=self.device))
-        name, feat = ((self._entry("forward"), self._layer1_args()) if X is None else
+        name, feat = ((self._entry("forward", large), self._layer1_args()) if X is None else
                       ("gmc_forward_features", (hip.ptr(Xd), Xd.shape[1])))
         model = self._call_model(loss=loss)
         rc = getattr(self.lib, name)(batch.ref(), C.byref(model), *feat, C_, hip.ptr(ws), ws.numel(), hip.ptr(P),
@@ -297,9 +338,14 @@ class FusedEngine:
         if batch.B == 0:   # no graphs: zero gradient AND zero loss in the tail slot, nothing to launch
             self.grad[:self.count + 1].zero_()
             return P, S, losses
+        large = self.needs_large(batch, loss)
+        if large:
+            self._large_only_what_it_offers(batch)
+            if slab and self.slab_enabled:
+                self._small_only(batch, "the slab copy of conv1.weight")
         ws, nbytes = (ws, ws.numel()) if ws is not None else self._workspace(batch, True)
         model = self._call_model(slab, loss)
-        name = self._entry("train_fwd_bwd")
+        name = self._entry("train_fwd_bwd", large)
         rc = getattr(self.lib, name)(batch.ref(), C.byref(model), *self._layer1_args(), C_, hip.ptr(ws), nbytes, hip.ptr(P),
                                      hip.ptr(S), hip.ptr(losses), hip.ptr(self.grad), hip.stream())
         hip.check(rc, name)
@@ -316,6 +362,7 @@ class FusedEngine:
         :meth:`forward` (gmc_train_step_loss_f32; a one-graph ``expected_cut`` step launches the head on its own)."""
         kind = hip.loss_kind(loss)
         self._three_way_only("the fused train_step")
+        self._small_only(batch, "the fused train_step")
         ws, nbytes = (ws, ws.numel()) if ws is not None else self._workspace(batch, True)
         P, S, losses = out if out is not None else self._outputs(batch)
         tail = (self.ensure_slab() if slab else None, hip.stream())
@@ -341,6 +388,7 @@ class FusedEngine:
         """:meth:`backward_from_gp` (``X`` None: gmc_backward_from_gp) and :meth:`backward_features_from_gp`
         (gmc_backward_features_from_gp): (parameter gradients, dX or None)."""
         self._three_way_only("the backward from a caller's dLoss/dP")
+        self._small_only(batch, "the backward from a caller's dLoss/dP")
         Xd = None if X is None else self.pad_features(batch, X)
         dX = torch.empty_like(Xd) if want_dx else None
         if batch.B == 0:
@@ -358,6 +406,7 @@ class FusedEngine:
     # ---- features that are not the padded adjacency (layer 1 is a dense GEMM: gmc_forward_features)
     def workspace_bytes_features(self, batch: GraphBatch, training: bool) -> int:
         self._three_way_only("a forward through dense node features")
+        self._small_only(batch, "a forward through dense node features")
         return max(256, int(self.lib.gmc_workspace_bytes_features(batch.ref(), C.byref(self._model), int(training))))
 
     def pad_features(self, batch: GraphBatch, X: torch.Tensor) -> torch.Tensor:

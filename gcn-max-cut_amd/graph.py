@@ -156,8 +156,8 @@ class BatchArrays:
         B = len(handles)
         ns = np.asarray([h.n for h in handles], np.int64)
         for h in handles:
-            if h.n < 3 or h.n > hip.MAX_GRAPH_NODES:
-                raise ValueError(f"graph with {h.n} nodes: need 3 <= n <= {hip.MAX_GRAPH_NODES}")
+            if h.n < 3 or h.n > hip.LARGE_MAX_GRAPH_NODES:
+                raise ValueError(f"graph with {h.n} nodes: need 3 <= n <= {hip.LARGE_MAX_GRAPH_NODES}")
             if not allow_zero_degree:
                 h.check_degrees()
         goff = np.zeros(B + 1, np.int64)
@@ -193,6 +193,8 @@ class BatchArrays:
         max_deg = int(degi.max()) if degi.size else 0
         R = int(goff[-1])
         W = self.choose_width(degi)
+        if B and int(ns.max()) > hip.MAX_GRAPH_NODES:   # no LDS-tiled kernel serves such a batch: no table for it
+            W = 0
         if W and int(ns.max()) < 65535:
             deg64 = degi.astype(np.int64)
             slot = np.arange(int(eoff[-1]), dtype=np.int64) - np.repeat(rowptr[:-1].astype(np.int64), deg64)

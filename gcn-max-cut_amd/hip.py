@@ -16,6 +16,9 @@ _PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("GCN_MAXCUT_LIB") or os.path.join(_PKG, "lib", "libgcnmaxcut_hip.so")
 
 MAX_GRAPH_NODES = 4096
+# GMC_LARGE_MAX_GRAPH_NODES: what a graph of a batch may have (gmc_large_*: several workgroups share a graph's head); the
+# fused, K-class and attention sequences, the decoders and the cut_loss op stay at MAX_GRAPH_NODES
+LARGE_MAX_GRAPH_NODES = 1 << 20
 ANNEAL_LEVELS = 1024  # GMC_ANNEAL_LEVELS: entries of the level table gmc_refine_anneal_f32 reads
 MODEL_GRAD_TAIL = 1   # gmc_model.flags: grad has a tail slot that receives the batch's loss sum
 MODEL_LOSS_EXPECTED = 2   # gmc_model.flags: loss and gradient are GMC_LOSS_EXPECTED_CUT
@@ -124,6 +127,10 @@ def _api() -> dict:
         "gmc_kway_workspace_bytes": (sz, [B, M, i]),
         "gmc_kway_forward": (i, [B, M, f32, vp, sz, vp, vp, vp, vp]),
         "gmc_kway_train_fwd_bwd": (i, [B, M, f32, vp, sz, vp, vp, vp, vp, vp]),
+        "gmc_large_workspace_bytes": (sz, [B, M, i]),
+        "gmc_large_forward": (i, [B, M, f32, vp, sz, vp, vp, vp, vp]),
+        "gmc_large_train_fwd_bwd": (i, [B, M, f32, vp, sz, vp, vp, vp, vp, vp]),
+        "gmc_large_required": (i, [B, M]),
         "gmc_att_workspace_bytes": (sz, [B, M, i]),
         "gmc_att_forward": (i, [B, M, vp, vp, f32, f32, vp, sz, vp, vp, vp, vp]),
         "gmc_att_train_fwd_bwd": (i, [B, M, vp, vp, f32, f32, vp, sz, vp, vp, vp, vp, vp]),

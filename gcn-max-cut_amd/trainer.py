@@ -102,6 +102,10 @@ class FusedTrainer:
         self._fused_step = hasattr(self.eng, "train_step") and not self._kway
         self._slab = not self._kway
         self._hip = hasattr(self.eng, "adam_step_dev")
+        # does the planned dataset hold a batch beyond the one-workgroup head (FusedEngine.needs_large)?  Decided per
+        # DATASET in prepare(): every step of such a dataset then runs train_fwd_bwd -> Adam, eager, without the slab copy
+        # (the path the K-class engine takes), so that an epoch's losses come back one way
+        self._large = False
         self._dp_graphs_env = os.environ.get("GCN_MAXCUT_DP_GRAPHS", "0") == "1"
         self._plan_key = None
         self._ws: Optional[torch.Tensor] = None   # scratch of this trainer's steps (captured graphs point into it)
@@ -159,6 +163,8 @@ class FusedTrainer:
             handles = [it[0] for it in mine]
             vals = [h.edge_values(it[1]) for h, it in zip(handles, mine)]
             self._batches.append(self.eng.make_batch(handles, vals))
+        self._large = hasattr(self.eng, "needs_large") and any(self.eng.needs_large(b, self.loss)
+                                                                 for b in self._batches if b.B)
         rmax = max((b.R for b in self._batches), default=0)
         bmax = max((b.B for b in self._batches), default=0)
         self._out = (torch.empty((rmax, int(getattr(self.eng, "K", 3))), dtype=torch.float32, device=dev),
@@ -221,9 +227,10 @@ class FusedTrainer:
                                       f"= {self.eng.K}): train it with dropout = 0")
         self.prepare(dataset)
         drop = self._dropout()
-        path = launch_path(dp=self.dp, dropout=drop, allow_graph=self.allow_graph, fused_step=self._fused_step,
+        path = launch_path(dp=self.dp, dropout=drop, allow_graph=self.allow_graph,
+                           fused_step=self._fused_step and not self._large,
                            steps=len(self._batches), mapped=self._loss_host_dev is not None, poll=self._poll,
-                           dp_graphs=self._dp_graphs_env and not self._kway)
+                           dp_graphs=self._dp_graphs_env and not self._kway and not self._large)
         if path is Launch.DROPOUT:
             self._run_dropout(drop)
         elif path is Launch.DP or path is Launch.DP_GRAPHS:
@@ -312,6 +319,7 @@ class FusedTrainer:
         tail = eng.grad[eng.count:eng.count + 1]
         last = len(self._batches) - 1
         lr, betas, eps = self._hyper()
+        slab = self._slab and not self._large
         publish = self._step_host_dev
         if self._poll and self._step_host is not None:
             _arm(self._step_host_bits)
@@ -329,7 +337,7 @@ class FusedTrainer:
                 fwd_bwd[i].replay()                   # forward + loss + backward + gradient fold of my shard
             elif self._hip:
                 eng.train_fwd_bwd(batch, cfg.C, out=(self._out[0], self._out[1], self._loss_slots[i]), ws=self._ws,
-                                  slab=self._slab, **self._loss_kw)
+                                  slab=slab, **self._loss_kw)
             else:
                 eng.train_fwd_bwd(batch, cfg.C, out=(self._out[0], self._out[1], self._loss_slots[i]), **self._loss_kw)
             eng.allreduce_grad()                      # ONE RCCL all-reduce of [gradient | loss] per step, eager
@@ -344,7 +352,7 @@ class FusedTrainer:
             elif self._hip:
                 eng.sync_step_dev()                   # (a launch only after host-stepped updates)
                 # keeps the slab copy of W1 current; with `publish`: loss store + counter tick + Adam in two launches
-                eng.adam_step_dev(lr, betas, eps, slab=self._slab,
+                eng.adam_step_dev(lr, betas, eps, slab=slab,
                                   publish=(tail, publish + 4 * i) if publish else None)
             else:
                 eng.adam_step(lr, betas, eps)

@@ -469,6 +469,39 @@ int gmc_kway_forward(const gmc_batch *batch, const gmc_model *model, float C, vo
 int gmc_kway_train_fwd_bwd(const gmc_batch *batch, const gmc_model *model, float C, void *workspace,
                            size_t workspace_bytes, float *P, int32_t *S, float *loss, float *grad, gmc_stream_t stream);
 
+/* ---- graphs beyond GMC_MAX_GRAPH_NODES (extension: up to GMC_LARGE_MAX_GRAPH_NODES nodes per graph) -------------------
+ *
+ * Every entry point above keeps one graph's head in one workgroup with the graph's [n,K] state in LDS, which is what
+ * GMC_MAX_GRAPH_NODES (and, for gmc_kway_*, the LDS bound near n_max = 2400 at K = 8) stands for.  These run the model of
+ * gmc_kway_forward / gmc_kway_train_fwd_bwd - same signatures, K = model->K in 2..GMC_KWAY_MAX_CLASSES with 3 included,
+ * same terminals, both losses (GMC_MODEL_LOSS_EXPECTED in model->flags), same layouts (P [R,K], grad [W1 | b1 | W2 | b2]
+ * plus the tail slot with GMC_MODEL_GRAD_TAIL), same empty-batch behaviour - on graphs of up to GMC_LARGE_MAX_GRAPH_NODES
+ * nodes.  Kernel sequence: that of gmc_kway_* (one kernel per operation on row-major [R, ld] buffers) with the head
+ * replaced by the four row-parallel launches of csrc/large.hip, which several workgroups share per graph: probabilities
+ * and decode; loss terms, dLoss/dP and the softmax backward; the per-graph fold (loss, db2 partials); GY2 (training only).
+ * Each is a GMC_K_HEAD probe record.  Summation orders (csrc/large.hip states them; all fixed, results bitwise
+ * reproducible, and a graph's P, S and loss do not depend on what else is in the batch): a row's neighbours in CSR order
+ * by one lane, a row of more than 64 entries by a wave (lane j takes entries j, j + 64, ..., then a butterfly over the
+ * lanes); the per-graph sums over tiles of 256 rows (wave butterfly, waves ascending), then over the tiles ascending.
+ * So they agree with gmc_kway_* (and at K = 3 with gmc_*) to rounding, not to the bit.
+ * No dropout (dropout_p > 0: GMC_ERR_UNSUPPORTED), W1_slab is not read.  P and model->W2 must be 16-byte aligned.
+ * Argument checks: the order of gmc_kway_*, whose graph-size step here is n_max < K or n_max >
+ * GMC_LARGE_MAX_GRAPH_NODES (no LDS condition).  The workspace is that of gmc_kway_* plus S [R], dinv o GZ [R,K]
+ * (training) and the head's tile partials [R / 256 + B + 1][K + 1]. */
+#define GMC_LARGE_MAX_GRAPH_NODES (1 << 20)
+/* bytes of scratch gmc_large_forward / gmc_large_train_fwd_bwd need (0 for a NULL struct, another abi word, or K outside
+ * 2..GMC_KWAY_MAX_CLASSES) */
+size_t gmc_large_workspace_bytes(const gmc_batch *batch, const gmc_model *model, int training);
+int gmc_large_forward(const gmc_batch *batch, const gmc_model *model, float C, void *workspace, size_t workspace_bytes,
+                      float *P, int32_t *S, float *loss, gmc_stream_t stream);
+int gmc_large_train_fwd_bwd(const gmc_batch *batch, const gmc_model *model, float C, void *workspace,
+                            size_t workspace_bytes, float *P, int32_t *S, float *loss, float *grad, gmc_stream_t stream);
+/* 1 when the model's ordinary entry points - gmc_* at model->K == 3, gmc_kway_* otherwise - would answer
+ * GMC_ERR_GRAPH_SIZE for this batch because n_max is too large (beyond GMC_MAX_GRAPH_NODES, or, for gmc_kway_*, beyond what
+ * the head's LDS tiles take at this K and loss), i.e. when the caller has to use gmc_large_*; 0 otherwise (an empty batch
+ * included).  Negative: GMC_ERR_NULL, GMC_ERR_ABI, GMC_ERR_CLASSES (K outside 2..GMC_KWAY_MAX_CLASSES).  Host only. */
+int gmc_large_required(const gmc_batch *batch, const gmc_model *model);
+
 /* ---- a graph-attention first layer (extension: the first of the "future improvements" of the reference's README) ------
  *
  * The entry points above have GraphConv(norm='both') as layer 1 (TrainingNeural.py:80).  These three replace that layer's
