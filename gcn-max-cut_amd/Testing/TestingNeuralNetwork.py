@@ -146,7 +146,9 @@ def _decoder_graph_size(what: str, nodes: int) -> None:
     if int(nodes) > hip.MAX_GRAPH_NODES:
         raise ValueError(f"{what} is implemented for graphs of up to {hip.MAX_GRAPH_NODES} nodes, got one with {int(nodes)}: "
                          "a larger graph gets the argmax partition (evaluate_model for its loss, "
-                         "simple_partition_assignment on net(g, None) under torch.no_grad() for the assignment)")
+                         "simple_partition_assignment on net(g, None) under torch.no_grad() for the assignment), or "
+                         "the rounding and the local search of large_conditional_rounding, large_local_search and "
+                         "round_large_dataset")
 
 
 def _sample_on_gpu(batch: GraphBatch, P: torch.Tensor, iterations: int, seed: Optional[int] = None, indices=None,
@@ -387,6 +389,88 @@ def conditional_rounding(node_probabilities, graph, descent_sweeps: int = 0) -> 
     probs = probs.detach().to(dev, torch.float32)
     batch = GraphBatch([from_networkx(graph)], None, dev)
     assign, cut, _, _ = _round_on_gpu(batch, probs, descent_sweeps)
+    return assign.cpu().tolist(), _as_number(cut.item())
+
+
+# ---- the rounding and the local search for graphs beyond hip.MAX_GRAPH_NODES nodes (extension) ----------------------
+def _large_workspace(batch: GraphBatch, K: int) -> torch.Tensor:
+    """The scratch of gmc_large_round_conditional_f32 / gmc_large_local_search_f32 (not zeroed: the calls write every
+    word they read)."""
+    need = int(hip.load().gmc_large_round_workspace_bytes(batch.ref(), K))
+    if need <= 0:
+        raise hip.HipExtensionError(f"gmc_large_round_workspace_bytes refused the batch (number_classes = {K})")
+    return torch.empty(need, dtype=torch.uint8, device=batch.device)
+
+
+def _large_round_on_gpu(batch: GraphBatch, P: torch.Tensor, descent_sweeps: int):
+    """:func:`_round_on_gpu` through gmc_large_round_conditional_f32: the same rule with a graph shared by several
+    workgroups, for graphs of up to ``hip.LARGE_MAX_GRAPH_NODES`` nodes; the same four results."""
+    K = _rounding_classes(P.shape[1])
+    if descent_sweeps < 0:
+        raise ValueError(f"descent_sweeps must be >= 0, got {descent_sweeps}")
+    _needs_terminals(batch, K)
+    dev = batch.device
+    assign = torch.empty(batch.R, dtype=torch.int8, device=dev)
+    cut = torch.empty(batch.B, dtype=torch.float32, device=dev)
+    expected = torch.empty(batch.B, dtype=torch.float32, device=dev)
+    sweeps = torch.empty(batch.B, dtype=torch.int32, device=dev)
+    if batch.B == 0:   # nothing to launch (empty tensors have no device pointer to hand over)
+        return assign, cut, expected, sweeps
+    order, cgoff, cptr = batch.refine_order(K)
+    ws = _large_workspace(batch, K)
+    p = hip.ptr
+    rc = hip.load().gmc_large_round_conditional_f32(batch.ref(), p(P.contiguous()), K, p(order), p(cgoff), p(cptr),
+                                                    batch.refine_classes(K), int(descent_sweeps), p(ws), ws.numel(),
+                                                    p(assign), p(cut), p(expected), p(sweeps), hip.stream())
+    hip.check(rc, "gmc_large_round_conditional_f32")
+    return assign, cut, expected, sweeps
+
+
+def large_conditional_rounding(node_probabilities, graph, descent_sweeps: int = 0) -> Tuple[List[int], Any]:
+    """:func:`conditional_rounding` for a graph of any size from number_classes to ``hip.LARGE_MAX_GRAPH_NODES`` nodes
+    (extension, include/gcnmaxcut.h ``gmc_large_round_conditional_f32``): the same rule, arguments and results - on a
+    graph :func:`conditional_rounding` takes, the same assignment - with the graph shared by several workgroups and
+    one launch per colour class.  It issues every launch of ``descent_sweeps`` sweeps whenever the descent converges
+    (a converged graph costs nothing but the launches), so give it the sweeps the descent may need, not a huge bound."""
+    probs = node_probabilities if isinstance(node_probabilities, torch.Tensor) else torch.from_numpy(np.asarray(node_probabilities))
+    if probs.dim() != 2:
+        raise ValueError(f"node_probabilities must be [n, number_classes], got {tuple(probs.shape)}")
+    K = _rounding_classes(probs.shape[1])
+    n = graph.number_of_nodes()
+    if n < K:
+        raise ValueError(f"number_classes = {K}: the graph needs at least {K} nodes (nodes 0..{K - 1} are the "
+                         f"terminals), got {n}")
+    if probs.shape[0] != n:
+        raise ValueError(f"node_probabilities has {probs.shape[0]} rows, the graph {n} nodes")
+    if descent_sweeps < 0:
+        raise ValueError(f"descent_sweeps must be >= 0, got {descent_sweeps}")
+    dev = hip.require_gpu()
+    probs = probs.detach().to(dev, torch.float32)
+    handle = graph if isinstance(graph, GraphHandle) else from_networkx(graph)
+    batch = GraphBatch([handle], None, dev)
+    assign, cut, _, _ = _large_round_on_gpu(batch, probs, descent_sweeps)
+    return assign.cpu().tolist(), _as_number(cut.item())
+
+
+def large_local_search(partition_assignment, graph, number_classes: int, max_sweeps: int = 100) -> Tuple[List[int], Any]:
+    """:func:`kway_local_search` for a graph of any size from number_classes to ``hip.LARGE_MAX_GRAPH_NODES`` nodes
+    (extension, include/gcnmaxcut.h ``gmc_large_local_search_f32``): the same rule, arguments and results - on a graph
+    :func:`kway_local_search` takes, the same assignment - with the graph shared by several workgroups.  Every launch
+    of ``max_sweeps`` sweeps is issued whenever the search converges."""
+    K, part = _kway_partition("large_local_search", partition_assignment, graph, number_classes)
+    if max_sweeps < 0:
+        raise ValueError(f"max_sweeps must be >= 0, got {max_sweeps}")
+    dev = hip.require_gpu()
+    handle = graph if isinstance(graph, GraphHandle) else from_networkx(graph)
+    batch = GraphBatch([handle], None, dev)
+    assign = torch.from_numpy(part.astype(np.int8)).to(dev)
+    cut = torch.empty(1, dtype=torch.float32, device=dev)
+    order, cgoff, cptr = batch.refine_order(K)
+    ws = _large_workspace(batch, K)
+    p = hip.ptr
+    rc = hip.load().gmc_large_local_search_f32(batch.ref(), K, p(order), p(cgoff), p(cptr), batch.refine_classes(K),
+                                               int(max_sweeps), p(ws), ws.numel(), p(assign), p(cut), None, hip.stream())
+    hip.check(rc, "gmc_large_local_search_f32")
     return assign.cpu().tolist(), _as_number(cut.item())
 
 
@@ -748,6 +832,33 @@ def round_dataset(model, processed_graphs: Dict, descent_sweeps: int = 0) -> Lis
     batch = GraphBatch(handles, vals, eng.device)
     P, S, loss = eng.forward(batch, 1.0, want_loss=True)
     assign, cut, expected, sweeps = [t.cpu().numpy() for t in _round_on_gpu(batch, P, descent_sweeps)]
+    S_host, simple = S.cpu().numpy(), (-loss).cpu().tolist()
+    out = []
+    for g in range(len(items)):
+        lo, hi = int(batch.goff_host[g]), int(batch.goff_host[g + 1])
+        out.append({'nodes': hi - lo, 'simple_cut': _as_number(simple[g]), 'simple_assignment': S_host[lo:hi].tolist(),
+                    'expected_cut': float(expected[g]), 'rounded_cut': _as_number(cut[g]),
+                    'rounded_assignment': assign[lo:hi].tolist(), 'descent_sweeps': int(sweeps[g])})
+    return out
+
+
+def round_large_dataset(model, processed_graphs: Dict, descent_sweeps: int = 0) -> List[Dict[str, Any]]:
+    """:func:`round_dataset` for datasets with graphs of any size up to ``hip.LARGE_MAX_GRAPH_NODES`` nodes (extension):
+    ONE batched forward (the engine takes a batch with a graph beyond ``hip.MAX_GRAPH_NODES`` nodes through
+    ``gmc_large_forward``; an ``adjacency="none"`` dataset has no padded adjacency and its edge weights come from the
+    graph) and ONE call of ``gmc_large_round_conditional_f32``.  The keys and, on a dataset :func:`round_dataset`
+    takes, the assignments and sweep counts are :func:`round_dataset`'s."""
+    if descent_sweeps < 0:
+        raise ValueError(f"descent_sweeps must be >= 0, got {descent_sweeps}")
+    items = list(processed_graphs.values())
+    eng = model.engine()
+    _rounding_classes(eng.K)
+    model.eval()
+    handles = [it[0] for it in items]
+    vals = [h.edge_values(it[1]) for h, it in zip(handles, items)]
+    batch = GraphBatch(handles, vals, eng.device)
+    P, S, loss = eng.forward(batch, 1.0, want_loss=True)
+    assign, cut, expected, sweeps = [t.cpu().numpy() for t in _large_round_on_gpu(batch, P, descent_sweeps)]
     S_host, simple = S.cpu().numpy(), (-loss).cpu().tolist()
     out = []
     for g in range(len(items)):

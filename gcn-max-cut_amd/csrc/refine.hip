@@ -79,18 +79,22 @@ __global__ __launch_bounds__(256) void refine_pick_kernel(gmc::PickArgs a) { gmc
 
 // HOST routine (all pointers are host pointers): first-fit colouring of every graph's movable nodes first..n-1 and the
 // (colour, id) order the kernels walk.  cptr_cap < R + B is refused before anything is written.  One body for
-// gmc_refine_order_host (first = 3) and gmc_round_order_host (first = K).
+// gmc_refine_order_host (first = 3), gmc_round_order_host (first = K) and gmc_large_round_order_host (first = K, graphs of
+// up to max_nodes = GMC_LARGE_MAX_GRAPH_NODES nodes).  max_classes (optional): the largest class count of any graph.
 static int order_host(int32_t B, const int32_t *goff, const int32_t *rowptr, const int32_t *lcol, int first,
-                      int32_t *order, int32_t *cgoff, int32_t *cptr, int32_t cptr_cap) {
+                      int max_nodes, int32_t *order, int32_t *cgoff, int32_t *cptr, int32_t cptr_cap,
+                      int32_t *max_classes = nullptr) {
     if (!goff || !rowptr || !lcol || !order || !cgoff || !cptr) return GMC_ERR_NULL;
     if (B < 0) return GMC_ERR_SHAPE;
+    int n_max = 0;
     for (int g = 0; g < B; ++g) {
         const int n = goff[g + 1] - goff[g];
-        if (n < first || n > GMC_MAX_GRAPH_NODES) return GMC_ERR_GRAPH_SIZE;
+        if (n < first || n > max_nodes) return GMC_ERR_GRAPH_SIZE;
+        n_max = n > n_max ? n : n_max;
     }
     if ((long long)cptr_cap < (long long)goff[B] + B) return GMC_ERR_SHAPE;
-    std::vector<int> colour(GMC_MAX_GRAPH_NODES), mark, count;
-    int pos = 0, kp = 0;
+    std::vector<int> colour(n_max), mark, count;
+    int pos = 0, kp = 0, most = 0;
     for (int g = 0; g < B; ++g) {
         const int r0 = goff[g], n = goff[g + 1] - r0;
         int ncol = 0;
@@ -108,6 +112,7 @@ static int order_host(int32_t B, const int32_t *goff, const int32_t *rowptr, con
             }
             colour[v] = c;
         }
+        most = ncol > most ? ncol : most;
         count.assign(ncol, 0);
         for (int v = first; v < n; ++v) ++count[colour[v]];
         cgoff[g] = kp;
@@ -121,12 +126,13 @@ static int order_host(int32_t B, const int32_t *goff, const int32_t *rowptr, con
         for (int v = first; v < n; ++v) order[count[colour[v]]++] = r0 + v;   // increasing id inside each class
     }
     cgoff[B] = kp;
+    if (max_classes) *max_classes = most;
     return GMC_OK;
 }
 
 extern "C" int gmc_refine_order_host(int32_t B, const int32_t *goff, const int32_t *rowptr, const int32_t *lcol,
                                      int32_t *order, int32_t *cgoff, int32_t *cptr, int32_t cptr_cap) {
-    return order_host(B, goff, rowptr, lcol, 3, order, cgoff, cptr, cptr_cap);
+    return order_host(B, goff, rowptr, lcol, 3, GMC_MAX_GRAPH_NODES, order, cgoff, cptr, cptr_cap);
 }
 
 // the same colouring with the movable nodes starting at K: the order gmc_round_conditional_f32 (round.hip) walks
@@ -134,7 +140,16 @@ extern "C" int gmc_round_order_host(int32_t B, const int32_t *goff, const int32_
                                     int32_t K, int32_t *order, int32_t *cgoff, int32_t *cptr, int32_t cptr_cap) {
     if (!goff || !rowptr || !lcol || !order || !cgoff || !cptr) return GMC_ERR_NULL;
     if (K < 2 || K > GMC_KWAY_MAX_CLASSES) return GMC_ERR_CLASSES;
-    return order_host(B, goff, rowptr, lcol, K, order, cgoff, cptr, cptr_cap);
+    return order_host(B, goff, rowptr, lcol, K, GMC_MAX_GRAPH_NODES, order, cgoff, cptr, cptr_cap);
+}
+
+// gmc_round_order_host for graphs of up to GMC_LARGE_MAX_GRAPH_NODES nodes: the order the kernels of large_round.hip walk
+extern "C" int gmc_large_round_order_host(int32_t B, const int32_t *goff, const int32_t *rowptr, const int32_t *lcol,
+                                          int32_t K, int32_t *order, int32_t *cgoff, int32_t *cptr, int32_t cptr_cap,
+                                          int32_t *max_classes) {
+    if (!goff || !rowptr || !lcol || !order || !cgoff || !cptr || !max_classes) return GMC_ERR_NULL;
+    if (K < 2 || K > GMC_KWAY_MAX_CLASSES) return GMC_ERR_CLASSES;
+    return order_host(B, goff, rowptr, lcol, K, GMC_LARGE_MAX_GRAPH_NODES, order, cgoff, cptr, cptr_cap, max_classes);
 }
 
 extern "C" int gmc_refine_local_f32(const gmc_batch *batch, const int32_t *order, const int32_t *cgoff,

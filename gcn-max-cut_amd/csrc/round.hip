@@ -17,12 +17,15 @@
 #include "gmc_common.h"
 #include "cut_body.h"
 #include "move_body.h"
+#include "round_body.h"
 
 namespace {
 
 using gmc::Sums;
 using gmc::class_sums_k;   // the sums over the class bytes and the pick of the smallest: move_body.h
 using gmc::smallest;
+using gmc::state_sums;     // the sums over the state and a row's share of the expected cut: round_body.h
+using gmc::expected_row;
 
 struct RoundArgs {
     gmc_batch b;
@@ -36,50 +39,6 @@ struct RoundArgs {
     float *expected;         // [B] or NULL
     int *sweeps;             // [B] or NULL
 };
-
-// M_k = sum over the edges of local row l, CSR order, self-loops skipped, of w_e * q_u[k], from +0.  Product and sum
-// are rounded separately: hipcc contracts a * b + c into one fused multiply-add unless told not to.
-template <int K>
-__device__ __forceinline__ Sums<K> state_sums(const int *rp, const int *col, const float *vals, const float *q, int l) {
-#pragma clang fp contract(off)
-    Sums<K> s;
-#pragma unroll
-    for (int k = 0; k < K; ++k) s.m[k] = 0.f;
-    const int e1 = rp[l + 1];
-    for (int e = rp[l]; e < e1; ++e) {
-        const int u = col[e];
-        if (u == l) continue;
-        const float w = vals ? vals[e] : 1.0f;
-        const float *qu = q + u * K;
-#pragma unroll
-        for (int k = 0; k < K; ++k) {
-            const float t = w * qu[k];
-            s.m[k] = s.m[k] + t;
-        }
-    }
-    return s;
-}
-
-// the node's share of the expected cut: sum over its edges (self-loops skipped) of w_e * (1 - q_u . q_l)
-template <int K>
-__device__ __forceinline__ float expected_row(const int *rp, const int *col, const float *vals, const float *q, int l) {
-#pragma clang fp contract(off)
-    float ql[K];
-#pragma unroll
-    for (int k = 0; k < K; ++k) ql[k] = q[l * K + k];
-    float acc = 0.f;
-    const int e1 = rp[l + 1];
-    for (int e = rp[l]; e < e1; ++e) {
-        const int u = col[e];
-        if (u == l) continue;
-        const float w = vals ? vals[e] : 1.0f;
-        float dot = 0.f;
-#pragma unroll
-        for (int k = 0; k < K; ++k) dot += q[u * K + k] * ql[k];
-        acc += w * (1.0f - dot);
-    }
-    return acc;
-}
 
 template <int K>
 __global__ __launch_bounds__(256) void round_conditional_kernel(RoundArgs a) {
@@ -102,9 +61,10 @@ __global__ __launch_bounds__(256) void round_conditional_kernel(RoundArgs a) {
     }
     for (int l = threadIdx.x; l < n; l += blockDim.x) cls[l] = (unsigned char)(l < K ? l : 0);
     __syncthreads();
+    const gmc::FloatState<K> state{q};
     if (a.expected) {   // workgroup-uniform
         float acc = 0.f;
-        for (int l = threadIdx.x; l < n; l += blockDim.x) acc += expected_row<K>(rp, col, vals, q, l);
+        for (int l = threadIdx.x; l < n; l += blockDim.x) acc += expected_row<K>(rp, col, vals, state, l);
         acc = gmc::wave_sum(acc);
         if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
         __syncthreads();
@@ -119,7 +79,7 @@ __global__ __launch_bounds__(256) void round_conditional_kernel(RoundArgs a) {
         for (int i = a.cptr[k0 + k] + threadIdx.x; i < hi; i += blockDim.x) {
             const int l = a.order[i] - r0;
             if (l < K || l >= n) continue;   // not a movable row of this graph: never touch LDS for it
-            const Sums<K> s = state_sums<K>(rp, col, vals, q, l);
+            const Sums<K> s = state_sums<K>(rp, col, vals, state, l);
             float wk;
             const int kk = smallest<K>(s, wk);
 #pragma unroll

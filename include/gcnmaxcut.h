@@ -187,7 +187,8 @@ enum {
     GMC_K_DECODE = 13,     /* post-processing sampler + cut count */
     GMC_K_FINISH = 14,     /* fold of the gradient partials (+ fused Adam) over the flat buffer */
     GMC_K_REFINE = 15,     /* local search over decoded candidates + cut count (gmc_refine_local_f32); also the
-                            * rounding by conditional expectations + descent (gmc_round_conditional_f32) */
+                            * rounding by conditional expectations + descent (gmc_round_conditional_f32), and one
+                            * record per call of gmc_large_round_conditional_f32 / gmc_large_local_search_f32 */
     GMC_K_ANNEAL = 16,     /* annealing + descent over decoded candidates + cut count (gmc_refine_anneal_f32,
                             * gmc_kway_refine_anneal_f32) */
     GMC_K_GEMM = 17,       /* dense fp32 GEMM on the matrix cores (gmc_gemm_f32; the dense-feature path) */
@@ -818,6 +819,66 @@ int gmc_kway_refine_anneal_f32(const gmc_batch *batch, int32_t K, const int32_t 
                                int32_t anneal_sweeps, const float *levels, uint64_t seed, int32_t max_descent_sweeps,
                                float *cut_all, int32_t *best_assign, float *best_cut, int32_t *best_idx,
                                int32_t *snap_sweep, int32_t *sweeps, gmc_stream_t stream);
+
+/* ---- the rounding and the K-class local search beyond GMC_MAX_GRAPH_NODES (extension) ---------------------------------
+ *
+ * gmc_round_conditional_f32 and gmc_kway_refine_anneal_f32 keep a graph's state in one workgroup's LDS and stop at
+ * GMC_MAX_GRAPH_NODES.  The entry points below run the same two rules on graphs of K .. GMC_LARGE_MAX_GRAPH_NODES nodes,
+ * a graph shared by several workgroups and its state kept in global memory:
+ *  - gmc_large_round_conditional_f32: steps 1-5 of the gmc_round_conditional_f32 comment above, unchanged;
+ *  - gmc_large_local_search_f32: the descent of gmc_kway_refine_anneal_f32 with anneal_sweeps = 0 on ONE candidate per
+ *    graph (assign [R], in/out), "a byte outside 0..K-1 on a movable node: always moves" included.
+ * Every node's sums are taken by one thread over its CSR row in order by the functions the one-workgroup kernels call, so
+ * on every batch those kernels take as well, for the same sweep limit: assign and sweeps are byte for byte theirs; cut is
+ * bit-equal for unit weights (every partial sum is an integer below 2^24) and agrees to rounding for real weights;
+ * expected agrees to rounding.  All outputs are reproducible run to run, and a graph's outputs do not depend on what
+ * else is in the batch.  What differs:
+ *  - sizes: n_max in K .. GMC_LARGE_MAX_GRAPH_NODES; rows are read by batch row id and neighbours through gcol, so
+ *    batch->gcol is required (a self-loop is gcol[e] == the row);
+ *  - the order arrays: gmc_large_round_order_host's (gmc_round_order_host's on every batch that one accepts), in device
+ *    memory, with max_classes, the largest class count of any graph, which tells the call how many colour launches to
+ *    issue (a larger value costs launches and changes nothing; a smaller one leaves colours unvisited);
+ *  - the workspace: gmc_large_round_workspace_bytes(batch, K) bytes of device memory, 16-byte aligned, NOT assumed
+ *    zeroed (every word read is written by the call first): 3 B + 1 int words (per graph moved / stopped / sweeps run,
+ *    one word "every graph has stopped") and R / 256 + B + 1 float partials, each of the two padded to 16 bytes, then
+ *    R class bytes (0xff: a movable node not rounded yet), padded likewise - about 1.02 bytes per row;
+ *  - the summation order of cut and expected: one partial per row (its edges in CSR order), a tile of 256 rows of the
+ *    graph by a butterfly per wave and the four waves ascending, a graph's tiles ascending, then * 0.5f (the order of
+ *    gmc_large_forward's loss);
+ *  - the launches, all on the caller's stream, kernel boundaries being the only synchronisation between workgroups (no
+ *    atomics, no spin waits): 1 (init) + 2 with expected + max_classes (rounding; none for the local search) +
+ *    max_sweeps * (max_classes + 1) (a launch per colour, one closing the sweep) + 2 (score).  The call does not
+ *    synchronise with the host, so ALL max_sweeps * (max_classes + 1) descent launches are issued whenever the descent
+ *    converges; the threads of a graph that has stopped return at once, and once every graph has stopped a launch
+ *    returns after reading one word.  A caller who knows the descent to be short passes a small max_sweeps.
+ * Argument checks, before any HIP call: a NULL required pointer (workspace included; expected and sweeps may be NULL)
+ * GMC_ERR_NULL, batch->abi GMC_ERR_ABI, a NULL goff / rowptr / lcol / gcol GMC_ERR_NULL, K outside
+ * 2..GMC_KWAY_MAX_CLASSES GMC_ERR_CLASSES, a negative sweep count, max_classes < 0 or B < 0 GMC_ERR_SHAPE, n_max < K or
+ * n_max > GMC_LARGE_MAX_GRAPH_NODES GMC_ERR_GRAPH_SIZE, a workspace below gmc_large_round_workspace_bytes
+ * GMC_ERR_WORKSPACE; B == 0 returns GMC_OK without a launch.  A graph with fewer than K or more than n_max nodes inside
+ * a batch is skipped (nothing of it is written).  The probe shows one GMC_K_REFINE record per call. */
+
+/* HOST routine (all pointers are host pointers): gmc_round_order_host for graphs of up to GMC_LARGE_MAX_GRAPH_NODES nodes
+ * - the same first-fit colouring, arrays and argument checks; on a batch gmc_round_order_host accepts, the same three
+ * arrays, array for array.  max_classes (required: NULL is GMC_ERR_NULL) receives the largest class count of any graph,
+ * 0 for B == 0. */
+int gmc_large_round_order_host(int32_t B, const int32_t *goff, const int32_t *rowptr, const int32_t *lcol, int32_t K,
+                               int32_t *order, int32_t *cgoff, int32_t *cptr, int32_t cptr_cap, int32_t *max_classes);
+
+/* bytes of workspace the two calls below need (0 for a NULL struct, another abi word, K outside 2..8 or negative sizes);
+ * host only, reads B and R */
+size_t gmc_large_round_workspace_bytes(const gmc_batch *batch, int32_t K);
+
+int gmc_large_round_conditional_f32(const gmc_batch *batch, const float *P /*[R,K]*/, int32_t K,
+                                    const int32_t *order, const int32_t *cgoff, const int32_t *cptr, int32_t max_classes,
+                                    int32_t max_descent_sweeps, void *workspace, size_t workspace_bytes,
+                                    int8_t *assign /*[R]*/, float *cut /*[B]*/, float *expected /*[B] or NULL*/,
+                                    int32_t *sweeps /*[B] or NULL*/, gmc_stream_t stream);
+
+int gmc_large_local_search_f32(const gmc_batch *batch, int32_t K, const int32_t *order, const int32_t *cgoff,
+                               const int32_t *cptr, int32_t max_classes, int32_t max_sweeps, void *workspace,
+                               size_t workspace_bytes, int8_t *assign /*[R], in/out: one candidate per graph*/,
+                               float *cut /*[B]*/, int32_t *sweeps /*[B] or NULL*/, gmc_stream_t stream);
 
 #ifdef __cplusplus
 }
