@@ -18,6 +18,11 @@ any ``number_classes`` in 2..8.
 sampler, the local search and the annealing for ``number_classes`` in 2..8 (``gmc_kway_decode_sample_seeded_f32``,
 ``gmc_kway_refine_anneal_f32``); at three classes they return what the 3-class functions return.  Those, and
 ``decode_dataset``, keep refusing any other class count.
+``large_conditional_rounding``, ``large_local_search``, ``round_large_dataset``, ``large_sampling_optimization``,
+``large_annealing`` and ``search_large_dataset`` (extension) are the same rounding, local search, sampler and annealing
+for graphs of up to ``hip.LARGE_MAX_GRAPH_NODES`` nodes (``gmc_large_round_conditional_f32``,
+``gmc_large_local_search_f32``, ``gmc_large_sample_seeded_f32``, ``gmc_large_anneal_f32``): a graph shared by several
+workgroups, its state in a workspace on the device.
 The reporting / plotting half of the reference module (``analyze_results`` .. ``generate_summary_report``,
 :297-638) is presentation code outside the path and is not reproduced.
 """
@@ -148,7 +153,8 @@ def _decoder_graph_size(what: str, nodes: int) -> None:
                          "a larger graph gets the argmax partition (evaluate_model for its loss, "
                          "simple_partition_assignment on net(g, None) under torch.no_grad() for the assignment), or "
                          "the rounding and the local search of large_conditional_rounding, large_local_search and "
-                         "round_large_dataset")
+                         "round_large_dataset, or the sampler and the annealing of large_sampling_optimization, "
+                         "large_annealing and search_large_dataset")
 
 
 def _sample_on_gpu(batch: GraphBatch, P: torch.Tensor, iterations: int, seed: Optional[int] = None, indices=None,
@@ -472,6 +478,118 @@ def large_local_search(partition_assignment, graph, number_classes: int, max_swe
                                                int(max_sweeps), p(ws), ws.numel(), p(assign), p(cut), None, hip.stream())
     hip.check(rc, "gmc_large_local_search_f32")
     return assign.cpu().tolist(), _as_number(cut.item())
+
+
+# ---- the seeded sampler and the annealing for graphs beyond hip.MAX_GRAPH_NODES nodes (extension) -------------------
+def _large_search_workspace(batch: GraphBatch, K: int, cands: int) -> torch.Tensor:
+    """The scratch of gmc_large_sample_seeded_f32 / gmc_large_anneal_f32 for ``cands`` candidates (not zeroed: the
+    calls write every word they read)."""
+    need = int(hip.load().gmc_large_search_workspace_bytes(batch.ref(), K, int(cands)))
+    if need <= 0:
+        raise hip.HipExtensionError(f"gmc_large_search_workspace_bytes refused the batch (number_classes = {K}, "
+                                    f"{int(cands)} candidates)")
+    return torch.empty(need, dtype=torch.uint8, device=batch.device)
+
+
+def _large_sample_on_gpu(batch: GraphBatch, P: torch.Tensor, iterations: int, seed: int, indices, keep_samples: bool,
+                         workspace: Optional[torch.Tensor] = None):
+    """:func:`_kway_sample_on_gpu` through gmc_large_sample_seeded_f32: the same draws with a graph shared by several
+    workgroups, for graphs of up to ``hip.LARGE_MAX_GRAPH_NODES`` nodes; the same four results."""
+    K = _search_classes("the K-class sampler", P.shape[1])
+    _needs_terminals(batch, K)
+    keys = sample_keys(seed, range(batch.B) if indices is None else indices)
+    if keys.size != batch.B:
+        raise ValueError(f"{keys.size} graph indices for a batch of {batch.B} graphs")
+    dev = batch.device
+    gkey = torch.from_numpy(keys.view(np.int64)).to(dev) if batch.B else torch.zeros(1, dtype=torch.int64, device=dev)
+    assign_all = torch.empty((iterations, batch.R), dtype=torch.int8, device=dev) if keep_samples else None
+    cut_all = torch.empty((batch.B, iterations), dtype=torch.float32, device=dev)
+    best_assign = torch.empty(batch.R, dtype=torch.int32, device=dev)
+    best_cut = torch.empty(batch.B, dtype=torch.float32, device=dev)
+    best_iter = torch.empty(batch.B, dtype=torch.int32, device=dev)
+    if batch.B == 0:   # nothing to launch (empty tensors have no device pointer to hand over)
+        return best_assign, best_cut, cut_all, assign_all
+    ws = _large_search_workspace(batch, K, iterations) if workspace is None else workspace
+    p = hip.ptr
+    rc = hip.load().gmc_large_sample_seeded_f32(batch.ref(), p(P.contiguous()), K, p(gkey), iterations, p(assign_all),
+                                                p(ws), ws.numel(), p(cut_all), p(best_assign), p(best_cut),
+                                                p(best_iter), hip.stream())
+    hip.check(rc, "gmc_large_sample_seeded_f32")
+    return best_assign, best_cut, cut_all, assign_all
+
+
+def _large_anneal_on_gpu(batch: GraphBatch, K: int, assign: torch.Tensor, inv_temp: np.ndarray, seed: int,
+                         max_descent_sweeps: int, workspace: Optional[torch.Tensor] = None):
+    """:func:`_kway_anneal_on_gpu` through gmc_large_anneal_f32, for graphs of up to ``hip.LARGE_MAX_GRAPH_NODES``
+    nodes: the candidates assign [cands, R] int8 searched in place; the best assignment [R], its cut and candidate
+    index per graph."""
+    _needs_terminals(batch, K)
+    dev = batch.device
+    cands = int(assign.shape[0])
+    cut_all = torch.empty((batch.B, cands), dtype=torch.float32, device=dev)
+    best_assign = torch.empty(batch.R, dtype=torch.int32, device=dev)
+    best_cut = torch.empty(batch.B, dtype=torch.float32, device=dev)
+    best_idx = torch.empty(batch.B, dtype=torch.int32, device=dev)
+    if batch.B == 0:
+        return best_assign, best_cut, best_idx
+    order, cgoff, cptr = batch.refine_order(K)
+    sweeps = int(len(inv_temp))
+    inv_t = torch.from_numpy(np.ascontiguousarray(inv_temp, np.float32)).to(dev) if sweeps else None
+    levels = torch.from_numpy(anneal_levels()).to(dev) if sweeps else None
+    ws = _large_search_workspace(batch, K, cands) if workspace is None else workspace
+    p = hip.ptr
+    rc = hip.load().gmc_large_anneal_f32(batch.ref(), K, p(order), p(cgoff), p(cptr), batch.refine_classes(K), cands,
+                                         p(assign), p(inv_t), sweeps, p(levels), int(seed) & _M64,
+                                         int(max_descent_sweeps), p(ws), ws.numel(), p(cut_all), p(best_assign),
+                                         p(best_cut), p(best_idx), None, None, hip.stream())
+    hip.check(rc, "gmc_large_anneal_f32")
+    return best_assign, best_cut, best_idx
+
+
+def large_sampling_optimization(node_probabilities, graph, iterations: int = 200, *, seed: int = 0,
+                                graph_index: int = 0) -> Tuple[List[int], Any]:
+    """:func:`sampling_optimization` for a graph of any size from number_classes to ``hip.LARGE_MAX_GRAPH_NODES`` nodes
+    (extension, include/gcnmaxcut.h ``gmc_large_sample_seeded_f32``): the same draws, arguments and results - on a
+    graph :func:`sampling_optimization` takes, the same assignment - with the graph shared by several workgroups.  The
+    samples live on the device while they are scored: about ``iterations`` bytes per node."""
+    probs = node_probabilities if isinstance(node_probabilities, torch.Tensor) else torch.from_numpy(np.asarray(node_probabilities))
+    if probs.dim() != 2:
+        raise ValueError(f"node_probabilities must be [n, number_classes], got {tuple(probs.shape)}")
+    K = _search_classes("large_sampling_optimization", probs.shape[1])
+    n = graph.number_of_nodes()
+    if n < K:
+        raise ValueError(f"number_classes = {K}: the graph needs at least {K} nodes (nodes 0..{K - 1} are the "
+                         f"terminals), got {n}")
+    if probs.shape[0] != n:
+        raise ValueError(f"node_probabilities has {probs.shape[0]} rows, the graph {n} nodes")
+    dev = hip.require_gpu()
+    probs = probs.detach().to(dev, torch.float32)
+    if iterations <= 0:
+        return None, -float('inf')
+    handle = graph if isinstance(graph, GraphHandle) else from_networkx(graph)
+    batch = GraphBatch([handle], None, dev)
+    best_assign, best_cut, _, _ = _large_sample_on_gpu(batch, probs, iterations, int(seed) & _M64, [graph_index],
+                                                       keep_samples=False)
+    return best_assign.cpu().tolist(), _as_number(best_cut.item())
+
+
+def large_annealing(partition_assignment, graph, number_classes: int, sweeps: int = 100, t_start: float = 1.5,
+                    t_end: float = 0.15, seed: int = 0, max_descent_sweeps: int = 100) -> Tuple[List[int], Any]:
+    """:func:`kway_annealing` for a graph of any size from number_classes to ``hip.LARGE_MAX_GRAPH_NODES`` nodes
+    (extension, include/gcnmaxcut.h ``gmc_large_anneal_f32``): the same rule, arguments and results - on a graph
+    :func:`kway_annealing` takes with unit or integer weights, the same assignment - with the graph shared by several
+    workgroups and one launch per colour class.  Every launch of ``sweeps`` annealing and ``max_descent_sweeps`` descent
+    sweeps is issued whenever the descent converges, so give the descent the sweeps it may need, not a huge bound."""
+    K, part = _kway_partition("large_annealing", partition_assignment, graph, number_classes)
+    if sweeps < 0 or max_descent_sweeps < 0:
+        raise ValueError(f"sweeps and max_descent_sweeps must be >= 0, got {sweeps} and {max_descent_sweeps}")
+    dev = hip.require_gpu()
+    handle = graph if isinstance(graph, GraphHandle) else from_networkx(graph)
+    batch = GraphBatch([handle], None, dev)
+    assign = torch.from_numpy(part.astype(np.int8)).to(dev).reshape(1, -1)
+    inv_temp = anneal_schedule(sweeps, t_start, t_end, _mean_edge_weight(batch))
+    best_assign, best_cut, _ = _large_anneal_on_gpu(batch, K, assign, inv_temp, seed, max_descent_sweeps)
+    return best_assign.cpu().tolist(), _as_number(best_cut.item())
 
 
 # ---- the seeded sampler, the local search and the annealing for number_classes K in 2..8 (extension) -----------------
@@ -912,6 +1030,71 @@ def search_dataset(model, processed_graphs: Dict, samples: int = 200, *, sample_
     inv_temp = anneal_schedule(anneal_sweeps, scale=_mean_edge_weight(batch))
     found_assign, found_cut, found_idx = [t.cpu().numpy() for t in
                                           _kway_anneal_on_gpu(batch, K, cands, inv_temp, anneal_seed, max_descent_sweeps)]
+    S_host, simple = S.cpu().numpy(), (-loss).cpu().tolist()
+    rnd_assign, rnd_cut, rnd_expected = rnd_assign.cpu().numpy(), rnd_cut.cpu().numpy(), rnd_expected.cpu().numpy()
+    out = []
+    for g in range(len(items)):
+        lo, hi = int(batch.goff_host[g]), int(batch.goff_host[g + 1])
+        out.append({'nodes': hi - lo, 'simple_cut': _as_number(simple[g]), 'simple_assignment': S_host[lo:hi].tolist(),
+                    'expected_cut': float(rnd_expected[g]), 'rounded_cut': _as_number(rnd_cut[g]),
+                    'rounded_assignment': rnd_assign[lo:hi].tolist()})
+        if sampled is not None:
+            out[-1].update({'post_cut': _as_number(sampled[1][g]), 'post_assignment': sampled[0][lo:hi].tolist()})
+        out[-1].update({'searched_cut': _as_number(found_cut[g]), 'searched_assignment': found_assign[lo:hi].tolist(),
+                        'searched_from': int(found_idx[g])})
+    return out
+
+
+def search_large_dataset(model, processed_graphs: Dict, samples: int = 200, *, sample_seed: int = 0,
+                         anneal_sweeps: int = 100, anneal_seed: int = 0, max_descent_sweeps: int = 100,
+                         candidates: Optional[int] = None) -> List[Dict[str, Any]]:
+    """:func:`search_dataset` for datasets with graphs of any size up to ``hip.LARGE_MAX_GRAPH_NODES`` nodes
+    (extension): ONE batched forward (the engine takes a batch with a graph beyond ``hip.MAX_GRAPH_NODES`` nodes
+    through ``gmc_large_forward``; an ``adjacency="none"`` dataset has no padded adjacency and its edge weights come
+    from the graph), ONE ``gmc_large_round_conditional_f32`` at descent 0, ONE ``gmc_large_sample_seeded_f32`` and ONE
+    ``gmc_large_anneal_f32``.  Arguments, candidates (0 the argmax, 1 the rounded partition, 2.. the samples) and keys
+    are :func:`search_dataset`'s; on a dataset that function takes, with unit or integer weights, so is every value.
+    ``searched_cut`` is never below ``rounded_cut`` when the rounded partition is among the candidates.
+
+    Memory on the device, R the nodes of the dataset: the candidates and the samples, ``candidates + samples`` bytes
+    per node, and the workspace of the search, about ``2.02 * cpad`` bytes per node, ``cpad`` the larger of
+    ``candidates`` and ``samples`` rounded up to a multiple of ``cp = min(64, its next power of two)`` - about
+    ``(candidates + samples + 2 * cpad) * R`` bytes in all (200 samples, all of them candidates: 0.9 GiB per million
+    nodes; 8 samples: 50 MiB).  The calls issue ``anneal_sweeps * (classes + 3) +
+    max_descent_sweeps * (classes + 1)`` launches and more (``classes`` the colour classes of the batch, see the
+    header), whenever the descent converges: give ``max_descent_sweeps`` the sweeps the descent may need."""
+    if samples < 0:
+        raise ValueError(f"samples must be >= 0, got {samples}")
+    if anneal_sweeps < 0 or max_descent_sweeps < 0:
+        raise ValueError(f"anneal_sweeps and max_descent_sweeps must be >= 0, got {anneal_sweeps} and {max_descent_sweeps}")
+    take = 2 + samples if candidates is None else int(candidates)
+    if not 1 <= take <= 2 + samples:
+        raise ValueError(f"candidates must be in 1..{2 + samples}, got {candidates}")
+    items = list(processed_graphs.values())
+    eng = model.engine()
+    K = _search_classes("search_large_dataset", eng.K)
+    model.eval()
+    handles = [it[0] for it in items]
+    vals = [h.edge_values(it[1]) for h, it in zip(handles, items)]
+    batch = GraphBatch(handles, vals, eng.device)
+    _needs_terminals(batch, K)
+    P, S, loss = eng.forward(batch, 1.0, want_loss=True)
+    rnd_assign, rnd_cut, rnd_expected, _ = _large_round_on_gpu(batch, P, 0)
+    rows = [S.to(torch.int8).reshape(1, -1), rnd_assign.reshape(1, -1)]
+    ws = _large_search_workspace(batch, K, max(take, samples)) if batch.B else None   # one scratch for both calls
+    sampled = None
+    if samples > 0:
+        best_assign, best_cut, _, assign_all = _large_sample_on_gpu(batch, P, samples, int(sample_seed) & _M64,
+                                                                    range(len(items)), keep_samples=take > 2,
+                                                                    workspace=ws)
+        sampled = (best_assign.cpu().numpy(), best_cut.cpu().tolist())
+        if assign_all is not None:
+            rows.append(assign_all)
+    cands = torch.cat(rows)[:take].contiguous()
+    inv_temp = anneal_schedule(anneal_sweeps, scale=_mean_edge_weight(batch))
+    found_assign, found_cut, found_idx = [t.cpu().numpy() for t in
+                                          _large_anneal_on_gpu(batch, K, cands, inv_temp, anneal_seed,
+                                                               max_descent_sweeps, workspace=ws)]
     S_host, simple = S.cpu().numpy(), (-loss).cpu().tolist()
     rnd_assign, rnd_cut, rnd_expected = rnd_assign.cpu().numpy(), rnd_cut.cpu().numpy(), rnd_expected.cpu().numpy()
     out = []

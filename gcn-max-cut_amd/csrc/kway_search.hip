@@ -6,7 +6,7 @@
 // K is a template argument, one 256-thread workgroup per (candidate, graph) as in those files.
 //
 // Sampler: the class bytes of a sample in n_max bytes of LDS, the cut by gmc::block_cut, the pick kernel regenerates
-// the winner from the hash.  The running sum of a row's probabilities lives in one register: the loop over the
+// the winner from the hash.  The draw is draw_body.h's (large_search.hip draws with it too).  The running sum of a row's probabilities lives in one register: the loop over the
 // constant K is unrolled and stops comparing after the first class that takes the draw.
 //
 // Annealing: the LDS layout of anneal.hip (anneal_layout.h: level table, state and best bytes, and the staged copy of
@@ -15,13 +15,16 @@
 // accessor paths run one templated body.
 #include "gmc_common.h"
 #include "cut_body.h"
+#include "draw_body.h"
 #include "mix64.h"
 #include "move_body.h"
 #include "anneal_layout.h"
 
 namespace {
 
+using gmc::iteration_base;
 using gmc::mix64;
+using gmc::seeded_class_k;
 using gmc::u64;
 using gmc::AnnealArgs;
 using gmc::AnnealLayout;
@@ -42,30 +45,6 @@ struct KSeededArgs {
     float *best_cut;         // [B]
     int *best_iter;          // [B]
 };
-
-// key + GOLD * (((u64)it << 32 | l) + 1) without the node: l < 2^32 only adds GOLD * l
-__device__ __forceinline__ u64 iteration_base(u64 key, int it) {
-    return key + GMC_GOLD * (((u64)(unsigned)it << 32) + 1ULL);
-}
-
-// class of local node l >= K with probabilities p[0..K-1]: the first class j in 0..K-2 whose running double sum
-// exceeds the hashed uniform, class K-1 otherwise (no compare against the last sum: a NaN row gives K-1)
-template <int K>
-__device__ __forceinline__ int seeded_class_k(u64 base, int l, const float *p) {
-    const u64 h = mix64(base + GMC_GOLD * (u64)(unsigned)l);
-    const double r = (double)(h >> 11) * 0x1.0p-53;   // [0, 1), exact
-    double c = (double)p[0];
-    int cls = K - 1;
-    bool open = true;   // no class has taken the draw yet
-#pragma unroll
-    for (int j = 0; j < K - 1; ++j) {
-        if (j > 0) c = c + (double)p[j];
-        const bool take = open && r < c;
-        cls = take ? j : cls;
-        open = open && !take;
-    }
-    return cls;
-}
 
 template <int K>
 __global__ __launch_bounds__(256) void sample_seeded_k_kernel(KSeededArgs a) {
@@ -145,17 +124,9 @@ __device__ __forceinline__ void anneal_body_k(const AnnealArgs &a, const G &g, u
                     const int l = g.node(i);
                     if (l < K || l >= n) continue;   // not a movable row of this graph: never touch LDS for it
                     const Sums<K> w = gmc::class_sums_k<K>(g.rp, g.col, g.vals, sa, l);
-                    const int c = sa[l];
-                    // a byte of no class equals no k: own sum +inf, the smallest of all K sums as the target, taken
-                    // unconditionally (delta = 0 - inf); no branch, so the sums stay in registers
-                    const bool has_class = (unsigned)c < (unsigned)K;
-                    const float wc = gmc::own_sum_or_inf<K>(w, c);
-                    float wk;
-                    const int kk = gmc::smallest_other<K>(w, c, wk);
-                    wk = has_class ? wk : 0.f;
-                    const float delta = wk - wc;
                     const u64 h = mix64(base + GMC_GOLD * (u64)(unsigned)l);
-                    if (delta < 0.f || delta * inv_t <= lv[h >> 54]) sa[l] = (unsigned char)kk;
+                    int kk;
+                    if (gmc::anneal_move<K>(w, sa[l], inv_t, lv, h, kk)) sa[l] = (unsigned char)kk;
                 }
                 __syncthreads();   // the next class, or the recount, reads what this one wrote
             }

@@ -45,10 +45,11 @@ struct Sums {
 
 // class_sums at K classes: W_k = sum of the weights of the edges of local row l to neighbours of class k, fp32, in the
 // CSR order of the row, self-loops skipped, a class byte outside 0..K-1 adding to none (K = 3: class_sums, the same
-// operations in the same order)
-template <int K, class RP, class COL>
-__device__ __forceinline__ Sums<K> class_sums_k(const RP *rp, const COL *col, const float *vals,
-                                                const unsigned char *cls, int l) {
+// operations in the same order).  cls[u] is the class byte of node u: a pointer, or a view with an operator[]
+// (large_search.hip keeps the bytes of one candidate a stride apart).
+template <int K, class RP, class COL, class CLS>
+__device__ __forceinline__ Sums<K> class_sums_k(const RP *rp, const COL *col, const float *vals, const CLS &cls,
+                                                int l) {
     Sums<K> s;
 #pragma unroll
     for (int k = 0; k < K; ++k) s.m[k] = 0.f;
@@ -94,6 +95,22 @@ __device__ __forceinline__ int smallest_other(const Sums<K> &s, int c, float &wk
     for (int k = 1; k < K; ++k)
         if (k != c && s.m[k] < wk) { kk = k; wk = s.m[k]; }
     return kk;
+}
+
+// One annealing visit of a node with sums w and class byte c (gmc_kway_refine_anneal_f32's rule): kk = the class of the
+// smallest sum among the classes other than c; true iff the node moves there, i.e. delta = W[kk] - W[c] < 0 or
+// delta * inv_t <= lv[h >> 54], h the node's hash.  A byte of no class equals no k: own sum +inf, the smallest of all K
+// sums as the target, taken unconditionally (delta = 0 - inf); no branch, so the sums stay in registers.
+template <int K>
+__device__ __forceinline__ bool anneal_move(const Sums<K> &w, int c, float inv_t, const float *lv,
+                                            unsigned long long h, int &kk) {
+    const bool has_class = (unsigned)c < (unsigned)K;
+    const float wc = own_sum_or_inf<K>(w, c);
+    float wk;
+    kk = smallest_other<K>(w, c, wk);
+    wk = has_class ? wk : 0.f;
+    const float delta = wk - wc;
+    return delta < 0.f || delta * inv_t <= lv[h >> 54];
 }
 
 }  // namespace gmc

@@ -17,7 +17,7 @@ LIB_PATH = os.environ.get("GCN_MAXCUT_LIB") or os.path.join(_PKG, "lib", "libgcn
 
 MAX_GRAPH_NODES = 4096
 # GMC_LARGE_MAX_GRAPH_NODES: what a graph of a batch may have (gmc_large_*: several workgroups share a graph's head); the
-# fused, K-class and attention sequences, the decoders and the cut_loss op stay at MAX_GRAPH_NODES
+# fused, K-class and attention sequences, the one-workgroup decoders and the cut_loss op stay at MAX_GRAPH_NODES
 LARGE_MAX_GRAPH_NODES = 1 << 20
 ANNEAL_LEVELS = 1024  # GMC_ANNEAL_LEVELS: entries of the level table gmc_refine_anneal_f32 reads
 MODEL_GRAD_TAIL = 1   # gmc_model.flags: grad has a tail slot that receives the batch's loss sum
@@ -157,6 +157,10 @@ def _api() -> dict:
         "gmc_large_round_workspace_bytes": (sz, [B, i32]),
         "gmc_large_round_conditional_f32": (i, [B, vp, i32, vp, vp, vp, i32, i32, vp, sz, vp, vp, vp, vp, vp]),
         "gmc_large_local_search_f32": (i, [B, i32, vp, vp, vp, i32, i32, vp, sz, vp, vp, vp, vp]),
+        "gmc_large_search_workspace_bytes": (sz, [B, i32, i32]),
+        "gmc_large_sample_seeded_f32": (i, [B, vp, i32, vp, i32, vp, vp, sz, vp, vp, vp, vp, vp]),
+        "gmc_large_anneal_f32": (i, [B, i32, vp, vp, vp, i32, i32, vp, vp, i32, vp, C.c_uint64, i32, vp, sz, vp, vp, vp,
+                                     vp, vp, vp, vp]),
     }
 
 

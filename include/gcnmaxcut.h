@@ -188,12 +188,13 @@ enum {
     GMC_K_FINISH = 14,     /* fold of the gradient partials (+ fused Adam) over the flat buffer */
     GMC_K_REFINE = 15,     /* local search over decoded candidates + cut count (gmc_refine_local_f32); also the
                             * rounding by conditional expectations + descent (gmc_round_conditional_f32), and one
-                            * record per call of gmc_large_round_conditional_f32 / gmc_large_local_search_f32 */
+                            * record per call of gmc_large_round_conditional_f32 / gmc_large_local_search_f32 /
+                            * gmc_large_anneal_f32 */
     GMC_K_ANNEAL = 16,     /* annealing + descent over decoded candidates + cut count (gmc_refine_anneal_f32,
                             * gmc_kway_refine_anneal_f32) */
     GMC_K_GEMM = 17,       /* dense fp32 GEMM on the matrix cores (gmc_gemm_f32; the dense-feature path) */
     GMC_K_SAMPLE = 18,     /* seeded post-processing sampler + cut count (gmc_decode_sample_seeded_f32,
-                            * gmc_kway_decode_sample_seeded_f32) */
+                            * gmc_kway_decode_sample_seeded_f32; one record per call of gmc_large_sample_seeded_f32) */
     GMC_K_COUNT = 19
 };
 
@@ -879,6 +880,85 @@ int gmc_large_local_search_f32(const gmc_batch *batch, int32_t K, const int32_t 
                                const int32_t *cptr, int32_t max_classes, int32_t max_sweeps, void *workspace,
                                size_t workspace_bytes, int8_t *assign /*[R], in/out: one candidate per graph*/,
                                float *cut /*[B]*/, int32_t *sweeps /*[B] or NULL*/, gmc_stream_t stream);
+
+/* ---- the seeded sampler and the annealing beyond GMC_MAX_GRAPH_NODES (extension) ---------------------------------------
+ *
+ * gmc_kway_decode_sample_seeded_f32 and gmc_kway_refine_anneal_f32 keep a graph's class bytes in one workgroup's LDS.
+ * The two entry points below run the same rules at K = 2 .. GMC_KWAY_MAX_CLASSES on graphs of K ..
+ * GMC_LARGE_MAX_GRAPH_NODES nodes, in the manner of gmc_large_round_conditional_f32: a graph shared by several workgroups,
+ * the state in a caller-owned workspace that is NOT assumed zeroed (every word read is written by the call first), kernel
+ * boundaries the only synchronisation between workgroups (no atomics, no spin waits), rows read by batch row id and
+ * neighbours through gcol (batch->gcol is required), the order arrays and max_classes those of
+ * gmc_large_round_order_host in device memory.  All outputs are reproducible run to run and a graph's outputs do not
+ * depend on what else is in the batch.
+ *
+ * gmc_large_anneal_f32: steps 1-4 of gmc_kway_refine_anneal_f32 per (candidate, graph), unchanged - the initial score,
+ * anneal_sweeps sweeps over the colour classes with that comment's move test, after each sweep a recount and a snapshot
+ * on a strictly larger cut, the descent from the snapshot until a sweep moves nothing or max_descent_sweeps have run (the
+ * stop is kept per (candidate, graph)), then score and pick.  A node's sums are taken by one thread over its CSR row in
+ * order by the functions the one-workgroup kernel calls; the unconditional move of a byte outside 0..K-1 is included.
+ *  - The counter of the move test is chosen per graph from its own node count n, so a candidate's result depends on its
+ *    graph alone:
+ *        n <= GMC_MAX_GRAPH_NODES:  ctr = (uint64)cand << 32 | (uint64)s << 12 | v     (gmc_kway_refine_anneal_f32's)
+ *        n >  GMC_MAX_GRAPH_NODES:  ctr = (uint64)cand << 40 | (uint64)s << 20 | v     (v < 2^20, s < 2^20, cand < 2^24)
+ *    With the first layout beyond 4096 nodes, node v of sweep s would share its hash with node v - 4096 of sweep s + 1.
+ *    anneal_sweeps >= 2^20 is GMC_ERR_SHAPE as before; cands >= 2^24 with n_max > GMC_MAX_GRAPH_NODES is GMC_ERR_SHAPE.
+ *  - The summation order of every cut (the initial score, each sweep's recount, the final score) is
+ *    gmc_large_round_conditional_f32's: one partial per row (its edges in CSR order), a tile of 256 rows of the graph by
+ *    a butterfly per wave and the four waves ascending, a graph's tiles ascending, then * 0.5f.  Snapshot decisions
+ *    compare these floats.  For unit and integer weights every partial is an integer below 2^24, so on every batch
+ *    gmc_kway_refine_anneal_f32 takes as well assign, cut_all, best_*, snap_sweep and sweeps are byte for byte that
+ *    call's.  For other weights cut_all agrees to rounding and a near-tie between a sweep's cut and the snapshot's may be
+ *    decided differently.  With anneal_sweeps = 0 no cut is compared: each candidate's assignment and sweep count are
+ *    gmc_large_local_search_f32's on that candidate alone, for any weights.
+ *  - Launches, all on the caller's stream:
+ *        5 + [anneal_sweeps > 0] * (2 + anneal_sweeps * (max_classes + 3)) + max_descent_sweeps * (max_classes + 1)
+ *    (init; the first recount and fold; per annealing sweep a launch per colour, recount, fold, snapshot; per descent
+ *    sweep a launch per colour and one closing it; score, fold, pick, copy).  The number never depends on data: as in
+ *    gmc_large_round_conditional_f32 every descent launch is issued, the lanes of a (candidate, graph) that has stopped
+ *    return at once, and once all have stopped a launch returns after reading one word.
+ *  - Arguments and outputs are gmc_kway_refine_anneal_f32's (assign [cands][R] int8 in/out, cut_all [B][cands],
+ *    best_assign [R] int32, best_cut [B], best_idx [B], optional snap_sweep / sweeps [B][cands]) plus max_classes and
+ *    the workspace.  Argument checks, before any HIP call: a NULL required pointer (workspace included) GMC_ERR_NULL,
+ *    batch->abi GMC_ERR_ABI, a NULL goff / rowptr / lcol / gcol GMC_ERR_NULL, K outside 2..GMC_KWAY_MAX_CLASSES
+ *    GMC_ERR_CLASSES, cands < 1, a negative sweep count, anneal_sweeps >= 2^20, max_classes < 0, B < 0 or the cands bound
+ *    above GMC_ERR_SHAPE, anneal_sweeps > 0 with a NULL inv_temp or levels GMC_ERR_NULL, n_max outside
+ *    K..GMC_LARGE_MAX_GRAPH_NODES GMC_ERR_GRAPH_SIZE, a workspace below gmc_large_search_workspace_bytes(batch, K, cands)
+ *    GMC_ERR_WORKSPACE; B == 0 returns GMC_OK without a launch.  A graph with fewer than K or more than n_max nodes
+ *    inside a batch is skipped (nothing of it is written).  The probe shows one GMC_K_REFINE record per call.
+ *
+ * gmc_large_sample_seeded_f32: the K-class draw rule above, unchanged ((u64)it << 32 | l has room for 2^20 local ids), so
+ * a graph's samples depend on its key alone and are gmc_kway_decode_sample_seeded_f32's.  Outputs as that call's; the
+ * draws go to assign_all [iters][R] when it is given and live in the workspace either way; cut_all in the summation
+ * order above (bit-equal to that call's for unit and integer weights); the pick is the strictly best sample, the first on
+ * ties, and best_assign is regenerated from the hash.  Five launches.  Argument checks: a NULL pointer (assign_all
+ * aside, workspace included) GMC_ERR_NULL, batch->abi GMC_ERR_ABI, a NULL goff / rowptr / lcol / gcol GMC_ERR_NULL, K
+ * GMC_ERR_CLASSES, iters < 1 or B < 0 GMC_ERR_SHAPE, n_max outside K..GMC_LARGE_MAX_GRAPH_NODES GMC_ERR_GRAPH_SIZE, a
+ * workspace below gmc_large_search_workspace_bytes(batch, K, iters) GMC_ERR_WORKSPACE; B == 0 returns GMC_OK without a
+ * launch; graphs outside K..n_max nodes are skipped.  The probe shows one GMC_K_SAMPLE record per call.
+ *
+ * The workspace, 16-byte aligned device memory, with cp = min(64, the next power of two >= cands) and cpad = cands
+ * rounded up to a multiple of cp: 5 B cands + 1 int words (per (graph, candidate) moved / stopped / sweeps run / snapshot
+ * sweep / "take a snapshot", one word "all have stopped"), B cands floats (the snapshot's cut), (R / 256 + B + 1) cpad
+ * float partials, each of the three padded to 16 bytes, then twice cpad R class bytes (state and snapshot, row by row
+ * the cp candidates of a chunk side by side), padded likewise: about 2.02 cpad bytes per row. */
+
+/* bytes of workspace the two calls below need for `cands` candidates (the sampler: iterations); 0 for a NULL struct,
+ * another abi word, K outside 2..8, cands < 1 or negative sizes; host only, reads B and R */
+size_t gmc_large_search_workspace_bytes(const gmc_batch *batch, int32_t K, int32_t cands);
+
+int gmc_large_sample_seeded_f32(const gmc_batch *batch, const float *P /*[R,K]*/, int32_t K, const uint64_t *gkey,
+                                int32_t iters, int8_t *assign_all /*[iters][R] or NULL*/, void *workspace,
+                                size_t workspace_bytes, float *cut_all /*[B][iters]*/, int32_t *best_assign /*[R]*/,
+                                float *best_cut /*[B]*/, int32_t *best_iter /*[B]*/, gmc_stream_t stream);
+
+int gmc_large_anneal_f32(const gmc_batch *batch, int32_t K, const int32_t *order, const int32_t *cgoff,
+                         const int32_t *cptr, int32_t max_classes, int32_t cands, int8_t *assign /*[cands][R], in/out*/,
+                         const float *inv_temp, int32_t anneal_sweeps, const float *levels, uint64_t seed,
+                         int32_t max_descent_sweeps, void *workspace, size_t workspace_bytes,
+                         float *cut_all /*[B][cands]*/, int32_t *best_assign /*[R]*/, float *best_cut /*[B]*/,
+                         int32_t *best_idx /*[B]*/, int32_t *snap_sweep /*or NULL*/, int32_t *sweeps /*or NULL*/,
+                         gmc_stream_t stream);
 
 #ifdef __cplusplus
 }
