@@ -11,6 +11,7 @@ import torch
 from oracle import c_oracle as CO
 from oracle import ref_dense as R
 from tests import stepcheck, util
+from tests.util import _slab_of
 
 pytestmark = pytest.mark.gpu
 
@@ -1044,14 +1045,6 @@ def test_bench_dump_outputs_of_the_last_timed_step(pkg, tmp_path):
     assert set(np.unique(S)) <= {0.0, 1.0, 2.0}
     assert a["param.conv1.weight"].shape == a["grad.conv1.weight"].shape == (1000, 500)
     assert a["param.conv2.weight"].shape == (500, 3) and a["param.conv2.bias"].shape == (3,)
-
-
-def _slab_of(W1: np.ndarray) -> np.ndarray:
-    """gmc_model.W1_slab: [ceil(F/16)][N][16], pad columns zero."""
-    N, F = W1.shape
-    pad = np.zeros((N, (F + 15) // 16 * 16), np.float32)
-    pad[:, :F] = W1
-    return pad.reshape(N, -1, 16).transpose(1, 0, 2).copy()
 
 
 @pytest.mark.parametrize("hidden,gps", [(500, 2), (72, 2), (72, 1)])      # 72 = 4.5 slabs: a partly padded last slab;

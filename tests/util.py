@@ -125,6 +125,14 @@ def poison(eng, batch, grad=True):
         eng.grad.fill_(float("nan"))
 
 
+def _slab_of(W1: np.ndarray) -> np.ndarray:
+    """gmc_model.W1_slab: [ceil(F/16)][N][16], pad columns zero."""
+    N, F = W1.shape
+    pad = np.zeros((N, (F + 15) // 16 * 16), np.float32)
+    pad[:, :F] = W1
+    return pad.reshape(N, -1, 16).transpose(1, 0, 2).copy()
+
+
 # ---- the dropout mask of csrc/dropout.hip restated: splitmix64 of (seed, batch row, column), 24-bit uniform in float32
 _U64 = np.uint64
 
