@@ -18,6 +18,8 @@ any ``number_classes`` in 2..8.
 sampler, the local search and the annealing for ``number_classes`` in 2..8 (``gmc_kway_decode_sample_seeded_f32``,
 ``gmc_kway_refine_anneal_f32``); at three classes they return what the 3-class functions return.  Those, and
 ``decode_dataset``, keep refusing any other class count.
+``kway_evolution`` and ``search_dataset(..., generations=G)`` (extension) recombine the annealed candidates of a graph
+across generations (``gmc_kway_evolve_f32``): children of two class-aligned parents, annealed and kept when no worse.
 ``large_conditional_rounding``, ``large_local_search``, ``round_large_dataset``, ``large_sampling_optimization``,
 ``large_annealing`` and ``search_large_dataset`` (extension) are the same rounding, local search, sampler and annealing
 for graphs of up to ``hip.LARGE_MAX_GRAPH_NODES`` nodes (``gmc_large_round_conditional_f32``,
@@ -754,6 +756,90 @@ def kway_annealing(partition_assignment, graph, number_classes: int, sweeps: int
     return best_assign.cpu().tolist(), _as_number(best_cut.item())
 
 
+# The evolution stage's defaults are PROVISIONAL: 10 generations of 10 sweeps cooling from 0.6
+# are a starting point nobody has measured yet, not the outcome of the sweep described there.
+EVOLVE_GENERATIONS = 10
+EVOLVE_GENERATION_SWEEPS = 10
+EVOLVE_T_START = 0.6
+
+
+def _evolve_arguments(what: str, cands: int, generations: int, generation_sweeps: int, elite: Optional[int],
+                      max_descent_sweeps: int) -> int:
+    """The checks the evolution's callers share; returns the elite count (``None``: ``max(2, cands // 4)``)."""
+    if generations < 0 or generation_sweeps < 0 or max_descent_sweeps < 0:
+        raise ValueError(f"{what}: generations, generation_sweeps and max_descent_sweeps must be >= 0, got "
+                         f"{generations}, {generation_sweeps} and {max_descent_sweeps}")
+    if generations >= 1 << 20 or generation_sweeps >= 1 << 20:
+        raise ValueError(f"{what}: generations and generation_sweeps must be below 2^20")
+    elite = max(2, cands // 4) if elite is None else int(elite)
+    if elite < 1:
+        raise ValueError(f"{what}: elite must be >= 1, got {elite}")
+    return elite
+
+
+def _kway_evolve_on_gpu(batch: GraphBatch, K: int, population: torch.Tensor, generations: int, elite: int,
+                        inv_temp: np.ndarray, seed: int, max_descent_sweeps: int):
+    """The evolution stage (gmc_kway_evolve_f32) over the population [cands, R] int8, which is left alone; returns the
+    best assignment [R], its cut and slot per graph, the best cut per generation [generations + 1, B] and the two
+    planes of the population and of its cuts."""
+    _needs_terminals(batch, K)
+    dev = batch.device
+    cands = int(population.shape[0])
+    order, cgoff, cptr = batch.refine_order(K)
+    sweeps = int(len(inv_temp))
+    inv_t = torch.from_numpy(np.ascontiguousarray(inv_temp, np.float32)).to(dev) if sweeps else None
+    levels = torch.from_numpy(anneal_levels()).to(dev) if sweeps else None
+    pop = torch.empty((2, cands, batch.R), dtype=torch.int8, device=dev)
+    pop[0].copy_(population)
+    cut = torch.empty((2, batch.B, cands), dtype=torch.float32, device=dev)
+    best_assign = torch.empty(batch.R, dtype=torch.int32, device=dev)
+    best_cut = torch.empty(batch.B, dtype=torch.float32, device=dev)
+    best_idx = torch.empty(batch.B, dtype=torch.int32, device=dev)
+    history = torch.empty((generations + 1, batch.B), dtype=torch.float32, device=dev)
+    p = hip.ptr
+    rc = hip.load().gmc_kway_evolve_f32(batch.ref(), K, p(order), p(cgoff), p(cptr), cands, p(pop), p(cut),
+                                        int(generations), int(elite), p(inv_t), sweeps, p(levels), int(seed) & _M64,
+                                        int(max_descent_sweeps), p(best_assign), p(best_cut), p(best_idx), p(history),
+                                        hip.stream())
+    hip.check(rc, "gmc_kway_evolve_f32")
+    return best_assign, best_cut, best_idx, history, pop, cut
+
+
+def kway_evolution(partitions, graph, number_classes: int, generations: int = EVOLVE_GENERATIONS,
+                   generation_sweeps: int = EVOLVE_GENERATION_SWEEPS, elite: Optional[int] = None,
+                   t_start: float = EVOLVE_T_START, t_end: float = 0.15, seed: int = 0,
+                   max_descent_sweeps: int = 100) -> Tuple[List[int], Any, List[Any]]:
+    """Recombine ``partitions`` [cands, n] of one graph into ``number_classes`` = 2..8 classes across ``generations``
+    generations (extension, include/gcnmaxcut.h ``gmc_kway_evolve_f32``): every generation gives each partition a
+    child of itself and one of the ``elite`` best (``None``: ``max(2, cands // 4)``) - class names aligned, the nodes
+    the two disagree on taken from either - anneals the child for ``generation_sweeps`` sweeps cooling from ``t_start``
+    to ``t_end`` (:func:`anneal_schedule`, in units of the mean edge weight), descends from the best state and keeps
+    the child when its cut is not below the partition's.  Nodes 0..K-1 are the terminals.  Reproducible from ``seed``.
+    Returns the best assignment, its cut and the best cut after every generation (``generations + 1`` entries, the
+    first that of the input; never decreasing).  The defaults of ``generations``, ``generation_sweeps`` and
+    ``t_start`` are provisional, see DESIGN.md section 22."""
+    K = _search_classes("kway_evolution", number_classes)
+    parts = np.asarray(partitions, dtype=np.int64)
+    n = graph.number_of_nodes()
+    if parts.ndim != 2 or parts.shape[0] < 1 or parts.shape[1] != n:
+        raise ValueError(f"partitions must be [cands, {n}] with cands >= 1, got {tuple(parts.shape)}")
+    if n < K:
+        raise ValueError(f"number_classes = {K}: the graph needs at least {K} nodes (nodes 0..{K - 1} are the "
+                         f"terminals), got {n}")
+    if int(parts.min()) < 0 or int(parts.max()) > K - 1:
+        raise ValueError(f"partitions holds a class outside 0..{K - 1} (number_classes = {K})")
+    elite = _evolve_arguments("kway_evolution", parts.shape[0], generations, generation_sweeps, elite,
+                              max_descent_sweeps)
+    dev = hip.require_gpu()
+    batch = GraphBatch([from_networkx(graph)], None, dev)
+    population = torch.from_numpy(parts.astype(np.int8)).to(dev)
+    inv_temp = anneal_schedule(generation_sweeps, t_start, t_end, _mean_edge_weight(batch))
+    best_assign, best_cut, _, history, _, _ = _kway_evolve_on_gpu(batch, K, population, generations, elite, inv_temp,
+                                                                  seed, max_descent_sweeps)
+    return (best_assign.cpu().tolist(), _as_number(best_cut.item()),
+            [_as_number(c) for c in history[:, 0].cpu().tolist()])
+
+
 def test_single_graph(model, dgl_graph, adjacency_matrix, nx_graph, terminals: List[int],
                       post_processing_iterations: int = 200, *, seed: Optional[int] = None,
                       graph_index: int = 0) -> Dict[str, Any]:
@@ -989,7 +1075,9 @@ def round_large_dataset(model, processed_graphs: Dict, descent_sweeps: int = 0) 
 
 def search_dataset(model, processed_graphs: Dict, samples: int = 200, *, sample_seed: int = 0, anneal_sweeps: int = 100,
                    anneal_seed: int = 0, max_descent_sweeps: int = 100,
-                   candidates: Optional[int] = None) -> List[Dict[str, Any]]:
+                   candidates: Optional[int] = None, generations: int = 0,
+                   generation_sweeps: int = EVOLVE_GENERATION_SWEEPS,
+                   elite: Optional[int] = None) -> List[Dict[str, Any]]:
     """Decode a whole dataset of a model of any ``number_classes`` in 2..8 with everything the 3-class path has
     (extension): ONE batched forward, ONE rounding launch (``round_dataset(..., 0)``), ONE launch of the seeded sampler
     (``gmc_kway_decode_sample_seeded_f32``, a graph's index its position in ``processed_graphs.values()``) and ONE
@@ -999,7 +1087,13 @@ def search_dataset(model, processed_graphs: Dict, samples: int = 200, *, sample_
     ``samples = 0`` is allowed: the candidates are then the argmax and the rounded one.  Per graph: ``nodes``,
     ``simple_cut`` / ``simple_assignment``, ``expected_cut``, ``rounded_cut`` / ``rounded_assignment`` (as
     ``round_dataset(..., 0)`` reports them), ``post_cut`` / ``post_assignment`` (the best sample, with ``samples > 0``)
-    and ``searched_cut``, ``searched_assignment``, ``searched_from`` (the winning candidate)."""
+    and ``searched_cut``, ``searched_assignment``, ``searched_from`` (the winning candidate).
+    ``generations > 0``: ONE call of the evolution stage (``gmc_kway_evolve_f32``, :func:`kway_evolution`) follows over
+    the searched candidates of every graph as its population - ``generations`` generations of ``generation_sweeps``
+    annealing sweeps cooling from ``EVOLVE_T_START``, ``elite`` as there, seeded by ``anneal_seed`` - and each result
+    gains ``evolved_cut`` (never below ``searched_cut``), ``evolved_assignment`` and ``evolved_history`` (the best cut
+    after every generation, ``generations + 1`` entries).  No other key changes; ``generations = 0`` launches nothing
+    more and adds no key."""
     if samples < 0:
         raise ValueError(f"samples must be >= 0, got {samples}")
     if anneal_sweeps < 0 or max_descent_sweeps < 0:
@@ -1007,6 +1101,7 @@ def search_dataset(model, processed_graphs: Dict, samples: int = 200, *, sample_
     take = 2 + samples if candidates is None else int(candidates)
     if not 1 <= take <= 2 + samples:
         raise ValueError(f"candidates must be in 1..{2 + samples}, got {candidates}")
+    elite = _evolve_arguments("search_dataset", take, generations, generation_sweeps, elite, max_descent_sweeps)
     items = list(processed_graphs.values())
     eng = model.engine()
     K = _search_classes("search_dataset", eng.K)
@@ -1030,6 +1125,11 @@ def search_dataset(model, processed_graphs: Dict, samples: int = 200, *, sample_
     inv_temp = anneal_schedule(anneal_sweeps, scale=_mean_edge_weight(batch))
     found_assign, found_cut, found_idx = [t.cpu().numpy() for t in
                                           _kway_anneal_on_gpu(batch, K, cands, inv_temp, anneal_seed, max_descent_sweeps)]
+    evolved = None
+    if generations > 0:   # the search left its candidates in `cands`: the population
+        inv_temp = anneal_schedule(generation_sweeps, t_start=EVOLVE_T_START, scale=_mean_edge_weight(batch))
+        evolved = [t.cpu().numpy() for t in _kway_evolve_on_gpu(batch, K, cands, generations, elite, inv_temp,
+                                                                anneal_seed, max_descent_sweeps)[:4]]
     S_host, simple = S.cpu().numpy(), (-loss).cpu().tolist()
     rnd_assign, rnd_cut, rnd_expected = rnd_assign.cpu().numpy(), rnd_cut.cpu().numpy(), rnd_expected.cpu().numpy()
     out = []
@@ -1042,6 +1142,10 @@ def search_dataset(model, processed_graphs: Dict, samples: int = 200, *, sample_
             out[-1].update({'post_cut': _as_number(sampled[1][g]), 'post_assignment': sampled[0][lo:hi].tolist()})
         out[-1].update({'searched_cut': _as_number(found_cut[g]), 'searched_assignment': found_assign[lo:hi].tolist(),
                         'searched_from': int(found_idx[g])})
+        if evolved is not None:
+            ev_assign, ev_cut, _, ev_history = evolved
+            out[-1].update({'evolved_cut': _as_number(ev_cut[g]), 'evolved_assignment': ev_assign[lo:hi].tolist(),
+                            'evolved_history': [_as_number(c) for c in ev_history[:, g].tolist()]})
     return out
 
 

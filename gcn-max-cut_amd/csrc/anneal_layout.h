@@ -1,4 +1,5 @@
-// What the two annealing kernels share (anneal.hip: 3 classes; kway_search.hip: K classes): the launch arguments, the
+// What the annealing kernels share (anneal.hip: 3 classes; kway_search.hip: K classes; kway_evolve.hip: the children of
+// a generation, through anneal_body.h): the launch arguments, the
 // two accessors of a graph's CSR (the batch's arrays in global memory, the workgroup's copy in LDS) and the LDS layout
 // of a launch.  None of it depends on the class count, so one definition serves both and gmc_refine_anneal_staged
 // answers for both.  The layout itself is described at the top of anneal.hip.

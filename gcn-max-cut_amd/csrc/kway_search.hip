@@ -12,13 +12,14 @@
 // Annealing: the LDS layout of anneal.hip (anneal_layout.h: level table, state and best bytes, and the staged copy of
 // the graph's CSR when it fits GMC_ANNEAL_LDS_BUDGET) - it does not depend on K.  The K sums of a node are
 // compare-selected accumulators (move_body.h), "own sum" and "smallest among the others" unrolled compare chains; both
-// accessor paths run one templated body.
+// accessor paths run one templated body (anneal_body.h, which kway_evolve.hip runs on its children too).
 #include "gmc_common.h"
 #include "cut_body.h"
 #include "draw_body.h"
 #include "mix64.h"
 #include "move_body.h"
 #include "anneal_layout.h"
+#include "anneal_body.h"
 
 namespace {
 
@@ -91,82 +92,6 @@ int sample_launch(const KSeededArgs &a, hipStream_t st) {
 
 // ---- annealing + descent ------------------------------------------------------------------------------------------
 
-// one descent visit of local node l: the local search's rule at K classes (round.hip's descent; K = 3: local_move)
-template <int K, class G>
-__device__ __forceinline__ bool descent_visit(const G &g, unsigned char *sa, int l) {
-    const Sums<K> s = gmc::class_sums_k<K>(g.rp, g.col, g.vals, sa, l);
-    const int c = sa[l];
-    const float wc = gmc::own_sum_or_inf<K>(s, c);
-    float wk;
-    const int kk = gmc::smallest<K>(s, wk);
-    if (wk < wc) {
-        sa[l] = (unsigned char)kk;
-        return true;
-    }
-    return false;
-}
-
-template <int K, class G>
-__device__ __forceinline__ void anneal_body_k(const AnnealArgs &a, const G &g, unsigned char *sa, unsigned char *sb,
-                                              const float *lv, int n, int k0, int classes, float *red, int *flag) {
-    const int cand = blockIdx.x, gi = blockIdx.y;
-    int snap = 0;
-    if (a.anneal_sweeps > 0) {
-        float best_cut = gmc::block_cut_csr(g.rp, g.col, g.vals, sa, n, red);   // thread 0
-        __syncthreads();   // (thread 0 has read red before a graph without classes recounts)
-        for (int s = 0; s < a.anneal_sweeps; ++s) {
-            const float inv_t = a.inv_temp[s];
-            // seed + GOLD * (ctr + 1), ctr = cand << 32 | s << 12 | v: the part without v (v < 2^12 only adds)
-            const u64 base = a.seed + GMC_GOLD * ((((u64)(unsigned)cand << 32) | ((u64)(unsigned)s << 12)) + 1ULL);
-            for (int k = 0; k < classes; ++k) {
-                const int hi = a.cptr[k0 + k + 1];
-                for (int i = a.cptr[k0 + k] + threadIdx.x; i < hi; i += blockDim.x) {
-                    const int l = g.node(i);
-                    if (l < K || l >= n) continue;   // not a movable row of this graph: never touch LDS for it
-                    const Sums<K> w = gmc::class_sums_k<K>(g.rp, g.col, g.vals, sa, l);
-                    const u64 h = mix64(base + GMC_GOLD * (u64)(unsigned)l);
-                    int kk;
-                    if (gmc::anneal_move<K>(w, sa[l], inv_t, lv, h, kk)) sa[l] = (unsigned char)kk;
-                }
-                __syncthreads();   // the next class, or the recount, reads what this one wrote
-            }
-            const float cut = gmc::block_cut_csr(g.rp, g.col, g.vals, sa, n, red);
-            if (threadIdx.x == 0) {
-                const int better = cut > best_cut;
-                if (better) best_cut = cut;
-                *flag = better;
-            }
-            __syncthreads();   // (also: thread 0 has read red before the next recount writes it)
-            if (*flag) {       // workgroup-uniform
-                snap = s + 1;
-                for (int l = threadIdx.x; l < n; l += blockDim.x) sb[l] = sa[l];
-                __syncthreads();   // the next sweep moves nodes other threads are copying
-            }
-        }
-        for (int l = threadIdx.x; l < n; l += blockDim.x) sa[l] = sb[l];
-        __syncthreads();
-    }
-    int s = 0;
-    while (s < a.max_descent_sweeps) {
-        ++s;
-        int moved = 0;
-        for (int k = 0; k < classes; ++k) {
-            const int hi = a.cptr[k0 + k + 1];
-            for (int i = a.cptr[k0 + k] + threadIdx.x; i < hi; i += blockDim.x) {
-                const int l = g.node(i);
-                if (l < K || l >= n) continue;
-                if (descent_visit<K>(g, sa, l)) moved = 1;
-            }
-            if (k + 1 < classes) __syncthreads();
-        }
-        if (!__syncthreads_or(moved)) break;
-    }
-    if (threadIdx.x == 0) {
-        if (a.snap_sweep) a.snap_sweep[(long)gi * a.cands + cand] = snap;
-        if (a.sweeps) a.sweeps[(long)gi * a.cands + cand] = s;
-    }
-}
-
 template <int K>
 __global__ __launch_bounds__(256) void anneal_k_kernel(AnnealArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
@@ -183,34 +108,15 @@ __global__ __launch_bounds__(256) void anneal_k_kernel(AnnealArgs a) {
     for (int l = threadIdx.x; l < n; l += blockDim.x) sa[l] = sb[l] = (unsigned char)as[l];
     if (a.anneal_sweeps > 0)
         for (int i = threadIdx.x; i < GMC_ANNEAL_LEVELS; i += blockDim.x) lv[i] = a.levels[i];
-    const int k0 = a.cgoff[gi];
-    const int classes = a.cgoff[gi + 1] - k0 - 1;
-    const int e0 = a.b.rowptr[r0];
-    const int nnz = a.b.rowptr[r0 + n] - e0;
-    const int i0 = a.cptr[k0];
-    const int movable = a.cptr[k0 + classes] - i0;
-    // the copy is sized by n_max and nnz_max: a graph that contradicts them takes the global path
-    if (a.staged && nnz >= 0 && nnz <= a.b.nnz_max && movable >= 0 && movable <= a.n_pad) {
-        int *starts = reinterpret_cast<int *>(lds + a.off_starts);
-        float *vals = a.b.vals ? reinterpret_cast<float *>(lds + a.off_vals) : nullptr;
-        unsigned short *ord = reinterpret_cast<unsigned short *>(lds + a.off_order);
-        unsigned short *ids = reinterpret_cast<unsigned short *>(lds + a.off_ids);
-        for (int l = threadIdx.x; l <= n; l += blockDim.x) starts[l] = a.b.rowptr[r0 + l] - e0;
-        for (int e = threadIdx.x; e < nnz; e += blockDim.x) {
-            ids[e] = (unsigned short)a.b.lcol[e0 + e];
-            if (vals) vals[e] = a.b.vals[e0 + e];
-        }
-        for (int i = threadIdx.x; i < movable; i += blockDim.x) {
-            const int l = a.order[i0 + i] - r0;
-            ord[i] = (unsigned)l < (unsigned)n ? (unsigned short)l : (unsigned short)0xffff;
-        }
+    const gmc::AnnealGraph q = gmc::anneal_graph(a, gi, r0, n);
+    if (gmc::anneal_fits_lds(a, q)) {
+        const LdsCsr g = gmc::anneal_stage_csr(a, q, lds);
         __syncthreads();
-        const LdsCsr g{starts, ids, vals, ord, i0};
-        anneal_body_k<K>(a, g, sa, sb, lv, n, k0, classes, red, &flag);
+        gmc::anneal_body_k<K>(a, g, sa, sb, lv, n, q.k0, q.classes, red, &flag);
     } else {
         __syncthreads();
         const GlobalCsr g{a.b.rowptr + r0, a.b.lcol, a.b.vals, a.order, r0};
-        anneal_body_k<K>(a, g, sa, sb, lv, n, k0, classes, red, &flag);
+        gmc::anneal_body_k<K>(a, g, sa, sb, lv, n, q.k0, q.classes, red, &flag);
     }
     for (int l = threadIdx.x; l < n; l += blockDim.x) as[l] = (signed char)sa[l];
     const float cut = gmc::block_cut(a.b, sa, r0, n, red);   // scored as gmc_refine_local_f32 scores

@@ -153,6 +153,8 @@ def _api() -> dict:
         "gmc_kway_decode_sample_seeded_f32": (i, [B, vp, i32, vp, i32, vp, vp, vp, vp, vp, vp]),
         "gmc_kway_refine_anneal_f32": (i, [B, i32, vp, vp, vp, i32, vp, vp, i32, vp, C.c_uint64, i32, vp, vp, vp, vp, vp,
                                            vp, vp]),
+        "gmc_kway_evolve_f32": (i, [B, i32, vp, vp, vp, i32, vp, vp, i32, i32, vp, i32, vp, C.c_uint64, i32, vp, vp, vp,
+                                    vp, vp]),
         "gmc_large_round_order_host": (i, [i32, vp, vp, vp, i32, vp, vp, vp, i32, vp]),
         "gmc_large_round_workspace_bytes": (sz, [B, i32]),
         "gmc_large_round_conditional_f32": (i, [B, vp, i32, vp, vp, vp, i32, i32, vp, sz, vp, vp, vp, vp, vp]),

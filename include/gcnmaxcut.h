@@ -821,6 +821,75 @@ int gmc_kway_refine_anneal_f32(const gmc_batch *batch, int32_t K, const int32_t 
                                float *cut_all, int32_t *best_assign, float *best_cut, int32_t *best_idx,
                                int32_t *snap_sweep, int32_t *sweeps, gmc_stream_t stream);
 
+/* ---- evolution: recombining the candidates of a graph across generations (extension; K = 2 .. GMC_KWAY_MAX_CLASSES) --
+ *
+ * gmc_kway_refine_anneal_f32 improves every candidate on its own and keeps the best.  This stage lets the candidates of
+ * a graph learn from each other: they form a population of `cands` members ("slots"), and every generation gives each
+ * slot a child of its own member and one of the best members, improves the child with the annealing above and keeps it
+ * when it is no worse.  Nodes 0..K-1 are the terminals of classes 0..K-1; the movable nodes are K..n-1.  All integer
+ * arithmetic below is modulo 2^64; GOLD = 0x9E3779B97F4A7C15 and mix64 are those of gmc_refine_anneal_f32.
+ *
+ * Buffers.  pop [2][cands][R] int8 and cut [2][B][cands] float, both the caller's (device).  Plane 0 of pop holds the
+ * input population, typically what gmc_kway_refine_anneal_f32 left in `assign`.  Generation g = 1..G reads plane
+ * (g-1) & 1 of both and writes plane g & 1 of both; nothing is updated in place.  Before generation 1 one launch writes
+ * plane 0 of cut: the cut of every member as gmc_refine_local_f32 counts it (fp32, the same code, the same bits).  What
+ * the caller left in cut is never read.
+ *
+ * Seeds of generation g:  S_g = mix64(seed + GOLD * g),  select_g = mix64(S_g ^ 0x53454C4543543031),
+ * cross_g = mix64(S_g ^ 0x43524F5353303031).
+ *
+ * Generation g for (slot i, graph), prev the plane it reads:
+ *  1. rank.  The slots of prev are ordered by (cut descending, slot ascending); rank 0 is the first.  E = elite clipped
+ *     to 1..cands; the elite set is the slots of rank 0..E-1.  (Cuts are compared as floats; nothing is claimed when
+ *     one of them is NaN.)
+ *  2. parents.  a = prev[i].  r = mix64(select_g + GOLD * (i + 1)) mod E; b = the slot of rank r, and if that slot is i
+ *     itself, the slot of rank (r + 1) mod E.  With E = 1 and i the slot of rank 0 there is no b: the child is a, with
+ *     the terminals set as in step 4, and steps 3 and 4 are not run.
+ *  3. align.  O[ca][cb] = #{v in K..n-1 : a[v] = ca and b[v] = cb}, integers; a byte outside 0..K-1 in either parent
+ *     counts for no pair.  K rounds of greedy matching: among the pairs (ca, cb) with ca and cb both unmatched take the
+ *     one of the largest O, the lowest ca and then the lowest cb on ties, and set pi(cb) = ca.  pi is a bijection of
+ *     0..K-1: b's class names translated into a's.
+ *  4. crossover.  child[l] = l for the terminals l < K, whatever the parents hold there.  For a movable node v:
+ *       b[v] outside 0..K-1:                  child[v] = a[v]         (a byte of no class loses to the other parent's)
+ *       else a[v] == pi(b[v]):                child[v] = a[v]
+ *       else a[v] outside 0..K-1:             child[v] = pi(b[v])
+ *       else h = mix64(cross_g + GOLD * (((uint64)i << 32 | v) + 1)):  child[v] = pi(b[v]) if h >> 63, else a[v].
+ *  5. improve.  Steps 1-3 of gmc_kway_refine_anneal_f32 on the child, with S_g in the place of seed and i in the place
+ *     of cand: anneal_sweeps sweeps over inv_temp with the best state kept, then the descent up to max_descent_sweeps.
+ *     It is the same device code.
+ *  6. replace.  c = cut(improved child), scored as above.  Plane g & 1 gets, in slot i, the improved child and c iff
+ *     c >= prev's cut of slot i, else a and its cut, both unchanged.  A tie goes to the child.  A slot's cut never
+ *     falls from plane to plane.
+ * Finish: the pick of gmc_refine_local_f32 (strictly best, first slot on ties) over plane G & 1: best_assign [R] int32,
+ * best_cut [B], best_idx [B].  history [G+1][B] (NULL: not written): history[g] = the best cut of the plane generation
+ * g wrote (g = 0: of the scored input); it never decreases with g.  G = 0 scores and picks.
+ * By construction: the three seeds feed different hash domains, so a generation's selection, crossover and annealing
+ * draws are independent; a slot's result depends on its graph, the population of the graph, the slot index, the seed
+ * and the schedule alone - not on the graph's place in the batch nor on the rest of the batch; and two parents that
+ * differ by a renaming of the classes on the movable nodes give a child that equals a there.
+ *
+ * Arguments: order / cgoff / cptr gmc_round_order_host's for the same K (device); inv_temp [anneal_sweeps] and levels
+ * [GMC_ANNEAL_LEVELS] as for gmc_kway_refine_anneal_f32 (either may be NULL when anneal_sweeps == 0).  Argument checks,
+ * before any HIP call, in that call's order: a NULL required pointer (history aside) GMC_ERR_NULL, batch->abi
+ * GMC_ERR_ABI, a NULL goff / rowptr / lcol GMC_ERR_NULL, K outside 2..GMC_KWAY_MAX_CLASSES GMC_ERR_CLASSES, cands < 1,
+ * a negative sweep count, anneal_sweeps >= 2^20, B < 0, generations < 0, generations >= 2^20 or elite < 1
+ * GMC_ERR_SHAPE, anneal_sweeps > 0 with a NULL inv_temp or levels GMC_ERR_NULL, n_max outside K..GMC_MAX_GRAPH_NODES
+ * GMC_ERR_GRAPH_SIZE; B == 0 returns GMC_OK without a launch.  A graph with fewer than K or more than n_max nodes inside
+ * a batch is skipped: nothing of it is written, history included.
+ * One 256-thread workgroup per (slot, graph); every workgroup ranks the `cands` cuts of its graph itself, so a
+ * generation is ONE launch and the call issues generations + 2: the scoring, the generations, the pick.  The LDS of a
+ * generation's launch is gmc_kway_refine_anneal_f32's (gmc_refine_anneal_staged answers for this call too): parent b
+ * lives in the best-state bytes and O, pi and the picks in the level table's until the crossover is done.  The
+ * ranking costs cands^2 / 256 compares per thread of a workgroup.  The call allocates nothing and does not
+ * synchronise; no float atomics (the counts of step 3 are integer LDS atomics: any order gives the same counts), no
+ * communication between workgroups inside a launch, bitwise reproducible. */
+int gmc_kway_evolve_f32(const gmc_batch *batch, int32_t K, const int32_t *order, const int32_t *cgoff,
+                        const int32_t *cptr, int32_t cands, int8_t *pop /*[2][cands][R]*/,
+                        float *cut /*[2][B][cands]*/, int32_t generations, int32_t elite, const float *inv_temp,
+                        int32_t anneal_sweeps, const float *levels, uint64_t seed, int32_t max_descent_sweeps,
+                        int32_t *best_assign, float *best_cut, int32_t *best_idx, float *history /*or NULL*/,
+                        gmc_stream_t stream);
+
 /* ---- the rounding and the K-class local search beyond GMC_MAX_GRAPH_NODES (extension) ---------------------------------
  *
  * gmc_round_conditional_f32 and gmc_kway_refine_anneal_f32 keep a graph's state in one workgroup's LDS and stop at
