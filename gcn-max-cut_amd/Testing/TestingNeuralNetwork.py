@@ -16,8 +16,9 @@ generated on the host, and a graph's samples depend on the seed and its index in
 any ``number_classes`` in 2..8.
 ``sampling_optimization``, ``kway_local_search``, ``kway_annealing`` and ``search_dataset`` (extension) are the seeded
 sampler, the local search and the annealing for ``number_classes`` in 2..8 (``gmc_kway_decode_sample_seeded_f32``,
-``gmc_kway_refine_anneal_f32``); at three classes they return what the 3-class functions return.  Those, and
-``decode_dataset``, keep refusing any other class count.
+``gmc_kway_refine_anneal_f32``); at three classes they return what the 3-class functions return - the library's
+3-class sampler and annealing are the K-class kernels at K = 3.  Those, and ``decode_dataset``, keep refusing any other
+class count.
 ``kway_evolution`` and ``search_dataset(..., generations=G)`` (extension) recombine the annealed candidates of a graph
 across generations (``gmc_kway_evolve_f32``): children of two class-aligned parents, annealed and kept when no worse.
 ``large_conditional_rounding``, ``large_local_search``, ``round_large_dataset``, ``large_sampling_optimization``,
@@ -100,7 +101,7 @@ def sample_keys(seed: int, indices) -> np.ndarray:
 
 
 def assign_partitions_seeded(node_probs: np.ndarray, seed: int, graph_index: int = 0, iteration: int = 0) -> List[int]:
-    """One sample of the seeded post-processing (host form of sample_seeded.hip, the counterpart of
+    """One sample of the seeded post-processing (host form of kway_search.hip's sampler at K = 3, the counterpart of
     :func:`assign_partitions`): iteration ``iteration`` of the graph at position ``graph_index``, the uniform of local
     node l hashed from the graph's key, the iteration and l.  Python integers masked to 64 bits and Python floats."""
     if int(iteration) < 0 or int(iteration) >= 1 << 31:
@@ -141,7 +142,8 @@ def simple_partition_assignment(node_probabilities: torch.Tensor) -> List[int]:
 
 
 def _three_classes_only(what: str, classes: int) -> None:
-    """The sampler and the refinement kernels (decode.hip, refine.hip, anneal.hip) are 3-class."""
+    """The numpy-stream sampler and the local search (decode.hip, refine.hip) are 3-class, and so are the entry points
+    these functions call (gmc_decode_sample_seeded_f32, gmc_refine_anneal_f32: kway_search.hip at K = 3)."""
     if int(classes) != 3:
         raise ValueError(f"{what} is implemented for number_classes = 3 only, got {int(classes)} classes: use the "
                          "argmax decode (simple_partition_assignment) for a model with another number_classes")

@@ -1,7 +1,8 @@
-// The K-class annealing of one (candidate, graph) workgroup, shared by kway_search.hip (gmc_kway_refine_anneal_f32) and
-// kway_evolve.hip (gmc_kway_evolve_f32, which improves every child with it): the staged copy of the graph's CSR, the
-// descent's visit and the body of steps 1-3 - annealing sweeps with the best state kept, then the descent.  One
-// definition, so a child is improved by exactly the code that annealed its parents.
+// The K-class annealing of one (candidate, graph) workgroup, shared by kway_search.hip (gmc_kway_refine_anneal_f32 and,
+// at K = 3, gmc_refine_anneal_f32) and kway_evolve.hip (gmc_kway_evolve_f32, which improves every child with it): the
+// staged copy of the graph's CSR and the body of steps 1-3 - annealing sweeps with the best state kept, then the
+// descent (move_body.h's descent_sweeps).  One definition, so a child is improved by exactly the code that annealed its
+// parents.
 #pragma once
 #include "gmc_common.h"
 #include "cut_body.h"
@@ -53,21 +54,6 @@ __device__ __forceinline__ LdsCsr anneal_stage_csr(const AnnealArgs &a, const An
     return LdsCsr{starts, ids, vals, ord, q.i0};
 }
 
-// one descent visit of local node l: the local search's rule at K classes (round.hip's descent; K = 3: local_move)
-template <int K, class G>
-__device__ __forceinline__ bool descent_visit(const G &g, unsigned char *sa, int l) {
-    const Sums<K> s = gmc::class_sums_k<K>(g.rp, g.col, g.vals, sa, l);
-    const int c = sa[l];
-    const float wc = gmc::own_sum_or_inf<K>(s, c);
-    float wk;
-    const int kk = gmc::smallest<K>(s, wk);
-    if (wk < wc) {
-        sa[l] = (unsigned char)kk;
-        return true;
-    }
-    return false;
-}
-
 // Steps 1-3 of gmc_kway_refine_anneal_f32 on the state in sa (sb: a copy of it, the best-state buffer) for candidate
 // blockIdx.x of graph blockIdx.y; on return sa holds the result and every thread may read it.
 template <int K, class G>
@@ -110,21 +96,8 @@ __device__ __forceinline__ void anneal_body_k(const AnnealArgs &a, const G &g, u
         for (int l = threadIdx.x; l < n; l += blockDim.x) sa[l] = sb[l];
         __syncthreads();
     }
-    int s = 0;
-    while (s < a.max_descent_sweeps) {
-        ++s;
-        int moved = 0;
-        for (int k = 0; k < classes; ++k) {
-            const int hi = a.cptr[k0 + k + 1];
-            for (int i = a.cptr[k0 + k] + threadIdx.x; i < hi; i += blockDim.x) {
-                const int l = g.node(i);
-                if (l < K || l >= n) continue;
-                if (descent_visit<K>(g, sa, l)) moved = 1;
-            }
-            if (k + 1 < classes) __syncthreads();
-        }
-        if (!__syncthreads_or(moved)) break;
-    }
+    // descent: the local search's sweeps from the best state
+    const int s = descent_sweeps<K>(g, a.cptr, k0, classes, sa, n, a.max_descent_sweeps);
     if (threadIdx.x == 0) {
         if (a.snap_sweep) a.snap_sweep[(long)gi * a.cands + cand] = snap;
         if (a.sweeps) a.sweeps[(long)gi * a.cands + cand] = s;

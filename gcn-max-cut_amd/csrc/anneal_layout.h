@@ -1,8 +1,26 @@
-// What the annealing kernels share (anneal.hip: 3 classes; kway_search.hip: K classes; kway_evolve.hip: the children of
-// a generation, through anneal_body.h): the launch arguments, the
-// two accessors of a graph's CSR (the batch's arrays in global memory, the workgroup's copy in LDS) and the LDS layout
-// of a launch.  None of it depends on the class count, so one definition serves both and gmc_refine_anneal_staged
-// answers for both.  The layout itself is described at the top of anneal.hip.
+// What the annealing kernels share (kway_search.hip: K classes, the 3-class entry point being K = 3; kway_evolve.hip:
+// the children of a generation, through anneal_body.h): the launch arguments, the two accessors of a graph's CSR (the
+// batch's arrays in global memory, the workgroup's copy in LDS; refine.hip and round.hip walk their descent through
+// the global one) and the LDS layout of a launch.  None of it depends on the class count, so gmc_refine_anneal_staged
+// answers for every K.
+//
+// One 256-thread workgroup per (candidate, graph), as in refine.hip.  Where the local search runs about 4 sweeps the
+// annealing runs about 100 and recounts the cut after each, so what it re-reads every sweep lives in LDS:
+//
+//   levels   [1024] float      4096 B   the caller's table (the device evaluates neither exp nor log)
+//   state    [n_pad] byte               the classes as they stand          (n_pad = n_max rounded up to 16)
+//   best     [n_pad] byte               the snapshot with the largest cut so far
+//   --- staged copy of the graph (only when it fits GMC_ANNEAL_LDS_BUDGET, see anneal_layout) ---
+//   starts   [n_max + 1] int            CSR row starts, relative to the graph's first edge
+//   vals     [nnz_max] float            edge weights (weighted batches only)
+//   order    [n_pad] uint16             the movable nodes in (colour, id) order as local ids
+//   ids      [nnz_max] uint16           neighbour ids (local ids fit 16 bits: n <= 4096)
+//
+// n = 1000, d = 7, unit weights: 4096 + 2 * 1008 + 4016 + 2016 + 14000 = 26144 B, six workgroups (24 waves) per CU.
+// A batch whose copy would push a workgroup past the budget (40 KiB including GMC_ANNEAL_LDS_STATIC for the kernel's
+// static LDS, so at least four workgroups = 16 waves, four per SIMD, fit the 160 KiB of a CU) runs the same
+// code over the batch's arrays in global memory (12 KiB of LDS at most, eight workgroups per CU).  Both paths are one
+// template over the accessor, so their arithmetic cannot differ.
 #pragma once
 #include "gmc_common.h"
 #include "mix64.h"

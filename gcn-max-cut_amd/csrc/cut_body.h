@@ -1,6 +1,7 @@
-// Cut count and best-candidate pick shared by the post-processing samplers (decode.hip, sample_seeded.hip), the local
-// search (refine.hip) and the annealing (anneal.hip): all score their candidates with the same code, so a candidate a
-// search does not move gets, bit for bit, the cut the sampler reports for it.
+// Cut count and best-candidate pick shared by the post-processing samplers (decode.hip, kway_search.hip), the local
+// search (refine.hip), the rounding (round.hip), the annealing (kway_search.hip) and the evolution (kway_evolve.hip):
+// all score their candidates with the same code, so a candidate a search does not move gets, bit for bit, the cut the
+// sampler reports for it.
 #pragma once
 #include "gmc_common.h"
 
@@ -13,7 +14,7 @@ namespace gmc {
 //
 // block_cut_csr is the count itself over any copy of the graph's CSR: rp[l] .. rp[l + 1] are the edges of local row l
 // in col (local neighbour ids) and vals (NULL: all ones).  block_cut reads the batch's arrays in global memory; the
-// annealing kernel (anneal.hip) also calls block_cut_csr on the copy it keeps in LDS - one piece of code, one
+// annealing body (anneal_body.h) also calls block_cut_csr on the copy it keeps in LDS - one piece of code, one
 // summation order, the same bits.
 template <class RP, class COL>
 __device__ __forceinline__ float block_cut_csr(const RP *rp, const COL *col, const float *vals, const unsigned char *sa,

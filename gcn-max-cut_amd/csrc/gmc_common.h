@@ -13,6 +13,20 @@
         if (e__ != hipSuccess) return (int)e__;    \
     } while (0)
 
+// The statement `...` with the runtime class count K as the constant KK (the template argument of the K-class
+// kernels); K outside 2..8: GMC_ERR_CLASSES.  The one place a class count is turned into an instantiation.
+#define GMC_KWAY_DISPATCH(K, ...)               \
+    switch (K) {                                \
+        case 2: { constexpr int KK = 2; __VA_ARGS__; } break; \
+        case 3: { constexpr int KK = 3; __VA_ARGS__; } break; \
+        case 4: { constexpr int KK = 4; __VA_ARGS__; } break; \
+        case 5: { constexpr int KK = 5; __VA_ARGS__; } break; \
+        case 6: { constexpr int KK = 6; __VA_ARGS__; } break; \
+        case 7: { constexpr int KK = 7; __VA_ARGS__; } break; \
+        case 8: { constexpr int KK = 8; __VA_ARGS__; } break; \
+        default: return GMC_ERR_CLASSES;        \
+    }
+
 // Optional per-kernel timing (bench.py): hipEvents recorded around each launch of the fused
 // step on the caller's stream.  Off by default (no events, capture-safe).
 void gmc_probe_mark(int tag, bool begin, hipStream_t st);

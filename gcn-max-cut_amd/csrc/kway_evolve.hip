@@ -247,16 +247,8 @@ extern "C" int gmc_kway_evolve_f32(const gmc_batch *batch, int32_t K, const int3
                            planes[from], planes[to], cuts[from], cuts[to],
                            history ? history + (size_t)(g - 1) * (size_t)B : nullptr, elite < cands ? elite : cands,
                            mix64(gen_seed ^ GMC_EVOLVE_SELECT), mix64(gen_seed ^ GMC_EVOLVE_CROSS)};
-        int rc;
-        switch (K) {
-            case 2: rc = generation_launch<2>(e, L.bytes, st); break;
-            case 3: rc = generation_launch<3>(e, L.bytes, st); break;
-            case 4: rc = generation_launch<4>(e, L.bytes, st); break;
-            case 5: rc = generation_launch<5>(e, L.bytes, st); break;
-            case 6: rc = generation_launch<6>(e, L.bytes, st); break;
-            case 7: rc = generation_launch<7>(e, L.bytes, st); break;
-            default: rc = generation_launch<8>(e, L.bytes, st); break;
-        }
+        int rc = GMC_OK;
+        GMC_KWAY_DISPATCH(K, rc = generation_launch<KK>(e, L.bytes, st));
         if (rc != GMC_OK) return rc;
     }
     const int last = generations & 1;

@@ -1,5 +1,6 @@
-// What the K-wide row kernels of kway.hip and large.hip share: a row of K floats as vector accesses, the deterministic
-// block sum, and the dispatch of a runtime class count onto the template argument.
+// What the K-wide row kernels of kway.hip and large.hip share: a row of K floats as vector accesses and the
+// deterministic block sum.  (The dispatch of a runtime class count onto the template argument, GMC_KWAY_DISPATCH, is
+// gmc_common.h's: the decoders use it too.)
 #pragma once
 #include "launchers.h"
 
@@ -68,17 +69,3 @@ __device__ __forceinline__ void block_sum(float (&v)[V], float *red /* [WAVES * 
 }
 
 }  // namespace
-
-// the statement `...` with the class count as the constant KK; K outside 2..8: GMC_ERR_CLASSES
-#define GMC_KWAY_DISPATCH(K, ...)               \
-    switch (K) {                                \
-        case 2: { constexpr int KK = 2; __VA_ARGS__; } break; \
-        case 3: { constexpr int KK = 3; __VA_ARGS__; } break; \
-        case 4: { constexpr int KK = 4; __VA_ARGS__; } break; \
-        case 5: { constexpr int KK = 5; __VA_ARGS__; } break; \
-        case 6: { constexpr int KK = 6; __VA_ARGS__; } break; \
-        case 7: { constexpr int KK = 7; __VA_ARGS__; } break; \
-        case 8: { constexpr int KK = 8; __VA_ARGS__; } break; \
-        default: return GMC_ERR_CLASSES;        \
-    }
-

@@ -1,18 +1,25 @@
-// The seeded sampler and the annealing (with the local search as its descent) at K = 2..8 classes: the decoders of the
-// models gmc_kway_forward serves (an extension: the reference samples and stops, TestingNeuralNetwork.py:66-98, and is
-// 3-class).  Both algorithms are stated in include/gcnmaxcut.h (gmc_kway_decode_sample_seeded_f32,
-// gmc_kway_refine_anneal_f32); at K = 3 they are sample_seeded.hip's and anneal.hip's, output for output.
+// The seeded sampler and the annealing (with the local search as its descent) at K = 2..8 classes (an extension: the
+// reference draws its uniforms from numpy's global RNG, samples and stops, TestingNeuralNetwork.py:18-98, and is
+// 3-class).  Both algorithms are stated in include/gcnmaxcut.h.  The entry points of the reference's 3-class model
+// (gmc_decode_sample_seeded_f32, gmc_refine_anneal_f32) and those of the models gmc_kway_forward serves
+// (gmc_kway_decode_sample_seeded_f32, gmc_kway_refine_anneal_f32) check their own arguments and then run the same
+// launches: the 3-class ones are K = 3.
 //
-// K is a template argument, one 256-thread workgroup per (candidate, graph) as in those files.
+// K is a template argument, one 256-thread workgroup per (candidate, graph).
 //
-// Sampler: the class bytes of a sample in n_max bytes of LDS, the cut by gmc::block_cut, the pick kernel regenerates
-// the winner from the hash.  The draw is draw_body.h's (large_search.hip draws with it too).  The running sum of a row's probabilities lives in one register: the loop over the
-// constant K is unrolled and stops comparing after the first class that takes the draw.
+// Sampler: a graph's key and the pair (iteration, local node) go through the counter-based hash of mix64.h, the top 53
+// bits are the uniform (draw_body.h; large_search.hip draws with it too): nothing is generated on the host and nothing
+// is copied.  The class bytes of a sample live in n_max bytes of LDS, the cut is gmc::block_cut's, so a sample scores
+// bit for bit what gmc_decode_sample_f32 and gmc_refine_local_f32 report for the same assignment.  The pick kernel
+// takes the winning iteration and REGENERATES that one assignment from the hash, so the [iters][R] array of all
+// samples is optional: without it a call writes [B][iters] floats and [R] ints, whatever `iters` is.  The running sum
+// of a row's probabilities lives in one register: the loop over the constant K is unrolled and stops comparing after
+// the first class that takes the draw.
 //
-// Annealing: the LDS layout of anneal.hip (anneal_layout.h: level table, state and best bytes, and the staged copy of
-// the graph's CSR when it fits GMC_ANNEAL_LDS_BUDGET) - it does not depend on K.  The K sums of a node are
-// compare-selected accumulators (move_body.h), "own sum" and "smallest among the others" unrolled compare chains; both
-// accessor paths run one templated body (anneal_body.h, which kway_evolve.hip runs on its children too).
+// Annealing: the LDS layout of anneal_layout.h (level table, state and best bytes, and the staged copy of the graph's
+// CSR when it fits GMC_ANNEAL_LDS_BUDGET) - it does not depend on K.  The K sums of a node are compare-selected
+// accumulators (move_body.h), "own sum" and "smallest among the others" unrolled compare chains; both accessor paths
+// run one templated body (anneal_body.h, which kway_evolve.hip runs on its children too).
 #include "gmc_common.h"
 #include "cut_body.h"
 #include "draw_body.h"
@@ -35,7 +42,7 @@ using gmc::Sums;
 
 // ---- the sampler --------------------------------------------------------------------------------------------------
 
-struct KSeededArgs {
+struct SeededArgs {
     gmc_batch b;
     const float *P;          // [R,K]
     const u64 *gkey;         // [B]
@@ -48,7 +55,7 @@ struct KSeededArgs {
 };
 
 template <int K>
-__global__ __launch_bounds__(256) void sample_seeded_k_kernel(KSeededArgs a) {
+__global__ __launch_bounds__(256) void sample_seeded_k_kernel(SeededArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char sa[];
     __shared__ float red[4];
     const int it = blockIdx.x, g = blockIdx.y;
@@ -66,9 +73,10 @@ __global__ __launch_bounds__(256) void sample_seeded_k_kernel(KSeededArgs a) {
     if (threadIdx.x == 0) a.cut_all[(long)g * a.iters + it] = cut;
 }
 
-// One workgroup per graph: the winning iteration, then its assignment again from the hash (never read from assign_all)
+// One workgroup per graph: the winning iteration, then its assignment again from the hash (never read from assign_all,
+// so the call with and without that array runs the same code)
 template <int K>
-__global__ __launch_bounds__(256) void sample_seeded_k_pick_kernel(KSeededArgs a) {
+__global__ __launch_bounds__(256) void sample_seeded_k_pick_kernel(SeededArgs a) {
     const int g = blockIdx.x;
     const int r0 = a.b.goff[g], n = a.b.goff[g + 1] - r0;
     if (n > a.b.n_max || n < K) return;   // workgroup-uniform: the graphs the sampler skipped
@@ -79,7 +87,7 @@ __global__ __launch_bounds__(256) void sample_seeded_k_pick_kernel(KSeededArgs a
 }
 
 template <int K>
-int sample_launch(const KSeededArgs &a, hipStream_t st) {
+int sample_launch_k(const SeededArgs &a, hipStream_t st) {
     {
         GmcProbeScope probe(GMC_K_SAMPLE, st);
         hipLaunchKernelGGL((sample_seeded_k_kernel<K>), dim3(a.iters, a.b.B), dim3(256), (size_t)a.b.n_max, st, a);
@@ -87,6 +95,16 @@ int sample_launch(const KSeededArgs &a, hipStream_t st) {
     }
     hipLaunchKernelGGL((sample_seeded_k_pick_kernel<K>), dim3(a.b.B), dim3(256), 0, st, a);
     GMC_LAUNCH_CHECK();
+    return GMC_OK;
+}
+
+// what a sampler entry point does once its arguments are checked (B > 0, K in 2..8)
+int sample_launch(const gmc_batch *batch, const float *P, int K, const uint64_t *gkey, int iters, int8_t *assign_all,
+                  float *cut_all, int32_t *best_assign, float *best_cut, int32_t *best_iter, gmc_stream_t stream) {
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const SeededArgs a{*batch, P, reinterpret_cast<const u64 *>(gkey), iters,
+                       reinterpret_cast<signed char *>(assign_all), cut_all, best_assign, best_cut, best_iter};
+    GMC_KWAY_DISPATCH(K, return sample_launch_k<KK>(a, st));
     return GMC_OK;
 }
 
@@ -135,14 +153,46 @@ __global__ __launch_bounds__(256) void anneal_k_pick_kernel(KPickArgs a) {
 }
 
 template <int K>
-int anneal_launch(const AnnealArgs &a, int lds_bytes, hipStream_t st) {
+int anneal_launch_k(const AnnealArgs &a, int lds_bytes, hipStream_t st) {
     GmcProbeScope probe(GMC_K_ANNEAL, st);
     hipLaunchKernelGGL((anneal_k_kernel<K>), dim3(a.cands, a.b.B), dim3(256), (size_t)lds_bytes, st, a);
     GMC_LAUNCH_CHECK();
     return GMC_OK;
 }
 
+// what an annealing entry point does once its arguments are checked (B > 0, K in 2..8)
+int anneal_launch(const gmc_batch *batch, int K, const int32_t *order, const int32_t *cgoff, const int32_t *cptr,
+                  int cands, int8_t *assign, const float *inv_temp, int anneal_sweeps, const float *levels,
+                  uint64_t seed, int max_descent_sweeps, float *cut_all, int32_t *best_assign, float *best_cut,
+                  int32_t *best_idx, int32_t *snap_sweep, int32_t *sweeps, gmc_stream_t stream) {
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const AnnealLayout L = gmc::anneal_layout(batch);
+    const AnnealArgs a{*batch, order, cgoff, cptr, cands, anneal_sweeps, max_descent_sweeps, inv_temp, levels, seed,
+                       reinterpret_cast<signed char *>(assign), cut_all, snap_sweep, sweeps,
+                       L.staged, L.n_pad, L.off_starts, L.off_vals, L.off_order, L.off_ids};
+    int rc = GMC_OK;
+    GMC_KWAY_DISPATCH(K, rc = anneal_launch_k<KK>(a, L.bytes, st));
+    if (rc != GMC_OK) return rc;
+    const KPickArgs p{{*batch, cands, reinterpret_cast<const signed char *>(assign), cut_all, best_assign, best_cut,
+                       best_idx}, K};
+    hipLaunchKernelGGL(anneal_k_pick_kernel, dim3(batch->B), dim3(256), 0, st, p);
+    GMC_LAUNCH_CHECK();
+    return GMC_OK;
+}
+
 }  // namespace
+
+extern "C" int gmc_decode_sample_seeded_f32(const gmc_batch *batch, const float *P, const uint64_t *gkey,
+                                            int32_t iters, int8_t *assign_all, float *cut_all, int32_t *best_assign,
+                                            float *best_cut, int32_t *best_iter, gmc_stream_t stream) {
+    if (!batch || !P || !gkey || !cut_all || !best_assign || !best_cut || !best_iter) return GMC_ERR_NULL;
+    if (batch->abi != GMC_VERSION) return GMC_ERR_ABI;
+    if (!batch->goff || !batch->rowptr || !batch->lcol) return GMC_ERR_NULL;
+    if (iters < 1 || batch->B < 0) return GMC_ERR_SHAPE;
+    if (batch->B > 0 && (batch->n_max < 3 || batch->n_max > 65535)) return GMC_ERR_GRAPH_SIZE;
+    if (batch->B == 0) return GMC_OK;
+    return sample_launch(batch, P, 3, gkey, iters, assign_all, cut_all, best_assign, best_cut, best_iter, stream);
+}
 
 extern "C" int gmc_kway_decode_sample_seeded_f32(const gmc_batch *batch, const float *P, int32_t K,
                                                  const uint64_t *gkey, int32_t iters, int8_t *assign_all,
@@ -155,18 +205,32 @@ extern "C" int gmc_kway_decode_sample_seeded_f32(const gmc_batch *batch, const f
     if (iters < 1 || batch->B < 0) return GMC_ERR_SHAPE;
     if (batch->B > 0 && (batch->n_max < K || batch->n_max > 65535)) return GMC_ERR_GRAPH_SIZE;
     if (batch->B == 0) return GMC_OK;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const KSeededArgs a{*batch, P, reinterpret_cast<const u64 *>(gkey), iters,
-                        reinterpret_cast<signed char *>(assign_all), cut_all, best_assign, best_cut, best_iter};
-    switch (K) {
-        case 2: return sample_launch<2>(a, st);
-        case 3: return sample_launch<3>(a, st);
-        case 4: return sample_launch<4>(a, st);
-        case 5: return sample_launch<5>(a, st);
-        case 6: return sample_launch<6>(a, st);
-        case 7: return sample_launch<7>(a, st);
-        default: return sample_launch<8>(a, st);
-    }
+    return sample_launch(batch, P, K, gkey, iters, assign_all, cut_all, best_assign, best_cut, best_iter, stream);
+}
+
+extern "C" int gmc_refine_anneal_staged(const gmc_batch *batch) {
+    if (!batch) return GMC_ERR_NULL;
+    if (batch->abi != GMC_VERSION) return GMC_ERR_ABI;
+    if (batch->n_max < 3 || batch->n_max > GMC_MAX_GRAPH_NODES) return GMC_ERR_GRAPH_SIZE;
+    return gmc::anneal_layout(batch).staged;
+}
+
+extern "C" int gmc_refine_anneal_f32(const gmc_batch *batch, const int32_t *order, const int32_t *cgoff,
+                                     const int32_t *cptr, int32_t cands, int8_t *assign, const float *inv_temp,
+                                     int32_t anneal_sweeps, const float *levels, uint64_t seed,
+                                     int32_t max_descent_sweeps, float *cut_all, int32_t *best_assign, float *best_cut,
+                                     int32_t *best_idx, int32_t *snap_sweep, int32_t *sweeps, gmc_stream_t stream) {
+    if (!batch || !order || !cgoff || !cptr || !assign || !cut_all || !best_assign || !best_cut || !best_idx)
+        return GMC_ERR_NULL;
+    if (batch->abi != GMC_VERSION) return GMC_ERR_ABI;
+    if (!batch->goff || !batch->rowptr || !batch->lcol) return GMC_ERR_NULL;
+    if (cands < 1 || anneal_sweeps < 0 || anneal_sweeps >= (1 << 20) || max_descent_sweeps < 0 || batch->B < 0)
+        return GMC_ERR_SHAPE;
+    if (anneal_sweeps > 0 && (!inv_temp || !levels)) return GMC_ERR_NULL;
+    if (batch->B > 0 && (batch->n_max < 3 || batch->n_max > GMC_MAX_GRAPH_NODES)) return GMC_ERR_GRAPH_SIZE;
+    if (batch->B == 0) return GMC_OK;
+    return anneal_launch(batch, 3, order, cgoff, cptr, cands, assign, inv_temp, anneal_sweeps, levels, seed,
+                         max_descent_sweeps, cut_all, best_assign, best_cut, best_idx, snap_sweep, sweeps, stream);
 }
 
 extern "C" int gmc_kway_refine_anneal_f32(const gmc_batch *batch, int32_t K, const int32_t *order,
@@ -185,25 +249,6 @@ extern "C" int gmc_kway_refine_anneal_f32(const gmc_batch *batch, int32_t K, con
     if (anneal_sweeps > 0 && (!inv_temp || !levels)) return GMC_ERR_NULL;
     if (batch->B > 0 && (batch->n_max < K || batch->n_max > GMC_MAX_GRAPH_NODES)) return GMC_ERR_GRAPH_SIZE;
     if (batch->B == 0) return GMC_OK;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const AnnealLayout L = gmc::anneal_layout(batch);
-    const AnnealArgs a{*batch, order, cgoff, cptr, cands, anneal_sweeps, max_descent_sweeps, inv_temp, levels, seed,
-                       reinterpret_cast<signed char *>(assign), cut_all, snap_sweep, sweeps,
-                       L.staged, L.n_pad, L.off_starts, L.off_vals, L.off_order, L.off_ids};
-    int rc;
-    switch (K) {
-        case 2: rc = anneal_launch<2>(a, L.bytes, st); break;
-        case 3: rc = anneal_launch<3>(a, L.bytes, st); break;
-        case 4: rc = anneal_launch<4>(a, L.bytes, st); break;
-        case 5: rc = anneal_launch<5>(a, L.bytes, st); break;
-        case 6: rc = anneal_launch<6>(a, L.bytes, st); break;
-        case 7: rc = anneal_launch<7>(a, L.bytes, st); break;
-        default: rc = anneal_launch<8>(a, L.bytes, st); break;
-    }
-    if (rc != GMC_OK) return rc;
-    const KPickArgs p{{*batch, cands, reinterpret_cast<const signed char *>(assign), cut_all, best_assign, best_cut,
-                       best_idx}, K};
-    hipLaunchKernelGGL(anneal_k_pick_kernel, dim3(batch->B), dim3(256), 0, st, p);
-    GMC_LAUNCH_CHECK();
-    return GMC_OK;
+    return anneal_launch(batch, K, order, cgoff, cptr, cands, assign, inv_temp, anneal_sweeps, levels, seed,
+                         max_descent_sweeps, cut_all, best_assign, best_cut, best_idx, snap_sweep, sweeps, stream);
 }

@@ -1,6 +1,6 @@
-// The counter-based hash of the annealing's move levels (anneal.hip) and of the seeded sampler's uniforms
-// (sample_seeded.hip): splitmix64's finaliser over seed + GOLD * (counter + 1), all in uint64 arithmetic.  One
-// definition, so the two kernels and their host restatements speak of the same function.
+// The counter-based hash of the annealing's move levels (anneal_body.h) and of the seeded sampler's uniforms
+// (draw_body.h): splitmix64's finaliser over seed + GOLD * (counter + 1), all in uint64 arithmetic.  One definition, so
+// the kernels and their host restatements speak of the same function.
 #pragma once
 #include "gmc_common.h"
 

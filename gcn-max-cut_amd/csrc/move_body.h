@@ -1,40 +1,12 @@
-// The node visit shared by the local search (refine.hip), the annealing (anneal.hip), the rounding's descent (round.hip)
-// and the K-class search (kway_search.hip): the class sums of a node and the local search's move rule, one definition so
-// that the kernels cannot drift apart.
+// The node visit shared by the local search (refine.hip), the annealing and the seeded search at K = 2..8 classes
+// (anneal_body.h, kway_search.hip, kway_evolve.hip; the 3-class entry points are their K = 3), the rounding's descent
+// (round.hip) and the kernels for large graphs (large_round.hip, large_search.hip): the class sums of a node, the move
+// rules, and the descent's sweep loop of the one-workgroup kernels - one definition each, so that the kernels cannot
+// drift apart.
 #pragma once
 #include "gmc_common.h"
 
 namespace gmc {
-
-// W0, W1, W2 of local node l: fp32 sums, in the CSR order of its row, of the weights of its edges to neighbours of class
-// 0, 1 and 2 (self-loops skipped).  Three sums chosen by compares (an indexed private array would live in scratch); a
-// class byte outside 0..2 adds to none of them.  rp[l] .. rp[l + 1] are the row's edges in col / vals (NULL: all ones).
-template <class RP, class COL>
-__device__ __forceinline__ void class_sums(const RP *rp, const COL *col, const float *vals, const unsigned char *sa,
-                                           int l, float &w0, float &w1, float &w2) {
-    w0 = 0.f; w1 = 0.f; w2 = 0.f;
-    const int e1 = rp[l + 1];
-    for (int e = rp[l]; e < e1; ++e) {
-        const int u = col[e];
-        if (u == l) continue;
-        const float w = vals ? vals[e] : 1.0f;
-        const int cu = sa[u];
-        w0 += cu == 0 ? w : 0.f;
-        w1 += cu == 1 ? w : 0.f;
-        w2 += cu == 2 ? w : 0.f;
-    }
-}
-
-// The local search's rule for a node of class byte c: kk = the class of the smallest W (lowest index on ties); true iff
-// the node moves there, i.e. W[kk] < W[c] (a byte outside 0..2 has W[c] = inf: such a node always moves).
-__device__ __forceinline__ bool local_move(float w0, float w1, float w2, int c, int &kk) {
-    const float wc = c == 0 ? w0 : c == 1 ? w1 : c == 2 ? w2 : __builtin_inff();
-    kk = 0;
-    float wk = w0;
-    if (w1 < wk) { kk = 1; wk = w1; }
-    if (w2 < wk) { kk = 2; wk = w2; }
-    return wk < wc;
-}
 
 // K floats in registers: every index below is a constant once the loops are unrolled (an index that is not would put
 // the array into scratch)
@@ -43,10 +15,11 @@ struct Sums {
     float m[K];
 };
 
-// class_sums at K classes: W_k = sum of the weights of the edges of local row l to neighbours of class k, fp32, in the
-// CSR order of the row, self-loops skipped, a class byte outside 0..K-1 adding to none (K = 3: class_sums, the same
-// operations in the same order).  cls[u] is the class byte of node u: a pointer, or a view with an operator[]
-// (large_search.hip keeps the bytes of one candidate a stride apart).
+// W_k = sum of the weights of the edges of local row l to neighbours of class k, fp32, in the CSR order of the row,
+// self-loops skipped, a class byte outside 0..K-1 adding to none.  K sums chosen by compares (an indexed private array
+// would live in scratch).  rp[l] .. rp[l + 1] are the row's edges in col / vals (NULL: all ones).  cls[u] is the class
+// byte of node u: a pointer, or a view with an operator[] (large_search.hip keeps the bytes of one candidate a stride
+// apart).
 template <int K, class RP, class COL, class CLS>
 __device__ __forceinline__ Sums<K> class_sums_k(const RP *rp, const COL *col, const float *vals, const CLS &cls,
                                                 int l) {
@@ -111,6 +84,57 @@ __device__ __forceinline__ bool anneal_move(const Sums<K> &w, int c, float inv_t
     wk = has_class ? wk : 0.f;
     const float delta = wk - wc;
     return delta < 0.f || delta * inv_t <= lv[h >> 54];
+}
+
+// One descent visit of local node l, the local search's rule: the node moves to the class kk of the smallest of its K
+// sums (lowest index on ties) iff W[kk] < W[own]; a byte of no class has W[own] = +inf, so such a node always moves.
+// g: a graph's CSR as one of anneal_layout.h's accessors (rp, col, vals); true iff the node moved.
+// The +inf is spelled as a test of the byte beside the compare, not as one more select in front of the own-sum chain:
+// the visit is the critical path of a colour step, and at K = 3 that select made the rounding's descent 3 % slower.
+template <int K, class G>
+__device__ __forceinline__ bool descent_visit(const G &g, unsigned char *cls, int l) {
+    const Sums<K> s = class_sums_k<K>(g.rp, g.col, g.vals, cls, l);
+    const int c = cls[l];
+    float wc = s.m[0];
+#pragma unroll
+    for (int j = 1; j < K; ++j) wc = c == j ? s.m[j] : wc;
+    float wk;
+    const int kk = smallest<K>(s, wk);
+    if (wk < wc || (unsigned)c >= (unsigned)K) {
+        cls[l] = (unsigned char)kk;
+        return true;
+    }
+    return false;
+}
+
+// The descent of one 256-thread workgroup over the class bytes cls (LDS) of a graph of n nodes: sweeps over the colour
+// classes cptr[k0] .. cptr[k0 + classes] of the (colour, id) order behind g.node(), one thread per node of the current
+// class, a barrier between classes, a workgroup-wide OR closing every sweep; stops after a sweep that moved nothing or
+// after max_sweeps.  An entry of the order that is not a movable row of this graph (a terminal l < K, or l >= n) is
+// never visited and never touches LDS.  Every thread must call it with cls published; on return every thread may read
+// cls.  Returns the sweeps run, the last of them the one that moved nothing when the descent converged.
+template <int K, class G>
+__device__ __forceinline__ int descent_sweeps(const G &g, const int *cptr, int k0, int classes, unsigned char *cls,
+                                              int n, int max_sweeps) {
+    // blockDim.x is read once, ahead of the sweeps: read inside the loop it becomes a vector load on every colour
+    // step's critical path (the rounding at K = 3 ran 4.5 % slower; DESIGN.md section 23 has this and the other forms tried)
+    const int threads = blockDim.x;
+    int s = 0;
+    while (s < max_sweeps) {
+        ++s;
+        int moved = 0;
+        for (int k = 0; k < classes; ++k) {
+            const int hi = cptr[k0 + k + 1];
+            for (int i = cptr[k0 + k] + threadIdx.x; i < hi; i += threads) {
+                const int l = g.node(i);
+                if (l < K || l >= n) continue;
+                if (descent_visit<K>(g, cls, l)) moved = 1;
+            }
+            if (k + 1 < classes) __syncthreads();
+        }
+        if (!__syncthreads_or(moved)) break;
+    }
+    return s;
 }
 
 }  // namespace gmc

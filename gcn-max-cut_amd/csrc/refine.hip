@@ -12,10 +12,13 @@
 // code (cut_body.h).
 //
 // One workgroup per (candidate, graph): the candidate's classes live in LDS as bytes (n_max <= 4096 -> 4 KB), one
-// thread per node of the current class, a barrier between classes, a workgroup-wide OR closing every sweep.
+// thread per node of the current class, a barrier between classes, a workgroup-wide OR closing every sweep: the
+// descent every one-workgroup search ends with (move_body.h's descent_sweeps), here at K = 3 over the batch's arrays
+// and with nothing else in LDS - no level table, no best state, no staged graph.
 #include "gmc_common.h"
 #include "cut_body.h"
 #include "move_body.h"
+#include "anneal_layout.h"
 
 #include <vector>
 
@@ -39,32 +42,14 @@ __global__ __launch_bounds__(256) void refine_local_kernel(RefineArgs a) {
     const int cand = blockIdx.x, g = blockIdx.y;
     const int r0 = a.b.goff[g];
     const int n = a.b.goff[g + 1] - r0;
+    if (n > a.b.n_max || n < 3) return;   // (the LDS is sized by n_max; a graph without its 3 terminals is skipped)
     signed char *as = a.assign + (long)cand * a.b.R + r0;
     for (int l = threadIdx.x; l < n; l += blockDim.x) sa[l] = (unsigned char)as[l];
     __syncthreads();
     const int k0 = a.cgoff[g];
     const int classes = a.cgoff[g + 1] - k0 - 1;
-    int s = 0;
-    while (s < a.max_sweeps) {
-        ++s;
-        int moved = 0;
-        for (int k = 0; k < classes; ++k) {
-            const int hi = a.cptr[k0 + k + 1];
-            for (int i = a.cptr[k0 + k] + threadIdx.x; i < hi; i += blockDim.x) {
-                const int l = a.order[i] - r0;
-                if ((unsigned)l >= (unsigned)n) continue;   // not a row of this graph: never touch LDS for it
-                float w0, w1, w2;
-                gmc::class_sums(a.b.rowptr + r0, a.b.lcol, a.b.vals, sa, l, w0, w1, w2);
-                int kk;
-                if (gmc::local_move(w0, w1, w2, sa[l], kk)) {
-                    sa[l] = (unsigned char)kk;
-                    moved = 1;
-                }
-            }
-            if (k + 1 < classes) __syncthreads();
-        }
-        if (!__syncthreads_or(moved)) break;
-    }
+    const gmc::GlobalCsr csr{a.b.rowptr + r0, a.b.lcol, a.b.vals, a.order, r0};
+    const int s = gmc::descent_sweeps<3>(csr, a.cptr, k0, classes, sa, n, a.max_sweeps);
     for (int l = threadIdx.x; l < n; l += blockDim.x) as[l] = (signed char)sa[l];
     const float cut = gmc::block_cut(a.b, sa, r0, n, red);
     if (threadIdx.x == 0) {
@@ -73,7 +58,11 @@ __global__ __launch_bounds__(256) void refine_local_kernel(RefineArgs a) {
     }
 }
 
-__global__ __launch_bounds__(256) void refine_pick_kernel(gmc::PickArgs a) { gmc::pick_best(a); }
+__global__ __launch_bounds__(256) void refine_pick_kernel(gmc::PickArgs a) {
+    const int n = a.b.goff[blockIdx.x + 1] - a.b.goff[blockIdx.x];
+    if (n > a.b.n_max || n < 3) return;   // workgroup-uniform: the graphs the search skipped
+    gmc::pick_best(a);
+}
 
 }  // namespace
 

@@ -1,8 +1,8 @@
 // Rounding of node probabilities by conditional expectations, followed by the local search's descent (an extension:
 // the reference decodes by argmax or by random samples, TestingNeuralNetwork.py:66-122).  The algorithm is stated in
 // include/gcnmaxcut.h (gmc_round_conditional_f32); the colouring and the (colour, id) order are those of refine.hip
-// with the movable nodes starting at K (gmc_round_order_host), the descent is refine.hip's sweep at K classes, the
-// score is cut_body.h's.
+// with the movable nodes starting at K (gmc_round_order_host), the descent is the sweep loop refine.hip and the
+// annealing run (move_body.h's descent_sweeps, refine.hip's being its K = 3), the score is cut_body.h's.
 //
 // One 256-thread workgroup per graph, K a template argument.  The workgroup's LDS, sized by n_max:
 //
@@ -18,12 +18,12 @@
 #include "cut_body.h"
 #include "move_body.h"
 #include "round_body.h"
+#include "anneal_layout.h"
 
 namespace {
 
 using gmc::Sums;
-using gmc::class_sums_k;   // the sums over the class bytes and the pick of the smallest: move_body.h
-using gmc::smallest;
+using gmc::smallest;       // the pick of the smallest sum, and the descent over the class bytes: move_body.h
 using gmc::state_sums;     // the sums over the state and a row's share of the expected cut: round_body.h
 using gmc::expected_row;
 
@@ -88,32 +88,9 @@ __global__ __launch_bounds__(256) void round_conditional_kernel(RoundArgs a) {
         }
         __syncthreads();   // the next class, the descent or the cut count reads what this one wrote
     }
-    // descent: refine.hip's sweeps at K classes over the class bytes
-    int sw = 0;
-    while (sw < a.max_descent_sweeps) {
-        ++sw;
-        int moved = 0;
-        for (int k = 0; k < classes; ++k) {
-            const int hi = a.cptr[k0 + k + 1];
-            for (int i = a.cptr[k0 + k] + threadIdx.x; i < hi; i += blockDim.x) {
-                const int l = a.order[i] - r0;
-                if (l < K || l >= n) continue;
-                const Sums<K> s = class_sums_k<K>(rp, col, vals, cls, l);
-                const int c = cls[l];
-                float wc = s.m[0];
-#pragma unroll
-                for (int j = 1; j < K; ++j) wc = c == j ? s.m[j] : wc;
-                float wk;
-                const int kk = smallest<K>(s, wk);
-                if (wk < wc) {
-                    cls[l] = (unsigned char)kk;
-                    moved = 1;
-                }
-            }
-            if (k + 1 < classes) __syncthreads();
-        }
-        if (!__syncthreads_or(moved)) break;
-    }
+    // descent: the local search's sweeps at K classes over the class bytes
+    const gmc::GlobalCsr csr{rp, col, vals, a.order, r0};
+    const int sw = gmc::descent_sweeps<K>(csr, a.cptr, k0, classes, cls, n, a.max_descent_sweeps);
     signed char *as = a.assign + r0;
     for (int l = threadIdx.x; l < n; l += blockDim.x) as[l] = (signed char)cls[l];
     const float cut = gmc::block_cut(a.b, cls, r0, n, red);   // scored as gmc_refine_local_f32 scores
@@ -153,13 +130,6 @@ extern "C" int gmc_round_conditional_f32(const gmc_batch *batch, const float *P,
     hipStream_t st = static_cast<hipStream_t>(stream);
     const RoundArgs a{*batch, P, order, cgoff, cptr, max_descent_sweeps, reinterpret_cast<signed char *>(assign), cut,
                       expected, sweeps};
-    switch (K) {
-        case 2: return round_launch<2>(a, st);
-        case 3: return round_launch<3>(a, st);
-        case 4: return round_launch<4>(a, st);
-        case 5: return round_launch<5>(a, st);
-        case 6: return round_launch<6>(a, st);
-        case 7: return round_launch<7>(a, st);
-        default: return round_launch<8>(a, st);
-    }
+    GMC_KWAY_DISPATCH(K, return round_launch<KK>(a, st));
+    return GMC_OK;
 }

@@ -578,7 +578,7 @@ int gmc_decode_sample_f32(const gmc_batch *batch, const float *P, const double *
  *
  * The draw rule.  All arithmetic is modulo 2^64.
  *  - GOLD = 0x9E3779B97F4A7C15.
- *  - mix64 is the splitmix64 finaliser, exactly as in anneal.hip (stated at gmc_refine_anneal_f32 below).
+ *  - mix64 is the splitmix64 finaliser, exactly as in the annealing (stated at gmc_refine_anneal_f32 below).
  *  - A graph's key is key = mix64(seed + GOLD * (index + 1)).  index is the graph's position in its dataset, a
  *    non-negative integer.
  *  - The uniform for iteration it (0-based) and local node l of that graph is
@@ -602,7 +602,9 @@ int gmc_decode_sample_f32(const gmc_batch *batch, const float *P, const double *
  * equals the non-NULL call's.  Argument checks, before any HIP call, in the order of the other decoders: a NULL
  * pointer (assign_all aside) GMC_ERR_NULL, batch->abi GMC_ERR_ABI, a NULL goff / rowptr / lcol GMC_ERR_NULL,
  * iters < 1 or B < 0 GMC_ERR_SHAPE, n_max < 3 or n_max > 65535 GMC_ERR_GRAPH_SIZE; B == 0 returns GMC_OK without a
- * launch.  The call allocates nothing and does not synchronise: two launches on the caller's stream. */
+ * launch.  A graph with fewer than 3 or more than n_max nodes inside a batch is skipped (nothing of it is written), as
+ * gmc_round_conditional_f32 skips it.  The call allocates nothing and does not synchronise: two launches on the
+ * caller's stream.  This is gmc_kway_decode_sample_seeded_f32 at K = 3: the same kernels. */
 int gmc_decode_sample_seeded_f32(const gmc_batch *batch, const float *P, const uint64_t *gkey, int32_t iters,
                                  int8_t *assign_all, float *cut_all, int32_t *best_assign, float *best_cut,
                                  int32_t *best_iter, gmc_stream_t stream);
@@ -612,7 +614,7 @@ int gmc_decode_sample_seeded_f32(const gmc_batch *batch, const float *P, const u
  * Single-node-move refinement of candidate partitions, per graph of the batch (local ids 0..n-1, CSR rows of an
  * undirected graph, weight 1 where vals is NULL):
  *  - nodes 0, 1, 2 never move, whatever class they hold (override_fixed_nodes, TrainingNeural.py:87-94); the
- *    movable nodes are 3..n-1;
+ *    movable nodes are 3..n-1.  An entry of `order` that names a terminal, or no row of its graph, is not visited;
  *  - colouring: first-fit over the movable nodes in increasing id, a node taking the smallest colour no movable
  *    neighbour of smaller id holds (self-loops and neighbours 0..2 ignored), so each colour class is an independent
  *    set among movable nodes;
@@ -642,7 +644,8 @@ int gmc_refine_order_host(int32_t B, const int32_t *goff, const int32_t *rowptr,
  * sweeps [B][cands] (NULL: not written): the sweeps run, the last of them the one that moved nothing when the
  * candidate converged within max_sweeps.  Errors: a NULL pointer (sweeps aside) GMC_ERR_NULL, batch->abi
  * GMC_ERR_ABI, cands < 1 or max_sweeps < 0 GMC_ERR_SHAPE, n_max outside 3..GMC_MAX_GRAPH_NODES GMC_ERR_GRAPH_SIZE;
- * B == 0 launches nothing. */
+ * B == 0 launches nothing.  A graph with fewer than 3 or more than n_max nodes inside a batch is skipped (nothing of
+ * it is written), as gmc_round_conditional_f32 skips it. */
 int gmc_refine_local_f32(const gmc_batch *batch, const int32_t *order, const int32_t *cgoff, const int32_t *cptr,
                          int32_t cands, int8_t *assign, int32_t max_sweeps, float *cut_all, int32_t *best_assign,
                          float *best_cut, int32_t *best_idx, int32_t *sweeps, gmc_stream_t stream);
@@ -687,7 +690,10 @@ int gmc_refine_local_f32(const gmc_batch *batch, const int32_t *order, const int
  * input, s + 1 = from the snapshot taken after sweep s; sweeps [B][cands]: the descent sweeps run, counted as the
  * local search counts them.  Errors, all found before any HIP call: a NULL required pointer GMC_ERR_NULL, batch->abi
  * GMC_ERR_ABI, cands < 1, a negative sweep count or anneal_sweeps >= 2^20 (the counter layout) GMC_ERR_SHAPE, n_max
- * outside 3..GMC_MAX_GRAPH_NODES GMC_ERR_GRAPH_SIZE; B == 0 launches nothing.  Two launches on the caller's stream. */
+ * outside 3..GMC_MAX_GRAPH_NODES GMC_ERR_GRAPH_SIZE; B == 0 launches nothing.  A graph with fewer than 3 or more than
+ * n_max nodes inside a batch is skipped (nothing of it is written); an entry of `order` that names a terminal, or no
+ * row of its graph, is not visited.  Two launches on the caller's stream.  This is gmc_kway_refine_anneal_f32 at
+ * K = 3: the same kernels. */
 int gmc_refine_anneal_f32(const gmc_batch *batch, const int32_t *order, const int32_t *cgoff, const int32_t *cptr,
                           int32_t cands, int8_t *assign, const float *inv_temp, int32_t anneal_sweeps,
                           const float *levels, uint64_t seed, int32_t max_descent_sweeps, float *cut_all,
@@ -757,8 +763,10 @@ int gmc_round_conditional_f32(const gmc_batch *batch, const float *P /*[R,K]*/, 
  *
  * gmc_decode_sample_seeded_f32, gmc_refine_local_f32 and gmc_refine_anneal_f32 are 3-class.  The two entry points below
  * are the same decoders for the models of gmc_kway_forward: nodes 0..K-1 of every graph are the terminals of classes
- * 0..K-1, P has K columns, class bytes are 0..K-1.  At K = 3 every output of either equals, byte for byte, the output
- * of its 3-class counterpart.
+ * 0..K-1, P has K columns, class bytes are 0..K-1.  gmc_decode_sample_seeded_f32 and gmc_refine_anneal_f32 ARE these
+ * two at K = 3: they check their own arguments as stated above and then launch the same kernels, so every output is
+ * the K = 3 output by construction; gmc_refine_local_f32 keeps a kernel of its own (no level table, no best state, no
+ * staged graph in LDS) around the descent loop all of them share.
  *
  * The K-class draw rule.  All arithmetic is modulo 2^64; GOLD, mix64 and a graph's key are those of
  * gmc_decode_sample_seeded_f32.

@@ -1,15 +1,19 @@
-"""The K-class sampler and annealing (gmc_kway_decode_sample_seeded_f32, gmc_kway_refine_anneal_f32): kernel time next to
-the 3-class kernels, and the cut quality of search_dataset for a 4-class model.
+"""The K-class sampler and annealing (gmc_kway_decode_sample_seeded_f32, gmc_kway_refine_anneal_f32): kernel time per
+class count, and the cut quality of search_dataset for a 4-class model.
 
     python scratch/kway_search_timing.py OUT.json
+
+profiles/r12_kway_search.json was recorded by an earlier form of this script, when gmc_refine_anneal_f32 and
+gmc_decode_sample_seeded_f32 had 3-class kernels of their own: it also timed those ("anneal_3class", "sampler_3class")
+next to K = 3 and compared their outputs.  The 3-class entry points now launch the K = 3 instantiations, so those
+variants would time one kernel twice and are gone; scratch/decoder_merge_timing.py compares the two libraries.
 
 1. Kernel time on 160 graphs n = 1000 d = 7 (unit weights), from the library's event probe (device events around the
    launch), after a warm-up call of every variant, the variants alternating in one run, 3 windows of 6 calls, median and
    window medians:
-   - annealing, 201 uniform random candidates (terminals fixed), 100 sweeps, descent 100 at most: gmc_refine_anneal_f32
-     and gmc_kway_refine_anneal_f32 at K = 3 on the same candidates, then the K-class kernel at K = 2, 4, 8;
-   - the seeded sampler, 200 samples of softmax rows, assign_all written: gmc_decode_sample_seeded_f32 and the K-class
-     kernel at K = 3 on the same P, then K = 2, 4, 8.
+   - annealing, 201 uniform random candidates (terminals fixed), 100 sweeps, descent 100 at most:
+     gmc_kway_refine_anneal_f32 at K = 3, 2, 4, 8;
+   - the seeded sampler, 200 samples of softmax rows, assign_all written: the K-class kernel at K = 3, 2, 4, 8.
 2. Quality: the 4-class model of scratch/rounding_timing.py (same dataset, same training), 10 held-out d = 7 regular
    graphs per size n = 500, 1000: mean cut of argmax, rounded, rounded + descent, best of 200 seeded samples,
    search_dataset with anneal_sweeps = 0 (the local search over 202 candidates) and with 100 annealing sweeps.
@@ -81,26 +85,11 @@ def kernel_times():
                                                             hip.stream()), "kway sample")
         variants[f"anneal_kway_K{K}"] = ("anneal", anneal_k, pristine)
         variants[f"sampler_kway_K{K}"] = ("sample", sample_k, None)
-        if K == 3:
-            def anneal_3(order=order, cgoff=cgoff, cptr=cptr):
-                hip.check(lib.gmc_refine_anneal_f32(batch.ref(), p(order), p(cgoff), p(cptr), CANDS, p(work), p(inv_t),
-                                                    SWEEPS, p(levels), 1, 100, p(cut_all), p(best_assign), p(best_cut),
-                                                    p(best_idx), None, None, hip.stream()), "anneal")
-
-            def sample_3(P=P):
-                hip.check(lib.gmc_decode_sample_seeded_f32(batch.ref(), p(P), p(gkey), SAMPLES, p(assign_all), p(cut_all),
-                                                           p(best_assign), p(best_cut), p(best_idx), hip.stream()), "sample")
-            variants["anneal_3class"] = ("anneal", anneal_3, pristine)
-            variants["sampler_3class"] = ("sample", sample_3, None)
-    results = {}
-    for name, (_tag, launch, pristine) in variants.items():       # warm-up (code object load) and the results
+    for name, (_tag, launch, pristine) in variants.items():       # warm-up (code object load)
         if pristine is not None:
             work.copy_(pristine)
         launch()
         torch.cuda.synchronize()
-        results[name] = (work.clone() if pristine is not None else assign_all.clone(), cut_all.clone())
-    same = {k: bool(torch.equal(results[f"{k}_3class"][0], results[f"{k}_kway_K3"][0])
-                    and torch.equal(results[f"{k}_3class"][1], results[f"{k}_kway_K3"][1])) for k in ("anneal", "sampler")}
     ms = {name: [] for name in variants}
     for _ in range(WINDOWS * PER_WINDOW):
         for name, (tag, launch, pristine) in variants.items():
@@ -110,9 +99,7 @@ def kernel_times():
     torch.cuda.synchronize()
     out = {name: RT.summary(v) for name, v in ms.items()}
     out.update(B=batch.B, R=batch.R, candidates=CANDS, samples=SAMPLES, anneal_sweeps=SWEEPS,
-               staged=int(lib.gmc_refine_anneal_staged(batch.ref())), k3_outputs_equal_the_3class_kernels=same,
-               anneal_k3_over_3class=out["anneal_kway_K3"]["kernel_ms_median"] / out["anneal_3class"]["kernel_ms_median"],
-               sampler_k3_over_3class=out["sampler_kway_K3"]["kernel_ms_median"] / out["sampler_3class"]["kernel_ms_median"])
+               staged=int(lib.gmc_refine_anneal_staged(batch.ref())))
     return out
 
 

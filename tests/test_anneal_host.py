@@ -165,19 +165,22 @@ def test_staging_follows_the_lds_budget(built):
 
 
 def test_anneal_kernel_is_in_the_code_object_without_scratch(built):
+    """gmc_refine_anneal_f32 runs the K-class annealing kernel at K = 3: that instantiation is in the code object once,
+    without scratch, and no 3-class annealing kernel stands beside it."""
     lib_path = built.hip.LIB_PATH
     names = util.kernel_symbols(lib_path)
-    assert any("anneal_kernel" in s for s in names), sorted(names)
+    assert sum("anneal_k_kernel<3>" in s for s in names) == 1, sorted(names)
+    assert not any("anneal_kernel" in s or "anneal_pick_kernel" in s for s in names), sorted(names)
     assert sum("refine_local_kernel" in s for s in names) == 1
     seen = 0
     for co in util.gfx950_code_objects(lib_path):
         notes = subprocess.run([f"{util.ROCM_LLVM}/llvm-readelf", "--notes", "-"], input=co, capture_output=True,
                                check=True).stdout.decode()
         for entry in notes.split("\n  - ")[1:]:
-            if not ("anneal_kernel" in entry and ".name:" in entry):
+            if not ("anneal_k_kernel" in entry and ".name:" in entry):
                 continue
             fields = dict(l.strip().split(":", 1) for l in entry.splitlines() if l.strip().startswith("."))
-            if "anneal_kernel" not in fields.get(".name", ""):
+            if "anneal_k_kernelILi3E" not in fields.get(".name", ""):   # the mangled <3>
                 continue
             seen += 1
             assert int(fields[".private_segment_fixed_size"]) == 0

@@ -128,6 +128,94 @@ def test_a_graph_refines_the_same_whatever_graphs_precede_it_in_the_batch(pkg):
     check_against_restatement(pkg, [STAMP_GRAPH(), VICTIM_GRAPH()] * 20, 201, 100, seed=5)
 
 
+def test_a_terminal_named_by_order_is_not_visited(pkg):
+    """Nodes 0..K-1 never move, whatever class they hold - also when `order` names one.  Two 3-regular graphs of 16 nodes
+    (the second with real weights), two candidates whose terminals hold foreign classes (node 0 class 1, node 1 class 2,
+    node 2 class 0, at K = 4 node 3 class 0), and an `order` whose first entry of every graph's first colour class is
+    overwritten by that graph's row 0.  The first colour class is visited on the input state, where row 0's movable
+    neighbours hold its class, so that - checked here on the host - row 0 has strictly less weight towards some class
+    than towards the one it holds: a visit would move it.
+    gmc_refine_local_f32 (100 sweeps), gmc_refine_anneal_f32 (10 annealing sweeps + 100) and gmc_kway_refine_anneal_f32
+    at K = 3 and 4 leave the terminals' bytes alone, report the cut of what they return and pick from it.
+
+    The cut of the unit-weight graph is exact.  On the weighted graph the kernel adds its m = 48 CSR weights (sum S) in
+    fp32 in some order, every partial sum <= S, so it is within m * 2^-24 * S of the float64 sum, half of that after
+    the division by 2."""
+    from gcn_max_cut_amd.graph import GraphBatch
+    from tests import anneal_ref as AR
+    hip = pkg.hip
+    lib, p = hip.load(), hip.ptr
+    hs = handles_of([R.regular_graph(16, 3, 41), weighted(R.regular_graph(16, 3, 42), "float", 6)])
+    batch = GraphBatch(hs, None, torch.device("cuda"))
+    h = batch.host
+    go32 = h.goff.astype(np.int32)
+    host = lambda a: a.ctypes.data_as(C.c_void_p)
+
+    def edited_order(K, refine_entry):
+        order, cgoff, cptr = np.zeros(h.R, np.int32), np.zeros(h.B + 1, np.int32), np.zeros(h.R + h.B, np.int32)
+        if refine_entry:
+            rc = lib.gmc_refine_order_host(h.B, host(go32), host(h.rowptr), host(h.lcol), host(order), host(cgoff),
+                                           host(cptr), cptr.size)
+        else:
+            rc = lib.gmc_round_order_host(h.B, host(go32), host(h.rowptr), host(h.lcol), K, host(order), host(cgoff),
+                                          host(cptr), cptr.size)
+        hip.check(rc, "order")
+        for g in range(h.B):
+            assert cptr[cgoff[g] + 1] > cptr[cgoff[g]]                  # the first colour class has an entry
+            order[cptr[cgoff[g]]] = go32[g]                             # ... which now names the graph's row 0
+        return [torch.from_numpy(a).cuda() for a in (order, cgoff, cptr)]
+
+    def candidates(K):
+        A = np.random.RandomState(50 + K).randint(0, K, (2, h.R)).astype(np.int8)
+        for g, hd in enumerate(hs):
+            nbrs = np.asarray(hd.col[hd.rowptr[0]:hd.rowptr[1]])
+            A[:, go32[g] + nbrs[nbrs >= K]] = 1                         # row 0's movable neighbours share its class
+            A[:, go32[g]:go32[g] + K] = [1, 2, 0, 0][:K]
+        for g, hd in enumerate(hs):                                     # a visit would move row 0: the case is not vacuous
+            for a in A[:, go32[g]:go32[g + 1]]:
+                W = np.zeros(K)
+                for e in range(hd.rowptr[0], hd.rowptr[1]):
+                    W[a[hd.col[e]]] += 1.0 if hd.weight is None else hd.weight[e]
+                assert W.min() < W[a[0]], (K, g)
+        return A
+
+    inv_t = torch.from_numpy(AR.schedule(10)).cuda()
+    lv = torch.from_numpy(AR.levels()).cuda()
+
+    def run(K, call):
+        A = candidates(K)
+        assign = torch.from_numpy(A).cuda()
+        cut_all = torch.full((h.B, 2), float("nan"), device="cuda")
+        best_assign = torch.full((h.R,), GARBAGE, dtype=torch.int32, device="cuda")
+        best_cut = torch.full((h.B,), float("nan"), device="cuda")
+        best_idx = torch.full((h.B,), GARBAGE, dtype=torch.int32, device="cuda")
+        hip.check(call(p(assign), (p(cut_all), p(best_assign), p(best_cut), p(best_idx))), f"K = {K}")
+        torch.cuda.synchronize()
+        out, cuts, ba, bi = (t.cpu().numpy() for t in (assign, cut_all, best_assign, best_idx))
+        for g, hd in enumerate(hs):
+            lo, hi = int(go32[g]), int(go32[g + 1])
+            assert (out[:, lo:lo + K] == A[:, lo:lo + K]).all(), (K, g, out[:, lo:lo + K].tolist())
+            assert ((out[:, lo:hi] >= 0) & (out[:, lo:hi] < K)).all()
+            ref = np.array([RR.cut(hd.rowptr, hd.col, hd.weight, a) for a in out[:, lo:hi]])
+            if hd.weight is None:
+                assert (cuts[g] == ref).all(), (K, g)
+            else:
+                w = np.asarray(hd.weight, np.float64)
+                assert np.abs(cuts[g] - ref).max() <= w.size * 2.0 ** -24 * w.sum() / 2, (K, g)
+            assert bi[g] == int(np.argmax(cuts[g])) and (ba[lo:hi] == out[bi[g], lo:hi]).all()
+
+    o3 = edited_order(3, True)
+    run(3, lambda a, outs: lib.gmc_refine_local_f32(batch.ref(), p(o3[0]), p(o3[1]), p(o3[2]), 2, a, 100, *outs, None,
+                                                    hip.stream()))
+    run(3, lambda a, outs: lib.gmc_refine_anneal_f32(batch.ref(), p(o3[0]), p(o3[1]), p(o3[2]), 2, a, p(inv_t), 10,
+                                                     p(lv), 1, 100, *outs, None, None, hip.stream()))
+    for K in (3, 4):
+        ok = edited_order(K, False)
+        run(K, lambda a, outs: lib.gmc_kway_refine_anneal_f32(batch.ref(), K, p(ok[0]), p(ok[1]), p(ok[2]), 2, a,
+                                                              p(inv_t), 10, p(lv), 1, 100, *outs, None, None,
+                                                              hip.stream()))
+
+
 @pytest.mark.parametrize("cands,max_sweeps", [(1, 100), (201, 100), (201, 1)])
 def test_fp32_weights_match_the_restatement(pkg, cands, max_sweeps):
     graphs = [weighted(R.regular_graph(300, 7, 17), "float", 3), weighted(loop_graph(120, 5, 18), "float", 4)]

@@ -145,24 +145,28 @@ def test_seeded_entry_point_checks_arguments_without_a_gpu(built):
 
 
 def test_seeded_kernels_are_in_the_code_object_without_scratch(built):
+    """gmc_decode_sample_seeded_f32 runs the K-class sampler's two kernels at K = 3: each instantiation is in the code
+    object once, without scratch, and no 3-class sampler kernel stands beside them."""
     lib_path = built.hip.LIB_PATH
     names = util.kernel_symbols(lib_path)
-    for kernel in ("sample_seeded_kernel", "sample_seeded_pick_kernel"):
-        assert any(kernel + "(" in s for s in names), sorted(names)
+    for kernel in ("sample_seeded_k_kernel<3>", "sample_seeded_k_pick_kernel<3>"):
+        assert sum(kernel + "(" in s for s in names) == 1, sorted(names)
+    assert not any("sample_seeded_kernel" in s or "sample_seeded_pick_kernel" in s for s in names), sorted(names)
     seen = 0
     for co in util.gfx950_code_objects(lib_path):
         notes = subprocess.run([f"{util.ROCM_LLVM}/llvm-readelf", "--notes", "-"], input=co, capture_output=True,
                                check=True).stdout.decode()
         for entry in notes.split("\n  - ")[1:]:
-            if "sample_seeded_kernel" not in entry or ".name:" not in entry:
+            if "sample_seeded_k_" not in entry or ".name:" not in entry:
                 continue
             fields = dict(l.strip().split(":", 1) for l in entry.splitlines() if l.strip().startswith("."))
-            if "sample_seeded_kernel" not in fields.get(".name", ""):
+            name = fields.get(".name", "")
+            if "sample_seeded_k_kernelILi3E" not in name and "sample_seeded_k_pick_kernelILi3E" not in name:   # <3>
                 continue
             seen += 1
             assert int(fields[".private_segment_fixed_size"]) == 0
             assert int(fields[".vgpr_spill_count"]) == 0
-    assert seen == 1
+    assert seen == 2
 
 
 def test_probe_tag():
