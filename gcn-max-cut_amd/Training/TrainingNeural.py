@@ -37,6 +37,7 @@ import torch.nn.functional as F  # noqa: F401
 from .. import hip
 from ..commons import open_file, save_object  # noqa: F401
 from ..engine import PARAM_ORDER, FusedEngine, device_cut_loss, dp_active, shard_by_weight, shard_for_rank  # noqa: F401
+from ..engine import InstanceEngine, check_instance_sizes, module_of
 from ..graph import GraphBatch, GraphHandle
 from ..trainer import FusedTrainer, Launch, _graphs_per_step, launch_path  # noqa: F401  (the launch machinery)
 
@@ -563,6 +564,92 @@ def train_model(dataset: Dict, config: TrainingConfig, dataset_files: Optional[L
         say(f'Final model saved to {final_filename}')
 
     return net, best_loss, epoch, embed.weight, loss_history
+
+
+def instance_chunks(sizes: List[int], max_rows_per_chunk: int) -> List[range]:
+    """Consecutive runs of a dataset's graphs with at most ``max_rows_per_chunk`` nodes each (a graph larger than that is
+    a chunk of its own), in dataset order."""
+    if max_rows_per_chunk < 1:
+        raise ValueError(f"max_rows_per_chunk must be positive, got {max_rows_per_chunk}")
+    chunks, start, rows = [], 0, 0
+    for i, n in enumerate(sizes):
+        if i > start and rows + n > max_rows_per_chunk:
+            chunks.append(range(start, i))
+            start, rows = i, 0
+        rows += n
+    if len(sizes) > start:
+        chunks.append(range(start, len(sizes)))
+    return chunks
+
+
+def solve_dataset(dataset: Dict, config: TrainingConfig, *, loss: Optional[str] = None,
+                  max_rows_per_chunk: int = 1 << 18) -> List[Dict]:
+    """Give every graph of ``dataset`` (the reference's items) ITS OWN model and train them all at once: the reference's
+    architecture as the instance-wise solver it is - ``conv1.weight[i]`` is the embedding of node id i, which means
+    something on the graph it was trained on only.  Graph g gets a ``GCNSoftmax(n_g, hidden_dim, number_classes)``,
+    initialised as the reference initialises a model of ``n_nodes = n_g`` (graph by graph in dataset order from torch's
+    generator); one launch sequence per step trains a whole chunk of them (:class:`gcn_max_cut_amd.engine.InstanceEngine`,
+    gmc_inst_*), and nothing couples two graphs.
+
+    ``config.number_classes`` (2..8), ``hidden_dim`` (ONE width for the call), ``learning_rate``, ``number_epochs`` and
+    ``C`` are honoured; ``loss`` as for :func:`train_single_epoch`.  The dataset is cut into chunks of at most
+    ``max_rows_per_chunk`` nodes, solved one after the other; every chunk runs ``number_epochs`` steps of
+    train_fwd_bwd -> Adam -> keep_best.  There is NO per-graph early stopping: ``tolerance`` and ``patience`` are ignored
+    (a graph that has converged costs its share of every later step).
+
+    Returns one dict per graph, in dataset order: ``best_loss`` / ``best_epoch`` (the lowest loss of the graph over the
+    epochs - measured before that epoch's update - and the first epoch that reached it), ``partition`` (the decode of
+    that epoch, nodes 0..K-1 in classes 0..K-1), ``cut`` (``calculate_cut_value`` of it), ``probabilities`` (the LAST
+    epoch's P [n_g, K], a CPU tensor), ``loss_history`` (the graph's loss per epoch) and ``model``: a zero-argument
+    callable returning a ``GCNSoftmax`` with the graph's parameters after the last step (as train_model's "best" state
+    aliases the live parameters), for ``evaluate_model``, ``round_dataset``, ``search_dataset`` and
+    ``sampling_optimization`` on that graph.
+
+    Refused: ``dropout > 0`` and ``layer1 = "attention"`` (NotImplementedError), a graph beyond the one-workgroup head
+    (ValueError: ``train_model`` serves one large graph), a graph with fewer than number_classes nodes (ValueError)."""
+    from ..Testing.TestingNeuralNetwork import calculate_cut_value
+    loss = hip.loss_name(loss)
+    if config.dropout > 0:
+        raise NotImplementedError(f"dropout = {config.dropout}: solve_dataset trains without dropout (the per-graph "
+                                  "models run the K-class row-kernel sequence)")
+    if hip.layer1_name(None) == "attention":
+        raise NotImplementedError("layer1 = 'attention' (GCN_MAXCUT_LAYER1): solve_dataset is implemented for layer1 = "
+                                  "'graphconv' only")
+    K, F = int(config.number_classes), int(config.hidden_dim)
+    items = list(dataset.values())
+    sizes = [it[0].n for it in items]
+    check_instance_sizes(sizes, K, loss)
+    results: List[Dict] = []
+    for chunk in instance_chunks(sizes, max_rows_per_chunk):
+        part = [items[i] for i in chunk]
+        handles = [it[0] for it in part]
+        eng = InstanceEngine(handles, F, K, values=[h.edge_values(it[1]) for h, it in zip(handles, part)])
+        eng.reset_parameters()
+        history = torch.empty((max(config.number_epochs, 0), eng.B), dtype=torch.float32, device=eng.device)
+        P = None
+        for epoch in range(config.number_epochs):
+            P, S, losses = eng.train_fwd_bwd(config.C, loss=loss)
+            eng.adam_step(config.learning_rate)
+            eng.keep_best(S, losses, epoch)
+            history[epoch].copy_(losses)
+        history = history.cpu()
+        best_S, best_loss, best_epoch = eng.best_S.cpu(), eng.best_loss.cpu(), eng.best_epoch.cpu()
+        P = None if P is None else P.cpu()
+        parameters = eng.parameters()
+        goff = [0]
+        for h in handles:
+            goff.append(goff[-1] + h.n)
+        for g, (_handle, _a_pad, nx_graph, _terminals) in enumerate(part):
+            partition = [int(s) for s in best_S[goff[g]:goff[g + 1]]]
+            params = parameters[g]
+            results.append({
+                'best_loss': float(best_loss[g]), 'best_epoch': int(best_epoch[g]), 'partition': partition,
+                'cut': calculate_cut_value(partition, nx_graph),
+                'probabilities': None if P is None else P[goff[g]:goff[g + 1]].clone(),
+                'loss_history': [float(x) for x in history[:, g]],
+                'model': (lambda params=params: module_of(params)),
+            })
+    return results
 
 
 def train_from_pickle(dataset_filename: str, model_name: str, n_nodes: int = 1000, **kwargs) -> Tuple:

@@ -663,6 +663,143 @@ extern "C" int gmc_large_required(const gmc_batch *batch, const gmc_model *model
     return kway_too_large(batch, model) ? 1 : 0;                            // gmc_kway_*: kway_check()
 }
 
+// ---- one model per graph: the K-class row-kernel sequence with the grouped kernels of instance.hip -------------------------
+// model: W1 [R,F] (row goff[g] + l = node l of graph g), b1 [B,F], W2 [B,F,K], b2 [B,K]; model->N must be batch->R.
+namespace {
+
+struct InstWorkspace {
+    long ld;         // leading dimension of the [R,F] buffers (F rounded up to 32 floats)
+    float *T0;       // [R,ld]  dinv o (A_val @ W1), later Gs = dinv o Gpre
+    float *H;        // [R,ld]  dinv o (A @ T0), then relu(. + b1_g), later U = dinv o (A @ Gs)
+    float *Z0;       // [R,K]
+    float *GY2;      // [R,K]
+    float *part;     // [slots,F,K+1]
+    size_t bytes;
+};
+
+// base == nullptr: sizes only
+InstWorkspace inst_carve(const gmc_batch *b, const gmc_model *m, bool training, void *base) {
+    InstWorkspace w{};
+    size_t off = 0;
+    auto take = [&](size_t floats) {
+        float *p = base ? reinterpret_cast<float *>(static_cast<char *>(base) + off) : nullptr;
+        off += align_up(floats * sizeof(float));
+        return p;
+    };
+    const size_t R = (size_t)b->R, F = (size_t)m->F, K = (size_t)m->K;
+    w.ld = (long)((F + 31) / 32 * 32);
+    w.T0 = take(R * w.ld);
+    w.H = take(R * w.ld);
+    w.Z0 = take(R * K);
+    if (training) {
+        w.GY2 = take(R * K);
+        w.part = take(gmc_inst_part_floats(b, m->F, m->K));
+    }
+    w.bytes = off;
+    return w;
+}
+
+// steps 1 and 2 of the documented order (kway_check with the stacked W1: N is the batch's row count)
+int inst_check(const gmc_batch *b, const gmc_model *m) {
+    if (int rc = check_abi(b, m)) return rc;
+    if (!b->goff || !b->rowptr || !b->gcol || !b->lcol || !b->dinv) return GMC_ERR_NULL;
+    if (!m->W1 || !m->b1 || !m->W2 || !m->b2) return GMC_ERR_NULL;
+    if (!kway_classes_ok(m->K)) return GMC_ERR_CLASSES;
+    if (b->B < 0 || b->R < 0 || b->nnz < 0 || m->N < 0 || m->F <= 0) return GMC_ERR_SHAPE;
+    if (m->F % 4 || m->F > GMC_MAX_HIDDEN) return GMC_ERR_UNSUPPORTED;  // float4 rows
+    if (!(m->dropout_p >= 0.f && m->dropout_p < 1.f)) return GMC_ERR_SHAPE;
+    if (m->dropout_p > 0.f) return GMC_ERR_UNSUPPORTED;
+    if (m->W1_slab && !gmc_aligned16(m->W1_slab)) return GMC_ERR_ALIGN;
+    if (b->B > 0 && (b->n_max < m->K || kway_too_large(b, m))) return GMC_ERR_GRAPH_SIZE;
+    if (m->N != b->R) return GMC_ERR_SHAPE;  // W1 has one row per node of the batch
+    return GMC_OK;
+}
+
+struct InstCall {
+    const gmc_batch *b; const gmc_model *m;
+    InstWorkspace w{}; hipStream_t st = nullptr;
+};
+
+int inst_open(InstCall &c, bool training, void *workspace, size_t workspace_bytes, gmc_stream_t stream, const float *P,
+              const float *grad) {
+    if (int rc = inst_check(c.b, c.m)) return rc;                                    // 1. 2.
+    if (!workspace || !P || (training && !grad)) return GMC_ERR_NULL;                // 4. workspace and outputs
+    if (!gmc_aligned16(grad) || !gmc_aligned16(P) || !gmc_aligned16(c.m->W2)) return GMC_ERR_ALIGN;   // 5.
+    c.w = inst_carve(c.b, c.m, training, workspace);                                 // 6. size
+    if (c.w.bytes > workspace_bytes) return GMC_ERR_WORKSPACE;
+    c.st = static_cast<hipStream_t>(stream);
+    return GMC_OK;
+}
+
+// the blocks of the flat gradient [dW1 [R,F] | db1 [B,F] | dW2 [B,F,K] | db2 [B,K]]
+struct InstGrad { float *dW1, *db1, *dW2, *db2; size_t count; };
+InstGrad inst_grad(const gmc_batch *b, const gmc_model *m, float *grad) {
+    const size_t R = (size_t)b->R, B = (size_t)b->B, F = (size_t)m->F, K = (size_t)m->K;
+    InstGrad g{grad, grad + R * F, grad + R * F + B * F, grad + R * F + B * F + B * F * K, R * F + B * (F + F * K + K)};
+    return g;
+}
+
+// forward and head; db2 != nullptr (training): GY2 of the workspace and db2 [B,K] - the head's per-graph sums - as well
+int inst_forward_body(const InstCall &c, float C, float *P, int32_t *S, float *loss, float *db2) {
+    const gmc_batch *b = c.b; const gmc_model *m = c.m; const InstWorkspace &w = c.w;
+    const int F = m->F;
+    // T0 = dinv o (A_val @ W1): the gather of the stacked W1 by batch row id
+    int rc = gmc_spmm_launch(b->rowptr, b->gcol, b->vals, b->dinv, m->W1, F, nullptr, 0, w.T0, w.ld, b->R, F,
+                             group_rows(b), nullptr, nullptr, GMC_K_GATHER_W1, c.st);
+    if (rc) return rc;
+    // dinv o (A @ T0); the graph's own bias and the relu are inst_hw2's
+    rc = gmc_spmm_launch(b->rowptr, b->gcol, nullptr, b->dinv, w.T0, w.ld, nullptr, 0, w.H, w.ld, b->R, F, group_rows(b),
+                         nullptr, nullptr, GMC_K_AGG_FWD, c.st);
+    if (rc) return rc;
+    rc = gmc_inst_hw2_launch(b, w.H, w.ld, m->b1, m->W2, w.Z0, F, m->K, c.st);
+    if (rc) return rc;
+    return gmc_kway_head_launch(b, w.Z0, m->b2, C, m->K, loss_of(m), P, S, loss, db2 ? w.GY2 : nullptr, db2, c.st, m->K);
+}
+
+int inst_backward_body(const InstCall &c, const InstGrad &g) {
+    const gmc_batch *b = c.b; const gmc_model *m = c.m; const InstWorkspace &w = c.w;
+    float *Gs = w.T0, *U = w.H;
+    int rc = gmc_inst_hidden_bwd_launch(b, w.H, w.ld, w.GY2, m->W2, Gs, w.ld, w.part, m->F, m->K, c.st);
+    if (rc) return rc;
+    rc = gmc_inst_fold_launch(b, w.part, m->F, m->K, g.dW2, g.db1, c.st);
+    if (rc) return rc;
+    // conv1 backward aggregation:  U = dinv o (A @ Gs)
+    rc = gmc_spmm_launch(b->rowptr, b->gcol, nullptr, b->dinv, Gs, w.ld, nullptr, 0, U, w.ld, b->R, m->F, group_rows(b),
+                         nullptr, nullptr, GMC_K_AGG_BWD, c.st);
+    if (rc) return rc;
+    // dW1 = A_val^T @ U = A_val @ U (undirected graphs, symmetric weights): every row of W1 belongs to one node
+    return gmc_spmm_launch(b->rowptr, b->gcol, b->vals, nullptr, U, w.ld, nullptr, 0, g.dW1, m->F, b->R, m->F,
+                           group_rows(b), nullptr, nullptr, GMC_K_DW1, c.st);
+}
+
+}  // namespace
+
+extern "C" size_t gmc_inst_workspace_bytes(const gmc_batch *batch, const gmc_model *model, int training) {
+    if (check_abi(batch, model) || !kway_classes_ok(model->K)) return 0;
+    return inst_carve(batch, model, training != 0, nullptr).bytes;
+}
+
+extern "C" int gmc_inst_forward(const gmc_batch *batch, const gmc_model *model, float C, void *workspace,
+                                size_t workspace_bytes, float *P, int32_t *S, float *loss, gmc_stream_t stream) {
+    InstCall c{batch, model};
+    int rc = inst_open(c, false, workspace, workspace_bytes, stream, P, nullptr);
+    if (rc || batch->R == 0) return rc;
+    return inst_forward_body(c, C, P, S, loss, nullptr);
+}
+
+extern "C" int gmc_inst_train_fwd_bwd(const gmc_batch *batch, const gmc_model *model, float C, void *workspace,
+                                      size_t workspace_bytes, float *P, int32_t *S, float *loss, float *grad,
+                                      gmc_stream_t stream) {
+    InstCall c{batch, model};
+    int rc = inst_open(c, true, workspace, workspace_bytes, stream, P, grad);
+    if (rc) return rc;
+    const InstGrad g = inst_grad(batch, model, grad);
+    if (batch->R == 0)   // an empty batch: its gradient (B * (F + F*K + K) floats: none when B is 0 too) is zero
+        return g.count ? (int)hipMemsetAsync(grad, 0, g.count * sizeof(float), c.st) : GMC_OK;
+    rc = inst_forward_body(c, C, P, S, loss, g.db2);
+    return rc ? rc : inst_backward_body(c, g);
+}
+
 // ---- graph-attention first layer: the row-kernel sequence with the kernels of attention.hip -------------------------------
 namespace {
 

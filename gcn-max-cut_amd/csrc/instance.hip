@@ -1,0 +1,275 @@
+// One model per graph (include/gcnmaxcut.h, gmc_inst_*): the kernels of the K-class row-kernel sequence that have to know
+// which graph a row belongs to, because every graph of the batch brings its own conv1.bias, conv2.weight and conv2.bias.
+//   inst_hw2_k         H[r,:] = relu(Hpre[r,:] + b1_g) written back in place, Z0[r,:] = dinv[r] * (H[r,:] @ W2_g)   [R,K]
+//                      (hw2_k_kernel of kway.hip with the row's graph selecting b1 and W2; the per-graph bias and the
+//                      relu of layer 1 ride in front of it, so H is read and written once for both)
+//   inst_hidden_bwd_k  Gs = dinv o relu'(H) o dinv o (GY2 @ W2_g^T), tile partials of dW2_g [F,K] and db1_g [F]
+//                      (hidden_bwd_k_kernel of kway.hip over tiles that start at the graph's first row)
+//   inst_fold          dW2_g, db1_g = the graph's tile partials, added in ascending tile order
+//   keep_best          rows of S -> best_S for the graphs whose loss improved, then best_loss / best_epoch
+// The head is head_k_kernel of kway.hip with a bias stride (gmc_kway_head_launch); the W1 gather, both F-wide
+// aggregations and dW1 are gmc_spmm_launch; Adam is adam.hip's over the flat buffer.
+//
+// Grid of the row kernels: (graph, tile of the graph's rows) as in large.hip - blockIdx.x is the graph, so a row's graph
+// is known without a search and without a [R] graph-id array; a tile past the graph's end returns at once.  A tile's
+// partials live in slot goff[g] / 64 + g + tile (large.hip's scheme: disjoint for any sizes, R / 64 + B + 1 in all).
+// No float atomics; every sum in a fixed order that depends on the graph alone: a graph's results have the same bits
+// wherever it stands in a batch and whatever stands next to it.
+#include "kway_rows.h"
+
+namespace {
+
+// ---- inst_hw2_k -----------------------------------------------------------------------------------------------------
+struct InstHw2Args {
+    const int *goff;
+    float *H;            // [R,ld] in: dinv o (A @ T0); out: relu(. + b1_g)
+    const float *dinv;
+    const float *b1;     // [B,F]
+    const float *W2;     // [B,F,K]
+    float *Z0;           // [R,K]
+    int F;
+    long ld;
+};
+
+// one wave per row, fixed-order butterfly sum; grid (B, ceil(n_max / 4))
+template <int K>
+__global__ __launch_bounds__(256) void inst_hw2_k_kernel(InstHw2Args a) {
+    const int g = blockIdx.x;
+    const int r0 = a.goff[g];
+    const int n = a.goff[g + 1] - r0;
+    const int l = gmc::uniform((int)(blockIdx.y * 4 + (threadIdx.x >> 6)));
+    if (l >= n) return;
+    const long r = (long)r0 + l;
+    const int lane = gmc::lane_id();
+    const float *b1 = a.b1 + (long)g * a.F;
+    const float *W2 = a.W2 + (long)g * a.F * K;
+    float *h_row = a.H + r * a.ld;
+    float z[K] = {};
+    for (int c = lane; c < a.F; c += GMC_WAVE) {
+        const float pre = h_row[c] + b1[c];
+        const float h = pre > 0.f ? pre : 0.f;
+        h_row[c] = h;
+        float w[K];
+        load_row<K>(W2, c, w);
+#pragma unroll
+        for (int k = 0; k < K; ++k) z[k] = fmaf(h, w[k], z[k]);
+    }
+#pragma unroll
+    for (int k = 0; k < K; ++k) z[k] = gmc::wave_sum(z[k]);
+    if (lane == 0) {
+        const float d = a.dinv[r];
+#pragma unroll
+        for (int k = 0; k < K; ++k) z[k] *= d;
+        store_row<K>(a.Z0, r, z);
+    }
+}
+
+// ---- inst_hidden_bwd_k ----------------------------------------------------------------------------------------------
+constexpr int kTileRows = 64;     // rows per workgroup
+constexpr int kColThreads = 128;  // x float4 = 512 columns per grid.z slice
+constexpr int kRowLanes = 2;
+
+struct InstHiddenArgs {
+    const int *goff;
+    const float *H;
+    long ldh;
+    const float *GY2;  // [R,K]
+    const float *W2;   // [B,F,K]
+    const float *dinv;
+    float *Gs;
+    long ldg;
+    float *part;       // [slots][F][K+1] = (dW2[f,0..K-1], db1[f])
+    int F;
+};
+
+// hidden_bwd_k_kernel of kway.hip per (graph, tile, column slice); the two row lanes take the tile's even and odd rows
+// counted from the graph's first row
+template <int K>
+__global__ __launch_bounds__(kColThreads * kRowLanes) void inst_hidden_bwd_k_kernel(InstHiddenArgs a) {
+    __shared__ float red[4][K + 1][kColThreads];
+    const int g = blockIdx.x;
+    const int r0 = a.goff[g];
+    const int n = a.goff[g + 1] - r0;
+    if ((int)blockIdx.y * kTileRows >= n) return;   // (workgroup-uniform)
+    const int ct = threadIdx.x & (kColThreads - 1);
+    const int rl = gmc::uniform((int)(threadIdx.x / kColThreads));
+    const int c4 = blockIdx.z * kColThreads + ct;  // float4 column index
+    const int F4 = a.F >> 2;
+    const bool on = c4 < F4;
+    const int cl = on ? c4 : F4 - 1;
+    const float *W2 = a.W2 + (long)g * a.F * K;
+    float w[4][K];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) load_row<K>(W2, cl * 4 + j, w[j]);
+
+    float dw[4][K] = {};
+    float db[4] = {};
+    const int rbeg = r0 + (int)blockIdx.y * kTileRows;
+    const int rend = min(rbeg + kTileRows, r0 + n);
+#pragma unroll 2
+    for (int r = rbeg + rl; r < rend; r += kRowLanes) {
+        const float4 h = reinterpret_cast<const float4 *>(a.H + (long)r * a.ldh)[cl];
+        const float d = a.dinv[r];
+        float gy[K];
+        load_row<K>(a.GY2, r, gy);   // (wave-uniform address: scalar loads)
+        const float hv[4] = {h.x, h.y, h.z, h.w};
+        float gs[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            float gh = gy[0] * w[j][0];
+#pragma unroll
+            for (int k = 1; k < K; ++k) gh += gy[k] * w[j][k];
+            const float gpre = hv[j] > 0.f ? gh * d : 0.f;
+            gs[j] = gpre * d;
+            db[j] += gpre;
+            const float hd = hv[j] * d;
+#pragma unroll
+            for (int k = 0; k < K; ++k) dw[j][k] = fmaf(hd, gy[k], dw[j][k]);
+        }
+        if (on) reinterpret_cast<float4 *>(a.Gs + (long)r * a.ldg)[c4] = make_float4(gs[0], gs[1], gs[2], gs[3]);
+    }
+    // fold the row lanes (fixed order), then K + 1 floats per (thread, column)
+    if (rl == 1) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+#pragma unroll
+            for (int k = 0; k < K; ++k) red[j][k][ct] = dw[j][k];
+            red[j][K][ct] = db[j];
+        }
+    }
+    __syncthreads();
+    if (rl == 0 && on) {
+        const long slot = (long)(r0 / kTileRows) + g + blockIdx.y;
+        float *out = a.part + (slot * a.F + (long)c4 * 4) * (K + 1);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+#pragma unroll
+            for (int k = 0; k < K; ++k) out[j * (K + 1) + k] = dw[j][k] + red[j][k][ct];
+            out[j * (K + 1) + K] = db[j] + red[j][K][ct];
+        }
+    }
+}
+
+// ---- inst_fold ------------------------------------------------------------------------------------------------------
+struct InstFoldArgs {
+    const int *goff;
+    const float *part;
+    int F, K;
+    float *dW2;   // [B,F,K]
+    float *db1;   // [B,F]
+};
+
+constexpr int kFoldThreads = 256;
+
+// thread = one of the F * (K + 1) entries of a graph's partial; the graph's tiles one after the other, ascending
+__global__ __launch_bounds__(kFoldThreads) void inst_fold_kernel(InstFoldArgs a) {
+    const int g = blockIdx.x;
+    const int i = blockIdx.y * kFoldThreads + threadIdx.x;
+    const int per = a.F * (a.K + 1);
+    if (i >= per) return;
+    const int r0 = a.goff[g];
+    const int n = a.goff[g + 1] - r0;
+    const int tiles = (n + kTileRows - 1) / kTileRows;
+    const float *p = a.part + ((long)(r0 / kTileRows) + g) * per + i;
+    float s = 0.f;
+    for (int t = 0; t < tiles; ++t) s += p[(long)t * per];
+    const int f = i / (a.K + 1), k = i - f * (a.K + 1);
+    if (k < a.K) a.dW2[((long)g * a.F + f) * a.K + k] = s;
+    else a.db1[(long)g * a.F + f] = s;
+}
+
+// ---- keep_best ------------------------------------------------------------------------------------------------------
+struct KeepArgs {
+    const int *goff;
+    const int *S;
+    const float *loss;
+    int *best_S;
+    float *best_loss;
+    int *best_epoch;
+    int epoch;
+    int B;
+};
+
+constexpr int kKeepRows = 256;
+
+// launch 1, grid (B, ceil(n_max / 256)): the rows of the graphs that improved.  best_loss is only read here - its store
+// is launch 2's, behind the kernel boundary, so every workgroup of a graph sees the same comparison.
+__global__ __launch_bounds__(kKeepRows) void keep_rows_kernel(KeepArgs a) {
+    const int g = blockIdx.x;
+    if (!(a.loss[g] < a.best_loss[g])) return;   // strict: the first minimum stays; a NaN loss never wins
+    const int r0 = a.goff[g];
+    const int l = (int)blockIdx.y * kKeepRows + (int)threadIdx.x;
+    if (l < a.goff[g + 1] - r0) a.best_S[r0 + l] = a.S[r0 + l];
+}
+
+// launch 2: one thread per graph
+__global__ __launch_bounds__(256) void keep_loss_kernel(KeepArgs a) {
+    const int g = blockIdx.x * 256 + threadIdx.x;
+    if (g >= a.B) return;
+    const float v = a.loss[g];
+    if (v < a.best_loss[g]) {
+        a.best_loss[g] = v;
+        a.best_epoch[g] = a.epoch;
+    }
+}
+
+}  // namespace
+
+size_t gmc_inst_part_floats(const gmc_batch *b, int F, int K) {
+    return ((size_t)b->R / kTileRows + (size_t)b->B + 1) * (size_t)F * (size_t)(K + 1);
+}
+
+int gmc_inst_hw2_launch(const gmc_batch *b, float *H, long ld, const float *b1, const float *W2, float *Z0, int F, int K,
+                        hipStream_t st) {
+    if (b->B == 0) return GMC_OK;
+    InstHw2Args a{b->goff, H, b->dinv, b1, W2, Z0, F, ld};
+    const dim3 grid(b->B, (b->n_max + 3) / 4);
+    GmcProbeScope probe(GMC_K_DENSE_MFMA, st);   // the tag of hw2_k in the K-class sequence
+    GMC_KWAY_DISPATCH(K, hipLaunchKernelGGL(inst_hw2_k_kernel<KK>, grid, dim3(256), 0, st, a));
+    GMC_LAUNCH_CHECK();
+    return GMC_OK;
+}
+
+// part must hold gmc_inst_part_floats(b, F, K) floats
+int gmc_inst_hidden_bwd_launch(const gmc_batch *b, const float *H, long ldh, const float *GY2, const float *W2, float *Gs,
+                               long ldg, float *part, int F, int K, hipStream_t st) {
+    if (F % 4 || ldh % 4 || ldg % 4) return GMC_ERR_ALIGN;
+    if (b->B == 0) return GMC_OK;
+    InstHiddenArgs a{b->goff, H, ldh, GY2, W2, b->dinv, Gs, ldg, part, F};
+    const dim3 grid(b->B, (b->n_max + kTileRows - 1) / kTileRows, (F / 4 + kColThreads - 1) / kColThreads);
+    GmcProbeScope probe(GMC_K_HIDDEN_BWD, st);
+    GMC_KWAY_DISPATCH(K, hipLaunchKernelGGL(inst_hidden_bwd_k_kernel<KK>, grid, dim3(kColThreads * kRowLanes), 0, st, a));
+    GMC_LAUNCH_CHECK();
+    return GMC_OK;
+}
+
+int gmc_inst_fold_launch(const gmc_batch *b, const float *part, int F, int K, float *dW2, float *db1, hipStream_t st) {
+    if (b->B == 0) return GMC_OK;
+    InstFoldArgs a{b->goff, part, F, K, dW2, db1};
+    const dim3 grid(b->B, (F * (K + 1) + kFoldThreads - 1) / kFoldThreads);
+    GmcProbeScope probe(GMC_K_COLSUM, st);
+    hipLaunchKernelGGL(inst_fold_kernel, grid, dim3(kFoldThreads), 0, st, a);
+    GMC_LAUNCH_CHECK();
+    return GMC_OK;
+}
+
+extern "C" int gmc_inst_keep_best_f32(const gmc_batch *batch, const int32_t *S, const float *loss, int32_t epoch,
+                                      int32_t *best_S, float *best_loss, int32_t *best_epoch, gmc_stream_t stream) {
+    if (!batch) return GMC_ERR_NULL;
+    if (batch->abi != GMC_VERSION) return GMC_ERR_ABI;
+    if (!batch->goff || !S || !loss || !best_S || !best_loss || !best_epoch) return GMC_ERR_NULL;
+    if (batch->B < 0 || batch->R < 0 || (batch->B > 0 && batch->n_max < 1)) return GMC_ERR_SHAPE;
+    if (batch->B == 0) return GMC_OK;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    KeepArgs a{batch->goff, S, loss, best_S, best_loss, best_epoch, epoch, batch->B};
+    {
+        GmcProbeScope probe(GMC_K_FINISH, st);
+        hipLaunchKernelGGL(keep_rows_kernel, dim3(batch->B, (batch->n_max + kKeepRows - 1) / kKeepRows), dim3(kKeepRows), 0,
+                           st, a);
+        GMC_LAUNCH_CHECK();
+    }
+    GmcProbeScope probe(GMC_K_FINISH, st);
+    hipLaunchKernelGGL(keep_loss_kernel, dim3((batch->B + 255) / 256), dim3(256), 0, st, a);
+    GMC_LAUNCH_CHECK();
+    return GMC_OK;
+}

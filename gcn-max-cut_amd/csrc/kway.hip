@@ -63,6 +63,7 @@ struct HeadKArgs {
     float *loss;
     float *GY2;        // [R,K]; nullptr: forward only
     float *db2part;    // [B,K]
+    long b2_stride;    // floats from one graph's bias to the next: 0 = one shared conv2.bias, K = b2 [B,K] (instance.hip)
 };
 
 // floats of dynamic LDS: sA [NP,K], sP [NP,K], SOFT: the terminals' own rows [K,K], sS [NP], the block sum's [waves, K+1]
@@ -91,7 +92,7 @@ __global__ __launch_bounds__(head_k_threads(K)) void head_k_kernel(HeadKArgs a) 
 
     float bias[K];
 #pragma unroll
-    for (int k = 0; k < K; ++k) bias[k] = a.b2[k];
+    for (int k = 0; k < K; ++k) bias[k] = a.b2[(long)g * a.b2_stride + k];
     for (int i = threadIdx.x; i < K * n; i += blockDim.x) sA[i] = a.Z0[(long)r0 * K + i];
     __syncthreads();
 
@@ -369,13 +370,13 @@ static int head_k_launch(const HeadKArgs &a, size_t lds, hipStream_t st) {
 
 // GY2 == nullptr: forward only.  The graphs' tiles must fit a CU's LDS (GMC_ERR_GRAPH_SIZE otherwise).
 int gmc_kway_head_launch(const gmc_batch *b, const float *Z0, const float *b2, float C, int K, int loss_kind, float *P,
-                         int32_t *S, float *loss, float *GY2, float *db2part, hipStream_t st) {
+                         int32_t *S, float *loss, float *GY2, float *db2part, hipStream_t st, long b2_stride) {
     if (!b || !Z0 || !b2 || !P || (GY2 && !db2part)) return GMC_ERR_NULL;
     if (K < 2 || K > GMC_KWAY_MAX_CLASSES) return GMC_ERR_CLASSES;
     const size_t lds = gmc_kway_head_lds_bytes(b->n_max, K, loss_kind);
     if (lds > GMC_KWAY_LDS_BYTES) return GMC_ERR_GRAPH_SIZE;
     if (b->B == 0) return GMC_OK;
-    HeadKArgs a{*b, Z0, b2, C, P, S, loss, GY2, db2part};
+    HeadKArgs a{*b, Z0, b2, C, P, S, loss, GY2, db2part, b2_stride};
     const bool soft = loss_kind == GMC_LOSS_EXPECTED_CUT;
     GMC_KWAY_DISPATCH(K, return soft ? head_k_launch<KK, true>(a, lds, st) : head_k_launch<KK, false>(a, lds, st));
     return GMC_OK;

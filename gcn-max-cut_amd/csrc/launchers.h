@@ -107,13 +107,25 @@ constexpr size_t GMC_KWAY_LDS_BYTES = 160 * 1024;   // a CU's LDS: what one grap
 size_t gmc_kway_head_lds_bytes(int n_max, int K, int loss_kind);
 int gmc_kway_hw2_launch(const float *H, long ld, const float *dinv, const float *W2, float *Z0, long R, int F, int K,
                         hipStream_t st);
-// GY2 == nullptr: forward only (P, S, loss); GMC_ERR_GRAPH_SIZE when gmc_kway_head_lds_bytes exceeds GMC_KWAY_LDS_BYTES
+// GY2 == nullptr: forward only (P, S, loss); GMC_ERR_GRAPH_SIZE when gmc_kway_head_lds_bytes exceeds GMC_KWAY_LDS_BYTES.
+// b2_stride: floats from one graph's conv2.bias to the next - 0 = the one shared bias, K = b2 [B,K] (the per-graph
+// models of instance.hip); the bias is read at b2 + g * b2_stride, so 0 is the launch it was before the argument
 int gmc_kway_head_launch(const gmc_batch *b, const float *Z0, const float *b2, float C, int K, int loss_kind, float *P,
-                         int32_t *S, float *loss, float *GY2, float *db2part, hipStream_t st);
+                         int32_t *S, float *loss, float *GY2, float *db2part, hipStream_t st, long b2_stride = 0);
 int gmc_kway_hidden_bwd_launch(const float *H, long ldh, const float *GY2, const float *W2, const float *dinv, float *Gs,
                                long ldg, float *part, int R, int F, int K, hipStream_t st);
 int gmc_kway_reduce_launch(const float *part, int tiles, int F, int K, float *dW2, float *db1, const float *db2part,
                            int B, float *db2, hipStream_t st);
+
+// ---- one model per graph (instance.hip): the kernels of the K-class sequence that select a graph's own b1 [B,F],
+// W2 [B,F,K] by the row's graph.  Grids are (graph, tile of the graph's rows); part: gmc_inst_part_floats floats.
+size_t gmc_inst_part_floats(const gmc_batch *b, int F, int K);
+// H [R,ld] in place: relu(H + b1_g); Z0[r,:] = dinv[r] * (H[r,:] @ W2_g)
+int gmc_inst_hw2_launch(const gmc_batch *b, float *H, long ld, const float *b1, const float *W2, float *Z0, int F, int K,
+                        hipStream_t st);
+int gmc_inst_hidden_bwd_launch(const gmc_batch *b, const float *H, long ldh, const float *GY2, const float *W2, float *Gs,
+                               long ldg, float *part, int F, int K, hipStream_t st);
+int gmc_inst_fold_launch(const gmc_batch *b, const float *part, int F, int K, float *dW2, float *db1, hipStream_t st);
 
 // ---- the head for graphs beyond a CU's LDS (large.hip): head_k_kernel as row-parallel launches, several workgroups per
 // graph (tiles of 256 rows).  Sw [R] ints, GZd [R,K] (dinv o GZ) and headpart [gmc_large_headpart_floats] are scratch.

@@ -513,6 +513,211 @@ class FusedEngine:
         return self.grad[self.count] if local_loss_sum is not None else None
 
 
+# ---- one model per graph ------------------------------------------------------------------------------------------------
+def instance_layout(sizes: Sequence[int], F: int, K: int) -> Tuple[List[int], int]:
+    """Offsets of the four blocks and the float count of the flat buffer of one model per graph (include/gcnmaxcut.h,
+    gmc_inst_*): ``[W1 [R,F] | b1 [B,F] | W2 [B,F,K] | b2 [B,K]]`` for graphs of ``sizes`` nodes, R = sum(sizes).  ``F`` is
+    the width the kernels see (a multiple of 4)."""
+    R, B = int(sum(int(n) for n in sizes)), len(sizes)
+    offs = [0]
+    for s in (R * F, B * F, B * F * K, B * K):
+        offs.append(offs[-1] + s)
+    return offs, offs[-1]
+
+
+def draw_instance_parameters(sizes: Sequence[int], F: int, K: int) -> List[Tuple[torch.Tensor, torch.Tensor]]:
+    """The reference's ``GraphConv`` init for one model of ``n_nodes = n_g`` per graph: graph by graph in batch order,
+    ``conv1.weight [n_g, F]`` and then ``conv2.weight [F, K]`` with ``nn.init.xavier_uniform_`` from torch's (CPU)
+    generator - uniform within sqrt(6 / (n_g + F)) and sqrt(6 / (F + K)); the biases are zero.  CPU tensors."""
+    out = []
+    for n in sizes:
+        w1, w2 = torch.empty(int(n), F), torch.empty(F, K)
+        torch.nn.init.xavier_uniform_(w1)
+        torch.nn.init.xavier_uniform_(w2)
+        out.append((w1, w2))
+    return out
+
+
+def instance_too_large(n_max: int, K: int, loss: str = "cut") -> bool:
+    """Is a graph of ``n_max`` nodes beyond what the one-workgroup head of gmc_kway_* / gmc_inst_* takes at ``K`` classes
+    and this loss?  The library decides (gmc_large_required: host only, no GPU)."""
+    if K == 3:   # (gmc_large_required answers for the fused 3-class entry points at K = 3; the bound here is gmc_kway_*'s)
+        return n_max > hip.MAX_GRAPH_NODES
+    model = hip.GmcModel(K=K, flags=hip.MODEL_LOSS_EXPECTED if hip.loss_kind(loss) else 0)
+    rc = int(hip.load().gmc_large_required(C.byref(hip.GmcBatch(B=1, n_max=int(n_max))), C.byref(model)))
+    if rc < 0:
+        hip.check(rc, "gmc_large_required")
+    return bool(rc)
+
+
+class InstanceEngine:
+    """One model PER GRAPH for a whole batch of graphs (gmc_inst_*): graph g of the batch has its own
+    ``conv1.weight [n_g, F]`` (one embedding row per node), ``conv1.bias``, ``conv2.weight [F, K]`` and ``conv2.bias``, and
+    one launch sequence trains all of them at once; nothing couples two graphs.  Owns the batch, the flat parameter
+    buffer ``[W1 [R,F] | b1 [B,F] | W2 [B,F,K] | b2 [B,K]]`` with gradient and Adam moments of the same layout, and the best
+    partition seen per graph.  It does not touch :class:`FusedEngine`; number_classes 2..8, both losses, layer1 =
+    graphconv, no dropout, graphs within the one-workgroup head's bound."""
+
+    def __init__(self, batch_handles, F: int, K: int, device: Optional[torch.device] = None, *, values=None):
+        self.device = device or hip.require_gpu()
+        self.lib = hip.load()
+        if not 2 <= K <= hip.KWAY_MAX_CLASSES:
+            raise ValueError(f"number_classes must be in 2..{hip.KWAY_MAX_CLASSES}, got {K} (nodes 0..K-1 of every graph "
+                             "are the terminals of classes 0..K-1)")
+        if F < 1 or F > MAX_HIDDEN:
+            raise ValueError(f"hidden_dim must be in 1..{MAX_HIDDEN} on this path (include/gcnmaxcut.h: GMC_MAX_HIDDEN), "
+                             f"got {F}")
+        handles = list(batch_handles)
+        check_instance_sizes([h.n for h in handles], K)
+        self.batch = GraphBatch(handles, values, self.device)
+        self.F, self.K, self.Fp = F, K, (F + 3) // 4 * 4   # (the kernels see the hidden width padded to float4 columns)
+        self.B, self.R = self.batch.B, self.batch.R
+        self.offs, self.count = instance_layout(self.batch.sizes, self.Fp, K)
+        self.flat = torch.zeros(self.count + 4, dtype=torch.float32, device=self.device)
+        self.grad = torch.zeros_like(self.flat)
+        self.m = torch.zeros_like(self.flat)
+        self.v = torch.zeros_like(self.flat)
+        self.step_count = 0
+        self.best_S = torch.zeros(self.R, dtype=torch.int32, device=self.device)
+        self.best_loss = torch.full((self.B,), float("inf"), dtype=torch.float32, device=self.device)
+        self.best_epoch = torch.full((self.B,), -1, dtype=torch.int32, device=self.device)
+        self._ws: Optional[torch.Tensor] = None
+
+    # ---- parameters
+    def blocks(self, buf: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
+        """The four stacked blocks as the kernels see them (hidden width padded to Fp): views of ``buf``."""
+        buf = self.flat if buf is None else buf
+        o, R, B, F, K = self.offs, self.R, self.B, self.Fp, self.K
+        return {"conv1.weight": buf[o[0]:o[1]].view(R, F), "conv1.bias": buf[o[1]:o[2]].view(B, F),
+                "conv2.weight": buf[o[2]:o[3]].view(B, F, K), "conv2.bias": buf[o[3]:o[4]].view(B, K)}
+
+    def views(self, g: int, buf: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
+        """Graph ``g``'s four tensors in the reference's shapes (``conv1.weight [n_g, F]``, ...): views of ``buf``
+        (default the parameters; ``eng.grad``, ``eng.m``, ``eng.v`` have the same layout)."""
+        b, F = self.blocks(buf), self.F
+        r0, r1 = int(self.batch.goff_host[g]), int(self.batch.goff_host[g + 1])
+        return {"conv1.weight": b["conv1.weight"][r0:r1, :F], "conv1.bias": b["conv1.bias"][g, :F],
+                "conv2.weight": b["conv2.weight"][g, :F], "conv2.bias": b["conv2.bias"][g]}
+
+    def reset_parameters(self) -> None:
+        """:func:`draw_instance_parameters` into the flat buffer (padding columns and biases zero), Adam state and the
+        kept partitions back to their start."""
+        for buf in (self.flat, self.grad, self.m, self.v):
+            buf.zero_()
+        for g, (w1, w2) in enumerate(draw_instance_parameters(self.batch.sizes, self.F, self.K)):
+            v = self.views(g)
+            v["conv1.weight"].copy_(w1)
+            v["conv2.weight"].copy_(w2)
+        self.step_count = 0
+        self.best_S.zero_()
+        self.best_loss.fill_(float("inf"))
+        self.best_epoch.fill_(-1)
+
+    def module(self, g: int):
+        """A ``GCNSoftmax(n_g, F, K)`` holding COPIES of graph ``g``'s parameters: ``evaluate_model``, ``round_dataset``,
+        ``search_dataset`` and ``sampling_optimization`` run on that graph with it as with any trained model.  (Building
+        it leaves torch's random generator where it was.)"""
+        return module_of({k: t.detach().cpu() for k, t in self.views(g).items()})
+
+    def parameters(self) -> List[Dict[str, torch.Tensor]]:
+        """CPU copies of every graph's four tensors, in batch order (one device-to-host copy of the flat buffer)."""
+        flat = self.flat.cpu()
+        return [{k: t.clone() for k, t in self.views(g, flat).items()} for g in range(self.B)]
+
+    def _model(self, loss: str) -> hip.GmcModel:
+        b = self.blocks()
+        return hip.GmcModel(N=self.R, F=self.Fp, K=self.K, flags=hip.MODEL_LOSS_EXPECTED if hip.loss_kind(loss) else 0,
+                            W1=hip.ptr(b["conv1.weight"]), b1=hip.ptr(b["conv1.bias"]), W2=hip.ptr(b["conv2.weight"]),
+                            b2=hip.ptr(b["conv2.bias"]))
+
+    # ---- compute
+    def workspace_bytes(self, training: bool) -> int:
+        model = hip.GmcModel(N=self.R, F=self.Fp, K=self.K)
+        return max(256, int(self.lib.gmc_inst_workspace_bytes(self.batch.ref(), C.byref(model), int(training))))
+
+    def _workspace(self, training: bool) -> torch.Tensor:
+        need = self.workspace_bytes(training)
+        if self._ws is None or self._ws.numel() < need:
+            self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        return self._ws
+
+    def _outputs(self, out=None):
+        if out is not None:
+            return out
+        return (torch.empty((self.R, self.K), dtype=torch.float32, device=self.device),
+                torch.empty(self.R, dtype=torch.int32, device=self.device),
+                torch.empty(self.B, dtype=torch.float32, device=self.device))
+
+    def forward(self, C_: float = 1.0, loss: str = "cut", out=None):
+        """(P [R,K], S [R], loss [B]) of every graph under its own model."""
+        P, S, losses = self._outputs(out)
+        if self.B == 0:
+            return P, S, losses
+        ws = self._workspace(False)
+        rc = self.lib.gmc_inst_forward(self.batch.ref(), C.byref(self._model(loss)), C_, hip.ptr(ws), ws.numel(),
+                                       hip.ptr(P), hip.ptr(S), hip.ptr(losses), hip.stream())
+        hip.check(rc, "gmc_inst_forward")
+        return P, S, losses
+
+    def train_fwd_bwd(self, C_: float = 1.0, loss: str = "cut", out=None):
+        """forward + loss + backward of every graph's own loss; the gradient lands in ``self.grad[:count]``."""
+        P, S, losses = self._outputs(out)
+        if self.B == 0:
+            self.grad.zero_()
+            return P, S, losses
+        ws = self._workspace(True)
+        rc = self.lib.gmc_inst_train_fwd_bwd(self.batch.ref(), C.byref(self._model(loss)), C_, hip.ptr(ws), ws.numel(),
+                                             hip.ptr(P), hip.ptr(S), hip.ptr(losses), hip.ptr(self.grad), hip.stream())
+        hip.check(rc, "gmc_inst_train_fwd_bwd")
+        return P, S, losses
+
+    def adam_step(self, lr: float, betas=(0.9, 0.999), eps: float = 1e-8) -> None:
+        """torch.optim.Adam.step over the flat buffer: every instance shares the step number."""
+        self.step_count += 1
+        if self.count == 0:
+            return
+        rc = self.lib.gmc_adam_f32(hip.ptr(self.flat), hip.ptr(self.grad), hip.ptr(self.m), hip.ptr(self.v), self.count,
+                                   lr, betas[0], betas[1], eps, self.step_count, hip.stream())
+        hip.check(rc, "gmc_adam_f32")
+
+    def keep_best(self, S: torch.Tensor, losses: torch.Tensor, epoch: int) -> None:
+        """For every graph whose loss is below its best so far (strictly: the first minimum wins, NaN never): its rows of
+        ``S`` into ``best_S``, the loss into ``best_loss``, ``epoch`` into ``best_epoch`` (gmc_inst_keep_best_f32)."""
+        if self.B == 0:
+            return
+        rc = self.lib.gmc_inst_keep_best_f32(self.batch.ref(), hip.ptr(S), hip.ptr(losses), int(epoch), hip.ptr(self.best_S),
+                                             hip.ptr(self.best_loss), hip.ptr(self.best_epoch), hip.stream())
+        hip.check(rc, "gmc_inst_keep_best_f32")
+
+
+def check_instance_sizes(sizes: Sequence[int], K: int, loss: str = "expected_cut") -> None:
+    """What one model per graph refuses of a batch's graph sizes: fewer than K nodes (the K-class engine's ValueError), or
+    a graph beyond the one-workgroup head (ValueError naming train_model; judged for the stricter loss by default)."""
+    sizes = [int(n) for n in sizes]
+    if sizes and min(sizes) < K:
+        raise ValueError(f"number_classes = {K}: every graph needs at least {K} nodes (nodes 0..{K - 1} "
+                         f"are its terminals), got one with {min(sizes)}")
+    if sizes and instance_too_large(max(sizes), K, loss):
+        raise ValueError(f"a graph of {max(sizes)} nodes is beyond the one-workgroup head of the per-graph models "
+                         f"(number_classes = {K}: {hip.MAX_GRAPH_NODES} nodes at most, fewer for number_classes > 3): one "
+                         "large graph on its own is what train_model already serves (a model of n_nodes = n)")
+
+
+def module_of(params: Dict[str, torch.Tensor]):
+    """A ``GCNSoftmax`` with these four tensors (by parameter name) as its parameters, built without advancing torch's
+    random generator."""
+    from .Training.TrainingNeural import TORCH_DEVICE, TORCH_DTYPE, GCNSoftmax
+    n, F = params["conv1.weight"].shape
+    K = params["conv2.weight"].shape[1]
+    with torch.random.fork_rng(devices=[]):
+        net = GCNSoftmax(n, F, K, 0.0, TORCH_DEVICE).type(TORCH_DTYPE).to(TORCH_DEVICE)
+    with torch.no_grad():
+        named = dict(net.named_parameters())
+        for k in PARAM_ORDER:
+            named[k].copy_(params[k])
+    return net
+
+
 def device_cut_loss(batch: GraphBatch, P: torch.Tensor, C_: float = 1.0, loss: str = "cut", want_gp: bool = True,
                     device: Optional[torch.device] = None):
     """(loss [B], GP [R,3] or None) of given probabilities ``P`` [R,3] (gmc_cut_loss_f32): per-graph loss and

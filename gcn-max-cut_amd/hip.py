@@ -131,6 +131,10 @@ def _api() -> dict:
         "gmc_large_forward": (i, [B, M, f32, vp, sz, vp, vp, vp, vp]),
         "gmc_large_train_fwd_bwd": (i, [B, M, f32, vp, sz, vp, vp, vp, vp, vp]),
         "gmc_large_required": (i, [B, M]),
+        "gmc_inst_workspace_bytes": (sz, [B, M, i]),
+        "gmc_inst_forward": (i, [B, M, f32, vp, sz, vp, vp, vp, vp]),
+        "gmc_inst_train_fwd_bwd": (i, [B, M, f32, vp, sz, vp, vp, vp, vp, vp]),
+        "gmc_inst_keep_best_f32": (i, [B, vp, vp, i32, vp, vp, vp, vp]),
         "gmc_att_workspace_bytes": (sz, [B, M, i]),
         "gmc_att_forward": (i, [B, M, vp, vp, f32, f32, vp, sz, vp, vp, vp, vp]),
         "gmc_att_train_fwd_bwd": (i, [B, M, vp, vp, f32, f32, vp, sz, vp, vp, vp, vp, vp]),

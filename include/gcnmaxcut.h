@@ -504,6 +504,65 @@ int gmc_large_train_fwd_bwd(const gmc_batch *batch, const gmc_model *model, floa
  * included).  Negative: GMC_ERR_NULL, GMC_ERR_ABI, GMC_ERR_CLASSES (K outside 2..GMC_KWAY_MAX_CLASSES).  Host only. */
 int gmc_large_required(const gmc_batch *batch, const gmc_model *model);
 
+/* ---- one model per graph (extension: the reference's model as an instance-wise solver, a whole batch per step) ---------
+ *
+ * The features of the reference are the padded adjacency, so row i of conv1.weight is the embedding of NODE ID i: a model
+ * knows the graphs it was trained on.  These entry points train B independent models on the B graphs of a batch in one
+ * launch sequence.  For a batch with R rows, K = model->K in 2..GMC_KWAY_MAX_CLASSES (3 included) and hidden width
+ * F = model->F the gmc_model is a parameter-block descriptor (its layout is unchanged):
+ *    W1 [R,F]    row goff[g] + l is the embedding of node l of graph g: graph g's own conv1.weight [n_g,F]
+ *    b1 [B,F], W2 [B,F,K], b2 [B,K]   one conv1.bias, conv2.weight, conv2.bias per graph
+ *    N           must equal batch->R (GMC_ERR_SHAPE)
+ * The flat order is [W1 | b1 | W2 | b2], count = R*F + B*(F + F*K + K) floats; grad (and a caller's Adam moments) use
+ * the same layout.  Graph g's forward, loss (GMC_LOSS_CUT, or GMC_LOSS_EXPECTED_CUT with GMC_MODEL_LOSS_EXPECTED in
+ * model->flags), terminals (nodes 0..K-1 fixed to classes 0..K-1) and gradient are exactly those of gmc_kway_forward /
+ * gmc_kway_train_fwd_bwd on the one-graph batch of g with a model of N = n_g holding g's four blocks.  Nothing couples
+ * two graphs: a graph's P, S, loss and its slices of the gradient have the same bits wherever it stands in the batch and
+ * whatever else the batch holds, and are bitwise reproducible (no float atomics, every sum in a fixed order).
+ * GMC_MODEL_GRAD_TAIL is not read (no sum over the graphs exists to carry); dropout_p > 0: GMC_ERR_UNSUPPORTED; W1_slab
+ * is not read.  Only undirected graphs with symmetric weights are batches of this library (gmc_batch), which step 7 uses.
+ *
+ * Kernel sequence (row-major [R, ld] buffers, the plan of gmc_kway_*; probe tag in brackets):
+ *  1. T0 = dinv o (A_val @ W1)                  gmc_spmm_f32's kernel, column array gcol, source the stacked W1  [GATHER_W1]
+ *  2. Hpre = dinv o (A @ T0)                    the same kernel, no bias, no relu                               [AGG_FWD]
+ *  3. H = relu(Hpre + b1_g) written in place of Hpre, Z0[r,:] = dinv[r] * (H[r,:] @ W2_g): one wave per row, the row's
+ *     graph is its workgroup's (grid = graph x 4-row tile).  The bias is added to the ROUNDED float32 Hpre
+ *     (gmc_kway_* fuses it into one fma with the row scale: one rounding less); the H @ W2_g sum is hw2_k's - lane j
+ *     takes columns j, j + 64, ... ascending, then a butterfly over the lanes                                    [DENSE_MFMA]
+ *  4. the head of gmc_kway_* with graph g's b2 (the same kernel; the bias is read at b2 + g*K).  Its per-graph sums of
+ *     the softmax backward ARE db2_g and go straight into the gradient.  Graph-size bound: that of gmc_kway_*       [HEAD]
+ *  5. Gs = dinv o relu'(H) o dinv o (GY2 @ W2_g^T) and partials of dW2_g [F,K], db1_g [F] over tiles of 64 rows that
+ *     start at the graph's first row (never two graphs in a tile; the two row lanes of a tile take its even and its odd
+ *     rows, each ascending, then lane 0 + lane 1)                                                             [HIDDEN_BWD]
+ *  6. dW2_g, db1_g = the graph's tile partials added one after the other, ascending                              [COLSUM]
+ *  7. U = dinv o (A @ Gs)                       gmc_spmm_f32's kernel                                            [AGG_BWD]
+ *  8. dW1[j,:] = sum over the entries e of row j of val[e] * U[gcol[e],:]: dW1 = A_val^T @ U, and A_val^T = A_val.  A
+ *     plain SpMM without scale or bias (CSR order), because every row of W1 belongs to exactly one node: the per-chunk
+ *     [N,F] partials and their fold, which gmc_kway_* needs for a W1 all graphs share, do not exist here            [DW1]
+ * A training call is these eight launches, a forward the first four.  Adam: gmc_adam_f32 / gmc_adam_devstep_f32 over the
+ * count floats (every instance shares the step number).
+ *
+ * Argument checks: all before any HIP call, in the order of gmc_kway_* - step 2's last item is N != R (SHAPE) in the
+ * place of n_max > N.  An empty batch (R == 0) launches nothing and zeroes the count floats of grad.  Workspace: T0, H
+ * [R, ld], Z0 [R,K]; training: GY2 [R,K] and the tile partials [R / 64 + B + 1][F][K+1]. */
+/* bytes of scratch gmc_inst_forward / gmc_inst_train_fwd_bwd need (0 for a NULL struct, another abi word, or K outside
+ * 2..GMC_KWAY_MAX_CLASSES) */
+size_t gmc_inst_workspace_bytes(const gmc_batch *batch, const gmc_model *model, int training);
+/* P [R,K]; S [R] / loss [B] optional */
+int gmc_inst_forward(const gmc_batch *batch, const gmc_model *model, float C, void *workspace, size_t workspace_bytes,
+                     float *P, int32_t *S, float *loss, gmc_stream_t stream);
+/* grad: the flat [dW1 [R,F] | db1 [B,F] | dW2 [B,F,K] | db2 [B,K]], overwritten */
+int gmc_inst_train_fwd_bwd(const gmc_batch *batch, const gmc_model *model, float C, void *workspace,
+                           size_t workspace_bytes, float *P, int32_t *S, float *loss, float *grad, gmc_stream_t stream);
+/* Keep every graph's best partition so far: for each graph g with loss[g] < best_loss[g] (strict: the first minimum
+ * wins; a NaN loss never does) the rows goff[g]..goff[g+1]-1 of S [R] are copied into best_S [R], best_loss[g] = loss[g]
+ * and best_epoch[g] = epoch.  Two launches (probe tag FINISH twice): the row-parallel copy only reads best_loss, the second
+ * launch - one thread per graph, behind the kernel boundary - stores it, so the workgroups of one graph all see the same
+ * comparison; no atomics, no waiting.  Initialise best_loss with +inf: epoch 0 then always wins.  Errors, before any HIP
+ * call: a NULL pointer GMC_ERR_NULL, batch->abi GMC_ERR_ABI, negative sizes GMC_ERR_SHAPE.  B == 0 launches nothing. */
+int gmc_inst_keep_best_f32(const gmc_batch *batch, const int32_t *S, const float *loss, int32_t epoch, int32_t *best_S,
+                           float *best_loss, int32_t *best_epoch, gmc_stream_t stream);
+
 /* ---- a graph-attention first layer (extension: the first of the "future improvements" of the reference's README) ------
  *
  * The entry points above have GraphConv(norm='both') as layer 1 (TrainingNeural.py:80).  These three replace that layer's
