@@ -1,26 +1,12 @@
 // Fused Adam step over one flat fp32 buffer (torch.optim.Adam defaults as constructed at
 // TrainingNeural.py:337 and stepped at :386): exp_avg lerp, exp_avg_sq addcmul, bias
 // corrections, addcdiv - one streaming pass, 28 B/parameter (read p,g,m,v; write p,m,v).
-#include "gmc_common.h"
-#include <math.h>
+#include "adam_body.h"
 
 namespace {
 
-struct AdamArgs {
-    float *p;
-    const float *g;
-    float *m;
-    float *v;
-    long n;
-    float one_minus_b1, b2, one_minus_b2, step_size, bc2_sqrt, eps;
-};
-
-__device__ __forceinline__ void adam1(float &p, float g, float &m, float &v, const AdamArgs &a) {
-    m = m + (g - m) * a.one_minus_b1;                 // exp_avg.lerp_(grad, 1-beta1)
-    v = fmaf(a.one_minus_b2 * g, g, v * a.b2);        // exp_avg_sq.mul_(b2).addcmul_(g, g, 1-b2)
-    const float denom = sqrtf(v) / a.bc2_sqrt + a.eps;
-    p = p - a.step_size * (m / denom);                // param.addcdiv_(m, denom, -step_size)
-}
+using gmc::AdamArgs;   // adam_body.h: the update itself, shared with instance.hip's per-graph sweep
+using gmc::adam1;
 
 __global__ __launch_bounds__(256) void adam_kernel(AdamArgs a) {
     const long n4 = a.n >> 2;
@@ -176,10 +162,7 @@ extern "C" int gmc_adam_f32(float *param, const float *grad, float *m, float *v,
     if (!gmc_aligned16(param) || !gmc_aligned16(grad) || !gmc_aligned16(m) || !gmc_aligned16(v))
         return GMC_ERR_ALIGN;
     if (count == 0) return GMC_OK;
-    const double bc1 = 1.0 - pow(beta1, (double)step);
-    const double bc2 = 1.0 - pow(beta2, (double)step);
-    AdamArgs a{param, grad, m, v, (long)count, (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2),
-               (float)(lr / bc1), (float)sqrt(bc2), (float)eps};
+    const AdamArgs a = gmc::adam_args(param, grad, m, v, (long)count, lr, beta1, beta2, eps, step);
     long blocks = ((count >> 2) + 255) / 256;
     if (blocks < 1) blocks = 1;
     if (blocks > 2048) blocks = 2048;

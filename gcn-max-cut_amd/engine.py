@@ -555,8 +555,9 @@ class InstanceEngine:
     ``conv1.weight [n_g, F]`` (one embedding row per node), ``conv1.bias``, ``conv2.weight [F, K]`` and ``conv2.bias``, and
     one launch sequence trains all of them at once; nothing couples two graphs.  Owns the batch, the flat parameter
     buffer ``[W1 [R,F] | b1 [B,F] | W2 [B,F,K] | b2 [B,K]]`` with gradient and Adam moments of the same layout, and the best
-    partition seen per graph.  It does not touch :class:`FusedEngine`; number_classes 2..8, both losses, layer1 =
-    graphconv, no dropout, graphs within the one-workgroup head's bound."""
+    partition seen per graph, and the per-graph state of early stopping (``prev_loss``, ``stall``, ``stop_epoch``: -1 while
+    a graph runs; include/gcnmaxcut.h, gmc_inst_early_stop_f32).  It does not touch :class:`FusedEngine`; number_classes
+    2..8, both losses, layer1 = graphconv, no dropout, graphs within the one-workgroup head's bound."""
 
     def __init__(self, batch_handles, F: int, K: int, device: Optional[torch.device] = None, *, values=None):
         self.device = device or hip.require_gpu()
@@ -569,6 +570,7 @@ class InstanceEngine:
                              f"got {F}")
         handles = list(batch_handles)
         check_instance_sizes([h.n for h in handles], K)
+        self._handles, self._values = handles, None if values is None else list(values)   # (kept for subset())
         self.batch = GraphBatch(handles, values, self.device)
         self.F, self.K, self.Fp = F, K, (F + 3) // 4 * 4   # (the kernels see the hidden width padded to float4 columns)
         self.B, self.R = self.batch.B, self.batch.R
@@ -581,6 +583,9 @@ class InstanceEngine:
         self.best_S = torch.zeros(self.R, dtype=torch.int32, device=self.device)
         self.best_loss = torch.full((self.B,), float("inf"), dtype=torch.float32, device=self.device)
         self.best_epoch = torch.full((self.B,), -1, dtype=torch.int32, device=self.device)
+        self.prev_loss = torch.full((self.B,), float("inf"), dtype=torch.float32, device=self.device)
+        self.stall = torch.zeros(self.B, dtype=torch.int32, device=self.device)
+        self.stop_epoch = torch.full((self.B,), -1, dtype=torch.int32, device=self.device)
         self._ws: Optional[torch.Tensor] = None
 
     # ---- parameters
@@ -600,8 +605,8 @@ class InstanceEngine:
                 "conv2.weight": b["conv2.weight"][g, :F], "conv2.bias": b["conv2.bias"][g]}
 
     def reset_parameters(self) -> None:
-        """:func:`draw_instance_parameters` into the flat buffer (padding columns and biases zero), Adam state and the
-        kept partitions back to their start."""
+        """:func:`draw_instance_parameters` into the flat buffer (padding columns and biases zero), Adam state, the kept
+        partitions and the early-stopping state back to their start."""
         for buf in (self.flat, self.grad, self.m, self.v):
             buf.zero_()
         for g, (w1, w2) in enumerate(draw_instance_parameters(self.batch.sizes, self.F, self.K)):
@@ -612,6 +617,9 @@ class InstanceEngine:
         self.best_S.zero_()
         self.best_loss.fill_(float("inf"))
         self.best_epoch.fill_(-1)
+        self.prev_loss.fill_(float("inf"))
+        self.stall.zero_()
+        self.stop_epoch.fill_(-1)
 
     def module(self, g: int):
         """A ``GCNSoftmax(n_g, F, K)`` holding COPIES of graph ``g``'s parameters: ``evaluate_model``, ``round_dataset``,
@@ -671,10 +679,18 @@ class InstanceEngine:
         hip.check(rc, "gmc_inst_train_fwd_bwd")
         return P, S, losses
 
-    def adam_step(self, lr: float, betas=(0.9, 0.999), eps: float = 1e-8) -> None:
-        """torch.optim.Adam.step over the flat buffer: every instance shares the step number."""
+    def adam_step(self, lr: float, betas=(0.9, 0.999), eps: float = 1e-8, running_only: bool = False) -> None:
+        """torch.optim.Adam.step over the flat buffer: every instance shares the step number.  ``running_only``: the
+        sweep cut by graph (gmc_inst_adam_f32) that neither reads nor writes anything of a graph whose ``stop_epoch`` is
+        set; a running graph takes the same bits from either sweep."""
         self.step_count += 1
         if self.count == 0:
+            return
+        if running_only:
+            rc = self.lib.gmc_inst_adam_f32(self.batch.ref(), self.Fp, self.K, hip.ptr(self.flat), hip.ptr(self.grad),
+                                            hip.ptr(self.m), hip.ptr(self.v), lr, betas[0], betas[1], eps, self.step_count,
+                                            hip.ptr(self.stop_epoch), hip.stream())
+            hip.check(rc, "gmc_inst_adam_f32")
             return
         rc = self.lib.gmc_adam_f32(hip.ptr(self.flat), hip.ptr(self.grad), hip.ptr(self.m), hip.ptr(self.v), self.count,
                                    lr, betas[0], betas[1], eps, self.step_count, hip.stream())
@@ -688,6 +704,49 @@ class InstanceEngine:
         rc = self.lib.gmc_inst_keep_best_f32(self.batch.ref(), hip.ptr(S), hip.ptr(losses), int(epoch), hip.ptr(self.best_S),
                                              hip.ptr(self.best_loss), hip.ptr(self.best_epoch), hip.stream())
         hip.check(rc, "gmc_inst_keep_best_f32")
+
+    def early_stop(self, S: torch.Tensor, losses: torch.Tensor, epoch: int, tolerance: float, patience: int) -> None:
+        """:meth:`keep_best` behind the reference's tolerance / patience rule, per graph (gmc_inst_early_stop_f32; the
+        rule is stated in include/gcnmaxcut.h): a graph whose loss has stalled ``patience`` epochs in a row gets
+        ``stop_epoch[g] = epoch`` and is frozen from then on - no keep-best in that call or later, and
+        ``adam_step(running_only=True)`` passes it by.  Nothing here waits for the device."""
+        if self.B == 0:
+            return
+        rc = self.lib.gmc_inst_early_stop_f32(self.batch.ref(), hip.ptr(S), hip.ptr(losses), int(epoch), float(tolerance),
+                                              int(patience), hip.ptr(self.prev_loss), hip.ptr(self.stall),
+                                              hip.ptr(self.stop_epoch), hip.ptr(self.best_S), hip.ptr(self.best_loss),
+                                              hip.ptr(self.best_epoch), hip.stream())
+        hip.check(rc, "gmc_inst_early_stop_f32")
+
+    def stopped(self) -> torch.Tensor:
+        """Host copy of ``stop_epoch`` ([B] int32; -1: still running).  The one call here that synchronises."""
+        return self.stop_epoch.cpu()
+
+    def subset(self, keep: Sequence[int]) -> "InstanceEngine":
+        """A new engine over the graphs ``keep`` of this one (indices into the batch, in ascending order: batch order is
+        kept) that goes on where this one stands: their parameters, gradient, Adam moments, ``step_count``, best
+        partition / loss / epoch and early-stopping state are carried across, block by block, by device-to-device
+        indexing.  A graph's bytes do not depend on its batch, so its further steps are the ones it would have taken
+        here."""
+        keep = [int(g) for g in keep]
+        if any(b <= a for a, b in zip(keep, keep[1:])) or (keep and not 0 <= keep[0] <= keep[-1] < self.B):
+            raise ValueError(f"subset: graph indices must ascend within 0..{self.B - 1}, got {keep}")
+        values = None if self._values is None else [self._values[g] for g in keep]
+        sub = InstanceEngine([self._handles[g] for g in keep], self.F, self.K, self.device, values=values)
+        gidx = torch.tensor(keep, dtype=torch.long, device=self.device)
+        goff = self.batch.goff_host
+        rows = [torch.arange(int(goff[g]), int(goff[g + 1]), device=self.device) for g in keep]
+        ridx = torch.cat(rows) if rows else torch.zeros(0, dtype=torch.long, device=self.device)
+        for src, dst in ((self.flat, sub.flat), (self.grad, sub.grad), (self.m, sub.m), (self.v, sub.v)):
+            a, b = self.blocks(src), sub.blocks(dst)
+            b["conv1.weight"].copy_(a["conv1.weight"][ridx])
+            for k in PARAM_ORDER[1:]:
+                b[k].copy_(a[k][gidx])
+        sub.step_count = self.step_count
+        sub.best_S.copy_(self.best_S[ridx])
+        for name in ("best_loss", "best_epoch", "prev_loss", "stall", "stop_epoch"):
+            getattr(sub, name).copy_(getattr(self, name)[gidx])
+        return sub
 
 
 def check_instance_sizes(sizes: Sequence[int], K: int, loss: str = "expected_cut") -> None:

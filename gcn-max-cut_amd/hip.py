@@ -30,6 +30,7 @@ LOSS_ENV = "GCN_MAXCUT_LOSS"
 LAYER1_KINDS = ("graphconv", "attention")
 LAYER1_ENV = "GCN_MAXCUT_LAYER1"
 ATTENTION_SLOPE = 0.2  # negative slope of the attention scores' leaky relu (the GAT paper's)
+INST_ADAM_TILE_FLOATS = 4096   # GMC_INST_ADAM_TILE_FLOATS: floats of a graph's W1 one workgroup of gmc_inst_adam_f32 takes
 KWAY_MAX_CLASSES = 8  # GMC_KWAY_MAX_CLASSES: number_classes the gmc_kway_* entry points take (2..8; 3 also has the fused path)
 ABI_VERSION = 200     # GMC_VERSION of include/gcnmaxcut.h these struct layouts follow (checked at load and per call)
 
@@ -135,6 +136,8 @@ def _api() -> dict:
         "gmc_inst_forward": (i, [B, M, f32, vp, sz, vp, vp, vp, vp]),
         "gmc_inst_train_fwd_bwd": (i, [B, M, f32, vp, sz, vp, vp, vp, vp, vp]),
         "gmc_inst_keep_best_f32": (i, [B, vp, vp, i32, vp, vp, vp, vp]),
+        "gmc_inst_early_stop_f32": (i, [B, vp, vp, i32, f64, i32, vp, vp, vp, vp, vp, vp, vp]),
+        "gmc_inst_adam_f32": (i, [B, i32, i32, vp, vp, vp, vp, *adam, i32, vp, vp]),
         "gmc_att_workspace_bytes": (sz, [B, M, i]),
         "gmc_att_forward": (i, [B, M, vp, vp, f32, f32, vp, sz, vp, vp, vp, vp]),
         "gmc_att_train_fwd_bwd": (i, [B, M, vp, vp, f32, f32, vp, sz, vp, vp, vp, vp, vp]),

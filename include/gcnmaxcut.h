@@ -563,6 +563,46 @@ int gmc_inst_train_fwd_bwd(const gmc_batch *batch, const gmc_model *model, float
 int gmc_inst_keep_best_f32(const gmc_batch *batch, const int32_t *S, const float *loss, int32_t epoch, int32_t *best_S,
                            float *best_loss, int32_t *best_epoch, gmc_stream_t stream);
 
+/* Per-graph early stopping: the reference's tolerance / patience rule (TrainingNeural.py:429-444: train_model stops a
+ * model whose loss has stalled `patience` times in a row) with keep-best behind it, for every graph of the batch on its
+ * own.  THE RULE, per graph g and epoch e:
+ *   L = loss[g], the loss measured in epoch e before that epoch's update; p = prev_loss[g] (+inf before epoch 0).
+ *   g stalls when  e > 0 && (L > p || fabs((double)p - (double)L) <= tolerance).  Comparisons are taken as written, so a
+ *   NaN loss never stalls (and never wins); the difference is taken in double because the reference compares Python
+ *   floats of float32 losses.
+ *   stalled:      stall[g] += 1; if stall[g] >= patience: stop_epoch[g] = e and NOTHING ELSE of g changes - no keep-best,
+ *                 no prev_loss (the reference breaks before both; the Adam update of epoch e has been applied by then,
+ *                 as in the reference).
+ *   not stalled:  stall[g] = 0.
+ *   not stopped in this call: keep-best exactly as gmc_inst_keep_best_f32 (strict <, the first minimum wins), then
+ *                 prev_loss[g] = L.
+ *   A graph with stop_epoch[g] >= 0 on entry is stopped: nothing of it is written, whatever its loss.
+ * Start with prev_loss = +inf, stall = 0, stop_epoch = -1, best_loss = +inf.  It takes the place of
+ * gmc_inst_keep_best_f32 in a loop with early stopping, in the same two-launch shape and for the same reason (probe tag
+ * FINISH twice): the row launch only reads the per-graph state and copies the rows of S of the graphs that are running,
+ * not stopping now, and improving; the one-thread-per-graph launch stores the decision behind the kernel boundary.  No
+ * atomics, no waiting, no scratch.  Errors, before any HIP call, in this order: a NULL pointer GMC_ERR_NULL (batch
+ * first), batch->abi GMC_ERR_ABI, negative sizes, patience < 1, a negative or NaN tolerance GMC_ERR_SHAPE.  B == 0
+ * launches nothing. */
+int gmc_inst_early_stop_f32(const gmc_batch *batch, const int32_t *S, const float *loss, int32_t epoch, double tolerance,
+                            int32_t patience, float *prev_loss, int32_t *stall, int32_t *stop_epoch, int32_t *best_S,
+                            float *best_loss, int32_t *best_epoch, gmc_stream_t stream);
+
+/* gmc_adam_f32 over the flat [W1 [R,F] | b1 [B,F] | W2 [B,F,K] | b2 [B,K]] buffer of one model per graph (count = R*F +
+ * B*(F + F*K + K) floats; param, grad, m, v in that layout), cut by graph: one launch (probe tag ADAM) whose grid is
+ * graph x tile of that graph's own floats - its n_g * F floats of W1 in tiles of GMC_INST_ADAM_TILE_FLOATS as float4, then
+ * its F + F*K + K floats of the three small blocks, scalar.  stop_epoch [B] or NULL (all running): a workgroup of a graph
+ * with stop_epoch[g] >= 0 returns after reading that word - no byte of that graph's param, grad, m or v is read or
+ * written.  The per-element update and the host-side derivation of lr / bias_correction1 and sqrt(bias_correction2) are
+ * gmc_adam_f32's (one definition), so with no graph stopped param, m and v are byte for byte gmc_adam_f32's over the same
+ * count floats.  Floats after count are never touched.  Errors, before any HIP call: a NULL batch / goff / param / grad /
+ * m / v GMC_ERR_NULL (batch first, then batch->abi GMC_ERR_ABI); negative sizes, F < 1, K < 1, step < 1 GMC_ERR_SHAPE;
+ * F % 4 or a buffer off a 16-byte boundary GMC_ERR_ALIGN.  B == 0 launches nothing. */
+#define GMC_INST_ADAM_TILE_FLOATS 4096
+int gmc_inst_adam_f32(const gmc_batch *batch, int32_t F, int32_t K, float *param, const float *grad, float *m, float *v,
+                      double lr, double beta1, double beta2, double eps, int32_t step, const int32_t *stop_epoch,
+                      gmc_stream_t stream);
+
 /* ---- a graph-attention first layer (extension: the first of the "future improvements" of the reference's README) ------
  *
  * The entry points above have GraphConv(norm='both') as layer 1 (TrainingNeural.py:80).  These three replace that layer's
