@@ -493,8 +493,9 @@ bool kway_too_large(const gmc_batch *b, const gmc_model *m) {
     return b->n_max > GMC_MAX_GRAPH_NODES || gmc_kway_head_lds_bytes(b->n_max, m->K, loss_of(m)) > GMC_KWAY_LDS_BYTES;
 }
 
-// steps 1 and 2 of the documented order; large: the gmc_large_* entry points (several workgroups per graph: no LDS bound)
-int kway_check(const gmc_batch *b, const gmc_model *m, bool large = false) {
+// steps 1 and 2 of the documented order; large: the gmc_large_* / gmc_fn_* entry points (several workgroups per graph: no
+// LDS bound); dense: features with their own N columns - a graph may then have more nodes than conv1.weight has rows
+int kway_check(const gmc_batch *b, const gmc_model *m, bool large = false, bool dense = false) {
     if (int rc = check_abi(b, m)) return rc;
     if (!b->goff || !b->rowptr || !b->gcol || !b->lcol || !b->dinv) return GMC_ERR_NULL;
     if (!m->W1 || !m->b1 || !m->W2 || !m->b2) return GMC_ERR_NULL;
@@ -506,7 +507,7 @@ int kway_check(const gmc_batch *b, const gmc_model *m, bool large = false) {
     if (m->W1_slab && !gmc_aligned16(m->W1_slab)) return GMC_ERR_ALIGN;
     if (b->B > 0 && (b->n_max < m->K || (large ? b->n_max > GMC_LARGE_MAX_GRAPH_NODES : kway_too_large(b, m))))
         return GMC_ERR_GRAPH_SIZE;
-    if (b->n_max > m->N) return GMC_ERR_SHAPE;  // more nodes than rows of conv1.weight
+    if (!dense && b->n_max > m->N) return GMC_ERR_SHAPE;  // more nodes than rows of conv1.weight
     return GMC_OK;
 }
 
@@ -530,6 +531,8 @@ struct KwayCall {
     const gmc_batch *b; const gmc_model *m;
     bool large = false;   // gmc_large_*: the head of large.hip, graphs up to GMC_LARGE_MAX_GRAPH_NODES nodes
     KwayWorkspace w{}; hipStream_t st = nullptr;
+    const float *X = nullptr; long ldx = 0;   // gmc_fn_*: dense features [R, N] instead of the padded adjacency
+    float *dX = nullptr; long lddx = 0;       // ... backward: dX = U @ W1^T when asked for
 };
 
 int kway_open(KwayCall &c, bool training, void *workspace, size_t workspace_bytes, gmc_stream_t stream, const float *P,
@@ -543,16 +546,21 @@ int kway_open(KwayCall &c, bool training, void *workspace, size_t workspace_byte
     return GMC_OK;
 }
 
-// forward and head; GY2 / db2part of the workspace are filled when it was carved for training
-int kway_forward_body(const KwayCall &c, float C, float *P, int32_t *S, float *loss) {
+// the two layers up to Z0 = dinv o (H @ W2); c.X: layer 1's feature transform is a GEMM
+int kway_layers(const KwayCall &c) {
     const gmc_batch *b = c.b; const gmc_model *m = c.m; const KwayWorkspace &w = c.w;
     const int F = m->F;
-    // T0 = dinv o (A_val @ W1[:n]): a row gather of W1
-    int rc = gmc_spmm_launch(b->rowptr, b->lcol, b->vals, b->dinv, m->W1, F, nullptr, 0, w.T0, w.ld, b->R, F,
+    int rc;
+    if (c.X) {   // T0 = dinv o (X @ W1)
+        rc = gmc_gemm_launch(0, 0, b->R, F, m->N, c.X, c.ldx, m->W1, F, b->dinv, w.T0, w.ld, c.st);
+    } else {
+        // T0 = dinv o (A_val @ W1[:n]): a row gather of W1
+        rc = gmc_spmm_launch(b->rowptr, b->lcol, b->vals, b->dinv, m->W1, F, nullptr, 0, w.T0, w.ld, b->R, F,
                              group_rows(b), nullptr, nullptr, GMC_K_GATHER_W1, c.st);
-    if (!rc && c.large)   // (gmc_large_*: rows of more than 64 entries once more, summed in chunks - launchers.h)
-        rc = gmc_large_hub_rows_launch(b->rowptr, b->lcol, b->vals, b->dinv, m->W1, F, nullptr, 0, w.T0, w.ld, b->R, F,
-                                       GMC_K_GATHER_W1, c.st);
+        if (!rc && c.large)   // (gmc_large_*: rows of more than 64 entries once more, summed in chunks - launchers.h)
+            rc = gmc_large_hub_rows_launch(b->rowptr, b->lcol, b->vals, b->dinv, m->W1, F, nullptr, 0, w.T0, w.ld, b->R, F,
+                                           GMC_K_GATHER_W1, c.st);
+    }
     if (rc) return rc;
     // H = relu(dinv o (A @ T0) + b1)
     rc = gmc_spmm_launch(b->rowptr, b->gcol, nullptr, b->dinv, w.T0, w.ld, m->b1, 1, w.H, w.ld, b->R, F, group_rows(b),
@@ -561,8 +569,13 @@ int kway_forward_body(const KwayCall &c, float C, float *P, int32_t *S, float *l
         rc = gmc_large_hub_rows_launch(b->rowptr, b->gcol, nullptr, b->dinv, w.T0, w.ld, m->b1, 1, w.H, w.ld, b->R, F,
                                        GMC_K_AGG_FWD, c.st);
     if (rc) return rc;
-    rc = gmc_kway_hw2_launch(w.H, w.ld, b->dinv, m->W2, w.Z0, b->R, F, m->K, c.st);
-    if (rc) return rc;
+    return gmc_kway_hw2_launch(w.H, w.ld, b->dinv, m->W2, w.Z0, b->R, F, m->K, c.st);
+}
+
+// forward and head; GY2 / db2part of the workspace are filled when it was carved for training
+int kway_forward_body(const KwayCall &c, float C, float *P, int32_t *S, float *loss) {
+    const gmc_batch *b = c.b; const gmc_model *m = c.m; const KwayWorkspace &w = c.w;
+    if (int rc = kway_layers(c)) return rc;
     if (c.large)
         return gmc_large_head_launch(b, w.Z0, m->b2, C, m->K, loss_of(m), P, S, loss, w.S, w.GZd, w.headpart, w.GY2,
                                      w.db2part, c.st);
@@ -585,7 +598,12 @@ int kway_backward_body(const KwayCall &c, float *grad, const float *loss_tail) {
         rc = gmc_large_hub_rows_launch(b->rowptr, b->gcol, nullptr, b->dinv, Gs, w.ld, nullptr, 0, U, w.ld, b->R, m->F,
                                        GMC_K_AGG_BWD, c.st);
     if (rc) return rc;
-    rc = gmc_dw1_launch(b, U, w.ld, dW1, w.dw1part, m->N, m->F, false, c.st);
+    if (c.X) {   // dW1 = X^T @ U straight into grad, dX = U @ W1^T
+        rc = gmc_gemm_launch(1, 0, m->N, m->F, b->R, c.X, c.ldx, U, w.ld, nullptr, dW1, F, c.st);
+        if (!rc && c.dX) rc = gmc_gemm_launch(0, 1, b->R, m->N, m->F, U, w.ld, m->W1, F, nullptr, c.dX, c.lddx, c.st);
+    } else {
+        rc = gmc_dw1_launch(b, U, w.ld, dW1, w.dw1part, m->N, m->F, false, c.st);
+    }
     if (rc || !loss_tail) return rc;
     return gmc_loss_tail_launch(loss_tail, b->B, db2 + K, c.st);
 }
@@ -661,6 +679,110 @@ extern "C" int gmc_large_required(const gmc_batch *batch, const gmc_model *model
     if (batch->B <= 0) return 0;
     if (model->K == 3) return batch->n_max > GMC_MAX_GRAPH_NODES ? 1 : 0;   // gmc_*: check()
     return kway_too_large(batch, model) ? 1 : 0;                            // gmc_kway_*: kway_check()
+}
+
+// ---- the functional form of the model: probabilities out, a caller's dLoss/dP in (functional.hip) -----------------------------
+namespace {
+
+// gmc_kway_*'s training buffers (the dW1 scratch only without features: with them dW1 is a GEMM into grad), then dinv o GZ
+// [R,K] and the tile partials of db2
+KwayWorkspace fn_carve(const gmc_batch *b, const gmc_model *m, bool features, void *base) {
+    KwayWorkspace w{};
+    size_t off = 0;
+    auto take = [&](size_t floats) {
+        float *p = base ? reinterpret_cast<float *>(static_cast<char *>(base) + off) : nullptr;
+        off += align_up(floats * sizeof(float));
+        return p;
+    };
+    const size_t R = (size_t)b->R, F = (size_t)m->F, K = (size_t)m->K;
+    w.ld = (long)((F + 31) / 32 * 32);
+    w.T0 = take(R * w.ld);
+    w.H = take(R * w.ld);
+    w.Z0 = take(R * K);
+    w.GY2 = take(R * K);
+    w.part = take((size_t)gmc_hidden_tiles(b->R) * F * (K + 1));
+    w.db2part = take((size_t)b->B * K);
+    w.dw1part = take(features ? 0 : gmc_dw1_scratch_floats(b, m->N, m->F, false));
+    w.GZd = take(R * K);
+    w.headpart = take(gmc_fn_part_floats(b, m->K));
+    w.bytes = off;
+    return w;
+}
+
+// every argument check of gmc_fn_forward / gmc_fn_backward in the documented order, then the carving; c carries b, m and
+// X / ldx / dX / lddx as the caller handed them over
+int fn_open(KwayCall &c, void *workspace, size_t workspace_bytes, gmc_stream_t stream, const float *P, const float *GP,
+            const float *grad, bool backward) {
+    if (int rc = kway_check(c.b, c.m, true, c.X != nullptr)) return rc;              // 1. 2.
+    if (c.X) {                                                                       // 3. the features
+        if (c.ldx < c.m->N) return GMC_ERR_SHAPE;
+        if (!gmc_aligned16(c.X) || c.ldx % 4 || !gmc_aligned16(c.m->W1)) return GMC_ERR_ALIGN;
+    }
+    if (!workspace || !P || (backward && (!GP || !grad))) return GMC_ERR_NULL;       // 4. workspace and outputs
+    if (c.dX && c.lddx < c.m->N) return GMC_ERR_SHAPE;                               // 5.
+    if (!gmc_aligned16(grad) || !gmc_aligned16(P) || !gmc_aligned16(GP) || !gmc_aligned16(c.m->W2) ||
+        (c.dX && (!gmc_aligned16(c.dX) || c.lddx % 4)))
+        return GMC_ERR_ALIGN;
+    c.w = fn_carve(c.b, c.m, c.X != nullptr, workspace);                             // 6. size
+    if (c.w.bytes > workspace_bytes) return GMC_ERR_WORKSPACE;
+    c.st = static_cast<hipStream_t>(stream);
+    return GMC_OK;
+}
+
+}  // namespace
+
+extern "C" size_t gmc_fn_workspace_bytes(const gmc_batch *batch, const gmc_model *model, int features) {
+    if (check_abi(batch, model) || !kway_classes_ok(model->K)) return 0;
+    return fn_carve(batch, model, features != 0, nullptr).bytes;
+}
+
+extern "C" int gmc_fn_forward(const gmc_batch *batch, const gmc_model *model, const float *X, int64_t ldx, void *workspace,
+                              size_t workspace_bytes, float *P, gmc_stream_t stream) {
+    KwayCall c{batch, model, true};
+    c.X = X; c.ldx = (long)ldx;
+    int rc = fn_open(c, workspace, workspace_bytes, stream, P, nullptr, nullptr, false);
+    if (rc || batch->B == 0 || batch->R == 0) return rc;
+    rc = kway_layers(c);
+    return rc ? rc : gmc_fn_prob_launch(batch, c.w.Z0, model->b2, model->K, P, c.st);
+}
+
+extern "C" int gmc_fn_backward(const gmc_batch *batch, const gmc_model *model, const float *X, int64_t ldx, void *workspace,
+                               size_t workspace_bytes, const float *P, const float *GP, float *grad, float *dX,
+                               int64_t lddx, gmc_stream_t stream) {
+    KwayCall c{batch, model, true};
+    c.X = X; c.ldx = (long)ldx; c.dX = dX; c.lddx = (long)lddx;
+    int rc = fn_open(c, workspace, workspace_bytes, stream, P, GP, grad, true);
+    if (rc) return rc;
+    if (batch->B == 0 || batch->R == 0) {
+        const size_t n = (size_t)model->N * model->F + model->F + (size_t)model->F * model->K + model->K;
+        return (int)hipMemsetAsync(grad, 0, n * sizeof(float), c.st);
+    }
+    rc = gmc_fn_softmax_bwd_launch(batch, P, GP, model->K, c.w.GZd, c.w.headpart, c.w.db2part, c.w.GY2, c.st);
+    return rc ? rc : kway_backward_body(c, grad, nullptr);
+}
+
+extern "C" size_t gmc_fn_cut_loss_workspace_bytes(const gmc_batch *batch, int32_t K) {
+    if (!batch || batch->abi != GMC_VERSION || !kway_classes_ok(K) || batch->B < 0 || batch->R < 0) return 0;
+    return align_up(gmc_fn_part_floats(batch, 1) * sizeof(float));
+}
+
+extern "C" int gmc_fn_cut_loss_f32(const gmc_batch *batch, int32_t K, int32_t terminals, const float *P, float C,
+                                   int32_t loss_kind, void *workspace, size_t workspace_bytes, float *loss, float *GP,
+                                   gmc_stream_t stream) {
+    if (!batch) return GMC_ERR_NULL;                                                  // 1.
+    if (batch->abi != GMC_VERSION) return GMC_ERR_ABI;                                // 2. the struct, K, loss_kind
+    if (!batch->goff || !batch->rowptr || !batch->gcol || !batch->lcol) return GMC_ERR_NULL;
+    if (!kway_classes_ok(K)) return GMC_ERR_CLASSES;
+    if (batch->B < 0 || batch->R < 0 || batch->nnz < 0) return GMC_ERR_SHAPE;
+    if (!gmc_loss_kind_ok(loss_kind)) return GMC_ERR_LOSS;
+    if (batch->B > 0 && ((terminals && batch->n_max < K) || batch->n_max > GMC_LARGE_MAX_GRAPH_NODES))
+        return GMC_ERR_GRAPH_SIZE;
+    if (!workspace || !P || !loss) return GMC_ERR_NULL;                               // 4. workspace and outputs
+    if (!gmc_aligned16(P) || !gmc_aligned16(GP)) return GMC_ERR_ALIGN;                // 5.
+    if (gmc_fn_cut_loss_workspace_bytes(batch, K) > workspace_bytes) return GMC_ERR_WORKSPACE;   // 6.
+    if (batch->B == 0 || batch->R == 0) return GMC_OK;
+    return gmc_fn_loss_launch(batch, P, K, terminals != 0, C, loss_kind, static_cast<float *>(workspace), loss, GP,
+                              static_cast<hipStream_t>(stream));
 }
 
 // ---- one model per graph: the K-class row-kernel sequence with the grouped kernels of instance.hip -------------------------

@@ -143,6 +143,19 @@ int gmc_large_hub_rows_launch(const int32_t *rowptr, const int32_t *col, const f
                               const float *X, long ldx, const float *bias, int relu, float *Y, long ldy, int32_t n_rows,
                               int32_t F, int tag, hipStream_t st);
 
+// ---- the functional form of the model (functional.hip: gmc_fn_*): row-parallel launches on large.hip's grid (graph, tile
+// of 256 rows), K in 2..GMC_KWAY_MAX_CLASSES, P / GP / GZd / GY2 [R,K] 16-byte aligned.  part: gmc_fn_part_floats(b, V) floats
+// of tile partials, V sums per tile (R / 256 + B + 1 slots, large.hip's).
+size_t gmc_fn_part_floats(const gmc_batch *b, int V);
+// P = softmax(dinv o (A @ Z0) + b2): gmc_large_head_launch's probabilities without decode and loss
+int gmc_fn_prob_launch(const gmc_batch *b, const float *Z0, const float *b2, int K, float *P, hipStream_t st);
+// the softmax backward of a caller's GP = dLoss/dP: GZd = dinv o GZ, db2part [B,K] (part: V = K), GY2 = A @ GZd
+int gmc_fn_softmax_bwd_launch(const gmc_batch *b, const float *P, const float *GP, int K, float *GZd, float *part,
+                              float *db2part, float *GY2, hipStream_t st);
+// loss [B] (and GP [R,K] when given) of the probabilities P; part: V = 1
+int gmc_fn_loss_launch(const gmc_batch *b, const float *P, int K, int terminals, float C, int loss_kind, float *part,
+                       float *loss, float *GP, hipStream_t st);
+
 // ---- the graph-attention first layer (attention.hip): the row kernels of the gmc_att_* entry points -----------------
 // Row-major [R, ld] operands T (= X @ W1), H, G (gradient at layer 1's pre-activation), dT; per-row scalars s_src, s_dst,
 // alpha_s, dz_s, ds_src, ds_dst [R]; per-CSR-entry scalars alpha_e, dz_e [nnz].  a_src / a_dst [F] need no alignment.

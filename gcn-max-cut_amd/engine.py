@@ -413,16 +413,7 @@ class FusedEngine:
         """``X`` [R, N] as the library takes it: fp32 on the device, 16-byte aligned rows - the columns padded with
         zeros to a multiple of 4 when N is not one.  A tensor this method returned passes through unchanged, so a
         caller that runs forward and backward on the same features pads them once."""
-        ld = (self.N + 3) // 4 * 4
-        if X.dim() != 2 or X.shape[0] != batch.R or X.shape[1] not in (self.N, ld):
-            raise ValueError(f"features must be [{batch.R}, {self.N}], got {tuple(X.shape)}")
-        X = X.detach().to(self.device, torch.float32)
-        if X.shape[1] != ld:
-            Xp = torch.zeros((batch.R, ld), dtype=torch.float32, device=self.device)
-            Xp[:, :self.N] = X
-            return Xp
-        X = X.contiguous()
-        return X.clone() if X.data_ptr() % 16 else X
+        return padded_features(X, batch.R, self.N, self.device)
 
     def forward_features(self, batch: GraphBatch, X: torch.Tensor, C_: float = 1.0, want_loss: bool = False,
                          ws: Optional[torch.Tensor] = None, loss: str = "cut"):
@@ -511,6 +502,20 @@ class FusedEngine:
         if dp_active():
             dist.all_reduce(self.grad, op=dist.ReduceOp.SUM)
         return self.grad[self.count] if local_loss_sum is not None else None
+
+
+def padded_features(X: torch.Tensor, R: int, N: int, device) -> torch.Tensor:
+    """:meth:`FusedEngine.pad_features` for ``R`` rows and ``N`` columns (``functional.gcn_softmax`` pads the same way)."""
+    ld = (N + 3) // 4 * 4
+    if X.dim() != 2 or X.shape[0] != R or X.shape[1] not in (N, ld):
+        raise ValueError(f"features must be [{R}, {N}], got {tuple(X.shape)}")
+    X = X.detach().to(device, torch.float32)
+    if X.shape[1] != ld:
+        Xp = torch.zeros((R, ld), dtype=torch.float32, device=device)
+        Xp[:, :N] = X
+        return Xp
+    X = X.contiguous()
+    return X.clone() if X.data_ptr() % 16 else X
 
 
 # ---- one model per graph ------------------------------------------------------------------------------------------------

@@ -132,6 +132,11 @@ def _api() -> dict:
         "gmc_large_forward": (i, [B, M, f32, vp, sz, vp, vp, vp, vp]),
         "gmc_large_train_fwd_bwd": (i, [B, M, f32, vp, sz, vp, vp, vp, vp, vp]),
         "gmc_large_required": (i, [B, M]),
+        "gmc_fn_workspace_bytes": (sz, [B, M, i]),
+        "gmc_fn_forward": (i, [B, M, vp, i64, vp, sz, vp, vp]),
+        "gmc_fn_backward": (i, [B, M, vp, i64, vp, sz, vp, vp, vp, vp, i64, vp]),
+        "gmc_fn_cut_loss_workspace_bytes": (sz, [B, i32]),
+        "gmc_fn_cut_loss_f32": (i, [B, i32, i32, vp, f32, i32, vp, sz, vp, vp, vp]),
         "gmc_inst_workspace_bytes": (sz, [B, M, i]),
         "gmc_inst_forward": (i, [B, M, f32, vp, sz, vp, vp, vp, vp]),
         "gmc_inst_train_fwd_bwd": (i, [B, M, f32, vp, sz, vp, vp, vp, vp, vp]),

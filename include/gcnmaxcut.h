@@ -504,6 +504,64 @@ int gmc_large_train_fwd_bwd(const gmc_batch *batch, const gmc_model *model, floa
  * included).  Negative: GMC_ERR_NULL, GMC_ERR_ABI, GMC_ERR_CLASSES (K outside 2..GMC_KWAY_MAX_CLASSES).  Host only. */
 int gmc_large_required(const gmc_batch *batch, const gmc_model *model);
 
+/* ---- the functional form of the model (extension): probabilities out, the caller's dLoss/dP in -------------------------
+ *
+ * The reference's own loop, P = net(g, X); loss = ...(P); loss.backward(); optimizer.step() (TrainingNeural.py:371-386),
+ * for every class count and graph size of the library: K = model->K in 2..GMC_KWAY_MAX_CLASSES (3 included), graphs of
+ * K..GMC_LARGE_MAX_GRAPH_NODES nodes, the padded adjacency or dense features.  gmc_backward_from_gp /
+ * gmc_backward_features_from_gp above stay what they are: 3 classes, graphs of up to GMC_MAX_GRAPH_NODES nodes.
+ *  - gmc_fn_forward: P [R,K] = softmax(conv2(relu(conv1(.)))) and nothing else - no terminals, loss or decode, exactly what
+ *    GCNSoftmax.forward returns (:79-85).  X == NULL: the features are the padded adjacency, the kernel sequence is that of
+ *    gmc_large_forward up to its head (W1 row gather, aggregation + bias + relu, H @ W2, each aggregation followed by the
+ *    launch that sums rows of more than 64 entries again).  X != NULL: features X [R, N] under the conventions of
+ *    gmc_forward_features (ldx >= N a multiple of 4, 16-byte aligned, layer 1 ignores batch->vals, a graph may have more
+ *    nodes than N): layer 1's feature transform is gmc_gemm_f32.  The head is one row-parallel launch of
+ *    csrc/functional.hip on the grid of csrc/large.hip (tiles of 256 rows, several workgroups per graph).
+ *  - gmc_fn_backward: the gradient of sum(GP o P) for the caller's GP [R,K] = dLoss/dP.  It takes the workspace (and X) of
+ *    the gmc_fn_forward call that produced P; the forward leaves H and Z0 there, and nothing that depends on P.  One
+ *    backward per forward: the backward turns those buffers into its own scratch.
+ *    GZ = P o (GP - rowsum(GP o P)) per row, dinv o GZ and the tile partials of db2 in one launch, the per-graph fold of
+ *    those, GY2 = A @ (dinv o GZ), then the backward of gmc_large_train_fwd_bwd behind its head.  With X: dW1 = X^T @ U is
+ *    written straight into grad and dX [R, N] (leading dimension lddx, as ldx; NULL: not computed) = U @ W1^T, both
+ *    gmc_gemm_f32.  grad is the flat [W1 | b1 | W2 | b2] buffer of N*F + F + F*K + K floats; there is no tail slot
+ *    (GMC_MODEL_GRAD_TAIL and GMC_MODEL_LOSS_EXPECTED are not read).  An empty batch zeroes grad and launches nothing else.
+ *  - gmc_fn_cut_loss_f32: the two losses as defined for gmc_kway_* above, for given probabilities P [R,K]: loss [B] (device
+ *    or pinned host memory: one system-scope store per graph) and, when GP != NULL, GP [R,K] = dLoss/dP.
+ *    GMC_LOSS_CUT: loss = -C * cut(S), S the row argmax (first maximum wins), GP = C * A_val @ onehot_K(S);
+ *    GMC_LOSS_EXPECTED_CUT: loss = -C/2 * sum w_uv (1 - Pt_u . Pt_v), GP = C * A_val @ Pt.  terminals = 1: nodes 0..K-1 of
+ *    every graph are forced to classes 0..K-1 (rows 0..K-1 of Pt are e_0..e_{K-1}, straight-through: GP is written on
+ *    every row), as everywhere in the library; n_max < K is then GMC_ERR_GRAPH_SIZE.  terminals = 0: no node is forced,
+ *    Pt = P and S is the plain argmax - unconstrained max-K-cut.  Two launches: the rows' terms (a row reads its
+ *    neighbours' rows of P; the hard loss takes their argmax on the fly), then the per-graph fold.
+ * Summation orders (csrc/functional.hip states them; all fixed, no float atomics: results are bitwise reproducible and a
+ * graph's P, loss, GP and share of the gradient's partials do not depend on what else is in the batch): a row's neighbours
+ * in CSR order by one lane, a row of more than 64 entries by a wave (lane j takes entries j, j + 64, ..., then a butterfly
+ * over the lanes); sums over a graph's rows by tiles of 256 rows (wave butterfly, waves ascending), then the tiles
+ * ascending; the per-graph db2 partials [B,K] folded as gmc_kway_train_fwd_bwd folds them.
+ * No dropout (dropout_p > 0: GMC_ERR_UNSUPPORTED), W1_slab is not read.  P, GP and model->W2 must be 16-byte aligned.
+ * Argument checks, all before any HIP call, in the order documented for the fused entry points with the steps of
+ * gmc_kway_*: 1. the struct pointers (NULL); 2. abi, required pointer fields, K (CLASSES), sizes (SHAPE), F (UNSUPPORTED),
+ * dropout_p (SHAPE, then > 0 UNSUPPORTED), W1_slab (ALIGN), n_max < K or > GMC_LARGE_MAX_GRAPH_NODES (GRAPH_SIZE), n_max > N
+ * without X (SHAPE); 3. with X: ldx < N (SHAPE), then X, ldx % 4, W1 (ALIGN); 4. workspace, P, GP, grad (NULL); 5. lddx < N
+ * (SHAPE), then grad, P, GP, W2, dX, lddx % 4 (ALIGN); 6. the workspace size.  gmc_fn_cut_loss_f32: 1. batch (NULL); 2. abi,
+ * goff / rowptr / gcol / lcol (NULL), K (CLASSES), sizes (SHAPE), loss_kind (GMC_ERR_LOSS), n_max (GRAPH_SIZE); 4. workspace,
+ * P, loss (NULL); 5. P, GP (ALIGN); 6. the workspace size.  B == 0 returns GMC_OK without a launch (gmc_fn_backward: after
+ * zeroing grad).  No call allocates or synchronises; everything is enqueued on the caller's stream. */
+/* bytes of scratch one gmc_fn_forward + gmc_fn_backward pair needs (features != 0: X is given - no dW1 scratch); 0 for a
+ * NULL struct, another abi word, or K outside 2..GMC_KWAY_MAX_CLASSES */
+size_t gmc_fn_workspace_bytes(const gmc_batch *batch, const gmc_model *model, int features);
+int gmc_fn_forward(const gmc_batch *batch, const gmc_model *model, const float *X /* NULL: the padded adjacency */,
+                   int64_t ldx, void *workspace, size_t workspace_bytes, float *P, gmc_stream_t stream);
+int gmc_fn_backward(const gmc_batch *batch, const gmc_model *model, const float *X, int64_t ldx, void *workspace,
+                    size_t workspace_bytes, const float *P, const float *GP, float *grad, float *dX /* or NULL */,
+                    int64_t lddx, gmc_stream_t stream);
+/* bytes of scratch gmc_fn_cut_loss_f32 needs: the tile partials, R / 256 + B + 1 floats (0 for a NULL batch, another abi
+ * word, negative sizes or K outside 2..GMC_KWAY_MAX_CLASSES) */
+size_t gmc_fn_cut_loss_workspace_bytes(const gmc_batch *batch, int32_t K);
+int gmc_fn_cut_loss_f32(const gmc_batch *batch, int32_t K, int32_t terminals, const float *P, float C, int32_t loss_kind,
+                        void *workspace, size_t workspace_bytes, float *loss /*[B]*/, float *GP /*[R,K] or NULL*/,
+                        gmc_stream_t stream);
+
 /* ---- one model per graph (extension: the reference's model as an instance-wise solver, a whole batch per step) ---------
  *
  * The features of the reference are the padded adjacency, so row i of conv1.weight is the embedding of NODE ID i: a model
