@@ -9,7 +9,7 @@ directory on ``sys.path`` to get the reference's own import roots
 (``Training.TrainingNeural``, ``DataGenerator.graphExtender``, ``commons``, ``python.*``).
 """
 from . import hip  # noqa: F401
-from .graph import BatchArrays, DGLError, GraphBatch, GraphHandle, from_networkx  # noqa: F401
+from .graph import BatchArrays, DGLError, GraphBatch, GraphHandle, from_edge_index, from_networkx  # noqa: F401
 from .engine import FusedEngine, shard_by_weight, shard_for_rank  # noqa: F401
 from . import functional  # noqa: F401
 

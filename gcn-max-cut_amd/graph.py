@@ -143,6 +143,83 @@ def from_networkx(nx_graph) -> GraphHandle:
                        None if bool(np.all(ww == 1.0)) else ww)
 
 
+PAIRS = ("both", "once")
+
+
+def _check_pairs(pairs: str) -> None:
+    if pairs not in PAIRS:
+        raise ValueError(f"pairs must be one of {PAIRS}, got {pairs!r}")
+
+
+def _integer_dtype(dtype) -> bool:
+    if isinstance(dtype, torch.dtype):
+        return dtype in (torch.uint8, torch.int8, torch.int16, torch.int32, torch.int64)
+    return np.issubdtype(dtype, np.integer)
+
+
+def _check_edge_arrays(edge_index, edge_weight) -> int:
+    """Shapes and dtypes of an ``edge_index`` [2, E] / ``edge_weight`` [E] pair (numpy or torch); returns E."""
+    shape = tuple(getattr(edge_index, "shape", ()))
+    if len(shape) != 2 or shape[0] != 2:
+        raise ValueError(f"edge_index must be [2, E], got shape {shape}")
+    if not _integer_dtype(edge_index.dtype):
+        raise ValueError(f"edge_index must hold integers, got {edge_index.dtype}")
+    E = int(shape[1])
+    if edge_weight is not None:
+        wshape = tuple(getattr(edge_weight, "shape", ()))
+        if wshape != (E,):
+            raise ValueError(f"edge_weight must be [E = {E}], got shape {wshape}")
+        floating = edge_weight.dtype.is_floating_point if isinstance(edge_weight.dtype, torch.dtype) \
+            else np.issubdtype(edge_weight.dtype, np.floating)
+        if not (floating or _integer_dtype(edge_weight.dtype)):
+            raise ValueError(f"edge_weight must hold real numbers, got {edge_weight.dtype}")
+    return E
+
+
+def from_edge_index(edge_index, num_nodes: int, edge_weight=None, pairs: str = "both") -> GraphHandle:
+    """The ``GraphHandle`` of one undirected graph given as an ``edge_index`` [2, E] array of node ids 0..num_nodes-1
+    (numpy or CPU torch, any integer dtype) and an optional ``edge_weight`` [E]: what ``from_networkx`` returns for the
+    same graph, byte for byte (``rowptr``, ``col``, ``weight`` or ``None`` when every weight is exactly 1), in vectorised
+    numpy.  ``pairs="both"``: every edge is listed in both directions and a self-loop once (the convention of the GNN
+    libraries); ``pairs="once"``: every edge is listed once, in either orientation.  Raises ``ValueError`` for ids out of
+    range, repeated entries, and - ``pairs="both"`` - an entry whose reverse is missing or carries another weight."""
+    _check_pairs(pairs)
+    E = _check_edge_arrays(edge_index, edge_weight)
+    n = int(num_nodes)
+    if n < 0 or n >= 2 ** 31:
+        raise ValueError(f"num_nodes = {n}: need 0 <= num_nodes < 2^31")
+    ei = edge_index.detach().cpu().numpy() if isinstance(edge_index, torch.Tensor) else np.asarray(edge_index)
+    rows, cols = ei[0].astype(np.int64), ei[1].astype(np.int64)
+    if edge_weight is None:
+        ww = np.ones(E, np.float32)
+    else:
+        ww = edge_weight.detach().cpu().numpy() if isinstance(edge_weight, torch.Tensor) else np.asarray(edge_weight)
+        ww = ww.astype(np.float32)
+    bad = int(((rows < 0) | (rows >= n) | (cols < 0) | (cols >= n)).sum())
+    if bad:
+        raise ValueError(f"edge_index: {bad} entries with an id outside 0..{n - 1}")
+    if pairs == "once":
+        keep = rows != cols
+        rows, cols, ww = (np.concatenate([rows, cols[keep]]), np.concatenate([cols, rows[keep]]),
+                          np.concatenate([ww, ww[keep]]))
+    if rows.size >= 2 ** 31:
+        raise ValueError("graph too large for int32 indices")
+    order = np.lexsort((cols, rows))
+    rows, cols, ww = rows[order], cols[order], ww[order]
+    dup = int(((rows[1:] == rows[:-1]) & (cols[1:] == cols[:-1])).sum())
+    if dup:
+        raise ValueError(f"edge_index: {dup} repeated entries")
+    keys = rows * max(n, 1) + cols   # ascending (the sort above) and distinct: every entry's reverse is looked up in it
+    at = np.minimum(np.searchsorted(keys, cols * max(n, 1) + rows), max(keys.size - 1, 0))
+    asym = int(((keys[at] != cols * max(n, 1) + rows) | (ww[at] != ww)).sum())
+    if asym:
+        raise ValueError(f"edge_index: {asym} entries whose reverse is missing or carries another weight")
+    rowptr = np.zeros(n + 1, np.int64)
+    np.cumsum(np.bincount(rows, minlength=n), out=rowptr[1:])
+    return GraphHandle(n, rowptr.astype(np.int32), cols.astype(np.int32),
+                       None if bool(np.all(ww == 1.0)) else ww)
+
+
 class BatchArrays:
     """Host-side (numpy) form of a block-diagonal batch: everything ``struct gmc_batch``
     points to, built without touching a GPU (so the layout is testable on CPU)."""
@@ -295,6 +372,177 @@ class GraphBatch:
             ell=hip.ptr(self.ell), ell_vals=hip.ptr(self.ell_vals), ell_width=h.ell_width, ell_slots=h.ell_slots,
             ovf_ptr=hip.ptr(self.ovf_ptr), ovf_ids=hip.ptr(self.ovf_ids), ovf_vals=hip.ptr(self.ovf_vals),
             ovf_max_blocks=h.ovf_max_blocks)
+
+    @classmethod
+    def from_edge_index(cls, edge_index, ptr=None, num_nodes: Optional[int] = None, edge_weight=None, *,
+                        pairs: str = "both", device: Optional[torch.device] = None,
+                        allow_zero_degree: bool = False) -> "GraphBatch":
+        """The batch of the graphs an ``edge_index`` [2, E] tensor describes, built on the GPU: every array and scalar
+        equals, byte for byte, what ``GraphBatch([from_networkx(g) for g in graphs])`` holds for the same graphs.
+
+        ``edge_index``: global node ids in block-diagonal numbering (graph ``g`` owns ``ptr[g] .. ptr[g+1]-1``), any
+        integer dtype, numpy or torch, on the CPU or already on the device.  ``ptr`` [B+1] is PyG's ``Batch.ptr``; for
+        one graph pass ``num_nodes`` instead.  ``edge_weight`` [E] is optional; weights that are all exactly 1.0 give
+        ``vals is None``.  ``pairs="both"``: every undirected edge is present in both directions and a self-loop once
+        (PyG's convention); ``pairs="once"``: every edge is listed once in either orientation and the flipped entries
+        are appended here.
+
+        Shapes, dtypes, a ``ptr`` that does not ascend from 0, graph sizes outside 3..``hip.LARGE_MAX_GRAPH_NODES`` and
+        the int32 limits raise ``ValueError`` before the library is loaded.  What only the data can tell - ids out of
+        range, endpoints in two graphs, repeated entries, an entry whose reverse is missing or weighted differently,
+        nodes without neighbours (unless ``allow_zero_degree``) - is counted on the device (such entries are never used
+        as an index) and raises ``ValueError`` naming the kind and the count, before the table stage is launched.
+
+        Synchronisation: the call reads the device's report (80 bytes) once, between gmc_batch_build_csr and
+        gmc_batch_build_table; that read is the only point at which it waits for the GPU when ``ptr`` is host data and
+        ``pairs="both"``.  (``ptr`` is needed on the host and is copied there when it is a device tensor; ``"once"``
+        selects the non-loop entries with a boolean mask, whose length torch reads back.)
+
+        The result is an ordinary ``GraphBatch``; ``.host`` (what ``refine_order`` and the colour orders read) is copied
+        back from the device on first access."""
+        _check_pairs(pairs)
+        E = _check_edge_arrays(edge_index, edge_weight)
+        if (ptr is None) == (num_nodes is None):
+            raise ValueError("pass exactly one of ptr (graph boundaries) and num_nodes (a single graph)")
+        if ptr is None:
+            goff = np.asarray([0, int(num_nodes)], np.int64)
+        else:
+            p = ptr.detach().cpu().numpy() if isinstance(ptr, torch.Tensor) else np.asarray(ptr)
+            if p.ndim != 1 or p.size < 1:
+                raise ValueError(f"ptr must be [B + 1], got shape {tuple(p.shape)}")
+            if not np.issubdtype(p.dtype, np.integer):
+                raise ValueError(f"ptr must hold integers, got {p.dtype}")
+            goff = p.astype(np.int64)
+            if int(goff[0]) != 0 or bool(np.any(np.diff(goff) < 0)):
+                raise ValueError("ptr must ascend from 0")
+        ns = np.diff(goff)
+        B = int(ns.size)
+        for n in ns:
+            if n < 3 or n > hip.LARGE_MAX_GRAPH_NODES:
+                raise ValueError(f"graph with {int(n)} nodes: need 3 <= n <= {hip.LARGE_MAX_GRAPH_NODES}")
+        R = int(goff[-1])
+        if R >= 2 ** 31 or E * (2 if pairs == "once" else 1) >= 2 ** 31:
+            raise ValueError("batch too large for int32 indices")
+        if B == 0 and E:
+            raise ValueError(f"edge_index holds {E} entries but ptr describes no graph")
+        device = device or hip.require_gpu()
+        lib = hip.load()
+        ei = edge_index if isinstance(edge_index, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(edge_index))
+        ei = ei.to(device)
+        if ei.dtype != torch.int32:   # ids beyond int32 must not wrap into range: -1 and R are both refused on the device
+            ei = ei.clamp(-1, R).to(torch.int32)
+        src, dst = ei[0].contiguous(), ei[1].contiguous()
+        w = None
+        if edge_weight is not None:
+            w = edge_weight if isinstance(edge_weight, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(edge_weight))
+            w = w.to(device=device, dtype=torch.float32).contiguous()
+        if pairs == "once":
+            keep = src != dst
+            src, dst = torch.cat([src, dst[keep]]), torch.cat([dst, src[keep]])
+            if w is not None:
+                w = torch.cat([w, w[keep]])
+            E = int(src.numel())
+            if E >= 2 ** 31:
+                raise ValueError("batch too large for int32 indices")
+        new = lambda shape, dtype: torch.empty(shape, dtype=dtype, device=device)
+        self = cls.__new__(cls)
+        self.device = device
+        self.B, self.R, self.sizes, self.goff_host = B, R, ns, goff
+        self.n_max = int(ns.max()) if B else 0
+        self.uniform_n = int(ns[0]) if B and bool(np.all(ns == ns[0])) else 0
+        self.goff = torch.from_numpy(goff.astype(np.int32)).to(device)
+        self.rowptr = torch.zeros(R + 1, dtype=torch.int32, device=device) if B == 0 else new(R + 1, torch.int32)
+        self.gcol, self.lcol, self.dinv = new(E, torch.int32), new(E, torch.int32), new(R, torch.float32)
+        self.vals = None if w is None else new(E, torch.float32)
+        self.ell = self.ell_vals = self.ovf_ptr = self.ovf_ids = self.ovf_vals = None
+        W = ell_slots = ovf_max_blocks = max_degree = nnz_max = 0
+        if B:
+            report = new(hip.BB_REPORT_WORDS, torch.int32)
+            ws = new(int(lib.gmc_batch_build_workspace_bytes(B, R, E)), torch.uint8)
+            rc = lib.gmc_batch_build_csr(B, R, E, hip.ptr(self.goff), hip.ptr(src), hip.ptr(dst), hip.ptr(w),
+                                         hip.ptr(self.rowptr), hip.ptr(self.lcol), hip.ptr(self.gcol), hip.ptr(self.vals),
+                                         hip.ptr(self.dinv), hip.ptr(report), hip.ptr(ws), ws.numel(), hip.stream())
+            hip.check(rc, "gmc_batch_build_csr")
+            rep = dict(zip(hip.BB_REPORT, report.cpu().tolist()))   # the call's one wait for the device
+            faults = [("out_of_range", "with an id outside 0..R-1"), ("cross_graph", "whose endpoints lie in two graphs"),
+                      ("duplicate", "that repeat another entry"),
+                      ("asymmetric", "whose reverse entry is missing or carries another weight")]
+            found = [f"{rep[k]} entries {what}" for k, what in faults if rep[k]]
+            if rep["zero_degree"] and not allow_zero_degree:
+                found.append(f"{rep['zero_degree']} nodes without neighbours (allow_zero_degree=False)")
+            if found:
+                raise ValueError("edge_index: " + "; ".join(found))
+            max_degree, nnz_max = rep["max_degree"], rep["nnz_max"]
+            if w is not None and rep["non_unit"] == 0:
+                self.vals = None
+            W = 0
+            if max_degree > 0:   # BatchArrays.choose_width on the report's statistics
+                for cand in (8, 16):
+                    if rep[f"rows_over_{cand}"] * 200 <= R or (cand == 16 and rep["excess_16"] * 8 <= E):
+                        W = cand
+                        break
+            if self.n_max > hip.MAX_GRAPH_NODES or self.n_max >= 65535:
+                W = 0
+            blocks = 0
+            if W and max_degree > W:
+                ovf_max_blocks, blocks = rep[f"graph_blocks_{W}"], rep[f"blocks_{W}"]
+                if rep[f"row_blocks_{W}"] > 15 or ovf_max_blocks > 4095:
+                    W = ovf_max_blocks = blocks = 0
+            if W:
+                ell_slots = max(min(max_degree, W), 7 if W == 8 else 9)   # gmc_ell_slots_for
+                self.ell = new((R, W), torch.int16)
+                if self.vals is not None:
+                    self.ell_vals = new((R, W), torch.float32)
+                if max_degree > W:
+                    self.ovf_ptr, self.ovf_ids = new(R + 1, torch.int32), new(blocks * 8, torch.int16)
+                    if self.vals is not None:
+                        self.ovf_vals = new(blocks * 8, torch.float32)
+                rc = lib.gmc_batch_build_table(B, R, self.n_max, hip.ptr(self.goff), hip.ptr(self.rowptr),
+                                               hip.ptr(self.lcol), hip.ptr(self.vals), W, ell_slots, hip.ptr(self.ell),
+                                               hip.ptr(self.ell_vals), hip.ptr(self.ovf_ptr), hip.ptr(self.ovf_ids),
+                                               hip.ptr(self.ovf_vals), blocks, hip.ptr(ws), ws.numel(), hip.stream())
+                hip.check(rc, "gmc_batch_build_table")
+        self.nnz = E
+        self._scalars = dict(nnz_max=nnz_max, max_degree=max_degree, ell_width=W, ell_slots=ell_slots,
+                             ovf_max_blocks=ovf_max_blocks)
+        self.c = hip.GmcBatch(
+            B=B, R=R, nnz=E, n_max=self.n_max, uniform_n=self.uniform_n, nnz_max=nnz_max,
+            goff=hip.ptr(self.goff), rowptr=hip.ptr(self.rowptr), gcol=hip.ptr(self.gcol),
+            lcol=hip.ptr(self.lcol), vals=hip.ptr(self.vals), dinv=hip.ptr(self.dinv),
+            ell=hip.ptr(self.ell), ell_vals=hip.ptr(self.ell_vals), ell_width=W, ell_slots=ell_slots,
+            ovf_ptr=hip.ptr(self.ovf_ptr), ovf_ids=hip.ptr(self.ovf_ids), ovf_vals=hip.ptr(self.ovf_vals),
+            ovf_max_blocks=ovf_max_blocks)
+        return self
+
+    def __getattr__(self, name):
+        # only reached for attributes the instance lacks: a batch built on the device has no ``host`` until it is asked for
+        if name == "host" and "_scalars" in self.__dict__:
+            h = BatchArrays.__new__(BatchArrays)
+            back = lambda t, dtype=None: None if t is None else (t.cpu().numpy() if dtype is None else t.cpu().numpy().view(dtype))
+            h.B, h.R, h.nnz, h.n_max, h.uniform_n = self.B, self.R, self.nnz, self.n_max, self.uniform_n
+            h.sizes, h.goff = self.sizes, self.goff_host
+            h.rowptr, h.gcol, h.lcol = back(self.rowptr), back(self.gcol), back(self.lcol)
+            h.vals, h.dinv = back(self.vals), back(self.dinv)
+            h.ell, h.ell_vals = back(self.ell, np.uint16), back(self.ell_vals)
+            h.ovf_ptr, h.ovf_ids, h.ovf_vals = back(self.ovf_ptr), back(self.ovf_ids, np.uint16), back(self.ovf_vals)
+            for k, v in self._scalars.items():
+                setattr(h, k, v)
+            self.__dict__["host"] = h
+            return h
+        raise AttributeError(f"{type(self).__name__!r} object has no attribute {name!r}")
+
+    def handles(self) -> List[GraphHandle]:
+        """One ``GraphHandle`` per graph of the batch, from the batch's own arrays (read through ``.host``): what
+        ``from_networkx`` gives for each graph, for the entry points that take dataset items."""
+        h = self.host
+        out = []
+        for g in range(h.B):
+            r0, r1 = int(h.goff[g]), int(h.goff[g + 1])
+            e0, e1 = int(h.rowptr[r0]), int(h.rowptr[r1])
+            wt = None if h.vals is None else h.vals[e0:e1]
+            out.append(GraphHandle(r1 - r0, h.rowptr[r0:r1 + 1] - e0, h.lcol[e0:e1],
+                                   None if wt is None or bool(np.all(wt == 1.0)) else wt.copy()))
+        return out
 
     def ref(self):
         return C.byref(self.c)

@@ -32,7 +32,12 @@ LAYER1_ENV = "GCN_MAXCUT_LAYER1"
 ATTENTION_SLOPE = 0.2  # negative slope of the attention scores' leaky relu (the GAT paper's)
 INST_ADAM_TILE_FLOATS = 4096   # GMC_INST_ADAM_TILE_FLOATS: floats of a graph's W1 one workgroup of gmc_inst_adam_f32 takes
 KWAY_MAX_CLASSES = 8  # GMC_KWAY_MAX_CLASSES: number_classes the gmc_kway_* entry points take (2..8; 3 also has the fused path)
-ABI_VERSION = 200     # GMC_VERSION of include/gcnmaxcut.h these struct layouts follow (checked at load and per call)
+# GMC_BB_*: the int32 words of the report gmc_batch_build_csr leaves on the device (word k is BB_REPORT[k])
+BB_REPORT = ("out_of_range", "cross_graph", "duplicate", "asymmetric", "zero_degree", "max_degree", "rows_over_8",
+             "rows_over_16", "excess_8", "excess_16", "row_blocks_8", "row_blocks_16", "graph_blocks_8", "graph_blocks_16",
+             "blocks_8", "blocks_16", "non_unit", "nnz", "nnz_max")
+BB_REPORT_WORDS = 20  # GMC_BB_REPORT_WORDS
+ABI_VERSION = 200    # GMC_VERSION of include/gcnmaxcut.h these struct layouts follow (checked at load and per call)
 
 
 class HipExtensionError(RuntimeError):
@@ -175,6 +180,9 @@ def _api() -> dict:
         "gmc_large_sample_seeded_f32": (i, [B, vp, i32, vp, i32, vp, vp, sz, vp, vp, vp, vp, vp]),
         "gmc_large_anneal_f32": (i, [B, i32, vp, vp, vp, i32, i32, vp, vp, i32, vp, C.c_uint64, i32, vp, sz, vp, vp, vp,
                                      vp, vp, vp, vp]),
+        "gmc_batch_build_workspace_bytes": (sz, [i32, i32, i64]),
+        "gmc_batch_build_csr": (i, [i32, i32, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]),
+        "gmc_batch_build_table": (i, [i32, i32, i32, vp, vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, i32, vp, sz, vp]),
     }
 
 

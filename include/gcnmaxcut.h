@@ -1194,6 +1194,69 @@ int gmc_large_anneal_f32(const gmc_batch *batch, int32_t K, const int32_t *order
                          int32_t *best_idx /*[B]*/, int32_t *snap_sweep /*or NULL*/, int32_t *sweeps /*or NULL*/,
                          gmc_stream_t stream);
 
+/* ---- building a batch on the device from directed entries -------------------------------------------------------------
+ * The arrays of a gmc_batch from E directed entries (src[e], dst[e][, w[e]]): int32 global row ids in block-diagonal
+ * numbering (graph g owns rows goff[g] .. goff[g+1]-1), both directions of every undirected edge present, a self-loop
+ * once.  What the reference's data path builds with dgl.from_networkx per graph (graphExtender.py:102) and what this
+ * library's host code builds from that (CSR sorted by column inside a row, dinv = 1/sqrt(max(deg,1)) with numpy's
+ * float32 bits, the neighbour table in gmc_ell_arrange_host's slot order, the 8-entry overflow blocks): the same bytes.
+ * All pointers are device memory; nothing is allocated, everything runs on the caller's stream, the workspace need not
+ * be zeroed, kernel boundaries are the only synchronisation, no floating-point value is summed, and two builds of the
+ * same entries in any order give the same bytes.
+ *
+ * gmc_batch_build_csr writes rowptr [R+1], gcol / lcol [E], vals [E] (exactly when w is given), dinv [R] and the report,
+ * in 11 launches (init, count, the three-launch scan, scatter, four sorts by row length, validate).  The row sorts: up
+ * to 8 entries 8 lanes, up to 64 a wave, up to 4096 a workgroup in LDS, beyond that one workgroup per row on global
+ * memory - slow (a star of 2^20 - 1 leaves is legal; estimated, not measured: on the order of 0.1 s) and rare.  An entry with an id
+ * outside 0..R-1, or with endpoints in two graphs, is counted in the report and skipped: it is never used as an index,
+ * and the arrays then hold the report's GMC_BB_NNZ < E entries.  The caller reads the report (one device-to-host copy)
+ * and decides: any of the first five words non-zero is bad input.
+ *
+ * gmc_batch_build_table writes the neighbour table ell [R][W] (W = 8 or 16, NS live slots as gmc_ell_slots_for says)
+ * and ell_vals (exactly when vals is given), and - when ovf_ptr is given - ovf_ptr [R+1] and the overflow lists of
+ * ovf_blocks blocks of eight (the report's GMC_BB_BLOCKS_8 / _16).  n_max: the largest graph, n_max + 4 <= 65535.
+ *
+ * Argument checks, before any HIP call: a NULL required pointer (workspace included) GMC_ERR_NULL; B < 0, R < B, E
+ * outside 0..2^31-1, W, NS outside 1..W, ovf_blocks < 0 GMC_ERR_SHAPE; n_max GMC_ERR_GRAPH_SIZE; a workspace below
+ * gmc_batch_build_workspace_bytes(B, R, E) GMC_ERR_WORKSPACE; B == 0 returns GMC_OK without a launch. */
+enum {
+    GMC_BB_OUT_OF_RANGE = 0,    /* entries with an id outside 0..R-1 (skipped) */
+    GMC_BB_CROSS_GRAPH = 1,     /* entries whose endpoints lie in two graphs (skipped) */
+    GMC_BB_DUPLICATE = 2,       /* entries equal to their predecessor in the sorted row */
+    GMC_BB_ASYMMETRIC = 3,      /* entries whose reverse is missing or has another weight */
+    GMC_BB_ZERO_DEGREE = 4,     /* rows without entries */
+    GMC_BB_MAX_DEGREE = 5,
+    GMC_BB_ROWS_OVER_8 = 6,     /* rows longer than 8 / 16 entries, and the entries beyond */
+    GMC_BB_ROWS_OVER_16 = 7,
+    GMC_BB_EXCESS_8 = 8,
+    GMC_BB_EXCESS_16 = 9,
+    GMC_BB_ROW_BLOCKS_8 = 10,   /* most overflow blocks of a row / of a graph at either width */
+    GMC_BB_ROW_BLOCKS_16 = 11,
+    GMC_BB_GRAPH_BLOCKS_8 = 12,
+    GMC_BB_GRAPH_BLOCKS_16 = 13,
+    GMC_BB_BLOCKS_8 = 14,       /* overflow blocks of the whole batch */
+    GMC_BB_BLOCKS_16 = 15,
+    GMC_BB_NON_UNIT = 16,       /* weights that are not exactly 1.0 */
+    GMC_BB_NNZ = 17,            /* entries kept: rowptr[R] */
+    GMC_BB_NNZ_MAX = 18,        /* most entries of a graph */
+    GMC_BB_REPORT_WORDS = 20
+};
+
+/* bytes of workspace either stage needs (about 16 R); 0 for negative sizes or E >= 2^31; host only */
+size_t gmc_batch_build_workspace_bytes(int32_t B, int32_t R, int64_t E);
+
+int gmc_batch_build_csr(int32_t B, int32_t R, int64_t E, const int32_t *goff /*[B+1]*/, const int32_t *src /*[E]*/,
+                        const int32_t *dst /*[E]*/, const float *w /*[E] or NULL*/, int32_t *rowptr /*[R+1]*/,
+                        int32_t *lcol /*[E]*/, int32_t *gcol /*[E]*/, float *vals /*[E], with w*/, float *dinv /*[R]*/,
+                        int32_t *report /*[GMC_BB_REPORT_WORDS]*/, void *workspace, size_t workspace_bytes,
+                        gmc_stream_t stream);
+
+int gmc_batch_build_table(int32_t B, int32_t R, int32_t n_max, const int32_t *goff, const int32_t *rowptr,
+                          const int32_t *lcol, const float *vals /*or NULL*/, int32_t W, int32_t NS,
+                          uint16_t *ell /*[R][W]*/, float *ell_vals /*[R][W], with vals*/, int32_t *ovf_ptr /*[R+1] or NULL*/,
+                          uint16_t *ovf_ids /*[8 ovf_blocks]*/, float *ovf_vals /*[8 ovf_blocks], with vals*/,
+                          int32_t ovf_blocks, void *workspace, size_t workspace_bytes, gmc_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
