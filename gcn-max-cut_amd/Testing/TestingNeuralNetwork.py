@@ -26,6 +26,10 @@ across generations (``gmc_kway_evolve_f32``): children of two class-aligned pare
 for graphs of up to ``hip.LARGE_MAX_GRAPH_NODES`` nodes (``gmc_large_round_conditional_f32``,
 ``gmc_large_local_search_f32``, ``gmc_large_sample_seeded_f32``, ``gmc_large_anneal_f32``): a graph shared by several
 workgroups, its state in a workspace on the device.
+Every K-class function above takes ``terminals`` (default ``True``: nodes 0..K-1 of a graph are fixed to classes
+0..K-1, the reference's problem).  ``terminals=False`` is plain max-K-cut: no node is fixed, a graph needs one node, and
+the calls go through the ``_t`` entry points of the library with ``terminals = 0``.  The 3-class functions and
+``decode_dataset`` keep their terminals.
 The reporting / plotting half of the reference module (``analyze_results`` .. ``generate_summary_report``,
 :297-638) is presentation code outside the path and is not reproduced.
 """
@@ -349,16 +353,33 @@ def _rounding_classes(classes: int) -> int:
     return K
 
 
-def _round_on_gpu(batch: GraphBatch, P: torch.Tensor, descent_sweeps: int):
+def _call(name: str, terminals: bool, head: tuple, tail: tuple) -> None:
+    """Calls the entry point ``name`` with the arguments ``head + tail`` - or, without terminals, its ``_t`` twin, whose
+    ``terminals`` argument (0) stands between the two - and raises on a status code."""
+    lib = hip.load()
+    if terminals:
+        hip.check(getattr(lib, name)(*head, *tail), name)
+    else:
+        twin = name[:-len("_f32")] + "_t_f32"
+        hip.check(getattr(lib, twin)(*head, 0, *tail), twin)
+
+
+def _first_argmax(P: torch.Tensor) -> torch.Tensor:
+    """The first maximum of every row of P [R, K] as int32 [R]: the argmax decode when no row is overridden."""
+    K = P.shape[1]
+    ids = torch.arange(K, device=P.device, dtype=torch.int32).expand_as(P)
+    top = P.max(dim=1, keepdim=True).values
+    return torch.where(P == top, ids, torch.full_like(ids, K)).min(dim=1).values.clamp_(max=K - 1)
+
+
+def _round_on_gpu(batch: GraphBatch, P: torch.Tensor, descent_sweeps: int, terminals: bool = True):
     """Rounding by conditional expectations + descent (gmc_round_conditional_f32) of P [R, K] for every graph of the
     batch, one launch; returns the assignment [R] int8, and per graph its cut, the expected cut and the descent sweeps
     run."""
     K = _rounding_classes(P.shape[1])
     if descent_sweeps < 0:
         raise ValueError(f"descent_sweeps must be >= 0, got {descent_sweeps}")
-    if batch.B and int(batch.sizes.min()) < K:
-        raise ValueError(f"number_classes = {K}: every graph needs at least {K} nodes (nodes 0..{K - 1} are the "
-                         f"terminals), got one with {int(batch.sizes.min())}")
+    _needs_terminals(batch, K, terminals)
     dev = batch.device
     assign = torch.empty(batch.R, dtype=torch.int8, device=dev)
     cut = torch.empty(batch.B, dtype=torch.float32, device=dev)
@@ -366,31 +387,28 @@ def _round_on_gpu(batch: GraphBatch, P: torch.Tensor, descent_sweeps: int):
     sweeps = torch.empty(batch.B, dtype=torch.int32, device=dev)
     if batch.B == 0:   # nothing to launch (empty tensors have no device pointer to hand over)
         return assign, cut, expected, sweeps
-    order, cgoff, cptr = batch.refine_order(K)
+    order, cgoff, cptr = batch.refine_order(K, terminals)
     p = hip.ptr
-    rc = hip.load().gmc_round_conditional_f32(batch.ref(), p(P.contiguous()), K, p(order), p(cgoff), p(cptr),
-                                              int(descent_sweeps), p(assign), p(cut), p(expected), p(sweeps),
-                                              hip.stream())
-    hip.check(rc, "gmc_round_conditional_f32")
+    _call("gmc_round_conditional_f32", terminals, (batch.ref(), p(P.contiguous()), K),
+          (p(order), p(cgoff), p(cptr), int(descent_sweeps), p(assign), p(cut), p(expected), p(sweeps), hip.stream()))
     return assign, cut, expected, sweeps
 
 
-def conditional_rounding(node_probabilities, graph, descent_sweeps: int = 0) -> Tuple[List[int], Any]:
+def conditional_rounding(node_probabilities, graph, descent_sweeps: int = 0,
+                         terminals: bool = True) -> Tuple[List[int], Any]:
     """Round the node probabilities of ``graph`` ([n, K], K = number_classes in 2..8, nodes 0..K-1 the terminals) into
     one partition by conditional expectations on the GPU (extension, include/gcnmaxcut.h
     ``gmc_round_conditional_f32``): every node in turn takes the class that keeps the expected cut of the still
     unrounded rest from falling, so the cut returned is at least the expected cut of rounding every node independently
     from its row - what ``loss="expected_cut"`` trains on - deterministic, one visit per node.  ``descent_sweeps > 0``
     then runs that many sweeps of the local search's rule at K classes (until one moves nothing).  Returns the
-    assignment and its cut value."""
+    assignment and its cut value.  ``terminals=False``: no node is fixed, every node is rounded (and may move)."""
     probs = node_probabilities if isinstance(node_probabilities, torch.Tensor) else torch.from_numpy(np.asarray(node_probabilities))
     if probs.dim() != 2:
         raise ValueError(f"node_probabilities must be [n, number_classes], got {tuple(probs.shape)}")
     K = _rounding_classes(probs.shape[1])
     n = graph.number_of_nodes()
-    if n < K:
-        raise ValueError(f"number_classes = {K}: the graph needs at least {K} nodes (nodes 0..{K - 1} are the "
-                         f"terminals), got {n}")
+    _check_graph_size(n, K, terminals)
     if probs.shape[0] != n:
         raise ValueError(f"node_probabilities has {probs.shape[0]} rows, the graph {n} nodes")
     if descent_sweeps < 0:
@@ -398,7 +416,7 @@ def conditional_rounding(node_probabilities, graph, descent_sweeps: int = 0) -> 
     dev = hip.require_gpu()
     probs = probs.detach().to(dev, torch.float32)
     batch = GraphBatch([from_networkx(graph)], None, dev)
-    assign, cut, _, _ = _round_on_gpu(batch, probs, descent_sweeps)
+    assign, cut, _, _ = _round_on_gpu(batch, probs, descent_sweeps, terminals)
     return assign.cpu().tolist(), _as_number(cut.item())
 
 
@@ -412,13 +430,13 @@ def _large_workspace(batch: GraphBatch, K: int) -> torch.Tensor:
     return torch.empty(need, dtype=torch.uint8, device=batch.device)
 
 
-def _large_round_on_gpu(batch: GraphBatch, P: torch.Tensor, descent_sweeps: int):
+def _large_round_on_gpu(batch: GraphBatch, P: torch.Tensor, descent_sweeps: int, terminals: bool = True):
     """:func:`_round_on_gpu` through gmc_large_round_conditional_f32: the same rule with a graph shared by several
     workgroups, for graphs of up to ``hip.LARGE_MAX_GRAPH_NODES`` nodes; the same four results."""
     K = _rounding_classes(P.shape[1])
     if descent_sweeps < 0:
         raise ValueError(f"descent_sweeps must be >= 0, got {descent_sweeps}")
-    _needs_terminals(batch, K)
+    _needs_terminals(batch, K, terminals)
     dev = batch.device
     assign = torch.empty(batch.R, dtype=torch.int8, device=dev)
     cut = torch.empty(batch.B, dtype=torch.float32, device=dev)
@@ -426,17 +444,17 @@ def _large_round_on_gpu(batch: GraphBatch, P: torch.Tensor, descent_sweeps: int)
     sweeps = torch.empty(batch.B, dtype=torch.int32, device=dev)
     if batch.B == 0:   # nothing to launch (empty tensors have no device pointer to hand over)
         return assign, cut, expected, sweeps
-    order, cgoff, cptr = batch.refine_order(K)
+    order, cgoff, cptr = batch.refine_order(K, terminals)
     ws = _large_workspace(batch, K)
     p = hip.ptr
-    rc = hip.load().gmc_large_round_conditional_f32(batch.ref(), p(P.contiguous()), K, p(order), p(cgoff), p(cptr),
-                                                    batch.refine_classes(K), int(descent_sweeps), p(ws), ws.numel(),
-                                                    p(assign), p(cut), p(expected), p(sweeps), hip.stream())
-    hip.check(rc, "gmc_large_round_conditional_f32")
+    _call("gmc_large_round_conditional_f32", terminals, (batch.ref(), p(P.contiguous()), K),
+          (p(order), p(cgoff), p(cptr), batch.refine_classes(K, terminals), int(descent_sweeps), p(ws), ws.numel(),
+           p(assign), p(cut), p(expected), p(sweeps), hip.stream()))
     return assign, cut, expected, sweeps
 
 
-def large_conditional_rounding(node_probabilities, graph, descent_sweeps: int = 0) -> Tuple[List[int], Any]:
+def large_conditional_rounding(node_probabilities, graph, descent_sweeps: int = 0,
+                               terminals: bool = True) -> Tuple[List[int], Any]:
     """:func:`conditional_rounding` for a graph of any size from number_classes to ``hip.LARGE_MAX_GRAPH_NODES`` nodes
     (extension, include/gcnmaxcut.h ``gmc_large_round_conditional_f32``): the same rule, arguments and results - on a
     graph :func:`conditional_rounding` takes, the same assignment - with the graph shared by several workgroups and
@@ -447,9 +465,7 @@ def large_conditional_rounding(node_probabilities, graph, descent_sweeps: int = 
         raise ValueError(f"node_probabilities must be [n, number_classes], got {tuple(probs.shape)}")
     K = _rounding_classes(probs.shape[1])
     n = graph.number_of_nodes()
-    if n < K:
-        raise ValueError(f"number_classes = {K}: the graph needs at least {K} nodes (nodes 0..{K - 1} are the "
-                         f"terminals), got {n}")
+    _check_graph_size(n, K, terminals)
     if probs.shape[0] != n:
         raise ValueError(f"node_probabilities has {probs.shape[0]} rows, the graph {n} nodes")
     if descent_sweeps < 0:
@@ -458,16 +474,17 @@ def large_conditional_rounding(node_probabilities, graph, descent_sweeps: int = 
     probs = probs.detach().to(dev, torch.float32)
     handle = graph if isinstance(graph, GraphHandle) else from_networkx(graph)
     batch = GraphBatch([handle], None, dev)
-    assign, cut, _, _ = _large_round_on_gpu(batch, probs, descent_sweeps)
+    assign, cut, _, _ = _large_round_on_gpu(batch, probs, descent_sweeps, terminals)
     return assign.cpu().tolist(), _as_number(cut.item())
 
 
-def large_local_search(partition_assignment, graph, number_classes: int, max_sweeps: int = 100) -> Tuple[List[int], Any]:
+def large_local_search(partition_assignment, graph, number_classes: int, max_sweeps: int = 100,
+                       terminals: bool = True) -> Tuple[List[int], Any]:
     """:func:`kway_local_search` for a graph of any size from number_classes to ``hip.LARGE_MAX_GRAPH_NODES`` nodes
     (extension, include/gcnmaxcut.h ``gmc_large_local_search_f32``): the same rule, arguments and results - on a graph
     :func:`kway_local_search` takes, the same assignment - with the graph shared by several workgroups.  Every launch
     of ``max_sweeps`` sweeps is issued whenever the search converges."""
-    K, part = _kway_partition("large_local_search", partition_assignment, graph, number_classes)
+    K, part = _kway_partition("large_local_search", partition_assignment, graph, number_classes, terminals)
     if max_sweeps < 0:
         raise ValueError(f"max_sweeps must be >= 0, got {max_sweeps}")
     dev = hip.require_gpu()
@@ -475,12 +492,12 @@ def large_local_search(partition_assignment, graph, number_classes: int, max_swe
     batch = GraphBatch([handle], None, dev)
     assign = torch.from_numpy(part.astype(np.int8)).to(dev)
     cut = torch.empty(1, dtype=torch.float32, device=dev)
-    order, cgoff, cptr = batch.refine_order(K)
+    order, cgoff, cptr = batch.refine_order(K, terminals)
     ws = _large_workspace(batch, K)
     p = hip.ptr
-    rc = hip.load().gmc_large_local_search_f32(batch.ref(), K, p(order), p(cgoff), p(cptr), batch.refine_classes(K),
-                                               int(max_sweeps), p(ws), ws.numel(), p(assign), p(cut), None, hip.stream())
-    hip.check(rc, "gmc_large_local_search_f32")
+    _call("gmc_large_local_search_f32", terminals, (batch.ref(), K),
+          (p(order), p(cgoff), p(cptr), batch.refine_classes(K, terminals), int(max_sweeps), p(ws), ws.numel(), p(assign),
+           p(cut), None, hip.stream()))
     return assign.cpu().tolist(), _as_number(cut.item())
 
 
@@ -496,11 +513,11 @@ def _large_search_workspace(batch: GraphBatch, K: int, cands: int) -> torch.Tens
 
 
 def _large_sample_on_gpu(batch: GraphBatch, P: torch.Tensor, iterations: int, seed: int, indices, keep_samples: bool,
-                         workspace: Optional[torch.Tensor] = None):
+                         workspace: Optional[torch.Tensor] = None, terminals: bool = True):
     """:func:`_kway_sample_on_gpu` through gmc_large_sample_seeded_f32: the same draws with a graph shared by several
     workgroups, for graphs of up to ``hip.LARGE_MAX_GRAPH_NODES`` nodes; the same four results."""
     K = _search_classes("the K-class sampler", P.shape[1])
-    _needs_terminals(batch, K)
+    _needs_terminals(batch, K, terminals)
     keys = sample_keys(seed, range(batch.B) if indices is None else indices)
     if keys.size != batch.B:
         raise ValueError(f"{keys.size} graph indices for a batch of {batch.B} graphs")
@@ -515,19 +532,18 @@ def _large_sample_on_gpu(batch: GraphBatch, P: torch.Tensor, iterations: int, se
         return best_assign, best_cut, cut_all, assign_all
     ws = _large_search_workspace(batch, K, iterations) if workspace is None else workspace
     p = hip.ptr
-    rc = hip.load().gmc_large_sample_seeded_f32(batch.ref(), p(P.contiguous()), K, p(gkey), iterations, p(assign_all),
-                                                p(ws), ws.numel(), p(cut_all), p(best_assign), p(best_cut),
-                                                p(best_iter), hip.stream())
-    hip.check(rc, "gmc_large_sample_seeded_f32")
+    _call("gmc_large_sample_seeded_f32", terminals, (batch.ref(), p(P.contiguous()), K),
+          (p(gkey), iterations, p(assign_all), p(ws), ws.numel(), p(cut_all), p(best_assign), p(best_cut), p(best_iter),
+           hip.stream()))
     return best_assign, best_cut, cut_all, assign_all
 
 
 def _large_anneal_on_gpu(batch: GraphBatch, K: int, assign: torch.Tensor, inv_temp: np.ndarray, seed: int,
-                         max_descent_sweeps: int, workspace: Optional[torch.Tensor] = None):
+                         max_descent_sweeps: int, workspace: Optional[torch.Tensor] = None, terminals: bool = True):
     """:func:`_kway_anneal_on_gpu` through gmc_large_anneal_f32, for graphs of up to ``hip.LARGE_MAX_GRAPH_NODES``
     nodes: the candidates assign [cands, R] int8 searched in place; the best assignment [R], its cut and candidate
     index per graph."""
-    _needs_terminals(batch, K)
+    _needs_terminals(batch, K, terminals)
     dev = batch.device
     cands = int(assign.shape[0])
     cut_all = torch.empty((batch.B, cands), dtype=torch.float32, device=dev)
@@ -536,22 +552,21 @@ def _large_anneal_on_gpu(batch: GraphBatch, K: int, assign: torch.Tensor, inv_te
     best_idx = torch.empty(batch.B, dtype=torch.int32, device=dev)
     if batch.B == 0:
         return best_assign, best_cut, best_idx
-    order, cgoff, cptr = batch.refine_order(K)
+    order, cgoff, cptr = batch.refine_order(K, terminals)
     sweeps = int(len(inv_temp))
     inv_t = torch.from_numpy(np.ascontiguousarray(inv_temp, np.float32)).to(dev) if sweeps else None
     levels = torch.from_numpy(anneal_levels()).to(dev) if sweeps else None
     ws = _large_search_workspace(batch, K, cands) if workspace is None else workspace
     p = hip.ptr
-    rc = hip.load().gmc_large_anneal_f32(batch.ref(), K, p(order), p(cgoff), p(cptr), batch.refine_classes(K), cands,
-                                         p(assign), p(inv_t), sweeps, p(levels), int(seed) & _M64,
-                                         int(max_descent_sweeps), p(ws), ws.numel(), p(cut_all), p(best_assign),
-                                         p(best_cut), p(best_idx), None, None, hip.stream())
-    hip.check(rc, "gmc_large_anneal_f32")
+    _call("gmc_large_anneal_f32", terminals, (batch.ref(), K),
+          (p(order), p(cgoff), p(cptr), batch.refine_classes(K, terminals), cands, p(assign), p(inv_t), sweeps, p(levels),
+           int(seed) & _M64, int(max_descent_sweeps), p(ws), ws.numel(), p(cut_all), p(best_assign), p(best_cut),
+           p(best_idx), None, None, hip.stream()))
     return best_assign, best_cut, best_idx
 
 
 def large_sampling_optimization(node_probabilities, graph, iterations: int = 200, *, seed: int = 0,
-                                graph_index: int = 0) -> Tuple[List[int], Any]:
+                                graph_index: int = 0, terminals: bool = True) -> Tuple[List[int], Any]:
     """:func:`sampling_optimization` for a graph of any size from number_classes to ``hip.LARGE_MAX_GRAPH_NODES`` nodes
     (extension, include/gcnmaxcut.h ``gmc_large_sample_seeded_f32``): the same draws, arguments and results - on a
     graph :func:`sampling_optimization` takes, the same assignment - with the graph shared by several workgroups.  The
@@ -561,9 +576,7 @@ def large_sampling_optimization(node_probabilities, graph, iterations: int = 200
         raise ValueError(f"node_probabilities must be [n, number_classes], got {tuple(probs.shape)}")
     K = _search_classes("large_sampling_optimization", probs.shape[1])
     n = graph.number_of_nodes()
-    if n < K:
-        raise ValueError(f"number_classes = {K}: the graph needs at least {K} nodes (nodes 0..{K - 1} are the "
-                         f"terminals), got {n}")
+    _check_graph_size(n, K, terminals)
     if probs.shape[0] != n:
         raise ValueError(f"node_probabilities has {probs.shape[0]} rows, the graph {n} nodes")
     dev = hip.require_gpu()
@@ -573,18 +586,19 @@ def large_sampling_optimization(node_probabilities, graph, iterations: int = 200
     handle = graph if isinstance(graph, GraphHandle) else from_networkx(graph)
     batch = GraphBatch([handle], None, dev)
     best_assign, best_cut, _, _ = _large_sample_on_gpu(batch, probs, iterations, int(seed) & _M64, [graph_index],
-                                                       keep_samples=False)
+                                                       keep_samples=False, terminals=terminals)
     return best_assign.cpu().tolist(), _as_number(best_cut.item())
 
 
 def large_annealing(partition_assignment, graph, number_classes: int, sweeps: int = 100, t_start: float = 1.5,
-                    t_end: float = 0.15, seed: int = 0, max_descent_sweeps: int = 100) -> Tuple[List[int], Any]:
+                    t_end: float = 0.15, seed: int = 0, max_descent_sweeps: int = 100,
+                    terminals: bool = True) -> Tuple[List[int], Any]:
     """:func:`kway_annealing` for a graph of any size from number_classes to ``hip.LARGE_MAX_GRAPH_NODES`` nodes
     (extension, include/gcnmaxcut.h ``gmc_large_anneal_f32``): the same rule, arguments and results - on a graph
     :func:`kway_annealing` takes with unit or integer weights, the same assignment - with the graph shared by several
     workgroups and one launch per colour class.  Every launch of ``sweeps`` annealing and ``max_descent_sweeps`` descent
     sweeps is issued whenever the descent converges, so give the descent the sweeps it may need, not a huge bound."""
-    K, part = _kway_partition("large_annealing", partition_assignment, graph, number_classes)
+    K, part = _kway_partition("large_annealing", partition_assignment, graph, number_classes, terminals)
     if sweeps < 0 or max_descent_sweeps < 0:
         raise ValueError(f"sweeps and max_descent_sweeps must be >= 0, got {sweeps} and {max_descent_sweeps}")
     dev = hip.require_gpu()
@@ -592,7 +606,8 @@ def large_annealing(partition_assignment, graph, number_classes: int, sweeps: in
     batch = GraphBatch([handle], None, dev)
     assign = torch.from_numpy(part.astype(np.int8)).to(dev).reshape(1, -1)
     inv_temp = anneal_schedule(sweeps, t_start, t_end, _mean_edge_weight(batch))
-    best_assign, best_cut, _ = _large_anneal_on_gpu(batch, K, assign, inv_temp, seed, max_descent_sweeps)
+    best_assign, best_cut, _ = _large_anneal_on_gpu(batch, K, assign, inv_temp, seed, max_descent_sweeps,
+                                                    terminals=terminals)
     return best_assign.cpu().tolist(), _as_number(best_cut.item())
 
 
@@ -605,10 +620,12 @@ def _search_classes(what: str, classes: int) -> int:
     return K
 
 
-def assign_partitions_seeded_kway(node_probs: np.ndarray, seed: int, graph_index: int = 0, iteration: int = 0) -> List[int]:
+def assign_partitions_seeded_kway(node_probs: np.ndarray, seed: int, graph_index: int = 0, iteration: int = 0,
+                                  terminals: bool = True) -> List[int]:
     """:func:`assign_partitions_seeded` for probabilities of K = 2..8 columns (host form of kway_search.hip's sampler):
     nodes 0..K-1 are the terminals, node l >= K takes the first class j in 0..K-2 whose running double sum exceeds the
-    hashed uniform, else class K-1 (no compare against the last sum).  At K = 3 it is :func:`assign_partitions_seeded`."""
+    hashed uniform, else class K-1 (no compare against the last sum).  At K = 3 it is :func:`assign_partitions_seeded`.
+    ``terminals=False``: every node, 0..K-1 included, is drawn by that rule with its own local id in the counter."""
     probs_all = np.asarray(node_probs)
     if probs_all.ndim != 2:
         raise ValueError(f"node_probs must be [n, number_classes], got {tuple(probs_all.shape)}")
@@ -616,8 +633,9 @@ def assign_partitions_seeded_kway(node_probs: np.ndarray, seed: int, graph_index
     if int(iteration) < 0 or int(iteration) >= 1 << 31:
         raise ValueError(f"iteration must be in 0..2^31-1, got {iteration}")
     key = _graph_key(int(seed) & _M64, graph_index)
-    out = list(range(min(K, len(probs_all))))
-    for l, probs in enumerate(probs_all[K:], K):
+    first = K if terminals else 0
+    out = list(range(min(first, len(probs_all))))
+    for l, probs in enumerate(probs_all[first:], first):
         h = _mix64((key + _GOLD * (((int(iteration) << 32) | l) + 1)) & _M64)
         r = float(h >> 11) * 2.0 ** -53          # < 2^53: exact
         running = float(probs[0])
@@ -632,16 +650,32 @@ def assign_partitions_seeded_kway(node_probs: np.ndarray, seed: int, graph_index
     return out
 
 
-def _needs_terminals(batch: GraphBatch, K: int) -> None:
+def _check_graph_size(n: int, K: int, terminals: bool = True) -> None:
+    """One graph's room for its terminals: K nodes with them, one node without."""
+    if terminals and n < K:
+        raise ValueError(f"number_classes = {K}: the graph needs at least {K} nodes (nodes 0..{K - 1} are the "
+                         f"terminals), got {n}")
+    if n < 1:
+        raise ValueError("the graph has no nodes")
+
+
+def _needs_terminals(batch: GraphBatch, K: int, terminals: bool = True) -> None:
+    """The batch form of :func:`_check_graph_size`: every graph has room for its terminals (K nodes), or, without
+    terminals, at least one node."""
+    if batch.B and not terminals:
+        if int(batch.sizes.min()) < 1:
+            raise ValueError("every graph needs at least one node, got an empty one")
+        return
     if batch.B and int(batch.sizes.min()) < K:
         raise ValueError(f"number_classes = {K}: every graph needs at least {K} nodes (nodes 0..{K - 1} are the "
                          f"terminals), got one with {int(batch.sizes.min())}")
 
 
-def _kway_sample_on_gpu(batch: GraphBatch, P: torch.Tensor, iterations: int, seed: int, indices, keep_samples: bool):
+def _kway_sample_on_gpu(batch: GraphBatch, P: torch.Tensor, iterations: int, seed: int, indices, keep_samples: bool,
+                        terminals: bool = True):
     """The seeded sampler at K = P.shape[1] classes (gmc_kway_decode_sample_seeded_f32), as ``_sample_seeded_on_gpu``."""
     K = _search_classes("the K-class sampler", P.shape[1])
-    _needs_terminals(batch, K)
+    _needs_terminals(batch, K, terminals)
     keys = sample_keys(seed, range(batch.B) if indices is None else indices)
     if keys.size != batch.B:
         raise ValueError(f"{keys.size} graph indices for a batch of {batch.B} graphs")
@@ -653,15 +687,13 @@ def _kway_sample_on_gpu(batch: GraphBatch, P: torch.Tensor, iterations: int, see
     best_cut = torch.empty(batch.B, dtype=torch.float32, device=dev)
     best_iter = torch.empty(batch.B, dtype=torch.int32, device=dev)
     p = hip.ptr
-    rc = hip.load().gmc_kway_decode_sample_seeded_f32(batch.ref(), p(P.contiguous()), K, p(gkey), iterations,
-                                                      p(assign_all), p(cut_all), p(best_assign), p(best_cut),
-                                                      p(best_iter), hip.stream())
-    hip.check(rc, "gmc_kway_decode_sample_seeded_f32")
+    _call("gmc_kway_decode_sample_seeded_f32", terminals, (batch.ref(), p(P.contiguous()), K),
+          (p(gkey), iterations, p(assign_all), p(cut_all), p(best_assign), p(best_cut), p(best_iter), hip.stream()))
     return best_assign, best_cut, cut_all, assign_all
 
 
 def sampling_optimization(node_probabilities, graph, iterations: int = 200, *, seed: int = 0,
-                          graph_index: int = 0) -> Tuple[List[int], Any]:
+                          graph_index: int = 0, terminals: bool = True) -> Tuple[List[int], Any]:
     """Best of ``iterations`` seeded samples of the node probabilities [n, K], K = number_classes in 2..8 (extension,
     include/gcnmaxcut.h ``gmc_kway_decode_sample_seeded_f32``): what ``post_processing_optimization(..., seed=seed)``
     does for a 3-class model - and, at K = 3, returns.  Nodes 0..K-1 are the terminals; ``graph_index`` is the graph's
@@ -671,9 +703,7 @@ def sampling_optimization(node_probabilities, graph, iterations: int = 200, *, s
         raise ValueError(f"node_probabilities must be [n, number_classes], got {tuple(probs.shape)}")
     K = _search_classes("sampling_optimization", probs.shape[1])
     n = graph.number_of_nodes()
-    if n < K:
-        raise ValueError(f"number_classes = {K}: the graph needs at least {K} nodes (nodes 0..{K - 1} are the "
-                         f"terminals), got {n}")
+    _check_graph_size(n, K, terminals)
     if probs.shape[0] != n:
         raise ValueError(f"node_probabilities has {probs.shape[0]} rows, the graph {n} nodes")
     dev = hip.require_gpu()
@@ -682,19 +712,19 @@ def sampling_optimization(node_probabilities, graph, iterations: int = 200, *, s
         return None, -float('inf')
     batch = GraphBatch([from_networkx(graph)], None, dev)
     best_assign, best_cut, _, _ = _kway_sample_on_gpu(batch, probs, iterations, int(seed) & _M64, [graph_index],
-                                                      keep_samples=False)
+                                                      keep_samples=False, terminals=terminals)
     return best_assign.cpu().tolist(), _as_number(best_cut.item())
 
 
 def _kway_anneal_on_gpu(batch: GraphBatch, K: int, assign: torch.Tensor, inv_temp: np.ndarray, seed: int,
-                        max_descent_sweeps: int):
+                        max_descent_sweeps: int, terminals: bool = True):
     """Annealing + descent at K classes (gmc_kway_refine_anneal_f32) over the candidates assign [cands, R] int8, in
     place; returns the best assignment [R], its cut and candidate index per graph.  No annealing sweeps: the K-class
     local search."""
-    _needs_terminals(batch, K)
+    _needs_terminals(batch, K, terminals)
     dev = batch.device
     cands = int(assign.shape[0])
-    order, cgoff, cptr = batch.refine_order(K)
+    order, cgoff, cptr = batch.refine_order(K, terminals)
     sweeps = int(len(inv_temp))
     inv_t = torch.from_numpy(np.ascontiguousarray(inv_temp, np.float32)).to(dev) if sweeps else None
     levels = torch.from_numpy(anneal_levels()).to(dev) if sweeps else None
@@ -703,58 +733,59 @@ def _kway_anneal_on_gpu(batch: GraphBatch, K: int, assign: torch.Tensor, inv_tem
     best_cut = torch.empty(batch.B, dtype=torch.float32, device=dev)
     best_idx = torch.empty(batch.B, dtype=torch.int32, device=dev)
     p = hip.ptr
-    rc = hip.load().gmc_kway_refine_anneal_f32(batch.ref(), K, p(order), p(cgoff), p(cptr), cands, p(assign), p(inv_t),
-                                               sweeps, p(levels), int(seed) & _M64, int(max_descent_sweeps), p(cut_all),
-                                               p(best_assign), p(best_cut), p(best_idx), None, None, hip.stream())
-    hip.check(rc, "gmc_kway_refine_anneal_f32")
+    _call("gmc_kway_refine_anneal_f32", terminals, (batch.ref(), K),
+          (p(order), p(cgoff), p(cptr), cands, p(assign), p(inv_t), sweeps, p(levels), int(seed) & _M64,
+           int(max_descent_sweeps), p(cut_all), p(best_assign), p(best_cut), p(best_idx), None, None, hip.stream()))
     return best_assign, best_cut, best_idx
 
 
-def _kway_partition(what: str, partition_assignment, graph, number_classes: int) -> Tuple[int, np.ndarray]:
+def _kway_partition(what: str, partition_assignment, graph, number_classes: int,
+                    terminals: bool = True) -> Tuple[int, np.ndarray]:
     """The checks the K-class searches share: the class count, the length, the class values, the terminals' room."""
     K = _search_classes(what, number_classes)
     part = np.asarray(list(partition_assignment), dtype=np.int64)
     n = graph.number_of_nodes()
     if part.shape != (n,):
         raise ValueError(f"partition_assignment has {part.size} entries, the graph {n} nodes")
-    if n < K:
-        raise ValueError(f"number_classes = {K}: the graph needs at least {K} nodes (nodes 0..{K - 1} are the "
-                         f"terminals), got {n}")
+    _check_graph_size(n, K, terminals)
     if int(part.min()) < 0 or int(part.max()) > K - 1:
         raise ValueError(f"partition_assignment holds a class outside 0..{K - 1} (number_classes = {K})")
     return K, part
 
 
-def kway_local_search(partition_assignment, graph, number_classes: int, max_sweeps: int = 100) -> Tuple[List[int], Any]:
+def kway_local_search(partition_assignment, graph, number_classes: int, max_sweeps: int = 100,
+                      terminals: bool = True) -> Tuple[List[int], Any]:
     """:func:`local_search_optimization` for a partition into ``number_classes`` = 2..8 classes (extension,
     include/gcnmaxcut.h ``gmc_kway_refine_anneal_f32`` without annealing sweeps): nodes 0..K-1 keep their classes,
     every other node moves to the class that cuts the most of its edge weight, sweep after sweep, until a sweep moves
-    nothing or ``max_sweeps`` have run.  Returns the refined assignment and its cut value."""
-    K, part = _kway_partition("kway_local_search", partition_assignment, graph, number_classes)
+    nothing or ``max_sweeps`` have run.  Returns the refined assignment and its cut value.  ``terminals=False``: every
+    node may move, so the result is a local optimum of plain max-K-cut under single moves."""
+    K, part = _kway_partition("kway_local_search", partition_assignment, graph, number_classes, terminals)
     if max_sweeps < 0:
         raise ValueError(f"max_sweeps must be >= 0, got {max_sweeps}")
     dev = hip.require_gpu()
     batch = GraphBatch([from_networkx(graph)], None, dev)
     assign = torch.from_numpy(part.astype(np.int8)).to(dev).reshape(1, -1)
-    best_assign, best_cut, _ = _kway_anneal_on_gpu(batch, K, assign, np.zeros(0, np.float32), 0, max_sweeps)
+    best_assign, best_cut, _ = _kway_anneal_on_gpu(batch, K, assign, np.zeros(0, np.float32), 0, max_sweeps, terminals)
     return best_assign.cpu().tolist(), _as_number(best_cut.item())
 
 
 def kway_annealing(partition_assignment, graph, number_classes: int, sweeps: int = 100, t_start: float = 1.5,
-                   t_end: float = 0.15, seed: int = 0, max_descent_sweeps: int = 100) -> Tuple[List[int], Any]:
+                   t_end: float = 0.15, seed: int = 0, max_descent_sweeps: int = 100,
+                   terminals: bool = True) -> Tuple[List[int], Any]:
     """:func:`annealing_optimization` for a partition into ``number_classes`` = 2..8 classes (extension,
     include/gcnmaxcut.h ``gmc_kway_refine_anneal_f32``): ``sweeps`` Metropolis sweeps cooling from ``t_start`` to
     ``t_end`` (in units of the graph's mean edge weight), each node proposing the best of the K-1 other classes, the
     best state passed through kept, then the K-class local search from it.  Nodes 0..K-1 keep their classes; the result
     is never worse than the input and is reproducible from ``seed``.  Returns the assignment and its cut value."""
-    K, part = _kway_partition("kway_annealing", partition_assignment, graph, number_classes)
+    K, part = _kway_partition("kway_annealing", partition_assignment, graph, number_classes, terminals)
     if sweeps < 0 or max_descent_sweeps < 0:
         raise ValueError(f"sweeps and max_descent_sweeps must be >= 0, got {sweeps} and {max_descent_sweeps}")
     dev = hip.require_gpu()
     batch = GraphBatch([from_networkx(graph)], None, dev)
     assign = torch.from_numpy(part.astype(np.int8)).to(dev).reshape(1, -1)
     inv_temp = anneal_schedule(sweeps, t_start, t_end, _mean_edge_weight(batch))
-    best_assign, best_cut, _ = _kway_anneal_on_gpu(batch, K, assign, inv_temp, seed, max_descent_sweeps)
+    best_assign, best_cut, _ = _kway_anneal_on_gpu(batch, K, assign, inv_temp, seed, max_descent_sweeps, terminals)
     return best_assign.cpu().tolist(), _as_number(best_cut.item())
 
 
@@ -825,9 +856,7 @@ def kway_evolution(partitions, graph, number_classes: int, generations: int = EV
     n = graph.number_of_nodes()
     if parts.ndim != 2 or parts.shape[0] < 1 or parts.shape[1] != n:
         raise ValueError(f"partitions must be [cands, {n}] with cands >= 1, got {tuple(parts.shape)}")
-    if n < K:
-        raise ValueError(f"number_classes = {K}: the graph needs at least {K} nodes (nodes 0..{K - 1} are the "
-                         f"terminals), got {n}")
+    _check_graph_size(n, K)
     if int(parts.min()) < 0 or int(parts.max()) > K - 1:
         raise ValueError(f"partitions holds a class outside 0..{K - 1} (number_classes = {K})")
     elite = _evolve_arguments("kway_evolution", parts.shape[0], generations, generation_sweeps, elite,
@@ -1018,14 +1047,36 @@ def decode_dataset(model, processed_graphs: Dict, post_processing_iterations: in
     return out
 
 
-def round_dataset(model, processed_graphs: Dict, descent_sweeps: int = 0) -> List[Dict[str, Any]]:
+def _plain_forward(terminals: bool) -> dict:
+    """What a dataset decode adds to ``eng.forward``: without terminals the per-graph minimum of number_classes nodes is
+    waived (``FusedEngine.forward(..., terminals=False)``: P is the plain softmax either way)."""
+    return {} if terminals else {"terminals": False}
+
+
+def _plain_argmax(batch: GraphBatch, P: torch.Tensor, K: int, large: bool = False):
+    """The argmax decode without terminals: the first maximum of every row of P (no row overridden) as int32 [R], and
+    its cut per graph, scored by a search launch that runs no sweep."""
+    S = _first_argmax(P)
+    if batch.B == 0:
+        return S, torch.empty(0, dtype=torch.float32, device=P.device)
+    search = _large_anneal_on_gpu if large else _kway_anneal_on_gpu
+    _, cut, _ = search(batch, K, S.to(torch.int8).reshape(1, -1).contiguous(), np.zeros(0, np.float32), 0, 0,
+                       terminals=False)
+    return S, cut
+
+
+def round_dataset(model, processed_graphs: Dict, descent_sweeps: int = 0, terminals: bool = True) -> List[Dict[str, Any]]:
     """Argmax decode and conditional rounding of a whole dataset (extension): ONE batched forward and ONE rounding
     launch (``gmc_round_conditional_f32``), for a model of any ``number_classes`` in 2..8 - the decoder, and with
     ``descent_sweeps > 0`` the local search, of the models the 3-class sampler and searches refuse.  Per graph:
     ``nodes``, ``simple_cut`` / ``simple_assignment`` (the argmax decode, as ``decode_dataset`` reports it),
     ``expected_cut`` (of rounding every node independently from its row, terminals fixed), ``rounded_cut`` /
     ``rounded_assignment`` (never below ``expected_cut`` but for fp32 rounding) and ``descent_sweeps`` (the sweeps
-    run, the last of them the one that moved nothing when the descent converged)."""
+    run, the last of them the one that moved nothing when the descent converged).
+    ``terminals=False``: plain max-K-cut - ``simple_assignment`` is the row argmax of P (first maximum, no row
+    overridden), the expected cut fixes no node, and the rounding and the descent visit every node.  A graph may then
+    have fewer than number_classes nodes, as long as the dataset's largest graph has that many (the shared model's
+    forward, ``gmc_kway_forward``, refuses a batch below that: ``ValueError``)."""
     if descent_sweeps < 0:
         raise ValueError(f"descent_sweeps must be >= 0, got {descent_sweeps}")
     items = list(processed_graphs.values())
@@ -1036,8 +1087,11 @@ def round_dataset(model, processed_graphs: Dict, descent_sweeps: int = 0) -> Lis
     _decoder_graph_size("round_dataset", max((h.n for h in handles), default=0))
     vals = [h.edge_values(it[1]) for h, it in zip(handles, items)]
     batch = GraphBatch(handles, vals, eng.device)
-    P, S, loss = eng.forward(batch, 1.0, want_loss=True)
-    assign, cut, expected, sweeps = [t.cpu().numpy() for t in _round_on_gpu(batch, P, descent_sweeps)]
+    P, S, loss = eng.forward(batch, 1.0, want_loss=True, **_plain_forward(terminals))
+    assign, cut, expected, sweeps = [t.cpu().numpy() for t in _round_on_gpu(batch, P, descent_sweeps, terminals)]
+    if not terminals:
+        S, plain = _plain_argmax(batch, P, eng.K)
+        loss = -plain
     S_host, simple = S.cpu().numpy(), (-loss).cpu().tolist()
     out = []
     for g in range(len(items)):
@@ -1048,12 +1102,13 @@ def round_dataset(model, processed_graphs: Dict, descent_sweeps: int = 0) -> Lis
     return out
 
 
-def round_large_dataset(model, processed_graphs: Dict, descent_sweeps: int = 0) -> List[Dict[str, Any]]:
+def round_large_dataset(model, processed_graphs: Dict, descent_sweeps: int = 0,
+                        terminals: bool = True) -> List[Dict[str, Any]]:
     """:func:`round_dataset` for datasets with graphs of any size up to ``hip.LARGE_MAX_GRAPH_NODES`` nodes (extension):
     ONE batched forward (the engine takes a batch with a graph beyond ``hip.MAX_GRAPH_NODES`` nodes through
     ``gmc_large_forward``; an ``adjacency="none"`` dataset has no padded adjacency and its edge weights come from the
     graph) and ONE call of ``gmc_large_round_conditional_f32``.  The keys and, on a dataset :func:`round_dataset`
-    takes, the assignments and sweep counts are :func:`round_dataset`'s."""
+    takes, the assignments and sweep counts are :func:`round_dataset`'s, with and without ``terminals``."""
     if descent_sweeps < 0:
         raise ValueError(f"descent_sweeps must be >= 0, got {descent_sweeps}")
     items = list(processed_graphs.values())
@@ -1063,8 +1118,11 @@ def round_large_dataset(model, processed_graphs: Dict, descent_sweeps: int = 0) 
     handles = [it[0] for it in items]
     vals = [h.edge_values(it[1]) for h, it in zip(handles, items)]
     batch = GraphBatch(handles, vals, eng.device)
-    P, S, loss = eng.forward(batch, 1.0, want_loss=True)
-    assign, cut, expected, sweeps = [t.cpu().numpy() for t in _large_round_on_gpu(batch, P, descent_sweeps)]
+    P, S, loss = eng.forward(batch, 1.0, want_loss=True, **_plain_forward(terminals))
+    assign, cut, expected, sweeps = [t.cpu().numpy() for t in _large_round_on_gpu(batch, P, descent_sweeps, terminals)]
+    if not terminals:
+        S, plain = _plain_argmax(batch, P, eng.K, large=True)
+        loss = -plain
     S_host, simple = S.cpu().numpy(), (-loss).cpu().tolist()
     out = []
     for g in range(len(items)):
@@ -1079,7 +1137,7 @@ def search_dataset(model, processed_graphs: Dict, samples: int = 200, *, sample_
                    anneal_seed: int = 0, max_descent_sweeps: int = 100,
                    candidates: Optional[int] = None, generations: int = 0,
                    generation_sweeps: int = EVOLVE_GENERATION_SWEEPS,
-                   elite: Optional[int] = None) -> List[Dict[str, Any]]:
+                   elite: Optional[int] = None, terminals: bool = True) -> List[Dict[str, Any]]:
     """Decode a whole dataset of a model of any ``number_classes`` in 2..8 with everything the 3-class path has
     (extension): ONE batched forward, ONE rounding launch (``round_dataset(..., 0)``), ONE launch of the seeded sampler
     (``gmc_kway_decode_sample_seeded_f32``, a graph's index its position in ``processed_graphs.values()``) and ONE
@@ -1095,7 +1153,13 @@ def search_dataset(model, processed_graphs: Dict, samples: int = 200, *, sample_
     annealing sweeps cooling from ``EVOLVE_T_START``, ``elite`` as there, seeded by ``anneal_seed`` - and each result
     gains ``evolved_cut`` (never below ``searched_cut``), ``evolved_assignment`` and ``evolved_history`` (the best cut
     after every generation, ``generations + 1`` entries).  No other key changes; ``generations = 0`` launches nothing
-    more and adds no key."""
+    more and adds no key.
+    ``terminals=False``: plain max-K-cut - candidate 0 is the row argmax of P (first maximum, no row overridden), and
+    the rounding, the sampler and the search fix no node.  The evolution stage keeps its terminals:
+    ``generations > 0`` then raises ``NotImplementedError``."""
+    if not terminals and generations > 0:
+        raise NotImplementedError("search_dataset(generations > 0, terminals=False): the evolution stage "
+                                  "(gmc_kway_evolve_f32) keeps its terminals")
     if samples < 0:
         raise ValueError(f"samples must be >= 0, got {samples}")
     if anneal_sweeps < 0 or max_descent_sweeps < 0:
@@ -1112,21 +1176,26 @@ def search_dataset(model, processed_graphs: Dict, samples: int = 200, *, sample_
     _decoder_graph_size("search_dataset", max((h.n for h in handles), default=0))
     vals = [h.edge_values(it[1]) for h, it in zip(handles, items)]
     batch = GraphBatch(handles, vals, eng.device)
-    _needs_terminals(batch, K)
-    P, S, loss = eng.forward(batch, 1.0, want_loss=True)
-    rnd_assign, rnd_cut, rnd_expected, _ = _round_on_gpu(batch, P, 0)
+    _needs_terminals(batch, K, terminals)
+    P, S, loss = eng.forward(batch, 1.0, want_loss=True, **_plain_forward(terminals))
+    if not terminals:
+        S, plain = _plain_argmax(batch, P, K)
+        loss = -plain
+    rnd_assign, rnd_cut, rnd_expected, _ = _round_on_gpu(batch, P, 0, terminals)
     rows = [S.to(torch.int8).reshape(1, -1), rnd_assign.reshape(1, -1)]
     sampled = None
     if samples > 0:
         best_assign, best_cut, _, assign_all = _kway_sample_on_gpu(batch, P, samples, int(sample_seed) & _M64,
-                                                                   range(len(items)), keep_samples=take > 2)
+                                                                   range(len(items)), keep_samples=take > 2,
+                                                                   terminals=terminals)
         sampled = (best_assign.cpu().numpy(), best_cut.cpu().tolist())
         if assign_all is not None:
             rows.append(assign_all)
     cands = torch.cat(rows)[:take].contiguous()
     inv_temp = anneal_schedule(anneal_sweeps, scale=_mean_edge_weight(batch))
     found_assign, found_cut, found_idx = [t.cpu().numpy() for t in
-                                          _kway_anneal_on_gpu(batch, K, cands, inv_temp, anneal_seed, max_descent_sweeps)]
+                                          _kway_anneal_on_gpu(batch, K, cands, inv_temp, anneal_seed, max_descent_sweeps,
+                                                              terminals)]
     evolved = None
     if generations > 0:   # the search left its candidates in `cands`: the population
         inv_temp = anneal_schedule(generation_sweeps, t_start=EVOLVE_T_START, scale=_mean_edge_weight(batch))
@@ -1153,7 +1222,7 @@ def search_dataset(model, processed_graphs: Dict, samples: int = 200, *, sample_
 
 def search_large_dataset(model, processed_graphs: Dict, samples: int = 200, *, sample_seed: int = 0,
                          anneal_sweeps: int = 100, anneal_seed: int = 0, max_descent_sweeps: int = 100,
-                         candidates: Optional[int] = None) -> List[Dict[str, Any]]:
+                         candidates: Optional[int] = None, terminals: bool = True) -> List[Dict[str, Any]]:
     """:func:`search_dataset` for datasets with graphs of any size up to ``hip.LARGE_MAX_GRAPH_NODES`` nodes
     (extension): ONE batched forward (the engine takes a batch with a graph beyond ``hip.MAX_GRAPH_NODES`` nodes
     through ``gmc_large_forward``; an ``adjacency="none"`` dataset has no padded adjacency and its edge weights come
@@ -1161,6 +1230,7 @@ def search_large_dataset(model, processed_graphs: Dict, samples: int = 200, *, s
     ``gmc_large_anneal_f32``.  Arguments, candidates (0 the argmax, 1 the rounded partition, 2.. the samples) and keys
     are :func:`search_dataset`'s; on a dataset that function takes, with unit or integer weights, so is every value.
     ``searched_cut`` is never below ``rounded_cut`` when the rounded partition is among the candidates.
+    ``terminals=False`` is :func:`search_dataset`'s: plain max-K-cut, for graphs of any size.
 
     Memory on the device, R the nodes of the dataset: the candidates and the samples, ``candidates + samples`` bytes
     per node, and the workspace of the search, about ``2.02 * cpad`` bytes per node, ``cpad`` the larger of
@@ -1183,16 +1253,19 @@ def search_large_dataset(model, processed_graphs: Dict, samples: int = 200, *, s
     handles = [it[0] for it in items]
     vals = [h.edge_values(it[1]) for h, it in zip(handles, items)]
     batch = GraphBatch(handles, vals, eng.device)
-    _needs_terminals(batch, K)
-    P, S, loss = eng.forward(batch, 1.0, want_loss=True)
-    rnd_assign, rnd_cut, rnd_expected, _ = _large_round_on_gpu(batch, P, 0)
+    _needs_terminals(batch, K, terminals)
+    P, S, loss = eng.forward(batch, 1.0, want_loss=True, **_plain_forward(terminals))
+    if not terminals:
+        S, plain = _plain_argmax(batch, P, K, large=True)
+        loss = -plain
+    rnd_assign, rnd_cut, rnd_expected, _ = _large_round_on_gpu(batch, P, 0, terminals)
     rows = [S.to(torch.int8).reshape(1, -1), rnd_assign.reshape(1, -1)]
     ws = _large_search_workspace(batch, K, max(take, samples)) if batch.B else None   # one scratch for both calls
     sampled = None
     if samples > 0:
         best_assign, best_cut, _, assign_all = _large_sample_on_gpu(batch, P, samples, int(sample_seed) & _M64,
                                                                     range(len(items)), keep_samples=take > 2,
-                                                                    workspace=ws)
+                                                                    workspace=ws, terminals=terminals)
         sampled = (best_assign.cpu().numpy(), best_cut.cpu().tolist())
         if assign_all is not None:
             rows.append(assign_all)
@@ -1200,7 +1273,7 @@ def search_large_dataset(model, processed_graphs: Dict, samples: int = 200, *, s
     inv_temp = anneal_schedule(anneal_sweeps, scale=_mean_edge_weight(batch))
     found_assign, found_cut, found_idx = [t.cpu().numpy() for t in
                                           _large_anneal_on_gpu(batch, K, cands, inv_temp, anneal_seed,
-                                                               max_descent_sweeps, workspace=ws)]
+                                                               max_descent_sweeps, workspace=ws, terminals=terminals)]
     S_host, simple = S.cpu().numpy(), (-loss).cpu().tolist()
     rnd_assign, rnd_cut, rnd_expected = rnd_assign.cpu().numpy(), rnd_cut.cpu().numpy(), rnd_expected.cpu().numpy()
     out = []

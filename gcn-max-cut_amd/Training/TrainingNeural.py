@@ -644,7 +644,7 @@ def _solve_chunk_early_stopping(part: List, eng, config: TrainingConfig, loss: s
 
 def solve_dataset(dataset: Dict, config: TrainingConfig, *, loss: Optional[str] = None,
                   max_rows_per_chunk: int = 1 << 18, early_stopping: bool = False, check_every: int = 64,
-                  compact_fraction: float = 0.25) -> List[Dict]:
+                  compact_fraction: float = 0.25, terminals: bool = True) -> List[Dict]:
     """Give every graph of ``dataset`` (the reference's items) ITS OWN model and train them all at once: the reference's
     architecture as the instance-wise solver it is - ``conv1.weight[i]`` is the embedding of node id i, which means
     something on the graph it was trained on only.  Graph g gets a ``GCNSoftmax(n_g, hidden_dim, number_classes)``,
@@ -683,8 +683,13 @@ def solve_dataset(dataset: Dict, config: TrainingConfig, *, loss: Optional[str] 
     the forward of exactly those parameters, the best comes from the epochs before the stop epoch, and a last key
     ``stopped_epoch`` (``None``: the graph ran to the end) is appended.
 
+    ``terminals=False`` solves plain max-K-cut: no node is fixed - the head overrides no row, ``partition`` is the row
+    argmax of the best epoch, both losses count every edge by its endpoints' own rows - and a graph needs one node,
+    not number_classes.  Early stopping, chunking and every key work as with terminals.
+
     Refused: ``dropout > 0`` and ``layer1 = "attention"`` (NotImplementedError), a graph beyond the one-workgroup head
-    (ValueError: ``train_model`` serves one large graph), a graph with fewer than number_classes nodes (ValueError)."""
+    (ValueError: ``train_model`` serves one large graph), a graph with fewer than number_classes nodes (ValueError;
+    with terminals)."""
     from ..Testing.TestingNeuralNetwork import calculate_cut_value
     loss = hip.loss_name(loss)
     if config.dropout > 0:
@@ -696,14 +701,17 @@ def solve_dataset(dataset: Dict, config: TrainingConfig, *, loss: Optional[str] 
     K, F = int(config.number_classes), int(config.hidden_dim)
     items = list(dataset.values())
     sizes = [it[0].n for it in items]
-    check_instance_sizes(sizes, K, loss)
+    check_instance_sizes(sizes, K, loss, terminals=bool(terminals))
     if early_stopping and (check_every < 0 or not 0.0 <= compact_fraction <= 1.0):
         raise ValueError(f"check_every must be >= 0 and compact_fraction within 0..1, got {check_every}, {compact_fraction}")
     results: List[Dict] = []
     for chunk in instance_chunks(sizes, max_rows_per_chunk):
         part = [items[i] for i in chunk]
         handles = [it[0] for it in part]
-        eng = InstanceEngine(handles, F, K, values=[h.edge_values(it[1]) for h, it in zip(handles, part)])
+        # (the keyword is passed only when it differs from the engine's default: an engine class put in this one's
+        # place, as the host tests do, need not know it)
+        plain = {} if terminals else {"terminals": False}
+        eng = InstanceEngine(handles, F, K, values=[h.edge_values(it[1]) for h, it in zip(handles, part)], **plain)
         eng.reset_parameters()
         if early_stopping:
             results.extend(_solve_chunk_early_stopping(part, eng, config, loss, int(check_every), float(compact_fraction)))

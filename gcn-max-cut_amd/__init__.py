@@ -12,6 +12,7 @@ from . import hip  # noqa: F401
 from .graph import BatchArrays, DGLError, GraphBatch, GraphHandle, from_edge_index, from_networkx  # noqa: F401
 from .engine import FusedEngine, shard_by_weight, shard_for_rank  # noqa: F401
 from . import functional  # noqa: F401
+from . import maxcut  # noqa: F401
 
 __version__ = "0.1.0"
 

@@ -49,7 +49,7 @@ __device__ __forceinline__ LdsCsr anneal_stage_csr(const AnnealArgs &a, const An
     }
     for (int i = threadIdx.x; i < q.movable; i += blockDim.x) {
         const int l = a.order[q.i0 + i] - q.r0;
-        ord[i] = (unsigned)l < (unsigned)q.n ? (unsigned short)l : (unsigned short)0xffff;
+        ord[i] = l >= a.first && l < q.n ? (unsigned short)l : (unsigned short)0xffff;
     }
     return LdsCsr{starts, ids, vals, ord, q.i0};
 }
@@ -72,7 +72,7 @@ __device__ __forceinline__ void anneal_body_k(const AnnealArgs &a, const G &g, u
                 const int hi = a.cptr[k0 + k + 1];
                 for (int i = a.cptr[k0 + k] + threadIdx.x; i < hi; i += blockDim.x) {
                     const int l = g.node(i);
-                    if (l < K || l >= n) continue;   // not a movable row of this graph: never touch LDS for it
+                    if (!g.movable(l, n)) continue;   // not a movable row of this graph: never touch LDS for it
                     const Sums<K> w = gmc::class_sums_k<K>(g.rp, g.col, g.vals, sa, l);
                     const u64 h = mix64(base + GMC_GOLD * (u64)(unsigned)l);
                     int kk;

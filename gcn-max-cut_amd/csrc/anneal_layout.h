@@ -34,6 +34,7 @@ struct AnnealArgs {
     gmc_batch b;
     const int *order, *cgoff, *cptr;   // gmc_refine_order_host's output
     int cands, anneal_sweeps, max_descent_sweeps;
+    int first;               // first movable local id: K with terminals, 0 without (in what was the struct's padding)
     const float *inv_temp;   // [anneal_sweeps]
     const float *levels;     // [GMC_ANNEAL_LEVELS]
     u64 seed;
@@ -52,7 +53,12 @@ struct GlobalCsr {
     const float *vals;
     const int *order;
     int r0;
+    int first;          // first movable local id: K with terminals, 0 without
     __device__ __forceinline__ int node(int i) const { return order[i] - r0; }
+    // is local id l, an entry of the order, a movable row of this graph of n nodes?
+    // (one unsigned compare, as the compiler made of `l < K || l >= n` while K was a literal: first <= n for every
+    // graph a kernel runs, and a negative l wraps beyond any n - first)
+    __device__ __forceinline__ bool movable(int l, int n) const { return (unsigned)(l - first) < (unsigned)(n - first); }
 };
 // the workgroup's copy in LDS (edge positions relative to the graph's first edge, order relative to its first entry)
 struct LdsCsr {
@@ -62,6 +68,8 @@ struct LdsCsr {
     const unsigned short *order;
     int i0;
     __device__ __forceinline__ int node(int i) const { return order[i - i0]; }
+    // (an entry that is no movable row was staged as 0xffff: the copy has applied `first` already)
+    __device__ __forceinline__ bool movable(int l, int n) const { return l < n; }
 };
 
 // LDS bytes of a launch for this batch and whether they include the staged copy

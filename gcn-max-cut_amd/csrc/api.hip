@@ -822,17 +822,18 @@ InstWorkspace inst_carve(const gmc_batch *b, const gmc_model *m, bool training, 
 }
 
 // steps 1 and 2 of the documented order (kway_check with the stacked W1: N is the batch's row count)
-int inst_check(const gmc_batch *b, const gmc_model *m) {
+int inst_check(const gmc_batch *b, const gmc_model *m, int terminals) {
     if (int rc = check_abi(b, m)) return rc;
     if (!b->goff || !b->rowptr || !b->gcol || !b->lcol || !b->dinv) return GMC_ERR_NULL;
     if (!m->W1 || !m->b1 || !m->W2 || !m->b2) return GMC_ERR_NULL;
     if (!kway_classes_ok(m->K)) return GMC_ERR_CLASSES;
-    if (b->B < 0 || b->R < 0 || b->nnz < 0 || m->N < 0 || m->F <= 0) return GMC_ERR_SHAPE;
+    if (b->B < 0 || b->R < 0 || b->nnz < 0 || m->N < 0 || m->F <= 0 || (terminals != 0 && terminals != 1))
+        return GMC_ERR_SHAPE;
     if (m->F % 4 || m->F > GMC_MAX_HIDDEN) return GMC_ERR_UNSUPPORTED;  // float4 rows
     if (!(m->dropout_p >= 0.f && m->dropout_p < 1.f)) return GMC_ERR_SHAPE;
     if (m->dropout_p > 0.f) return GMC_ERR_UNSUPPORTED;
     if (m->W1_slab && !gmc_aligned16(m->W1_slab)) return GMC_ERR_ALIGN;
-    if (b->B > 0 && (b->n_max < m->K || kway_too_large(b, m))) return GMC_ERR_GRAPH_SIZE;
+    if (b->B > 0 && (b->n_max < (terminals ? m->K : 1) || kway_too_large(b, m))) return GMC_ERR_GRAPH_SIZE;
     if (m->N != b->R) return GMC_ERR_SHAPE;  // W1 has one row per node of the batch
     return GMC_OK;
 }
@@ -840,11 +841,12 @@ int inst_check(const gmc_batch *b, const gmc_model *m) {
 struct InstCall {
     const gmc_batch *b; const gmc_model *m;
     InstWorkspace w{}; hipStream_t st = nullptr;
+    int terminals = 1;   // 0: the head overrides no row (the _t entry points)
 };
 
 int inst_open(InstCall &c, bool training, void *workspace, size_t workspace_bytes, gmc_stream_t stream, const float *P,
               const float *grad) {
-    if (int rc = inst_check(c.b, c.m)) return rc;                                    // 1. 2.
+    if (int rc = inst_check(c.b, c.m, c.terminals)) return rc;                                    // 1. 2.
     if (!workspace || !P || (training && !grad)) return GMC_ERR_NULL;                // 4. workspace and outputs
     if (!gmc_aligned16(grad) || !gmc_aligned16(P) || !gmc_aligned16(c.m->W2)) return GMC_ERR_ALIGN;   // 5.
     c.w = inst_carve(c.b, c.m, training, workspace);                                 // 6. size
@@ -875,7 +877,8 @@ int inst_forward_body(const InstCall &c, float C, float *P, int32_t *S, float *l
     if (rc) return rc;
     rc = gmc_inst_hw2_launch(b, w.H, w.ld, m->b1, m->W2, w.Z0, F, m->K, c.st);
     if (rc) return rc;
-    return gmc_kway_head_launch(b, w.Z0, m->b2, C, m->K, loss_of(m), P, S, loss, db2 ? w.GY2 : nullptr, db2, c.st, m->K);
+    return gmc_kway_head_launch(b, w.Z0, m->b2, C, m->K, loss_of(m), P, S, loss, db2 ? w.GY2 : nullptr, db2, c.st, m->K,
+                                c.terminals);
 }
 
 int inst_backward_body(const InstCall &c, const InstGrad &g) {
@@ -901,18 +904,26 @@ extern "C" size_t gmc_inst_workspace_bytes(const gmc_batch *batch, const gmc_mod
     return inst_carve(batch, model, training != 0, nullptr).bytes;
 }
 
-extern "C" int gmc_inst_forward(const gmc_batch *batch, const gmc_model *model, float C, void *workspace,
-                                size_t workspace_bytes, float *P, int32_t *S, float *loss, gmc_stream_t stream) {
+extern "C" int gmc_inst_forward_t(const gmc_batch *batch, const gmc_model *model, int32_t terminals, float C,
+                                  void *workspace, size_t workspace_bytes, float *P, int32_t *S, float *loss,
+                                  gmc_stream_t stream) {
     InstCall c{batch, model};
+    c.terminals = terminals;
     int rc = inst_open(c, false, workspace, workspace_bytes, stream, P, nullptr);
     if (rc || batch->R == 0) return rc;
     return inst_forward_body(c, C, P, S, loss, nullptr);
 }
 
-extern "C" int gmc_inst_train_fwd_bwd(const gmc_batch *batch, const gmc_model *model, float C, void *workspace,
-                                      size_t workspace_bytes, float *P, int32_t *S, float *loss, float *grad,
-                                      gmc_stream_t stream) {
+extern "C" int gmc_inst_forward(const gmc_batch *batch, const gmc_model *model, float C, void *workspace,
+                                size_t workspace_bytes, float *P, int32_t *S, float *loss, gmc_stream_t stream) {
+    return gmc_inst_forward_t(batch, model, 1, C, workspace, workspace_bytes, P, S, loss, stream);
+}
+
+extern "C" int gmc_inst_train_fwd_bwd_t(const gmc_batch *batch, const gmc_model *model, int32_t terminals, float C,
+                                        void *workspace, size_t workspace_bytes, float *P, int32_t *S, float *loss,
+                                        float *grad, gmc_stream_t stream) {
     InstCall c{batch, model};
+    c.terminals = terminals;
     int rc = inst_open(c, true, workspace, workspace_bytes, stream, P, grad);
     if (rc) return rc;
     const InstGrad g = inst_grad(batch, model, grad);
@@ -920,6 +931,12 @@ extern "C" int gmc_inst_train_fwd_bwd(const gmc_batch *batch, const gmc_model *m
         return g.count ? (int)hipMemsetAsync(grad, 0, g.count * sizeof(float), c.st) : GMC_OK;
     rc = inst_forward_body(c, C, P, S, loss, g.db2);
     return rc ? rc : inst_backward_body(c, g);
+}
+
+extern "C" int gmc_inst_train_fwd_bwd(const gmc_batch *batch, const gmc_model *model, float C, void *workspace,
+                                      size_t workspace_bytes, float *P, int32_t *S, float *loss, float *grad,
+                                      gmc_stream_t stream) {
+    return gmc_inst_train_fwd_bwd_t(batch, model, 1, C, workspace, workspace_bytes, P, S, loss, grad, stream);
 }
 
 // ---- graph-attention first layer: the row-kernel sequence with the kernels of attention.hip -------------------------------

@@ -64,6 +64,7 @@ struct HeadKArgs {
     float *GY2;        // [R,K]; nullptr: forward only
     float *db2part;    // [B,K]
     long b2_stride;    // floats from one graph's bias to the next: 0 = one shared conv2.bias, K = b2 [B,K] (instance.hip)
+    int terminals;     // 1: rows 0..K-1 of a graph are the terminals; 0: no row is overridden (gmc_inst_*_t)
 };
 
 // floats of dynamic LDS: sA [NP,K], sP [NP,K], SOFT: the terminals' own rows [K,K], sS [NP], the block sum's [waves, K+1]
@@ -75,6 +76,8 @@ __host__ __device__ inline size_t head_k_lds_floats(int n_max, int K, bool soft)
 //   SOFT  the relaxed loss (GMC_LOSS_EXPECTED_CUT): loss = -C/2 sum_u sum_{v in N(u)} w_uv (1 - Pt_u . Pt_v),
 //         GP_u = C sum_{v in N(u)} w_uv Pt_v, Pt = P with rows 0..K-1 replaced by e_0..e_{K-1}; S stays the argmax decode.
 // A graph with fewer than K nodes (the host refuses one) has min(K, n) terminals: no access leaves the graph's rows.
+// Without terminals (a.terminals == 0, a run-time value: the same instantiation) there are none: no row is overridden, S
+// is the first maximum of every row, and both losses are those of gmc_fn_cut_loss_f32 with terminals = 0.
 template <int K, bool SOFT>
 __global__ __launch_bounds__(head_k_threads(K)) void head_k_kernel(HeadKArgs a) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -88,7 +91,7 @@ __global__ __launch_bounds__(head_k_threads(K)) void head_k_kernel(HeadKArgs a) 
     int *sS = reinterpret_cast<int *>(sT + (SOFT ? K * K : 0));   // [NP] argmax class (after every row array: those
     float *red = reinterpret_cast<float *>(sS) + NP;         // [waves*(K+1)]        keep their 16- / 8-byte alignment)
     const bool train = a.GY2 != nullptr;
-    const int terms = n < K ? n : K;
+    const int terms = a.terminals ? (n < K ? n : K) : 0;
 
     float bias[K];
 #pragma unroll
@@ -370,13 +373,14 @@ static int head_k_launch(const HeadKArgs &a, size_t lds, hipStream_t st) {
 
 // GY2 == nullptr: forward only.  The graphs' tiles must fit a CU's LDS (GMC_ERR_GRAPH_SIZE otherwise).
 int gmc_kway_head_launch(const gmc_batch *b, const float *Z0, const float *b2, float C, int K, int loss_kind, float *P,
-                         int32_t *S, float *loss, float *GY2, float *db2part, hipStream_t st, long b2_stride) {
+                         int32_t *S, float *loss, float *GY2, float *db2part, hipStream_t st, long b2_stride,
+                         int terminals) {
     if (!b || !Z0 || !b2 || !P || (GY2 && !db2part)) return GMC_ERR_NULL;
     if (K < 2 || K > GMC_KWAY_MAX_CLASSES) return GMC_ERR_CLASSES;
     const size_t lds = gmc_kway_head_lds_bytes(b->n_max, K, loss_kind);
     if (lds > GMC_KWAY_LDS_BYTES) return GMC_ERR_GRAPH_SIZE;
     if (b->B == 0) return GMC_OK;
-    HeadKArgs a{*b, Z0, b2, C, P, S, loss, GY2, db2part, b2_stride};
+    HeadKArgs a{*b, Z0, b2, C, P, S, loss, GY2, db2part, b2_stride, terminals};
     const bool soft = loss_kind == GMC_LOSS_EXPECTED_CUT;
     GMC_KWAY_DISPATCH(K, return soft ? head_k_launch<KK, true>(a, lds, st) : head_k_launch<KK, false>(a, lds, st));
     return GMC_OK;

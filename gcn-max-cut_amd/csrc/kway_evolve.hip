@@ -166,7 +166,7 @@ __global__ __launch_bounds__(256) void evolve_generation_kernel(EvolveArgs e) {
     if (staged) {
         gmc::anneal_body_k<K>(a, gl, sa, sb, lv, n, q.k0, q.classes, red, &flag);
     } else {
-        const GlobalCsr g{a.b.rowptr + r0, a.b.lcol, a.b.vals, a.order, r0};
+        const GlobalCsr g{a.b.rowptr + r0, a.b.lcol, a.b.vals, a.order, r0, a.first};
         gmc::anneal_body_k<K>(a, g, sa, sb, lv, n, q.k0, q.classes, red, &flag);
     }
 
@@ -241,7 +241,7 @@ extern "C" int gmc_kway_evolve_f32(const gmc_batch *batch, int32_t K, const int3
     for (int g = 1; g <= generations; ++g) {
         const u64 gen_seed = mix64(seed + GMC_GOLD * (u64)g);
         const int from = (g - 1) & 1, to = g & 1;
-        const EvolveArgs e{{*batch, order, cgoff, cptr, cands, anneal_sweeps, max_descent_sweeps, inv_temp, levels,
+        const EvolveArgs e{{*batch, order, cgoff, cptr, cands, anneal_sweeps, max_descent_sweeps, K, inv_temp, levels,
                             gen_seed, nullptr, nullptr, nullptr, nullptr, L.staged, L.n_pad, L.off_starts, L.off_vals,
                             L.off_order, L.off_ids},
                            planes[from], planes[to], cuts[from], cuts[to],

@@ -47,6 +47,7 @@ struct SeededArgs {
     const float *P;          // [R,K]
     const u64 *gkey;         // [B]
     int iters;
+    int first;               // first drawn local id: K with terminals (ids below it keep their own class), 0 without
     signed char *assign_all; // [iters][R] or NULL
     float *cut_all;          // [B][iters]
     int *best_assign;        // [R]        (the pick kernel)
@@ -61,10 +62,11 @@ __global__ __launch_bounds__(256) void sample_seeded_k_kernel(SeededArgs a) {
     const int it = blockIdx.x, g = blockIdx.y;
     const int r0 = a.b.goff[g];
     const int n = a.b.goff[g + 1] - r0;
-    if (n > a.b.n_max || n < K) return;   // (the LDS is sized by n_max; a graph without its K terminals is skipped)
+    const int first = a.first;
+    if (n > a.b.n_max || n < first) return;   // (the LDS is sized by n_max; a graph without its terminals is skipped)
     const u64 base = iteration_base(a.gkey[g], it);
     for (int l = threadIdx.x; l < n; l += blockDim.x) {
-        const int c = l < K ? l : seeded_class_k<K>(base, l, a.P + (long)(r0 + l) * K);
+        const int c = l < first ? l : seeded_class_k<K>(base, l, a.P + (long)(r0 + l) * K);
         sa[l] = (unsigned char)c;
         if (a.assign_all) a.assign_all[(long)it * a.b.R + r0 + l] = (signed char)c;
     }
@@ -79,11 +81,12 @@ template <int K>
 __global__ __launch_bounds__(256) void sample_seeded_k_pick_kernel(SeededArgs a) {
     const int g = blockIdx.x;
     const int r0 = a.b.goff[g], n = a.b.goff[g + 1] - r0;
-    if (n > a.b.n_max || n < K) return;   // workgroup-uniform: the graphs the sampler skipped
+    const int first = a.first;
+    if (n > a.b.n_max || n < first) return;   // workgroup-uniform: the graphs the sampler skipped
     const int best = gmc::pick_best_index(a.cut_all, a.iters, g, a.best_cut, a.best_iter);
     const u64 base = iteration_base(a.gkey[g], best);
     for (int l = threadIdx.x; l < n; l += blockDim.x)
-        a.best_assign[r0 + l] = l < K ? l : seeded_class_k<K>(base, l, a.P + (long)(r0 + l) * K);
+        a.best_assign[r0 + l] = l < first ? l : seeded_class_k<K>(base, l, a.P + (long)(r0 + l) * K);
 }
 
 template <int K>
@@ -98,11 +101,12 @@ int sample_launch_k(const SeededArgs &a, hipStream_t st) {
     return GMC_OK;
 }
 
-// what a sampler entry point does once its arguments are checked (B > 0, K in 2..8)
-int sample_launch(const gmc_batch *batch, const float *P, int K, const uint64_t *gkey, int iters, int8_t *assign_all,
-                  float *cut_all, int32_t *best_assign, float *best_cut, int32_t *best_iter, gmc_stream_t stream) {
+// what a sampler entry point does once its arguments are checked (B > 0, K in 2..8; first = K or 0)
+int sample_launch(const gmc_batch *batch, const float *P, int K, int first, const uint64_t *gkey, int iters,
+                  int8_t *assign_all, float *cut_all, int32_t *best_assign, float *best_cut, int32_t *best_iter,
+                  gmc_stream_t stream) {
     hipStream_t st = static_cast<hipStream_t>(stream);
-    const SeededArgs a{*batch, P, reinterpret_cast<const u64 *>(gkey), iters,
+    const SeededArgs a{*batch, P, reinterpret_cast<const u64 *>(gkey), iters, first,
                        reinterpret_cast<signed char *>(assign_all), cut_all, best_assign, best_cut, best_iter};
     GMC_KWAY_DISPATCH(K, return sample_launch_k<KK>(a, st));
     return GMC_OK;
@@ -118,7 +122,7 @@ __global__ __launch_bounds__(256) void anneal_k_kernel(AnnealArgs a) {
     const int cand = blockIdx.x, gi = blockIdx.y;
     const int r0 = a.b.goff[gi];
     const int n = a.b.goff[gi + 1] - r0;
-    if (n > a.b.n_max || n < K) return;   // (the LDS is sized by n_max; a graph without its K terminals is skipped)
+    if (n > a.b.n_max || n < a.first) return;   // (the LDS is sized by n_max; a graph without its terminals is skipped)
     float *lv = reinterpret_cast<float *>(lds);
     unsigned char *sa = lds + 4 * GMC_ANNEAL_LEVELS;
     unsigned char *sb = sa + a.n_pad;
@@ -133,7 +137,7 @@ __global__ __launch_bounds__(256) void anneal_k_kernel(AnnealArgs a) {
         gmc::anneal_body_k<K>(a, g, sa, sb, lv, n, q.k0, q.classes, red, &flag);
     } else {
         __syncthreads();
-        const GlobalCsr g{a.b.rowptr + r0, a.b.lcol, a.b.vals, a.order, r0};
+        const GlobalCsr g{a.b.rowptr + r0, a.b.lcol, a.b.vals, a.order, r0, a.first};
         gmc::anneal_body_k<K>(a, g, sa, sb, lv, n, q.k0, q.classes, red, &flag);
     }
     for (int l = threadIdx.x; l < n; l += blockDim.x) as[l] = (signed char)sa[l];
@@ -143,12 +147,12 @@ __global__ __launch_bounds__(256) void anneal_k_kernel(AnnealArgs a) {
 
 struct KPickArgs {
     gmc::PickArgs p;
-    int K;
+    int first;
 };
 __global__ __launch_bounds__(256) void anneal_k_pick_kernel(KPickArgs a) {
     const int g = blockIdx.x;
     const int n = a.p.b.goff[g + 1] - a.p.b.goff[g];
-    if (n > a.p.b.n_max || n < a.K) return;   // workgroup-uniform: the graphs the search skipped
+    if (n > a.p.b.n_max || n < a.first) return;   // workgroup-uniform: the graphs the search skipped
     gmc::pick_best(a.p);
 }
 
@@ -160,21 +164,21 @@ int anneal_launch_k(const AnnealArgs &a, int lds_bytes, hipStream_t st) {
     return GMC_OK;
 }
 
-// what an annealing entry point does once its arguments are checked (B > 0, K in 2..8)
-int anneal_launch(const gmc_batch *batch, int K, const int32_t *order, const int32_t *cgoff, const int32_t *cptr,
+// what an annealing entry point does once its arguments are checked (B > 0, K in 2..8; first = K or 0)
+int anneal_launch(const gmc_batch *batch, int K, int first, const int32_t *order, const int32_t *cgoff, const int32_t *cptr,
                   int cands, int8_t *assign, const float *inv_temp, int anneal_sweeps, const float *levels,
                   uint64_t seed, int max_descent_sweeps, float *cut_all, int32_t *best_assign, float *best_cut,
                   int32_t *best_idx, int32_t *snap_sweep, int32_t *sweeps, gmc_stream_t stream) {
     hipStream_t st = static_cast<hipStream_t>(stream);
     const AnnealLayout L = gmc::anneal_layout(batch);
-    const AnnealArgs a{*batch, order, cgoff, cptr, cands, anneal_sweeps, max_descent_sweeps, inv_temp, levels, seed,
+    const AnnealArgs a{*batch, order, cgoff, cptr, cands, anneal_sweeps, max_descent_sweeps, first, inv_temp, levels, seed,
                        reinterpret_cast<signed char *>(assign), cut_all, snap_sweep, sweeps,
                        L.staged, L.n_pad, L.off_starts, L.off_vals, L.off_order, L.off_ids};
     int rc = GMC_OK;
     GMC_KWAY_DISPATCH(K, rc = anneal_launch_k<KK>(a, L.bytes, st));
     if (rc != GMC_OK) return rc;
     const KPickArgs p{{*batch, cands, reinterpret_cast<const signed char *>(assign), cut_all, best_assign, best_cut,
-                       best_idx}, K};
+                       best_idx}, first};
     hipLaunchKernelGGL(anneal_k_pick_kernel, dim3(batch->B), dim3(256), 0, st, p);
     GMC_LAUNCH_CHECK();
     return GMC_OK;
@@ -191,21 +195,38 @@ extern "C" int gmc_decode_sample_seeded_f32(const gmc_batch *batch, const float 
     if (iters < 1 || batch->B < 0) return GMC_ERR_SHAPE;
     if (batch->B > 0 && (batch->n_max < 3 || batch->n_max > 65535)) return GMC_ERR_GRAPH_SIZE;
     if (batch->B == 0) return GMC_OK;
-    return sample_launch(batch, P, 3, gkey, iters, assign_all, cut_all, best_assign, best_cut, best_iter, stream);
+    return sample_launch(batch, P, 3, 3, gkey, iters, assign_all, cut_all, best_assign, best_cut, best_iter, stream);
+}
+
+// what gmc_kway_decode_sample_seeded_f32 and its _t twin do (terminals: 0 or 1)
+static int kway_sample_seeded(const gmc_batch *batch, const float *P, int32_t K, int32_t terminals, const uint64_t *gkey,
+                              int32_t iters, int8_t *assign_all, float *cut_all, int32_t *best_assign, float *best_cut,
+                              int32_t *best_iter, gmc_stream_t stream) {
+    if (!batch || !P || !gkey || !cut_all || !best_assign || !best_cut || !best_iter) return GMC_ERR_NULL;
+    if (batch->abi != GMC_VERSION) return GMC_ERR_ABI;
+    if (!batch->goff || !batch->rowptr || !batch->lcol) return GMC_ERR_NULL;
+    if (K < 2 || K > GMC_KWAY_MAX_CLASSES) return GMC_ERR_CLASSES;
+    if (iters < 1 || batch->B < 0 || (terminals != 0 && terminals != 1)) return GMC_ERR_SHAPE;
+    const int first = terminals ? K : 0;
+    if (batch->B > 0 && (batch->n_max < (first > 1 ? first : 1) || batch->n_max > 65535))
+        return GMC_ERR_GRAPH_SIZE;
+    if (batch->B == 0) return GMC_OK;
+    return sample_launch(batch, P, K, first, gkey, iters, assign_all, cut_all, best_assign, best_cut, best_iter, stream);
 }
 
 extern "C" int gmc_kway_decode_sample_seeded_f32(const gmc_batch *batch, const float *P, int32_t K,
                                                  const uint64_t *gkey, int32_t iters, int8_t *assign_all,
                                                  float *cut_all, int32_t *best_assign, float *best_cut,
                                                  int32_t *best_iter, gmc_stream_t stream) {
-    if (!batch || !P || !gkey || !cut_all || !best_assign || !best_cut || !best_iter) return GMC_ERR_NULL;
-    if (batch->abi != GMC_VERSION) return GMC_ERR_ABI;
-    if (!batch->goff || !batch->rowptr || !batch->lcol) return GMC_ERR_NULL;
-    if (K < 2 || K > GMC_KWAY_MAX_CLASSES) return GMC_ERR_CLASSES;
-    if (iters < 1 || batch->B < 0) return GMC_ERR_SHAPE;
-    if (batch->B > 0 && (batch->n_max < K || batch->n_max > 65535)) return GMC_ERR_GRAPH_SIZE;
-    if (batch->B == 0) return GMC_OK;
-    return sample_launch(batch, P, K, gkey, iters, assign_all, cut_all, best_assign, best_cut, best_iter, stream);
+    return kway_sample_seeded(batch, P, K, 1, gkey, iters, assign_all, cut_all, best_assign, best_cut, best_iter, stream);
+}
+
+extern "C" int gmc_kway_decode_sample_seeded_t_f32(const gmc_batch *batch, const float *P, int32_t K, int32_t terminals,
+                                                   const uint64_t *gkey, int32_t iters, int8_t *assign_all,
+                                                   float *cut_all, int32_t *best_assign, float *best_cut,
+                                                   int32_t *best_iter, gmc_stream_t stream) {
+    return kway_sample_seeded(batch, P, K, terminals, gkey, iters, assign_all, cut_all, best_assign, best_cut, best_iter,
+                              stream);
 }
 
 extern "C" int gmc_refine_anneal_staged(const gmc_batch *batch) {
@@ -229,7 +250,30 @@ extern "C" int gmc_refine_anneal_f32(const gmc_batch *batch, const int32_t *orde
     if (anneal_sweeps > 0 && (!inv_temp || !levels)) return GMC_ERR_NULL;
     if (batch->B > 0 && (batch->n_max < 3 || batch->n_max > GMC_MAX_GRAPH_NODES)) return GMC_ERR_GRAPH_SIZE;
     if (batch->B == 0) return GMC_OK;
-    return anneal_launch(batch, 3, order, cgoff, cptr, cands, assign, inv_temp, anneal_sweeps, levels, seed,
+    return anneal_launch(batch, 3, 3, order, cgoff, cptr, cands, assign, inv_temp, anneal_sweeps, levels, seed,
+                         max_descent_sweeps, cut_all, best_assign, best_cut, best_idx, snap_sweep, sweeps, stream);
+}
+
+// what gmc_kway_refine_anneal_f32 and its _t twin do (terminals: 0 or 1)
+static int kway_refine_anneal(const gmc_batch *batch, int32_t K, int32_t terminals, const int32_t *order,
+                              const int32_t *cgoff, const int32_t *cptr, int32_t cands, int8_t *assign,
+                              const float *inv_temp, int32_t anneal_sweeps, const float *levels, uint64_t seed,
+                              int32_t max_descent_sweeps, float *cut_all, int32_t *best_assign, float *best_cut,
+                              int32_t *best_idx, int32_t *snap_sweep, int32_t *sweeps, gmc_stream_t stream) {
+    if (!batch || !order || !cgoff || !cptr || !assign || !cut_all || !best_assign || !best_cut || !best_idx)
+        return GMC_ERR_NULL;
+    if (batch->abi != GMC_VERSION) return GMC_ERR_ABI;
+    if (!batch->goff || !batch->rowptr || !batch->lcol) return GMC_ERR_NULL;
+    if (K < 2 || K > GMC_KWAY_MAX_CLASSES) return GMC_ERR_CLASSES;
+    if (cands < 1 || anneal_sweeps < 0 || anneal_sweeps >= (1 << 20) || max_descent_sweeps < 0 || batch->B < 0 ||
+        (terminals != 0 && terminals != 1))
+        return GMC_ERR_SHAPE;
+    if (anneal_sweeps > 0 && (!inv_temp || !levels)) return GMC_ERR_NULL;
+    const int first = terminals ? K : 0;
+    if (batch->B > 0 && (batch->n_max < (first > 1 ? first : 1) || batch->n_max > GMC_MAX_GRAPH_NODES))
+        return GMC_ERR_GRAPH_SIZE;
+    if (batch->B == 0) return GMC_OK;
+    return anneal_launch(batch, K, first, order, cgoff, cptr, cands, assign, inv_temp, anneal_sweeps, levels, seed,
                          max_descent_sweeps, cut_all, best_assign, best_cut, best_idx, snap_sweep, sweeps, stream);
 }
 
@@ -239,16 +283,17 @@ extern "C" int gmc_kway_refine_anneal_f32(const gmc_batch *batch, int32_t K, con
                                           uint64_t seed, int32_t max_descent_sweeps, float *cut_all,
                                           int32_t *best_assign, float *best_cut, int32_t *best_idx,
                                           int32_t *snap_sweep, int32_t *sweeps, gmc_stream_t stream) {
-    if (!batch || !order || !cgoff || !cptr || !assign || !cut_all || !best_assign || !best_cut || !best_idx)
-        return GMC_ERR_NULL;
-    if (batch->abi != GMC_VERSION) return GMC_ERR_ABI;
-    if (!batch->goff || !batch->rowptr || !batch->lcol) return GMC_ERR_NULL;
-    if (K < 2 || K > GMC_KWAY_MAX_CLASSES) return GMC_ERR_CLASSES;
-    if (cands < 1 || anneal_sweeps < 0 || anneal_sweeps >= (1 << 20) || max_descent_sweeps < 0 || batch->B < 0)
-        return GMC_ERR_SHAPE;
-    if (anneal_sweeps > 0 && (!inv_temp || !levels)) return GMC_ERR_NULL;
-    if (batch->B > 0 && (batch->n_max < K || batch->n_max > GMC_MAX_GRAPH_NODES)) return GMC_ERR_GRAPH_SIZE;
-    if (batch->B == 0) return GMC_OK;
-    return anneal_launch(batch, K, order, cgoff, cptr, cands, assign, inv_temp, anneal_sweeps, levels, seed,
-                         max_descent_sweeps, cut_all, best_assign, best_cut, best_idx, snap_sweep, sweeps, stream);
+    return kway_refine_anneal(batch, K, 1, order, cgoff, cptr, cands, assign, inv_temp, anneal_sweeps, levels, seed,
+                              max_descent_sweeps, cut_all, best_assign, best_cut, best_idx, snap_sweep, sweeps, stream);
+}
+
+extern "C" int gmc_kway_refine_anneal_t_f32(const gmc_batch *batch, int32_t K, int32_t terminals, const int32_t *order,
+                                            const int32_t *cgoff, const int32_t *cptr, int32_t cands, int8_t *assign,
+                                            const float *inv_temp, int32_t anneal_sweeps, const float *levels,
+                                            uint64_t seed, int32_t max_descent_sweeps, float *cut_all,
+                                            int32_t *best_assign, float *best_cut, int32_t *best_idx,
+                                            int32_t *snap_sweep, int32_t *sweeps, gmc_stream_t stream) {
+    return kway_refine_anneal(batch, K, terminals, order, cgoff, cptr, cands, assign, inv_temp, anneal_sweeps, levels,
+                              seed, max_descent_sweeps, cut_all, best_assign, best_cut, best_idx, snap_sweep, sweeps,
+                              stream);
 }

@@ -50,6 +50,7 @@ struct LargeRoundArgs {
     gmc_batch b;
     const float *P;          // [R][K]; nullptr: the local search (the state starts from assign)
     int K;
+    int first;               // first movable local id: K with terminals, 0 without
     const int *order, *cgoff, *cptr;
     unsigned char *cls;      // [R] workspace
     Flags f;
@@ -79,14 +80,14 @@ struct ByteState {
     }
 };
 
-// the graph of this workgroup and whether the call runs it (a graph with fewer than K or more than n_max nodes is skipped)
+// the graph of this workgroup and whether the call runs it (a graph with fewer than `first` or more than n_max nodes is skipped)
 struct Graph { int g, r0, n; bool runs; };
 __device__ __forceinline__ Graph my_graph(const LargeRoundArgs &a) {
     Graph t;
     t.g = blockIdx.x;
     t.r0 = a.b.goff[t.g];
     t.n = a.b.goff[t.g + 1] - t.r0;
-    t.runs = t.n >= a.K && t.n <= a.b.n_max;
+    t.runs = t.n >= a.first && t.n <= a.b.n_max;
     return t;
 }
 __device__ __forceinline__ long part_slot(const Graph &t) { return (long)(t.r0 / kTile) + t.g + blockIdx.y; }
@@ -100,7 +101,7 @@ __device__ __forceinline__ int colour_row(const LargeRoundArgs &a, const Graph &
     if (i >= a.cptr[k0 + a.colour + 1]) return -1;
     const int r = a.order[i];
     const int l = r - t.r0;
-    return l < a.K || l >= t.n ? -1 : r;   // not a movable row of this graph: never touch the state for it
+    return l < a.first || l >= t.n ? -1 : r;   // not a movable row of this graph: never touch the state for it
 }
 
 __global__ __launch_bounds__(kTile) void large_round_init_kernel(LargeRoundArgs a) {
@@ -114,7 +115,7 @@ __global__ __launch_bounds__(kTile) void large_round_init_kernel(LargeRoundArgs 
     const int l = (int)blockIdx.y * kTile + (int)threadIdx.x;
     if (!t.runs || l >= t.n) return;
     const int r = t.r0 + l;
-    a.cls[r] = a.P ? (l < a.K ? (unsigned char)l : kUnrounded) : (unsigned char)a.assign[r];
+    a.cls[r] = a.P ? (l < a.first ? (unsigned char)l : kUnrounded) : (unsigned char)a.assign[r];
 }
 
 template <int K>
@@ -134,7 +135,7 @@ __global__ __launch_bounds__(kTile) void large_round_fold_kernel(LargeRoundArgs 
     const int g = (int)blockIdx.x * kTile + (int)threadIdx.x;
     if (g >= a.b.B) return;
     const int r0 = a.b.goff[g], n = a.b.goff[g + 1] - r0;
-    if (n < a.K || n > a.b.n_max) return;
+    if (n < a.first || n > a.b.n_max) return;
     const int tiles = (n + kTile - 1) / kTile;
     const float *p = a.part + (long)(r0 / kTile) + g;
     float s = 0.f;
@@ -217,7 +218,7 @@ template <int K>
 int large_round_launch(LargeRoundArgs a, int max_classes, int max_sweeps, hipStream_t st) {
     const dim3 block(kTile);
     const dim3 rows(a.b.B, (a.b.n_max + kTile - 1) / kTile);
-    const int class_tiles = (a.b.n_max - K + kTile - 1) / kTile;   // a colour class has at most n_max - K nodes
+    const int class_tiles = (a.b.n_max - a.first + kTile - 1) / kTile;   // a colour class has at most n_max - first nodes
     const dim3 nodes(a.b.B, class_tiles > 0 ? class_tiles : 1);
     const dim3 graphs((a.b.B + kTile - 1) / kTile);
     GmcProbeScope probe(GMC_K_REFINE, st);
@@ -251,7 +252,8 @@ int large_round_launch(LargeRoundArgs a, int max_classes, int max_sweeps, hipStr
 }
 
 // the checks the two entry points share (P aside), in the family's order, and the launch
-int large_round_run(const gmc_batch *batch, const float *P, bool rounding, int32_t K, const int32_t *order,
+int large_round_run(const gmc_batch *batch, const float *P, bool rounding, int32_t K, int32_t terminals,
+                    const int32_t *order,
                     const int32_t *cgoff, const int32_t *cptr, int32_t max_classes, int32_t max_sweeps, void *workspace,
                     size_t workspace_bytes_given, int8_t *assign, float *cut, float *expected, int32_t *sweeps,
                     gmc_stream_t stream) {
@@ -259,8 +261,10 @@ int large_round_run(const gmc_batch *batch, const float *P, bool rounding, int32
     if (batch->abi != GMC_VERSION) return GMC_ERR_ABI;
     if (!batch->goff || !batch->rowptr || !batch->lcol || !batch->gcol) return GMC_ERR_NULL;
     if (K < 2 || K > GMC_KWAY_MAX_CLASSES) return GMC_ERR_CLASSES;
-    if (max_sweeps < 0 || max_classes < 0 || batch->B < 0) return GMC_ERR_SHAPE;
-    if (batch->B > 0 && (batch->n_max < K || batch->n_max > GMC_LARGE_MAX_GRAPH_NODES)) return GMC_ERR_GRAPH_SIZE;
+    if (max_sweeps < 0 || max_classes < 0 || batch->B < 0 || (terminals != 0 && terminals != 1)) return GMC_ERR_SHAPE;
+    const int first = terminals ? K : 0;
+    if (batch->B > 0 && (batch->n_max < (first > 1 ? first : 1) || batch->n_max > GMC_LARGE_MAX_GRAPH_NODES))
+        return GMC_ERR_GRAPH_SIZE;
     if (batch->R < 0 || workspace_bytes_given < workspace_bytes(batch)) return GMC_ERR_WORKSPACE;
     if (batch->B == 0) return GMC_OK;
     int *words = static_cast<int *>(workspace);
@@ -268,7 +272,7 @@ int large_round_run(const gmc_batch *batch, const float *P, bool rounding, int32
     const Flags f{words, words + B, words + 2 * B, words + 3 * B};
     float *part = reinterpret_cast<float *>(words + flag_words(batch));
     unsigned char *cls = reinterpret_cast<unsigned char *>(part + part_slots(batch));
-    const LargeRoundArgs a{*batch, P, K, order, cgoff, cptr, cls, f, part, reinterpret_cast<signed char *>(assign), cut,
+    const LargeRoundArgs a{*batch, P, K, first, order, cgoff, cptr, cls, f, part, reinterpret_cast<signed char *>(assign), cut,
                            expected, sweeps, 0};
     hipStream_t st = static_cast<hipStream_t>(stream);
     GMC_KWAY_DISPATCH(K, return large_round_launch<KK>(a, max_classes, max_sweeps, st));
@@ -287,7 +291,7 @@ extern "C" int gmc_large_round_conditional_f32(const gmc_batch *batch, const flo
                                                int32_t max_descent_sweeps, void *workspace, size_t workspace_bytes,
                                                int8_t *assign, float *cut, float *expected, int32_t *sweeps,
                                                gmc_stream_t stream) {
-    return large_round_run(batch, P, true, K, order, cgoff, cptr, max_classes, max_descent_sweeps, workspace,
+    return large_round_run(batch, P, true, K, 1, order, cgoff, cptr, max_classes, max_descent_sweeps, workspace,
                            workspace_bytes, assign, cut, expected, sweeps, stream);
 }
 
@@ -295,6 +299,24 @@ extern "C" int gmc_large_local_search_f32(const gmc_batch *batch, int32_t K, con
                                           const int32_t *cptr, int32_t max_classes, int32_t max_sweeps, void *workspace,
                                           size_t workspace_bytes, int8_t *assign, float *cut, int32_t *sweeps,
                                           gmc_stream_t stream) {
-    return large_round_run(batch, nullptr, false, K, order, cgoff, cptr, max_classes, max_sweeps, workspace,
+    return large_round_run(batch, nullptr, false, K, 1, order, cgoff, cptr, max_classes, max_sweeps, workspace,
+                           workspace_bytes, assign, cut, nullptr, sweeps, stream);
+}
+
+// the two entry points above with the terminals optional (terminals = 0: every node is movable)
+extern "C" int gmc_large_round_conditional_t_f32(const gmc_batch *batch, const float *P, int32_t K, int32_t terminals,
+                                                 const int32_t *order, const int32_t *cgoff, const int32_t *cptr,
+                                                 int32_t max_classes, int32_t max_descent_sweeps, void *workspace,
+                                                 size_t workspace_bytes, int8_t *assign, float *cut, float *expected,
+                                                 int32_t *sweeps, gmc_stream_t stream) {
+    return large_round_run(batch, P, true, K, terminals, order, cgoff, cptr, max_classes, max_descent_sweeps, workspace,
+                           workspace_bytes, assign, cut, expected, sweeps, stream);
+}
+
+extern "C" int gmc_large_local_search_t_f32(const gmc_batch *batch, int32_t K, int32_t terminals, const int32_t *order,
+                                            const int32_t *cgoff, const int32_t *cptr, int32_t max_classes,
+                                            int32_t max_sweeps, void *workspace, size_t workspace_bytes, int8_t *assign,
+                                            float *cut, int32_t *sweeps, gmc_stream_t stream) {
+    return large_round_run(batch, nullptr, false, K, terminals, order, cgoff, cptr, max_classes, max_sweeps, workspace,
                            workspace_bytes, assign, cut, nullptr, sweeps, stream);
 }

@@ -63,6 +63,7 @@ struct Flags {      // the int words of the workspace, [B * cands] each
 struct SearchArgs {
     gmc_batch b;
     int K;
+    int first;                       // first movable local id: K with terminals, 0 without
     const int *order, *cgoff, *cptr;
     int cands, lcp, chunks;          // cp = 1 << lcp
     unsigned char *sa;               // [chunks][R][cp] workspace: the state the node launches move
@@ -90,14 +91,14 @@ struct CandBytes {
     __device__ __forceinline__ int operator[](int u) const { return p[(long)u << lcp]; }
 };
 
-// the graph of this workgroup and whether the call runs it (a graph with fewer than K or more than n_max nodes is skipped)
+// the graph of this workgroup and whether the call runs it (a graph with fewer than `first` or more than n_max nodes is skipped)
 struct Graph { int g, r0, n; bool runs; };
 __device__ __forceinline__ Graph my_graph(const SearchArgs &a) {
     Graph t;
     t.g = blockIdx.x;
     t.r0 = a.b.goff[t.g];
     t.n = a.b.goff[t.g + 1] - t.r0;
-    t.runs = t.n >= a.K && t.n <= a.b.n_max;
+    t.runs = t.n >= a.first && t.n <= a.b.n_max;
     return t;
 }
 
@@ -151,7 +152,7 @@ __global__ __launch_bounds__(kTile) void large_sample_draw_kernel(SearchArgs a) 
             if (l >= t.n) break;
             const int r = t.r0 + l;
             int c = 0;
-            if (it < a.cands) c = l < K ? l : gmc::seeded_class_k<K>(base, l, a.P + (long)r * K);
+            if (it < a.cands) c = l < a.first ? l : gmc::seeded_class_k<K>(base, l, a.P + (long)r * K);
             a.sa[state_index(a, chunk, r, q.cl)] = (unsigned char)c;
         }
     }
@@ -214,7 +215,7 @@ __global__ __launch_bounds__(kTile) void large_search_fold_kernel(SearchArgs a, 
     const int g = (int)(i / a.cands);
     const int cand = (int)(i - (long)g * a.cands);
     const int r0 = a.b.goff[g], n = a.b.goff[g + 1] - r0;
-    if (n < a.K || n > a.b.n_max) return;
+    if (n < a.first || n > a.b.n_max) return;
     const int tiles = (n + kTile - 1) / kTile;
     const long cpad = (long)a.chunks << a.lcp;
     const float *p = a.part + ((long)(r0 / kTile) + g) * cpad + cand;
@@ -287,7 +288,7 @@ __global__ __launch_bounds__(kTile) void large_anneal_colour_kernel(SearchArgs a
             if (i >= cr.hi) break;
             const int r = a.order[i];
             const int l = r - t.r0;
-            if (l < K || l >= t.n) continue;   // not a movable row of this graph: never touch the state for it
+            if (l < a.first || l >= t.n) continue;   // not a movable row of this graph: never touch the state for it
             const Sums<K> w = gmc::class_sums_k<K>(a.b.rowptr, a.b.gcol, a.b.vals, cls, r);
             const u64 h = mix64(base + GMC_GOLD * (u64)(unsigned)l);
             int kk;
@@ -317,7 +318,7 @@ __global__ __launch_bounds__(kTile) void large_search_descent_colour_kernel(Sear
             if (i >= cr.hi) break;
             const int r = a.order[i];
             const int l = r - t.r0;
-            if (l < K || l >= t.n) continue;
+            if (l < a.first || l >= t.n) continue;
             const Sums<K> s = gmc::class_sums_k<K>(a.b.rowptr, a.b.gcol, a.b.vals, cls, r);
             const float wc = gmc::own_sum_or_inf<K>(s, cls[r]);
             float wk;
@@ -350,7 +351,7 @@ __global__ __launch_bounds__(kTile) void large_search_pick_kernel(SearchArgs a) 
     const int g = (int)blockIdx.x * kTile + (int)threadIdx.x;
     if (g >= a.b.B) return;
     const int n = a.b.goff[g + 1] - a.b.goff[g];
-    if (n < a.K || n > a.b.n_max) return;
+    if (n < a.first || n > a.b.n_max) return;
     const float *c = a.cut_all + (long)g * a.cands;
     int bi = 0;
     float bc = c[0];
@@ -374,7 +375,7 @@ __global__ __launch_bounds__(kTile) void large_sample_regenerate_kernel(SearchAr
     const int l = (int)blockIdx.y * kTile + (int)threadIdx.x;
     if (!t.runs || l >= t.n) return;
     const u64 base = gmc::iteration_base(a.gkey[t.g], a.best_idx[t.g]);
-    a.best_assign[t.r0 + l] = l < K ? l : gmc::seeded_class_k<K>(base, l, a.P + (long)(t.r0 + l) * K);
+    a.best_assign[t.r0 + l] = l < a.first ? l : gmc::seeded_class_k<K>(base, l, a.P + (long)(t.r0 + l) * K);
 }
 
 // ---- host ---------------------------------------------------------------------------------------------------------------
@@ -420,7 +421,7 @@ Grids grids(const SearchArgs &a, const Layout &L, int G) {
     Grids g;
     const int per = kPasses * (kTile >> a.lcp);   // rows (nodes of a class) of a workgroup with candidates along the lanes
     const int z = (int)(L.chunks < (size_t)kMaxZ ? L.chunks : (size_t)kMaxZ);
-    const int class_tiles = (a.b.n_max - a.K + per - 1) / per;   // a colour class has at most n_max - K nodes
+    const int class_tiles = (a.b.n_max - a.first + per - 1) / per;   // a colour class has at most n_max - first nodes
     g.block = dim3(kTile);
     g.lanes = dim3(a.b.B, (a.b.n_max + per - 1) / per, z);
     g.nodes = dim3(a.b.B, class_tiles > 0 ? class_tiles : 1, z);
@@ -518,16 +519,19 @@ extern "C" size_t gmc_large_search_workspace_bytes(const gmc_batch *batch, int32
     return sizes_ok(batch, K, cands) ? layout(batch, cands).bytes : 0;
 }
 
-extern "C" int gmc_large_sample_seeded_f32(const gmc_batch *batch, const float *P, int32_t K, const uint64_t *gkey,
-                                           int32_t iters, int8_t *assign_all, void *workspace, size_t workspace_bytes,
-                                           float *cut_all, int32_t *best_assign, float *best_cut, int32_t *best_iter,
-                                           gmc_stream_t stream) {
+// what gmc_large_sample_seeded_f32 and its _t twin do (terminals: 0 or 1)
+static int large_sample_seeded(const gmc_batch *batch, const float *P, int32_t K, int32_t terminals, const uint64_t *gkey,
+                               int32_t iters, int8_t *assign_all, void *workspace, size_t workspace_bytes,
+                               float *cut_all, int32_t *best_assign, float *best_cut, int32_t *best_iter,
+                               gmc_stream_t stream) {
     if (!batch || !P || !gkey || !workspace || !cut_all || !best_assign || !best_cut || !best_iter) return GMC_ERR_NULL;
     if (batch->abi != GMC_VERSION) return GMC_ERR_ABI;
     if (!batch->goff || !batch->rowptr || !batch->lcol || !batch->gcol) return GMC_ERR_NULL;
     if (K < 2 || K > GMC_KWAY_MAX_CLASSES) return GMC_ERR_CLASSES;
-    if (iters < 1 || batch->B < 0) return GMC_ERR_SHAPE;
-    if (batch->B > 0 && (batch->n_max < K || batch->n_max > GMC_LARGE_MAX_GRAPH_NODES)) return GMC_ERR_GRAPH_SIZE;
+    if (iters < 1 || batch->B < 0 || (terminals != 0 && terminals != 1)) return GMC_ERR_SHAPE;
+    const int first = terminals ? K : 0;
+    if (batch->B > 0 && (batch->n_max < (first > 1 ? first : 1) || batch->n_max > GMC_LARGE_MAX_GRAPH_NODES))
+        return GMC_ERR_GRAPH_SIZE;
     if (batch->R < 0) return GMC_ERR_WORKSPACE;
     const Layout L = layout(batch, iters);
     if (workspace_bytes < L.bytes) return GMC_ERR_WORKSPACE;
@@ -535,6 +539,7 @@ extern "C" int gmc_large_sample_seeded_f32(const gmc_batch *batch, const float *
     SearchArgs a{};
     a.b = *batch;
     a.K = K;
+    a.first = first;
     a.cands = iters;
     a.assign = reinterpret_cast<signed char *>(assign_all);
     a.cut_all = cut_all;
@@ -549,23 +554,41 @@ extern "C" int gmc_large_sample_seeded_f32(const gmc_batch *batch, const float *
     return GMC_OK;
 }
 
-extern "C" int gmc_large_anneal_f32(const gmc_batch *batch, int32_t K, const int32_t *order, const int32_t *cgoff,
-                                    const int32_t *cptr, int32_t max_classes, int32_t cands, int8_t *assign,
-                                    const float *inv_temp, int32_t anneal_sweeps, const float *levels, uint64_t seed,
-                                    int32_t max_descent_sweeps, void *workspace, size_t workspace_bytes, float *cut_all,
-                                    int32_t *best_assign, float *best_cut, int32_t *best_idx, int32_t *snap_sweep,
-                                    int32_t *sweeps, gmc_stream_t stream) {
+extern "C" int gmc_large_sample_seeded_f32(const gmc_batch *batch, const float *P, int32_t K, const uint64_t *gkey,
+                                           int32_t iters, int8_t *assign_all, void *workspace, size_t workspace_bytes,
+                                           float *cut_all, int32_t *best_assign, float *best_cut, int32_t *best_iter,
+                                           gmc_stream_t stream) {
+    return large_sample_seeded(batch, P, K, 1, gkey, iters, assign_all, workspace, workspace_bytes, cut_all, best_assign,
+                               best_cut, best_iter, stream);
+}
+
+extern "C" int gmc_large_sample_seeded_t_f32(const gmc_batch *batch, const float *P, int32_t K, int32_t terminals,
+                                             const uint64_t *gkey, int32_t iters, int8_t *assign_all, void *workspace,
+                                             size_t workspace_bytes, float *cut_all, int32_t *best_assign,
+                                             float *best_cut, int32_t *best_iter, gmc_stream_t stream) {
+    return large_sample_seeded(batch, P, K, terminals, gkey, iters, assign_all, workspace, workspace_bytes, cut_all,
+                               best_assign, best_cut, best_iter, stream);
+}
+
+// what gmc_large_anneal_f32 and its _t twin do (terminals: 0 or 1)
+static int large_anneal(const gmc_batch *batch, int32_t K, int32_t terminals, const int32_t *order, const int32_t *cgoff,
+                        const int32_t *cptr, int32_t max_classes, int32_t cands, int8_t *assign, const float *inv_temp,
+                        int32_t anneal_sweeps, const float *levels, uint64_t seed, int32_t max_descent_sweeps,
+                        void *workspace, size_t workspace_bytes, float *cut_all, int32_t *best_assign, float *best_cut,
+                        int32_t *best_idx, int32_t *snap_sweep, int32_t *sweeps, gmc_stream_t stream) {
     if (!batch || !order || !cgoff || !cptr || !workspace || !assign || !cut_all || !best_assign || !best_cut || !best_idx)
         return GMC_ERR_NULL;
     if (batch->abi != GMC_VERSION) return GMC_ERR_ABI;
     if (!batch->goff || !batch->rowptr || !batch->lcol || !batch->gcol) return GMC_ERR_NULL;
     if (K < 2 || K > GMC_KWAY_MAX_CLASSES) return GMC_ERR_CLASSES;
     if (cands < 1 || anneal_sweeps < 0 || anneal_sweeps >= (1 << 20) || max_descent_sweeps < 0 || max_classes < 0 ||
-        batch->B < 0)
+        batch->B < 0 || (terminals != 0 && terminals != 1))
         return GMC_ERR_SHAPE;
     if (cands >= kWideCands && batch->n_max > GMC_MAX_GRAPH_NODES) return GMC_ERR_SHAPE;
     if (anneal_sweeps > 0 && (!inv_temp || !levels)) return GMC_ERR_NULL;
-    if (batch->B > 0 && (batch->n_max < K || batch->n_max > GMC_LARGE_MAX_GRAPH_NODES)) return GMC_ERR_GRAPH_SIZE;
+    const int first = terminals ? K : 0;
+    if (batch->B > 0 && (batch->n_max < (first > 1 ? first : 1) || batch->n_max > GMC_LARGE_MAX_GRAPH_NODES))
+        return GMC_ERR_GRAPH_SIZE;
     if (batch->R < 0) return GMC_ERR_WORKSPACE;
     const Layout L = layout(batch, cands);
     if (workspace_bytes < L.bytes) return GMC_ERR_WORKSPACE;
@@ -573,6 +596,7 @@ extern "C" int gmc_large_anneal_f32(const gmc_batch *batch, int32_t K, const int
     SearchArgs a{};
     a.b = *batch;
     a.K = K;
+    a.first = first;
     a.order = order;
     a.cgoff = cgoff;
     a.cptr = cptr;
@@ -591,4 +615,26 @@ extern "C" int gmc_large_anneal_f32(const gmc_batch *batch, int32_t K, const int
     hipStream_t st = static_cast<hipStream_t>(stream);
     GMC_KWAY_DISPATCH(K, return anneal_launch<KK>(a, L, max_classes, anneal_sweeps, max_descent_sweeps, st));
     return GMC_OK;
+}
+
+extern "C" int gmc_large_anneal_f32(const gmc_batch *batch, int32_t K, const int32_t *order, const int32_t *cgoff,
+                                    const int32_t *cptr, int32_t max_classes, int32_t cands, int8_t *assign,
+                                    const float *inv_temp, int32_t anneal_sweeps, const float *levels, uint64_t seed,
+                                    int32_t max_descent_sweeps, void *workspace, size_t workspace_bytes, float *cut_all,
+                                    int32_t *best_assign, float *best_cut, int32_t *best_idx, int32_t *snap_sweep,
+                                    int32_t *sweeps, gmc_stream_t stream) {
+    return large_anneal(batch, K, 1, order, cgoff, cptr, max_classes, cands, assign, inv_temp, anneal_sweeps, levels, seed,
+                        max_descent_sweeps, workspace, workspace_bytes, cut_all, best_assign, best_cut, best_idx,
+                        snap_sweep, sweeps, stream);
+}
+
+extern "C" int gmc_large_anneal_t_f32(const gmc_batch *batch, int32_t K, int32_t terminals, const int32_t *order,
+                                      const int32_t *cgoff, const int32_t *cptr, int32_t max_classes, int32_t cands,
+                                      int8_t *assign, const float *inv_temp, int32_t anneal_sweeps, const float *levels,
+                                      uint64_t seed, int32_t max_descent_sweeps, void *workspace, size_t workspace_bytes,
+                                      float *cut_all, int32_t *best_assign, float *best_cut, int32_t *best_idx,
+                                      int32_t *snap_sweep, int32_t *sweeps, gmc_stream_t stream) {
+    return large_anneal(batch, K, terminals, order, cgoff, cptr, max_classes, cands, assign, inv_temp, anneal_sweeps,
+                        levels, seed, max_descent_sweeps, workspace, workspace_bytes, cut_all, best_assign, best_cut,
+                        best_idx, snap_sweep, sweeps, stream);
 }

@@ -110,7 +110,8 @@ __device__ __forceinline__ bool descent_visit(const G &g, unsigned char *cls, in
 // The descent of one 256-thread workgroup over the class bytes cls (LDS) of a graph of n nodes: sweeps over the colour
 // classes cptr[k0] .. cptr[k0 + classes] of the (colour, id) order behind g.node(), one thread per node of the current
 // class, a barrier between classes, a workgroup-wide OR closing every sweep; stops after a sweep that moved nothing or
-// after max_sweeps.  An entry of the order that is not a movable row of this graph (a terminal l < K, or l >= n) is
+// after max_sweeps.  An entry of the order that is not a movable row of this graph (a terminal l < first, or l >= n; first = K with
+// terminals, 0 without: a run-time value behind g.movable(), so both serve from one instantiation) is
 // never visited and never touches LDS.  Every thread must call it with cls published; on return every thread may read
 // cls.  Returns the sweeps run, the last of them the one that moved nothing when the descent converged.
 template <int K, class G>
@@ -127,7 +128,7 @@ __device__ __forceinline__ int descent_sweeps(const G &g, const int *cptr, int k
             const int hi = cptr[k0 + k + 1];
             for (int i = cptr[k0 + k] + threadIdx.x; i < hi; i += threads) {
                 const int l = g.node(i);
-                if (l < K || l >= n) continue;
+                if (!g.movable(l, n)) continue;
                 if (descent_visit<K>(g, cls, l)) moved = 1;
             }
             if (k + 1 < classes) __syncthreads();

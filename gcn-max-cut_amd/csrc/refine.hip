@@ -48,7 +48,7 @@ __global__ __launch_bounds__(256) void refine_local_kernel(RefineArgs a) {
     __syncthreads();
     const int k0 = a.cgoff[g];
     const int classes = a.cgoff[g + 1] - k0 - 1;
-    const gmc::GlobalCsr csr{a.b.rowptr + r0, a.b.lcol, a.b.vals, a.order, r0};
+    const gmc::GlobalCsr csr{a.b.rowptr + r0, a.b.lcol, a.b.vals, a.order, r0, 3};
     const int s = gmc::descent_sweeps<3>(csr, a.cptr, k0, classes, sa, n, a.max_sweeps);
     for (int l = threadIdx.x; l < n; l += blockDim.x) as[l] = (signed char)sa[l];
     const float cut = gmc::block_cut(a.b, sa, r0, n, red);
@@ -68,8 +68,8 @@ __global__ __launch_bounds__(256) void refine_pick_kernel(gmc::PickArgs a) {
 
 // HOST routine (all pointers are host pointers): first-fit colouring of every graph's movable nodes first..n-1 and the
 // (colour, id) order the kernels walk.  cptr_cap < R + B is refused before anything is written.  One body for
-// gmc_refine_order_host (first = 3), gmc_round_order_host (first = K) and gmc_large_round_order_host (first = K, graphs of
-// up to max_nodes = GMC_LARGE_MAX_GRAPH_NODES nodes).  max_classes (optional): the largest class count of any graph.
+// gmc_refine_order_host (first = 3), gmc_round_order_host (first = K), gmc_large_round_order_host (first = K, graphs of
+// up to max_nodes = GMC_LARGE_MAX_GRAPH_NODES nodes) and gmc_order_host_t (first = K or 0, graphs as large).  max_classes (optional): the largest class count of any graph.
 static int order_host(int32_t B, const int32_t *goff, const int32_t *rowptr, const int32_t *lcol, int first,
                       int max_nodes, int32_t *order, int32_t *cgoff, int32_t *cptr, int32_t cptr_cap,
                       int32_t *max_classes = nullptr) {
@@ -139,6 +139,18 @@ extern "C" int gmc_large_round_order_host(int32_t B, const int32_t *goff, const 
     if (!goff || !rowptr || !lcol || !order || !cgoff || !cptr || !max_classes) return GMC_ERR_NULL;
     if (K < 2 || K > GMC_KWAY_MAX_CLASSES) return GMC_ERR_CLASSES;
     return order_host(B, goff, rowptr, lcol, K, GMC_LARGE_MAX_GRAPH_NODES, order, cgoff, cptr, cptr_cap, max_classes);
+}
+
+// gmc_large_round_order_host with the terminals optional: first = terminals ? K : 0, so without them every node is
+// coloured and `order` holds all R rows
+extern "C" int gmc_order_host_t(int32_t B, const int32_t *goff, const int32_t *rowptr, const int32_t *lcol, int32_t K,
+                                int32_t terminals, int32_t *order, int32_t *cgoff, int32_t *cptr, int32_t cptr_cap,
+                                int32_t *max_classes) {
+    if (!goff || !rowptr || !lcol || !order || !cgoff || !cptr || !max_classes) return GMC_ERR_NULL;
+    if (K < 2 || K > GMC_KWAY_MAX_CLASSES) return GMC_ERR_CLASSES;
+    if (terminals != 0 && terminals != 1) return GMC_ERR_SHAPE;
+    return order_host(B, goff, rowptr, lcol, terminals ? K : 0, GMC_LARGE_MAX_GRAPH_NODES, order, cgoff, cptr, cptr_cap,
+                      max_classes);
 }
 
 extern "C" int gmc_refine_local_f32(const gmc_batch *batch, const int32_t *order, const int32_t *cgoff,

@@ -34,6 +34,7 @@ struct RoundArgs {
     const int *cgoff;        // [B+1] first class pointer of each graph
     const int *cptr;         // class k of graph g: order[cptr[cgoff[g]+k] .. cptr[cgoff[g]+k+1])
     int max_descent_sweeps;
+    int first;               // first movable local id: K with terminals, 0 without
     signed char *assign;     // [R]
     float *cut;              // [B]
     float *expected;         // [B] or NULL
@@ -47,19 +48,20 @@ __global__ __launch_bounds__(256) void round_conditional_kernel(RoundArgs a) {
     const int g = blockIdx.x;
     const int r0 = a.b.goff[g];
     const int n = a.b.goff[g + 1] - r0;
-    if (n > a.b.n_max || n < K) return;   // (a batch that contradicts its own n_max: the LDS is sized by it)
+    const int first = a.first;
+    if (n > a.b.n_max || n < first) return;   // (a batch that contradicts its own n_max: the LDS is sized by it)
     float *q = reinterpret_cast<float *>(lds);
     unsigned char *cls = lds + (size_t)a.b.n_max * K * sizeof(float);
     const int *rp = a.b.rowptr + r0;
     const int *col = a.b.lcol;
     const float *vals = a.b.vals;
-    // state: terminals e_l (their rows of P are not read), every other node its row of P
+    // state: terminals (l < first) e_l (their rows of P are not read), every other node its row of P
     const float *Pg = a.P + (long)r0 * K;
     for (int i = threadIdx.x; i < n * K; i += blockDim.x) {
         const int l = i / K, k = i - l * K;
-        q[i] = l < K ? (l == k ? 1.0f : 0.0f) : Pg[i];
+        q[i] = l < first ? (l == k ? 1.0f : 0.0f) : Pg[i];
     }
-    for (int l = threadIdx.x; l < n; l += blockDim.x) cls[l] = (unsigned char)(l < K ? l : 0);
+    for (int l = threadIdx.x; l < n; l += blockDim.x) cls[l] = (unsigned char)(l < first ? l : 0);
     __syncthreads();
     const gmc::FloatState<K> state{q};
     if (a.expected) {   // workgroup-uniform
@@ -78,7 +80,7 @@ __global__ __launch_bounds__(256) void round_conditional_kernel(RoundArgs a) {
         const int hi = a.cptr[k0 + k + 1];
         for (int i = a.cptr[k0 + k] + threadIdx.x; i < hi; i += blockDim.x) {
             const int l = a.order[i] - r0;
-            if (l < K || l >= n) continue;   // not a movable row of this graph: never touch LDS for it
+            if ((unsigned)(l - first) >= (unsigned)(n - first)) continue;   // not a movable row: never touch LDS for it
             const Sums<K> s = state_sums<K>(rp, col, vals, state, l);
             float wk;
             const int kk = smallest<K>(s, wk);
@@ -89,7 +91,7 @@ __global__ __launch_bounds__(256) void round_conditional_kernel(RoundArgs a) {
         __syncthreads();   // the next class, the descent or the cut count reads what this one wrote
     }
     // descent: the local search's sweeps at K classes over the class bytes
-    const gmc::GlobalCsr csr{rp, col, vals, a.order, r0};
+    const gmc::GlobalCsr csr{rp, col, vals, a.order, r0, first};
     const int sw = gmc::descent_sweeps<K>(csr, a.cptr, k0, classes, cls, n, a.max_descent_sweeps);
     signed char *as = a.assign + r0;
     for (int l = threadIdx.x; l < n; l += blockDim.x) as[l] = (signed char)cls[l];
@@ -116,20 +118,38 @@ int round_launch(const RoundArgs &a, hipStream_t st) {
 
 }  // namespace
 
-extern "C" int gmc_round_conditional_f32(const gmc_batch *batch, const float *P, int32_t K, const int32_t *order,
-                                         const int32_t *cgoff, const int32_t *cptr, int32_t max_descent_sweeps,
-                                         int8_t *assign, float *cut, float *expected, int32_t *sweeps,
-                                         gmc_stream_t stream) {
+// what both entry points do: the checks in the documented order, then the launch (terminals: 0 or 1)
+static int round_conditional(const gmc_batch *batch, const float *P, int32_t K, int32_t terminals, const int32_t *order,
+                             const int32_t *cgoff, const int32_t *cptr, int32_t max_descent_sweeps, int8_t *assign,
+                             float *cut, float *expected, int32_t *sweeps, gmc_stream_t stream) {
     if (!batch || !P || !order || !cgoff || !cptr || !assign || !cut) return GMC_ERR_NULL;
     if (batch->abi != GMC_VERSION) return GMC_ERR_ABI;
     if (!batch->goff || !batch->rowptr || !batch->lcol) return GMC_ERR_NULL;
     if (K < 2 || K > GMC_KWAY_MAX_CLASSES) return GMC_ERR_CLASSES;
-    if (max_descent_sweeps < 0 || batch->B < 0) return GMC_ERR_SHAPE;
-    if (batch->B > 0 && (batch->n_max < K || batch->n_max > GMC_MAX_GRAPH_NODES)) return GMC_ERR_GRAPH_SIZE;
+    if (max_descent_sweeps < 0 || batch->B < 0 || (terminals != 0 && terminals != 1)) return GMC_ERR_SHAPE;
+    const int first = terminals ? K : 0;
+    if (batch->B > 0 && (batch->n_max < (first > 1 ? first : 1) || batch->n_max > GMC_MAX_GRAPH_NODES))
+        return GMC_ERR_GRAPH_SIZE;
     if (batch->B == 0) return GMC_OK;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    const RoundArgs a{*batch, P, order, cgoff, cptr, max_descent_sweeps, reinterpret_cast<signed char *>(assign), cut,
-                      expected, sweeps};
+    const RoundArgs a{*batch, P, order, cgoff, cptr, max_descent_sweeps, first,
+                      reinterpret_cast<signed char *>(assign), cut, expected, sweeps};
     GMC_KWAY_DISPATCH(K, return round_launch<KK>(a, st));
     return GMC_OK;
+}
+
+extern "C" int gmc_round_conditional_f32(const gmc_batch *batch, const float *P, int32_t K, const int32_t *order,
+                                         const int32_t *cgoff, const int32_t *cptr, int32_t max_descent_sweeps,
+                                         int8_t *assign, float *cut, float *expected, int32_t *sweeps,
+                                         gmc_stream_t stream) {
+    return round_conditional(batch, P, K, 1, order, cgoff, cptr, max_descent_sweeps, assign, cut, expected, sweeps,
+                             stream);
+}
+
+extern "C" int gmc_round_conditional_t_f32(const gmc_batch *batch, const float *P, int32_t K, int32_t terminals,
+                                           const int32_t *order, const int32_t *cgoff, const int32_t *cptr,
+                                           int32_t max_descent_sweeps, int8_t *assign, float *cut, float *expected,
+                                           int32_t *sweeps, gmc_stream_t stream) {
+    return round_conditional(batch, P, K, terminals, order, cgoff, cptr, max_descent_sweeps, assign, cut, expected,
+                             sweeps, stream);
 }

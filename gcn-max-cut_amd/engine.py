@@ -294,20 +294,25 @@ class FusedEngine:
             self._small_only(batch, "dropout")
 
     def forward(self, batch: GraphBatch, C_: float = 1.0, want_loss: bool = False,
-                ws: Optional[torch.Tensor] = None, loss: str = "cut"):
+                ws: Optional[torch.Tensor] = None, loss: str = "cut", terminals: bool = True):
         """P [R,K] (and S [R], loss [B] when ``want_loss``) - TrainingNeural.py:79-85.
         ``ws``: caller-owned scratch (kept alive for a later :meth:`backward_from_gp`).  ``loss``: ``"cut"`` (the
-        reference's -C * cut of the argmax decode) or ``"expected_cut"`` (the relaxed loss: ``hip.LOSS_KINDS``)."""
-        return self._forward(batch, None, C_, want_loss, ws, loss)
+        reference's -C * cut of the argmax decode) or ``"expected_cut"`` (the relaxed loss: ``hip.LOSS_KINDS``).
+        ``terminals=False``: the caller wants P alone - the plain softmax, the same bytes either way - for a decode
+        without terminals, so a graph of fewer than number_classes nodes is no error here (the head gives such a graph
+        min(n, K) terminals and reads nothing outside its rows; S and the loss still carry them).  The library's own
+        bound stays: a batch whose LARGEST graph is below number_classes is refused (``ValueError``, gmc error -6)."""
+        return self._forward(batch, None, C_, want_loss, ws, loss, check_terminals=bool(terminals))
 
     def _forward(self, batch: GraphBatch, X: Optional[torch.Tensor], C_: float, want_loss: bool,
-                 ws: Optional[torch.Tensor], loss: str):
+                 ws: Optional[torch.Tensor], loss: str, check_terminals: bool = True):
         """:meth:`forward` (``X`` None: gmc_forward) and :meth:`forward_features` (gmc_forward_features)."""
         hip.loss_kind(loss)
         if X is not None:
             self._three_way_only("a forward through dense node features")
             self._small_only(batch, "a forward through dense node features")
-        self._check_terminals(batch)
+        if check_terminals:
+            self._check_terminals(batch)
         large = X is None and self.needs_large(batch, loss)
         if large:
             self._large_only_what_it_offers(batch)
@@ -562,10 +567,18 @@ class InstanceEngine:
     buffer ``[W1 [R,F] | b1 [B,F] | W2 [B,F,K] | b2 [B,K]]`` with gradient and Adam moments of the same layout, and the best
     partition seen per graph, and the per-graph state of early stopping (``prev_loss``, ``stall``, ``stop_epoch``: -1 while
     a graph runs; include/gcnmaxcut.h, gmc_inst_early_stop_f32).  It does not touch :class:`FusedEngine`; number_classes
-    2..8, both losses, layer1 = graphconv, no dropout, graphs within the one-workgroup head's bound."""
+    2..8, both losses, layer1 = graphconv, no dropout, graphs within the one-workgroup head's bound.
 
-    def __init__(self, batch_handles, F: int, K: int, device: Optional[torch.device] = None, *, values=None):
-        self.device = device or hip.require_gpu()
+    ``batch_handles``: the graphs' handles, or a ready :class:`GraphBatch` (``GraphBatch.from_edge_index`` builds one on
+    the device; ``values`` must then be ``None``).  ``terminals=False``: plain max-K-cut - the head overrides no row, ``S``
+    is the row argmax and both losses fix no node (gmc_inst_forward_t / gmc_inst_train_fwd_bwd_t with terminals = 0); a
+    graph then needs one node, not K."""
+
+    def __init__(self, batch_handles, F: int, K: int, device: Optional[torch.device] = None, *, values=None,
+                 terminals: bool = True):
+        if isinstance(batch_handles, GraphBatch) and device is not None and torch.device(device) != batch_handles.device:
+            raise ValueError(f"the batch lives on {batch_handles.device}, the engine was asked for {torch.device(device)}")
+        self.device = batch_handles.device if isinstance(batch_handles, GraphBatch) else device or hip.require_gpu()
         self.lib = hip.load()
         if not 2 <= K <= hip.KWAY_MAX_CLASSES:
             raise ValueError(f"number_classes must be in 2..{hip.KWAY_MAX_CLASSES}, got {K} (nodes 0..K-1 of every graph "
@@ -573,10 +586,18 @@ class InstanceEngine:
         if F < 1 or F > MAX_HIDDEN:
             raise ValueError(f"hidden_dim must be in 1..{MAX_HIDDEN} on this path (include/gcnmaxcut.h: GMC_MAX_HIDDEN), "
                              f"got {F}")
-        handles = list(batch_handles)
-        check_instance_sizes([h.n for h in handles], K)
-        self._handles, self._values = handles, None if values is None else list(values)   # (kept for subset())
-        self.batch = GraphBatch(handles, values, self.device)
+        self.terminals = bool(terminals)
+        if isinstance(batch_handles, GraphBatch):
+            if values is not None:
+                raise ValueError("values come with handles: a ready GraphBatch already holds its edge weights")
+            check_instance_sizes(batch_handles.sizes, K, terminals=self.terminals)
+            self._handles, self._values = None, None   # (subset() reads them from the batch when it needs them)
+            self.batch = batch_handles
+        else:
+            handles = list(batch_handles)
+            check_instance_sizes([h.n for h in handles], K, terminals=self.terminals)
+            self._handles, self._values = handles, None if values is None else list(values)   # (kept for subset())
+            self.batch = GraphBatch(handles, values, self.device)
         self.F, self.K, self.Fp = F, K, (F + 3) // 4 * 4   # (the kernels see the hidden width padded to float4 columns)
         self.B, self.R = self.batch.B, self.batch.R
         self.offs, self.count = instance_layout(self.batch.sizes, self.Fp, K)
@@ -667,9 +688,9 @@ class InstanceEngine:
         if self.B == 0:
             return P, S, losses
         ws = self._workspace(False)
-        rc = self.lib.gmc_inst_forward(self.batch.ref(), C.byref(self._model(loss)), C_, hip.ptr(ws), ws.numel(),
-                                       hip.ptr(P), hip.ptr(S), hip.ptr(losses), hip.stream())
-        hip.check(rc, "gmc_inst_forward")
+        rc = self.lib.gmc_inst_forward_t(self.batch.ref(), C.byref(self._model(loss)), int(self.terminals), C_,
+                                         hip.ptr(ws), ws.numel(), hip.ptr(P), hip.ptr(S), hip.ptr(losses), hip.stream())
+        hip.check(rc, "gmc_inst_forward_t")
         return P, S, losses
 
     def train_fwd_bwd(self, C_: float = 1.0, loss: str = "cut", out=None):
@@ -679,9 +700,10 @@ class InstanceEngine:
             self.grad.zero_()
             return P, S, losses
         ws = self._workspace(True)
-        rc = self.lib.gmc_inst_train_fwd_bwd(self.batch.ref(), C.byref(self._model(loss)), C_, hip.ptr(ws), ws.numel(),
-                                             hip.ptr(P), hip.ptr(S), hip.ptr(losses), hip.ptr(self.grad), hip.stream())
-        hip.check(rc, "gmc_inst_train_fwd_bwd")
+        rc = self.lib.gmc_inst_train_fwd_bwd_t(self.batch.ref(), C.byref(self._model(loss)), int(self.terminals), C_,
+                                               hip.ptr(ws), ws.numel(), hip.ptr(P), hip.ptr(S), hip.ptr(losses),
+                                               hip.ptr(self.grad), hip.stream())
+        hip.check(rc, "gmc_inst_train_fwd_bwd_t")
         return P, S, losses
 
     def adam_step(self, lr: float, betas=(0.9, 0.999), eps: float = 1e-8, running_only: bool = False) -> None:
@@ -737,7 +759,10 @@ class InstanceEngine:
         if any(b <= a for a, b in zip(keep, keep[1:])) or (keep and not 0 <= keep[0] <= keep[-1] < self.B):
             raise ValueError(f"subset: graph indices must ascend within 0..{self.B - 1}, got {keep}")
         values = None if self._values is None else [self._values[g] for g in keep]
-        sub = InstanceEngine([self._handles[g] for g in keep], self.F, self.K, self.device, values=values)
+        if self._handles is None:   # built over a ready batch: its graphs as handles, edge weights included
+            self._handles = self.batch.handles()
+        sub = InstanceEngine([self._handles[g] for g in keep], self.F, self.K, self.device, values=values,
+                             terminals=self.terminals)
         gidx = torch.tensor(keep, dtype=torch.long, device=self.device)
         goff = self.batch.goff_host
         rows = [torch.arange(int(goff[g]), int(goff[g + 1]), device=self.device) for g in keep]
@@ -754,11 +779,14 @@ class InstanceEngine:
         return sub
 
 
-def check_instance_sizes(sizes: Sequence[int], K: int, loss: str = "expected_cut") -> None:
-    """What one model per graph refuses of a batch's graph sizes: fewer than K nodes (the K-class engine's ValueError), or
-    a graph beyond the one-workgroup head (ValueError naming train_model; judged for the stricter loss by default)."""
+def check_instance_sizes(sizes: Sequence[int], K: int, loss: str = "expected_cut", terminals: bool = True) -> None:
+    """What one model per graph refuses of a batch's graph sizes: fewer than K nodes (the K-class engine's ValueError;
+    waived with ``terminals=False``, where a graph needs one node), or a graph beyond the one-workgroup head (ValueError
+    naming train_model; judged for the stricter loss by default)."""
     sizes = [int(n) for n in sizes]
-    if sizes and min(sizes) < K:
+    if sizes and not terminals and min(sizes) < 1:
+        raise ValueError("every graph needs at least one node, got an empty one")
+    if sizes and terminals and min(sizes) < K:
         raise ValueError(f"number_classes = {K}: every graph needs at least {K} nodes (nodes 0..{K - 1} "
                          f"are its terminals), got one with {min(sizes)}")
     if sizes and instance_too_large(max(sizes), K, loss):

@@ -547,15 +547,19 @@ class GraphBatch:
     def ref(self):
         return C.byref(self.c)
 
-    def refine_order(self, K: int = 3):
+    def refine_order(self, K: int = 3, terminals: bool = True):
         """(order, cgoff, cptr) on the device: the colour classes gmc_refine_local_f32 walks (gmc_refine_order_host),
         or, for ``K`` other than 3, the ones gmc_round_conditional_f32 walks when nodes 0..K-1 are the terminals
         (gmc_round_order_host).  A batch with a graph beyond ``hip.MAX_GRAPH_NODES`` nodes gets the same arrays from
         gmc_large_round_order_host (the order gmc_large_round_conditional_f32 walks).  Computed on first use and kept
-        with the batch, per ``K``; batches that are never refined never pay for it."""
-        K = int(K)
+        with the batch, per ``(K, terminals)``; batches that are never refined never pay for it.
+
+        ``terminals=False``: no node is fixed, every node is coloured and ``order`` holds all ``R`` rows
+        (gmc_order_host_t): the order the ``_t`` entry points walk with ``terminals = 0``."""
+        K, terminals = int(K), bool(terminals)
+        key = (K, terminals)
         cache = self.__dict__.setdefault("_refine", {})
-        if K not in cache:
+        if key not in cache:
             classes = C.c_int32(-1)   # the largest class count of any graph: known without a look at cgoff
             h = self.host
             order = np.zeros(max(h.R, 1), np.int32)
@@ -563,7 +567,11 @@ class GraphBatch:
             cptr = np.zeros(h.R + h.B, np.int32)
             ptr = lambda a: a.ctypes.data_as(C.c_void_p)
             go32 = h.goff.astype(np.int32)
-            if h.B and h.n_max > hip.MAX_GRAPH_NODES:
+            if not terminals:
+                rc = hip.load().gmc_order_host_t(h.B, ptr(go32), ptr(h.rowptr), ptr(h.lcol), K, 0, ptr(order), ptr(cgoff),
+                                                 ptr(cptr), cptr.size, C.byref(classes))
+                hip.check(rc, "gmc_order_host_t")
+            elif h.B and h.n_max > hip.MAX_GRAPH_NODES:
                 rc = hip.load().gmc_large_round_order_host(h.B, ptr(go32), ptr(h.rowptr), ptr(h.lcol), K, ptr(order),
                                                            ptr(cgoff), ptr(cptr), cptr.size, C.byref(classes))
                 hip.check(rc, "gmc_large_round_order_host")
@@ -576,17 +584,17 @@ class GraphBatch:
                                                      ptr(cgoff), ptr(cptr), cptr.size)
                 hip.check(rc, "gmc_round_order_host")
             dev = lambda a: torch.from_numpy(a).to(self.device)
-            cache[K] = (dev(order), dev(cgoff), dev(cptr[:max(int(cgoff[-1]), 1)].copy()))
+            cache[key] = (dev(order), dev(cgoff), dev(cptr[:max(int(cgoff[-1]), 1)].copy()))
             if classes.value < 0:
                 classes.value = int(np.diff(cgoff).max()) - 1 if h.B else 0
-            self.__dict__.setdefault("_refine_classes", {})[K] = int(classes.value)
-        return cache[K]
+            self.__dict__.setdefault("_refine_classes", {})[key] = int(classes.value)
+        return cache[key]
 
-    def refine_classes(self, K: int = 3) -> int:
-        """The largest number of colour classes any graph of the batch has in ``refine_order(K)``: the colour launches
+    def refine_classes(self, K: int = 3, terminals: bool = True) -> int:
+        """The largest number of colour classes any graph of the batch has in ``refine_order(K, terminals)``: the colour launches
         gmc_large_round_conditional_f32 / gmc_large_local_search_f32 issue per sweep (0 for an empty batch)."""
-        self.refine_order(K)
-        return self.__dict__["_refine_classes"][int(K)]
+        self.refine_order(K, terminals)
+        return self.__dict__["_refine_classes"][(int(K), bool(terminals))]
 
     def split(self, t: torch.Tensor) -> List[torch.Tensor]:
         """Per-graph views of a [R, ...] tensor."""

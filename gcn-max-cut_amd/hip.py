@@ -183,6 +183,19 @@ def _api() -> dict:
         "gmc_batch_build_workspace_bytes": (sz, [i32, i32, i64]),
         "gmc_batch_build_csr": (i, [i32, i32, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]),
         "gmc_batch_build_table": (i, [i32, i32, i32, vp, vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, i32, vp, sz, vp]),
+        # the terminals optional: the entry points above with `terminals` (0 or 1) after the class count / the model
+        "gmc_order_host_t": (i, [i32, vp, vp, vp, i32, i32, vp, vp, vp, i32, vp]),
+        "gmc_round_conditional_t_f32": (i, [B, vp, i32, i32, vp, vp, vp, i32, vp, vp, vp, vp, vp]),
+        "gmc_kway_decode_sample_seeded_t_f32": (i, [B, vp, i32, i32, vp, i32, vp, vp, vp, vp, vp, vp]),
+        "gmc_kway_refine_anneal_t_f32": (i, [B, i32, i32, vp, vp, vp, i32, vp, vp, i32, vp, C.c_uint64, i32, vp, vp, vp, vp,
+                                             vp, vp, vp]),
+        "gmc_large_round_conditional_t_f32": (i, [B, vp, i32, i32, vp, vp, vp, i32, i32, vp, sz, vp, vp, vp, vp, vp]),
+        "gmc_large_local_search_t_f32": (i, [B, i32, i32, vp, vp, vp, i32, i32, vp, sz, vp, vp, vp, vp]),
+        "gmc_large_sample_seeded_t_f32": (i, [B, vp, i32, i32, vp, i32, vp, vp, sz, vp, vp, vp, vp, vp]),
+        "gmc_large_anneal_t_f32": (i, [B, i32, i32, vp, vp, vp, i32, i32, vp, vp, i32, vp, C.c_uint64, i32, vp, sz, vp, vp,
+                                       vp, vp, vp, vp, vp]),
+        "gmc_inst_forward_t": (i, [B, M, i32, f32, vp, sz, vp, vp, vp, vp]),
+        "gmc_inst_train_fwd_bwd_t": (i, [B, M, i32, f32, vp, sz, vp, vp, vp, vp, vp]),
     }
 
 

@@ -1,0 +1,117 @@
+"""Plain max-K-cut from the tensors a GNN user holds: ``solve(edge_index, ptr, ...)``.
+
+The tensor-first front door of the instance-wise solver.  One call builds the batch on the GPU
+(``GraphBatch.from_edge_index``), gives every graph its own model and trains them all at once
+(``engine.InstanceEngine``: train / Adam / keep_best, ``epochs`` times), and decodes with one rounding, one sampler and
+one annealing launch (the ``_t`` entry points of include/gcnmaxcut.h).  By default there are no terminals: this is the
+max-cut of Gset and the max-cut papers, not the reference's variant with nodes 0..K-1 forced apart; ``terminals=True``
+gives that one.  No ``networkx`` graph and no dataset item is involved.
+"""
+from __future__ import annotations
+
+from dataclasses import dataclass
+from typing import Optional
+
+import numpy as np
+import torch
+
+from . import hip
+from .engine import InstanceEngine, instance_too_large
+from .graph import GraphBatch
+
+
+_TOO_LARGE = ("a graph of {n} nodes is beyond the one-workgroup head of the per-graph models (number_classes = {K}): "
+              "train a model through gcn_max_cut_amd.functional (terminal-free up to 2^20 nodes) and decode it with "
+              "search_large_dataset(..., terminals=False)")
+
+
+@dataclass
+class MaxCutResult:
+    """What :func:`solve` returns: device tensors, graph g owning rows ``ptr[g] .. ptr[g+1]-1`` of ``partition``."""
+    partition: torch.Tensor     # [R] int32: the class of every node
+    cut: torch.Tensor           # [B] float32: the cut of ``partition``
+    trained_cut: torch.Tensor   # [B] float32: the cut of the best partition training saw (``best_S``)
+    rounded_cut: torch.Tensor   # [B] float32: the cut of the conditional rounding of the last P
+    ptr: torch.Tensor           # [B + 1] int32
+
+
+def solve(edge_index, ptr=None, num_nodes: Optional[int] = None, edge_weight=None, *, number_classes: int = 2,
+          terminals: bool = False, pairs: str = "both", hidden_dim: int, epochs: int, learning_rate: float,
+          loss: str = "expected_cut", samples: int = 32, anneal_sweeps: int = 100, max_descent_sweeps: int = 100,
+          seed: int = 0) -> MaxCutResult:
+    """Max-K-cut of every graph of a batch given as ``edge_index`` [2, E] (with ``ptr`` [B+1], or ``num_nodes`` for one
+    graph, ``edge_weight`` and ``pairs`` as ``GraphBatch.from_edge_index`` takes them).
+
+    1. the batch, built on the GPU;
+    2. one ``GraphConv(n_g, hidden_dim) -> GraphConv(hidden_dim, number_classes)`` model per graph, initialised as the
+       reference initialises one (from a generator seeded with ``seed``; torch's global generator is left alone), trained
+       together for ``epochs`` steps of train / Adam(``learning_rate``) / keep_best on ``loss``;
+    3. one forward for P;
+    4. one conditional rounding of P, ``samples`` seeded samples of P and one annealing launch (``anneal_sweeps``
+       Metropolis sweeps, then at most ``max_descent_sweeps`` sweeps of the local search) over the candidates: the best
+       partition training saw, the rounded one and the samples.  ``cut`` is therefore never below ``trained_cut`` or
+       ``rounded_cut``.
+
+    ``terminals=False`` (default): no node is fixed.  ``terminals=True``: nodes 0..K-1 of every graph keep classes
+    0..K-1, as everywhere else in this package.  The same arguments give the same bytes.
+
+    A graph beyond the one-workgroup head of the per-graph models raises ``ValueError``: for such a graph train a model
+    through ``gcn_max_cut_amd.functional`` (terminal-free up to 2^20 nodes) and decode it with
+    ``search_large_dataset(..., terminals=False)``."""
+    K, terminals = int(number_classes), bool(terminals)
+    if not 2 <= K <= hip.KWAY_MAX_CLASSES:
+        raise ValueError(f"number_classes must be in 2..{hip.KWAY_MAX_CLASSES}, got {K}")
+    loss = hip.loss_name(loss)
+    if ptr is not None:   # judged before anything is built: the sizes are all it takes
+        p = ptr.detach().cpu().numpy() if isinstance(ptr, torch.Tensor) else np.asarray(ptr)
+        n_max = int(np.diff(p.astype(np.int64)).max()) if p.ndim == 1 and p.size > 1 else 0
+    else:
+        n_max = int(num_nodes) if num_nodes is not None else 0
+    if n_max > 0 and instance_too_large(n_max, K, loss):
+        raise ValueError(_TOO_LARGE.format(n=n_max, K=K))
+    batch = GraphBatch.from_edge_index(edge_index, ptr, num_nodes, edge_weight, pairs=pairs)
+    return solve_batch(batch, number_classes=K, terminals=terminals, hidden_dim=hidden_dim, epochs=epochs,
+                       learning_rate=learning_rate, loss=loss, samples=samples, anneal_sweeps=anneal_sweeps,
+                       max_descent_sweeps=max_descent_sweeps, seed=seed)
+
+
+def solve_batch(batch: GraphBatch, *, number_classes: int = 2, terminals: bool = False, hidden_dim: int, epochs: int,
+                learning_rate: float, loss: str = "expected_cut", samples: int = 32, anneal_sweeps: int = 100,
+                max_descent_sweeps: int = 100, seed: int = 0) -> MaxCutResult:
+    """Steps 2 to 4 of :func:`solve` on a ready batch - one built on the device or one built from handles: the batches
+    hold the same bytes, so the results do too."""
+    from .Testing import TestingNeuralNetwork as T
+    K, terminals = int(number_classes), bool(terminals)
+    if not 2 <= K <= hip.KWAY_MAX_CLASSES:
+        raise ValueError(f"number_classes must be in 2..{hip.KWAY_MAX_CLASSES}, got {K}")
+    if epochs < 0 or samples < 0 or anneal_sweeps < 0 or max_descent_sweeps < 0:
+        raise ValueError(f"epochs, samples, anneal_sweeps and max_descent_sweeps must be >= 0, got {epochs}, {samples}, "
+                         f"{anneal_sweeps}, {max_descent_sweeps}")
+    loss = hip.loss_name(loss)
+    if batch.B and instance_too_large(batch.n_max, K, loss):
+        raise ValueError(_TOO_LARGE.format(n=batch.n_max, K=K))
+    eng = InstanceEngine(batch, int(hidden_dim), K, batch.device, terminals=terminals)
+    with torch.random.fork_rng(devices=[]):
+        torch.manual_seed(int(seed))
+        eng.reset_parameters()
+    for epoch in range(int(epochs)):
+        _, S, losses = eng.train_fwd_bwd(1.0, loss=loss)
+        eng.adam_step(float(learning_rate))
+        eng.keep_best(S, losses, epoch)
+    P, S, _ = eng.forward(1.0, loss=loss)
+    best_S = eng.best_S if epochs > 0 else S
+    dev = batch.device
+    if batch.B == 0:
+        none = torch.empty(0, dtype=torch.float32, device=dev)
+        return MaxCutResult(best_S, none, none.clone(), none.clone(), batch.goff)
+    rounded, rounded_cut, _, _ = T._round_on_gpu(batch, P, 0, terminals)
+    trained = best_S.to(torch.int8).reshape(1, -1)
+    no_sweeps = np.zeros(0, np.float32)
+    _, trained_cut, _ = T._kway_anneal_on_gpu(batch, K, trained.clone(), no_sweeps, 0, 0, terminals)   # scores, moves nothing
+    rows = [trained, rounded.reshape(1, -1)]
+    if samples > 0:
+        rows.append(T._kway_sample_on_gpu(batch, P, int(samples), int(seed) & T._M64, range(batch.B), True, terminals)[3])
+    cands = torch.cat(rows).contiguous()
+    inv_temp = T.anneal_schedule(int(anneal_sweeps), scale=T._mean_edge_weight(batch))
+    partition, cut, _ = T._kway_anneal_on_gpu(batch, K, cands, inv_temp, seed, int(max_descent_sweeps), terminals)
+    return MaxCutResult(partition, cut, trained_cut, rounded_cut, batch.goff)

@@ -1257,6 +1257,88 @@ int gmc_batch_build_table(int32_t B, int32_t R, int32_t n_max, const int32_t *go
                           uint16_t *ovf_ids /*[8 ovf_blocks]*/, float *ovf_vals /*[8 ovf_blocks], with vals*/,
                           int32_t ovf_blocks, void *workspace, size_t workspace_bytes, gmc_stream_t stream);
 
+/* ---- plain max-K-cut: the terminals optional ---------------------------------------------------------------------------
+ * Everything above solves max-K-cut with local nodes 0..K-1 of every graph forced into classes 0..K-1 (the reference's
+ * problem, TrainingNeural.py:87-94).  The entry points below are the ones above with one more argument, `terminals`,
+ * directly after the class count (after `model` for the instance calls): 1 runs exactly what the entry point without
+ * the `_t` runs - the same kernels, the same bytes on every output - and 0 solves the problem without terminals, the
+ * standard max-K-cut.  The flag is a run-time argument of the same kernels: first = terminals ? K : 0 is the first
+ * movable local id, and every rule above that says "l < K" reads "l < first".  With terminals = 0:
+ *
+ *   - rounding, step 1: every node's q is its row of P (no node starts as a unit vector); every node is visited;
+ *   - the sampler's draw rule applies to every local id, with the same counter (iteration, local id);
+ *   - annealing, local search and descent: every node is movable; the counters (the wide one of graphs beyond
+ *     GMC_MAX_GRAPH_NODES included) and the level table are unchanged;
+ *   - the head of the instance calls: no row is overridden, S is the first maximum on every row, and both losses (and
+ *     their gradients) are those of gmc_fn_cut_loss_f32 with terminals = 0;
+ *   - order / cgoff / cptr come from gmc_order_host_t with the same K and terminals: `order` then holds all R rows;
+ *   - a graph needs one node, not K: the lower bound of GMC_ERR_GRAPH_SIZE is n_max >= 1.
+ *
+ * Checks and status codes are those of the entry point without the `_t`, in its order; terminals outside {0, 1} is
+ * GMC_ERR_SHAPE, reported where that entry point reports its other shape errors.  The workspace queries are shared: no
+ * size depends on the flag.
+ *
+ * gmc_order_host_t is a HOST routine (host pointers): gmc_large_round_order_host with first = terminals ? K : 0, for
+ * graphs of up to GMC_LARGE_MAX_GRAPH_NODES nodes (the one-workgroup calls then refuse what is too large for them).
+ * `order` receives R - first * B entries.  With terminals = 1 it writes what gmc_round_order_host and
+ * gmc_large_round_order_host write, array for array.  NULL (max_classes included) GMC_ERR_NULL, K GMC_ERR_CLASSES,
+ * terminals GMC_ERR_SHAPE, then the checks of gmc_large_round_order_host. */
+int gmc_order_host_t(int32_t B, const int32_t *goff, const int32_t *rowptr, const int32_t *lcol, int32_t K,
+                     int32_t terminals, int32_t *order, int32_t *cgoff, int32_t *cptr, int32_t cptr_cap,
+                     int32_t *max_classes);
+
+int gmc_round_conditional_t_f32(const gmc_batch *batch, const float *P /*[R,K]*/, int32_t K, int32_t terminals,
+                                const int32_t *order, const int32_t *cgoff, const int32_t *cptr,
+                                int32_t max_descent_sweeps, int8_t *assign /*[R]*/, float *cut /*[B]*/,
+                                float *expected /*[B] or NULL*/, int32_t *sweeps /*[B] or NULL*/, gmc_stream_t stream);
+
+int gmc_kway_decode_sample_seeded_t_f32(const gmc_batch *batch, const float *P /*[R,K]*/, int32_t K, int32_t terminals,
+                                        const uint64_t *gkey /*[B]*/, int32_t iters,
+                                        int8_t *assign_all /*[iters][R] or NULL*/, float *cut_all /*[B][iters]*/,
+                                        int32_t *best_assign /*[R]*/, float *best_cut /*[B]*/,
+                                        int32_t *best_iter /*[B]*/, gmc_stream_t stream);
+
+int gmc_kway_refine_anneal_t_f32(const gmc_batch *batch, int32_t K, int32_t terminals, const int32_t *order,
+                                 const int32_t *cgoff, const int32_t *cptr, int32_t cands,
+                                 int8_t *assign /*[cands][R], in/out*/, const float *inv_temp, int32_t anneal_sweeps,
+                                 const float *levels, uint64_t seed, int32_t max_descent_sweeps,
+                                 float *cut_all /*[B][cands]*/, int32_t *best_assign /*[R]*/, float *best_cut /*[B]*/,
+                                 int32_t *best_idx /*[B]*/, int32_t *snap_sweep /*or NULL*/, int32_t *sweeps /*or NULL*/,
+                                 gmc_stream_t stream);
+
+int gmc_large_round_conditional_t_f32(const gmc_batch *batch, const float *P /*[R,K]*/, int32_t K, int32_t terminals,
+                                      const int32_t *order, const int32_t *cgoff, const int32_t *cptr,
+                                      int32_t max_classes, int32_t max_descent_sweeps, void *workspace,
+                                      size_t workspace_bytes, int8_t *assign /*[R]*/, float *cut /*[B]*/,
+                                      float *expected /*[B] or NULL*/, int32_t *sweeps /*[B] or NULL*/,
+                                      gmc_stream_t stream);
+
+int gmc_large_local_search_t_f32(const gmc_batch *batch, int32_t K, int32_t terminals, const int32_t *order,
+                                 const int32_t *cgoff, const int32_t *cptr, int32_t max_classes, int32_t max_sweeps,
+                                 void *workspace, size_t workspace_bytes, int8_t *assign /*[R], in/out*/,
+                                 float *cut /*[B]*/, int32_t *sweeps /*[B] or NULL*/, gmc_stream_t stream);
+
+int gmc_large_sample_seeded_t_f32(const gmc_batch *batch, const float *P /*[R,K]*/, int32_t K, int32_t terminals,
+                                  const uint64_t *gkey, int32_t iters, int8_t *assign_all /*[iters][R] or NULL*/,
+                                  void *workspace, size_t workspace_bytes, float *cut_all /*[B][iters]*/,
+                                  int32_t *best_assign /*[R]*/, float *best_cut /*[B]*/, int32_t *best_iter /*[B]*/,
+                                  gmc_stream_t stream);
+
+int gmc_large_anneal_t_f32(const gmc_batch *batch, int32_t K, int32_t terminals, const int32_t *order,
+                           const int32_t *cgoff, const int32_t *cptr, int32_t max_classes, int32_t cands,
+                           int8_t *assign /*[cands][R], in/out*/, const float *inv_temp, int32_t anneal_sweeps,
+                           const float *levels, uint64_t seed, int32_t max_descent_sweeps, void *workspace,
+                           size_t workspace_bytes, float *cut_all /*[B][cands]*/, int32_t *best_assign /*[R]*/,
+                           float *best_cut /*[B]*/, int32_t *best_idx /*[B]*/, int32_t *snap_sweep /*or NULL*/,
+                           int32_t *sweeps /*or NULL*/, gmc_stream_t stream);
+
+int gmc_inst_forward_t(const gmc_batch *batch, const gmc_model *model, int32_t terminals, float C, void *workspace,
+                       size_t workspace_bytes, float *P, int32_t *S, float *loss, gmc_stream_t stream);
+
+int gmc_inst_train_fwd_bwd_t(const gmc_batch *batch, const gmc_model *model, int32_t terminals, float C,
+                             void *workspace, size_t workspace_bytes, float *P, int32_t *S, float *loss, float *grad,
+                             gmc_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
