@@ -796,6 +796,9 @@ struct InstWorkspace {
     float *Z0;       // [R,K]
     float *GY2;      // [R,K]
     float *part;     // [slots,F,K+1]
+    int32_t *S;      // [R]            gmc_inst_large_* only (inst_large_carve): the decode, for the loss launch
+    float *headpart; // [slots,K+1]    ... the head's tile partials (gmc_large_headpart_floats)
+    float *GZd;      // [R,K]          ... dinv o GZ (training)
     size_t bytes;
 };
 
@@ -821,8 +824,25 @@ InstWorkspace inst_carve(const gmc_batch *b, const gmc_model *m, bool training, 
     return w;
 }
 
-// steps 1 and 2 of the documented order (kway_check with the stacked W1: N is the batch's row count)
-int inst_check(const gmc_batch *b, const gmc_model *m, int terminals) {
+// gmc_inst_large_*: the same buffers, then what the row-parallel head of instance_large.hip keeps between its launches
+InstWorkspace inst_large_carve(const gmc_batch *b, const gmc_model *m, bool training, void *base) {
+    InstWorkspace w = inst_carve(b, m, training, base);
+    size_t off = w.bytes;
+    auto take = [&](size_t floats) {
+        float *p = base ? reinterpret_cast<float *>(static_cast<char *>(base) + off) : nullptr;
+        off += align_up(floats * sizeof(float));
+        return p;
+    };
+    w.S = reinterpret_cast<int32_t *>(take((size_t)b->R));
+    w.headpart = take(gmc_large_headpart_floats(b, m->K));
+    if (training) w.GZd = take((size_t)b->R * m->K);
+    w.bytes = off;
+    return w;
+}
+
+// steps 1 and 2 of the documented order (kway_check with the stacked W1: N is the batch's row count); large: the
+// gmc_inst_large_* entry points (several workgroups per graph: no LDS bound)
+int inst_check(const gmc_batch *b, const gmc_model *m, int terminals, bool large = false) {
     if (int rc = check_abi(b, m)) return rc;
     if (!b->goff || !b->rowptr || !b->gcol || !b->lcol || !b->dinv) return GMC_ERR_NULL;
     if (!m->W1 || !m->b1 || !m->W2 || !m->b2) return GMC_ERR_NULL;
@@ -833,7 +853,9 @@ int inst_check(const gmc_batch *b, const gmc_model *m, int terminals) {
     if (!(m->dropout_p >= 0.f && m->dropout_p < 1.f)) return GMC_ERR_SHAPE;
     if (m->dropout_p > 0.f) return GMC_ERR_UNSUPPORTED;
     if (m->W1_slab && !gmc_aligned16(m->W1_slab)) return GMC_ERR_ALIGN;
-    if (b->B > 0 && (b->n_max < (terminals ? m->K : 1) || kway_too_large(b, m))) return GMC_ERR_GRAPH_SIZE;
+    if (b->B > 0 && (b->n_max < (terminals ? m->K : 1) ||
+                     (large ? b->n_max > GMC_LARGE_MAX_GRAPH_NODES : kway_too_large(b, m))))
+        return GMC_ERR_GRAPH_SIZE;
     if (m->N != b->R) return GMC_ERR_SHAPE;  // W1 has one row per node of the batch
     return GMC_OK;
 }
@@ -842,14 +864,16 @@ struct InstCall {
     const gmc_batch *b; const gmc_model *m;
     InstWorkspace w{}; hipStream_t st = nullptr;
     int terminals = 1;   // 0: the head overrides no row (the _t entry points)
+    bool large = false;  // gmc_inst_large_*: the kernels of instance_large.hip, graphs up to GMC_LARGE_MAX_GRAPH_NODES nodes
 };
 
 int inst_open(InstCall &c, bool training, void *workspace, size_t workspace_bytes, gmc_stream_t stream, const float *P,
               const float *grad) {
-    if (int rc = inst_check(c.b, c.m, c.terminals)) return rc;                                    // 1. 2.
+    if (int rc = inst_check(c.b, c.m, c.terminals, c.large)) return rc;                           // 1. 2.
     if (!workspace || !P || (training && !grad)) return GMC_ERR_NULL;                // 4. workspace and outputs
     if (!gmc_aligned16(grad) || !gmc_aligned16(P) || !gmc_aligned16(c.m->W2)) return GMC_ERR_ALIGN;   // 5.
-    c.w = inst_carve(c.b, c.m, training, workspace);                                 // 6. size
+    if (c.large && !gmc_aligned16(c.m->W1)) return GMC_ERR_ALIGN;   // (the hub-row launches read W1 as float4 only)
+    c.w = c.large ? inst_large_carve(c.b, c.m, training, workspace) : inst_carve(c.b, c.m, training, workspace);   // 6. size
     if (c.w.bytes > workspace_bytes) return GMC_ERR_WORKSPACE;
     c.st = static_cast<hipStream_t>(stream);
     return GMC_OK;
@@ -870,13 +894,23 @@ int inst_forward_body(const InstCall &c, float C, float *P, int32_t *S, float *l
     // T0 = dinv o (A_val @ W1): the gather of the stacked W1 by batch row id
     int rc = gmc_spmm_launch(b->rowptr, b->gcol, b->vals, b->dinv, m->W1, F, nullptr, 0, w.T0, w.ld, b->R, F,
                              group_rows(b), nullptr, nullptr, GMC_K_GATHER_W1, c.st);
+    if (!rc && c.large)   // (gmc_inst_large_*: rows of more than 64 entries once more, summed in chunks - launchers.h)
+        rc = gmc_large_hub_rows_launch(b->rowptr, b->gcol, b->vals, b->dinv, m->W1, F, nullptr, 0, w.T0, w.ld, b->R, F,
+                                       GMC_K_GATHER_W1, c.st);
     if (rc) return rc;
     // dinv o (A @ T0); the graph's own bias and the relu are inst_hw2's
     rc = gmc_spmm_launch(b->rowptr, b->gcol, nullptr, b->dinv, w.T0, w.ld, nullptr, 0, w.H, w.ld, b->R, F, group_rows(b),
                          nullptr, nullptr, GMC_K_AGG_FWD, c.st);
+    if (!rc && c.large)
+        rc = gmc_large_hub_rows_launch(b->rowptr, b->gcol, nullptr, b->dinv, w.T0, w.ld, nullptr, 0, w.H, w.ld, b->R, F,
+                                       GMC_K_AGG_FWD, c.st);
     if (rc) return rc;
-    rc = gmc_inst_hw2_launch(b, w.H, w.ld, m->b1, m->W2, w.Z0, F, m->K, c.st);
+    rc = c.large ? gmc_inst_large_hw2_launch(b, w.H, w.ld, m->b1, m->W2, w.Z0, F, m->K, c.st)
+                 : gmc_inst_hw2_launch(b, w.H, w.ld, m->b1, m->W2, w.Z0, F, m->K, c.st);
     if (rc) return rc;
+    if (c.large)
+        return gmc_inst_large_head_launch(b, w.Z0, m->b2, C, m->K, loss_of(m), c.terminals, P, S, loss, w.S,
+                                          db2 ? w.GZd : nullptr, w.headpart, w.GY2, db2, c.st);
     return gmc_kway_head_launch(b, w.Z0, m->b2, C, m->K, loss_of(m), P, S, loss, db2 ? w.GY2 : nullptr, db2, c.st, m->K,
                                 c.terminals);
 }
@@ -891,10 +925,17 @@ int inst_backward_body(const InstCall &c, const InstGrad &g) {
     // conv1 backward aggregation:  U = dinv o (A @ Gs)
     rc = gmc_spmm_launch(b->rowptr, b->gcol, nullptr, b->dinv, Gs, w.ld, nullptr, 0, U, w.ld, b->R, m->F, group_rows(b),
                          nullptr, nullptr, GMC_K_AGG_BWD, c.st);
+    if (!rc && c.large)
+        rc = gmc_large_hub_rows_launch(b->rowptr, b->gcol, nullptr, b->dinv, Gs, w.ld, nullptr, 0, U, w.ld, b->R, m->F,
+                                       GMC_K_AGG_BWD, c.st);
     if (rc) return rc;
     // dW1 = A_val^T @ U = A_val @ U (undirected graphs, symmetric weights): every row of W1 belongs to one node
-    return gmc_spmm_launch(b->rowptr, b->gcol, b->vals, nullptr, U, w.ld, nullptr, 0, g.dW1, m->F, b->R, m->F,
-                           group_rows(b), nullptr, nullptr, GMC_K_DW1, c.st);
+    rc = gmc_spmm_launch(b->rowptr, b->gcol, b->vals, nullptr, U, w.ld, nullptr, 0, g.dW1, m->F, b->R, m->F,
+                         group_rows(b), nullptr, nullptr, GMC_K_DW1, c.st);
+    if (!rc && c.large)
+        rc = gmc_large_hub_rows_launch(b->rowptr, b->gcol, b->vals, nullptr, U, w.ld, nullptr, 0, g.dW1, m->F, b->R, m->F,
+                                       GMC_K_DW1, c.st);
+    return rc;
 }
 
 }  // namespace
@@ -904,14 +945,39 @@ extern "C" size_t gmc_inst_workspace_bytes(const gmc_batch *batch, const gmc_mod
     return inst_carve(batch, model, training != 0, nullptr).bytes;
 }
 
+namespace {
+
+int inst_forward_call(InstCall c, float C, void *workspace, size_t workspace_bytes, float *P, int32_t *S, float *loss,
+                      gmc_stream_t stream) {
+    int rc = inst_open(c, false, workspace, workspace_bytes, stream, P, nullptr);
+    if (rc || c.b->R == 0) return rc;
+    return inst_forward_body(c, C, P, S, loss, nullptr);
+}
+
+int inst_train_call(InstCall c, float C, void *workspace, size_t workspace_bytes, float *P, int32_t *S, float *loss,
+                    float *grad, gmc_stream_t stream) {
+    int rc = inst_open(c, true, workspace, workspace_bytes, stream, P, grad);
+    if (rc) return rc;
+    const InstGrad g = inst_grad(c.b, c.m, grad);
+    if (c.b->R == 0)   // an empty batch: its gradient (B * (F + F*K + K) floats: none when B is 0 too) is zero
+        return g.count ? (int)hipMemsetAsync(grad, 0, g.count * sizeof(float), c.st) : GMC_OK;
+    rc = inst_forward_body(c, C, P, S, loss, g.db2);
+    return rc ? rc : inst_backward_body(c, g);
+}
+
+InstCall inst_call_of(const gmc_batch *batch, const gmc_model *model, int terminals, bool large) {
+    InstCall c{batch, model};
+    c.terminals = terminals;
+    c.large = large;
+    return c;
+}
+
+}  // namespace
+
 extern "C" int gmc_inst_forward_t(const gmc_batch *batch, const gmc_model *model, int32_t terminals, float C,
                                   void *workspace, size_t workspace_bytes, float *P, int32_t *S, float *loss,
                                   gmc_stream_t stream) {
-    InstCall c{batch, model};
-    c.terminals = terminals;
-    int rc = inst_open(c, false, workspace, workspace_bytes, stream, P, nullptr);
-    if (rc || batch->R == 0) return rc;
-    return inst_forward_body(c, C, P, S, loss, nullptr);
+    return inst_forward_call(inst_call_of(batch, model, terminals, false), C, workspace, workspace_bytes, P, S, loss, stream);
 }
 
 extern "C" int gmc_inst_forward(const gmc_batch *batch, const gmc_model *model, float C, void *workspace,
@@ -922,21 +988,38 @@ extern "C" int gmc_inst_forward(const gmc_batch *batch, const gmc_model *model, 
 extern "C" int gmc_inst_train_fwd_bwd_t(const gmc_batch *batch, const gmc_model *model, int32_t terminals, float C,
                                         void *workspace, size_t workspace_bytes, float *P, int32_t *S, float *loss,
                                         float *grad, gmc_stream_t stream) {
-    InstCall c{batch, model};
-    c.terminals = terminals;
-    int rc = inst_open(c, true, workspace, workspace_bytes, stream, P, grad);
-    if (rc) return rc;
-    const InstGrad g = inst_grad(batch, model, grad);
-    if (batch->R == 0)   // an empty batch: its gradient (B * (F + F*K + K) floats: none when B is 0 too) is zero
-        return g.count ? (int)hipMemsetAsync(grad, 0, g.count * sizeof(float), c.st) : GMC_OK;
-    rc = inst_forward_body(c, C, P, S, loss, g.db2);
-    return rc ? rc : inst_backward_body(c, g);
+    return inst_train_call(inst_call_of(batch, model, terminals, false), C, workspace, workspace_bytes, P, S, loss, grad,
+                           stream);
 }
 
 extern "C" int gmc_inst_train_fwd_bwd(const gmc_batch *batch, const gmc_model *model, float C, void *workspace,
                                       size_t workspace_bytes, float *P, int32_t *S, float *loss, float *grad,
                                       gmc_stream_t stream) {
     return gmc_inst_train_fwd_bwd_t(batch, model, 1, C, workspace, workspace_bytes, P, S, loss, grad, stream);
+}
+
+// ---- one model per graph beyond GMC_MAX_GRAPH_NODES: the same sequence with the kernels of instance_large.hip ------------
+// Every launch of the sequence was read for a grid dimension sized by n_max at n_max = GMC_LARGE_MAX_GRAPH_NODES:
+// gmc_inst_hw2_launch has ceil(n_max / 4) workgroups in y (262,144: beyond 65,535 - gmc_inst_large_hw2_launch walks the
+// tiles instead), gmc_inst_hidden_bwd_launch 16,384, the head 4,096, keep-best / early-stop 4,096; gmc_spmm_launch,
+// gmc_large_hub_rows_launch and gmc_inst_fold_launch size no y or z dimension by n_max.  gmc_inst_adam_f32 refuses
+// n_max * F beyond about 2^28 (GMC_ERR_SHAPE), as before.
+extern "C" size_t gmc_inst_large_workspace_bytes(const gmc_batch *batch, const gmc_model *model, int training) {
+    if (check_abi(batch, model) || !kway_classes_ok(model->K)) return 0;
+    return inst_large_carve(batch, model, training != 0, nullptr).bytes;
+}
+
+extern "C" int gmc_inst_large_forward(const gmc_batch *batch, const gmc_model *model, int32_t terminals, float C,
+                                      void *workspace, size_t workspace_bytes, float *P, int32_t *S, float *loss,
+                                      gmc_stream_t stream) {
+    return inst_forward_call(inst_call_of(batch, model, terminals, true), C, workspace, workspace_bytes, P, S, loss, stream);
+}
+
+extern "C" int gmc_inst_large_train_fwd_bwd(const gmc_batch *batch, const gmc_model *model, int32_t terminals, float C,
+                                            void *workspace, size_t workspace_bytes, float *P, int32_t *S, float *loss,
+                                            float *grad, gmc_stream_t stream) {
+    return inst_train_call(inst_call_of(batch, model, terminals, true), C, workspace, workspace_bytes, P, S, loss, grad,
+                           stream);
 }
 
 // ---- graph-attention first layer: the row-kernel sequence with the kernels of attention.hip -------------------------------

@@ -128,6 +128,16 @@ int gmc_inst_hidden_bwd_launch(const gmc_batch *b, const float *H, long ldh, con
                                long ldg, float *part, int F, int K, hipStream_t st);
 int gmc_inst_fold_launch(const gmc_batch *b, const float *part, int F, int K, float *dW2, float *db1, hipStream_t st);
 
+// ---- one model per graph beyond a CU's LDS (instance_large.hip: gmc_inst_large_*), n_max up to GMC_LARGE_MAX_GRAPH_NODES.
+// gmc_inst_hw2_launch with a grid that stays within 65,535 in y (a workgroup walks the graph's 4-row tiles): the same bytes
+int gmc_inst_large_hw2_launch(const gmc_batch *b, float *H, long ld, const float *b1, const float *W2, float *Z0, int F,
+                              int K, hipStream_t st);
+// gmc_large_head_launch (same scratch: Sw [R], GZd [R,K], headpart [gmc_large_headpart_floats]) with b2 [B,K] read at
+// b2 + g * K, terminals (0 / 1) a run-time value and the per-graph sums of the softmax backward written to db2 [B,K]
+int gmc_inst_large_head_launch(const gmc_batch *b, const float *Z0, const float *b2, float C, int K, int loss_kind,
+                               int terminals, float *P, int32_t *S, float *loss, int32_t *Sw, float *GZd, float *headpart,
+                               float *GY2, float *db2, hipStream_t st);
+
 // ---- the head for graphs beyond a CU's LDS (large.hip): head_k_kernel as row-parallel launches, several workgroups per
 // graph (tiles of 256 rows).  Sw [R] ints, GZd [R,K] (dinv o GZ) and headpart [gmc_large_headpart_floats] are scratch.
 size_t gmc_large_headpart_floats(const gmc_batch *b, int K);

@@ -574,6 +574,9 @@ class InstanceEngine:
     is the row argmax and both losses fix no node (gmc_inst_forward_t / gmc_inst_train_fwd_bwd_t with terminals = 0); a
     graph then needs one node, not K."""
 
+    # the three entry points of include/gcnmaxcut.h the engine computes through (LargeInstanceEngine: gmc_inst_large_*)
+    _WORKSPACE, _FORWARD, _TRAIN = "gmc_inst_workspace_bytes", "gmc_inst_forward_t", "gmc_inst_train_fwd_bwd_t"
+
     def __init__(self, batch_handles, F: int, K: int, device: Optional[torch.device] = None, *, values=None,
                  terminals: bool = True):
         if isinstance(batch_handles, GraphBatch) and device is not None and torch.device(device) != batch_handles.device:
@@ -590,12 +593,12 @@ class InstanceEngine:
         if isinstance(batch_handles, GraphBatch):
             if values is not None:
                 raise ValueError("values come with handles: a ready GraphBatch already holds its edge weights")
-            check_instance_sizes(batch_handles.sizes, K, terminals=self.terminals)
+            self._check_sizes(batch_handles.sizes, K)
             self._handles, self._values = None, None   # (subset() reads them from the batch when it needs them)
             self.batch = batch_handles
         else:
             handles = list(batch_handles)
-            check_instance_sizes([h.n for h in handles], K, terminals=self.terminals)
+            self._check_sizes([h.n for h in handles], K)
             self._handles, self._values = handles, None if values is None else list(values)   # (kept for subset())
             self.batch = GraphBatch(handles, values, self.device)
         self.F, self.K, self.Fp = F, K, (F + 3) // 4 * 4   # (the kernels see the hidden width padded to float4 columns)
@@ -613,6 +616,9 @@ class InstanceEngine:
         self.stall = torch.zeros(self.B, dtype=torch.int32, device=self.device)
         self.stop_epoch = torch.full((self.B,), -1, dtype=torch.int32, device=self.device)
         self._ws: Optional[torch.Tensor] = None
+
+    def _check_sizes(self, sizes: Sequence[int], K: int) -> None:
+        check_instance_sizes(sizes, K, terminals=self.terminals)
 
     # ---- parameters
     def blocks(self, buf: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
@@ -667,7 +673,7 @@ class InstanceEngine:
     # ---- compute
     def workspace_bytes(self, training: bool) -> int:
         model = hip.GmcModel(N=self.R, F=self.Fp, K=self.K)
-        return max(256, int(self.lib.gmc_inst_workspace_bytes(self.batch.ref(), C.byref(model), int(training))))
+        return max(256, int(getattr(self.lib, self._WORKSPACE)(self.batch.ref(), C.byref(model), int(training))))
 
     def _workspace(self, training: bool) -> torch.Tensor:
         need = self.workspace_bytes(training)
@@ -688,9 +694,10 @@ class InstanceEngine:
         if self.B == 0:
             return P, S, losses
         ws = self._workspace(False)
-        rc = self.lib.gmc_inst_forward_t(self.batch.ref(), C.byref(self._model(loss)), int(self.terminals), C_,
-                                         hip.ptr(ws), ws.numel(), hip.ptr(P), hip.ptr(S), hip.ptr(losses), hip.stream())
-        hip.check(rc, "gmc_inst_forward_t")
+        rc = getattr(self.lib, self._FORWARD)(self.batch.ref(), C.byref(self._model(loss)), int(self.terminals), C_,
+                                              hip.ptr(ws), ws.numel(), hip.ptr(P), hip.ptr(S), hip.ptr(losses),
+                                              hip.stream())
+        hip.check(rc, self._FORWARD)
         return P, S, losses
 
     def train_fwd_bwd(self, C_: float = 1.0, loss: str = "cut", out=None):
@@ -700,10 +707,10 @@ class InstanceEngine:
             self.grad.zero_()
             return P, S, losses
         ws = self._workspace(True)
-        rc = self.lib.gmc_inst_train_fwd_bwd_t(self.batch.ref(), C.byref(self._model(loss)), int(self.terminals), C_,
-                                               hip.ptr(ws), ws.numel(), hip.ptr(P), hip.ptr(S), hip.ptr(losses),
-                                               hip.ptr(self.grad), hip.stream())
-        hip.check(rc, "gmc_inst_train_fwd_bwd_t")
+        rc = getattr(self.lib, self._TRAIN)(self.batch.ref(), C.byref(self._model(loss)), int(self.terminals), C_,
+                                            hip.ptr(ws), ws.numel(), hip.ptr(P), hip.ptr(S), hip.ptr(losses),
+                                            hip.ptr(self.grad), hip.stream())
+        hip.check(rc, self._TRAIN)
         return P, S, losses
 
     def adam_step(self, lr: float, betas=(0.9, 0.999), eps: float = 1e-8, running_only: bool = False) -> None:
@@ -714,6 +721,10 @@ class InstanceEngine:
         if self.count == 0:
             return
         if running_only:
+            if inst_adam_too_large(self.batch.n_max, self.Fp, self.K):
+                raise ValueError(f"adam_step(running_only=True): a graph of {self.batch.n_max} nodes at hidden width "
+                                 f"{self.Fp} is beyond the segmented Adam's bound of {INST_ADAM_MAX_TILES} tiles of "
+                                 f"{hip.INST_ADAM_TILE_FLOATS} floats per graph (n_max * hidden_dim up to about 2^28)")
             rc = self.lib.gmc_inst_adam_f32(self.batch.ref(), self.Fp, self.K, hip.ptr(self.flat), hip.ptr(self.grad),
                                             hip.ptr(self.m), hip.ptr(self.v), lr, betas[0], betas[1], eps, self.step_count,
                                             hip.ptr(self.stop_epoch), hip.stream())
@@ -761,8 +772,8 @@ class InstanceEngine:
         values = None if self._values is None else [self._values[g] for g in keep]
         if self._handles is None:   # built over a ready batch: its graphs as handles, edge weights included
             self._handles = self.batch.handles()
-        sub = InstanceEngine([self._handles[g] for g in keep], self.F, self.K, self.device, values=values,
-                             terminals=self.terminals)
+        sub = type(self)([self._handles[g] for g in keep], self.F, self.K, self.device, values=values,
+                         terminals=self.terminals)
         gidx = torch.tensor(keep, dtype=torch.long, device=self.device)
         goff = self.batch.goff_host
         rows = [torch.arange(int(goff[g]), int(goff[g + 1]), device=self.device) for g in keep]
@@ -779,6 +790,47 @@ class InstanceEngine:
         return sub
 
 
+INST_ADAM_MAX_TILES = 65535   # gmc_inst_adam_f32: a graph's tiles are a grid dimension
+
+
+def inst_adam_too_large(n_max: int, F: int, K: int) -> bool:
+    """Would gmc_inst_adam_f32 refuse a graph of ``n_max`` nodes at hidden width ``F`` (a multiple of 4)?  Its grid has
+    one y entry per tile of ``hip.INST_ADAM_TILE_FLOATS`` floats of the largest graph's W1 and of the three small blocks."""
+    tile = hip.INST_ADAM_TILE_FLOATS
+    w1_tiles = (int(n_max) * (F // 4) + tile // 4 - 1) // (tile // 4)
+    small_tiles = (F + F * K + K + tile - 1) // tile
+    return w1_tiles + small_tiles > INST_ADAM_MAX_TILES
+
+
+class LargeInstanceEngine(InstanceEngine):
+    """:class:`InstanceEngine` for graphs of up to ``hip.LARGE_MAX_GRAPH_NODES`` nodes (gmc_inst_large_*: several
+    workgroups share a graph's head).  Same constructor, buffers and methods; ``forward`` and
+    ``train_fwd_bwd`` run the large sequence for every graph of the batch, small ones included - on a batch
+    :class:`InstanceEngine` takes the partitions are the same, and probabilities, losses and gradients agree to rounding.
+    ``adam_step(running_only=True)`` keeps the segmented Adam's own bound (n_max * hidden_dim up to about 2^28) and
+    raises ``ValueError`` beyond it; the plain ``adam_step`` has none.  About 16 * hidden_dim bytes per node for the
+    parameters, gradient and moments and 8 * ld for the workspace (ld = hidden_dim rounded up to 32)."""
+
+    _WORKSPACE, _FORWARD, _TRAIN = "gmc_inst_large_workspace_bytes", "gmc_inst_large_forward", "gmc_inst_large_train_fwd_bwd"
+
+    def _check_sizes(self, sizes: Sequence[int], K: int) -> None:
+        check_large_instance_sizes(sizes, K, terminals=self.terminals)
+
+
+def check_large_instance_sizes(sizes: Sequence[int], K: int, terminals: bool = True) -> None:
+    """:func:`check_instance_sizes` for :class:`LargeInstanceEngine`: the same minimum, ``hip.LARGE_MAX_GRAPH_NODES`` nodes
+    at most."""
+    sizes = [int(n) for n in sizes]
+    if sizes and not terminals and min(sizes) < 1:
+        raise ValueError("every graph needs at least one node, got an empty one")
+    if sizes and terminals and min(sizes) < K:
+        raise ValueError(f"number_classes = {K}: every graph needs at least {K} nodes (nodes 0..{K - 1} "
+                         f"are its terminals), got one with {min(sizes)}")
+    if sizes and max(sizes) > hip.LARGE_MAX_GRAPH_NODES:
+        raise ValueError(f"a graph of {max(sizes)} nodes is beyond the {hip.LARGE_MAX_GRAPH_NODES} nodes of the per-graph "
+                         "models' large sequence (gmc_inst_large_*)")
+
+
 def check_instance_sizes(sizes: Sequence[int], K: int, loss: str = "expected_cut", terminals: bool = True) -> None:
     """What one model per graph refuses of a batch's graph sizes: fewer than K nodes (the K-class engine's ValueError;
     waived with ``terminals=False``, where a graph needs one node), or a graph beyond the one-workgroup head (ValueError
@@ -792,7 +844,9 @@ def check_instance_sizes(sizes: Sequence[int], K: int, loss: str = "expected_cut
     if sizes and instance_too_large(max(sizes), K, loss):
         raise ValueError(f"a graph of {max(sizes)} nodes is beyond the one-workgroup head of the per-graph models "
                          f"(number_classes = {K}: {hip.MAX_GRAPH_NODES} nodes at most, fewer for number_classes > 3): one "
-                         "large graph on its own is what train_model already serves (a model of n_nodes = n)")
+                         "large graph on its own is what train_model already serves (a model of n_nodes = n), and "
+                         "LargeInstanceEngine / maxcut.solve_large train one model per graph up to "
+                         f"{hip.LARGE_MAX_GRAPH_NODES} nodes")
 
 
 def module_of(params: Dict[str, torch.Tensor]):

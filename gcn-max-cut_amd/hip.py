@@ -196,6 +196,10 @@ def _api() -> dict:
                                        vp, vp, vp, vp, vp]),
         "gmc_inst_forward_t": (i, [B, M, i32, f32, vp, sz, vp, vp, vp, vp]),
         "gmc_inst_train_fwd_bwd_t": (i, [B, M, i32, f32, vp, sz, vp, vp, vp, vp, vp]),
+        # one model per graph for graphs of up to LARGE_MAX_GRAPH_NODES nodes
+        "gmc_inst_large_workspace_bytes": (sz, [B, M, i]),
+        "gmc_inst_large_forward": (i, [B, M, i32, f32, vp, sz, vp, vp, vp, vp]),
+        "gmc_inst_large_train_fwd_bwd": (i, [B, M, i32, f32, vp, sz, vp, vp, vp, vp, vp]),
     }
 
 

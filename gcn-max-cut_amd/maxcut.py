@@ -10,19 +10,21 @@ gives that one.  No ``networkx`` graph and no dataset item is involved.
 from __future__ import annotations
 
 from dataclasses import dataclass
-from typing import Optional
+from typing import Callable, Optional
 
 import numpy as np
 import torch
 
 from . import hip
-from .engine import InstanceEngine, instance_too_large
+from .engine import InstanceEngine, LargeInstanceEngine, instance_too_large
 from .graph import GraphBatch
 
 
 _TOO_LARGE = ("a graph of {n} nodes is beyond the one-workgroup head of the per-graph models (number_classes = {K}): "
               "train a model through gcn_max_cut_amd.functional (terminal-free up to 2^20 nodes) and decode it with "
-              "search_large_dataset(..., terminals=False)")
+              "search_large_dataset(..., terminals=False), or call maxcut.solve_large, which trains one model per graph up "
+              "to 2^20 nodes")
+_BEYOND_LARGE = "a graph of {n} nodes is beyond the {bound} nodes of the per-graph models' large sequence (solve_large)"
 
 
 @dataclass
@@ -80,6 +82,85 @@ def solve_batch(batch: GraphBatch, *, number_classes: int = 2, terminals: bool =
                 max_descent_sweeps: int = 100, seed: int = 0) -> MaxCutResult:
     """Steps 2 to 4 of :func:`solve` on a ready batch - one built on the device or one built from handles: the batches
     hold the same bytes, so the results do too."""
+    return _solve_batch(_small_route(), batch, number_classes, terminals, hidden_dim, epochs, learning_rate, loss, samples,
+                        anneal_sweeps, max_descent_sweeps, seed)
+
+
+def solve_large(edge_index, ptr=None, num_nodes: Optional[int] = None, edge_weight=None, *, number_classes: int = 2,
+                terminals: bool = False, pairs: str = "both", hidden_dim: int, epochs: int, learning_rate: float,
+                loss: str = "expected_cut", samples: int = 32, anneal_sweeps: int = 100, max_descent_sweeps: int = 100,
+                seed: int = 0) -> MaxCutResult:
+    """:func:`solve` for graphs of up to ``hip.LARGE_MAX_GRAPH_NODES`` (2^20) nodes: the same arguments, steps and
+    result, with ``engine.LargeInstanceEngine`` (gmc_inst_large_*) as the trainer and the large decoders (one rounding,
+    one sampler and one annealing call of gmc_large_*_t_f32; several workgroups share a graph).  It takes small graphs
+    too - :func:`solve` is the faster route for those; nothing routes from one to the other.  The large decoders issue
+    every launch of ``anneal_sweeps`` + ``max_descent_sweeps`` sweeps whether or not the descent has converged, and the
+    samples live on the device while they are scored (``samples`` + 2 bytes per node).  Memory while training: about
+    16 * hidden_dim bytes per node for parameters, gradient and Adam moments plus 8 * ld for the workspace (ld =
+    hidden_dim rounded up to 32): 1.5 KB per node at hidden_dim = 64."""
+    K, terminals = int(number_classes), bool(terminals)
+    if not 2 <= K <= hip.KWAY_MAX_CLASSES:
+        raise ValueError(f"number_classes must be in 2..{hip.KWAY_MAX_CLASSES}, got {K}")
+    loss = hip.loss_name(loss)
+    batch = GraphBatch.from_edge_index(edge_index, ptr, num_nodes, edge_weight, pairs=pairs)
+    return solve_large_batch(batch, number_classes=K, terminals=terminals, hidden_dim=hidden_dim, epochs=epochs,
+                             learning_rate=learning_rate, loss=loss, samples=samples, anneal_sweeps=anneal_sweeps,
+                             max_descent_sweeps=max_descent_sweeps, seed=seed)
+
+
+def solve_large_batch(batch: GraphBatch, *, number_classes: int = 2, terminals: bool = False, hidden_dim: int,
+                      epochs: int, learning_rate: float, loss: str = "expected_cut", samples: int = 32,
+                      anneal_sweeps: int = 100, max_descent_sweeps: int = 100, seed: int = 0) -> MaxCutResult:
+    """:func:`solve_batch` through ``engine.LargeInstanceEngine`` and the large decoders: steps 2 to 4 of
+    :func:`solve_large` on a ready batch."""
+    return _solve_batch(_large_route(), batch, number_classes, terminals, hidden_dim, epochs, learning_rate, loss, samples,
+                        anneal_sweeps, max_descent_sweeps, seed)
+
+
+@dataclass
+class _Route:
+    """What tells :func:`solve_batch` from :func:`solve_large_batch`: the engine class, the refusal of a batch by its
+    largest graph, and the three decoders as ``round(batch, P, terminals)``, ``sample(batch, P, samples, seed, terminals)``
+    and ``anneal(batch, K, cands, inv_temp, seed, max_descent_sweeps, terminals)``."""
+    engine: type
+    refuse: Callable
+    round: Callable
+    sample: Callable
+    anneal: Callable
+
+
+def _small_route() -> _Route:
+    from .Testing import TestingNeuralNetwork as T
+
+    def refuse(n_max, K, loss):
+        if instance_too_large(n_max, K, loss):
+            raise ValueError(_TOO_LARGE.format(n=n_max, K=K))
+
+    return _Route(InstanceEngine, refuse,
+                  lambda batch, P, t: T._round_on_gpu(batch, P, 0, t),
+                  lambda batch, P, n, seed, t: T._kway_sample_on_gpu(batch, P, n, seed, range(batch.B), True, t)[3],
+                  lambda batch, K, cands, inv_temp, seed, sweeps, t: T._kway_anneal_on_gpu(batch, K, cands, inv_temp, seed,
+                                                                                           sweeps, t))
+
+
+def _large_route() -> _Route:
+    from .Testing import TestingNeuralNetwork as T
+
+    def refuse(n_max, K, loss):
+        if n_max > hip.LARGE_MAX_GRAPH_NODES:
+            raise ValueError(_BEYOND_LARGE.format(n=n_max, bound=hip.LARGE_MAX_GRAPH_NODES))
+
+    return _Route(LargeInstanceEngine, refuse,
+                  lambda batch, P, t: T._large_round_on_gpu(batch, P, 0, t),
+                  lambda batch, P, n, seed, t: T._large_sample_on_gpu(batch, P, n, seed, range(batch.B), True,
+                                                                      terminals=t)[3],
+                  lambda batch, K, cands, inv_temp, seed, sweeps, t: T._large_anneal_on_gpu(batch, K, cands, inv_temp, seed,
+                                                                                            sweeps, terminals=t))
+
+
+def _solve_batch(route: _Route, batch: GraphBatch, number_classes: int, terminals: bool, hidden_dim: int, epochs: int,
+                 learning_rate: float, loss: str, samples: int, anneal_sweeps: int, max_descent_sweeps: int,
+                 seed: int) -> MaxCutResult:
     from .Testing import TestingNeuralNetwork as T
     K, terminals = int(number_classes), bool(terminals)
     if not 2 <= K <= hip.KWAY_MAX_CLASSES:
@@ -88,9 +169,9 @@ def solve_batch(batch: GraphBatch, *, number_classes: int = 2, terminals: bool =
         raise ValueError(f"epochs, samples, anneal_sweeps and max_descent_sweeps must be >= 0, got {epochs}, {samples}, "
                          f"{anneal_sweeps}, {max_descent_sweeps}")
     loss = hip.loss_name(loss)
-    if batch.B and instance_too_large(batch.n_max, K, loss):
-        raise ValueError(_TOO_LARGE.format(n=batch.n_max, K=K))
-    eng = InstanceEngine(batch, int(hidden_dim), K, batch.device, terminals=terminals)
+    if batch.B:
+        route.refuse(batch.n_max, K, loss)
+    eng = route.engine(batch, int(hidden_dim), K, batch.device, terminals=terminals)
     with torch.random.fork_rng(devices=[]):
         torch.manual_seed(int(seed))
         eng.reset_parameters()
@@ -104,14 +185,14 @@ def solve_batch(batch: GraphBatch, *, number_classes: int = 2, terminals: bool =
     if batch.B == 0:
         none = torch.empty(0, dtype=torch.float32, device=dev)
         return MaxCutResult(best_S, none, none.clone(), none.clone(), batch.goff)
-    rounded, rounded_cut, _, _ = T._round_on_gpu(batch, P, 0, terminals)
+    rounded, rounded_cut, _, _ = route.round(batch, P, terminals)
     trained = best_S.to(torch.int8).reshape(1, -1)
     no_sweeps = np.zeros(0, np.float32)
-    _, trained_cut, _ = T._kway_anneal_on_gpu(batch, K, trained.clone(), no_sweeps, 0, 0, terminals)   # scores, moves nothing
+    _, trained_cut, _ = route.anneal(batch, K, trained.clone(), no_sweeps, 0, 0, terminals)   # scores, moves nothing
     rows = [trained, rounded.reshape(1, -1)]
     if samples > 0:
-        rows.append(T._kway_sample_on_gpu(batch, P, int(samples), int(seed) & T._M64, range(batch.B), True, terminals)[3])
+        rows.append(route.sample(batch, P, int(samples), int(seed) & T._M64, terminals))
     cands = torch.cat(rows).contiguous()
     inv_temp = T.anneal_schedule(int(anneal_sweeps), scale=T._mean_edge_weight(batch))
-    partition, cut, _ = T._kway_anneal_on_gpu(batch, K, cands, inv_temp, seed, int(max_descent_sweeps), terminals)
+    partition, cut, _ = route.anneal(batch, K, cands, inv_temp, seed, int(max_descent_sweeps), terminals)
     return MaxCutResult(partition, cut, trained_cut, rounded_cut, batch.goff)

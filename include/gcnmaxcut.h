@@ -661,6 +661,52 @@ int gmc_inst_adam_f32(const gmc_batch *batch, int32_t F, int32_t K, float *param
                       double lr, double beta1, double beta2, double eps, int32_t step, const int32_t *stop_epoch,
                       gmc_stream_t stream);
 
+/* ---- one model per graph for graphs beyond GMC_MAX_GRAPH_NODES (extension) -------------------------------------------------
+ *
+ * gmc_inst_forward_t / gmc_inst_train_fwd_bwd_t for graphs of up to GMC_LARGE_MAX_GRAPH_NODES nodes: the same model
+ * descriptor (W1 [R,F], b1 [B,F], W2 [B,F,K], b2 [B,K], N == R), flat layout [W1 | b1 | W2 | b2], loss flag, `terminals`
+ * (1: nodes 0..K-1 of every graph fixed to classes 0..K-1; 0: no node fixed, a graph then needs one node) and empty-batch
+ * behaviour.  They take ANY batch within the bound, small graphs included; gmc_inst_* stays the faster sequence for the
+ * graphs it accepts, and no entry point routes a batch from one to the other.
+ *
+ * Kernel sequence of a training call (probe tag in brackets; the numbers are gmc_inst_*'s steps):
+ *  1. T0 = dinv o (A_val @ W1)        gmc_spmm_f32's kernel, then the rows of more than 64 entries once more      [GATHER_W1 x2]
+ *  2. Hpre = dinv o (A @ T0)          likewise                                                                    [AGG_FWD x2]
+ *  3. H = relu(Hpre + b1_g), Z0 = dinv o (H @ W2_g): gmc_inst_*'s row arithmetic (one wave per row, lane j columns j,
+ *     j + 64, ..., then the butterfly) on a grid of (graph, min(ceil(n_max / 4), 65535)) whose workgroup y takes the
+ *     graph's 4-row tiles y, y + gridDim.y, ...: H and Z0 are byte for byte gmc_inst_*'s                          [DENSE_MFMA]
+ *  4. the head of gmc_large_* (four launches on a grid of (graph, tile of 256 rows): probabilities and decode; the loss
+ *     terms and the softmax backward; the per-graph fold; GY2 = A @ (dinv o GZ)) with graph g's b2 read at b2 + g*K,
+ *     terms = terminals ? min(n_g, K) : 0 terminals - also what decides, in the relaxed loss, whether a neighbour is a
+ *     terminal - and the fold's per-graph sums of the softmax backward, which ARE db2_g, written straight into the
+ *     gradient.  A forward ends after the first three of the four                                                  [HEAD x4]
+ *  5. Gs and the tile partials of dW2_g, db1_g       gmc_inst_*'s kernel                                          [HIDDEN_BWD]
+ *  6. their fold                                     gmc_inst_*'s kernel                                          [COLSUM]
+ *  7. U = dinv o (A @ Gs)             gmc_spmm_f32's kernel, then the rows of more than 64 entries once more      [AGG_BWD x2]
+ *  8. dW1 = A_val @ U                 likewise                                                                    [DW1 x2]
+ * Summation orders: a row of at most 64 entries in CSR order by its lane; a longer row (a hub) in the head by its wave
+ * (lane j entries j, j + 64, ..., then the butterfly over the lanes), in the four F-wide sums of steps 1, 2, 7, 8 as its
+ * first 64 entries plus, one after the other, the sum of each further 64 (each in CSR order); a tile's K + 1 head sums
+ * by the wave butterfly over its rows, then its four waves ascending; a graph's sums by its tiles ascending.  (The
+ * one-workgroup head of gmc_inst_* deals a graph's rows over 1024 / 512 threads instead: the two agree in S and to
+ * rounding in P, loss and gradient, not to the bit.)  No float atomics, no waiting between workgroups; a graph's results
+ * have the same bits wherever it stands in the batch and are bitwise reproducible.
+ *
+ * Argument checks: all before any HIP call, in the order of gmc_inst_*_t, with n_max > GMC_LARGE_MAX_GRAPH_NODES
+ * (GMC_ERR_GRAPH_SIZE) in the place of the one-workgroup head's bound, and W1 among the pointers that must be 16-byte
+ * aligned (GMC_ERR_ALIGN: the launches for the rows of more than 64 entries read it as float4 only).  Workspace: gmc_inst_*'s buffers (T0, H [R, ld],
+ * Z0 [R,K]; training: GY2 [R,K], the tile partials [R / 64 + B + 1][F][K+1]), then the decode Sw [R], the head's tile
+ * partials [R / 256 + B + 1][K+1] and - training - dinv o GZ [R,K], each rounded up to 256 bytes.
+ * Memory per node: the flat buffer, its gradient and two Adam moments 16 * F bytes, the workspace about 8 * ld bytes
+ * (ld = F rounded up to 32): about 1.5 KB at F = 64.  gmc_inst_adam_f32 keeps its own bound (n_max * F up to about 2^28);
+ * gmc_adam_f32 over the flat buffer has none. */
+size_t gmc_inst_large_workspace_bytes(const gmc_batch *batch, const gmc_model *model, int training);
+int gmc_inst_large_forward(const gmc_batch *batch, const gmc_model *model, int32_t terminals, float C, void *workspace,
+                           size_t workspace_bytes, float *P, int32_t *S, float *loss, gmc_stream_t stream);
+int gmc_inst_large_train_fwd_bwd(const gmc_batch *batch, const gmc_model *model, int32_t terminals, float C,
+                                 void *workspace, size_t workspace_bytes, float *P, int32_t *S, float *loss, float *grad,
+                                 gmc_stream_t stream);
+
 /* ---- a graph-attention first layer (extension: the first of the "future improvements" of the reference's README) ------
  *
  * The entry points above have GraphConv(norm='both') as layer 1 (TrainingNeural.py:80).  These three replace that layer's
