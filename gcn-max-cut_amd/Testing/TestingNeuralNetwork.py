@@ -21,6 +21,9 @@ sampler, the local search and the annealing for ``number_classes`` in 2..8 (``gm
 class count.
 ``kway_evolution`` and ``search_dataset(..., generations=G)`` (extension) recombine the annealed candidates of a graph
 across generations (``gmc_kway_evolve_f32``): children of two class-aligned parents, annealed and kept when no worse.
+``kway_tabu_search`` and ``search_dataset(..., tabu_iterations=I)`` (extension) run a one-flip tabu search over
+partitions (``gmc_kway_tabu_f32``): the best single move every iteration, a recency ban with aspiration, the best state
+kept.  Off by default.
 ``large_conditional_rounding``, ``large_local_search``, ``round_large_dataset``, ``large_sampling_optimization``,
 ``large_annealing`` and ``search_large_dataset`` (extension) are the same rounding, local search, sampler and annealing
 for graphs of up to ``hip.LARGE_MAX_GRAPH_NODES`` nodes (``gmc_large_round_conditional_f32``,
@@ -789,6 +792,65 @@ def kway_annealing(partition_assignment, graph, number_classes: int, sweeps: int
     return best_assign.cpu().tolist(), _as_number(best_cut.item())
 
 
+# The tabu stage's tenure defaults are PROVISIONAL: the literature's 3 + rand(n / 10), taken over
+# as a starting point, not a measured choice.
+TABU_TENURE = (3, 0, 10)   # tenure_base, tenure_span, tenure_div
+
+
+def _tabu_arguments(what: str, iterations: int, tenure) -> Tuple[int, int, int]:
+    """The checks the tabu stage's callers share; returns (tenure_base, tenure_span, tenure_div)."""
+    base, span, div = (int(t) for t in tenure)
+    if not 0 <= int(iterations) < 1 << 31:
+        raise ValueError(f"{what}: iterations must be in 0..2^31-1, got {iterations}")
+    if min(base, span, div) < 0 or max(base, span, div) >= 1 << 31:
+        raise ValueError(f"{what}: tenure_base, tenure_span and tenure_div must be in 0..2^31-1, got {base}, {span}, {div}")
+    return base, span, div
+
+
+def _kway_tabu_on_gpu(batch: GraphBatch, K: int, assign: torch.Tensor, iterations: int, tenure, seed: int,
+                      terminals: bool = True):
+    """One-flip tabu search at K classes (gmc_kway_tabu_f32) over the candidates assign [cands, R] int8, in place:
+    ``iterations`` iterations per candidate with ``tenure`` = (tenure_base, tenure_span, tenure_div).  Returns the best
+    assignment [R], its cut and candidate index per graph, then best_iter and moves [B, cands] and cut_all [B, cands]."""
+    _needs_terminals(batch, K, terminals)
+    base, span, div = _tabu_arguments("the tabu search", iterations, tenure)
+    dev = batch.device
+    cands = int(assign.shape[0])
+    cut_all = torch.empty((batch.B, cands), dtype=torch.float32, device=dev)
+    best_assign = torch.empty(batch.R, dtype=torch.int32, device=dev)
+    best_cut = torch.empty(batch.B, dtype=torch.float32, device=dev)
+    best_idx = torch.empty(batch.B, dtype=torch.int32, device=dev)
+    best_iter = torch.empty((batch.B, cands), dtype=torch.int32, device=dev)
+    moves = torch.empty((batch.B, cands), dtype=torch.int32, device=dev)
+    p = hip.ptr
+    rc = hip.load().gmc_kway_tabu_f32(batch.ref(), K, 1 if terminals else 0, cands, p(assign), int(iterations), base,
+                                      span, div, int(seed) & _M64, p(cut_all), p(best_assign), p(best_cut), p(best_idx),
+                                      p(best_iter), p(moves), hip.stream())
+    hip.check(rc, "gmc_kway_tabu_f32")
+    return best_assign, best_cut, best_idx, best_iter, moves, cut_all
+
+
+def kway_tabu_search(partition_assignment, graph, number_classes: int, iterations: Optional[int] = None,
+                     tenure_base: int = 3, tenure_span: int = 0, tenure_div: int = 10, seed: int = 0,
+                     terminals: bool = True) -> Tuple[List[int], Any]:
+    """One-flip tabu search from a partition into ``number_classes`` = 2..8 classes (extension, include/gcnmaxcut.h
+    ``gmc_kway_tabu_f32``), the sibling of :func:`kway_annealing`: every iteration makes the best single move, the
+    moved node may not move again for ``tenure_base + rand(tenure_span + n_mov // tenure_div)`` iterations
+    (``tenure_div = 0``: no size term) unless moving it would beat the best cut seen, and the best state passed through
+    is returned.  ``iterations=None`` means ``20 * n``.  Nodes 0..K-1 keep their classes (``terminals=False``: every
+    node may move); for unit and integer weights the result is never worse than the input; reproducible from ``seed``.
+    The tenure defaults are the literature's ``3 + rand(n / 10)``, provisional: a starting point nobody has tuned, see
+    DESIGN.md section 30.  Returns the assignment and its cut value."""
+    K, part = _kway_partition("kway_tabu_search", partition_assignment, graph, number_classes, terminals)
+    iterations = 20 * graph.number_of_nodes() if iterations is None else int(iterations)
+    tenure = _tabu_arguments("kway_tabu_search", iterations, (tenure_base, tenure_span, tenure_div))
+    dev = hip.require_gpu()
+    batch = GraphBatch([from_networkx(graph)], None, dev)
+    assign = torch.from_numpy(part.astype(np.int8)).to(dev).reshape(1, -1)
+    best_assign, best_cut = _kway_tabu_on_gpu(batch, K, assign, iterations, tenure, seed, terminals)[:2]
+    return best_assign.cpu().tolist(), _as_number(best_cut.item())
+
+
 # The evolution stage's defaults are PROVISIONAL (DESIGN.md section 22): 10 generations of 10 sweeps cooling from 0.6
 # are a starting point nobody has measured yet, not the outcome of the sweep described there.
 EVOLVE_GENERATIONS = 10
@@ -1137,7 +1199,8 @@ def search_dataset(model, processed_graphs: Dict, samples: int = 200, *, sample_
                    anneal_seed: int = 0, max_descent_sweeps: int = 100,
                    candidates: Optional[int] = None, generations: int = 0,
                    generation_sweeps: int = EVOLVE_GENERATION_SWEEPS,
-                   elite: Optional[int] = None, terminals: bool = True) -> List[Dict[str, Any]]:
+                   elite: Optional[int] = None, terminals: bool = True, tabu_iterations: int = 0,
+                   tabu_seed: int = 0) -> List[Dict[str, Any]]:
     """Decode a whole dataset of a model of any ``number_classes`` in 2..8 with everything the 3-class path has
     (extension): ONE batched forward, ONE rounding launch (``round_dataset(..., 0)``), ONE launch of the seeded sampler
     (``gmc_kway_decode_sample_seeded_f32``, a graph's index its position in ``processed_graphs.values()``) and ONE
@@ -1156,7 +1219,13 @@ def search_dataset(model, processed_graphs: Dict, samples: int = 200, *, sample_
     more and adds no key.
     ``terminals=False``: plain max-K-cut - candidate 0 is the row argmax of P (first maximum, no row overridden), and
     the rounding, the sampler and the search fix no node.  The evolution stage keeps its terminals:
-    ``generations > 0`` then raises ``NotImplementedError``."""
+    ``generations > 0`` then raises ``NotImplementedError``.
+    ``tabu_iterations > 0``: ONE call of the tabu stage (``gmc_kway_tabu_f32``, :func:`kway_tabu_search`, the tenure
+    ``TABU_TENURE``, seeded by ``tabu_seed``) follows on a copy of the candidates the annealing (and the evolution, if
+    any) left, ``tabu_iterations`` iterations each, and each result gains ``tabu_cut``, ``tabu_assignment`` and
+    ``tabu_iteration`` (the iteration at which the winning chain found it; 0: its input).  No other key changes;
+    ``tabu_iterations = 0`` launches nothing more and adds no key."""
+    _tabu_arguments("search_dataset", tabu_iterations, TABU_TENURE)
     if not terminals and generations > 0:
         raise NotImplementedError("search_dataset(generations > 0, terminals=False): the evolution stage "
                                   "(gmc_kway_evolve_f32) keeps its terminals")
@@ -1197,10 +1266,18 @@ def search_dataset(model, processed_graphs: Dict, samples: int = 200, *, sample_
                                           _kway_anneal_on_gpu(batch, K, cands, inv_temp, anneal_seed, max_descent_sweeps,
                                                               terminals)]
     evolved = None
+    start = cands             # what the tabu stage starts from: the searched candidates, or the last population
     if generations > 0:   # the search left its candidates in `cands`: the population
         inv_temp = anneal_schedule(generation_sweeps, t_start=EVOLVE_T_START, scale=_mean_edge_weight(batch))
-        evolved = [t.cpu().numpy() for t in _kway_evolve_on_gpu(batch, K, cands, generations, elite, inv_temp,
-                                                                anneal_seed, max_descent_sweeps)[:4]]
+        ev = _kway_evolve_on_gpu(batch, K, cands, generations, elite, inv_temp, anneal_seed, max_descent_sweeps)
+        evolved = [t.cpu().numpy() for t in ev[:4]]
+        start = ev[4][generations & 1]
+    tabu = None
+    if tabu_iterations > 0:
+        tb_assign, tb_cut, tb_idx, tb_iter = _kway_tabu_on_gpu(batch, K, start.clone(), int(tabu_iterations), TABU_TENURE,
+                                                               tabu_seed, terminals)[:4]
+        tb_iter = tb_iter.gather(1, tb_idx.to(torch.int64).reshape(-1, 1)).reshape(-1)
+        tabu = [t.cpu().numpy() for t in (tb_assign, tb_cut, tb_iter)]
     S_host, simple = S.cpu().numpy(), (-loss).cpu().tolist()
     rnd_assign, rnd_cut, rnd_expected = rnd_assign.cpu().numpy(), rnd_cut.cpu().numpy(), rnd_expected.cpu().numpy()
     out = []
@@ -1214,9 +1291,12 @@ def search_dataset(model, processed_graphs: Dict, samples: int = 200, *, sample_
         out[-1].update({'searched_cut': _as_number(found_cut[g]), 'searched_assignment': found_assign[lo:hi].tolist(),
                         'searched_from': int(found_idx[g])})
         if evolved is not None:
-            ev_assign, ev_cut, _, ev_history = evolved
+            ev_assign, ev_cut, _, ev_history = evolved[:4]
             out[-1].update({'evolved_cut': _as_number(ev_cut[g]), 'evolved_assignment': ev_assign[lo:hi].tolist(),
                             'evolved_history': [_as_number(c) for c in ev_history[:, g].tolist()]})
+        if tabu is not None:
+            out[-1].update({'tabu_cut': _as_number(tabu[1][g]), 'tabu_assignment': tabu[0][lo:hi].tolist(),
+                            'tabu_iteration': int(tabu[2][g])})
     return out
 
 

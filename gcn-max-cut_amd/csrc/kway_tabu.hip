@@ -1,0 +1,407 @@
+// One-flip tabu search over decoded partitions at K = 2..8 classes (an extension: the reference samples and stops):
+// gmc_kway_tabu_f32, stated to the operation in include/gcnmaxcut.h.  A chain is one (candidate, graph) pair; every
+// iteration takes the best admissible single move, forbids moving that node again for a while and lets a move that
+// would beat the best cut seen override the ban.
+//
+// One WAVE per chain, so the iteration loop holds no workgroup barrier: lane j owns the movable nodes first + j,
+// first + j + 64, ...  The chain's state is private to its wave, in LDS:
+//
+//   W      [n_pad][K] float   the class sums of every node, kept up to date move by move   (n_pad = n_max up to 16)
+//   until  [n_pad] uint32     the first iteration at which the node may move again
+//   state  [n_pad] byte       the classes as they stand
+//   snap   [n_pad] byte       the state of the largest cut so far
+//
+// n_pad * (4 K + 6) bytes per chain.  A 256-thread workgroup runs 4, 2 or 1 chains of ONE graph (tabu_layout: as many
+// as fit), which share one staged copy of the graph's CSR in anneal_stage_csr's layout (starts, ids as uint16, vals);
+// when the copy does not fit beside one chain, the chains read the batch's arrays in global memory - one template
+// over LdsCsr / GlobalCsr (anneal_layout.h), so the arithmetic cannot differ.  The waves without a chain (slots < 4,
+// or the last workgroup of a graph) wait at the closing barrier.
+//
+// An iteration: each lane scans its nodes (the W row, the class byte, until) for its best admissible move as ONE
+// 64-bit key - the gain mapped to an order-preserving uint32 in the high half, ~(rank * K + k) in the low half; keys
+// are unique, 0 means "none".  A node enters with its own best move only (the largest gain, the smallest k on ties: one
+// subtraction and one compare per class, one key per node), and the scan has a wave-uniform trip count with
+// unconditional loads, unrolled by two, so that the LDS reads of two nodes are in flight together - the first form, a
+// key per (node, class) behind a branch on the class byte, took 4.0 us per iteration at n = 1000, K = 2 and 19.9 at
+// K = 8, this one 2.6 and 10.6 (unrolled by four the compiler spilled 36 bytes of scratch).
+// Then a 64-lane max butterfly on the VALU (v_permlane32/16_swap + DPP, as gmc::xor_add) gives
+// every lane the winner, which is read straight from the key; then one lane per edge of the winner's row updates the
+// neighbours' W rows (a row holds a neighbour once, so the read-modify-writes need no atomics).  The wave's own LDS
+// traffic is ordered by wavefront-scope fences and wave barriers: no __syncthreads() inside the loop.
+//
+// The snapshot copy is deferred: an improving move only marks it pending; the state is copied before the first move
+// that does not improve (and at the end), which gives the same bytes as copying at every improvement.
+//
+// After the chains the whole workgroup scores each of its snapshots with gmc::block_cut - 256 threads, the summation
+// order of every other decoder, so the reported cuts carry the same bits - and writes them back; the second launch is
+// the pick.  (The scoring is the tail of the chain launch and not a launch of its own: the pick needs every cut of a
+// graph, so scoring and picking cannot share a launch without communication between workgroups, and this way the
+// call stays at two launches with the snapshots scored out of LDS.)
+#include "gmc_common.h"
+#include "cut_body.h"
+#include "mix64.h"
+#include "move_body.h"
+#include "anneal_layout.h"
+
+#define GMC_TABU_LDS_BYTES (160 * 1024)   // the LDS of a CU
+#define GMC_TABU_LDS_STATIC 512           // allowance for red and the pick's word (16 B as built)
+
+namespace {
+
+using gmc::mix64;
+using gmc::u64;
+using gmc::GlobalCsr;
+using gmc::LdsCsr;
+
+// LDS of a launch: `slots` chains of chain_bytes each, then the staged copy.  Depends on n_max, nnz_max, vals and K.
+struct TabuLayout {
+    int fits;      // one chain's state fits a CU's LDS (and n_max is in 1..GMC_MAX_GRAPH_NODES)
+    int slots;     // chains per workgroup: 4, 2 or 1
+    int staged;    // the launch has room for the copy of the graph's CSR
+    int n_pad, chain_bytes, off_starts, off_vals, off_ids, bytes;
+};
+inline TabuLayout tabu_layout(const gmc_batch *b, int K) {
+    TabuLayout L{};
+    const long cap = GMC_TABU_LDS_BYTES - GMC_TABU_LDS_STATIC;
+    const long n_max = b->n_max > 0 ? b->n_max : 0;
+    const long n_pad = (n_max + 15) & ~15L;
+    const long chain = n_pad * (4 * K + 6);
+    L.fits = n_max >= 1 && n_max <= GMC_MAX_GRAPH_NODES && chain <= cap;
+    if (!L.fits) return L;
+    const long nnz = b->nnz_max > 0 ? b->nnz_max : 0;
+    const long starts = ((n_max + 1) * 4 + 15) & ~15L;
+    const long vals = b->vals ? (nnz * 4 + 15) & ~15L : 0;
+    const long ids = (nnz * 2 + 15) & ~15L;
+    const long csr = starts + vals + ids;
+    L.staged = nnz > 0 && chain + csr <= cap;
+    const long room = cap - (L.staged ? csr : 0);
+    L.slots = 4 * chain <= room ? 4 : 2 * chain <= room ? 2 : 1;
+    L.n_pad = (int)n_pad;
+    L.chain_bytes = (int)chain;
+    L.off_starts = L.slots * L.chain_bytes;
+    L.off_vals = L.off_starts + (int)starts;
+    L.off_ids = L.off_vals + (int)vals;
+    L.bytes = L.staged ? L.off_ids + (int)ids : L.off_starts;
+    return L;
+}
+
+struct TabuArgs {
+    gmc_batch b;
+    int first;               // first movable local id: K with terminals, 0 without
+    int cands, iterations;
+    unsigned tenure_base, tenure_span, tenure_div;
+    u64 seed;
+    signed char *assign;     // [cands][R], in/out
+    float *cut_all;          // [B][cands]
+    int *best_iter;          // [B][cands] or NULL
+    int *moves;              // [B][cands] or NULL
+    int slots, staged, n_pad, chain_bytes, off_starts, off_vals, off_ids;
+};
+
+// orders the wave's own LDS traffic: what its lanes wrote before is what they read after
+__device__ __forceinline__ void wave_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// max(key[lane], key[lane ^ O]) of a 64-bit key on the VALU: the exchanges of gmc::xor_add on both halves
+template <int O>
+__device__ __forceinline__ u64 xor_max(u64 key) {
+    const unsigned hi = (unsigned)(key >> 32), lo = (unsigned)key;
+    u64 other;
+    if constexpr (O == 32) {
+        const auto rh = __builtin_amdgcn_permlane32_swap(hi, hi, false, false);
+        const auto rl = __builtin_amdgcn_permlane32_swap(lo, lo, false, false);
+        key = ((u64)rh[0] << 32) | rl[0];   // one of the two is the lane's own, the other its partner's
+        other = ((u64)rh[1] << 32) | rl[1];
+    } else if constexpr (O == 16) {
+        const auto rh = __builtin_amdgcn_permlane16_swap(hi, hi, false, false);
+        const auto rl = __builtin_amdgcn_permlane16_swap(lo, lo, false, false);
+        key = ((u64)rh[0] << 32) | rl[0];
+        other = ((u64)rh[1] << 32) | rl[1];
+    } else if constexpr (O == 4) {
+        unsigned th = __builtin_amdgcn_update_dpp(hi, hi, 0x104 /* row_shl:4 */, 0xf, 0x5, false);
+        th = __builtin_amdgcn_update_dpp(th, hi, 0x114 /* row_shr:4 */, 0xf, 0xa, false);
+        unsigned tl = __builtin_amdgcn_update_dpp(lo, lo, 0x104, 0xf, 0x5, false);
+        tl = __builtin_amdgcn_update_dpp(tl, lo, 0x114, 0xf, 0xa, false);
+        other = ((u64)th << 32) | tl;
+    } else {
+        static_assert(O == 8 || O == 2 || O == 1, "lane distance");
+        constexpr int ctrl = O == 8 ? 0x128 /* row_ror:8 */ : O == 2 ? 0x4e /* quad_perm:[2,3,0,1] */ : 0xb1 /* [1,0,3,2] */;
+        const unsigned th = __builtin_amdgcn_update_dpp(0u, hi, ctrl, 0xf, 0xf, false);
+        const unsigned tl = __builtin_amdgcn_update_dpp(0u, lo, ctrl, 0xf, 0xf, false);
+        other = ((u64)th << 32) | tl;
+    }
+    return other > key ? other : key;
+}
+__device__ __forceinline__ u64 wave_max(u64 key) {
+    key = xor_max<32>(key);
+    key = xor_max<16>(key);
+    key = xor_max<8>(key);
+    key = xor_max<4>(key);
+    key = xor_max<2>(key);
+    return xor_max<1>(key);
+}
+
+// float -> uint32 with the order of the floats (no NaN); -0.0 does not arise: a sum that starts at +0.0 and only adds
+// and subtracts in round-to-nearest never becomes -0.0, nor does a difference of two such sums
+__device__ __forceinline__ unsigned ordered_bits(float f) {
+    const unsigned u = __float_as_uint(f);
+    return u ^ ((u >> 31) ? 0xffffffffu : 0x80000000u);
+}
+__device__ __forceinline__ float ordered_float(unsigned o) {
+    return __uint_as_float(o ^ ((o >> 31) ? 0x80000000u : 0xffffffffu));
+}
+
+// One chain on the calling wave: the table, the iterations, the snapshot left in sn.  lds: the chain's bytes.
+template <int K, class G>
+__device__ __forceinline__ void tabu_chain(const TabuArgs &a, const G &g, unsigned char *lds, int n, int cand,
+                                           const signed char *in, int &best_it_out, int &moves_out) {
+    const int lane = gmc::lane_id();
+    float *W = reinterpret_cast<float *>(lds);
+    unsigned *until = reinterpret_cast<unsigned *>(lds + (size_t)a.n_pad * K * 4);
+    unsigned char *st = lds + (size_t)a.n_pad * (K * 4 + 4);
+    unsigned char *sn = st + a.n_pad;
+    const int first = a.first;
+    const int n_mov = n - first;
+    for (int l = lane; l < n; l += GMC_WAVE) {
+        const unsigned char c = (unsigned char)in[l];
+        st[l] = c;
+        sn[l] = c;
+        until[l] = 0u;
+    }
+    int best_it = 0, moves = 0;
+    if (a.iterations > 0 && n_mov > 0) {
+        wave_sync();
+        for (int l = lane; l < n; l += GMC_WAVE) {
+            const gmc::Sums<K> s = gmc::class_sums_k<K>(g.rp, g.col, g.vals, st, l);
+#pragma unroll
+            for (int k = 0; k < K; ++k) W[l * K + k] = s.m[k];
+        }
+        wave_sync();
+        float rel = 0.0f, best = 0.0f;
+        bool pending = false;   // the state is better than the snapshot and not copied yet
+        const unsigned span = a.tenure_span + (a.tenure_div > 0 ? (unsigned)n_mov / a.tenure_div : 0u);
+        const u64 base = a.seed + GMC_GOLD * (((u64)(unsigned)cand << 32) + 1ULL);   // it < 2^32 only adds
+        const int trips = (n_mov + GMC_WAVE - 1) / GMC_WAVE;   // scan steps of a lane
+        for (int it = 0; it < a.iterations; ++it) {
+            const u64 h = mix64(base + GMC_GOLD * (u64)(unsigned)it);
+            const int r = (int)((unsigned)h % (unsigned)n_mov);
+            const unsigned tenure_draw = (unsigned)(h >> 32) % (span + 1u);
+            // 2-3. the lane's best admissible move
+            // (a wave-uniform trip count and unconditional loads from a clamped node, so that the unrolled steps' LDS
+            // reads go out together: a lane past its last node reads node `first` and admits nothing)
+            u64 key = 0;
+#pragma unroll 2
+            for (int t = 0; t < trips; ++t) {
+                const int v0 = first + lane + (t << 6);
+                const bool valid = v0 < n;
+                const int v = valid ? v0 : first;
+                const unsigned c = st[v];
+                float w[K];
+#pragma unroll
+                for (int k = 0; k < K; ++k) w[k] = W[v * K + k];
+                float wc = w[0];
+#pragma unroll
+                for (int j = 1; j < K; ++j) wc = c == (unsigned)j ? w[j] : wc;
+                const bool is_free = until[v] <= (unsigned)it;
+                int rank = v - first - r;
+                rank = rank < 0 ? rank + n_mov : rank;
+                // the node's own best move - the largest gain, the smallest k on ties - stands for all its moves: when
+                // the node is banned, rel + gain is monotone in the gain, so if any of its moves is admissible this one is
+                float bg = -__builtin_inff();
+                int bk = 0;
+#pragma unroll
+                for (int k = 0; k < K; ++k) {
+                    const float gain = wc - w[k];
+                    const bool take = c != (unsigned)k && gain > bg;
+                    bg = take ? gain : bg;
+                    bk = take ? k : bk;
+                }
+                // (a byte of no class: the node never moves)
+                const bool adm = valid && c < (unsigned)K && (is_free || rel + bg > best);
+                const u64 cnd = ((u64)ordered_bits(bg) << 32) | (u64)(~(unsigned)(rank * K + bk));
+                key = adm && cnd > key ? cnd : key;
+            }
+            key = wave_max(key);
+            const unsigned khi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(key >> 32));
+            const unsigned klo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)key);
+            if (khi == 0u && klo == 0u) continue;   // no admissible move (wave-uniform)
+            const unsigned x = ~klo;
+            const int k = (int)(x % (unsigned)K);
+            int v = first + (int)(x / (unsigned)K) + r;
+            v = v - first >= n_mov ? v - n_mov : v;
+            const float gain = ordered_float(khi);
+            const float new_rel = rel + gain;
+            const bool improves = new_rel > best;
+            if (!improves && pending) {   // the snapshot takes the state before this move
+                const unsigned *s32 = reinterpret_cast<const unsigned *>(st);
+                unsigned *d32 = reinterpret_cast<unsigned *>(sn);
+                for (int i = lane; i < (a.n_pad >> 2); i += GMC_WAVE) d32[i] = s32[i];
+                pending = false;
+                wave_sync();
+            }
+            // 4. apply
+            const int c = st[v];
+            const int e1 = g.rp[v + 1];
+            for (int e = (int)g.rp[v] + lane; e < e1; e += GMC_WAVE) {
+                const int u = g.col[e];
+                if (u == v) continue;
+                const float wt = g.vals ? g.vals[e] : 1.0f;
+                W[u * K + c] -= wt;
+                W[u * K + k] += wt;
+            }
+            if (lane == 0) {
+                st[v] = (unsigned char)k;
+                const u64 u = (u64)(unsigned)it + 1ULL + (u64)a.tenure_base + (u64)tenure_draw;
+                until[v] = u > 0xffffffffULL ? 0xffffffffu : (unsigned)u;   // it < 2^31: saturated is "never again"
+            }
+            rel = new_rel;
+            ++moves;
+            // 5. best so far
+            if (improves) {
+                best = rel;
+                best_it = it + 1;
+                pending = true;
+            }
+            wave_sync();
+        }
+        if (pending) {
+            const unsigned *s32 = reinterpret_cast<const unsigned *>(st);
+            unsigned *d32 = reinterpret_cast<unsigned *>(sn);
+            for (int i = lane; i < (a.n_pad >> 2); i += GMC_WAVE) d32[i] = s32[i];
+        }
+    }
+    best_it_out = best_it;
+    moves_out = moves;
+}
+
+template <int K>
+__global__ __launch_bounds__(256) void tabu_kernel(TabuArgs a) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
+    __shared__ float red[4];
+    const int gi = blockIdx.y;
+    const int r0 = a.b.goff[gi];
+    const int n = a.b.goff[gi + 1] - r0;
+    if (n > a.b.n_max || n < (a.first > 1 ? a.first : 1)) return;   // (the LDS is sized by n_max; workgroup-uniform)
+    const int wave = gmc::uniform((int)(threadIdx.x >> 6));
+    const int cand0 = blockIdx.x * a.slots;
+    const int cand = cand0 + wave;
+    const int e0 = a.b.rowptr[r0];
+    const int nnz = a.b.rowptr[r0 + n] - e0;
+    // the copy is sized by n_max and nnz_max: a graph that contradicts them takes the global path
+    const bool staged = a.staged && nnz >= 0 && nnz <= a.b.nnz_max;   // workgroup-uniform
+    const bool runs = wave < a.slots && cand < a.cands;               // wave-uniform
+    int best_it = 0, moves = 0;
+    if (staged) {
+        int *starts = reinterpret_cast<int *>(lds + a.off_starts);
+        float *vals = a.b.vals ? reinterpret_cast<float *>(lds + a.off_vals) : nullptr;
+        unsigned short *ids = reinterpret_cast<unsigned short *>(lds + a.off_ids);
+        if (a.iterations > 0) {
+            for (int l = threadIdx.x; l <= n; l += blockDim.x) starts[l] = a.b.rowptr[r0 + l] - e0;
+            for (int e = threadIdx.x; e < nnz; e += blockDim.x) {
+                ids[e] = (unsigned short)a.b.lcol[e0 + e];
+                if (vals) vals[e] = a.b.vals[e0 + e];
+            }
+        }
+        __syncthreads();
+        if (runs) {
+            const LdsCsr g{starts, ids, vals, nullptr, 0};
+            tabu_chain<K>(a, g, lds + (size_t)wave * a.chain_bytes, n, cand, a.assign + (long)cand * a.b.R + r0,
+                          best_it, moves);
+        }
+    } else if (runs) {
+        const GlobalCsr g{a.b.rowptr + r0, a.b.lcol, a.b.vals, nullptr, r0, a.first};
+        tabu_chain<K>(a, g, lds + (size_t)wave * a.chain_bytes, n, cand, a.assign + (long)cand * a.b.R + r0,
+                      best_it, moves);
+    }
+    if (runs && gmc::lane_id() == 0) {
+        if (a.best_iter) a.best_iter[(long)gi * a.cands + cand] = best_it;
+        if (a.moves) a.moves[(long)gi * a.cands + cand] = moves;
+    }
+    __syncthreads();   // every chain of the workgroup has left its snapshot
+    // the result and its score, chain by chain, the whole workgroup on each: scored as gmc_refine_local_f32 scores
+    for (int s = 0; s < a.slots; ++s) {
+        const int cs = cand0 + s;
+        if (cs >= a.cands) break;   // workgroup-uniform
+        const unsigned char *sn = lds + (size_t)s * a.chain_bytes + (size_t)a.n_pad * (K * 4 + 5);
+        signed char *as = a.assign + (long)cs * a.b.R + r0;
+        for (int l = threadIdx.x; l < n; l += blockDim.x) as[l] = (signed char)sn[l];
+        const float cut = gmc::block_cut(a.b, sn, r0, n, red);
+        if (threadIdx.x == 0) a.cut_all[(long)gi * a.cands + cs] = cut;
+        __syncthreads();   // thread 0 has read red before the next recount writes it
+    }
+}
+
+struct TabuPickArgs {
+    gmc::PickArgs p;
+    int first;
+};
+__global__ __launch_bounds__(256) void tabu_pick_kernel(TabuPickArgs a) {
+    const int g = blockIdx.x;
+    const int n = a.p.b.goff[g + 1] - a.p.b.goff[g];
+    if (n > a.p.b.n_max || n < (a.first > 1 ? a.first : 1)) return;   // workgroup-uniform: the graphs the chains skipped
+    gmc::pick_best(a.p);
+}
+
+template <int K>
+int tabu_launch(const TabuArgs &a, int lds_bytes, hipStream_t st) {
+    if (lds_bytes > 64 * 1024) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(tabu_kernel<K>),
+                                           hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
+        if (e != hipSuccess) return (int)e;
+    }
+    GmcProbeScope probe(GMC_K_ANNEAL, st);
+    hipLaunchKernelGGL((tabu_kernel<K>), dim3((a.cands + a.slots - 1) / a.slots, a.b.B), dim3(256), (size_t)lds_bytes,
+                       st, a);
+    GMC_LAUNCH_CHECK();
+    return GMC_OK;
+}
+
+}  // namespace
+
+extern "C" int gmc_kway_tabu_fits(const gmc_batch *batch, int32_t K) {
+    if (!batch) return GMC_ERR_NULL;
+    if (batch->abi != GMC_VERSION) return GMC_ERR_ABI;
+    if (K < 2 || K > GMC_KWAY_MAX_CLASSES) return GMC_ERR_CLASSES;
+    return tabu_layout(batch, K).fits;
+}
+
+extern "C" int gmc_kway_tabu_shape(const gmc_batch *batch, int32_t K) {
+    if (!batch) return GMC_ERR_NULL;
+    if (batch->abi != GMC_VERSION) return GMC_ERR_ABI;
+    if (K < 2 || K > GMC_KWAY_MAX_CLASSES) return GMC_ERR_CLASSES;
+    const TabuLayout L = tabu_layout(batch, K);
+    if (!L.fits) return GMC_ERR_GRAPH_SIZE;
+    return L.slots | (L.staged << 4);
+}
+
+extern "C" int gmc_kway_tabu_f32(const gmc_batch *batch, int32_t K, int32_t terminals, int32_t cands, int8_t *assign,
+                                 int32_t iterations, int32_t tenure_base, int32_t tenure_span, int32_t tenure_div,
+                                 uint64_t seed, float *cut_all, int32_t *best_assign, float *best_cut,
+                                 int32_t *best_idx, int32_t *best_iter, int32_t *moves, gmc_stream_t stream) {
+    if (!batch || !assign || !cut_all || !best_assign || !best_cut || !best_idx) return GMC_ERR_NULL;
+    if (batch->abi != GMC_VERSION) return GMC_ERR_ABI;
+    if (!batch->goff || !batch->rowptr || !batch->lcol) return GMC_ERR_NULL;
+    if (K < 2 || K > GMC_KWAY_MAX_CLASSES) return GMC_ERR_CLASSES;
+    if (cands < 1 || iterations < 0 || tenure_base < 0 || tenure_span < 0 || tenure_div < 0 || batch->B < 0 ||
+        (terminals != 0 && terminals != 1))
+        return GMC_ERR_SHAPE;
+    const int first = terminals ? K : 0;
+    const TabuLayout L = tabu_layout(batch, K);
+    if (batch->B > 0 && (batch->n_max < (first > 1 ? first : 1) || !L.fits)) return GMC_ERR_GRAPH_SIZE;
+    if (batch->B == 0) return GMC_OK;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const TabuArgs a{*batch, first, cands, iterations, (unsigned)tenure_base, (unsigned)tenure_span,
+                     (unsigned)tenure_div, seed, reinterpret_cast<signed char *>(assign), cut_all, best_iter, moves,
+                     L.slots, L.staged, L.n_pad, L.chain_bytes, L.off_starts, L.off_vals, L.off_ids};
+    int rc = GMC_OK;
+    GMC_KWAY_DISPATCH(K, rc = tabu_launch<KK>(a, L.bytes, st));
+    if (rc != GMC_OK) return rc;
+    const TabuPickArgs p{{*batch, cands, reinterpret_cast<const signed char *>(assign), cut_all, best_assign, best_cut,
+                          best_idx}, first};
+    hipLaunchKernelGGL(tabu_pick_kernel, dim3(batch->B), dim3(256), 0, st, p);
+    GMC_LAUNCH_CHECK();
+    return GMC_OK;
+}

@@ -24,6 +24,7 @@ _TOO_LARGE = ("a graph of {n} nodes is beyond the one-workgroup head of the per-
               "train a model through gcn_max_cut_amd.functional (terminal-free up to 2^20 nodes) and decode it with "
               "search_large_dataset(..., terminals=False), or call maxcut.solve_large, which trains one model per graph up "
               "to 2^20 nodes")
+_NO_TABU = "the tabu stage keeps a graph's state in one workgroup: solve_large does not have it (tabu_iterations must be 0)"
 _BEYOND_LARGE = "a graph of {n} nodes is beyond the {bound} nodes of the per-graph models' large sequence (solve_large)"
 
 
@@ -35,12 +36,13 @@ class MaxCutResult:
     trained_cut: torch.Tensor   # [B] float32: the cut of the best partition training saw (``best_S``)
     rounded_cut: torch.Tensor   # [B] float32: the cut of the conditional rounding of the last P
     ptr: torch.Tensor           # [B + 1] int32
+    annealed_cut: Optional[torch.Tensor] = None   # [B] float32, with tabu_iterations > 0 only: the cut the annealing reached
 
 
 def solve(edge_index, ptr=None, num_nodes: Optional[int] = None, edge_weight=None, *, number_classes: int = 2,
           terminals: bool = False, pairs: str = "both", hidden_dim: int, epochs: int, learning_rate: float,
           loss: str = "expected_cut", samples: int = 32, anneal_sweeps: int = 100, max_descent_sweeps: int = 100,
-          seed: int = 0) -> MaxCutResult:
+          seed: int = 0, tabu_iterations: int = 0) -> MaxCutResult:
     """Max-K-cut of every graph of a batch given as ``edge_index`` [2, E] (with ``ptr`` [B+1], or ``num_nodes`` for one
     graph, ``edge_weight`` and ``pairs`` as ``GraphBatch.from_edge_index`` takes them).
 
@@ -53,6 +55,11 @@ def solve(edge_index, ptr=None, num_nodes: Optional[int] = None, edge_weight=Non
        Metropolis sweeps, then at most ``max_descent_sweeps`` sweeps of the local search) over the candidates: the best
        partition training saw, the rounded one and the samples.  ``cut`` is therefore never below ``trained_cut`` or
        ``rounded_cut``.
+    5. with ``tabu_iterations > 0`` only: one call of the tabu stage (``gmc_kway_tabu_f32``,
+       ``Testing.kway_tabu_search``; ``tabu_iterations`` iterations per candidate, seeded by ``seed``) on a copy of the
+       annealed candidates.  Per graph ``partition`` / ``cut`` are then the better of the annealed and the tabu result
+       by their recounted cuts, chosen on the device, and ``annealed_cut`` holds the annealed one: ``cut >=
+       annealed_cut``.  The default 0 launches nothing more and leaves ``annealed_cut`` None.
 
     ``terminals=False`` (default): no node is fixed.  ``terminals=True``: nodes 0..K-1 of every graph keep classes
     0..K-1, as everywhere else in this package.  The same arguments give the same bytes.
@@ -74,22 +81,22 @@ def solve(edge_index, ptr=None, num_nodes: Optional[int] = None, edge_weight=Non
     batch = GraphBatch.from_edge_index(edge_index, ptr, num_nodes, edge_weight, pairs=pairs)
     return solve_batch(batch, number_classes=K, terminals=terminals, hidden_dim=hidden_dim, epochs=epochs,
                        learning_rate=learning_rate, loss=loss, samples=samples, anneal_sweeps=anneal_sweeps,
-                       max_descent_sweeps=max_descent_sweeps, seed=seed)
+                       max_descent_sweeps=max_descent_sweeps, seed=seed, tabu_iterations=tabu_iterations)
 
 
 def solve_batch(batch: GraphBatch, *, number_classes: int = 2, terminals: bool = False, hidden_dim: int, epochs: int,
                 learning_rate: float, loss: str = "expected_cut", samples: int = 32, anneal_sweeps: int = 100,
-                max_descent_sweeps: int = 100, seed: int = 0) -> MaxCutResult:
-    """Steps 2 to 4 of :func:`solve` on a ready batch - one built on the device or one built from handles: the batches
+                max_descent_sweeps: int = 100, seed: int = 0, tabu_iterations: int = 0) -> MaxCutResult:
+    """Steps 2 to 5 of :func:`solve` on a ready batch - one built on the device or one built from handles: the batches
     hold the same bytes, so the results do too."""
     return _solve_batch(_small_route(), batch, number_classes, terminals, hidden_dim, epochs, learning_rate, loss, samples,
-                        anneal_sweeps, max_descent_sweeps, seed)
+                        anneal_sweeps, max_descent_sweeps, seed, tabu_iterations)
 
 
 def solve_large(edge_index, ptr=None, num_nodes: Optional[int] = None, edge_weight=None, *, number_classes: int = 2,
                 terminals: bool = False, pairs: str = "both", hidden_dim: int, epochs: int, learning_rate: float,
                 loss: str = "expected_cut", samples: int = 32, anneal_sweeps: int = 100, max_descent_sweeps: int = 100,
-                seed: int = 0) -> MaxCutResult:
+                seed: int = 0, tabu_iterations: int = 0) -> MaxCutResult:
     """:func:`solve` for graphs of up to ``hip.LARGE_MAX_GRAPH_NODES`` (2^20) nodes: the same arguments, steps and
     result, with ``engine.LargeInstanceEngine`` (gmc_inst_large_*) as the trainer and the large decoders (one rounding,
     one sampler and one annealing call of gmc_large_*_t_f32; several workgroups share a graph).  It takes small graphs
@@ -97,7 +104,11 @@ def solve_large(edge_index, ptr=None, num_nodes: Optional[int] = None, edge_weig
     every launch of ``anneal_sweeps`` + ``max_descent_sweeps`` sweeps whether or not the descent has converged, and the
     samples live on the device while they are scored (``samples`` + 2 bytes per node).  Memory while training: about
     16 * hidden_dim bytes per node for parameters, gradient and Adam moments plus 8 * ld for the workspace (ld =
-    hidden_dim rounded up to 32): 1.5 KB per node at hidden_dim = 64."""
+    hidden_dim rounded up to 32): 1.5 KB per node at hidden_dim = 64.  The tabu stage keeps a graph's state in one
+    workgroup, so this route does not have it: ``tabu_iterations`` is taken for the sake of one signature and anything
+    but 0 raises ``NotImplementedError``."""
+    if tabu_iterations:
+        raise NotImplementedError(_NO_TABU)
     K, terminals = int(number_classes), bool(terminals)
     if not 2 <= K <= hip.KWAY_MAX_CLASSES:
         raise ValueError(f"number_classes must be in 2..{hip.KWAY_MAX_CLASSES}, got {K}")
@@ -105,28 +116,31 @@ def solve_large(edge_index, ptr=None, num_nodes: Optional[int] = None, edge_weig
     batch = GraphBatch.from_edge_index(edge_index, ptr, num_nodes, edge_weight, pairs=pairs)
     return solve_large_batch(batch, number_classes=K, terminals=terminals, hidden_dim=hidden_dim, epochs=epochs,
                              learning_rate=learning_rate, loss=loss, samples=samples, anneal_sweeps=anneal_sweeps,
-                             max_descent_sweeps=max_descent_sweeps, seed=seed)
+                             max_descent_sweeps=max_descent_sweeps, seed=seed, tabu_iterations=tabu_iterations)
 
 
 def solve_large_batch(batch: GraphBatch, *, number_classes: int = 2, terminals: bool = False, hidden_dim: int,
                       epochs: int, learning_rate: float, loss: str = "expected_cut", samples: int = 32,
-                      anneal_sweeps: int = 100, max_descent_sweeps: int = 100, seed: int = 0) -> MaxCutResult:
+                      anneal_sweeps: int = 100, max_descent_sweeps: int = 100, seed: int = 0,
+                      tabu_iterations: int = 0) -> MaxCutResult:
     """:func:`solve_batch` through ``engine.LargeInstanceEngine`` and the large decoders: steps 2 to 4 of
-    :func:`solve_large` on a ready batch."""
+    :func:`solve_large` on a ready batch (``tabu_iterations``: as :func:`solve_large`)."""
     return _solve_batch(_large_route(), batch, number_classes, terminals, hidden_dim, epochs, learning_rate, loss, samples,
-                        anneal_sweeps, max_descent_sweeps, seed)
+                        anneal_sweeps, max_descent_sweeps, seed, tabu_iterations)
 
 
 @dataclass
 class _Route:
     """What tells :func:`solve_batch` from :func:`solve_large_batch`: the engine class, the refusal of a batch by its
     largest graph, and the three decoders as ``round(batch, P, terminals)``, ``sample(batch, P, samples, seed, terminals)``
-    and ``anneal(batch, K, cands, inv_temp, seed, max_descent_sweeps, terminals)``."""
+    and ``anneal(batch, K, cands, inv_temp, seed, max_descent_sweeps, terminals)``; ``tabu(batch, K, cands, iterations,
+    seed, terminals)`` where the route has the stage."""
     engine: type
     refuse: Callable
     round: Callable
     sample: Callable
     anneal: Callable
+    tabu: Optional[Callable] = None
 
 
 def _small_route() -> _Route:
@@ -140,7 +154,9 @@ def _small_route() -> _Route:
                   lambda batch, P, t: T._round_on_gpu(batch, P, 0, t),
                   lambda batch, P, n, seed, t: T._kway_sample_on_gpu(batch, P, n, seed, range(batch.B), True, t)[3],
                   lambda batch, K, cands, inv_temp, seed, sweeps, t: T._kway_anneal_on_gpu(batch, K, cands, inv_temp, seed,
-                                                                                           sweeps, t))
+                                                                                           sweeps, t),
+                  lambda batch, K, cands, iterations, seed, t: T._kway_tabu_on_gpu(batch, K, cands, iterations,
+                                                                                   T.TABU_TENURE, seed, t))
 
 
 def _large_route() -> _Route:
@@ -160,7 +176,7 @@ def _large_route() -> _Route:
 
 def _solve_batch(route: _Route, batch: GraphBatch, number_classes: int, terminals: bool, hidden_dim: int, epochs: int,
                  learning_rate: float, loss: str, samples: int, anneal_sweeps: int, max_descent_sweeps: int,
-                 seed: int) -> MaxCutResult:
+                 seed: int, tabu_iterations: int = 0) -> MaxCutResult:
     from .Testing import TestingNeuralNetwork as T
     K, terminals = int(number_classes), bool(terminals)
     if not 2 <= K <= hip.KWAY_MAX_CLASSES:
@@ -168,6 +184,10 @@ def _solve_batch(route: _Route, batch: GraphBatch, number_classes: int, terminal
     if epochs < 0 or samples < 0 or anneal_sweeps < 0 or max_descent_sweeps < 0:
         raise ValueError(f"epochs, samples, anneal_sweeps and max_descent_sweeps must be >= 0, got {epochs}, {samples}, "
                          f"{anneal_sweeps}, {max_descent_sweeps}")
+    if not 0 <= int(tabu_iterations) < 1 << 31:
+        raise ValueError(f"tabu_iterations must be in 0..2^31-1, got {tabu_iterations}")
+    if tabu_iterations and route.tabu is None:
+        raise NotImplementedError(_NO_TABU)
     loss = hip.loss_name(loss)
     if batch.B:
         route.refuse(batch.n_max, K, loss)
@@ -195,4 +215,12 @@ def _solve_batch(route: _Route, batch: GraphBatch, number_classes: int, terminal
     cands = torch.cat(rows).contiguous()
     inv_temp = T.anneal_schedule(int(anneal_sweeps), scale=T._mean_edge_weight(batch))
     partition, cut, _ = route.anneal(batch, K, cands, inv_temp, seed, int(max_descent_sweeps), terminals)
-    return MaxCutResult(partition, cut, trained_cut, rounded_cut, batch.goff)
+    if not tabu_iterations:
+        return MaxCutResult(partition, cut, trained_cut, rounded_cut, batch.goff)
+    # the annealing left its candidates in `cands`; the better of the two results per graph, chosen on the device
+    tabu_partition, tabu_cut = route.tabu(batch, K, cands.clone(), int(tabu_iterations), seed, terminals)[:2]
+    better = tabu_cut > cut
+    sizes = (batch.goff[1:] - batch.goff[:-1]).to(torch.int64)
+    rows = torch.repeat_interleave(better, sizes, output_size=batch.R)
+    return MaxCutResult(torch.where(rows, tabu_partition, partition), torch.where(better, tabu_cut, cut), trained_cut,
+                        rounded_cut, batch.goff, cut)

@@ -1101,6 +1101,76 @@ int gmc_kway_evolve_f32(const gmc_batch *batch, int32_t K, const int32_t *order,
                         int32_t *best_assign, float *best_cut, int32_t *best_idx, float *history /*or NULL*/,
                         gmc_stream_t stream);
 
+/* ---- one-flip tabu search over decoded partitions (extension; K = 2 .. GMC_KWAY_MAX_CLASSES) --------------------------
+ *
+ * The annealing proposes random moves under a temperature and remembers nothing.  This stage is the other classic move
+ * rule of the max-cut literature: every iteration takes the BEST single move, forbids moving that node again for a
+ * while (the tenure), and lets a move that would beat the best cut seen so far override the ban (aspiration).
+ *
+ * One chain is one (candidate `cand`, graph) pair and is independent of every other chain.  first = terminals ? K : 0;
+ * the movable nodes are the local ids first..n-1 and n_mov = n - first.  All float arithmetic is fp32 and every step
+ * named below is ONE fp32 operation (no multiply occurs, so no fused multiply-add can arise).  Integer arithmetic on
+ * uint64 is modulo 2^64; GOLD = 0x9E3779B97F4A7C15 and mix64 are those of gmc_refine_anneal_f32.
+ *
+ * Table.  W[v][k], k = 0..K-1, v = 0..n-1: the sum, in the CSR order of v's row, of the weights of v's edges to
+ *   neighbours of class k, starting from +0.0f; self-loops skipped, unit weights when batch->vals is NULL (the sums of
+ *   gmc_kway_refine_anneal_f32, the same code).  Computed once, from the input state.  A class byte outside 0..K-1
+ *   counts for no class (it adds to no sum and receives no update), and a movable node that holds one never moves:
+ *   it keeps its byte.  (The annealing moves such a node at once; here it is inert.  The Python wrappers pass none.)
+ * Running values.  rel = 0.0f (the sum of the gains taken), best = 0.0f, best_it = 0, snapshot = the input state,
+ *   until[v] = 0 for every v.
+ * Iteration it = 0..iterations-1:
+ *   1. h = mix64(seed + GOLD * (((uint64)cand << 32 | it) + 1));  r = (uint32)h mod n_mov;
+ *      span = tenure_span + (tenure_div > 0 ? n_mov / tenure_div : 0)  (integer division);
+ *      tenure = tenure_base + (uint32)(h >> 32) mod (span + 1).
+ *   2. For every movable v whose byte c = class(v) is in 0..K-1 and every k != c:  gain = W[v][c] - W[v][k].  The move
+ *      (v, k) is admissible iff until[v] <= it, or rel + gain > best.
+ *   3. Among the admissible moves the largest gain wins (compared as floats); ties go to the smallest
+ *      rank = (v - first - r) mod n_mov (v - first - r + n_mov when negative), then to the smallest k.  With no
+ *      admissible move the iteration moves nothing and steps 4 and 5 are skipped.
+ *   4. class(v) = k.  For every edge (v, u, w) of v's row with u != v:  W[u][c] = W[u][c] - w, W[u][k] = W[u][k] + w.
+ *      Then rel = rel + gain and until[v] = it + 1 + tenure (as an unbounded integer).
+ *   5. If rel > best:  best = rel, best_it = it + 1, and the snapshot becomes the state.
+ * Result.  The snapshot goes back into `assign`; best_iter [B][cands] (or NULL) receives best_it and moves [B][cands]
+ *   (or NULL) the number of iterations that moved a node.  Every candidate is then scored as gmc_refine_local_f32
+ *   scores (fp32, the same code, the same bits the sampler, the local search and the annealing report for the same
+ *   bytes) into cut_all [B][cands], and picked as it picks (strictly best, first on ties): best_assign [R] int32,
+ *   best_cut [B], best_idx [B].  iterations == 0 scores and picks only.
+ * A row must hold a neighbour at most once (a simple graph, self-loops aside): the updates of step 4 are made by one
+ *   lane per edge without atomics.  For a row that repeats a neighbour nothing is claimed.
+ * By construction.  For unit and integer weights every sum is exact while it stays below 2^24 in magnitude; the cut of
+ *   the result is then the input's cut plus `best`, so it is never below the input's, and when best_it < iterations
+ *   the result is a local optimum under single moves of its movable nodes (a move of positive gain from the best
+ *   state is admissible by aspiration and would have been taken at iteration best_it).  For other weights the table drifts by rounding:
+ *   the result is then whatever the recount says and nothing stronger is claimed.  A chain depends on its graph, the
+ *   input bytes, cand, seed and the five parameters - not on the batch, the graph's place in it, or cands.
+ *
+ * Argument checks, before any HIP call, in the order of gmc_kway_refine_anneal_t_f32: a NULL required pointer
+ * (best_iter and moves aside) GMC_ERR_NULL, batch->abi GMC_ERR_ABI, a NULL goff / rowptr / lcol GMC_ERR_NULL, K outside
+ * 2..GMC_KWAY_MAX_CLASSES GMC_ERR_CLASSES, cands < 1, iterations < 0 (so iterations < 2^31), a negative tenure
+ * argument, B < 0 or terminals outside {0, 1} GMC_ERR_SHAPE, n_max < max(first, 1) or a batch gmc_kway_tabu_fits
+ * refuses GMC_ERR_GRAPH_SIZE; B == 0 returns GMC_OK without a launch.  A graph with fewer than max(first, 1) or more
+ * than n_max nodes inside a batch is skipped: nothing of it is written.
+ *
+ * One wave per chain; a 256-thread workgroup runs 4, 2 or 1 chains of one graph, as many as fit, which share one copy
+ * of the graph's CSR in LDS when it fits beside them and read the batch's arrays otherwise (one code path over both).
+ * With n_pad = n_max rounded up to 16 a chain keeps n_pad * (4 K + 6) bytes of LDS: W, until, the state and the
+ * snapshot.  gmc_kway_tabu_fits is 1 iff n_max is in 1..GMC_MAX_GRAPH_NODES and n_pad * (4 K + 6) + 512 <= 160 KiB -
+ * at K <= 8 that is every n_max up to GMC_MAX_GRAPH_NODES (K = 8: 4096 * 38 + 512 = 156,160 B) - else 0 (NULL
+ * GMC_ERR_NULL, abi GMC_ERR_ABI, K GMC_ERR_CLASSES).  gmc_kway_tabu_shape tells what the launcher chose for a batch
+ * and K: chains per workgroup (4, 2 or 1) + 16 if the CSR copy is staged in LDS; GMC_ERR_GRAPH_SIZE where
+ * gmc_kway_tabu_fits is 0.  The call allocates nothing and does not synchronise: two launches on the caller's stream
+ * (the chains, whose workgroups also score their snapshots; the pick), no atomics, no spin waits, no scratch, bitwise
+ * reproducible. */
+int gmc_kway_tabu_f32(const gmc_batch *batch, int32_t K, int32_t terminals, int32_t cands,
+                      int8_t *assign /*[cands][R], in/out*/, int32_t iterations, int32_t tenure_base,
+                      int32_t tenure_span, int32_t tenure_div, uint64_t seed, float *cut_all /*[B][cands]*/,
+                      int32_t *best_assign /*[R]*/, float *best_cut /*[B]*/, int32_t *best_idx /*[B]*/,
+                      int32_t *best_iter /*[B][cands] or NULL*/, int32_t *moves /*[B][cands] or NULL*/,
+                      gmc_stream_t stream);
+int gmc_kway_tabu_fits(const gmc_batch *batch, int32_t K);
+int gmc_kway_tabu_shape(const gmc_batch *batch, int32_t K);
+
 /* ---- the rounding and the K-class local search beyond GMC_MAX_GRAPH_NODES (extension) ---------------------------------
  *
  * gmc_round_conditional_f32 and gmc_kway_refine_anneal_f32 keep a graph's state in one workgroup's LDS and stop at
