@@ -220,6 +220,153 @@ def from_edge_index(edge_index, num_nodes: int, edge_weight=None, pairs: str = "
                        None if bool(np.all(ww == 1.0)) else ww)
 
 
+def _check_pins(nodes, classes, number_classes) -> int:
+    """Shapes and dtypes of a pin list (``nodes`` [P], ``classes`` [P]; numpy or torch) and the class count; returns P.
+    Touches neither the library nor a device."""
+    K = int(number_classes)
+    if not 2 <= K <= hip.KWAY_MAX_CLASSES:
+        raise ValueError(f"number_classes must be in 2..{hip.KWAY_MAX_CLASSES}, got {K}")
+    for name, a in (("nodes", nodes), ("classes", classes)):
+        shape = getattr(a, "shape", None)
+        if shape is None or len(tuple(shape)) != 1:
+            raise ValueError(f"{name} must be a one-dimensional array, got {type(a).__name__}"
+                             + ("" if shape is None else f" of shape {tuple(shape)}"))
+        if not _integer_dtype(a.dtype):
+            raise ValueError(f"{name} must hold integers, got {a.dtype}")
+    if tuple(nodes.shape) != tuple(classes.shape):
+        raise ValueError(f"nodes and classes must have one length, got {tuple(nodes.shape)} and {tuple(classes.shape)}")
+    return int(nodes.shape[0])
+
+
+def _pin_ids(a, top: int, device) -> torch.Tensor:
+    """A pin list's ids or classes as contiguous int32 on ``device``.  Values beyond int32 must not wrap into range, so
+    anything but int32 is clamped to -1..``top`` first - both are refused on the device - and clamped as int64: neither
+    bound need fit a narrow dtype, and a uint64 beyond int64 turns negative."""
+    if not isinstance(a, torch.Tensor):
+        a = np.asarray(a)
+        if a.dtype != np.int32:
+            a = np.clip(a.astype(np.int64), -1, top).astype(np.int32)
+        a = torch.from_numpy(np.ascontiguousarray(a))
+    a = a.to(device)
+    return (a if a.dtype == torch.int32 else a.to(torch.int64).clamp(-1, top).to(torch.int32)).contiguous()
+
+
+def _pin_faults(rep: dict, K: int) -> None:
+    """Raise ``ValueError`` for a contraction report (``hip.CT_REPORT`` names -> counts) with bad input in it."""
+    kinds = [("pin_out_of_range", "{} pins with a node id out of range"),
+             ("pin_class", "{} pins with a class outside 0.." + str(K - 1)),
+             ("pin_conflict", "{} nodes pinned to two different classes"),
+             ("graphs_missing_class", "{} graphs in which some class has no pinned node (pin every class in every graph: "
+                                      "a class without a pin has no terminal to stand for it)"),
+             ("graphs_no_free", "{} graphs without a free node (nothing is left to solve)"),
+             ("bare_terminals", "{} (graph, class) pairs whose pinned nodes have no free neighbour (pin a node with a free "
+                                "neighbour in that class: the class's terminal would be a node without neighbours)")]
+    found = [text.format(rep[k]) for k, text in kinds if rep[k]]
+    if found:
+        raise ValueError("pins: " + "; ".join(found))
+
+
+def _sequential_sums(keys: np.ndarray, w: np.ndarray):
+    """``(distinct keys, float32 sums)`` of ``w`` grouped by the ascending ``keys``: every sum starts at +0 and adds its
+    group's weights one after the other in array order (the k-th step of every group in one vector operation)."""
+    if keys.size == 0:
+        return keys[:0], np.zeros(0, np.float32)
+    first = np.flatnonzero(np.concatenate([[True], keys[1:] != keys[:-1]]))
+    length = np.diff(np.concatenate([first, [keys.size]]))
+    sums = np.zeros(first.size, np.float32)
+    for k in range(int(length.max())):
+        m = length > k
+        sums[m] = sums[m] + w[first[m] + k]
+    return keys[first], sums
+
+
+def _fold_fixed_cut(t: np.ndarray) -> np.float32:
+    """The fixed-shape fold of include/gcnmaxcut.h over one graph's per-row sums ``t`` [n] (float32): tiles of 256 rows,
+    a butterfly over each quarter of 64, the quarters in order, the tiles in order."""
+    tiles = (t.size + 255) // 256
+    v = np.zeros(tiles * 256, np.float32)
+    v[:t.size] = t
+    v = v.reshape(tiles, 4, 64)
+    lane = np.arange(64)
+    for d in (32, 16, 8, 4, 2, 1):
+        v = v + v[:, :, lane ^ d]
+    q = v[:, :, 0]
+    part = ((q[:, 0] + q[:, 1]) + q[:, 2]) + q[:, 3]
+    return np.cumsum(np.concatenate([np.zeros(1, np.float32), part]), dtype=np.float32)[-1]
+
+
+class HostContraction:
+    """What :func:`contract` returns: ``handle`` (the contracted graph), ``node_map`` [n] int32, ``fixed_cut`` (float32),
+    ``pinned`` [n] bool, and ``lift``."""
+
+    def __init__(self, handle: GraphHandle, node_map: np.ndarray, fixed_cut: np.float32, pinned: np.ndarray):
+        self.handle, self.node_map, self.fixed_cut, self.pinned = handle, node_map, fixed_cut, pinned
+
+    def lift(self, partition) -> np.ndarray:
+        """The partition of the original nodes a partition of the contracted graph stands for."""
+        return np.asarray(partition)[self.node_map].astype(np.int32)
+
+
+def contract(handle: GraphHandle, nodes, classes, number_classes: int) -> HostContraction:
+    """Contract the pinned nodes of one graph on the host, in vectorised numpy: the host twin of
+    ``GraphBatch.contract`` and the rule of include/gcnmaxcut.h ("pinning any nodes to classes") array for array.
+    ``nodes`` [P] are node ids of ``handle``, ``classes`` [P] their classes in 0..number_classes-1 (numpy or CPU torch, any
+    integer dtype, any order; a repeated identical pin is harmless).  Every node pinned to class c becomes node c of the
+    result, the free nodes follow in ascending order from ``number_classes``, parallel edges are merged by adding their
+    weights, edges between pinned nodes of different classes add up to ``fixed_cut``.  Bad pins raise ``ValueError``
+    naming the kind and the count, as ``GraphBatch.contract`` does."""
+    _check_pins(nodes, classes, number_classes)
+    K, n = int(number_classes), handle.n
+    as_np = lambda a: a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
+    nd, cl = as_np(nodes), as_np(classes)
+    # (compared as Python-sized integers: no id wraps into range)
+    node_ok = (nd >= 0) & (nd < n)
+    class_ok = (cl >= 0) & (cl < K)
+    rep = dict.fromkeys(hip.CT_REPORT, 0)
+    rep["pin_out_of_range"] = int((~node_ok).sum())
+    rep["pin_class"] = int((node_ok & ~class_ok).sum())
+    ok = node_ok & class_ok
+    pairs = np.unique(nd[ok].astype(np.int64) * K + cl[ok].astype(np.int64))
+    pin_node, pin_class = pairs // K, pairs % K
+    rep["pin_conflict"] = int((np.unique(pin_node, return_counts=True)[1] > 1).sum())
+    cls = np.full(n, -1, np.int64)
+    cls[pin_node[::-1]] = pin_class[::-1]   # (with a conflict: the smallest class; the call raises below anyway)
+    free = cls < 0
+    rows, cols = handle.row_index(), handle.col.astype(np.int64)
+    w = np.ones(cols.size, np.float32) if handle.weight is None else handle.weight
+    row_free, col_free = free[rows], free[cols]
+    present = np.zeros(K, bool)
+    present[cls[~free]] = True
+    touched = np.zeros(K, bool)
+    touched[cls[cols[row_free & ~col_free]]] = True
+    rep["graphs_missing_class"] = int(not present.all())
+    rep["graphs_no_free"] = int(not free.any())
+    rep["bare_terminals"] = int((present & ~touched).sum())
+    _pin_faults(rep, K)
+    new_id = np.where(free, K + np.cumsum(free) - 1, cls)
+    ff = row_free & col_free
+    fp = np.flatnonzero(row_free & ~col_free)
+    key = rows[fp] * K + cls[cols[fp]]
+    order = np.argsort(key, kind="stable")   # a (row, class) group keeps its ascending columns
+    groups, sums = _sequential_sums(key[order], w[fp][order])
+    v, c = new_id[groups // K], groups % K
+    out_rows = np.concatenate([new_id[rows[ff]], v, c])
+    out_cols = np.concatenate([new_id[cols[ff]], c, v])
+    out_w = np.concatenate([w[ff], sums, sums])
+    order = np.lexsort((out_cols, out_rows))
+    out_rows, out_cols, out_w = out_rows[order], out_cols[order], out_w[order]
+    n_out = K + int(free.sum())
+    rowptr = np.zeros(n_out + 1, np.int64)
+    np.cumsum(np.bincount(out_rows, minlength=n_out), out=rowptr[1:])
+    pp = np.flatnonzero(~row_free & ~col_free & (cols > rows) & (cls[rows] != cls[cols]))
+    t = np.zeros(n, np.float32)
+    at, per_row = _sequential_sums(rows[pp], w[pp])
+    t[at] = per_row
+    out = GraphHandle(n_out, rowptr.astype(np.int32), out_cols.astype(np.int32),
+                      None if bool(np.all(out_w == 1.0)) else out_w.astype(np.float32))
+    return HostContraction(out, new_id.astype(np.int32), _fold_fixed_cut(t), ~free)
+
+
 class BatchArrays:
     """Host-side (numpy) form of a block-diagonal batch: everything ``struct gmc_batch``
     points to, built without touching a GPU (so the layout is testable on CPU)."""
@@ -514,6 +661,55 @@ class GraphBatch:
             ovf_max_blocks=ovf_max_blocks)
         return self
 
+    def contract(self, nodes, classes, number_classes: int) -> "Contraction":
+        """Pin ``nodes`` [P] (global row ids of this batch) to ``classes`` [P] (0..number_classes-1) and contract them on
+        the GPU: every node pinned to class c of a graph becomes local node c of the contracted graph, the free nodes
+        follow in ascending order, parallel edges are merged by adding their weights (the rule and its sum orders:
+        include/gcnmaxcut.h, "pinning any nodes to classes").  The result's ``batch`` is the problem ``terminals=True``
+        solves; ``lift`` carries a partition of it back to this batch's rows, and the cut of the lifted partition is the
+        contracted one plus ``fixed_cut``.
+
+        ``nodes`` / ``classes``: any integer dtype, numpy or torch, on the CPU or the device, in any order; a repeated
+        identical pin is harmless.  Shapes, dtypes and ``number_classes`` outside 2..8 raise ``ValueError`` before the
+        library is loaded.  What only the data can tell is counted on the device and raises ``ValueError`` naming the kind
+        and the count before the entries are emitted: ids or classes out of range (such a pin is never used as an index),
+        a node pinned to two classes, a graph in which some class has no pin (a graph without pins included), a graph
+        without a free node, and a class of a graph whose pinned nodes have no free neighbour.
+
+        Synchronisation: the call waits for the device once, to read the report and the contracted graphs' offsets (one
+        copy); ``GraphBatch.from_edge_index``, which builds ``batch`` from the emitted entries, then reads its own
+        report."""
+        P = _check_pins(nodes, classes, number_classes)
+        K, B, R, device = int(number_classes), self.B, self.R, self.device
+        lib = hip.load()
+
+        pin_node, pin_class = _pin_ids(nodes, R, device), _pin_ids(classes, K, device)
+        new = lambda shape, dtype: torch.empty(shape, dtype=dtype, device=device)
+        words = new(hip.CT_REPORT_WORDS + B + 1, torch.int32)   # the report and goff_out: read back in one copy
+        report, goff_out = words[:hip.CT_REPORT_WORDS], words[hip.CT_REPORT_WORDS:]
+        node_map, fixed_cut = new(R, torch.int32), new(B, torch.float32)
+        if B == 0:
+            empty = GraphBatch.from_edge_index(new((2, 0), torch.int32), np.zeros(1, np.int64), device=device)
+            return Contraction(empty, node_map, fixed_cut, new(R, torch.bool))
+        ws = new(int(lib.gmc_contract_workspace_bytes(B, R, self.nnz, K)), torch.uint8)
+        rc = lib.gmc_contract_map(self.ref(), K, P, hip.ptr(pin_node), hip.ptr(pin_class), hip.ptr(node_map),
+                                  hip.ptr(goff_out), hip.ptr(report), hip.ptr(ws), ws.numel(), hip.stream())
+        hip.check(rc, "gmc_contract_map")
+        host = words.cpu().numpy()   # the call's one wait for the device
+        rep = dict(zip(hip.CT_REPORT, host[:hip.CT_REPORT_WORDS].tolist()))
+        _pin_faults(rep, K)
+        E = rep["nnz"]
+        entries, w = new((2, E), torch.int32), new(E, torch.float32)
+        rc = lib.gmc_contract_entries(self.ref(), K, hip.ptr(node_map), hip.ptr(goff_out), E, hip.ptr(entries[0]),
+                                      hip.ptr(entries[1]), hip.ptr(w), hip.ptr(fixed_cut), hip.ptr(ws), ws.numel(),
+                                      hip.stream())
+        hip.check(rc, "gmc_contract_entries")
+        batch = GraphBatch.from_edge_index(entries, host[hip.CT_REPORT_WORDS:].astype(np.int64), edge_weight=w,
+                                           device=device)
+        # pinned rows sit in the first K rows of their contracted graph (a binary search per row over goff_out)
+        first = goff_out[torch.bucketize(node_map, goff_out[1:], right=True).clamp_(max=B - 1)]
+        return Contraction(batch, node_map, fixed_cut, node_map < first + K)
+
     def __getattr__(self, name):
         # only reached for attributes the instance lacks: a batch built on the device has no ``host`` until it is asked for
         if name == "host" and "_scalars" in self.__dict__:
@@ -603,3 +799,17 @@ class GraphBatch:
     def spmm_bytes(self, F: int) -> int:
         """Algorithmic HBM bytes of one F-wide SpMM over this batch."""
         return 2 * self.R * F * 4 + self.nnz * 4 + (self.R + 1) * 4 + 2 * self.R * 4 + F * 4
+
+
+class Contraction:
+    """What ``GraphBatch.contract`` returns, all on the device: ``batch`` (the contracted graphs as an ordinary
+    ``GraphBatch``: local nodes 0..K-1 of every graph are the classes' super-nodes), ``node_map`` [R] int32 (the row of
+    ``batch`` every original row went to), ``fixed_cut`` [B] float32 (the weight of the edges between pinned nodes of
+    different classes), ``pinned`` [R] bool, and ``lift``."""
+
+    def __init__(self, batch: GraphBatch, node_map: torch.Tensor, fixed_cut: torch.Tensor, pinned: torch.Tensor):
+        self.batch, self.node_map, self.fixed_cut, self.pinned = batch, node_map, fixed_cut, pinned
+
+    def lift(self, partition: torch.Tensor) -> torch.Tensor:
+        """The [R] int32 partition of the original rows a partition of ``batch``'s rows stands for."""
+        return partition.to(torch.int32)[self.node_map.to(torch.int64)]

@@ -37,6 +37,12 @@ BB_REPORT = ("out_of_range", "cross_graph", "duplicate", "asymmetric", "zero_deg
              "rows_over_16", "excess_8", "excess_16", "row_blocks_8", "row_blocks_16", "graph_blocks_8", "graph_blocks_16",
              "blocks_8", "blocks_16", "non_unit", "nnz", "nnz_max")
 BB_REPORT_WORDS = 20  # GMC_BB_REPORT_WORDS
+# GMC_CT_*: the int32 words of the report gmc_contract_map leaves on the device (word k is CT_REPORT[k]); any of the first
+# CT_BAD_WORDS non-zero is bad input
+CT_REPORT = ("pin_out_of_range", "pin_class", "pin_conflict", "graphs_missing_class", "graphs_no_free", "bare_terminals",
+             "nnz", "pinned")
+CT_BAD_WORDS = 6
+CT_REPORT_WORDS = 8  # GMC_CT_REPORT_WORDS
 ABI_VERSION = 200    # GMC_VERSION of include/gcnmaxcut.h these struct layouts follow (checked at load and per call)
 
 
@@ -186,6 +192,9 @@ def _api() -> dict:
         "gmc_batch_build_workspace_bytes": (sz, [i32, i32, i64]),
         "gmc_batch_build_csr": (i, [i32, i32, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]),
         "gmc_batch_build_table": (i, [i32, i32, i32, vp, vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, i32, vp, sz, vp]),
+        "gmc_contract_workspace_bytes": (sz, [i32, i32, i64, i32]),
+        "gmc_contract_map": (i, [B, i32, i64, vp, vp, vp, vp, vp, vp, sz, vp]),
+        "gmc_contract_entries": (i, [B, i32, vp, vp, i64, vp, vp, vp, vp, vp, sz, vp]),
         # the terminals optional: the entry points above with `terminals` (0 or 1) after the class count / the model
         "gmc_order_host_t": (i, [i32, vp, vp, vp, i32, i32, vp, vp, vp, i32, vp]),
         "gmc_round_conditional_t_f32": (i, [B, vp, i32, i32, vp, vp, vp, i32, vp, vp, vp, vp, vp]),

@@ -17,7 +17,7 @@ import torch
 
 from . import hip
 from .engine import InstanceEngine, LargeInstanceEngine, instance_too_large
-from .graph import GraphBatch
+from .graph import GraphBatch, _check_pins
 
 
 _TOO_LARGE = ("a graph of {n} nodes is beyond the one-workgroup head of the per-graph models (number_classes = {K}): "
@@ -37,12 +37,14 @@ class MaxCutResult:
     rounded_cut: torch.Tensor   # [B] float32: the cut of the conditional rounding of the last P
     ptr: torch.Tensor           # [B + 1] int32
     annealed_cut: Optional[torch.Tensor] = None   # [B] float32, with tabu_iterations > 0 only: the cut the annealing reached
+    fixed_cut: Optional[torch.Tensor] = None      # [B] float32, with fixed only: the weight of the edges between pinned
+    #                                               nodes of different classes (a constant of every partition)
 
 
 def solve(edge_index, ptr=None, num_nodes: Optional[int] = None, edge_weight=None, *, number_classes: int = 2,
           terminals: bool = False, pairs: str = "both", hidden_dim: int, epochs: int, learning_rate: float,
           loss: str = "expected_cut", samples: int = 32, anneal_sweeps: int = 100, max_descent_sweeps: int = 100,
-          seed: int = 0, tabu_iterations: int = 0) -> MaxCutResult:
+          seed: int = 0, tabu_iterations: int = 0, fixed=None) -> MaxCutResult:
     """Max-K-cut of every graph of a batch given as ``edge_index`` [2, E] (with ``ptr`` [B+1], or ``num_nodes`` for one
     graph, ``edge_weight`` and ``pairs`` as ``GraphBatch.from_edge_index`` takes them).
 
@@ -64,6 +66,16 @@ def solve(edge_index, ptr=None, num_nodes: Optional[int] = None, edge_weight=Non
     ``terminals=False`` (default): no node is fixed.  ``terminals=True``: nodes 0..K-1 of every graph keep classes
     0..K-1, as everywhere else in this package.  The same arguments give the same bytes.
 
+    ``fixed=(nodes, classes)``: any nodes pinned to classes - ``nodes`` [P] global ids as in ``edge_index``, ``classes``
+    [P] in 0..K-1, as ``GraphBatch.contract`` takes them; every class needs a pin in every graph.  The pinned nodes are
+    contracted on the GPU (``GraphBatch.contract``), the steps above run on the contracted batch with its K super-nodes
+    as terminals, and the result is lifted: ``partition`` and ``ptr`` are the original graph's, ``cut``, ``trained_cut``,
+    ``rounded_cut`` (and ``annealed_cut``) are recounts of the lifted partitions on the original batch, ``fixed_cut``
+    holds the weight of the edges between pinned nodes of different classes, and the size refusal below is judged on
+    the contracted sizes: a graph of up to ``hip.LARGE_MAX_GRAPH_NODES`` nodes is taken when enough of it is pinned,
+    and its cuts are then recounted by the large decoders' scoring call (the cut order of ``solve_large``; the same
+    number for unit and integer weights).  ``fixed`` together with ``terminals=True`` raises ``ValueError``.
+
     A graph beyond the one-workgroup head of the per-graph models raises ``ValueError``: for such a graph train a model
     through ``gcn_max_cut_amd.functional`` (terminal-free up to 2^20 nodes) and decode it with
     ``search_large_dataset(..., terminals=False)``."""
@@ -71,32 +83,33 @@ def solve(edge_index, ptr=None, num_nodes: Optional[int] = None, edge_weight=Non
     if not 2 <= K <= hip.KWAY_MAX_CLASSES:
         raise ValueError(f"number_classes must be in 2..{hip.KWAY_MAX_CLASSES}, got {K}")
     loss = hip.loss_name(loss)
+    _check_fixed(fixed, terminals, K)
     if ptr is not None:   # judged before anything is built: the sizes are all it takes
         p = ptr.detach().cpu().numpy() if isinstance(ptr, torch.Tensor) else np.asarray(ptr)
         n_max = int(np.diff(p.astype(np.int64)).max()) if p.ndim == 1 and p.size > 1 else 0
     else:
         n_max = int(num_nodes) if num_nodes is not None else 0
-    if n_max > 0 and instance_too_large(n_max, K, loss):
+    if fixed is None and n_max > 0 and instance_too_large(n_max, K, loss):   # (with pins: the contracted sizes decide)
         raise ValueError(_TOO_LARGE.format(n=n_max, K=K))
     batch = GraphBatch.from_edge_index(edge_index, ptr, num_nodes, edge_weight, pairs=pairs)
     return solve_batch(batch, number_classes=K, terminals=terminals, hidden_dim=hidden_dim, epochs=epochs,
                        learning_rate=learning_rate, loss=loss, samples=samples, anneal_sweeps=anneal_sweeps,
-                       max_descent_sweeps=max_descent_sweeps, seed=seed, tabu_iterations=tabu_iterations)
+                       max_descent_sweeps=max_descent_sweeps, seed=seed, tabu_iterations=tabu_iterations, fixed=fixed)
 
 
 def solve_batch(batch: GraphBatch, *, number_classes: int = 2, terminals: bool = False, hidden_dim: int, epochs: int,
                 learning_rate: float, loss: str = "expected_cut", samples: int = 32, anneal_sweeps: int = 100,
-                max_descent_sweeps: int = 100, seed: int = 0, tabu_iterations: int = 0) -> MaxCutResult:
+                max_descent_sweeps: int = 100, seed: int = 0, tabu_iterations: int = 0, fixed=None) -> MaxCutResult:
     """Steps 2 to 5 of :func:`solve` on a ready batch - one built on the device or one built from handles: the batches
-    hold the same bytes, so the results do too."""
-    return _solve_batch(_small_route(), batch, number_classes, terminals, hidden_dim, epochs, learning_rate, loss, samples,
-                        anneal_sweeps, max_descent_sweeps, seed, tabu_iterations)
+    hold the same bytes, so the results do too.  ``fixed``: as :func:`solve`, with row ids of ``batch``."""
+    return _solve_fixed(_small_route(), batch, fixed, number_classes, terminals, hidden_dim, epochs, learning_rate, loss,
+                        samples, anneal_sweeps, max_descent_sweeps, seed, tabu_iterations)
 
 
 def solve_large(edge_index, ptr=None, num_nodes: Optional[int] = None, edge_weight=None, *, number_classes: int = 2,
                 terminals: bool = False, pairs: str = "both", hidden_dim: int, epochs: int, learning_rate: float,
                 loss: str = "expected_cut", samples: int = 32, anneal_sweeps: int = 100, max_descent_sweeps: int = 100,
-                seed: int = 0, tabu_iterations: int = 0) -> MaxCutResult:
+                seed: int = 0, tabu_iterations: int = 0, fixed=None) -> MaxCutResult:
     """:func:`solve` for graphs of up to ``hip.LARGE_MAX_GRAPH_NODES`` (2^20) nodes: the same arguments, steps and
     result, with ``engine.LargeInstanceEngine`` (gmc_inst_large_*) as the trainer and the large decoders (one rounding,
     one sampler and one annealing call of gmc_large_*_t_f32; several workgroups share a graph).  It takes small graphs
@@ -113,20 +126,63 @@ def solve_large(edge_index, ptr=None, num_nodes: Optional[int] = None, edge_weig
     if not 2 <= K <= hip.KWAY_MAX_CLASSES:
         raise ValueError(f"number_classes must be in 2..{hip.KWAY_MAX_CLASSES}, got {K}")
     loss = hip.loss_name(loss)
+    _check_fixed(fixed, terminals, K)
     batch = GraphBatch.from_edge_index(edge_index, ptr, num_nodes, edge_weight, pairs=pairs)
     return solve_large_batch(batch, number_classes=K, terminals=terminals, hidden_dim=hidden_dim, epochs=epochs,
                              learning_rate=learning_rate, loss=loss, samples=samples, anneal_sweeps=anneal_sweeps,
-                             max_descent_sweeps=max_descent_sweeps, seed=seed, tabu_iterations=tabu_iterations)
+                             max_descent_sweeps=max_descent_sweeps, seed=seed, tabu_iterations=tabu_iterations,
+                             fixed=fixed)
 
 
 def solve_large_batch(batch: GraphBatch, *, number_classes: int = 2, terminals: bool = False, hidden_dim: int,
                       epochs: int, learning_rate: float, loss: str = "expected_cut", samples: int = 32,
                       anneal_sweeps: int = 100, max_descent_sweeps: int = 100, seed: int = 0,
-                      tabu_iterations: int = 0) -> MaxCutResult:
+                      tabu_iterations: int = 0, fixed=None) -> MaxCutResult:
     """:func:`solve_batch` through ``engine.LargeInstanceEngine`` and the large decoders: steps 2 to 4 of
-    :func:`solve_large` on a ready batch (``tabu_iterations``: as :func:`solve_large`)."""
-    return _solve_batch(_large_route(), batch, number_classes, terminals, hidden_dim, epochs, learning_rate, loss, samples,
-                        anneal_sweeps, max_descent_sweeps, seed, tabu_iterations)
+    :func:`solve_large` on a ready batch (``tabu_iterations``: as :func:`solve_large`; ``fixed``: as :func:`solve_batch`)."""
+    return _solve_fixed(_large_route(), batch, fixed, number_classes, terminals, hidden_dim, epochs, learning_rate, loss,
+                        samples, anneal_sweeps, max_descent_sweeps, seed, tabu_iterations)
+
+
+def _check_fixed(fixed, terminals: bool, number_classes: int) -> None:
+    """The argument errors of ``fixed``, raised before anything is built."""
+    if fixed is None:
+        return
+    if terminals:
+        raise ValueError("fixed pins the nodes it names and terminals=True pins nodes 0..K-1 of every graph: pass one of "
+                         "the two (add nodes 0..K-1 to fixed to have both)")
+    if not isinstance(fixed, (tuple, list)) or len(fixed) != 2:
+        raise ValueError("fixed must be a pair (nodes, classes)")
+    _check_pins(fixed[0], fixed[1], number_classes)
+
+
+def _solve_fixed(route: "_Route", batch: GraphBatch, fixed, number_classes: int, terminals: bool, *args) -> MaxCutResult:
+    """:func:`_solve_batch`, or with ``fixed``: contract, solve the contracted batch with its super-nodes as terminals, lift,
+    and recount every reported cut on the original batch (the route's annealing call with zero sweeps and no terminals
+    moves nothing and scores: the bits every other decoder reports for those bytes).  The route is chosen by the
+    contracted sizes, the recount by the original ones: an original graph beyond ``hip.MAX_GRAPH_NODES`` nodes is
+    scored by the large sequence's call, the only decoders that take it."""
+    if fixed is None:
+        return _solve_batch(route, batch, number_classes, terminals, *args)
+    K = int(number_classes)
+    _check_fixed(fixed, bool(terminals), K)
+    ct = batch.contract(fixed[0], fixed[1], K)
+    parts = {}
+    res = _solve_batch(route, ct.batch, K, True, *args, parts=parts)
+    no_sweeps = np.zeros(0, np.float32)
+    score = _large_route().anneal if batch.B and batch.n_max > hip.MAX_GRAPH_NODES else route.anneal
+
+    def recount(partition):
+        return score(batch, K, partition.to(torch.int8).reshape(1, -1).contiguous(), no_sweeps, 0, 0, False)[1]
+
+    partition = ct.lift(res.partition)
+    if batch.B == 0:
+        return MaxCutResult(partition, res.cut, res.trained_cut, res.rounded_cut, batch.goff, fixed_cut=ct.fixed_cut)
+    # the cuts of the contracted run differ from the original graph's by fixed_cut; for weights that are not integers the
+    # sum of the two need not carry the bits of a recount, so every cut is recounted from its lifted partition
+    return MaxCutResult(partition, recount(partition), recount(ct.lift(parts["trained"])),
+                        recount(ct.lift(parts["rounded"])), batch.goff,
+                        recount(ct.lift(parts["annealed"])) if "annealed" in parts else None, ct.fixed_cut)
 
 
 @dataclass
@@ -176,7 +232,8 @@ def _large_route() -> _Route:
 
 def _solve_batch(route: _Route, batch: GraphBatch, number_classes: int, terminals: bool, hidden_dim: int, epochs: int,
                  learning_rate: float, loss: str, samples: int, anneal_sweeps: int, max_descent_sweeps: int,
-                 seed: int, tabu_iterations: int = 0) -> MaxCutResult:
+                 seed: int, tabu_iterations: int = 0, parts: Optional[dict] = None) -> MaxCutResult:
+    """``parts``: a dict that receives the partitions behind ``trained_cut``, ``rounded_cut`` (and ``annealed_cut``)."""
     from .Testing import TestingNeuralNetwork as T
     K, terminals = int(number_classes), bool(terminals)
     if not 2 <= K <= hip.KWAY_MAX_CLASSES:
@@ -215,6 +272,10 @@ def _solve_batch(route: _Route, batch: GraphBatch, number_classes: int, terminal
     cands = torch.cat(rows).contiguous()
     inv_temp = T.anneal_schedule(int(anneal_sweeps), scale=T._mean_edge_weight(batch))
     partition, cut, _ = route.anneal(batch, K, cands, inv_temp, seed, int(max_descent_sweeps), terminals)
+    if parts is not None:
+        parts.update(trained=best_S, rounded=rounded)
+        if tabu_iterations:
+            parts.update(annealed=partition)
     if not tabu_iterations:
         return MaxCutResult(partition, cut, trained_cut, rounded_cut, batch.goff)
     # the annealing left its candidates in `cands`; the better of the two results per graph, chosen on the device

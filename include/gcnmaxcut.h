@@ -1455,6 +1455,86 @@ int gmc_inst_train_fwd_bwd_t(const gmc_batch *batch, const gmc_model *model, int
                              void *workspace, size_t workspace_bytes, float *P, int32_t *S, float *loss, float *grad,
                              gmc_stream_t stream);
 
+/* ---- pinning any nodes to classes: contraction on the device -----------------------------------------------------------
+ * `terminals = 1` above means "local nodes 0..K-1 of every graph sit in classes 0..K-1".  Any other set of pinned nodes
+ * (several per class, anywhere in the graph) is brought to that form by contracting every node pinned to class c into one
+ * super-node c.  The rule, for graph g with n nodes, pinned set Pi with classes c(u), and free nodes F = V \ Pi in
+ * ascending local id:
+ *
+ *   size         n' = K + |F| nodes.
+ *   numbering    local id c is the super-node of class c; the free node of rank r in F gets local id K + r.
+ *   node_map     node_map[row] = goff'[g] + (c(u) if pinned else K + rank), goff'[g] = K g + free rows before graph g.
+ *   free-free    an entry (v, x, w) with both ends free is kept as (v', x', w); a self-loop on a free node is kept once.
+ *   free-pinned  for a free v and a class c with at least one entry (v, u), u in Pi_c, the two entries (v', c, s) and
+ *                (c, v', s): s is the float32 sum that starts at +0 and adds those entries' weights one after the other
+ *                in ascending u (for unit weights: their count).  s is computed once and stored twice - both directions
+ *                carry the same bits, as gmc_batch_build_csr demands - and the entries are kept whatever s is, 0 from
+ *                signed weights included.
+ *   pinned-pinned  no entry, and no self-loop on a pinned node.
+ *   fixed_cut[g] the sum of w over undirected edges {u, x} with both ends pinned and c(u) != c(x), each edge once, in
+ *                this order: (1) per pinned row u, t_u = +0 plus the weights of its entries (u, x) with x pinned, x > u
+ *                and c(x) != c(u), one after the other in ascending x (free rows: t_u = 0); (2) per tile of 256
+ *                consecutive rows of the graph, the first tile starting at the graph's first row (rows beyond the graph:
+ *                0): the 64 values of each quarter are summed by a butterfly - v[i] <- v[i] + v[i ^ d] for d = 32, 16, 8,
+ *                4, 2, 1 - and the four quarter sums q0..q3 give the tile's partial ((q0 + q1) + q2) + q3; (3) the graph's
+ *                partials are added to +0 one after the other in ascending tile order.  All in float32.
+ *
+ * For every assignment p' of g' with p'[c] = c, cut_g(lift(p')) = cut_g'(p') + fixed_cut[g], lift(p')[row] =
+ * p'[node_map[row]]: exact for integer weights while every sum stays below 2^24, to rounding otherwise.  The contracted
+ * graph is what the library solves with terminals = 1.  A class without a pinned node in some graph (a graph without pins
+ * included) has no super-node to stand for: that is bad input here, as is a super-node without a free neighbour (every
+ * GraphConv path refuses its zero-degree row).
+ *
+ * Both stages read the sorted CSR of a gmc_batch (goff, rowptr, gcol, vals or NULL; B, R, nnz, n_max; n_max up to
+ * GMC_LARGE_MAX_GRAPH_NODES), so "ascending u" is a row's own order.  All pointers are device memory; nothing is
+ * allocated; the workspace is caller-owned, need not be zeroed, and carries the class words and offsets from
+ * gmc_contract_map to gmc_contract_entries (the same buffer, untouched in between); kernel boundaries are the only
+ * synchronisation; no scratch, no floating-point atomics; any order of the pin list gives the same bytes.
+ *
+ * gmc_contract_map (7 launches: init, pins, count, a three-launch scan, finish) takes P pins (pin_node[p] a global row
+ * id, pin_class[p] its class), sets every row's class word from "free" with an integer compare-and-swap - a repeated
+ * identical pin is harmless - ranks the free rows per graph, counts and places every row's output entries, and writes
+ * node_map [R], goff_out [B+1] and the report.  The caller reads the report (one device-to-host copy) and decides: any of
+ * the first six words non-zero is bad input, and GMC_CT_NNZ is the E' <= nnz that sizes gmc_contract_entries' outputs.
+ *
+ * gmc_contract_entries (2 launches) writes the E' directed entries of the rule (src_out, dst_out as global ids of the
+ * contracted batch, w_out always, 1.0 for a batch without vals) in an order that is fixed for a given batch and pin set
+ * and otherwise of no account - gmc_batch_build_csr gives the same bytes for any order - and fixed_cut [B].  Entries at
+ * positions >= E_out are not written.  Row-length regimes: ONE - a thread walks its row's entries one after the other,
+ * whatever the row's length, with the K running sums in registers, so the sum order above holds by construction.  A free
+ * hub row therefore costs its length in dependent loads on one thread (a star of 2^20 - 1 leaves: see DESIGN.md
+ * section 31); the workloads here have short rows.
+ *
+ * Argument checks, before any HIP call, in this order: a NULL batch or required pointer (workspace included; the pin
+ * arrays when P > 0, the entry arrays when E_out > 0) GMC_ERR_NULL; batch->abi GMC_ERR_ABI; a NULL goff / rowptr / gcol
+ * (gcol: with nnz > 0) GMC_ERR_NULL; K outside 2..GMC_KWAY_MAX_CLASSES GMC_ERR_CLASSES; a negative B, R, nnz, n_max, P or E_out GMC_ERR_SHAPE;
+ * n_max beyond GMC_LARGE_MAX_GRAPH_NODES GMC_ERR_GRAPH_SIZE; a workspace below gmc_contract_workspace_bytes(B, R, nnz, K)
+ * GMC_ERR_WORKSPACE; B == 0 returns GMC_OK without a launch. */
+enum {
+    GMC_CT_PIN_OUT_OF_RANGE = 0,      /* pins with a node id outside 0..R-1 (skipped, never used as an index) */
+    GMC_CT_PIN_CLASS = 1,             /* pins with a class outside 0..K-1 (skipped) */
+    GMC_CT_PIN_CONFLICT = 2,          /* nodes that were given two different classes */
+    GMC_CT_GRAPHS_MISSING_CLASS = 3,  /* graphs in which some class has no pinned node */
+    GMC_CT_GRAPHS_NO_FREE = 4,        /* graphs without a free node */
+    GMC_CT_BARE_TERMINALS = 5,        /* (graph, class) pairs with pinned nodes none of which has a free neighbour */
+    GMC_CT_NNZ = 6,                   /* E': directed entries of the contracted batch, <= nnz */
+    GMC_CT_PINNED = 7,                /* pinned rows */
+    GMC_CT_REPORT_WORDS = 8
+};
+
+/* bytes of workspace both stages need (about 20 R + 12 B); 0 for negative sizes, E >= 2^31 or K outside 2..8; host only */
+size_t gmc_contract_workspace_bytes(int32_t B, int32_t R, int64_t E, int32_t K);
+
+int gmc_contract_map(const gmc_batch *batch, int32_t K, int64_t P, const int32_t *pin_node /*[P]*/,
+                     const int32_t *pin_class /*[P]*/, int32_t *node_map /*[R]*/, int32_t *goff_out /*[B+1]*/,
+                     int32_t *report /*[GMC_CT_REPORT_WORDS]*/, void *workspace, size_t workspace_bytes,
+                     gmc_stream_t stream);
+
+int gmc_contract_entries(const gmc_batch *batch, int32_t K, const int32_t *node_map /*[R]*/,
+                         const int32_t *goff_out /*[B+1]*/, int64_t E_out, int32_t *src_out /*[E_out]*/,
+                         int32_t *dst_out /*[E_out]*/, float *w_out /*[E_out]*/, float *fixed_cut /*[B]*/,
+                         void *workspace, size_t workspace_bytes, gmc_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
