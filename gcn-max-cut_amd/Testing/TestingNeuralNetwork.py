@@ -851,6 +851,102 @@ def kway_tabu_search(partition_assignment, graph, number_classes: int, iteration
     return best_assign.cpu().tolist(), _as_number(best_cut.item())
 
 
+def class_size_bounds(what: str, class_sizes, sizes, K: int, terminals: bool) -> Tuple[np.ndarray, np.ndarray]:
+    """``class_sizes`` as the balanced stage takes it -> (lo, hi), int32 [B, K], for graphs of ``sizes`` [B] nodes, all on
+    the host: ``"balanced"`` is ``n // K`` and ``ceil(n / K)`` for every class; a pair ``(lo, hi)`` holds [K] (every
+    graph) or [B, K] integers.  Bounds that admit no partition (include/gcnmaxcut.h, gmc_kway_balance_f32: ``lo <= hi``,
+    ``hi >= 1`` for a terminal's class, ``sum(max(lo, t)) <= n <= sum(hi)``) raise ``ValueError`` naming the graph."""
+    sizes = np.asarray(sizes, np.int64).reshape(-1)
+    B = sizes.size
+    if isinstance(class_sizes, str):
+        if class_sizes != "balanced":
+            raise ValueError(f"{what}: class_sizes must be 'balanced' or a pair (lo, hi), got {class_sizes!r}")
+        lo = np.repeat((sizes // K)[:, None], K, axis=1)
+        hi = np.repeat((-(-sizes // K))[:, None], K, axis=1)
+    else:
+        if not isinstance(class_sizes, (tuple, list)) or len(class_sizes) != 2:
+            raise ValueError(f"{what}: class_sizes must be 'balanced' or a pair (lo, hi)")
+        pair = []
+        for name, x in zip(("lo", "hi"), class_sizes):
+            x = x.detach().cpu().numpy() if isinstance(x, torch.Tensor) else np.asarray(x)
+            if x.dtype.kind not in "iu" or x.shape not in ((K,), (B, K)):
+                raise ValueError(f"{what}: class_sizes {name} must hold integers of shape [{K}] or [{B}, {K}], got "
+                                 f"{x.dtype} {tuple(x.shape)}")
+            if x.size and (int(x.min()) < -(1 << 31) or int(x.max()) >= 1 << 31):
+                raise ValueError(f"{what}: class_sizes {name} does not fit int32")
+            pair.append(np.broadcast_to(x.astype(np.int64), (B, K)))
+        lo, hi = pair
+    t = 1 if terminals else 0
+    for g in range(B):
+        n = int(sizes[g])
+        why = None
+        if (lo[g] > hi[g]).any():
+            why = f"lo > hi for class {int(np.argmax(lo[g] > hi[g]))}"
+        elif (hi[g] < t).any():
+            why = f"hi < 1 for class {int(np.argmax(hi[g] < t))}, which holds a terminal"
+        elif int(np.maximum(lo[g], t).sum()) > n:
+            why = f"the lower bounds ask for {int(np.maximum(lo[g], t).sum())} nodes"
+        elif int(hi[g].sum()) < n:
+            why = f"the upper bounds leave room for {int(hi[g].sum())} nodes"
+        if why is not None:
+            raise ValueError(f"{what}: the class sizes of graph {g} ({n} nodes, number_classes = {K}) admit no "
+                             f"partition: {why}")
+    return np.ascontiguousarray(lo, np.int32), np.ascontiguousarray(hi, np.int32)
+
+
+def _kway_balance_on_gpu(batch: GraphBatch, K: int, assign: torch.Tensor, lo: np.ndarray, hi: np.ndarray,
+                         iterations: int, tenure, seed: int, terminals: bool = True):
+    """Tabu search under class-size bounds (gmc_kway_balance_f32) over the candidates assign [cands, R] int8, in place,
+    with lo, hi int32 [B, K] as :func:`class_size_bounds` returns them.  Returns the best assignment [R], its cut and
+    candidate index per graph, then best_iter, moves and repairs [B, cands] and cut_all [B, cands]."""
+    _needs_terminals(batch, K, terminals)
+    base, span, div = _tabu_arguments("the balanced search", iterations, tenure)
+    if lo.shape != (batch.B, K) or hi.shape != (batch.B, K):
+        raise ValueError(f"the balanced search: bounds of shape {lo.shape} and {hi.shape} for {batch.B} graphs and {K} classes")
+    dev = batch.device
+    cands = int(assign.shape[0])
+    size_lo = torch.from_numpy(np.ascontiguousarray(lo, np.int32)).to(dev)
+    size_hi = torch.from_numpy(np.ascontiguousarray(hi, np.int32)).to(dev)
+    cut_all = torch.empty((batch.B, cands), dtype=torch.float32, device=dev)
+    best_assign = torch.empty(batch.R, dtype=torch.int32, device=dev)
+    best_cut = torch.empty(batch.B, dtype=torch.float32, device=dev)
+    best_idx = torch.empty(batch.B, dtype=torch.int32, device=dev)
+    best_iter = torch.empty((batch.B, cands), dtype=torch.int32, device=dev)
+    moves = torch.empty((batch.B, cands), dtype=torch.int32, device=dev)
+    repairs = torch.empty((batch.B, cands), dtype=torch.int32, device=dev)
+    p = hip.ptr
+    rc = hip.load().gmc_kway_balance_f32(batch.ref(), K, 1 if terminals else 0, cands, p(assign), p(size_lo), p(size_hi),
+                                         int(iterations), base, span, div, int(seed) & _M64, p(cut_all), p(best_assign),
+                                         p(best_cut), p(best_idx), p(best_iter), p(moves), p(repairs), None, hip.stream())
+    hip.check(rc, "gmc_kway_balance_f32")
+    return best_assign, best_cut, best_idx, best_iter, moves, repairs, cut_all
+
+
+def kway_balanced_search(partition_assignment, graph, number_classes: int, class_sizes="balanced",
+                         iterations: Optional[int] = None, tenure_base: int = 3, tenure_span: int = 0,
+                         tenure_div: int = 10, seed: int = 0, terminals: bool = True) -> Tuple[List[int], Any]:
+    """:func:`kway_tabu_search` with the size of every class kept within bounds (extension, include/gcnmaxcut.h
+    ``gmc_kway_balance_f32``): max-bisection and balanced max-K-cut, and on negated weights balanced minimum cut.
+    ``class_sizes`` is ``"balanced"`` (every class holds ``n // K`` to ``ceil(n / K)`` nodes, terminals included) or a
+    pair ``(lo, hi)`` of ``number_classes`` integers each.  The input need not be within the bounds: it is first
+    repaired by the moves that cost the least cut.  Then every iteration makes the best single move that keeps the
+    bounds, or the best move that breaks one followed by the best move back out of the class it entered; the best
+    state passed through is returned and is always within the bounds.  ``iterations=None`` means ``20 * n``; the tenure
+    arguments are :func:`kway_tabu_search`'s.  Bounds that admit no partition raise ``ValueError``.  With
+    ``class_sizes=([0] * K, [n] * K)`` it is :func:`kway_tabu_search`, byte for byte.  Returns the assignment and
+    its cut value."""
+    K, part = _kway_partition("kway_balanced_search", partition_assignment, graph, number_classes, terminals)
+    n = graph.number_of_nodes()
+    iterations = 20 * n if iterations is None else int(iterations)
+    tenure = _tabu_arguments("kway_balanced_search", iterations, (tenure_base, tenure_span, tenure_div))
+    lo, hi = class_size_bounds("kway_balanced_search", class_sizes, [n], K, terminals)
+    dev = hip.require_gpu()
+    batch = GraphBatch([from_networkx(graph)], None, dev)
+    assign = torch.from_numpy(part.astype(np.int8)).to(dev).reshape(1, -1)
+    best_assign, best_cut = _kway_balance_on_gpu(batch, K, assign, lo, hi, iterations, tenure, seed, terminals)[:2]
+    return best_assign.cpu().tolist(), _as_number(best_cut.item())
+
+
 # The evolution stage's defaults are PROVISIONAL (DESIGN.md section 22): 10 generations of 10 sweeps cooling from 0.6
 # are a starting point nobody has measured yet, not the outcome of the sweep described there.
 EVOLVE_GENERATIONS = 10

@@ -1,0 +1,503 @@
+// Tabu search under class-size bounds at K = 2..8 classes (an extension): gmc_kway_balance_f32, stated to the operation
+// in include/gcnmaxcut.h.  It is gmc_kway_tabu_f32's chain (kway_tabu.hip: one WAVE per chain, W / until / state /
+// snapshot in LDS, 4, 2 or 1 chains of one graph per 256-thread workgroup over one staged copy of the CSR or the
+// batch's arrays, the 64-bit key scan, the max butterfly on the VALU, one lane per edge applying a move, the deferred
+// snapshot copy, the scoring tail and the pick) with three additions:
+//
+//   - the class sizes s[c] (every node) and m[c] (movable nodes) and the bounds lo[c], hi[c]: wave-uniform integers,
+//     selected by compares as gmc::Sums<K> is, so they stay in scalar registers and the chain's LDS stays at tabu's
+//     n_pad * (4 K + 6) bytes;
+//   - which moves a -> b a node of class a may make is a property of (a, b) alone, so it is worked out once per change
+//     of the sizes as K rows of K bits (a byte per class in one 64-bit word) and the scan only shifts and masks:
+//     `open` for a node that is not banned (free moves, and paired ones into a class with a movable node), `free_` for
+//     a banned one (aspiration belongs to free moves only).  A node still enters the scan with ONE key, its best move
+//     among the targets of its row: for a banned node rel + gain is monotone in the gain, as in tabu;
+//   - the same scan serves the repair (rows: the moves that lower the violation; no bans, rank = v - first) and the
+//     counter-move of a paired move (one row with one bit: class b -> a; no bans; the node just moved left out).
+//
+// A paired move changes no size, so the rows are rebuilt after free moves and repair moves only.  With lo = 0 and
+// hi = n every row is "every other class", nothing is repaired and the arithmetic is tabu's, step for step.
+// The snapshot copy stays deferred; a paired move does not know whether it improves before its counter-move is chosen,
+// so a pending copy is made ahead of every paired move - the state then IS the best state, so the bytes are the same.
+#include "gmc_common.h"
+#include "cut_body.h"
+#include "mix64.h"
+#include "move_body.h"
+#include "anneal_layout.h"
+#include "tabu_body.h"
+
+namespace {
+
+using gmc::mix64;
+using gmc::u64;
+using gmc::GlobalCsr;
+using gmc::LdsCsr;
+using gmc::TabuLayout;
+using gmc::tabu_layout;
+using gmc::wave_sync;
+using gmc::wave_max;
+using gmc::ordered_bits;
+using gmc::ordered_float;
+
+struct BalanceArgs {
+    gmc_batch b;
+    int first;               // first movable local id: K with terminals, 0 without
+    int cands, iterations;
+    unsigned tenure_base, tenure_span, tenure_div;
+    u64 seed;
+    signed char *assign;     // [cands][R], in/out
+    const int *size_lo;      // [B][K]
+    const int *size_hi;      // [B][K]
+    float *cut_all;          // [B][cands]
+    int *best_iter;          // [B][cands] or NULL
+    int *moves;              // [B][cands] or NULL
+    int *repairs;            // [B][cands] or NULL
+    int slots, staged, n_pad, chain_bytes, off_starts, off_vals, off_ids;
+};
+
+// the sizes and their bounds: wave-uniform, every index a constant once the loops are unrolled
+// (s and m share a word, s in the low half and m in the high half - both are at most GMC_MAX_GRAPH_NODES = 4096 - and so do
+// lo and hi, clamped to 0..n, which changes no compare against a size in 0..n; with four words a class the K = 7
+// instantiation spilled 20 bytes of scratch)
+template <int K>
+struct Sizes {
+    unsigned sm[K], lh[K];
+    __device__ __forceinline__ int s(int k) const { return (int)(sm[k] & 0xffffu); }
+    __device__ __forceinline__ int m(int k) const { return (int)(sm[k] >> 16); }
+    __device__ __forceinline__ int lo(int k) const { return (int)(lh[k] & 0xffffu); }
+    __device__ __forceinline__ int hi(int k) const { return (int)(lh[k] >> 16); }
+};
+
+// "the bounds admit a partition" of include/gcnmaxcut.h for a graph of n nodes; t = 1 under terminals
+template <int K>
+__device__ __forceinline__ bool bounds_admit(const int *lo, const int *hi, int n, int t) {
+    bool ok = true;
+    long long need = 0, room = 0;
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+        const int l = lo[k], h = hi[k];
+        ok = ok && l <= h && h >= t;
+        need += l > t ? l : t;
+        room += h;
+    }
+    return ok && need <= (long long)n && (long long)n <= room;
+}
+
+template <int K>
+__device__ __forceinline__ int violation(const Sizes<K> &z) {
+    int V = 0;
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+        V += z.lo(k) > z.s(k) ? z.lo(k) - z.s(k) : 0;
+        V += z.s(k) > z.hi(k) ? z.s(k) - z.hi(k) : 0;
+    }
+    return V;
+}
+
+// one movable node leaves class a for class b (wave-uniform a, b)
+template <int K>
+__device__ __forceinline__ void resize(Sizes<K> &z, int a, int b) {
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+        const int d = (k == b ? 1 : 0) - (k == a ? 1 : 0);
+        z.sm[k] += (unsigned)(d * 0x10001);   // (s and m are at least 1 where one is taken: no borrow between the halves)
+    }
+}
+
+// rows of the search: bit (a * 8 + b) of free_ - the move a -> b is free; of open - it is free, or paired with a
+// movable node in b to come back
+template <int K>
+__device__ __forceinline__ void search_rows(const Sizes<K> &z, u64 &open, u64 &free_) {
+    open = 0;
+    free_ = 0;
+#pragma unroll
+    for (int a = 0; a < K; ++a) {
+#pragma unroll
+        for (int b = 0; b < K; ++b) {
+            if (a == b) continue;
+            const bool fr = z.s(a) > z.lo(a) && z.s(b) < z.hi(b);
+            const u64 bit = 1ULL << (a * 8 + b);
+            free_ |= fr ? bit : 0ULL;
+            open |= fr || z.m(b) >= 1 ? bit : 0ULL;
+        }
+    }
+}
+
+// rows of the repair: bit (a * 8 + b) - the move a -> b lowers the violation
+template <int K>
+__device__ __forceinline__ u64 repair_rows(const Sizes<K> &z) {
+    u64 rows = 0;
+#pragma unroll
+    for (int a = 0; a < K; ++a) {
+        const int da = z.s(a) > z.hi(a) ? -1 : z.s(a) <= z.lo(a) ? 1 : 0;
+#pragma unroll
+        for (int b = 0; b < K; ++b) {
+            if (a == b) continue;
+            const int db = z.s(b) < z.lo(b) ? -1 : z.s(b) >= z.hi(b) ? 1 : 0;
+            rows |= da + db < 0 ? 1ULL << (a * 8 + b) : 0ULL;
+        }
+    }
+    return rows;
+}
+
+// The chain's views of its LDS and its graph, and the two steps every kind of move shares.
+template <int K, class G>
+struct Chain {
+    const G &g;
+    float *W;
+    unsigned *until;
+    unsigned char *st;
+    int first, n, n_mov, trips, lane;
+
+    // The wave's best move as one 64-bit key (0: none) - the gain mapped to an order-preserving uint32 in the high
+    // half, ~(rank * K + k) in the low half - over the movable nodes other than `skip`: a node of class c whose ban
+    // has run out by `now` takes its targets from row c of `open`, a banned one from row c of `free_` and only when
+    // rel + gain > best.  A wave-uniform trip count and unconditional loads from a clamped node, unrolled by two, as
+    // in tabu: a lane past its last node reads node `first` and admits nothing.
+    __device__ __forceinline__ u64 scan(u64 open, u64 free_, unsigned now, int r, int skip, float rel,
+                                        float best) const {
+        u64 key = 0;
+#pragma unroll 2
+        for (int t = 0; t < trips; ++t) {
+            const int v0 = first + lane + (t << 6);
+            const bool valid = v0 < n;
+            const int v = valid ? v0 : first;
+            const unsigned c = st[v];
+            float w[K];
+#pragma unroll
+            for (int k = 0; k < K; ++k) w[k] = W[v * K + k];
+            float wc = w[0];
+#pragma unroll
+            for (int j = 1; j < K; ++j) wc = c == (unsigned)j ? w[j] : wc;
+            const bool is_free = until[v] <= now;
+            const unsigned row = (unsigned)((is_free ? open : free_) >> ((c & 7u) << 3)) & 0xffu;
+            int rank = v - first - r;
+            rank = rank < 0 ? rank + n_mov : rank;
+            // the node's own best move among its row's targets - the largest gain, the smallest k on ties
+            float bg = -__builtin_inff();
+            int bk = 0;
+#pragma unroll
+            for (int k = 0; k < K; ++k) {
+                const float gain = wc - w[k];
+                const bool take = ((row >> k) & 1u) != 0u && gain > bg;
+                bg = take ? gain : bg;
+                bk = take ? k : bk;
+            }
+            // (a byte of no class: the node never moves)
+            const bool adm = valid && v0 != skip && c < (unsigned)K && row != 0u && (is_free || rel + bg > best);
+            const u64 cnd = ((u64)ordered_bits(bg) << 32) | (u64)(~(unsigned)(rank * K + bk));
+            key = adm && cnd > key ? cnd : key;
+        }
+        return wave_max(key);
+    }
+
+    // step 4 of tabu: node v leaves class c for class k; one lane per edge of its row
+    __device__ __forceinline__ void apply(int v, int c, int k) const {
+        const int e1 = g.rp[v + 1];
+        for (int e = (int)g.rp[v] + lane; e < e1; e += GMC_WAVE) {
+            const int u = g.col[e];
+            if (u == v) continue;
+            const float wt = g.vals ? g.vals[e] : 1.0f;
+            W[u * K + c] -= wt;
+            W[u * K + k] += wt;
+        }
+        if (lane == 0) st[v] = (unsigned char)k;
+    }
+};
+
+// One chain on the calling wave: the sizes, the repair, the table, the iterations, the snapshot left in sn.
+template <int K, class G>
+__device__ __forceinline__ void balance_chain(const BalanceArgs &a, const G &g, unsigned char *lds, int n, int cand,
+                                              const signed char *in, const int *lo, const int *hi, int &best_it_out,
+                                              int &moves_out, int &repairs_out) {
+    const int lane = gmc::lane_id();
+    float *W = reinterpret_cast<float *>(lds);
+    unsigned *until = reinterpret_cast<unsigned *>(lds + (size_t)a.n_pad * K * 4);
+    unsigned char *st = lds + (size_t)a.n_pad * (K * 4 + 4);
+    unsigned char *sn = st + a.n_pad;
+    const int first = a.first;
+    const int n_mov = n - first;
+    Sizes<K> z;
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+        z.sm[k] = 0u;
+        const int l = lo[k] < 0 ? 0 : lo[k] > n ? n : lo[k];   // (admitted bounds have lo <= n and hi >= 0)
+        const int h = hi[k] < 0 ? 0 : hi[k] > n ? n : hi[k];
+        z.lh[k] = (unsigned)l | ((unsigned)h << 16);
+    }
+    for (int l0 = 0; l0 < n; l0 += GMC_WAVE) {   // wave-uniform trip count: the ballots below take every lane
+        const int l = l0 + lane;
+        unsigned c = 0xffu;
+        if (l < n) {
+            c = (unsigned char)in[l];
+            st[l] = (unsigned char)c;
+            sn[l] = (unsigned char)c;
+            until[l] = 0u;
+        }
+#pragma unroll
+        for (int k = 0; k < K; ++k) {
+            z.sm[k] += (unsigned)__popcll(__ballot(c == (unsigned)k)) +
+                       ((unsigned)__popcll(__ballot(c == (unsigned)k && l >= first)) << 16);
+        }
+    }
+    int best_it = 0, moves = 0, repairs = 0;
+    int V = violation<K>(z);
+    if (n_mov > 0 && (a.iterations > 0 || V > 0)) {
+        wave_sync();
+        for (int l = lane; l < n; l += GMC_WAVE) {
+            const gmc::Sums<K> s = gmc::class_sums_k<K>(g.rp, g.col, g.vals, st, l);
+#pragma unroll
+            for (int k = 0; k < K; ++k) W[l * K + k] = s.m[k];
+        }
+        wave_sync();
+        const Chain<K, G> ch{g, W, until, st, first, n, n_mov, (n_mov + GMC_WAVE - 1) / GMC_WAVE, lane};
+        // the repair: the largest gain among the moves that lower the violation, until none is left
+        // (every move lowers V, so the loop ends within V <= 2 n moves whatever the bytes are)
+        while (V > 0) {
+            const u64 rows = repair_rows<K>(z);
+            const u64 key = ch.scan(rows, rows, 0xffffffffu, 0, -1, 0.0f, 0.0f);
+            const unsigned khi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(key >> 32));
+            const unsigned klo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)key);
+            if (khi == 0u && klo == 0u) break;   // (wave-uniform)
+            const unsigned x = ~klo;
+            const int k = (int)(x % (unsigned)K);
+            const int v = first + (int)(x / (unsigned)K);
+            const int c = __builtin_amdgcn_readfirstlane((int)st[v]);   // (keeps the sizes in scalar registers)
+            ch.apply(v, c, k);
+            resize<K>(z, c, k);
+            V = violation<K>(z);
+            ++repairs;
+            wave_sync();
+        }
+        if (repairs > 0) {   // the repaired state is the base of the search
+            const unsigned *s32 = reinterpret_cast<const unsigned *>(st);
+            unsigned *d32 = reinterpret_cast<unsigned *>(sn);
+            for (int i = lane; i < (a.n_pad >> 2); i += GMC_WAVE) d32[i] = s32[i];
+            wave_sync();
+        }
+        float rel = 0.0f, best = 0.0f;
+        bool pending = false;   // the state is better than the snapshot and not copied yet
+        const unsigned span = a.tenure_span + (a.tenure_div > 0 ? (unsigned)n_mov / a.tenure_div : 0u);
+        const u64 base = a.seed + GMC_GOLD * (((u64)(unsigned)cand << 32) + 1ULL);   // it < 2^32 only adds
+        u64 open, free_;
+        search_rows<K>(z, open, free_);
+        for (int it = 0; it < a.iterations; ++it) {
+            const u64 h = mix64(base + GMC_GOLD * (u64)(unsigned)it);
+            const int r = (int)((unsigned)h % (unsigned)n_mov);
+            const unsigned tenure_draw = (unsigned)(h >> 32) % (span + 1u);
+            const u64 key = ch.scan(open, free_, (unsigned)it, r, -1, rel, best);
+            const unsigned khi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(key >> 32));
+            const unsigned klo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)key);
+            if (khi == 0u && klo == 0u) continue;   // no admissible move (wave-uniform)
+            const unsigned x = ~klo;
+            const int k = (int)(x % (unsigned)K);
+            int v = first + (int)(x / (unsigned)K) + r;
+            v = v - first >= n_mov ? v - n_mov : v;
+            const float gain = ordered_float(khi);
+            const int c = __builtin_amdgcn_readfirstlane((int)st[v]);   // (keeps the sizes in scalar registers)
+            const bool is_free = ((free_ >> (c * 8 + k)) & 1ULL) != 0ULL;   // (wave-uniform)
+            const float new_rel = rel + gain;
+            if (pending && !(is_free && new_rel > best)) {   // the snapshot takes the state before this move
+                const unsigned *s32 = reinterpret_cast<const unsigned *>(st);
+                unsigned *d32 = reinterpret_cast<unsigned *>(sn);
+                for (int i = lane; i < (a.n_pad >> 2); i += GMC_WAVE) d32[i] = s32[i];
+                pending = false;
+                wave_sync();
+            }
+            const u64 u64_until = (u64)(unsigned)it + 1ULL + (u64)a.tenure_base + (u64)tenure_draw;
+            const unsigned ban = u64_until > 0xffffffffULL ? 0xffffffffu : (unsigned)u64_until;   // saturated: "never again"
+            ch.apply(v, c, k);
+            if (lane == 0) until[v] = ban;
+            rel = new_rel;
+            ++moves;
+            if (is_free) {
+                resize<K>(z, c, k);
+                search_rows<K>(z, open, free_);
+            } else {
+                // the counter-move: the best movable u != v of class k goes to class c, bans ignored
+                wave_sync();
+                const u64 back = 1ULL << (k * 8 + c);
+                const u64 key2 = ch.scan(back, back, 0xffffffffu, r, v, 0.0f, 0.0f);
+                const unsigned k2hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(key2 >> 32));
+                const unsigned k2lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)key2);
+                if (k2hi != 0u || k2lo != 0u) {   // (always, for class bytes in 0..K-1: m[k] >= 1 before v came)
+                    int u = first + (int)(~k2lo / (unsigned)K) + r;
+                    u = u - first >= n_mov ? u - n_mov : u;
+                    ch.apply(u, k, c);
+                    if (lane == 0) until[u] = ban;
+                    rel = rel + ordered_float(k2hi);
+                }
+            }
+            // 5. best so far
+            if (rel > best) {
+                best = rel;
+                best_it = it + 1;
+                pending = true;
+            }
+            wave_sync();
+        }
+        if (pending) {
+            const unsigned *s32 = reinterpret_cast<const unsigned *>(st);
+            unsigned *d32 = reinterpret_cast<unsigned *>(sn);
+            for (int i = lane; i < (a.n_pad >> 2); i += GMC_WAVE) d32[i] = s32[i];
+        }
+    }
+    best_it_out = best_it;
+    moves_out = moves;
+    repairs_out = repairs;
+}
+
+// workgroup-uniform: the graph has a size the launch takes and bounds that admit a partition
+template <int K>
+__device__ __forceinline__ bool graph_runs(const gmc_batch &b, int first, int gi, const int *size_lo,
+                                           const int *size_hi, int &n, bool &admitted) {
+    n = b.goff[gi + 1] - b.goff[gi];
+    admitted = false;
+    if (n > b.n_max || n < (first > 1 ? first : 1)) return false;   // (the LDS is sized by n_max)
+    admitted = bounds_admit<K>(size_lo + (long)gi * K, size_hi + (long)gi * K, n, first > 0 ? 1 : 0);
+    return admitted;
+}
+
+template <int K>
+__global__ __launch_bounds__(256) void balance_kernel(BalanceArgs a) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
+    __shared__ float red[4];
+    const int gi = blockIdx.y;
+    const int r0 = a.b.goff[gi];
+    int n;
+    bool admitted;
+    if (!graph_runs<K>(a.b, a.first, gi, a.size_lo, a.size_hi, n, admitted)) return;
+    const int *lo = a.size_lo + (long)gi * K;
+    const int *hi = a.size_hi + (long)gi * K;
+    const int wave = gmc::uniform((int)(threadIdx.x >> 6));
+    const int cand0 = blockIdx.x * a.slots;
+    const int cand = cand0 + wave;
+    const int e0 = a.b.rowptr[r0];
+    const int nnz = a.b.rowptr[r0 + n] - e0;
+    // the copy is sized by n_max and nnz_max: a graph that contradicts them takes the global path
+    const bool staged = a.staged && nnz >= 0 && nnz <= a.b.nnz_max;   // workgroup-uniform
+    const bool runs = wave < a.slots && cand < a.cands;               // wave-uniform
+    int best_it = 0, moves = 0, repairs = 0;
+    if (staged) {
+        int *starts = reinterpret_cast<int *>(lds + a.off_starts);
+        float *vals = a.b.vals ? reinterpret_cast<float *>(lds + a.off_vals) : nullptr;
+        unsigned short *ids = reinterpret_cast<unsigned short *>(lds + a.off_ids);
+        // (staged whatever the iteration count: the repair needs the table too)
+        for (int l = threadIdx.x; l <= n; l += blockDim.x) starts[l] = a.b.rowptr[r0 + l] - e0;
+        for (int e = threadIdx.x; e < nnz; e += blockDim.x) {
+            ids[e] = (unsigned short)a.b.lcol[e0 + e];
+            if (vals) vals[e] = a.b.vals[e0 + e];
+        }
+        __syncthreads();
+        if (runs) {
+            const LdsCsr g{starts, ids, vals, nullptr, 0};
+            balance_chain<K>(a, g, lds + (size_t)wave * a.chain_bytes, n, cand, a.assign + (long)cand * a.b.R + r0, lo,
+                             hi, best_it, moves, repairs);
+        }
+    } else if (runs) {
+        const GlobalCsr g{a.b.rowptr + r0, a.b.lcol, a.b.vals, nullptr, r0, a.first};
+        balance_chain<K>(a, g, lds + (size_t)wave * a.chain_bytes, n, cand, a.assign + (long)cand * a.b.R + r0, lo, hi,
+                         best_it, moves, repairs);
+    }
+    if (runs && gmc::lane_id() == 0) {
+        if (a.best_iter) a.best_iter[(long)gi * a.cands + cand] = best_it;
+        if (a.moves) a.moves[(long)gi * a.cands + cand] = moves;
+        if (a.repairs) a.repairs[(long)gi * a.cands + cand] = repairs;
+    }
+    __syncthreads();   // every chain of the workgroup has left its snapshot
+    // the result and its score, chain by chain, the whole workgroup on each: scored as gmc_refine_local_f32 scores
+    for (int s = 0; s < a.slots; ++s) {
+        const int cs = cand0 + s;
+        if (cs >= a.cands) break;   // workgroup-uniform
+        const unsigned char *sn = lds + (size_t)s * a.chain_bytes + (size_t)a.n_pad * (K * 4 + 5);
+        signed char *as = a.assign + (long)cs * a.b.R + r0;
+        for (int l = threadIdx.x; l < n; l += blockDim.x) as[l] = (signed char)sn[l];
+        const float cut = gmc::block_cut(a.b, sn, r0, n, red);
+        if (threadIdx.x == 0) a.cut_all[(long)gi * a.cands + cs] = cut;
+        __syncthreads();   // thread 0 has read red before the next recount writes it
+    }
+}
+
+struct BalancePickArgs {
+    gmc::PickArgs p;
+    int first;
+    const int *size_lo, *size_hi;
+    int *feasible;   // [B] or NULL
+};
+template <int K>
+__global__ __launch_bounds__(256) void balance_pick_kernel(BalancePickArgs a) {
+    const int g = blockIdx.x;
+    int n;
+    bool admitted;
+    const bool runs = graph_runs<K>(a.p.b, a.first, g, a.size_lo, a.size_hi, n, admitted);
+    if (n > a.p.b.n_max || n < (a.first > 1 ? a.first : 1)) return;   // workgroup-uniform: a graph of the wrong size
+    if (a.feasible && threadIdx.x == 0) a.feasible[g] = admitted ? 1 : 0;
+    if (!runs) return;                                                // workgroup-uniform: the graphs the chains skipped
+    gmc::pick_best(a.p);
+}
+
+template <int K>
+int balance_launch(const BalanceArgs &a, const BalancePickArgs &p, int lds_bytes, hipStream_t st) {
+    if (lds_bytes > 64 * 1024) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(balance_kernel<K>),
+                                           hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
+        if (e != hipSuccess) return (int)e;
+    }
+    {
+        GmcProbeScope probe(GMC_K_ANNEAL, st);
+        hipLaunchKernelGGL((balance_kernel<K>), dim3((a.cands + a.slots - 1) / a.slots, a.b.B), dim3(256),
+                           (size_t)lds_bytes, st, a);
+        GMC_LAUNCH_CHECK();
+    }
+    hipLaunchKernelGGL((balance_pick_kernel<K>), dim3(a.b.B), dim3(256), 0, st, p);
+    GMC_LAUNCH_CHECK();
+    return GMC_OK;
+}
+
+}  // namespace
+
+extern "C" int gmc_kway_balance_fits(const gmc_batch *batch, int32_t K) {
+    if (!batch) return GMC_ERR_NULL;
+    if (batch->abi != GMC_VERSION) return GMC_ERR_ABI;
+    if (K < 2 || K > GMC_KWAY_MAX_CLASSES) return GMC_ERR_CLASSES;
+    return tabu_layout(batch, K).fits;
+}
+
+extern "C" int gmc_kway_balance_shape(const gmc_batch *batch, int32_t K) {
+    if (!batch) return GMC_ERR_NULL;
+    if (batch->abi != GMC_VERSION) return GMC_ERR_ABI;
+    if (K < 2 || K > GMC_KWAY_MAX_CLASSES) return GMC_ERR_CLASSES;
+    const TabuLayout L = tabu_layout(batch, K);
+    if (!L.fits) return GMC_ERR_GRAPH_SIZE;
+    return L.slots | (L.staged << 4);
+}
+
+extern "C" int gmc_kway_balance_f32(const gmc_batch *batch, int32_t K, int32_t terminals, int32_t cands, int8_t *assign,
+                                    const int32_t *size_lo, const int32_t *size_hi, int32_t iterations,
+                                    int32_t tenure_base, int32_t tenure_span, int32_t tenure_div, uint64_t seed,
+                                    float *cut_all, int32_t *best_assign, float *best_cut, int32_t *best_idx,
+                                    int32_t *best_iter, int32_t *moves, int32_t *repairs, int32_t *feasible,
+                                    gmc_stream_t stream) {
+    if (!batch || !assign || !size_lo || !size_hi || !cut_all || !best_assign || !best_cut || !best_idx)
+        return GMC_ERR_NULL;
+    if (batch->abi != GMC_VERSION) return GMC_ERR_ABI;
+    if (!batch->goff || !batch->rowptr || !batch->lcol) return GMC_ERR_NULL;
+    if (K < 2 || K > GMC_KWAY_MAX_CLASSES) return GMC_ERR_CLASSES;
+    if (cands < 1 || iterations < 0 || tenure_base < 0 || tenure_span < 0 || tenure_div < 0 || batch->B < 0 ||
+        (terminals != 0 && terminals != 1))
+        return GMC_ERR_SHAPE;
+    const int first = terminals ? K : 0;
+    const TabuLayout L = tabu_layout(batch, K);
+    if (batch->B > 0 && (batch->n_max < (first > 1 ? first : 1) || !L.fits)) return GMC_ERR_GRAPH_SIZE;
+    if (batch->B == 0) return GMC_OK;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const BalanceArgs a{*batch, first, cands, iterations, (unsigned)tenure_base, (unsigned)tenure_span,
+                        (unsigned)tenure_div, seed, reinterpret_cast<signed char *>(assign), size_lo, size_hi, cut_all,
+                        best_iter, moves, repairs, L.slots, L.staged, L.n_pad, L.chain_bytes, L.off_starts, L.off_vals,
+                        L.off_ids};
+    const BalancePickArgs p{{*batch, cands, reinterpret_cast<const signed char *>(assign), cut_all, best_assign,
+                             best_cut, best_idx}, first, size_lo, size_hi, feasible};
+    int rc = GMC_OK;
+    GMC_KWAY_DISPATCH(K, rc = balance_launch<KK>(a, p, L.bytes, st));
+    return rc;
+}

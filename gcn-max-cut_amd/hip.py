@@ -181,6 +181,10 @@ def _api() -> dict:
         "gmc_kway_tabu_f32": (i, [B, i32, i32, i32, vp, i32, i32, i32, i32, C.c_uint64, vp, vp, vp, vp, vp, vp, vp]),
         "gmc_kway_tabu_fits": (i, [B, i32]),
         "gmc_kway_tabu_shape": (i, [B, i32]),
+        "gmc_kway_balance_f32": (i, [B, i32, i32, i32, vp, vp, vp, i32, i32, i32, i32, C.c_uint64, vp, vp, vp, vp, vp, vp,
+                                     vp, vp, vp]),
+        "gmc_kway_balance_fits": (i, [B, i32]),
+        "gmc_kway_balance_shape": (i, [B, i32]),
         "gmc_large_round_order_host": (i, [i32, vp, vp, vp, i32, vp, vp, vp, i32, vp]),
         "gmc_large_round_workspace_bytes": (sz, [B, i32]),
         "gmc_large_round_conditional_f32": (i, [B, vp, i32, vp, vp, vp, i32, i32, vp, sz, vp, vp, vp, vp, vp]),

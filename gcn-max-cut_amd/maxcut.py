@@ -25,6 +25,8 @@ _TOO_LARGE = ("a graph of {n} nodes is beyond the one-workgroup head of the per-
               "search_large_dataset(..., terminals=False), or call maxcut.solve_large, which trains one model per graph up "
               "to 2^20 nodes")
 _NO_TABU = "the tabu stage keeps a graph's state in one workgroup: solve_large does not have it (tabu_iterations must be 0)"
+_NO_BALANCE = ("the balanced stage keeps a graph's state in one workgroup, as the tabu stage does: solve_large does not "
+               "have it (class_sizes must be None)")
 _BEYOND_LARGE = "a graph of {n} nodes is beyond the {bound} nodes of the per-graph models' large sequence (solve_large)"
 
 
@@ -39,12 +41,33 @@ class MaxCutResult:
     annealed_cut: Optional[torch.Tensor] = None   # [B] float32, with tabu_iterations > 0 only: the cut the annealing reached
     fixed_cut: Optional[torch.Tensor] = None      # [B] float32, with fixed only: the weight of the edges between pinned
     #                                               nodes of different classes (a constant of every partition)
+    unconstrained_cut: Optional[torch.Tensor] = None   # [B] float32, with class_sizes only: what ``cut`` would have been
+
+
+def balanced_sizes(ptr, number_classes: int, imbalance: float = 0.0):
+    """``class_sizes`` for :func:`solve` from the graphs' sizes: ``(lo, hi)``, int32 numpy arrays [B, K] with
+    ``lo = floor((1 - imbalance) * n / K)`` and ``hi = ceil((1 + imbalance) * n / K)`` for every class of a graph of n
+    nodes (``ptr`` [B + 1] as :func:`solve` takes it).  ``imbalance = 0``: ``"balanced"``.  The products are taken in
+    float64 and a value within 1e-9 of an integer counts as that integer, so 1.03 * 1000 / 2 is 515 and not 516."""
+    K = int(number_classes)
+    if not 2 <= K <= hip.KWAY_MAX_CLASSES:
+        raise ValueError(f"number_classes must be in 2..{hip.KWAY_MAX_CLASSES}, got {K}")
+    if not 0.0 <= float(imbalance) <= 1.0:
+        raise ValueError(f"imbalance must be in 0..1, got {imbalance}")
+    p = ptr.detach().cpu().numpy() if isinstance(ptr, torch.Tensor) else np.asarray(ptr)
+    if p.ndim != 1 or p.size < 1:
+        raise ValueError("ptr must be [B + 1]")
+    n = np.diff(p.astype(np.int64)).astype(np.float64)
+    lo = np.floor((1.0 - float(imbalance)) * n / K + 1e-9).astype(np.int32)
+    hi = np.ceil((1.0 + float(imbalance)) * n / K - 1e-9).astype(np.int32)
+    return np.repeat(lo[:, None], K, axis=1), np.repeat(hi[:, None], K, axis=1)
 
 
 def solve(edge_index, ptr=None, num_nodes: Optional[int] = None, edge_weight=None, *, number_classes: int = 2,
           terminals: bool = False, pairs: str = "both", hidden_dim: int, epochs: int, learning_rate: float,
           loss: str = "expected_cut", samples: int = 32, anneal_sweeps: int = 100, max_descent_sweeps: int = 100,
-          seed: int = 0, tabu_iterations: int = 0, fixed=None) -> MaxCutResult:
+          seed: int = 0, tabu_iterations: int = 0, fixed=None, class_sizes=None,
+          balance_iterations: Optional[int] = None) -> MaxCutResult:
     """Max-K-cut of every graph of a batch given as ``edge_index`` [2, E] (with ``ptr`` [B+1], or ``num_nodes`` for one
     graph, ``edge_weight`` and ``pairs`` as ``GraphBatch.from_edge_index`` takes them).
 
@@ -62,6 +85,18 @@ def solve(edge_index, ptr=None, num_nodes: Optional[int] = None, edge_weight=Non
        annealed candidates.  Per graph ``partition`` / ``cut`` are then the better of the annealed and the tabu result
        by their recounted cuts, chosen on the device, and ``annealed_cut`` holds the annealed one: ``cut >=
        annealed_cut``.  The default 0 launches nothing more and leaves ``annealed_cut`` None.
+    6. with ``class_sizes`` only: one call of the balanced stage (``gmc_kway_balance_f32``,
+       ``Testing.kway_balanced_search``; ``balance_iterations`` iterations per candidate, ``None``: 20 times the
+       largest graph's nodes; seeded by ``seed``) on a copy of the annealed candidates, which it first repairs into the
+       bounds.  ``class_sizes`` is ``"balanced"`` (every class ``n // K`` to ``ceil(n / K)`` nodes), or a pair
+       ``(lo, hi)`` of [K] or [B, K] integers, e.g. from :func:`balanced_sizes`; a terminal counts for its class.
+       ``partition`` / ``cut`` are then this stage's pick - every returned partition is within its bounds - and
+       ``unconstrained_cut`` holds what ``cut`` would have been without the keyword, so ``cut`` may be below
+       ``trained_cut`` and ``rounded_cut``.  On this path the annealing's temperature is in units of the mean ABSOLUTE
+       edge weight (1 when that is 0), so negated weights - balanced minimum cut - go through.  Bounds that admit no
+       partition raise ``ValueError`` naming the graph; ``class_sizes`` together with ``fixed`` raises ``ValueError``
+       (a contracted super-node stands for many nodes, and node weights are not implemented).  The default ``None``
+       launches nothing more and changes no byte of the result.
 
     ``terminals=False`` (default): no node is fixed.  ``terminals=True``: nodes 0..K-1 of every graph keep classes
     0..K-1, as everywhere else in this package.  The same arguments give the same bytes.
@@ -84,32 +119,43 @@ def solve(edge_index, ptr=None, num_nodes: Optional[int] = None, edge_weight=Non
         raise ValueError(f"number_classes must be in 2..{hip.KWAY_MAX_CLASSES}, got {K}")
     loss = hip.loss_name(loss)
     _check_fixed(fixed, terminals, K)
+    _check_sizes(class_sizes, balance_iterations, fixed)
     if ptr is not None:   # judged before anything is built: the sizes are all it takes
         p = ptr.detach().cpu().numpy() if isinstance(ptr, torch.Tensor) else np.asarray(ptr)
         n_max = int(np.diff(p.astype(np.int64)).max()) if p.ndim == 1 and p.size > 1 else 0
+        if class_sizes is not None and p.ndim == 1 and p.size > 1:
+            _size_bounds(class_sizes, np.diff(p.astype(np.int64)), K, terminals)
     else:
         n_max = int(num_nodes) if num_nodes is not None else 0
+        if class_sizes is not None and num_nodes is not None:
+            _size_bounds(class_sizes, [n_max], K, terminals)
     if fixed is None and n_max > 0 and instance_too_large(n_max, K, loss):   # (with pins: the contracted sizes decide)
         raise ValueError(_TOO_LARGE.format(n=n_max, K=K))
     batch = GraphBatch.from_edge_index(edge_index, ptr, num_nodes, edge_weight, pairs=pairs)
     return solve_batch(batch, number_classes=K, terminals=terminals, hidden_dim=hidden_dim, epochs=epochs,
                        learning_rate=learning_rate, loss=loss, samples=samples, anneal_sweeps=anneal_sweeps,
-                       max_descent_sweeps=max_descent_sweeps, seed=seed, tabu_iterations=tabu_iterations, fixed=fixed)
+                       max_descent_sweeps=max_descent_sweeps, seed=seed, tabu_iterations=tabu_iterations, fixed=fixed,
+                       class_sizes=class_sizes, balance_iterations=balance_iterations)
 
 
 def solve_batch(batch: GraphBatch, *, number_classes: int = 2, terminals: bool = False, hidden_dim: int, epochs: int,
                 learning_rate: float, loss: str = "expected_cut", samples: int = 32, anneal_sweeps: int = 100,
-                max_descent_sweeps: int = 100, seed: int = 0, tabu_iterations: int = 0, fixed=None) -> MaxCutResult:
-    """Steps 2 to 5 of :func:`solve` on a ready batch - one built on the device or one built from handles: the batches
-    hold the same bytes, so the results do too.  ``fixed``: as :func:`solve`, with row ids of ``batch``."""
+                max_descent_sweeps: int = 100, seed: int = 0, tabu_iterations: int = 0, fixed=None, class_sizes=None,
+                balance_iterations: Optional[int] = None) -> MaxCutResult:
+    """Steps 2 to 6 of :func:`solve` on a ready batch - one built on the device or one built from handles: the batches
+    hold the same bytes, so the results do too.  ``fixed``: as :func:`solve`, with row ids of ``batch``;
+    ``class_sizes`` and ``balance_iterations``: as :func:`solve`."""
+    _check_sizes(class_sizes, balance_iterations, fixed)
     return _solve_fixed(_small_route(), batch, fixed, number_classes, terminals, hidden_dim, epochs, learning_rate, loss,
-                        samples, anneal_sweeps, max_descent_sweeps, seed, tabu_iterations)
+                        samples, anneal_sweeps, max_descent_sweeps, seed, tabu_iterations, class_sizes,
+                        balance_iterations)
 
 
 def solve_large(edge_index, ptr=None, num_nodes: Optional[int] = None, edge_weight=None, *, number_classes: int = 2,
                 terminals: bool = False, pairs: str = "both", hidden_dim: int, epochs: int, learning_rate: float,
                 loss: str = "expected_cut", samples: int = 32, anneal_sweeps: int = 100, max_descent_sweeps: int = 100,
-                seed: int = 0, tabu_iterations: int = 0, fixed=None) -> MaxCutResult:
+                seed: int = 0, tabu_iterations: int = 0, fixed=None, class_sizes=None,
+                balance_iterations: Optional[int] = None) -> MaxCutResult:
     """:func:`solve` for graphs of up to ``hip.LARGE_MAX_GRAPH_NODES`` (2^20) nodes: the same arguments, steps and
     result, with ``engine.LargeInstanceEngine`` (gmc_inst_large_*) as the trainer and the large decoders (one rounding,
     one sampler and one annealing call of gmc_large_*_t_f32; several workgroups share a graph).  It takes small graphs
@@ -119,9 +165,12 @@ def solve_large(edge_index, ptr=None, num_nodes: Optional[int] = None, edge_weig
     16 * hidden_dim bytes per node for parameters, gradient and Adam moments plus 8 * ld for the workspace (ld =
     hidden_dim rounded up to 32): 1.5 KB per node at hidden_dim = 64.  The tabu stage keeps a graph's state in one
     workgroup, so this route does not have it: ``tabu_iterations`` is taken for the sake of one signature and anything
-    but 0 raises ``NotImplementedError``."""
+    but 0 raises ``NotImplementedError``.  So are ``class_sizes`` and ``balance_iterations``: the balanced stage is the
+    tabu kernel's sibling, and ``class_sizes`` other than ``None`` raises ``NotImplementedError``."""
     if tabu_iterations:
         raise NotImplementedError(_NO_TABU)
+    if class_sizes is not None:
+        raise NotImplementedError(_NO_BALANCE)
     K, terminals = int(number_classes), bool(terminals)
     if not 2 <= K <= hip.KWAY_MAX_CLASSES:
         raise ValueError(f"number_classes must be in 2..{hip.KWAY_MAX_CLASSES}, got {K}")
@@ -137,9 +186,13 @@ def solve_large(edge_index, ptr=None, num_nodes: Optional[int] = None, edge_weig
 def solve_large_batch(batch: GraphBatch, *, number_classes: int = 2, terminals: bool = False, hidden_dim: int,
                       epochs: int, learning_rate: float, loss: str = "expected_cut", samples: int = 32,
                       anneal_sweeps: int = 100, max_descent_sweeps: int = 100, seed: int = 0,
-                      tabu_iterations: int = 0, fixed=None) -> MaxCutResult:
+                      tabu_iterations: int = 0, fixed=None, class_sizes=None,
+                      balance_iterations: Optional[int] = None) -> MaxCutResult:
     """:func:`solve_batch` through ``engine.LargeInstanceEngine`` and the large decoders: steps 2 to 4 of
-    :func:`solve_large` on a ready batch (``tabu_iterations``: as :func:`solve_large`; ``fixed``: as :func:`solve_batch`)."""
+    :func:`solve_large` on a ready batch (``tabu_iterations``, ``class_sizes``: as :func:`solve_large`; ``fixed``: as
+    :func:`solve_batch`)."""
+    if class_sizes is not None:
+        raise NotImplementedError(_NO_BALANCE)
     return _solve_fixed(_large_route(), batch, fixed, number_classes, terminals, hidden_dim, epochs, learning_rate, loss,
                         samples, anneal_sweeps, max_descent_sweeps, seed, tabu_iterations)
 
@@ -154,6 +207,27 @@ def _check_fixed(fixed, terminals: bool, number_classes: int) -> None:
     if not isinstance(fixed, (tuple, list)) or len(fixed) != 2:
         raise ValueError("fixed must be a pair (nodes, classes)")
     _check_pins(fixed[0], fixed[1], number_classes)
+
+
+def _check_sizes(class_sizes, balance_iterations, fixed) -> None:
+    """The argument errors of ``class_sizes`` that need no graph, raised before anything is built."""
+    if balance_iterations is not None and not 0 <= int(balance_iterations) < 1 << 31:
+        raise ValueError(f"balance_iterations must be None or in 0..2^31-1, got {balance_iterations}")
+    if class_sizes is not None and fixed is not None:
+        raise ValueError("class_sizes with fixed: a contracted super-node stands for many nodes and the balanced stage "
+                         "counts nodes, not node weights - pass one of the two")
+
+
+def _size_bounds(class_sizes, sizes, K: int, terminals: bool):
+    from .Testing import TestingNeuralNetwork as T
+    return T.class_size_bounds("solve", class_sizes, sizes, K, terminals)
+
+
+def _mean_abs_edge_weight(batch: GraphBatch) -> float:
+    """The annealing's temperature scale on the class_sizes path: the mean absolute edge weight, 1 when that is 0."""
+    vals = batch.host.vals
+    mean = 1.0 if vals is None or len(vals) == 0 else float(np.mean(np.abs(vals), dtype=np.float64))
+    return mean if mean > 0 else 1.0
 
 
 def _solve_fixed(route: "_Route", batch: GraphBatch, fixed, number_classes: int, terminals: bool, *args) -> MaxCutResult:
@@ -190,13 +264,15 @@ class _Route:
     """What tells :func:`solve_batch` from :func:`solve_large_batch`: the engine class, the refusal of a batch by its
     largest graph, and the three decoders as ``round(batch, P, terminals)``, ``sample(batch, P, samples, seed, terminals)``
     and ``anneal(batch, K, cands, inv_temp, seed, max_descent_sweeps, terminals)``; ``tabu(batch, K, cands, iterations,
-    seed, terminals)`` where the route has the stage."""
+    seed, terminals)`` and ``balance(batch, K, cands, lo, hi, iterations, seed, terminals)`` where the route has the
+    stage."""
     engine: type
     refuse: Callable
     round: Callable
     sample: Callable
     anneal: Callable
     tabu: Optional[Callable] = None
+    balance: Optional[Callable] = None
 
 
 def _small_route() -> _Route:
@@ -212,7 +288,10 @@ def _small_route() -> _Route:
                   lambda batch, K, cands, inv_temp, seed, sweeps, t: T._kway_anneal_on_gpu(batch, K, cands, inv_temp, seed,
                                                                                            sweeps, t),
                   lambda batch, K, cands, iterations, seed, t: T._kway_tabu_on_gpu(batch, K, cands, iterations,
-                                                                                   T.TABU_TENURE, seed, t))
+                                                                                   T.TABU_TENURE, seed, t),
+                  lambda batch, K, cands, lo, hi, iterations, seed, t: T._kway_balance_on_gpu(batch, K, cands, lo, hi,
+                                                                                              iterations, T.TABU_TENURE,
+                                                                                              seed, t))
 
 
 def _large_route() -> _Route:
@@ -232,7 +311,8 @@ def _large_route() -> _Route:
 
 def _solve_batch(route: _Route, batch: GraphBatch, number_classes: int, terminals: bool, hidden_dim: int, epochs: int,
                  learning_rate: float, loss: str, samples: int, anneal_sweeps: int, max_descent_sweeps: int,
-                 seed: int, tabu_iterations: int = 0, parts: Optional[dict] = None) -> MaxCutResult:
+                 seed: int, tabu_iterations: int = 0, class_sizes=None, balance_iterations: Optional[int] = None,
+                 parts: Optional[dict] = None) -> MaxCutResult:
     """``parts``: a dict that receives the partitions behind ``trained_cut``, ``rounded_cut`` (and ``annealed_cut``)."""
     from .Testing import TestingNeuralNetwork as T
     K, terminals = int(number_classes), bool(terminals)
@@ -245,6 +325,12 @@ def _solve_batch(route: _Route, batch: GraphBatch, number_classes: int, terminal
         raise ValueError(f"tabu_iterations must be in 0..2^31-1, got {tabu_iterations}")
     if tabu_iterations and route.tabu is None:
         raise NotImplementedError(_NO_TABU)
+    _check_sizes(class_sizes, balance_iterations, None)
+    bounds = None
+    if class_sizes is not None:
+        if route.balance is None:
+            raise NotImplementedError(_NO_BALANCE)
+        bounds = _size_bounds(class_sizes, batch.sizes, K, terminals)   # on the host, before anything is trained
     loss = hip.loss_name(loss)
     if batch.B:
         route.refuse(batch.n_max, K, loss)
@@ -270,18 +356,24 @@ def _solve_batch(route: _Route, batch: GraphBatch, number_classes: int, terminal
     if samples > 0:
         rows.append(route.sample(batch, P, int(samples), int(seed) & T._M64, terminals))
     cands = torch.cat(rows).contiguous()
-    inv_temp = T.anneal_schedule(int(anneal_sweeps), scale=T._mean_edge_weight(batch))
+    scale = T._mean_edge_weight(batch) if bounds is None else _mean_abs_edge_weight(batch)
+    inv_temp = T.anneal_schedule(int(anneal_sweeps), scale=scale)
     partition, cut, _ = route.anneal(batch, K, cands, inv_temp, seed, int(max_descent_sweeps), terminals)
     if parts is not None:
         parts.update(trained=best_S, rounded=rounded)
         if tabu_iterations:
             parts.update(annealed=partition)
-    if not tabu_iterations:
-        return MaxCutResult(partition, cut, trained_cut, rounded_cut, batch.goff)
-    # the annealing left its candidates in `cands`; the better of the two results per graph, chosen on the device
-    tabu_partition, tabu_cut = route.tabu(batch, K, cands.clone(), int(tabu_iterations), seed, terminals)[:2]
-    better = tabu_cut > cut
-    sizes = (batch.goff[1:] - batch.goff[:-1]).to(torch.int64)
-    rows = torch.repeat_interleave(better, sizes, output_size=batch.R)
-    return MaxCutResult(torch.where(rows, tabu_partition, partition), torch.where(better, tabu_cut, cut), trained_cut,
-                        rounded_cut, batch.goff, cut)
+    annealed_cut = None
+    if tabu_iterations:
+        # the annealing left its candidates in `cands`; the better of the two results per graph, chosen on the device
+        tabu_partition, tabu_cut = route.tabu(batch, K, cands.clone(), int(tabu_iterations), seed, terminals)[:2]
+        better = tabu_cut > cut
+        sizes = (batch.goff[1:] - batch.goff[:-1]).to(torch.int64)
+        rows = torch.repeat_interleave(better, sizes, output_size=batch.R)
+        partition, cut, annealed_cut = torch.where(rows, tabu_partition, partition), torch.where(better, tabu_cut, cut), cut
+    if bounds is None:
+        return MaxCutResult(partition, cut, trained_cut, rounded_cut, batch.goff, annealed_cut)
+    # the balanced stage starts from the annealed candidates too (a copy: repaired into the bounds, then searched)
+    iterations = 20 * int(batch.n_max) if balance_iterations is None else int(balance_iterations)
+    within, within_cut = route.balance(batch, K, cands.clone(), bounds[0], bounds[1], iterations, seed, terminals)[:2]
+    return MaxCutResult(within, within_cut, trained_cut, rounded_cut, batch.goff, annealed_cut, unconstrained_cut=cut)

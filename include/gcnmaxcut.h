@@ -1171,6 +1171,73 @@ int gmc_kway_tabu_f32(const gmc_batch *batch, int32_t K, int32_t terminals, int3
 int gmc_kway_tabu_fits(const gmc_batch *batch, int32_t K);
 int gmc_kway_tabu_shape(const gmc_batch *batch, int32_t K);
 
+/* ---- tabu search under class-size bounds (extension; K = 2 .. GMC_KWAY_MAX_CLASSES) ------------------------------------
+ *
+ * gmc_kway_tabu_f32 with a lower and an upper bound on the number of nodes of every class: max-bisection, balanced
+ * max-K-cut and, on negated weights, balanced minimum cut.  It is the max-bisection tabu of the literature: a best move,
+ * and where that move would break a bound, a best counter-move out of the class it entered.
+ *
+ * Everything of gmc_kway_tabu_f32 holds unchanged: fp32 throughout, every step ONE operation, no multiply; mix64, GOLD,
+ * h, r, span and tenure of its step 1; the tie rank (v - first - r) mod n_mov; the table W[v][k] and its update on a
+ * move (its step 4); first = terminals ? K : 0.
+ *
+ * Sizes.  size_lo and size_hi, int32 [B][K] in device memory: lo[c] and hi[c] of graph g are word g * K + c.
+ *   s[c] = the number of nodes of the graph whose class byte is c, terminals included; m[c] = the same count over the
+ *   movable nodes first..n-1.  A state is feasible iff lo[c] <= s[c] <= hi[c] for every class c, and
+ *   V = sum over c of max(0, lo[c] - s[c]) + max(0, s[c] - hi[c]) is its violation.
+ * Bounds admit a partition iff, with t = 1 under terminals and 0 without: lo[c] <= hi[c] and hi[c] >= t for every c, and
+ *   sum of max(lo[c], t) <= n <= sum of hi[c] (sums as unbounded integers).  A graph whose bounds admit none is skipped as
+ *   a graph of the wrong size is: nothing of it is written, by the chains or by the pick.  feasible [B] (or NULL)
+ *   receives 0 for such a graph and 1 for a graph that ran; the word of a graph of the wrong size is not written.
+ * Repair, before iteration 0 (also when iterations == 0).  While V > 0: among the moves (v: a -> b) of movable nodes v
+ *   with a = class(v) in 0..K-1 and b != a for which da + db < 0, where
+ *     da = -1 if s[a] > hi[a], +1 if s[a] <= lo[a], else 0;   db = -1 if s[b] < lo[b], +1 if s[b] >= hi[b], else 0
+ *   (the move changes V by da + db), the largest gain = W[v][a] - W[v][b] wins, ties going to the smallest v - first,
+ *   then to the smallest b; no bans, no hash.  The move is applied as tabu's step 4 (rel and until aside), s and m
+ *   follow.  Under bounds that admit a partition and class bytes in 0..K-1 such a move exists while V > 0 (a class over
+ *   its bound: some other class has room; otherwise some class sits above max(lo, t) and can give), every move lowers V
+ *   by 1 or 2 (the largest gain decides, not the larger drop), so the repair ends within V <= 2 n moves; it also ends
+ *   when no such move exists.  The repaired state is the base of the search: rel = best = 0.0f, best_it = 0, the snapshot is the repaired state,
+ *   until[v] = 0 for every v.  repairs [B][cands] (or NULL) receives the number of repair moves.
+ * Iteration it = 0..iterations-1:
+ *   1. as tabu's step 1.
+ *   2. A move (v: a -> b), v movable, a = class(v) in 0..K-1, b != a, gain = W[v][a] - W[v][b], is FREE iff
+ *      s[a] > lo[a] and s[b] < hi[b]; any other move is PAIRED and exists only if m[b] >= 1.  A free move is admissible
+ *      iff until[v] <= it, or rel + gain > best; a paired move iff until[v] <= it (no aspiration: the state after it
+ *      is not feasible).
+ *   3. as tabu's step 3: the largest gain, then the smallest rank, then the smallest b.  With no admissible move the
+ *      iteration moves nothing.
+ *   4. The move is applied as tabu's step 4: class(v) = b, the table, rel = rel + gain, until[v] = it + 1 + tenure.
+ *      After a free move s[a], m[a] lose one and s[b], m[b] gain one.  After a paired move the counter-move follows,
+ *      chosen from the updated table: among the movable u != v with class(u) = b the largest
+ *      gain' = W[u][b] - W[u][a] wins, ties going to the smallest rank of u; bans are ignored, and m[b] >= 1 says that
+ *      u exists.  class(u) = a, the table follows, rel = rel + gain', until[u] = it + 1 + tenure (the same tenure).
+ *      The sizes are then what they were.
+ *   5. as tabu's step 5, once per iteration, after the counter-move if there was one.
+ *   The state is feasible after the repair and after every iteration.  moves counts the iterations that moved a node.
+ * Result.  As gmc_kway_tabu_f32: the snapshot goes back into `assign`, best_iter, moves (and repairs), every candidate
+ *   scored into cut_all with the bits gmc_kway_tabu_f32 reports for the same bytes, and picked.  iterations == 0 repairs,
+ *   scores and picks.  A class byte outside 0..K-1 is inert as in tabu and counts for no class; the Python wrappers pass
+ *   none, and nothing is claimed about the feasibility of a chain that holds one.
+ * By construction.  With lo[c] = 0 and hi[c] = n for every class every move is free and nothing is repaired: every
+ *   output is then byte for byte gmc_kway_tabu_f32's.  Every candidate written is feasible, so the pick is.
+ *
+ * Argument checks, before any HIP call, in gmc_kway_tabu_f32's order and with its codes; size_lo and size_hi are required
+ * pointers (NULL: GMC_ERR_NULL), best_iter, moves, repairs and feasible may be NULL.  The bounds themselves are device
+ * data and are judged by the kernels, graph by graph.  The launcher, the LDS (n_pad * (4 K + 6) bytes per chain: the
+ * sizes and bounds are wave-uniform registers), gmc_kway_balance_fits and gmc_kway_balance_shape are gmc_kway_tabu_f32's,
+ * value for value.  Two launches on the caller's stream, no atomics, no spin waits, no scratch, bitwise reproducible. */
+int gmc_kway_balance_f32(const gmc_batch *batch, int32_t K, int32_t terminals, int32_t cands,
+                         int8_t *assign /*[cands][R], in/out*/, const int32_t *size_lo /*[B][K]*/,
+                         const int32_t *size_hi /*[B][K]*/, int32_t iterations, int32_t tenure_base,
+                         int32_t tenure_span, int32_t tenure_div, uint64_t seed, float *cut_all /*[B][cands]*/,
+                         int32_t *best_assign /*[R]*/, float *best_cut /*[B]*/, int32_t *best_idx /*[B]*/,
+                         int32_t *best_iter /*[B][cands] or NULL*/, int32_t *moves /*[B][cands] or NULL*/,
+                         int32_t *repairs /*[B][cands] or NULL*/, int32_t *feasible /*[B] or NULL*/,
+                         gmc_stream_t stream);
+int gmc_kway_balance_fits(const gmc_batch *batch, int32_t K);
+int gmc_kway_balance_shape(const gmc_batch *batch, int32_t K);
+
 /* ---- the rounding and the K-class local search beyond GMC_MAX_GRAPH_NODES (extension) ---------------------------------
  *
  * gmc_round_conditional_f32 and gmc_kway_refine_anneal_f32 keep a graph's state in one workgroup's LDS and stop at
