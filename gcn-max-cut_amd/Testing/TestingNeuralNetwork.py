@@ -356,11 +356,24 @@ def _rounding_classes(classes: int) -> int:
     return K
 
 
-def _call(name: str, terminals: bool, head: tuple, tail: tuple) -> None:
+def _cost_tensor(batch: GraphBatch, K: int, node_cost) -> Optional[torch.Tensor]:
+    """``node_cost`` as the ``_c`` entry points read it: a contiguous [R, K] float32 tensor on the batch's device."""
+    if node_cost is None:
+        return None
+    if not isinstance(node_cost, torch.Tensor) or tuple(node_cost.shape) != (batch.R, K):
+        raise ValueError(f"node_cost must be a [{batch.R}, {K}] tensor (one row per batch row, one column per class)")
+    return node_cost.to(batch.device, torch.float32).contiguous()
+
+
+def _call(name: str, terminals: bool, head: tuple, tail: tuple, node_cost: Optional[torch.Tensor] = None) -> None:
     """Calls the entry point ``name`` with the arguments ``head + tail`` - or, without terminals, its ``_t`` twin, whose
-    ``terminals`` argument (0) stands between the two - and raises on a status code."""
+    ``terminals`` argument (0) stands between the two; or, with ``node_cost`` ([R, K] float32 on the device), its ``_c``
+    twin, which takes ``terminals`` and the cost array there - and raises on a status code."""
     lib = hip.load()
-    if terminals:
+    if node_cost is not None:
+        twin = name[:-len("_f32")] + "_c_f32"
+        hip.check(getattr(lib, twin)(*head, int(bool(terminals)), hip.ptr(node_cost), *tail), twin)
+    elif terminals:
         hip.check(getattr(lib, name)(*head, *tail), name)
     else:
         twin = name[:-len("_f32")] + "_t_f32"
@@ -375,11 +388,13 @@ def _first_argmax(P: torch.Tensor) -> torch.Tensor:
     return torch.where(P == top, ids, torch.full_like(ids, K)).min(dim=1).values.clamp_(max=K - 1)
 
 
-def _round_on_gpu(batch: GraphBatch, P: torch.Tensor, descent_sweeps: int, terminals: bool = True):
+def _round_on_gpu(batch: GraphBatch, P: torch.Tensor, descent_sweeps: int, terminals: bool = True, node_cost=None):
     """Rounding by conditional expectations + descent (gmc_round_conditional_f32) of P [R, K] for every graph of the
     batch, one launch; returns the assignment [R] int8, and per graph its cut, the expected cut and the descent sweeps
-    run."""
+    run.  ``node_cost`` [R, K]: per-node class costs (gmc_round_conditional_c_f32) - cut and expected cut are then the
+    objective, cut minus cost, and its expectation."""
     K = _rounding_classes(P.shape[1])
+    node_cost = _cost_tensor(batch, K, node_cost)
     if descent_sweeps < 0:
         raise ValueError(f"descent_sweeps must be >= 0, got {descent_sweeps}")
     _needs_terminals(batch, K, terminals)
@@ -393,7 +408,8 @@ def _round_on_gpu(batch: GraphBatch, P: torch.Tensor, descent_sweeps: int, termi
     order, cgoff, cptr = batch.refine_order(K, terminals)
     p = hip.ptr
     _call("gmc_round_conditional_f32", terminals, (batch.ref(), p(P.contiguous()), K),
-          (p(order), p(cgoff), p(cptr), int(descent_sweeps), p(assign), p(cut), p(expected), p(sweeps), hip.stream()))
+          (p(order), p(cgoff), p(cptr), int(descent_sweeps), p(assign), p(cut), p(expected), p(sweeps), hip.stream()),
+          node_cost)
     return assign, cut, expected, sweeps
 
 
@@ -675,9 +691,11 @@ def _needs_terminals(batch: GraphBatch, K: int, terminals: bool = True) -> None:
 
 
 def _kway_sample_on_gpu(batch: GraphBatch, P: torch.Tensor, iterations: int, seed: int, indices, keep_samples: bool,
-                        terminals: bool = True):
-    """The seeded sampler at K = P.shape[1] classes (gmc_kway_decode_sample_seeded_f32), as ``_sample_seeded_on_gpu``."""
+                        terminals: bool = True, node_cost=None):
+    """The seeded sampler at K = P.shape[1] classes (gmc_kway_decode_sample_seeded_f32), as ``_sample_seeded_on_gpu``.
+    ``node_cost`` [R, K]: the samples are scored by cut minus cost (gmc_kway_decode_sample_seeded_c_f32)."""
     K = _search_classes("the K-class sampler", P.shape[1])
+    node_cost = _cost_tensor(batch, K, node_cost)
     _needs_terminals(batch, K, terminals)
     keys = sample_keys(seed, range(batch.B) if indices is None else indices)
     if keys.size != batch.B:
@@ -691,7 +709,8 @@ def _kway_sample_on_gpu(batch: GraphBatch, P: torch.Tensor, iterations: int, see
     best_iter = torch.empty(batch.B, dtype=torch.int32, device=dev)
     p = hip.ptr
     _call("gmc_kway_decode_sample_seeded_f32", terminals, (batch.ref(), p(P.contiguous()), K),
-          (p(gkey), iterations, p(assign_all), p(cut_all), p(best_assign), p(best_cut), p(best_iter), hip.stream()))
+          (p(gkey), iterations, p(assign_all), p(cut_all), p(best_assign), p(best_cut), p(best_iter), hip.stream()),
+          node_cost)
     return best_assign, best_cut, cut_all, assign_all
 
 
@@ -720,11 +739,12 @@ def sampling_optimization(node_probabilities, graph, iterations: int = 200, *, s
 
 
 def _kway_anneal_on_gpu(batch: GraphBatch, K: int, assign: torch.Tensor, inv_temp: np.ndarray, seed: int,
-                        max_descent_sweeps: int, terminals: bool = True):
+                        max_descent_sweeps: int, terminals: bool = True, node_cost=None):
     """Annealing + descent at K classes (gmc_kway_refine_anneal_f32) over the candidates assign [cands, R] int8, in
     place; returns the best assignment [R], its cut and candidate index per graph.  No annealing sweeps: the K-class
-    local search."""
+    local search.  ``node_cost`` [R, K]: moves and scores follow cut minus cost (gmc_kway_refine_anneal_c_f32)."""
     _needs_terminals(batch, K, terminals)
+    node_cost = _cost_tensor(batch, K, node_cost)
     dev = batch.device
     cands = int(assign.shape[0])
     order, cgoff, cptr = batch.refine_order(K, terminals)
@@ -738,7 +758,8 @@ def _kway_anneal_on_gpu(batch: GraphBatch, K: int, assign: torch.Tensor, inv_tem
     p = hip.ptr
     _call("gmc_kway_refine_anneal_f32", terminals, (batch.ref(), K),
           (p(order), p(cgoff), p(cptr), cands, p(assign), p(inv_t), sweeps, p(levels), int(seed) & _M64,
-           int(max_descent_sweeps), p(cut_all), p(best_assign), p(best_cut), p(best_idx), None, None, hip.stream()))
+           int(max_descent_sweeps), p(cut_all), p(best_assign), p(best_cut), p(best_idx), None, None, hip.stream()),
+          node_cost)
     return best_assign, best_cut, best_idx
 
 

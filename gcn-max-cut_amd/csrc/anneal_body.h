@@ -55,14 +55,20 @@ __device__ __forceinline__ LdsCsr anneal_stage_csr(const AnnealArgs &a, const An
 }
 
 // Steps 1-3 of gmc_kway_refine_anneal_f32 on the state in sa (sb: a copy of it, the best-state buffer) for candidate
-// blockIdx.x of graph blockIdx.y; on return sa holds the result and every thread may read it.
-template <int K, class G>
+// blockIdx.x of graph blockIdx.y; on return sa holds the result and every thread may read it.  nc: the graph's rows of
+// a.node_cost (class_sums_k's and block_cost's argument) or NULL: the sums start from it and the best state is kept by
+// the objective, cut - cost.  COST says at compile time whether nc may be set: without it the body is, statement for
+// statement, the one it was before costs existed (the run-time test alone cost 1.6 % at K = 3).
+template <int K, bool COST = false, class G>
 __device__ __forceinline__ void anneal_body_k(const AnnealArgs &a, const G &g, unsigned char *sa, unsigned char *sb,
-                                              const float *lv, int n, int k0, int classes, float *red, int *flag) {
+                                              const float *lv, int n, int k0, int classes, float *red, int *flag,
+                                              const float *nc = nullptr) {
     const int cand = blockIdx.x, gi = blockIdx.y;
     int snap = 0;
     if (a.anneal_sweeps > 0) {
-        float best_cut = gmc::block_cut_csr(g.rp, g.col, g.vals, sa, n, red);   // thread 0
+        float best_cut;   // thread 0
+        if constexpr (COST) best_cut = gmc::block_score_csr<K>(g.rp, g.col, g.vals, nc, sa, n, red);
+        else best_cut = gmc::block_cut_csr(g.rp, g.col, g.vals, sa, n, red);
         __syncthreads();   // (thread 0 has read red before a graph without classes recounts)
         for (int s = 0; s < a.anneal_sweeps; ++s) {
             const float inv_t = a.inv_temp[s];
@@ -73,14 +79,16 @@ __device__ __forceinline__ void anneal_body_k(const AnnealArgs &a, const G &g, u
                 for (int i = a.cptr[k0 + k] + threadIdx.x; i < hi; i += blockDim.x) {
                     const int l = g.node(i);
                     if (!g.movable(l, n)) continue;   // not a movable row of this graph: never touch LDS for it
-                    const Sums<K> w = gmc::class_sums_k<K>(g.rp, g.col, g.vals, sa, l);
+                    const Sums<K> w = gmc::class_sums_k<K>(g.rp, g.col, g.vals, sa, l, COST ? nc : nullptr);
                     const u64 h = mix64(base + GMC_GOLD * (u64)(unsigned)l);
                     int kk;
                     if (gmc::anneal_move<K>(w, sa[l], inv_t, lv, h, kk)) sa[l] = (unsigned char)kk;
                 }
                 __syncthreads();   // the next class, or the recount, reads what this one wrote
             }
-            const float cut = gmc::block_cut_csr(g.rp, g.col, g.vals, sa, n, red);
+            float cut;
+            if constexpr (COST) cut = gmc::block_score_csr<K>(g.rp, g.col, g.vals, nc, sa, n, red);
+            else cut = gmc::block_cut_csr(g.rp, g.col, g.vals, sa, n, red);
             if (threadIdx.x == 0) {
                 const int better = cut > best_cut;
                 if (better) best_cut = cut;
@@ -97,7 +105,7 @@ __device__ __forceinline__ void anneal_body_k(const AnnealArgs &a, const G &g, u
         __syncthreads();
     }
     // descent: the local search's sweeps from the best state
-    const int s = descent_sweeps<K>(g, a.cptr, k0, classes, sa, n, a.max_descent_sweeps);
+    const int s = descent_sweeps<K>(g, a.cptr, k0, classes, sa, n, a.max_descent_sweeps, COST ? nc : nullptr);
     if (threadIdx.x == 0) {
         if (a.snap_sweep) a.snap_sweep[(long)gi * a.cands + cand] = snap;
         if (a.sweeps) a.sweeps[(long)gi * a.cands + cand] = s;

@@ -44,6 +44,7 @@ struct AnnealArgs {
     int *sweeps;             // [B][cands] or NULL
     int staged;              // the launch has room for the staged copy
     int n_pad, off_starts, off_vals, off_order, off_ids;   // LDS layout (bytes from the dynamic base)
+    const float *node_cost;  // [R][K] by batch row or NULL (gmc_kway_refine_anneal_c_f32; read from global memory)
 };
 
 // the graph as the batch holds it in global memory

@@ -865,6 +865,7 @@ struct InstCall {
     InstWorkspace w{}; hipStream_t st = nullptr;
     int terminals = 1;   // 0: the head overrides no row (the _t entry points)
     bool large = false;  // gmc_inst_large_*: the kernels of instance_large.hip, graphs up to GMC_LARGE_MAX_GRAPH_NODES nodes
+    const float *node_cost = nullptr;   // [R,K] per-node class costs of the loss (the _c entry points; never with large)
 };
 
 int inst_open(InstCall &c, bool training, void *workspace, size_t workspace_bytes, gmc_stream_t stream, const float *P,
@@ -912,7 +913,7 @@ int inst_forward_body(const InstCall &c, float C, float *P, int32_t *S, float *l
         return gmc_inst_large_head_launch(b, w.Z0, m->b2, C, m->K, loss_of(m), c.terminals, P, S, loss, w.S,
                                           db2 ? w.GZd : nullptr, w.headpart, w.GY2, db2, c.st);
     return gmc_kway_head_launch(b, w.Z0, m->b2, C, m->K, loss_of(m), P, S, loss, db2 ? w.GY2 : nullptr, db2, c.st, m->K,
-                                c.terminals);
+                                c.terminals, c.node_cost);
 }
 
 int inst_backward_body(const InstCall &c, const InstGrad &g) {
@@ -965,10 +966,12 @@ int inst_train_call(InstCall c, float C, void *workspace, size_t workspace_bytes
     return rc ? rc : inst_backward_body(c, g);
 }
 
-InstCall inst_call_of(const gmc_batch *batch, const gmc_model *model, int terminals, bool large) {
+InstCall inst_call_of(const gmc_batch *batch, const gmc_model *model, int terminals, bool large,
+                      const float *node_cost = nullptr) {
     InstCall c{batch, model};
     c.terminals = terminals;
     c.large = large;
+    c.node_cost = node_cost;
     return c;
 }
 
@@ -977,7 +980,14 @@ InstCall inst_call_of(const gmc_batch *batch, const gmc_model *model, int termin
 extern "C" int gmc_inst_forward_t(const gmc_batch *batch, const gmc_model *model, int32_t terminals, float C,
                                   void *workspace, size_t workspace_bytes, float *P, int32_t *S, float *loss,
                                   gmc_stream_t stream) {
-    return inst_forward_call(inst_call_of(batch, model, terminals, false), C, workspace, workspace_bytes, P, S, loss, stream);
+    return gmc_inst_forward_c(batch, model, terminals, nullptr, C, workspace, workspace_bytes, P, S, loss, stream);
+}
+
+extern "C" int gmc_inst_forward_c(const gmc_batch *batch, const gmc_model *model, int32_t terminals,
+                                  const float *node_cost, float C, void *workspace, size_t workspace_bytes, float *P,
+                                  int32_t *S, float *loss, gmc_stream_t stream) {
+    return inst_forward_call(inst_call_of(batch, model, terminals, false, node_cost), C, workspace, workspace_bytes, P, S,
+                             loss, stream);
 }
 
 extern "C" int gmc_inst_forward(const gmc_batch *batch, const gmc_model *model, float C, void *workspace,
@@ -988,8 +998,15 @@ extern "C" int gmc_inst_forward(const gmc_batch *batch, const gmc_model *model, 
 extern "C" int gmc_inst_train_fwd_bwd_t(const gmc_batch *batch, const gmc_model *model, int32_t terminals, float C,
                                         void *workspace, size_t workspace_bytes, float *P, int32_t *S, float *loss,
                                         float *grad, gmc_stream_t stream) {
-    return inst_train_call(inst_call_of(batch, model, terminals, false), C, workspace, workspace_bytes, P, S, loss, grad,
-                           stream);
+    return gmc_inst_train_fwd_bwd_c(batch, model, terminals, nullptr, C, workspace, workspace_bytes, P, S, loss, grad,
+                                    stream);
+}
+
+extern "C" int gmc_inst_train_fwd_bwd_c(const gmc_batch *batch, const gmc_model *model, int32_t terminals,
+                                        const float *node_cost, float C, void *workspace, size_t workspace_bytes,
+                                        float *P, int32_t *S, float *loss, float *grad, gmc_stream_t stream) {
+    return inst_train_call(inst_call_of(batch, model, terminals, false, node_cost), C, workspace, workspace_bytes, P, S,
+                           loss, grad, stream);
 }
 
 extern "C" int gmc_inst_train_fwd_bwd(const gmc_batch *batch, const gmc_model *model, float C, void *workspace,

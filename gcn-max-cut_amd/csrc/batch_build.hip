@@ -654,7 +654,31 @@ int arrange_launch(int B, int R, int n_max, const int32_t *goff, const int32_t *
     return GMC_OK;
 }
 
+// out[r] = +0 plus the weights of row r's entries one after the other in the row's (sorted) order, the entry on the
+// diagonal skipped; one thread per row, so the order holds by construction (gmc_row_weight_sums_f32)
+__global__ __launch_bounds__(kThreads) void bb_row_weight_sums_kernel(int R, const int32_t *rowptr, const int32_t *gcol,
+                                                                      const float *vals, float *out) {
+    const long r = (long)blockIdx.x * kThreads + threadIdx.x;
+    if (r >= R) return;
+    float s = 0.f;
+    for (int e = rowptr[r]; e < rowptr[r + 1]; ++e)
+        if (gcol[e] != r) s += vals ? vals[e] : 1.0f;
+    out[r] = s;
+}
+
 }  // namespace
+
+extern "C" int gmc_row_weight_sums_f32(int32_t R, const int32_t *rowptr, const int32_t *gcol, const float *vals,
+                                       float *out, gmc_stream_t stream) {
+    if (!rowptr || !out) return GMC_ERR_NULL;
+    if (R < 0) return GMC_ERR_SHAPE;
+    if (R == 0) return GMC_OK;
+    if (!gcol) return GMC_ERR_NULL;
+    hipLaunchKernelGGL(bb_row_weight_sums_kernel, dim3((R + kThreads - 1) / kThreads), dim3(kThreads), 0,
+                       static_cast<hipStream_t>(stream), R, rowptr, gcol, vals, out);
+    GMC_LAUNCH_CHECK();
+    return GMC_OK;
+}
 
 extern "C" size_t gmc_batch_build_workspace_bytes(int32_t B, int32_t R, int64_t E) {
     if (B < 0 || R < 0 || E < 0 || E > INT32_MAX) return 0;

@@ -37,6 +37,41 @@ __device__ __forceinline__ float block_cut(const gmc_batch &b, const unsigned ch
     return block_cut_csr(b.rowptr + r0, b.lcol, b.vals, sa, n, red);
 }
 
+// Cost of the assignment `sa` under the per-node class costs nc ([n][K] by local id: the caller's node_cost + r0 * K):
+// the sum of nc[l][sa[l]], a class byte outside 0..K-1 adding nothing, over the rows l = tid, tid + 256, ... per thread,
+// a butterfly per wave, the four wave sums in block_cut_csr's order.  Every thread of the 256-thread workgroup must
+// call it (two barriers: the first lets thread 0 finish reading a block_cut's red); thread 0 gets the cost.
+template <int K>
+__device__ __forceinline__ float block_cost(const float *nc, const unsigned char *sa, int n, float *red) {
+    float cost = 0.f;
+    for (int l = threadIdx.x; l < n; l += blockDim.x) {
+        const unsigned c = sa[l];
+        cost += c < (unsigned)K ? nc[(long)l * K + c] : 0.f;
+    }
+    cost = wave_sum(cost);
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = cost;
+    __syncthreads();
+    return ((red[0] + red[1]) + red[2]) + red[3];
+}
+
+// The score of a state wherever one is scored: block_cut_csr, and with costs (nc != NULL, workgroup-uniform) one fp32
+// subtraction of block_cost from it.  nc == NULL is block_cut_csr and nothing else.
+template <int K, class RP, class COL>
+__device__ __forceinline__ float block_score_csr(const RP *rp, const COL *col, const float *vals, const float *nc,
+                                                 const unsigned char *sa, int n, float *red) {
+#pragma clang fp contract(off)
+    const float cut = block_cut_csr(rp, col, vals, sa, n, red);
+    if (!nc) return cut;
+    const float cost = block_cost<K>(nc, sa, n, red);
+    return cut - cost;
+}
+template <int K>
+__device__ __forceinline__ float block_score(const gmc_batch &b, const float *nc, const unsigned char *sa, int r0, int n,
+                                             float *red) {
+    return block_score_csr<K>(b.rowptr + r0, b.lcol, b.vals, nc, sa, n, red);
+}
+
 struct PickArgs {
     gmc_batch b;
     int iters;                     // candidates per graph

@@ -65,6 +65,7 @@ struct HeadKArgs {
     float *db2part;    // [B,K]
     long b2_stride;    // floats from one graph's bias to the next: 0 = one shared conv2.bias, K = b2 [B,K] (instance.hip)
     int terminals;     // 1: rows 0..K-1 of a graph are the terminals; 0: no row is overridden (gmc_inst_*_t)
+    const float *node_cost;   // [R,K] by batch row or NULL: the per-node class costs of the loss (gmc_inst_*_c)
 };
 
 // floats of dynamic LDS: sA [NP,K], sP [NP,K], SOFT: the terminals' own rows [K,K], sS [NP], the block sum's [waves, K+1]
@@ -78,6 +79,10 @@ __host__ __device__ inline size_t head_k_lds_floats(int n_max, int K, bool soft)
 // A graph with fewer than K nodes (the host refuses one) has min(K, n) terminals: no access leaves the graph's rows.
 // Without terminals (a.terminals == 0, a run-time value: the same instantiation) there are none: no row is overridden, S
 // is the first maximum of every row, and both losses are those of gmc_fn_cut_loss_f32 with terminals = 0.
+// With a.node_cost (a run-time pointer: the same instantiation) the loss is -C (cut - costsum), costsum = sum_u
+// node_cost_u . Pt_u (SOFT) or sum_u node_cost[u][S_u]: gp starts from the node's cost row, so GP_u = C (sum_v w_uv Pt_v +
+// node_cost_u), and the row's accumulator of the doubled cut takes cut_u - 2 cost_u - one sum, one block reduction,
+// the LDS as it was.
 template <int K, bool SOFT>
 __global__ __launch_bounds__(head_k_threads(K)) void head_k_kernel(HeadKArgs a) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -146,9 +151,18 @@ __global__ __launch_bounds__(head_k_threads(K)) void head_k_kernel(HeadKArgs a) 
     for (int l = threadIdx.x; l < n; l += blockDim.x) {
         const int r = r0 + l;
         float gp[K] = {}, cut = 0.f;
+        if (a.node_cost) {
+#pragma unroll
+            for (int k = 0; k < K; ++k) gp[k] = a.node_cost[(long)r * K + k];
+        }
+        float cost = 0.f;   // the node's share of costsum
         if constexpr (SOFT) {
             float u[K];
             load_row<K>(sP, l, u);
+            if (a.node_cost) {
+#pragma unroll
+                for (int k = 0; k < K; ++k) cost += gp[k] * u[k];
+            }
             for (int e = a.b.rowptr[r]; e < a.b.rowptr[r + 1]; ++e) {
                 const float w = a.b.vals ? a.b.vals[e] : 1.0f;
                 float q[K];
@@ -160,6 +174,10 @@ __global__ __launch_bounds__(head_k_threads(K)) void head_k_kernel(HeadKArgs a) 
             }
         } else {
             const int me = sS[l];
+            if (a.node_cost) {
+#pragma unroll
+                for (int k = 0; k < K; ++k) cost = me == k ? gp[k] : cost;
+            }
             for (int e = a.b.rowptr[r]; e < a.b.rowptr[r + 1]; ++e) {
                 const float w = a.b.vals ? a.b.vals[e] : 1.0f;
                 const int sc = sS[a.b.lcol[e]];
@@ -168,6 +186,7 @@ __global__ __launch_bounds__(head_k_threads(K)) void head_k_kernel(HeadKArgs a) 
                 cut += sc != me ? w : 0.f;
             }
         }
+        if (a.node_cost) cut -= 2.0f * cost;   // (acc[0] is halved below)
         acc[0] += cut;
         if (train) {
             float p[K];
@@ -374,13 +393,13 @@ static int head_k_launch(const HeadKArgs &a, size_t lds, hipStream_t st) {
 // GY2 == nullptr: forward only.  The graphs' tiles must fit a CU's LDS (GMC_ERR_GRAPH_SIZE otherwise).
 int gmc_kway_head_launch(const gmc_batch *b, const float *Z0, const float *b2, float C, int K, int loss_kind, float *P,
                          int32_t *S, float *loss, float *GY2, float *db2part, hipStream_t st, long b2_stride,
-                         int terminals) {
+                         int terminals, const float *node_cost) {
     if (!b || !Z0 || !b2 || !P || (GY2 && !db2part)) return GMC_ERR_NULL;
     if (K < 2 || K > GMC_KWAY_MAX_CLASSES) return GMC_ERR_CLASSES;
     const size_t lds = gmc_kway_head_lds_bytes(b->n_max, K, loss_kind);
     if (lds > GMC_KWAY_LDS_BYTES) return GMC_ERR_GRAPH_SIZE;
     if (b->B == 0) return GMC_OK;
-    HeadKArgs a{*b, Z0, b2, C, P, S, loss, GY2, db2part, b2_stride, terminals};
+    HeadKArgs a{*b, Z0, b2, C, P, S, loss, GY2, db2part, b2_stride, terminals, node_cost};
     const bool soft = loss_kind == GMC_LOSS_EXPECTED_CUT;
     GMC_KWAY_DISPATCH(K, return soft ? head_k_launch<KK, true>(a, lds, st) : head_k_launch<KK, false>(a, lds, st));
     return GMC_OK;

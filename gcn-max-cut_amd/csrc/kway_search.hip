@@ -53,6 +53,7 @@ struct SeededArgs {
     int *best_assign;        // [R]        (the pick kernel)
     float *best_cut;         // [B]
     int *best_iter;          // [B]
+    const float *node_cost;  // [R][K] or NULL: a sample scores cut - cost (gmc_kway_decode_sample_seeded_c_f32)
 };
 
 template <int K>
@@ -71,7 +72,8 @@ __global__ __launch_bounds__(256) void sample_seeded_k_kernel(SeededArgs a) {
         if (a.assign_all) a.assign_all[(long)it * a.b.R + r0 + l] = (signed char)c;
     }
     __syncthreads();
-    const float cut = gmc::block_cut(a.b, sa, r0, n, red);
+    const float *nc = a.node_cost ? a.node_cost + (long)r0 * K : nullptr;
+    const float cut = gmc::block_score<K>(a.b, nc, sa, r0, n, red);
     if (threadIdx.x == 0) a.cut_all[(long)g * a.iters + it] = cut;
 }
 
@@ -104,45 +106,30 @@ int sample_launch_k(const SeededArgs &a, hipStream_t st) {
 // what a sampler entry point does once its arguments are checked (B > 0, K in 2..8; first = K or 0)
 int sample_launch(const gmc_batch *batch, const float *P, int K, int first, const uint64_t *gkey, int iters,
                   int8_t *assign_all, float *cut_all, int32_t *best_assign, float *best_cut, int32_t *best_iter,
-                  gmc_stream_t stream) {
+                  gmc_stream_t stream, const float *node_cost = nullptr) {
     hipStream_t st = static_cast<hipStream_t>(stream);
     const SeededArgs a{*batch, P, reinterpret_cast<const u64 *>(gkey), iters, first,
-                       reinterpret_cast<signed char *>(assign_all), cut_all, best_assign, best_cut, best_iter};
+                       reinterpret_cast<signed char *>(assign_all), cut_all, best_assign, best_cut, best_iter, node_cost};
     GMC_KWAY_DISPATCH(K, return sample_launch_k<KK>(a, st));
     return GMC_OK;
 }
 
 // ---- annealing + descent ------------------------------------------------------------------------------------------
 
+// Two kernels over one body text (anneal_kernel_body.inc, which says why): anneal_k_kernel<K> is the launch without
+// per-node class costs and keeps its name and, instruction for instruction, its code; anneal_k_cost_kernel<K> is the
+// launch with them (a.node_cost != NULL).
 template <int K>
 __global__ __launch_bounds__(256) void anneal_k_kernel(AnnealArgs a) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
-    __shared__ float red[4];
-    __shared__ int flag;
-    const int cand = blockIdx.x, gi = blockIdx.y;
-    const int r0 = a.b.goff[gi];
-    const int n = a.b.goff[gi + 1] - r0;
-    if (n > a.b.n_max || n < a.first) return;   // (the LDS is sized by n_max; a graph without its terminals is skipped)
-    float *lv = reinterpret_cast<float *>(lds);
-    unsigned char *sa = lds + 4 * GMC_ANNEAL_LEVELS;
-    unsigned char *sb = sa + a.n_pad;
-    signed char *as = a.assign + (long)cand * a.b.R + r0;
-    for (int l = threadIdx.x; l < n; l += blockDim.x) sa[l] = sb[l] = (unsigned char)as[l];
-    if (a.anneal_sweeps > 0)
-        for (int i = threadIdx.x; i < GMC_ANNEAL_LEVELS; i += blockDim.x) lv[i] = a.levels[i];
-    const gmc::AnnealGraph q = gmc::anneal_graph(a, gi, r0, n);
-    if (gmc::anneal_fits_lds(a, q)) {
-        const LdsCsr g = gmc::anneal_stage_csr(a, q, lds);
-        __syncthreads();
-        gmc::anneal_body_k<K>(a, g, sa, sb, lv, n, q.k0, q.classes, red, &flag);
-    } else {
-        __syncthreads();
-        const GlobalCsr g{a.b.rowptr + r0, a.b.lcol, a.b.vals, a.order, r0, a.first};
-        gmc::anneal_body_k<K>(a, g, sa, sb, lv, n, q.k0, q.classes, red, &flag);
-    }
-    for (int l = threadIdx.x; l < n; l += blockDim.x) as[l] = (signed char)sa[l];
-    const float cut = gmc::block_cut(a.b, sa, r0, n, red);   // scored as gmc_refine_local_f32 scores
-    if (threadIdx.x == 0) a.cut_all[(long)gi * a.cands + cand] = cut;
+#define GMC_COST false
+#include "anneal_kernel_body.inc"
+#undef GMC_COST
+}
+template <int K>
+__global__ __launch_bounds__(256) void anneal_k_cost_kernel(AnnealArgs a) {
+#define GMC_COST true
+#include "anneal_kernel_body.inc"
+#undef GMC_COST
 }
 
 struct KPickArgs {
@@ -159,7 +146,10 @@ __global__ __launch_bounds__(256) void anneal_k_pick_kernel(KPickArgs a) {
 template <int K>
 int anneal_launch_k(const AnnealArgs &a, int lds_bytes, hipStream_t st) {
     GmcProbeScope probe(GMC_K_ANNEAL, st);
-    hipLaunchKernelGGL((anneal_k_kernel<K>), dim3(a.cands, a.b.B), dim3(256), (size_t)lds_bytes, st, a);
+    if (a.node_cost)
+        hipLaunchKernelGGL((anneal_k_cost_kernel<K>), dim3(a.cands, a.b.B), dim3(256), (size_t)lds_bytes, st, a);
+    else
+        hipLaunchKernelGGL((anneal_k_kernel<K>), dim3(a.cands, a.b.B), dim3(256), (size_t)lds_bytes, st, a);
     GMC_LAUNCH_CHECK();
     return GMC_OK;
 }
@@ -168,12 +158,13 @@ int anneal_launch_k(const AnnealArgs &a, int lds_bytes, hipStream_t st) {
 int anneal_launch(const gmc_batch *batch, int K, int first, const int32_t *order, const int32_t *cgoff, const int32_t *cptr,
                   int cands, int8_t *assign, const float *inv_temp, int anneal_sweeps, const float *levels,
                   uint64_t seed, int max_descent_sweeps, float *cut_all, int32_t *best_assign, float *best_cut,
-                  int32_t *best_idx, int32_t *snap_sweep, int32_t *sweeps, gmc_stream_t stream) {
+                  int32_t *best_idx, int32_t *snap_sweep, int32_t *sweeps, gmc_stream_t stream,
+                  const float *node_cost = nullptr) {
     hipStream_t st = static_cast<hipStream_t>(stream);
     const AnnealLayout L = gmc::anneal_layout(batch);
     const AnnealArgs a{*batch, order, cgoff, cptr, cands, anneal_sweeps, max_descent_sweeps, first, inv_temp, levels, seed,
                        reinterpret_cast<signed char *>(assign), cut_all, snap_sweep, sweeps,
-                       L.staged, L.n_pad, L.off_starts, L.off_vals, L.off_order, L.off_ids};
+                       L.staged, L.n_pad, L.off_starts, L.off_vals, L.off_order, L.off_ids, node_cost};
     int rc = GMC_OK;
     GMC_KWAY_DISPATCH(K, rc = anneal_launch_k<KK>(a, L.bytes, st));
     if (rc != GMC_OK) return rc;
@@ -198,10 +189,10 @@ extern "C" int gmc_decode_sample_seeded_f32(const gmc_batch *batch, const float 
     return sample_launch(batch, P, 3, 3, gkey, iters, assign_all, cut_all, best_assign, best_cut, best_iter, stream);
 }
 
-// what gmc_kway_decode_sample_seeded_f32 and its _t twin do (terminals: 0 or 1)
-static int kway_sample_seeded(const gmc_batch *batch, const float *P, int32_t K, int32_t terminals, const uint64_t *gkey,
-                              int32_t iters, int8_t *assign_all, float *cut_all, int32_t *best_assign, float *best_cut,
-                              int32_t *best_iter, gmc_stream_t stream) {
+// what gmc_kway_decode_sample_seeded_f32 and its _t twin do (terminals: 0 or 1); node_cost: the _c twin's, or NULL
+static int kway_sample_seeded(const gmc_batch *batch, const float *P, int32_t K, int32_t terminals, const float *node_cost,
+                              const uint64_t *gkey, int32_t iters, int8_t *assign_all, float *cut_all,
+                              int32_t *best_assign, float *best_cut, int32_t *best_iter, gmc_stream_t stream) {
     if (!batch || !P || !gkey || !cut_all || !best_assign || !best_cut || !best_iter) return GMC_ERR_NULL;
     if (batch->abi != GMC_VERSION) return GMC_ERR_ABI;
     if (!batch->goff || !batch->rowptr || !batch->lcol) return GMC_ERR_NULL;
@@ -211,22 +202,32 @@ static int kway_sample_seeded(const gmc_batch *batch, const float *P, int32_t K,
     if (batch->B > 0 && (batch->n_max < (first > 1 ? first : 1) || batch->n_max > 65535))
         return GMC_ERR_GRAPH_SIZE;
     if (batch->B == 0) return GMC_OK;
-    return sample_launch(batch, P, K, first, gkey, iters, assign_all, cut_all, best_assign, best_cut, best_iter, stream);
+    return sample_launch(batch, P, K, first, gkey, iters, assign_all, cut_all, best_assign, best_cut, best_iter, stream,
+                         node_cost);
 }
 
 extern "C" int gmc_kway_decode_sample_seeded_f32(const gmc_batch *batch, const float *P, int32_t K,
                                                  const uint64_t *gkey, int32_t iters, int8_t *assign_all,
                                                  float *cut_all, int32_t *best_assign, float *best_cut,
                                                  int32_t *best_iter, gmc_stream_t stream) {
-    return kway_sample_seeded(batch, P, K, 1, gkey, iters, assign_all, cut_all, best_assign, best_cut, best_iter, stream);
+    return gmc_kway_decode_sample_seeded_t_f32(batch, P, K, 1, gkey, iters, assign_all, cut_all, best_assign, best_cut,
+                                               best_iter, stream);
 }
 
 extern "C" int gmc_kway_decode_sample_seeded_t_f32(const gmc_batch *batch, const float *P, int32_t K, int32_t terminals,
                                                    const uint64_t *gkey, int32_t iters, int8_t *assign_all,
                                                    float *cut_all, int32_t *best_assign, float *best_cut,
                                                    int32_t *best_iter, gmc_stream_t stream) {
-    return kway_sample_seeded(batch, P, K, terminals, gkey, iters, assign_all, cut_all, best_assign, best_cut, best_iter,
-                              stream);
+    return gmc_kway_decode_sample_seeded_c_f32(batch, P, K, terminals, nullptr, gkey, iters, assign_all, cut_all,
+                                               best_assign, best_cut, best_iter, stream);
+}
+
+extern "C" int gmc_kway_decode_sample_seeded_c_f32(const gmc_batch *batch, const float *P, int32_t K, int32_t terminals,
+                                                   const float *node_cost, const uint64_t *gkey, int32_t iters,
+                                                   int8_t *assign_all, float *cut_all, int32_t *best_assign,
+                                                   float *best_cut, int32_t *best_iter, gmc_stream_t stream) {
+    return kway_sample_seeded(batch, P, K, terminals, node_cost, gkey, iters, assign_all, cut_all, best_assign, best_cut,
+                              best_iter, stream);
 }
 
 extern "C" int gmc_refine_anneal_staged(const gmc_batch *batch) {
@@ -254,8 +255,9 @@ extern "C" int gmc_refine_anneal_f32(const gmc_batch *batch, const int32_t *orde
                          max_descent_sweeps, cut_all, best_assign, best_cut, best_idx, snap_sweep, sweeps, stream);
 }
 
-// what gmc_kway_refine_anneal_f32 and its _t twin do (terminals: 0 or 1)
-static int kway_refine_anneal(const gmc_batch *batch, int32_t K, int32_t terminals, const int32_t *order,
+// what gmc_kway_refine_anneal_f32 and its _t twin do (terminals: 0 or 1); node_cost: the _c twin's, or NULL
+static int kway_refine_anneal(const gmc_batch *batch, int32_t K, int32_t terminals, const float *node_cost,
+                              const int32_t *order,
                               const int32_t *cgoff, const int32_t *cptr, int32_t cands, int8_t *assign,
                               const float *inv_temp, int32_t anneal_sweeps, const float *levels, uint64_t seed,
                               int32_t max_descent_sweeps, float *cut_all, int32_t *best_assign, float *best_cut,
@@ -274,7 +276,8 @@ static int kway_refine_anneal(const gmc_batch *batch, int32_t K, int32_t termina
         return GMC_ERR_GRAPH_SIZE;
     if (batch->B == 0) return GMC_OK;
     return anneal_launch(batch, K, first, order, cgoff, cptr, cands, assign, inv_temp, anneal_sweeps, levels, seed,
-                         max_descent_sweeps, cut_all, best_assign, best_cut, best_idx, snap_sweep, sweeps, stream);
+                         max_descent_sweeps, cut_all, best_assign, best_cut, best_idx, snap_sweep, sweeps, stream,
+                         node_cost);
 }
 
 extern "C" int gmc_kway_refine_anneal_f32(const gmc_batch *batch, int32_t K, const int32_t *order,
@@ -283,8 +286,9 @@ extern "C" int gmc_kway_refine_anneal_f32(const gmc_batch *batch, int32_t K, con
                                           uint64_t seed, int32_t max_descent_sweeps, float *cut_all,
                                           int32_t *best_assign, float *best_cut, int32_t *best_idx,
                                           int32_t *snap_sweep, int32_t *sweeps, gmc_stream_t stream) {
-    return kway_refine_anneal(batch, K, 1, order, cgoff, cptr, cands, assign, inv_temp, anneal_sweeps, levels, seed,
-                              max_descent_sweeps, cut_all, best_assign, best_cut, best_idx, snap_sweep, sweeps, stream);
+    return gmc_kway_refine_anneal_t_f32(batch, K, 1, order, cgoff, cptr, cands, assign, inv_temp, anneal_sweeps, levels,
+                                        seed, max_descent_sweeps, cut_all, best_assign, best_cut, best_idx, snap_sweep,
+                                        sweeps, stream);
 }
 
 extern "C" int gmc_kway_refine_anneal_t_f32(const gmc_batch *batch, int32_t K, int32_t terminals, const int32_t *order,
@@ -293,7 +297,18 @@ extern "C" int gmc_kway_refine_anneal_t_f32(const gmc_batch *batch, int32_t K, i
                                             uint64_t seed, int32_t max_descent_sweeps, float *cut_all,
                                             int32_t *best_assign, float *best_cut, int32_t *best_idx,
                                             int32_t *snap_sweep, int32_t *sweeps, gmc_stream_t stream) {
-    return kway_refine_anneal(batch, K, terminals, order, cgoff, cptr, cands, assign, inv_temp, anneal_sweeps, levels,
-                              seed, max_descent_sweeps, cut_all, best_assign, best_cut, best_idx, snap_sweep, sweeps,
-                              stream);
+    return gmc_kway_refine_anneal_c_f32(batch, K, terminals, nullptr, order, cgoff, cptr, cands, assign, inv_temp,
+                                        anneal_sweeps, levels, seed, max_descent_sweeps, cut_all, best_assign, best_cut,
+                                        best_idx, snap_sweep, sweeps, stream);
+}
+
+extern "C" int gmc_kway_refine_anneal_c_f32(const gmc_batch *batch, int32_t K, int32_t terminals, const float *node_cost,
+                                            const int32_t *order, const int32_t *cgoff, const int32_t *cptr,
+                                            int32_t cands, int8_t *assign, const float *inv_temp, int32_t anneal_sweeps,
+                                            const float *levels, uint64_t seed, int32_t max_descent_sweeps,
+                                            float *cut_all, int32_t *best_assign, float *best_cut, int32_t *best_idx,
+                                            int32_t *snap_sweep, int32_t *sweeps, gmc_stream_t stream) {
+    return kway_refine_anneal(batch, K, terminals, node_cost, order, cgoff, cptr, cands, assign, inv_temp, anneal_sweeps,
+                              levels, seed, max_descent_sweeps, cut_all, best_assign, best_cut, best_idx, snap_sweep,
+                              sweeps, stream);
 }

@@ -109,10 +109,11 @@ int gmc_kway_hw2_launch(const float *H, long ld, const float *dinv, const float 
                         hipStream_t st);
 // GY2 == nullptr: forward only (P, S, loss); GMC_ERR_GRAPH_SIZE when gmc_kway_head_lds_bytes exceeds GMC_KWAY_LDS_BYTES.
 // b2_stride: floats from one graph's conv2.bias to the next - 0 = the one shared bias, K = b2 [B,K] (the per-graph
-// models of instance.hip); the bias is read at b2 + g * b2_stride, so 0 is the launch it was before the argument
+// models of instance.hip); the bias is read at b2 + g * b2_stride, so 0 is the launch it was before the argument.
+// node_cost: [R,K] per-node class costs of the loss (gmc_inst_*_c) or NULL
 int gmc_kway_head_launch(const gmc_batch *b, const float *Z0, const float *b2, float C, int K, int loss_kind, float *P,
                          int32_t *S, float *loss, float *GY2, float *db2part, hipStream_t st, long b2_stride = 0,
-                         int terminals = 1);
+                         int terminals = 1, const float *node_cost = nullptr);
 int gmc_kway_hidden_bwd_launch(const float *H, long ldh, const float *GY2, const float *W2, const float *dinv, float *Gs,
                                long ldg, float *part, int R, int F, int K, hipStream_t st);
 int gmc_kway_reduce_launch(const float *part, int tiles, int F, int K, float *dW2, float *db1, const float *db2part,

@@ -19,13 +19,15 @@ struct Sums {
 // self-loops skipped, a class byte outside 0..K-1 adding to none.  K sums chosen by compares (an indexed private array
 // would live in scratch).  rp[l] .. rp[l + 1] are the row's edges in col / vals (NULL: all ones).  cls[u] is the class
 // byte of node u: a pointer, or a view with an operator[] (large_search.hip keeps the bytes of one candidate a stride
-// apart).
+// apart).  nc: the per-node class costs of the graph's rows, [n][K] by local id (the caller's node_cost + r0 * K), or
+// NULL; with it W_k starts from nc[l][k] instead of +0 (the _c entry points of include/gcnmaxcut.h) and nothing else
+// changes - the K loads come from global memory, once per visit.
 template <int K, class RP, class COL, class CLS>
 __device__ __forceinline__ Sums<K> class_sums_k(const RP *rp, const COL *col, const float *vals, const CLS &cls,
-                                                int l) {
+                                                int l, const float *nc = nullptr) {
     Sums<K> s;
 #pragma unroll
-    for (int k = 0; k < K; ++k) s.m[k] = 0.f;
+    for (int k = 0; k < K; ++k) s.m[k] = nc ? nc[(long)l * K + k] : 0.f;
     const int e1 = rp[l + 1];
     for (int e = rp[l]; e < e1; ++e) {
         const int u = col[e];
@@ -88,12 +90,12 @@ __device__ __forceinline__ bool anneal_move(const Sums<K> &w, int c, float inv_t
 
 // One descent visit of local node l, the local search's rule: the node moves to the class kk of the smallest of its K
 // sums (lowest index on ties) iff W[kk] < W[own]; a byte of no class has W[own] = +inf, so such a node always moves.
-// g: a graph's CSR as one of anneal_layout.h's accessors (rp, col, vals); true iff the node moved.
+// g: a graph's CSR as one of anneal_layout.h's accessors (rp, col, vals); nc: class_sums_k's; true iff the node moved.
 // The +inf is spelled as a test of the byte beside the compare, not as one more select in front of the own-sum chain:
 // the visit is the critical path of a colour step, and at K = 3 that select made the rounding's descent 3 % slower.
 template <int K, class G>
-__device__ __forceinline__ bool descent_visit(const G &g, unsigned char *cls, int l) {
-    const Sums<K> s = class_sums_k<K>(g.rp, g.col, g.vals, cls, l);
+__device__ __forceinline__ bool descent_visit(const G &g, unsigned char *cls, int l, const float *nc = nullptr) {
+    const Sums<K> s = class_sums_k<K>(g.rp, g.col, g.vals, cls, l, nc);
     const int c = cls[l];
     float wc = s.m[0];
 #pragma unroll
@@ -113,10 +115,11 @@ __device__ __forceinline__ bool descent_visit(const G &g, unsigned char *cls, in
 // after max_sweeps.  An entry of the order that is not a movable row of this graph (a terminal l < first, or l >= n; first = K with
 // terminals, 0 without: a run-time value behind g.movable(), so both serve from one instantiation) is
 // never visited and never touches LDS.  Every thread must call it with cls published; on return every thread may read
-// cls.  Returns the sweeps run, the last of them the one that moved nothing when the descent converged.
+// cls.  Returns the sweeps run, the last of them the one that moved nothing when the descent converged.  nc: the graph's
+// per-node class costs as class_sums_k takes them, or NULL.
 template <int K, class G>
 __device__ __forceinline__ int descent_sweeps(const G &g, const int *cptr, int k0, int classes, unsigned char *cls,
-                                              int n, int max_sweeps) {
+                                              int n, int max_sweeps, const float *nc = nullptr) {
     // blockDim.x is read once, ahead of the sweeps: read inside the loop it becomes a vector load on every colour
     // step's critical path (the rounding at K = 3 ran 4.5 % slower; DESIGN.md section 23 has this and the other forms tried)
     const int threads = blockDim.x;
@@ -129,7 +132,7 @@ __device__ __forceinline__ int descent_sweeps(const G &g, const int *cptr, int k
             for (int i = cptr[k0 + k] + threadIdx.x; i < hi; i += threads) {
                 const int l = g.node(i);
                 if (!g.movable(l, n)) continue;
-                if (descent_visit<K>(g, cls, l)) moved = 1;
+                if (descent_visit<K>(g, cls, l, nc)) moved = 1;
             }
             if (k + 1 < classes) __syncthreads();
         }

@@ -39,87 +39,47 @@ struct RoundArgs {
     float *cut;              // [B]
     float *expected;         // [B] or NULL
     int *sweeps;             // [B] or NULL
+    const float *node_cost;  // [R][K] by batch row or NULL (gmc_round_conditional_c_f32)
 };
 
+// Two kernels over one body text (round_kernel_body.inc; anneal_kernel_body.inc says why text): round_conditional_kernel<K>
+// is the launch without per-node class costs and keeps its name and its code, round_conditional_cost_kernel<K> is the
+// launch with them (a.node_cost != NULL).
 template <int K>
 __global__ __launch_bounds__(256) void round_conditional_kernel(RoundArgs a) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
-    __shared__ float red[4];
-    const int g = blockIdx.x;
-    const int r0 = a.b.goff[g];
-    const int n = a.b.goff[g + 1] - r0;
-    const int first = a.first;
-    if (n > a.b.n_max || n < first) return;   // (a batch that contradicts its own n_max: the LDS is sized by it)
-    float *q = reinterpret_cast<float *>(lds);
-    unsigned char *cls = lds + (size_t)a.b.n_max * K * sizeof(float);
-    const int *rp = a.b.rowptr + r0;
-    const int *col = a.b.lcol;
-    const float *vals = a.b.vals;
-    // state: terminals (l < first) e_l (their rows of P are not read), every other node its row of P
-    const float *Pg = a.P + (long)r0 * K;
-    for (int i = threadIdx.x; i < n * K; i += blockDim.x) {
-        const int l = i / K, k = i - l * K;
-        q[i] = l < first ? (l == k ? 1.0f : 0.0f) : Pg[i];
-    }
-    for (int l = threadIdx.x; l < n; l += blockDim.x) cls[l] = (unsigned char)(l < first ? l : 0);
-    __syncthreads();
-    const gmc::FloatState<K> state{q};
-    if (a.expected) {   // workgroup-uniform
-        float acc = 0.f;
-        for (int l = threadIdx.x; l < n; l += blockDim.x) acc += expected_row<K>(rp, col, vals, state, l);
-        acc = gmc::wave_sum(acc);
-        if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
-        __syncthreads();
-        if (threadIdx.x == 0) a.expected[g] = (((red[0] + red[1]) + red[2]) + red[3]) * 0.5f;
-        __syncthreads();   // every row has read the unrounded state, thread 0 has read red
-    }
-    const int k0 = a.cgoff[g];
-    const int classes = a.cgoff[g + 1] - k0 - 1;
-    // rounding: one visit of every movable node, class by class
-    for (int k = 0; k < classes; ++k) {
-        const int hi = a.cptr[k0 + k + 1];
-        for (int i = a.cptr[k0 + k] + threadIdx.x; i < hi; i += blockDim.x) {
-            const int l = a.order[i] - r0;
-            if ((unsigned)(l - first) >= (unsigned)(n - first)) continue;   // not a movable row: never touch LDS for it
-            const Sums<K> s = state_sums<K>(rp, col, vals, state, l);
-            float wk;
-            const int kk = smallest<K>(s, wk);
-#pragma unroll
-            for (int c = 0; c < K; ++c) q[l * K + c] = c == kk ? 1.0f : 0.0f;
-            cls[l] = (unsigned char)kk;
-        }
-        __syncthreads();   // the next class, the descent or the cut count reads what this one wrote
-    }
-    // descent: the local search's sweeps at K classes over the class bytes
-    const gmc::GlobalCsr csr{rp, col, vals, a.order, r0, first};
-    const int sw = gmc::descent_sweeps<K>(csr, a.cptr, k0, classes, cls, n, a.max_descent_sweeps);
-    signed char *as = a.assign + r0;
-    for (int l = threadIdx.x; l < n; l += blockDim.x) as[l] = (signed char)cls[l];
-    const float cut = gmc::block_cut(a.b, cls, r0, n, red);   // scored as gmc_refine_local_f32 scores
-    if (threadIdx.x == 0) {
-        a.cut[g] = cut;
-        if (a.sweeps) a.sweeps[g] = sw;
-    }
+#define GMC_COST false
+#include "round_kernel_body.inc"
+#undef GMC_COST
+}
+template <int K>
+__global__ __launch_bounds__(256) void round_conditional_cost_kernel(RoundArgs a) {
+#define GMC_COST true
+#include "round_kernel_body.inc"
+#undef GMC_COST
 }
 
 template <int K>
 int round_launch(const RoundArgs &a, hipStream_t st) {
     const size_t lds = (size_t)a.b.n_max * (K * sizeof(float) + 1);
+    const void *kernel = a.node_cost ? reinterpret_cast<const void *>(round_conditional_cost_kernel<K>)
+                                     : reinterpret_cast<const void *>(round_conditional_kernel<K>);
     if (lds > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(round_conditional_kernel<K>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return (int)e;
     }
     GmcProbeScope probe(GMC_K_REFINE, st);
-    hipLaunchKernelGGL((round_conditional_kernel<K>), dim3(a.b.B), dim3(256), lds, st, a);
+    if (a.node_cost) hipLaunchKernelGGL((round_conditional_cost_kernel<K>), dim3(a.b.B), dim3(256), lds, st, a);
+    else hipLaunchKernelGGL((round_conditional_kernel<K>), dim3(a.b.B), dim3(256), lds, st, a);
     GMC_LAUNCH_CHECK();
     return GMC_OK;
 }
 
 }  // namespace
 
-// what both entry points do: the checks in the documented order, then the launch (terminals: 0 or 1)
-static int round_conditional(const gmc_batch *batch, const float *P, int32_t K, int32_t terminals, const int32_t *order,
+// what the entry points do: the checks in the documented order, then the launch (terminals: 0 or 1; node_cost: the _c
+// twin's, or NULL)
+static int round_conditional(const gmc_batch *batch, const float *P, int32_t K, int32_t terminals, const float *node_cost,
+                             const int32_t *order,
                              const int32_t *cgoff, const int32_t *cptr, int32_t max_descent_sweeps, int8_t *assign,
                              float *cut, float *expected, int32_t *sweeps, gmc_stream_t stream) {
     if (!batch || !P || !order || !cgoff || !cptr || !assign || !cut) return GMC_ERR_NULL;
@@ -133,7 +93,7 @@ static int round_conditional(const gmc_batch *batch, const float *P, int32_t K, 
     if (batch->B == 0) return GMC_OK;
     hipStream_t st = static_cast<hipStream_t>(stream);
     const RoundArgs a{*batch, P, order, cgoff, cptr, max_descent_sweeps, first,
-                      reinterpret_cast<signed char *>(assign), cut, expected, sweeps};
+                      reinterpret_cast<signed char *>(assign), cut, expected, sweeps, node_cost};
     GMC_KWAY_DISPATCH(K, return round_launch<KK>(a, st));
     return GMC_OK;
 }
@@ -142,14 +102,22 @@ extern "C" int gmc_round_conditional_f32(const gmc_batch *batch, const float *P,
                                          const int32_t *cgoff, const int32_t *cptr, int32_t max_descent_sweeps,
                                          int8_t *assign, float *cut, float *expected, int32_t *sweeps,
                                          gmc_stream_t stream) {
-    return round_conditional(batch, P, K, 1, order, cgoff, cptr, max_descent_sweeps, assign, cut, expected, sweeps,
-                             stream);
+    return gmc_round_conditional_t_f32(batch, P, K, 1, order, cgoff, cptr, max_descent_sweeps, assign, cut, expected,
+                                       sweeps, stream);
 }
 
 extern "C" int gmc_round_conditional_t_f32(const gmc_batch *batch, const float *P, int32_t K, int32_t terminals,
                                            const int32_t *order, const int32_t *cgoff, const int32_t *cptr,
                                            int32_t max_descent_sweeps, int8_t *assign, float *cut, float *expected,
                                            int32_t *sweeps, gmc_stream_t stream) {
-    return round_conditional(batch, P, K, terminals, order, cgoff, cptr, max_descent_sweeps, assign, cut, expected,
-                             sweeps, stream);
+    return gmc_round_conditional_c_f32(batch, P, K, terminals, nullptr, order, cgoff, cptr, max_descent_sweeps, assign,
+                                       cut, expected, sweeps, stream);
+}
+
+extern "C" int gmc_round_conditional_c_f32(const gmc_batch *batch, const float *P, int32_t K, int32_t terminals,
+                                           const float *node_cost, const int32_t *order, const int32_t *cgoff,
+                                           const int32_t *cptr, int32_t max_descent_sweeps, int8_t *assign, float *cut,
+                                           float *expected, int32_t *sweeps, gmc_stream_t stream) {
+    return round_conditional(batch, P, K, terminals, node_cost, order, cgoff, cptr, max_descent_sweeps, assign, cut,
+                             expected, sweeps, stream);
 }

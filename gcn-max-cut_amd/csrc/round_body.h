@@ -21,13 +21,15 @@ struct FloatState {
 };
 
 // M_k = sum over the edges of row l, CSR order, self-loops skipped, of w_e * q_u[k], from +0.  Product and sum are
-// rounded separately: hipcc contracts a * b + c into one fused multiply-add unless told not to.
+// rounded separately: hipcc contracts a * b + c into one fused multiply-add unless told not to.  nc: the per-node class
+// costs of the rows the CSR numbers ([.][K], row l at nc + l * K) or NULL; with it M_k starts from nc[l][k] instead of +0.
 template <int K, class RP, class COL, class Q>
-__device__ __forceinline__ Sums<K> state_sums(const RP *rp, const COL *col, const float *vals, const Q &q, int l) {
+__device__ __forceinline__ Sums<K> state_sums(const RP *rp, const COL *col, const float *vals, const Q &q, int l,
+                                              const float *nc = nullptr) {
 #pragma clang fp contract(off)
     Sums<K> s;
 #pragma unroll
-    for (int k = 0; k < K; ++k) s.m[k] = 0.f;
+    for (int k = 0; k < K; ++k) s.m[k] = nc ? nc[(long)l * K + k] : 0.f;
     const int e1 = rp[l + 1];
     for (int e = rp[l]; e < e1; ++e) {
         const int u = col[e];
@@ -62,6 +64,22 @@ __device__ __forceinline__ float expected_row(const RP *rp, const COL *col, cons
 #pragma unroll
         for (int k = 0; k < K; ++k) dot += qu[k] * ql[k];
         acc += w * (1.0f - dot);
+    }
+    return acc;
+}
+
+// the node's share of the expected cost: nc[l] . q_l, the products added in ascending k from +0, product and sum
+// rounded separately
+template <int K, class Q>
+__device__ __forceinline__ float expected_cost_row(const float *nc, const Q &q, int l) {
+#pragma clang fp contract(off)
+    float ql[K];
+    q.load(l, ql);
+    float acc = 0.f;
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+        const float t = nc[(long)l * K + k] * ql[k];
+        acc = acc + t;
     }
     return acc;
 }

@@ -572,13 +572,19 @@ class InstanceEngine:
     ``batch_handles``: the graphs' handles, or a ready :class:`GraphBatch` (``GraphBatch.from_edge_index`` builds one on
     the device; ``values`` must then be ``None``).  ``terminals=False``: plain max-K-cut - the head overrides no row, ``S``
     is the row argmax and both losses fix no node (gmc_inst_forward_t / gmc_inst_train_fwd_bwd_t with terminals = 0); a
-    graph then needs one node, not K."""
+    graph then needs one node, not K.  ``node_cost``: a [R, K] float32 tensor of per-node class costs (moved to the engine's device if it is elsewhere), indexed by
+    batch row - both losses then train on ``cut - sum_v node_cost[v] . P_v`` (the hard loss: ``node_cost[v][S_v]``) through
+    gmc_inst_forward_c / gmc_inst_train_fwd_bwd_c; ``subset`` keeps the rows of the graphs it keeps."""
 
     # the three entry points of include/gcnmaxcut.h the engine computes through (LargeInstanceEngine: gmc_inst_large_*)
     _WORKSPACE, _FORWARD, _TRAIN = "gmc_inst_workspace_bytes", "gmc_inst_forward_t", "gmc_inst_train_fwd_bwd_t"
+    _FORWARD_COST, _TRAIN_COST = "gmc_inst_forward_c", "gmc_inst_train_fwd_bwd_c"   # (None: the sequence takes no cost)
 
     def __init__(self, batch_handles, F: int, K: int, device: Optional[torch.device] = None, *, values=None,
-                 terminals: bool = True):
+                 terminals: bool = True, node_cost: Optional[torch.Tensor] = None):
+        if node_cost is not None and self._FORWARD_COST is None:
+            raise NotImplementedError(f"{type(self).__name__} takes no node_cost: the per-node class costs enter the "
+                                      "one-workgroup head of InstanceEngine only")
         if isinstance(batch_handles, GraphBatch) and device is not None and torch.device(device) != batch_handles.device:
             raise ValueError(f"the batch lives on {batch_handles.device}, the engine was asked for {torch.device(device)}")
         self.device = batch_handles.device if isinstance(batch_handles, GraphBatch) else device or hip.require_gpu()
@@ -616,6 +622,12 @@ class InstanceEngine:
         self.stall = torch.zeros(self.B, dtype=torch.int32, device=self.device)
         self.stop_epoch = torch.full((self.B,), -1, dtype=torch.int32, device=self.device)
         self._ws: Optional[torch.Tensor] = None
+        if node_cost is not None:
+            if (not isinstance(node_cost, torch.Tensor) or node_cost.dtype != torch.float32
+                    or tuple(node_cost.shape) != (self.R, K)):
+                raise ValueError(f"node_cost must be a [{self.R}, {K}] float32 tensor")
+            node_cost = node_cost.to(self.device).contiguous()   # (a no-op for a tensor that is there already)
+        self.node_cost = node_cost
 
     def _check_sizes(self, sizes: Sequence[int], K: int) -> None:
         check_instance_sizes(sizes, K, terminals=self.terminals)
@@ -694,10 +706,10 @@ class InstanceEngine:
         if self.B == 0:
             return P, S, losses
         ws = self._workspace(False)
-        rc = getattr(self.lib, self._FORWARD)(self.batch.ref(), C.byref(self._model(loss)), int(self.terminals), C_,
-                                              hip.ptr(ws), ws.numel(), hip.ptr(P), hip.ptr(S), hip.ptr(losses),
-                                              hip.stream())
-        hip.check(rc, self._FORWARD)
+        name, cost = (self._FORWARD, ()) if self.node_cost is None else (self._FORWARD_COST, (hip.ptr(self.node_cost),))
+        rc = getattr(self.lib, name)(self.batch.ref(), C.byref(self._model(loss)), int(self.terminals), *cost, C_,
+                                     hip.ptr(ws), ws.numel(), hip.ptr(P), hip.ptr(S), hip.ptr(losses), hip.stream())
+        hip.check(rc, name)
         return P, S, losses
 
     def train_fwd_bwd(self, C_: float = 1.0, loss: str = "cut", out=None):
@@ -707,10 +719,11 @@ class InstanceEngine:
             self.grad.zero_()
             return P, S, losses
         ws = self._workspace(True)
-        rc = getattr(self.lib, self._TRAIN)(self.batch.ref(), C.byref(self._model(loss)), int(self.terminals), C_,
-                                            hip.ptr(ws), ws.numel(), hip.ptr(P), hip.ptr(S), hip.ptr(losses),
-                                            hip.ptr(self.grad), hip.stream())
-        hip.check(rc, self._TRAIN)
+        name, cost = (self._TRAIN, ()) if self.node_cost is None else (self._TRAIN_COST, (hip.ptr(self.node_cost),))
+        rc = getattr(self.lib, name)(self.batch.ref(), C.byref(self._model(loss)), int(self.terminals), *cost, C_,
+                                     hip.ptr(ws), ws.numel(), hip.ptr(P), hip.ptr(S), hip.ptr(losses),
+                                     hip.ptr(self.grad), hip.stream())
+        hip.check(rc, name)
         return P, S, losses
 
     def adam_step(self, lr: float, betas=(0.9, 0.999), eps: float = 1e-8, running_only: bool = False) -> None:
@@ -772,12 +785,13 @@ class InstanceEngine:
         values = None if self._values is None else [self._values[g] for g in keep]
         if self._handles is None:   # built over a ready batch: its graphs as handles, edge weights included
             self._handles = self.batch.handles()
-        sub = type(self)([self._handles[g] for g in keep], self.F, self.K, self.device, values=values,
-                         terminals=self.terminals)
         gidx = torch.tensor(keep, dtype=torch.long, device=self.device)
         goff = self.batch.goff_host
         rows = [torch.arange(int(goff[g]), int(goff[g + 1]), device=self.device) for g in keep]
         ridx = torch.cat(rows) if rows else torch.zeros(0, dtype=torch.long, device=self.device)
+        cost = {} if self.node_cost is None else {"node_cost": self.node_cost[ridx].contiguous()}
+        sub = type(self)([self._handles[g] for g in keep], self.F, self.K, self.device, values=values,
+                         terminals=self.terminals, **cost)
         for src, dst in ((self.flat, sub.flat), (self.grad, sub.grad), (self.m, sub.m), (self.v, sub.v)):
             a, b = self.blocks(src), sub.blocks(dst)
             b["conv1.weight"].copy_(a["conv1.weight"][ridx])
@@ -812,6 +826,7 @@ class LargeInstanceEngine(InstanceEngine):
     parameters, gradient and moments and 8 * ld for the workspace (ld = hidden_dim rounded up to 32)."""
 
     _WORKSPACE, _FORWARD, _TRAIN = "gmc_inst_large_workspace_bytes", "gmc_inst_large_forward", "gmc_inst_large_train_fwd_bwd"
+    _FORWARD_COST = _TRAIN_COST = None
 
     def _check_sizes(self, sizes: Sequence[int], K: int) -> None:
         check_large_instance_sizes(sizes, K, terminals=self.terminals)

@@ -216,6 +216,14 @@ def _api() -> dict:
         "gmc_inst_large_workspace_bytes": (sz, [B, M, i]),
         "gmc_inst_large_forward": (i, [B, M, i32, f32, vp, sz, vp, vp, vp, vp]),
         "gmc_inst_large_train_fwd_bwd": (i, [B, M, i32, f32, vp, sz, vp, vp, vp, vp, vp]),
+        # per-node class costs: the `_t` entry points with `node_cost` ([R][K] or NULL) after `terminals`
+        "gmc_round_conditional_c_f32": (i, [B, vp, i32, i32, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp]),
+        "gmc_kway_decode_sample_seeded_c_f32": (i, [B, vp, i32, i32, vp, vp, i32, vp, vp, vp, vp, vp, vp]),
+        "gmc_kway_refine_anneal_c_f32": (i, [B, i32, i32, vp, vp, vp, vp, i32, vp, vp, i32, vp, C.c_uint64, i32, vp, vp, vp,
+                                             vp, vp, vp, vp]),
+        "gmc_inst_forward_c": (i, [B, M, i32, vp, f32, vp, sz, vp, vp, vp, vp]),
+        "gmc_inst_train_fwd_bwd_c": (i, [B, M, i32, vp, f32, vp, sz, vp, vp, vp, vp, vp]),
+        "gmc_row_weight_sums_f32": (i, [i32, vp, vp, vp, vp, vp]),
     }
 
 

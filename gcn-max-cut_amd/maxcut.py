@@ -6,6 +6,9 @@ The tensor-first front door of the instance-wise solver. 
 one annealing launch (the ``_t`` entry points of include/gcnmaxcut.h).  By default there are no terminals: this is the
 max-cut of Gset and the max-cut papers, not the reference's variant with nodes 0..K-1 forced apart; ``terminals=True``
 gives that one.  No ``networkx`` graph and no dataset item is involved.
+
+``node_cost`` adds a linear term per node and class to the objective, and two more doors map the
+QUBO family onto it exactly: :func:`solve_ising` and :func:`solve_qubo`.
 """
 from __future__ import annotations
 
@@ -27,6 +30,14 @@ _TOO_LARGE = ("a graph of {n} nodes is beyond the one-workgroup head of the per-
 _NO_TABU = "the tabu stage keeps a graph's state in one workgroup: solve_large does not have it (tabu_iterations must be 0)"
 _NO_BALANCE = ("the balanced stage keeps a graph's state in one workgroup, as the tabu stage does: solve_large does not "
                "have it (class_sizes must be None)")
+_NO_COST_TABU = ("node_cost with tabu_iterations > 0: the tabu stage scores and moves by the plain cut - per-node costs are "
+                 "not implemented in it")
+_NO_COST_SIZES = ("node_cost with class_sizes: the balanced stage scores and moves by the plain cut - per-node costs are "
+                  "not implemented in it")
+_NO_COST_FIXED = ("node_cost with fixed: a contracted super-node stands for many nodes and their costs are not summed "
+                  "onto it - express the pins as large costs, or pass one of the two")
+_NO_COST_LARGE = ("node_cost on the large route: the multi-workgroup head and decoders of solve_large take no per-node "
+                  "costs - maxcut.solve has them for graphs within its bound")
 _BEYOND_LARGE = "a graph of {n} nodes is beyond the {bound} nodes of the per-graph models' large sequence (solve_large)"
 
 
@@ -42,6 +53,9 @@ class MaxCutResult:
     fixed_cut: Optional[torch.Tensor] = None      # [B] float32, with fixed only: the weight of the edges between pinned
     #                                               nodes of different classes (a constant of every partition)
     unconstrained_cut: Optional[torch.Tensor] = None   # [B] float32, with class_sizes only: what ``cut`` would have been
+    node_cost_sum: Optional[torch.Tensor] = None   # [B] float32, with node_cost only: sum_v node_cost[v][partition_v]; every
+    #                                                ``*_cut`` field then holds the objective cut - cost of its partition,
+    #                                                and the plain cut of ``partition`` is ``cut + node_cost_sum``
 
 
 def balanced_sizes(ptr, number_classes: int, imbalance: float = 0.0):
@@ -67,7 +81,7 @@ def solve(edge_index, ptr=None, num_nodes: Optional[int] = None, edge_weight=Non
           terminals: bool = False, pairs: str = "both", hidden_dim: int, epochs: int, learning_rate: float,
           loss: str = "expected_cut", samples: int = 32, anneal_sweeps: int = 100, max_descent_sweeps: int = 100,
           seed: int = 0, tabu_iterations: int = 0, fixed=None, class_sizes=None,
-          balance_iterations: Optional[int] = None) -> MaxCutResult:
+          balance_iterations: Optional[int] = None, node_cost=None) -> MaxCutResult:
     """Max-K-cut of every graph of a batch given as ``edge_index`` [2, E] (with ``ptr`` [B+1], or ``num_nodes`` for one
     graph, ``edge_weight`` and ``pairs`` as ``GraphBatch.from_edge_index`` takes them).
 
@@ -111,6 +125,15 @@ def solve(edge_index, ptr=None, num_nodes: Optional[int] = None, edge_weight=Non
     and its cuts are then recounted by the large decoders' scoring call (the cut order of ``solve_large``; the same
     number for unit and integer weights).  ``fixed`` together with ``terminals=True`` raises ``ValueError``.
 
+    ``node_cost`` [R, K] (numpy or torch, any float dtype; row = global node id, converted to float32 once): the
+    objective becomes ``cut(S) - sum_v node_cost[v][S_v]`` - node preferences, external fields, the linear part of a QUBO.
+    Training (both losses), the rounding, the sampler's scores and the annealing all follow it (the ``_c`` entry points
+    of include/gcnmaxcut.h), every ``*_cut`` field of the result then holds the objective of its partition (what the
+    stages compared), and ``node_cost_sum`` holds the cost of ``partition``, so its plain cut is ``cut +
+    node_cost_sum``.  A wrong shape or a value that is not finite raises ``ValueError`` before anything is built;
+    ``node_cost`` together with ``tabu_iterations > 0``, ``class_sizes`` or ``fixed`` raises ``NotImplementedError``.
+    ``None`` changes no byte, and an all-zero array returns the bytes of ``None`` in ``partition`` and ``cut``.
+
     A graph beyond the one-workgroup head of the per-graph models raises ``ValueError``: for such a graph train a model
     through ``gcn_max_cut_amd.functional`` (terminal-free up to 2^20 nodes) and decode it with
     ``search_large_dataset(..., terminals=False)``."""
@@ -120,6 +143,8 @@ def solve(edge_index, ptr=None, num_nodes: Optional[int] = None, edge_weight=Non
     loss = hip.loss_name(loss)
     _check_fixed(fixed, terminals, K)
     _check_sizes(class_sizes, balance_iterations, fixed)
+    if node_cost is not None:
+        node_cost = _check_node_cost(node_cost, _rows_of(ptr, num_nodes), K, tabu_iterations, class_sizes, fixed)
     if ptr is not None:   # judged before anything is built: the sizes are all it takes
         p = ptr.detach().cpu().numpy() if isinstance(ptr, torch.Tensor) else np.asarray(ptr)
         n_max = int(np.diff(p.astype(np.int64)).max()) if p.ndim == 1 and p.size > 1 else 0
@@ -132,6 +157,9 @@ def solve(edge_index, ptr=None, num_nodes: Optional[int] = None, edge_weight=Non
     if fixed is None and n_max > 0 and instance_too_large(n_max, K, loss):   # (with pins: the contracted sizes decide)
         raise ValueError(_TOO_LARGE.format(n=n_max, K=K))
     batch = GraphBatch.from_edge_index(edge_index, ptr, num_nodes, edge_weight, pairs=pairs)
+    if node_cost is not None:   # (checked above, once: no tabu, sizes or pins come with it)
+        return _solve_batch(_small_route(), batch, K, terminals, hidden_dim, epochs, learning_rate, loss, samples,
+                            anneal_sweeps, max_descent_sweeps, seed, node_cost=node_cost)
     return solve_batch(batch, number_classes=K, terminals=terminals, hidden_dim=hidden_dim, epochs=epochs,
                        learning_rate=learning_rate, loss=loss, samples=samples, anneal_sweeps=anneal_sweeps,
                        max_descent_sweeps=max_descent_sweeps, seed=seed, tabu_iterations=tabu_iterations, fixed=fixed,
@@ -141,11 +169,15 @@ def solve(edge_index, ptr=None, num_nodes: Optional[int] = None, edge_weight=Non
 def solve_batch(batch: GraphBatch, *, number_classes: int = 2, terminals: bool = False, hidden_dim: int, epochs: int,
                 learning_rate: float, loss: str = "expected_cut", samples: int = 32, anneal_sweeps: int = 100,
                 max_descent_sweeps: int = 100, seed: int = 0, tabu_iterations: int = 0, fixed=None, class_sizes=None,
-                balance_iterations: Optional[int] = None) -> MaxCutResult:
+                balance_iterations: Optional[int] = None, node_cost=None) -> MaxCutResult:
     """Steps 2 to 6 of :func:`solve` on a ready batch - one built on the device or one built from handles: the batches
     hold the same bytes, so the results do too.  ``fixed``: as :func:`solve`, with row ids of ``batch``;
-    ``class_sizes`` and ``balance_iterations``: as :func:`solve`."""
+    ``class_sizes``, ``balance_iterations`` and ``node_cost`` (rows = batch rows): as :func:`solve`."""
     _check_sizes(class_sizes, balance_iterations, fixed)
+    if node_cost is not None:
+        node_cost = _check_node_cost(node_cost, batch.R, int(number_classes), tabu_iterations, class_sizes, fixed)
+        return _solve_batch(_small_route(), batch, number_classes, terminals, hidden_dim, epochs, learning_rate, loss,
+                            samples, anneal_sweeps, max_descent_sweeps, seed, node_cost=node_cost)
     return _solve_fixed(_small_route(), batch, fixed, number_classes, terminals, hidden_dim, epochs, learning_rate, loss,
                         samples, anneal_sweeps, max_descent_sweeps, seed, tabu_iterations, class_sizes,
                         balance_iterations)
@@ -155,7 +187,7 @@ def solve_large(edge_index, ptr=None, num_nodes: Optional[int] = None, edge_weig
                 terminals: bool = False, pairs: str = "both", hidden_dim: int, epochs: int, learning_rate: float,
                 loss: str = "expected_cut", samples: int = 32, anneal_sweeps: int = 100, max_descent_sweeps: int = 100,
                 seed: int = 0, tabu_iterations: int = 0, fixed=None, class_sizes=None,
-                balance_iterations: Optional[int] = None) -> MaxCutResult:
+                balance_iterations: Optional[int] = None, node_cost=None) -> MaxCutResult:
     """:func:`solve` for graphs of up to ``hip.LARGE_MAX_GRAPH_NODES`` (2^20) nodes: the same arguments, steps and
     result, with ``engine.LargeInstanceEngine`` (gmc_inst_large_*) as the trainer and the large decoders (one rounding,
     one sampler and one annealing call of gmc_large_*_t_f32; several workgroups share a graph).  It takes small graphs
@@ -166,7 +198,10 @@ def solve_large(edge_index, ptr=None, num_nodes: Optional[int] = None, edge_weig
     hidden_dim rounded up to 32): 1.5 KB per node at hidden_dim = 64.  The tabu stage keeps a graph's state in one
     workgroup, so this route does not have it: ``tabu_iterations`` is taken for the sake of one signature and anything
     but 0 raises ``NotImplementedError``.  So are ``class_sizes`` and ``balance_iterations``: the balanced stage is the
-    tabu kernel's sibling, and ``class_sizes`` other than ``None`` raises ``NotImplementedError``."""
+    tabu kernel's sibling, and ``class_sizes`` other than ``None`` raises ``NotImplementedError``.  ``node_cost`` other
+    than ``None`` raises it too: the large head and decoders take no per-node costs."""
+    if node_cost is not None:
+        raise NotImplementedError(_NO_COST_LARGE)
     if tabu_iterations:
         raise NotImplementedError(_NO_TABU)
     if class_sizes is not None:
@@ -187,10 +222,12 @@ def solve_large_batch(batch: GraphBatch, *, number_classes: int = 2, terminals: 
                       epochs: int, learning_rate: float, loss: str = "expected_cut", samples: int = 32,
                       anneal_sweeps: int = 100, max_descent_sweeps: int = 100, seed: int = 0,
                       tabu_iterations: int = 0, fixed=None, class_sizes=None,
-                      balance_iterations: Optional[int] = None) -> MaxCutResult:
+                      balance_iterations: Optional[int] = None, node_cost=None) -> MaxCutResult:
     """:func:`solve_batch` through ``engine.LargeInstanceEngine`` and the large decoders: steps 2 to 4 of
     :func:`solve_large` on a ready batch (``tabu_iterations``, ``class_sizes``: as :func:`solve_large`; ``fixed``: as
-    :func:`solve_batch`)."""
+    :func:`solve_batch`; ``node_cost``: as :func:`solve_large`)."""
+    if node_cost is not None:
+        raise NotImplementedError(_NO_COST_LARGE)
     if class_sizes is not None:
         raise NotImplementedError(_NO_BALANCE)
     return _solve_fixed(_large_route(), batch, fixed, number_classes, terminals, hidden_dim, epochs, learning_rate, loss,
@@ -207,6 +244,41 @@ def _check_fixed(fixed, terminals: bool, number_classes: int) -> None:
     if not isinstance(fixed, (tuple, list)) or len(fixed) != 2:
         raise ValueError("fixed must be a pair (nodes, classes)")
     _check_pins(fixed[0], fixed[1], number_classes)
+
+
+def _rows_of(ptr, num_nodes) -> Optional[int]:
+    """The batch's row count as ``ptr`` / ``num_nodes`` state it (None when they do not: from_edge_index then raises)."""
+    if ptr is not None:
+        p = ptr.detach().cpu().numpy() if isinstance(ptr, torch.Tensor) else np.asarray(ptr)
+        return int(p[-1]) if p.ndim == 1 and p.size >= 1 else None
+    return None if num_nodes is None else int(num_nodes)
+
+
+def _check_node_cost(node_cost, rows: Optional[int], K: int, tabu_iterations=0, class_sizes=None, fixed=None) -> torch.Tensor:
+    """The argument errors of ``node_cost``, raised before anything is built; returns it as a float32 tensor [R, K]
+    (on whatever device it came from: the one conversion)."""
+    if isinstance(node_cost, torch.Tensor):
+        t = node_cost.detach()
+        if not t.is_floating_point():
+            raise ValueError(f"node_cost must hold floats, got {t.dtype}")
+    else:
+        a = np.asarray(node_cost)
+        if not np.issubdtype(a.dtype, np.floating):
+            raise ValueError(f"node_cost must hold floats, got {a.dtype}")
+        t = torch.from_numpy(np.ascontiguousarray(a))
+    if t.dim() != 2 or t.shape[1] != K or (rows is not None and t.shape[0] != rows):
+        raise ValueError(f"node_cost must be [R, number_classes] = [{'R' if rows is None else rows}, {K}], got "
+                         f"{tuple(t.shape)}")
+    t = t.to(torch.float32)
+    if not bool(torch.isfinite(t).all()):
+        raise ValueError("node_cost holds values that are not finite (in float32)")
+    if tabu_iterations:
+        raise NotImplementedError(_NO_COST_TABU)
+    if class_sizes is not None:
+        raise NotImplementedError(_NO_COST_SIZES)
+    if fixed is not None:
+        raise NotImplementedError(_NO_COST_FIXED)
+    return t.contiguous()
 
 
 def _check_sizes(class_sizes, balance_iterations, fixed) -> None:
@@ -263,7 +335,8 @@ def _solve_fixed(route: "_Route", batch: GraphBatch, fixed, number_classes: int,
 class _Route:
     """What tells :func:`solve_batch` from :func:`solve_large_batch`: the engine class, the refusal of a batch by its
     largest graph, and the three decoders as ``round(batch, P, terminals)``, ``sample(batch, P, samples, seed, terminals)``
-    and ``anneal(batch, K, cands, inv_temp, seed, max_descent_sweeps, terminals)``; ``tabu(batch, K, cands, iterations,
+    and ``anneal(batch, K, cands, inv_temp, seed, max_descent_sweeps, terminals)`` (the small route's three take a
+    trailing ``node_cost`` as well); ``tabu(batch, K, cands, iterations,
     seed, terminals)`` and ``balance(batch, K, cands, lo, hi, iterations, seed, terminals)`` where the route has the
     stage."""
     engine: type
@@ -283,10 +356,11 @@ def _small_route() -> _Route:
             raise ValueError(_TOO_LARGE.format(n=n_max, K=K))
 
     return _Route(InstanceEngine, refuse,
-                  lambda batch, P, t: T._round_on_gpu(batch, P, 0, t),
-                  lambda batch, P, n, seed, t: T._kway_sample_on_gpu(batch, P, n, seed, range(batch.B), True, t)[3],
-                  lambda batch, K, cands, inv_temp, seed, sweeps, t: T._kway_anneal_on_gpu(batch, K, cands, inv_temp, seed,
-                                                                                           sweeps, t),
+                  lambda batch, P, t, c=None: T._round_on_gpu(batch, P, 0, t, c),
+                  lambda batch, P, n, seed, t, c=None: T._kway_sample_on_gpu(batch, P, n, seed, range(batch.B), True, t,
+                                                                             c)[3],
+                  lambda batch, K, cands, inv_temp, seed, sweeps, t, c=None: T._kway_anneal_on_gpu(batch, K, cands, inv_temp,
+                                                                                                   seed, sweeps, t, c),
                   lambda batch, K, cands, iterations, seed, t: T._kway_tabu_on_gpu(batch, K, cands, iterations,
                                                                                    T.TABU_TENURE, seed, t),
                   lambda batch, K, cands, lo, hi, iterations, seed, t: T._kway_balance_on_gpu(batch, K, cands, lo, hi,
@@ -312,8 +386,12 @@ def _large_route() -> _Route:
 def _solve_batch(route: _Route, batch: GraphBatch, number_classes: int, terminals: bool, hidden_dim: int, epochs: int,
                  learning_rate: float, loss: str, samples: int, anneal_sweeps: int, max_descent_sweeps: int,
                  seed: int, tabu_iterations: int = 0, class_sizes=None, balance_iterations: Optional[int] = None,
-                 parts: Optional[dict] = None) -> MaxCutResult:
-    """``parts``: a dict that receives the partitions behind ``trained_cut``, ``rounded_cut`` (and ``annealed_cut``)."""
+                 parts: Optional[dict] = None, *, node_cost: Optional[torch.Tensor] = None,
+                 abs_scale: bool = False) -> MaxCutResult:
+    """``parts``: a dict that receives the partitions behind ``trained_cut``, ``rounded_cut`` (and ``annealed_cut``).
+    ``node_cost``: a float32 tensor [R, K] that :func:`_check_node_cost` has returned - the public doors check once and
+    pass the checked tensor down (small route, no tabu, no bounds, no pins); ``abs_scale``: the annealing's
+    temperature in units of the mean absolute edge weight (the doors with signed weights)."""
     from .Testing import TestingNeuralNetwork as T
     K, terminals = int(number_classes), bool(terminals)
     if not 2 <= K <= hip.KWAY_MAX_CLASSES:
@@ -334,7 +412,14 @@ def _solve_batch(route: _Route, batch: GraphBatch, number_classes: int, terminal
     loss = hip.loss_name(loss)
     if batch.B:
         route.refuse(batch.n_max, K, loss)
-    eng = route.engine(batch, int(hidden_dim), K, batch.device, terminals=terminals)
+    cost = {}
+    if node_cost is not None:
+        if route.tabu is None:
+            raise NotImplementedError(_NO_COST_LARGE)
+        node_cost = node_cost.to(batch.device)
+        cost = {"node_cost": node_cost}
+    dec = () if node_cost is None else (node_cost,)   # the decoders' trailing argument
+    eng = route.engine(batch, int(hidden_dim), K, batch.device, terminals=terminals, **cost)
     with torch.random.fork_rng(devices=[]):
         torch.manual_seed(int(seed))
         eng.reset_parameters()
@@ -347,18 +432,22 @@ def _solve_batch(route: _Route, batch: GraphBatch, number_classes: int, terminal
     dev = batch.device
     if batch.B == 0:
         none = torch.empty(0, dtype=torch.float32, device=dev)
-        return MaxCutResult(best_S, none, none.clone(), none.clone(), batch.goff)
-    rounded, rounded_cut, _, _ = route.round(batch, P, terminals)
+        return MaxCutResult(best_S, none, none.clone(), none.clone(), batch.goff,
+                            node_cost_sum=None if node_cost is None else none.clone())
+    rounded, rounded_cut, _, _ = route.round(batch, P, terminals, *dec)
     trained = best_S.to(torch.int8).reshape(1, -1)
     no_sweeps = np.zeros(0, np.float32)
-    _, trained_cut, _ = route.anneal(batch, K, trained.clone(), no_sweeps, 0, 0, terminals)   # scores, moves nothing
+    _, trained_cut, _ = route.anneal(batch, K, trained.clone(), no_sweeps, 0, 0, terminals, *dec)   # scores, moves nothing
     rows = [trained, rounded.reshape(1, -1)]
     if samples > 0:
-        rows.append(route.sample(batch, P, int(samples), int(seed) & T._M64, terminals))
+        rows.append(route.sample(batch, P, int(samples), int(seed) & T._M64, terminals, *dec))
     cands = torch.cat(rows).contiguous()
-    scale = T._mean_edge_weight(batch) if bounds is None else _mean_abs_edge_weight(batch)
+    scale = T._mean_edge_weight(batch) if bounds is None and not abs_scale else _mean_abs_edge_weight(batch)
     inv_temp = T.anneal_schedule(int(anneal_sweeps), scale=scale)
-    partition, cut, _ = route.anneal(batch, K, cands, inv_temp, seed, int(max_descent_sweeps), terminals)
+    partition, cut, _ = route.anneal(batch, K, cands, inv_temp, seed, int(max_descent_sweeps), terminals, *dec)
+    if node_cost is not None:
+        return MaxCutResult(partition, cut, trained_cut, rounded_cut, batch.goff,
+                            node_cost_sum=_node_cost_sum(batch, node_cost, partition))
     if parts is not None:
         parts.update(trained=best_S, rounded=rounded)
         if tabu_iterations:
@@ -377,3 +466,146 @@ def _solve_batch(route: _Route, batch: GraphBatch, number_classes: int, terminal
     iterations = 20 * int(batch.n_max) if balance_iterations is None else int(balance_iterations)
     within, within_cut = route.balance(batch, K, cands.clone(), bounds[0], bounds[1], iterations, seed, terminals)[:2]
     return MaxCutResult(within, within_cut, trained_cut, rounded_cut, batch.goff, annealed_cut, unconstrained_cut=cut)
+
+
+def _node_cost_sum(batch: GraphBatch, node_cost: torch.Tensor, partition: torch.Tensor) -> torch.Tensor:
+    """[B] float32: sum_v node_cost[v][partition_v] per graph, without atomics: a float64 running sum over the batch's
+    rows (a scan: the same bits every time), differenced at the graphs' boundaries."""
+    picked = node_cost.gather(1, partition.to(torch.int64).reshape(-1, 1)).reshape(-1).to(torch.float64)
+    run = torch.cat([picked.new_zeros(1), torch.cumsum(picked, 0)])
+    goff = batch.goff.to(torch.int64)
+    return (run[goff[1:]] - run[goff[:-1]]).to(torch.float32)
+
+
+@dataclass
+class IsingResult:
+    """What :func:`solve_ising` returns."""
+    spins: torch.Tensor    # [R] int8: +1 / -1 (device)
+    energy: torch.Tensor   # [B] float64: H(spins) per graph (host)
+    ptr: torch.Tensor      # [B + 1] int32
+    result: MaxCutResult   # the max-cut run behind it: class 0 is spin +1, result.cut the objective sum(J) - H
+
+
+@dataclass
+class QuboResult:
+    """What :func:`solve_qubo` returns."""
+    x: torch.Tensor        # [R] int8: 0 / 1 (device)
+    energy: torch.Tensor   # [B] float32: E(x) per graph (device)
+    ptr: torch.Tensor      # [B + 1] int32
+    result: MaxCutResult   # the max-cut run behind it: class 1 is x = 1, result.cut the objective -E
+
+
+def _edge_values(what: str, values, E: int) -> Optional[np.ndarray]:
+    if values is None:
+        return None
+    v = values.detach().cpu().numpy() if isinstance(values, torch.Tensor) else np.asarray(values)
+    if v.ndim != 1 or v.shape[0] != E:
+        raise ValueError(f"{what} must be [E] = [{E}], got {tuple(v.shape)}")
+    if not np.all(np.isfinite(v.astype(np.float64))):
+        raise ValueError(f"{what} holds values that are not finite")
+    return v.astype(np.float64)
+
+
+def _node_values(what: str, values, rows: int) -> np.ndarray:
+    if values is None:
+        return np.zeros(rows, np.float64)
+    v = values.detach().cpu().numpy() if isinstance(values, torch.Tensor) else np.asarray(values)
+    if v.ndim != 1 or v.shape[0] != rows:
+        raise ValueError(f"{what} must be [R] = [{rows}], got {tuple(v.shape)}")
+    if not np.all(np.isfinite(v.astype(np.float64))):
+        raise ValueError(f"{what} holds values that are not finite")
+    return v.astype(np.float64)
+
+
+def _door(edge_index, ptr, num_nodes):
+    """(edge_index on the host, graph offsets [B + 1] int64) of a door's arguments."""
+    ei = edge_index.detach().cpu().numpy() if isinstance(edge_index, torch.Tensor) else np.asarray(edge_index)
+    if ei.ndim != 2 or ei.shape[0] != 2:
+        raise ValueError(f"edge_index must be [2, E], got {tuple(ei.shape)}")
+    if (ptr is None) == (num_nodes is None):
+        raise ValueError("pass exactly one of ptr (graph boundaries) and num_nodes (a single graph)")
+    goff = np.asarray([0, int(num_nodes)], np.int64) if ptr is None else (
+        ptr.detach().cpu().numpy() if isinstance(ptr, torch.Tensor) else np.asarray(ptr)).astype(np.int64)
+    if goff.ndim != 1 or goff.size < 1:
+        raise ValueError("ptr must be [B + 1]")
+    return ei, goff
+
+
+def _solve_door(batch: GraphBatch, node_cost: np.ndarray, hidden_dim, epochs, learning_rate, loss, samples, anneal_sweeps,
+                max_descent_sweeps, seed) -> MaxCutResult:
+    loss = hip.loss_name(loss)
+    if batch.B and instance_too_large(batch.n_max, 2, loss):
+        raise ValueError(_TOO_LARGE.format(n=batch.n_max, K=2))
+    return _solve_batch(_small_route(), batch, 2, False, hidden_dim, epochs, learning_rate, loss, samples, anneal_sweeps,
+                        max_descent_sweeps, seed, node_cost=_check_node_cost(node_cost, batch.R, 2), abs_scale=True)
+
+
+def solve_ising(edge_index, ptr=None, num_nodes: Optional[int] = None, coupling=None, field=None, *, pairs: str = "both",
+                hidden_dim: int, epochs: int, learning_rate: float, loss: str = "expected_cut", samples: int = 32,
+                anneal_sweeps: int = 100, max_descent_sweeps: int = 100, seed: int = 0) -> IsingResult:
+    """Minimises ``H(s) = sum_{i<j} J_ij s_i s_j + sum_i h_i s_i`` over ``s`` in {+1, -1}^n for every graph of a batch:
+    ``edge_index`` / ``ptr`` / ``num_nodes`` / ``pairs`` as :func:`solve` takes them, ``coupling`` [E] the J of every
+    entry (``None``: 1; with ``pairs="both"`` both directions carry the same J), ``field`` [R] the h of every node
+    (``None``: 0); the training and decoding keywords are :func:`solve`'s.
+
+    The mapping onto :func:`solve` is exact: edge weight ``w = 2 J``, two classes without terminals, class 0 is ``s =
+    +1``, ``node_cost[i] = (h_i, -h_i)``; then ``H(s) = sum_{i<j} J_ij - obj``, ``obj`` the objective ``cut - cost``
+    the solver maximises.  The weights are signed, so the annealing's temperature is in units of the mean absolute edge
+    weight.  Returns ``spins`` [R] int8, ``energy`` [B] float64 (``sum J`` taken in float64 on the host, ``obj`` the
+    solver's float32), ``ptr`` and the :class:`MaxCutResult` as ``.result``.
+
+    A spin without any coupling is refused by the batch builder (``ValueError``: "nodes without neighbours"); its optimum
+    is its own sign, ``s_i = -sign(h_i)`` - leave it out and add ``-|h_i|`` to the energy."""
+    ei, goff = _door(edge_index, ptr, num_nodes)
+    E, R = ei.shape[1], int(goff[-1])
+    J = _edge_values("coupling", coupling, E)
+    h = _node_values("field", field, R)
+    J = np.ones(E, np.float64) if J is None else J
+    src, dst = ei[0].astype(np.int64), ei[1].astype(np.int64)
+    once = src < dst if pairs == "both" else src != dst   # every undirected edge once; a self-loop is no i < j
+    B = goff.size - 1
+    graph = np.clip(np.searchsorted(goff, src[once], side="right") - 1, 0, max(B - 1, 0))
+    sum_j = np.zeros(B, np.float64)
+    np.add.at(sum_j, graph, J[once])
+    node_cost = np.stack([h, -h], axis=1).astype(np.float32)
+    batch = GraphBatch.from_edge_index(edge_index, ptr, num_nodes, (2.0 * J).astype(np.float32), pairs=pairs)
+    res = _solve_door(batch, node_cost, hidden_dim, epochs, learning_rate, loss, samples, anneal_sweeps,
+                      max_descent_sweeps, seed)
+    spins = (1 - 2 * res.partition).to(torch.int8)
+    energy = torch.from_numpy(sum_j) - res.cut.detach().cpu().to(torch.float64)
+    return IsingResult(spins, energy, res.ptr, res)
+
+
+def solve_qubo(edge_index, ptr=None, num_nodes: Optional[int] = None, quadratic=None, linear=None, *, pairs: str = "both",
+               hidden_dim: int, epochs: int, learning_rate: float, loss: str = "expected_cut", samples: int = 32,
+               anneal_sweeps: int = 100, max_descent_sweeps: int = 100, seed: int = 0) -> QuboResult:
+    """Minimises ``E(x) = sum_i a_i x_i + sum_{i<j} q_ij x_i x_j`` over ``x`` in {0, 1}^n for every graph of a batch:
+    ``edge_index`` / ``ptr`` / ``num_nodes`` / ``pairs`` as :func:`solve` takes them, ``quadratic`` [E] the q of every
+    entry (``None``: 1; with ``pairs="both"`` both directions carry the same q), ``linear`` [R] the a of every variable
+    (``None``: 0); the training and decoding keywords are :func:`solve`'s.
+
+    The mapping onto :func:`solve` is exact and has no offset: edge weight ``w_ij = q_ij / 2``, two classes without
+    terminals, class 1 is ``x = 1``, ``node_cost[i] = (0, a_i + 1/2 sum_j q_ij)``; then ``E(x) = -obj``.  The row sums
+    ``1/2 sum_j q_ij = sum_j w_ij`` are taken on the device from the built batch's sorted CSR, one thread per row in CSR
+    order (gmc_row_weight_sums_f32: no atomics, the same bits every time).  The weights are signed, so the annealing's
+    temperature is in units of the mean absolute edge weight.  Returns ``x`` [R] int8, ``energy`` [B] float32, ``ptr``
+    and the :class:`MaxCutResult` as ``.result``.
+
+    A variable without any quadratic term is refused by the batch builder (``ValueError``: "nodes without
+    neighbours"); its optimum is its own sign, ``x_i = 1`` iff ``a_i < 0`` - leave it out and add ``min(a_i, 0)``."""
+    ei, goff = _door(edge_index, ptr, num_nodes)
+    E, R = ei.shape[1], int(goff[-1])
+    q = _edge_values("quadratic", quadratic, E)
+    a = _node_values("linear", linear, R)
+    q = np.ones(E, np.float64) if q is None else q
+    batch = GraphBatch.from_edge_index(edge_index, ptr, num_nodes, (0.5 * q).astype(np.float32), pairs=pairs)
+    half = torch.zeros(batch.R, dtype=torch.float32, device=batch.device)
+    if batch.R:
+        rc = hip.load().gmc_row_weight_sums_f32(batch.R, hip.ptr(batch.rowptr), hip.ptr(batch.gcol), hip.ptr(batch.vals),
+                                                hip.ptr(half), hip.stream())
+        hip.check(rc, "gmc_row_weight_sums_f32")
+    node_cost = np.zeros((R, 2), np.float32)
+    node_cost[:, 1] = a.astype(np.float32) + half.cpu().numpy()   # (one fp32 addition per variable)
+    res = _solve_door(batch, node_cost, hidden_dim, epochs, learning_rate, loss, samples, anneal_sweeps,
+                      max_descent_sweeps, seed)
+    return QuboResult(res.partition.to(torch.int8), -res.cut, res.ptr, res)

@@ -1602,6 +1602,90 @@ int gmc_contract_entries(const gmc_batch *batch, int32_t K, const int32_t *node_
                          int32_t *dst_out /*[E_out]*/, float *w_out /*[E_out]*/, float *fixed_cut /*[B]*/,
                          void *workspace, size_t workspace_bytes, gmc_stream_t stream);
 
+/* ---- per-node class costs: a linear term in the objective ---------------------------------------------------------------
+ * Everything above maximises the pairwise objective cut(S) = sum over undirected edges {u,v} of w_uv [S_u != S_v].  The
+ * entry points below are `_t` entry points with one more argument, `node_cost`, directly after `terminals`: [R][K] fp32
+ * device memory, row-major, indexed by BATCH ROW (the row goff[g] + l of local node l of graph g), or NULL.  They serve
+ *
+ *   obj(S) = cut(S) - sum_v node_cost[v][S_v]
+ *
+ * the sum over every node of the graph, terminals included (their share is a constant of the graph); a class byte outside
+ * 0..K-1 adds no cost, as it adds to no class sum.  A QUBO or an Ising model with fields is this objective at K = 2
+ * (DESIGN.md section 33 has the two changes of variables).  With node_cost == NULL every `_c` entry point IS its `_t` twin
+ * - the `_t` entry points are these calls with NULL - the same kernels, the same bytes on every output.  With a cost
+ * the sampler and the head run the same instantiations (node_cost is a run-time pointer of theirs); the annealing and
+ * the rounding launch a second kernel compiled from the same body text with the cost switched on
+ * (anneal_k_cost_kernel<K>, round_conditional_cost_kernel<K>), so that the kernels of the NULL call keep, instruction
+ * for instruction, the code they had (DESIGN.md section 33 has the measurements behind that).  The cost is read from
+ * global memory (K loads per visit), never staged in LDS: the LDS of every launch is what it was.  No float atomics,
+ * no scratch, bitwise reproducible.  Argument checks and status codes
+ * are the `_t` twin's, in its order; node_cost is optional and its contents are never checked (a NaN or an infinity in it
+ * behaves as it would in an edge weight).  The rules, operation by operation:
+ *
+ * 1. Class sums (annealing, local search / descent; move_body.h).  The K sums of a visit of local node v of the graph on
+ *    rows r0.. start from node_cost[r0 + v][k] instead of +0.0f; the row's edges are then added in CSR order exactly as
+ *    before.  Everything derived from the sums is unchanged: the smallest sum and the smallest among the others (lowest
+ *    index on ties), the Metropolis test delta = W[kk] - W[c] against the level table, the descent's strict "<".  The same
+ *    holds for the rounding's M_k (round_body.h): M_k starts from node_cost[r0 + v][k], and product and sum of every
+ *    edge term stay separately rounded.  An all-+0.0f node_cost therefore gives the NULL call's bytes on every output.
+ *
+ * 2. Scores.  Wherever a state is scored - the sampler's cut_all, the rounding's cut, the annealing's best-state
+ *    bookkeeping (the snapshot is taken when the OBJECTIVE improved) and its final cut_all, and so the input of every
+ *    pick - the score is block_cut(...) - block_cost(...), one fp32 subtraction, not fused with the cut's halving:
+ *    block_cut is the count stated above (edge-parallel, each edge twice, halved); block_cost sums node_cost[r0 + l][S_l]
+ *    (nothing for a byte outside 0..K-1) over the rows l = t, t + 256, ... of thread t from +0, then the wave's butterfly
+ *    (v[i] += v[i ^ d], d = 32 .. 1), then the four wave sums as ((q0 + q1) + q2) + q3 - block_cut's order (cut_body.h).
+ *    best_cut / cut outputs hold that score; the plain cut of a returned state is score + its cost.
+ *
+ * 3. The rounding's `expected` output becomes the expected objective: the expected cut as before, minus the expected cost
+ *    sum_v sum_k node_cost[v][k] q_v[k], q the state the rounding starts from (terminal rows e_l).  Order: per row
+ *    t_v = +0 then + node_cost[v][k] * q_v[k] for k ascending, product and sum separately rounded; the rows l = t, t + 256,
+ *    ... of thread t added from +0; butterfly; ((q0 + q1) + q2) + q3; then one fp32 subtraction from the (halved) expected
+ *    cut.  obj(rounded) >= expected objective holds as before: the linear term is separable, so a visit that takes the
+ *    smallest M_k (cost included) does not lower the conditional expectation; the descent never lowers obj.
+ *
+ * 4. Head of the instance calls (head_k_kernel).  gp[k] of row u starts from node_cost[u][k] before the edge loop, so
+ *    GP_u = C (sum_v w_uv Pt_v + node_cost_u) (hard loss: Pt_v = e_{S_v}); the loss is -C (cut - costsum) with costsum =
+ *    sum_u node_cost_u . Pt_u for GMC_LOSS_EXPECTED_CUT (Pt: P with the terminal rows overridden) and sum_u
+ *    node_cost[u][S_u] for the hard loss.  Summation: row u adds (cut_u - 2 cost_u) to the accumulator that held cut_u
+ *    (cut_u the row's doubled share, cost_u = the k-ascending dot product, or the one selected entry), and the block sum
+ *    and the halving are the ones that were: one reduction, no extra LDS.  The softmax backward, db2, GY2 and everything
+ *    downstream follow from gp unchanged.  The 3-class fused head and the gmc_inst_large_* sequence take no cost. */
+int gmc_round_conditional_c_f32(const gmc_batch *batch, const float *P /*[R,K]*/, int32_t K, int32_t terminals,
+                                const float *node_cost /*[R][K] or NULL*/, const int32_t *order, const int32_t *cgoff,
+                                const int32_t *cptr, int32_t max_descent_sweeps, int8_t *assign /*[R]*/,
+                                float *cut /*[B]*/, float *expected /*[B] or NULL*/, int32_t *sweeps /*[B] or NULL*/,
+                                gmc_stream_t stream);
+
+int gmc_kway_decode_sample_seeded_c_f32(const gmc_batch *batch, const float *P /*[R,K]*/, int32_t K, int32_t terminals,
+                                        const float *node_cost /*[R][K] or NULL*/, const uint64_t *gkey /*[B]*/,
+                                        int32_t iters, int8_t *assign_all /*[iters][R] or NULL*/,
+                                        float *cut_all /*[B][iters]*/, int32_t *best_assign /*[R]*/,
+                                        float *best_cut /*[B]*/, int32_t *best_iter /*[B]*/, gmc_stream_t stream);
+
+int gmc_kway_refine_anneal_c_f32(const gmc_batch *batch, int32_t K, int32_t terminals,
+                                 const float *node_cost /*[R][K] or NULL*/, const int32_t *order, const int32_t *cgoff,
+                                 const int32_t *cptr, int32_t cands, int8_t *assign /*[cands][R], in/out*/,
+                                 const float *inv_temp, int32_t anneal_sweeps, const float *levels, uint64_t seed,
+                                 int32_t max_descent_sweeps, float *cut_all /*[B][cands]*/, int32_t *best_assign /*[R]*/,
+                                 float *best_cut /*[B]*/, int32_t *best_idx /*[B]*/, int32_t *snap_sweep /*or NULL*/,
+                                 int32_t *sweeps /*or NULL*/, gmc_stream_t stream);
+
+int gmc_inst_forward_c(const gmc_batch *batch, const gmc_model *model, int32_t terminals,
+                       const float *node_cost /*[R][K] or NULL*/, float C, void *workspace, size_t workspace_bytes,
+                       float *P, int32_t *S, float *loss, gmc_stream_t stream);
+
+int gmc_inst_train_fwd_bwd_c(const gmc_batch *batch, const gmc_model *model, int32_t terminals,
+                             const float *node_cost /*[R][K] or NULL*/, float C, void *workspace, size_t workspace_bytes,
+                             float *P, int32_t *S, float *loss, float *grad, gmc_stream_t stream);
+
+/* out[r] = the float32 sum that starts at +0 and adds the weights of row r's entries one after the other in the row's
+ * (sorted) CSR order, the entry on the diagonal (gcol[e] == r) skipped; vals == NULL: every weight is 1.  One thread per
+ * row, one launch, no atomics: the order holds by construction.  (maxcut.solve_qubo takes sum_j q_ij from it.)  NULL rowptr
+ * / out GMC_ERR_NULL; R < 0 GMC_ERR_SHAPE; R == 0 GMC_OK without a launch; NULL gcol GMC_ERR_NULL. */
+int gmc_row_weight_sums_f32(int32_t R, const int32_t *rowptr /*[R+1]*/, const int32_t *gcol /*[nnz], global row ids*/,
+                            const float *vals /*[nnz] or NULL*/, float *out /*[R]*/, gmc_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
