@@ -828,6 +828,16 @@ def _tabu_arguments(what: str, iterations: int, tenure) -> Tuple[int, int, int]:
     return base, span, div
 
 
+def _chain_outputs(batch: GraphBatch, cands: int):
+    """What both chain searches write: cut_all [B, cands], best_assign [R], best_cut and best_idx [B], best_iter and
+    moves [B, cands]."""
+    dev = batch.device
+    per_chain = lambda dtype: torch.empty((batch.B, cands), dtype=dtype, device=dev)
+    return (per_chain(torch.float32), torch.empty(batch.R, dtype=torch.int32, device=dev),
+            torch.empty(batch.B, dtype=torch.float32, device=dev), torch.empty(batch.B, dtype=torch.int32, device=dev),
+            per_chain(torch.int32), per_chain(torch.int32))
+
+
 def _kway_tabu_on_gpu(batch: GraphBatch, K: int, assign: torch.Tensor, iterations: int, tenure, seed: int,
                       terminals: bool = True):
     """One-flip tabu search at K classes (gmc_kway_tabu_f32) over the candidates assign [cands, R] int8, in place:
@@ -835,14 +845,8 @@ def _kway_tabu_on_gpu(batch: GraphBatch, K: int, assign: torch.Tensor, iteration
     assignment [R], its cut and candidate index per graph, then best_iter and moves [B, cands] and cut_all [B, cands]."""
     _needs_terminals(batch, K, terminals)
     base, span, div = _tabu_arguments("the tabu search", iterations, tenure)
-    dev = batch.device
     cands = int(assign.shape[0])
-    cut_all = torch.empty((batch.B, cands), dtype=torch.float32, device=dev)
-    best_assign = torch.empty(batch.R, dtype=torch.int32, device=dev)
-    best_cut = torch.empty(batch.B, dtype=torch.float32, device=dev)
-    best_idx = torch.empty(batch.B, dtype=torch.int32, device=dev)
-    best_iter = torch.empty((batch.B, cands), dtype=torch.int32, device=dev)
-    moves = torch.empty((batch.B, cands), dtype=torch.int32, device=dev)
+    cut_all, best_assign, best_cut, best_idx, best_iter, moves = _chain_outputs(batch, cands)
     p = hip.ptr
     rc = hip.load().gmc_kway_tabu_f32(batch.ref(), K, 1 if terminals else 0, cands, p(assign), int(iterations), base,
                                       span, div, int(seed) & _M64, p(cut_all), p(best_assign), p(best_cut), p(best_idx),
@@ -928,13 +932,8 @@ def _kway_balance_on_gpu(batch: GraphBatch, K: int, assign: torch.Tensor, lo: np
     cands = int(assign.shape[0])
     size_lo = torch.from_numpy(np.ascontiguousarray(lo, np.int32)).to(dev)
     size_hi = torch.from_numpy(np.ascontiguousarray(hi, np.int32)).to(dev)
-    cut_all = torch.empty((batch.B, cands), dtype=torch.float32, device=dev)
-    best_assign = torch.empty(batch.R, dtype=torch.int32, device=dev)
-    best_cut = torch.empty(batch.B, dtype=torch.float32, device=dev)
-    best_idx = torch.empty(batch.B, dtype=torch.int32, device=dev)
-    best_iter = torch.empty((batch.B, cands), dtype=torch.int32, device=dev)
-    moves = torch.empty((batch.B, cands), dtype=torch.int32, device=dev)
-    repairs = torch.empty((batch.B, cands), dtype=torch.int32, device=dev)
+    cut_all, best_assign, best_cut, best_idx, best_iter, moves = _chain_outputs(batch, cands)
+    repairs = torch.empty_like(moves)
     p = hip.ptr
     rc = hip.load().gmc_kway_balance_f32(batch.ref(), K, 1 if terminals else 0, cands, p(assign), p(size_lo), p(size_hi),
                                          int(iterations), base, span, div, int(seed) & _M64, p(cut_all), p(best_assign),

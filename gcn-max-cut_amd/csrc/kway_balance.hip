@@ -191,18 +191,8 @@ struct Chain {
         return wave_max(key);
     }
 
-    // step 4 of tabu: node v leaves class c for class k; one lane per edge of its row
-    __device__ __forceinline__ void apply(int v, int c, int k) const {
-        const int e1 = g.rp[v + 1];
-        for (int e = (int)g.rp[v] + lane; e < e1; e += GMC_WAVE) {
-            const int u = g.col[e];
-            if (u == v) continue;
-            const float wt = g.vals ? g.vals[e] : 1.0f;
-            W[u * K + c] -= wt;
-            W[u * K + k] += wt;
-        }
-        if (lane == 0) st[v] = (unsigned char)k;
-    }
+    // step 4 of tabu: node v leaves class c for class k
+    __device__ __forceinline__ void apply(int v, int c, int k) const { gmc::apply_move<K>(g, W, st, v, c, k, lane); }
 };
 
 // One chain on the calling wave: the sizes, the repair, the table, the iterations, the snapshot left in sn.
@@ -304,8 +294,7 @@ __device__ __forceinline__ void balance_chain(const BalanceArgs &a, const G &g, 
                 pending = false;
                 wave_sync();
             }
-            const u64 u64_until = (u64)(unsigned)it + 1ULL + (u64)a.tenure_base + (u64)tenure_draw;
-            const unsigned ban = u64_until > 0xffffffffULL ? 0xffffffffu : (unsigned)u64_until;   // saturated: "never again"
+            const unsigned ban = gmc::ban_until(it, a.tenure_base, tenure_draw);
             ch.apply(v, c, k);
             if (lane == 0) until[v] = ban;
             rel = new_rel;
@@ -438,17 +427,8 @@ __global__ __launch_bounds__(256) void balance_pick_kernel(BalancePickArgs a) {
 
 template <int K>
 int balance_launch(const BalanceArgs &a, const BalancePickArgs &p, int lds_bytes, hipStream_t st) {
-    if (lds_bytes > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(balance_kernel<K>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
-        if (e != hipSuccess) return (int)e;
-    }
-    {
-        GmcProbeScope probe(GMC_K_ANNEAL, st);
-        hipLaunchKernelGGL((balance_kernel<K>), dim3((a.cands + a.slots - 1) / a.slots, a.b.B), dim3(256),
-                           (size_t)lds_bytes, st, a);
-        GMC_LAUNCH_CHECK();
-    }
+    const int rc = gmc::chain_launch(balance_kernel<K>, a, lds_bytes, st);
+    if (rc != GMC_OK) return rc;
     hipLaunchKernelGGL((balance_pick_kernel<K>), dim3(a.b.B), dim3(256), 0, st, p);
     GMC_LAUNCH_CHECK();
     return GMC_OK;
@@ -457,19 +437,11 @@ int balance_launch(const BalanceArgs &a, const BalancePickArgs &p, int lds_bytes
 }  // namespace
 
 extern "C" int gmc_kway_balance_fits(const gmc_batch *batch, int32_t K) {
-    if (!batch) return GMC_ERR_NULL;
-    if (batch->abi != GMC_VERSION) return GMC_ERR_ABI;
-    if (K < 2 || K > GMC_KWAY_MAX_CLASSES) return GMC_ERR_CLASSES;
-    return tabu_layout(batch, K).fits;
+    return gmc::chain_query(batch, K, false);
 }
 
 extern "C" int gmc_kway_balance_shape(const gmc_batch *batch, int32_t K) {
-    if (!batch) return GMC_ERR_NULL;
-    if (batch->abi != GMC_VERSION) return GMC_ERR_ABI;
-    if (K < 2 || K > GMC_KWAY_MAX_CLASSES) return GMC_ERR_CLASSES;
-    const TabuLayout L = tabu_layout(batch, K);
-    if (!L.fits) return GMC_ERR_GRAPH_SIZE;
-    return L.slots | (L.staged << 4);
+    return gmc::chain_query(batch, K, true);
 }
 
 extern "C" int gmc_kway_balance_f32(const gmc_batch *batch, int32_t K, int32_t terminals, int32_t cands, int8_t *assign,
@@ -480,16 +452,11 @@ extern "C" int gmc_kway_balance_f32(const gmc_batch *batch, int32_t K, int32_t t
                                     gmc_stream_t stream) {
     if (!batch || !assign || !size_lo || !size_hi || !cut_all || !best_assign || !best_cut || !best_idx)
         return GMC_ERR_NULL;
-    if (batch->abi != GMC_VERSION) return GMC_ERR_ABI;
-    if (!batch->goff || !batch->rowptr || !batch->lcol) return GMC_ERR_NULL;
-    if (K < 2 || K > GMC_KWAY_MAX_CLASSES) return GMC_ERR_CLASSES;
-    if (cands < 1 || iterations < 0 || tenure_base < 0 || tenure_span < 0 || tenure_div < 0 || batch->B < 0 ||
-        (terminals != 0 && terminals != 1))
-        return GMC_ERR_SHAPE;
-    const int first = terminals ? K : 0;
-    const TabuLayout L = tabu_layout(batch, K);
-    if (batch->B > 0 && (batch->n_max < (first > 1 ? first : 1) || !L.fits)) return GMC_ERR_GRAPH_SIZE;
-    if (batch->B == 0) return GMC_OK;
+    int first;
+    TabuLayout L;
+    int rc = gmc::chain_checks(batch, K, terminals, cands, iterations, tenure_base, tenure_span, tenure_div, first,
+                               L);
+    if (rc != GMC_OK || batch->B == 0) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
     const BalanceArgs a{*batch, first, cands, iterations, (unsigned)tenure_base, (unsigned)tenure_span,
                         (unsigned)tenure_div, seed, reinterpret_cast<signed char *>(assign), size_lo, size_hi, cut_all,
@@ -497,7 +464,6 @@ extern "C" int gmc_kway_balance_f32(const gmc_batch *batch, int32_t K, int32_t t
                         L.off_ids};
     const BalancePickArgs p{{*batch, cands, reinterpret_cast<const signed char *>(assign), cut_all, best_assign,
                              best_cut, best_idx}, first, size_lo, size_hi, feasible};
-    int rc = GMC_OK;
     GMC_KWAY_DISPATCH(K, rc = balance_launch<KK>(a, p, L.bytes, st));
     return rc;
 }

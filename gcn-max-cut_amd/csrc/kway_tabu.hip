@@ -159,19 +159,9 @@ __device__ __forceinline__ void tabu_chain(const TabuArgs &a, const G &g, unsign
                 wave_sync();
             }
             // 4. apply
-            const int c = st[v];
-            const int e1 = g.rp[v + 1];
-            for (int e = (int)g.rp[v] + lane; e < e1; e += GMC_WAVE) {
-                const int u = g.col[e];
-                if (u == v) continue;
-                const float wt = g.vals ? g.vals[e] : 1.0f;
-                W[u * K + c] -= wt;
-                W[u * K + k] += wt;
-            }
+            gmc::apply_move<K>(g, W, st, v, st[v], k, lane);
             if (lane == 0) {
-                st[v] = (unsigned char)k;
-                const u64 u = (u64)(unsigned)it + 1ULL + (u64)a.tenure_base + (u64)tenure_draw;
-                until[v] = u > 0xffffffffULL ? 0xffffffffu : (unsigned)u;   // it < 2^31: saturated is "never again"
+                until[v] = gmc::ban_until(it, a.tenure_base, tenure_draw);
             }
             rel = new_rel;
             ++moves;
@@ -261,36 +251,14 @@ __global__ __launch_bounds__(256) void tabu_pick_kernel(TabuPickArgs a) {
     gmc::pick_best(a.p);
 }
 
-template <int K>
-int tabu_launch(const TabuArgs &a, int lds_bytes, hipStream_t st) {
-    if (lds_bytes > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(tabu_kernel<K>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
-        if (e != hipSuccess) return (int)e;
-    }
-    GmcProbeScope probe(GMC_K_ANNEAL, st);
-    hipLaunchKernelGGL((tabu_kernel<K>), dim3((a.cands + a.slots - 1) / a.slots, a.b.B), dim3(256), (size_t)lds_bytes,
-                       st, a);
-    GMC_LAUNCH_CHECK();
-    return GMC_OK;
-}
-
 }  // namespace
 
 extern "C" int gmc_kway_tabu_fits(const gmc_batch *batch, int32_t K) {
-    if (!batch) return GMC_ERR_NULL;
-    if (batch->abi != GMC_VERSION) return GMC_ERR_ABI;
-    if (K < 2 || K > GMC_KWAY_MAX_CLASSES) return GMC_ERR_CLASSES;
-    return tabu_layout(batch, K).fits;
+    return gmc::chain_query(batch, K, false);
 }
 
 extern "C" int gmc_kway_tabu_shape(const gmc_batch *batch, int32_t K) {
-    if (!batch) return GMC_ERR_NULL;
-    if (batch->abi != GMC_VERSION) return GMC_ERR_ABI;
-    if (K < 2 || K > GMC_KWAY_MAX_CLASSES) return GMC_ERR_CLASSES;
-    const TabuLayout L = tabu_layout(batch, K);
-    if (!L.fits) return GMC_ERR_GRAPH_SIZE;
-    return L.slots | (L.staged << 4);
+    return gmc::chain_query(batch, K, true);
 }
 
 extern "C" int gmc_kway_tabu_f32(const gmc_batch *batch, int32_t K, int32_t terminals, int32_t cands, int8_t *assign,
@@ -298,22 +266,16 @@ extern "C" int gmc_kway_tabu_f32(const gmc_batch *batch, int32_t K, int32_t term
                                  uint64_t seed, float *cut_all, int32_t *best_assign, float *best_cut,
                                  int32_t *best_idx, int32_t *best_iter, int32_t *moves, gmc_stream_t stream) {
     if (!batch || !assign || !cut_all || !best_assign || !best_cut || !best_idx) return GMC_ERR_NULL;
-    if (batch->abi != GMC_VERSION) return GMC_ERR_ABI;
-    if (!batch->goff || !batch->rowptr || !batch->lcol) return GMC_ERR_NULL;
-    if (K < 2 || K > GMC_KWAY_MAX_CLASSES) return GMC_ERR_CLASSES;
-    if (cands < 1 || iterations < 0 || tenure_base < 0 || tenure_span < 0 || tenure_div < 0 || batch->B < 0 ||
-        (terminals != 0 && terminals != 1))
-        return GMC_ERR_SHAPE;
-    const int first = terminals ? K : 0;
-    const TabuLayout L = tabu_layout(batch, K);
-    if (batch->B > 0 && (batch->n_max < (first > 1 ? first : 1) || !L.fits)) return GMC_ERR_GRAPH_SIZE;
-    if (batch->B == 0) return GMC_OK;
+    int first;
+    TabuLayout L;
+    int rc = gmc::chain_checks(batch, K, terminals, cands, iterations, tenure_base, tenure_span, tenure_div, first,
+                               L);
+    if (rc != GMC_OK || batch->B == 0) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
     const TabuArgs a{*batch, first, cands, iterations, (unsigned)tenure_base, (unsigned)tenure_span,
                      (unsigned)tenure_div, seed, reinterpret_cast<signed char *>(assign), cut_all, best_iter, moves,
                      L.slots, L.staged, L.n_pad, L.chain_bytes, L.off_starts, L.off_vals, L.off_ids};
-    int rc = GMC_OK;
-    GMC_KWAY_DISPATCH(K, rc = tabu_launch<KK>(a, L.bytes, st));
+    GMC_KWAY_DISPATCH(K, rc = gmc::chain_launch(tabu_kernel<KK>, a, L.bytes, st));
     if (rc != GMC_OK) return rc;
     const TabuPickArgs p{{*batch, cands, reinterpret_cast<const signed char *>(assign), cut_all, best_assign, best_cut,
                           best_idx}, first};

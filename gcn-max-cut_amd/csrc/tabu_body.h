@@ -1,7 +1,10 @@
-// What the one-wave-per-chain searches share (kway_tabu.hip, kway_balance.hip): the LDS layout of a launch, the ordering
-// of a wave's own LDS traffic, the 64-lane max of a 64-bit key on the VALU and the order-preserving float <-> uint32 map.
+// What the one-wave-per-chain searches share (kway_tabu.hip, kway_balance.hip): the LDS layout of a launch, the host
+// side of their entry points (fits / shape, the argument checks, the launch), the ordering of a wave's own LDS traffic,
+// the 64-lane max of a 64-bit key on the VALU, the order-preserving float <-> uint32 map and the steps of a chain that
+// both kernels take in the same words.
 #pragma once
 #include "gmc_common.h"
+#include "mix64.h"
 
 #define GMC_TABU_LDS_BYTES (160 * 1024)   // the LDS of a CU
 #define GMC_TABU_LDS_STATIC 512           // allowance for red and the pick's word (16 B as built)
@@ -38,6 +41,48 @@ inline TabuLayout tabu_layout(const gmc_batch *b, int K) {
     L.off_ids = L.off_vals + (int)vals;
     L.bytes = L.staged ? L.off_ids + (int)ids : L.off_starts;
     return L;
+}
+
+// gmc_kway_{tabu,balance}_fits, and with `shape` gmc_kway_{tabu,balance}_shape
+inline int chain_query(const gmc_batch *batch, int K, bool shape) {
+    if (!batch) return GMC_ERR_NULL;
+    if (batch->abi != GMC_VERSION) return GMC_ERR_ABI;
+    if (K < 2 || K > GMC_KWAY_MAX_CLASSES) return GMC_ERR_CLASSES;
+    const TabuLayout L = tabu_layout(batch, K);
+    if (!shape) return L.fits;
+    return L.fits ? L.slots | (L.staged << 4) : GMC_ERR_GRAPH_SIZE;
+}
+
+// What the two entry points check after their own NULL test of the pointers each requires, in this order: the abi
+// word, the batch's arrays, K, the shapes, the graph size.  GMC_OK: `first` (the first movable local id: K with
+// terminals, 0 without) and L are the launch's; the caller returns GMC_OK without a launch for a batch of no graphs.
+inline int chain_checks(const gmc_batch *batch, int K, int terminals, int cands, int iterations, int tenure_base,
+                        int tenure_span, int tenure_div, int &first, TabuLayout &L) {
+    if (batch->abi != GMC_VERSION) return GMC_ERR_ABI;
+    if (!batch->goff || !batch->rowptr || !batch->lcol) return GMC_ERR_NULL;
+    if (K < 2 || K > GMC_KWAY_MAX_CLASSES) return GMC_ERR_CLASSES;
+    if (cands < 1 || iterations < 0 || tenure_base < 0 || tenure_span < 0 || tenure_div < 0 || batch->B < 0 ||
+        (terminals != 0 && terminals != 1))
+        return GMC_ERR_SHAPE;
+    first = terminals ? K : 0;
+    L = tabu_layout(batch, K);
+    if (batch->B > 0 && (batch->n_max < (first > 1 ? first : 1) || !L.fits)) return GMC_ERR_GRAPH_SIZE;
+    return GMC_OK;
+}
+
+// the chain launch of either search: Args holds the batch b, cands and slots
+template <class Args>
+int chain_launch(void (*kernel)(Args), const Args &a, int lds_bytes, hipStream_t st) {
+    if (lds_bytes > 64 * 1024) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kernel),
+                                           hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
+        if (e != hipSuccess) return (int)e;
+    }
+    GmcProbeScope probe(GMC_K_ANNEAL, st);
+    hipLaunchKernelGGL(kernel, dim3((a.cands + a.slots - 1) / a.slots, a.b.B), dim3(256), (size_t)lds_bytes, st,
+                       a);
+    GMC_LAUNCH_CHECK();
+    return GMC_OK;
 }
 
 // orders the wave's own LDS traffic: what its lanes wrote before is what they read after
@@ -95,6 +140,26 @@ __device__ __forceinline__ unsigned ordered_bits(float f) {
 }
 __device__ __forceinline__ float ordered_float(unsigned o) {
     return __uint_as_float(o ^ ((o >> 31) ? 0x80000000u : 0xffffffffu));
+}
+
+// node v leaves class c for class k: one lane per edge of its row updates the neighbours' rows of W
+template <int K, class G>
+__device__ __forceinline__ void apply_move(const G &g, float *W, unsigned char *st, int v, int c, int k, int lane) {
+    const int e1 = g.rp[v + 1];
+    for (int e = (int)g.rp[v] + lane; e < e1; e += GMC_WAVE) {
+        const int u = g.col[e];
+        if (u == v) continue;
+        const float wt = g.vals ? g.vals[e] : 1.0f;
+        W[u * K + c] -= wt;
+        W[u * K + k] += wt;
+    }
+    if (lane == 0) st[v] = (unsigned char)k;
+}
+
+// until[v] of a node moved at iteration `it` (it < 2^31: saturated is "never again")
+__device__ __forceinline__ unsigned ban_until(int it, unsigned tenure_base, unsigned tenure_draw) {
+    const u64 u = (u64)(unsigned)it + 1ULL + (u64)tenure_base + (u64)tenure_draw;
+    return u > 0xffffffffULL ? 0xffffffffu : (unsigned)u;
 }
 
 }  // namespace gmc

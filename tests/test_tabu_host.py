@@ -254,6 +254,24 @@ def test_every_instantiation_is_in_the_code_object(built):
         assert sum(f"tabu_kernel<{K}>" in s for s in names) == 1, K
 
 
+def test_no_instantiation_uses_scratch(built):
+    """The twin of test_balanced_host's: the code object's own notes say that tabu_kernel<2..8> and tabu_pick_kernel
+    have no private segment and spill no vector register to memory."""
+    import subprocess
+    seen = 0
+    for co in util.gfx950_code_objects(built.hip.LIB_PATH):
+        notes = subprocess.run([f"{util.ROCM_LLVM}/llvm-readelf", "--notes", "-"], input=co, capture_output=True,
+                               check=True).stdout.decode()
+        for entry in notes.split("\n  - ")[1:]:
+            fields = dict(l.strip().split(":", 1) for l in entry.splitlines() if l.strip().startswith(".") and ":" in l)
+            if "tabu_kernel" not in fields.get(".name", "") and "tabu_pick_kernel" not in fields.get(".name", ""):
+                continue
+            seen += 1
+            assert int(fields[".private_segment_fixed_size"]) == 0, fields[".name"]
+            assert int(fields[".vgpr_spill_count"]) == 0, fields[".name"]
+    assert seen == 8                                                    # K = 2..8 and the pick
+
+
 def test_solve_large_takes_the_keyword_and_refuses_the_stage():
     from gcn_max_cut_amd import maxcut
     with pytest.raises(NotImplementedError, match="tabu"):
