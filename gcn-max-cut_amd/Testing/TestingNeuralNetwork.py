@@ -365,6 +365,19 @@ def _cost_tensor(batch: GraphBatch, K: int, node_cost) -> Optional[torch.Tensor]
     return node_cost.to(batch.device, torch.float32).contiguous()
 
 
+def _graph_cost(what: str, node_cost, n: int, K: int) -> Optional[torch.Tensor]:
+    """``node_cost`` of a one-graph search -> a [n, K] float32 tensor (host), or None: floats, the shape, finite."""
+    if node_cost is None:
+        return None
+    a = node_cost.detach().cpu().numpy() if isinstance(node_cost, torch.Tensor) else np.asarray(node_cost)
+    if not np.issubdtype(a.dtype, np.floating) or a.shape != (n, K):
+        raise ValueError(f"{what}: node_cost must hold floats of shape [{n}, {K}], got {a.dtype} {tuple(a.shape)}")
+    a = np.ascontiguousarray(a, np.float32)
+    if not np.all(np.isfinite(a)):
+        raise ValueError(f"{what}: node_cost holds values that are not finite (in float32)")
+    return torch.from_numpy(a)
+
+
 def _call(name: str, terminals: bool, head: tuple, tail: tuple, node_cost: Optional[torch.Tensor] = None) -> None:
     """Calls the entry point ``name`` with the arguments ``head + tail`` - or, without terminals, its ``_t`` twin, whose
     ``terminals`` argument (0) stands between the two; or, with ``node_cost`` ([R, K] float32 on the device), its ``_c``
@@ -839,25 +852,31 @@ def _chain_outputs(batch: GraphBatch, cands: int):
 
 
 def _kway_tabu_on_gpu(batch: GraphBatch, K: int, assign: torch.Tensor, iterations: int, tenure, seed: int,
-                      terminals: bool = True):
+                      terminals: bool = True, node_cost=None):
     """One-flip tabu search at K classes (gmc_kway_tabu_f32) over the candidates assign [cands, R] int8, in place:
     ``iterations`` iterations per candidate with ``tenure`` = (tenure_base, tenure_span, tenure_div).  Returns the best
-    assignment [R], its cut and candidate index per graph, then best_iter and moves [B, cands] and cut_all [B, cands]."""
+    assignment [R], its cut and candidate index per graph, then best_iter and moves [B, cands] and cut_all [B, cands].
+    ``node_cost`` [R, K]: moves and scores follow cut minus cost (gmc_kway_tabu_c_f32)."""
     _needs_terminals(batch, K, terminals)
+    node_cost = _cost_tensor(batch, K, node_cost)
     base, span, div = _tabu_arguments("the tabu search", iterations, tenure)
     cands = int(assign.shape[0])
     cut_all, best_assign, best_cut, best_idx, best_iter, moves = _chain_outputs(batch, cands)
     p = hip.ptr
-    rc = hip.load().gmc_kway_tabu_f32(batch.ref(), K, 1 if terminals else 0, cands, p(assign), int(iterations), base,
-                                      span, div, int(seed) & _M64, p(cut_all), p(best_assign), p(best_cut), p(best_idx),
-                                      p(best_iter), p(moves), hip.stream())
-    hip.check(rc, "gmc_kway_tabu_f32")
+    tail = (cands, p(assign), int(iterations), base, span, div, int(seed) & _M64, p(cut_all), p(best_assign), p(best_cut),
+            p(best_idx), p(best_iter), p(moves), hip.stream())
+    if node_cost is None:
+        rc = hip.load().gmc_kway_tabu_f32(batch.ref(), K, 1 if terminals else 0, *tail)
+        hip.check(rc, "gmc_kway_tabu_f32")
+    else:
+        rc = hip.load().gmc_kway_tabu_c_f32(batch.ref(), K, 1 if terminals else 0, p(node_cost), *tail)
+        hip.check(rc, "gmc_kway_tabu_c_f32")
     return best_assign, best_cut, best_idx, best_iter, moves, cut_all
 
 
 def kway_tabu_search(partition_assignment, graph, number_classes: int, iterations: Optional[int] = None,
                      tenure_base: int = 3, tenure_span: int = 0, tenure_div: int = 10, seed: int = 0,
-                     terminals: bool = True) -> Tuple[List[int], Any]:
+                     terminals: bool = True, node_cost=None) -> Tuple[List[int], Any]:
     """One-flip tabu search from a partition into ``number_classes`` = 2..8 classes (extension, include/gcnmaxcut.h
     ``gmc_kway_tabu_f32``), the sibling of :func:`kway_annealing`: every iteration makes the best single move, the
     moved node may not move again for ``tenure_base + rand(tenure_span + n_mov // tenure_div)`` iterations
@@ -865,14 +884,17 @@ def kway_tabu_search(partition_assignment, graph, number_classes: int, iteration
     is returned.  ``iterations=None`` means ``20 * n``.  Nodes 0..K-1 keep their classes (``terminals=False``: every
     node may move); for unit and integer weights the result is never worse than the input; reproducible from ``seed``.
     The tenure defaults are the literature's ``3 + rand(n / 10)``, provisional: a starting point nobody has tuned, see
-    DESIGN.md section 30.  Returns the assignment and its cut value."""
+    DESIGN.md section 30.  Returns the assignment and its cut value.  ``node_cost`` [n, K] (numpy or torch floats, row =
+    node): the search follows the objective ``cut - sum_v node_cost[v][class_v]`` (``gmc_kway_tabu_c_f32``) and the
+    returned value is that objective."""
     K, part = _kway_partition("kway_tabu_search", partition_assignment, graph, number_classes, terminals)
+    node_cost = _graph_cost("kway_tabu_search", node_cost, graph.number_of_nodes(), K)
     iterations = 20 * graph.number_of_nodes() if iterations is None else int(iterations)
     tenure = _tabu_arguments("kway_tabu_search", iterations, (tenure_base, tenure_span, tenure_div))
     dev = hip.require_gpu()
     batch = GraphBatch([from_networkx(graph)], None, dev)
     assign = torch.from_numpy(part.astype(np.int8)).to(dev).reshape(1, -1)
-    best_assign, best_cut = _kway_tabu_on_gpu(batch, K, assign, iterations, tenure, seed, terminals)[:2]
+    best_assign, best_cut = _kway_tabu_on_gpu(batch, K, assign, iterations, tenure, seed, terminals, node_cost)[:2]
     return best_assign.cpu().tolist(), _as_number(best_cut.item())
 
 
@@ -920,11 +942,13 @@ def class_size_bounds(what: str, class_sizes, sizes, K: int, terminals: bool) ->
 
 
 def _kway_balance_on_gpu(batch: GraphBatch, K: int, assign: torch.Tensor, lo: np.ndarray, hi: np.ndarray,
-                         iterations: int, tenure, seed: int, terminals: bool = True):
+                         iterations: int, tenure, seed: int, terminals: bool = True, node_cost=None):
     """Tabu search under class-size bounds (gmc_kway_balance_f32) over the candidates assign [cands, R] int8, in place,
     with lo, hi int32 [B, K] as :func:`class_size_bounds` returns them.  Returns the best assignment [R], its cut and
-    candidate index per graph, then best_iter, moves and repairs [B, cands] and cut_all [B, cands]."""
+    candidate index per graph, then best_iter, moves and repairs [B, cands] and cut_all [B, cands].  ``node_cost``
+    [R, K]: moves, repairs and scores follow cut minus cost (gmc_kway_balance_c_f32)."""
     _needs_terminals(batch, K, terminals)
+    node_cost = _cost_tensor(batch, K, node_cost)
     base, span, div = _tabu_arguments("the balanced search", iterations, tenure)
     if lo.shape != (batch.B, K) or hi.shape != (batch.B, K):
         raise ValueError(f"the balanced search: bounds of shape {lo.shape} and {hi.shape} for {batch.B} graphs and {K} classes")
@@ -935,16 +959,21 @@ def _kway_balance_on_gpu(batch: GraphBatch, K: int, assign: torch.Tensor, lo: np
     cut_all, best_assign, best_cut, best_idx, best_iter, moves = _chain_outputs(batch, cands)
     repairs = torch.empty_like(moves)
     p = hip.ptr
-    rc = hip.load().gmc_kway_balance_f32(batch.ref(), K, 1 if terminals else 0, cands, p(assign), p(size_lo), p(size_hi),
-                                         int(iterations), base, span, div, int(seed) & _M64, p(cut_all), p(best_assign),
-                                         p(best_cut), p(best_idx), p(best_iter), p(moves), p(repairs), None, hip.stream())
-    hip.check(rc, "gmc_kway_balance_f32")
+    tail = (cands, p(assign), p(size_lo), p(size_hi), int(iterations), base, span, div, int(seed) & _M64, p(cut_all),
+            p(best_assign), p(best_cut), p(best_idx), p(best_iter), p(moves), p(repairs), None, hip.stream())
+    if node_cost is None:
+        rc = hip.load().gmc_kway_balance_f32(batch.ref(), K, 1 if terminals else 0, *tail)
+        hip.check(rc, "gmc_kway_balance_f32")
+    else:
+        rc = hip.load().gmc_kway_balance_c_f32(batch.ref(), K, 1 if terminals else 0, p(node_cost), *tail)
+        hip.check(rc, "gmc_kway_balance_c_f32")
     return best_assign, best_cut, best_idx, best_iter, moves, repairs, cut_all
 
 
 def kway_balanced_search(partition_assignment, graph, number_classes: int, class_sizes="balanced",
                          iterations: Optional[int] = None, tenure_base: int = 3, tenure_span: int = 0,
-                         tenure_div: int = 10, seed: int = 0, terminals: bool = True) -> Tuple[List[int], Any]:
+                         tenure_div: int = 10, seed: int = 0, terminals: bool = True,
+                         node_cost=None) -> Tuple[List[int], Any]:
     """:func:`kway_tabu_search` with the size of every class kept within bounds (extension, include/gcnmaxcut.h
     ``gmc_kway_balance_f32``): max-bisection and balanced max-K-cut, and on negated weights balanced minimum cut.
     ``class_sizes`` is ``"balanced"`` (every class holds ``n // K`` to ``ceil(n / K)`` nodes, terminals included) or a
@@ -954,16 +983,19 @@ def kway_balanced_search(partition_assignment, graph, number_classes: int, class
     state passed through is returned and is always within the bounds.  ``iterations=None`` means ``20 * n``; the tenure
     arguments are :func:`kway_tabu_search`'s.  Bounds that admit no partition raise ``ValueError``.  With
     ``class_sizes=([0] * K, [n] * K)`` it is :func:`kway_tabu_search`, byte for byte.  Returns the assignment and
-    its cut value."""
+    its cut value.  ``node_cost`` [n, K]: as :func:`kway_tabu_search` takes it (``gmc_kway_balance_c_f32``); the repair
+    then gives up the least objective, and the returned value is the objective."""
     K, part = _kway_partition("kway_balanced_search", partition_assignment, graph, number_classes, terminals)
     n = graph.number_of_nodes()
+    node_cost = _graph_cost("kway_balanced_search", node_cost, n, K)
     iterations = 20 * n if iterations is None else int(iterations)
     tenure = _tabu_arguments("kway_balanced_search", iterations, (tenure_base, tenure_span, tenure_div))
     lo, hi = class_size_bounds("kway_balanced_search", class_sizes, [n], K, terminals)
     dev = hip.require_gpu()
     batch = GraphBatch([from_networkx(graph)], None, dev)
     assign = torch.from_numpy(part.astype(np.int8)).to(dev).reshape(1, -1)
-    best_assign, best_cut = _kway_balance_on_gpu(batch, K, assign, lo, hi, iterations, tenure, seed, terminals)[:2]
+    best_assign, best_cut = _kway_balance_on_gpu(batch, K, assign, lo, hi, iterations, tenure, seed, terminals,
+                                                 node_cost)[:2]
     return best_assign.cpu().tolist(), _as_number(best_cut.item())
 
 

@@ -306,6 +306,19 @@ class HostContraction:
         """The partition of the original nodes a partition of the contracted graph stands for."""
         return np.asarray(partition)[self.node_map].astype(np.int32)
 
+    def contract_cost(self, node_cost):
+        """Per-node class costs [n, K] of the original graph -> (the costs of the contracted graph [n_out, K] float32,
+        ``fixed_cost`` float32): a free node's row goes to its contracted row, the K super-nodes get zero rows, and
+        ``fixed_cost`` is the sum of ``node_cost[v][class_v]`` over the pinned nodes (a float64 running sum in node
+        order, rounded once).  The host twin of ``Contraction.contract_cost``."""
+        cost = np.asarray(node_cost, np.float32)
+        K = cost.shape[1]
+        free = ~self.pinned
+        out = np.zeros((self.handle.n, K), np.float32)
+        out[self.node_map[free]] = cost[free]
+        picked = cost[np.flatnonzero(self.pinned), self.node_map[self.pinned]].astype(np.float64)
+        return out, np.float32(np.cumsum(picked)[-1] if picked.size else 0.0)
+
 
 def contract(handle: GraphHandle, nodes, classes, number_classes: int) -> HostContraction:
     """Contract the pinned nodes of one graph on the host, in vectorised numpy: the host twin of
@@ -813,3 +826,24 @@ class Contraction:
     def lift(self, partition: torch.Tensor) -> torch.Tensor:
         """The [R] int32 partition of the original rows a partition of ``batch``'s rows stands for."""
         return partition.to(torch.int32)[self.node_map.to(torch.int64)]
+
+    def contract_cost(self, node_cost: torch.Tensor, goff: torch.Tensor):
+        """Per-node class costs [R, K] (float32, on the device) of the original batch, whose graph offsets are ``goff``
+        [B + 1] -> (the costs of ``batch`` [R_out, K], ``fixed_cost`` [B] float32): a free row's costs go to its
+        contracted row, the K super-nodes of every graph get zero rows, and ``fixed_cost`` is the sum of
+        ``node_cost[v][class_v]`` over each graph's pinned rows - a float64 running sum over the rows differenced at the
+        graphs' boundaries, without atomics: the same bits every time."""
+        K = node_cost.shape[1]
+        node_map = self.node_map.to(torch.int64)
+        out = torch.zeros((self.batch.R, K), dtype=torch.float32, device=node_cost.device)
+        free = ~self.pinned
+        out[node_map[free]] = node_cost[free]   # (a free row has a contracted row of its own: no two writes meet)
+        B = goff.numel() - 1
+        goff = goff.to(torch.int64)
+        sizes = goff[1:] - goff[:-1]
+        first = torch.repeat_interleave(self.batch.goff.to(torch.int64)[:-1], sizes, output_size=node_map.numel())
+        cls = (node_map - first).clamp_(0, K - 1)   # a pinned row's class is its super-node's local id
+        picked = node_cost.gather(1, cls.reshape(-1, 1)).reshape(-1).to(torch.float64)
+        picked = torch.where(self.pinned, picked, torch.zeros_like(picked))
+        run = torch.cat([picked.new_zeros(1), torch.cumsum(picked, 0)])
+        return out, (run[goff[1:]] - run[goff[:-1]]).to(torch.float32) if B else picked.new_zeros(0).to(torch.float32)

@@ -224,6 +224,10 @@ def _api() -> dict:
         "gmc_inst_forward_c": (i, [B, M, i32, vp, f32, vp, sz, vp, vp, vp, vp]),
         "gmc_inst_train_fwd_bwd_c": (i, [B, M, i32, vp, f32, vp, sz, vp, vp, vp, vp, vp]),
         "gmc_row_weight_sums_f32": (i, [i32, vp, vp, vp, vp, vp]),
+        # the two chain searches with `node_cost` after `terminals`
+        "gmc_kway_tabu_c_f32": (i, [B, i32, i32, vp, i32, vp, i32, i32, i32, i32, C.c_uint64, vp, vp, vp, vp, vp, vp, vp]),
+        "gmc_kway_balance_c_f32": (i, [B, i32, i32, vp, i32, vp, vp, vp, i32, i32, i32, i32, C.c_uint64, vp, vp, vp, vp, vp,
+                                       vp, vp, vp, vp]),
     }
 
 

@@ -30,12 +30,11 @@ _TOO_LARGE = ("a graph of {n} nodes is beyond the one-workgroup head of the per-
 _NO_TABU = "the tabu stage keeps a graph's state in one workgroup: solve_large does not have it (tabu_iterations must be 0)"
 _NO_BALANCE = ("the balanced stage keeps a graph's state in one workgroup, as the tabu stage does: solve_large does not "
                "have it (class_sizes must be None)")
-_NO_COST_TABU = ("node_cost with tabu_iterations > 0: the tabu stage scores and moves by the plain cut - per-node costs are "
-                 "not implemented in it")
-_NO_COST_SIZES = ("node_cost with class_sizes: the balanced stage scores and moves by the plain cut - per-node costs are "
-                  "not implemented in it")
-_NO_COST_FIXED = ("node_cost with fixed: a contracted super-node stands for many nodes and their costs are not summed "
-                  "onto it - express the pins as large costs, or pass one of the two")
+_BATCH_DOOR = "this door does not take the two together; solve_batch(GraphBatch.from_edge_index(...), ...), which it wraps, does"
+_NO_COST_TABU = "node_cost with tabu_iterations > 0: " + _BATCH_DOOR + " - its tabu stage follows the objective"
+_NO_COST_SIZES = "node_cost with class_sizes: " + _BATCH_DOOR + " - its balanced stage follows the objective"
+_NO_COST_FIXED = ("node_cost with fixed: " + _BATCH_DOOR + " - it carries the free nodes' costs to the contracted batch and "
+                  "reports the pinned nodes' as fixed_cost")
 _NO_COST_LARGE = ("node_cost on the large route: the multi-workgroup head and decoders of solve_large take no per-node "
                   "costs - maxcut.solve has them for graphs within its bound")
 _BEYOND_LARGE = "a graph of {n} nodes is beyond the {bound} nodes of the per-graph models' large sequence (solve_large)"
@@ -56,6 +55,8 @@ class MaxCutResult:
     node_cost_sum: Optional[torch.Tensor] = None   # [B] float32, with node_cost only: sum_v node_cost[v][partition_v]; every
     #                                                ``*_cut`` field then holds the objective cut - cost of its partition,
     #                                                and the plain cut of ``partition`` is ``cut + node_cost_sum``
+    fixed_cost: Optional[torch.Tensor] = None      # [B] float32, with fixed and node_cost only: the cost of the pinned nodes,
+    #                                                sum_v node_cost[v][class_v] (a constant of every partition)
 
 
 def balanced_sizes(ptr, number_classes: int, imbalance: float = 0.0):
@@ -130,8 +131,11 @@ def solve(edge_index, ptr=None, num_nodes: Optional[int] = None, edge_weight=Non
     Training (both losses), the rounding, the sampler's scores and the annealing all follow it (the ``_c`` entry points
     of include/gcnmaxcut.h), every ``*_cut`` field of the result then holds the objective of its partition (what the
     stages compared), and ``node_cost_sum`` holds the cost of ``partition``, so its plain cut is ``cut +
-    node_cost_sum``.  A wrong shape or a value that is not finite raises ``ValueError`` before anything is built;
-    ``node_cost`` together with ``tabu_iterations > 0``, ``class_sizes`` or ``fixed`` raises ``NotImplementedError``.
+    node_cost_sum``.  A wrong shape or a value that is not finite raises ``ValueError`` before anything is built.
+    Through THIS door ``node_cost`` together with ``tabu_iterations > 0``, ``class_sizes`` or ``fixed`` raises
+    ``NotImplementedError``; :func:`solve_batch` on ``GraphBatch.from_edge_index(...)``, which this function wraps,
+    takes each of the three: the tabu and the balanced stage then follow the objective
+    (``gmc_kway_tabu_c_f32``, ``gmc_kway_balance_c_f32``), and pins carry the free nodes' costs to the contracted batch.
     ``None`` changes no byte, and an all-zero array returns the bytes of ``None`` in ``partition`` and ``cut``.
 
     A graph beyond the one-workgroup head of the per-graph models raises ``ValueError``: for such a graph train a model
@@ -172,15 +176,21 @@ def solve_batch(batch: GraphBatch, *, number_classes: int = 2, terminals: bool =
                 balance_iterations: Optional[int] = None, node_cost=None) -> MaxCutResult:
     """Steps 2 to 6 of :func:`solve` on a ready batch - one built on the device or one built from handles: the batches
     hold the same bytes, so the results do too.  ``fixed``: as :func:`solve`, with row ids of ``batch``;
-    ``class_sizes``, ``balance_iterations`` and ``node_cost`` (rows = batch rows): as :func:`solve`."""
+    ``class_sizes``, ``balance_iterations`` and ``node_cost`` (rows = batch rows): as :func:`solve`.
+
+    ``node_cost`` goes together with each of ``tabu_iterations``, ``class_sizes`` and ``fixed`` here.  The tabu stage
+    and the balanced stage then search the objective ``cut - cost`` (``gmc_kway_tabu_c_f32``,
+    ``gmc_kway_balance_c_f32``): the better of the annealed and the tabu result is chosen by objective, and
+    ``annealed_cut`` and ``unconstrained_cut`` are objectives like every other ``*_cut`` field; ``node_cost_sum`` is the
+    cost of the returned ``partition``.  With ``fixed``, a free node's cost row goes to its contracted row, the K
+    super-nodes get zero rows, ``fixed_cost`` [B] holds the cost of each graph's pinned nodes, and every reported value
+    is a recount of the lifted partition on the original batch with the original cost."""
     _check_sizes(class_sizes, balance_iterations, fixed)
     if node_cost is not None:
-        node_cost = _check_node_cost(node_cost, batch.R, int(number_classes), tabu_iterations, class_sizes, fixed)
-        return _solve_batch(_small_route(), batch, number_classes, terminals, hidden_dim, epochs, learning_rate, loss,
-                            samples, anneal_sweeps, max_descent_sweeps, seed, node_cost=node_cost)
+        node_cost = _check_node_cost(node_cost, batch.R, int(number_classes))
     return _solve_fixed(_small_route(), batch, fixed, number_classes, terminals, hidden_dim, epochs, learning_rate, loss,
                         samples, anneal_sweeps, max_descent_sweeps, seed, tabu_iterations, class_sizes,
-                        balance_iterations)
+                        balance_iterations, node_cost=node_cost)
 
 
 def solve_large(edge_index, ptr=None, num_nodes: Optional[int] = None, edge_weight=None, *, number_classes: int = 2,
@@ -302,28 +312,45 @@ def _mean_abs_edge_weight(batch: GraphBatch) -> float:
     return mean if mean > 0 else 1.0
 
 
-def _solve_fixed(route: "_Route", batch: GraphBatch, fixed, number_classes: int, terminals: bool, *args) -> MaxCutResult:
+def _solve_fixed(route: "_Route", batch: GraphBatch, fixed, number_classes: int, terminals: bool, *args,
+                 node_cost: Optional[torch.Tensor] = None) -> MaxCutResult:
     """:func:`_solve_batch`, or with ``fixed``: contract, solve the contracted batch with its super-nodes as terminals, lift,
     and recount every reported cut on the original batch (the route's annealing call with zero sweeps and no terminals
     moves nothing and scores: the bits every other decoder reports for those bytes).  The route is chosen by the
     contracted sizes, the recount by the original ones: an original graph beyond ``hip.MAX_GRAPH_NODES`` nodes is
-    scored by the large sequence's call, the only decoders that take it."""
+    scored by the large sequence's call, the only decoders that take it.  ``node_cost`` (checked, [R, K] float32): the
+    free rows' costs go to the contracted batch (``Contraction.contract_cost``), the recount is the annealing's scoring
+    call with the ORIGINAL cost on the original batch, and ``fixed_cost`` holds the pinned nodes' share."""
     if fixed is None:
-        return _solve_batch(route, batch, number_classes, terminals, *args)
+        return _solve_batch(route, batch, number_classes, terminals, *args, node_cost=node_cost)
     K = int(number_classes)
     _check_fixed(fixed, bool(terminals), K)
+    large = bool(batch.B) and batch.n_max > hip.MAX_GRAPH_NODES
+    if node_cost is not None and (large or route.tabu is None):
+        raise NotImplementedError(_NO_COST_LARGE)
     ct = batch.contract(fixed[0], fixed[1], K)
     parts = {}
-    res = _solve_batch(route, ct.batch, K, True, *args, parts=parts)
+    cost, fixed_cost, dec = None, None, ()
+    if node_cost is not None:
+        node_cost = node_cost.to(batch.device)
+        cost, fixed_cost = ct.contract_cost(node_cost, batch.goff)
+        dec = (node_cost,)
+    res = _solve_batch(route, ct.batch, K, True, *args, parts=parts, node_cost=cost)
     no_sweeps = np.zeros(0, np.float32)
-    score = _large_route().anneal if batch.B and batch.n_max > hip.MAX_GRAPH_NODES else route.anneal
+    score = _large_route().anneal if large else route.anneal
 
     def recount(partition):
-        return score(batch, K, partition.to(torch.int8).reshape(1, -1).contiguous(), no_sweeps, 0, 0, False)[1]
+        return score(batch, K, partition.to(torch.int8).reshape(1, -1).contiguous(), no_sweeps, 0, 0, False, *dec)[1]
 
     partition = ct.lift(res.partition)
     if batch.B == 0:
-        return MaxCutResult(partition, res.cut, res.trained_cut, res.rounded_cut, batch.goff, fixed_cut=ct.fixed_cut)
+        return MaxCutResult(partition, res.cut, res.trained_cut, res.rounded_cut, batch.goff, fixed_cut=ct.fixed_cut,
+                            node_cost_sum=res.node_cost_sum, fixed_cost=fixed_cost)
+    if node_cost is not None:
+        return MaxCutResult(partition, recount(partition), recount(ct.lift(parts["trained"])),
+                            recount(ct.lift(parts["rounded"])), batch.goff,
+                            recount(ct.lift(parts["annealed"])) if "annealed" in parts else None, ct.fixed_cut,
+                            node_cost_sum=_node_cost_sum(batch, node_cost, partition), fixed_cost=fixed_cost)
     # the cuts of the contracted run differ from the original graph's by fixed_cut; for weights that are not integers the
     # sum of the two need not carry the bits of a recount, so every cut is recounted from its lifted partition
     return MaxCutResult(partition, recount(partition), recount(ct.lift(parts["trained"])),
@@ -338,7 +365,7 @@ class _Route:
     and ``anneal(batch, K, cands, inv_temp, seed, max_descent_sweeps, terminals)`` (the small route's three take a
     trailing ``node_cost`` as well); ``tabu(batch, K, cands, iterations,
     seed, terminals)`` and ``balance(batch, K, cands, lo, hi, iterations, seed, terminals)`` where the route has the
-    stage."""
+    stage (the small route's two take a trailing ``node_cost`` too)."""
     engine: type
     refuse: Callable
     round: Callable
@@ -361,11 +388,10 @@ def _small_route() -> _Route:
                                                                              c)[3],
                   lambda batch, K, cands, inv_temp, seed, sweeps, t, c=None: T._kway_anneal_on_gpu(batch, K, cands, inv_temp,
                                                                                                    seed, sweeps, t, c),
-                  lambda batch, K, cands, iterations, seed, t: T._kway_tabu_on_gpu(batch, K, cands, iterations,
-                                                                                   T.TABU_TENURE, seed, t),
-                  lambda batch, K, cands, lo, hi, iterations, seed, t: T._kway_balance_on_gpu(batch, K, cands, lo, hi,
-                                                                                              iterations, T.TABU_TENURE,
-                                                                                              seed, t))
+                  lambda batch, K, cands, iterations, seed, t, c=None: T._kway_tabu_on_gpu(batch, K, cands, iterations,
+                                                                                           T.TABU_TENURE, seed, t, c),
+                  lambda batch, K, cands, lo, hi, iterations, seed, t, c=None: T._kway_balance_on_gpu(
+                      batch, K, cands, lo, hi, iterations, T.TABU_TENURE, seed, t, c))
 
 
 def _large_route() -> _Route:
@@ -390,8 +416,8 @@ def _solve_batch(route: _Route, batch: GraphBatch, number_classes: int, terminal
                  abs_scale: bool = False) -> MaxCutResult:
     """``parts``: a dict that receives the partitions behind ``trained_cut``, ``rounded_cut`` (and ``annealed_cut``).
     ``node_cost``: a float32 tensor [R, K] that :func:`_check_node_cost` has returned - the public doors check once and
-    pass the checked tensor down (small route, no tabu, no bounds, no pins); ``abs_scale``: the annealing's
-    temperature in units of the mean absolute edge weight (the doors with signed weights)."""
+    pass the checked tensor down (small route); the tabu and the balanced stage then take it too; ``abs_scale``: the
+    annealing's temperature in units of the mean absolute edge weight (the doors with signed weights)."""
     from .Testing import TestingNeuralNetwork as T
     K, terminals = int(number_classes), bool(terminals)
     if not 2 <= K <= hip.KWAY_MAX_CLASSES:
@@ -445,9 +471,12 @@ def _solve_batch(route: _Route, batch: GraphBatch, number_classes: int, terminal
     scale = T._mean_edge_weight(batch) if bounds is None and not abs_scale else _mean_abs_edge_weight(batch)
     inv_temp = T.anneal_schedule(int(anneal_sweeps), scale=scale)
     partition, cut, _ = route.anneal(batch, K, cands, inv_temp, seed, int(max_descent_sweeps), terminals, *dec)
-    if node_cost is not None:
+    if node_cost is not None and not tabu_iterations and bounds is None:
+        if parts is not None:
+            parts.update(trained=best_S, rounded=rounded)
         return MaxCutResult(partition, cut, trained_cut, rounded_cut, batch.goff,
                             node_cost_sum=_node_cost_sum(batch, node_cost, partition))
+    cost_sum = (lambda part: None) if node_cost is None else (lambda part: _node_cost_sum(batch, node_cost, part))
     if parts is not None:
         parts.update(trained=best_S, rounded=rounded)
         if tabu_iterations:
@@ -455,17 +484,20 @@ def _solve_batch(route: _Route, batch: GraphBatch, number_classes: int, terminal
     annealed_cut = None
     if tabu_iterations:
         # the annealing left its candidates in `cands`; the better of the two results per graph, chosen on the device
-        tabu_partition, tabu_cut = route.tabu(batch, K, cands.clone(), int(tabu_iterations), seed, terminals)[:2]
+        tabu_partition, tabu_cut = route.tabu(batch, K, cands.clone(), int(tabu_iterations), seed, terminals, *dec)[:2]
         better = tabu_cut > cut
         sizes = (batch.goff[1:] - batch.goff[:-1]).to(torch.int64)
         rows = torch.repeat_interleave(better, sizes, output_size=batch.R)
         partition, cut, annealed_cut = torch.where(rows, tabu_partition, partition), torch.where(better, tabu_cut, cut), cut
     if bounds is None:
-        return MaxCutResult(partition, cut, trained_cut, rounded_cut, batch.goff, annealed_cut)
+        return MaxCutResult(partition, cut, trained_cut, rounded_cut, batch.goff, annealed_cut,
+                            node_cost_sum=cost_sum(partition))
     # the balanced stage starts from the annealed candidates too (a copy: repaired into the bounds, then searched)
     iterations = 20 * int(batch.n_max) if balance_iterations is None else int(balance_iterations)
-    within, within_cut = route.balance(batch, K, cands.clone(), bounds[0], bounds[1], iterations, seed, terminals)[:2]
-    return MaxCutResult(within, within_cut, trained_cut, rounded_cut, batch.goff, annealed_cut, unconstrained_cut=cut)
+    within, within_cut = route.balance(batch, K, cands.clone(), bounds[0], bounds[1], iterations, seed, terminals,
+                                       *dec)[:2]
+    return MaxCutResult(within, within_cut, trained_cut, rounded_cut, batch.goff, annealed_cut, unconstrained_cut=cut,
+                        node_cost_sum=cost_sum(within))
 
 
 def _node_cost_sum(batch: GraphBatch, node_cost: torch.Tensor, partition: torch.Tensor) -> torch.Tensor:
@@ -532,31 +564,66 @@ def _door(edge_index, ptr, num_nodes):
 
 
 def _solve_door(batch: GraphBatch, node_cost: np.ndarray, hidden_dim, epochs, learning_rate, loss, samples, anneal_sweeps,
-                max_descent_sweeps, seed) -> MaxCutResult:
+                max_descent_sweeps, seed, tabu_iterations=0, class_sizes=None, balance_iterations=None) -> MaxCutResult:
     loss = hip.loss_name(loss)
     if batch.B and instance_too_large(batch.n_max, 2, loss):
         raise ValueError(_TOO_LARGE.format(n=batch.n_max, K=2))
     return _solve_batch(_small_route(), batch, 2, False, hidden_dim, epochs, learning_rate, loss, samples, anneal_sweeps,
-                        max_descent_sweeps, seed, node_cost=_check_node_cost(node_cost, batch.R, 2), abs_scale=True)
+                        max_descent_sweeps, seed, tabu_iterations, class_sizes, balance_iterations,
+                        node_cost=_check_node_cost(node_cost, batch.R, 2), abs_scale=True)
+
+
+def _door_stages(what: str, goff: np.ndarray, tabu_iterations, class_sizes, balance_iterations):
+    """The argument errors of a door's stage keywords, raised on the host before anything is built; returns
+    ``class_sizes`` as (lo, hi) int32 [B, 2], or None."""
+    if not 0 <= int(tabu_iterations) < 1 << 31:
+        raise ValueError(f"tabu_iterations must be in 0..2^31-1, got {tabu_iterations}")
+    _check_sizes(class_sizes, balance_iterations, None)
+    if class_sizes is None:
+        return None
+    from .Testing import TestingNeuralNetwork as T
+    return T.class_size_bounds(what, class_sizes, np.diff(goff), 2, False)
+
+
+def _cardinality_sizes(cardinality, goff: np.ndarray):
+    """``cardinality`` of :func:`solve_qubo` - an integer k or a pair (lo, hi) on the number of ``x_i = 1`` of every
+    graph - as ``class_sizes``: class 1 holds lo..hi nodes, class 0 the rest."""
+    pair = (cardinality, cardinality) if isinstance(cardinality, (int, np.integer)) else cardinality
+    if (not isinstance(pair, (tuple, list)) or len(pair) != 2
+            or not all(isinstance(x, (int, np.integer)) for x in pair)):
+        raise ValueError(f"cardinality must be an integer or a pair (lo, hi) of integers, got {cardinality!r}")
+    lo, hi = int(pair[0]), int(pair[1])
+    n = np.diff(goff).astype(np.int64)
+    ones = np.ones_like(n)
+    return (np.stack([np.maximum(n - hi, 0), lo * ones], axis=1), np.stack([np.maximum(n - lo, 0), hi * ones], axis=1))
 
 
 def solve_ising(edge_index, ptr=None, num_nodes: Optional[int] = None, coupling=None, field=None, *, pairs: str = "both",
                 hidden_dim: int, epochs: int, learning_rate: float, loss: str = "expected_cut", samples: int = 32,
-                anneal_sweeps: int = 100, max_descent_sweeps: int = 100, seed: int = 0) -> IsingResult:
+                anneal_sweeps: int = 100, max_descent_sweeps: int = 100, seed: int = 0, tabu_iterations: int = 0,
+                class_sizes=None, balance_iterations: Optional[int] = None) -> IsingResult:
     """Minimises ``H(s) = sum_{i<j} J_ij s_i s_j + sum_i h_i s_i`` over ``s`` in {+1, -1}^n for every graph of a batch:
     ``edge_index`` / ``ptr`` / ``num_nodes`` / ``pairs`` as :func:`solve` takes them, ``coupling`` [E] the J of every
     entry (``None``: 1; with ``pairs="both"`` both directions carry the same J), ``field`` [R] the h of every node
     (``None``: 0); the training and decoding keywords are :func:`solve`'s.
 
     The mapping onto :func:`solve` is exact: edge weight ``w = 2 J``, two classes without terminals, class 0 is ``s =
-    +1``, ``node_cost[i] = (h_i, -h_i)``; then ``H(s) = sum_{i<j} J_ij - obj``, ``obj`` the objective ``cut - cost``
+    +1`` (class 1 is ``s = -1``), ``node_cost[i] = (h_i, -h_i)``; then ``H(s) = sum_{i<j} J_ij - obj``, ``obj`` the objective ``cut - cost``
     the solver maximises.  The weights are signed, so the annealing's temperature is in units of the mean absolute edge
     weight.  Returns ``spins`` [R] int8, ``energy`` [B] float64 (``sum J`` taken in float64 on the host, ``obj`` the
     solver's float32), ``ptr`` and the :class:`MaxCutResult` as ``.result``.
 
+    ``tabu_iterations``, ``class_sizes`` and ``balance_iterations`` have :func:`solve`'s meaning, on the objective (the
+    tabu and the balanced stage with costs, ``gmc_kway_tabu_c_f32`` / ``gmc_kway_balance_c_f32``).  Class 0 is ``s = +1``
+    and class 1 is ``s = -1``, so ``class_sizes=(lo, hi)`` bounds the number of up spins by ``lo[0]..hi[0]`` and of down
+    spins by ``lo[1]..hi[1]`` - a bounded magnetisation; ``spins`` and ``energy`` are then those of the within-bounds
+    partition.  Bounds that admit no partition raise ``ValueError`` before anything is built.  The defaults launch
+    nothing more and change no byte.
+
     A spin without any coupling is refused by the batch builder (``ValueError``: "nodes without neighbours"); its optimum
     is its own sign, ``s_i = -sign(h_i)`` - leave it out and add ``-|h_i|`` to the energy."""
     ei, goff = _door(edge_index, ptr, num_nodes)
+    class_sizes = _door_stages("solve_ising", goff, tabu_iterations, class_sizes, balance_iterations)
     E, R = ei.shape[1], int(goff[-1])
     J = _edge_values("coupling", coupling, E)
     h = _node_values("field", field, R)
@@ -570,7 +637,7 @@ def solve_ising(edge_index, ptr=None, num_nodes: Optional[int] = None, coupling=
     node_cost = np.stack([h, -h], axis=1).astype(np.float32)
     batch = GraphBatch.from_edge_index(edge_index, ptr, num_nodes, (2.0 * J).astype(np.float32), pairs=pairs)
     res = _solve_door(batch, node_cost, hidden_dim, epochs, learning_rate, loss, samples, anneal_sweeps,
-                      max_descent_sweeps, seed)
+                      max_descent_sweeps, seed, tabu_iterations, class_sizes, balance_iterations)
     spins = (1 - 2 * res.partition).to(torch.int8)
     energy = torch.from_numpy(sum_j) - res.cut.detach().cpu().to(torch.float64)
     return IsingResult(spins, energy, res.ptr, res)
@@ -578,7 +645,8 @@ def solve_ising(edge_index, ptr=None, num_nodes: Optional[int] = None, coupling=
 
 def solve_qubo(edge_index, ptr=None, num_nodes: Optional[int] = None, quadratic=None, linear=None, *, pairs: str = "both",
                hidden_dim: int, epochs: int, learning_rate: float, loss: str = "expected_cut", samples: int = 32,
-               anneal_sweeps: int = 100, max_descent_sweeps: int = 100, seed: int = 0) -> QuboResult:
+               anneal_sweeps: int = 100, max_descent_sweeps: int = 100, seed: int = 0, tabu_iterations: int = 0,
+               class_sizes=None, balance_iterations: Optional[int] = None, cardinality=None) -> QuboResult:
     """Minimises ``E(x) = sum_i a_i x_i + sum_{i<j} q_ij x_i x_j`` over ``x`` in {0, 1}^n for every graph of a batch:
     ``edge_index`` / ``ptr`` / ``num_nodes`` / ``pairs`` as :func:`solve` takes them, ``quadratic`` [E] the q of every
     entry (``None``: 1; with ``pairs="both"`` both directions carry the same q), ``linear`` [R] the a of every variable
@@ -591,9 +659,22 @@ def solve_qubo(edge_index, ptr=None, num_nodes: Optional[int] = None, quadratic=
     temperature is in units of the mean absolute edge weight.  Returns ``x`` [R] int8, ``energy`` [B] float32, ``ptr``
     and the :class:`MaxCutResult` as ``.result``.
 
+    ``tabu_iterations``, ``class_sizes`` and ``balance_iterations`` have :func:`solve`'s meaning, on the objective (the
+    tabu and the balanced stage with costs, ``gmc_kway_tabu_c_f32`` / ``gmc_kway_balance_c_f32``).  Class 1 is ``x = 1``
+    and class 0 is ``x = 0``.  ``cardinality``: an integer ``k`` (exactly ``k`` variables set per graph) or a pair
+    ``(lo, hi)`` (between ``lo`` and ``hi``) - the cardinality-constrained QUBO; it is mapped onto ``class_sizes``
+    (class 1 holds ``lo..hi`` nodes), and passing both raises ``ValueError``.  With bounds ``x`` and ``energy`` are those
+    of the within-bounds partition.  Bounds that admit no partition raise ``ValueError`` before anything is built.  The
+    defaults launch nothing more and change no byte.
+
     A variable without any quadratic term is refused by the batch builder (``ValueError``: "nodes without
     neighbours"); its optimum is its own sign, ``x_i = 1`` iff ``a_i < 0`` - leave it out and add ``min(a_i, 0)``."""
     ei, goff = _door(edge_index, ptr, num_nodes)
+    if cardinality is not None:
+        if class_sizes is not None:
+            raise ValueError("cardinality is mapped onto class_sizes: pass one of the two")
+        class_sizes = _cardinality_sizes(cardinality, goff)
+    class_sizes = _door_stages("solve_qubo", goff, tabu_iterations, class_sizes, balance_iterations)
     E, R = ei.shape[1], int(goff[-1])
     q = _edge_values("quadratic", quadratic, E)
     a = _node_values("linear", linear, R)
@@ -607,5 +688,5 @@ def solve_qubo(edge_index, ptr=None, num_nodes: Optional[int] = None, quadratic=
     node_cost = np.zeros((R, 2), np.float32)
     node_cost[:, 1] = a.astype(np.float32) + half.cpu().numpy()   # (one fp32 addition per variable)
     res = _solve_door(batch, node_cost, hidden_dim, epochs, learning_rate, loss, samples, anneal_sweeps,
-                      max_descent_sweeps, seed)
+                      max_descent_sweeps, seed, tabu_iterations, class_sizes, balance_iterations)
     return QuboResult(res.partition.to(torch.int8), -res.cut, res.ptr, res)

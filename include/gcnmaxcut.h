@@ -1686,6 +1686,63 @@ int gmc_inst_train_fwd_bwd_c(const gmc_batch *batch, const gmc_model *model, int
 int gmc_row_weight_sums_f32(int32_t R, const int32_t *rowptr /*[R+1]*/, const int32_t *gcol /*[nnz], global row ids*/,
                             const float *vals /*[nnz] or NULL*/, float *out /*[R]*/, gmc_stream_t stream);
 
+/* ---- per-node class costs in the two chain searches (extension) -----------------------------------------------------------
+ * gmc_kway_tabu_f32 and gmc_kway_balance_f32 with `node_cost` ([R][K] fp32 by batch row, as above, or NULL) directly
+ * after `terminals`: the chains then search obj(S) = cut(S) - sum_v node_cost[v][S_v] - a QUBO or an Ising model with
+ * fields through one-flip tabu search, and with size bounds a cardinality-constrained QUBO.  Each rule is its twin's rule
+ * with exactly these changes:
+ *
+ * Table.  W[v][k] of local node v of the graph on rows r0.. starts from node_cost[r0 + v][k] instead of +0.0f and then
+ *   adds the row's weights in CSR order as before (rule 1 above: class_sums_k, the same code); a sum that comes out as
+ *   -0.0f is stored as +0.0f (see "Negative zero").  gain = W[v][c] - W[v][k] is then the change of obj for the move
+ *   v: c -> k, since the update of step 4 touches the neighbours' rows only and a node's own cost row never changes.
+ *   Every other word of the twin's rule stands: the scan, the admissibility test rel + gain > best, h, r, the tenure
+ *   draw, the tie order, the +- w update of the neighbours' rows, the deferred snapshot, best_iter and moves; for
+ *   gmc_kway_balance_c_f32 also the sizes, the bounds test, the repair (its gains come from this table too), free and
+ *   paired moves, the counter-move and repairs / feasible.  No step multiplies, so nothing can be contracted.  A
+ *   terminal's cost row starts its W row like any other; it never moves, so only its score counts.
+ * Scores.  Every snapshot is scored as rule 2 above states: block_cut(...) - block_cost(...), one fp32 subtraction, the
+ *   same code (block_score<K>).  cut_all therefore carries, bit for bit, what gmc_kway_refine_anneal_c_f32 with
+ *   anneal_sweeps = 0 and max_descent_sweeps = 0 reports for the same bytes and the same node_cost; a terminal's cost
+ *   counts in it.  The pick is unchanged (strictly best score, first on ties).
+ * Negative zero.  The twins' order-preserving key relies on gains that are never -0.0f.  With costs a -0.0f could
+ *   arise in the table (a cost of -0.0f under a class without neighbours) and from it in a gain ((-0.0f) - (+0.0f)).
+ *   The cost variants canonicalise ONCE, where the table is filled: W[v][k] = sum + (+0.0f), which turns -0.0f into
+ *   +0.0f and changes no other value.  After that no table entry is -0.0f (x - x and x + (-x) are +0.0f in
+ *   round-to-nearest; an update by a weight w leaves +0.0f + (+-0.0f) = +0.0f), so no gain is, and the key's order is the
+ *   floats' order as in the twins.  block_cost sums from +0.0f, so the score cannot tell the two zeros apart either: a
+ *   node_cost with -0.0f entries gives, on every output, the bytes of the same array with +0.0f entries.
+ * By construction.  node_cost == NULL: each entry point IS its twin - the twin's kernels, the same bytes on every
+ *   output.  An all-+0.0f node_cost gives the twin's bytes too (the sums start from +0.0f either way; cut - (+0.0f) is
+ *   the cut).  With lo[c] = 0 and hi[c] = n gmc_kway_balance_c_f32 is gmc_kway_tabu_c_f32 byte for byte, for the same
+ *   cost.  For integer weights and costs every sum is exact below 2^24 and obj(result) = obj(input or repaired state) + best.
+ *
+ * Argument checks and status codes are the twin's, in its order; node_cost is never tested (NULL selects the twin).
+ * Costs must be finite; the C side does not check it.  A cost that is not cannot make a kernel index out of range -
+ * the winner of an iteration is decoded from the low half of a key that only a valid (node, class) pair produced - but
+ * nothing is claimed about the result.  The launches are the twins': one wave per chain, the same LDS layout
+ * (gmc_kway_tabu_shape answers for these calls too), 4 / 2 / 1 chains per workgroup over the staged or the global CSR,
+ * two launches on the caller's stream.  With a cost the chain launch is a second kernel compiled from the same body text
+ * with the cost switched on (tabu_cost_kernel<K>, balance_cost_kernel<K>), so that the kernels of the twins keep,
+ * instruction for instruction, the code they had.  The cost is read from global memory at the
+ * table fill and in the scoring tail only and costs no LDS.  No atomics, no spin waits, no scratch, bitwise reproducible. */
+int gmc_kway_tabu_c_f32(const gmc_batch *batch, int32_t K, int32_t terminals,
+                        const float *node_cost /*[R][K] or NULL*/, int32_t cands, int8_t *assign /*[cands][R], in/out*/,
+                        int32_t iterations, int32_t tenure_base, int32_t tenure_span, int32_t tenure_div, uint64_t seed,
+                        float *cut_all /*[B][cands]*/, int32_t *best_assign /*[R]*/, float *best_cut /*[B]*/,
+                        int32_t *best_idx /*[B]*/, int32_t *best_iter /*[B][cands] or NULL*/,
+                        int32_t *moves /*[B][cands] or NULL*/, gmc_stream_t stream);
+
+int gmc_kway_balance_c_f32(const gmc_batch *batch, int32_t K, int32_t terminals,
+                           const float *node_cost /*[R][K] or NULL*/, int32_t cands,
+                           int8_t *assign /*[cands][R], in/out*/, const int32_t *size_lo /*[B][K]*/,
+                           const int32_t *size_hi /*[B][K]*/, int32_t iterations, int32_t tenure_base,
+                           int32_t tenure_span, int32_t tenure_div, uint64_t seed, float *cut_all /*[B][cands]*/,
+                           int32_t *best_assign /*[R]*/, float *best_cut /*[B]*/, int32_t *best_idx /*[B]*/,
+                           int32_t *best_iter /*[B][cands] or NULL*/, int32_t *moves /*[B][cands] or NULL*/,
+                           int32_t *repairs /*[B][cands] or NULL*/, int32_t *feasible /*[B] or NULL*/,
+                           gmc_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
