@@ -47,7 +47,7 @@ import numpy as np
 import torch
 
 from .. import hip
-from ..graph import GraphBatch, GraphHandle, from_networkx
+from ..graph import GraphBatch, GraphHandle, _host_array, from_networkx
 
 
 def assign_partitions(node_probs: np.ndarray) -> List[int]:
@@ -168,6 +168,40 @@ def _decoder_graph_size(what: str, nodes: int) -> None:
                          "large_annealing and search_large_dataset")
 
 
+def _best_outputs(batch: GraphBatch):
+    """Where every search and sampler leaves its pick: best_assign [R], best_cut [B] and the index of the best
+    candidate [B]."""
+    dev = batch.device
+    return (torch.empty(batch.R, dtype=torch.int32, device=dev), torch.empty(batch.B, dtype=torch.float32, device=dev),
+            torch.empty(batch.B, dtype=torch.int32, device=dev))
+
+
+def _search_outputs(batch: GraphBatch, cands: int):
+    """What every search and sampler writes: cut_all [B, cands], then :func:`_best_outputs`."""
+    return (torch.empty((batch.B, cands), dtype=torch.float32, device=batch.device),) + _best_outputs(batch)
+
+
+def _sample_outputs(batch: GraphBatch, iterations: int, keep_samples: bool, seed: int, indices):
+    """What a seeded sampler reads and writes: gkey [B] (the keys of the graphs at dataset positions ``indices``,
+    default 0..B-1), assign_all [iterations, R] int8 (None unless ``keep_samples``), then :func:`_search_outputs`."""
+    keys = sample_keys(seed, range(batch.B) if indices is None else indices)
+    if keys.size != batch.B:
+        raise ValueError(f"{keys.size} graph indices for a batch of {batch.B} graphs")
+    dev = batch.device
+    gkey = torch.from_numpy(keys.view(np.int64)).to(dev) if batch.B else torch.zeros(1, dtype=torch.int64, device=dev)
+    assign_all = torch.empty((iterations, batch.R), dtype=torch.int8, device=dev) if keep_samples else None
+    return (gkey, assign_all) + _search_outputs(batch, iterations)
+
+
+def _schedule_tensors(inv_temp: np.ndarray, dev):
+    """An annealing schedule on the device: inv_t [sweeps] and the level table (both None without sweeps), and sweeps."""
+    sweeps = int(len(inv_temp))
+    if not sweeps:
+        return None, None, 0
+    return (torch.from_numpy(np.ascontiguousarray(inv_temp, np.float32)).to(dev),
+            torch.from_numpy(anneal_levels()).to(dev), sweeps)
+
+
 def _sample_on_gpu(batch: GraphBatch, P: torch.Tensor, iterations: int, seed: Optional[int] = None, indices=None,
                    keep_samples: bool = True):
     """Draw the uniforms in the reference's order and run the fused sampler + cut count.  With ``seed`` (a uint64; the
@@ -175,8 +209,14 @@ def _sample_on_gpu(batch: GraphBatch, P: torch.Tensor, iterations: int, seed: Op
     dataset positions ``indices`` (default 0..B-1) make their keys, no uniform exists on the host, and the
     [iterations, R] samples are allocated only if ``keep_samples`` (else ``assign_all`` is returned as None)."""
     _three_classes_only("the sampling post-processing", P.shape[1])
+    p = hip.ptr
     if seed is not None:
-        return _sample_seeded_on_gpu(batch, P, iterations, seed, indices, keep_samples)
+        gkey, assign_all, cut_all, best_assign, best_cut, best_iter = _sample_outputs(batch, iterations, keep_samples,
+                                                                                      seed, indices)
+        rc = hip.load().gmc_decode_sample_seeded_f32(batch.ref(), p(P.contiguous()), p(gkey), iterations, p(assign_all),
+                                                     p(cut_all), p(best_assign), p(best_cut), p(best_iter), hip.stream())
+        hip.check(rc, "gmc_decode_sample_seeded_f32")
+        return best_assign, best_cut, cut_all, assign_all
     sizes = [int(n) - 3 for n in batch.sizes]
     draws = [np.random.rand(iterations, m) for m in sizes]          # graph -> iteration -> node
     uoff = np.zeros(batch.B + 1, np.int64)
@@ -185,45 +225,19 @@ def _sample_on_gpu(batch: GraphBatch, P: torch.Tensor, iterations: int, seed: Op
     u = torch.from_numpy(np.concatenate([d.ravel() for d in draws]) if uoff[-1] else np.zeros(1)).to(dev)
     uo = torch.from_numpy(uoff).to(dev)
     assign_all = torch.empty((iterations, batch.R), dtype=torch.int8, device=dev)
-    cut_all = torch.empty((batch.B, iterations), dtype=torch.float32, device=dev)
-    best_assign = torch.empty(batch.R, dtype=torch.int32, device=dev)
-    best_cut = torch.empty(batch.B, dtype=torch.float32, device=dev)
-    best_iter = torch.empty(batch.B, dtype=torch.int32, device=dev)
-    p = hip.ptr
+    cut_all, best_assign, best_cut, best_iter = _search_outputs(batch, iterations)
     rc = hip.load().gmc_decode_sample_f32(batch.ref(), p(P.contiguous()), p(u), p(uo), iterations, p(assign_all),
                                           p(cut_all), p(best_assign), p(best_cut), p(best_iter), hip.stream())
     hip.check(rc, "gmc_decode_sample_f32")
     return best_assign, best_cut, cut_all, assign_all
 
 
-def _sample_seeded_on_gpu(batch: GraphBatch, P: torch.Tensor, iterations: int, seed: int, indices, keep_samples: bool):
-    keys = sample_keys(seed, range(batch.B) if indices is None else indices)
-    if keys.size != batch.B:
-        raise ValueError(f"{keys.size} graph indices for a batch of {batch.B} graphs")
-    dev = batch.device
-    gkey = torch.from_numpy(keys.view(np.int64)).to(dev) if batch.B else torch.zeros(1, dtype=torch.int64, device=dev)
-    assign_all = torch.empty((iterations, batch.R), dtype=torch.int8, device=dev) if keep_samples else None
-    cut_all = torch.empty((batch.B, iterations), dtype=torch.float32, device=dev)
-    best_assign = torch.empty(batch.R, dtype=torch.int32, device=dev)
-    best_cut = torch.empty(batch.B, dtype=torch.float32, device=dev)
-    best_iter = torch.empty(batch.B, dtype=torch.int32, device=dev)
-    p = hip.ptr
-    rc = hip.load().gmc_decode_sample_seeded_f32(batch.ref(), p(P.contiguous()), p(gkey), iterations, p(assign_all),
-                                                 p(cut_all), p(best_assign), p(best_cut), p(best_iter), hip.stream())
-    hip.check(rc, "gmc_decode_sample_seeded_f32")
-    return best_assign, best_cut, cut_all, assign_all
-
-
 def _refine_on_gpu(batch: GraphBatch, assign: torch.Tensor, max_sweeps: int):
     """Local search (gmc_refine_local_f32) over the candidates assign [cands, R] int8, refined in place; returns the
     best refined assignment [R], its cut and candidate index per graph."""
-    dev = batch.device
     cands = int(assign.shape[0])
     order, cgoff, cptr = batch.refine_order()
-    cut_all = torch.empty((batch.B, cands), dtype=torch.float32, device=dev)
-    best_assign = torch.empty(batch.R, dtype=torch.int32, device=dev)
-    best_cut = torch.empty(batch.B, dtype=torch.float32, device=dev)
-    best_idx = torch.empty(batch.B, dtype=torch.int32, device=dev)
+    cut_all, best_assign, best_cut, best_idx = _search_outputs(batch, cands)
     p = hip.ptr
     rc = hip.load().gmc_refine_local_f32(batch.ref(), p(order), p(cgoff), p(cptr), cands, p(assign), int(max_sweeps),
                                          p(cut_all), p(best_assign), p(best_cut), p(best_idx), None, hip.stream())
@@ -254,16 +268,10 @@ def anneal_schedule(sweeps: int, t_start: float = 1.5, t_end: float = 0.15, scal
 def _anneal_on_gpu(batch: GraphBatch, assign: torch.Tensor, inv_temp: np.ndarray, seed: int, max_descent_sweeps: int):
     """Annealing + descent (gmc_refine_anneal_f32) over the candidates assign [cands, R] int8, in place; returns the
     best annealed assignment [R], its cut and candidate index per graph."""
-    dev = batch.device
     cands = int(assign.shape[0])
     order, cgoff, cptr = batch.refine_order()
-    sweeps = int(len(inv_temp))
-    inv_t = torch.from_numpy(np.ascontiguousarray(inv_temp, np.float32)).to(dev) if sweeps else None
-    levels = torch.from_numpy(anneal_levels()).to(dev) if sweeps else None
-    cut_all = torch.empty((batch.B, cands), dtype=torch.float32, device=dev)
-    best_assign = torch.empty(batch.R, dtype=torch.int32, device=dev)
-    best_cut = torch.empty(batch.B, dtype=torch.float32, device=dev)
-    best_idx = torch.empty(batch.B, dtype=torch.int32, device=dev)
+    inv_t, levels, sweeps = _schedule_tensors(inv_temp, batch.device)
+    cut_all, best_assign, best_cut, best_idx = _search_outputs(batch, cands)
     p = hip.ptr
     rc = hip.load().gmc_refine_anneal_f32(batch.ref(), p(order), p(cgoff), p(cptr), cands, p(assign), p(inv_t), sweeps,
                                           p(levels), int(seed) & (2 ** 64 - 1), int(max_descent_sweeps), p(cut_all),
@@ -281,6 +289,36 @@ def _as_number(x: float):
     return int(x) if float(x).is_integer() else float(x)
 
 
+def _graph_batch(graph, dev, large: bool = False) -> GraphBatch:
+    """The batch of a one-graph function: a networkx graph, or on the large route a ``GraphHandle`` as well."""
+    handle = graph if large and isinstance(graph, GraphHandle) else from_networkx(graph)
+    return GraphBatch([handle], None, dev)
+
+
+def _one_candidate(part: np.ndarray, dev) -> torch.Tensor:
+    """A checked partition [n] as the searches' candidates [1, n] int8 on the device."""
+    return torch.from_numpy(part.astype(np.int8)).to(dev).reshape(1, -1)
+
+
+def _graph_result(assign: torch.Tensor, cut: torch.Tensor) -> Tuple[List[int], Any]:
+    """What a one-graph function returns: the assignment as a list and its cut as a number."""
+    return assign.cpu().tolist(), _as_number(cut.item())
+
+
+def _graph_probabilities(what: str, node_probabilities, graph, terminals: bool) -> Tuple[torch.Tensor, int]:
+    """The checks the one-graph functions share for node probabilities [n, K], all on the host: two dimensions, the
+    class count (refused in ``what``'s name), the terminals' room, one row per node.  Returns them as a tensor, and K."""
+    probs = node_probabilities if isinstance(node_probabilities, torch.Tensor) else torch.from_numpy(np.asarray(node_probabilities))
+    if probs.dim() != 2:
+        raise ValueError(f"node_probabilities must be [n, number_classes], got {tuple(probs.shape)}")
+    K = _search_classes(what, probs.shape[1])
+    n = graph.number_of_nodes()
+    _check_graph_size(n, K, terminals)
+    if probs.shape[0] != n:
+        raise ValueError(f"node_probabilities has {probs.shape[0]} rows, the graph {n} nodes")
+    return probs, K
+
+
 def post_processing_optimization(node_probabilities, graph, iterations: int = 200, *, seed: Optional[int] = None,
                                  graph_index: int = 0) -> Tuple[List[int], int]:
     """Best of ``iterations`` random samples (TestingNeuralNetwork.py:66-98), on the GPU.  ``seed`` (extension; None
@@ -292,9 +330,9 @@ def post_processing_optimization(node_probabilities, graph, iterations: int = 20
     probs = probs.detach().to(dev, torch.float32)
     if iterations <= 0:
         return None, -float('inf')
-    batch = GraphBatch([from_networkx(graph)], None, dev)
-    best_assign, best_cut, _, _ = _sample_on_gpu(batch, probs, iterations, seed, [graph_index], keep_samples=False)
-    return best_assign.cpu().tolist(), _as_number(best_cut.item())
+    best_assign, best_cut, _, _ = _sample_on_gpu(_graph_batch(graph, dev), probs, iterations, seed, [graph_index],
+                                                 keep_samples=False)
+    return _graph_result(best_assign, best_cut)
 
 
 def local_search_optimization(partition_assignment, graph, max_sweeps: int = 100,
@@ -316,10 +354,8 @@ def local_search_optimization(partition_assignment, graph, max_sweeps: int = 100
                          "number_classes = 3)")
     if max_sweeps < 0:
         raise ValueError(f"max_sweeps must be >= 0, got {max_sweeps}")
-    batch = GraphBatch([from_networkx(graph)], None, dev)
-    assign = torch.from_numpy(part.astype(np.int8)).to(dev).reshape(1, n)
-    best_assign, best_cut, _ = _refine_on_gpu(batch, assign, max_sweeps)
-    return best_assign.cpu().tolist(), _as_number(best_cut.item())
+    best_assign, best_cut, _ = _refine_on_gpu(_graph_batch(graph, dev), _one_candidate(part, dev), max_sweeps)
+    return _graph_result(best_assign, best_cut)
 
 
 def annealing_optimization(partition_assignment, graph, sweeps: int = 100, t_start: float = 1.5, t_end: float = 0.15,
@@ -341,19 +377,22 @@ def annealing_optimization(partition_assignment, graph, sweeps: int = 100, t_sta
                          "number_classes = 3)")
     if sweeps < 0 or max_descent_sweeps < 0:
         raise ValueError(f"sweeps and max_descent_sweeps must be >= 0, got {sweeps} and {max_descent_sweeps}")
-    batch = GraphBatch([from_networkx(graph)], None, dev)
-    assign = torch.from_numpy(part.astype(np.int8)).to(dev).reshape(1, n)
+    batch = _graph_batch(graph, dev)
     inv_temp = anneal_schedule(sweeps, t_start, t_end, _mean_edge_weight(batch))
-    best_assign, best_cut, _ = _anneal_on_gpu(batch, assign, inv_temp, seed, max_descent_sweeps)
-    return best_assign.cpu().tolist(), _as_number(best_cut.item())
+    best_assign, best_cut, _ = _anneal_on_gpu(batch, _one_candidate(part, dev), inv_temp, seed, max_descent_sweeps)
+    return _graph_result(best_assign, best_cut)
+
+
+def _search_classes(what: str, classes: int) -> int:
+    """The class count of the K-class decoders (round.hip and kway_search.hip are written for 2..8 classes)."""
+    K = int(classes)
+    if not 2 <= K <= hip.KWAY_MAX_CLASSES:
+        raise ValueError(f"{what} takes number_classes in 2..{hip.KWAY_MAX_CLASSES}, got {K} classes")
+    return K
 
 
 def _rounding_classes(classes: int) -> int:
-    """The class count of the rounding (round.hip is written for 2..8 classes)."""
-    K = int(classes)
-    if not 2 <= K <= hip.KWAY_MAX_CLASSES:
-        raise ValueError(f"conditional rounding takes number_classes in 2..{hip.KWAY_MAX_CLASSES}, got {K} classes")
-    return K
+    return _search_classes("conditional rounding", classes)
 
 
 def _cost_tensor(batch: GraphBatch, K: int, node_cost) -> Optional[torch.Tensor]:
@@ -369,7 +408,7 @@ def _graph_cost(what: str, node_cost, n: int, K: int) -> Optional[torch.Tensor]:
     """``node_cost`` of a one-graph search -> a [n, K] float32 tensor (host), or None: floats, the shape, finite."""
     if node_cost is None:
         return None
-    a = node_cost.detach().cpu().numpy() if isinstance(node_cost, torch.Tensor) else np.asarray(node_cost)
+    a = _host_array(node_cost)
     if not np.issubdtype(a.dtype, np.floating) or a.shape != (n, K):
         raise ValueError(f"{what}: node_cost must hold floats of shape [{n}, {K}], got {a.dtype} {tuple(a.shape)}")
     a = np.ascontiguousarray(a, np.float32)
@@ -378,19 +417,30 @@ def _graph_cost(what: str, node_cost, n: int, K: int) -> Optional[torch.Tensor]:
     return torch.from_numpy(a)
 
 
-def _call(name: str, terminals: bool, head: tuple, tail: tuple, node_cost: Optional[torch.Tensor] = None) -> None:
-    """Calls the entry point ``name`` with the arguments ``head + tail`` - or, without terminals, its ``_t`` twin, whose
-    ``terminals`` argument (0) stands between the two; or, with ``node_cost`` ([R, K] float32 on the device), its ``_c``
-    twin, which takes ``terminals`` and the cost array there - and raises on a status code."""
-    lib = hip.load()
+def _call(name: str, terminals: bool, head: tuple, tail: tuple, node_cost: Optional[torch.Tensor] = None, *,
+          t_twin: bool = True) -> None:
+    """Calls one entry point of the family ``name`` with ``head + middle + tail`` and raises on a status code.  With
+    ``node_cost`` ([R, K] float32 on the device) it is the ``_c`` twin, whose middle is ``terminals`` and the cost array.
+    Without one, a family with a ``_t`` twin (the rounding, the samplers, the annealings) calls ``name`` itself, which
+    has no middle, with terminals and the ``_t`` twin with ``terminals = 0`` without them; a family without one
+    (``t_twin=False``: the chain searches) calls ``name``, whose middle is ``terminals``."""
+    flag = int(bool(terminals))
     if node_cost is not None:
-        twin = name[:-len("_f32")] + "_c_f32"
-        hip.check(getattr(lib, twin)(*head, int(bool(terminals)), hip.ptr(node_cost), *tail), twin)
+        name, middle = name[:-len("_f32")] + "_c_f32", (flag, hip.ptr(node_cost))
+    elif not t_twin:
+        middle = (flag,)
     elif terminals:
-        hip.check(getattr(lib, name)(*head, *tail), name)
+        middle = ()
     else:
-        twin = name[:-len("_f32")] + "_t_f32"
-        hip.check(getattr(lib, twin)(*head, 0, *tail), twin)
+        name, middle = name[:-len("_f32")] + "_t_f32", (0,)
+    hip.check(getattr(hip.load(), name)(*head, *middle, *tail), name)
+
+
+def _no_large_cost(large: bool, node_cost) -> None:
+    """The large entry points (gmc_large_*) have no ``_c`` twin."""
+    if large and node_cost is not None:
+        raise NotImplementedError("the decoders for graphs beyond hip.MAX_GRAPH_NODES nodes (gmc_large_*) take no "
+                                  "per-node costs: node_cost must be None with large=True")
 
 
 def _first_argmax(P: torch.Tensor) -> torch.Tensor:
@@ -401,11 +451,14 @@ def _first_argmax(P: torch.Tensor) -> torch.Tensor:
     return torch.where(P == top, ids, torch.full_like(ids, K)).min(dim=1).values.clamp_(max=K - 1)
 
 
-def _round_on_gpu(batch: GraphBatch, P: torch.Tensor, descent_sweeps: int, terminals: bool = True, node_cost=None):
+def _round_on_gpu(batch: GraphBatch, P: torch.Tensor, descent_sweeps: int, terminals: bool = True, node_cost=None, *,
+                  large: bool = False):
     """Rounding by conditional expectations + descent (gmc_round_conditional_f32) of P [R, K] for every graph of the
     batch, one launch; returns the assignment [R] int8, and per graph its cut, the expected cut and the descent sweeps
     run.  ``node_cost`` [R, K]: per-node class costs (gmc_round_conditional_c_f32) - cut and expected cut are then the
-    objective, cut minus cost, and its expectation."""
+    objective, cut minus cost, and its expectation.  ``large``: through gmc_large_round_conditional_f32 - the same rule
+    with a graph shared by several workgroups, for graphs of up to ``hip.LARGE_MAX_GRAPH_NODES`` nodes."""
+    _no_large_cost(large, node_cost)
     K = _rounding_classes(P.shape[1])
     node_cost = _cost_tensor(batch, K, node_cost)
     if descent_sweeps < 0:
@@ -420,9 +473,13 @@ def _round_on_gpu(batch: GraphBatch, P: torch.Tensor, descent_sweeps: int, termi
         return assign, cut, expected, sweeps
     order, cgoff, cptr = batch.refine_order(K, terminals)
     p = hip.ptr
-    _call("gmc_round_conditional_f32", terminals, (batch.ref(), p(P.contiguous()), K),
-          (p(order), p(cgoff), p(cptr), int(descent_sweeps), p(assign), p(cut), p(expected), p(sweeps), hip.stream()),
-          node_cost)
+    name, classes, scratch = "gmc_round_conditional_f32", (), ()
+    if large:
+        ws = _large_workspace(batch, K)
+        name, classes, scratch = "gmc_large_round_conditional_f32", (batch.refine_classes(K, terminals),), (p(ws), ws.numel())
+    _call(name, terminals, (batch.ref(), p(P.contiguous()), K),
+          (p(order), p(cgoff), p(cptr), *classes, int(descent_sweeps), *scratch, p(assign), p(cut), p(expected), p(sweeps),
+           hip.stream()), node_cost)
     return assign, cut, expected, sweeps
 
 
@@ -435,21 +492,17 @@ def conditional_rounding(node_probabilities, graph, descent_sweeps: int = 0,
     from its row - what ``loss="expected_cut"`` trains on - deterministic, one visit per node.  ``descent_sweeps > 0``
     then runs that many sweeps of the local search's rule at K classes (until one moves nothing).  Returns the
     assignment and its cut value.  ``terminals=False``: no node is fixed, every node is rounded (and may move)."""
-    probs = node_probabilities if isinstance(node_probabilities, torch.Tensor) else torch.from_numpy(np.asarray(node_probabilities))
-    if probs.dim() != 2:
-        raise ValueError(f"node_probabilities must be [n, number_classes], got {tuple(probs.shape)}")
-    K = _rounding_classes(probs.shape[1])
-    n = graph.number_of_nodes()
-    _check_graph_size(n, K, terminals)
-    if probs.shape[0] != n:
-        raise ValueError(f"node_probabilities has {probs.shape[0]} rows, the graph {n} nodes")
+    return _round_graph(node_probabilities, graph, descent_sweeps, terminals, large=False)
+
+
+def _round_graph(node_probabilities, graph, descent_sweeps: int, terminals: bool, large: bool) -> Tuple[List[int], Any]:
+    probs, _ = _graph_probabilities("conditional rounding", node_probabilities, graph, terminals)
     if descent_sweeps < 0:
         raise ValueError(f"descent_sweeps must be >= 0, got {descent_sweeps}")
     dev = hip.require_gpu()
     probs = probs.detach().to(dev, torch.float32)
-    batch = GraphBatch([from_networkx(graph)], None, dev)
-    assign, cut, _, _ = _round_on_gpu(batch, probs, descent_sweeps, terminals)
-    return assign.cpu().tolist(), _as_number(cut.item())
+    assign, cut, _, _ = _round_on_gpu(_graph_batch(graph, dev, large), probs, descent_sweeps, terminals, large=large)
+    return _graph_result(assign, cut)
 
 
 # ---- the rounding and the local search for graphs beyond hip.MAX_GRAPH_NODES nodes (extension) ----------------------
@@ -462,29 +515,6 @@ def _large_workspace(batch: GraphBatch, K: int) -> torch.Tensor:
     return torch.empty(need, dtype=torch.uint8, device=batch.device)
 
 
-def _large_round_on_gpu(batch: GraphBatch, P: torch.Tensor, descent_sweeps: int, terminals: bool = True):
-    """:func:`_round_on_gpu` through gmc_large_round_conditional_f32: the same rule with a graph shared by several
-    workgroups, for graphs of up to ``hip.LARGE_MAX_GRAPH_NODES`` nodes; the same four results."""
-    K = _rounding_classes(P.shape[1])
-    if descent_sweeps < 0:
-        raise ValueError(f"descent_sweeps must be >= 0, got {descent_sweeps}")
-    _needs_terminals(batch, K, terminals)
-    dev = batch.device
-    assign = torch.empty(batch.R, dtype=torch.int8, device=dev)
-    cut = torch.empty(batch.B, dtype=torch.float32, device=dev)
-    expected = torch.empty(batch.B, dtype=torch.float32, device=dev)
-    sweeps = torch.empty(batch.B, dtype=torch.int32, device=dev)
-    if batch.B == 0:   # nothing to launch (empty tensors have no device pointer to hand over)
-        return assign, cut, expected, sweeps
-    order, cgoff, cptr = batch.refine_order(K, terminals)
-    ws = _large_workspace(batch, K)
-    p = hip.ptr
-    _call("gmc_large_round_conditional_f32", terminals, (batch.ref(), p(P.contiguous()), K),
-          (p(order), p(cgoff), p(cptr), batch.refine_classes(K, terminals), int(descent_sweeps), p(ws), ws.numel(),
-           p(assign), p(cut), p(expected), p(sweeps), hip.stream()))
-    return assign, cut, expected, sweeps
-
-
 def large_conditional_rounding(node_probabilities, graph, descent_sweeps: int = 0,
                                terminals: bool = True) -> Tuple[List[int], Any]:
     """:func:`conditional_rounding` for a graph of any size from number_classes to ``hip.LARGE_MAX_GRAPH_NODES`` nodes
@@ -492,22 +522,7 @@ def large_conditional_rounding(node_probabilities, graph, descent_sweeps: int = 
     graph :func:`conditional_rounding` takes, the same assignment - with the graph shared by several workgroups and
     one launch per colour class.  It issues every launch of ``descent_sweeps`` sweeps whenever the descent converges
     (a converged graph costs nothing but the launches), so give it the sweeps the descent may need, not a huge bound."""
-    probs = node_probabilities if isinstance(node_probabilities, torch.Tensor) else torch.from_numpy(np.asarray(node_probabilities))
-    if probs.dim() != 2:
-        raise ValueError(f"node_probabilities must be [n, number_classes], got {tuple(probs.shape)}")
-    K = _rounding_classes(probs.shape[1])
-    n = graph.number_of_nodes()
-    _check_graph_size(n, K, terminals)
-    if probs.shape[0] != n:
-        raise ValueError(f"node_probabilities has {probs.shape[0]} rows, the graph {n} nodes")
-    if descent_sweeps < 0:
-        raise ValueError(f"descent_sweeps must be >= 0, got {descent_sweeps}")
-    dev = hip.require_gpu()
-    probs = probs.detach().to(dev, torch.float32)
-    handle = graph if isinstance(graph, GraphHandle) else from_networkx(graph)
-    batch = GraphBatch([handle], None, dev)
-    assign, cut, _, _ = _large_round_on_gpu(batch, probs, descent_sweeps, terminals)
-    return assign.cpu().tolist(), _as_number(cut.item())
+    return _round_graph(node_probabilities, graph, descent_sweeps, terminals, large=True)
 
 
 def large_local_search(partition_assignment, graph, number_classes: int, max_sweeps: int = 100,
@@ -520,8 +535,7 @@ def large_local_search(partition_assignment, graph, number_classes: int, max_swe
     if max_sweeps < 0:
         raise ValueError(f"max_sweeps must be >= 0, got {max_sweeps}")
     dev = hip.require_gpu()
-    handle = graph if isinstance(graph, GraphHandle) else from_networkx(graph)
-    batch = GraphBatch([handle], None, dev)
+    batch = _graph_batch(graph, dev, large=True)
     assign = torch.from_numpy(part.astype(np.int8)).to(dev)
     cut = torch.empty(1, dtype=torch.float32, device=dev)
     order, cgoff, cptr = batch.refine_order(K, terminals)
@@ -530,7 +544,7 @@ def large_local_search(partition_assignment, graph, number_classes: int, max_swe
     _call("gmc_large_local_search_f32", terminals, (batch.ref(), K),
           (p(order), p(cgoff), p(cptr), batch.refine_classes(K, terminals), int(max_sweeps), p(ws), ws.numel(), p(assign),
            p(cut), None, hip.stream()))
-    return assign.cpu().tolist(), _as_number(cut.item())
+    return _graph_result(assign, cut)
 
 
 # ---- the seeded sampler and the annealing for graphs beyond hip.MAX_GRAPH_NODES nodes (extension) -------------------
@@ -544,82 +558,14 @@ def _large_search_workspace(batch: GraphBatch, K: int, cands: int) -> torch.Tens
     return torch.empty(need, dtype=torch.uint8, device=batch.device)
 
 
-def _large_sample_on_gpu(batch: GraphBatch, P: torch.Tensor, iterations: int, seed: int, indices, keep_samples: bool,
-                         workspace: Optional[torch.Tensor] = None, terminals: bool = True):
-    """:func:`_kway_sample_on_gpu` through gmc_large_sample_seeded_f32: the same draws with a graph shared by several
-    workgroups, for graphs of up to ``hip.LARGE_MAX_GRAPH_NODES`` nodes; the same four results."""
-    K = _search_classes("the K-class sampler", P.shape[1])
-    _needs_terminals(batch, K, terminals)
-    keys = sample_keys(seed, range(batch.B) if indices is None else indices)
-    if keys.size != batch.B:
-        raise ValueError(f"{keys.size} graph indices for a batch of {batch.B} graphs")
-    dev = batch.device
-    gkey = torch.from_numpy(keys.view(np.int64)).to(dev) if batch.B else torch.zeros(1, dtype=torch.int64, device=dev)
-    assign_all = torch.empty((iterations, batch.R), dtype=torch.int8, device=dev) if keep_samples else None
-    cut_all = torch.empty((batch.B, iterations), dtype=torch.float32, device=dev)
-    best_assign = torch.empty(batch.R, dtype=torch.int32, device=dev)
-    best_cut = torch.empty(batch.B, dtype=torch.float32, device=dev)
-    best_iter = torch.empty(batch.B, dtype=torch.int32, device=dev)
-    if batch.B == 0:   # nothing to launch (empty tensors have no device pointer to hand over)
-        return best_assign, best_cut, cut_all, assign_all
-    ws = _large_search_workspace(batch, K, iterations) if workspace is None else workspace
-    p = hip.ptr
-    _call("gmc_large_sample_seeded_f32", terminals, (batch.ref(), p(P.contiguous()), K),
-          (p(gkey), iterations, p(assign_all), p(ws), ws.numel(), p(cut_all), p(best_assign), p(best_cut), p(best_iter),
-           hip.stream()))
-    return best_assign, best_cut, cut_all, assign_all
-
-
-def _large_anneal_on_gpu(batch: GraphBatch, K: int, assign: torch.Tensor, inv_temp: np.ndarray, seed: int,
-                         max_descent_sweeps: int, workspace: Optional[torch.Tensor] = None, terminals: bool = True):
-    """:func:`_kway_anneal_on_gpu` through gmc_large_anneal_f32, for graphs of up to ``hip.LARGE_MAX_GRAPH_NODES``
-    nodes: the candidates assign [cands, R] int8 searched in place; the best assignment [R], its cut and candidate
-    index per graph."""
-    _needs_terminals(batch, K, terminals)
-    dev = batch.device
-    cands = int(assign.shape[0])
-    cut_all = torch.empty((batch.B, cands), dtype=torch.float32, device=dev)
-    best_assign = torch.empty(batch.R, dtype=torch.int32, device=dev)
-    best_cut = torch.empty(batch.B, dtype=torch.float32, device=dev)
-    best_idx = torch.empty(batch.B, dtype=torch.int32, device=dev)
-    if batch.B == 0:
-        return best_assign, best_cut, best_idx
-    order, cgoff, cptr = batch.refine_order(K, terminals)
-    sweeps = int(len(inv_temp))
-    inv_t = torch.from_numpy(np.ascontiguousarray(inv_temp, np.float32)).to(dev) if sweeps else None
-    levels = torch.from_numpy(anneal_levels()).to(dev) if sweeps else None
-    ws = _large_search_workspace(batch, K, cands) if workspace is None else workspace
-    p = hip.ptr
-    _call("gmc_large_anneal_f32", terminals, (batch.ref(), K),
-          (p(order), p(cgoff), p(cptr), batch.refine_classes(K, terminals), cands, p(assign), p(inv_t), sweeps, p(levels),
-           int(seed) & _M64, int(max_descent_sweeps), p(ws), ws.numel(), p(cut_all), p(best_assign), p(best_cut),
-           p(best_idx), None, None, hip.stream()))
-    return best_assign, best_cut, best_idx
-
-
 def large_sampling_optimization(node_probabilities, graph, iterations: int = 200, *, seed: int = 0,
                                 graph_index: int = 0, terminals: bool = True) -> Tuple[List[int], Any]:
     """:func:`sampling_optimization` for a graph of any size from number_classes to ``hip.LARGE_MAX_GRAPH_NODES`` nodes
     (extension, include/gcnmaxcut.h ``gmc_large_sample_seeded_f32``): the same draws, arguments and results - on a
     graph :func:`sampling_optimization` takes, the same assignment - with the graph shared by several workgroups.  The
     samples live on the device while they are scored: about ``iterations`` bytes per node."""
-    probs = node_probabilities if isinstance(node_probabilities, torch.Tensor) else torch.from_numpy(np.asarray(node_probabilities))
-    if probs.dim() != 2:
-        raise ValueError(f"node_probabilities must be [n, number_classes], got {tuple(probs.shape)}")
-    K = _search_classes("large_sampling_optimization", probs.shape[1])
-    n = graph.number_of_nodes()
-    _check_graph_size(n, K, terminals)
-    if probs.shape[0] != n:
-        raise ValueError(f"node_probabilities has {probs.shape[0]} rows, the graph {n} nodes")
-    dev = hip.require_gpu()
-    probs = probs.detach().to(dev, torch.float32)
-    if iterations <= 0:
-        return None, -float('inf')
-    handle = graph if isinstance(graph, GraphHandle) else from_networkx(graph)
-    batch = GraphBatch([handle], None, dev)
-    best_assign, best_cut, _, _ = _large_sample_on_gpu(batch, probs, iterations, int(seed) & _M64, [graph_index],
-                                                       keep_samples=False, terminals=terminals)
-    return best_assign.cpu().tolist(), _as_number(best_cut.item())
+    return _sample_graph("large_sampling_optimization", node_probabilities, graph, iterations, seed, graph_index,
+                         terminals, large=True)
 
 
 def large_annealing(partition_assignment, graph, number_classes: int, sweeps: int = 100, t_start: float = 1.5,
@@ -630,28 +576,11 @@ def large_annealing(partition_assignment, graph, number_classes: int, sweeps: in
     :func:`kway_annealing` takes with unit or integer weights, the same assignment - with the graph shared by several
     workgroups and one launch per colour class.  Every launch of ``sweeps`` annealing and ``max_descent_sweeps`` descent
     sweeps is issued whenever the descent converges, so give the descent the sweeps it may need, not a huge bound."""
-    K, part = _kway_partition("large_annealing", partition_assignment, graph, number_classes, terminals)
-    if sweeps < 0 or max_descent_sweeps < 0:
-        raise ValueError(f"sweeps and max_descent_sweeps must be >= 0, got {sweeps} and {max_descent_sweeps}")
-    dev = hip.require_gpu()
-    handle = graph if isinstance(graph, GraphHandle) else from_networkx(graph)
-    batch = GraphBatch([handle], None, dev)
-    assign = torch.from_numpy(part.astype(np.int8)).to(dev).reshape(1, -1)
-    inv_temp = anneal_schedule(sweeps, t_start, t_end, _mean_edge_weight(batch))
-    best_assign, best_cut, _ = _large_anneal_on_gpu(batch, K, assign, inv_temp, seed, max_descent_sweeps,
-                                                    terminals=terminals)
-    return best_assign.cpu().tolist(), _as_number(best_cut.item())
+    return _anneal_graph("large_annealing", partition_assignment, graph, number_classes, sweeps, t_start, t_end, seed,
+                         max_descent_sweeps, terminals, large=True)
 
 
 # ---- the seeded sampler, the local search and the annealing for number_classes K in 2..8 (extension) -----------------
-def _search_classes(what: str, classes: int) -> int:
-    """The class count of the K-class decoders (kway_search.hip is written for 2..8 classes)."""
-    K = int(classes)
-    if not 2 <= K <= hip.KWAY_MAX_CLASSES:
-        raise ValueError(f"{what} takes number_classes in 2..{hip.KWAY_MAX_CLASSES}, got {K} classes")
-    return K
-
-
 def assign_partitions_seeded_kway(node_probs: np.ndarray, seed: int, graph_index: int = 0, iteration: int = 0,
                                   terminals: bool = True) -> List[int]:
     """:func:`assign_partitions_seeded` for probabilities of K = 2..8 columns (host form of kway_search.hip's sampler):
@@ -704,26 +633,29 @@ def _needs_terminals(batch: GraphBatch, K: int, terminals: bool = True) -> None:
 
 
 def _kway_sample_on_gpu(batch: GraphBatch, P: torch.Tensor, iterations: int, seed: int, indices, keep_samples: bool,
-                        terminals: bool = True, node_cost=None):
-    """The seeded sampler at K = P.shape[1] classes (gmc_kway_decode_sample_seeded_f32), as ``_sample_seeded_on_gpu``.
-    ``node_cost`` [R, K]: the samples are scored by cut minus cost (gmc_kway_decode_sample_seeded_c_f32)."""
+                        terminals: bool = True, node_cost=None, *, large: bool = False,
+                        workspace: Optional[torch.Tensor] = None):
+    """The seeded sampler at K = P.shape[1] classes (gmc_kway_decode_sample_seeded_f32), as the seeded
+    ``_sample_on_gpu``.  ``node_cost`` [R, K]: the samples are scored by cut minus cost
+    (gmc_kway_decode_sample_seeded_c_f32).  ``large``: through gmc_large_sample_seeded_f32 - the same draws with a graph
+    shared by several workgroups, for graphs of up to ``hip.LARGE_MAX_GRAPH_NODES`` nodes, in ``workspace``
+    (:func:`_large_search_workspace`; None: its own)."""
+    _no_large_cost(large, node_cost)
     K = _search_classes("the K-class sampler", P.shape[1])
     node_cost = _cost_tensor(batch, K, node_cost)
     _needs_terminals(batch, K, terminals)
-    keys = sample_keys(seed, range(batch.B) if indices is None else indices)
-    if keys.size != batch.B:
-        raise ValueError(f"{keys.size} graph indices for a batch of {batch.B} graphs")
-    dev = batch.device
-    gkey = torch.from_numpy(keys.view(np.int64)).to(dev) if batch.B else torch.zeros(1, dtype=torch.int64, device=dev)
-    assign_all = torch.empty((iterations, batch.R), dtype=torch.int8, device=dev) if keep_samples else None
-    cut_all = torch.empty((batch.B, iterations), dtype=torch.float32, device=dev)
-    best_assign = torch.empty(batch.R, dtype=torch.int32, device=dev)
-    best_cut = torch.empty(batch.B, dtype=torch.float32, device=dev)
-    best_iter = torch.empty(batch.B, dtype=torch.int32, device=dev)
+    gkey, assign_all, cut_all, best_assign, best_cut, best_iter = _sample_outputs(batch, iterations, keep_samples, seed,
+                                                                                  indices)
     p = hip.ptr
-    _call("gmc_kway_decode_sample_seeded_f32", terminals, (batch.ref(), p(P.contiguous()), K),
-          (p(gkey), iterations, p(assign_all), p(cut_all), p(best_assign), p(best_cut), p(best_iter), hip.stream()),
-          node_cost)
+    name, scratch = "gmc_kway_decode_sample_seeded_f32", ()
+    if large:
+        if batch.B == 0:   # nothing to launch (the workspace query refuses an empty batch)
+            return best_assign, best_cut, cut_all, assign_all
+        ws = _large_search_workspace(batch, K, iterations) if workspace is None else workspace
+        name, scratch = "gmc_large_sample_seeded_f32", (p(ws), ws.numel())
+    _call(name, terminals, (batch.ref(), p(P.contiguous()), K),
+          (p(gkey), iterations, p(assign_all), *scratch, p(cut_all), p(best_assign), p(best_cut), p(best_iter),
+           hip.stream()), node_cost)
     return best_assign, best_cut, cut_all, assign_all
 
 
@@ -733,46 +665,49 @@ def sampling_optimization(node_probabilities, graph, iterations: int = 200, *, s
     include/gcnmaxcut.h ``gmc_kway_decode_sample_seeded_f32``): what ``post_processing_optimization(..., seed=seed)``
     does for a 3-class model - and, at K = 3, returns.  Nodes 0..K-1 are the terminals; ``graph_index`` is the graph's
     position in its dataset.  Returns the assignment and its cut value."""
-    probs = node_probabilities if isinstance(node_probabilities, torch.Tensor) else torch.from_numpy(np.asarray(node_probabilities))
-    if probs.dim() != 2:
-        raise ValueError(f"node_probabilities must be [n, number_classes], got {tuple(probs.shape)}")
-    K = _search_classes("sampling_optimization", probs.shape[1])
-    n = graph.number_of_nodes()
-    _check_graph_size(n, K, terminals)
-    if probs.shape[0] != n:
-        raise ValueError(f"node_probabilities has {probs.shape[0]} rows, the graph {n} nodes")
+    return _sample_graph("sampling_optimization", node_probabilities, graph, iterations, seed, graph_index, terminals,
+                         large=False)
+
+
+def _sample_graph(what: str, node_probabilities, graph, iterations: int, seed: int, graph_index: int, terminals: bool,
+                  large: bool) -> Tuple[List[int], Any]:
+    probs, _ = _graph_probabilities(what, node_probabilities, graph, terminals)
     dev = hip.require_gpu()
     probs = probs.detach().to(dev, torch.float32)
     if iterations <= 0:
         return None, -float('inf')
-    batch = GraphBatch([from_networkx(graph)], None, dev)
-    best_assign, best_cut, _, _ = _kway_sample_on_gpu(batch, probs, iterations, int(seed) & _M64, [graph_index],
-                                                      keep_samples=False, terminals=terminals)
-    return best_assign.cpu().tolist(), _as_number(best_cut.item())
+    best_assign, best_cut, _, _ = _kway_sample_on_gpu(_graph_batch(graph, dev, large), probs, iterations,
+                                                      int(seed) & _M64, [graph_index], keep_samples=False,
+                                                      terminals=terminals, large=large)
+    return _graph_result(best_assign, best_cut)
 
 
 def _kway_anneal_on_gpu(batch: GraphBatch, K: int, assign: torch.Tensor, inv_temp: np.ndarray, seed: int,
-                        max_descent_sweeps: int, terminals: bool = True, node_cost=None):
+                        max_descent_sweeps: int, terminals: bool = True, node_cost=None, *, large: bool = False,
+                        workspace: Optional[torch.Tensor] = None):
     """Annealing + descent at K classes (gmc_kway_refine_anneal_f32) over the candidates assign [cands, R] int8, in
     place; returns the best assignment [R], its cut and candidate index per graph.  No annealing sweeps: the K-class
-    local search.  ``node_cost`` [R, K]: moves and scores follow cut minus cost (gmc_kway_refine_anneal_c_f32)."""
+    local search.  ``node_cost`` [R, K]: moves and scores follow cut minus cost (gmc_kway_refine_anneal_c_f32).
+    ``large``: through gmc_large_anneal_f32, for graphs of up to ``hip.LARGE_MAX_GRAPH_NODES`` nodes, in ``workspace``
+    (:func:`_large_search_workspace`; None: its own)."""
+    _no_large_cost(large, node_cost)
     _needs_terminals(batch, K, terminals)
     node_cost = _cost_tensor(batch, K, node_cost)
-    dev = batch.device
     cands = int(assign.shape[0])
+    cut_all, best_assign, best_cut, best_idx = _search_outputs(batch, cands)
+    if large and batch.B == 0:   # nothing to launch (the workspace query refuses an empty batch)
+        return best_assign, best_cut, best_idx
     order, cgoff, cptr = batch.refine_order(K, terminals)
-    sweeps = int(len(inv_temp))
-    inv_t = torch.from_numpy(np.ascontiguousarray(inv_temp, np.float32)).to(dev) if sweeps else None
-    levels = torch.from_numpy(anneal_levels()).to(dev) if sweeps else None
-    cut_all = torch.empty((batch.B, cands), dtype=torch.float32, device=dev)
-    best_assign = torch.empty(batch.R, dtype=torch.int32, device=dev)
-    best_cut = torch.empty(batch.B, dtype=torch.float32, device=dev)
-    best_idx = torch.empty(batch.B, dtype=torch.int32, device=dev)
+    inv_t, levels, sweeps = _schedule_tensors(inv_temp, batch.device)
     p = hip.ptr
-    _call("gmc_kway_refine_anneal_f32", terminals, (batch.ref(), K),
-          (p(order), p(cgoff), p(cptr), cands, p(assign), p(inv_t), sweeps, p(levels), int(seed) & _M64,
-           int(max_descent_sweeps), p(cut_all), p(best_assign), p(best_cut), p(best_idx), None, None, hip.stream()),
-          node_cost)
+    name, classes, scratch = "gmc_kway_refine_anneal_f32", (), ()
+    if large:
+        ws = _large_search_workspace(batch, K, cands) if workspace is None else workspace
+        name, classes, scratch = "gmc_large_anneal_f32", (batch.refine_classes(K, terminals),), (p(ws), ws.numel())
+    _call(name, terminals, (batch.ref(), K),
+          (p(order), p(cgoff), p(cptr), *classes, cands, p(assign), p(inv_t), sweeps, p(levels), int(seed) & _M64,
+           int(max_descent_sweeps), *scratch, p(cut_all), p(best_assign), p(best_cut), p(best_idx), None, None,
+           hip.stream()), node_cost)
     return best_assign, best_cut, best_idx
 
 
@@ -801,10 +736,9 @@ def kway_local_search(partition_assignment, graph, number_classes: int, max_swee
     if max_sweeps < 0:
         raise ValueError(f"max_sweeps must be >= 0, got {max_sweeps}")
     dev = hip.require_gpu()
-    batch = GraphBatch([from_networkx(graph)], None, dev)
-    assign = torch.from_numpy(part.astype(np.int8)).to(dev).reshape(1, -1)
-    best_assign, best_cut, _ = _kway_anneal_on_gpu(batch, K, assign, np.zeros(0, np.float32), 0, max_sweeps, terminals)
-    return best_assign.cpu().tolist(), _as_number(best_cut.item())
+    best_assign, best_cut, _ = _kway_anneal_on_gpu(_graph_batch(graph, dev), K, _one_candidate(part, dev),
+                                                   np.zeros(0, np.float32), 0, max_sweeps, terminals)
+    return _graph_result(best_assign, best_cut)
 
 
 def kway_annealing(partition_assignment, graph, number_classes: int, sweeps: int = 100, t_start: float = 1.5,
@@ -815,15 +749,21 @@ def kway_annealing(partition_assignment, graph, number_classes: int, sweeps: int
     ``t_end`` (in units of the graph's mean edge weight), each node proposing the best of the K-1 other classes, the
     best state passed through kept, then the K-class local search from it.  Nodes 0..K-1 keep their classes; the result
     is never worse than the input and is reproducible from ``seed``.  Returns the assignment and its cut value."""
-    K, part = _kway_partition("kway_annealing", partition_assignment, graph, number_classes, terminals)
+    return _anneal_graph("kway_annealing", partition_assignment, graph, number_classes, sweeps, t_start, t_end, seed,
+                         max_descent_sweeps, terminals, large=False)
+
+
+def _anneal_graph(what: str, partition_assignment, graph, number_classes: int, sweeps: int, t_start: float, t_end: float,
+                  seed: int, max_descent_sweeps: int, terminals: bool, large: bool) -> Tuple[List[int], Any]:
+    K, part = _kway_partition(what, partition_assignment, graph, number_classes, terminals)
     if sweeps < 0 or max_descent_sweeps < 0:
         raise ValueError(f"sweeps and max_descent_sweeps must be >= 0, got {sweeps} and {max_descent_sweeps}")
     dev = hip.require_gpu()
-    batch = GraphBatch([from_networkx(graph)], None, dev)
-    assign = torch.from_numpy(part.astype(np.int8)).to(dev).reshape(1, -1)
+    batch = _graph_batch(graph, dev, large)
     inv_temp = anneal_schedule(sweeps, t_start, t_end, _mean_edge_weight(batch))
-    best_assign, best_cut, _ = _kway_anneal_on_gpu(batch, K, assign, inv_temp, seed, max_descent_sweeps, terminals)
-    return best_assign.cpu().tolist(), _as_number(best_cut.item())
+    best_assign, best_cut, _ = _kway_anneal_on_gpu(batch, K, _one_candidate(part, dev), inv_temp, seed, max_descent_sweeps,
+                                                   terminals, large=large)
+    return _graph_result(best_assign, best_cut)
 
 
 # The tabu stage's tenure defaults are PROVISIONAL (DESIGN.md section 30): the literature's 3 + rand(n / 10), taken over
@@ -842,13 +782,9 @@ def _tabu_arguments(what: str, iterations: int, tenure) -> Tuple[int, int, int]:
 
 
 def _chain_outputs(batch: GraphBatch, cands: int):
-    """What both chain searches write: cut_all [B, cands], best_assign [R], best_cut and best_idx [B], best_iter and
-    moves [B, cands]."""
-    dev = batch.device
-    per_chain = lambda dtype: torch.empty((batch.B, cands), dtype=dtype, device=dev)
-    return (per_chain(torch.float32), torch.empty(batch.R, dtype=torch.int32, device=dev),
-            torch.empty(batch.B, dtype=torch.float32, device=dev), torch.empty(batch.B, dtype=torch.int32, device=dev),
-            per_chain(torch.int32), per_chain(torch.int32))
+    """What both chain searches write: :func:`_search_outputs`, then best_iter and moves [B, cands]."""
+    per_chain = lambda: torch.empty((batch.B, cands), dtype=torch.int32, device=batch.device)
+    return _search_outputs(batch, cands) + (per_chain(), per_chain())
 
 
 def _kway_tabu_on_gpu(batch: GraphBatch, K: int, assign: torch.Tensor, iterations: int, tenure, seed: int,
@@ -863,14 +799,9 @@ def _kway_tabu_on_gpu(batch: GraphBatch, K: int, assign: torch.Tensor, iteration
     cands = int(assign.shape[0])
     cut_all, best_assign, best_cut, best_idx, best_iter, moves = _chain_outputs(batch, cands)
     p = hip.ptr
-    tail = (cands, p(assign), int(iterations), base, span, div, int(seed) & _M64, p(cut_all), p(best_assign), p(best_cut),
-            p(best_idx), p(best_iter), p(moves), hip.stream())
-    if node_cost is None:
-        rc = hip.load().gmc_kway_tabu_f32(batch.ref(), K, 1 if terminals else 0, *tail)
-        hip.check(rc, "gmc_kway_tabu_f32")
-    else:
-        rc = hip.load().gmc_kway_tabu_c_f32(batch.ref(), K, 1 if terminals else 0, p(node_cost), *tail)
-        hip.check(rc, "gmc_kway_tabu_c_f32")
+    _call("gmc_kway_tabu_f32", terminals, (batch.ref(), K),
+          (cands, p(assign), int(iterations), base, span, div, int(seed) & _M64, p(cut_all), p(best_assign), p(best_cut),
+           p(best_idx), p(best_iter), p(moves), hip.stream()), node_cost, t_twin=False)
     return best_assign, best_cut, best_idx, best_iter, moves, cut_all
 
 
@@ -892,10 +823,9 @@ def kway_tabu_search(partition_assignment, graph, number_classes: int, iteration
     iterations = 20 * graph.number_of_nodes() if iterations is None else int(iterations)
     tenure = _tabu_arguments("kway_tabu_search", iterations, (tenure_base, tenure_span, tenure_div))
     dev = hip.require_gpu()
-    batch = GraphBatch([from_networkx(graph)], None, dev)
-    assign = torch.from_numpy(part.astype(np.int8)).to(dev).reshape(1, -1)
-    best_assign, best_cut = _kway_tabu_on_gpu(batch, K, assign, iterations, tenure, seed, terminals, node_cost)[:2]
-    return best_assign.cpu().tolist(), _as_number(best_cut.item())
+    best_assign, best_cut = _kway_tabu_on_gpu(_graph_batch(graph, dev), K, _one_candidate(part, dev), iterations, tenure,
+                                              seed, terminals, node_cost)[:2]
+    return _graph_result(best_assign, best_cut)
 
 
 def class_size_bounds(what: str, class_sizes, sizes, K: int, terminals: bool) -> Tuple[np.ndarray, np.ndarray]:
@@ -915,7 +845,7 @@ def class_size_bounds(what: str, class_sizes, sizes, K: int, terminals: bool) ->
             raise ValueError(f"{what}: class_sizes must be 'balanced' or a pair (lo, hi)")
         pair = []
         for name, x in zip(("lo", "hi"), class_sizes):
-            x = x.detach().cpu().numpy() if isinstance(x, torch.Tensor) else np.asarray(x)
+            x = _host_array(x)
             if x.dtype.kind not in "iu" or x.shape not in ((K,), (B, K)):
                 raise ValueError(f"{what}: class_sizes {name} must hold integers of shape [{K}] or [{B}, {K}], got "
                                  f"{x.dtype} {tuple(x.shape)}")
@@ -959,14 +889,10 @@ def _kway_balance_on_gpu(batch: GraphBatch, K: int, assign: torch.Tensor, lo: np
     cut_all, best_assign, best_cut, best_idx, best_iter, moves = _chain_outputs(batch, cands)
     repairs = torch.empty_like(moves)
     p = hip.ptr
-    tail = (cands, p(assign), p(size_lo), p(size_hi), int(iterations), base, span, div, int(seed) & _M64, p(cut_all),
-            p(best_assign), p(best_cut), p(best_idx), p(best_iter), p(moves), p(repairs), None, hip.stream())
-    if node_cost is None:
-        rc = hip.load().gmc_kway_balance_f32(batch.ref(), K, 1 if terminals else 0, *tail)
-        hip.check(rc, "gmc_kway_balance_f32")
-    else:
-        rc = hip.load().gmc_kway_balance_c_f32(batch.ref(), K, 1 if terminals else 0, p(node_cost), *tail)
-        hip.check(rc, "gmc_kway_balance_c_f32")
+    _call("gmc_kway_balance_f32", terminals, (batch.ref(), K),
+          (cands, p(assign), p(size_lo), p(size_hi), int(iterations), base, span, div, int(seed) & _M64, p(cut_all),
+           p(best_assign), p(best_cut), p(best_idx), p(best_iter), p(moves), p(repairs), None, hip.stream()), node_cost,
+          t_twin=False)
     return best_assign, best_cut, best_idx, best_iter, moves, repairs, cut_all
 
 
@@ -992,11 +918,9 @@ def kway_balanced_search(partition_assignment, graph, number_classes: int, class
     tenure = _tabu_arguments("kway_balanced_search", iterations, (tenure_base, tenure_span, tenure_div))
     lo, hi = class_size_bounds("kway_balanced_search", class_sizes, [n], K, terminals)
     dev = hip.require_gpu()
-    batch = GraphBatch([from_networkx(graph)], None, dev)
-    assign = torch.from_numpy(part.astype(np.int8)).to(dev).reshape(1, -1)
-    best_assign, best_cut = _kway_balance_on_gpu(batch, K, assign, lo, hi, iterations, tenure, seed, terminals,
-                                                 node_cost)[:2]
-    return best_assign.cpu().tolist(), _as_number(best_cut.item())
+    best_assign, best_cut = _kway_balance_on_gpu(_graph_batch(graph, dev), K, _one_candidate(part, dev), lo, hi,
+                                                 iterations, tenure, seed, terminals, node_cost)[:2]
+    return _graph_result(best_assign, best_cut)
 
 
 # The evolution stage's defaults are PROVISIONAL: 10 generations of 10 sweeps cooling from 0.6
@@ -1029,15 +953,11 @@ def _kway_evolve_on_gpu(batch: GraphBatch, K: int, population: torch.Tensor, gen
     dev = batch.device
     cands = int(population.shape[0])
     order, cgoff, cptr = batch.refine_order(K)
-    sweeps = int(len(inv_temp))
-    inv_t = torch.from_numpy(np.ascontiguousarray(inv_temp, np.float32)).to(dev) if sweeps else None
-    levels = torch.from_numpy(anneal_levels()).to(dev) if sweeps else None
+    inv_t, levels, sweeps = _schedule_tensors(inv_temp, dev)
     pop = torch.empty((2, cands, batch.R), dtype=torch.int8, device=dev)
     pop[0].copy_(population)
     cut = torch.empty((2, batch.B, cands), dtype=torch.float32, device=dev)
-    best_assign = torch.empty(batch.R, dtype=torch.int32, device=dev)
-    best_cut = torch.empty(batch.B, dtype=torch.float32, device=dev)
-    best_idx = torch.empty(batch.B, dtype=torch.int32, device=dev)
+    best_assign, best_cut, best_idx = _best_outputs(batch)
     history = torch.empty((generations + 1, batch.B), dtype=torch.float32, device=dev)
     p = hip.ptr
     rc = hip.load().gmc_kway_evolve_f32(batch.ref(), K, p(order), p(cgoff), p(cptr), cands, p(pop), p(cut),
@@ -1072,7 +992,7 @@ def kway_evolution(partitions, graph, number_classes: int, generations: int = EV
     elite = _evolve_arguments("kway_evolution", parts.shape[0], generations, generation_sweeps, elite,
                               max_descent_sweeps)
     dev = hip.require_gpu()
-    batch = GraphBatch([from_networkx(graph)], None, dev)
+    batch = _graph_batch(graph, dev)
     population = torch.from_numpy(parts.astype(np.int8)).to(dev)
     inv_temp = anneal_schedule(generation_sweeps, t_start, t_end, _mean_edge_weight(batch))
     best_assign, best_cut, _, history, _, _ = _kway_evolve_on_gpu(batch, K, population, generations, elite, inv_temp,
@@ -1183,6 +1103,27 @@ def test_multiple_graphs(model, processed_graphs: Dict, graph_sizes: List[int],
 test_multiple_graphs.__test__ = False
 
 
+def _dataset_batch(what: str, model, processed_graphs: Dict, large: bool, classes):
+    """What opens every dataset function: the model's engine, the batch of the dataset's graphs with their edge values
+    on the engine's device, and ``classes(eng.K)`` - the function's check of the class count, made before anything is
+    built.  Unless ``large``, a graph beyond ``hip.MAX_GRAPH_NODES`` nodes is refused in ``what``'s name."""
+    items = list(processed_graphs.values())
+    eng = model.engine()
+    K = classes(eng.K)
+    model.eval()
+    handles = [it[0] for it in items]
+    if not large:
+        _decoder_graph_size(what, max((h.n for h in handles), default=0))
+    vals = [h.edge_values(it[1]) for h, it in zip(handles, items)]
+    return eng, GraphBatch(handles, vals, eng.device), K
+
+
+def _graph_rows(batch: GraphBatch):
+    """(g, lo, hi) for every graph of the batch: graph g owns rows lo..hi-1."""
+    for g in range(batch.B):
+        yield g, int(batch.goff_host[g]), int(batch.goff_host[g + 1])
+
+
 def decode_dataset(model, processed_graphs: Dict, post_processing_iterations: int = 200,
                    local_search_sweeps: int = 0, anneal_sweeps: int = 0, anneal_candidates: Optional[int] = None,
                    anneal_seed: int = 0, *, sample_seed: Optional[int] = None,
@@ -1207,17 +1148,11 @@ def decode_dataset(model, processed_graphs: Dict, post_processing_iterations: in
     are without it, and the rounded assignment is not among the candidates of the two searches."""
     if rounding_descent_sweeps is not None and rounding_descent_sweeps < 0:
         raise ValueError(f"rounding_descent_sweeps must be >= 0, got {rounding_descent_sweeps}")
-    items = list(processed_graphs.values())
-    eng = model.engine()
-    _three_classes_only("decode_dataset", eng.K)
-    model.eval()
-    handles = [it[0] for it in items]
-    _decoder_graph_size("decode_dataset", max((h.n for h in handles), default=0))
-    vals = [h.edge_values(it[1]) for h, it in zip(handles, items)]
-    batch = GraphBatch(handles, vals, eng.device)
+    eng, batch, _ = _dataset_batch("decode_dataset", model, processed_graphs, False,
+                                   lambda K: _three_classes_only("decode_dataset", K))
     P, S, loss = eng.forward(batch, 1.0, want_loss=True)
     best_assign, best_cut, _, assign_all = _sample_on_gpu(batch, P, post_processing_iterations,
-                                                          _sample_seed(sample_seed), range(len(items)),
+                                                          _sample_seed(sample_seed), range(batch.B),
                                                           keep_samples=local_search_sweeps > 0 or anneal_sweeps > 0)
     refined = None
     if local_search_sweeps > 0:
@@ -1237,8 +1172,7 @@ def decode_dataset(model, processed_graphs: Dict, post_processing_iterations: in
     S_host, best_host = S.cpu().numpy(), best_assign.cpu().numpy()
     simple, post = (-loss).cpu().tolist(), best_cut.cpu().tolist()
     out = []
-    for g, it in enumerate(items):
-        lo, hi = int(batch.goff_host[g]), int(batch.goff_host[g + 1])
+    for g, lo, hi in _graph_rows(batch):
         out.append({'nodes': hi - lo, 'simple_cut': _as_number(simple[g]), 'simple_assignment': S_host[lo:hi].tolist(),
                     'post_cut': _as_number(post[g]), 'post_assignment': best_host[lo:hi].tolist(),
                     'improvement': _as_number(post[g] - simple[g])})
@@ -1269,9 +1203,8 @@ def _plain_argmax(batch: GraphBatch, P: torch.Tensor, K: int, large: bool = Fals
     S = _first_argmax(P)
     if batch.B == 0:
         return S, torch.empty(0, dtype=torch.float32, device=P.device)
-    search = _large_anneal_on_gpu if large else _kway_anneal_on_gpu
-    _, cut, _ = search(batch, K, S.to(torch.int8).reshape(1, -1).contiguous(), np.zeros(0, np.float32), 0, 0,
-                       terminals=False)
+    _, cut, _ = _kway_anneal_on_gpu(batch, K, S.to(torch.int8).reshape(1, -1).contiguous(), np.zeros(0, np.float32), 0, 0,
+                                    terminals=False, large=large)
     return S, cut
 
 
@@ -1287,29 +1220,25 @@ def round_dataset(model, processed_graphs: Dict, descent_sweeps: int = 0, termin
     overridden), the expected cut fixes no node, and the rounding and the descent visit every node.  A graph may then
     have fewer than number_classes nodes, as long as the dataset's largest graph has that many (the shared model's
     forward, ``gmc_kway_forward``, refuses a batch below that: ``ValueError``)."""
+    return _round_dataset("round_dataset", model, processed_graphs, descent_sweeps, terminals, large=False)
+
+
+def _round_dataset(what: str, model, processed_graphs: Dict, descent_sweeps: int, terminals: bool,
+                   large: bool) -> List[Dict[str, Any]]:
     if descent_sweeps < 0:
         raise ValueError(f"descent_sweeps must be >= 0, got {descent_sweeps}")
-    items = list(processed_graphs.values())
-    eng = model.engine()
-    _rounding_classes(eng.K)
-    model.eval()
-    handles = [it[0] for it in items]
-    _decoder_graph_size("round_dataset", max((h.n for h in handles), default=0))
-    vals = [h.edge_values(it[1]) for h, it in zip(handles, items)]
-    batch = GraphBatch(handles, vals, eng.device)
+    eng, batch, K = _dataset_batch(what, model, processed_graphs, large, _rounding_classes)
     P, S, loss = eng.forward(batch, 1.0, want_loss=True, **_plain_forward(terminals))
-    assign, cut, expected, sweeps = [t.cpu().numpy() for t in _round_on_gpu(batch, P, descent_sweeps, terminals)]
+    assign, cut, expected, sweeps = [t.cpu().numpy() for t in
+                                     _round_on_gpu(batch, P, descent_sweeps, terminals, large=large)]
     if not terminals:
-        S, plain = _plain_argmax(batch, P, eng.K)
+        S, plain = _plain_argmax(batch, P, K, large)
         loss = -plain
     S_host, simple = S.cpu().numpy(), (-loss).cpu().tolist()
-    out = []
-    for g in range(len(items)):
-        lo, hi = int(batch.goff_host[g]), int(batch.goff_host[g + 1])
-        out.append({'nodes': hi - lo, 'simple_cut': _as_number(simple[g]), 'simple_assignment': S_host[lo:hi].tolist(),
-                    'expected_cut': float(expected[g]), 'rounded_cut': _as_number(cut[g]),
-                    'rounded_assignment': assign[lo:hi].tolist(), 'descent_sweeps': int(sweeps[g])})
-    return out
+    return [{'nodes': hi - lo, 'simple_cut': _as_number(simple[g]), 'simple_assignment': S_host[lo:hi].tolist(),
+             'expected_cut': float(expected[g]), 'rounded_cut': _as_number(cut[g]),
+             'rounded_assignment': assign[lo:hi].tolist(), 'descent_sweeps': int(sweeps[g])}
+            for g, lo, hi in _graph_rows(batch)]
 
 
 def round_large_dataset(model, processed_graphs: Dict, descent_sweeps: int = 0,
@@ -1319,28 +1248,7 @@ def round_large_dataset(model, processed_graphs: Dict, descent_sweeps: int = 0,
     ``gmc_large_forward``; an ``adjacency="none"`` dataset has no padded adjacency and its edge weights come from the
     graph) and ONE call of ``gmc_large_round_conditional_f32``.  The keys and, on a dataset :func:`round_dataset`
     takes, the assignments and sweep counts are :func:`round_dataset`'s, with and without ``terminals``."""
-    if descent_sweeps < 0:
-        raise ValueError(f"descent_sweeps must be >= 0, got {descent_sweeps}")
-    items = list(processed_graphs.values())
-    eng = model.engine()
-    _rounding_classes(eng.K)
-    model.eval()
-    handles = [it[0] for it in items]
-    vals = [h.edge_values(it[1]) for h, it in zip(handles, items)]
-    batch = GraphBatch(handles, vals, eng.device)
-    P, S, loss = eng.forward(batch, 1.0, want_loss=True, **_plain_forward(terminals))
-    assign, cut, expected, sweeps = [t.cpu().numpy() for t in _large_round_on_gpu(batch, P, descent_sweeps, terminals)]
-    if not terminals:
-        S, plain = _plain_argmax(batch, P, eng.K, large=True)
-        loss = -plain
-    S_host, simple = S.cpu().numpy(), (-loss).cpu().tolist()
-    out = []
-    for g in range(len(items)):
-        lo, hi = int(batch.goff_host[g]), int(batch.goff_host[g + 1])
-        out.append({'nodes': hi - lo, 'simple_cut': _as_number(simple[g]), 'simple_assignment': S_host[lo:hi].tolist(),
-                    'expected_cut': float(expected[g]), 'rounded_cut': _as_number(cut[g]),
-                    'rounded_assignment': assign[lo:hi].tolist(), 'descent_sweeps': int(sweeps[g])})
-    return out
+    return _round_dataset("round_large_dataset", model, processed_graphs, descent_sweeps, terminals, large=True)
 
 
 def search_dataset(model, processed_graphs: Dict, samples: int = 200, *, sample_seed: int = 0, anneal_sweeps: int = 100,
@@ -1373,9 +1281,20 @@ def search_dataset(model, processed_graphs: Dict, samples: int = 200, *, sample_
     any) left, ``tabu_iterations`` iterations each, and each result gains ``tabu_cut``, ``tabu_assignment`` and
     ``tabu_iteration`` (the iteration at which the winning chain found it; 0: its input).  No other key changes;
     ``tabu_iterations = 0`` launches nothing more and adds no key."""
-    _tabu_arguments("search_dataset", tabu_iterations, TABU_TENURE)
+    return _search_dataset("search_dataset", model, processed_graphs, samples, sample_seed, anneal_sweeps, anneal_seed,
+                           max_descent_sweeps, candidates, generations, generation_sweeps, elite, terminals,
+                           tabu_iterations, tabu_seed, large=False)
+
+
+def _search_dataset(what: str, model, processed_graphs: Dict, samples: int, sample_seed: int, anneal_sweeps: int,
+                    anneal_seed: int, max_descent_sweeps: int, candidates: Optional[int], generations: int,
+                    generation_sweeps: int, elite: Optional[int], terminals: bool, tabu_iterations: int, tabu_seed: int,
+                    large: bool) -> List[Dict[str, Any]]:
+    """:func:`search_dataset`, or with ``large`` :func:`search_large_dataset`: the large decoders, which have neither the
+    evolution nor the tabu stage (its caller passes ``generations = tabu_iterations = 0``), in one workspace."""
+    _tabu_arguments(what, tabu_iterations, TABU_TENURE)
     if not terminals and generations > 0:
-        raise NotImplementedError("search_dataset(generations > 0, terminals=False): the evolution stage "
+        raise NotImplementedError(f"{what}(generations > 0, terminals=False): the evolution stage "
                                   "(gmc_kway_evolve_f32) keeps its terminals")
     if samples < 0:
         raise ValueError(f"samples must be >= 0, got {samples}")
@@ -1384,27 +1303,22 @@ def search_dataset(model, processed_graphs: Dict, samples: int = 200, *, sample_
     take = 2 + samples if candidates is None else int(candidates)
     if not 1 <= take <= 2 + samples:
         raise ValueError(f"candidates must be in 1..{2 + samples}, got {candidates}")
-    elite = _evolve_arguments("search_dataset", take, generations, generation_sweeps, elite, max_descent_sweeps)
-    items = list(processed_graphs.values())
-    eng = model.engine()
-    K = _search_classes("search_dataset", eng.K)
-    model.eval()
-    handles = [it[0] for it in items]
-    _decoder_graph_size("search_dataset", max((h.n for h in handles), default=0))
-    vals = [h.edge_values(it[1]) for h, it in zip(handles, items)]
-    batch = GraphBatch(handles, vals, eng.device)
+    elite = _evolve_arguments(what, take, generations, generation_sweeps, elite, max_descent_sweeps)
+    eng, batch, K = _dataset_batch(what, model, processed_graphs, large, lambda classes: _search_classes(what, classes))
     _needs_terminals(batch, K, terminals)
     P, S, loss = eng.forward(batch, 1.0, want_loss=True, **_plain_forward(terminals))
     if not terminals:
-        S, plain = _plain_argmax(batch, P, K)
+        S, plain = _plain_argmax(batch, P, K, large)
         loss = -plain
-    rnd_assign, rnd_cut, rnd_expected, _ = _round_on_gpu(batch, P, 0, terminals)
+    rnd_assign, rnd_cut, rnd_expected, _ = _round_on_gpu(batch, P, 0, terminals, large=large)
     rows = [S.to(torch.int8).reshape(1, -1), rnd_assign.reshape(1, -1)]
+    # the large route's sampler and annealing share one scratch
+    ws = _large_search_workspace(batch, K, max(take, samples)) if large and batch.B else None
     sampled = None
     if samples > 0:
         best_assign, best_cut, _, assign_all = _kway_sample_on_gpu(batch, P, samples, int(sample_seed) & _M64,
-                                                                   range(len(items)), keep_samples=take > 2,
-                                                                   terminals=terminals)
+                                                                   range(batch.B), keep_samples=take > 2,
+                                                                   terminals=terminals, large=large, workspace=ws)
         sampled = (best_assign.cpu().numpy(), best_cut.cpu().tolist())
         if assign_all is not None:
             rows.append(assign_all)
@@ -1412,7 +1326,7 @@ def search_dataset(model, processed_graphs: Dict, samples: int = 200, *, sample_
     inv_temp = anneal_schedule(anneal_sweeps, scale=_mean_edge_weight(batch))
     found_assign, found_cut, found_idx = [t.cpu().numpy() for t in
                                           _kway_anneal_on_gpu(batch, K, cands, inv_temp, anneal_seed, max_descent_sweeps,
-                                                              terminals)]
+                                                              terminals, large=large, workspace=ws)]
     evolved = None
     start = cands             # what the tabu stage starts from: the searched candidates, or the last population
     if generations > 0:   # the search left its candidates in `cands`: the population
@@ -1429,8 +1343,7 @@ def search_dataset(model, processed_graphs: Dict, samples: int = 200, *, sample_
     S_host, simple = S.cpu().numpy(), (-loss).cpu().tolist()
     rnd_assign, rnd_cut, rnd_expected = rnd_assign.cpu().numpy(), rnd_cut.cpu().numpy(), rnd_expected.cpu().numpy()
     out = []
-    for g in range(len(items)):
-        lo, hi = int(batch.goff_host[g]), int(batch.goff_host[g + 1])
+    for g, lo, hi in _graph_rows(batch):
         out.append({'nodes': hi - lo, 'simple_cut': _as_number(simple[g]), 'simple_assignment': S_host[lo:hi].tolist(),
                     'expected_cut': float(rnd_expected[g]), 'rounded_cut': _as_number(rnd_cut[g]),
                     'rounded_assignment': rnd_assign[lo:hi].tolist()})
@@ -1467,51 +1380,6 @@ def search_large_dataset(model, processed_graphs: Dict, samples: int = 200, *, s
     nodes; 8 samples: 50 MiB).  The calls issue ``anneal_sweeps * (classes + 3) +
     max_descent_sweeps * (classes + 1)`` launches and more (``classes`` the colour classes of the batch, see the
     header), whenever the descent converges: give ``max_descent_sweeps`` the sweeps the descent may need."""
-    if samples < 0:
-        raise ValueError(f"samples must be >= 0, got {samples}")
-    if anneal_sweeps < 0 or max_descent_sweeps < 0:
-        raise ValueError(f"anneal_sweeps and max_descent_sweeps must be >= 0, got {anneal_sweeps} and {max_descent_sweeps}")
-    take = 2 + samples if candidates is None else int(candidates)
-    if not 1 <= take <= 2 + samples:
-        raise ValueError(f"candidates must be in 1..{2 + samples}, got {candidates}")
-    items = list(processed_graphs.values())
-    eng = model.engine()
-    K = _search_classes("search_large_dataset", eng.K)
-    model.eval()
-    handles = [it[0] for it in items]
-    vals = [h.edge_values(it[1]) for h, it in zip(handles, items)]
-    batch = GraphBatch(handles, vals, eng.device)
-    _needs_terminals(batch, K, terminals)
-    P, S, loss = eng.forward(batch, 1.0, want_loss=True, **_plain_forward(terminals))
-    if not terminals:
-        S, plain = _plain_argmax(batch, P, K, large=True)
-        loss = -plain
-    rnd_assign, rnd_cut, rnd_expected, _ = _large_round_on_gpu(batch, P, 0, terminals)
-    rows = [S.to(torch.int8).reshape(1, -1), rnd_assign.reshape(1, -1)]
-    ws = _large_search_workspace(batch, K, max(take, samples)) if batch.B else None   # one scratch for both calls
-    sampled = None
-    if samples > 0:
-        best_assign, best_cut, _, assign_all = _large_sample_on_gpu(batch, P, samples, int(sample_seed) & _M64,
-                                                                    range(len(items)), keep_samples=take > 2,
-                                                                    workspace=ws, terminals=terminals)
-        sampled = (best_assign.cpu().numpy(), best_cut.cpu().tolist())
-        if assign_all is not None:
-            rows.append(assign_all)
-    cands = torch.cat(rows)[:take].contiguous()
-    inv_temp = anneal_schedule(anneal_sweeps, scale=_mean_edge_weight(batch))
-    found_assign, found_cut, found_idx = [t.cpu().numpy() for t in
-                                          _large_anneal_on_gpu(batch, K, cands, inv_temp, anneal_seed,
-                                                               max_descent_sweeps, workspace=ws, terminals=terminals)]
-    S_host, simple = S.cpu().numpy(), (-loss).cpu().tolist()
-    rnd_assign, rnd_cut, rnd_expected = rnd_assign.cpu().numpy(), rnd_cut.cpu().numpy(), rnd_expected.cpu().numpy()
-    out = []
-    for g in range(len(items)):
-        lo, hi = int(batch.goff_host[g]), int(batch.goff_host[g + 1])
-        out.append({'nodes': hi - lo, 'simple_cut': _as_number(simple[g]), 'simple_assignment': S_host[lo:hi].tolist(),
-                    'expected_cut': float(rnd_expected[g]), 'rounded_cut': _as_number(rnd_cut[g]),
-                    'rounded_assignment': rnd_assign[lo:hi].tolist()})
-        if sampled is not None:
-            out[-1].update({'post_cut': _as_number(sampled[1][g]), 'post_assignment': sampled[0][lo:hi].tolist()})
-        out[-1].update({'searched_cut': _as_number(found_cut[g]), 'searched_assignment': found_assign[lo:hi].tolist(),
-                        'searched_from': int(found_idx[g])})
-    return out
+    return _search_dataset("search_large_dataset", model, processed_graphs, samples, sample_seed, anneal_sweeps,
+                           anneal_seed, max_descent_sweeps, candidates, 0, EVOLVE_GENERATION_SWEEPS, None, terminals, 0, 0,
+                           large=True)

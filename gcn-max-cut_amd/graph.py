@@ -151,6 +151,11 @@ def _check_pairs(pairs: str) -> None:
         raise ValueError(f"pairs must be one of {PAIRS}, got {pairs!r}")
 
 
+def _host_array(x) -> np.ndarray:
+    """``x`` (numpy, torch on any device, or anything ``np.asarray`` takes) as a numpy array on the host."""
+    return x.detach().cpu().numpy() if isinstance(x, torch.Tensor) else np.asarray(x)
+
+
 def _integer_dtype(dtype) -> bool:
     if isinstance(dtype, torch.dtype):
         return dtype in (torch.uint8, torch.int8, torch.int16, torch.int32, torch.int64)
@@ -188,13 +193,12 @@ def from_edge_index(edge_index, num_nodes: int, edge_weight=None, pairs: str = "
     n = int(num_nodes)
     if n < 0 or n >= 2 ** 31:
         raise ValueError(f"num_nodes = {n}: need 0 <= num_nodes < 2^31")
-    ei = edge_index.detach().cpu().numpy() if isinstance(edge_index, torch.Tensor) else np.asarray(edge_index)
+    ei = _host_array(edge_index)
     rows, cols = ei[0].astype(np.int64), ei[1].astype(np.int64)
     if edge_weight is None:
         ww = np.ones(E, np.float32)
     else:
-        ww = edge_weight.detach().cpu().numpy() if isinstance(edge_weight, torch.Tensor) else np.asarray(edge_weight)
-        ww = ww.astype(np.float32)
+        ww = _host_array(edge_weight).astype(np.float32)
     bad = int(((rows < 0) | (rows >= n) | (cols < 0) | (cols >= n)).sum())
     if bad:
         raise ValueError(f"edge_index: {bad} entries with an id outside 0..{n - 1}")
@@ -330,8 +334,7 @@ def contract(handle: GraphHandle, nodes, classes, number_classes: int) -> HostCo
     naming the kind and the count, as ``GraphBatch.contract`` does."""
     _check_pins(nodes, classes, number_classes)
     K, n = int(number_classes), handle.n
-    as_np = lambda a: a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
-    nd, cl = as_np(nodes), as_np(classes)
+    nd, cl = _host_array(nodes), _host_array(classes)
     # (compared as Python-sized integers: no id wraps into range)
     node_ok = (nd >= 0) & (nd < n)
     class_ok = (cl >= 0) & (cl < K)
@@ -567,7 +570,7 @@ class GraphBatch:
         if ptr is None:
             goff = np.asarray([0, int(num_nodes)], np.int64)
         else:
-            p = ptr.detach().cpu().numpy() if isinstance(ptr, torch.Tensor) else np.asarray(ptr)
+            p = _host_array(ptr)
             if p.ndim != 1 or p.size < 1:
                 raise ValueError(f"ptr must be [B + 1], got shape {tuple(p.shape)}")
             if not np.issubdtype(p.dtype, np.integer):

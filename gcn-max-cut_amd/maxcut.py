@@ -20,7 +20,7 @@ import torch
 
 from . import hip
 from .engine import InstanceEngine, LargeInstanceEngine, instance_too_large
-from .graph import GraphBatch, _check_pins
+from .graph import GraphBatch, _check_pins, _host_array
 
 
 _TOO_LARGE = ("a graph of {n} nodes is beyond the one-workgroup head of the per-graph models (number_classes = {K}): "
@@ -59,17 +59,22 @@ class MaxCutResult:
     #                                                sum_v node_cost[v][class_v] (a constant of every partition)
 
 
+def _classes(number_classes) -> int:
+    K = int(number_classes)
+    if not 2 <= K <= hip.KWAY_MAX_CLASSES:
+        raise ValueError(f"number_classes must be in 2..{hip.KWAY_MAX_CLASSES}, got {K}")
+    return K
+
+
 def balanced_sizes(ptr, number_classes: int, imbalance: float = 0.0):
     """``class_sizes`` for :func:`solve` from the graphs' sizes: ``(lo, hi)``, int32 numpy arrays [B, K] with
     ``lo = floor((1 - imbalance) * n / K)`` and ``hi = ceil((1 + imbalance) * n / K)`` for every class of a graph of n
     nodes (``ptr`` [B + 1] as :func:`solve` takes it).  ``imbalance = 0``: ``"balanced"``.  The products are taken in
     float64 and a value within 1e-9 of an integer counts as that integer, so 1.03 * 1000 / 2 is 515 and not 516."""
-    K = int(number_classes)
-    if not 2 <= K <= hip.KWAY_MAX_CLASSES:
-        raise ValueError(f"number_classes must be in 2..{hip.KWAY_MAX_CLASSES}, got {K}")
+    K = _classes(number_classes)
     if not 0.0 <= float(imbalance) <= 1.0:
         raise ValueError(f"imbalance must be in 0..1, got {imbalance}")
-    p = ptr.detach().cpu().numpy() if isinstance(ptr, torch.Tensor) else np.asarray(ptr)
+    p = _host_array(ptr)
     if p.ndim != 1 or p.size < 1:
         raise ValueError("ptr must be [B + 1]")
     n = np.diff(p.astype(np.int64)).astype(np.float64)
@@ -141,16 +146,14 @@ def solve(edge_index, ptr=None, num_nodes: Optional[int] = None, edge_weight=Non
     A graph beyond the one-workgroup head of the per-graph models raises ``ValueError``: for such a graph train a model
     through ``gcn_max_cut_amd.functional`` (terminal-free up to 2^20 nodes) and decode it with
     ``search_large_dataset(..., terminals=False)``."""
-    K, terminals = int(number_classes), bool(terminals)
-    if not 2 <= K <= hip.KWAY_MAX_CLASSES:
-        raise ValueError(f"number_classes must be in 2..{hip.KWAY_MAX_CLASSES}, got {K}")
+    K, terminals = _classes(number_classes), bool(terminals)
     loss = hip.loss_name(loss)
     _check_fixed(fixed, terminals, K)
     _check_sizes(class_sizes, balance_iterations, fixed)
     if node_cost is not None:
         node_cost = _check_node_cost(node_cost, _rows_of(ptr, num_nodes), K, tabu_iterations, class_sizes, fixed)
     if ptr is not None:   # judged before anything is built: the sizes are all it takes
-        p = ptr.detach().cpu().numpy() if isinstance(ptr, torch.Tensor) else np.asarray(ptr)
+        p = _host_array(ptr)
         n_max = int(np.diff(p.astype(np.int64)).max()) if p.ndim == 1 and p.size > 1 else 0
         if class_sizes is not None and p.ndim == 1 and p.size > 1:
             _size_bounds(class_sizes, np.diff(p.astype(np.int64)), K, terminals)
@@ -158,11 +161,11 @@ def solve(edge_index, ptr=None, num_nodes: Optional[int] = None, edge_weight=Non
         n_max = int(num_nodes) if num_nodes is not None else 0
         if class_sizes is not None and num_nodes is not None:
             _size_bounds(class_sizes, [n_max], K, terminals)
-    if fixed is None and n_max > 0 and instance_too_large(n_max, K, loss):   # (with pins: the contracted sizes decide)
-        raise ValueError(_TOO_LARGE.format(n=n_max, K=K))
+    if fixed is None and n_max > 0:   # (with pins: the contracted sizes decide)
+        _refuse_small(n_max, K, loss)
     batch = GraphBatch.from_edge_index(edge_index, ptr, num_nodes, edge_weight, pairs=pairs)
     if node_cost is not None:   # (checked above, once: no tabu, sizes or pins come with it)
-        return _solve_batch(_small_route(), batch, K, terminals, hidden_dim, epochs, learning_rate, loss, samples,
+        return _solve_batch(_SMALL, batch, K, terminals, hidden_dim, epochs, learning_rate, loss, samples,
                             anneal_sweeps, max_descent_sweeps, seed, node_cost=node_cost)
     return solve_batch(batch, number_classes=K, terminals=terminals, hidden_dim=hidden_dim, epochs=epochs,
                        learning_rate=learning_rate, loss=loss, samples=samples, anneal_sweeps=anneal_sweeps,
@@ -188,7 +191,7 @@ def solve_batch(batch: GraphBatch, *, number_classes: int = 2, terminals: bool =
     _check_sizes(class_sizes, balance_iterations, fixed)
     if node_cost is not None:
         node_cost = _check_node_cost(node_cost, batch.R, int(number_classes))
-    return _solve_fixed(_small_route(), batch, fixed, number_classes, terminals, hidden_dim, epochs, learning_rate, loss,
+    return _solve_fixed(_SMALL, batch, fixed, number_classes, terminals, hidden_dim, epochs, learning_rate, loss,
                         samples, anneal_sweeps, max_descent_sweeps, seed, tabu_iterations, class_sizes,
                         balance_iterations, node_cost=node_cost)
 
@@ -216,9 +219,7 @@ def solve_large(edge_index, ptr=None, num_nodes: Optional[int] = None, edge_weig
         raise NotImplementedError(_NO_TABU)
     if class_sizes is not None:
         raise NotImplementedError(_NO_BALANCE)
-    K, terminals = int(number_classes), bool(terminals)
-    if not 2 <= K <= hip.KWAY_MAX_CLASSES:
-        raise ValueError(f"number_classes must be in 2..{hip.KWAY_MAX_CLASSES}, got {K}")
+    K, terminals = _classes(number_classes), bool(terminals)
     loss = hip.loss_name(loss)
     _check_fixed(fixed, terminals, K)
     batch = GraphBatch.from_edge_index(edge_index, ptr, num_nodes, edge_weight, pairs=pairs)
@@ -240,7 +241,7 @@ def solve_large_batch(batch: GraphBatch, *, number_classes: int = 2, terminals: 
         raise NotImplementedError(_NO_COST_LARGE)
     if class_sizes is not None:
         raise NotImplementedError(_NO_BALANCE)
-    return _solve_fixed(_large_route(), batch, fixed, number_classes, terminals, hidden_dim, epochs, learning_rate, loss,
+    return _solve_fixed(_LARGE, batch, fixed, number_classes, terminals, hidden_dim, epochs, learning_rate, loss,
                         samples, anneal_sweeps, max_descent_sweeps, seed, tabu_iterations)
 
 
@@ -259,7 +260,7 @@ def _check_fixed(fixed, terminals: bool, number_classes: int) -> None:
 def _rows_of(ptr, num_nodes) -> Optional[int]:
     """The batch's row count as ``ptr`` / ``num_nodes`` state it (None when they do not: from_edge_index then raises)."""
     if ptr is not None:
-        p = ptr.detach().cpu().numpy() if isinstance(ptr, torch.Tensor) else np.asarray(ptr)
+        p = _host_array(ptr)
         return int(p[-1]) if p.ndim == 1 and p.size >= 1 else None
     return None if num_nodes is None else int(num_nodes)
 
@@ -325,88 +326,59 @@ def _solve_fixed(route: "_Route", batch: GraphBatch, fixed, number_classes: int,
         return _solve_batch(route, batch, number_classes, terminals, *args, node_cost=node_cost)
     K = int(number_classes)
     _check_fixed(fixed, bool(terminals), K)
-    large = bool(batch.B) and batch.n_max > hip.MAX_GRAPH_NODES
-    if node_cost is not None and (large or route.tabu is None):
+    from .Testing import TestingNeuralNetwork as T
+    large = route.large or (bool(batch.B) and batch.n_max > hip.MAX_GRAPH_NODES)   # the recount's route
+    if node_cost is not None and large:
         raise NotImplementedError(_NO_COST_LARGE)
     ct = batch.contract(fixed[0], fixed[1], K)
     parts = {}
-    cost, fixed_cost, dec = None, None, ()
+    cost, fixed_cost = None, None
     if node_cost is not None:
         node_cost = node_cost.to(batch.device)
         cost, fixed_cost = ct.contract_cost(node_cost, batch.goff)
-        dec = (node_cost,)
     res = _solve_batch(route, ct.batch, K, True, *args, parts=parts, node_cost=cost)
     no_sweeps = np.zeros(0, np.float32)
-    score = _large_route().anneal if large else route.anneal
 
     def recount(partition):
-        return score(batch, K, partition.to(torch.int8).reshape(1, -1).contiguous(), no_sweeps, 0, 0, False, *dec)[1]
+        return T._kway_anneal_on_gpu(batch, K, partition.to(torch.int8).reshape(1, -1).contiguous(), no_sweeps, 0, 0, False,
+                                     node_cost, large=large)[1]
 
     partition = ct.lift(res.partition)
-    if batch.B == 0:
-        return MaxCutResult(partition, res.cut, res.trained_cut, res.rounded_cut, batch.goff, fixed_cut=ct.fixed_cut,
-                            node_cost_sum=res.node_cost_sum, fixed_cost=fixed_cost)
-    if node_cost is not None:
-        return MaxCutResult(partition, recount(partition), recount(ct.lift(parts["trained"])),
-                            recount(ct.lift(parts["rounded"])), batch.goff,
-                            recount(ct.lift(parts["annealed"])) if "annealed" in parts else None, ct.fixed_cut,
-                            node_cost_sum=_node_cost_sum(batch, node_cost, partition), fixed_cost=fixed_cost)
-    # the cuts of the contracted run differ from the original graph's by fixed_cut; for weights that are not integers the
-    # sum of the two need not carry the bits of a recount, so every cut is recounted from its lifted partition
-    return MaxCutResult(partition, recount(partition), recount(ct.lift(parts["trained"])),
-                        recount(ct.lift(parts["rounded"])), batch.goff,
-                        recount(ct.lift(parts["annealed"])) if "annealed" in parts else None, ct.fixed_cut)
+    cuts, cost_sum = (res.cut, res.trained_cut, res.rounded_cut, None), res.node_cost_sum
+    if batch.B:
+        # the cuts of the contracted run differ from the original graph's by fixed_cut; for weights that are not integers
+        # the sum of the two need not carry the bits of a recount, so every cut is recounted from its lifted partition
+        cuts = (recount(partition), recount(ct.lift(parts["trained"])), recount(ct.lift(parts["rounded"])),
+                recount(ct.lift(parts["annealed"])) if "annealed" in parts else None)
+        cost_sum = None if node_cost is None else _node_cost_sum(batch, node_cost, partition)
+    cut, trained_cut, rounded_cut, annealed_cut = cuts
+    return MaxCutResult(partition, cut, trained_cut, rounded_cut, batch.goff, annealed_cut, ct.fixed_cut,
+                        node_cost_sum=cost_sum, fixed_cost=fixed_cost)
 
 
-@dataclass
+def _refuse_small(n_max: int, K: int, loss: str) -> None:
+    if instance_too_large(n_max, K, loss):
+        raise ValueError(_TOO_LARGE.format(n=n_max, K=K))
+
+
+def _refuse_large(n_max: int, K: int, loss: str) -> None:
+    if n_max > hip.LARGE_MAX_GRAPH_NODES:
+        raise ValueError(_BEYOND_LARGE.format(n=n_max, bound=hip.LARGE_MAX_GRAPH_NODES))
+
+
+@dataclass(frozen=True)
 class _Route:
     """What tells :func:`solve_batch` from :func:`solve_large_batch`: the engine class, the refusal of a batch by its
-    largest graph, and the three decoders as ``round(batch, P, terminals)``, ``sample(batch, P, samples, seed, terminals)``
-    and ``anneal(batch, K, cands, inv_temp, seed, max_descent_sweeps, terminals)`` (the small route's three take a
-    trailing ``node_cost`` as well); ``tabu(batch, K, cands, iterations,
-    seed, terminals)`` and ``balance(batch, K, cands, lo, hi, iterations, seed, terminals)`` where the route has the
-    stage (the small route's two take a trailing ``node_cost`` too)."""
+    largest graph, ``large`` as the decoders of ``Testing.TestingNeuralNetwork`` take it, and whether the route has the
+    tabu and the balanced stage - and with them per-node costs."""
     engine: type
     refuse: Callable
-    round: Callable
-    sample: Callable
-    anneal: Callable
-    tabu: Optional[Callable] = None
-    balance: Optional[Callable] = None
+    large: bool
+    stages: bool
 
 
-def _small_route() -> _Route:
-    from .Testing import TestingNeuralNetwork as T
-
-    def refuse(n_max, K, loss):
-        if instance_too_large(n_max, K, loss):
-            raise ValueError(_TOO_LARGE.format(n=n_max, K=K))
-
-    return _Route(InstanceEngine, refuse,
-                  lambda batch, P, t, c=None: T._round_on_gpu(batch, P, 0, t, c),
-                  lambda batch, P, n, seed, t, c=None: T._kway_sample_on_gpu(batch, P, n, seed, range(batch.B), True, t,
-                                                                             c)[3],
-                  lambda batch, K, cands, inv_temp, seed, sweeps, t, c=None: T._kway_anneal_on_gpu(batch, K, cands, inv_temp,
-                                                                                                   seed, sweeps, t, c),
-                  lambda batch, K, cands, iterations, seed, t, c=None: T._kway_tabu_on_gpu(batch, K, cands, iterations,
-                                                                                           T.TABU_TENURE, seed, t, c),
-                  lambda batch, K, cands, lo, hi, iterations, seed, t, c=None: T._kway_balance_on_gpu(
-                      batch, K, cands, lo, hi, iterations, T.TABU_TENURE, seed, t, c))
-
-
-def _large_route() -> _Route:
-    from .Testing import TestingNeuralNetwork as T
-
-    def refuse(n_max, K, loss):
-        if n_max > hip.LARGE_MAX_GRAPH_NODES:
-            raise ValueError(_BEYOND_LARGE.format(n=n_max, bound=hip.LARGE_MAX_GRAPH_NODES))
-
-    return _Route(LargeInstanceEngine, refuse,
-                  lambda batch, P, t: T._large_round_on_gpu(batch, P, 0, t),
-                  lambda batch, P, n, seed, t: T._large_sample_on_gpu(batch, P, n, seed, range(batch.B), True,
-                                                                      terminals=t)[3],
-                  lambda batch, K, cands, inv_temp, seed, sweeps, t: T._large_anneal_on_gpu(batch, K, cands, inv_temp, seed,
-                                                                                            sweeps, terminals=t))
+_SMALL = _Route(InstanceEngine, _refuse_small, large=False, stages=True)
+_LARGE = _Route(LargeInstanceEngine, _refuse_large, large=True, stages=False)
 
 
 def _solve_batch(route: _Route, batch: GraphBatch, number_classes: int, terminals: bool, hidden_dim: int, epochs: int,
@@ -419,20 +391,18 @@ def _solve_batch(route: _Route, batch: GraphBatch, number_classes: int, terminal
     pass the checked tensor down (small route); the tabu and the balanced stage then take it too; ``abs_scale``: the
     annealing's temperature in units of the mean absolute edge weight (the doors with signed weights)."""
     from .Testing import TestingNeuralNetwork as T
-    K, terminals = int(number_classes), bool(terminals)
-    if not 2 <= K <= hip.KWAY_MAX_CLASSES:
-        raise ValueError(f"number_classes must be in 2..{hip.KWAY_MAX_CLASSES}, got {K}")
+    K, terminals = _classes(number_classes), bool(terminals)
     if epochs < 0 or samples < 0 or anneal_sweeps < 0 or max_descent_sweeps < 0:
         raise ValueError(f"epochs, samples, anneal_sweeps and max_descent_sweeps must be >= 0, got {epochs}, {samples}, "
                          f"{anneal_sweeps}, {max_descent_sweeps}")
     if not 0 <= int(tabu_iterations) < 1 << 31:
         raise ValueError(f"tabu_iterations must be in 0..2^31-1, got {tabu_iterations}")
-    if tabu_iterations and route.tabu is None:
+    if tabu_iterations and not route.stages:
         raise NotImplementedError(_NO_TABU)
     _check_sizes(class_sizes, balance_iterations, None)
     bounds = None
     if class_sizes is not None:
-        if route.balance is None:
+        if not route.stages:
             raise NotImplementedError(_NO_BALANCE)
         bounds = _size_bounds(class_sizes, batch.sizes, K, terminals)   # on the host, before anything is trained
     loss = hip.loss_name(loss)
@@ -440,11 +410,10 @@ def _solve_batch(route: _Route, batch: GraphBatch, number_classes: int, terminal
         route.refuse(batch.n_max, K, loss)
     cost = {}
     if node_cost is not None:
-        if route.tabu is None:
+        if not route.stages:
             raise NotImplementedError(_NO_COST_LARGE)
         node_cost = node_cost.to(batch.device)
         cost = {"node_cost": node_cost}
-    dec = () if node_cost is None else (node_cost,)   # the decoders' trailing argument
     eng = route.engine(batch, int(hidden_dim), K, batch.device, terminals=terminals, **cost)
     with torch.random.fork_rng(devices=[]):
         torch.manual_seed(int(seed))
@@ -460,22 +429,21 @@ def _solve_batch(route: _Route, batch: GraphBatch, number_classes: int, terminal
         none = torch.empty(0, dtype=torch.float32, device=dev)
         return MaxCutResult(best_S, none, none.clone(), none.clone(), batch.goff,
                             node_cost_sum=None if node_cost is None else none.clone())
-    rounded, rounded_cut, _, _ = route.round(batch, P, terminals, *dec)
+    large = route.large
+    rounded, rounded_cut, _, _ = T._round_on_gpu(batch, P, 0, terminals, node_cost, large=large)
     trained = best_S.to(torch.int8).reshape(1, -1)
     no_sweeps = np.zeros(0, np.float32)
-    _, trained_cut, _ = route.anneal(batch, K, trained.clone(), no_sweeps, 0, 0, terminals, *dec)   # scores, moves nothing
+    _, trained_cut, _ = T._kway_anneal_on_gpu(batch, K, trained.clone(), no_sweeps, 0, 0, terminals, node_cost,
+                                              large=large)   # scores, moves nothing
     rows = [trained, rounded.reshape(1, -1)]
     if samples > 0:
-        rows.append(route.sample(batch, P, int(samples), int(seed) & T._M64, terminals, *dec))
+        rows.append(T._kway_sample_on_gpu(batch, P, int(samples), int(seed) & T._M64, range(batch.B), True, terminals,
+                                          node_cost, large=large)[3])
     cands = torch.cat(rows).contiguous()
     scale = T._mean_edge_weight(batch) if bounds is None and not abs_scale else _mean_abs_edge_weight(batch)
     inv_temp = T.anneal_schedule(int(anneal_sweeps), scale=scale)
-    partition, cut, _ = route.anneal(batch, K, cands, inv_temp, seed, int(max_descent_sweeps), terminals, *dec)
-    if node_cost is not None and not tabu_iterations and bounds is None:
-        if parts is not None:
-            parts.update(trained=best_S, rounded=rounded)
-        return MaxCutResult(partition, cut, trained_cut, rounded_cut, batch.goff,
-                            node_cost_sum=_node_cost_sum(batch, node_cost, partition))
+    partition, cut, _ = T._kway_anneal_on_gpu(batch, K, cands, inv_temp, seed, int(max_descent_sweeps), terminals,
+                                              node_cost, large=large)
     cost_sum = (lambda part: None) if node_cost is None else (lambda part: _node_cost_sum(batch, node_cost, part))
     if parts is not None:
         parts.update(trained=best_S, rounded=rounded)
@@ -484,7 +452,8 @@ def _solve_batch(route: _Route, batch: GraphBatch, number_classes: int, terminal
     annealed_cut = None
     if tabu_iterations:
         # the annealing left its candidates in `cands`; the better of the two results per graph, chosen on the device
-        tabu_partition, tabu_cut = route.tabu(batch, K, cands.clone(), int(tabu_iterations), seed, terminals, *dec)[:2]
+        tabu_partition, tabu_cut = T._kway_tabu_on_gpu(batch, K, cands.clone(), int(tabu_iterations), T.TABU_TENURE, seed,
+                                                       terminals, node_cost)[:2]
         better = tabu_cut > cut
         sizes = (batch.goff[1:] - batch.goff[:-1]).to(torch.int64)
         rows = torch.repeat_interleave(better, sizes, output_size=batch.R)
@@ -494,8 +463,8 @@ def _solve_batch(route: _Route, batch: GraphBatch, number_classes: int, terminal
                             node_cost_sum=cost_sum(partition))
     # the balanced stage starts from the annealed candidates too (a copy: repaired into the bounds, then searched)
     iterations = 20 * int(batch.n_max) if balance_iterations is None else int(balance_iterations)
-    within, within_cut = route.balance(batch, K, cands.clone(), bounds[0], bounds[1], iterations, seed, terminals,
-                                       *dec)[:2]
+    within, within_cut = T._kway_balance_on_gpu(batch, K, cands.clone(), bounds[0], bounds[1], iterations, T.TABU_TENURE,
+                                                seed, terminals, node_cost)[:2]
     return MaxCutResult(within, within_cut, trained_cut, rounded_cut, batch.goff, annealed_cut, unconstrained_cut=cut,
                         node_cost_sum=cost_sum(within))
 
@@ -527,23 +496,13 @@ class QuboResult:
     result: MaxCutResult   # the max-cut run behind it: class 1 is x = 1, result.cut the objective -E
 
 
-def _edge_values(what: str, values, E: int) -> Optional[np.ndarray]:
+def _values(what: str, values, shape_name: str, count: int, default: float) -> np.ndarray:
+    """A door's per-edge or per-node values as float64 [count] (``None``: ``default`` everywhere): the shape, finite."""
     if values is None:
-        return None
-    v = values.detach().cpu().numpy() if isinstance(values, torch.Tensor) else np.asarray(values)
-    if v.ndim != 1 or v.shape[0] != E:
-        raise ValueError(f"{what} must be [E] = [{E}], got {tuple(v.shape)}")
-    if not np.all(np.isfinite(v.astype(np.float64))):
-        raise ValueError(f"{what} holds values that are not finite")
-    return v.astype(np.float64)
-
-
-def _node_values(what: str, values, rows: int) -> np.ndarray:
-    if values is None:
-        return np.zeros(rows, np.float64)
-    v = values.detach().cpu().numpy() if isinstance(values, torch.Tensor) else np.asarray(values)
-    if v.ndim != 1 or v.shape[0] != rows:
-        raise ValueError(f"{what} must be [R] = [{rows}], got {tuple(v.shape)}")
+        return np.full(count, default, np.float64)
+    v = _host_array(values)
+    if v.ndim != 1 or v.shape[0] != count:
+        raise ValueError(f"{what} must be [{shape_name}] = [{count}], got {tuple(v.shape)}")
     if not np.all(np.isfinite(v.astype(np.float64))):
         raise ValueError(f"{what} holds values that are not finite")
     return v.astype(np.float64)
@@ -551,13 +510,12 @@ def _node_values(what: str, values, rows: int) -> np.ndarray:
 
 def _door(edge_index, ptr, num_nodes):
     """(edge_index on the host, graph offsets [B + 1] int64) of a door's arguments."""
-    ei = edge_index.detach().cpu().numpy() if isinstance(edge_index, torch.Tensor) else np.asarray(edge_index)
+    ei = _host_array(edge_index)
     if ei.ndim != 2 or ei.shape[0] != 2:
         raise ValueError(f"edge_index must be [2, E], got {tuple(ei.shape)}")
     if (ptr is None) == (num_nodes is None):
         raise ValueError("pass exactly one of ptr (graph boundaries) and num_nodes (a single graph)")
-    goff = np.asarray([0, int(num_nodes)], np.int64) if ptr is None else (
-        ptr.detach().cpu().numpy() if isinstance(ptr, torch.Tensor) else np.asarray(ptr)).astype(np.int64)
+    goff = np.asarray([0, int(num_nodes)], np.int64) if ptr is None else _host_array(ptr).astype(np.int64)
     if goff.ndim != 1 or goff.size < 1:
         raise ValueError("ptr must be [B + 1]")
     return ei, goff
@@ -566,9 +524,9 @@ def _door(edge_index, ptr, num_nodes):
 def _solve_door(batch: GraphBatch, node_cost: np.ndarray, hidden_dim, epochs, learning_rate, loss, samples, anneal_sweeps,
                 max_descent_sweeps, seed, tabu_iterations=0, class_sizes=None, balance_iterations=None) -> MaxCutResult:
     loss = hip.loss_name(loss)
-    if batch.B and instance_too_large(batch.n_max, 2, loss):
-        raise ValueError(_TOO_LARGE.format(n=batch.n_max, K=2))
-    return _solve_batch(_small_route(), batch, 2, False, hidden_dim, epochs, learning_rate, loss, samples, anneal_sweeps,
+    if batch.B:
+        _refuse_small(batch.n_max, 2, loss)
+    return _solve_batch(_SMALL, batch, 2, False, hidden_dim, epochs, learning_rate, loss, samples, anneal_sweeps,
                         max_descent_sweeps, seed, tabu_iterations, class_sizes, balance_iterations,
                         node_cost=_check_node_cost(node_cost, batch.R, 2), abs_scale=True)
 
@@ -625,9 +583,8 @@ def solve_ising(edge_index, ptr=None, num_nodes: Optional[int] = None, coupling=
     ei, goff = _door(edge_index, ptr, num_nodes)
     class_sizes = _door_stages("solve_ising", goff, tabu_iterations, class_sizes, balance_iterations)
     E, R = ei.shape[1], int(goff[-1])
-    J = _edge_values("coupling", coupling, E)
-    h = _node_values("field", field, R)
-    J = np.ones(E, np.float64) if J is None else J
+    J = _values("coupling", coupling, "E", E, 1.0)
+    h = _values("field", field, "R", R, 0.0)
     src, dst = ei[0].astype(np.int64), ei[1].astype(np.int64)
     once = src < dst if pairs == "both" else src != dst   # every undirected edge once; a self-loop is no i < j
     B = goff.size - 1
@@ -676,9 +633,8 @@ def solve_qubo(edge_index, ptr=None, num_nodes: Optional[int] = None, quadratic=
         class_sizes = _cardinality_sizes(cardinality, goff)
     class_sizes = _door_stages("solve_qubo", goff, tabu_iterations, class_sizes, balance_iterations)
     E, R = ei.shape[1], int(goff[-1])
-    q = _edge_values("quadratic", quadratic, E)
-    a = _node_values("linear", linear, R)
-    q = np.ones(E, np.float64) if q is None else q
+    q = _values("quadratic", quadratic, "E", E, 1.0)
+    a = _values("linear", linear, "R", R, 0.0)
     batch = GraphBatch.from_edge_index(edge_index, ptr, num_nodes, (0.5 * q).astype(np.float32), pairs=pairs)
     half = torch.zeros(batch.R, dtype=torch.float32, device=batch.device)
     if batch.R:

@@ -228,12 +228,13 @@ def stages_of_the_search(n, samples, sweeps, descent):
            "max_descent_sweeps": descent, "colour_classes": batch.refine_classes(K)}
     for attempt in ("first call ms", "second call ms"):
         ws = TN._large_search_workspace(batch, K, samples + 2)
-        (rnd, _cut, _e, _s), t_round = timed(lambda: TN._large_round_on_gpu(batch, P, 0))
+        (rnd, _cut, _e, _s), t_round = timed(lambda: TN._round_on_gpu(batch, P, 0, large=True))
         (_ba, best_cut, _ca, assign_all), t_sample = timed(
-            lambda: TN._large_sample_on_gpu(batch, P, samples, 5, [0], True, workspace=ws))
+            lambda: TN._kway_sample_on_gpu(batch, P, samples, 5, [0], True, large=True, workspace=ws))
         cands = torch.cat([S.reshape(1, -1), rnd.reshape(1, -1), assign_all]).contiguous()
         (_fa, found_cut, found_idx), t_anneal = timed(
-            lambda: TN._large_anneal_on_gpu(batch, K, cands, TN.anneal_schedule(sweeps), 3, descent, workspace=ws))
+            lambda: TN._kway_anneal_on_gpu(batch, K, cands, TN.anneal_schedule(sweeps), 3, descent, large=True,
+                                           workspace=ws))
         rec[attempt] = {"rounding at descent 0": t_round, "sampler": t_sample, "annealing": t_anneal}
         rec["workspace_bytes"] = int(ws.numel())
         rec["rounded_cut"], rec["best_sample_cut"] = float(_cut.item()), float(best_cut.item())

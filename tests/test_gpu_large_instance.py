@@ -394,13 +394,13 @@ def test_solve_large(pkg, K):
         eng.adam_step(2e-2)
         eng.keep_best(S, losses, epoch)
     P, _S, _l = eng.forward(1.0, loss="expected_cut")
-    r_assign, r_cut, _, _ = T._large_round_on_gpu(batch, P, 0, False)
+    r_assign, r_cut, _, _ = T._round_on_gpu(batch, P, 0, False, large=True)
     best = eng.best_S.to(torch.int8).reshape(1, -1)
-    _, t_cut, _ = T._large_anneal_on_gpu(batch, K, best.clone(), np.zeros(0, np.float32), 0, 0, terminals=False)
-    samples = T._large_sample_on_gpu(batch, P, 6, 4, range(batch.B), True, terminals=False)[3]
+    _, t_cut, _ = T._kway_anneal_on_gpu(batch, K, best.clone(), np.zeros(0, np.float32), 0, 0, terminals=False, large=True)
+    samples = T._kway_sample_on_gpu(batch, P, 6, 4, range(batch.B), True, terminals=False, large=True)[3]
     cands = torch.cat([best, r_assign.reshape(1, -1), samples]).contiguous()
     inv_temp = T.anneal_schedule(10, scale=T._mean_edge_weight(batch))
-    h_part, h_cut, _ = T._large_anneal_on_gpu(batch, K, cands, inv_temp, 4, 100, terminals=False)
+    h_part, h_cut, _ = T._kway_anneal_on_gpu(batch, K, cands, inv_temp, 4, 100, terminals=False, large=True)
     for got, want in ((h_part, res.partition), (h_cut, res.cut), (t_cut, res.trained_cut), (r_cut, res.rounded_cut)):
         assert got.cpu().numpy().tobytes() == want.cpu().numpy().tobytes()
     # a batch built from handles holds the same bytes as the one built on the device: the same result
