@@ -231,14 +231,29 @@ def _api() -> dict:
     }
 
 
+def _sdp_api() -> dict:
+    """name -> (restype, argtypes) of every symbol include/gcnmaxcut_sdp.h declares (the semidefinite relaxation: a
+    header and a table of its own, so ``SYMBOLS`` stays the mirror of include/gcnmaxcut.h)."""
+    vp, i32, sz, i = C.c_void_p, C.c_int32, C.c_size_t, C.c_int
+    B = C.POINTER(GmcBatch)
+    return {
+        "gmc_sdp_workspace_bytes": (sz, [B, i32]),
+        "gmc_sdp_relax_f32": (i, [B, i32, i32, vp, vp, vp, vp, i32, vp, i32, i32, vp, vp, vp, sz, vp]),
+        "gmc_sdp_round_f32": (i, [B, i32, i32, vp, vp, i32, i32, vp, vp]),
+    }
+
+
 _API = _api()
 SYMBOLS = tuple(_API)
+_SDP_API = _sdp_api()
+SDP_SYMBOLS = tuple(_SDP_API)
+SDP_RANKS = (16, 32, 64)   # the ranks gmc_sdp_relax_f32 / gmc_sdp_round_f32 take
 
 _lib: Optional[C.CDLL] = None
 
 
 def _declare(lib: C.CDLL) -> None:
-    for name, (restype, argtypes) in _API.items():
+    for name, (restype, argtypes) in list(_API.items()) + list(_SDP_API.items()):
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = restype, argtypes
     lib.gmc_debug_set_device_cus.argtypes = [C.c_int]   # test hook (not part of gcnmaxcut.h)

@@ -646,3 +646,171 @@ def solve_qubo(edge_index, ptr=None, num_nodes: Optional[int] = None, quadratic=
     res = _solve_door(batch, node_cost, hidden_dim, epochs, learning_rate, loss, samples, anneal_sweeps,
                       max_descent_sweeps, seed, tabu_iterations, class_sizes, balance_iterations)
     return QuboResult(res.partition.to(torch.int8), -res.cut, res.ptr, res)
+
+
+# ---- the semidefinite relaxation (Goemans-Williamson): no model, no training ---------------------
+@dataclass
+class SdpResult:
+    """What :func:`solve_sdp` returns: device tensors, graph g owning rows ``ptr[g] .. ptr[g+1]-1`` of ``partition``."""
+    partition: torch.Tensor       # [R] int32: the class of every node
+    cut: torch.Tensor             # [B] float32: the cut of ``partition`` (with node_cost: the objective cut - cost)
+    rounded_cut: torch.Tensor     # [B] float32: the best hyperplane's, before any search
+    relaxed_value: torch.Tensor   # [B] float32: the relaxed objective after the last sweep - an upper bound on the optimum
+    #                               only at the relaxation's optimum, not a certificate
+    ptr: torch.Tensor             # [B + 1] int32
+    node_cost_sum: Optional[torch.Tensor] = None   # [B] float32, with node_cost only: sum_v node_cost[v][partition_v]
+
+
+def _sdp_rank(rank, n_max: int) -> int:
+    if rank is None:
+        need = np.sqrt(2.0 * max(int(n_max), 1)) + 1.0
+        return next((r for r in hip.SDP_RANKS if r >= need), hip.SDP_RANKS[-1])
+    if int(rank) not in hip.SDP_RANKS:
+        raise ValueError(f"rank must be one of {hip.SDP_RANKS} (or None), got {rank}")
+    return int(rank)
+
+
+def _sdp_cost(batch: GraphBatch, node_cost) -> Optional[torch.Tensor]:
+    if node_cost is None:
+        return None
+    return _check_node_cost(node_cost, batch.R, 2).to(batch.device).contiguous()
+
+
+def _sdp_keys(batch: GraphBatch, seed: int) -> torch.Tensor:
+    from .Testing import TestingNeuralNetwork as T
+    keys = T.sample_keys(int(seed) & T._M64, range(batch.B))
+    return torch.from_numpy(keys.view(np.int64)).to(batch.device)
+
+
+def _sdp_relax_keys(batch: GraphBatch, gkey: Optional[torch.Tensor], rank: int, sweeps: int, terminals: bool,
+                    node_cost: Optional[torch.Tensor], V: Optional[torch.Tensor]):
+    """gmc_sdp_relax_f32 with the graphs' keys given ([B] int64 on the device: the uint64 words; None with ``V``)."""
+    from .Testing import TestingNeuralNetwork as T
+    if not 0 <= int(sweeps) < 1 << 31:
+        raise ValueError(f"sweeps must be in 0..2^31-1, got {sweeps}")
+    T._needs_terminals(batch, 2, terminals)
+    dev = batch.device
+    if V is None:
+        V = torch.empty((batch.R, rank), dtype=torch.float32, device=dev)
+        init = 1
+    else:
+        if not isinstance(V, torch.Tensor) or tuple(V.shape) != (batch.R, rank) or V.dtype != torch.float32:
+            raise ValueError(f"V must be a float32 tensor [{batch.R}, {rank}] (what sdp_relax returned)")
+        V = V.to(dev).contiguous().clone()
+        init = 0
+    value = torch.empty(batch.B, dtype=torch.float32, device=dev)
+    if batch.B == 0:
+        return V, value
+    lib = hip.load()
+    need = int(lib.gmc_sdp_workspace_bytes(batch.ref(), rank))
+    if need <= 0:
+        raise hip.HipExtensionError(f"gmc_sdp_workspace_bytes refused the batch (rank = {rank})")
+    ws = torch.empty(need, dtype=torch.uint8, device=dev)
+    order, cgoff, cptr = batch.refine_order(2, terminals)
+    p = hip.ptr
+    rc = lib.gmc_sdp_relax_f32(batch.ref(), rank, int(terminals), p(node_cost), p(order), p(cgoff), p(cptr),
+                               batch.refine_classes(2, terminals), p(gkey), init, int(sweeps), p(V), p(value), p(ws),
+                               ws.numel(), hip.stream())
+    hip.check(rc, "gmc_sdp_relax_f32")
+    return V, value
+
+
+def _sdp_round_keys(batch: GraphBatch, V: torch.Tensor, gkey: torch.Tensor, first_plane: int, planes: int,
+                    terminals: bool) -> torch.Tensor:
+    """gmc_sdp_round_f32: planes ``first_plane .. first_plane + planes - 1`` as [planes, R] int8."""
+    if V.dim() != 2 or V.shape[0] != batch.R or int(V.shape[1]) not in hip.SDP_RANKS or V.dtype != torch.float32:
+        raise ValueError(f"V must be a float32 tensor [{batch.R}, rank], rank one of {hip.SDP_RANKS}")
+    if planes < 0 or first_plane < 0 or first_plane + planes >= 1 << 31:
+        raise ValueError(f"planes and first_plane must be >= 0 and end below 2^31, got {planes}, {first_plane}")
+    assign = torch.empty((int(planes), batch.R), dtype=torch.int8, device=batch.device)
+    if batch.B == 0 or planes == 0:
+        return assign
+    V = V.to(batch.device).contiguous()
+    p = hip.ptr
+    rc = hip.load().gmc_sdp_round_f32(batch.ref(), int(V.shape[1]), int(terminals), p(V), p(gkey), int(first_plane),
+                                      int(planes), p(assign), hip.stream())
+    hip.check(rc, "gmc_sdp_round_f32")
+    return assign
+
+
+def sdp_relax(batch: GraphBatch, *, rank: Optional[int] = None, sweeps: int = 50, seed: int = 0, terminals: bool = False,
+              node_cost=None, V: Optional[torch.Tensor] = None):
+    """The low-rank semidefinite relaxation of max-cut (K = 2) of every graph of ``batch`` by the mixing method
+    (include/gcnmaxcut_sdp.h, ``gmc_sdp_relax_f32``): one unit vector of ``rank`` floats per node, ``sweeps`` sweeps of
+    ``v_i <- -normalize(sum_j w_ij v_j)`` over the colour classes.  Returns ``(V [R, rank], value [B])``, float32 on
+    the device; ``value`` is the relaxed objective ``1/2 sum_uv w_uv (1 - v_u . v_v)`` after the last sweep, which no
+    sweep lowers.  It is an upper bound on the optimum only at the relaxation's optimum, not a certificate.
+
+    ``rank``: 16, 32 or 64; ``None`` takes the smallest of them that is at least ``sqrt(2 n_max) + 1`` - the bound above
+    which the low-rank form has no spurious local optima - else 64: beyond 2,048 nodes rank 64 lies under that bound, and
+    the sweeps may then stop at a local optimum of the low-rank problem.  ``seed`` seeds the start (graph ``g`` of the
+    batch draws from ``sample_keys(seed, [g])``).  ``V``: a state to continue from instead (``sdp_relax(sweeps=a + b)``
+    equals ``sdp_relax(sweeps=a)`` followed by ``sdp_relax(sweeps=b, V=...)`` byte for byte; it is not modified).
+    ``terminals=True``: nodes 0 and 1 of every graph are fixed to classes 0 and 1.  ``node_cost`` [R, 2]: the objective
+    ``cut(S) - sum_v node_cost[v][S_v]`` as :func:`solve` takes it, relaxed along the reference direction."""
+    rank = _sdp_rank(rank, batch.n_max if batch.B else 1)
+    cost = _sdp_cost(batch, node_cost)
+    gkey = _sdp_keys(batch, seed) if V is None else None
+    return _sdp_relax_keys(batch, gkey, rank, sweeps, bool(terminals), cost, V)
+
+
+def sdp_round(batch: GraphBatch, V: torch.Tensor, planes: int = 200, seed: int = 0, terminals: bool = False) -> torch.Tensor:
+    """``planes`` random hyperplanes through the vectors ``V`` of :func:`sdp_relax` (``gmc_sdp_round_f32``): [planes, R]
+    int8 class bytes, class 0 on the side of the reference direction.  The normals are seeded by ``seed``; plane m's
+    bytes do not depend on ``planes``."""
+    return _sdp_round_keys(batch, V, _sdp_keys(batch, seed), 0, int(planes), bool(terminals))
+
+
+def solve_sdp_batch(batch: GraphBatch, *, rank: Optional[int] = None, sweeps: int = 50, planes: int = 200,
+                    anneal_sweeps: int = 100, max_descent_sweeps: int = 100, seed: int = 0, terminals: bool = False,
+                    node_cost=None) -> SdpResult:
+    """:func:`solve_sdp` on a ready batch (``node_cost`` rows = batch rows)."""
+    from .Testing import TestingNeuralNetwork as T
+    terminals = bool(terminals)
+    if planes < 1 or anneal_sweeps < 0 or max_descent_sweeps < 0:
+        raise ValueError(f"planes must be >= 1, anneal_sweeps and max_descent_sweeps >= 0, got {planes}, {anneal_sweeps}, "
+                         f"{max_descent_sweeps}")
+    large = bool(batch.B) and batch.n_max > hip.MAX_GRAPH_NODES
+    if large and node_cost is not None:
+        raise NotImplementedError("node_cost with a graph beyond hip.MAX_GRAPH_NODES nodes: the annealing for such graphs "
+                                  "(gmc_large_anneal_f32) takes no per-node costs")
+    cost = _sdp_cost(batch, node_cost)
+    V, value = sdp_relax(batch, rank=rank, sweeps=sweeps, seed=seed, terminals=terminals, node_cost=cost)
+    if batch.B == 0:
+        none = torch.empty(0, dtype=torch.float32, device=batch.device)
+        return SdpResult(torch.empty(0, dtype=torch.int32, device=batch.device), none, none.clone(), value, batch.goff,
+                         None if cost is None else none.clone())
+    cands = sdp_round(batch, V, int(planes), seed, terminals)
+    _, rounded_cut, _ = T._kway_anneal_on_gpu(batch, 2, cands.clone(), np.zeros(0, np.float32), 0, 0, terminals, cost,
+                                              large=large)   # scores and picks, moves nothing
+    inv_temp = T.anneal_schedule(int(anneal_sweeps), scale=_mean_abs_edge_weight(batch))
+    partition, cut, _ = T._kway_anneal_on_gpu(batch, 2, cands, inv_temp, seed, int(max_descent_sweeps), terminals, cost,
+                                              large=large)
+    return SdpResult(partition, cut, rounded_cut, value, batch.goff,
+                     None if cost is None else _node_cost_sum(batch, cost, partition))
+
+
+def solve_sdp(edge_index, ptr=None, num_nodes: Optional[int] = None, edge_weight=None, *, pairs: str = "both",
+              rank: Optional[int] = None, sweeps: int = 50, planes: int = 200, anneal_sweeps: int = 100,
+              max_descent_sweeps: int = 100, seed: int = 0, terminals: bool = False, node_cost=None) -> SdpResult:
+    """Max-cut (two classes) of every graph of a batch given as :func:`solve` takes it, without a model and without
+    training: the Goemans-Williamson route.
+
+    1. the batch, built on the GPU;
+    2. :func:`sdp_relax`: ``sweeps`` sweeps of the low-rank semidefinite relaxation at ``rank``;
+    3. :func:`sdp_round`: ``planes`` random hyperplanes, each a candidate partition; ``rounded_cut`` is the best of them;
+    4. the annealing launch of :func:`solve` over these candidates (``anneal_sweeps`` Metropolis sweeps, then at most
+       ``max_descent_sweeps`` sweeps of the local search; for a graph beyond ``hip.MAX_GRAPH_NODES`` nodes through
+       ``gmc_large_anneal_f32``), which scores and picks: ``cut >= rounded_cut``.
+
+    ``relaxed_value`` is the relaxation's objective after the last sweep.  At the relaxation's optimum it bounds the
+    optimum from above; after finitely many sweeps of a low-rank form it is below that optimum and is NOT a certificate.
+    ``node_cost`` [R, 2] has :func:`solve`'s meaning (every ``*_cut`` field is then the objective, ``relaxed_value`` its
+    relaxed form); with a graph beyond ``hip.MAX_GRAPH_NODES`` nodes it raises ``NotImplementedError``.  Signed weights
+    are taken (the annealing's temperature is in units of the mean absolute weight), but the 0.878 guarantee of the
+    hyperplane rounding holds for non-negative weights only."""
+    if node_cost is not None:
+        node_cost = _check_node_cost(node_cost, _rows_of(ptr, num_nodes), 2)
+    batch = GraphBatch.from_edge_index(edge_index, ptr, num_nodes, edge_weight, pairs=pairs)
+    return solve_sdp_batch(batch, rank=rank, sweeps=sweeps, planes=planes, anneal_sweeps=anneal_sweeps,
+                           max_descent_sweeps=max_descent_sweeps, seed=seed, terminals=terminals, node_cost=node_cost)
