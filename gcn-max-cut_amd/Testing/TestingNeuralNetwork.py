@@ -24,6 +24,8 @@ across generations (``gmc_kway_evolve_f32``): children of two class-aligned pare
 ``kway_tabu_search`` and ``search_dataset(..., tabu_iterations=I)`` (extension) run a one-flip tabu search over
 partitions (``gmc_kway_tabu_f32``): the best single move every iteration, a recency ban with aspiration, the best state
 kept.  Off by default.
+``kway_tempering`` (extension) runs parallel tempering over partitions of a graph (``gmc_kway_temper_f32``,
+include/gcnmaxcut_temper.h): the annealing's sweep on ladders of fixed temperatures with replica exchange between rounds.
 ``large_conditional_rounding``, ``large_local_search``, ``round_large_dataset``, ``large_sampling_optimization``,
 ``large_annealing`` and ``search_large_dataset`` (extension) are the same rounding, local search, sampler and annealing
 for graphs of up to ``hip.LARGE_MAX_GRAPH_NODES`` nodes (``gmc_large_round_conditional_f32``,
@@ -999,6 +1001,107 @@ def kway_evolution(partitions, graph, number_classes: int, generations: int = EV
                                                                   seed, max_descent_sweeps)
     return (best_assign.cpu().tolist(), _as_number(best_cut.item()),
             [_as_number(c) for c in history[:, 0].cpu().tolist()])
+
+
+# The tempering stage's defaults are PROVISIONAL: the annealing's own temperature range as a
+# ladder of 8 rungs, 50 rounds of 4 sweeps - a starting point, not the outcome of the grid described there.
+TEMPER_ROUNDS = 50
+TEMPER_ROUND_SWEEPS = 4
+TEMPER_RUNGS = 8
+TEMPER_T_HOT = 1.5
+TEMPER_T_COLD = 0.15
+
+
+def temper_ladder(rungs: int, t_hot: float = TEMPER_T_HOT, t_cold: float = TEMPER_T_COLD, scale: float = 1.0) -> np.ndarray:
+    """float32 ``1 / T_r`` of a geometric ladder ``T_r = scale * t_hot * (t_cold / t_hot) ** (r / max(rungs-1, 1))``,
+    rung 0 the hottest (float64, rounded once; one rung: ``t_hot``).  ``scale``: the mean edge weight of the batch, the
+    mean absolute weight for signed weights (1 for unit weights)."""
+    if not 1 <= int(rungs) <= hip.TEMPER_MAX_RUNGS:
+        raise ValueError(f"rungs must be in 1..{hip.TEMPER_MAX_RUNGS}, got {rungs}")
+    if not (t_hot > 0 and t_cold > 0 and scale > 0):
+        raise ValueError("t_hot, t_cold and scale must be > 0")
+    r = np.arange(int(rungs), dtype=np.float64)
+    temps = float(scale) * float(t_hot) * (float(t_cold) / float(t_hot)) ** (r / max(int(rungs) - 1, 1))
+    return (1.0 / temps).astype(np.float32)
+
+
+def _temper_arguments(what: str, cands: int, rounds: int, round_sweeps: int, rungs: int, max_descent_sweeps: int = 0) -> None:
+    """The checks the tempering's callers share."""
+    if not 1 <= int(rungs) <= hip.TEMPER_MAX_RUNGS:
+        raise ValueError(f"{what}: rungs must be in 1..{hip.TEMPER_MAX_RUNGS}, got {rungs}")
+    if cands < 1 or cands % int(rungs):
+        raise ValueError(f"{what}: {cands} candidates do not fill ladders of {rungs} rungs (rungs must divide the count)")
+    if rounds < 0 or max_descent_sweeps < 0 or round_sweeps < (1 if rounds else 0):
+        raise ValueError(f"{what}: rounds and max_descent_sweeps must be >= 0 and round_sweeps >= 1, got {rounds}, "
+                         f"{max_descent_sweeps} and {round_sweeps}")
+    if int(rounds) * int(round_sweeps) >= 1 << 20:
+        raise ValueError(f"{what}: rounds * round_sweeps must be below 2^20")
+
+
+def _kway_temper_on_gpu(batch: GraphBatch, K: int, state: torch.Tensor, ladder: np.ndarray, rounds: int,
+                        round_sweeps: int, seed: int, terminals: bool = True, node_cost=None):
+    """Parallel tempering (gmc_kway_temper_f32) over the walkers state [cands, R] int8, in place: ``rounds`` rounds of
+    ``round_sweeps`` sweeps on ladders of ``len(ladder)`` inverse temperatures.  Returns the best states [cands, R] int8,
+    their scores [B, cands] and best_round, rung and swaps [B, cands] int32.  ``node_cost`` [R, K]: moves and scores
+    follow cut minus cost."""
+    _needs_terminals(batch, K, terminals)
+    node_cost = _cost_tensor(batch, K, node_cost)
+    dev = batch.device
+    cands, rungs = int(state.shape[0]), int(len(ladder))
+    _temper_arguments("the tempering", cands, int(rounds), int(round_sweeps), rungs)
+    order, cgoff, cptr = batch.refine_order(K, terminals)
+    lad = torch.from_numpy(np.ascontiguousarray(ladder, np.float32)).to(dev)
+    levels = torch.from_numpy(anneal_levels()).to(dev)
+    best = torch.empty_like(state)
+    best_score = torch.empty((batch.B, cands), dtype=torch.float32, device=dev)
+    best_round, rung, swaps = (torch.empty((batch.B, cands), dtype=torch.int32, device=dev) for _ in range(3))
+    lib, p = hip.load(), hip.ptr
+    ws = torch.empty(max(int(lib.gmc_kway_temper_workspace_bytes(batch.ref(), cands)), 16), dtype=torch.uint8, device=dev)
+    rc = lib.gmc_kway_temper_f32(batch.ref(), K, int(bool(terminals)), p(node_cost), p(order), p(cgoff), p(cptr), cands,
+                                 rungs, p(lad), int(rounds), int(round_sweeps), p(levels), int(seed) & _M64, p(state),
+                                 p(best), p(best_score), p(best_round), p(rung), p(swaps), p(ws), ws.numel(), hip.stream())
+    hip.check(rc, "gmc_kway_temper_f32")
+    return best, best_score, best_round, rung, swaps
+
+
+def kway_tempering(partitions, graph, number_classes: int, rounds: int = TEMPER_ROUNDS,
+                   round_sweeps: int = TEMPER_ROUND_SWEEPS, rungs: int = TEMPER_RUNGS, t_hot: float = TEMPER_T_HOT,
+                   t_cold: float = TEMPER_T_COLD, seed: int = 0, max_descent_sweeps: int = 100, terminals: bool = True,
+                   node_cost=None) -> Tuple[List[int], Any, Dict[str, Any]]:
+    """Parallel tempering (replica exchange) from ``partitions`` [cands, n] of one graph into ``number_classes`` = 2..8
+    classes (extension, include/gcnmaxcut_temper.h ``gmc_kway_temper_f32``): the partitions are walkers of the
+    annealing's Metropolis sweep on ``cands / rungs`` ladders of ``rungs`` fixed temperatures from ``t_hot`` to ``t_cold``
+    (:func:`temper_ladder`, in units of the graph's mean absolute edge weight); after every round of ``round_sweeps``
+    sweeps neighbouring rungs exchange their temperatures by the Metropolis rule, so a walker frozen in a poor basin can
+    climb to a hot rung and leave it.  The best state every walker passed through is kept, the K-class local search
+    descends from each and the best is returned.  ``rungs`` must divide the number of partitions.  Nodes 0..K-1 keep
+    their classes (``terminals=False``: every node may move); reproducible from ``seed``; ``node_cost`` [n, K]: the
+    objective ``cut - sum_v node_cost[v][class_v]``.  Returns the assignment, its cut (objective) and a dict with
+    ``best_round``, ``rung``, ``swaps`` and ``scores`` (per partition: the round that found its best state, its final
+    rung, the exchanges it took part in, its best score before the descent).  The defaults are provisional, see
+    DESIGN.md section 39."""
+    K = _search_classes("kway_tempering", number_classes)
+    parts = np.asarray(partitions, dtype=np.int64)
+    n = graph.number_of_nodes()
+    if parts.ndim != 2 or parts.shape[0] < 1 or parts.shape[1] != n:
+        raise ValueError(f"partitions must be [cands, {n}] with cands >= 1, got {tuple(parts.shape)}")
+    _check_graph_size(n, K, terminals)
+    if int(parts.min()) < 0 or int(parts.max()) > K - 1:
+        raise ValueError(f"partitions holds a class outside 0..{K - 1} (number_classes = {K})")
+    _temper_arguments("kway_tempering", parts.shape[0], rounds, round_sweeps, rungs, max_descent_sweeps)
+    cost = _graph_cost("kway_tempering", node_cost, n, K)
+    dev = hip.require_gpu()
+    batch = _graph_batch(graph, dev)
+    from ..maxcut import _mean_abs_edge_weight
+    ladder = temper_ladder(rungs, t_hot, t_cold, _mean_abs_edge_weight(batch))
+    state = torch.from_numpy(parts.astype(np.int8)).to(dev)
+    best, scores, best_round, rung, swaps = _kway_temper_on_gpu(batch, K, state, ladder, rounds, round_sweeps, seed,
+                                                                terminals, cost)
+    best_assign, best_cut, _ = _kway_anneal_on_gpu(batch, K, best, np.zeros(0, np.float32), 0, max_descent_sweeps,
+                                                   terminals, cost)
+    info = {"best_round": best_round[0].cpu().tolist(), "rung": rung[0].cpu().tolist(), "swaps": swaps[0].cpu().tolist(),
+            "scores": [_as_number(c) for c in scores[0].cpu().tolist()]}
+    return best_assign.cpu().tolist(), _as_number(best_cut.item()), info
 
 
 def test_single_graph(model, dgl_graph, adjacency_matrix, nx_graph, terminals: List[int],

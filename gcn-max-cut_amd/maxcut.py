@@ -37,6 +37,10 @@ _NO_COST_FIXED = ("node_cost with fixed: " + _BATCH_DOOR + " - it carries the fr
                   "reports the pinned nodes' as fixed_cost")
 _NO_COST_LARGE = ("node_cost on the large route: the multi-workgroup head and decoders of solve_large take no per-node "
                   "costs - maxcut.solve has them for graphs within its bound")
+_NO_TEMPER = ("the tempering stage keeps a graph's state in one workgroup, as the tabu stage does: solve_large does not have "
+              "it (tempering_rounds must be 0)")
+_TEMPER_ALONE = ("tempering_rounds > 0 together with {other}: the tempering stage is not combined with the tabu or the "
+                 "balanced stage - pass one of tempering_rounds and {other}")
 _BEYOND_LARGE = "a graph of {n} nodes is beyond the {bound} nodes of the per-graph models' large sequence (solve_large)"
 
 
@@ -48,7 +52,8 @@ class MaxCutResult:
     trained_cut: torch.Tensor   # [B] float32: the cut of the best partition training saw (``best_S``)
     rounded_cut: torch.Tensor   # [B] float32: the cut of the conditional rounding of the last P
     ptr: torch.Tensor           # [B + 1] int32
-    annealed_cut: Optional[torch.Tensor] = None   # [B] float32, with tabu_iterations > 0 only: the cut the annealing reached
+    annealed_cut: Optional[torch.Tensor] = None   # [B] float32, with tabu_iterations > 0 or tempering_rounds > 0 only: the
+    #                                               cut the annealing reached
     fixed_cut: Optional[torch.Tensor] = None      # [B] float32, with fixed only: the weight of the edges between pinned
     #                                               nodes of different classes (a constant of every partition)
     unconstrained_cut: Optional[torch.Tensor] = None   # [B] float32, with class_sizes only: what ``cut`` would have been
@@ -87,7 +92,8 @@ def solve(edge_index, ptr=None, num_nodes: Optional[int] = None, edge_weight=Non
           terminals: bool = False, pairs: str = "both", hidden_dim: int, epochs: int, learning_rate: float,
           loss: str = "expected_cut", samples: int = 32, anneal_sweeps: int = 100, max_descent_sweeps: int = 100,
           seed: int = 0, tabu_iterations: int = 0, fixed=None, class_sizes=None,
-          balance_iterations: Optional[int] = None, node_cost=None) -> MaxCutResult:
+          balance_iterations: Optional[int] = None, node_cost=None, tempering_rounds: int = 0,
+          tempering_sweeps: int = 4, tempering_rungs: int = 8) -> MaxCutResult:
     """Max-K-cut of every graph of a batch given as ``edge_index`` [2, E] (with ``ptr`` [B+1], or ``num_nodes`` for one
     graph, ``edge_weight`` and ``pairs`` as ``GraphBatch.from_edge_index`` takes them).
 
@@ -105,6 +111,14 @@ def solve(edge_index, ptr=None, num_nodes: Optional[int] = None, edge_weight=Non
        annealed candidates.  Per graph ``partition`` / ``cut`` are then the better of the annealed and the tabu result
        by their recounted cuts, chosen on the device, and ``annealed_cut`` holds the annealed one: ``cut >=
        annealed_cut``.  The default 0 launches nothing more and leaves ``annealed_cut`` None.
+       With ``tempering_rounds > 0`` only, in the tabu stage's place: one call of the tempering stage
+       (``gmc_kway_temper_f32``, ``Testing.kway_tempering``: ``tempering_rounds`` rounds of ``tempering_sweeps`` Metropolis
+       sweeps on ladders of ``tempering_rungs`` fixed temperatures with replica exchange between the rounds, seeded by
+       ``seed``) on a copy of the first ``tempering_rungs * (candidates // tempering_rungs)`` annealed candidates, then
+       the local search from every walker's best state.  ``partition`` / ``cut`` and ``annealed_cut`` are chosen and
+       filled exactly as for the tabu stage: ``cut >= annealed_cut``.  Fewer candidates (``samples + 2``) than
+       ``tempering_rungs`` raise ``ValueError``; together with ``tabu_iterations > 0`` or ``class_sizes`` it raises
+       ``NotImplementedError``.  The default 0 launches nothing more and changes no byte of the result.
     6. with ``class_sizes`` only: one call of the balanced stage (``gmc_kway_balance_f32``,
        ``Testing.kway_balanced_search``; ``balance_iterations`` iterations per candidate, ``None``: 20 times the
        largest graph's nodes; seeded by ``seed``) on a copy of the annealed candidates, which it first repairs into the
@@ -150,6 +164,7 @@ def solve(edge_index, ptr=None, num_nodes: Optional[int] = None, edge_weight=Non
     loss = hip.loss_name(loss)
     _check_fixed(fixed, terminals, K)
     _check_sizes(class_sizes, balance_iterations, fixed)
+    tempering = _check_tempering(tempering_rounds, tempering_sweeps, tempering_rungs, tabu_iterations, class_sizes, samples)
     if node_cost is not None:
         node_cost = _check_node_cost(node_cost, _rows_of(ptr, num_nodes), K, tabu_iterations, class_sizes, fixed)
     if ptr is not None:   # judged before anything is built: the sizes are all it takes
@@ -166,17 +181,19 @@ def solve(edge_index, ptr=None, num_nodes: Optional[int] = None, edge_weight=Non
     batch = GraphBatch.from_edge_index(edge_index, ptr, num_nodes, edge_weight, pairs=pairs)
     if node_cost is not None:   # (checked above, once: no tabu, sizes or pins come with it)
         return _solve_batch(_SMALL, batch, K, terminals, hidden_dim, epochs, learning_rate, loss, samples,
-                            anneal_sweeps, max_descent_sweeps, seed, node_cost=node_cost)
+                            anneal_sweeps, max_descent_sweeps, seed, node_cost=node_cost, tempering=tempering)
     return solve_batch(batch, number_classes=K, terminals=terminals, hidden_dim=hidden_dim, epochs=epochs,
                        learning_rate=learning_rate, loss=loss, samples=samples, anneal_sweeps=anneal_sweeps,
                        max_descent_sweeps=max_descent_sweeps, seed=seed, tabu_iterations=tabu_iterations, fixed=fixed,
-                       class_sizes=class_sizes, balance_iterations=balance_iterations)
+                       class_sizes=class_sizes, balance_iterations=balance_iterations, tempering_rounds=tempering_rounds,
+                       tempering_sweeps=tempering_sweeps, tempering_rungs=tempering_rungs)
 
 
 def solve_batch(batch: GraphBatch, *, number_classes: int = 2, terminals: bool = False, hidden_dim: int, epochs: int,
                 learning_rate: float, loss: str = "expected_cut", samples: int = 32, anneal_sweeps: int = 100,
                 max_descent_sweeps: int = 100, seed: int = 0, tabu_iterations: int = 0, fixed=None, class_sizes=None,
-                balance_iterations: Optional[int] = None, node_cost=None) -> MaxCutResult:
+                balance_iterations: Optional[int] = None, node_cost=None, tempering_rounds: int = 0,
+                tempering_sweeps: int = 4, tempering_rungs: int = 8) -> MaxCutResult:
     """Steps 2 to 6 of :func:`solve` on a ready batch - one built on the device or one built from handles: the batches
     hold the same bytes, so the results do too.  ``fixed``: as :func:`solve`, with row ids of ``batch``;
     ``class_sizes``, ``balance_iterations`` and ``node_cost`` (rows = batch rows): as :func:`solve`.
@@ -187,20 +204,23 @@ def solve_batch(batch: GraphBatch, *, number_classes: int = 2, terminals: bool =
     ``annealed_cut`` and ``unconstrained_cut`` are objectives like every other ``*_cut`` field; ``node_cost_sum`` is the
     cost of the returned ``partition``.  With ``fixed``, a free node's cost row goes to its contracted row, the K
     super-nodes get zero rows, ``fixed_cost`` [B] holds the cost of each graph's pinned nodes, and every reported value
-    is a recount of the lifted partition on the original batch with the original cost."""
+    is a recount of the lifted partition on the original batch with the original cost.  ``tempering_rounds``,
+    ``tempering_sweeps`` and ``tempering_rungs``: as :func:`solve`; the stage takes ``node_cost`` and ``fixed``."""
     _check_sizes(class_sizes, balance_iterations, fixed)
+    tempering = _check_tempering(tempering_rounds, tempering_sweeps, tempering_rungs, tabu_iterations, class_sizes, samples)
     if node_cost is not None:
         node_cost = _check_node_cost(node_cost, batch.R, int(number_classes))
     return _solve_fixed(_SMALL, batch, fixed, number_classes, terminals, hidden_dim, epochs, learning_rate, loss,
                         samples, anneal_sweeps, max_descent_sweeps, seed, tabu_iterations, class_sizes,
-                        balance_iterations, node_cost=node_cost)
+                        balance_iterations, node_cost=node_cost, tempering=tempering)
 
 
 def solve_large(edge_index, ptr=None, num_nodes: Optional[int] = None, edge_weight=None, *, number_classes: int = 2,
                 terminals: bool = False, pairs: str = "both", hidden_dim: int, epochs: int, learning_rate: float,
                 loss: str = "expected_cut", samples: int = 32, anneal_sweeps: int = 100, max_descent_sweeps: int = 100,
                 seed: int = 0, tabu_iterations: int = 0, fixed=None, class_sizes=None,
-                balance_iterations: Optional[int] = None, node_cost=None) -> MaxCutResult:
+                balance_iterations: Optional[int] = None, node_cost=None, tempering_rounds: int = 0,
+                tempering_sweeps: int = 4, tempering_rungs: int = 8) -> MaxCutResult:
     """:func:`solve` for graphs of up to ``hip.LARGE_MAX_GRAPH_NODES`` (2^20) nodes: the same arguments, steps and
     result, with ``engine.LargeInstanceEngine`` (gmc_inst_large_*) as the trainer and the large decoders (one rounding,
     one sampler and one annealing call of gmc_large_*_t_f32; several workgroups share a graph).  It takes small graphs
@@ -212,9 +232,12 @@ def solve_large(edge_index, ptr=None, num_nodes: Optional[int] = None, edge_weig
     workgroup, so this route does not have it: ``tabu_iterations`` is taken for the sake of one signature and anything
     but 0 raises ``NotImplementedError``.  So are ``class_sizes`` and ``balance_iterations``: the balanced stage is the
     tabu kernel's sibling, and ``class_sizes`` other than ``None`` raises ``NotImplementedError``.  ``node_cost`` other
-    than ``None`` raises it too: the large head and decoders take no per-node costs."""
+    than ``None`` raises it too: the large head and decoders take no per-node costs.  And so does
+    ``tempering_rounds`` other than 0: the tempering stage is a one-workgroup kernel as well."""
     if node_cost is not None:
         raise NotImplementedError(_NO_COST_LARGE)
+    if tempering_rounds:
+        raise NotImplementedError(_NO_TEMPER)
     if tabu_iterations:
         raise NotImplementedError(_NO_TABU)
     if class_sizes is not None:
@@ -233,12 +256,15 @@ def solve_large_batch(batch: GraphBatch, *, number_classes: int = 2, terminals: 
                       epochs: int, learning_rate: float, loss: str = "expected_cut", samples: int = 32,
                       anneal_sweeps: int = 100, max_descent_sweeps: int = 100, seed: int = 0,
                       tabu_iterations: int = 0, fixed=None, class_sizes=None,
-                      balance_iterations: Optional[int] = None, node_cost=None) -> MaxCutResult:
+                      balance_iterations: Optional[int] = None, node_cost=None, tempering_rounds: int = 0,
+                      tempering_sweeps: int = 4, tempering_rungs: int = 8) -> MaxCutResult:
     """:func:`solve_batch` through ``engine.LargeInstanceEngine`` and the large decoders: steps 2 to 4 of
     :func:`solve_large` on a ready batch (``tabu_iterations``, ``class_sizes``: as :func:`solve_large`; ``fixed``: as
-    :func:`solve_batch`; ``node_cost``: as :func:`solve_large`)."""
+    :func:`solve_batch`; ``node_cost`` and ``tempering_rounds``: as :func:`solve_large`)."""
     if node_cost is not None:
         raise NotImplementedError(_NO_COST_LARGE)
+    if tempering_rounds:
+        raise NotImplementedError(_NO_TEMPER)
     if class_sizes is not None:
         raise NotImplementedError(_NO_BALANCE)
     return _solve_fixed(_LARGE, batch, fixed, number_classes, terminals, hidden_dim, epochs, learning_rate, loss,
@@ -301,6 +327,27 @@ def _check_sizes(class_sizes, balance_iterations, fixed) -> None:
                          "counts nodes, not node weights - pass one of the two")
 
 
+def _check_tempering(rounds, sweeps, rungs, tabu_iterations=0, class_sizes=None, samples: Optional[int] = None):
+    """The argument errors of the tempering keywords, raised before anything is built; returns (rounds, sweeps, rungs),
+    or None when the stage is off (``rounds == 0``: the other two are then not looked at)."""
+    if not 0 <= int(rounds) < 1 << 20:
+        raise ValueError(f"tempering_rounds must be in 0..2^20-1, got {rounds}")
+    if not int(rounds):
+        return None
+    if tabu_iterations:
+        raise NotImplementedError(_TEMPER_ALONE.format(other="tabu_iterations > 0"))
+    if class_sizes is not None:
+        raise NotImplementedError(_TEMPER_ALONE.format(other="class_sizes"))
+    if not 1 <= int(rungs) <= hip.TEMPER_MAX_RUNGS:
+        raise ValueError(f"tempering_rungs must be in 1..{hip.TEMPER_MAX_RUNGS}, got {rungs}")
+    if int(sweeps) < 1 or int(rounds) * int(sweeps) >= 1 << 20:
+        raise ValueError(f"tempering_sweeps must be >= 1 and tempering_rounds * tempering_sweeps below 2^20, got {sweeps}")
+    if samples is not None and int(samples) >= 0 and int(samples) + 2 < int(rungs):
+        raise ValueError(f"the tempering stage needs at least tempering_rungs = {rungs} candidates, and samples + 2 = "
+                         f"{int(samples) + 2} are annealed")
+    return int(rounds), int(sweeps), int(rungs)
+
+
 def _size_bounds(class_sizes, sizes, K: int, terminals: bool):
     from .Testing import TestingNeuralNetwork as T
     return T.class_size_bounds("solve", class_sizes, sizes, K, terminals)
@@ -314,7 +361,7 @@ def _mean_abs_edge_weight(batch: GraphBatch) -> float:
 
 
 def _solve_fixed(route: "_Route", batch: GraphBatch, fixed, number_classes: int, terminals: bool, *args,
-                 node_cost: Optional[torch.Tensor] = None) -> MaxCutResult:
+                 node_cost: Optional[torch.Tensor] = None, tempering: Optional[tuple] = None) -> MaxCutResult:
     """:func:`_solve_batch`, or with ``fixed``: contract, solve the contracted batch with its super-nodes as terminals, lift,
     and recount every reported cut on the original batch (the route's annealing call with zero sweeps and no terminals
     moves nothing and scores: the bits every other decoder reports for those bytes).  The route is chosen by the
@@ -323,7 +370,7 @@ def _solve_fixed(route: "_Route", batch: GraphBatch, fixed, number_classes: int,
     free rows' costs go to the contracted batch (``Contraction.contract_cost``), the recount is the annealing's scoring
     call with the ORIGINAL cost on the original batch, and ``fixed_cost`` holds the pinned nodes' share."""
     if fixed is None:
-        return _solve_batch(route, batch, number_classes, terminals, *args, node_cost=node_cost)
+        return _solve_batch(route, batch, number_classes, terminals, *args, node_cost=node_cost, tempering=tempering)
     K = int(number_classes)
     _check_fixed(fixed, bool(terminals), K)
     from .Testing import TestingNeuralNetwork as T
@@ -336,7 +383,7 @@ def _solve_fixed(route: "_Route", batch: GraphBatch, fixed, number_classes: int,
     if node_cost is not None:
         node_cost = node_cost.to(batch.device)
         cost, fixed_cost = ct.contract_cost(node_cost, batch.goff)
-    res = _solve_batch(route, ct.batch, K, True, *args, parts=parts, node_cost=cost)
+    res = _solve_batch(route, ct.batch, K, True, *args, parts=parts, node_cost=cost, tempering=tempering)
     no_sweeps = np.zeros(0, np.float32)
 
     def recount(partition):
@@ -385,11 +432,12 @@ def _solve_batch(route: _Route, batch: GraphBatch, number_classes: int, terminal
                  learning_rate: float, loss: str, samples: int, anneal_sweeps: int, max_descent_sweeps: int,
                  seed: int, tabu_iterations: int = 0, class_sizes=None, balance_iterations: Optional[int] = None,
                  parts: Optional[dict] = None, *, node_cost: Optional[torch.Tensor] = None,
-                 abs_scale: bool = False) -> MaxCutResult:
+                 abs_scale: bool = False, tempering: Optional[tuple] = None) -> MaxCutResult:
     """``parts``: a dict that receives the partitions behind ``trained_cut``, ``rounded_cut`` (and ``annealed_cut``).
     ``node_cost``: a float32 tensor [R, K] that :func:`_check_node_cost` has returned - the public doors check once and
     pass the checked tensor down (small route); the tabu and the balanced stage then take it too; ``abs_scale``: the
-    annealing's temperature in units of the mean absolute edge weight (the doors with signed weights)."""
+    annealing's temperature in units of the mean absolute edge weight (the doors with signed weights); ``tempering``:
+    what :func:`_check_tempering` returned."""
     from .Testing import TestingNeuralNetwork as T
     K, terminals = _classes(number_classes), bool(terminals)
     if epochs < 0 or samples < 0 or anneal_sweeps < 0 or max_descent_sweeps < 0:
@@ -400,6 +448,10 @@ def _solve_batch(route: _Route, batch: GraphBatch, number_classes: int, terminal
     if tabu_iterations and not route.stages:
         raise NotImplementedError(_NO_TABU)
     _check_sizes(class_sizes, balance_iterations, None)
+    if tempering is not None:
+        if not route.stages:
+            raise NotImplementedError(_NO_TEMPER)
+        tempering = _check_tempering(*tempering, tabu_iterations, class_sizes, samples)
     bounds = None
     if class_sizes is not None:
         if not route.stages:
@@ -447,9 +499,23 @@ def _solve_batch(route: _Route, batch: GraphBatch, number_classes: int, terminal
     cost_sum = (lambda part: None) if node_cost is None else (lambda part: _node_cost_sum(batch, node_cost, part))
     if parts is not None:
         parts.update(trained=best_S, rounded=rounded)
-        if tabu_iterations:
+        if tabu_iterations or tempering is not None:
             parts.update(annealed=partition)
     annealed_cut = None
+    if tempering is not None:
+        # the annealing left its candidates in `cands`: whole ladders of them become the walkers (a copy), their best
+        # states descend and are picked by the annealing call without sweeps; then the better of the two, as below
+        rounds, sweeps, rungs = tempering
+        walkers = cands[:rungs * (cands.shape[0] // rungs)].clone()
+        best = T._kway_temper_on_gpu(batch, K, walkers, T.temper_ladder(rungs, scale=scale), rounds, sweeps, seed,
+                                     terminals, node_cost)[0]
+        temper_partition, temper_cut, _ = T._kway_anneal_on_gpu(batch, K, best, no_sweeps, 0, int(max_descent_sweeps),
+                                                                terminals, node_cost)
+        better = temper_cut > cut
+        sizes = (batch.goff[1:] - batch.goff[:-1]).to(torch.int64)
+        rows = torch.repeat_interleave(better, sizes, output_size=batch.R)
+        partition, cut, annealed_cut = (torch.where(rows, temper_partition, partition), torch.where(better, temper_cut, cut),
+                                        cut)
     if tabu_iterations:
         # the annealing left its candidates in `cands`; the better of the two results per graph, chosen on the device
         tabu_partition, tabu_cut = T._kway_tabu_on_gpu(batch, K, cands.clone(), int(tabu_iterations), T.TABU_TENURE, seed,
@@ -522,13 +588,14 @@ def _door(edge_index, ptr, num_nodes):
 
 
 def _solve_door(batch: GraphBatch, node_cost: np.ndarray, hidden_dim, epochs, learning_rate, loss, samples, anneal_sweeps,
-                max_descent_sweeps, seed, tabu_iterations=0, class_sizes=None, balance_iterations=None) -> MaxCutResult:
+                max_descent_sweeps, seed, tabu_iterations=0, class_sizes=None, balance_iterations=None,
+                tempering=None) -> MaxCutResult:
     loss = hip.loss_name(loss)
     if batch.B:
         _refuse_small(batch.n_max, 2, loss)
     return _solve_batch(_SMALL, batch, 2, False, hidden_dim, epochs, learning_rate, loss, samples, anneal_sweeps,
                         max_descent_sweeps, seed, tabu_iterations, class_sizes, balance_iterations,
-                        node_cost=_check_node_cost(node_cost, batch.R, 2), abs_scale=True)
+                        node_cost=_check_node_cost(node_cost, batch.R, 2), abs_scale=True, tempering=tempering)
 
 
 def _door_stages(what: str, goff: np.ndarray, tabu_iterations, class_sizes, balance_iterations):
@@ -559,7 +626,8 @@ def _cardinality_sizes(cardinality, goff: np.ndarray):
 def solve_ising(edge_index, ptr=None, num_nodes: Optional[int] = None, coupling=None, field=None, *, pairs: str = "both",
                 hidden_dim: int, epochs: int, learning_rate: float, loss: str = "expected_cut", samples: int = 32,
                 anneal_sweeps: int = 100, max_descent_sweeps: int = 100, seed: int = 0, tabu_iterations: int = 0,
-                class_sizes=None, balance_iterations: Optional[int] = None) -> IsingResult:
+                class_sizes=None, balance_iterations: Optional[int] = None, tempering_rounds: int = 0,
+                tempering_sweeps: int = 4, tempering_rungs: int = 8) -> IsingResult:
     """Minimises ``H(s) = sum_{i<j} J_ij s_i s_j + sum_i h_i s_i`` over ``s`` in {+1, -1}^n for every graph of a batch:
     ``edge_index`` / ``ptr`` / ``num_nodes`` / ``pairs`` as :func:`solve` takes them, ``coupling`` [E] the J of every
     entry (``None``: 1; with ``pairs="both"`` both directions carry the same J), ``field`` [R] the h of every node
@@ -576,12 +644,14 @@ def solve_ising(edge_index, ptr=None, num_nodes: Optional[int] = None, coupling=
     and class 1 is ``s = -1``, so ``class_sizes=(lo, hi)`` bounds the number of up spins by ``lo[0]..hi[0]`` and of down
     spins by ``lo[1]..hi[1]`` - a bounded magnetisation; ``spins`` and ``energy`` are then those of the within-bounds
     partition.  Bounds that admit no partition raise ``ValueError`` before anything is built.  The defaults launch
-    nothing more and change no byte.
+    nothing more and change no byte.  ``tempering_rounds``, ``tempering_sweeps`` and ``tempering_rungs``: :func:`solve`'s
+    tempering stage on the objective, its ladder in units of the mean absolute edge weight.
 
     A spin without any coupling is refused by the batch builder (``ValueError``: "nodes without neighbours"); its optimum
     is its own sign, ``s_i = -sign(h_i)`` - leave it out and add ``-|h_i|`` to the energy."""
     ei, goff = _door(edge_index, ptr, num_nodes)
     class_sizes = _door_stages("solve_ising", goff, tabu_iterations, class_sizes, balance_iterations)
+    tempering = _check_tempering(tempering_rounds, tempering_sweeps, tempering_rungs, tabu_iterations, class_sizes, samples)
     E, R = ei.shape[1], int(goff[-1])
     J = _values("coupling", coupling, "E", E, 1.0)
     h = _values("field", field, "R", R, 0.0)
@@ -594,7 +664,7 @@ def solve_ising(edge_index, ptr=None, num_nodes: Optional[int] = None, coupling=
     node_cost = np.stack([h, -h], axis=1).astype(np.float32)
     batch = GraphBatch.from_edge_index(edge_index, ptr, num_nodes, (2.0 * J).astype(np.float32), pairs=pairs)
     res = _solve_door(batch, node_cost, hidden_dim, epochs, learning_rate, loss, samples, anneal_sweeps,
-                      max_descent_sweeps, seed, tabu_iterations, class_sizes, balance_iterations)
+                      max_descent_sweeps, seed, tabu_iterations, class_sizes, balance_iterations, tempering)
     spins = (1 - 2 * res.partition).to(torch.int8)
     energy = torch.from_numpy(sum_j) - res.cut.detach().cpu().to(torch.float64)
     return IsingResult(spins, energy, res.ptr, res)
@@ -603,7 +673,8 @@ def solve_ising(edge_index, ptr=None, num_nodes: Optional[int] = None, coupling=
 def solve_qubo(edge_index, ptr=None, num_nodes: Optional[int] = None, quadratic=None, linear=None, *, pairs: str = "both",
                hidden_dim: int, epochs: int, learning_rate: float, loss: str = "expected_cut", samples: int = 32,
                anneal_sweeps: int = 100, max_descent_sweeps: int = 100, seed: int = 0, tabu_iterations: int = 0,
-               class_sizes=None, balance_iterations: Optional[int] = None, cardinality=None) -> QuboResult:
+               class_sizes=None, balance_iterations: Optional[int] = None, cardinality=None, tempering_rounds: int = 0,
+               tempering_sweeps: int = 4, tempering_rungs: int = 8) -> QuboResult:
     """Minimises ``E(x) = sum_i a_i x_i + sum_{i<j} q_ij x_i x_j`` over ``x`` in {0, 1}^n for every graph of a batch:
     ``edge_index`` / ``ptr`` / ``num_nodes`` / ``pairs`` as :func:`solve` takes them, ``quadratic`` [E] the q of every
     entry (``None``: 1; with ``pairs="both"`` both directions carry the same q), ``linear`` [R] the a of every variable
@@ -622,7 +693,8 @@ def solve_qubo(edge_index, ptr=None, num_nodes: Optional[int] = None, quadratic=
     ``(lo, hi)`` (between ``lo`` and ``hi``) - the cardinality-constrained QUBO; it is mapped onto ``class_sizes``
     (class 1 holds ``lo..hi`` nodes), and passing both raises ``ValueError``.  With bounds ``x`` and ``energy`` are those
     of the within-bounds partition.  Bounds that admit no partition raise ``ValueError`` before anything is built.  The
-    defaults launch nothing more and change no byte.
+    defaults launch nothing more and change no byte.  ``tempering_rounds``, ``tempering_sweeps`` and ``tempering_rungs``:
+    :func:`solve`'s tempering stage on the objective, its ladder in units of the mean absolute edge weight.
 
     A variable without any quadratic term is refused by the batch builder (``ValueError``: "nodes without
     neighbours"); its optimum is its own sign, ``x_i = 1`` iff ``a_i < 0`` - leave it out and add ``min(a_i, 0)``."""
@@ -632,6 +704,7 @@ def solve_qubo(edge_index, ptr=None, num_nodes: Optional[int] = None, quadratic=
             raise ValueError("cardinality is mapped onto class_sizes: pass one of the two")
         class_sizes = _cardinality_sizes(cardinality, goff)
     class_sizes = _door_stages("solve_qubo", goff, tabu_iterations, class_sizes, balance_iterations)
+    tempering = _check_tempering(tempering_rounds, tempering_sweeps, tempering_rungs, tabu_iterations, class_sizes, samples)
     E, R = ei.shape[1], int(goff[-1])
     q = _values("quadratic", quadratic, "E", E, 1.0)
     a = _values("linear", linear, "R", R, 0.0)
@@ -644,7 +717,7 @@ def solve_qubo(edge_index, ptr=None, num_nodes: Optional[int] = None, quadratic=
     node_cost = np.zeros((R, 2), np.float32)
     node_cost[:, 1] = a.astype(np.float32) + half.cpu().numpy()   # (one fp32 addition per variable)
     res = _solve_door(batch, node_cost, hidden_dim, epochs, learning_rate, loss, samples, anneal_sweeps,
-                      max_descent_sweeps, seed, tabu_iterations, class_sizes, balance_iterations)
+                      max_descent_sweeps, seed, tabu_iterations, class_sizes, balance_iterations, tempering)
     return QuboResult(res.partition.to(torch.int8), -res.cut, res.ptr, res)
 
 
