@@ -1104,6 +1104,102 @@ def kway_tempering(partitions, graph, number_classes: int, rounds: int = TEMPER_
     return best_assign.cpu().tolist(), _as_number(best_cut.item()), info
 
 
+def dense_matrices(what: str, W, dev) -> torch.Tensor:
+    """A dense door's matrices -> a contiguous [B, n, n] float32 tensor on ``dev``: ``W`` is [n, n] or [B, n, n], a
+    tensor (host or device) or a numpy array; 2 <= n <= ``hip.MAX_GRAPH_NODES``, every entry finite in float32, and
+    symmetric bit for bit (the diagonal is never read and is not checked).  ``ValueError`` otherwise."""
+    t = W if isinstance(W, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(W))
+    if t.ndim == 2:
+        t = t.reshape(1, *t.shape)
+    if t.ndim != 3 or t.shape[1] != t.shape[2]:
+        raise ValueError(f"{what} must be [n, n] or [B, n, n], got {tuple(t.shape)}")
+    if not 2 <= t.shape[1] <= hip.MAX_GRAPH_NODES:
+        raise ValueError(f"{what}: n must be in 2..{hip.MAX_GRAPH_NODES}, got {t.shape[1]}")
+    t = t.to(dev, torch.float32).contiguous()
+    off = ~torch.eye(t.shape[1], dtype=torch.bool, device=dev)
+    if not bool(torch.isfinite(t[:, off]).all()):
+        raise ValueError(f"{what} holds values that are not finite (in float32)")
+    if not bool((t == t.transpose(1, 2))[:, off].all()):
+        raise ValueError(f"{what} is not symmetric")
+    return t
+
+
+def dense_scale(W: torch.Tensor) -> float:
+    """The temperature unit of the dense doors: ``sqrt(mean_v sum_{u != v} w_vu^2)`` over all rows of W [B, n, n], the
+    spread of a local field under random classes, in float64 (1 for matrices of zeros).  PROVISIONAL: nobody has
+    measured this choice against the sparse doors' mean absolute weight."""
+    off = ~torch.eye(W.shape[1], dtype=torch.bool, device=W.device)
+    sq = torch.where(off, W.to(torch.float64) ** 2, torch.zeros((), dtype=torch.float64, device=W.device))
+    s = float(sq.sum(dim=2).mean().sqrt().item())
+    return s if s > 0 else 1.0
+
+
+def _dense_anneal_on_gpu(W: torch.Tensor, assign: torch.Tensor, inv_temp: np.ndarray, seed: int, max_descent_sweeps: int,
+                         node_cost: Optional[torch.Tensor] = None, order: Optional[torch.Tensor] = None) -> Dict[str, Any]:
+    """gmc_dense_anneal_f32 over the candidates assign [cands, B * n] int8, in place, on W [B, n, n] (contiguous float32
+    on the device, symmetric); ``node_cost`` [B * n, 2] float32 and ``order`` [B * n] int32 (local ids) on the device, or
+    None.  Returns best_assign [B * n] int32, best_score / best_idx [B], score_all [B, cands], snap_sweep / sweeps
+    [B, cands] int32 and moves [B, cands] int64."""
+    B, n = int(W.shape[0]), int(W.shape[1])
+    dev, cands = W.device, int(assign.shape[0])
+    if tuple(assign.shape) != (cands, B * n) or assign.dtype != torch.int8 or cands < 1:
+        raise ValueError(f"assign must be [cands, {B * n}] int8 with cands >= 1, got {assign.dtype} {tuple(assign.shape)}")
+    inv_t, levels, sweeps = _schedule_tensors(inv_temp, dev)
+    f32 = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
+    i32 = lambda *shape: torch.empty(shape, dtype=torch.int32, device=dev)
+    out = dict(best_assign=i32(B * n), best_score=f32(B), best_idx=i32(B), score_all=f32(B, cands),
+               snap_sweep=i32(B, cands), sweeps=i32(B, cands),
+               moves=torch.empty((B, cands), dtype=torch.int64, device=dev))
+    lib, p = hip.load(), hip.ptr
+    ws = torch.empty(max(int(lib.gmc_dense_anneal_workspace_bytes(B, n, cands)), 16), dtype=torch.uint8, device=dev)
+    rc = lib.gmc_dense_anneal_f32(B, n, p(W), n, p(node_cost), p(order), cands, p(assign), p(inv_t), sweeps, p(levels),
+                                  int(seed) & _M64, int(max_descent_sweeps), p(ws), ws.numel(), p(out["score_all"]),
+                                  p(out["best_assign"]), p(out["best_score"]), p(out["best_idx"]), p(out["snap_sweep"]),
+                                  p(out["sweeps"]), p(out["moves"]), hip.stream())
+    hip.check(rc, "gmc_dense_anneal_f32")
+    return out
+
+
+def dense_annealing(partitions, W, sweeps: int = 100, t_start: float = 1.5, t_end: float = 0.15, seed: int = 0,
+                    max_descent_sweeps: int = 100, node_cost=None, order=None) -> Tuple[List[int], Any, Dict[str, Any]]:
+    """Annealing + descent of two-class partitions of ONE dense instance (extension, include/gcnmaxcut_dense.h
+    ``gmc_dense_anneal_f32``): ``W`` [n, n] symmetric (max-cut weights; the diagonal is ignored), ``partitions`` [cands, n]
+    (or [n]) of 0 / 1, ``node_cost`` [n, 2] the objective ``cut - sum_v node_cost[v][class_v]``, ``order`` a permutation
+    of 0..n-1 (the visit order; None: 0, 1, ...).  Every chain keeps one cached local field per node, so a rejected
+    proposal costs no row of W.  ``sweeps`` Metropolis sweeps cool from ``t_start`` to ``t_end`` (:func:`anneal_schedule`,
+    :func:`anneal_levels`) in units of :func:`dense_scale` - the spread of a local field, where the sparse searches use
+    the mean absolute weight; that unit and these defaults are PROVISIONAL, nobody has measured them (DESIGN.md section
+    40).  Reproducible from ``seed``.  Returns the best assignment, its objective and a dict with ``scores``,
+    ``snap_sweep``, ``sweeps`` and ``moves`` per partition."""
+    if sweeps < 0 or max_descent_sweeps < 0:
+        raise ValueError(f"sweeps and max_descent_sweeps must be >= 0, got {sweeps} and {max_descent_sweeps}")
+    dev = hip.require_gpu()
+    Wd = dense_matrices("W", W, dev)
+    if Wd.shape[0] != 1:
+        raise ValueError("dense_annealing takes one instance: W must be [n, n]")
+    n = int(Wd.shape[1])
+    parts = np.asarray(partitions, dtype=np.int64)
+    parts = parts.reshape(1, -1) if parts.ndim == 1 else parts
+    if parts.ndim != 2 or parts.shape[0] < 1 or parts.shape[1] != n:
+        raise ValueError(f"partitions must be [cands, {n}] with cands >= 1, got {tuple(parts.shape)}")
+    if int(parts.min()) < 0 or int(parts.max()) > 1:
+        raise ValueError("partitions holds a class outside 0..1")
+    cost = _graph_cost("dense_annealing", node_cost, n, 2)
+    ord_t = None
+    if order is not None:
+        o = np.asarray(order, dtype=np.int64)
+        if o.shape != (n,) or not np.array_equal(np.sort(o), np.arange(n)):
+            raise ValueError(f"order must be a permutation of 0..{n - 1}")
+        ord_t = torch.from_numpy(o.astype(np.int32)).to(dev)
+    inv_temp = anneal_schedule(sweeps, t_start, t_end, dense_scale(Wd))
+    out = _dense_anneal_on_gpu(Wd, torch.from_numpy(parts.astype(np.int8)).to(dev), inv_temp, seed, max_descent_sweeps,
+                               None if cost is None else cost.to(dev), ord_t)
+    info = {"scores": [_as_number(c) for c in out["score_all"][0].cpu().tolist()],
+            "snap_sweep": out["snap_sweep"][0].cpu().tolist(), "sweeps": out["sweeps"][0].cpu().tolist(),
+            "moves": out["moves"][0].cpu().tolist()}
+    return out["best_assign"].cpu().tolist(), _as_number(out["best_score"].item()), info
+
+
 def test_single_graph(model, dgl_graph, adjacency_matrix, nx_graph, terminals: List[int],
                       post_processing_iterations: int = 200, *, seed: Optional[int] = None,
                       graph_index: int = 0) -> Dict[str, Any]:

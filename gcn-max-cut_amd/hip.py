@@ -255,12 +255,25 @@ def _temper_api() -> dict:
     }
 
 
+def _dense_api() -> dict:
+    """name -> (restype, argtypes) of every symbol include/gcnmaxcut_dense.h declares (annealing of dense two-class
+    instances on cached local fields: a header and a table of its own, as the tempering has)."""
+    vp, i32, i64, sz, i = C.c_void_p, C.c_int32, C.c_int64, C.c_size_t, C.c_int
+    return {
+        "gmc_dense_anneal_workspace_bytes": (sz, [i32, i32, i32]),
+        "gmc_dense_anneal_f32": (i, [i32, i32, vp, i64, vp, vp, i32, vp, vp, i32, vp, C.c_uint64, i32, vp, sz, vp, vp, vp,
+                                     vp, vp, vp, vp, vp]),
+    }
+
+
 _API = _api()
 SYMBOLS = tuple(_API)
 _SDP_API = _sdp_api()
 SDP_SYMBOLS = tuple(_SDP_API)
 _TEMPER_API = _temper_api()
 TEMPER_SYMBOLS = tuple(_TEMPER_API)
+_DENSE_API = _dense_api()
+DENSE_SYMBOLS = tuple(_DENSE_API)
 TEMPER_MAX_RUNGS = 256   # GMC_TEMPER_MAX_RUNGS: the longest ladder gmc_kway_temper_f32 takes
 SDP_RANKS = (16, 32, 64)   # the ranks gmc_sdp_relax_f32 / gmc_sdp_round_f32 take
 
@@ -268,7 +281,8 @@ _lib: Optional[C.CDLL] = None
 
 
 def _declare(lib: C.CDLL) -> None:
-    for name, (restype, argtypes) in list(_API.items()) + list(_SDP_API.items()) + list(_TEMPER_API.items()):
+    for name, (restype, argtypes) in (list(_API.items()) + list(_SDP_API.items()) + list(_TEMPER_API.items())
+                                      + list(_DENSE_API.items())):
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = restype, argtypes
     lib.gmc_debug_set_device_cus.argtypes = [C.c_int]   # test hook (not part of gcnmaxcut.h)

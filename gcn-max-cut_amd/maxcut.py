@@ -887,3 +887,176 @@ def solve_sdp(edge_index, ptr=None, num_nodes: Optional[int] = None, edge_weight
     batch = GraphBatch.from_edge_index(edge_index, ptr, num_nodes, edge_weight, pairs=pairs)
     return solve_sdp_batch(batch, rank=rank, sweeps=sweeps, planes=planes, anneal_sweeps=anneal_sweeps,
                            max_descent_sweeps=max_descent_sweeps, seed=seed, terminals=terminals, node_cost=node_cost)
+
+
+# ---- dense instances: annealing on cached local fields, no model, no training ---------------------
+@dataclass
+class DenseResult:
+    """What :func:`solve_dense` returns: device tensors, one row per instance."""
+    partition: torch.Tensor                 # [B, n] int32: the class of every node
+    cut: torch.Tensor                       # [B] float32: the cut of ``partition`` (with node_cost: the objective cut - cost)
+    node_cost_sum: Optional[torch.Tensor]   # [B] float32, with node_cost only: sum_v node_cost[v][partition_v]
+    moves: torch.Tensor                     # [B, candidates] int64: the annealing moves every chain accepted
+
+
+@dataclass
+class DenseIsingResult:
+    """What :func:`solve_ising_dense` returns."""
+    spins: torch.Tensor     # [B, n] int8: +1 / -1 (device)
+    energy: torch.Tensor    # [B] float64: H(spins), recounted in float64 (device)
+    result: DenseResult     # the max-cut run behind it: class 0 is spin +1, result.cut the objective sum(J) - H in float32
+
+
+@dataclass
+class DenseQuboResult:
+    """What :func:`solve_qubo_dense` returns."""
+    x: torch.Tensor         # [B, n] int8: 0 / 1 (device)
+    energy: torch.Tensor    # [B] float64: E(x), recounted in float64 (device)
+    result: DenseResult     # the max-cut run behind it: class 1 is x = 1, result.cut the objective -E in float32
+
+
+def _dense_cost(what: str, node_cost, B: int, n: int, dev) -> Optional[torch.Tensor]:
+    """``node_cost`` of a dense door -> [B * n, 2] float32 on the device, or None: [n, 2] / [B, n, 2] / [B * n, 2], finite."""
+    if node_cost is None:
+        return None
+    t = node_cost if isinstance(node_cost, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(node_cost))
+    if t.numel() != B * n * 2 or t.shape[-1] != 2:
+        raise ValueError(f"{what} must be [{n}, 2] per instance ({B} instances), got {tuple(t.shape)}")
+    t = t.to(dev, torch.float32).reshape(B * n, 2).contiguous()
+    if not bool(torch.isfinite(t).all()):
+        raise ValueError(f"{what} holds values that are not finite (in float32)")
+    return t
+
+
+def _dense_vector(what: str, values, B: int, n: int, dev) -> torch.Tensor:
+    """A dense door's per-node values -> [B, n] float64 on the device (None: zeros): [n] / [B, n], finite."""
+    if values is None:
+        return torch.zeros((B, n), dtype=torch.float64, device=dev)
+    t = values if isinstance(values, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(values))
+    if t.numel() != B * n:
+        raise ValueError(f"{what} must be [{n}] per instance ({B} instances), got {tuple(t.shape)}")
+    t = t.to(dev, torch.float64).reshape(B, n)
+    if not bool(torch.isfinite(t.to(torch.float32)).all()):
+        raise ValueError(f"{what} holds values that are not finite")
+    return t
+
+
+def _dense_starts(B: int, n: int, candidates: int, seed: int, partitions, dev) -> torch.Tensor:
+    """The chains' starts [candidates, B * n] int8: ``partitions`` when given ([candidates, B * n] or, for one instance,
+    [candidates, n]; classes 0 / 1), else seeded random bytes drawn by torch on the device - plumbing: reproducible on one
+    installation, NOT part of the kernel's byte-for-byte contract."""
+    if partitions is not None:
+        p = partitions if isinstance(partitions, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(partitions))
+        if p.ndim != 2 or p.shape[0] < 1 or p.shape[1] != B * n:
+            raise ValueError(f"partitions must be [candidates, {B * n}], got {tuple(p.shape)}")
+        if int(p.min()) < 0 or int(p.max()) > 1:
+            raise ValueError("partitions holds a class outside 0..1")
+        return p.to(dev, torch.int8).contiguous().clone()
+    if int(candidates) < 1:
+        raise ValueError(f"candidates must be >= 1, got {candidates}")
+    gen = torch.Generator(device=dev)
+    gen.manual_seed(int(seed) & ((1 << 63) - 1))
+    return torch.randint(0, 2, (int(candidates), B * n), generator=gen, device=dev, dtype=torch.int8)
+
+
+def _solve_dense(W: torch.Tensor, cost: Optional[torch.Tensor], candidates, anneal_sweeps, seed, max_descent_sweeps,
+                 t_start, t_end, partitions) -> DenseResult:
+    from .Testing import TestingNeuralNetwork as T
+    if anneal_sweeps < 0 or max_descent_sweeps < 0:
+        raise ValueError(f"anneal_sweeps and max_descent_sweeps must be >= 0, got {anneal_sweeps} and {max_descent_sweeps}")
+    B, n = int(W.shape[0]), int(W.shape[1])
+    starts = _dense_starts(B, n, candidates, seed, partitions, W.device)
+    inv_temp = T.anneal_schedule(int(anneal_sweeps), t_start, t_end, T.dense_scale(W))
+    out = T._dense_anneal_on_gpu(W, starts, inv_temp, seed, int(max_descent_sweeps), cost)
+    partition = out["best_assign"].reshape(B, n)
+    cost_sum = None
+    if cost is not None:
+        picked = cost.reshape(B, n, 2).gather(2, partition.to(torch.int64).unsqueeze(2)).squeeze(2)
+        cost_sum = picked.to(torch.float64).sum(dim=1).to(torch.float32)
+    return DenseResult(partition, out["best_score"], cost_sum, out["moves"])
+
+
+def solve_dense(W, candidates: int = 200, anneal_sweeps: int = 100, seed: int = 0, node_cost=None, *,
+                max_descent_sweeps: int = 100, t_start: float = 1.5, t_end: float = 0.15, partitions=None) -> DenseResult:
+    """Max-cut (two classes, no terminals) of dense instances given as matrices: ``W`` is [n, n] or [B, n, n] (B instances
+    of one size, 2 <= n <= ``hip.MAX_GRAPH_NODES``), a tensor on the host or the device or a numpy array, symmetric and
+    finite (``ValueError`` otherwise; the diagonal is ignored).  No model and no training: ``candidates`` chains per
+    instance start from seeded random partitions (drawn by torch on the device; or from ``partitions``), run
+    ``anneal_sweeps`` Metropolis sweeps and at most ``max_descent_sweeps`` sweeps of single-move descent on the GPU
+    (``gmc_dense_anneal_f32``, include/gcnmaxcut_dense.h), and the best chain of every instance is returned.
+    ``node_cost`` [n, 2] / [B, n, 2]: the objective ``cut - sum_v node_cost[v][class_v]`` of :func:`solve`.
+
+    A chain keeps one cached local field per node, decides a visit from it and reads a row of ``W`` only for an accepted
+    move - the form for matrices where :func:`solve`'s sparse decoders walk n entries per visit.  The schedule cools from
+    ``t_start`` to ``t_end`` in units of ``sqrt(mean_v sum_u w_vu^2)``, the spread of a local field, where the sparse doors
+    use the mean absolute weight.  That unit and the defaults are PROVISIONAL: nobody has measured them (DESIGN.md section
+    40).  For a given start the kernel's outputs are reproducible bit for bit; the random starts are torch's."""
+    dev = hip.require_gpu()
+    from .Testing import TestingNeuralNetwork as T
+    Wd = T.dense_matrices("W", W, dev)
+    cost = _dense_cost("node_cost", node_cost, int(Wd.shape[0]), int(Wd.shape[1]), dev)
+    return _solve_dense(Wd, cost, candidates, anneal_sweeps, seed, max_descent_sweeps, t_start, t_end, partitions)
+
+
+def _pair_energy(M: torch.Tensor, lin: torch.Tensor, z: torch.Tensor) -> torch.Tensor:
+    """[B] float64: sum_{i<j} M_ij z_i z_j + sum_i lin_i z_i of z [B, n] (M symmetric, its diagonal ignored)."""
+    off = ~torch.eye(M.shape[1], dtype=torch.bool, device=M.device)
+    M64 = torch.where(off, M.to(torch.float64), torch.zeros((), dtype=torch.float64, device=M.device))
+    z = z.to(torch.float64)
+    return 0.5 * torch.einsum("bi,bij,bj->b", z, M64, z) + (lin * z).sum(dim=1)
+
+
+def solve_ising_dense(J, field=None, candidates: int = 200, anneal_sweeps: int = 100, seed: int = 0, *,
+                      max_descent_sweeps: int = 100, t_start: float = 1.5, t_end: float = 0.15,
+                      partitions=None) -> DenseIsingResult:
+    """Minimises ``H(s) = sum_{i<j} J_ij s_i s_j + sum_i h_i s_i`` over ``s`` in {+1, -1}^n for dense couplings ``J``
+    ([n, n] or [B, n, n], symmetric, as :func:`solve_dense` takes ``W``) and ``field`` h ([n] / [B, n]; None: 0) - a
+    Sherrington-Kirkpatrick instance, for one.  The mapping is :func:`solve_ising`'s: ``w = 2 J`` (exact in float32),
+    class 0 is ``s = +1``, ``node_cost[i] = (h_i, -h_i)``; then ``H(s) = sum_{i<j} J_ij - obj``.  Returns ``spins``
+    [B, n] int8, ``energy`` [B] float64 - ``H(spins)`` recounted in float64 from ``J`` and ``h``, not derived from the
+    kernel's float32 objective - and the :class:`DenseResult` as ``.result``.  The other keywords, and the provisional
+    temperature unit, are :func:`solve_dense`'s."""
+    dev = hip.require_gpu()
+    from .Testing import TestingNeuralNetwork as T
+    Jd = T.dense_matrices("J", J, dev)
+    B, n = int(Jd.shape[0]), int(Jd.shape[1])
+    h = _dense_vector("field", field, B, n, dev)
+    h32 = h.to(torch.float32).reshape(B * n)
+    cost = torch.stack([h32, -h32], dim=1).contiguous()
+    res = _solve_dense(2.0 * Jd, cost, candidates, anneal_sweeps, seed, max_descent_sweeps, t_start, t_end, partitions)
+    spins = (1 - 2 * res.partition).to(torch.int8)
+    return DenseIsingResult(spins, _pair_energy(Jd, h, spins), res)
+
+
+def dense_row_sums(w: torch.Tensor) -> torch.Tensor:
+    """[B, n] float32: ``sum_{j != i} w_ij`` of w [B, n, n], every row summed in float32 from +0 over j ascending (one
+    elementwise addition per column, so the order is the stated one whatever the device's reductions do)."""
+    off = ~torch.eye(w.shape[1], dtype=torch.bool, device=w.device)
+    wz = torch.where(off, w, torch.zeros((), dtype=w.dtype, device=w.device))
+    acc = torch.zeros(w.shape[:2], dtype=torch.float32, device=w.device)
+    for j in range(w.shape[2]):
+        acc = acc + wz[:, :, j]
+    return acc
+
+
+def solve_qubo_dense(Q, linear=None, candidates: int = 200, anneal_sweeps: int = 100, seed: int = 0, *,
+                     max_descent_sweeps: int = 100, t_start: float = 1.5, t_end: float = 0.15,
+                     partitions=None) -> DenseQuboResult:
+    """Minimises ``E(x) = sum_i a_i x_i + sum_{i<j} q_ij x_i x_j`` over ``x`` in {0, 1}^n for a dense ``Q`` ([n, n] or
+    [B, n, n], symmetric, as :func:`solve_dense` takes ``W``; Beasley / BiqMac style) and ``linear`` a ([n] / [B, n]; None:
+    0).  The mapping is :func:`solve_qubo`'s and has no offset: ``w = q / 2``, class 1 is ``x = 1``, ``node_cost[i] =
+    (0, a_i + sum_j w_ij)``, the row sums in float32 over j ascending (:func:`dense_row_sums`) and one float32 addition
+    per variable; then ``E(x) = -obj``.  Returns ``x`` [B, n] int8, ``energy`` [B] float64 - ``E(x)`` recounted in float64
+    from ``Q`` and ``a`` - and the :class:`DenseResult` as ``.result``.  The other keywords, and the provisional
+    temperature unit, are :func:`solve_dense`'s."""
+    dev = hip.require_gpu()
+    from .Testing import TestingNeuralNetwork as T
+    Qd = T.dense_matrices("Q", Q, dev)
+    B, n = int(Qd.shape[0]), int(Qd.shape[1])
+    a = _dense_vector("linear", linear, B, n, dev)
+    w = 0.5 * Qd
+    cost = torch.zeros((B * n, 2), dtype=torch.float32, device=dev)
+    cost[:, 1] = a.to(torch.float32).reshape(B * n) + dense_row_sums(w).reshape(B * n)
+    res = _solve_dense(w, cost, candidates, anneal_sweeps, seed, max_descent_sweeps, t_start, t_end, partitions)
+    x = res.partition.to(torch.int8)
+    return DenseQuboResult(x, _pair_energy(Qd, a, x), res)
