@@ -1200,6 +1200,96 @@ def dense_annealing(partitions, W, sweeps: int = 100, t_start: float = 1.5, t_en
     return out["best_assign"].cpu().tolist(), _as_number(out["best_score"].item()), info
 
 
+def bifurcation_pump(steps: int) -> np.ndarray:
+    """The pump table of the bifurcation, ``a0 - a(t)`` with a0 = 1 as float32 [steps]: the linear ramp from 1 at the
+    first step to 0 at the last (one step: 1).  PROVISIONAL, like every default of the stage."""
+    steps = int(steps)
+    if steps < 0:
+        raise ValueError(f"steps must be >= 0, got {steps}")
+    return np.linspace(1.0, 0.0, steps).astype(np.float32) if steps > 1 else np.ones(steps, np.float32)
+
+
+def _dense_bifurcation_on_gpu(W: torch.Tensor, cands: int, pump: np.ndarray, c0: float, dt: float,
+                              node_cost: Optional[torch.Tensor] = None, x: Optional[torch.Tensor] = None,
+                              y: Optional[torch.Tensor] = None, seed: int = 0,
+                              amplitude: float = 0.1) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """gmc_dense_sb_f32 over ``cands`` chains per problem of W [B, n, n] (contiguous float32 on the device, symmetric):
+    ``len(pump)`` steps from the state ``x``, ``y`` ([B * n, cands] float32 on the device, updated in place) or, without
+    one, from gmc_dense_sb_init_f32's seeded start.  Returns (assign [cands, B * n] int8, x, y)."""
+    B, n = int(W.shape[0]), int(W.shape[1])
+    dev, cands = W.device, int(cands)
+    if cands < 1:
+        raise ValueError(f"candidates must be >= 1, got {cands}")
+    lib, p = hip.load(), hip.ptr
+    if (x is None) != (y is None):
+        raise ValueError("a state is both x and y")
+    if x is None:
+        x = torch.empty((B * n, cands), dtype=torch.float32, device=dev)
+        y = torch.empty((B * n, cands), dtype=torch.float32, device=dev)
+        hip.check(lib.gmc_dense_sb_init_f32(B, n, cands, int(seed) & _M64, float(amplitude), p(x), p(y), hip.stream()),
+                  "gmc_dense_sb_init_f32")
+    for name, t in (("x", x), ("y", y)):
+        if tuple(t.shape) != (B * n, cands) or t.dtype != torch.float32 or not t.is_contiguous() or t.device != dev:
+            raise ValueError(f"{name} must be a contiguous [{B * n}, {cands}] float32 tensor on {dev}")
+    pump_t = torch.from_numpy(np.ascontiguousarray(pump, dtype=np.float32)).to(dev)
+    steps = int(pump_t.numel())
+    assign = torch.empty((cands, B * n), dtype=torch.int8, device=dev)
+    ws = torch.empty(max(int(lib.gmc_dense_sb_workspace_bytes(B, n, cands)), 16), dtype=torch.uint8, device=dev)
+    rc = lib.gmc_dense_sb_f32(B, n, p(W), n, p(node_cost), cands, p(x), p(y), p(pump_t) if steps else None, steps,
+                              float(c0), float(dt), p(ws), ws.numel(), p(assign), hip.stream())
+    hip.check(rc, "gmc_dense_sb_f32")
+    return assign, x, y
+
+
+def bifurcation_c0(W: torch.Tensor, c0: Optional[float]) -> float:
+    """The coupling scale of the bifurcation: ``c0``, or for None ``0.5 / dense_scale(W)`` - the literature's
+    ``0.5 / (sigma_J sqrt(N))`` up to N - 1 against N.  PROVISIONAL."""
+    value = 0.5 / dense_scale(W) if c0 is None else float(c0)
+    if not (np.isfinite(value) and value > 0):
+        raise ValueError(f"bifurcation c0 must be finite and > 0, got {value}")
+    return value
+
+
+def dense_bifurcation(W, candidates: int = 200, steps: int = 1000, dt: float = 1.25, c0: Optional[float] = None,
+                      amplitude: float = 0.1, seed: int = 0, node_cost=None,
+                      state: Optional[Dict[str, Any]] = None) -> Tuple[np.ndarray, List[Any], Dict[str, Any]]:
+    """Discrete simulated bifurcation of ONE dense instance (extension, include/gcnmaxcut_bifurcation.h
+    ``gmc_dense_sb_f32``): ``W`` [n, n] symmetric (max-cut weights; the diagonal is ignored), ``node_cost`` [n, 2] the
+    objective ``cut - sum_v node_cost[v][class_v]``.  ``candidates`` chains move all their nodes at once for ``steps``
+    time steps of length ``dt`` under the linear pump (:func:`bifurcation_pump`); a step is one fp32 MFMA product
+    ``W . sign(X)`` and an elementwise update.  ``c0=None`` means ``0.5 / dense_scale(W)``.  The chains start from the
+    seeded state of ``gmc_dense_sb_init_f32`` (positions 0, momenta uniform in ``amplitude * [-1, 1)``) or continue from
+    ``state``, the dict a previous call returned: ``x`` and ``y`` as numpy float32 [n, candidates] - the device's own
+    layout, a node's candidates side by side.  To continue a ramp, pass the tail of the table yourself through
+    ``gmc_dense_sb_f32``; this function always runs a whole ramp.
+
+    Every default here (dt, c0's unit, amplitude, steps, the linear pump) is the literature's as far as recalled and
+    PROVISIONAL: nobody has measured any of them on this code.
+
+    Returns the partitions [candidates, n] (numpy int8, class 0 is spin +1), their scores - from ``gmc_dense_anneal_f32``
+    with zero sweeps and zero descent, so they carry the bits every other dense output reports - and the dict
+    ``{"x", "y"}``."""
+    if steps < 0:
+        raise ValueError(f"steps must be >= 0, got {steps}")
+    dev = hip.require_gpu()
+    Wd = dense_matrices("W", W, dev)
+    if Wd.shape[0] != 1:
+        raise ValueError("dense_bifurcation takes one instance: W must be [n, n]")
+    n = int(Wd.shape[1])
+    cost = _graph_cost("dense_bifurcation", node_cost, n, 2)
+    cost = None if cost is None else cost.to(dev)
+    x = y = None
+    if state is not None:
+        x, y = (torch.from_numpy(np.ascontiguousarray(state[k], dtype=np.float32)).to(dev) for k in ("x", "y"))
+        if tuple(x.shape) != (n, int(candidates)) or tuple(y.shape) != (n, int(candidates)):
+            raise ValueError(f"state must hold x and y of shape [{n}, {int(candidates)}]")
+    assign, x, y = _dense_bifurcation_on_gpu(Wd, candidates, bifurcation_pump(steps), bifurcation_c0(Wd, c0), dt, cost, x,
+                                             y, seed, amplitude)
+    out = _dense_anneal_on_gpu(Wd, assign, np.zeros(0, np.float32), seed, 0, cost)
+    scores = [_as_number(c) for c in out["score_all"][0].cpu().tolist()]
+    return assign.cpu().numpy(), scores, {"x": x.cpu().numpy(), "y": y.cpu().numpy()}
+
+
 def test_single_graph(model, dgl_graph, adjacency_matrix, nx_graph, terminals: List[int],
                       post_processing_iterations: int = 200, *, seed: Optional[int] = None,
                       graph_index: int = 0) -> Dict[str, Any]:

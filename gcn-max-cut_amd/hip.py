@@ -266,8 +266,22 @@ def _dense_api() -> dict:
     }
 
 
+def _bifurcation_api() -> dict:
+    """name -> (restype, argtypes) of every symbol include/gcnmaxcut_bifurcation.h declares (discrete simulated
+    bifurcation of dense two-class instances: a header and a table of its own, as the dense annealing has)."""
+    vp, i32, i64, sz, i, f32 = C.c_void_p, C.c_int32, C.c_int64, C.c_size_t, C.c_int, C.c_float
+    return {
+        "gmc_dense_sb_state_bytes": (sz, [i32, i32, i32]),
+        "gmc_dense_sb_workspace_bytes": (sz, [i32, i32, i32]),
+        "gmc_dense_sb_init_f32": (i, [i32, i32, i32, C.c_uint64, f32, vp, vp, vp]),
+        "gmc_dense_sb_f32": (i, [i32, i32, vp, i64, vp, i32, vp, vp, vp, i32, f32, f32, vp, sz, vp, vp]),
+    }
+
+
 _API = _api()
 SYMBOLS = tuple(_API)
+_BIFURCATION_API = _bifurcation_api()
+BIFURCATION_SYMBOLS = tuple(_BIFURCATION_API)
 _SDP_API = _sdp_api()
 SDP_SYMBOLS = tuple(_SDP_API)
 _TEMPER_API = _temper_api()
@@ -282,7 +296,7 @@ _lib: Optional[C.CDLL] = None
 
 def _declare(lib: C.CDLL) -> None:
     for name, (restype, argtypes) in (list(_API.items()) + list(_SDP_API.items()) + list(_TEMPER_API.items())
-                                      + list(_DENSE_API.items())):
+                                      + list(_DENSE_API.items()) + list(_BIFURCATION_API.items())):
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = restype, argtypes
     lib.gmc_debug_set_device_cus.argtypes = [C.c_int]   # test hook (not part of gcnmaxcut.h)

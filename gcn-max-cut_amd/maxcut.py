@@ -959,13 +959,28 @@ def _dense_starts(B: int, n: int, candidates: int, seed: int, partitions, dev) -
     return torch.randint(0, 2, (int(candidates), B * n), generator=gen, device=dev, dtype=torch.int8)
 
 
+def _check_bifurcation(partitions, bifurcation_steps) -> None:
+    """The dense doors' refusals about ``bifurcation_steps``, made before the GPU is asked for."""
+    if int(bifurcation_steps) < 0:
+        raise ValueError(f"bifurcation_steps must be >= 0, got {bifurcation_steps}")
+    if int(bifurcation_steps) > 0 and partitions is not None:
+        raise ValueError("partitions= and bifurcation_steps > 0 both name the chains' starts: give one of them")
+
+
 def _solve_dense(W: torch.Tensor, cost: Optional[torch.Tensor], candidates, anneal_sweeps, seed, max_descent_sweeps,
-                 t_start, t_end, partitions) -> DenseResult:
+                 t_start, t_end, partitions, bifurcation_steps=0, bifurcation_dt=1.25,
+                 bifurcation_c0=None) -> DenseResult:
     from .Testing import TestingNeuralNetwork as T
     if anneal_sweeps < 0 or max_descent_sweeps < 0:
         raise ValueError(f"anneal_sweeps and max_descent_sweeps must be >= 0, got {anneal_sweeps} and {max_descent_sweeps}")
     B, n = int(W.shape[0]), int(W.shape[1])
-    starts = _dense_starts(B, n, candidates, seed, partitions, W.device)
+    _check_bifurcation(partitions, bifurcation_steps)
+    if int(bifurcation_steps) > 0:
+        starts, _, _ = T._dense_bifurcation_on_gpu(W, int(candidates), T.bifurcation_pump(int(bifurcation_steps)),
+                                                   T.bifurcation_c0(W, bifurcation_c0), float(bifurcation_dt), cost,
+                                                   seed=seed)
+    else:
+        starts = _dense_starts(B, n, candidates, seed, partitions, W.device)
     inv_temp = T.anneal_schedule(int(anneal_sweeps), t_start, t_end, T.dense_scale(W))
     out = T._dense_anneal_on_gpu(W, starts, inv_temp, seed, int(max_descent_sweeps), cost)
     partition = out["best_assign"].reshape(B, n)
@@ -977,7 +992,9 @@ def _solve_dense(W: torch.Tensor, cost: Optional[torch.Tensor], candidates, anne
 
 
 def solve_dense(W, candidates: int = 200, anneal_sweeps: int = 100, seed: int = 0, node_cost=None, *,
-                max_descent_sweeps: int = 100, t_start: float = 1.5, t_end: float = 0.15, partitions=None) -> DenseResult:
+                max_descent_sweeps: int = 100, t_start: float = 1.5, t_end: float = 0.15, partitions=None,
+                bifurcation_steps: int = 0, bifurcation_dt: float = 1.25,
+                bifurcation_c0: Optional[float] = None) -> DenseResult:
     """Max-cut (two classes, no terminals) of dense instances given as matrices: ``W`` is [n, n] or [B, n, n] (B instances
     of one size, 2 <= n <= ``hip.MAX_GRAPH_NODES``), a tensor on the host or the device or a numpy array, symmetric and
     finite (``ValueError`` otherwise; the diagonal is ignored).  No model and no training: ``candidates`` chains per
@@ -990,12 +1007,22 @@ def solve_dense(W, candidates: int = 200, anneal_sweeps: int = 100, seed: int = 
     move - the form for matrices where :func:`solve`'s sparse decoders walk n entries per visit.  The schedule cools from
     ``t_start`` to ``t_end`` in units of ``sqrt(mean_v sum_u w_vu^2)``, the spread of a local field, where the sparse doors
     use the mean absolute weight.  That unit and the defaults are PROVISIONAL: nobody has measured them (DESIGN.md section
-    40).  For a given start the kernel's outputs are reproducible bit for bit; the random starts are torch's."""
+    40).  For a given start the kernel's outputs are reproducible bit for bit; the random starts are torch's.
+
+    ``bifurcation_steps`` > 0 (keyword only, default 0: nothing new is launched): the chains start from the partitions of
+    that many steps of discrete simulated bifurcation (``gmc_dense_sb_f32``, include/gcnmaxcut_bifurcation.h: all nodes of
+    all chains move at once, a step is an fp32 MFMA product) where they started from torch's random bytes; everything
+    after it is unchanged.  ``bifurcation_dt`` is the time step, ``bifurcation_c0`` the coupling scale (None:
+    ``0.5 / dense_scale(W)``); the start is seeded by ``seed`` on the device.  ``partitions=`` together with
+    ``bifurcation_steps > 0`` raises ``ValueError``.  These defaults are the literature's as far as recalled and
+    PROVISIONAL as well: nobody has measured them on this code."""
+    _check_bifurcation(partitions, bifurcation_steps)
     dev = hip.require_gpu()
     from .Testing import TestingNeuralNetwork as T
     Wd = T.dense_matrices("W", W, dev)
     cost = _dense_cost("node_cost", node_cost, int(Wd.shape[0]), int(Wd.shape[1]), dev)
-    return _solve_dense(Wd, cost, candidates, anneal_sweeps, seed, max_descent_sweeps, t_start, t_end, partitions)
+    return _solve_dense(Wd, cost, candidates, anneal_sweeps, seed, max_descent_sweeps, t_start, t_end, partitions,
+                       bifurcation_steps, bifurcation_dt, bifurcation_c0)
 
 
 def _pair_energy(M: torch.Tensor, lin: torch.Tensor, z: torch.Tensor) -> torch.Tensor:
@@ -1008,7 +1035,8 @@ def _pair_energy(M: torch.Tensor, lin: torch.Tensor, z: torch.Tensor) -> torch.T
 
 def solve_ising_dense(J, field=None, candidates: int = 200, anneal_sweeps: int = 100, seed: int = 0, *,
                       max_descent_sweeps: int = 100, t_start: float = 1.5, t_end: float = 0.15,
-                      partitions=None) -> DenseIsingResult:
+                      partitions=None, bifurcation_steps: int = 0, bifurcation_dt: float = 1.25,
+                      bifurcation_c0: Optional[float] = None) -> DenseIsingResult:
     """Minimises ``H(s) = sum_{i<j} J_ij s_i s_j + sum_i h_i s_i`` over ``s`` in {+1, -1}^n for dense couplings ``J``
     ([n, n] or [B, n, n], symmetric, as :func:`solve_dense` takes ``W``) and ``field`` h ([n] / [B, n]; None: 0) - a
     Sherrington-Kirkpatrick instance, for one.  The mapping is :func:`solve_ising`'s: ``w = 2 J`` (exact in float32),
@@ -1016,6 +1044,7 @@ def solve_ising_dense(J, field=None, candidates: int = 200, anneal_sweeps: int =
     [B, n] int8, ``energy`` [B] float64 - ``H(spins)`` recounted in float64 from ``J`` and ``h``, not derived from the
     kernel's float32 objective - and the :class:`DenseResult` as ``.result``.  The other keywords, and the provisional
     temperature unit, are :func:`solve_dense`'s."""
+    _check_bifurcation(partitions, bifurcation_steps)
     dev = hip.require_gpu()
     from .Testing import TestingNeuralNetwork as T
     Jd = T.dense_matrices("J", J, dev)
@@ -1023,7 +1052,8 @@ def solve_ising_dense(J, field=None, candidates: int = 200, anneal_sweeps: int =
     h = _dense_vector("field", field, B, n, dev)
     h32 = h.to(torch.float32).reshape(B * n)
     cost = torch.stack([h32, -h32], dim=1).contiguous()
-    res = _solve_dense(2.0 * Jd, cost, candidates, anneal_sweeps, seed, max_descent_sweeps, t_start, t_end, partitions)
+    res = _solve_dense(2.0 * Jd, cost, candidates, anneal_sweeps, seed, max_descent_sweeps, t_start, t_end, partitions,
+                       bifurcation_steps, bifurcation_dt, bifurcation_c0)
     spins = (1 - 2 * res.partition).to(torch.int8)
     return DenseIsingResult(spins, _pair_energy(Jd, h, spins), res)
 
@@ -1041,7 +1071,8 @@ def dense_row_sums(w: torch.Tensor) -> torch.Tensor:
 
 def solve_qubo_dense(Q, linear=None, candidates: int = 200, anneal_sweeps: int = 100, seed: int = 0, *,
                      max_descent_sweeps: int = 100, t_start: float = 1.5, t_end: float = 0.15,
-                     partitions=None) -> DenseQuboResult:
+                     partitions=None, bifurcation_steps: int = 0, bifurcation_dt: float = 1.25,
+                     bifurcation_c0: Optional[float] = None) -> DenseQuboResult:
     """Minimises ``E(x) = sum_i a_i x_i + sum_{i<j} q_ij x_i x_j`` over ``x`` in {0, 1}^n for a dense ``Q`` ([n, n] or
     [B, n, n], symmetric, as :func:`solve_dense` takes ``W``; Beasley / BiqMac style) and ``linear`` a ([n] / [B, n]; None:
     0).  The mapping is :func:`solve_qubo`'s and has no offset: ``w = q / 2``, class 1 is ``x = 1``, ``node_cost[i] =
@@ -1049,6 +1080,7 @@ def solve_qubo_dense(Q, linear=None, candidates: int = 200, anneal_sweeps: int =
     per variable; then ``E(x) = -obj``.  Returns ``x`` [B, n] int8, ``energy`` [B] float64 - ``E(x)`` recounted in float64
     from ``Q`` and ``a`` - and the :class:`DenseResult` as ``.result``.  The other keywords, and the provisional
     temperature unit, are :func:`solve_dense`'s."""
+    _check_bifurcation(partitions, bifurcation_steps)
     dev = hip.require_gpu()
     from .Testing import TestingNeuralNetwork as T
     Qd = T.dense_matrices("Q", Q, dev)
@@ -1057,6 +1089,7 @@ def solve_qubo_dense(Q, linear=None, candidates: int = 200, anneal_sweeps: int =
     w = 0.5 * Qd
     cost = torch.zeros((B * n, 2), dtype=torch.float32, device=dev)
     cost[:, 1] = a.to(torch.float32).reshape(B * n) + dense_row_sums(w).reshape(B * n)
-    res = _solve_dense(w, cost, candidates, anneal_sweeps, seed, max_descent_sweeps, t_start, t_end, partitions)
+    res = _solve_dense(w, cost, candidates, anneal_sweeps, seed, max_descent_sweeps, t_start, t_end, partitions,
+                       bifurcation_steps, bifurcation_dt, bifurcation_c0)
     x = res.partition.to(torch.int8)
     return DenseQuboResult(x, _pair_energy(Qd, a, x), res)
